@@ -20,7 +20,12 @@ touches HIP); under `python -m torch.distributed.run --nproc-per-node N bench.py
 scaling); the only collective is the gather of the finished proof bytes (fixed length), an RCCL all_gather.
 `--batch B` is BASELINE config 4: B independent witnesses (seeds 0..B-1), proof i on rank i mod N, gathered on all ranks.
 
-The timed region runs `--regions` times (5 by default: same steps, fresh blinding seeds); `value` and `ms_per_step` are
+A plain run sets up, warms up, times `--steps` proofs once (one region), writes the last timed proof with
+`--dump-outputs DIR` and prints the JSON line. `--full` adds everything beside the headline: 5 regions by default, the
+resident-witness pass and its byte comparison, the roofline, the single-proof latencies, the 2^22 stress (config 5) and
+the CPU baselines.
+
+The timed region runs `--regions` times (same steps, fresh blinding seeds); `value` and `ms_per_step` are
 those of the MEDIAN region and `config.value_samples` lists them all. `config.host_cpu_s_per_proof` is the process's CPU
 time over that region divided by its proofs (all host threads: the per-proof drivers that block on the GPU), and
 `--host-cores N` confines the rank to N cores before anything touches the GPU (one GPU's share of an 8-GPU host).
@@ -30,7 +35,7 @@ context's two device buffers on its copy stream, the next proof's upload under t
 (anon-aadhaar-halo2_amd/feeder.py), the upload for a region's first proofs issued under the previous region's last proofs —
 so every region issues exactly `steps` uploads and the first P witnesses are in HBM when it starts: that is `value`, what
 a caller of create_proof with a freshly synthesized witness gets. The same regions with the witnesses kept resident in HBM
-are config.resident_proofs_per_s (the figure rounds 1-3 called `value`); region 0 of both passes must give the same bytes.
+are config.resident_proofs_per_s (the figure rounds 1-3 called `value`; --full); region 0 of both passes must give the same bytes.
 --no-stream-pass times the resident pass only (profiling).
 """
 import argparse
@@ -75,7 +80,13 @@ def parse_args(argv=None):
     ap.add_argument("--stagger-ms", type=float, default=float(os.environ.get("AMDZK_BENCH_STAGGER_MS", "0")),
                     help="worker w starts its share of a timed region w x this many ms late (inside the timed region): the proofs in flight then sit "
                          "in different phases instead of in step")
-    ap.add_argument("--regions", type=int, default=5, help="how many times the timed region (--steps proofs per GPU) runs; the median is reported")
+    ap.add_argument("--regions", type=int, default=None,
+                    help="how many times the timed region (--steps proofs per GPU) runs; the median is reported (default 1, 5 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: 5 timed regions, the resident-witness pass and its byte comparison, the "
+                         "per-kernel roofline, the single-proof latencies, the 2^22 stress (config 5) and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the proof of the last timed step as DIR/proof.npy (its bytes, float32)")
     ap.add_argument("--host-cores", type=int, default=0,
                     help="confine this rank to the first N cores of its affinity mask (sched_setaffinity before any GPU call); 0 = leave it alone")
     ap.add_argument("--host-wait", default="auto", choices=("auto", "spin", "block"),
@@ -474,8 +485,8 @@ def run_rank(args):
     else:
         witness_seeds = [7 + 1000 * rank + j for j in range(nw)]
     # the CPU baseline and the k = 22 stress belong to the N = 1 line only (rank 0 of N > 1 has 1/N of the host's cores,
-    # and the other ranks would sit in the closing barrier meanwhile)
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline and not stub
+    # and the other ranks would sit in the closing barrier meanwhile); like every figure beside the headline, only with --full
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not stub
     if world > 1:
         args.no_cpu_baseline = args.no_k22 = True
     prover = (StubProver if stub else GpuProver)(args, rank, local_rank, P, witness_seeds, want_cpu)
@@ -516,15 +527,17 @@ def run_rank(args):
     #     region's first proof is issued before the previous region's last proof (a service's steady state), so each region
     #     issues exactly `steps` uploads and the first P witnesses are in HBM when a region starts.
     #   resident (`config.resident_proofs_per_s`, the figure rounds 1-3 called `value`): the witnesses stay in HBM.
-    # Region 0 of both passes uses the same seeds: the proofs must be the same bytes.
+    # Region 0 of both passes uses the same seeds: the proofs must be the same bytes. A plain run times one region of the
+    # pass that gives `value`; the resident pass beside the streamed one, and 5 regions by default, come with --full.
     per_worker = [[j for i, j in enumerate(jobs) if i % P == w] for w in range(P)]
-    R_ = max(1, args.regions)
+    R_ = max(1, args.regions if args.regions is not None else (5 if args.full else 1))
 
     def region_items(reg):
         return [[(wi, seed + 100000 * reg) for wi, seed in per_worker[w]] for w in range(P)]
 
     def run_regions(streamed):
-        regs, first = [], None
+        """(region times, region 0's proofs, the last region's proofs), proofs in step order."""
+        regs, first, last = [], None, None
         if streamed:
             # untimed: both halves of every double buffer touched once, and the pipeline primed with region 0's first witness
             run_pool(P, list(range(P)), lambda _, cx: prover.prove_stream(
@@ -548,27 +561,31 @@ def run_rank(args):
                 pr = run_pool(P, list(range(P)), lambda _, cx: (lag(cx), [prover.prove(cx, wi, seed) for wi, seed in items[cx]])[1])
             barrier()
             regs.append((max_over_ranks(time.perf_counter() - t0), time.process_time() - c0))
+            last = [None] * steps
+            for w in range(P):
+                for q, proof in enumerate(pr[w]):
+                    last[w + q * P] = proof
             if reg == 0:
-                first = [None] * steps
-                for w in range(P):
-                    for q, proof in enumerate(pr[w]):
-                        first[w + q * P] = proof
-        return regs, first
+                first = last
+        return regs, first, last
 
-    stream_equal = None
+    stream_equal = res_regions = None
     streamed_value = not args.no_stream_pass
     if streamed_value:
         prover.stream_setup()
-        regions, proofs = run_regions(True)
-        res_regions, res_proofs = run_regions(False)
-        stream_equal = res_proofs == proofs
-        if not stream_equal:
-            raise SystemExit("bench.py: proofs from streamed witnesses differ from the resident-witness proofs")
+        regions, proofs, last_proofs = run_regions(True)
+        if args.full:
+            res_regions, res_proofs, _ = run_regions(False)
+            stream_equal = res_proofs == proofs
+            if not stream_equal:
+                raise SystemExit("bench.py: proofs from streamed witnesses differ from the resident-witness proofs")
     else:
-        regions, proofs = run_regions(False)
+        regions, proofs, last_proofs = run_regions(False)
         res_regions = regions
     dt, host_cpu_s = sorted(regions)[len(regions) // 2]
-    res_dt = sorted(res_regions)[len(res_regions) // 2][0]
+    res_dt = sorted(res_regions)[len(res_regions) // 2][0] if res_regions else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_proofs[-1])
     gathered_ok = None
     if dist_on:
         # the one exchange step: every rank's proofs (equal length) gathered on all ranks (RCCL all_gather)
@@ -594,7 +611,7 @@ def run_rank(args):
 
     roof = cpu = None
     wall_prof = lat_ms = lat_serial_ms = k22 = None
-    if rank == 0 and not stub:
+    if args.full and rank == 0 and not stub:
         roof, wall_prof = roofline(prover, desc)
         # single-proof latency: one proof alone on the GPU, no per-kernel events (median of 3); then the same with a
         # serial-mode key (one stream), whose proof must be the same bytes
@@ -636,11 +653,11 @@ def run_rank(args):
                                         "stream, double-buffered, the next proof's upload under the current proof; the first %d witnesses "
                                         "are in HBM when a region starts)" % (desc["num_advice"] * prover.n * 32 / 2 ** 20, P)) if streamed_value
                            else "resident witnesses (--no-stream-pass)",
-                           "resident_proofs_per_s": round(world * steps / res_dt, 4),
-                           "resident_samples": [round(world * steps / r[0], 4) for r in res_regions],
-                           "streamed_over_resident": round(res_dt / dt, 4),
+                           "resident_proofs_per_s": round(world * steps / res_dt, 4) if res_regions else None,
+                           "resident_samples": [round(world * steps / r[0], 4) for r in res_regions] if res_regions else None,
+                           "streamed_over_resident": round(res_dt / dt, 4) if res_regions else None,
                            "streamed_equals_resident_bytes": stream_equal,
-                           "timed_regions": len(regions),
+                           "timed_regions": len(regions), "full": args.full,
                            "host_cpu_s_per_proof": round(host_cpu_s / steps, 5), "host_threads": min(P, steps) + 1,
                            "host_cores_allowed": cores_allowed, "host_cgroup_cpu_max": cgroup_cpu_max()[0],
                            "host_cores_usable": usable_cores(cores_allowed),
@@ -991,6 +1008,15 @@ def cpu_baseline(prover, gpu_proof):
             PF.set_threads(None)
     out["proof_bytes_equal_gpu"] = equal
     return out
+
+
+def dump_outputs(out_dir, proof):
+    """--dump-outputs: what a caller of the timed path receives from its last step, the proof bytes, as DIR/proof.npy
+    (float32, one element per byte: exact). Witnesses, SRS and blinding seeds depend on the arguments only, so two builds
+    run with the same arguments must write the same file."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "proof.npy"), np.frombuffer(bytes(proof), dtype=np.uint8).astype(np.float32))
 
 
 def main(argv=None):

@@ -45,8 +45,8 @@ def test_batch_mode_shards_config4_over_ranks():
 
 def test_config4_verbatim_eight_ranks_batch_64():
     """BASELINE config 4's rank and batch count (8 ranks x 8 proofs, gathered on every rank), on CPU with the stub: the
-    launcher, the rendezvous of 8 processes on 127.0.0.1, the barriers around 5 timed regions and the 64-proof gather."""
-    r = run_bench(["--gpus", "8", "--batch", "64", "--warmup", "1", "--concurrency", "2"], {"AMDZK_BENCH_STUB": "1"}, timeout=400)
+    launcher, the rendezvous of 8 processes on 127.0.0.1, the barriers around the 5 timed regions of --full and the 64-proof gather."""
+    r = run_bench(["--gpus", "8", "--batch", "64", "--warmup", "1", "--concurrency", "2", "--full"], {"AMDZK_BENCH_STUB": "1"}, timeout=400)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = json_lines(r.stdout)
     assert len(lines) == 1
@@ -79,6 +79,26 @@ def test_single_rank_needs_no_rendezvous():
     assert r.returncode == 0, r.stderr[-2000:]
     ln = json_lines(r.stdout)[0]
     assert ln["n_gpus"] == 1 and ln["config"]["gather"] is None
+
+
+def test_plain_run_times_steps_once_and_dumps_the_last_proof(tmp_path):
+    """A plain run times --steps proofs in one region and nothing beside the headline (that is --full); --dump-outputs
+    writes the last timed proof's bytes as float32, the same file from run to run with the same arguments."""
+    import numpy as np
+
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ("run%d" % i)
+        r = run_bench(["--steps", "5", "--warmup", "1", "--dump-outputs", str(d)], {"AMDZK_BENCH_STUB": "1"})
+        assert r.returncode == 0, r.stderr[-2000:]
+        ln = json_lines(r.stdout)[0]
+        assert ln["steps"] == 5 and ln["config"]["timed_regions"] == 1 and ln["config"]["full"] is False
+        assert abs(ln["ms_per_step"] - 1e3 / ln["value"]) < 1e-2 * ln["ms_per_step"]
+        assert ln["config"]["resident_proofs_per_s"] is None and ln["roofline"] is None and ln["cpu_baseline"] is None
+        a = np.load(d / "proof.npy")
+        assert a.dtype == np.float32 and a.shape == (96,) and a.min() >= 0 and a.max() <= 255
+        dumps.append(a)
+    assert np.array_equal(dumps[0], dumps[1])
 
 
 def test_launcher_does_not_import_torch_or_load_the_library():

@@ -19,7 +19,7 @@ def test_two_ranks_on_one_gpu_batch_mode():
         env.pop(k, None)
     env.update({"AMDZK_BENCH_FORCE_DEVICE": "0", "AMDZK_BENCH_BACKEND": "gloo"})
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "8", "--shape", "k15", "--warmup", "1",
-                        "--concurrency", "2", "--no-cpu-baseline", "--no-k22", "--regions", "2"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+                        "--concurrency", "2", "--full", "--no-cpu-baseline", "--no-k22", "--regions", "2"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -40,7 +40,7 @@ def test_one_rank_rccl_collectives():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "AMDZK_BENCH_BACKEND", "AMDZK_BENCH_FORCE_DEVICE"):
         env.pop(k, None)
     env["AMDZK_BENCH_DIST_SELF"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--shape", "k15", "--warmup", "1", "--concurrency", "4",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--shape", "k15", "--warmup", "1", "--concurrency", "4", "--full",
                         "--regions", "2", "--no-cpu-baseline", "--no-k22", "--no-serial-latency"], env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -28,7 +28,7 @@ P1=$!
 probe_smi > $OUT/smi.log 2>/dev/null &
 P2=$!
 trap 'kill $P1 $P2 2>/dev/null' EXIT
-AMDZK_BENCH_TRACE=$OUT/trace.json timeout -k 10 400 python bench.py --steps 160 --concurrency 8 --regions 10 --warmup 2 --no-cpu-baseline --no-k22 --no-serial-latency > $OUT/bench.json 2> $OUT/bench.err || { echo bench failed; tail -3 $OUT/bench.err; exit 1; }
+AMDZK_BENCH_TRACE=$OUT/trace.json timeout -k 10 400 python bench.py --steps 160 --concurrency 8 --full --regions 10 --warmup 2 --no-cpu-baseline --no-k22 --no-serial-latency > $OUT/bench.json 2> $OUT/bench.err || { echo bench failed; tail -3 $OUT/bench.err; exit 1; }
 kill $P1 $P2 2>/dev/null
 python - <<'PY'
 import json

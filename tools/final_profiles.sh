@@ -5,7 +5,7 @@
 #      tools/summarize_prof.py <tag>: kernel stats, PMC summary, steady-state proof, instruction counts
 #   2. the single-proof timeline on lanes (tools/timeline_single_proof.py)
 #   3. tools/profile_k22.sh -> tools/summarize_k22.py (BASELINE config 5)
-#   4. the default bench line (python bench.py --steps 20 --warmup 5), read AFTER the summaries exist so that its roofline
+#   4. the full bench line (python bench.py --steps 20 --warmup 5 --full), read AFTER the summaries exist so that its roofline
 #      carries this build's PMC counters
 # Usage: bash tools/final_profiles.sh <tag>      e.g. r04z
 set -o pipefail
@@ -19,7 +19,7 @@ python tools/summarize_prof.py gpurun_out/prof "$TAG" > "$OUT/summarize.log" 2>&
 cp profiles/${TAG}_* "$OUT"/
 rm -rf gpurun_out/prof
 echo "1/4 rocprofv3 passes summarised" >> "$OUT/progress.log"
-CMD="python3 $ROOT/bench.py --steps 1 --warmup 1 --concurrency 1 --regions 1 --no-cpu-baseline --no-stream-pass --no-serial-latency --no-k22"
+CMD="python3 $ROOT/bench.py --steps 1 --warmup 1 --concurrency 1 --full --regions 1 --no-cpu-baseline --no-stream-pass --no-serial-latency --no-k22"
 (cd /tmp && rocprofv3 --kernel-trace -d "$OUT/tl" -o run -- $CMD > "$OUT/tl.json" 2> "$OUT/tl.err") || { echo "timeline trace failed"; tail -3 "$OUT/tl.err"; exit 1; }
 python tools/timeline_single_proof.py "$OUT/tl" -v > "$OUT/${TAG}_timeline_single_proof.txt" 2>> "$OUT/tl.err" || { echo "timeline failed"; exit 1; }
 rm -rf "$OUT/tl"
@@ -29,6 +29,6 @@ python tools/summarize_k22.py gpurun_out/prof_k22 "$OUT/${TAG}_k22_kernel_summar
 cp gpurun_out/prof_k22/stats.json "$OUT/${TAG}_k22_stress_profiled_run.json"
 rm -rf gpurun_out/prof_k22
 echo "3/4 k22" >> "$OUT/progress.log"
-timeout -k 10 500 python bench.py --steps 20 --warmup 5 > "$OUT/${TAG}_bench_default.json" 2> "$OUT/bench_default.err" || { echo "bench failed"; tail -5 "$OUT/bench_default.err"; exit 1; }
+timeout -k 10 500 python bench.py --steps 20 --warmup 5 --full > "$OUT/${TAG}_bench_default.json" 2> "$OUT/bench_default.err" || { echo "bench failed"; tail -5 "$OUT/bench_default.err"; exit 1; }
 python tools/show_bench.py "$OUT/${TAG}_bench_default.json" 2>/dev/null | head -12
 echo "4/4 bench" >> "$OUT/progress.log"

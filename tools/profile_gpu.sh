@@ -15,7 +15,7 @@ rm -rf "$OUT"; mkdir -p "$OUT"
 # AMDZK_SERIAL=1: every key keeps one proof on one stream, so no two kernels of the trace overlap and a kernel's duration
 # is its own (the default keys spread a proof over three streams: tools/timeline_single_proof.py looks at those)
 export AMDZK_SERIAL=1
-CMD="python3 $ROOT/bench.py --steps 1 --warmup 1 --concurrency 1 --regions 1 --no-cpu-baseline --no-stream-pass --no-serial-latency --no-k22"
+CMD="python3 $ROOT/bench.py --steps 1 --warmup 1 --concurrency 1 --full --regions 1 --no-cpu-baseline --no-stream-pass --no-serial-latency --no-k22"
 cd /tmp
 rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o run -- $CMD > "$OUT/stats.json" 2> "$OUT/stats.err" && echo "stats ok" &&
 rocprofv3 --pmc FETCH_SIZE -d "$OUT/fetch" -o run -- $CMD > "$OUT/fetch.json" 2> "$OUT/fetch.err" && echo "fetch ok" &&

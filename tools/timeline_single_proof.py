@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """One proof alone on the GPU, kernel by kernel: reads the rocpd database of
-  rocprofv3 --kernel-trace -d <dir> -o run -- python3 bench.py --steps 1 --warmup 1 --concurrency 1 --regions 1 \
+  rocprofv3 --kernel-trace -d <dir> -o run -- python3 bench.py --steps 1 --warmup 1 --concurrency 1 --full --regions 1 \
       --no-cpu-baseline --no-stream-pass --no-serial-latency --no-k22
 takes the LAST whole proof made with the default (lanes) key — the interval between the starts of the last two
 random-polynomial kernels, the first kernel of every proof — and reports
