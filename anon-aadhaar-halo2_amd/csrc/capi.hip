@@ -163,12 +163,8 @@ int zk_stream_after_l1(amdzk_ctx* waiter, amdzk_ctx* signaler) {
 int zk_sync_all(amdzk_ctx* ctx) {
   amdzk_ctx* root = ctx->parent ? ctx->parent : ctx;
   ZK_HIP(ctx, zk_host_wait(root, root->stream));
-  if (root->msm_stream) ZK_HIP(ctx, zk_host_wait(root, root->msm_stream));
   for (amdzk_ctx* l : root->lanes)
-    if (l) {
-      ZK_HIP(ctx, zk_host_wait(l, l->stream));
-      if (l->msm_stream) ZK_HIP(ctx, zk_host_wait(l, l->msm_stream));
-    }
+    if (l) ZK_HIP(ctx, zk_host_wait(l, l->stream));
   return AMDZK_OK;
 }
 
@@ -182,13 +178,7 @@ static void ctx_release(amdzk_ctx* ctx) {
   for (auto e : ctx->evt_pool) hipEventDestroy(e);
   for (auto e : ctx->order_evt)
     if (e) hipEventDestroy(e);
-  for (auto e : ctx->msm_evt)
-    if (e) hipEventDestroy(e);
   if (ctx->msm_l1_evt) hipEventDestroy(ctx->msm_l1_evt);
-  if (ctx->msm_stream) {
-    zk_host_wait(ctx, ctx->msm_stream);
-    hipStreamDestroy(ctx->msm_stream);
-  }
   if (ctx->t0) hipEventDestroy(ctx->t0);
   if (ctx->t1) hipEventDestroy(ctx->t1);
   if (ctx->copy_stream) {

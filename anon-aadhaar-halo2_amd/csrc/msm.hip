@@ -376,150 +376,6 @@ __global__ __launch_bounds__(MSM_THREADS) void msm_accum_seg_kernel(AccArgs a) {
   st_x29(out + off_out[b] + (t - off_in[b] / a.T), acc);
 }
 
-// Level 1 as a PERSISTENT grid (AMDZK_L1_LDS=9; round-4 experiment, profiles/r04b_*): a fixed number of workgroups, each
-// fetching (column, block) items from an atomic counter — items are numbered block-major, so the blocks that hold entries
-// come first whatever the column — instead of one workgroup per 256 * T entries of CAPACITY: the grid of the generic
-// kernel is sized on len * W entries per column, and a witness column (5-6 non-zero digits per scalar of 20) leaves 70 %
-// of its workgroups with nothing to do. Same arithmetic, same slots, same results.
-__global__ __launch_bounds__(MSM_THREADS) void msm_accum_l1_persist_kernel(AccArgs a, uint32_t* counter, uint32_t blocks_x, uint32_t ncols) {
-  __shared__ uint32_t s_item;
-  for (;;) {
-    if (threadIdx.x == 0) s_item = atomicAdd(counter, 1u);
-    __syncthreads();
-    const uint32_t item = s_item;
-    __syncthreads();
-    if (item >= blocks_x * ncols) return;
-    const uint32_t col = item % ncols, bx = item / ncols;
-    const uint32_t t = bx * blockDim.x + threadIdx.x;
-    const uint32_t* off_in = a.off_in + (size_t)col * (a.nb + 1);
-    const uint32_t* off_out = a.off_out + (size_t)col * (a.nb + 1);
-    const uint32_t total = off_in[a.nb];
-    const uint32_t start = t * a.T;
-    if (start >= total) continue;
-    const uint32_t end = min(start + a.T, total);
-    uint32_t lo = 0, hi = a.nb;
-    while (hi - lo > 1) {
-      uint32_t mid = (lo + hi) >> 1;
-      if (off_in[mid] <= start) lo = mid; else hi = mid;
-    }
-    uint32_t b = lo, b_end = off_in[b + 1];
-    const uint32_t* ent = a.entries + (size_t)col * a.ecap;
-    G1X29* out = a.out_list + (size_t)col * a.out_cap;
-    G1X29 acc = G1X29::inf();
-    for (uint32_t e = start; e < end; e++) {
-      if (e >= b_end) {
-        st_x29(out + off_out[b] + (t - off_in[b] / a.T), acc);
-        acc = G1X29::inf();
-        do {
-          b++;
-          b_end = off_in[b + 1];
-        } while (e >= b_end);
-      }
-      const uint32_t id = ent[e];
-      G1Affine p = ld_aff(a.table + (id & 0x7fffffffu));
-      const bool p_inf = p.is_inf();
-      if (id >> 31) p.y = neg(p.y);
-      acc = x29_add_affine(acc, fq29_unpack(p.x), fq29_unpack(p.y), p_inf);
-    }
-    st_x29(out + off_out[b] + (t - off_in[b] / a.T), acc);
-  }
-}
-
-// Level 1 with the XYZZ accumulator in LDS (AMDZK_L1_LDS=1; round-4 experiment, profiles/r04b_*): the generic kernel above
-// keeps 36 accumulator limbs + 18 limbs of the table point + the temporaries of the addition in registers — 152 VGPRs,
-// three wavefronts per SIMD. Here the accumulator lives in LDS as [word][thread] (conflict-free 32-bit accesses, 36 KiB
-// per 256-thread workgroup, four workgroups per compute unit) and each coordinate is read where the formula needs it
-// and written back when its new value exists: 12 coordinate moves (108 LDS words) per 2,160-instruction addition.
-constexpr int L1L_THREADS = 256;
-struct LdsAcc {
-  uint32_t* base;  // &lds[threadIdx.x]; word w of this thread's accumulator at base[w * L1L_THREADS]
-  __device__ __forceinline__ Fq29 ld(int f) const {
-    Fq29 r;
-#pragma unroll
-    for (int i = 0; i < 9; i++) r.l[i] = base[(f * 9 + i) * L1L_THREADS];
-    return r;
-  }
-  __device__ __forceinline__ void st(int f, const Fq29& v) const {
-#pragma unroll
-    for (int i = 0; i < 9; i++) base[(f * 9 + i) * L1L_THREADS] = v.l[i];
-  }
-  __device__ __forceinline__ G1X29 all() const {
-    G1X29 r;
-    r.x = ld(0); r.y = ld(1); r.zz = ld(2); r.zzz = ld(3);
-    return r;
-  }
-};
-template <int WAVES>
-__global__ __launch_bounds__(L1L_THREADS, WAVES) void msm_accum_l1_lds_kernel(AccArgs a) {
-  __shared__ uint32_t lds[36 * L1L_THREADS];
-  const uint32_t col = blockIdx.y;
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t* off_in = a.off_in + (size_t)col * (a.nb + 1);
-  const uint32_t* off_out = a.off_out + (size_t)col * (a.nb + 1);
-  const uint32_t total = off_in[a.nb];
-  const uint32_t start = t * a.T;
-  if (start >= total) return;
-  const uint32_t end = min(start + a.T, total);
-  uint32_t lo = 0, hi = a.nb;
-  while (hi - lo > 1) {
-    uint32_t mid = (lo + hi) >> 1;
-    if (off_in[mid] <= start) lo = mid; else hi = mid;
-  }
-  uint32_t b = lo, b_end = off_in[b + 1];
-  const uint32_t* ent = a.entries + (size_t)col * a.ecap;
-  G1X29* out = a.out_list + (size_t)col * a.out_cap;
-  const LdsAcc A{lds + threadIdx.x};
-  bool acc_inf = true;
-  for (uint32_t e = start; e < end; e++) {
-    if (e >= b_end) {
-      st_x29(out + off_out[b] + (t - off_in[b] / a.T), acc_inf ? G1X29::inf() : A.all());
-      acc_inf = true;
-      do {
-        b++;
-        b_end = off_in[b + 1];
-      } while (e >= b_end);
-    }
-    const uint32_t id = ent[e];
-    G1Affine p = ld_aff(a.table + (id & 0x7fffffffu));
-    if (p.is_inf()) continue;
-    if (id >> 31) p.y = neg(p.y);
-    const Fq29 qx = fq29_unpack(p.x), qy = fq29_unpack(p.y);
-    if (acc_inf) {
-      A.st(0, qx);
-      A.st(1, qy);
-      A.st(2, f29_one<Fq29P>());
-      A.st(3, f29_one<Fq29P>());
-      acc_inf = false;
-      continue;
-    }
-    const Fq29 u2 = f29_mul(qx, A.ld(2));
-    const Fq29 s2 = f29_mul(qy, A.ld(3));
-    const Fq29 pd = f29_sub10(u2, A.ld(0));
-    const Fq29 r = f29_sub6(s2, A.ld(1));
-    const Fq29 pp = f29_sqr(pd);
-    const Fq29 rr = f29_sqr(r);
-    if (f29_is_zero_mod_p(pp)) {
-      if (f29_is_zero_mod_p(rr)) {
-        const G1X29 d = x29_dbl_affine(qx, qy);
-        A.st(0, d.x); A.st(1, d.y); A.st(2, d.zz); A.st(3, d.zzz);
-      } else {
-        acc_inf = true;
-      }
-      continue;
-    }
-    const Fq29 ppp = f29_mul(pd, pp);
-    const Fq29 q = f29_mul(A.ld(0), pp);
-    const Fq29 s = f29_add(ppp, f29_add_lazy(q, q));
-    const Fq29 ox = f29_sub7(rr, s);
-    A.st(0, ox);
-    const Fq29 tq = f29_sub10_lazy(q, ox);
-    A.st(1, f29_mul2(r, tq, f29_neg6(A.ld(1)), ppp));
-    A.st(2, f29_mul(A.ld(2), pp));
-    A.st(3, f29_mul(A.ld(3), ppp));
-  }
-  st_x29(out + off_out[b] + (t - off_in[b] / a.T), acc_inf ? G1X29::inf() : A.all());
-}
-
 // ------------------------------------------------------------------ wavefront reductions
 __device__ __forceinline__ G1X29 shfl_xor_x29(const G1X29& v, int m) {
   G1X29 r;
@@ -1391,28 +1247,28 @@ void zk_srs_free(amdzk_ctx*, amdzk_srs* s) {
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-// One group of columns of a batch: counting sort, level-1 accumulation, folds, bucket reduction — every launch on
-// ctx->stream (the caller may have pointed it at the ctx's second MSM stream). The level-1 kernel fills the chip; what
-// precedes it (the sort) and what follows it (folds, per-bucket sums, the row/column reduction: few wavefronts,
-// latency-bound) does not. `l1_after` / `l1_done`: the level-1 launch waits for the previous group's and signals its
-// own end, so that group g's tail and group g + 2's sort run UNDER group g + 1's level-1 kernel (zk_msm_dev_xyzz).
+// Geometry of one batch (msm_group): counting sort, level-1 accumulation, folds, bucket reduction.
 struct MsmGeom {
   uint32_t c, W, nb, T1, TL, chunk, nblk;
-  int nlev;  // accumulation levels in front of the per-bucket final: 2 (level 1 + one fold) or 3
   bool latency;  // latency mode for this batch: amdzk_ctx::msm_latency_mode and a batch of a few columns
   bool big_digits;  // counting sort with 1024-thread workgroups, up to 256 of them per column
   size_t ecap, cap[4], G;
-  size_t o_bh, o_cnt, o_off[4], o_ent, o_list[4], o_dense, o_rows, o_cols, o_ctr, bytes;
+  size_t o_bh, o_cnt, o_off[4], o_ent, o_list[4], o_dense, o_rows, o_cols, bytes;
 };
-static constexpr int MSM_NLEV = 3;  // at most: level 1 + two folding levels, then the per-bucket final (MsmGeom::nlev of them are used)
+// Accumulation levels in front of the per-bucket final: level 1 + two folding levels. ONE fold (with TL = max(6, partial
+// sums per bucket / 4)) was measured in round 4 and is a trap: the AVERAGE bucket of a proof-sized MSM then reaches the
+// final kernel with ~5 partial sums, but witness columns are skewed — a few hundred buckets per column hold hundreds — and
+// every such bucket takes the whole wavefront of its 64 neighbours through the cooperative path: msm_accum_final
+// 0.76 -> 8.9 ms per proof, 79.6 -> 72 proofs/s (profiles/r04d_one_fold_level_ab.txt).
+static constexpr int MSM_NLEV = 3;
 
-static MsmGeom msm_geometry(const amdzk_srs* srs, size_t ncols, size_t len, size_t ncols_for_task_size, bool latency_mode) {
+static MsmGeom msm_geometry(const amdzk_srs* srs, size_t ncols, size_t len, bool latency_mode) {
   MsmGeom g;
   // latency mode applies to batches of a few columns only (the h pieces, the multiopen argument's two, the random polynomial:
   // the chip is empty behind them); the bucket reduction of a 141-column batch is 2,000 wavefronts and throughput-bound —
   // spending 4 lanes per addition there made a lone proof 0.4 ms SLOWER (profiles/r04h_*)
   static const size_t latency_cols = getenv("AMDZK_LATENCY_COLS") && atoi(getenv("AMDZK_LATENCY_COLS")) > 0 ? (size_t)atoi(getenv("AMDZK_LATENCY_COLS")) : 8;
-  g.latency = latency_mode && ncols_for_task_size <= latency_cols;
+  g.latency = latency_mode && ncols <= latency_cols;
   g.c = srs->c;
   g.W = srs->W;
   g.nb = 1u << (g.c - 1);
@@ -1423,7 +1279,7 @@ static MsmGeom msm_geometry(const amdzk_srs* srs, size_t ncols, size_t len, size
   // 5.8 / 5.7 / 6.5 / 7.1 / 7.8 ms per proof in level 1 against 2.4 / 2.1 / 1.9 / 1.6 / 1.6 in the folds — a task of 32
   // additions leaves the last of its few thousand wavefronts running alone — and 76.9 against 76.0 proofs/s for
   // 12 against 16 with ten proofs in flight). e_total is a capacity: zero digits never become entries.
-  const size_t e_total = g.ecap * ncols_for_task_size;
+  const size_t e_total = g.ecap * ncols;
   g.T1 = 4;
   if (e_total > (size_t)4 * 262144) g.T1 = 8;
   if (e_total > (size_t)8 * 262144) g.T1 = 12;
@@ -1447,19 +1303,6 @@ static MsmGeom msm_geometry(const amdzk_srs* srs, size_t ncols, size_t len, size
       while (g.TL < 16 && fullest / g.T1 / ((double)g.TL * g.TL) > 4.5) g.TL++;
   }
   if (const char* e = getenv("AMDZK_MSM_TL")) g.TL = (uint32_t)atoi(e) > 1 ? (uint32_t)atoi(e) : g.TL;
-  // Folding levels: two (TL = 6) in front of the per-bucket final. ONE fold (AMDZK_MSM_NLEV=2, with TL = max(6, partial
-  // sums per bucket / 4)) was measured in round 4 and is a trap: the AVERAGE bucket of a proof-sized MSM then reaches the
-  // final kernel with ~5 partial sums, but witness columns are skewed — a few hundred buckets per column hold hundreds — and
-  // every such bucket takes the whole wavefront of its 64 neighbours through the cooperative path: msm_accum_final
-  // 0.76 -> 8.9 ms per proof, 79.6 -> 72 proofs/s (profiles/r04d_one_fold_level_ab.txt).
-  g.nlev = MSM_NLEV;
-  if (const char* e = getenv("AMDZK_MSM_NLEV")) {
-    if (atoi(e) == 2) {
-      const double per_bucket = (double)len * g.W / g.nb / g.T1;
-      g.nlev = 2;
-      if (!getenv("AMDZK_MSM_TL")) g.TL = std::max<uint32_t>(6, (uint32_t)((per_bucket + 3.0) / 4.0));
-    }
-  }
   g.cap[0] = g.ecap;
   g.cap[1] = g.ecap / g.T1 + g.nb + 1;
   for (int l = 2; l <= MSM_NLEV; l++) g.cap[l] = g.cap[l - 1] / g.TL + g.nb + 1;
@@ -1483,13 +1326,12 @@ static MsmGeom msm_geometry(const amdzk_srs* srs, size_t ncols, size_t len, size
   g.G = g.nb >> 6;
   g.o_rows = take(ncols * g.G * sizeof(G1X29));
   g.o_cols = take(ncols * ((g.G + 63) / 64) * 64 * sizeof(G1X29));
-  g.o_ctr = take(256);
   g.bytes = o;
   return g;
 }
 
 static int msm_group(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const MsmGeom& g, char* ws, const Fr* d_scalars, size_t ncols, size_t len,
-                     size_t col_stride, G1X* outp, hipEvent_t l1_after, hipEvent_t l1_done) {
+                     size_t col_stride, G1X* outp, hipEvent_t l1_done) {
   const uint32_t nb = g.nb;
   uint32_t* blk_hist = (uint32_t*)(ws + g.o_bh);
   uint32_t* cnt = (uint32_t*)(ws + g.o_cnt);
@@ -1517,18 +1359,13 @@ static int msm_group(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const MsmG
   static const int tail_quad = getenv("AMDZK_TAIL_QUAD") ? atoi(getenv("AMDZK_TAIL_QUAD")) : -1;
   const bool quad_on = (tail_quad < 0 ? g.latency : tail_quad != 0) && ncols <= 65535;
   const size_t scan_shmem = (16 + (nb + 1 <= SCAN_LDS_WORDS ? (size_t)nb + 1 : 0)) * sizeof(uint32_t);
-  if (scan_shmem > 65536) {
-    static bool scan_attr_set = false;  // per process: the attribute belongs to the function, not to the context
-    if (!scan_attr_set) {
-      ZK_HIP(ctx, hipFuncSetAttribute((const void*)msm_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((16 + SCAN_LDS_WORDS) * sizeof(uint32_t))));
-      scan_attr_set = true;
-    }
-  }
+  if (scan_shmem > 65536)
+    ZK_HIP(ctx, hipFuncSetAttribute((const void*)msm_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((16 + SCAN_LDS_WORDS) * sizeof(uint32_t))));
   ZK_TRY(launch_digits<false>(ctx, g.c, da, dgrid, g.big_digits));
   ZK_LAUNCH(ctx, "msm_blk_offsets", msm_blk_offsets_kernel, dim3((nb + 255) / 256, (unsigned)ncols), dim3(256), 0, blk_hist, cnt, nb, g.nblk);
   ZK_LAUNCH(ctx, "msm_scan", msm_scan_kernel, dim3((unsigned)ncols), dim3(1024), scan_shmem, cnt, off[0], nb, 1u, 1);
   ZK_TRY(launch_digits<true>(ctx, g.c, da, dgrid, g.big_digits));
-  for (int l = 1; l <= g.nlev; l++) {
+  for (int l = 1; l <= MSM_NLEV; l++) {
     const uint32_t T = l == 1 ? g.T1 : g.TL;
     ZK_LAUNCH(ctx, "msm_scan", msm_scan_kernel, dim3((unsigned)ncols), dim3(1024), scan_shmem, off[l - 1], off[l], nb, T, 2);
     AccArgs a;
@@ -1546,17 +1383,8 @@ static int msm_group(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const MsmG
     const size_t threads = (g.cap[l - 1] + T - 1) / T;
     dim3 grid((unsigned)((threads + MSM_THREADS - 1) / MSM_THREADS), (unsigned)ncols);
     if (l == 1) {
-      if (l1_after) ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, l1_after, 0));
-      static const int l1_lds = getenv("AMDZK_L1_LDS") ? atoi(getenv("AMDZK_L1_LDS")) : 0;
-      if (l1_lds == 9) {
-        uint32_t* ctr = (uint32_t*)(ws + g.o_ctr);
-        ZK_HIP(ctx, hipMemsetAsync(ctr, 0, sizeof(uint32_t), ctx->stream));
-        const unsigned persist = (unsigned)std::min<size_t>((size_t)grid.x * ncols, (size_t)ctx->num_cu * 3);
-        ZK_LAUNCH(ctx, "msm_accum_l1", msm_accum_l1_persist_kernel, dim3(persist), dim3(MSM_THREADS), 0, a, ctr, grid.x, (uint32_t)ncols);
-      } else if (l1_lds == 4) ZK_LAUNCH(ctx, "msm_accum_l1", msm_accum_l1_lds_kernel<4>, grid, dim3(L1L_THREADS), 0, a);
-      else if (l1_lds == 3) ZK_LAUNCH(ctx, "msm_accum_l1", msm_accum_l1_lds_kernel<3>, grid, dim3(L1L_THREADS), 0, a);
-      else ZK_LAUNCH(ctx, "msm_accum_l1", msm_accum_seg_kernel<true>, grid, dim3(MSM_THREADS), 0, a);
-      if (l1_done) ZK_HIP(ctx, hipEventRecord(l1_done, ctx->stream));
+      ZK_LAUNCH(ctx, "msm_accum_l1", msm_accum_seg_kernel<true>, grid, dim3(MSM_THREADS), 0, a);
+      ZK_HIP(ctx, hipEventRecord(l1_done, ctx->stream));
     } else if (quad_on && !(getenv("AMDZK_FOLD_QUAD") && atoi(getenv("AMDZK_FOLD_QUAD")) == 0)) {
       const dim3 qgrid((unsigned)((4 * threads + MSM_THREADS - 1) / MSM_THREADS), (unsigned)ncols);
       ZK_LAUNCH(ctx, "msm_accum_fold", msm_accum_fold_quad_kernel, qgrid, dim3(MSM_THREADS), 0, a);
@@ -1565,8 +1393,8 @@ static int msm_group(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const MsmG
     }
   }
   const unsigned fold_w = (unsigned)((g.G + 63) / 64);  // 1, 2, 4 or 8 (c <= 16): at most 9 wavefronts per workgroup (launch bound 576)
-  ZK_LAUNCH(ctx, "msm_accum_final", msm_accum_final_kernel, dim3(nb / 64, (unsigned)ncols), dim3(64), 0, off[g.nlev], nb, list[g.nlev],
-            g.cap[g.nlev], dense);
+  ZK_LAUNCH(ctx, "msm_accum_final", msm_accum_final_kernel, dim3(nb / 64, (unsigned)ncols), dim3(64), 0, off[MSM_NLEV], nb, list[MSM_NLEV],
+            g.cap[MSM_NLEV], dense);
   static const int tail_tree = getenv("AMDZK_TAIL_TREE") ? atoi(getenv("AMDZK_TAIL_TREE")) : -1;  // -1: in latency mode; 0 / 1: never / always
   const bool quad = quad_on && fold_w == 1;
   if (quad)
@@ -1581,58 +1409,22 @@ static int msm_group(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const MsmG
   return AMDZK_OK;
 }
 
-// ncols MSMs of length len over srs->table[basis]; results (XYZZ) land in d_out[ncols].
-// With ctx->msm_pipeline (an experiment: create_proof sets it under AMDZK_MSM_PIPELINE=1) a batch of many columns is cut
-// into groups that alternate between the ctx's stream and a second stream of its own, level-1 kernels chained, so that
-// a group's latency-bound tail and sort could hide under the next group's level-1 kernel (see msm_group). It does not
-// pay on this chip — the small kernels then queue for workgroup slots behind the chip-filling one — and is off by
-// default: one group, one stream.
+// ncols MSMs of length len over srs->table[basis]; results (XYZZ) land in d_out[ncols]. ctx->msm_l1_evt is recorded
+// when the level-1 kernel ends (zk_stream_after_l1).
 int zk_msm_dev_xyzz(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const Fr* d_scalars, size_t ncols,
                     size_t len, size_t col_stride, G1X** d_out) {
   if (!srs || basis < 0 || basis > 1 || !srs->table[basis]) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm: basis %d not uploaded", basis);
   if (len > srs->n) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm: len %zu > 2^k = %zu", len, srs->n);
   if (ncols == 0 || ncols > 65535) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm: ncols %zu out of range", ncols);
   if ((uint64_t)srs->W * srs->n >= (1ull << 31)) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "msm: table too large for 31-bit ids");
-  // groups: at least AMDZK_MSM_GROUP_COLS columns each (default 16), at most 6
-  size_t ngroups = 1;
-  if (ctx->msm_pipeline && !ctx->prof) {
-    size_t per = 16;
-    if (const char* e = getenv("AMDZK_MSM_GROUP_COLS")) per = atoi(e) > 0 ? (size_t)atoi(e) : per;
-    ngroups = std::min<size_t>(std::max<size_t>(ncols / per, 1), 6);
-  }
-  const size_t gcols = (ncols + ngroups - 1) / ngroups;
-  ngroups = (ncols + gcols - 1) / gcols;
-  const MsmGeom g = msm_geometry(srs, gcols, len, ncols, ctx->msm_latency_mode);  // task sizes as for the whole batch
-  const size_t o_out = align_up(ngroups * g.bytes, 256);
+  const MsmGeom g = msm_geometry(srs, ncols, len, ctx->msm_latency_mode);
+  const size_t o_out = align_up(g.bytes, 256);
   char* ws = nullptr;
   ZK_TRY(zk_ws_reserve(ctx, 1, o_out + align_up(ncols * sizeof(G1X), 256), (void**)&ws));
   G1X* outp = (G1X*)(ws + o_out);
   if (!ctx->msm_l1_evt) ZK_HIP(ctx, hipEventCreateWithFlags(&ctx->msm_l1_evt, hipEventDisableTiming));
-  if (ngroups == 1) {
-    ZK_TRY(msm_group(ctx, srs, basis, g, ws, d_scalars, ncols, len, col_stride, outp, nullptr, ctx->msm_l1_evt));
-    ctx->msm_l1_fresh = true;
-    *d_out = outp;
-    return AMDZK_OK;
-  }
-  if (!ctx->msm_stream) ZK_HIP(ctx, zk_stream_create(&ctx->msm_stream, ctx->parent != nullptr));
-  for (hipEvent_t& e : ctx->msm_evt)
-    if (!e) ZK_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  hipStream_t main_stream = ctx->stream;
-  // the scalars were produced on the ctx's stream: the second stream starts after them
-  ZK_HIP(ctx, hipEventRecord(ctx->msm_evt[6], main_stream));
-  ZK_HIP(ctx, hipStreamWaitEvent(ctx->msm_stream, ctx->msm_evt[6], 0));
-  int rc = AMDZK_OK;
-  for (size_t gi = 0; gi < ngroups && rc == AMDZK_OK; gi++) {
-    const size_t first = gi * gcols, m = std::min(gcols, ncols - first);
-    ctx->stream = (gi & 1) ? ctx->msm_stream : main_stream;
-    rc = msm_group(ctx, srs, basis, g, ws + gi * g.bytes, d_scalars + first * col_stride, m, len, col_stride, outp + first,
-                   gi ? ctx->msm_evt[gi - 1] : nullptr, gi + 1 < ngroups ? ctx->msm_evt[gi] : ctx->msm_l1_evt);
-  }
-  ctx->stream = main_stream;
-  ZK_TRY(rc);
+  ZK_TRY(msm_group(ctx, srs, basis, g, ws, d_scalars, ncols, len, col_stride, outp, ctx->msm_l1_evt));
   ctx->msm_l1_fresh = true;
-  ZK_HIP(ctx, hipEventRecord(ctx->msm_evt[7], ctx->msm_stream));
-  ZK_HIP(ctx, hipStreamWaitEvent(main_stream, ctx->msm_evt[7], 0));
   *d_out = outp;
   return AMDZK_OK;
 }

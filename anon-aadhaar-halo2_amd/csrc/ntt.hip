@@ -345,17 +345,15 @@ struct Plan {
   uint32_t s[3];
 };
 
-uint32_t env_u32(const char* name, uint32_t dflt) {
-  const char* v = getenv(name);
-  return v ? (uint32_t)atoi(v) : dflt;
-}
+// Elements per LDS tile: 2^8...2^11 were measured at 2^15...2^22.
+constexpr uint32_t NTT_TILE_LOG = 10;
 
-Plan make_plan(uint32_t log_n, uint32_t tile_log) {
-  // Keep at least 4 elements (128 contiguous bytes) per global run: s <= tile_log - 2
-  // (AMDZK_NTT_SMAX_SLACK=1 allows 2-element runs when that saves a whole step).
-  uint32_t smax = tile_log - 2 + env_u32("AMDZK_NTT_SMAX_SLACK", 1);
+Plan make_plan(uint32_t log_n) {
+  // At least 2 elements (64 contiguous bytes) per global run: s <= NTT_TILE_LOG - 1. Runs of 4 (s <= NTT_TILE_LOG - 2)
+  // would cost a whole step at some sizes.
+  const uint32_t smax = NTT_TILE_LOG - 1;
   Plan p;
-  if (log_n <= tile_log) {  // whole column in one tile
+  if (log_n <= NTT_TILE_LOG) {  // whole column in one tile
     p.npass = 1;
     p.s[0] = log_n;
     p.s[1] = p.s[2] = 0;
@@ -390,8 +388,7 @@ int zk_ntt_ex(amdzk_ctx* ctx, const Fr* d_in, size_t in_stride, Fr* d_out, size_
   if (ncols > 65535) ZK_FAIL(ctx, AMDZK_E_INVALID, "ntt: more than 65535 columns in one call");
   Fr* tw = nullptr;
   ZK_TRY(get_twiddles(ctx, log_n, omega, &tw));
-  const uint32_t tile_log = env_u32("AMDZK_NTT_TILE_LOG", 10);
-  Plan plan = make_plan(log_n, tile_log);
+  Plan plan = make_plan(log_n);
 
   const uint32_t nz = tabs && tabs->nz ? tabs->nz : 1;
   if (nz > 1 && (in_coset || out_mul)) ZK_FAIL(ctx, AMDZK_E_INVALID, "ntt: the z dimension goes with multiplier tables only");
@@ -429,7 +426,7 @@ int zk_ntt_ex(amdzk_ctx* ctx, const Fr* d_in, size_t in_stride, Fr* d_out, size_
     a.log_prev = log_prev;
     a.log_stride = log_n - log_prev - a.s;
     a.log_next = last ? 0 : plan.s[p + 1];
-    uint32_t lc = a.s >= tile_log ? 0 : tile_log - a.s;
+    uint32_t lc = a.s >= NTT_TILE_LOG ? 0 : NTT_TILE_LOG - a.s;
     if (!last && lc > a.log_stride) lc = a.log_stride;
     if (last) {
       if (plan.npass == 1) lc = 0;
@@ -463,7 +460,6 @@ int zk_ntt_ex(amdzk_ctx* ctx, const Fr* d_in, size_t in_stride, Fr* d_out, size_
     dim3 grid((uint32_t)(n >> tile_elems_log), (uint32_t)ncols, nz), block(threads);
     const size_t tile_elems = (size_t)1 << tile_elems_log;
     size_t shmem = (tile_elems + ((size_t)1 << a.s) / 2 + 1) * 9 * sizeof(uint32_t);  // limbs, see ntt_step_kernel
-    shmem += env_u32(last ? "AMDZK_NTT_LDS_PAD_LAST" : "AMDZK_NTT_LDS_PAD_FIRST", 0);  // occupancy experiments
     if (last) {
       if (shmem > 65536) ZK_HIP(ctx, hipFuncSetAttribute((const void*)ntt_step_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
       ZK_LAUNCH(ctx, "ntt_step_last", ntt_step_kernel<true>, grid, block, shmem, a);

@@ -1650,20 +1650,7 @@ static int create_proof_impl(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t ncirc,
   ZK_ENTER(ctx);
   if (!ctx) return AMDZK_E_INVALID;
   if (!pks || ncirc == 0 || !pks[0]) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: no proving key");
-  amdzk_pk* pk = pks[0];
-  // AMDZK_MSM_PIPELINE=1 (experiment, off by default): lanes mode also cuts every commitment batch into column groups on
-  // two streams with chained level-1 kernels (msm.hip zk_msm_dev_xyzz). Measured slower on both counts — 22.7-25.8 ms
-  // against 21.5 for one proof, 66-74 against 74 proofs/s — because a group's small kernels wait for workgroup slots
-  // behind the other group's level-1 kernel (profiles/r03b_stream_priorities_and_gating.txt). The caller's ctx gets
-  // its own setting back.
-  const bool keep_pipeline = ctx->msm_pipeline;
-  if (pk->use_lanes && ncirc == 1 && getenv("AMDZK_MSM_PIPELINE") && atoi(getenv("AMDZK_MSM_PIPELINE")) != 0) {
-    ctx->msm_pipeline = true;
-    for (amdzk_ctx* l : ctx->lanes)
-      if (l) l->msm_pipeline = true;
-  }
   const int r = create_proof_body(ctx, pks, ncirc, instances, instance_lens, d_advice, advice_stride, rng, transcript_kind, proof_out, proof_cap, proof_len);
-  ctx->msm_pipeline = keep_pipeline;
   if (r != AMDZK_OK) {  // a failed proof may have left work on the lanes: the key's workspace must be quiet before it is used again
     const std::string keep = ctx->err;
     (void)zk_sync_all(ctx);
@@ -1724,7 +1711,6 @@ static int create_proof_body(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t ncirc,
   if (pk->use_lanes && NC == 1) {  // several instances: one stream (each lane holds one commitment batch's result at a time)
     ZK_TRY(zk_lane(ctx, 0, &B));
     ZK_TRY(zk_lane(ctx, 1, &C));
-    B->msm_pipeline = C->msm_pipeline = ctx->msm_pipeline;
   }
   const bool serial = B == M;
   // latency mode of the commitments (common.hpp): while this proof runs on lanes; the caller's setting comes back at the end
@@ -1789,11 +1775,9 @@ static int create_proof_body(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t ncirc,
   // after_l1: the columns' commitment batch has already been launched on `after`; the transforms start behind its
   // level-1 kernel (both fill the chip: side by side they only stretch each other) and run beside its tail and beside
   // the next phase's latency-bound kernels instead
-  static const bool gate_l1 = !(getenv("AMDZK_NTT_AFTER_L1") && atoi(getenv("AMDZK_NTT_AFTER_L1")) == 0);
   auto transforms_on_B = [&](amdzk_pk* pk, amdzk_ctx* after, size_t first, size_t count, bool after_l1 = false) -> int {
     if (!count) return AMDZK_OK;
-    // (behind the WHOLE batch instead — AMDZK_NTT_AFTER_L1=2 in an experiment — measured 19.1-19.8 ms per proof against 18.7-19.1)
-    if (after_l1 && gate_l1) ZK_TRY(zk_stream_after_l1(B, after));
+    if (after_l1) ZK_TRY(zk_stream_after_l1(B, after));
     else ZK_TRY(zk_stream_after(B, after));
     LN_TRY(B, zk_lagrange_to_coeff(B, pk->dom, pk->P + first * n, n, pk->PQ + first * n, n, count));
     LN_TRY(B, zk_coeff_to_cosets_r261(B, pk->dom, pk->PQ + first * n, n, pk->PC + first * pk->ext, pk->ext, count));
@@ -1872,7 +1856,7 @@ static int create_proof_body(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t ncirc,
       }
     }
     Commit cm;
-    if (A && !serial && gate_l1) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->adv(), A, cm));
+    if (A && !serial) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->adv(), A, cm));
     ZK_TRY(transforms_on_B(pk, M, 0, (size_t)A + I, cm.begun));
     if (A && !cm.begun) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->adv(), A, cm));
     ZK_TRY(commit_end(cm));
@@ -1919,7 +1903,7 @@ static int create_proof_body(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t ncirc,
       ZK_TRY(zk_scatter_rows(ctx, pk->ls(), n, usable, pk0->small + ta.size(), bf + 1, L));
     }
     Commit cmc;
-    if (!serial && gate_l1) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->la(), 2 * L, cmc));
+    if (!serial) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->la(), 2 * L, cmc));
     ZK_TRY(transforms_on_B(pk, M, (size_t)A + I, 2 * (size_t)L, cmc.begun));
     if (!cmc.begun) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->la(), 2 * L, cmc));
     ZK_TRY(commit_end(cmc));
@@ -1986,9 +1970,9 @@ static int create_proof_body(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t ncirc,
     // ... and their commitment, enqueued BEFORE the permutation chain: the lookup chain is the shorter one, so its
     // level-1 kernel runs while M is still in fractions, inversion and scans rather than beside M's own level-1 kernel.
     // (Measured: 18.8-19.3 ms per proof either way — what one lane gains the other loses; kept for the simpler order.)
-    if (serial || !gate_l1) ZK_TRY(transforms_on_B(pk, C, (size_t)A + I + 2 * L + ns, L));
+    if (serial) ZK_TRY(transforms_on_B(pk, C, (size_t)A + I + 2 * L + ns, L));
     ZK_TRY(commit_begin(C, AMDZK_BASIS_G_LAGRANGE, pk->zl(), L, cm_zl));
-    if (!serial && gate_l1) ZK_TRY(transforms_on_B(pk, C, (size_t)A + I + 2 * L + ns, L, true));
+    if (!serial) ZK_TRY(transforms_on_B(pk, C, (size_t)A + I + 2 * L + ns, L, true));
     return AMDZK_OK;
   };
   auto perm_products = [&](size_t ci) -> int {  // fractions, inversion, running products, blinding: everything in front of the commitment
@@ -2007,7 +1991,7 @@ static int create_proof_body(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t ncirc,
   };
   auto perm_commit = [&](size_t ci) -> int {
     amdzk_pk* const pk = pks[ci];
-    if (serial || !gate_l1) ZK_TRY(transforms_on_B(pk, M, (size_t)A + I + 2 * L, ns));
+    if (serial) ZK_TRY(transforms_on_B(pk, M, (size_t)A + I + 2 * L, ns));
     ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->zp(), ns, cm_zp_all[ci]));
     return AMDZK_OK;
   };
@@ -2026,7 +2010,7 @@ static int create_proof_body(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t ncirc,
       ZK_TRY(perm_commit(ci));
     }
   }
-  if (ns && !serial && gate_l1) ZK_TRY(transforms_on_B(pk, M, (size_t)A + I + 2 * L, ns, true));  // lanes: one instance
+  if (ns && !serial) ZK_TRY(transforms_on_B(pk, M, (size_t)A + I + 2 * L, ns, true));  // lanes: one instance
   for (size_t ci = 0; ci < NC; ci++) {
     ZK_TRY(commit_end(cm_zp_all[ci]));
     ZK_TRY(write_points(cm_zp_all[ci].pts, "perm_z"));

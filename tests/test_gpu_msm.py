@@ -243,12 +243,11 @@ def test_params_write_read_roundtrip(ctx, pkg, oracle):
     p2.free(); params.free()
 
 
-@pytest.mark.parametrize("env", [{"AMDZK_TAIL_QUAD": "1"}, {"AMDZK_TAIL_QUAD": "0", "AMDZK_TAIL_TREE": "1"}, {"AMDZK_MSM_NLEV": "2"}, {"AMDZK_L1_LDS": "4"}, {"AMDZK_L1_LDS": "9"}])
+@pytest.mark.parametrize("env", [{"AMDZK_TAIL_QUAD": "1"}, {"AMDZK_TAIL_QUAD": "0", "AMDZK_TAIL_TREE": "1"}])
 def test_alternative_kernels_give_the_same_points(env):
     """The kernel variants that only run in a proof's latency mode (the bucket reduction with quad-lane point additions, or
-    with shuffle-tree row / column sums) and the measured-and-rejected ones that stay in the tree behind switches (one fold
-    level, level 1 with the accumulator in LDS, level 1 as a persistent grid) must give the oracle's points too: the parity
-    tests above, again, in a child process with the switch forced (the switches are read once per process)."""
+    with shuffle-tree row / column sums) must give the oracle's points too: the parity tests above, again, in a child
+    process with the switch forced (the switches are read once per process)."""
     import subprocess
     import sys
     e = dict(os.environ)

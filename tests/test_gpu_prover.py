@@ -509,16 +509,14 @@ def test_create_proof_argument_errors_leave_the_context_usable(ctx, pkg, plonk, 
 
 SWITCHES = [
     {"AMDZK_LATENCY_MODE": "0"}, {"AMDZK_LATENCY_COLS": "64"}, {"AMDZK_FOLD_QUAD": "0"}, {"AMDZK_TAIL_QUAD": "0", "AMDZK_TAIL_TREE": "1"},
-    {"AMDZK_MSM_NLEV": "2"}, {"AMDZK_L1_LDS": "4"}, {"AMDZK_L1_LDS": "9"}, {"AMDZK_SERIAL": "1"}, {"AMDZK_FULL_COSETS": "1"},
-    {"AMDZK_HOST_WAIT": "block"}, {"AMDZK_H_PARTS": "1"}, {"AMDZK_MSM_T1": "32", "AMDZK_MSM_TL": "4"}, {"AMDZK_MSM_PIPELINE": "0"},
-    {"AMDZK_NTT_AFTER_L1": "0"}, {"AMDZK_MSM_C": "12"}]
+    {"AMDZK_SERIAL": "1"}, {"AMDZK_FULL_COSETS": "1"}, {"AMDZK_HOST_WAIT": "block"}, {"AMDZK_H_PARTS": "1"},
+    {"AMDZK_MSM_T1": "32", "AMDZK_MSM_TL": "4"}, {"AMDZK_MSM_C": "12"}]
 
 
 def test_whole_proofs_under_every_documented_switch():
-    """INTEGRATION.md's environment switches — the variants kept behind them (latency mode off / wider, one fold level, level 1
-    with the accumulator in LDS or as a persistent grid, serial or full-coset default keys, polling waits, one-piece h(X)
-    program, other task sizes and window width, no pipelining) prove the oracle's BYTES: whole-proof tests of this file and a
-    few random constraint systems, again, in child processes with the switch forced (switches are read once per process).
+    """INTEGRATION.md's environment switches — the variants kept behind them (latency mode off / wider, serial or full-coset
+    default keys, polling waits, one-piece h(X) program, other task sizes and window width) prove the oracle's BYTES:
+    whole-proof tests of this file and a few random constraint systems, again, in child processes with the switch forced (switches are read once per process).
     Four children at a time (with this process, five on the GPU: the pool allows six)."""
     import subprocess
     here = os.path.dirname(os.path.abspath(__file__))
