@@ -119,23 +119,20 @@ std::array<uint64_t, 4> canon(const Fr& a) {
 
 }  // namespace
 
-// Source of the prover's Fr::random draws, in upstream's draw order: either ChaCha20Rng::seed_from_u64
-// replayed here, or scalars the caller drew from its own RngCore (amdzk_create_proof_scalars).
+// Source of the prover's Fr::random draws, addressed by position in upstream's draw order (DrawLayout): draw j is
+// either block ctr0 + j of ChaCha20Rng::seed_from_u64's key stream — every Fr::random this prover makes is exactly one
+// 64-byte block, so the device generates any run of draws straight into place (the blinding tails and the random
+// polynomial; the host used to draw ~1,800 scalars per proof at 0.3 us each) — or the caller's scalars[j], drawn from
+// its own RngCore (amdzk_create_proof_scalars, which checks their number against the layout).
 struct RandomSource {
-  zkhost::ChaCha20Rng* rng = nullptr;
-  const uint64_t* scalars = nullptr;
-  size_t count = 0, used = 0;
-  bool exhausted = false;
-  Fr fr() {
-    if (rng) return rng->fr();
-    if (used >= count) {
-      exhausted = true;
-      return Fr::zero();
-    }
-    Fr r;
-    memcpy(r.l, scalars + 4 * used, 32);
-    used++;
-    return r;
+  uint32_t key[8] = {};
+  uint64_t ctr0 = 0;
+  const uint64_t* scalars = nullptr;  // non-null: the caller's draws, 4 words (Montgomery) each
+  RandomSource() = default;
+  explicit RandomSource(uint64_t seed) {
+    const ChaCha20Rng rng(seed);
+    memcpy(key, rng.key(), sizeof(key));
+    ctr0 = rng.block_counter();
   }
 };
 
@@ -1548,32 +1545,826 @@ int amdzk_pk_commitments(const amdzk_pk* pk, uint64_t* fixed_out /* F x 8 */, ui
   return AMDZK_OK;
 }
 
-int amdzk_create_proof_ex(amdzk_ctx* ctx, amdzk_pk* pk, const uint64_t* const* instances, const size_t* instance_lens, const void* d_advice,
-                          size_t advice_stride, uint64_t rng_seed, int transcript_kind, uint8_t* proof_out, size_t proof_cap,
-                          size_t* proof_len);
-static int create_proof_impl(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t ncirc, const uint64_t* const* const* instances,
-                             const size_t* const* instance_lens, const void* const* d_advice, size_t advice_stride, RandomSource& rng,
-                             int transcript_kind, uint8_t* proof_out, size_t proof_cap, size_t* proof_len);
-// one circuit instance
-static int create_proof_impl(amdzk_ctx* ctx, amdzk_pk* pk, const uint64_t* const* instances, const size_t* instance_lens, const void* d_advice,
-                             size_t advice_stride, RandomSource& rng, int transcript_kind, uint8_t* proof_out, size_t proof_cap,
-                             size_t* proof_len) {
-  amdzk_pk* const pks[1] = {pk};
-  const uint64_t* const* const inst[1] = {instances};
-  const size_t* const lens[1] = {instance_lens};
-  const void* const adv[1] = {d_advice};
-  return create_proof_impl(ctx, pks, 1, inst, lens, adv, advice_stride, rng, transcript_kind, proof_out, proof_cap, proof_len);
+}  // extern "C"
+
+namespace {
+
+// Where upstream's Fr::random draws of one create_proof over NC circuit instances fall. Blocks in
+// draw order, each holding the NC instances' shares one after another: advice (per column bf + 1 tails, column-major,
+// then one unused blind per column); lookups (per lookup bf + 1 tails of A', bf + 1 of S', two unused blinds);
+// permutation products, then lookup products (per set / lookup bf tails and an unused blind); the random polynomial's n
+// coefficients and its blind; the h pieces' blinds. A blinding tail of column c, row i is draw first + c * stride + i.
+struct DrawLayout {
+  size_t col;                              // stride of a column's draws: advice, permutation and lookup products (bf + 1)
+  size_t lk_col;                           // stride of a lookup's draws in the lookups block
+  size_t per_adv, per_lk, per_pz, per_lz;  // one instance's share of each block
+  size_t adv, lk, pz, lz, rnd, h, total;   // first draw of each block; all draws
+  DrawLayout(const amdzk_pk* pk, size_t NC)
+      : col((size_t)pk->bf + 1), lk_col(2 * col + 2), per_adv((size_t)pk->A * (col + 1)), per_lk((size_t)pk->L * lk_col),
+        per_pz((size_t)pk->nsets * col), per_lz((size_t)pk->L * col), adv(0), lk(NC * per_adv), pz(lk + NC * per_lk),
+        lz(pz + NC * per_pz), rnd(lz + NC * per_lz), h(rnd + pk->n + 1), total(h + pk->qdeg) {}
+  size_t advice(size_t ci) const { return adv + ci * per_adv; }
+  size_t lookup(size_t ci) const { return lk + ci * per_lk; }  // the A' tails; the S' tails follow at + col
+  size_t perm_product(size_t ci) const { return pz + ci * per_pz; }
+  size_t lookup_product(size_t ci) const { return lz + ci * per_lz; }
+};
+
+// A commitment batch begun on a lane and collected when the transcript needs it. On one stream (serial) it is
+// collected at once: a context holds one batch's result at a time.
+struct Commit {
+  PendingCommit pc;
+  std::vector<G1Affine> pts;
+  bool begun = false, done = false;
+};
+
+// The multiopen argument's lists for pks[0..NC) (amdzk_pk::Multiopen): the evaluations in proof order, then h_poly's;
+// the queries in upstream order; SHPLONK's rotation sets. Built once per key (per list of instance keys).
+int build_multiopen(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, amdzk_pk::Multiopen& mo) {
+  amdzk_pk* const pk = pks[0];
+  const size_t n = pk->n;
+  const uint32_t S = pk->S, L = pk->L, ns = pk->nsets, bf = pk->bf;
+  auto rot_id = [&](int rot) -> uint32_t {
+    for (size_t i = 0; i < mo.rots.size(); i++)
+      if (mo.rots[i] == rot) return (uint32_t)i;
+    mo.rots.push_back(rot);
+    return (uint32_t)mo.rots.size() - 1;
+  };
+  auto addq = [&](const Fr* p, int rot) {
+    mo.ev.push_back({p, rot});
+    mo.ev_rot.push_back(rot_id(rot));
+  };
+  // written evaluations: advice (instance after instance), fixed, random, sigma, permutation products (instance after
+  // instance), lookups (instance after instance)
+  for (size_t ci = 0; ci < NC; ci++)
+    for (auto& q : pk->advice_queries) addq(pks[ci]->q_adv() + (size_t)q.first * n, q.second);
+  for (auto& q : pk->fixed_queries) addq(pk->fixed_poly + (size_t)q.first * n, q.second);
+  addq(pk->rnd, 0);
+  for (uint32_t i = 0; i < S; i++) addq(pk->sigma_poly + (size_t)i * n, 0);
+  for (size_t ci = 0; ci < NC; ci++)
+    for (uint32_t s = 0; s < ns; s++) {
+      addq(pks[ci]->q_zp() + (size_t)s * n, 0);
+      addq(pks[ci]->q_zp() + (size_t)s * n, 1);
+      if (s + 1 < ns) addq(pks[ci]->q_zp() + (size_t)s * n, -(int)(bf + 1));
+    }
+  for (size_t ci = 0; ci < NC; ci++)
+    for (uint32_t l = 0; l < L; l++) {
+      addq(pks[ci]->q_zl() + (size_t)l * n, 0);
+      addq(pks[ci]->q_zl() + (size_t)l * n, 1);
+      addq(pks[ci]->q_la() + (size_t)l * n, 0);
+      addq(pks[ci]->q_la() + (size_t)l * n, -1);
+      addq(pks[ci]->q_ls() + (size_t)l * n, 0);
+    }
+  mo.n_written = mo.ev.size();
+  addq(pk->hpoly, 0);
+  // 8. multiopen queries in upstream order
+  std::map<std::pair<const Fr*, int>, uint32_t> where;
+  for (size_t i = 0; i < mo.ev.size(); i++) where.emplace(mo.ev[i], (uint32_t)i);
+  bool missing = false;
+  auto addpq = [&](const Fr* p, int rot) {
+    auto it = where.find({p, rot});
+    if (it == where.end()) {
+      missing = true;
+      return;
+    }
+    mo.q_poly.push_back(p);
+    mo.q_rot.push_back(rot_id(rot));
+    mo.q_ev.push_back(it->second);
+  };
+  // per instance: advice queries, the permutation argument's openings, the lookups' openings; then what exists once
+  for (size_t ci = 0; ci < NC; ci++) {
+    amdzk_pk* const pk = pks[ci];
+    for (auto& q : pk->advice_queries) addpq(pk->q_adv() + (size_t)q.first * n, q.second);
+    for (uint32_t s = 0; s < ns; s++) {
+      addpq(pk->q_zp() + (size_t)s * n, 0);
+      addpq(pk->q_zp() + (size_t)s * n, 1);
+    }
+    for (int s = (int)ns - 2; s >= 0; s--) addpq(pk->q_zp() + (size_t)s * n, -(int)(bf + 1));
+    for (uint32_t l = 0; l < L; l++) {
+      addpq(pk->q_zl() + (size_t)l * n, 0);
+      addpq(pk->q_la() + (size_t)l * n, 0);
+      addpq(pk->q_ls() + (size_t)l * n, 0);
+      addpq(pk->q_la() + (size_t)l * n, -1);
+      addpq(pk->q_zl() + (size_t)l * n, 1);
+    }
+  }
+  for (auto& q : pk->fixed_queries) addpq(pk->fixed_poly + (size_t)q.first * n, q.second);
+  for (uint32_t i = 0; i < S; i++) addpq(pk->sigma_poly + (size_t)i * n, 0);
+  addpq(pk->hpoly, 0);
+  addpq(pk->rnd, 0);
+  if (missing) {
+    mo = amdzk_pk::Multiopen();
+    pk->mo_multi_keys.clear();
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: a multiopen query has no evaluation");
+  }
+  // shplonk construct_intermediate_sets, in terms of rotations: the polynomials with their sets of rotations
+  // (first seen first), then the distinct sets with their polynomials (first seen first)
+  std::vector<const Fr*> cr_poly;
+  std::vector<std::vector<std::pair<uint32_t, uint32_t>>> cr_rots;  // (rot id, ev index), ascending rot id
+  std::map<const Fr*, uint32_t> cr_of;
+  for (size_t i = 0; i < mo.q_poly.size(); i++) {
+    auto it = cr_of.find(mo.q_poly[i]);
+    if (it == cr_of.end()) {
+      it = cr_of.emplace(mo.q_poly[i], (uint32_t)cr_poly.size()).first;
+      cr_poly.push_back(mo.q_poly[i]);
+      cr_rots.emplace_back();
+    }
+    auto& v = cr_rots[it->second];
+    const std::pair<uint32_t, uint32_t> e{mo.q_rot[i], mo.q_ev[i]};
+    auto pos = std::lower_bound(v.begin(), v.end(), e, [](const auto& x1, const auto& x2) { return x1.first < x2.first; });
+    if (pos == v.end() || pos->first != e.first) v.insert(pos, e);
+  }
+  for (size_t c = 0; c < cr_poly.size(); c++) {
+    std::vector<uint32_t> ids, evs;
+    for (auto& e : cr_rots[c]) ids.push_back(e.first), evs.push_back(e.second);
+    amdzk_pk::Multiopen::Set* hit = nullptr;
+    for (auto& st : mo.sets)
+      if (st.rot_ids == ids) hit = &st;
+    if (!hit) {
+      mo.sets.emplace_back();
+      hit = &mo.sets.back();
+      hit->rot_ids = ids;
+    }
+    hit->polys.push_back(cr_poly[c]);
+    hit->ev_idx.push_back(evs);
+  }
+  size_t pairs = 0;
+  for (auto& st : mo.sets) pairs += st.rot_ids.size();
+  if (mo.sets.size() > pk->max_sets) {
+    mo = amdzk_pk::Multiopen();
+    ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "create_proof: more than %u rotation sets", pk->max_sets);
+  }
+  if (std::max<size_t>(pairs, 1) > pk->sets_Q_pairs) {
+    ZK_TRY(dalloc(ctx, pk, &pk->sets_Q, std::max<size_t>(pairs, 1) * n));
+    pk->sets_Q_pairs = std::max<size_t>(pairs, 1);
+  }
+  mo.built = true;
+  return AMDZK_OK;
 }
 
-// Number of Fr::random draws one create_proof makes for this key:
-// advice tails + advice blinds, per lookup 2 tails + 2 blinds, per permutation set tail + blind,
-// per lookup product tail + blind, the random polynomial + blind, the h-piece blinds.
-size_t amdzk_proof_random_count(const amdzk_pk* pk) {
-  if (!pk) return 0;
-  const size_t bf = pk->bf;
-  return (size_t)pk->A * (bf + 1) + pk->A + (size_t)pk->L * (2 * (bf + 1) + 2) + (size_t)pk->nsets * (bf + 1) + (size_t)pk->L * (bf + 1) +
-         pk->n + 1 + pk->qdeg;
+// SHPLONK's host side (multiopen/shplonk/prover.rs [UP]) for the sets of `mo`, whose points (rot_pt, canonical form
+// rot_canon) are kept in ascending order of the canonical field elements as upstream's BTreeSets do.
+// Per set i with points p_t (ascending): R_i(X) = sum_j y^j R_ij(X), R_ij the interpolation of polynomial j's
+// evaluations. Interpolation is linear, so R_i is the interpolation of E_i[t] = sum_j y^j eval_ij[t]:
+// R_i = sum_t E_i[t] c_it prod_{s != t} (X - p_s), c_it = 1 / prod_{s != t} (p_t - p_s) — one host product per
+// evaluation instead of one small interpolation per polynomial, and ONE field inversion (batched over all c_it)
+// instead of one per basis polynomial and point: the host used to spend 0.26 ms here with the GPU idle.
+struct ShplonkSets {
+  std::vector<std::vector<Fr>> pts;  // per set: its points, ascending
+  std::vector<std::vector<Fr>> c;    // c_it
+  std::vector<std::vector<Fr>> low;  // R_i, coefficients
+};
+ShplonkSets shplonk_interpolate(const amdzk_pk::Multiopen& mo, const std::vector<Fr>& rot_pt,
+                                const std::vector<std::array<uint64_t, 4>>& rot_canon, const std::vector<Fr>& evals, const Fr& ys) {
+  const size_t nr = mo.sets.size();
+  ShplonkSets sh;
+  sh.pts.resize(nr);
+  sh.c.resize(nr);
+  sh.low.resize(nr);
+  std::vector<std::vector<uint32_t>> set_order(nr);  // positions in rot_ids, by ascending point
+  std::vector<Fr> dens;
+  for (size_t i = 0; i < nr; i++) {
+    const amdzk_pk::Multiopen::Set& st = mo.sets[i];
+    const size_t m = st.rot_ids.size();
+    std::vector<uint32_t>& order = set_order[i];
+    order.resize(m);
+    for (size_t t = 0; t < m; t++) order[t] = (uint32_t)t;
+    std::sort(order.begin(), order.end(),
+              [&](uint32_t t1, uint32_t t2) { return fr_less_canon(rot_canon[st.rot_ids[t1]], rot_canon[st.rot_ids[t2]]); });
+    for (size_t t = 0; t < m; t++) sh.pts[i].push_back(rot_pt[st.rot_ids[order[t]]]);
+    for (size_t t = 0; t < m; t++) {
+      Fr den = Fr::one();
+      for (size_t s2 = 0; s2 < m; s2++)
+        if (s2 != t) den = mul(den, sub(sh.pts[i][t], sh.pts[i][s2]));
+      dens.push_back(den);  // non-zero: the points of a set are distinct
+    }
+  }
+  // Montgomery's trick: prefix products, one inversion, walk back
+  std::vector<Fr> pre(dens.size() + 1, Fr::one());
+  for (size_t k2 = 0; k2 < dens.size(); k2++) pre[k2 + 1] = mul(pre[k2], dens[k2]);
+  Fr acc = inv(pre[dens.size()]);
+  std::vector<Fr> dinv(dens.size());
+  for (size_t k2 = dens.size(); k2-- > 0;) {
+    dinv[k2] = mul(acc, pre[k2]);
+    acc = mul(acc, dens[k2]);
+  }
+  size_t at = 0;
+  for (size_t i = 0; i < nr; i++)
+    for (size_t t = 0; t < sh.pts[i].size(); t++) sh.c[i].push_back(dinv[at++]);
+  for (size_t i = 0; i < nr; i++) {
+    const amdzk_pk::Multiopen::Set& st = mo.sets[i];
+    const std::vector<Fr>& pts = sh.pts[i];
+    const size_t np = pts.size();
+    std::vector<Fr> E(np, Fr::zero());
+    Fr yp = Fr::one();
+    for (size_t j = 0; j < st.polys.size(); j++) {
+      for (size_t t = 0; t < np; t++) E[t] = add(E[t], mul(yp, evals[st.ev_idx[j][set_order[i][t]]]));
+      yp = mul(yp, ys);
+    }
+    sh.low[i].assign(np, Fr::zero());
+    for (size_t t = 0; t < np; t++) {
+      std::vector<Fr> num(1, Fr::one());  // prod_{s != t} (X - p_s), ascending coefficients
+      for (size_t s2 = 0; s2 < np; s2++) {
+        if (s2 == t) continue;
+        num.push_back(Fr::zero());
+        for (size_t d = num.size() - 1; d > 0; d--) num[d] = sub(num[d - 1], mul(pts[s2], num[d]));
+        num[0] = neg(mul(pts[s2], num[0]));
+      }
+      const Fr w = mul(E[t], sh.c[i][t]);
+      for (size_t d = 0; d < np; d++) sh.low[i][d] = add(sh.low[i][d], mul(w, num[d]));
+    }
+  }
+  return sh;
 }
+
+// One create_proof in flight: what its phases share, and the phases themselves (create_proof_body runs them in order).
+// pks[c] holds instance c's workspace; `pk` is pks[0]: what the proof has once (transcript representative, random
+// polynomial, h(X), multiopen buffers, staging); every per-circuit step runs in a loop over the instances with `pk`
+// shadowed by that instance's key.
+// Lanes: M = the caller's ctx (everything the transcript waits for), B and C = its auxiliary streams (common.hpp).
+// M carries the chain commitment -> challenge -> next phase; B takes each phase's columns to coefficient form and to
+// the quotient domain as soon as they are blinded (out of place: the commitments and the next phase's programs keep
+// reading the Lagrange values); C computes the lookup products beside the permutation products and commits the random
+// polynomial at the very start. Only the ORDER OF TRANSCRIPT WRITES is upstream's;
+// the arithmetic between two challenges is unordered there too. With AMDZK_KEYGEN_SERIAL, or while per-kernel
+// profiling is on, B = C = M and everything below degenerates to one stream.
+struct Prover {
+  amdzk_ctx* const ctx;
+  amdzk_pk* const* const pks;
+  amdzk_pk* const pk;
+  const size_t NC, n, usable;
+  const uint32_t A, I, L, ns, bf;
+  amdzk_ctx *const M, *const B, *const C;
+  const bool serial;
+  zkhost::TranscriptWrite& T;
+  const RandomSource& rng;
+  const DrawLayout draws;
+  Commit cm_rnd;
+  std::vector<Commit> cm_zp, cm_zl;  // per instance
+  // the multiopen lists (the key's) and what evaluations() leaves for the opening argument
+  amdzk_pk::Multiopen* mo = nullptr;
+  std::vector<Fr> rot_pt, evals;  // the points x * omega^rot, once per distinct rotation; the evaluations
+  std::vector<std::array<uint64_t, 4>> rot_canon;
+  ShplonkSets sh;
+  const bool ttrace = getenv("AMDZK_TRACE_TIME") != nullptr;
+  double tlast;
+
+  Prover(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, amdzk_ctx* B, amdzk_ctx* C, zkhost::TranscriptWrite& T, const RandomSource& rng)
+      : ctx(ctx), pks(pks), pk(pks[0]), NC(NC), n(pk->n), usable(pk->n - (pk->bf + 1)), A(pk->A), I(pk->I), L(pk->L), ns(pk->nsets),
+        bf(pk->bf), M(ctx), B(B), C(C), serial(B == ctx), T(T), rng(rng), draws(pk, NC), cm_zp(NC), cm_zl(NC), tlast(now_ms()) {}
+
+  static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+  void tick(const char* label) {
+    if (!ttrace) return;
+    zk_host_wait(ctx, ctx->stream);
+    const double t = now_ms();
+    fprintf(stderr, "[amdzk-time] %-28s %8.3f ms\n", label, t - tlast);
+    tlast = t;
+  }
+  Fr challenge(const char* label) {
+    const Fr c = T.squeeze_challenge();
+    trace_fr(label, c);
+    return c;
+  }
+  int lane_id(amdzk_ctx* l) const { return l == M ? 0 : l == B ? 1 : 2; }
+  // a failure on a lane is reported through the caller's ctx
+  int on_lane(amdzk_ctx* l, int r) {
+    if (r != AMDZK_OK && l != ctx) ctx->err = l->err;
+    return r;
+  }
+  int upload_small_on(amdzk_ctx* l, const std::vector<Fr>& v, size_t off_elems) {
+    if (off_elems + v.size() > pk->small_cap) ZK_FAIL(ctx, AMDZK_E_NOMEM, "create_proof: small buffer overflow");
+    return on_lane(l, h2d_staged(l, pk, pk->small_l[lane_id(l)] + off_elems, v.data(), v.size() * 32));
+  }
+  int write_points(const std::vector<G1Affine>& pts, const char* label) {
+    for (auto& p : pts) {
+      trace_pt(label, p);
+      if (!T.write_point(p)) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: %s commitment is the identity (cannot write points at infinity to the transcript)", label);
+    }
+    return AMDZK_OK;
+  }
+  // Blinding tails on lane l: rows [row0, row0 + cnt) of ncols columns, column c's row row0 + i taking draw
+  // first_draw + c * stride + i. A seeded ChaCha20Rng generates them on the device straight into their rows; the
+  // caller's scalars are gathered here, uploaded (staged through pinned memory) and scattered.
+  int blind(amdzk_ctx* l, Fr* d_cols, uint32_t ncols, size_t row0, uint32_t cnt, size_t first_draw, size_t stride) {
+    if (!rng.scalars)
+      return on_lane(l, zk_chacha20_blind_rows(l, d_cols, n, row0, cnt, ncols, rng.key, rng.ctr0 + first_draw, (uint32_t)stride, zkhost::fr_r3()));
+    std::vector<Fr> v((size_t)ncols * cnt);
+    for (uint32_t c = 0; c < ncols; c++) memcpy(&v[(size_t)c * cnt], rng.scalars + 4 * (first_draw + c * stride), (size_t)cnt * 32);
+    ZK_TRY(upload_small_on(l, v, 0));
+    return on_lane(l, zk_scatter_rows(l, d_cols, n, row0, pk->small_l[lane_id(l)], cnt, ncols));
+  }
+  int commit_end(Commit& c) {
+    if (c.begun && !c.done) ZK_TRY(on_lane(c.pc.ctx, commit_finish(c.pc, c.pts)));
+    c.done = true;
+    return AMDZK_OK;
+  }
+  int commit_begin(amdzk_ctx* l, int basis, const Fr* d_cols, size_t ncols, Commit& c) {
+    ZK_TRY(on_lane(l, commit_launch(l, pk, basis, d_cols, ncols, c.pc)));
+    c.begun = true;
+    if (serial) ZK_TRY(commit_end(c));
+    return AMDZK_OK;
+  }
+  // columns [first, first + count) of the arena, blinded on lane `after`: coefficients (PQ) and quotient-domain values (PC) on B
+  // after_l1: the columns' commitment batch has already been launched on `after`; the transforms start behind its
+  // level-1 kernel (both fill the chip: side by side they only stretch each other) and run beside its tail and beside
+  // the next phase's latency-bound kernels instead
+  int transforms_on_B(amdzk_pk* pk, amdzk_ctx* after, size_t first, size_t count, bool after_l1 = false) {
+    if (!count) return AMDZK_OK;
+    if (after_l1) ZK_TRY(zk_stream_after_l1(B, after));
+    else ZK_TRY(zk_stream_after(B, after));
+    ZK_TRY(on_lane(B, zk_lagrange_to_coeff(B, pk->dom, pk->P + first * n, n, pk->PQ + first * n, n, count)));
+    return on_lane(B, zk_coeff_to_cosets_r261(B, pk->dom, pk->PQ + first * n, n, pk->PC + first * pk->ext, pk->ext, count));
+  }
+  // d_out = sum_j coefs[j] polys[j] (len elements each) on lane l, through l's pointer-table and small slices; `extra`
+  // follows the coefficients in the small slice, for the kernel the caller launches next
+  int lincomb(amdzk_ctx* l, const std::vector<const Fr*>& polys, const std::vector<Fr>& coefs, Fr* d_out, size_t len,
+              const std::vector<Fr>& extra = {}) {
+    const int li = lane_id(l);
+    ZK_TRY(on_lane(l, h2d_staged(l, pk, pk->ptrs_l[li], polys.data(), polys.size() * sizeof(Fr*))));
+    ZK_TRY(upload_small_on(l, coefs, 0));
+    ZK_TRY(upload_small_on(l, extra, coefs.size()));
+    return on_lane(l, zk_lincomb(l, (const Fr* const*)pk->ptrs_l[li], pk->small_l[li], (uint32_t)polys.size(), d_out, len, false));
+  }
+  // challenges into their slots of every instance's constant table, and the span of slots they cover up to the device
+  int put_consts(std::initializer_list<std::pair<uint32_t amdzk_pk::*, Fr>> vals) {
+    for (size_t ci = 0; ci < NC; ci++) {
+      amdzk_pk* const pk = pks[ci];
+      uint32_t lo = UINT32_MAX, hi = 0;
+      for (auto& v : vals) {
+        const uint32_t s = pk->*v.first;
+        pk->consts[s] = v.second;
+        lo = std::min(lo, s);
+        hi = std::max(hi, s);
+      }
+      ZK_TRY(h2d_staged(ctx, pk, pk->d_consts + lo, &pk->consts[lo], (size_t)(hi + 1 - lo) * 32));
+    }
+    return AMDZK_OK;
+  }
+
+  // 0. vk, instances
+  int instances(const uint64_t* const* const* instances_all, const size_t* const* instance_lens_all) {
+    T.common_scalar(pk->transcript_repr);
+    for (size_t ci = 0; ci < NC && I; ci++) {  // columns are zero beyond the caller's values: clear on the device, upload only what was given
+      amdzk_pk* const pk = pks[ci];
+      const uint64_t* const* instances = instances_all ? instances_all[ci] : nullptr;
+      const size_t* instance_lens = instance_lens_all ? instance_lens_all[ci] : nullptr;
+      ZK_HIP(ctx, hipMemsetAsync(pk->inst(), 0, (size_t)I * n * 32, ctx->stream));
+      std::vector<Fr> iv;
+      for (uint32_t c = 0; c < I; c++) {
+        const size_t len = instance_lens ? instance_lens[c] : 0;
+        if (len > usable) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: instance column %u too long (InstanceTooLarge)", c);
+        if (!len) continue;
+        if (!instances || !instances[c]) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: instance column %u is null", c);
+        iv.resize(len);
+        for (size_t i = 0; i < len; i++) {
+          memcpy(iv[i].l, instances[c] + 4 * i, 32);
+          T.common_scalar(iv[i]);
+        }
+        ZK_TRY(h2d_staged(ctx, pk, pk->inst() + (size_t)c * n, iv.data(), len * 32));
+        // without room in the pinned staging area the copy reads `iv` asynchronously: finish it before the next column reuses it
+        if (!pk->pin || len * 32 > pk->pin_cap) ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
+      }
+    }
+    return AMDZK_OK;
+  }
+  // The random polynomial of the vanishing argument (step 5) depends on nothing but the RNG, at a position of the draws
+  // the key fixes: it is made now and committed on lane C while M commits the advice columns.
+  int random_poly() {
+    ZK_TRY(zk_stream_after(C, M));  // the previous proof on this key may still be reading rnd on M's stream
+    if (!rng.scalars) ZK_TRY(on_lane(C, zk_chacha20_fr_random(C, pk->rnd, n, rng.key, rng.ctr0 + draws.rnd, zkhost::fr_r3())));
+    else ZK_TRY(on_lane(C, h2d(C, pk->rnd, rng.scalars + 4 * draws.rnd, n * 32)));  // the caller's buffer outlives the call
+    return commit_begin(C, AMDZK_BASIS_G, pk->rnd, 1, cm_rnd);
+  }
+  // 1. advice: copy in, blind the unusable rows of every column, commit
+  int advice(const void* const* d_advice_all, size_t advice_stride) {
+    for (size_t ci = 0; ci < NC; ci++) {
+      amdzk_pk* const pk = pks[ci];
+      if (A) {
+        ZK_HIP(ctx, hipMemcpy2DAsync(pk->adv(), n * 32, d_advice_all[ci], advice_stride * 32, n * 32, A, hipMemcpyDeviceToDevice, ctx->stream));
+        ZK_TRY(blind(M, pk->adv(), A, usable, bf + 1, draws.advice(ci), draws.col));
+      }
+      Commit cm;
+      if (A && !serial) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->adv(), A, cm));
+      ZK_TRY(transforms_on_B(pk, M, 0, (size_t)A + I, cm.begun));
+      if (A && !cm.begun) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->adv(), A, cm));
+      ZK_TRY(commit_end(cm));
+      ZK_TRY(write_points(cm.pts, "advice"));
+    }
+    ZK_TRY(commit_end(cm_rnd));  // long done; lane C's MSM workspace is free for the lookup products' commitment
+    tick("advice");
+    return AMDZK_OK;
+  }
+  // 2. lookups: compress, permute (on the device), blind, commit
+  int lookups() {
+    for (size_t ci = 0; ci < NC && L; ci++) {
+      amdzk_pk* const pk = pks[ci];
+      ZK_TRY(run_program(ctx, pk, pk->prog_compress, false, pk->d_outs_compress, nullptr, "expr_lookup_compress"));
+      ZK_TRY(d2d(ctx, pk->la(), pk->ci, (size_t)L * n * 32));
+      ZK_TRY(zk_permute_expression_pairs(ctx, pk->la(), pk->ct, pk->lk_ts, pk->ls(), pk->lk_left, pk->lk_flags, pk->d_err, L, (uint32_t)n,
+                                         (uint32_t)usable, pk->lk_ts_const, pk->lk_const));
+      // the "input not in table" word comes down behind the permutation and is read once the host has waited for this
+      // phase's commitment anyway (it used to be a host wait of its own in the middle of the phase: 0.1 ms of idle device)
+      *pk->h_err = 0;
+      ZK_HIP(ctx, hipMemcpyAsync(pk->h_err, pk->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+      tick("  lookup: device permute");
+      ZK_TRY(blind(M, pk->la(), L, usable, bf + 1, draws.lookup(ci), draws.lk_col));
+      ZK_TRY(blind(M, pk->ls(), L, usable, bf + 1, draws.lookup(ci) + draws.col, draws.lk_col));
+      Commit cmc;
+      if (!serial) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->la(), 2 * L, cmc));
+      ZK_TRY(transforms_on_B(pk, M, (size_t)A + I, 2 * (size_t)L, cmc.begun));
+      if (!cmc.begun) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->la(), 2 * L, cmc));
+      ZK_TRY(commit_end(cmc));
+      if (*pk->h_err) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: lookup %d input not in table (ConstraintSystemFailure)", *pk->h_err - 1);
+      const std::vector<G1Affine>& cm = cmc.pts;
+      for (uint32_t l = 0; l < L; l++) {
+        std::vector<G1Affine> two = {cm[l], cm[L + l]};
+        ZK_TRY(write_points(two, "lookup_permuted"));
+      }
+    }
+    tick("lookups_permuted");
+    return AMDZK_OK;
+  }
+  int lookup_products(size_t ci, bool ordered_behind_m) {
+    amdzk_pk* const pk = pks[ci];
+    if (!ordered_behind_m) ZK_TRY(zk_stream_after(C, M));  // beta, gamma and the permuted columns are in place
+    ZK_TRY(on_lane(C, run_program(C, pk, pk->prog_lfrac, false, pk->d_outs_lfrac, nullptr, "expr_lookup_fractions")));
+    ZK_TRY(on_lane(C, zk_batch_invert(C, pk->frac2, pk->scratch2, (size_t)L * n)));
+    ZK_TRY(on_lane(C, zk_mul_elem(C, pk->zl(), pk->frac2, (size_t)L * n)));
+    ZK_TRY(on_lane(C, zk_running_product(C, pk->zl(), L, n, n, false, 0, pk->scan_tmp2)));
+    ZK_TRY(blind(C, pk->zl(), L, n - bf, bf, draws.lookup_product(ci), draws.col));
+    // ... and their commitment, enqueued BEFORE the permutation chain: the lookup chain is the shorter one, so its
+    // level-1 kernel runs while M is still in fractions, inversion and scans rather than beside M's own level-1 kernel.
+    // (Measured: 18.8-19.3 ms per proof either way — what one lane gains the other loses; kept for the simpler order.)
+    if (serial) ZK_TRY(transforms_on_B(pk, C, (size_t)A + I + 2 * L + ns, L));
+    ZK_TRY(commit_begin(C, AMDZK_BASIS_G_LAGRANGE, pk->zl(), L, cm_zl[ci]));
+    if (!serial) ZK_TRY(transforms_on_B(pk, C, (size_t)A + I + 2 * L + ns, L, true));
+    return AMDZK_OK;
+  }
+  int perm_products(size_t ci) {  // fractions, inversion, running products, blinding: everything in front of the commitment
+    amdzk_pk* const pk = pks[ci];
+    ZK_TRY(run_program(ctx, pk, pk->prog_pfrac, false, pk->d_outs_pfrac, nullptr, "expr_perm_fractions"));
+    tick("  perm: fractions program");
+    ZK_TRY(zk_batch_invert(ctx, pk->frac, pk->scratch, (size_t)ns * n));
+    tick("  perm: batch invert");
+    ZK_TRY(zk_mul_elem(ctx, pk->zp(), pk->frac, (size_t)ns * n));
+    ZK_TRY(zk_running_product(ctx, pk->zp(), ns, n, n, true, usable, pk->scan_tmp));
+    tick("  perm: running product");
+    return blind(M, pk->zp(), ns, n - bf, bf, draws.perm_product(ci), draws.col);
+  }
+  int perm_commit(size_t ci) {
+    amdzk_pk* const pk = pks[ci];
+    if (serial) ZK_TRY(transforms_on_B(pk, M, (size_t)A + I + 2 * L, ns));
+    return commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->zp(), ns, cm_zp[ci]);
+  }
+  // 3. + 4. permutation grand products on M, lookup grand products on C (they depend on beta and gamma only, not on
+  // each other). (Several instances: every instance's permutation products are committed before the first lookup product.)
+  int products() {
+    if (!serial) {
+      // Lanes (one instance): the HOST enqueues M's chain first — seven launches the transcript waits for — and lane C's
+      // lookup products (a dozen launches and a commitment batch's fourteen) while M's fractions and inversion run: the
+      // device used to sit 0.48 ms behind beta / gamma waiting for M's first kernel (profiles/r03zz_timeline_single_proof.txt).
+      if (L) ZK_TRY(zk_stream_after(C, M));  // C starts behind beta, gamma and the permuted columns — NOT behind M's products below
+      if (ns) ZK_TRY(perm_products(0));
+      if (L) ZK_TRY(lookup_products(0, true));
+      if (ns) ZK_TRY(perm_commit(0));
+    } else {
+      for (size_t ci = 0; ci < NC && L; ci++) ZK_TRY(lookup_products(ci, false));
+      for (size_t ci = 0; ci < NC && ns; ci++) {
+        ZK_TRY(perm_products(ci));
+        ZK_TRY(perm_commit(ci));
+      }
+    }
+    if (ns && !serial) ZK_TRY(transforms_on_B(pk, M, (size_t)A + I + 2 * L, ns, true));  // lanes: one instance
+    for (size_t ci = 0; ci < NC; ci++) {
+      ZK_TRY(commit_end(cm_zp[ci]));
+      ZK_TRY(write_points(cm_zp[ci].pts, "perm_z"));
+    }
+    tick("perm_products");
+    for (size_t ci = 0; ci < NC; ci++) {
+      ZK_TRY(commit_end(cm_zl[ci]));
+      ZK_TRY(write_points(cm_zl[ci].pts, "lookup_z"));
+    }
+    tick("lookup_products");
+    return AMDZK_OK;
+  }
+  // 6. h(X): every committed column is on the quotient domain once lane B has drained
+  int vanishing(const Fr& y) {
+    ZK_TRY(zk_stream_after(M, B));
+    for (size_t ci = 0; ci < NC; ci++) ZK_TRY(quotient_from_cosets(ctx, pks[ci]));  // theta, beta, gamma, delta powers, y are all known by now
+    if (NC > 1) {
+      // evaluate_h folds the instances' terms in ONE Horner chain with y, instance after instance: with K terms per instance
+      // the numerator is sum_c y^(K (NC - 1 - c)) * numerator_c, and the division by X^n - 1, the interpolation and the cut
+      // into pieces are linear — so the pieces are the same combination of the instances' pieces.
+      std::vector<const Fr*> pp(NC);
+      std::vector<Fr> cf(NC);
+      const Fr yK = pow_u64(y, pk->h_terms);
+      Fr cur = Fr::one();
+      for (size_t ci = NC; ci-- > 0;) {
+        pp[ci] = pks[ci]->hpieces;
+        cf[ci] = cur;
+        cur = mul(cur, yK);
+      }
+      const size_t len = (size_t)pk->qdeg * n;
+      ZK_TRY(lincomb(M, pp, cf, pk->scratch, len));  // scratch holds >= ext >= qdeg * n
+      ZK_TRY(d2d(ctx, pk->hpieces, pk->scratch, len * 32));
+    }
+    std::vector<G1Affine> cm;
+    ZK_TRY(commit_cols(ctx, pk, AMDZK_BASIS_G, pk->hpieces, pk->qdeg, cm));  // consecutive n-blocks
+    ZK_TRY(write_points(cm, "h_piece"));
+    tick("h_eval+commit");
+    return AMDZK_OK;
+  }
+  // 7. evaluations: h_poly = sum_i piece_i * x^(n i), then one list of (polynomial, rotation) in proof order and the
+  //    extra evaluation SHPLONK needs (h_poly at x; random at x is already in the list)
+  int evaluations(const Fr& x) {
+    {
+      const Fr xn = pow_u64(x, n);
+      std::vector<const Fr*> pp(pk->qdeg);
+      std::vector<Fr> cf(pk->qdeg);
+      Fr cur = Fr::one();
+      for (uint32_t i = 0; i < pk->qdeg; i++) {
+        pp[i] = pk->hpieces + (size_t)i * n;
+        cf[i] = cur;
+        cur = mul(cur, xn);
+      }
+      ZK_TRY(lincomb(M, pp, cf, pk->hpoly, n));
+    }
+    mo = NC == 1 ? &pk->mo : &pk->mo_multi;
+    if (NC > 1) {  // the cached lists name the polynomials of one particular list of instance keys
+      std::vector<const amdzk_pk*> keys(pks, pks + NC);
+      if (keys != pk->mo_multi_keys) {
+        pk->mo_multi = amdzk_pk::Multiopen();
+        pk->mo_multi_keys = keys;
+      }
+    }
+    if (!mo->built) ZK_TRY(build_multiopen(ctx, pks, NC, *mo));
+    const size_t nrot = mo->rots.size();
+    rot_pt.resize(nrot);
+    rot_canon.resize(nrot);
+    for (size_t r = 0; r < nrot; r++) {
+      rot_pt[r] = rotate_omega(pk, x, mo->rots[r]);
+      rot_canon[r] = canon(rot_pt[r]);
+    }
+    const size_t nq = mo->ev.size();
+    if (nq > pk->ptrs_cap || 2 * nq > pk->small_cap) ZK_FAIL(ctx, AMDZK_E_NOMEM, "create_proof: too many queries (%zu)", nq);
+    std::vector<const Fr*> pp(nq);
+    std::vector<Fr> pts(nq);
+    for (size_t i = 0; i < nq; i++) pp[i] = mo->ev[i].first, pts[i] = rot_pt[mo->ev_rot[i]];
+    ZK_TRY(h2d_staged(ctx, pk, pk->ptrs, pp.data(), nq * sizeof(Fr*)));
+    ZK_TRY(upload_small_on(M, pts, 0));
+    ZK_TRY(zk_poly_eval(ctx, (const Fr* const*)pk->ptrs, pk->small, pk->small + nq, nq, (uint32_t)n));
+    evals.resize(nq);
+    ZK_TRY(d2h(ctx, evals.data(), pk->small + nq, nq * 32));
+    for (size_t i = 0; i < mo->n_written; i++) T.write_scalar(evals[i]);
+    tick("evals");
+    return AMDZK_OK;
+  }
+  // 9a. GWC (multiopen/gwc/prover.rs [UP]): queries grouped by point in first-seen order;
+  // per point z:  W_z = (sum_j v^j p_j - sum_j v^j p_j(z)) / (X - z), committed and written in that order.
+  int gwc(const Fr& v) {
+    struct PS {
+      Fr z;
+      std::vector<const Fr*> polys;
+      std::vector<Fr> evals;
+    };
+    std::vector<PS> psets;  // one per distinct point (= distinct rotation), first seen first
+    std::vector<int> ps_of_rot(rot_pt.size(), -1);
+    for (size_t i = 0; i < mo->q_poly.size(); i++) {
+      const uint32_t r = mo->q_rot[i];
+      if (ps_of_rot[r] < 0) {
+        ps_of_rot[r] = (int)psets.size();
+        psets.push_back(PS{rot_pt[r], {}, {}});
+      }
+      PS& hit = psets[ps_of_rot[r]];
+      hit.polys.push_back(mo->q_poly[i]);
+      hit.evals.push_back(evals[mo->q_ev[i]]);
+    }
+    const size_t np = psets.size();
+    if (np > 16) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "create_proof: more than 16 opening points");
+    for (size_t i = 0; i < np; i++) {
+      const size_t m = psets[i].polys.size();
+      if (m > pk->ptrs_cap || m + 1 > pk->small_cap) ZK_FAIL(ctx, AMDZK_E_NOMEM, "create_proof: opening set too large");
+      std::vector<Fr> cf(m);
+      Fr cur = Fr::one(), eb = Fr::zero();
+      for (size_t j = 0; j < m; j++) {
+        cf[j] = cur;
+        eb = add(eb, mul(cur, psets[i].evals[j]));
+        cur = mul(cur, v);
+      }
+      Fr* Wi = pk->sets_N + i * n;
+      ZK_TRY(lincomb(M, psets[i].polys, cf, Wi, n, {eb}));
+      ZK_TRY(zk_sub_low(ctx, Wi, pk->small + m, 1));
+    }
+    std::vector<Fr*> pp(np);
+    std::vector<Fr> roots(np);
+    for (size_t i = 0; i < np; i++) {
+      pp[i] = pk->sets_N + i * n;
+      roots[i] = psets[i].z;
+    }
+    ZK_TRY(h2d_staged(ctx, pk, pk->ptrs, pp.data(), np * sizeof(Fr*)));
+    ZK_TRY(upload_small_on(M, roots, 0));
+    ZK_TRY(zk_kate_div(ctx, (Fr* const*)pk->ptrs, pk->small, np, (uint32_t)n));
+    std::vector<G1Affine> cm;
+    ZK_TRY(commit_cols(ctx, pk, AMDZK_BASIS_G, pk->sets_N, np, cm));
+    return write_points(cm, "gwc_w");
+  }
+  // 9b. SHPLONK (multiopen/shplonk/prover.rs [UP]), up to its first commitment h(X)
+  int shplonk(const Fr& ys, const Fr& v) {
+    const size_t nr = mo->sets.size();
+    if (nr > 16) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "create_proof: more than 16 rotation sets");
+    sh = shplonk_interpolate(*mo, rot_pt, rot_canon, evals, ys);
+    // L_i = sum_j y^j P_ij ; N_i = (L_i - R_i) / prod_t (X - p_t), R_i = sum_j y^j R_ij. The division runs once, not once
+    // per point: 1 / prod_t (X - p_t) = sum_t c_t / (X - p_t) with c_t = 1 / prod_{s != t} (p_t - p_s) (the points of a
+    // set are distinct), and L_i - R_i vanishes at every p_t, so N_i = sum_t c_t Q_it with Q_it = (L_i - R_i) / (X - p_t)
+    // — all (set, point) quotients in ONE division launch, then h(X) = sum_i v^i N_i = sum_it (v^i c_it) Q_it in one
+    // linear combination. Exact arithmetic, same polynomial. The L_i of different sets are independent: one lane each.
+    size_t maxm = 0;
+    for (size_t i = 0; i < nr; i++) maxm = std::max(maxm, sh.pts[i].size());
+    std::vector<const Fr*> q_src;
+    std::vector<Fr*> q_dst;
+    std::vector<Fr> q_root, q_low, q_coef;
+    amdzk_ctx* lanes3[3] = {M, B, C};
+    Fr vpow = Fr::one();
+    for (size_t i = 0; i < nr; i++) {
+      const size_t m = mo->sets[i].polys.size(), np = sh.pts[i].size();
+      if (m > pk->ptrs_cap || m > pk->small_cap / 2) ZK_FAIL(ctx, AMDZK_E_NOMEM, "create_proof: rotation set too large");
+      std::vector<Fr> cf(m);
+      Fr cur = Fr::one();
+      for (size_t j = 0; j < m; j++) {
+        cf[j] = cur;
+        cur = mul(cur, ys);
+      }
+      amdzk_ctx* ln = lanes3[i % 3];
+      if (ln != M && i < 3) ZK_TRY(zk_stream_after(ln, M));  // the evaluations above came off M; hpoly is in place
+      Fr* Li = pk->sets_L + i * n;
+      ZK_TRY(lincomb(ln, mo->sets[i].polys, cf, Li, n));
+      for (size_t t = 0; t < np; t++) {
+        q_src.push_back(Li);
+        q_dst.push_back(pk->sets_Q + q_dst.size() * n);
+        q_root.push_back(sh.pts[i][t]);
+        q_coef.push_back(mul(vpow, sh.c[i][t]));
+        for (size_t d = 0; d < maxm; d++) q_low.push_back(d < np ? sh.low[i][d] : Fr::zero());
+      }
+      vpow = mul(vpow, v);
+    }
+    ZK_TRY(zk_stream_after(M, B));
+    ZK_TRY(zk_stream_after(M, C));
+    const size_t nq = q_dst.size();
+    if (2 * nq > pk->ptrs_cap || nq * (maxm + 2) > pk->small_cap) ZK_FAIL(ctx, AMDZK_E_NOMEM, "create_proof: too many opening points");
+    void** pt = (void**)pk->ptrs;
+    ZK_TRY(h2d_staged(ctx, pk, pt, q_dst.data(), nq * sizeof(Fr*)));
+    ZK_TRY(h2d_staged(ctx, pk, pt + nq, q_src.data(), nq * sizeof(Fr*)));
+    ZK_TRY(upload_small_on(M, q_root, 0));
+    ZK_TRY(upload_small_on(M, q_low, nq));
+    ZK_TRY(upload_small_on(M, q_coef, nq + q_low.size()));
+    ZK_TRY(zk_kate_div_from(ctx, (Fr* const*)pt, (const Fr* const*)(pt + nq), pk->small, pk->small + nq, (uint32_t)maxm, nq, (uint32_t)n));
+    ZK_TRY(zk_lincomb(ctx, (const Fr* const*)pt, pk->small + nq + q_low.size(), (uint32_t)nq, pk->hx, n, false));
+    std::vector<G1Affine> cm;
+    ZK_TRY(commit_cols(ctx, pk, AMDZK_BASIS_G, pk->hx, 1, cm));
+    return write_points(cm, "shplonk_h1");
+  }
+  // ... and its second: l(X) = sum_i v^i z_i (L_i - r_i) - zt(u) h(X);  then / (X - u) / z_0 — the factor 1 / z_0 rides
+  // in on the coefficients. The super point set is kept in ascending order of the canonical field elements.
+  int shplonk_final(const Fr& v, const Fr& u) {
+    const size_t nr = mo->sets.size();
+    std::vector<uint32_t> super(rot_pt.size());
+    for (size_t r = 0; r < super.size(); r++) super[r] = (uint32_t)r;
+    std::sort(super.begin(), super.end(), [&](uint32_t r1, uint32_t r2) { return fr_less_canon(rot_canon[r1], rot_canon[r2]); });
+    Fr zt = Fr::one();
+    for (uint32_t r : super) zt = mul(zt, sub(u, rot_pt[r]));
+    std::vector<const Fr*> pp(nr + 1);
+    std::vector<Fr> cf(nr + 1);
+    Fr cur = Fr::one(), z0 = Fr::one(), cterm = Fr::zero();
+    for (size_t i = 0; i < nr; i++) {
+      Fr zi = Fr::one();
+      for (uint32_t r : super)
+        if (!std::binary_search(mo->sets[i].rot_ids.begin(), mo->sets[i].rot_ids.end(), r)) zi = mul(zi, sub(u, rot_pt[r]));
+      if (i == 0) z0 = zi;
+      const Fr ri = eval_small(sh.low[i], u);  // R_i(u) = sum_j y^j R_ij(u)
+      Fr w = mul(cur, zi);
+      pp[i] = pk->sets_L + i * n;
+      cf[i] = w;
+      cterm = add(cterm, mul(w, ri));
+      cur = mul(cur, v);
+    }
+    pp[nr] = pk->hx;
+    cf[nr] = neg(zt);
+    const Fr z0inv = inv(z0);
+    for (auto& c : cf) c = mul(c, z0inv);
+    cterm = mul(cterm, z0inv);
+    Fr* lx = pk->sets_Q;  // reuse
+    ZK_TRY(lincomb(M, pp, cf, lx, n, {cterm, u}));
+    std::vector<Fr*> one_p = {lx};
+    ZK_TRY(h2d_staged(ctx, pk, (void**)pk->ptrs + nr + 1, one_p.data(), sizeof(Fr*)));
+    ZK_TRY(zk_kate_div_from(ctx, (Fr* const*)((void**)pk->ptrs + nr + 1), nullptr, pk->small + nr + 2, pk->small + nr + 1, 1, 1, (uint32_t)n));
+    std::vector<G1Affine> cm;
+    ZK_TRY(commit_cols(ctx, pk, AMDZK_BASIS_G, lx, 1, cm));
+    return write_points(cm, "shplonk_h2");
+  }
+};
+
+// One proof over NC instances of the circuit (upstream's `circuits: &[C]`, `instances: &[&[&[F]]]`): pks[c] holds
+// instance c's workspace — the key itself for c = 0, workspace clones of it for the others (amdzk_pk_clone_workspace).
+// Upstream's order (plonk/prover.rs [UP]): instances, advice, lookup permutations, permutation products and lookup
+// products are each written circuit after circuit; the challenges, the random polynomial and h(X) exist once; the
+// evaluations are advice (per circuit), fixed, random, sigma, permutation products (per circuit), lookups (per circuit).
+int create_proof_body(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, const uint64_t* const* const* instances_all,
+                      const size_t* const* instance_lens_all, const void* const* d_advice_all, size_t advice_stride, const RandomSource& rng,
+                      int transcript_kind, uint8_t* proof_out, size_t proof_cap, size_t* proof_len) {
+  amdzk_pk* const pk = pks[0];
+  if (!proof_len) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: null argument");
+  for (size_t c = 0; c < NC; c++) {
+    if (!pks[c] || (pk->A && (!d_advice_all || !d_advice_all[c]))) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: null argument (circuit %zu)", c);
+    const amdzk_pk* root_c = pks[c]->clone_of ? pks[c]->clone_of : pks[c];
+    const amdzk_pk* root_0 = pk->clone_of ? pk->clone_of : pk;
+    if (root_c != root_0) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: circuit %zu's key is not the first key or a workspace clone of it", c);
+    for (size_t d = 0; d < c; d++)
+      if (pks[d] == pks[c]) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: circuits %zu and %zu share one workspace", d, c);
+  }
+  if (advice_stride < pk->n) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: advice stride < n");
+  const bool use_gwc = (transcript_kind & AMDZK_MULTIOPEN_GWC) != 0;
+  transcript_kind &= ~AMDZK_MULTIOPEN_GWC;
+  zkhost::Blake2bWrite t_blake;
+  zkhost::Keccak256Write t_keccak;
+  if (transcript_kind != AMDZK_TRANSCRIPT_BLAKE2B && transcript_kind != AMDZK_TRANSCRIPT_KECCAK256_EVM)
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: unknown transcript kind %d", transcript_kind);
+  zkhost::TranscriptWrite& T = transcript_kind == AMDZK_TRANSCRIPT_BLAKE2B ? (zkhost::TranscriptWrite&)t_blake : (zkhost::TranscriptWrite&)t_keccak;
+  amdzk_ctx *B = ctx, *C = ctx;  // the lanes (Prover)
+  if (pk->use_lanes && NC == 1) {  // several instances: one stream (each lane holds one commitment batch's result at a time)
+    ZK_TRY(zk_lane(ctx, 0, &B));
+    ZK_TRY(zk_lane(ctx, 1, &C));
+  }
+  const bool serial = B == ctx;
+  // latency mode of the commitments (common.hpp): while this proof runs on lanes; the caller's setting comes back at the end
+  struct LatencyMode {
+    amdzk_ctx* c[3];
+    bool keep[3];
+    LatencyMode(amdzk_ctx* m, amdzk_ctx* b, amdzk_ctx* cc, bool on) : c{m, b, cc} {
+      for (int i = 0; i < 3; i++) keep[i] = c[i]->msm_latency_mode, c[i]->msm_latency_mode = on || keep[i];
+    }
+    ~LatencyMode() {
+      for (int i = 0; i < 3; i++) c[i]->msm_latency_mode = keep[i];
+    }
+  } latency_mode(ctx, B, C, !serial && !(getenv("AMDZK_LATENCY_MODE") && atoi(getenv("AMDZK_LATENCY_MODE")) == 0));
+
+  Prover P(ctx, pks, NC, B, C, T, rng);
+  ZK_TRY(P.instances(instances_all, instance_lens_all));
+  ZK_TRY(P.random_poly());
+  ZK_TRY(P.advice(d_advice_all, advice_stride));
+  const Fr theta = P.challenge("theta");
+  ZK_TRY(P.put_consts({{&amdzk_pk::c_theta, theta}}));
+  ZK_TRY(P.lookups());
+  const Fr beta = P.challenge("beta");
+  const Fr gamma = P.challenge("gamma");
+  // the permutation factors are evaluated as beta (sigma + w) and beta (delta^j X + w) with w = (v + gamma) / beta
+  if (pk->S && beta.is_zero()) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "create_proof: the challenge beta is zero (probability 2^-254): the factored permutation terms need 1 / beta");
+  ZK_TRY(P.put_consts({{&amdzk_pk::c_beta, beta}, {&amdzk_pk::c_gamma, gamma}, {&amdzk_pk::c_betainv, inv(beta)}}));
+  P.tick("  perm: challenges+consts");
+  ZK_TRY(P.products());
+  ZK_TRY(P.write_points(P.cm_rnd.pts, "random_poly"));  // 5. vanishing: the random polynomial, committed at the start
+  const Fr y = P.challenge("y");
+  ZK_TRY(P.put_consts({{&amdzk_pk::c_y, y}}));
+  ZK_TRY(P.vanishing(y));
+  const Fr x = P.challenge("x");
+  ZK_TRY(P.evaluations(x));
+  if (use_gwc) {
+    ZK_TRY(P.gwc(P.challenge("gwc_v")));
+  } else {
+    const Fr ys = P.challenge("shplonk_y");
+    const Fr v = P.challenge("shplonk_v");
+    ZK_TRY(P.shplonk(ys, v));
+    ZK_TRY(P.shplonk_final(v, P.challenge("u")));
+  }
+  P.tick("multiopen");
+  *proof_len = T.proof.size();
+  if (proof_out) {
+    if (proof_cap < T.proof.size()) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: proof buffer too small (%zu < %zu)", proof_cap, T.proof.size());
+    memcpy(proof_out, T.proof.data(), T.proof.size());
+  }
+  return AMDZK_OK;
+}
+
+int create_proof_impl(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t ncirc, const uint64_t* const* const* instances,
+                      const size_t* const* instance_lens, const void* const* d_advice, size_t advice_stride, const RandomSource& rng,
+                      int transcript_kind, uint8_t* proof_out, size_t proof_cap, size_t* proof_len) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  if (!pks || ncirc == 0 || !pks[0]) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: no proving key");
+  const int r = create_proof_body(ctx, pks, ncirc, instances, instance_lens, d_advice, advice_stride, rng, transcript_kind, proof_out, proof_cap, proof_len);
+  if (r != AMDZK_OK) {  // a failed proof may have left work on the lanes: the key's workspace must be quiet before it is used again
+    const std::string keep = ctx->err;
+    (void)zk_sync_all(ctx);
+    ctx->err = keep;
+  }
+  return r;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Number of Fr::random draws one create_proof makes for this key (DrawLayout).
+size_t amdzk_proof_random_count(const amdzk_pk* pk) { return pk ? DrawLayout(pk, 1).total : 0; }
 
 // Length of the proof create_proof writes for this key: commitments — advice, 2 per lookup (A', S'), one per
 // permutation set, one per lookup product, the random polynomial, the h pieces, SHPLONK's two — then the
@@ -1597,15 +2388,7 @@ static size_t opening_point_count(const amdzk_pk* pk) {
   return rots.size();
 }
 
-size_t amdzk_proof_size(const amdzk_pk* pk, int format) {
-  if (!pk) return 0;
-  const int transcript_kind = format & 0xff;
-  const size_t openings = (format & AMDZK_MULTIOPEN_GWC) ? opening_point_count(pk) : 2;
-  const size_t points = (size_t)pk->A + 2 * (size_t)pk->L + pk->nsets + pk->L + 1 + pk->qdeg + openings;
-  const size_t scalars = pk->advice_queries.size() + pk->fixed_queries.size() + 1 + pk->S + (pk->nsets ? 3 * (size_t)pk->nsets - 1 : 0) +
-                         5 * (size_t)pk->L;
-  return points * (transcript_kind == AMDZK_TRANSCRIPT_KECCAK256_EVM ? 64 : 32) + scalars * 32;
-}
+size_t amdzk_proof_size(const amdzk_pk* pk, int format) { return amdzk_proof_size_multi(pk, 1, format); }
 
 // create_proof with the caller's randomness: `scalars` = amdzk_proof_random_count(pk) Fr elements
 // (Montgomery), drawn by the caller with Fr::random(&mut rng) in order.
@@ -1619,8 +2402,7 @@ int amdzk_create_proof_scalars(amdzk_ctx* ctx, amdzk_pk* pk, const uint64_t* con
     ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_scalars: %zu scalars given, %zu needed", scalar_count, amdzk_proof_random_count(pk));
   RandomSource rs;
   rs.scalars = scalars;
-  rs.count = scalar_count;
-  return create_proof_impl(ctx, pk, instances, instance_lens, d_advice, advice_stride, rs, transcript_kind, proof_out, proof_cap, proof_len);
+  return create_proof_impl(ctx, &pk, 1, &instances, &instance_lens, &d_advice, advice_stride, rs, transcript_kind, proof_out, proof_cap, proof_len);
 }
 
 int amdzk_create_proof(amdzk_ctx* ctx, amdzk_pk* pk, const uint64_t* const* instances, const size_t* instance_lens, const void* d_advice,
@@ -1635,828 +2417,8 @@ int amdzk_create_proof_ex(amdzk_ctx* ctx, amdzk_pk* pk, const uint64_t* const* i
                           size_t* proof_len) {
   ZK_ENTER(ctx);
   if (!ctx) return AMDZK_E_INVALID;
-  ChaCha20Rng chacha(rng_seed);
-  RandomSource rs;
-  rs.rng = &chacha;
-  return create_proof_impl(ctx, pk, instances, instance_lens, d_advice, advice_stride, rs, transcript_kind, proof_out, proof_cap, proof_len);
-}
-
-static int create_proof_body(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t ncirc, const uint64_t* const* const* instances_all,
-                             const size_t* const* instance_lens_all, const void* const* d_advice_all, size_t advice_stride, RandomSource& rng,
-                             int transcript_kind, uint8_t* proof_out, size_t proof_cap, size_t* proof_len);
-static int create_proof_impl(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t ncirc, const uint64_t* const* const* instances,
-                             const size_t* const* instance_lens, const void* const* d_advice, size_t advice_stride, RandomSource& rng,
-                             int transcript_kind, uint8_t* proof_out, size_t proof_cap, size_t* proof_len) {
-  ZK_ENTER(ctx);
-  if (!ctx) return AMDZK_E_INVALID;
-  if (!pks || ncirc == 0 || !pks[0]) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: no proving key");
-  const int r = create_proof_body(ctx, pks, ncirc, instances, instance_lens, d_advice, advice_stride, rng, transcript_kind, proof_out, proof_cap, proof_len);
-  if (r != AMDZK_OK) {  // a failed proof may have left work on the lanes: the key's workspace must be quiet before it is used again
-    const std::string keep = ctx->err;
-    (void)zk_sync_all(ctx);
-    ctx->err = keep;
-  }
-  return r;
-}
-// One proof over ncirc instances of the circuit (upstream's `circuits: &[C]`, `instances: &[&[&[F]]]`): pks[c] holds
-// instance c's workspace — the key itself for c = 0, workspace clones of it for the others (amdzk_pk_clone_workspace).
-// `pk` below is pks[0]: what the proof has once (transcript representative, random polynomial, h(X), multiopen buffers,
-// staging); every per-circuit step runs in a loop over the instances with `pk` shadowed by that instance's key.
-// Upstream's order (plonk/prover.rs [UP]): instances, advice, lookup permutations, permutation products and lookup
-// products are each written circuit after circuit; the challenges, the random polynomial and h(X) exist once; the
-// evaluations are advice (per circuit), fixed, random, sigma, permutation products (per circuit), lookups (per circuit).
-static int create_proof_body(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t ncirc, const uint64_t* const* const* instances_all,
-                             const size_t* const* instance_lens_all, const void* const* d_advice_all, size_t advice_stride, RandomSource& rng,
-                             int transcript_kind, uint8_t* proof_out, size_t proof_cap, size_t* proof_len) {
-  amdzk_pk* const pk = pks[0];
-  const size_t NC = ncirc;
-  if (!proof_len) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: null argument");
-  for (size_t c = 0; c < NC; c++) {
-    if (!pks[c] || (pk->A && (!d_advice_all || !d_advice_all[c]))) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: null argument (circuit %zu)", c);
-    const amdzk_pk* root_c = pks[c]->clone_of ? pks[c]->clone_of : pks[c];
-    const amdzk_pk* root_0 = pk->clone_of ? pk->clone_of : pk;
-    if (root_c != root_0) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: circuit %zu's key is not the first key or a workspace clone of it", c);
-    for (size_t d = 0; d < c; d++)
-      if (pks[d] == pks[c]) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: circuits %zu and %zu share one workspace", d, c);
-  }
-  const size_t n = pk->n;
-  const uint32_t F = pk->F, A = pk->A, I = pk->I, S = pk->S, L = pk->L, ns = pk->nsets, bf = pk->bf;
-  const size_t usable = n - (bf + 1);
-  if (advice_stride < n) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: advice stride < n");
-  const bool use_gwc = (transcript_kind & AMDZK_MULTIOPEN_GWC) != 0;
-  transcript_kind &= ~AMDZK_MULTIOPEN_GWC;
-  zkhost::Blake2bWrite t_blake;
-  zkhost::Keccak256Write t_keccak;
-  if (transcript_kind != AMDZK_TRANSCRIPT_BLAKE2B && transcript_kind != AMDZK_TRANSCRIPT_KECCAK256_EVM)
-    ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: unknown transcript kind %d", transcript_kind);
-  zkhost::TranscriptWrite& T = transcript_kind == AMDZK_TRANSCRIPT_BLAKE2B ? (zkhost::TranscriptWrite&)t_blake : (zkhost::TranscriptWrite&)t_keccak;
-  const bool ttrace = getenv("AMDZK_TRACE_TIME") != nullptr;
-  auto tnow = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double tlast = tnow();
-  auto tick = [&](const char* label) {
-    if (!ttrace) return;
-    zk_host_wait(ctx, ctx->stream);
-    double t = tnow();
-    fprintf(stderr, "[amdzk-time] %-28s %8.3f ms\n", label, t - tlast);
-    tlast = t;
-  };
-  // Lanes: M = the caller's ctx (everything the transcript waits for), B and C = its auxiliary streams (common.hpp).
-  // M carries the chain commitment -> challenge -> next phase; B takes each phase's columns to coefficient form and to
-  // the quotient domain as soon as they are blinded (out of place: the commitments and the next phase's programs keep
-  // reading the Lagrange values); C computes the lookup products beside the permutation products and commits the random
-  // polynomial at the very start. Only the ORDER OF TRANSCRIPT WRITES is upstream's;
-  // the arithmetic between two challenges is unordered there too. With AMDZK_KEYGEN_SERIAL, or while per-kernel
-  // profiling is on, B = C = M and everything below degenerates to one stream.
-  amdzk_ctx *M = ctx, *B = ctx, *C = ctx;
-  if (pk->use_lanes && NC == 1) {  // several instances: one stream (each lane holds one commitment batch's result at a time)
-    ZK_TRY(zk_lane(ctx, 0, &B));
-    ZK_TRY(zk_lane(ctx, 1, &C));
-  }
-  const bool serial = B == M;
-  // latency mode of the commitments (common.hpp): while this proof runs on lanes; the caller's setting comes back at the end
-  struct LatencyMode {
-    amdzk_ctx* c[3];
-    bool keep[3];
-    LatencyMode(amdzk_ctx* m, amdzk_ctx* b, amdzk_ctx* cc, bool on) : c{m, b, cc} {
-      for (int i = 0; i < 3; i++) keep[i] = c[i]->msm_latency_mode, c[i]->msm_latency_mode = on || keep[i];
-    }
-    ~LatencyMode() {
-      for (int i = 0; i < 3; i++) c[i]->msm_latency_mode = keep[i];
-    }
-  } latency_mode(M, B, C, !serial && !(getenv("AMDZK_LATENCY_MODE") && atoi(getenv("AMDZK_LATENCY_MODE")) == 0));
-  auto lane_id = [&](amdzk_ctx* l) { return l == M ? 0 : l == B ? 1 : 2; };
-// a failure on a lane is reported through the caller's ctx
-#define LN_TRY(lane, expr)                                  \
-  do {                                                      \
-    int _lr = (expr);                                       \
-    if (_lr != AMDZK_OK) {                                  \
-      if ((lane) != ctx) ctx->err = (lane)->err;            \
-      return _lr;                                           \
-    }                                                       \
-  } while (0)
-  auto upload_small_on = [&](amdzk_ctx* l, const std::vector<Fr>& v, size_t off_elems) -> int {
-    if (off_elems + v.size() > pk->small_cap) ZK_FAIL(ctx, AMDZK_E_NOMEM, "create_proof: small buffer overflow");
-    LN_TRY(l, h2d_staged(l, pk, pk->small_l[lane_id(l)] + off_elems, v.data(), v.size() * 32));
-    return AMDZK_OK;
-  };
-  auto upload_small = [&](const std::vector<Fr>& v, size_t off_elems) -> int { return upload_small_on(M, v, off_elems); };
-  auto write_points = [&](const std::vector<G1Affine>& pts, const char* label) -> int {
-    for (auto& p : pts) {
-      trace_pt(label, p);
-      if (!T.write_point(p)) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: %s commitment is the identity (cannot write points at infinity to the transcript)", label);
-    }
-    return AMDZK_OK;
-  };
-  // blinding tails: cnt scalars per column (column-major draw order) scattered into rows [row0, row0+cnt), on lane l
-  auto blind_rows = [&](amdzk_ctx* l, Fr* d_cols, uint32_t ncols, size_t row0, uint32_t cnt, const std::vector<Fr>& vals) -> int {
-    ZK_TRY(upload_small_on(l, vals, 0));  // staged through pinned memory: `vals` may die right after
-    LN_TRY(l, zk_scatter_rows(l, d_cols, n, row0, pk->small_l[lane_id(l)], cnt, ncols));
-    return AMDZK_OK;
-  };
-  // A commitment batch begun on a lane and collected when the transcript needs it. On one stream (serial) it is
-  // collected at once: a context holds one batch's result at a time.
-  struct Commit {
-    PendingCommit pc;
-    std::vector<G1Affine> pts;
-    bool begun = false, done = false;
-  };
-  auto commit_end = [&](Commit& c) -> int {
-    if (c.begun && !c.done) LN_TRY(c.pc.ctx, commit_finish(c.pc, c.pts));
-    c.done = true;
-    return AMDZK_OK;
-  };
-  auto commit_begin = [&](amdzk_ctx* l, int basis, const Fr* d_cols, size_t ncols, Commit& c) -> int {
-    LN_TRY(l, commit_launch(l, pk, basis, d_cols, ncols, c.pc));
-    c.begun = true;
-    if (serial) ZK_TRY(commit_end(c));
-    return AMDZK_OK;
-  };
-  // columns [first, first + count) of the arena, blinded on lane `after`: coefficients (PQ) and quotient-domain values (PC) on B
-  // after_l1: the columns' commitment batch has already been launched on `after`; the transforms start behind its
-  // level-1 kernel (both fill the chip: side by side they only stretch each other) and run beside its tail and beside
-  // the next phase's latency-bound kernels instead
-  auto transforms_on_B = [&](amdzk_pk* pk, amdzk_ctx* after, size_t first, size_t count, bool after_l1 = false) -> int {
-    if (!count) return AMDZK_OK;
-    if (after_l1) ZK_TRY(zk_stream_after_l1(B, after));
-    else ZK_TRY(zk_stream_after(B, after));
-    LN_TRY(B, zk_lagrange_to_coeff(B, pk->dom, pk->P + first * n, n, pk->PQ + first * n, n, count));
-    LN_TRY(B, zk_coeff_to_cosets_r261(B, pk->dom, pk->PQ + first * n, n, pk->PC + first * pk->ext, pk->ext, count));
-    return AMDZK_OK;
-  };
-
-  // 0. vk, instances
-  T.common_scalar(pk->transcript_repr);
-  for (size_t ci = 0; ci < NC && I; ci++) {  // columns are zero beyond the caller's values: clear on the device, upload only what was given
-    amdzk_pk* const pk = pks[ci];
-    const uint64_t* const* instances = instances_all ? instances_all[ci] : nullptr;
-    const size_t* instance_lens = instance_lens_all ? instance_lens_all[ci] : nullptr;
-    ZK_HIP(ctx, hipMemsetAsync(pk->inst(), 0, (size_t)I * n * 32, ctx->stream));
-    std::vector<Fr> iv;
-    for (uint32_t c = 0; c < I; c++) {
-      const size_t len = instance_lens ? instance_lens[c] : 0;
-      if (len > usable) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: instance column %u too long (InstanceTooLarge)", c);
-      if (!len) continue;
-      if (!instances || !instances[c]) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: instance column %u is null", c);
-      iv.resize(len);
-      for (size_t i = 0; i < len; i++) {
-        memcpy(iv[i].l, instances[c] + 4 * i, 32);
-        T.common_scalar(iv[i]);
-      }
-      ZK_TRY(h2d_staged(ctx, pk, pk->inst() + (size_t)c * n, iv.data(), len * 32));
-      // without room in the pinned staging area the copy reads `iv` asynchronously: finish it before the next column reuses it
-      if (!pk->pin || len * 32 > pk->pin_cap) ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
-    }
-  }
-  // The random polynomial of the vanishing argument (step 5 below) depends on nothing but the RNG: its n draws follow
-  // all blinding draws, whose number is fixed by the key, so they are taken from that position of the stream now —
-  // generated and committed on lane C while M commits the advice columns.
-  const size_t draws_before_random = NC * ((size_t)A * (bf + 1) + A + (size_t)L * (2 * (bf + 1) + 2) + (size_t)ns * (bf + 1) + (size_t)L * (bf + 1));
-  // With the seeded ChaCha20Rng every Fr::random is one key-stream block, draw j = block ctr0 + j, and WHICH draw blinds
-  // which cell is fixed by the key: the blinding tails are generated on the device straight into their rows
-  // (chacha20_blind_rows, like the random polynomial) and the host only moves its counter past them — it used to draw
-  // ~1,800 scalars per proof at 0.3 us each, a third of them in front of the proof's first kernel. A caller's own
-  // RngCore (pre-drawn scalars) keeps the host path. Draw positions, upstream's order:
-  //   advice of instance c: A (bf + 1) tails, column-major, then A blinds;  then per instance and lookup: bf + 1 tails
-  //   of A', bf + 1 of S', two blinds;  then per instance and permutation set bf tails + a blind;  then per instance and
-  //   lookup product bf tails + a blind;  then the random polynomial.
-  const uint64_t ctr0 = rng.rng ? rng.rng->block_counter() : 0;
-  const size_t per_adv = (size_t)A * (bf + 1) + A, per_lk = (size_t)L * (2 * (bf + 1) + 2), per_pz = (size_t)ns * (bf + 1), per_lz = (size_t)L * (bf + 1);
-  const size_t base_lk = NC * per_adv, base_pz = base_lk + NC * per_lk, base_lz = base_pz + NC * per_pz;
-  auto blind_dev = [&](amdzk_ctx* l, Fr* d_cols, uint32_t ncols, size_t row0, uint32_t cnt, size_t first_draw, uint32_t draw_stride) -> int {
-    LN_TRY(l, zk_chacha20_blind_rows(l, d_cols, n, row0, cnt, ncols, rng.rng->key(), ctr0 + first_draw, draw_stride, zkhost::fr_r3()));
-    return AMDZK_OK;
-  };
-  Commit cm_rnd;
-  std::vector<Commit> cm_zp_all(NC), cm_zl_all(NC);
-  {
-    ZK_TRY(zk_stream_after(C, M));  // the previous proof on this key may still be reading rnd on M's stream
-    if (rng.rng) {
-      // ChaCha20Rng: every draw is one key-stream block, so draw j of the stream is block j: one kernel
-      if (!rng.rng->at_block_boundary()) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: RNG stream not on a block boundary");
-      LN_TRY(C, zk_chacha20_fr_random(C, pk->rnd, n, rng.rng->key(), rng.rng->block_counter() + draws_before_random, zkhost::fr_r3()));
-    } else {  // the caller's own RngCore: its pre-drawn scalars
-      if (draws_before_random + n > rng.count) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: ran out of caller-supplied random scalars");
-      LN_TRY(C, h2d(C, pk->rnd, rng.scalars + 4 * draws_before_random, n * 32));  // the caller's buffer outlives the call
-    }
-    ZK_TRY(commit_begin(C, AMDZK_BASIS_G, pk->rnd, 1, cm_rnd));
-  }
-  // 1. advice: copy in, blind the unusable rows of every column, draw the (unused) blinds, commit
-  for (size_t ci = 0; ci < NC; ci++) {
-    amdzk_pk* const pk = pks[ci];
-    if (A) {
-      ZK_HIP(ctx, hipMemcpy2DAsync(pk->adv(), n * 32, d_advice_all[ci], advice_stride * 32, n * 32, A, hipMemcpyDeviceToDevice, ctx->stream));
-      if (rng.rng) {
-        ZK_TRY(blind_dev(M, pk->adv(), A, usable, bf + 1, ci * per_adv, bf + 1));
-        rng.rng->skip_blocks(per_adv);
-      } else {
-        std::vector<Fr> tail((size_t)A * (bf + 1));
-        for (auto& v : tail) v = rng.fr();
-        for (uint32_t c = 0; c < A; c++) (void)rng.fr();
-        ZK_TRY(blind_rows(M, pk->adv(), A, usable, bf + 1, tail));
-      }
-    }
-    Commit cm;
-    if (A && !serial) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->adv(), A, cm));
-    ZK_TRY(transforms_on_B(pk, M, 0, (size_t)A + I, cm.begun));
-    if (A && !cm.begun) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->adv(), A, cm));
-    ZK_TRY(commit_end(cm));
-    ZK_TRY(write_points(cm.pts, "advice"));
-  }
-  ZK_TRY(commit_end(cm_rnd));  // long done; lane C's MSM workspace is free for the lookup products' commitment
-  tick("advice");
-  Fr theta = T.squeeze_challenge();
-  trace_fr("theta", theta);
-  for (size_t ci = 0; ci < NC; ci++) {
-    amdzk_pk* const pk = pks[ci];
-    pk->consts[pk->c_theta] = theta;
-    ZK_TRY(h2d_staged(ctx, pk, pk->d_consts + pk->c_theta, &pk->consts[pk->c_theta], 32));
-  }
-  // 2. lookups: compress, permute (on the device), blind, commit
-  amdzk_pk* const pk0 = pk;  // the small staging buffers the lambdas above write are the first key's
-  for (size_t ci = 0; ci < NC && L; ci++) {
-    amdzk_pk* const pk = pks[ci];
-    ZK_TRY(run_program(ctx, pk, pk->prog_compress, false, pk->d_outs_compress, nullptr, "expr_lookup_compress"));
-    ZK_TRY(d2d(ctx, pk->la(), pk->ci, (size_t)L * n * 32));
-    ZK_TRY(zk_permute_expression_pairs(ctx, pk->la(), pk->ct, pk->lk_ts, pk->ls(), pk->lk_left, pk->lk_flags, pk->d_err, L, (uint32_t)n,
-                                       (uint32_t)usable, pk->lk_ts_const, pk->lk_const));
-    // the "input not in table" word comes down behind the permutation and is read once the host has waited for this
-    // phase's commitment anyway (it used to be a host wait of its own in the middle of the phase: 0.1 ms of idle device)
-    *pk->h_err = 0;
-    ZK_HIP(ctx, hipMemcpyAsync(pk->h_err, pk->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    tick("  lookup: device permute");
-    // RNG order per lookup: a' tail, s' tail, blind(a'), blind(s')
-    if (rng.rng) {
-      const uint32_t per = 2 * (bf + 1) + 2;
-      ZK_TRY(blind_dev(M, pk->la(), L, usable, bf + 1, base_lk + ci * per_lk, per));
-      ZK_TRY(blind_dev(M, pk->ls(), L, usable, bf + 1, base_lk + ci * per_lk + (bf + 1), per));
-      rng.rng->skip_blocks(per_lk);
-    } else {
-      std::vector<Fr> ta((size_t)L * (bf + 1)), ts((size_t)L * (bf + 1));
-      for (uint32_t l = 0; l < L; l++) {
-        for (uint32_t i = 0; i <= bf; i++) ta[(size_t)l * (bf + 1) + i] = rng.fr();
-        for (uint32_t i = 0; i <= bf; i++) ts[(size_t)l * (bf + 1) + i] = rng.fr();
-        (void)rng.fr();
-        (void)rng.fr();
-      }
-      ZK_TRY(blind_rows(M, pk->la(), L, usable, bf + 1, ta));
-      ZK_TRY(upload_small(ts, ta.size()));
-      ZK_TRY(zk_scatter_rows(ctx, pk->ls(), n, usable, pk0->small + ta.size(), bf + 1, L));
-    }
-    Commit cmc;
-    if (!serial) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->la(), 2 * L, cmc));
-    ZK_TRY(transforms_on_B(pk, M, (size_t)A + I, 2 * (size_t)L, cmc.begun));
-    if (!cmc.begun) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->la(), 2 * L, cmc));
-    ZK_TRY(commit_end(cmc));
-    if (*pk->h_err) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: lookup %d input not in table (ConstraintSystemFailure)", *pk->h_err - 1);
-    const std::vector<G1Affine>& cm = cmc.pts;
-    for (uint32_t l = 0; l < L; l++) {
-      std::vector<G1Affine> two = {cm[l], cm[L + l]};
-      ZK_TRY(write_points(two, "lookup_permuted"));
-    }
-  }
-  tick("lookups_permuted");
-  Fr beta = T.squeeze_challenge();
-  Fr gamma = T.squeeze_challenge();
-  trace_fr("beta", beta);
-  trace_fr("gamma", gamma);
-  // the permutation factors are evaluated as beta (sigma + w) and beta (delta^j X + w) with w = (v + gamma) / beta
-  if (S && beta.is_zero()) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "create_proof: the challenge beta is zero (probability 2^-254): the factored permutation terms need 1 / beta");
-  const Fr beta_inv = inv(beta);
-  for (size_t ci = 0; ci < NC; ci++) {
-    amdzk_pk* const pk = pks[ci];
-    pk->consts[pk->c_beta] = beta;
-    pk->consts[pk->c_gamma] = gamma;
-    pk->consts[pk->c_betainv] = beta_inv;
-    ZK_TRY(h2d_staged(ctx, pk, pk->d_consts + pk->c_beta, &pk->consts[pk->c_beta], (size_t)(pk->consts.size() - pk->c_beta) * 32));
-  }
-  tick("  perm: challenges+consts");
-  // 3. + 4. permutation grand products on M, lookup grand products on C (they depend on beta and gamma only, not on
-  // each other). RNG order: the permutation sets' tails and blinds, then the lookups'.
-  // (Several instances: every instance's permutation products are committed before the first lookup product.)
-  std::vector<std::vector<Fr>> tail_p_all(NC), tail_l_all(NC);
-  if (rng.rng) {
-    rng.rng->skip_blocks(NC * (per_pz + per_lz));  // generated on the device, below
-  } else {
-    for (size_t ci = 0; ci < NC; ci++) {
-      tail_p_all[ci].resize((size_t)ns * bf);
-      for (uint32_t s = 0; s < ns; s++) {
-        for (uint32_t i = 0; i < bf; i++) tail_p_all[ci][(size_t)s * bf + i] = rng.fr();
-        (void)rng.fr();
-      }
-    }
-    for (size_t ci = 0; ci < NC; ci++) {
-      tail_l_all[ci].resize((size_t)L * bf);
-      for (uint32_t l = 0; l < L; l++) {
-        for (uint32_t i = 0; i < bf; i++) tail_l_all[ci][(size_t)l * bf + i] = rng.fr();
-        (void)rng.fr();
-      }
-    }
-  }
-  // 5. vanishing: the random polynomial's n draws and its blind (generated above from this position of the stream)
-  if (rng.rng) rng.rng->skip_blocks(n);
-  else rng.used += n;
-  (void)rng.fr();
-  auto lookup_products = [&](size_t ci, bool ordered_behind_m) -> int {
-    amdzk_pk* const pk = pks[ci];
-    const std::vector<Fr>& tail_l = tail_l_all[ci];
-    Commit& cm_zl = cm_zl_all[ci];
-    if (!ordered_behind_m) ZK_TRY(zk_stream_after(C, M));  // beta, gamma and the permuted columns are in place
-    LN_TRY(C, run_program(C, pk, pk->prog_lfrac, false, pk->d_outs_lfrac, nullptr, "expr_lookup_fractions"));
-    LN_TRY(C, zk_batch_invert(C, pk->frac2, pk->scratch2, (size_t)L * n));
-    LN_TRY(C, zk_mul_elem(C, pk->zl(), pk->frac2, (size_t)L * n));
-    LN_TRY(C, zk_running_product(C, pk->zl(), L, n, n, false, 0, pk->scan_tmp2));
-    if (rng.rng) ZK_TRY(blind_dev(C, pk->zl(), L, n - bf, bf, base_lz + ci * per_lz, bf + 1));
-    else ZK_TRY(blind_rows(C, pk->zl(), L, n - bf, bf, tail_l));
-    // ... and their commitment, enqueued BEFORE the permutation chain: the lookup chain is the shorter one, so its
-    // level-1 kernel runs while M is still in fractions, inversion and scans rather than beside M's own level-1 kernel.
-    // (Measured: 18.8-19.3 ms per proof either way — what one lane gains the other loses; kept for the simpler order.)
-    if (serial) ZK_TRY(transforms_on_B(pk, C, (size_t)A + I + 2 * L + ns, L));
-    ZK_TRY(commit_begin(C, AMDZK_BASIS_G_LAGRANGE, pk->zl(), L, cm_zl));
-    if (!serial) ZK_TRY(transforms_on_B(pk, C, (size_t)A + I + 2 * L + ns, L, true));
-    return AMDZK_OK;
-  };
-  auto perm_products = [&](size_t ci) -> int {  // fractions, inversion, running products, blinding: everything in front of the commitment
-    amdzk_pk* const pk = pks[ci];
-    const std::vector<Fr>& tail_p = tail_p_all[ci];
-    ZK_TRY(run_program(ctx, pk, pk->prog_pfrac, false, pk->d_outs_pfrac, nullptr, "expr_perm_fractions"));
-    tick("  perm: fractions program");
-    ZK_TRY(zk_batch_invert(ctx, pk->frac, pk->scratch, (size_t)ns * n));
-    tick("  perm: batch invert");
-    ZK_TRY(zk_mul_elem(ctx, pk->zp(), pk->frac, (size_t)ns * n));
-    ZK_TRY(zk_running_product(ctx, pk->zp(), ns, n, n, true, usable, pk->scan_tmp));
-    tick("  perm: running product");
-    if (rng.rng) ZK_TRY(blind_dev(M, pk->zp(), ns, n - bf, bf, base_pz + ci * per_pz, bf + 1));
-    else ZK_TRY(blind_rows(M, pk->zp(), ns, n - bf, bf, tail_p));
-    return AMDZK_OK;
-  };
-  auto perm_commit = [&](size_t ci) -> int {
-    amdzk_pk* const pk = pks[ci];
-    if (serial) ZK_TRY(transforms_on_B(pk, M, (size_t)A + I + 2 * L, ns));
-    ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->zp(), ns, cm_zp_all[ci]));
-    return AMDZK_OK;
-  };
-  if (!serial) {
-    // Lanes (one instance): the HOST enqueues M's chain first — seven launches the transcript waits for — and lane C's
-    // lookup products (a dozen launches and a commitment batch's fourteen) while M's fractions and inversion run: the
-    // device used to sit 0.48 ms behind beta / gamma waiting for M's first kernel (profiles/r03zz_timeline_single_proof.txt).
-    if (L) ZK_TRY(zk_stream_after(C, M));  // C starts behind beta, gamma and the permuted columns — NOT behind M's products below
-    if (ns) ZK_TRY(perm_products(0));
-    if (L) ZK_TRY(lookup_products(0, true));
-    if (ns) ZK_TRY(perm_commit(0));
-  } else {
-    for (size_t ci = 0; ci < NC && L; ci++) ZK_TRY(lookup_products(ci, false));
-    for (size_t ci = 0; ci < NC && ns; ci++) {
-      ZK_TRY(perm_products(ci));
-      ZK_TRY(perm_commit(ci));
-    }
-  }
-  if (ns && !serial) ZK_TRY(transforms_on_B(pk, M, (size_t)A + I + 2 * L, ns, true));  // lanes: one instance
-  for (size_t ci = 0; ci < NC; ci++) {
-    ZK_TRY(commit_end(cm_zp_all[ci]));
-    ZK_TRY(write_points(cm_zp_all[ci].pts, "perm_z"));
-  }
-  tick("perm_products");
-  for (size_t ci = 0; ci < NC; ci++) {
-    ZK_TRY(commit_end(cm_zl_all[ci]));
-    ZK_TRY(write_points(cm_zl_all[ci].pts, "lookup_z"));
-  }
-  tick("lookup_products");
-  ZK_TRY(write_points(cm_rnd.pts, "random_poly"));
-  Fr y = T.squeeze_challenge();
-  trace_fr("y", y);
-  for (size_t ci = 0; ci < NC; ci++) {
-    amdzk_pk* const pk = pks[ci];
-    pk->consts[pk->c_y] = y;
-    ZK_TRY(h2d_staged(ctx, pk, pk->d_consts + pk->c_y, &pk->consts[pk->c_y], 32));
-  }
-  // 6. h(X): every committed column is on the quotient domain once lane B has drained
-  ZK_TRY(zk_stream_after(M, B));
-  for (size_t ci = 0; ci < NC; ci++) ZK_TRY(quotient_from_cosets(ctx, pks[ci]));  // theta, beta, gamma, delta powers, y are all known by now
-  if (NC > 1) {
-    // evaluate_h folds the instances' terms in ONE Horner chain with y, instance after instance: with K terms per instance
-    // the numerator is sum_c y^(K (NC - 1 - c)) * numerator_c, and the division by X^n - 1, the interpolation and the cut
-    // into pieces are linear — so the pieces are the same combination of the instances' pieces.
-    std::vector<const Fr*> pp(NC);
-    std::vector<Fr> cf(NC);
-    const Fr yK = pow_u64(y, pk->h_terms);
-    Fr cur = Fr::one();
-    for (size_t ci = NC; ci-- > 0;) {
-      pp[ci] = pks[ci]->hpieces;
-      cf[ci] = cur;
-      cur = mul(cur, yK);
-    }
-    const size_t len = (size_t)pk->qdeg * n;
-    ZK_TRY(h2d_staged(ctx, pk, pk->ptrs, pp.data(), pp.size() * sizeof(Fr*)));
-    ZK_TRY(upload_small(cf, 0));
-    ZK_TRY(zk_lincomb(ctx, (const Fr* const*)pk->ptrs, pk->small, (uint32_t)NC, pk->scratch, len, false));  // scratch holds >= ext >= qdeg * n
-    ZK_TRY(d2d(ctx, pk->hpieces, pk->scratch, len * 32));
-  }
-  {
-    for (uint32_t i = 0; i < pk->qdeg; i++) (void)rng.fr();  // h_blinds
-    std::vector<G1Affine> cm;
-    ZK_TRY(commit_cols(ctx, pk, AMDZK_BASIS_G, pk->hpieces, pk->qdeg, cm));  // consecutive n-blocks
-    ZK_TRY(write_points(cm, "h_piece"));
-  }
-  tick("h_eval+commit");
-  Fr x = T.squeeze_challenge();
-  trace_fr("x", x);
-  Fr xn = pow_u64(x, n);
-  // h_poly = sum_i piece_i * xn^i
-  {
-    std::vector<const Fr*> pp(pk->qdeg);
-    std::vector<Fr> cf(pk->qdeg);
-    Fr cur = Fr::one();
-    for (uint32_t i = 0; i < pk->qdeg; i++) {
-      pp[i] = pk->hpieces + (size_t)i * n;
-      cf[i] = cur;
-      cur = mul(cur, xn);
-    }
-    ZK_TRY(h2d_staged(ctx, pk, pk->ptrs, pp.data(), pp.size() * sizeof(Fr*)));
-    ZK_TRY(upload_small(cf, 0));
-    ZK_TRY(zk_lincomb(ctx, (const Fr* const*)pk->ptrs, pk->small, pk->qdeg, pk->hpoly, n, false));
-  }
-  // 7. evaluations. One list of (polynomial, rotation) in proof order, then the two extra
-  //    evaluations SHPLONK needs (h_poly at x; random at x is already in the list).
-  amdzk_pk::Multiopen& mo = NC == 1 ? pk->mo : pk->mo_multi;
-  if (NC > 1) {  // the cached lists name the polynomials of one particular list of instance keys
-    std::vector<const amdzk_pk*> keys(pks, pks + NC);
-    if (keys != pk->mo_multi_keys) {
-      pk->mo_multi = amdzk_pk::Multiopen();
-      pk->mo_multi_keys = keys;
-    }
-  }
-  if (!mo.built) {
-    auto rot_id = [&](int rot) -> uint32_t {
-      for (size_t i = 0; i < mo.rots.size(); i++)
-        if (mo.rots[i] == rot) return (uint32_t)i;
-      mo.rots.push_back(rot);
-      return (uint32_t)mo.rots.size() - 1;
-    };
-    auto addq = [&](const Fr* p, int rot) {
-      mo.ev.push_back({p, rot});
-      mo.ev_rot.push_back(rot_id(rot));
-    };
-    // written evaluations: advice (instance after instance), fixed, random, sigma, permutation products (instance after
-    // instance), lookups (instance after instance)
-    for (size_t ci = 0; ci < NC; ci++)
-      for (auto& q : pk->advice_queries) addq(pks[ci]->q_adv() + (size_t)q.first * n, q.second);
-    for (auto& q : pk->fixed_queries) addq(pk->fixed_poly + (size_t)q.first * n, q.second);
-    addq(pk->rnd, 0);
-    for (uint32_t i = 0; i < S; i++) addq(pk->sigma_poly + (size_t)i * n, 0);
-    for (size_t ci = 0; ci < NC; ci++)
-      for (uint32_t s = 0; s < ns; s++) {
-        addq(pks[ci]->q_zp() + (size_t)s * n, 0);
-        addq(pks[ci]->q_zp() + (size_t)s * n, 1);
-        if (s + 1 < ns) addq(pks[ci]->q_zp() + (size_t)s * n, -(int)(bf + 1));
-      }
-    for (size_t ci = 0; ci < NC; ci++)
-      for (uint32_t l = 0; l < L; l++) {
-        addq(pks[ci]->q_zl() + (size_t)l * n, 0);
-        addq(pks[ci]->q_zl() + (size_t)l * n, 1);
-        addq(pks[ci]->q_la() + (size_t)l * n, 0);
-        addq(pks[ci]->q_la() + (size_t)l * n, -1);
-        addq(pks[ci]->q_ls() + (size_t)l * n, 0);
-      }
-    mo.n_written = mo.ev.size();
-    addq(pk->hpoly, 0);
-    // 8. multiopen queries in upstream order
-    std::map<std::pair<const Fr*, int>, uint32_t> where;
-    for (size_t i = 0; i < mo.ev.size(); i++) where.emplace(mo.ev[i], (uint32_t)i);
-    bool missing = false;
-    auto addpq = [&](const Fr* p, int rot) {
-      auto it = where.find({p, rot});
-      if (it == where.end()) {
-        missing = true;
-        return;
-      }
-      mo.q_poly.push_back(p);
-      mo.q_rot.push_back(rot_id(rot));
-      mo.q_ev.push_back(it->second);
-    };
-    // per instance: advice queries, the permutation argument's openings, the lookups' openings; then what exists once
-    for (size_t ci = 0; ci < NC; ci++) {
-      amdzk_pk* const pk = pks[ci];
-      for (auto& q : pk->advice_queries) addpq(pk->q_adv() + (size_t)q.first * n, q.second);
-      for (uint32_t s = 0; s < ns; s++) {
-        addpq(pk->q_zp() + (size_t)s * n, 0);
-        addpq(pk->q_zp() + (size_t)s * n, 1);
-      }
-      for (int s = (int)ns - 2; s >= 0; s--) addpq(pk->q_zp() + (size_t)s * n, -(int)(bf + 1));
-      for (uint32_t l = 0; l < L; l++) {
-        addpq(pk->q_zl() + (size_t)l * n, 0);
-        addpq(pk->q_la() + (size_t)l * n, 0);
-        addpq(pk->q_ls() + (size_t)l * n, 0);
-        addpq(pk->q_la() + (size_t)l * n, -1);
-        addpq(pk->q_zl() + (size_t)l * n, 1);
-      }
-    }
-    for (auto& q : pk->fixed_queries) addpq(pk->fixed_poly + (size_t)q.first * n, q.second);
-    for (uint32_t i = 0; i < S; i++) addpq(pk->sigma_poly + (size_t)i * n, 0);
-    addpq(pk->hpoly, 0);
-    addpq(pk->rnd, 0);
-    if (missing) {
-      mo = amdzk_pk::Multiopen();
-      pk->mo_multi_keys.clear();
-      ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: a multiopen query has no evaluation");
-    }
-    // shplonk construct_intermediate_sets, in terms of rotations: the polynomials with their sets of rotations
-    // (first seen first), then the distinct sets with their polynomials (first seen first)
-    std::vector<const Fr*> cr_poly;
-    std::vector<std::vector<std::pair<uint32_t, uint32_t>>> cr_rots;  // (rot id, ev index), ascending rot id
-    std::map<const Fr*, uint32_t> cr_of;
-    for (size_t i = 0; i < mo.q_poly.size(); i++) {
-      auto it = cr_of.find(mo.q_poly[i]);
-      if (it == cr_of.end()) {
-        it = cr_of.emplace(mo.q_poly[i], (uint32_t)cr_poly.size()).first;
-        cr_poly.push_back(mo.q_poly[i]);
-        cr_rots.emplace_back();
-      }
-      auto& v = cr_rots[it->second];
-      const std::pair<uint32_t, uint32_t> e{mo.q_rot[i], mo.q_ev[i]};
-      auto pos = std::lower_bound(v.begin(), v.end(), e, [](const auto& x1, const auto& x2) { return x1.first < x2.first; });
-      if (pos == v.end() || pos->first != e.first) v.insert(pos, e);
-    }
-    for (size_t c = 0; c < cr_poly.size(); c++) {
-      std::vector<uint32_t> ids, evs;
-      for (auto& e : cr_rots[c]) ids.push_back(e.first), evs.push_back(e.second);
-      amdzk_pk::Multiopen::Set* hit = nullptr;
-      for (auto& st : mo.sets)
-        if (st.rot_ids == ids) hit = &st;
-      if (!hit) {
-        mo.sets.emplace_back();
-        hit = &mo.sets.back();
-        hit->rot_ids = ids;
-      }
-      hit->polys.push_back(cr_poly[c]);
-      hit->ev_idx.push_back(evs);
-    }
-    size_t pairs = 0;
-    for (auto& st : mo.sets) pairs += st.rot_ids.size();
-    if (mo.sets.size() > pk->max_sets) {
-      mo = amdzk_pk::Multiopen();
-      ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "create_proof: more than %u rotation sets", pk->max_sets);
-    }
-    if (std::max<size_t>(pairs, 1) > pk->sets_Q_pairs) {
-      ZK_TRY(dalloc(ctx, pk, &pk->sets_Q, std::max<size_t>(pairs, 1) * n));
-      pk->sets_Q_pairs = std::max<size_t>(pairs, 1);
-    }
-    mo.built = true;
-  }
-  // the points x * omega^rot, once per distinct rotation
-  const size_t nrot = mo.rots.size();
-  std::vector<Fr> rot_pt(nrot);
-  std::vector<std::array<uint64_t, 4>> rot_canon(nrot);
-  for (size_t r = 0; r < nrot; r++) {
-    rot_pt[r] = rotate_omega(pk, x, mo.rots[r]);
-    rot_canon[r] = canon(rot_pt[r]);
-  }
-  std::vector<Fr> evals(mo.ev.size());
-  {
-    const size_t nq = mo.ev.size();
-    if (nq > pk->ptrs_cap || 2 * nq > pk->small_cap) ZK_FAIL(ctx, AMDZK_E_NOMEM, "create_proof: too many queries (%zu)", nq);
-    std::vector<const Fr*> pp(nq);
-    std::vector<Fr> pts(nq);
-    for (size_t i = 0; i < nq; i++) pp[i] = mo.ev[i].first, pts[i] = rot_pt[mo.ev_rot[i]];
-    ZK_TRY(h2d_staged(ctx, pk, pk->ptrs, pp.data(), nq * sizeof(Fr*)));
-    ZK_TRY(upload_small(pts, 0));
-    ZK_TRY(zk_poly_eval(ctx, (const Fr* const*)pk->ptrs, pk->small, pk->small + nq, nq, (uint32_t)n));
-    ZK_TRY(d2h(ctx, evals.data(), pk->small + nq, nq * 32));
-    for (size_t i = 0; i < mo.n_written; i++) T.write_scalar(evals[i]);
-  }
-  tick("evals");
-
-  // 9a. GWC (multiopen/gwc/prover.rs [UP]): v <- transcript; queries grouped by point in first-seen order;
-  // per point z:  W_z = (sum_j v^j p_j - sum_j v^j p_j(z)) / (X - z), committed and written in that order.
-  if (use_gwc) {
-    struct PS {
-      std::array<uint64_t, 4> key;
-      Fr z;
-      std::vector<const Fr*> polys;
-      std::vector<Fr> evals;
-    };
-    std::vector<PS> psets;  // one per distinct point (= distinct rotation), first seen first
-    std::vector<int> ps_of_rot(nrot, -1);
-    for (size_t i = 0; i < mo.q_poly.size(); i++) {
-      const uint32_t r = mo.q_rot[i];
-      if (ps_of_rot[r] < 0) {
-        ps_of_rot[r] = (int)psets.size();
-        psets.push_back(PS{rot_canon[r], rot_pt[r], {}, {}});
-      }
-      PS& hit = psets[ps_of_rot[r]];
-      hit.polys.push_back(mo.q_poly[i]);
-      hit.evals.push_back(evals[mo.q_ev[i]]);
-    }
-    const size_t np = psets.size();
-    if (np > 16) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "create_proof: more than 16 opening points");
-    Fr v = T.squeeze_challenge();
-    trace_fr("gwc_v", v);
-    for (size_t i = 0; i < np; i++) {
-      const size_t m = psets[i].polys.size();
-      if (m > pk->ptrs_cap || m + 1 > pk->small_cap) ZK_FAIL(ctx, AMDZK_E_NOMEM, "create_proof: opening set too large");
-      std::vector<Fr> cf(m);
-      Fr cur = Fr::one(), eb = Fr::zero();
-      for (size_t j = 0; j < m; j++) {
-        cf[j] = cur;
-        eb = add(eb, mul(cur, psets[i].evals[j]));
-        cur = mul(cur, v);
-      }
-      std::vector<Fr> low = {eb};
-      Fr* Wi = pk->sets_N + i * n;
-      ZK_TRY(h2d_staged(ctx, pk, pk->ptrs, psets[i].polys.data(), m * sizeof(Fr*)));
-      ZK_TRY(upload_small(cf, 0));
-      ZK_TRY(upload_small(low, m));
-      ZK_TRY(zk_lincomb(ctx, (const Fr* const*)pk->ptrs, pk->small, (uint32_t)m, Wi, n, false));
-      ZK_TRY(zk_sub_low(ctx, Wi, pk->small + m, 1));
-    }
-    std::vector<Fr*> pp(np);
-    std::vector<Fr> roots(np);
-    for (size_t i = 0; i < np; i++) {
-      pp[i] = pk->sets_N + i * n;
-      roots[i] = psets[i].z;
-    }
-    ZK_TRY(h2d_staged(ctx, pk, pk->ptrs, pp.data(), np * sizeof(Fr*)));
-    ZK_TRY(upload_small(roots, 0));
-    ZK_TRY(zk_kate_div(ctx, (Fr* const*)pk->ptrs, pk->small, np, (uint32_t)n));
-    std::vector<G1Affine> cm;
-    ZK_TRY(commit_cols(ctx, pk, AMDZK_BASIS_G, pk->sets_N, np, cm));
-    ZK_TRY(write_points(cm, "gwc_w"));
-  } else
-  // 9b. SHPLONK (multiopen/shplonk/prover.rs [UP])
-  {
-    // construct_intermediate_sets: the sets are the key's (mo.sets); their points, and the super point set, are kept
-    // in ascending order of the canonical field elements as upstream's BTreeSets do
-    const size_t nr = mo.sets.size();
-    if (nr > 16) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "create_proof: more than 16 rotation sets");
-    auto by_point = [&](uint32_t r1, uint32_t r2) { return fr_less_canon(rot_canon[r1], rot_canon[r2]); };
-    std::vector<uint32_t> super(nrot);
-    for (size_t r = 0; r < nrot; r++) super[r] = (uint32_t)r;
-    std::sort(super.begin(), super.end(), by_point);
-    Fr ys = T.squeeze_challenge();
-    Fr v = T.squeeze_challenge();
-    trace_fr("shplonk_y", ys);
-    trace_fr("shplonk_v", v);
-    // Per set i with points p_t (ascending): R_i(X) = sum_j y^j R_ij(X), R_ij the interpolation of polynomial j's
-    // evaluations. Interpolation is linear, so R_i is the interpolation of E_i[t] = sum_j y^j eval_ij[t]:
-    // R_i = sum_t E_i[t] c_it prod_{s != t} (X - p_s), c_it = 1 / prod_{s != t} (p_t - p_s) — one host product per
-    // evaluation instead of one small interpolation per polynomial, and ONE field inversion (batched over all c_it)
-    // instead of one per basis polynomial and point: the host used to spend 0.26 ms here with the GPU idle.
-    std::vector<std::vector<Fr>> set_pts(nr);
-    std::vector<std::vector<uint32_t>> set_order(nr);  // positions in rot_ids, by ascending point
-    std::vector<std::vector<Fr>> set_c(nr);            // c_it
-    {
-      std::vector<Fr> dens;
-      for (size_t i = 0; i < nr; i++) {
-        const amdzk_pk::Multiopen::Set& st = mo.sets[i];
-        const size_t m = st.rot_ids.size();
-        std::vector<uint32_t>& order = set_order[i];
-        order.resize(m);
-        for (size_t t = 0; t < m; t++) order[t] = (uint32_t)t;
-        std::sort(order.begin(), order.end(), [&](uint32_t t1, uint32_t t2) { return by_point(st.rot_ids[t1], st.rot_ids[t2]); });
-        for (size_t t = 0; t < m; t++) set_pts[i].push_back(rot_pt[st.rot_ids[order[t]]]);
-        for (size_t t = 0; t < m; t++) {
-          Fr den = Fr::one();
-          for (size_t s2 = 0; s2 < m; s2++)
-            if (s2 != t) den = mul(den, sub(set_pts[i][t], set_pts[i][s2]));
-          dens.push_back(den);  // non-zero: the points of a set are distinct
-        }
-      }
-      // Montgomery's trick: prefix products, one inversion, walk back
-      std::vector<Fr> pre(dens.size() + 1, Fr::one());
-      for (size_t k2 = 0; k2 < dens.size(); k2++) pre[k2 + 1] = mul(pre[k2], dens[k2]);
-      Fr acc = inv(pre[dens.size()]);
-      std::vector<Fr> dinv(dens.size());
-      for (size_t k2 = dens.size(); k2-- > 0;) {
-        dinv[k2] = mul(acc, pre[k2]);
-        acc = mul(acc, dens[k2]);
-      }
-      size_t at = 0;
-      for (size_t i = 0; i < nr; i++)
-        for (size_t t = 0; t < set_pts[i].size(); t++) set_c[i].push_back(dinv[at++]);
-    }
-    std::vector<std::vector<Fr>> lowsum(nr);  // R_i, coefficients
-    for (size_t i = 0; i < nr; i++) {
-      const amdzk_pk::Multiopen::Set& st = mo.sets[i];
-      const size_t np = set_pts[i].size();
-      std::vector<Fr> E(np, Fr::zero());
-      Fr yp = Fr::one();
-      for (size_t j = 0; j < st.polys.size(); j++) {
-        for (size_t t = 0; t < np; t++) E[t] = add(E[t], mul(yp, evals[st.ev_idx[j][set_order[i][t]]]));
-        yp = mul(yp, ys);
-      }
-      lowsum[i].assign(np, Fr::zero());
-      for (size_t t = 0; t < np; t++) {
-        std::vector<Fr> num(1, Fr::one());  // prod_{s != t} (X - p_s), ascending coefficients
-        for (size_t s2 = 0; s2 < np; s2++) {
-          if (s2 == t) continue;
-          num.push_back(Fr::zero());
-          for (size_t d = num.size() - 1; d > 0; d--) num[d] = sub(num[d - 1], mul(set_pts[i][s2], num[d]));
-          num[0] = neg(mul(set_pts[i][s2], num[0]));
-        }
-        const Fr w = mul(E[t], set_c[i][t]);
-        for (size_t d = 0; d < np; d++) lowsum[i][d] = add(lowsum[i][d], mul(w, num[d]));
-      }
-    }
-    // L_i = sum_j y^j P_ij ; N_i = (L_i - R_i) / prod_t (X - p_t), R_i = sum_j y^j R_ij. The division runs once, not once
-    // per point: 1 / prod_t (X - p_t) = sum_t c_t / (X - p_t) with c_t = 1 / prod_{s != t} (p_t - p_s) (the points of a
-    // set are distinct), and L_i - R_i vanishes at every p_t, so N_i = sum_t c_t Q_it with Q_it = (L_i - R_i) / (X - p_t)
-    // — all (set, point) quotients in ONE division launch, then h(X) = sum_i v^i N_i = sum_it (v^i c_it) Q_it in one
-    // linear combination. Exact arithmetic, same polynomial. The L_i of different sets are independent: one lane each.
-    size_t maxm = 0;
-    for (size_t i = 0; i < nr; i++) maxm = std::max(maxm, set_pts[i].size());
-    std::vector<const Fr*> q_src;
-    std::vector<Fr*> q_dst;
-    std::vector<Fr> q_root, q_low, q_coef;
-    amdzk_ctx* lanes3[3] = {M, B, C};
-    Fr vpow = Fr::one();
-    for (size_t i = 0; i < nr; i++) {
-      const size_t m = mo.sets[i].polys.size(), np = set_pts[i].size();
-      if (m > pk->ptrs_cap || m > pk->small_cap / 2) ZK_FAIL(ctx, AMDZK_E_NOMEM, "create_proof: rotation set too large");
-      std::vector<Fr> cf(m);
-      Fr cur = Fr::one();
-      for (size_t j = 0; j < m; j++) {
-        cf[j] = cur;
-        cur = mul(cur, ys);
-      }
-      amdzk_ctx* ln = lanes3[i % 3];
-      const int li = lane_id(ln);
-      if (ln != M && i < 3) ZK_TRY(zk_stream_after(ln, M));  // the evaluations above came off M; hpoly is in place
-      LN_TRY(ln, h2d_staged(ln, pk, pk->ptrs_l[li], mo.sets[i].polys.data(), m * sizeof(Fr*)));
-      ZK_TRY(upload_small_on(ln, cf, 0));
-      Fr* Li = pk->sets_L + i * n;
-      LN_TRY(ln, zk_lincomb(ln, (const Fr* const*)pk->ptrs_l[li], pk->small_l[li], (uint32_t)m, Li, n, false));
-      for (size_t t = 0; t < np; t++) {
-        q_src.push_back(Li);
-        q_dst.push_back(pk->sets_Q + q_dst.size() * n);
-        q_root.push_back(set_pts[i][t]);
-        q_coef.push_back(mul(vpow, set_c[i][t]));
-        for (size_t d = 0; d < maxm; d++) q_low.push_back(d < np ? lowsum[i][d] : Fr::zero());
-      }
-      vpow = mul(vpow, v);
-    }
-    ZK_TRY(zk_stream_after(M, B));
-    ZK_TRY(zk_stream_after(M, C));
-    {
-      const size_t nq = q_dst.size();
-      if (2 * nq > pk->ptrs_cap || nq * (maxm + 2) > pk->small_cap) ZK_FAIL(ctx, AMDZK_E_NOMEM, "create_proof: too many opening points");
-      void** pt = (void**)pk->ptrs;
-      ZK_TRY(h2d_staged(ctx, pk, pt, q_dst.data(), nq * sizeof(Fr*)));
-      ZK_TRY(h2d_staged(ctx, pk, pt + nq, q_src.data(), nq * sizeof(Fr*)));
-      ZK_TRY(upload_small(q_root, 0));
-      ZK_TRY(upload_small(q_low, nq));
-      ZK_TRY(upload_small(q_coef, nq + q_low.size()));
-      ZK_TRY(zk_kate_div_from(ctx, (Fr* const*)pt, (const Fr* const*)(pt + nq), pk->small, pk->small + nq, (uint32_t)maxm, nq, (uint32_t)n));
-      ZK_TRY(zk_lincomb(ctx, (const Fr* const*)pt, pk->small + nq + q_low.size(), (uint32_t)nq, pk->hx, n, false));
-    }
-    std::vector<G1Affine> cm;
-    ZK_TRY(commit_cols(ctx, pk, AMDZK_BASIS_G, pk->hx, 1, cm));
-    ZK_TRY(write_points(cm, "shplonk_h1"));
-    Fr u = T.squeeze_challenge();
-    trace_fr("u", u);
-    // l(X) = sum_i v^i z_i (L_i - r_i) - zt(u) h(X);  then / (X - u) / z_0 — the factor 1 / z_0 rides in on the coefficients
-    Fr zt = Fr::one();
-    for (uint32_t r : super) zt = mul(zt, sub(u, rot_pt[r]));
-    std::vector<const Fr*> pp(nr + 1);
-    std::vector<Fr> cf(nr + 1);
-    Fr cur = Fr::one(), z0 = Fr::one(), cterm = Fr::zero();
-    for (size_t i = 0; i < nr; i++) {
-      Fr zi = Fr::one();
-      for (uint32_t r : super)
-        if (!std::binary_search(mo.sets[i].rot_ids.begin(), mo.sets[i].rot_ids.end(), r)) zi = mul(zi, sub(u, rot_pt[r]));
-      if (i == 0) z0 = zi;
-      const Fr ri = eval_small(lowsum[i], u);  // R_i(u) = sum_j y^j R_ij(u)
-      Fr w = mul(cur, zi);
-      pp[i] = pk->sets_L + i * n;
-      cf[i] = w;
-      cterm = add(cterm, mul(w, ri));
-      cur = mul(cur, v);
-    }
-    pp[nr] = pk->hx;
-    cf[nr] = neg(zt);
-    const Fr z0inv = inv(z0);
-    for (auto& c : cf) c = mul(c, z0inv);
-    cterm = mul(cterm, z0inv);
-    Fr* lx = pk->sets_Q;  // reuse
-    ZK_TRY(h2d_staged(ctx, pk, pk->ptrs, pp.data(), (nr + 1) * sizeof(Fr*)));
-    ZK_TRY(upload_small(cf, 0));
-    std::vector<Fr> tailv = {cterm, u};
-    ZK_TRY(upload_small(tailv, nr + 1));
-    ZK_TRY(zk_lincomb(ctx, (const Fr* const*)pk->ptrs, pk->small, (uint32_t)(nr + 1), lx, n, false));
-    std::vector<Fr*> one_p = {lx};
-    ZK_TRY(h2d_staged(ctx, pk, (void**)pk->ptrs + nr + 1, one_p.data(), sizeof(Fr*)));
-    ZK_TRY(zk_kate_div_from(ctx, (Fr* const*)((void**)pk->ptrs + nr + 1), nullptr, pk->small + nr + 2, pk->small + nr + 1, 1, 1, (uint32_t)n));
-    ZK_TRY(commit_cols(ctx, pk, AMDZK_BASIS_G, lx, 1, cm));
-    ZK_TRY(write_points(cm, "shplonk_h2"));
-  }
-  tick("multiopen");
-  if (rng.exhausted) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: ran out of caller-supplied random scalars");
-  *proof_len = T.proof.size();
-  if (proof_out) {
-    if (proof_cap < T.proof.size()) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: proof buffer too small (%zu < %zu)", proof_cap, T.proof.size());
-    memcpy(proof_out, T.proof.data(), T.proof.size());
-  }
-  (void)F;
-  return AMDZK_OK;
-#undef LN_TRY
+  return create_proof_impl(ctx, &pk, 1, &instances, &instance_lens, &d_advice, advice_stride, RandomSource(rng_seed), transcript_kind, proof_out,
+                           proof_cap, proof_len);
 }
 
 // One more circuit instance's workspace for `src`'s circuit: a key handle that shares src's key material (fixed and
@@ -2520,10 +2482,8 @@ int amdzk_create_proof_multi(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_circ
   ZK_ENTER(ctx);
   if (!ctx) return AMDZK_E_INVALID;
   if (!pks || n_circuits == 0) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_multi: no circuits");
-  ChaCha20Rng chacha(rng_seed);
-  RandomSource rs;
-  rs.rng = &chacha;
-  return create_proof_impl(ctx, pks, n_circuits, instances, instance_lens, d_advice, advice_stride, rs, transcript_kind, proof_out, proof_cap, proof_len);
+  return create_proof_impl(ctx, pks, n_circuits, instances, instance_lens, d_advice, advice_stride, RandomSource(rng_seed), transcript_kind,
+                           proof_out, proof_cap, proof_len);
 }
 
 // Byte length of the proof amdzk_create_proof_multi writes for n_circuits instances (amdzk_proof_size for one).

@@ -394,10 +394,7 @@ def test_evm_proof_accepted_by_reference_solidity_verifier(ctx, pkg, plonk, orac
         d_adv.free(); pk.free(); params.free()
 
 
-def test_caller_supplied_randomness_equals_seeded_rng(ctx, pkg, plonk, oracle):
-    """amdzk_create_proof_scalars with the scalars a ChaCha20Rng would have drawn gives the same bytes as
-    the seeded entry point (draw count and order = SURVEY.md Appendix A); too few scalars is an error."""
-    c = circuits.lookup_circuit(plonk, 6, seed=9)
+def check_caller_scalars_equal_seeded_rng(ctx, pkg, plonk, oracle, c):
     params, pk, d_adv, inst = setup(ctx, pkg, plonk, oracle, c)
     want = plonk.create_proof(ctx, pk, inst, d_adv, seed=77)
     cnt = plonk.proof_random_count(ctx, pk)
@@ -407,6 +404,20 @@ def test_caller_supplied_randomness_equals_seeded_rng(ctx, pkg, plonk, oracle):
     with pytest.raises(pkg.AmdzkError):
         plonk.create_proof_with_scalars(ctx, pk, inst, d_adv, draws[:-1])
     d_adv.free(); pk.free(); params.free()
+
+
+def test_caller_supplied_randomness_equals_seeded_rng(ctx, pkg, plonk, oracle):
+    """amdzk_create_proof_scalars with the scalars a ChaCha20Rng would have drawn gives the same bytes as
+    the seeded entry point (draw count and order = SURVEY.md Appendix A); too few scalars is an error."""
+    check_caller_scalars_equal_seeded_rng(ctx, pkg, plonk, oracle, circuits.lookup_circuit(plonk, 6, seed=9))
+
+
+def test_caller_supplied_randomness_with_several_permutation_sets(ctx, pkg, plonk, oracle):
+    """The same with several permutation sets and lookups: the blinding draws of every set and every lookup product sit
+    at their own stride in the caller's scalars."""
+    c = circuits.rsa_sha256_shape(plonk, k=7, num_advice=5, num_lookup_advice=2, lookup_bits=5, num_spread=2, spread_bits=3)
+    assert len(c.desc["permutation_columns"]) > c.desc["cs_degree"] - 2 and c.desc["lookups"]
+    check_caller_scalars_equal_seeded_rng(ctx, pkg, plonk, oracle, c)
 
 
 @pytest.mark.parametrize("k,ncirc,transcript", [(7, 2, "blake2b"), (7, 2, "keccak"), (8, 2, "blake2b"), (7, 3, "blake2b")])
