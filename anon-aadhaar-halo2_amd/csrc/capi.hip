@@ -17,6 +17,8 @@ void zk_srs_free(amdzk_ctx*, amdzk_srs* s);
 int zk_msm_dev_xyzz(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const Fr* d_scalars, size_t ncols,
                     size_t len, size_t col_stride, G1X** d_out);
 int zk_msm_finish(amdzk_ctx* ctx, const G1X* d_res, size_t ncols, uint64_t* out_jac);
+int zk_msm_bases_dev_xyzz(amdzk_ctx* ctx, const Fr* d_scalars, size_t ncols, size_t len, size_t col_stride, const G1Affine* d_bases, G1X** d_out);
+int zk_msm_bases_plan_host(size_t ncols, size_t len, uint32_t* window_bits, uint32_t* windows, size_t* scratch_bytes, char why[160]);
 int zk_srs_setup(amdzk_ctx* ctx, uint32_t k, const uint64_t s_mont[4], const uint64_t omega_mont[4], amdzk_srs** out, uint64_t* g_out,
                  uint64_t* g_lagrange_out);
 size_t zk_srs_serialized_size(uint32_t k);
@@ -226,11 +228,11 @@ static std::atomic<bool> g_blocking_note_given{false};
 
 extern "C" {
 
-int amdzk_version(void) { return 1001; }
+int amdzk_version(void) { return 1002; }
 
 // "amdzk <abi> src=<hash of the comment-stripped kernel sources and the Makefile> arch=gfx950": what this binary was built
 // from. bench.py refuses a library whose stamp is not its tree's bench.kernel_src_hash().
-const char* amdzk_build_info(void) { return "amdzk 1001 src=" AMDZK_SRC_HASH " arch=gfx950"; }
+const char* amdzk_build_info(void) { return "amdzk 1002 src=" AMDZK_SRC_HASH " arch=gfx950"; }
 
 int amdzk_init(int device_id, amdzk_ctx** out) {
   if (!out) return AMDZK_E_INVALID;
@@ -488,6 +490,67 @@ int amdzk_msm_g1(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const uint64_t
   ZK_ENTER(ctx);
   const uint64_t* cols[1] = {scalars};
   return amdzk_msm_g1_batch(ctx, srs, basis, cols, 1, len, out_jacobian);
+}
+
+// ---- best_multiexp over the caller's own bases (msm.hip, zk_msm_bases_dev_xyzz): no amdzk_srs, no window table.
+int amdzk_msm_g1_bases_plan(size_t ncols, size_t len, uint32_t* window_bits, uint32_t* windows, size_t* scratch_bytes) {
+  char why[160];
+  return zk_msm_bases_plan_host(ncols, len, window_bits, windows, scratch_bytes, why);
+}
+
+int amdzk_msm_g1_bases_dev(amdzk_ctx* ctx, const void* d_scalars, size_t ncols, size_t len, size_t col_stride, const void* d_bases,
+                           uint64_t* out_jacobian) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  if (!out_jacobian) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm_bases: null output pointer");
+  {  // refused shapes first, so that an empty MSM of a refused shape is refused too
+    char why[160];
+    const int rc = zk_msm_bases_plan_host(ncols, len, nullptr, nullptr, nullptr, why);
+    if (rc != AMDZK_OK) ZK_FAIL(ctx, rc, "%s", why);
+  }
+  if (len == 0) {  // the empty sum: the identity in normal form, as the window-table route returns it
+    for (size_t c = 0; c < ncols; c++) {
+      G1Jac* o = reinterpret_cast<G1Jac*>(out_jacobian + 12 * c);
+      o->x = Fq::zero();
+      o->y = Fq::one();
+      o->z = Fq::zero();
+    }
+    return AMDZK_OK;
+  }
+  if (!d_scalars || !d_bases) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm_bases: null pointer");
+  G1X* d_res = nullptr;
+  ZK_TRY(zk_msm_bases_dev_xyzz(ctx, (const Fr*)d_scalars, ncols, len, col_stride, (const G1Affine*)d_bases, &d_res));
+  return zk_msm_finish(ctx, d_res, ncols, out_jacobian);
+}
+
+int amdzk_msm_g1_bases_batch(amdzk_ctx* ctx, const uint64_t* const* scalars, size_t ncols, const uint64_t* bases, size_t len,
+                             uint64_t* out_jacobian) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  if (!scalars || !out_jacobian || ncols == 0) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm_bases_batch: null pointer or ncols == 0");
+  if (!bases && len) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm_bases_batch: bases is null");
+  {  // a refused shape stages nothing
+    char why[160];
+    const int rc = zk_msm_bases_plan_host(ncols, len, nullptr, nullptr, nullptr, why);
+    if (rc != AMDZK_OK) ZK_FAIL(ctx, rc, "%s", why);
+  }
+  char* d = nullptr;  // scalars[ncols][len] | bases[len]
+  const size_t stride = len ? len : 1;
+  ZK_TRY(zk_ws_reserve(ctx, 2, ncols * stride * sizeof(Fr) + stride * sizeof(G1Affine), (void**)&d));
+  Fr* d_scal = (Fr*)d;
+  G1Affine* d_bases = (G1Affine*)(d + ncols * stride * sizeof(Fr));
+  for (size_t c = 0; c < ncols; c++) {
+    if (!scalars[c] && len) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm_bases_batch: column %zu is null", c);
+    if (len) ZK_HIP(ctx, hipMemcpyAsync(d_scal + c * stride, scalars[c], len * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (len) ZK_HIP(ctx, hipMemcpyAsync(d_bases, bases, len * sizeof(G1Affine), hipMemcpyHostToDevice, ctx->stream));
+  return amdzk_msm_g1_bases_dev(ctx, d_scal, ncols, len, stride, d_bases, out_jacobian);
+}
+
+int amdzk_msm_g1_bases(amdzk_ctx* ctx, const uint64_t* scalars, const uint64_t* bases, size_t len, uint64_t out_jacobian[12]) {
+  ZK_ENTER(ctx);
+  const uint64_t* cols[1] = {scalars};
+  return amdzk_msm_g1_bases_batch(ctx, cols, 1, bases, len, out_jacobian);
 }
 
 int amdzk_ntt_fr_dev(amdzk_ctx* ctx, void* d_a, uint32_t log_n, const uint64_t omega[4], uint32_t flags,

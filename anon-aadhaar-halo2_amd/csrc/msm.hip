@@ -198,6 +198,53 @@ __global__ __launch_bounds__(BIG ? 1024 : MSM_THREADS) void msm_digit_kernel(Dig
   }
 }
 
+// The same counting sort for caller-supplied bases (zk_msm_bases_dev_xyzz): no window table, so every window keeps a
+// bucket set of its own. grid.y = column * W + window is one VIRTUAL column: the workgroup walks the signed digits of its
+// scalars from window 0 (the carry chain decides the digit) and keeps only its window's, as entry `i | neg << 31` — an
+// index into the one copy of the bases. Every scalar is converted W times over the two passes: one product each, against
+// the W mixed additions of 14 products it feeds.
+// A kernel of its own, on purpose: msm_digit_kernel is on every proof's path, and one body shared by both (tried: a
+// __device__ template with a per-digit filter) reordered the instructions of the prover's scatter kernels. Kept apart,
+// msm_digit_kernel compiles to the instructions it had before this kernel existed; a change to one body is a change to both.
+template <int C, bool SCATTER>
+__global__ __launch_bounds__(MSM_THREADS) void msm_digit_win_kernel(DigitArgs a) {
+  extern __shared__ uint32_t lds_cnt[];  // nb counters / cursors
+  constexpr uint32_t W = (255 + C - 1) / C;
+  const uint32_t vcol = blockIdx.y, col = vcol / W, win = vcol % W, blk = blockIdx.x, t = threadIdx.x;
+  uint32_t* gh = a.blk_hist + ((size_t)vcol * a.nblk + blk) * a.nb;
+  if (!SCATTER) {
+    for (uint32_t b = t; b < a.nb; b += MSM_THREADS) lds_cnt[b] = 0;
+  } else {
+    const uint32_t* off = a.off0 + (size_t)vcol * (a.nb + 1);
+    for (uint32_t b = t; b < a.nb; b += MSM_THREADS) lds_cnt[b] = off[b] + gh[b];
+  }
+  __syncthreads();
+  const uint32_t lo_i = blk * a.chunk, hi_i = min(lo_i + a.chunk, a.len);
+  uint32_t* ent = a.entries + (size_t)vcol * a.ecap;
+  for (uint32_t i = lo_i + t; i < hi_i; i += MSM_THREADS) {
+    const uint4* sp = reinterpret_cast<const uint4*>(a.scalars + (size_t)col * a.col_stride + i);
+    uint4 lo = sp[0], hi = sp[1];
+    if ((lo.x | lo.y | lo.z | lo.w | hi.x | hi.y | hi.z | hi.w) == 0) continue;
+    Fr s;
+    s.l[0] = lo.x; s.l[1] = lo.y; s.l[2] = lo.z; s.l[3] = lo.w;
+    s.l[4] = hi.x; s.l[5] = hi.y; s.l[6] = hi.z; s.l[7] = hi.w;
+    Fr canon = fr29_from_mont(s);
+    for_each_digit<C>(canon, [&](uint32_t w, uint32_t b, uint32_t negv) {
+      if (w != win) return;
+      if (!SCATTER) {
+        atomicAdd(&lds_cnt[b], 1u);
+      } else {
+        uint32_t pos = atomicAdd(&lds_cnt[b], 1u);
+        ent[pos] = i | (negv << 31);
+      }
+    });
+  }
+  if (!SCATTER) {
+    __syncthreads();
+    for (uint32_t b = t; b < a.nb; b += MSM_THREADS) gh[b] = lds_cnt[b];
+  }
+}
+
 // Per bucket: turn the per-workgroup counts into per-workgroup start offsets (relative to the
 // bucket's own start) and emit the bucket total.
 __global__ __launch_bounds__(256) void msm_blk_offsets_kernel(uint32_t* blk_hist, uint32_t* cnt, uint32_t nb, uint32_t nblk) {
@@ -839,6 +886,51 @@ int launch_digits(amdzk_ctx* ctx, uint32_t c, const DigitArgs& a, dim3 grid, boo
   return AMDZK_OK;
 }
 
+template <bool SCATTER>
+int launch_digits_win(amdzk_ctx* ctx, uint32_t c, const DigitArgs& a, dim3 grid) {
+  const size_t shmem = (size_t)a.nb * sizeof(uint32_t);
+  const char* nm = SCATTER ? "msm_scatter_win" : "msm_hist_win";
+  switch (c) {
+#define ZK_CASE(CC)                                                                                                                \
+  case CC: {                                                                                                                       \
+    auto kfn = msm_digit_win_kernel<CC, SCATTER>;                                                                                  \
+    if (shmem > 65536) ZK_HIP(ctx, hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); \
+    ZK_LAUNCH(ctx, nm, kfn, grid, dim3(MSM_THREADS), shmem, a);                                                                    \
+  } break;
+    ZK_CASE(8) ZK_CASE(9) ZK_CASE(10) ZK_CASE(11) ZK_CASE(12) ZK_CASE(13) ZK_CASE(14) ZK_CASE(15) ZK_CASE(16)
+#undef ZK_CASE
+    default:
+      ZK_FAIL(ctx, AMDZK_E_INVALID, "msm: window bits %u unsupported", c);
+  }
+  return AMDZK_OK;
+}
+
+// Caller-supplied bases: out[col] = sum_w 2^(c w) win[col][w], Horner from the top window down — c doublings and one
+// addition per window, about 255 dependent doublings per column that no layout removes. One QUAD per column
+// (x29_dbl_quad / x29_add_quad: a lone wavefront issues a dependent instruction every few cycles whatever it is, and the
+// quad forms are 0.4 x the instructions per lane); the kernel is a handful of wavefronts and pure latency. The window
+// sums arrive as msm_fold left them (packed radix 2^256) and the result leaves in the same form for zk_msm_finish.
+__global__ __launch_bounds__(64) void msm_window_combine_kernel(const G1X* win, uint32_t W, uint32_t c, uint32_t ncols, G1X* out) {
+  const uint32_t gtid = blockIdx.x * 64 + threadIdx.x, col = gtid >> 2, role = gtid & 3u;
+  if (col >= ncols) return;  // whole quads leave together
+  G1X29 acc = G1X29::inf();
+#pragma unroll 1
+  for (int w = (int)W - 1; w >= 0; w--) {
+#pragma unroll 1
+    for (uint32_t i = 0; i < c; i++) acc = x29_dbl_quad(acc, role);  // the identity stays the identity
+    const G1X s = ld_x(win + (size_t)col * W + w);
+    G1X29 v = G1X29::inf();
+    if (!s.is_inf()) {
+      v.x = fq29_from_r256(s.x);
+      v.y = fq29_from_r256(s.y);
+      v.zz = fq29_from_r256(s.zz);
+      v.zzz = fq29_from_r256(s.zzz);
+    }
+    acc = x29_add_quad(acc, v, role);
+  }
+  if (role == 0) st_x(out + col, x29_to_r256(acc));
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------- host side
@@ -1262,17 +1354,21 @@ struct MsmGeom {
 // 0.76 -> 8.9 ms per proof, 79.6 -> 72 proofs/s (profiles/r04d_one_fold_level_ab.txt).
 static constexpr int MSM_NLEV = 3;
 
-static MsmGeom msm_geometry(const amdzk_srs* srs, size_t ncols, size_t len, bool latency_mode) {
+// per_window = false: the window-table form (amdzk_srs) — a scalar's W digits all land in ONE bucket set per column.
+// per_window = true: caller-supplied bases (zk_msm_bases_dev_xyzz) — `ncols` counts VIRTUAL columns (column, window), each
+// with one digit per scalar and a bucket set of its own.
+static MsmGeom msm_geometry_cw(uint32_t c, uint32_t W, bool per_window, size_t ncols, size_t len, bool latency_mode) {
   MsmGeom g;
+  const size_t dps = per_window ? 1 : W;  // digits per scalar and (virtual) column
   // latency mode applies to batches of a few columns only (the h pieces, the multiopen argument's two, the random polynomial:
   // the chip is empty behind them); the bucket reduction of a 141-column batch is 2,000 wavefronts and throughput-bound —
   // spending 4 lanes per addition there made a lone proof 0.4 ms SLOWER (profiles/r04h_*)
   static const size_t latency_cols = getenv("AMDZK_LATENCY_COLS") && atoi(getenv("AMDZK_LATENCY_COLS")) > 0 ? (size_t)atoi(getenv("AMDZK_LATENCY_COLS")) : 8;
   g.latency = latency_mode && ncols <= latency_cols;
-  g.c = srs->c;
-  g.W = srs->W;
+  g.c = c;
+  g.W = W;
   g.nb = 1u << (g.c - 1);
-  g.ecap = align_up(len * g.W ? len * g.W : 1, 4);
+  g.ecap = align_up(len * dps ? len * dps : 1, 4);
   // task sizes: level 1 adds T1 table points per thread, levels 2.. fold TL partial sums per thread;
   // all levels use the balanced segmented kernel. Every extra folding level costs a latency-bound launch, so two
   // folding levels; T1 = 12 for the large batches (profiles/r02j_msm_task_size.txt: T1 = 8 / 12 / 16 / 32 / 48 take
@@ -1285,7 +1381,8 @@ static MsmGeom msm_geometry(const amdzk_srs* srs, size_t ncols, size_t len, bool
   if (e_total > (size_t)8 * 262144) g.T1 = 12;
   // one long column (k >= 19): tens of millions of entries keep the chip full whatever the task size, and every partial
   // sum a task leaves behind is one more addition in the folds (profiles/r04a_*: 2^22 points, T1 = 12 / 24 / 32 / 48 / 64: 7.48 / 7.44 / 7.36 / 7.32 / 7.28 ms)
-  if (g.ecap >= ((size_t)1 << 23)) g.T1 = g.ecap >= ((size_t)1 << 25) ? 64 : 32;  // 2^19 points: 1.53 ms with 32, 1.69 with 64; 2^22: 7.33 / 7.14
+  const size_t col_digits = align_up(len * W ? len * W : 1, 4);  // of one column over all its windows (= ecap with a window table)
+  if (col_digits >= ((size_t)1 << 23)) g.T1 = col_digits >= ((size_t)1 << 25) ? 64 : 32;  // 2^19 points: 1.53 ms with 32, 1.69 with 64; 2^22: 7.33 / 7.14
   if (const char* e = getenv("AMDZK_MSM_T1")) g.T1 = (uint32_t)atoi(e) > 0 ? (uint32_t)atoi(e) : g.T1;
   g.TL = 6;  // 4 / 6 / 8 / 12 / 16 prove at the same rate (76.7-78.0 proofs/s); 6 has the shortest proof (profiles/r02j_msm_task_size.txt)
   {
@@ -1298,7 +1395,7 @@ static MsmGeom msm_geometry(const amdzk_srs* srs, size_t ncols, size_t len, bool
     const unsigned top_shift = g.c * (g.W - 1);
     const uint64_t r_top = 0x30644e72e131a029ULL;  // the scalar field's modulus, bits 192..255 (contract.sol:211)
     const double top_digits = top_shift >= 192 && top_shift < 256 ? (double)((r_top >> (top_shift - 192)) + 1) : (double)g.nb;
-    const double fullest = (double)len * g.W / g.nb + (double)len / std::min<double>(top_digits, (double)g.nb);
+    const double fullest = (double)len * dps / g.nb + (double)len / std::min<double>(top_digits, (double)g.nb);
     if (top_digits >= 8)  // two or four such buckets (c = 11, 12) cost 40 us each in the final: not worth wider folds
       while (g.TL < 16 && fullest / g.T1 / ((double)g.TL * g.TL) > 4.5) g.TL++;
   }
@@ -1310,6 +1407,7 @@ static MsmGeom msm_geometry(const amdzk_srs* srs, size_t ncols, size_t len, bool
   // threads when the batch is a few long columns (msm_digit_kernel<.., BIG>: window widths 14-16 only)
   g.big_digits = g.c >= 14 && len >= ((size_t)1 << 18) && ncols * ((len + 65535) / 65536) < 256;
   if (const char* e = getenv("AMDZK_MSM_BIG_DIGITS")) g.big_digits = g.c >= 14 && atoi(e) != 0;
+  if (per_window) g.big_digits = false;  // msm_digit_win_kernel: 256 threads; a batch of W virtual columns is workgroups enough
   const size_t maxblk = g.big_digits ? 256 : 64;
   g.chunk = g.big_digits ? 4096 : 2048;
   while ((len + g.chunk - 1) / g.chunk > maxblk) g.chunk <<= 1;
@@ -1329,9 +1427,14 @@ static MsmGeom msm_geometry(const amdzk_srs* srs, size_t ncols, size_t len, bool
   g.bytes = o;
   return g;
 }
+static MsmGeom msm_geometry(const amdzk_srs* srs, size_t ncols, size_t len, bool latency_mode) {
+  return msm_geometry_cw(srs->c, srs->W, false, ncols, len, latency_mode);
+}
 
-static int msm_group(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const MsmGeom& g, char* ws, const Fr* d_scalars, size_t ncols, size_t len,
-                     size_t col_stride, G1X* outp, hipEvent_t l1_done) {
+// table: what level 1 gathers from (a window table of rows of table_n points, or — per_window — the converted copy of the
+// caller's bases, table_n = 0). per_window: ncols counts virtual columns (column, window) over ncols / g.W scalar columns.
+static int msm_group(amdzk_ctx* ctx, const G1Affine* table, uint32_t table_n, bool per_window, const MsmGeom& g, char* ws, const Fr* d_scalars,
+                     size_t ncols, size_t len, size_t col_stride, G1X* outp, hipEvent_t l1_done) {
   const uint32_t nb = g.nb;
   uint32_t* blk_hist = (uint32_t*)(ws + g.o_bh);
   uint32_t* cnt = (uint32_t*)(ws + g.o_cnt);
@@ -1353,7 +1456,7 @@ static int msm_group(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const MsmG
   da.off0 = off[0];
   da.entries = entries;
   da.ecap = g.ecap;
-  da.table_n = (uint32_t)srs->n;
+  da.table_n = table_n;
   dim3 dgrid(g.nblk, (unsigned)ncols);
   // quad-lane point additions in the folds and the bucket reduction: in latency mode (-1), never (0), always (1: tests)
   static const int tail_quad = getenv("AMDZK_TAIL_QUAD") ? atoi(getenv("AMDZK_TAIL_QUAD")) : -1;
@@ -1361,10 +1464,12 @@ static int msm_group(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const MsmG
   const size_t scan_shmem = (16 + (nb + 1 <= SCAN_LDS_WORDS ? (size_t)nb + 1 : 0)) * sizeof(uint32_t);
   if (scan_shmem > 65536)
     ZK_HIP(ctx, hipFuncSetAttribute((const void*)msm_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((16 + SCAN_LDS_WORDS) * sizeof(uint32_t))));
-  ZK_TRY(launch_digits<false>(ctx, g.c, da, dgrid, g.big_digits));
+  if (per_window) ZK_TRY(launch_digits_win<false>(ctx, g.c, da, dgrid));
+  else ZK_TRY(launch_digits<false>(ctx, g.c, da, dgrid, g.big_digits));
   ZK_LAUNCH(ctx, "msm_blk_offsets", msm_blk_offsets_kernel, dim3((nb + 255) / 256, (unsigned)ncols), dim3(256), 0, blk_hist, cnt, nb, g.nblk);
   ZK_LAUNCH(ctx, "msm_scan", msm_scan_kernel, dim3((unsigned)ncols), dim3(1024), scan_shmem, cnt, off[0], nb, 1u, 1);
-  ZK_TRY(launch_digits<true>(ctx, g.c, da, dgrid, g.big_digits));
+  if (per_window) ZK_TRY(launch_digits_win<true>(ctx, g.c, da, dgrid));
+  else ZK_TRY(launch_digits<true>(ctx, g.c, da, dgrid, g.big_digits));
   for (int l = 1; l <= MSM_NLEV; l++) {
     const uint32_t T = l == 1 ? g.T1 : g.TL;
     ZK_LAUNCH(ctx, "msm_scan", msm_scan_kernel, dim3((unsigned)ncols), dim3(1024), scan_shmem, off[l - 1], off[l], nb, T, 2);
@@ -1375,7 +1480,7 @@ static int msm_group(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const MsmG
     a.T = T;
     a.entries = entries;
     a.ecap = g.ecap;
-    a.table = srs->table[basis];
+    a.table = table;
     a.in_list = list[l - 1];
     a.in_cap = g.cap[l - 1];
     a.out_list = list[l];
@@ -1423,8 +1528,108 @@ int zk_msm_dev_xyzz(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const Fr* d
   ZK_TRY(zk_ws_reserve(ctx, 1, o_out + align_up(ncols * sizeof(G1X), 256), (void**)&ws));
   G1X* outp = (G1X*)(ws + o_out);
   if (!ctx->msm_l1_evt) ZK_HIP(ctx, hipEventCreateWithFlags(&ctx->msm_l1_evt, hipEventDisableTiming));
-  ZK_TRY(msm_group(ctx, srs, basis, g, ws, d_scalars, ncols, len, col_stride, outp, ctx->msm_l1_evt));
+  ZK_TRY(msm_group(ctx, srs->table[basis], (uint32_t)srs->n, false, g, ws, d_scalars, ncols, len, col_stride, outp, ctx->msm_l1_evt));
   ctx->msm_l1_fresh = true;
+  *d_out = outp;
+  return AMDZK_OK;
+}
+
+// ---- caller-supplied bases: arithmetic::best_multiexp(coeffs, bases) without an amdzk_srs.
+// No window table: the classical Pippenger shape — one bucket set per window (virtual column = (column, window), the whole
+// pipeline above with grid.y = ncols * W over ONE converted copy of the bases), then sum_w 2^(c w) S_w
+// (msm_window_combine_kernel). Costs W bucket reductions and ~255 dependent doublings where the table form has one and
+// none; saves the table: (W - 1) (c doublings + one inversion) per point and W x 64 bytes.
+//
+// Window width. By operation count a call costs W (len + a nb) point additions (level 1, plus a ~ 6 per bucket on its
+// way through the folds, the per-bucket final and the row / column sums): 8, 10, 13, 15, 16 bits from 2^10 to 2^22 points.
+// The sweep (2^10 .. 2^22 points, all nine widths: profiles/msm_foreign_bases.txt) did not follow the count, for two
+// reasons it also shows:
+//  * up to 2^18 points the call is latency, not work: msm_window_combine's ~255 dependent doublings (0.6 - 0.8 ms at any
+//    width) and the bucket reduction's chain; fewer windows are fewer virtual columns in that tail;
+//  * from 2^20 the counting sort is W passes over the scalars, each workgroup with 2^(c-1) counters in LDS — one workgroup
+//    per compute unit at c = 16 — and grows faster with c than level 1 shrinks (2^22, c = 13 -> 16: level 1 5.86 -> 4.96 ms, the
+//    whole call 10.3 -> 11.0; the sort is 2.8 ms at c = 13).
+// c = 13 is the fastest width at 2^14 (1.13 ms), 2^16, 2^18, 2^20 (3.36 against 3.51 at c = 15) and 2^22 (10.3 against 10.4
+// at c = 15, 11.0 at c = 16); at 2^10 c = 12 is the fastest (1.24 ms against 1.32 at c = 13). The widths whose TOP window is
+// poorly filled pay for it as predicted: the top window of a 254-bit scalar has (r >> c (W - 1)) + 1 digits — 97 at c = 13, but 4 at c = 9,
+// 12 and 14 and 2 at c = 11 — so its virtual column is two or four buckets of len / 4 entries that msm_accum_final's
+// cooperative path takes one after the other: 0.15 - 0.35 ms in msm_accum_final from 2^14 points at c = 9, 12, 14 (1.0 ms at
+// c = 9 and 2^22), 0.10 - 0.25 at c = 11 (and 0.2 - 0.5 from 2^18 at c = 10 with its 13 digits), 0.03 - 0.05 at c = 13 at every size (msm_geometry's fold-width rule sees to its 97).
+// AMDZK_MSM_BASES_C forces a width 8..16 (sweeps, tests).
+static uint32_t pick_window_bits_bases(size_t len) {
+  if (const char* e = getenv("AMDZK_MSM_BASES_C")) {
+    int v = atoi(e);
+    if (v >= 8 && v <= 16) return (uint32_t)v;
+  }
+  return len < ((size_t)1 << 12) ? 12 : 13;  // measured at 2^10 and 2^14; where between them the cut belongs is not
+}
+
+// THE geometry of a table-free MSM: amdzk_msm_g1_bases_plan reports it, zk_msm_bases_dev_xyzz reserves it.
+struct MsmBasesPlan {
+  MsmGeom g;       // over ncols * W virtual columns
+  size_t vcols;
+  size_t o_win;    // G1X[vcols]: the window sums
+  size_t o_out;    // G1X[ncols]: the results
+  size_t o_bases;  // G1Affine[len]: the bases in radix 2^261
+  size_t bytes;
+};
+// Pure host code. Returns AMDZK_OK or the status of the refusal, with its reason in `why`.
+static int zk_msm_bases_plan(size_t ncols, size_t len, bool latency_mode, MsmBasesPlan* p, char why[160]) {
+  why[0] = 0;
+  if (ncols == 0) {
+    snprintf(why, 160, "msm_bases: ncols == 0");
+    return AMDZK_E_INVALID;
+  }
+  if (len >= ((size_t)1 << 31)) {
+    snprintf(why, 160, "msm_bases: len %zu >= 2^31 (31-bit point ids)", len);
+    return AMDZK_E_UNSUPPORTED;
+  }
+  const uint32_t c = pick_window_bits_bases(len), W = (255 + c - 1) / c;
+  if (ncols > 65535 / W) {
+    snprintf(why, 160, "msm_bases: ncols %zu x %u windows > 65535 (one launch per batch: split the batch)", ncols, W);
+    return AMDZK_E_UNSUPPORTED;
+  }
+  p->vcols = ncols * W;
+  p->g = msm_geometry_cw(c, W, true, p->vcols, len, latency_mode);
+  p->o_win = align_up(p->g.bytes, 256);
+  p->o_out = p->o_win + align_up(p->vcols * sizeof(G1X), 256);
+  p->o_bases = p->o_out + align_up(ncols * sizeof(G1X), 256);
+  p->bytes = p->o_bases + align_up((len ? len : 1) * sizeof(G1Affine), 256);
+  return AMDZK_OK;
+}
+
+int zk_msm_bases_plan_host(size_t ncols, size_t len, uint32_t* window_bits, uint32_t* windows, size_t* scratch_bytes, char why[160]) {
+  MsmBasesPlan p;
+  const int rc = zk_msm_bases_plan(ncols, len, false, &p, why);  // latency mode picks kernels, never sizes
+  if (rc != AMDZK_OK) return rc;
+  if (window_bits) *window_bits = p.g.c;
+  if (windows) *windows = p.g.W;
+  if (scratch_bytes) *scratch_bytes = p.bytes;
+  return AMDZK_OK;
+}
+
+// ncols MSMs of `len` scalars each (column c at d_scalars + c * col_stride) over the `len` affine points at d_bases
+// (radix 2^256 as everywhere on the ABI, (0, 0) = identity, not checked to be on the curve; read only). len > 0.
+// Results (XYZZ) land in d_out[ncols].
+int zk_msm_bases_dev_xyzz(amdzk_ctx* ctx, const Fr* d_scalars, size_t ncols, size_t len, size_t col_stride, const G1Affine* d_bases,
+                          G1X** d_out) {
+  MsmBasesPlan p;
+  char why[160];
+  const int rc = zk_msm_bases_plan(ncols, len, ctx->msm_latency_mode, &p, why);
+  if (rc != AMDZK_OK) ZK_FAIL(ctx, rc, "%s", why);
+  if (!d_scalars || !d_bases || len == 0) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm_bases: null pointer or len == 0");
+  if (ncols > 1 && col_stride < len) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm_bases: col_stride %zu < len %zu", col_stride, len);
+  char* ws = nullptr;
+  ZK_TRY(zk_ws_reserve(ctx, 1, p.bytes, (void**)&ws));
+  G1X *win = (G1X*)(ws + p.o_win), *outp = (G1X*)(ws + p.o_out);
+  G1Affine* bases = (G1Affine*)(ws + p.o_bases);
+  ZK_HIP(ctx, hipMemcpyAsync(bases, d_bases, len * sizeof(G1Affine), hipMemcpyDeviceToDevice, ctx->stream));
+  ZK_LAUNCH(ctx, "msm_bases_to_r261", table_to_r261_kernel, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, bases, len);
+  if (!ctx->msm_l1_evt) ZK_HIP(ctx, hipEventCreateWithFlags(&ctx->msm_l1_evt, hipEventDisableTiming));
+  ZK_TRY(msm_group(ctx, bases, 0, true, p.g, ws, d_scalars, p.vcols, len, col_stride, win, ctx->msm_l1_evt));
+  ctx->msm_l1_fresh = true;
+  ZK_LAUNCH(ctx, "msm_window_combine", msm_window_combine_kernel, dim3((unsigned)((4 * ncols + 63) / 64)), dim3(64), 0, (const G1X*)win, p.g.W,
+            p.g.c, (uint32_t)ncols, outp);
   *d_out = outp;
   return AMDZK_OK;
 }

@@ -61,6 +61,10 @@ def lib():
         "amdzk_msm_g1": (i32, [vp, vp, i32, vp, sz, vp]),
         "amdzk_msm_g1_batch": (i32, [vp, vp, i32, C.POINTER(vp), sz, sz, vp]),
         "amdzk_msm_g1_dev": (i32, [vp, vp, i32, vp, sz, sz, sz, vp]),
+        "amdzk_msm_g1_bases": (i32, [vp, vp, vp, sz, vp]),
+        "amdzk_msm_g1_bases_batch": (i32, [vp, C.POINTER(vp), sz, vp, sz, vp]),
+        "amdzk_msm_g1_bases_dev": (i32, [vp, vp, sz, sz, sz, vp, vp]),
+        "amdzk_msm_g1_bases_plan": (i32, [sz, sz, C.POINTER(u32), C.POINTER(u32), C.POINTER(sz)]),
         "amdzk_ntt_fr": (i32, [vp, vp, u32, vp, u32]),
         "amdzk_ntt_fr_dev": (i32, [vp, vp, u32, vp, u32, sz, sz]),
         "amdzk_fr_from_raw_dev": (i32, [vp, vp, sz]),

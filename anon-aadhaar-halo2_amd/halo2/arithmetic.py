@@ -55,6 +55,58 @@ def best_multiexp_dev(ctx, srs, basis, dbuf, ncols, length, col_stride=None):
     return out
 
 
+def as_g1_array(bases):
+    """(n, 8) uint64 C-contiguous: n G1Affine, x then y, Montgomery limbs; (0, 0) is the identity."""
+    b = np.ascontiguousarray(bases, dtype=np.uint64)
+    if b.ndim == 1:
+        b = b.reshape(-1, 8)
+    assert b.shape[-1] == 8
+    return b
+
+
+def best_multiexp_bases(ctx, coeffs, bases):
+    """arithmetic::best_multiexp(coeffs, bases) over the caller's own points: no ParamsKZG, no window table, any length.
+    Returns the normalised Jacobian point as (12,) uint64."""
+    coeffs, bases = as_fr_array(coeffs), as_g1_array(bases)
+    assert coeffs.shape[0] == bases.shape[0], "best_multiexp: coeffs.len() != bases.len()"
+    out = np.zeros(12, dtype=np.uint64)
+    ctx._chk(ctx.L.amdzk_msm_g1_bases(ctx.h, _ptr(coeffs), _ptr(bases), coeffs.shape[0], _ptr(out)))
+    return out
+
+
+def best_multiexp_bases_batch(ctx, columns, bases):
+    """Several scalar columns over the same caller-supplied bases in one submission: (ncols, 12) uint64."""
+    cols = [as_fr_array(c) for c in columns]
+    bases = as_g1_array(bases)
+    n = bases.shape[0]
+    assert all(c.shape[0] == n for c in cols)
+    ptrs = (C.c_void_p * len(cols))(*[c.ctypes.data for c in cols])
+    out = np.zeros((len(cols), 12), dtype=np.uint64)
+    ctx._chk(ctx.L.amdzk_msm_g1_bases_batch(ctx.h, ptrs, len(cols), _ptr(bases), n, _ptr(out)))
+    return out
+
+
+def best_multiexp_bases_dev(ctx, dbuf, d_bases, ncols, length, col_stride=None):
+    """The same on resident data: `dbuf` holds the scalar columns (column c at c * col_stride elements), `d_bases` the
+    `length` points (read only)."""
+    if col_stride is None:
+        col_stride = length
+    out = np.zeros((ncols, 12), dtype=np.uint64)
+    ctx._chk(ctx.L.amdzk_msm_g1_bases_dev(ctx.h, dbuf.ptr, ncols, length, col_stride, d_bases.ptr, _ptr(out)))
+    return out
+
+
+def multiexp_bases_plan(ncols, length):
+    """amdzk_msm_g1_bases_plan: what best_multiexp_bases* does for this shape, as {"window_bits", "windows", "scratch_bytes"}.
+    Needs no device and no Context; a refused shape raises AmdzkError with the call's status."""
+    from ..ffi import AmdzkError, lib
+    c, w, b = C.c_uint32(), C.c_uint32(), C.c_size_t()
+    rc = lib().amdzk_msm_g1_bases_plan(ncols, length, C.byref(c), C.byref(w), C.byref(b))
+    if rc != 0:
+        raise AmdzkError(rc, "msm_bases_plan: shape (ncols = %d, len = %d) is refused" % (ncols, length))
+    return {"window_bits": c.value, "windows": w.value, "scratch_bytes": b.value}
+
+
 def g_to_lagrange(ctx, g, k):
     """arithmetic::g_to_lagrange(g_projective, k): (n, 8) uint64 affine points in the monomial basis ->
     the Lagrange-basis points (1/n)·FFT_{omega^-1}(g), affine."""

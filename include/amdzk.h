@@ -155,6 +155,32 @@ int amdzk_msm_g1_dev(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const void
                      size_t ncols, size_t len, size_t col_stride,
                      uint64_t* out_jacobian /* host, ncols x 12 */);
 
+/* ---- MSM over the caller's own bases: arithmetic::best_multiexp(coeffs, bases) [UP] wherever the bases are not a resident
+ * ParamsKZG — the verifier's MSMKZG::eval, a commitment under other parameters, a one-off check, any len (no power of
+ * two needed). No amdzk_srs and no window table: one bucket set per window and sum_w 2^(c w) S_w (DESIGN.md §3.1
+ * "Caller-supplied bases"), so nothing is paid per point beyond the MSM itself. Slower per call than amdzk_msm_g1* over a
+ * resident table; far faster than building a table for a few MSMs (INTEGRATION.md says where the routes cross).
+ * bases: len G1Affine (64 B each, (0,0) = identity), any len; not modified. As upstream, points are NOT checked to be on
+ * the curve. One normalised Jacobian point out; len = 0 gives the identity (0, 1, 0).
+ * Refused with a message: null pointers, ncols = 0 (AMDZK_E_INVALID); ncols x windows > 65535, len >= 2^31
+ * (AMDZK_E_UNSUPPORTED). The ctx stays usable. */
+int amdzk_msm_g1_bases(amdzk_ctx* ctx, const uint64_t* scalars, const uint64_t* bases, size_t len,
+                       uint64_t out_jacobian[12]);
+/* ncols scalar columns over the same bases in one submission. */
+int amdzk_msm_g1_bases_batch(amdzk_ctx* ctx, const uint64_t* const* scalars, size_t ncols,
+                             const uint64_t* bases, size_t len, uint64_t* out_jacobian /* ncols x 12 */);
+/* scalars and bases already resident (any device pointer of this GPU): column c at d_scalars + c*col_stride (Fr
+ * elements, col_stride >= len), d_bases: len G1Affine, read only. */
+int amdzk_msm_g1_bases_dev(amdzk_ctx* ctx, const void* d_scalars, size_t ncols, size_t len,
+                           size_t col_stride, const void* d_bases,
+                           uint64_t* out_jacobian /* host, ncols x 12 */);
+/* What the three calls above will do for this shape: window bits, windows = ceil(255 / window bits), and the bytes of
+ * workspace the ctx will hold for it (the copy of the bases included; the host-pointer forms stage scalars and bases in
+ * ncols*len*32 + len*64 bytes more). Pure host code, callable without a device (like amdzk_debug_limb_program); the
+ * same status as the calls for a shape they refuse. Any output pointer may be NULL. */
+int amdzk_msm_g1_bases_plan(size_t ncols, size_t len, uint32_t* window_bits, uint32_t* windows,
+                            size_t* scratch_bytes);
+
 /* ---- NTT: replaces arithmetic::best_fft(a, omega, log_n) [UP] (rows a3, a4).
  * In place, natural order in, natural order out: a[j] <- sum_i a[i] * omega^(i*j). */
 int amdzk_ntt_fr(amdzk_ctx* ctx, uint64_t* a, uint32_t log_n, const uint64_t omega[4],

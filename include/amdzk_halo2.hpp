@@ -570,6 +570,16 @@ class ParamsKZG {
   amdzk_srs* h_ = nullptr;
 };
 
+// arithmetic::best_multiexp(coeffs, bases) over the caller's own points — no ParamsKZG, no window table, any length
+// (amdzk_msm_g1_bases). For bases that serve a few MSMs; a ParamsKZG pays for its table after the number of commitments
+// INTEGRATION.md gives. The result is normalised (z = 1, or the identity (0, 1, 0)).
+inline G1 best_multiexp(const Context& ctx, const std::vector<Fr>& coeffs, const std::vector<G1Affine>& bases) {
+  if (coeffs.size() != bases.size()) throw Error(AMDZK_E_INVALID, "best_multiexp: coeffs.len() != bases.len()");
+  G1 out;
+  ctx.check(amdzk_msm_g1_bases(ctx.get(), (const uint64_t*)coeffs.data(), (const uint64_t*)bases.data(), coeffs.size(), (uint64_t*)&out));
+  return out;
+}
+
 // ------------------------------------------------------------------------------------------ keys and proofs
 // plonk::keygen_vk + keygen_pk: fixed[c] = the 2^k Lagrange values of fixed column c (selectors included).
 class ProvingKey {
