@@ -11,6 +11,7 @@
 
 #include <vector>
 
+#include "../../include/amdzk.h"
 #include "bn254.cuh"
 
 namespace zkhost {
@@ -164,6 +165,38 @@ class TranscriptWrite {
   virtual bool write_point(const bn254::G1Affine& p) = 0;
   virtual void write_scalar(const Fr& s) = 0;
   std::vector<uint8_t> proof;
+  bool failed = false;  // a caller-owned transcript reported an error: the proof ends at the next step boundary
+};
+
+// The caller's own TranscriptWrite (include/amdzk.h, amdzk_transcript): every call is forwarded, no byte is kept here.
+// Only the refusal to write the identity stays on this side.
+class CallbackWrite : public TranscriptWrite {
+ public:
+  explicit CallbackWrite(const amdzk_transcript& t) : t_(t) {}
+  Fr squeeze_challenge() override {
+    Fr c = Fr::zero();
+    if (t_.squeeze_challenge(t_.user, (uint64_t*)c.l) != 0) failed = true;
+    return c;
+  }
+  bool common_point(const bn254::G1Affine& p) override {
+    if (p.is_inf()) return false;
+    if (t_.common_point(t_.user, (const uint64_t*)&p) != 0) failed = true;
+    return true;
+  }
+  void common_scalar(const Fr& s) override {
+    if (t_.common_scalar(t_.user, (const uint64_t*)s.l) != 0) failed = true;
+  }
+  bool write_point(const bn254::G1Affine& p) override {
+    if (p.is_inf()) return false;
+    if (t_.write_point(t_.user, (const uint64_t*)&p) != 0) failed = true;
+    return true;
+  }
+  void write_scalar(const Fr& s) override {
+    if (t_.write_scalar(t_.user, (const uint64_t*)s.l) != 0) failed = true;
+  }
+
+ private:
+  const amdzk_transcript t_;
 };
 
 class Blake2bWrite : public TranscriptWrite {

@@ -60,7 +60,7 @@ int amdzk_fr_from_raw_dev(amdzk_ctx* ctx, void* d_a, size_t n);
 namespace {
 
 // host-format expression words (include/amdzk.h)
-enum : uint32_t { XOP_CONST = 1, XOP_FIXED = 2, XOP_ADVICE = 3, XOP_INSTANCE = 4, XOP_NEG = 5, XOP_ADD = 6, XOP_MUL = 7, XOP_SCALE = 8 };
+enum : uint32_t { XOP_CONST = 1, XOP_FIXED = 2, XOP_ADVICE = 3, XOP_INSTANCE = 4, XOP_NEG = 5, XOP_ADD = 6, XOP_MUL = 7, XOP_SCALE = 8, XOP_CHALLENGE = 9 };
 
 Fr fr_delta() {  // Fr::DELTA = 7^(2^28)  (contract.sol:440)
   Fr r;
@@ -147,6 +147,11 @@ struct amdzk_pk {
   std::vector<std::pair<uint32_t, uint32_t>> lookup_shape;  // (#inputs, #tables); expressions follow the gates in order
   std::vector<Fr> consts;                                   // circuit constants, then the dynamic ones
   uint32_t c_one = 0, c_theta = 0, c_beta = 0, c_gamma = 0, c_y = 0, c_betainv = 0;
+  // Challenge phases (amdzk_keygen_phased): challenge i lives in slot c_chal0 + i of the constant table, refreshed per
+  // proof like theta ... y; nothing made at keygen reads those slots. nphases = 1 and no challenges: a phase-0 key.
+  uint32_t num_challenges = 0, c_chal0 = 0, nphases = 1;
+  std::vector<uint8_t> advice_phase, challenge_phase;
+  bool phased() const { return nphases > 1 || num_challenges > 0; }
   amdzk_domain* dom = nullptr;
   const amdzk_srs* srs = nullptr;
   Fr transcript_repr, omega, omega_inv;
@@ -510,6 +515,11 @@ int emit_expr(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, const std::vector<uint3
         t.push_back(ENode{op, pl, -1, -1});
         st.push_back((int)t.size() - 1);
       } break;
+      case XOP_CHALLENGE:  // one more constant operand: its slot is written per proof, so nothing here may read its value
+        if (pl >= pk->num_challenges) ZK_FAIL(ctx, AMDZK_E_INVALID, "circuit: bad expression word %08x", w);
+        t.push_back(ENode{XOP_CONST, pk->c_chal0 + pl, -1, -1});
+        st.push_back((int)t.size() - 1);
+        break;
       case XOP_NEG:
       case XOP_SCALE:
         if (st.empty()) ZK_FAIL(ctx, AMDZK_E_INVALID, "circuit: malformed expression");
@@ -1055,8 +1065,40 @@ int amdzk_keygen(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* c, c
 
 int amdzk_keygen_ex(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* c, const uint64_t* fixed_values, const uint32_t* perm_mapping,
                     const uint64_t transcript_repr[4], uint32_t flags, amdzk_pk** out) {
+  return amdzk_keygen_phased(ctx, srs, c, nullptr, fixed_values, perm_mapping, transcript_repr, flags, out);
+}
+
+// keygen with ConstraintSystem::{advice_column_in, challenge_usable_after}'s phase table (NULL: every column in phase 0,
+// no challenges). The table is checked the way upstream's two functions assert, before anything is allocated.
+int amdzk_keygen_phased(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* c, const amdzk_phases* ph, const uint64_t* fixed_values,
+                        const uint32_t* perm_mapping, const uint64_t transcript_repr[4], uint32_t flags, amdzk_pk** out) {
   ZK_ENTER(ctx);
   if (!ctx) return AMDZK_E_INVALID;
+  uint32_t nphases = 1;
+  if (ph && c) {
+    if ((c->num_advice && !ph->advice_phase) || (ph->num_challenges && !ph->challenge_phase))
+      ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: phase table has a null array");
+    bool has[3] = {false, false, false};
+    for (uint32_t a = 0; a < c->num_advice; a++) {
+      if (ph->advice_phase[a] > 2) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: advice column %u is in phase %u (phases are 0, 1, 2)", a, ph->advice_phase[a]);
+      has[ph->advice_phase[a]] = true;
+    }
+    for (uint32_t p = 1; p < 3; p++)
+      if (has[p]) {
+        if (!has[p - 1]) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: phase %u has advice columns but phase %u has none", p, p - 1);
+        nphases = p + 1;
+      }
+    for (uint32_t i = 0; i < ph->num_challenges; i++) {
+      const uint32_t p = ph->challenge_phase[i];
+      if (p > 2) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: challenge %u is usable after phase %u (phases are 0, 1, 2)", i, p);
+      if (!has[p]) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: challenge %u is usable after phase %u, which has no advice column", i, p);
+    }
+    if (c->expr_offsets && c->expr_words)
+      for (uint32_t i = 0; i < c->expr_offsets[c->num_exprs]; i++)
+        if ((c->expr_words[i] >> 24) == XOP_CHALLENGE && (c->expr_words[i] & 0xffffffu) >= ph->num_challenges)
+          ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: challenge index %u out of range (num_challenges = %u)", c->expr_words[i] & 0xffffffu,
+                  ph->num_challenges);
+  }
   if (flags & ~(uint32_t)(AMDZK_KEYGEN_FULL_COSETS | AMDZK_KEYGEN_SERIAL)) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: unknown flags %#x", flags);
   if (!srs || !c || !out || !transcript_repr) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: null argument");
   if (c->cs_degree < 3) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: cs_degree %u < 3", c->cs_degree);
@@ -1082,6 +1124,12 @@ int amdzk_keygen_ex(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* c
   pk->chunk = pk->degree - 2;
   pk->nsets = (pk->S + pk->chunk - 1) / pk->chunk;
   pk->qdeg = pk->degree - 1;
+  if (ph) {
+    pk->nphases = nphases;
+    pk->num_challenges = ph->num_challenges;
+    pk->advice_phase.assign(ph->advice_phase, ph->advice_phase + (c->num_advice ? c->num_advice : 0));
+    pk->challenge_phase.assign(ph->challenge_phase, ph->challenge_phase + ph->num_challenges);
+  }
   if (pk->n < pk->bf + 3) {
     amdzk_pk_free(ctx, pk);
     ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: not enough rows (n = %zu, blinding factors = %u)", pk->n, pk->bf);
@@ -1123,7 +1171,8 @@ int amdzk_keygen_ex(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* c
   pk->c_gamma = pk->c_one + 3;
   pk->c_y = pk->c_one + 4;
   pk->c_betainv = pk->c_one + 5;
-  pk->consts.resize(pk->c_betainv + 1, Fr::zero());
+  pk->c_chal0 = pk->c_betainv + 1;
+  pk->consts.resize((size_t)pk->c_chal0 + pk->num_challenges, Fr::zero());
   pk->consts[pk->c_one] = Fr::one();
 
   const size_t n = pk->n, ext = pk->ext;
@@ -1256,7 +1305,7 @@ int amdzk_keygen_ex(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* c
       const uint32_t ni = pk->lookup_shape[l].first, nt = pk->lookup_shape[l].second;
       bool constant = nt == 1;
       if (constant)
-        for (uint32_t w : pk->exprs[e + ni]) constant = constant && (w >> 24) != XOP_ADVICE && (w >> 24) != XOP_INSTANCE;
+        for (uint32_t w : pk->exprs[e + ni]) constant = constant && (w >> 24) != XOP_ADVICE && (w >> 24) != XOP_INSTANCE && (w >> 24) != XOP_CHALLENGE;
       if (!constant) break;
       pk->lk_const++;
       e += ni + nt;
@@ -1564,6 +1613,12 @@ struct DrawLayout {
         per_pz((size_t)pk->nsets * col), per_lz((size_t)pk->L * col), adv(0), lk(NC * per_adv), pz(lk + NC * per_lk),
         lz(pz + NC * per_pz), rnd(lz + NC * per_lz), h(rnd + pk->n + 1), total(h + pk->qdeg) {}
   size_t advice(size_t ci) const { return adv + ci * per_adv; }
+  // A key with challenge phases (upstream loops over cs.phases() outside the loop over the circuits): the advice block is
+  // phase, then instance, then the bf + 1 tails of each of the phase's columns in column order, then one blind per column.
+  // first_in_phase: the columns of phases below p (NC instances each); cols_in_phase: those of p itself.
+  size_t advice_phase(size_t NC, size_t first_in_phase, size_t cols_in_phase, size_t ci) const {
+    return adv + (NC * first_in_phase + ci * cols_in_phase) * (col + 1);
+  }
   size_t lookup(size_t ci) const { return lk + ci * per_lk; }  // the A' tails; the S' tails follow at + col
   size_t perm_product(size_t ci) const { return pz + ci * per_pz; }
   size_t lookup_product(size_t ci) const { return lz + ci * per_lz; }
@@ -1805,6 +1860,8 @@ struct Prover {
   std::vector<Fr> rot_pt, evals;  // the points x * omega^rot, once per distinct rotation; the evaluations
   std::vector<std::array<uint64_t, 4>> rot_canon;
   ShplonkSets sh;
+  amdzk_phase_fn phase_fn = nullptr;  // amdzk_proof_opts: the caller's synthesize of phases >= 1
+  void* phase_user = nullptr;
   const bool ttrace = getenv("AMDZK_TRACE_TIME") != nullptr;
   double tlast;
 
@@ -1935,8 +1992,71 @@ struct Prover {
     else ZK_TRY(on_lane(C, h2d(C, pk->rnd, rng.scalars + 4 * draws.rnd, n * 32)));  // the caller's buffer outlives the call
     return commit_begin(C, AMDZK_BASIS_G, pk->rnd, 1, cm_rnd);
   }
+  // challenge i of a phased key into its slot of every instance's constant table (host copy and device)
+  int put_challenge(uint32_t i, const Fr& v) {
+    for (size_t ci = 0; ci < NC; ci++) {
+      amdzk_pk* const pk = pks[ci];
+      const uint32_t s = pk->c_chal0 + i;
+      pk->consts[s] = v;
+      ZK_TRY(h2d_staged(ctx, pk, pk->d_consts + s, &pk->consts[s], 32));
+    }
+    return AMDZK_OK;
+  }
+  // 1. advice of a key with challenge phases (amdzk_keygen_phased), upstream's order: phase after phase, and inside a phase
+  // instance after instance, the phase's columns (runs of consecutive columns of the arena) are copied in, blinded,
+  // committed and written; then the phase's challenges are squeezed into their constant slots. Phases >= 1 start with the
+  // caller's callback, which fills their columns of d_advice from the challenges so far.
+  int advice_phased(const void* const* d_advice_all, size_t advice_stride) {
+    const uint32_t NCH = pk->num_challenges;
+    std::vector<Fr> chal(NCH, Fr::zero());
+    for (uint32_t i = 0; i < NCH; i++) ZK_TRY(put_challenge(i, chal[i]));  // the last proof's values are gone
+    size_t before = 0;  // advice columns in the phases below p
+    for (uint32_t p = 0; p < pk->nphases; p++) {
+      std::vector<std::pair<uint32_t, uint32_t>> runs;  // (first column, count)
+      size_t in_phase = 0;
+      for (uint32_t c = 0; c < A; c++)
+        if (pk->advice_phase[c] == p) {
+          if (!runs.empty() && runs.back().first + runs.back().second == c) runs.back().second++;
+          else runs.push_back({c, 1});
+          in_phase++;
+        }
+      if (p > 0) {
+        const int r = phase_fn(phase_user, p, (const uint64_t*)chal.data(), NCH, (void*)ctx->stream);
+        if (r != 0) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: the phase callback returned %d in phase %u", r, p);
+      }
+      for (size_t ci = 0; ci < NC; ci++) {
+        amdzk_pk* const pk = pks[ci];
+        size_t j0 = 0;  // position of the run's first column among the phase's columns
+        for (auto& run : runs) {
+          const uint32_t c0 = run.first, cnt = run.second;
+          Fr* const cols = pk->adv() + (size_t)c0 * n;
+          ZK_HIP(ctx, hipMemcpy2DAsync(cols, n * 32, (const Fr*)d_advice_all[ci] + (size_t)c0 * advice_stride, advice_stride * 32, n * 32, cnt,
+                                       hipMemcpyDeviceToDevice, ctx->stream));
+          ZK_TRY(blind(M, cols, cnt, usable, bf + 1, draws.advice_phase(NC, before, in_phase, ci) + j0 * draws.col, draws.col));
+          Commit cm;
+          if (!serial) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, cols, cnt, cm));
+          ZK_TRY(transforms_on_B(pk, M, c0, cnt, cm.begun));
+          if (!cm.begun) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, cols, cnt, cm));
+          ZK_TRY(commit_end(cm));
+          ZK_TRY(write_points(cm.pts, "advice"));
+          j0 += cnt;
+        }
+        if (p == 0) ZK_TRY(transforms_on_B(pk, M, A, I));  // the instance columns ride with the first phase
+      }
+      for (uint32_t i = 0; i < NCH; i++)
+        if (pk->challenge_phase[i] == p) {
+          chal[i] = challenge("phase challenge");
+          ZK_TRY(put_challenge(i, chal[i]));
+        }
+      before += in_phase;
+    }
+    ZK_TRY(commit_end(cm_rnd));
+    tick("advice (phased)");
+    return AMDZK_OK;
+  }
   // 1. advice: copy in, blind the unusable rows of every column, commit
   int advice(const void* const* d_advice_all, size_t advice_stride) {
+    if (pk->phased()) return advice_phased(d_advice_all, advice_stride);
     for (size_t ci = 0; ci < NC; ci++) {
       amdzk_pk* const pk = pks[ci];
       if (A) {
@@ -2263,6 +2383,13 @@ struct Prover {
   }
 };
 
+// What amdzk_create_proof_opts adds to a proof: the caller's transcript and its synthesize of the later phases.
+struct ProofExtras {
+  const amdzk_transcript* transcript = nullptr;
+  amdzk_phase_fn phase_fn = nullptr;
+  void* phase_user = nullptr;
+};
+
 // One proof over NC instances of the circuit (upstream's `circuits: &[C]`, `instances: &[&[&[F]]]`): pks[c] holds
 // instance c's workspace — the key itself for c = 0, workspace clones of it for the others (amdzk_pk_clone_workspace).
 // Upstream's order (plonk/prover.rs [UP]): instances, advice, lookup permutations, permutation products and lookup
@@ -2270,7 +2397,7 @@ struct Prover {
 // evaluations are advice (per circuit), fixed, random, sigma, permutation products (per circuit), lookups (per circuit).
 int create_proof_body(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, const uint64_t* const* const* instances_all,
                       const size_t* const* instance_lens_all, const void* const* d_advice_all, size_t advice_stride, const RandomSource& rng,
-                      int transcript_kind, uint8_t* proof_out, size_t proof_cap, size_t* proof_len) {
+                      int transcript_kind, uint8_t* proof_out, size_t proof_cap, size_t* proof_len, const ProofExtras& ex) {
   amdzk_pk* const pk = pks[0];
   if (!proof_len) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: null argument");
   for (size_t c = 0; c < NC; c++) {
@@ -2282,13 +2409,27 @@ int create_proof_body(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, const uin
       if (pks[d] == pks[c]) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: circuits %zu and %zu share one workspace", d, c);
   }
   if (advice_stride < pk->n) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: advice stride < n");
+  if (pk->nphases > 1 && !ex.phase_fn)
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: the key has advice in %u phases: amdzk_create_proof_opts with a phase callback is needed", pk->nphases);
   const bool use_gwc = (transcript_kind & AMDZK_MULTIOPEN_GWC) != 0;
   transcript_kind &= ~AMDZK_MULTIOPEN_GWC;
   zkhost::Blake2bWrite t_blake;
   zkhost::Keccak256Write t_keccak;
-  if (transcript_kind != AMDZK_TRANSCRIPT_BLAKE2B && transcript_kind != AMDZK_TRANSCRIPT_KECCAK256_EVM)
+  if (!ex.transcript && transcript_kind != AMDZK_TRANSCRIPT_BLAKE2B && transcript_kind != AMDZK_TRANSCRIPT_KECCAK256_EVM)
     ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: unknown transcript kind %d", transcript_kind);
-  zkhost::TranscriptWrite& T = transcript_kind == AMDZK_TRANSCRIPT_BLAKE2B ? (zkhost::TranscriptWrite&)t_blake : (zkhost::TranscriptWrite&)t_keccak;
+  if (ex.transcript && (!ex.transcript->common_point || !ex.transcript->common_scalar || !ex.transcript->write_point ||
+                        !ex.transcript->write_scalar || !ex.transcript->squeeze_challenge))
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: amdzk_transcript has a null member");
+  const amdzk_transcript no_transcript = {};
+  zkhost::CallbackWrite t_caller(ex.transcript ? *ex.transcript : no_transcript);
+  zkhost::TranscriptWrite& T = ex.transcript                                  ? (zkhost::TranscriptWrite&)t_caller
+                               : transcript_kind == AMDZK_TRANSCRIPT_BLAKE2B ? (zkhost::TranscriptWrite&)t_blake
+                                                                             : (zkhost::TranscriptWrite&)t_keccak;
+// a caller-owned transcript that reported an error ends the proof at the next step
+#define T_OK()                                                                                                   \
+  do {                                                                                                           \
+    if (T.failed) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: the caller's transcript reported an error");     \
+  } while (0)
   amdzk_ctx *B = ctx, *C = ctx;  // the lanes (Prover)
   if (pk->use_lanes && NC == 1) {  // several instances: one stream (each lane holds one commitment batch's result at a time)
     ZK_TRY(zk_lane(ctx, 0, &B));
@@ -2308,14 +2449,19 @@ int create_proof_body(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, const uin
   } latency_mode(ctx, B, C, !serial && !(getenv("AMDZK_LATENCY_MODE") && atoi(getenv("AMDZK_LATENCY_MODE")) == 0));
 
   Prover P(ctx, pks, NC, B, C, T, rng);
+  P.phase_fn = ex.phase_fn;
+  P.phase_user = ex.phase_user;
   ZK_TRY(P.instances(instances_all, instance_lens_all));
+  T_OK();
   ZK_TRY(P.random_poly());
   ZK_TRY(P.advice(d_advice_all, advice_stride));
+  T_OK();
   const Fr theta = P.challenge("theta");
   ZK_TRY(P.put_consts({{&amdzk_pk::c_theta, theta}}));
   ZK_TRY(P.lookups());
   const Fr beta = P.challenge("beta");
   const Fr gamma = P.challenge("gamma");
+  T_OK();
   // the permutation factors are evaluated as beta (sigma + w) and beta (delta^j X + w) with w = (v + gamma) / beta
   if (pk->S && beta.is_zero()) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "create_proof: the challenge beta is zero (probability 2^-254): the factored permutation terms need 1 / beta");
   ZK_TRY(P.put_consts({{&amdzk_pk::c_beta, beta}, {&amdzk_pk::c_gamma, gamma}, {&amdzk_pk::c_betainv, inv(beta)}}));
@@ -2323,10 +2469,13 @@ int create_proof_body(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, const uin
   ZK_TRY(P.products());
   ZK_TRY(P.write_points(P.cm_rnd.pts, "random_poly"));  // 5. vanishing: the random polynomial, committed at the start
   const Fr y = P.challenge("y");
+  T_OK();
   ZK_TRY(P.put_consts({{&amdzk_pk::c_y, y}}));
   ZK_TRY(P.vanishing(y));
   const Fr x = P.challenge("x");
+  T_OK();
   ZK_TRY(P.evaluations(x));
+  T_OK();
   if (use_gwc) {
     ZK_TRY(P.gwc(P.challenge("gwc_v")));
   } else {
@@ -2336,6 +2485,8 @@ int create_proof_body(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, const uin
     ZK_TRY(P.shplonk_final(v, P.challenge("u")));
   }
   P.tick("multiopen");
+  T_OK();
+#undef T_OK
   *proof_len = T.proof.size();
   if (proof_out) {
     if (proof_cap < T.proof.size()) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: proof buffer too small (%zu < %zu)", proof_cap, T.proof.size());
@@ -2346,11 +2497,11 @@ int create_proof_body(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, const uin
 
 int create_proof_impl(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t ncirc, const uint64_t* const* const* instances,
                       const size_t* const* instance_lens, const void* const* d_advice, size_t advice_stride, const RandomSource& rng,
-                      int transcript_kind, uint8_t* proof_out, size_t proof_cap, size_t* proof_len) {
+                      int transcript_kind, uint8_t* proof_out, size_t proof_cap, size_t* proof_len, const ProofExtras& ex = ProofExtras()) {
   ZK_ENTER(ctx);
   if (!ctx) return AMDZK_E_INVALID;
   if (!pks || ncirc == 0 || !pks[0]) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: no proving key");
-  const int r = create_proof_body(ctx, pks, ncirc, instances, instance_lens, d_advice, advice_stride, rng, transcript_kind, proof_out, proof_cap, proof_len);
+  const int r = create_proof_body(ctx, pks, ncirc, instances, instance_lens, d_advice, advice_stride, rng, transcript_kind, proof_out, proof_cap, proof_len, ex);
   if (r != AMDZK_OK) {  // a failed proof may have left work on the lanes: the key's workspace must be quiet before it is used again
     const std::string keep = ctx->err;
     (void)zk_sync_all(ctx);
@@ -2486,6 +2637,33 @@ int amdzk_create_proof_multi(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_circ
                            proof_out, proof_cap, proof_len);
 }
 
+// create_proof with everything optional in one struct: the transcript (built-in or the caller's), the callback that
+// synthesizes the later phases of a phased key, the randomness (seed or the caller's scalars).
+int amdzk_create_proof_opts(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_circuits, const uint64_t* const* const* instances,
+                            const size_t* const* instance_lens, const void* const* d_advice, size_t advice_stride, const amdzk_proof_opts* opts,
+                            uint8_t* proof_out, size_t proof_cap, size_t* proof_len) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  if (!pks || n_circuits == 0 || !pks[0]) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_opts: no circuits");
+  if (!opts) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_opts: null options");
+  if (opts->size < sizeof(amdzk_proof_opts))
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_opts: amdzk_proof_opts.size is %zu, this library needs %zu", opts->size, sizeof(amdzk_proof_opts));
+  RandomSource rs;
+  if (opts->scalars) {
+    const size_t need = DrawLayout(pks[0], n_circuits).total;
+    if (opts->scalar_count < need) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_opts: %zu scalars given, %zu needed", opts->scalar_count, need);
+    rs.scalars = opts->scalars;
+  } else {
+    rs = RandomSource(opts->rng_seed);
+  }
+  ProofExtras ex;
+  ex.transcript = opts->transcript;
+  ex.phase_fn = opts->phase_fn;
+  ex.phase_user = opts->phase_user;
+  return create_proof_impl(ctx, pks, n_circuits, instances, instance_lens, d_advice, advice_stride, rs, opts->transcript_kind, proof_out, proof_cap,
+                           proof_len, ex);
+}
+
 // Byte length of the proof amdzk_create_proof_multi writes for n_circuits instances (amdzk_proof_size for one).
 size_t amdzk_proof_size_multi(const amdzk_pk* pk, size_t n_circuits, int format) {
   if (!pk || n_circuits == 0) return 0;
@@ -2525,7 +2703,7 @@ int amdzk_quotient_eval_dev(amdzk_ctx* ctx, amdzk_pk* pk, const void* d_polys, s
 
 // What the last create_proof on this key left in its workspace, for tests that check one stage at a time against the
 // oracle: what = 0 the NP committed polynomials in coefficient form ([NP][n], arena order as above); 1 the
-// challenges theta, beta, gamma, y; 2 the pieces of h(X) ([cs_degree - 1][n]). `out` holds cap Fr elements;
+// challenges theta, beta, gamma, y; 2 the pieces of h(X) ([cs_degree - 1][n]); 3 the phase challenges. `out` holds cap Fr elements;
 // *count = elements available.
 int amdzk_pk_inspect(amdzk_ctx* ctx, const amdzk_pk* pk, int what, uint64_t* out, size_t cap, size_t* count) {
   ZK_ENTER(ctx);
@@ -2546,6 +2724,8 @@ int amdzk_pk_inspect(amdzk_ctx* ctx, const amdzk_pk* pk, int what, uint64_t* out
     ch[2] = pk->consts[pk->c_gamma];
     ch[3] = pk->consts[pk->c_y];
     cnt = 4;
+  } else if (what == 3) {
+    cnt = pk->num_challenges;
   } else {
     ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_inspect: unknown selector %d", what);
   }
@@ -2553,6 +2733,7 @@ int amdzk_pk_inspect(amdzk_ctx* ctx, const amdzk_pk* pk, int what, uint64_t* out
   if (!out) return AMDZK_OK;
   if (cap < cnt) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_inspect: buffer holds %zu elements, %zu needed", cap, cnt);
   if (what == 1) memcpy(out, ch, sizeof(ch));
+  else if (what == 3) memcpy(out, pk->consts.data() + pk->c_chal0, cnt * 32);
   else ZK_TRY(d2h(ctx, out, src, cnt * 32));
   return AMDZK_OK;
 }

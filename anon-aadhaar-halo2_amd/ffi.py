@@ -82,6 +82,7 @@ def lib():
         "amdzk_set_host_wait": (i32, [vp, i32]),
         "amdzk_keygen": (i32, [vp, vp, vp, vp, vp, vp, C.POINTER(vp)]),
         "amdzk_keygen_ex": (i32, [vp, vp, vp, vp, vp, vp, u32, C.POINTER(vp)]),
+        "amdzk_keygen_phased": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, C.POINTER(vp)]),
         "amdzk_pk_free": (None, [vp, vp]),
         "amdzk_pk_commitments": (i32, [vp, vp, vp]),
         "amdzk_create_proof": (i32, [vp, vp, C.POINTER(vp), C.POINTER(sz), vp, sz, C.c_uint64, vp, sz, C.POINTER(sz)]),
@@ -89,6 +90,8 @@ def lib():
         "amdzk_pk_clone_workspace": (i32, [vp, vp, C.POINTER(vp)]),
         "amdzk_create_proof_multi": (i32, [vp, C.POINTER(vp), sz, C.POINTER(C.POINTER(vp)), C.POINTER(C.POINTER(sz)), C.POINTER(vp), sz, C.c_uint64, i32,
                                            vp, sz, C.POINTER(sz)]),
+        "amdzk_create_proof_opts": (i32, [vp, C.POINTER(vp), sz, C.POINTER(C.POINTER(vp)), C.POINTER(C.POINTER(sz)), C.POINTER(vp), sz, vp,
+                                          vp, sz, C.POINTER(sz)]),
         "amdzk_proof_size_multi": (sz, [vp, sz, i32]),
         "amdzk_proof_random_count": (sz, [vp]),
         "amdzk_proof_size": (sz, [vp, i32]),
@@ -119,6 +122,25 @@ def lib():
     L._amdzk_sig = sig
     _LIB = L
     return L
+
+
+# include/amdzk.h: amdzk_phases, amdzk_phase_fn, amdzk_transcript, amdzk_proof_opts
+class Phases(C.Structure):
+    _fields_ = [("num_challenges", C.c_uint32), ("advice_phase", C.c_void_p), ("challenge_phase", C.c_void_p)]
+
+
+PHASE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.c_uint32, C.c_void_p)
+_T_IN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint64))
+
+
+class Transcript(C.Structure):
+    _fields_ = [("user", C.c_void_p), ("common_point", _T_IN), ("common_scalar", _T_IN), ("write_point", _T_IN),
+                ("write_scalar", _T_IN), ("squeeze_challenge", _T_IN)]
+
+
+class ProofOpts(C.Structure):
+    _fields_ = [("size", C.c_size_t), ("transcript_kind", C.c_int), ("transcript", C.POINTER(Transcript)), ("phase_fn", PHASE_FN),
+                ("phase_user", C.c_void_p), ("rng_seed", C.c_uint64), ("scalars", C.c_void_p), ("scalar_count", C.c_size_t)]
 
 
 def build_info():

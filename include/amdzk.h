@@ -228,14 +228,15 @@ int amdzk_divide_by_vanishing_dev(amdzk_ctx* ctx, const amdzk_domain* dom, void*
 
 /* ---- create_proof: replaces plonk::{keygen_pk, create_proof} [UP] for
  * KZGCommitmentScheme<Bn256> + ProverSHPLONK (or ProverGWC, AMDZK_MULTIOPEN_GWC) + Blake2bWrite/Challenge255
- * (or the EVM transcript), one circuit instance (amdzk_create_proof_multi: several),
- * phase-0 advice. The circuit arrives as plain data: what ConstraintSystem holds after
+ * (or the EVM transcript, or the caller's own: amdzk_create_proof_opts), one circuit instance (amdzk_create_proof_multi:
+ * several), advice in up to three challenge phases (amdzk_keygen_phased). The circuit arrives as plain data: what ConstraintSystem holds after
  * Circuit::configure (/root/reference/src/lib.rs:295-326 etc.) and selector compression.
  *
  * Expressions are postfix u32 words, op << 24 | payload:
  *   1 CONST  payload = index into `constants`      2 FIXED / 3 ADVICE / 4 INSTANCE
  *   5 NEG   6 ADD   7 MUL                              payload = column << 8 | (rotation + 128)
  *   8 SCALE  payload = index into `constants` (multiply the top of stack by that constant)
+ *   9 CHALLENGE  payload = challenge index (Expression::Challenge; keys made by amdzk_keygen_phased only)
  * `expr_offsets[e] .. expr_offsets[e+1]` delimits expression e inside `expr_words`. The first
  * num_gates expressions are the gate polynomials in order; then, per lookup l,
  * lookup_shape[2l] input expressions followed by lookup_shape[2l+1] table expressions. */
@@ -272,6 +273,23 @@ int amdzk_keygen(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* circ
 int amdzk_keygen_ex(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* circuit,
                     const uint64_t* fixed_values, const uint32_t* perm_mapping,
                     const uint64_t transcript_repr[4], uint32_t flags, amdzk_pk** out);
+/* ---- challenge phases: ConstraintSystem::{advice_column_in, challenge_usable_after} [UP]. advice_phase[c] is the phase
+ * (0, 1 or 2) of advice column c, challenge_phase[i] the phase after whose commitments challenge i is squeezed; expression
+ * word 9 CHALLENGE names challenge i. As upstream: a phase above 0 needs an advice column in the phase before it, a
+ * challenge's phase needs an advice column, every challenge index is below num_challenges — each violation is
+ * AMDZK_E_INVALID with a message, and the ctx stays usable. phases = NULL is amdzk_keygen_ex (through it and amdzk_keygen a
+ * CHALLENGE word is a bad expression word). A challenge is one more per-proof slot of the key's constant table, beside
+ * theta, beta, gamma and y: nothing derived at keygen depends on its value, and a lookup whose table expression contains
+ * one is compressed and sorted per proof. A table without later phases and without challenges gives exactly the key
+ * amdzk_keygen_ex gives. */
+typedef struct amdzk_phases {
+  uint32_t num_challenges;
+  const uint8_t* advice_phase;    /* num_advice */
+  const uint8_t* challenge_phase; /* num_challenges */
+} amdzk_phases;
+int amdzk_keygen_phased(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* circuit, const amdzk_phases* phases,
+                        const uint64_t* fixed_values, const uint32_t* perm_mapping, const uint64_t transcript_repr[4],
+                        uint32_t flags, amdzk_pk** out);
 void amdzk_pk_free(amdzk_ctx* ctx, amdzk_pk* pk);
 int amdzk_pk_check_affinity(amdzk_ctx* ctx, const amdzk_pk* pk);
 /* VerifyingKey commitments: fixed columns (num_fixed x G1Affine), permutation (num_perm_columns x G1Affine). */
@@ -299,7 +317,7 @@ int amdzk_create_proof_ex(amdzk_ctx* ctx, amdzk_pk* pk, const uint64_t* const* i
                           size_t proof_cap, size_t* proof_len);
 /* ---- several circuit instances in ONE proof: upstream's create_proof(params, pk, &[circuit; N], &[instances; N], rng,
  * transcript) [UP] takes slices; the reference passes one circuit (/root/reference/src/lib.rs:299-300 uses
- * phase 0 only; later phases stay out of scope). Per-circuit steps run circuit after circuit in upstream's order — instance
+ * phase 0 only; later phases: amdzk_keygen_phased + amdzk_create_proof_opts). Per-circuit steps run circuit after circuit in upstream's order — instance
  * values absorbed, advice blinded and committed, lookups permuted, permutation products, lookup products, then the advice /
  * permutation / lookup evaluations and openings — while the challenges, the random polynomial and h(X) exist once (h folds the
  * instances' terms in one chain with y).
@@ -329,6 +347,55 @@ int amdzk_create_proof_scalars(amdzk_ctx* ctx, amdzk_pk* pk, const uint64_t* con
                                size_t advice_stride, const uint64_t* scalars, size_t scalar_count,
                                int transcript_kind, uint8_t* proof_out, size_t proof_cap,
                                size_t* proof_len);
+
+/* ---- create_proof with challenge phases and / or a caller-owned transcript.
+ * Order of a phased proof (upstream's create_proof at the pin): for each phase p = 0, 1, 2 and, inside it, for each
+ * circuit instance: the instance's advice columns of phase p in column-index order get their blinding_factors + 1
+ * blinding tails, one unused blind is drawn per column of the phase, the columns are committed and the commitments
+ * written; after all instances one squeeze_challenge per challenge whose phase is p, in challenge-index order. theta
+ * follows the last phase; everything behind theta is as for any proof. Fr::random draws: the advice block is phase, then
+ * instance, then the phase's column tails, then its blinds; amdzk_proof_random_count and every later block are unchanged.
+ *
+ * amdzk_phase_fn: later-phase witnesses depend on the challenges, so the caller computes them in a callback. It is called
+ * once per phase >= 1 (for all instances together) before the library reads that phase's columns from d_advice; phase-0
+ * columns must be present when the proof starts. challenges: num_challenges x 4 words, Montgomery; those of phases not yet
+ * finished are zero. Work the callback enqueues on hip_stream (the ctx's stream) is ordered before the read; anything
+ * else must be complete when it returns. It may call amdzk_dev_*, amdzk_upload_fence and amdzk_sync on the same ctx, and no
+ * proving function on the same key. A non-zero return ends the proof with AMDZK_E_INVALID (the workspace is left quiet, as
+ * after any failed proof). A key with later phases proved without a callback is refused with a message. */
+typedef int (*amdzk_phase_fn)(void* user, uint32_t phase, const uint64_t* challenges, uint32_t num_challenges, void* hip_stream);
+/* A caller-owned TranscriptWrite (`&mut T: TranscriptWrite` on the other side): the library forwards every call and keeps
+ * no bytes. Scalars are Montgomery Fr (4 words), points G1Affine (8 words), never the identity (the library refuses to write
+ * it, as upstream's transcripts do). Every member returns 0 on success; non-zero ends the proof with AMDZK_E_INVALID.
+ * squeeze_challenge writes a Montgomery Fr below the modulus. */
+typedef struct amdzk_transcript {
+  void* user;
+  int (*common_point)(void* user, const uint64_t xy[8]);
+  int (*common_scalar)(void* user, const uint64_t s[4]);
+  int (*write_point)(void* user, const uint64_t xy[8]);
+  int (*write_scalar)(void* user, const uint64_t s[4]);
+  int (*squeeze_challenge)(void* user, uint64_t out[4]);
+} amdzk_transcript;
+/* size = sizeof(amdzk_proof_opts) as the caller compiled it (a smaller value than the fields below need is refused).
+ * transcript_kind as for amdzk_create_proof_ex; with `transcript` set only its AMDZK_MULTIOPEN_GWC bit counts, proof_out
+ * is unused and *proof_len comes back 0 (the bytes are the caller's). scalars != NULL: the caller's Fr::random draws
+ * (amdzk_create_proof_scalars; scalar_count >= amdzk_proof_random_count(pk) for one instance), else ChaCha20Rng::seed_from_u64(rng_seed). */
+typedef struct amdzk_proof_opts {
+  size_t size;
+  int transcript_kind;
+  const amdzk_transcript* transcript; /* NULL: the built-in transcript transcript_kind names */
+  amdzk_phase_fn phase_fn;            /* NULL: the key must have phase-0 advice only */
+  void* phase_user;
+  uint64_t rng_seed;
+  const uint64_t* scalars;
+  size_t scalar_count;
+} amdzk_proof_opts;
+/* pks / n_circuits / instances / instance_lens / d_advice as for amdzk_create_proof_multi (n_circuits = 1: one key). A key
+ * without later phases and challenges takes exactly the path of amdzk_create_proof_multi and gives its bytes. */
+int amdzk_create_proof_opts(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_circuits,
+                            const uint64_t* const* const* instances, const size_t* const* instance_lens,
+                            const void* const* d_advice, size_t advice_stride, const amdzk_proof_opts* opts,
+                            uint8_t* proof_out, size_t proof_cap, size_t* proof_len);
 
 /* ---- the PLONK layer function by function: the kernels create_proof runs,
  * callable on their own on device-resident columns — for a fork that replaces upstream one function at a time and
@@ -369,8 +436,8 @@ int amdzk_quotient_eval_dev(amdzk_ctx* ctx, amdzk_pk* pk, const void* d_polys, s
                             const uint64_t theta[4], const uint64_t beta[4], const uint64_t gamma[4],
                             const uint64_t y[4], void* d_pieces_out);
 /* What the last create_proof on this key left in its workspace (test hook): what = 0 the NP committed polynomials in
- * coefficient form [NP][n]; 1 the challenges theta, beta, gamma, y; 2 the pieces of h(X) [cs_degree - 1][n].
- * out may be NULL to query *count (in Fr elements). */
+ * coefficient form [NP][n]; 1 the challenges theta, beta, gamma, y; 2 the pieces of h(X) [cs_degree - 1][n]; 3 the
+ * num_challenges phase challenges of the last proof (amdzk_keygen_phased). out may be NULL to query *count (in Fr elements). */
 int amdzk_pk_inspect(amdzk_ctx* ctx, const amdzk_pk* pk, int what, uint64_t* out, size_t cap, size_t* count);
 
 /* Test hooks for the host pass that prepares quotient-domain programs for the limb-resident interpreter (bounds in

@@ -8,6 +8,9 @@
 //   plonk::permutation::keygen::Assembly                           <- region.constrain_equal / copy_advice
 //   poly::kzg::commitment::ParamsKZG {setup, read, write, downsize, commit, commit_lagrange, get_g}
 //   plonk::{keygen_pk -> ProvingKey, create_proof}
+//   plonk::{Challenge, ConstraintSystem::advice_column_in / challenge_usable_after, Expression::Challenge} and
+//   transcript::TranscriptWrite — challenge phases and a caller-owned transcript (amdzk_keygen_phased,
+//   amdzk_create_proof_opts)
 //
 // Header-only over the C ABI of include/amdzk.h (link libamdzk.so); the same names, argument meaning and
 // derived quantities (query order, degree(), blinding_factors()) as upstream. Everything O(n) runs on
@@ -19,7 +22,9 @@
 #define AMDZK_HALO2_HPP
 
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
+#include <exception>
 #include <functional>
 #include <map>
 #include <memory>
@@ -195,14 +200,20 @@ struct Rotation {
 };
 
 // ------------------------------------------------------------------------------------------ Expression
-// plonk::Expression: Constant | Fixed | Advice | Instance | Negated | Sum | Product | Scaled.
+// plonk::Challenge: squeezed once the advice columns of `phase` (and of the phases before it) are committed.
+struct Challenge {
+  uint32_t index;
+  uint8_t phase;
+};
+
+// plonk::Expression: Constant | Fixed | Advice | Instance | Challenge | Negated | Sum | Product | Scaled.
 class Expression {
  public:
-  enum Op : uint32_t { Constant = 1, Fixed = 2, Advice = 3, Instance = 4, Negated = 5, Sum = 6, Product = 7, Scaled = 8 };
+  enum Op : uint32_t { Constant = 1, Fixed = 2, Advice = 3, Instance = 4, Negated = 5, Sum = 6, Product = 7, Scaled = 8, ChallengeOp = 9 };
   struct Node {
     Op op;
     Fr c;               // Constant / Scaled
-    uint32_t column;    // queries
+    uint32_t column;    // queries; the index of a challenge
     int32_t rotation;
     std::shared_ptr<const Node> a, b;
   };
@@ -213,6 +224,7 @@ class Expression {
     Op op = kind == Any::Advice ? Advice : kind == Any::Fixed ? Fixed : Instance;
     return Expression(mk(op, Fr::zero(), column, rot, nullptr, nullptr));
   }
+  static Expression challenge(Challenge ch) { return Expression(mk(ChallengeOp, Fr::zero(), ch.index, 0, nullptr, nullptr)); }
   Expression operator-() const { return Expression(mk(Negated, Fr::zero(), 0, 0, n_, nullptr)); }
   Expression operator+(const Expression& o) const { return Expression(mk(Sum, Fr::zero(), 0, 0, n_, o.n_)); }
   Expression operator-(const Expression& o) const { return *this + (-o); }  // upstream: Sum(a, Negated(b))
@@ -237,7 +249,7 @@ class Expression {
   }
   static uint32_t degree(const Node* n) {
     switch (n->op) {
-      case Constant: return 0;
+      case Constant: case ChallengeOp: return 0;
       case Fixed: case Advice: case Instance: return 1;
       case Negated: case Scaled: return degree(n->a.get());
       case Sum: return std::max(degree(n->a.get()), degree(n->b.get()));
@@ -279,10 +291,35 @@ class ConstraintSystem {
   std::vector<Lookup> lookups;
   std::vector<Column> permutation_columns;
   uint32_t minimum_degree = 0;
+  std::vector<uint8_t> advice_column_phase, challenge_phase;  // per advice column / per challenge
 
-  Column advice_column() {
+  Column advice_column() { return advice_column_in(0); }
+  // ConstraintSystem::advice_column_in: phases are 0, 1, 2; a phase above 0 needs a column in the phase before it.
+  Column advice_column_in(uint32_t phase) {
+    if (phase > 2) throw Error(AMDZK_E_INVALID, "advice_column_in: phase " + std::to_string(phase) + " (phases are 0, 1, 2)");
+    if (phase > 0 && !phase_has_advice(phase - 1))
+      throw Error(AMDZK_E_INVALID, "advice_column_in: no advice column in phase " + std::to_string(phase - 1) + ", the one before phase " +
+                                       std::to_string(phase));
     num_advice_queries.push_back(0);
+    advice_column_phase.push_back((uint8_t)phase);
     return {Any::Advice, num_advice++};
+  }
+  // ConstraintSystem::challenge_usable_after: the phase must already have an advice column.
+  Challenge challenge_usable_after(uint32_t phase) {
+    if (phase > 2 || !phase_has_advice(phase)) throw Error(AMDZK_E_INVALID, "challenge_usable_after: no advice column in phase " + std::to_string(phase));
+    challenge_phase.push_back((uint8_t)phase);
+    return {(uint32_t)challenge_phase.size() - 1, (uint8_t)phase};
+  }
+  bool phase_has_advice(uint32_t phase) const {
+    for (uint8_t p : advice_column_phase)
+      if (p == phase) return true;
+    return false;
+  }
+  // later phases or challenges: the key goes through amdzk_keygen_phased, the proof needs a synthesize callback
+  bool phased() const {
+    for (uint8_t p : advice_column_phase)
+      if (p) return true;
+    return !challenge_phase.empty();
   }
   Column fixed_column() { return {Any::Fixed, num_fixed++}; }
   Column selector() { return fixed_column(); }
@@ -370,8 +407,14 @@ struct CircuitData {
   std::vector<uint32_t> lookup_shape, expr_offsets, expr_words, perm_columns;
   std::vector<uint64_t> constants;  // 4 limbs each, Montgomery
   amdzk_circuit c;
+  std::vector<uint8_t> advice_phase, challenge_phase;
+  amdzk_phases phases;  // amdzk_keygen_phased's table (use it when `phased`)
+  bool phased;
 
-  CircuitData(const ConstraintSystem& cs, uint32_t k) {
+  CircuitData(const ConstraintSystem& cs, uint32_t k) : advice_phase(cs.advice_column_phase), challenge_phase(cs.challenge_phase), phased(cs.phased()) {
+    phases.num_challenges = (uint32_t)challenge_phase.size();
+    phases.advice_phase = advice_phase.data();
+    phases.challenge_phase = challenge_phase.data();
     auto put = [](std::vector<int32_t>& dst, const std::vector<ConstraintSystem::Query>& qs) {
       for (auto& q : qs) {
         dst.push_back((int32_t)q.first.index);
@@ -442,6 +485,9 @@ struct CircuitData {
       case Expression::Fixed: case Expression::Advice: case Expression::Instance:
         if (n->rotation < -128 || n->rotation > 127 || n->column >= (1u << 16)) throw Error(AMDZK_E_UNSUPPORTED, "query out of encodable range");
         expr_words.push_back(((uint32_t)n->op << 24) | (n->column << 8) | (uint32_t)(n->rotation + 128));
+        break;
+      case Expression::ChallengeOp:
+        expr_words.push_back((9u << 24) | n->column);
         break;
       case Expression::Negated:
         emit(n->a.get());
@@ -600,7 +646,14 @@ class ProvingKey {
     CircuitData cd(cs, k_);
     const uint64_t* fx = flat.empty() ? nullptr : (const uint64_t*)flat.data();
     const uint32_t* mp = num_perm_ ? assembly.mapping() : nullptr;
-    if (flags == kEnvDefaults) ctx_.check(amdzk_keygen(ctx_.get(), params.handle(), &cd.c, fx, mp, transcript_repr.l, &h_));
+    if (cd.phased) {
+      uint32_t f = flags;
+      if (flags == kEnvDefaults) {  // as amdzk_keygen reads them
+        const char *fc = std::getenv("AMDZK_FULL_COSETS"), *se = std::getenv("AMDZK_SERIAL");
+        f = (fc && (std::atoi(fc) != 0 || !*fc) ? AMDZK_KEYGEN_FULL_COSETS : 0u) | (se && std::atoi(se) != 0 ? AMDZK_KEYGEN_SERIAL : 0u);
+      }
+      ctx_.check(amdzk_keygen_phased(ctx_.get(), params.handle(), &cd.c, &cd.phases, fx, mp, transcript_repr.l, f, &h_));
+    } else if (flags == kEnvDefaults) ctx_.check(amdzk_keygen(ctx_.get(), params.handle(), &cd.c, fx, mp, transcript_repr.l, &h_));
     else ctx_.check(amdzk_keygen_ex(ctx_.get(), params.handle(), &cd.c, fx, mp, transcript_repr.l, flags, &h_));
   }
   ~ProvingKey() {
@@ -688,6 +741,104 @@ inline std::vector<uint8_t> create_proof(const Context& ctx, const std::vector<c
   std::vector<uint8_t> proof(amdzk_proof_size_multi(pks[0], N, format));
   ctx.check(amdzk_create_proof_multi(ctx.get(), pks.data(), N, pp.data(), lp.data(), d_advice.data(), advice_stride, rng_seed, format, proof.data(),
                                      proof.size(), &need));
+  proof.resize(need);
+  return proof;
+}
+
+// transcript::TranscriptWrite as far as create_proof uses it: implement it to own the transcript (`&mut T:
+// TranscriptWrite` upstream). Values are Montgomery; a point is never the identity. Throwing from a member ends the
+// proof: the exception is rethrown by create_proof once the library has returned.
+class TranscriptWrite {
+ public:
+  virtual ~TranscriptWrite() {}
+  virtual void common_point(const G1Affine& p) = 0;
+  virtual void common_scalar(const Fr& s) = 0;
+  virtual void write_point(const G1Affine& p) = 0;
+  virtual void write_scalar(const Fr& s) = 0;
+  virtual Fr squeeze_challenge() = 0;
+};
+
+// What `synthesize` of a circuit with challenge phases is here: called once per phase >= 1 with the challenges known so
+// far (index order; those of unfinished phases are zero), it fills that phase's advice columns of every instance on the
+// device — work on `hip_stream` is ordered before the library's read, anything else must be complete on return.
+using Synthesize = std::function<void(uint32_t phase, const std::vector<Fr>& challenges, void* hip_stream)>;
+
+namespace detail {
+// what the C callbacks of amdzk_create_proof_opts get as `user`: nothing may unwind through the library, so the first
+// exception is kept and rethrown by create_proof
+struct Trampoline {
+  const Synthesize* syn;
+  TranscriptWrite* t;
+  std::exception_ptr err;
+  template <class F>
+  int guard(F&& f) {
+    try {
+      f();
+      return 0;
+    } catch (...) {
+      if (!err) err = std::current_exception();
+      return 1;
+    }
+  }
+};
+}  // namespace detail
+
+// plonk::create_proof for circuits with challenge phases and / or the caller's own transcript (amdzk_create_proof_opts).
+// keys / instances / d_advice as for the multi-circuit overload (one entry each for one circuit). With `transcript_obj`
+// the bytes are the caller's and the result is empty; `transcript` then only selects nothing and `multiopen` still counts.
+inline std::vector<uint8_t> create_proof(const Context& ctx, const std::vector<const ProvingKey*>& keys,
+                                         const std::vector<std::vector<std::vector<Fr>>>& instances, const std::vector<const void*>& d_advice,
+                                         size_t advice_stride, uint64_t rng_seed, const Synthesize& synthesize,
+                                         TranscriptWrite* transcript_obj = nullptr, Transcript transcript = Transcript::Blake2b,
+                                         Multiopen multiopen = Multiopen::Shplonk) {
+  const size_t N = keys.size();
+  if (N == 0 || instances.size() != N || d_advice.size() != N) throw Error(AMDZK_E_INVALID, "create_proof: one key, instance set and witness per circuit");
+  detail::Trampoline tr{&synthesize, transcript_obj, nullptr};
+  amdzk_transcript ct;
+  ct.user = &tr;
+  ct.common_point = [](void* u, const uint64_t* xy) { auto* t = (detail::Trampoline*)u; return t->guard([&] { G1Affine p; std::memcpy(&p, xy, 64); t->t->common_point(p); }); };
+  ct.common_scalar = [](void* u, const uint64_t* s) { auto* t = (detail::Trampoline*)u; return t->guard([&] { Fr v; std::memcpy(v.l, s, 32); t->t->common_scalar(v); }); };
+  ct.write_point = [](void* u, const uint64_t* xy) { auto* t = (detail::Trampoline*)u; return t->guard([&] { G1Affine p; std::memcpy(&p, xy, 64); t->t->write_point(p); }); };
+  ct.write_scalar = [](void* u, const uint64_t* s) { auto* t = (detail::Trampoline*)u; return t->guard([&] { Fr v; std::memcpy(v.l, s, 32); t->t->write_scalar(v); }); };
+  ct.squeeze_challenge = [](void* u, uint64_t* out) { auto* t = (detail::Trampoline*)u; return t->guard([&] { Fr v = t->t->squeeze_challenge(); std::memcpy(out, v.l, 32); }); };
+  amdzk_proof_opts opts;
+  std::memset(&opts, 0, sizeof(opts));
+  opts.size = sizeof(opts);
+  opts.transcript_kind = (int)transcript | (int)multiopen;
+  opts.transcript = transcript_obj ? &ct : nullptr;
+  opts.phase_user = &tr;
+  if (synthesize)
+    opts.phase_fn = [](void* u, uint32_t phase, const uint64_t* ch, uint32_t nch, void* stream) {
+      auto* t = (detail::Trampoline*)u;
+      return t->guard([&] {
+        std::vector<Fr> v(nch);
+        if (nch) std::memcpy((void*)v.data(), ch, (size_t)nch * 32);
+        (*t->syn)(phase, v, stream);
+      });
+    };
+  opts.rng_seed = rng_seed;
+  std::vector<amdzk_pk*> pks(N);
+  std::vector<std::vector<const uint64_t*>> ptrs(N);
+  std::vector<std::vector<size_t>> lens(N);
+  std::vector<const uint64_t* const*> pp(N);
+  std::vector<const size_t*> lp(N);
+  for (size_t c = 0; c < N; c++) {
+    pks[c] = keys[c]->handle();
+    ptrs[c].assign(std::max<size_t>(1, instances[c].size()), nullptr);
+    lens[c].assign(std::max<size_t>(1, instances[c].size()), 0);
+    for (size_t i = 0; i < instances[c].size(); i++) {
+      ptrs[c][i] = instances[c][i].empty() ? nullptr : (const uint64_t*)instances[c][i].data();
+      lens[c][i] = instances[c][i].size();
+    }
+    pp[c] = ptrs[c].data();
+    lp[c] = lens[c].data();
+  }
+  size_t need = 0;
+  std::vector<uint8_t> proof(transcript_obj ? 0 : amdzk_proof_size_multi(pks[0], N, opts.transcript_kind));
+  const int rc = amdzk_create_proof_opts(ctx.get(), pks.data(), N, pp.data(), lp.data(), d_advice.data(), advice_stride, &opts, proof.data(),
+                                         proof.size(), &need);
+  if (rc != AMDZK_OK && tr.err) std::rethrow_exception(tr.err);
+  ctx.check(rc);
   proof.resize(need);
   return proof;
 }

@@ -13,7 +13,12 @@ HEADER = os.path.join(ROOT, "include", "amdzk.h")
 DOC = os.path.join(ROOT, "INTEGRATION.md")
 BEGIN, END = "<!-- BEGIN GENERATED FFI (tools/gen_rust_ffi.py) -->", "<!-- END GENERATED FFI -->"
 
-OPAQUE = {"amdzk_ctx": "Ctx", "amdzk_srs": "Srs", "amdzk_domain": "Domain", "amdzk_pk": "Pk", "amdzk_circuit": "AmdzkCircuit"}
+OPAQUE = {"amdzk_ctx": "Ctx", "amdzk_srs": "Srs", "amdzk_domain": "Domain", "amdzk_pk": "Pk", "amdzk_circuit": "AmdzkCircuit",
+          "amdzk_phases": "AmdzkPhases", "amdzk_transcript": "AmdzkTranscript", "amdzk_proof_opts": "AmdzkProofOpts",
+          "amdzk_phase_fn": "AmdzkPhaseFn"}
+# structs and function-pointer types of the header that the block spells out as #[repr(C)] Rust (amdzk_circuit's
+# counterpart is written by hand in INTEGRATION.md, beside the code that fills it)
+GENERATED_TYPES = ("amdzk_phases", "amdzk_transcript", "amdzk_proof_opts")
 SCALAR = {"int": "c_int", "uint32_t": "u32", "int32_t": "i32", "uint64_t": "u64", "size_t": "usize", "uint8_t": "u8", "float": "f32",
           "double": "f64", "char": "c_char", "void": "c_void"}
 
@@ -54,6 +59,59 @@ def rust_type(ctype):
     return out
 
 
+def uncomment(text):
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    return re.sub(r"//[^\n]*", " ", text)
+
+
+def params(text):
+    """`void* user, const uint64_t xy[8]` -> [(name, rust type)]; unnamed parameters get a0, a1, ..."""
+    args = []
+    text = text.strip()
+    if not text or text == "void":
+        return args
+    for i, p in enumerate(text.split(",")):
+        p = p.strip()
+        arr = re.search(r"\[\s*\d*\s*\]$", p)
+        if arr:
+            p = p[:arr.start()].strip()
+        mm = re.match(r"^(.*?[\s\*])(\w+)$", p)
+        ctype, pname = (mm.group(1).strip(), mm.group(2)) if mm and mm.group(2) not in SCALAR else (p, "a%d" % i)
+        if arr:
+            ctype += "*"
+        args.append((pname if pname not in ("in", "type", "fn") else pname + "_", rust_type(ctype)))
+    return args
+
+
+def fn_pointer(ret, args):
+    return "Option<unsafe extern \"C\" fn(%s)%s>" % (", ".join("%s: %s" % a for a in params(args)), "" if ret == "void" else " -> " + rust_type(ret))
+
+
+def types():
+    """The #[repr(C)] structs and function-pointer aliases: [(rust name, [lines])]."""
+    text = uncomment(open(HEADER).read())
+    out = []
+    for m in re.finditer(r"typedef\s+(\w[\w\s\*]*?)\(\s*\*\s*(amdzk_\w+)\s*\)\s*\((.*?)\)\s*;", text, flags=re.S):
+        out.append((m.start(), ["pub type %s = %s;" % (OPAQUE[m.group(2)], fn_pointer(m.group(1).strip(), " ".join(m.group(3).split())))]))
+    for m in re.finditer(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*\w+\s*;", text, flags=re.S):
+        if m.group(1) not in GENERATED_TYPES:
+            continue
+        lines = ["#[repr(C)]", "pub struct %s {" % OPAQUE[m.group(1)]]
+        for field in m.group(2).split(";"):
+            field = " ".join(field.split())
+            if not field:
+                continue
+            fp = re.match(r"^(.*?)\(\s*\*\s*(\w+)\s*\)\s*\((.*)\)$", field)
+            if fp:
+                lines.append("    pub %s: %s," % (fp.group(2), fn_pointer(fp.group(1).strip(), fp.group(3))))
+            else:
+                (name, rt), = params(field)
+                lines.append("    pub %s: %s," % (name, rt))
+        lines.append("}")
+        out.append((m.start(), lines))
+    return [lines for _, lines in sorted(out)]
+
+
 def functions():
     text = strip(open(HEADER).read())
     out = []
@@ -80,7 +138,10 @@ def functions():
 
 
 def block():
-    lines = ["extern \"C\" {"]
+    lines = []
+    for t in types():
+        lines += t
+    lines.append("extern \"C\" {")
     for name, args, ret in functions():
         sig = "    pub fn %s(%s)%s;" % (name, ", ".join("%s: %s" % a for a in args), " -> " + ret if ret else "")
         if len(sig) > 150:  # wrap long signatures at argument boundaries
