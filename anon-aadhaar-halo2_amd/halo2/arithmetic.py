@@ -28,6 +28,26 @@ def best_fft_dev(ctx, dbuf, omega, log_n, ncols=1, col_stride=None, flags=0):
     ctx._chk(ctx.L.amdzk_ntt_fr_dev(ctx.h, dbuf.ptr, log_n, _ptr(omega), flags, ncols, col_stride))
 
 
+def best_fft_batch(ctx, columns, omega, log_n, flags=0):
+    """Several host columns of 1 << log_n in one submission (amdzk_ntt_fr_batch), each transformed in place; returns them."""
+    cols = [as_fr_array(c) for c in columns]
+    assert all(c.shape[0] == 1 << log_n for c in cols), "best_fft_batch: a.len() != 1 << log_n"
+    omega = np.ascontiguousarray(omega, dtype=np.uint64).reshape(4)
+    ptrs = (C.c_void_p * max(1, len(cols)))(*[c.ctypes.data for c in cols])
+    ctx._chk(ctx.L.amdzk_ntt_fr_batch(ctx.h, ptrs, len(cols), log_n, _ptr(omega), flags))
+    return cols
+
+
+def fr_from_raw_dev(ctx, dbuf, n):
+    """Fr::from_raw on n resident elements in place (amdzk_fr_from_raw_dev): canonical 4 x u64 below r -> Montgomery."""
+    ctx._chk(ctx.L.amdzk_fr_from_raw_dev(ctx.h, dbuf.ptr if dbuf is not None else None, n))
+
+
+def fr_to_repr_dev(ctx, dbuf, n):
+    """Fr::to_repr on n resident elements in place (amdzk_fr_to_repr_dev): Montgomery -> canonical 4 x u64."""
+    ctx._chk(ctx.L.amdzk_fr_to_repr_dev(ctx.h, dbuf.ptr if dbuf is not None else None, n))
+
+
 def best_multiexp(ctx, srs, basis, coeffs):
     """arithmetic::best_multiexp(coeffs, bases) with bases = srs.{g|g_lagrange}[..len].
     Returns the normalised Jacobian point as (12,) uint64 (x, y, z=1 | identity (0,1,0))."""

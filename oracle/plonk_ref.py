@@ -559,36 +559,10 @@ def create_proof_multi(pk, instances_list, advice_list, seed, trace=None, transc
     y = T.squeeze_challenge()
     tr("y", y)
     # quotient: evaluate every constraint of every circuit on the extended coset, fold with y, divide by Z_H
-    ext = d.extended_len()
-    rot_scale = 1 << (d.extended_k - d.k)
-    to_ext = d.coeff_to_extended
-    fixed_cos, sigma_cos = [to_ext(p) for p in pk.fixed_polys], [to_ext(p) for p in pk.permutation_polys]
-    for st in C:
-        st["cos"] = {"fixed": fixed_cos, "advice": [to_ext(p) for p in st["adv_polys"]],
-                     "instance": [to_ext(p) for p in st["inst_polys"]], "sigma": sigma_cos,
-                     "z": [to_ext(p) for p in st["sets"]], "lz": [to_ext(l["pz"]) for l in st["lookups"]],
-                     "la": [to_ext(l["pa"]) for l in st["lookups"]], "ls": [to_ext(l["ps"]) for l in st["lookups"]]}
-    l0e, lle, lbe = to_ext(pk.l0_coeff), to_ext(pk.l_last_coeff), to_ext(pk.l_blind_coeff)
-    h = []
-    for idx in range(ext):
-        acc = 0
-        for st in C:
-            cos = st["cos"]
-
-            def get(kind, i, rot, idx=idx, cos=cos):
-                if kind == "l0":
-                    return l0e[idx]
-                if kind == "l_last":
-                    return lle[idx]
-                if kind == "l_active":
-                    return (1 - (lle[idx] + lbe[idx])) % R
-                return cos[kind][i][(idx + rot * rot_scale) % ext]
-            vals = h_constraints(desc, d, get, beta, gamma, theta, d.coset_point(idx), len(st["sets"]), len(st["lookups"]))
-            for v in vals:
-                acc = (acc * y + v) % R
-        h.append(acc)
-    h = d.extended_to_coeff(d.divide_by_vanishing_poly(h))
-    pieces = [h[i * n:(i + 1) * n] for i in range(d.quotient_poly_degree)]
+    quotient_polys = [{"advice": st["adv_polys"], "instance": st["inst_polys"], "z": st["sets"], "lz": [l["pz"] for l in st["lookups"]],
+                       "la": [l["pa"] for l in st["lookups"]], "ls": [l["ps"] for l in st["lookups"]]} for st in C]
+    tr("quotient_polys", quotient_polys)
+    pieces = quotient_pieces(pk, quotient_polys, theta, beta, gamma, y)
     for _ in pieces:
         rng.fr()
     for pc in pieces:
@@ -647,6 +621,89 @@ def create_proof_multi(pk, instances_list, advice_list, seed, trace=None, transc
     else:
         shplonk_prove(queries, T, tau, n, tr)
     return bytes(T.proof)
+
+
+# ------------------------------------------------------------------------------------ quotient
+QUOTIENT_KINDS = ("advice", "instance", "z", "lz", "la", "ls")
+
+
+def quotient_numerator(pk, polys, theta, beta, gamma, y):
+    """evaluate_h [UP] before the division: the constraints of `polys` folded with y (one Horner chain, circuit after
+    circuit) at every point zeta * extended_omega^idx of the extended domain. polys: one circuit's committed polynomials
+    in coefficient form by kind — {"advice", "instance", "z" (permutation products), "lz" (lookup products), "la", "ls"
+    (permuted inputs / tables)}, n ints each — or a list of such dicts (the circuits of create_proof_multi). Nothing
+    about them has to be satisfied: this is arithmetic on arbitrary polynomials."""
+    desc, d = pk.desc, pk.domain
+    circuits_ = [polys] if isinstance(polys, dict) else list(polys)
+    ext = d.extended_len()
+    rot_scale = 1 << (d.extended_k - d.k)
+    to_ext = d.coeff_to_extended
+    if not hasattr(pk, "_key_cosets"):  # the key's own polynomials on the extended domain, once per key
+        pk._key_cosets = ([to_ext(p) for p in pk.fixed_polys], [to_ext(p) for p in pk.permutation_polys],
+                          to_ext(pk.l0_coeff), to_ext(pk.l_last_coeff), to_ext(pk.l_blind_coeff))
+    fixed_cos, sigma_cos, l0e, lle, lbe = pk._key_cosets
+    cosets = []
+    for c in circuits_:
+        cos = {kind: [to_ext(p) for p in c[kind]] for kind in QUOTIENT_KINDS}
+        cos["fixed"], cos["sigma"] = fixed_cos, sigma_cos
+        cosets.append(cos)
+    h = []
+    for idx in range(ext):
+        acc = 0
+        for cos in cosets:
+            def get(kind, i, rot, idx=idx, cos=cos):
+                if kind == "l0":
+                    return l0e[idx]
+                if kind == "l_last":
+                    return lle[idx]
+                if kind == "l_active":
+                    return (1 - (lle[idx] + lbe[idx])) % R
+                return cos[kind][i][(idx + rot * rot_scale) % ext]
+            vals = h_constraints(desc, d, get, beta, gamma, theta, d.coset_point(idx), len(cos["z"]), len(cos["lz"]))
+            for v in vals:
+                acc = (acc * y + v) % R
+        h.append(acc)
+    return h
+
+
+def quotient_pieces(pk, polys, theta, beta, gamma, y, numerator=None):
+    """The pieces of h(X) as upstream computes them: the numerator on the whole extended domain, divide_by_vanishing_poly,
+    extended_to_coeff (which truncates to quotient_poly_degree * n coefficients), split into cs_degree - 1 pieces of n.
+    For a numerator that X^n - 1 does not divide this is still what upstream would commit to. `numerator`: a
+    quotient_numerator result for the same arguments, to share it between calls."""
+    d, n = pk.domain, pk.n
+    num = quotient_numerator(pk, polys, theta, beta, gamma, y) if numerator is None else numerator
+    h = d.extended_to_coeff(d.divide_by_vanishing_poly(num))
+    return [h[i * n:(i + 1) * n] for i in range(d.quotient_poly_degree)]
+
+
+def quotient_pieces_on_cosets(pk, polys, theta, beta, gamma, y, numerator=None):
+    """The pieces from nc = cs_degree - 1 cosets only: the unique polynomial h of degree below nc * n
+    with h(x) = N(x) / (x^n - 1) at every point of the cosets g_c * H, c < nc, g_c = zeta * extended_omega^c (the first
+    nc cosets of the extended domain; extended index c + 2^(ek-k) * i is row i of coset c). From the definition: on
+    coset c, X^n is the constant g_c^n, so h = sum_j X^(jn) h_j restricted to it is E_c = sum_j (g_c^n)^j h_j, of
+    degree below n — one size-n inverse coset transform gives E_c's coefficients, and per coefficient the nc values
+    E_c[t] are the polynomial sum_j h_j[t] Y^j at Y = g_c^n: a Lagrange interpolation over the nc points g_c^n.
+    Equal to quotient_pieces when X^n - 1 divides the numerator or when nc cosets are the whole extended domain."""
+    d, n = pk.domain, pk.n
+    nc = d.quotient_poly_degree
+    m = 1 << (d.extended_k - d.k)
+    assert nc <= m
+    num = quotient_numerator(pk, polys, theta, beta, gamma, y) if numerator is None else numerator
+    gn, coeffs = [], []
+    for c in range(nc):
+        g = d.coset_point(c)
+        gn.append(pow(g, n, R))
+        tinv = pow(gn[c] - 1, -1, R)
+        e = d.lagrange_to_coeff([num[c + m * i] * tinv % R for i in range(n)])  # E_c(g_c X): coefficient t carries g_c^t
+        ginv, s = pow(g, -1, R), 1
+        for t in range(n):
+            e[t] = e[t] * s % R
+            s = s * ginv % R
+        coeffs.append(e)
+    # column c of the inverse of V[c][j] = (g_c^n)^j: the interpolant of the c-th unit vector over the points g_c^n
+    vinv = [lagrange_interpolate(gn, [int(i == c) for i in range(nc)]) for c in range(nc)]
+    return [[sum(vinv[c][j] * coeffs[c][t] for c in range(nc)) % R for t in range(n)] for j in range(nc)]
 
 
 def lagrange_interpolate(points, evals):

@@ -58,3 +58,30 @@ def test_domain_batched_columns(ctx, pkg, oracle):
     for c in range(ncols):
         assert np.array_equal(out[c], od.lagrange_to_coeff(cols[c]))
     src.free(); dst.free(); d.free()
+
+
+# Extreme columns (see test_gpu_ntt.py): Montgomery words written directly. coeff_to_extended is the zero-padding + coset
+# + table path of the first step; extended_to_coeff and lagrange_to_coeff leave through the output product.
+def _extreme_columns(n):
+    rm1 = np.array(zu.limbs(zu.R - 1), dtype=np.uint64)
+    t232m1 = np.array(zu.limbs((zu.R >> 232 << 232) - 1), dtype=np.uint64)
+    alt, alt2, half = (np.zeros((n, 4), np.uint64) for _ in range(3))
+    alt[0::2] = rm1
+    alt2[1::2] = rm1
+    half[: n // 2] = rm1
+    return {"const_rm1": np.tile(rm1, (n, 1)), "const_t232m1": np.tile(t232m1, (n, 1)), "alt_rm1_0": alt, "alt_0_rm1": alt2, "half_rm1_0": half}
+
+
+@pytest.mark.parametrize("pattern", ["const_rm1", "const_t232m1", "alt_rm1_0", "alt_0_rm1", "half_rm1_0"])
+@pytest.mark.parametrize("j,k", [(4, 9), (4, 12)])
+def test_domain_extreme_columns_match_oracle(ctx, pkg, oracle, j, k, pattern):
+    od = zu.OracleDomain(oracle, j, k)
+    d = pkg.domain.EvaluationDomain(ctx, j, k)
+    a = _extreme_columns(1 << k)[pattern]
+    e = _extreme_columns(d.extended_len())[pattern]
+    assert np.array_equal(d.coeff_to_extended(a), od.coeff_to_extended(a))
+    assert np.array_equal(d.extended_to_coeff(e), od.extended_to_coeff(e))
+    assert np.array_equal(d.lagrange_to_coeff(a), od.lagrange_to_coeff(a))
+    assert np.array_equal(d.coeff_to_lagrange(a), od.coeff_to_lagrange(a))
+    assert np.array_equal(d.divide_by_vanishing_poly(e), od.divide_by_vanishing_poly(e))
+    d.free()

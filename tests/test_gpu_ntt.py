@@ -68,3 +68,81 @@ def test_ntt_linearity_at_full_size(ctx, pkg, oracle):
     assert np.array_equal(back, a)
     # full-size cross-check against the oracle itself (CPU, a few seconds)
     assert np.array_equal(fa, oracle.best_fft(a.copy(), w, k))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Extreme operands. ntt_step_kernel keeps its tile on 9 x 29-bit limbs, leaves sums unreduced for up to two rounds and
+# makes differences non-negative by adding a fixed multiple of p; the bounds that make this safe are proved on the host
+# and pinned per function (fp29_check, fp29_device_check). With uniform data a bound that is one bit too tight goes wrong
+# with negligible probability, so the composed kernel is run here on Montgomery words written directly (no conversion:
+# the word IS the operand), all below r: the largest word, the word with the most one-bits in its low limbs, and layouts
+# that make every butterfly of a round a maximal sum, a maximal difference, or both at once.
+RM1 = np.array(zu.limbs(zu.R - 1), dtype=np.uint64)
+T232M1 = np.array(zu.limbs((zu.R >> 232 << 232) - 1), dtype=np.uint64)  # T * 2^232 - 1, T = r >> 232: low eight limbs all ones
+
+
+def _const(w):
+    return lambda n: np.tile(w, (n, 1))
+
+
+def _alternating(first):
+    def make(n):
+        a = np.zeros((n, 4), np.uint64)
+        a[(0 if first else 1)::2] = RM1
+        return a
+    return make
+
+
+def _half(n):
+    a = np.zeros((n, 4), np.uint64)
+    a[: n // 2] = RM1
+    return a
+
+
+def _single(last):
+    def make(n):
+        a = np.zeros((n, 4), np.uint64)
+        a[n - 1 if last else 0] = RM1
+        return a
+    return make
+
+
+def _random_with_rm1(n):
+    a = zu.random_fr(n, seed=31337 + n)
+    a[::8] = RM1
+    return a
+
+
+PATTERNS = {"const_rm1": _const(RM1), "const_t232m1": _const(T232M1), "alt_rm1_0": _alternating(True), "alt_0_rm1": _alternating(False),
+            "half_rm1_0": _half, "single_first": _single(False), "single_last": _single(True), "zero": lambda n: np.zeros((n, 4), np.uint64),
+            "random_8th_rm1": _random_with_rm1}
+# One size per plan class and per parity of the sub-transform length s (odd s: the single-round prologue; s >= 2 ends in
+# f29_dif4_last). One step: s = k. Two steps: 11 = 6 + 5, 14 = 7 + 7, 17 = 9 + 8, 18 = 9 + 9. Three steps: 19 = 7 + 6 + 6
+# (the first size with the half twiddle table), 21 = 7 + 7 + 7. From k = 17 up three patterns per size, dealt so that
+# every pattern meets a large size.
+SMALL_K = [1, 2, 3, 4, 7, 9, 10, 11, 14]
+LARGE = {17: ("const_rm1", "alt_rm1_0", "random_8th_rm1"), 18: ("const_t232m1", "half_rm1_0", "single_last"),
+         19: ("const_rm1", "half_rm1_0", "random_8th_rm1"), 21: ("const_rm1", "alt_0_rm1", "random_8th_rm1")}
+EXTREME_CASES = [(k, p) for k in SMALL_K for p in PATTERNS] + [(k, p) for k in sorted(LARGE) for p in LARGE[k]]
+SCALED_CASES = [(k, p) for k in (4, 11) for p in PATTERNS] + [(19, p) for p in LARGE[19]]
+
+
+@pytest.mark.parametrize("k,pattern", EXTREME_CASES)
+def test_ntt_extreme_operands_match_oracle(ctx, pkg, oracle, k, pattern):
+    a = PATTERNS[pattern](1 << k)
+    w = oracle.omega(k)
+    want = oracle.best_fft(a.copy(), w, k)
+    got = pkg.arithmetic.best_fft(ctx, a.copy(), w, k)
+    assert np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("k,pattern", SCALED_CASES)
+def test_ntt_extreme_operands_scaled_match_oracle(ctx, pkg, oracle, k, pattern):
+    """NTT_SCALE_NINV: every element leaves the last step through the F_OUT_MUL product instead of the weak reduction.
+    Expected: the oracle's transform times 2^-k in the oracle's field arithmetic."""
+    n = 1 << k
+    a = PATTERNS[pattern](n)
+    w = oracle.omega(k)
+    want = oracle.fr_mul(oracle.best_fft(a.copy(), w, k), np.tile(zu.fr_from_int(pow(n, -1, zu.R)), (n, 1)))
+    got = pkg.arithmetic.best_fft(ctx, a.copy(), w, k, flags=pkg.arithmetic.NTT_SCALE_NINV)
+    assert np.array_equal(got, want)
