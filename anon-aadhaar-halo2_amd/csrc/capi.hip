@@ -16,6 +16,8 @@ int zk_srs_upload(amdzk_ctx* ctx, const uint64_t* g, const uint64_t* g_lagrange,
 void zk_srs_free(amdzk_ctx*, amdzk_srs* s);
 int zk_msm_dev_xyzz(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const Fr* d_scalars, size_t ncols,
                     size_t len, size_t col_stride, G1X** d_out);
+int zk_msm_dev_xyzz_cols(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const Fr* const* d_col_ptrs, size_t ncols, size_t len,
+                         size_t max_ws_bytes, G1X** d_out);
 int zk_msm_finish(amdzk_ctx* ctx, const G1X* d_res, size_t ncols, uint64_t* out_jac);
 int zk_msm_bases_dev_xyzz(amdzk_ctx* ctx, const Fr* d_scalars, size_t ncols, size_t len, size_t col_stride, const G1Affine* d_bases, G1X** d_out);
 int zk_msm_bases_plan_host(size_t ncols, size_t len, uint32_t* window_bits, uint32_t* windows, size_t* scratch_bytes, char why[160]);
@@ -228,11 +230,11 @@ static std::atomic<bool> g_blocking_note_given{false};
 
 extern "C" {
 
-int amdzk_version(void) { return 1003; }
+int amdzk_version(void) { return 1004; }
 
 // "amdzk <abi> src=<hash of the comment-stripped kernel sources and the Makefile> arch=gfx950": what this binary was built
 // from. bench.py refuses a library whose stamp is not its tree's bench.kernel_src_hash().
-const char* amdzk_build_info(void) { return "amdzk 1003 src=" AMDZK_SRC_HASH " arch=gfx950"; }
+const char* amdzk_build_info(void) { return "amdzk 1004 src=" AMDZK_SRC_HASH " arch=gfx950"; }
 
 int amdzk_init(int device_id, amdzk_ctx** out) {
   if (!out) return AMDZK_E_INVALID;
@@ -467,6 +469,30 @@ int amdzk_msm_g1_dev(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const void
   if (!d_scalars || !out_jacobian) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm: null pointer");
   G1X* d_res = nullptr;
   ZK_TRY(zk_msm_dev_xyzz(ctx, srs, basis, (const Fr*)d_scalars, ncols, len, col_stride, &d_res));
+  return zk_msm_finish(ctx, d_res, ncols, out_jacobian);
+}
+
+// Columns anywhere on the device (msm.hip, zk_msm_dev_xyzz_cols): the caller's host array of device pointers goes up as the
+// kernels' pointer table.
+int amdzk_msm_g1_cols_dev(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const void* const* d_cols, size_t ncols, size_t len,
+                          size_t max_scratch_bytes, uint64_t* out_jacobian) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  if (!d_cols || !out_jacobian || ncols == 0) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm_cols: null pointer or ncols == 0");
+  for (size_t c = 0; c < ncols; c++)
+    if (!d_cols[c]) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm_cols: column %zu is null", c);
+  const Fr** d_tab = nullptr;
+  ZK_TRY(zk_ws_reserve(ctx, 2, ncols * sizeof(Fr*), (void**)&d_tab));
+  // the caller's array is read before the call returns: every path below waits for the stream
+  ZK_HIP(ctx, hipMemcpyAsync(d_tab, d_cols, ncols * sizeof(Fr*), hipMemcpyHostToDevice, ctx->stream));
+  G1X* d_res = nullptr;
+  const int r = zk_msm_dev_xyzz_cols(ctx, srs, basis, d_tab, ncols, len, max_scratch_bytes, &d_res);
+  if (r != AMDZK_OK) {  // refused: the copy above may still be reading the caller's array
+    const std::string keep = ctx->err;
+    (void)zk_host_wait(ctx, ctx->stream);
+    ctx->err = keep;
+    return r;
+  }
   return zk_msm_finish(ctx, d_res, ncols, out_jacobian);
 }
 

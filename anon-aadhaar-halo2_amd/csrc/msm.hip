@@ -139,8 +139,11 @@ __device__ __forceinline__ void for_each_digit(const Fr& canon, Fn f) {
 }
 
 struct DigitArgs {
-  const Fr* scalars;     // column 0
-  size_t col_stride;     // elements
+  union {
+    const Fr* scalars;           // column 0 (strided form)
+    const Fr* const* col_ptrs;   // PTRS: device array of the columns' addresses (zk_msm_dev_xyzz_cols); same slot, same layout
+  };
+  size_t col_stride;     // elements (strided form only)
   uint32_t len;
   uint32_t nb;           // buckets per column = 2^(C-1)
   uint32_t chunk;        // scalars per workgroup
@@ -160,7 +163,9 @@ struct DigitArgs {
 // dependent chain of load -> Montgomery reduction -> 16 LDS atomics -> 16 scattered stores: 1.96 + 0.43 ms of the 9.9 ms
 // of a 2^22-point MSM, profiles/r04a_*). The counters of a workgroup fill LDS (2^15 buckets = 128 KiB), so a compute unit
 // holds one workgroup whatever its size: sixteen wavefronts hide that chain where four do not.
-template <int C, bool SCATTER, bool BIG>
+// PTRS: column `col` starts at a.col_ptrs[col] instead of a.scalars + col * a.col_stride — one wave-uniform pointer load per
+// workgroup; the strided instantiations are the code they were before the parameter existed.
+template <int C, bool SCATTER, bool BIG, bool PTRS>
 __global__ __launch_bounds__(BIG ? 1024 : MSM_THREADS) void msm_digit_kernel(DigitArgs a) {
   extern __shared__ uint32_t lds_cnt[];  // nb counters / cursors
   constexpr uint32_t THREADS = BIG ? 1024 : MSM_THREADS;
@@ -175,8 +180,12 @@ __global__ __launch_bounds__(BIG ? 1024 : MSM_THREADS) void msm_digit_kernel(Dig
   __syncthreads();
   const uint32_t lo_i = blk * a.chunk, hi_i = min(lo_i + a.chunk, a.len);
   uint32_t* ent = a.entries + (size_t)col * a.ecap;
+  const Fr* colp = nullptr;
+  if constexpr (PTRS) colp = a.col_ptrs[col];
   for (uint32_t i = lo_i + t; i < hi_i; i += THREADS) {
-    const uint4* sp = reinterpret_cast<const uint4*>(a.scalars + (size_t)col * a.col_stride + i);
+    const uint4* sp;
+    if constexpr (PTRS) sp = reinterpret_cast<const uint4*>(colp + i);
+    else sp = reinterpret_cast<const uint4*>(a.scalars + (size_t)col * a.col_stride + i);
     uint4 lo = sp[0], hi = sp[1];
     if ((lo.x | lo.y | lo.z | lo.w | hi.x | hi.y | hi.z | hi.w) == 0) continue;
     Fr s;
@@ -857,14 +866,14 @@ uint32_t pick_window_bits(uint32_t k) {
   return 16;
 }
 
-template <bool SCATTER>
+template <bool SCATTER, bool PTRS>
 int launch_digits(amdzk_ctx* ctx, uint32_t c, const DigitArgs& a, dim3 grid, bool big) {
   const size_t shmem = (size_t)a.nb * sizeof(uint32_t);
   const char* nm = SCATTER ? "msm_scatter" : "msm_hist";
   switch (c) {
 #define ZK_CASE_T(CC, BIG)                                         \
   {                                                                \
-    auto kfn = msm_digit_kernel<CC, SCATTER, BIG>;                 \
+    auto kfn = msm_digit_kernel<CC, SCATTER, BIG, PTRS>;           \
     if (shmem > 65536) ZK_HIP(ctx, hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); \
     ZK_LAUNCH(ctx, nm, kfn, grid, dim3(BIG ? 1024 : MSM_THREADS), shmem, a); \
   }
@@ -1433,8 +1442,9 @@ static MsmGeom msm_geometry(const amdzk_srs* srs, size_t ncols, size_t len, bool
 
 // table: what level 1 gathers from (a window table of rows of table_n points, or — per_window — the converted copy of the
 // caller's bases, table_n = 0). per_window: ncols counts virtual columns (column, window) over ncols / g.W scalar columns.
+// d_col_ptrs != null (window-table form only): column c is read from d_col_ptrs[c], a device array, instead of d_scalars + c * col_stride.
 static int msm_group(amdzk_ctx* ctx, const G1Affine* table, uint32_t table_n, bool per_window, const MsmGeom& g, char* ws, const Fr* d_scalars,
-                     size_t ncols, size_t len, size_t col_stride, G1X* outp, hipEvent_t l1_done) {
+                     size_t ncols, size_t len, size_t col_stride, G1X* outp, hipEvent_t l1_done, const Fr* const* d_col_ptrs = nullptr) {
   const uint32_t nb = g.nb;
   uint32_t* blk_hist = (uint32_t*)(ws + g.o_bh);
   uint32_t* cnt = (uint32_t*)(ws + g.o_cnt);
@@ -1448,6 +1458,11 @@ static int msm_group(amdzk_ctx* ctx, const G1Affine* table, uint32_t table_n, bo
   DigitArgs da;
   da.scalars = d_scalars;
   da.col_stride = col_stride;
+  if (d_col_ptrs) {
+    if (per_window) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm: a column pointer table needs the window-table form");
+    da.col_ptrs = d_col_ptrs;
+    da.col_stride = 0;
+  }
   da.len = (uint32_t)len;
   da.nb = nb;
   da.chunk = g.chunk;
@@ -1465,11 +1480,13 @@ static int msm_group(amdzk_ctx* ctx, const G1Affine* table, uint32_t table_n, bo
   if (scan_shmem > 65536)
     ZK_HIP(ctx, hipFuncSetAttribute((const void*)msm_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((16 + SCAN_LDS_WORDS) * sizeof(uint32_t))));
   if (per_window) ZK_TRY(launch_digits_win<false>(ctx, g.c, da, dgrid));
-  else ZK_TRY(launch_digits<false>(ctx, g.c, da, dgrid, g.big_digits));
+  else if (d_col_ptrs) ZK_TRY((launch_digits<false, true>(ctx, g.c, da, dgrid, g.big_digits)));
+  else ZK_TRY((launch_digits<false, false>(ctx, g.c, da, dgrid, g.big_digits)));
   ZK_LAUNCH(ctx, "msm_blk_offsets", msm_blk_offsets_kernel, dim3((nb + 255) / 256, (unsigned)ncols), dim3(256), 0, blk_hist, cnt, nb, g.nblk);
   ZK_LAUNCH(ctx, "msm_scan", msm_scan_kernel, dim3((unsigned)ncols), dim3(1024), scan_shmem, cnt, off[0], nb, 1u, 1);
   if (per_window) ZK_TRY(launch_digits_win<true>(ctx, g.c, da, dgrid));
-  else ZK_TRY(launch_digits<true>(ctx, g.c, da, dgrid, g.big_digits));
+  else if (d_col_ptrs) ZK_TRY((launch_digits<true, true>(ctx, g.c, da, dgrid, g.big_digits)));
+  else ZK_TRY((launch_digits<true, false>(ctx, g.c, da, dgrid, g.big_digits)));
   for (int l = 1; l <= MSM_NLEV; l++) {
     const uint32_t T = l == 1 ? g.T1 : g.TL;
     ZK_LAUNCH(ctx, "msm_scan", msm_scan_kernel, dim3((unsigned)ncols), dim3(1024), scan_shmem, off[l - 1], off[l], nb, T, 2);
@@ -1529,6 +1546,50 @@ int zk_msm_dev_xyzz(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const Fr* d
   G1X* outp = (G1X*)(ws + o_out);
   if (!ctx->msm_l1_evt) ZK_HIP(ctx, hipEventCreateWithFlags(&ctx->msm_l1_evt, hipEventDisableTiming));
   ZK_TRY(msm_group(ctx, srs->table[basis], (uint32_t)srs->n, false, g, ws, d_scalars, ncols, len, col_stride, outp, ctx->msm_l1_evt));
+  ctx->msm_l1_fresh = true;
+  *d_out = outp;
+  return AMDZK_OK;
+}
+
+// The same MSM with column c read from d_col_ptrs[c] — a DEVICE array of ncols device pointers, `len` scalars behind each —
+// instead of d_scalars + c * col_stride: the columns of one commitment step of a batch of proofs live in as many workspaces
+// (prover.hip, Gang). Only the counting sort's scalar loads differ (msm_digit_kernel<.., PTRS>); geometry, level 1, folds
+// and the bucket reduction are those of zk_msm_dev_xyzz for the same column count. Results (XYZZ) land in d_out[ncols],
+// column order. A batch whose geometry would take more than max_ws_bytes of workspace (0: MSM_COLS_WS_BYTES) or more than
+// 65535 columns is cut into the fewest equal runs of columns that fit, submitted one behind the other on the stream over
+// the same scratch; the results of all runs sit in front of it. One column is never cut: it runs alone whatever it takes.
+// The table must stay untouched until the call's kernels have run (stream order).
+// 16 GiB: at k = 15 (c = 13, 20 windows) a column's counting-sort entries and bucket lists take about 15 MiB, so ten proofs'
+// 1410 advice columns go as two runs of 705 — five times the 141 columns with which one proof already fills the chip, so the
+// cut costs no occupancy — and two contexts with full scratch hold a ninth of the 288 GB of HBM beside keys and workspaces.
+static constexpr size_t MSM_COLS_WS_BYTES = (size_t)16 << 30;
+int zk_msm_dev_xyzz_cols(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const Fr* const* d_col_ptrs, size_t ncols, size_t len,
+                         size_t max_ws_bytes, G1X** d_out) {
+  if (!srs || basis < 0 || basis > 1 || !srs->table[basis]) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm: basis %d not uploaded", basis);
+  if (len > srs->n) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm: len %zu > 2^k = %zu", len, srs->n);
+  if (!d_col_ptrs || ncols == 0) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm: no column pointer table or ncols == 0");
+  if ((uint64_t)srs->W * srs->n >= (1ull << 31)) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "msm: table too large for 31-bit ids");
+  const size_t cap = max_ws_bytes ? max_ws_bytes : MSM_COLS_WS_BYTES;
+  // a run's geometry: that of its column count; the last run may be shorter, and fewer columns can mean finer tasks and so
+  // more bytes per column — the scratch holds the larger of the two
+  size_t runs = (ncols + 65534) / 65535, per = 0, bytes = 0;
+  for (;; runs++) {
+    per = (ncols + runs - 1) / runs;
+    const size_t last = ncols - (ncols - 1) / per * per;
+    bytes = std::max(msm_geometry(srs, per, len, ctx->msm_latency_mode).bytes, msm_geometry(srs, last, len, ctx->msm_latency_mode).bytes);
+    if (per == 1 || bytes <= cap) break;
+  }
+  const size_t o_scratch = align_up(ncols * sizeof(G1X), 256);
+  char* ws = nullptr;
+  ZK_TRY(zk_ws_reserve(ctx, 1, o_scratch + align_up(bytes, 256), (void**)&ws));
+  G1X* outp = (G1X*)ws;
+  if (!ctx->msm_l1_evt) ZK_HIP(ctx, hipEventCreateWithFlags(&ctx->msm_l1_evt, hipEventDisableTiming));
+  for (size_t first = 0; first < ncols; first += per) {
+    const size_t cnt = std::min(per, ncols - first);
+    const MsmGeom gr = msm_geometry(srs, cnt, len, ctx->msm_latency_mode);
+    ZK_TRY(msm_group(ctx, srs->table[basis], (uint32_t)srs->n, false, gr, ws + o_scratch, nullptr, cnt, len, 0, outp + first, ctx->msm_l1_evt,
+                     d_col_ptrs + first));
+  }
   ctx->msm_l1_fresh = true;
   *d_out = outp;
   return AMDZK_OK;

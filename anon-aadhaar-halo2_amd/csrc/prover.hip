@@ -21,6 +21,8 @@
 #include <array>
 #include <chrono>
 #include <map>
+#include <memory>
+#include <string>
 
 #include "hostcrypto.hpp"
 #include "plonk_kernels.hpp"
@@ -34,6 +36,8 @@ struct amdzk_srs;
 struct amdzk_domain;
 int zk_msm_dev_xyzz(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const Fr* d_scalars, size_t ncols, size_t len, size_t col_stride,
                     G1X** d_out);
+int zk_msm_dev_xyzz_cols(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const Fr* const* d_col_ptrs, size_t ncols, size_t len,
+                         size_t max_ws_bytes, G1X** d_out);
 int zk_msm_finish(amdzk_ctx* ctx, const G1X* d_res, size_t ncols, uint64_t* out_jac);
 int zk_lagrange_to_coeff(amdzk_ctx* ctx, const amdzk_domain* d, const Fr* d_in, size_t in_stride, Fr* d_out, size_t out_stride, size_t ncols);
 extern "C" {
@@ -1632,6 +1636,17 @@ struct Commit {
   bool begun = false, done = false;
 };
 
+// A commitment batch a Prover of a gang (amdzk_create_proof_batch) hands to the gang instead of launching it: `ncols`
+// columns of n at `cols`. The gang commits the batches of all its provers in ONE submission and hands the points back:
+// into `into` (the prover writes them when its order says so) or, with a label, straight to the prover's transcript.
+struct DeferredCommit {
+  int basis;
+  const Fr* cols;
+  size_t ncols;
+  Commit* into;
+  const char* label;
+};
+
 // The multiopen argument's lists for pks[0..NC) (amdzk_pk::Multiopen): the evaluations in proof order, then h_poly's;
 // the queries in upstream order; SHPLONK's rotation sets. Built once per key (per list of instance keys).
 int build_multiopen(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, amdzk_pk::Multiopen& mo) {
@@ -1862,6 +1877,11 @@ struct Prover {
   ShplonkSets sh;
   amdzk_phase_fn phase_fn = nullptr;  // amdzk_proof_opts: the caller's synthesize of phases >= 1
   void* phase_user = nullptr;
+  // Member of a gang (serial, one instance): commit_begin / commit_write leave their batch here instead of launching it
+  std::vector<DeferredCommit>* sink = nullptr;
+  Commit cm_adv, cm_lk;                     // the advice and permuted-lookup batches between their two halves (advice_enqueue / _write)
+  std::vector<const Fr*> ev_pp;             // evaluations_prepare: the (polynomial, point) pairs
+  std::vector<Fr> ev_pts;
   const bool ttrace = getenv("AMDZK_TRACE_TIME") != nullptr;
   double tlast;
 
@@ -1916,10 +1936,26 @@ struct Prover {
     return AMDZK_OK;
   }
   int commit_begin(amdzk_ctx* l, int basis, const Fr* d_cols, size_t ncols, Commit& c) {
+    if (sink) {  // the gang launches it with the other provers' and fills c.pts
+      c.begun = true;
+      if (ncols) sink->push_back(DeferredCommit{basis, d_cols, ncols, &c, nullptr});
+      else c.done = true;
+      return AMDZK_OK;
+    }
     ZK_TRY(on_lane(l, commit_launch(l, pk, basis, d_cols, ncols, c.pc)));
     c.begun = true;
     if (serial) ZK_TRY(commit_end(c));
     return AMDZK_OK;
+  }
+  // commit on the caller's stream and write the points at once (the commitments the transcript waits for alone)
+  int commit_write(int basis, const Fr* d_cols, size_t ncols, const char* label) {
+    if (sink) {
+      if (ncols) sink->push_back(DeferredCommit{basis, d_cols, ncols, nullptr, label});
+      return AMDZK_OK;
+    }
+    std::vector<G1Affine> cm;
+    ZK_TRY(commit_cols(ctx, pk, basis, d_cols, ncols, cm));
+    return write_points(cm, label);
   }
   // columns [first, first + count) of the arena, blinded on lane `after`: coefficients (PQ) and quotient-domain values (PC) on B
   // after_l1: the columns' commitment batch has already been launched on `after`; the transforms start behind its
@@ -2058,50 +2094,68 @@ struct Prover {
   int advice(const void* const* d_advice_all, size_t advice_stride) {
     if (pk->phased()) return advice_phased(d_advice_all, advice_stride);
     for (size_t ci = 0; ci < NC; ci++) {
-      amdzk_pk* const pk = pks[ci];
-      if (A) {
-        ZK_HIP(ctx, hipMemcpy2DAsync(pk->adv(), n * 32, d_advice_all[ci], advice_stride * 32, n * 32, A, hipMemcpyDeviceToDevice, ctx->stream));
-        ZK_TRY(blind(M, pk->adv(), A, usable, bf + 1, draws.advice(ci), draws.col));
-      }
-      Commit cm;
-      if (A && !serial) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->adv(), A, cm));
-      ZK_TRY(transforms_on_B(pk, M, 0, (size_t)A + I, cm.begun));
-      if (A && !cm.begun) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->adv(), A, cm));
-      ZK_TRY(commit_end(cm));
-      ZK_TRY(write_points(cm.pts, "advice"));
+      ZK_TRY(advice_enqueue(ci, d_advice_all ? d_advice_all[ci] : nullptr, advice_stride));
+      ZK_TRY(commit_end(cm_adv));
+      ZK_TRY(advice_write());
     }
     ZK_TRY(commit_end(cm_rnd));  // long done; lane C's MSM workspace is free for the lookup products' commitment
     tick("advice");
     return AMDZK_OK;
   }
-  // 2. lookups: compress, permute (on the device), blind, commit
+  // ... in two halves per instance, so that a gang (amdzk_create_proof_batch) commits the batches of all its provers between
+  // them: everything up to the commitment's launch (with a sink: its hand-over to the gang), then the points' write
+  int advice_enqueue(size_t ci, const void* d_advice, size_t advice_stride) {
+    amdzk_pk* const pk = pks[ci];
+    if (A) {
+      ZK_HIP(ctx, hipMemcpy2DAsync(pk->adv(), n * 32, d_advice, advice_stride * 32, n * 32, A, hipMemcpyDeviceToDevice, ctx->stream));
+      ZK_TRY(blind(M, pk->adv(), A, usable, bf + 1, draws.advice(ci), draws.col));
+    }
+    cm_adv = Commit();
+    if (A && !serial) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->adv(), A, cm_adv));
+    ZK_TRY(transforms_on_B(pk, M, 0, (size_t)A + I, cm_adv.begun));
+    if (A && !cm_adv.begun) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->adv(), A, cm_adv));
+    return AMDZK_OK;
+  }
+  int advice_write() { return write_points(cm_adv.pts, "advice"); }
+  // 2. lookups: compress, permute (on the device), blind, commit — the same two halves per instance
   int lookups() {
     for (size_t ci = 0; ci < NC && L; ci++) {
-      amdzk_pk* const pk = pks[ci];
-      ZK_TRY(run_program(ctx, pk, pk->prog_compress, false, pk->d_outs_compress, nullptr, "expr_lookup_compress"));
-      ZK_TRY(d2d(ctx, pk->la(), pk->ci, (size_t)L * n * 32));
-      ZK_TRY(zk_permute_expression_pairs(ctx, pk->la(), pk->ct, pk->lk_ts, pk->ls(), pk->lk_left, pk->lk_flags, pk->d_err, L, (uint32_t)n,
-                                         (uint32_t)usable, pk->lk_ts_const, pk->lk_const));
-      // the "input not in table" word comes down behind the permutation and is read once the host has waited for this
-      // phase's commitment anyway (it used to be a host wait of its own in the middle of the phase: 0.1 ms of idle device)
-      *pk->h_err = 0;
-      ZK_HIP(ctx, hipMemcpyAsync(pk->h_err, pk->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-      tick("  lookup: device permute");
-      ZK_TRY(blind(M, pk->la(), L, usable, bf + 1, draws.lookup(ci), draws.lk_col));
-      ZK_TRY(blind(M, pk->ls(), L, usable, bf + 1, draws.lookup(ci) + draws.col, draws.lk_col));
-      Commit cmc;
-      if (!serial) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->la(), 2 * L, cmc));
-      ZK_TRY(transforms_on_B(pk, M, (size_t)A + I, 2 * (size_t)L, cmc.begun));
-      if (!cmc.begun) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->la(), 2 * L, cmc));
-      ZK_TRY(commit_end(cmc));
-      if (*pk->h_err) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: lookup %d input not in table (ConstraintSystemFailure)", *pk->h_err - 1);
-      const std::vector<G1Affine>& cm = cmc.pts;
-      for (uint32_t l = 0; l < L; l++) {
-        std::vector<G1Affine> two = {cm[l], cm[L + l]};
-        ZK_TRY(write_points(two, "lookup_permuted"));
-      }
+      ZK_TRY(lookups_enqueue(ci));
+      ZK_TRY(commit_end(cm_lk));
+      ZK_TRY(lookups_write(ci));
     }
     tick("lookups_permuted");
+    return AMDZK_OK;
+  }
+  int lookups_enqueue(size_t ci) {
+    if (!L) return AMDZK_OK;
+    amdzk_pk* const pk = pks[ci];
+    ZK_TRY(run_program(ctx, pk, pk->prog_compress, false, pk->d_outs_compress, nullptr, "expr_lookup_compress"));
+    ZK_TRY(d2d(ctx, pk->la(), pk->ci, (size_t)L * n * 32));
+    ZK_TRY(zk_permute_expression_pairs(ctx, pk->la(), pk->ct, pk->lk_ts, pk->ls(), pk->lk_left, pk->lk_flags, pk->d_err, L, (uint32_t)n,
+                                       (uint32_t)usable, pk->lk_ts_const, pk->lk_const));
+    // the "input not in table" word comes down behind the permutation and is read once the host has waited for this
+    // phase's commitment anyway (it used to be a host wait of its own in the middle of the phase: 0.1 ms of idle device)
+    *pk->h_err = 0;
+    ZK_HIP(ctx, hipMemcpyAsync(pk->h_err, pk->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    tick("  lookup: device permute");
+    ZK_TRY(blind(M, pk->la(), L, usable, bf + 1, draws.lookup(ci), draws.lk_col));
+    ZK_TRY(blind(M, pk->ls(), L, usable, bf + 1, draws.lookup(ci) + draws.col, draws.lk_col));
+    cm_lk = Commit();
+    if (!serial) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->la(), 2 * L, cm_lk));
+    ZK_TRY(transforms_on_B(pk, M, (size_t)A + I, 2 * (size_t)L, cm_lk.begun));
+    if (!cm_lk.begun) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->la(), 2 * L, cm_lk));
+    return AMDZK_OK;
+  }
+  int lookups_write(size_t ci) {
+    if (!L) return AMDZK_OK;
+    amdzk_pk* const pk = pks[ci];
+    if (*pk->h_err) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: lookup %d input not in table (ConstraintSystemFailure)", *pk->h_err - 1);
+    const std::vector<G1Affine>& cm = cm_lk.pts;
+    for (uint32_t l = 0; l < L; l++) {
+      std::vector<G1Affine> two = {cm[l], cm[L + l]};
+      ZK_TRY(write_points(two, "lookup_permuted"));
+    }
     return AMDZK_OK;
   }
   int lookup_products(size_t ci, bool ordered_behind_m) {
@@ -2148,13 +2202,20 @@ struct Prover {
       if (L) ZK_TRY(lookup_products(0, true));
       if (ns) ZK_TRY(perm_commit(0));
     } else {
-      for (size_t ci = 0; ci < NC && L; ci++) ZK_TRY(lookup_products(ci, false));
-      for (size_t ci = 0; ci < NC && ns; ci++) {
-        ZK_TRY(perm_products(ci));
-        ZK_TRY(perm_commit(ci));
-      }
+      ZK_TRY(products_enqueue_serial());
     }
     if (ns && !serial) ZK_TRY(transforms_on_B(pk, M, (size_t)A + I + 2 * L, ns, true));  // lanes: one instance
+    return products_write();
+  }
+  int products_enqueue_serial() {
+    for (size_t ci = 0; ci < NC && L; ci++) ZK_TRY(lookup_products(ci, false));
+    for (size_t ci = 0; ci < NC && ns; ci++) {
+      ZK_TRY(perm_products(ci));
+      ZK_TRY(perm_commit(ci));
+    }
+    return AMDZK_OK;
+  }
+  int products_write() {
     for (size_t ci = 0; ci < NC; ci++) {
       ZK_TRY(commit_end(cm_zp[ci]));
       ZK_TRY(write_points(cm_zp[ci].pts, "perm_z"));
@@ -2188,15 +2249,25 @@ struct Prover {
       ZK_TRY(lincomb(M, pp, cf, pk->scratch, len));  // scratch holds >= ext >= qdeg * n
       ZK_TRY(d2d(ctx, pk->hpieces, pk->scratch, len * 32));
     }
-    std::vector<G1Affine> cm;
-    ZK_TRY(commit_cols(ctx, pk, AMDZK_BASIS_G, pk->hpieces, pk->qdeg, cm));  // consecutive n-blocks
-    ZK_TRY(write_points(cm, "h_piece"));
+    ZK_TRY(commit_write(AMDZK_BASIS_G, pk->hpieces, pk->qdeg, "h_piece"));  // consecutive n-blocks
     tick("h_eval+commit");
     return AMDZK_OK;
   }
   // 7. evaluations: h_poly = sum_i piece_i * x^(n i), then one list of (polynomial, rotation) in proof order and the
   //    extra evaluation SHPLONK needs (h_poly at x; random at x is already in the list)
   int evaluations(const Fr& x) {
+    ZK_TRY(evaluations_prepare(x));
+    const size_t nq = ev_pp.size();
+    ZK_TRY(h2d_staged(ctx, pk, pk->ptrs, ev_pp.data(), nq * sizeof(Fr*)));
+    ZK_TRY(upload_small_on(M, ev_pts, 0));
+    ZK_TRY(zk_poly_eval(ctx, (const Fr* const*)pk->ptrs, pk->small, pk->small + nq, nq, (uint32_t)n));
+    evals.resize(nq);
+    ZK_TRY(d2h(ctx, evals.data(), pk->small + nq, nq * 32));
+    return evaluations_write();
+  }
+  // ... in three parts, so that a gang evaluates the pairs of all its provers in one launch behind one wait: h_poly and
+  // the pairs (ev_pp, ev_pts); [the evaluation into `evals`]; the written evaluations
+  int evaluations_prepare(const Fr& x) {
     {
       const Fr xn = pow_u64(x, n);
       std::vector<const Fr*> pp(pk->qdeg);
@@ -2227,14 +2298,12 @@ struct Prover {
     }
     const size_t nq = mo->ev.size();
     if (nq > pk->ptrs_cap || 2 * nq > pk->small_cap) ZK_FAIL(ctx, AMDZK_E_NOMEM, "create_proof: too many queries (%zu)", nq);
-    std::vector<const Fr*> pp(nq);
-    std::vector<Fr> pts(nq);
-    for (size_t i = 0; i < nq; i++) pp[i] = mo->ev[i].first, pts[i] = rot_pt[mo->ev_rot[i]];
-    ZK_TRY(h2d_staged(ctx, pk, pk->ptrs, pp.data(), nq * sizeof(Fr*)));
-    ZK_TRY(upload_small_on(M, pts, 0));
-    ZK_TRY(zk_poly_eval(ctx, (const Fr* const*)pk->ptrs, pk->small, pk->small + nq, nq, (uint32_t)n));
-    evals.resize(nq);
-    ZK_TRY(d2h(ctx, evals.data(), pk->small + nq, nq * 32));
+    ev_pp.resize(nq);
+    ev_pts.resize(nq);
+    for (size_t i = 0; i < nq; i++) ev_pp[i] = mo->ev[i].first, ev_pts[i] = rot_pt[mo->ev_rot[i]];
+    return AMDZK_OK;
+  }
+  int evaluations_write() {
     for (size_t i = 0; i < mo->n_written; i++) T.write_scalar(evals[i]);
     tick("evals");
     return AMDZK_OK;
@@ -2284,9 +2353,7 @@ struct Prover {
     ZK_TRY(h2d_staged(ctx, pk, pk->ptrs, pp.data(), np * sizeof(Fr*)));
     ZK_TRY(upload_small_on(M, roots, 0));
     ZK_TRY(zk_kate_div(ctx, (Fr* const*)pk->ptrs, pk->small, np, (uint32_t)n));
-    std::vector<G1Affine> cm;
-    ZK_TRY(commit_cols(ctx, pk, AMDZK_BASIS_G, pk->sets_N, np, cm));
-    return write_points(cm, "gwc_w");
+    return commit_write(AMDZK_BASIS_G, pk->sets_N, np, "gwc_w");
   }
   // 9b. SHPLONK (multiopen/shplonk/prover.rs [UP]), up to its first commitment h(X)
   int shplonk(const Fr& ys, const Fr& v) {
@@ -2339,9 +2406,7 @@ struct Prover {
     ZK_TRY(upload_small_on(M, q_coef, nq + q_low.size()));
     ZK_TRY(zk_kate_div_from(ctx, (Fr* const*)pt, (const Fr* const*)(pt + nq), pk->small, pk->small + nq, (uint32_t)maxm, nq, (uint32_t)n));
     ZK_TRY(zk_lincomb(ctx, (const Fr* const*)pt, pk->small + nq + q_low.size(), (uint32_t)nq, pk->hx, n, false));
-    std::vector<G1Affine> cm;
-    ZK_TRY(commit_cols(ctx, pk, AMDZK_BASIS_G, pk->hx, 1, cm));
-    return write_points(cm, "shplonk_h1");
+    return commit_write(AMDZK_BASIS_G, pk->hx, 1, "shplonk_h1");
   }
   // ... and its second: l(X) = sum_i v^i z_i (L_i - r_i) - zt(u) h(X);  then / (X - u) / z_0 — the factor 1 / z_0 rides
   // in on the coefficients. The super point set is kept in ascending order of the canonical field elements.
@@ -2377,9 +2442,7 @@ struct Prover {
     std::vector<Fr*> one_p = {lx};
     ZK_TRY(h2d_staged(ctx, pk, (void**)pk->ptrs + nr + 1, one_p.data(), sizeof(Fr*)));
     ZK_TRY(zk_kate_div_from(ctx, (Fr* const*)((void**)pk->ptrs + nr + 1), nullptr, pk->small + nr + 2, pk->small + nr + 1, 1, 1, (uint32_t)n));
-    std::vector<G1Affine> cm;
-    ZK_TRY(commit_cols(ctx, pk, AMDZK_BASIS_G, lx, 1, cm));
-    return write_points(cm, "shplonk_h2");
+    return commit_write(AMDZK_BASIS_G, lx, 1, "shplonk_h2");
   }
 };
 
@@ -2509,6 +2572,216 @@ int create_proof_impl(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t ncirc, const 
   }
   return r;
 }
+
+
+// amdzk_create_proof_batch: B independent proofs of one circuit advanced in lock-step on the caller's stream. Every member
+// is a Prover of its own (one instance, no lanes) with its own transcript, random source and workspace, and walks
+// create_proof_body's steps in their order; what the members of a step have in common is done once for all of them:
+//   * every commitment step — the random polynomial, advice, A' / S', the permutation and lookup products (together),
+//     the h pieces, SHPLONK's two or GWC's witnesses — is ONE pointer-table MSM (zk_msm_dev_xyzz_cols) over the live
+//     members' columns, one host wait and one download, the points handed back per member (DeferredCommit);
+//   * the lookup permutations' error words are read behind that step's wait;
+//   * the evaluations of all members are one zk_poly_eval over the concatenated (polynomial, point) pairs and one download.
+// One launch per member on the same stream: the compress / fraction / h(X) programs (their constant tables differ), the
+// transforms, the lookup permutation, inversions and running products, the linear combinations and divisions of the
+// opening argument, ChaCha blinding. No arithmetic differs from the single path, so the bytes do not either.
+// A member whose witness fails (lookup input not in its table, a commitment that is the identity, beta = 0) gets its status
+// and leaves the gang; the others go on. A failure of the device or of memory ends the batch for all.
+struct Gang {
+  struct Member {
+    size_t index = 0;
+    amdzk_pk* pk = nullptr;
+    zkhost::Blake2bWrite t_blake;
+    zkhost::Keccak256Write t_keccak;
+    RandomSource rng;
+    std::unique_ptr<Prover> P;
+    std::vector<DeferredCommit> deferred;
+    bool live = true;
+    int status = AMDZK_OK;
+    std::string err;
+    Fr x, v;  // the challenges a later step of the same member needs again
+    zkhost::TranscriptWrite& T() { return P->T; }
+  };
+  amdzk_ctx* const ctx;
+  std::vector<std::unique_ptr<Member>> members;
+  int fatal = AMDZK_OK;  // a status that is not one witness's: the batch ends
+  explicit Gang(amdzk_ctx* ctx) : ctx(ctx) {}
+
+  void fail(Member& m, int r) {
+    m.live = false;
+    m.status = r;
+    m.err = "proof " + std::to_string(m.index) + ": " + ctx->err;
+    m.deferred.clear();
+    if (r == AMDZK_E_HIP || r == AMDZK_E_NOMEM) fatal = r;
+  }
+  // one step of every live member, in index order
+  template <class F>
+  int each(F f) {
+    for (auto& m : members) {
+      if (!m->live) continue;
+      const int r = f(*m);
+      if (r != AMDZK_OK) fail(*m, r);
+      if (fatal != AMDZK_OK) return fatal;
+    }
+    return AMDZK_OK;
+  }
+  size_t live() const {
+    size_t c = 0;
+    for (auto& m : members) c += m->live ? 1 : 0;
+    return c;
+  }
+  // device scratch of the gang's own (pointer tables, evaluation points and results): workspace slot 2, the staging slot of
+  // the host-pointer MSM / NTT entry points, which no proof uses. Valid until the next call (the slot may grow).
+  int scratch(size_t bytes, char** out) { return zk_ws_reserve(ctx, 2, bytes, (void**)out); }
+
+  // The commitment batches the live members left in their sinks, as ONE submission per basis (a step has one basis), then
+  // per member in the order it deferred them: into the Commit it named, or written to its transcript under the label.
+  int commit_step() {
+    for (int basis = 0; basis <= 1; basis++) {
+      std::vector<const Fr*> cols;
+      for (auto& m : members)
+        if (m->live)
+          for (auto& d : m->deferred)
+            if (d.basis == basis)
+              for (size_t c = 0; c < d.ncols; c++) cols.push_back(d.cols + c * m->pk->n);
+      if (cols.empty()) continue;
+      amdzk_pk* const pk0 = members[0]->pk;  // srs, n and the staging ring: any member's
+      char* d_tab = nullptr;
+      ZK_TRY(scratch(cols.size() * sizeof(Fr*), &d_tab));
+      ZK_TRY(h2d_staged(ctx, pk0, d_tab, cols.data(), cols.size() * sizeof(Fr*)));
+      G1X* d_res = nullptr;
+      ZK_TRY(zk_msm_dev_xyzz_cols(ctx, pk0->srs, basis, (const Fr* const*)d_tab, cols.size(), pk0->n, 0, &d_res));
+      PendingCommit pc;
+      pc.ctx = ctx;
+      pc.d_res = d_res;
+      pc.ncols = cols.size();
+      std::vector<G1Affine> pts;
+      ZK_TRY(commit_finish(pc, pts));  // the wait: `cols` (if it went up unstaged) has been read
+      size_t at = 0;
+      for (auto& m : members) {
+        if (!m->live) continue;
+        for (auto& d : m->deferred) {
+          if (d.basis != basis) continue;
+          std::vector<G1Affine> mine(pts.begin() + at, pts.begin() + at + d.ncols);
+          at += d.ncols;
+          if (d.into) {
+            d.into->pts.swap(mine);
+            d.into->done = true;
+          } else if (m->live) {
+            const int r = m->P->write_points(mine, d.label);
+            if (r != AMDZK_OK) {  // (clears m->deferred: leave its loop)
+              const size_t rest_from = &d - m->deferred.data();
+              for (size_t j = rest_from + 1; j < m->deferred.size(); j++)
+                if (m->deferred[j].basis == basis) at += m->deferred[j].ncols;
+              fail(*m, r);
+              break;
+            }
+          }
+        }
+      }
+    }
+    for (auto& m : members) m->deferred.clear();
+    return fatal;
+  }
+
+  // all live members' evaluations (Prover::evaluations_prepare left the pairs) in one launch, one wait, one download
+  int evaluate_step() {
+    std::vector<const Fr*> pp;
+    std::vector<Fr> pts;
+    for (auto& m : members)
+      if (m->live) {
+        pp.insert(pp.end(), m->P->ev_pp.begin(), m->P->ev_pp.end());
+        pts.insert(pts.end(), m->P->ev_pts.begin(), m->P->ev_pts.end());
+      }
+    const size_t nq = pp.size();
+    if (!nq) return AMDZK_OK;
+    amdzk_pk* const pk0 = members[0]->pk;
+    const size_t o_pts = (nq * sizeof(Fr*) + 255) / 256 * 256;
+    char* d = nullptr;
+    ZK_TRY(scratch(o_pts + 2 * nq * 32, &d));
+    Fr* d_pts = (Fr*)(d + o_pts);
+    ZK_TRY(h2d_staged(ctx, pk0, d, pp.data(), nq * sizeof(Fr*)));
+    ZK_TRY(h2d_staged(ctx, pk0, d_pts, pts.data(), nq * 32));
+    ZK_TRY(zk_poly_eval(ctx, (const Fr* const*)d, d_pts, d_pts + nq, nq, (uint32_t)pk0->n));
+    std::vector<Fr> out(nq);
+    ZK_TRY(d2h(ctx, out.data(), d_pts + nq, nq * 32));
+    size_t at = 0;
+    for (auto& m : members)
+      if (m->live) {
+        const size_t k = m->P->ev_pp.size();
+        m->P->evals.assign(out.begin() + at, out.begin() + at + k);
+        at += k;
+      }
+    return AMDZK_OK;
+  }
+
+#define GANG_TRY(x)                      \
+  do {                                   \
+    const int _g = (x);                  \
+    if (_g != AMDZK_OK) return _g;       \
+  } while (0)
+  // create_proof_body's steps, each for all live members
+  int run(const uint64_t* const* const* instances, const size_t* const* instance_lens, const void* const* d_advice, size_t advice_stride,
+          bool use_gwc) {
+    GANG_TRY(each([&](Member& m) -> int {
+      const uint64_t* const* inst = instances ? instances[m.index] : nullptr;
+      const size_t* lens = instance_lens ? instance_lens[m.index] : nullptr;
+      ZK_TRY(m.P->instances(&inst, &lens));
+      return m.P->random_poly();
+    }));
+    GANG_TRY(commit_step());  // the random polynomials (basis g)
+    GANG_TRY(each([&](Member& m) -> int { return m.P->advice_enqueue(0, d_advice ? d_advice[m.index] : nullptr, advice_stride); }));
+    GANG_TRY(commit_step());
+    GANG_TRY(each([&](Member& m) -> int {
+      ZK_TRY(m.P->advice_write());
+      const Fr theta = m.P->challenge("theta");
+      ZK_TRY(m.P->put_consts({{&amdzk_pk::c_theta, theta}}));
+      return m.P->lookups_enqueue(0);
+    }));
+    GANG_TRY(commit_step());
+    GANG_TRY(each([&](Member& m) -> int {
+      ZK_TRY(m.P->lookups_write(0));
+      const Fr beta = m.P->challenge("beta");
+      const Fr gamma = m.P->challenge("gamma");
+      if (m.pk->S && beta.is_zero()) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "create_proof: the challenge beta is zero (probability 2^-254): the factored permutation terms need 1 / beta");
+      ZK_TRY(m.P->put_consts({{&amdzk_pk::c_beta, beta}, {&amdzk_pk::c_gamma, gamma}, {&amdzk_pk::c_betainv, inv(beta)}}));
+      return m.P->products_enqueue_serial();
+    }));
+    GANG_TRY(commit_step());  // permutation and lookup products together: both over g_lagrange
+    GANG_TRY(each([&](Member& m) -> int {
+      ZK_TRY(m.P->products_write());
+      ZK_TRY(m.P->write_points(m.P->cm_rnd.pts, "random_poly"));
+      const Fr y = m.P->challenge("y");
+      ZK_TRY(m.P->put_consts({{&amdzk_pk::c_y, y}}));
+      return m.P->vanishing(y);
+    }));
+    GANG_TRY(commit_step());  // the h pieces, written as they come back
+    GANG_TRY(each([&](Member& m) -> int {
+      m.x = m.P->challenge("x");
+      return m.P->evaluations_prepare(m.x);
+    }));
+    GANG_TRY(evaluate_step());
+    if (use_gwc) {
+      GANG_TRY(each([&](Member& m) -> int {
+        ZK_TRY(m.P->evaluations_write());
+        return m.P->gwc(m.P->challenge("gwc_v"));
+      }));
+      GANG_TRY(commit_step());
+    } else {
+      GANG_TRY(each([&](Member& m) -> int {
+        ZK_TRY(m.P->evaluations_write());
+        const Fr ys = m.P->challenge("shplonk_y");
+        m.v = m.P->challenge("shplonk_v");
+        return m.P->shplonk(ys, m.v);
+      }));
+      GANG_TRY(commit_step());
+      GANG_TRY(each([&](Member& m) -> int { return m.P->shplonk_final(m.v, m.P->challenge("u")); }));
+      GANG_TRY(commit_step());
+    }
+    return AMDZK_OK;
+  }
+#undef GANG_TRY
+};
 
 }  // namespace
 
@@ -2662,6 +2935,94 @@ int amdzk_create_proof_opts(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_circu
   ex.phase_user = opts->phase_user;
   return create_proof_impl(ctx, pks, n_circuits, instances, instance_lens, d_advice, advice_stride, rs, opts->transcript_kind, proof_out, proof_cap,
                            proof_len, ex);
+}
+
+// n_proofs independent proofs of one circuit from one host thread, advanced in lock-step (Gang above). pks[b]: proof b's
+// workspace — the key or workspace clones of it, pairwise different. Bytes: those of n_proofs amdzk_create_proof_ex /
+// amdzk_create_proof_scalars calls.
+static int proof_batch(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_proofs, const uint64_t* const* const* instances,
+                       const size_t* const* instance_lens, const void* const* d_advice, size_t advice_stride, const amdzk_batch_opts* opts,
+                       uint8_t* proofs_out, size_t proof_stride, size_t* proof_lens, int* statuses, bool* ran) {
+  if (!pks || n_proofs == 0) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: no proofs");
+  if (!opts || !proofs_out || !proof_lens) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: null argument");
+  if (opts->size < sizeof(amdzk_batch_opts))
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: amdzk_batch_opts.size is %zu, this library needs %zu", opts->size, sizeof(amdzk_batch_opts));
+  if (!opts->rng_seeds && !opts->scalars) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: neither rng_seeds nor scalars");
+  for (size_t b = 0; b < n_proofs; b++) {
+    if (!pks[b]) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: null key (proof %zu)", b);
+    const amdzk_pk* root_b = pks[b]->clone_of ? pks[b]->clone_of : pks[b];
+    const amdzk_pk* root_0 = pks[0]->clone_of ? pks[0]->clone_of : pks[0];
+    if (root_b != root_0) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: proof %zu's key is not the first key or a workspace clone of it", b);
+    for (size_t d = 0; d < b; d++)
+      if (pks[d] == pks[b]) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: proofs %zu and %zu share one workspace", d, b);
+    if (pks[0]->A && (!d_advice || !d_advice[b])) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: null advice (proof %zu)", b);
+    if (opts->scalars && !opts->scalars[b]) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: null scalars (proof %zu)", b);
+  }
+  amdzk_pk* const pk = pks[0];
+  if (pk->phased())
+    ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "create_proof_batch: the key has challenge phases or challenges: prove it with amdzk_create_proof_opts");
+  if (advice_stride < pk->n) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: advice stride < n");
+  const bool use_gwc = (opts->transcript_kind & AMDZK_MULTIOPEN_GWC) != 0;
+  const int kind = opts->transcript_kind & ~AMDZK_MULTIOPEN_GWC;
+  if (kind != AMDZK_TRANSCRIPT_BLAKE2B && kind != AMDZK_TRANSCRIPT_KECCAK256_EVM)
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: unknown transcript kind %d", kind);
+  const size_t psize = amdzk_proof_size(pk, opts->transcript_kind);
+  if (proof_stride < psize) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: proof_stride %zu < proof size %zu", proof_stride, psize);
+  if (opts->scalars && opts->scalar_count < DrawLayout(pk, 1).total)
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: %zu scalars given, %zu needed", opts->scalar_count, DrawLayout(pk, 1).total);
+
+  *ran = true;
+  Gang g(ctx);
+  for (size_t b = 0; b < n_proofs; b++) {
+    std::unique_ptr<Gang::Member> m(new Gang::Member);
+    m->index = b;
+    m->pk = pks[b];
+    if (opts->scalars) m->rng.scalars = opts->scalars[b];
+    else m->rng = RandomSource(opts->rng_seeds[b]);
+    zkhost::TranscriptWrite& T = kind == AMDZK_TRANSCRIPT_BLAKE2B ? (zkhost::TranscriptWrite&)m->t_blake : (zkhost::TranscriptWrite&)m->t_keccak;
+    m->P.reset(new Prover(ctx, &pks[b], 1, ctx, ctx, T, m->rng));  // B = C = ctx: one stream, no lanes
+    m->P->sink = &m->deferred;
+    g.members.push_back(std::move(m));
+  }
+  const int run = g.run(instances, instance_lens, d_advice, advice_stride, use_gwc);
+  int first = AMDZK_OK;
+  std::string first_err;
+  for (auto& m : g.members) {
+    if (m->live && run != AMDZK_OK) {  // the batch ended under it
+      m->live = false;
+      m->status = run;
+      m->err = ctx->err;
+    }
+    if (m->live && m->T().proof.size() > proof_stride) {  // (cannot happen: amdzk_proof_size is exact)
+      m->live = false;
+      m->status = AMDZK_E_INVALID;
+      m->err = "proof " + std::to_string(m->index) + ": create_proof: proof buffer too small";
+    }
+    if (statuses) statuses[m->index] = m->status;
+    proof_lens[m->index] = m->live ? m->T().proof.size() : 0;
+    if (m->live) memcpy(proofs_out + m->index * proof_stride, m->T().proof.data(), m->T().proof.size());
+    else if (first == AMDZK_OK) first = m->status, first_err = m->err;
+  }
+  if (first != AMDZK_OK) {  // a failed proof may have left work behind: the workspaces must be quiet before they are used again
+    (void)zk_sync_all(ctx);
+    ctx->err = first_err;
+  }
+  return first;
+}
+int amdzk_create_proof_batch(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_proofs, const uint64_t* const* const* instances,
+                             const size_t* const* instance_lens, const void* const* d_advice, size_t advice_stride,
+                             const amdzk_batch_opts* opts, uint8_t* proofs_out, size_t proof_stride, size_t* proof_lens, int* statuses) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  bool ran = false;
+  const int r = proof_batch(ctx, pks, n_proofs, instances, instance_lens, d_advice, advice_stride, opts, proofs_out, proof_stride, proof_lens,
+                            statuses, &ran);
+  if (!ran)  // refused as a whole: no proof was started, and every proof says so
+    for (size_t b = 0; b < n_proofs; b++) {
+      if (statuses) statuses[b] = r;
+      if (proof_lens) proof_lens[b] = 0;
+    }
+  return r;
 }
 
 // Byte length of the proof amdzk_create_proof_multi writes for n_circuits instances (amdzk_proof_size for one).

@@ -61,6 +61,7 @@ def lib():
         "amdzk_msm_g1": (i32, [vp, vp, i32, vp, sz, vp]),
         "amdzk_msm_g1_batch": (i32, [vp, vp, i32, C.POINTER(vp), sz, sz, vp]),
         "amdzk_msm_g1_dev": (i32, [vp, vp, i32, vp, sz, sz, sz, vp]),
+        "amdzk_msm_g1_cols_dev": (i32, [vp, vp, i32, C.POINTER(vp), sz, sz, sz, vp]),
         "amdzk_msm_g1_bases": (i32, [vp, vp, vp, sz, vp]),
         "amdzk_msm_g1_bases_batch": (i32, [vp, C.POINTER(vp), sz, vp, sz, vp]),
         "amdzk_msm_g1_bases_dev": (i32, [vp, vp, sz, sz, sz, vp, vp]),
@@ -92,6 +93,8 @@ def lib():
                                            vp, sz, C.POINTER(sz)]),
         "amdzk_create_proof_opts": (i32, [vp, C.POINTER(vp), sz, C.POINTER(C.POINTER(vp)), C.POINTER(C.POINTER(sz)), C.POINTER(vp), sz, vp,
                                           vp, sz, C.POINTER(sz)]),
+        "amdzk_create_proof_batch": (i32, [vp, C.POINTER(vp), sz, C.POINTER(C.POINTER(vp)), C.POINTER(C.POINTER(sz)), C.POINTER(vp), sz, vp,
+                                           vp, sz, C.POINTER(sz), C.POINTER(i32)]),
         "amdzk_proof_size_multi": (sz, [vp, sz, i32]),
         "amdzk_proof_random_count": (sz, [vp]),
         "amdzk_proof_size": (sz, [vp, i32]),
@@ -124,7 +127,7 @@ def lib():
     return L
 
 
-# include/amdzk.h: amdzk_phases, amdzk_phase_fn, amdzk_transcript, amdzk_proof_opts
+# include/amdzk.h: amdzk_phases, amdzk_phase_fn, amdzk_transcript, amdzk_proof_opts, amdzk_batch_opts
 class Phases(C.Structure):
     _fields_ = [("num_challenges", C.c_uint32), ("advice_phase", C.c_void_p), ("challenge_phase", C.c_void_p)]
 
@@ -141,6 +144,11 @@ class Transcript(C.Structure):
 class ProofOpts(C.Structure):
     _fields_ = [("size", C.c_size_t), ("transcript_kind", C.c_int), ("transcript", C.POINTER(Transcript)), ("phase_fn", PHASE_FN),
                 ("phase_user", C.c_void_p), ("rng_seed", C.c_uint64), ("scalars", C.c_void_p), ("scalar_count", C.c_size_t)]
+
+
+class BatchOpts(C.Structure):
+    _fields_ = [("size", C.c_size_t), ("transcript_kind", C.c_int), ("rng_seeds", C.c_void_p), ("scalars", C.POINTER(C.c_void_p)),
+                ("scalar_count", C.c_size_t)]
 
 
 def build_info():

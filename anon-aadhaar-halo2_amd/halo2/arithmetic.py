@@ -75,6 +75,16 @@ def best_multiexp_dev(ctx, srs, basis, dbuf, ncols, length, col_stride=None):
     return out
 
 
+def best_multiexp_cols_dev(ctx, srs, basis, col_ptrs, length, max_scratch_bytes=0):
+    """amdzk_msm_g1_cols_dev: one MSM per column over srs.{g|g_lagrange}[..length], column c read from the device address
+    col_ptrs[c] (ints) — columns in different buffers, one submission, no copy. max_scratch_bytes > 0 bounds one
+    submission's workspace (the columns are then cut into runs). Returns (ncols, 12) uint64 normalised Jacobian points."""
+    tab = (C.c_void_p * len(col_ptrs))(*[int(p) for p in col_ptrs])
+    out = np.zeros((len(col_ptrs), 12), np.uint64)
+    ctx._chk(ctx.L.amdzk_msm_g1_cols_dev(ctx.h, srs, basis, tab, len(col_ptrs), length, max_scratch_bytes, _ptr(out)))
+    return out
+
+
 def as_g1_array(bases):
     """(n, 8) uint64 C-contiguous: n G1Affine, x then y, Montgomery limbs; (0, 0) is the identity."""
     b = np.ascontiguousarray(bases, dtype=np.uint64)

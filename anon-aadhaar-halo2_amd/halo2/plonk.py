@@ -586,6 +586,56 @@ def create_proof_multi(ctx, pks, instances_list, d_advice_list, seed, advice_str
     return bytes(buf[: need.value])
 
 
+def create_proof_batch(ctx, pks, instances_list, d_advice_list, seeds, advice_stride=None, transcript=TRANSCRIPT_BLAKE2B, scalars=None,
+                       opts_size=None, proof_stride=None):
+    """amdzk_create_proof_batch: len(pks) independent proofs of one circuit in lock-step on ctx's stream — each step's
+    commitments of all proofs in one MSM, one host wait per step. pks: the key and workspace clones of it; instances_list[b],
+    d_advice_list[b], seeds[b]: proof b's, as for create_proof. scalars: per proof the caller's Fr::random draws
+    (create_proof_with_scalars) instead of seeds. Returns one entry per proof: its bytes — those of create_proof on the
+    same workspace — or the AmdzkError of a proof whose witness failed (the others are unaffected). A refused call
+    raises. opts_size / proof_stride: what to report to the library (tests)."""
+    N = len(pks)
+    n = 1 << pks[0].desc["k"] if N else 0
+    assert len(instances_list) == N and len(d_advice_list) == N
+    keep, inst_pp, lens_pp = [], (C.POINTER(C.c_void_p) * max(1, N))(), (C.POINTER(C.c_size_t) * max(1, N))()
+    for c, instances in enumerate(instances_list):
+        cols = [np.ascontiguousarray(col, dtype=np.uint64).reshape(-1, 4) for col in instances]
+        ptrs = (C.c_void_p * max(1, len(cols)))(*[col.ctypes.data if col.size else None for col in cols])
+        lens = (C.c_size_t * max(1, len(cols)))(*[col.shape[0] for col in cols])
+        keep += [cols, ptrs, lens]
+        inst_pp[c] = C.cast(ptrs, C.POINTER(C.c_void_p))
+        lens_pp[c] = C.cast(lens, C.POINTER(C.c_size_t))
+    keys = (C.c_void_p * max(1, N))(*[pk.h for pk in pks])
+    adv = (C.c_void_p * max(1, N))(*[d.ptr if d is not None else None for d in d_advice_list])
+    sd = np.ascontiguousarray(seeds, dtype=np.uint64).reshape(-1) if seeds is not None else None
+    assert sd is None or sd.shape[0] == N
+    sc_ptrs, sc_count = None, 0
+    if scalars is not None:
+        assert len(scalars) == N
+        sc = [np.ascontiguousarray(s_, dtype=np.uint64).reshape(-1, 4) for s_ in scalars]
+        sc_ptrs = (C.c_void_p * max(1, N))(*[a.ctypes.data for a in sc])
+        sc_count = min(a.shape[0] for a in sc) if sc else 0
+        keep += [sc]
+    opts = _ffi.BatchOpts(C.sizeof(_ffi.BatchOpts) if opts_size is None else opts_size, transcript,
+                          sd.ctypes.data if sd is not None and sd.size else None, sc_ptrs, sc_count)
+    stride = proof_stride if proof_stride is not None else (int(ctx.L.amdzk_proof_size(pks[0].h, transcript)) if N else 0)
+    buf = (C.c_uint8 * max(1, stride * N))()
+    lens_out = (C.c_size_t * max(1, N))()
+    st = (C.c_int * max(1, N))()
+    rc = ctx.L.amdzk_create_proof_batch(ctx.h, keys, N, inst_pp, lens_pp, adv, advice_stride or n, C.byref(opts), buf, stride, lens_out, st)
+    del keep
+    msg = ctx.L.amdzk_last_error(ctx.h).decode() if rc != 0 else ""
+    if rc != 0 and not msg.startswith("proof "):  # refused as a whole, or ended for all by the device: not one proof's failure
+        ctx._chk(rc)
+    out = []
+    for b in range(N):
+        if st[b] == 0:
+            out.append(bytes(buf[b * stride: b * stride + lens_out[b]]))
+        else:  # the library keeps the first failing proof's message; a later one gets its index and status
+            out.append(_ffi.AmdzkError(st[b], msg if msg.startswith("proof %d:" % b) else "proof %d: failed" % b))
+    return out
+
+
 def proof_size_multi(ctx, pk, n_circuits, transcript=TRANSCRIPT_BLAKE2B):
     return int(ctx.L.amdzk_proof_size_multi(pk.h, n_circuits, transcript))
 

@@ -155,6 +155,21 @@ int amdzk_msm_g1_dev(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const void
                      size_t ncols, size_t len, size_t col_stride,
                      uint64_t* out_jacobian /* host, ncols x 12 */);
 
+/* Same over the resident table, but column c is read from d_cols[c]: a HOST array of ncols device pointers (any device
+ * memory of this GPU, `len` Fr each) — columns that live in different buffers, committed in one submission without a copy.
+ * This is the MSM amdzk_create_proof_batch commits a step of a whole batch with; only the counting sort's scalar loads
+ * differ from amdzk_msm_g1_dev, and the points are equal word for word. Every d_cols[c] must be 16-byte aligned (the
+ * kernel reads a scalar as two 16-byte loads; 32-byte alignment is not needed) and readable for len * 32 bytes; columns may
+ * overlap or repeat. max_scratch_bytes: the workspace one submission may take; 0 = the library's default, which is what a
+ * caller wants (16 GiB: at the k = 15 shape a column costs about 15 MiB of counting-sort and bucket lists, so a batch of
+ * ten proofs' 1410 advice columns goes as two runs of 705 — five times the 141 columns that already fill the chip for one
+ * proof — and two contexts hold their scratch in a ninth of the MI355X's 288 GB). A batch that needs more, or has more than
+ * 65535 columns, is cut into the fewest equal runs of columns that fit; a smaller bound only makes more runs (tests use it
+ * to reach that path at small sizes). */
+int amdzk_msm_g1_cols_dev(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const void* const* d_cols,
+                          size_t ncols, size_t len, size_t max_scratch_bytes,
+                          uint64_t* out_jacobian /* host, ncols x 12 */);
+
 /* ---- MSM over the caller's own bases: arithmetic::best_multiexp(coeffs, bases) [UP] wherever the bases are not a resident
  * ParamsKZG — the verifier's MSMKZG::eval, a commitment under other parameters, a one-off check, any len (no power of
  * two needed). No amdzk_srs and no window table: one bucket set per window and sum_w 2^(c w) S_w (DESIGN.md §3.1
@@ -396,6 +411,43 @@ int amdzk_create_proof_opts(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_circu
                             const uint64_t* const* const* instances, const size_t* const* instance_lens,
                             const void* const* d_advice, size_t advice_stride, const amdzk_proof_opts* opts,
                             uint8_t* proof_out, size_t proof_cap, size_t* proof_len);
+
+/* ---- a batch of independent proofs of ONE circuit from one host thread, advanced in lock-step on the caller's stream:
+ * what a proving service, or a rank that owns a shard of a batch, calls instead of one thread and one ctx per proof in flight.
+ * Each step of create_proof runs for all proofs of the batch before the next: a step's commitments of ALL proofs are one MSM
+ * submission (amdzk_msm_g1_cols_dev's kernel: the columns stay in their workspaces), and each step has one host wait and
+ * one download for the batch instead of one per proof (DESIGN.md §3.4 lists what is merged). Every proof has its own
+ * transcript, RNG stream and challenges: proof b's bytes are exactly those of
+ *   amdzk_create_proof_ex(ctx, pks[b], instances[b], instance_lens[b], d_advice[b], advice_stride, rng_seeds[b], transcript_kind, ..)
+ * (with `scalars`: amdzk_create_proof_scalars), written to proofs_out + b*proof_stride with proof_lens[b] their length;
+ * proof_stride >= amdzk_proof_size(pk, transcript_kind). n_proofs = 1 is that call.
+ * pks[b]: the key or workspace clones of it (amdzk_pk_clone_workspace), pairwise different, all on this ctx's device — the
+ * rule of amdzk_create_proof_multi. Instance lengths may differ between proofs. The batch runs on the caller's stream only
+ * (no lanes, no latency mode of the commitments) whether the key was made with AMDZK_KEYGEN_SERIAL or not.
+ * size = sizeof(amdzk_batch_opts) as the caller compiled it. rng_seeds: n_proofs seeds (ChaCha20Rng::seed_from_u64 each), or
+ * scalars: per proof amdzk_proof_random_count(pk) caller-drawn Fr (scalar_count of them each); scalars wins if both are set.
+ * Refused with a message, the ctx stays usable: AMDZK_E_UNSUPPORTED for a key with later phases or challenges
+ * (amdzk_create_proof_opts proves those); AMDZK_E_INVALID for n_proofs = 0, null arguments, a too-small `size`, duplicate or
+ * foreign workspaces, proof_stride too small, neither seeds nor scalars. A refused call starts no proof and says so for
+ * every proof: statuses[b] (if given) = the returned status and proof_lens[b] (if given) = 0 for all b < n_proofs; its
+ * message starts with "create_proof_batch:", never with "proof <b>:".
+ * One bad witness does not cost the batch: a proof whose lookup input is not in its table, whose commitment is the identity
+ * or whose beta is 0 gets its status in statuses[b] (may be NULL) and proof_lens[b] = 0 and drops out; the others finish
+ * with their exact bytes. Returns AMDZK_OK if every proof succeeded, else the status of the first failing proof, whose usual
+ * message amdzk_last_error carries behind "proof <b>: ". After a failure the workspaces are quiet, as after a failed single
+ * proof. A HIP or out-of-memory error ends the whole batch with that status for every unfinished proof. */
+typedef struct amdzk_batch_opts {
+  size_t size;
+  int transcript_kind;             /* as amdzk_create_proof_ex, AMDZK_MULTIOPEN_GWC included */
+  const uint64_t* rng_seeds;       /* n_proofs seeds, or NULL if scalars is set */
+  const uint64_t* const* scalars;  /* optional: per proof, the caller's Fr::random draws (amdzk_create_proof_scalars) */
+  size_t scalar_count;
+} amdzk_batch_opts;
+int amdzk_create_proof_batch(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_proofs,
+                             const uint64_t* const* const* instances, const size_t* const* instance_lens,
+                             const void* const* d_advice, size_t advice_stride, const amdzk_batch_opts* opts,
+                             uint8_t* proofs_out, size_t proof_stride, size_t* proof_lens /* n_proofs */,
+                             int* statuses /* n_proofs, may be NULL */);
 
 /* ---- the PLONK layer function by function: the kernels create_proof runs,
  * callable on their own on device-resident columns — for a fork that replaces upstream one function at a time and

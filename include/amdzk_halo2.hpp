@@ -10,7 +10,7 @@
 //   plonk::{keygen_pk -> ProvingKey, create_proof}
 //   plonk::{Challenge, ConstraintSystem::advice_column_in / challenge_usable_after, Expression::Challenge} and
 //   transcript::TranscriptWrite — challenge phases and a caller-owned transcript (amdzk_keygen_phased,
-//   amdzk_create_proof_opts)
+//   amdzk_create_proof_opts); create_proof_batch: many independent proofs in lock-step (amdzk_create_proof_batch)
 //
 // Header-only over the C ABI of include/amdzk.h (link libamdzk.so); the same names, argument meaning and
 // derived quantities (query order, degree(), blinding_factors()) as upstream. Everything O(n) runs on
@@ -743,6 +743,64 @@ inline std::vector<uint8_t> create_proof(const Context& ctx, const std::vector<c
                                      proof.size(), &need));
   proof.resize(need);
   return proof;
+}
+
+// amdzk_create_proof_batch: keys.size() INDEPENDENT proofs of one circuit (own transcript, RNG stream and challenges each)
+// from one host thread, advanced in lock-step on the context's stream — every step's commitments of all proofs in one MSM,
+// one host wait per step. keys[b]: proof b's workspace — the key itself and ProvingKey::clone_workspace() handles, pairwise
+// different; instances[b], d_advice[b], rng_seeds[b] as for one proof, and proof b's bytes are create_proof's for the same
+// arguments. A proof whose witness fails (a lookup input not in its table, ...) comes back with its status and no bytes while
+// the others finish; `error` is set for the first failing proof (the library keeps one message). A refused call throws.
+struct BatchProof {
+  int status = AMDZK_OK;
+  std::vector<uint8_t> proof;
+  std::string error;
+};
+inline std::vector<BatchProof> create_proof_batch(const Context& ctx, const std::vector<const ProvingKey*>& keys,
+                                                  const std::vector<std::vector<std::vector<Fr>>>& instances,
+                                                  const std::vector<const void*>& d_advice, size_t advice_stride,
+                                                  const std::vector<uint64_t>& rng_seeds, Transcript transcript = Transcript::Blake2b,
+                                                  Multiopen multiopen = Multiopen::Shplonk) {
+  const size_t N = keys.size();
+  if (N == 0 || instances.size() != N || d_advice.size() != N || rng_seeds.size() != N)
+    throw Error(AMDZK_E_INVALID, "create_proof_batch: one key, instance set, witness and seed per proof");
+  const int format = (int)transcript | (int)multiopen;
+  std::vector<amdzk_pk*> pks(N);
+  std::vector<std::vector<const uint64_t*>> ptrs(N);
+  std::vector<std::vector<size_t>> lens(N);
+  std::vector<const uint64_t* const*> pp(N);
+  std::vector<const size_t*> lp(N);
+  for (size_t b = 0; b < N; b++) {
+    pks[b] = keys[b]->handle();
+    ptrs[b].assign(std::max<size_t>(1, instances[b].size()), nullptr);
+    lens[b].assign(std::max<size_t>(1, instances[b].size()), 0);
+    for (size_t i = 0; i < instances[b].size(); i++) {
+      ptrs[b][i] = instances[b][i].empty() ? nullptr : (const uint64_t*)instances[b][i].data();
+      lens[b][i] = instances[b][i].size();
+    }
+    pp[b] = ptrs[b].data();
+    lp[b] = lens[b].data();
+  }
+  amdzk_batch_opts opts = {};
+  opts.size = sizeof(opts);
+  opts.transcript_kind = format;
+  opts.rng_seeds = rng_seeds.data();
+  const size_t stride = amdzk_proof_size(pks[0], format);
+  std::vector<uint8_t> bytes(stride * N);
+  std::vector<size_t> got(N, 0);
+  std::vector<int> st(N, AMDZK_OK);
+  const int rc = amdzk_create_proof_batch(ctx.get(), pks.data(), N, pp.data(), lp.data(), d_advice.data(), advice_stride, &opts, bytes.data(),
+                                          stride, got.data(), st.data());
+  // refused as a whole (or ended for all by the device): the message is not one proof's ("proof <b>: ...")
+  if (rc != AMDZK_OK && std::string(amdzk_last_error(ctx.get())).rfind("proof ", 0) != 0) ctx.check(rc);
+  std::vector<BatchProof> out(N);
+  bool first = true;
+  for (size_t b = 0; b < N; b++) {
+    out[b].status = st[b];
+    if (st[b] == AMDZK_OK) out[b].proof.assign(bytes.begin() + b * stride, bytes.begin() + b * stride + got[b]);
+    else if (first) out[b].error = amdzk_last_error(ctx.get()), first = false;
+  }
+  return out;
 }
 
 // transcript::TranscriptWrite as far as create_proof uses it: implement it to own the transcript (`&mut T:
