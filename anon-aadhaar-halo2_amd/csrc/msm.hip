@@ -50,6 +50,8 @@ struct amdzk_srs {
   G1Affine* base[2] = {nullptr, nullptr};
 };
 
+uint32_t zk_srs_k(const amdzk_srs* srs) { return srs->k; }
+
 namespace {
 
 constexpr int MSM_THREADS = 256;

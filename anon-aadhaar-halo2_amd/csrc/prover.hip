@@ -25,6 +25,7 @@
 #include <string>
 
 #include "hostcrypto.hpp"
+#include "pkblob.hpp"
 #include "plonk_kernels.hpp"
 
 using namespace bn254;
@@ -39,6 +40,7 @@ int zk_msm_dev_xyzz(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const Fr* d
 int zk_msm_dev_xyzz_cols(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const Fr* const* d_col_ptrs, size_t ncols, size_t len,
                          size_t max_ws_bytes, G1X** d_out);
 int zk_msm_finish(amdzk_ctx* ctx, const G1X* d_res, size_t ncols, uint64_t* out_jac);
+uint32_t zk_srs_k(const amdzk_srs* srs);
 int zk_lagrange_to_coeff(amdzk_ctx* ctx, const amdzk_domain* d, const Fr* d_in, size_t in_stride, Fr* d_out, size_t out_stride, size_t ncols);
 extern "C" {
 int amdzk_domain_new(amdzk_ctx* ctx, uint32_t j, uint32_t k, amdzk_domain** out);
@@ -160,6 +162,9 @@ struct amdzk_pk {
   const amdzk_srs* srs = nullptr;
   Fr transcript_repr, omega, omega_inv;
   std::vector<G1Affine> fixed_commitments, perm_commitments;
+  // What keygen was given, as the caller passed it (the flattened amdzk_circuit arrays and the phase table): the header of
+  // the key file (amdzk_pk_write). Shared with workspace clones.
+  std::shared_ptr<const pkblob::Desc> src_desc;
 
   // device: key material
   Fr *fixed_lag = nullptr, *fixed_poly = nullptr, *fixed_coset = nullptr;
@@ -1074,8 +1079,28 @@ int amdzk_keygen_ex(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* c
 
 // keygen with ConstraintSystem::{advice_column_in, challenge_usable_after}'s phase table (NULL: every column in phase 0,
 // no challenges). The table is checked the way upstream's two functions assert, before anything is allocated.
+// One of perm_mapping (Assembly::mapping: the sigma values are computed here) and sigma_values (the Lagrange values
+// themselves, amdzk_keygen_sigma / amdzk_pk_read) feeds the permutation columns; everything behind their upload is shared.
+// fixed_values / sigma_values are only copied to the device: any alignment (amdzk_pk_read passes pointers into the file).
+static int keygen_common(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* c, const amdzk_phases* ph, const void* fixed_values,
+                         const uint32_t* perm_mapping, const void* sigma_values, bool from_sigma, const uint64_t transcript_repr[4],
+                         uint32_t flags, amdzk_pk** out);
+
 int amdzk_keygen_phased(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* c, const amdzk_phases* ph, const uint64_t* fixed_values,
                         const uint32_t* perm_mapping, const uint64_t transcript_repr[4], uint32_t flags, amdzk_pk** out) {
+  return keygen_common(ctx, srs, c, ph, fixed_values, perm_mapping, nullptr, false, transcript_repr, flags, out);
+}
+
+// keygen from the sigma columns (permutation::ProvingKey::permutations, Lagrange form) instead of the mapping: what a
+// process that has read a cached key holds. The values are taken as they are (upstream's read does not check them either).
+int amdzk_keygen_sigma(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* c, const amdzk_phases* ph, const uint64_t* fixed_values,
+                       const uint64_t* sigma_values, const uint64_t transcript_repr[4], uint32_t flags, amdzk_pk** out) {
+  return keygen_common(ctx, srs, c, ph, fixed_values, nullptr, sigma_values, true, transcript_repr, flags, out);
+}
+
+static int keygen_common(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* c, const amdzk_phases* ph, const void* fixed_values,
+                         const uint32_t* perm_mapping, const void* sigma_values, bool from_sigma, const uint64_t transcript_repr[4],
+                         uint32_t flags, amdzk_pk** out) {
   ZK_ENTER(ctx);
   if (!ctx) return AMDZK_E_INVALID;
   uint32_t nphases = 1;
@@ -1166,6 +1191,11 @@ int amdzk_keygen_phased(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circui
   }
   for (uint32_t e = 0; e < c->num_exprs; e++)
     pk->exprs.emplace_back(c->expr_words + c->expr_offsets[e], c->expr_words + c->expr_offsets[e + 1]);
+  {
+    auto desc = std::make_shared<pkblob::Desc>();
+    desc->assign(*c, ph);
+    pk->src_desc = desc;
+  }
   // constants: circuit | one theta beta gamma y 1/beta
   pk->consts.resize(c->num_constants);
   if (c->num_constants) memcpy(pk->consts.data(), c->constants, (size_t)c->num_constants * 32);
@@ -1256,7 +1286,14 @@ int amdzk_keygen_phased(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circui
     KG_TRY(zk_coeff_to_cosets_r261(ctx, pk->dom, pk->fixed_poly, n, pk->fixed_coset, ext, F));
     KG_TRY(commit_cols(ctx, pk, AMDZK_BASIS_G_LAGRANGE, pk->fixed_lag, F, pk->fixed_commitments));
   }
-  if (S) {
+  if (S && from_sigma) {
+    if (!sigma_values) {
+      amdzk_pk_free(ctx, pk);
+      ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: sigma_values is null");
+    }
+    KG_TRY(h2d(ctx, pk->sigma_lag, sigma_values, (size_t)S * n * 32));
+    ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
+  } else if (S) {
     if (!perm_mapping) {
       amdzk_pk_free(ctx, pk);
       ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: perm_mapping is null");
@@ -1284,6 +1321,8 @@ int amdzk_keygen_phased(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circui
       }
     KG_TRY(h2d(ctx, pk->sigma_lag, sig.data(), (size_t)S * n * 32));
     ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
+  }
+  if (S) {  // shared by both routes from here on
     KG_TRY(d2d(ctx, pk->sigma_poly, pk->sigma_lag, (size_t)S * n * 32));
     KG_TRY(amdzk_lagrange_to_coeff_dev(ctx, pk->dom, pk->sigma_poly, S, n));
     KG_TRY(zk_coeff_to_cosets_r261(ctx, pk->dom, pk->sigma_poly, n, pk->sigma_coset, ext, S));
@@ -3096,6 +3135,118 @@ int amdzk_pk_inspect(amdzk_ctx* ctx, const amdzk_pk* pk, int what, uint64_t* out
   if (what == 1) memcpy(out, ch, sizeof(ch));
   else if (what == 3) memcpy(out, pk->consts.data() + pk->c_chal0, cnt * 32);
   else ZK_TRY(d2h(ctx, out, src, cnt * 32));
+  return AMDZK_OK;
+}
+
+// The key's own columns, for a fork whose ProvingKey::write stores a key that was made on the device: what = 0 the fixed
+// columns (Lagrange), 1 the sigma columns (Lagrange), 2 / 3 the same as coefficients. A workspace clone shares these
+// buffers with its root key, so it returns the root's columns.
+int amdzk_pk_export(amdzk_ctx* ctx, const amdzk_pk* pk, int what, uint64_t* out, size_t cap, size_t* count) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  if (!pk || !count) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_export: null argument");
+  if (what < 0 || what > 3) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_export: unknown selector %d", what);
+  const Fr* src[4] = {pk->fixed_lag, pk->sigma_lag, pk->fixed_poly, pk->sigma_poly};
+  const size_t cnt = (size_t)((what & 1) ? pk->S : pk->F) * pk->n;
+  *count = cnt;
+  if (!out) return AMDZK_OK;
+  if (cap < cnt) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_export: buffer holds %zu elements, %zu needed", cap, cnt);
+  return d2h(ctx, out, src[what], cnt * 32);
+}
+
+// ---- the key file (csrc/pkblob.hpp has the layout, the header's writer and the host-only parser)
+// keygen takes a circuit on trust where pkblob::validate() does not (a query that no expression uses may name any column,
+// for one): such a key proves, but its file would be refused by amdzk_pk_read, so it is not written at all.
+size_t amdzk_pk_serialized_size(const amdzk_pk* pk) {
+  return pk && pk->src_desc && pkblob::validate(*pk->src_desc, nullptr) == AMDZK_OK ? pk->src_desc->serialized_size() : 0;
+}
+
+int amdzk_pk_write(amdzk_ctx* ctx, const amdzk_pk* pk, uint8_t* out, size_t cap, size_t* written) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  if (!pk || !pk->src_desc || (!out && !written)) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_write: null argument");
+  const pkblob::Desc& d = *pk->src_desc;
+  std::string why;
+  if (pkblob::validate(d, &why) != AMDZK_OK)
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_write: amdzk_pk_read would refuse this key's circuit (%s)", why.c_str());
+  const size_t need = d.serialized_size();
+  if (written) *written = need;
+  if (!out) return AMDZK_OK;
+  if (cap < need) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_write: buffer holds %zu bytes, %zu needed", cap, need);
+  d.write_header(out);
+  uint8_t* p = out + d.header_bytes();
+  memcpy(p, pk->transcript_repr.l, 32);
+  p += 32;
+  if (pk->F) memcpy(p, pk->fixed_commitments.data(), (size_t)pk->F * 64);
+  p += (size_t)pk->F * 64;
+  if (pk->S) memcpy(p, pk->perm_commitments.data(), (size_t)pk->S * 64);
+  p += (size_t)pk->S * 64;
+  ZK_TRY(d2h(ctx, p, pk->fixed_lag, (size_t)pk->F * pk->n * 32));
+  p += (size_t)pk->F * pk->n * 32;
+  ZK_TRY(d2h(ctx, p, pk->sigma_lag, (size_t)pk->S * pk->n * 32));
+  p += (size_t)pk->S * pk->n * 32;
+  pkblob::digest(out, (size_t)(p - out), p);
+  return AMDZK_OK;
+}
+
+// Pure host code: every check amdzk_pk_read makes before it touches the device.
+int amdzk_pk_blob_info(const uint8_t* data, size_t len, uint32_t* k, uint32_t* num_fixed, uint32_t* num_advice, uint32_t* num_perm_columns,
+                       uint32_t* num_challenges) {
+  pkblob::Desc d;
+  if (int rc = pkblob::parse(data, len, &d, nullptr, nullptr)) return rc;
+  if (k) *k = d.k;
+  if (num_fixed) *num_fixed = d.num_fixed;
+  if (num_advice) *num_advice = d.num_advice;
+  if (num_perm_columns) *num_perm_columns = d.num_perm_columns();
+  if (num_challenges) *num_challenges = d.num_challenges;
+  return AMDZK_OK;
+}
+
+// amdzk_pk_blob_info's verdict with its reason: the message amdzk_pk_read would leave in the ctx ("pk_read: digest mismatch
+// ..."), for a host without a device. msg (may be NULL) receives at most msg_cap bytes, NUL-terminated; "" for a good file.
+int amdzk_pk_blob_check(const uint8_t* data, size_t len, char* msg, size_t msg_cap) {
+  pkblob::Desc d;
+  std::string err;
+  const int rc = pkblob::parse(data, len, &d, nullptr, &err);
+  if (msg && msg_cap) snprintf(msg, msg_cap, "%s", err.c_str());
+  return rc;
+}
+
+// The file's header and columns through the tail keygen shares (keygen_common), then the commitments it computed against
+// the stored ones: they differ exactly when the parameters are not the ones the key was made under.
+int amdzk_pk_read(amdzk_ctx* ctx, const amdzk_srs* srs, const uint8_t* data, size_t len, uint32_t flags, amdzk_pk** out) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  if (!srs || !data || !out) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_read: null argument");
+  pkblob::Desc d;
+  pkblob::Layout lay;
+  std::string err;
+  if (int rc = pkblob::parse(data, len, &d, &lay, &err)) {
+    ctx->err = err;
+    return rc;
+  }
+  if (d.k != zk_srs_k(srs)) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_read: the key is for k = %u, the parameters are for k = %u", d.k, zk_srs_k(srs));
+  amdzk_circuit c;
+  amdzk_phases ph;
+  d.view(&c, &ph);
+  uint64_t repr[4];
+  memcpy(repr, data + lay.transcript_repr, 32);
+  amdzk_pk* pk = nullptr;
+  const int rc = keygen_common(ctx, srs, &c, d.has_phases ? &ph : nullptr, data + lay.fixed_values, nullptr, data + lay.sigma_values, true, repr,
+                               flags, &pk);
+  if (rc != AMDZK_OK) {
+    if (rc == AMDZK_E_INVALID) ctx->err = "pk_read: " + ctx->err;
+    return rc;
+  }
+  const bool same = (!pk->F || memcmp(pk->fixed_commitments.data(), data + lay.fixed_commitments, (size_t)pk->F * 64) == 0) &&
+                    (!pk->S || memcmp(pk->perm_commitments.data(), data + lay.perm_commitments, (size_t)pk->S * 64) == 0);
+  if (!same) {
+    amdzk_pk_free(ctx, pk);
+    ZK_FAIL(ctx, AMDZK_E_INVALID,
+            "pk_read: the commitments in the file are not those of its columns under these parameters: the key was made under other "
+            "parameters (another SRS)");
+  }
+  *out = pk;
   return AMDZK_OK;
 }
 

@@ -84,6 +84,13 @@ def lib():
         "amdzk_keygen": (i32, [vp, vp, vp, vp, vp, vp, C.POINTER(vp)]),
         "amdzk_keygen_ex": (i32, [vp, vp, vp, vp, vp, vp, u32, C.POINTER(vp)]),
         "amdzk_keygen_phased": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, C.POINTER(vp)]),
+        "amdzk_keygen_sigma": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, C.POINTER(vp)]),
+        "amdzk_pk_export": (i32, [vp, vp, i32, vp, sz, C.POINTER(sz)]),
+        "amdzk_pk_serialized_size": (sz, [vp]),
+        "amdzk_pk_write": (i32, [vp, vp, vp, sz, C.POINTER(sz)]),
+        "amdzk_pk_read": (i32, [vp, vp, vp, sz, u32, C.POINTER(vp)]),
+        "amdzk_pk_blob_info": (i32, [vp, sz, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]),
+        "amdzk_pk_blob_check": (i32, [vp, sz, vp, sz]),
         "amdzk_pk_free": (None, [vp, vp]),
         "amdzk_pk_commitments": (i32, [vp, vp, vp]),
         "amdzk_create_proof": (i32, [vp, vp, C.POINTER(vp), C.POINTER(sz), vp, sz, C.c_uint64, vp, sz, C.POINTER(sz)]),

@@ -414,6 +414,57 @@ class ProvingKey:
         self.h = h
         del keep
 
+    @classmethod
+    def from_sigma(cls, ctx, params, desc, fixed_values, sigma_values, transcript_repr, flags=None, phases=None):
+        """amdzk_keygen_sigma: the key from the sigma columns — permutation::ProvingKey::permutations, (num_perm_columns, n, 4)
+        uint64 Montgomery, Lagrange form — instead of Assembly.mapping: what a process that has read a cached key holds. The
+        same key as ProvingKey(...) from the mapping. flags: None = the modes from the environment."""
+        n = 1 << desc["k"]
+        cc, keep = flatten_circuit(desc)
+        fv = np.ascontiguousarray(fixed_values, dtype=np.uint64).reshape(desc["num_fixed"], n, 4) if desc["num_fixed"] else np.zeros((0, n, 4), np.uint64)
+        sg = None if sigma_values is None else np.ascontiguousarray(sigma_values, dtype=np.uint64).reshape(-1, n, 4)
+        assert sg is None or sg.shape[0] == len(desc["permutation_columns"])
+        tr = np.ascontiguousarray(transcript_repr, dtype=np.uint64).reshape(4)
+        ph, keep_ph = flatten_phases(desc) if phases is None else (phases, None)
+        h = C.c_void_p()
+        ctx._chk(ctx.L.amdzk_keygen_sigma(ctx.h, params.h, C.byref(cc), C.byref(ph) if ph is not None else None, fv.ctypes.data if fv.size else None,
+                                          sg.ctypes.data if sg is not None and sg.size else None, tr.ctypes.data,
+                                          _env_keygen_flags() if flags is None else int(flags), C.byref(h)))
+        pk = object.__new__(cls)
+        pk.ctx, pk.params, pk.desc, pk.h = ctx, params, desc, h
+        del keep, keep_ph
+        return pk
+
+    @classmethod
+    def read(cls, ctx, params, data, flags=None):
+        """amdzk_pk_read: the key of a file made by write(), under `params` (the SRS the key was made with: anything else is
+        refused). `desc` is rebuilt from the file. flags: None = the modes from the environment, as for a new key."""
+        buf = None if data is None else np.frombuffer(data, dtype=np.uint8)
+        h = C.c_void_p()
+        ctx._chk(ctx.L.amdzk_pk_read(ctx.h, params.h, buf.ctypes.data if buf is not None else None, buf.size if buf is not None else 0,
+                                     _env_keygen_flags() if flags is None else int(flags), C.byref(h)))
+        pk = object.__new__(cls)
+        pk.ctx, pk.params, pk.desc, pk.h = ctx, params, blob_desc(data), h
+        return pk
+
+    def export(self, what):
+        """amdzk_pk_export: the key's own columns as (columns, n, 4) uint64 Montgomery. 0: fixed (Lagrange), 1: sigma
+        (Lagrange), 2: fixed coefficients, 3: sigma coefficients. A clone returns its root key's columns."""
+        cnt = C.c_size_t(0)
+        self.ctx._chk(self.ctx.L.amdzk_pk_export(self.ctx.h, self.h, what, None, 0, C.byref(cnt)))
+        out = np.zeros((cnt.value, 4), np.uint64)
+        self.ctx._chk(self.ctx.L.amdzk_pk_export(self.ctx.h, self.h, what, out.ctypes.data, cnt.value, C.byref(cnt)))
+        return out.reshape(-1, 1 << self.desc["k"], 4)
+
+    def write(self):
+        """amdzk_pk_write: the key file (include/amdzk.h has the layout) as bytes."""
+        size = int(self.ctx.L.amdzk_pk_serialized_size(self.h))
+        out = np.zeros(size, np.uint8)
+        written = C.c_size_t(0)
+        self.ctx._chk(self.ctx.L.amdzk_pk_write(self.ctx.h, self.h, out.ctypes.data, size, C.byref(written)))
+        assert written.value == size
+        return out.tobytes()
+
     def clone_workspace(self):
         """amdzk_pk_clone_workspace: a key that shares this key's material and owns one more circuit instance's per-proof
         workspace — the second, third, ... instance of create_proof_multi, or one more proof of this circuit in flight.
@@ -468,6 +519,75 @@ class ProvingKey:
 KEYGEN_FULL_COSETS, KEYGEN_SERIAL = 1, 2  # include/amdzk.h AMDZK_KEYGEN_*
 TRANSCRIPT_BLAKE2B, TRANSCRIPT_KECCAK256_EVM = 0, 1
 MULTIOPEN_GWC = 0x100  # OR into `transcript`: poly::kzg::multiopen::ProverGWC instead of ProverSHPLONK
+
+
+def blob_info(data):
+    """amdzk_pk_blob_info: the shape of a key file — pure host code, no device needed. Runs every check ProvingKey.read makes
+    before it touches the device (magic, version, exact length, digest, a consistent header); AmdzkError for a file it
+    refuses, with the reason ProvingKey.read would give (amdzk_pk_blob_check: "pk_read: digest mismatch ...")."""
+    buf = np.frombuffer(data, dtype=np.uint8) if data is not None else None
+    ptr, size = (buf.ctypes.data, buf.size) if buf is not None and buf.size else (None, 0)
+    out = [C.c_uint32(0) for _ in range(5)]
+    rc = _ffi.lib().amdzk_pk_blob_info(ptr, size, *[C.byref(o) for o in out])
+    if rc != 0:
+        msg = C.create_string_buffer(256)
+        _ffi.lib().amdzk_pk_blob_check(ptr, size, msg, len(msg))
+        raise _ffi.AmdzkError(rc, msg.value.decode())
+    return dict(zip(("k", "num_fixed", "num_advice", "num_perm_columns", "num_challenges"), (o.value for o in out)))
+
+
+def blob_desc(data):
+    """The describe() dict in a key file's header (what flatten_circuit / flatten_phases had flattened), for a file
+    blob_info / ProvingKey.read accepted."""
+    mv, pos = memoryview(data), [12]  # behind the magic and the format version
+
+    def arr(count, dtype=np.uint32):
+        a = np.frombuffer(mv, dtype=dtype, count=count, offset=pos[0])
+        pos[0] += a.nbytes
+        return a
+
+    k, nf, na, ni, bf, deg = (int(v) for v in arr(6))
+    queries = [[(int(c), int(r)) for c, r in arr(2 * int(arr(1)[0]), np.int32).reshape(-1, 2)] for _ in range(3)]
+    ngates, nlookups, nexprs = (int(v) for v in arr(3))
+    shape, off = arr(2 * nlookups), arr(nexprs + 1)
+    words = arr(int(off[-1]))
+    rinv = pow(1 << 256, -1, R)
+    consts = [sum(int(x) << (64 * i) for i, x in enumerate(c)) * rinv % R for c in arr(4 * int(arr(1)[0]), np.uint64).reshape(-1, 4)]
+    perm = [(int(a), int(b)) for a, b in arr(2 * int(arr(1)[0])).reshape(-1, 2)]
+    names = {v: k_ for k_, v in _XOP.items()}
+
+    def expr(e):
+        st = []
+        for w in words[int(off[e]):int(off[e + 1])]:
+            op, pl = names[int(w) >> 24], int(w) & 0xFFFFFF
+            if op == "const":
+                st.append(("const", consts[pl]))
+            elif op == "challenge":
+                st.append(("challenge", pl))
+            elif op in ("fixed", "advice", "instance"):
+                st.append((op, pl >> 8, (pl & 0xFF) - 128))
+            elif op == "neg":
+                st.append(("neg", st.pop()))
+            elif op == "scaled":
+                st.append(("scaled", st.pop(), consts[pl]))
+            else:
+                b = st.pop()
+                st.append((op, st.pop(), b))
+        return st[0]
+
+    exprs = [expr(e) for e in range(nexprs)]
+    lookups, e = [], ngates
+    for l in range(nlookups):
+        a, b = int(shape[2 * l]), int(shape[2 * l + 1])
+        lookups.append({"inputs": exprs[e:e + a], "tables": exprs[e + a:e + a + b]})
+        e += a + b
+    phases = {}
+    if int(arr(1, np.uint8)[0]):
+        nch = int(arr(1)[0])
+        phases = {"advice_column_phase": [int(v) for v in arr(na, np.uint8)], "challenge_phase": [int(v) for v in arr(nch, np.uint8)]}
+    return {**phases, "k": k, "num_fixed": nf, "num_advice": na, "num_instance": ni, "blinding_factors": bf, "cs_degree": deg,
+            "advice_queries": queries[0], "fixed_queries": queries[1], "instance_queries": queries[2], "gates": exprs[:ngates],
+            "lookups": lookups, "permutation_columns": perm}
 
 
 def _trampolines(synthesize, tobj, errors):

@@ -305,6 +305,65 @@ typedef struct amdzk_phases {
 int amdzk_keygen_phased(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* circuit, const amdzk_phases* phases,
                         const uint64_t* fixed_values, const uint32_t* perm_mapping, const uint64_t transcript_repr[4],
                         uint32_t flags, amdzk_pk** out);
+/* ---- keys that outlive the process: ProvingKey::read / ProvingKey::write [UP]. Upstream stores and reads back the sigma
+ * columns (permutation::ProvingKey::permutations, Lagrange form), not the mapping they were made from.
+ *
+ * amdzk_keygen_sigma is amdzk_keygen_phased with those columns in place of perm_mapping: sigma_values is
+ * num_perm_columns x 2^k Fr, Montgomery, Lagrange form, column after column — sigma_i(omega^j) = delta^i' omega^j' for
+ * (i', j') = mapping[i][j]. Both routes share everything behind the upload of these columns, and a key made either way
+ * from the same circuit is the same key. The values are NOT checked to be a permutation of delta^i omega^j, as upstream's
+ * read does not check them. phases may be NULL. Refusals are keygen's: a null sigma_values with num_perm_columns > 0 is
+ * AMDZK_E_INVALID, and the ctx stays usable. */
+int amdzk_keygen_sigma(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* circuit, const amdzk_phases* phases /* may be NULL */,
+                       const uint64_t* fixed_values, const uint64_t* sigma_values, const uint64_t transcript_repr[4], uint32_t flags,
+                       amdzk_pk** out);
+/* The key's columns, for a fork's ProvingKey::write of a key made on the device. what: 0 the fixed columns (Lagrange),
+ * 1 the sigma columns (Lagrange), 2 the fixed columns as coefficients, 3 the sigma columns as coefficients; num_fixed (or
+ * num_perm_columns) x 2^k Fr, column after column. out = NULL queries *count (in Fr elements), as amdzk_pk_inspect does;
+ * cap is in Fr elements. A workspace clone returns its root key's columns. */
+int amdzk_pk_export(amdzk_ctx* ctx, const amdzk_pk* pk, int what, uint64_t* out, size_t cap /* Fr */, size_t* count);
+/* The key file: everything keygen took except the SRS and the mode flags (AMDZK_KEYGEN_* describe a deployment, not a key:
+ * amdzk_pk_read takes them as amdzk_keygen_ex does). Little-endian, no padding, deterministic for a given key, and
+ * self-delimiting — `len` must be exactly the size the header implies:
+ *   "AMDZKPK\0" (8 bytes) | format version u32 = 1
+ *   amdzk_circuit in declaration order, as keygen's caller passed it: k, num_fixed, num_advice, num_instance,
+ *     blinding_factors, cs_degree (u32 each) | num_advice_queries u32, advice_queries 2 x i32 each | the same for
+ *     fixed_queries and instance_queries | num_gates, num_lookups, num_exprs (u32) | lookup_shape 2 x num_lookups u32 |
+ *     expr_offsets (num_exprs + 1) u32 | expr_words expr_offsets[num_exprs] u32 | num_constants u32, constants 4 x u64 each |
+ *     num_perm_columns u32, perm_columns 2 x u32 each
+ *   has-phases u8 (1: keygen was given an amdzk_phases); if 1: num_challenges u32 | advice_phase num_advice x u8 |
+ *     challenge_phase num_challenges x u8
+ *   transcript_repr 4 x u64
+ *   fixed commitments num_fixed x 64 B | permutation commitments num_perm_columns x 64 B (as amdzk_pk_commitments)
+ *   fixed columns num_fixed x 2^k x 32 B | sigma columns num_perm_columns x 2^k x 32 B (Lagrange, Montgomery)
+ *   BLAKE2b-512 (64 B) of all bytes before it, personalisation "amdzk_pk_blob_v1" (hashlib.blake2b(person=...))
+ * Cosets and compiled programs are not stored: amdzk_pk_read rebuilds them with keygen's own transforms and commitments,
+ * then compares the commitments it computed with the stored ones — a mismatch (AMDZK_E_INVALID, the message says that the
+ * key was made under other parameters) is how a key file paired with the wrong SRS is caught. A key that was read is a
+ * root key: amdzk_pk_clone_workspace, every amdzk_create_proof* and amdzk_pk_write (the same bytes again) work on it.
+ * amdzk_pk_read keeps no pointer into `data`. Refused with AMDZK_E_INVALID and a message that starts "pk_read:", the ctx
+ * usable afterwards: bad magic or version, any length mismatch or truncation, a digest mismatch, an internally
+ * inconsistent header (the checks keygen makes on a circuit, and column / constant / challenge indices out of range), k
+ * different from the SRS's. Columns are limited to 65536 of a kind (fixed, advice, instance, permutation: an expression
+ * word addresses a column with 16 bits).
+ * These header checks are stricter than keygen, which takes a circuit on trust where nothing it runs depends on it: every
+ * query, used by an expression or not, must name a column of the circuit and a rotation in -128 .. 127, and every
+ * expression must be a well-formed stack program. So that write followed by read never fails, amdzk_pk_write applies the
+ * same checks to the key it is given: a key keygen accepted but amdzk_pk_read would refuse is not written
+ * (AMDZK_E_INVALID, "pk_write: ..." with the reason), and amdzk_pk_serialized_size is 0 for it.
+ * amdzk_pk_write: out = NULL queries *written; cap >= amdzk_pk_serialized_size(pk). Works on a clone (its root's file). */
+size_t amdzk_pk_serialized_size(const amdzk_pk* pk);
+int amdzk_pk_write(amdzk_ctx* ctx, const amdzk_pk* pk, uint8_t* out, size_t cap, size_t* written);
+int amdzk_pk_read(amdzk_ctx* ctx, const amdzk_srs* srs, const uint8_t* data, size_t len, uint32_t flags, amdzk_pk** out);
+/* The shape of a key file. Pure host code, callable without a device (like amdzk_msm_g1_bases_plan): it runs every check
+ * amdzk_pk_read makes before touching the device — the digest included — and allocates nothing in proportion to a count
+ * that `len` does not back. AMDZK_E_INVALID for a file amdzk_pk_read would refuse. Any output pointer may be NULL. */
+int amdzk_pk_blob_info(const uint8_t* data, size_t len, uint32_t* k, uint32_t* num_fixed, uint32_t* num_advice,
+                       uint32_t* num_perm_columns, uint32_t* num_challenges);
+/* amdzk_pk_blob_info's verdict with its reason, also without a device: the same return code, and in msg (at most msg_cap
+ * bytes, NUL-terminated; may be NULL) the message amdzk_pk_read would leave in its ctx for this file — "pk_read: bad magic
+ * ...", "pk_read: digest mismatch ...", "pk_read: length mismatch ..." — or "" for a file it accepts. */
+int amdzk_pk_blob_check(const uint8_t* data, size_t len, char* msg, size_t msg_cap);
 void amdzk_pk_free(amdzk_ctx* ctx, amdzk_pk* pk);
 int amdzk_pk_check_affinity(amdzk_ctx* ctx, const amdzk_pk* pk);
 /* VerifyingKey commitments: fixed columns (num_fixed x G1Affine), permutation (num_perm_columns x G1Affine). */

@@ -647,12 +647,7 @@ class ProvingKey {
     const uint64_t* fx = flat.empty() ? nullptr : (const uint64_t*)flat.data();
     const uint32_t* mp = num_perm_ ? assembly.mapping() : nullptr;
     if (cd.phased) {
-      uint32_t f = flags;
-      if (flags == kEnvDefaults) {  // as amdzk_keygen reads them
-        const char *fc = std::getenv("AMDZK_FULL_COSETS"), *se = std::getenv("AMDZK_SERIAL");
-        f = (fc && (std::atoi(fc) != 0 || !*fc) ? AMDZK_KEYGEN_FULL_COSETS : 0u) | (se && std::atoi(se) != 0 ? AMDZK_KEYGEN_SERIAL : 0u);
-      }
-      ctx_.check(amdzk_keygen_phased(ctx_.get(), params.handle(), &cd.c, &cd.phases, fx, mp, transcript_repr.l, f, &h_));
+      ctx_.check(amdzk_keygen_phased(ctx_.get(), params.handle(), &cd.c, &cd.phases, fx, mp, transcript_repr.l, resolve(flags), &h_));
     } else if (flags == kEnvDefaults) ctx_.check(amdzk_keygen(ctx_.get(), params.handle(), &cd.c, fx, mp, transcript_repr.l, &h_));
     else ctx_.check(amdzk_keygen_ex(ctx_.get(), params.handle(), &cd.c, fx, mp, transcript_repr.l, flags, &h_));
   }
@@ -661,6 +656,64 @@ class ProvingKey {
   }
   ProvingKey(const ProvingKey&) = delete;
   ProvingKey& operator=(const ProvingKey&) = delete;
+  // ProvingKey::read for a fork that parsed upstream's own file: the key from the sigma columns it holds
+  // (pk.permutation.permutations, Lagrange form, one vector of 2^k per permutation column) instead of the Assembly
+  // (amdzk_keygen_sigma). The same key as the constructor's.
+  static std::unique_ptr<ProvingKey> from_sigma(const Context& ctx, const ParamsKZG& params, const ConstraintSystem& cs,
+                                                const std::vector<std::vector<Fr>>& fixed, const std::vector<std::vector<Fr>>& sigma,
+                                                const Fr& transcript_repr, uint32_t flags = kEnvDefaults) {
+    std::unique_ptr<ProvingKey> pk(new ProvingKey(ctx, cs.num_fixed, cs.permutation_columns.size(), cs.num_advice, params.k()));
+    const size_t n = (size_t)1 << pk->k_;
+    if (fixed.size() != pk->num_fixed_ || sigma.size() != pk->num_perm_) throw Error(AMDZK_E_INVALID, "keygen: column count");
+    auto flatten = [n](const std::vector<std::vector<Fr>>& cols) {
+      std::vector<Fr> flat(cols.size() * n, Fr::zero());
+      for (size_t c = 0; c < cols.size(); c++) {
+        if (cols[c].size() > n) throw Error(AMDZK_E_INVALID, "keygen: column longer than 2^k");
+        std::copy(cols[c].begin(), cols[c].end(), flat.begin() + c * n);
+      }
+      return flat;
+    };
+    const std::vector<Fr> fx = flatten(fixed), sg = flatten(sigma);
+    CircuitData cd(cs, pk->k_);
+    ctx.check(amdzk_keygen_sigma(ctx.get(), params.handle(), &cd.c, cd.phased ? &cd.phases : nullptr, fx.empty() ? nullptr : (const uint64_t*)fx.data(),
+                                 sg.empty() ? nullptr : (const uint64_t*)sg.data(), transcript_repr.l, resolve(flags), &pk->h_));
+    return pk;
+  }
+  // The key of a file write() made (amdzk_pk_read), under the parameters the key was made with: a file paired with another
+  // SRS, a damaged or truncated one is refused with a message that starts "pk_read:".
+  static std::unique_ptr<ProvingKey> read(const Context& ctx, const ParamsKZG& params, const std::vector<uint8_t>& data,
+                                          uint32_t flags = kEnvDefaults) {
+    std::unique_ptr<ProvingKey> pk(new ProvingKey(ctx, 0, 0, 0, params.k()));  // amdzk_pk_read refuses a file of another k
+    ctx.check(amdzk_pk_read(ctx.get(), params.handle(), data.data(), data.size(), resolve(flags), &pk->h_));
+    // The shape from the key that was read, not from amdzk_pk_blob_info: that would hash the whole file a second time.
+    const size_t n = (size_t)1 << pk->k_;
+    size_t count = 0;
+    ctx.check(amdzk_pk_export(ctx.get(), pk->h_, 0, nullptr, 0, &count));
+    pk->num_fixed_ = count / n;
+    ctx.check(amdzk_pk_export(ctx.get(), pk->h_, 1, nullptr, 0, &count));
+    pk->num_perm_ = count / n;
+    uint32_t na = 0;
+    std::memcpy(&na, data.data() + 20, 4);  // magic (8), format version, k, num_fixed, then num_advice: the file was accepted
+    pk->num_advice_ = na;
+    return pk;
+  }
+  // The key file (include/amdzk.h has the layout): everything keygen took except the SRS and the mode flags.
+  std::vector<uint8_t> write() const {
+    std::vector<uint8_t> out(amdzk_pk_serialized_size(h_));
+    size_t written = 0;
+    ctx_.check(amdzk_pk_write(ctx_.get(), h_, out.data(), out.size(), &written));
+    out.resize(written);
+    return out;
+  }
+  // amdzk_pk_export: what = 0 the fixed columns (Lagrange), 1 the sigma columns (Lagrange), 2 / 3 the same as coefficients;
+  // column c is [c * 2^k, (c + 1) * 2^k) — what a fork's ProvingKey::write stores of a key made on the device.
+  std::vector<Fr> export_columns(int what) const {
+    size_t count = 0;
+    ctx_.check(amdzk_pk_export(ctx_.get(), h_, what, nullptr, 0, &count));
+    std::vector<Fr> out(count, Fr::zero());
+    ctx_.check(amdzk_pk_export(ctx_.get(), h_, what, count ? (uint64_t*)out.data() : nullptr, count, &count));
+    return out;
+  }
   // amdzk_pk_clone_workspace: a key sharing this key's material that owns one more circuit instance's per-proof
   // workspace (the second, third, ... instance of a multi-circuit create_proof, or one more proof in flight). Must not
   // outlive this key.
@@ -681,6 +734,11 @@ class ProvingKey {
 
  private:
   ProvingKey(const Context& ctx, size_t nf, size_t np, size_t na, uint32_t k) : ctx_(ctx), num_fixed_(nf), num_perm_(np), num_advice_(na), k_(k) {}
+  static uint32_t resolve(uint32_t flags) {  // kEnvDefaults: the modes as amdzk_keygen reads them from the environment
+    if (flags != kEnvDefaults) return flags;
+    const char *fc = std::getenv("AMDZK_FULL_COSETS"), *se = std::getenv("AMDZK_SERIAL");
+    return (fc && (std::atoi(fc) != 0 || !*fc) ? AMDZK_KEYGEN_FULL_COSETS : 0u) | (se && std::atoi(se) != 0 ? AMDZK_KEYGEN_SERIAL : 0u);
+  }
   const Context& ctx_;
   size_t num_fixed_, num_perm_, num_advice_;
   uint32_t k_;
