@@ -7,6 +7,7 @@
 
 #include <chrono>
 #include <map>
+#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
@@ -178,6 +179,12 @@ inline hipError_t zk_host_wait(amdzk_ctx* ctx, hipStream_t s) {
 }
 // Host waits for an event already recorded (the timer's stop event).
 inline hipError_t zk_host_wait_event(amdzk_ctx* ctx, hipEvent_t evt) { return zk_waits_poll(ctx) ? zk_event_poll(evt) : hipEventSynchronize(evt); }
+
+// basis slots of an amdzk_srs: AMDZK_BASIS_G, AMDZK_BASIS_G_LAGRANGE, AMDZK_BASIS_G_LAGRANGE_PREFIX
+constexpr int AMDZK_NUM_BASES = 3;
+// The prefix-sum basis of srs (msm.hip), built on ctx's stream the first time it is asked for and resident from then on:
+// every maker of a proving key with permutation columns calls this. Safe from several threads (one guard in the SRS).
+int zk_srs_ensure_prefix(amdzk_ctx* ctx, const amdzk_srs* srs);
 
 int zk_ws_reserve(amdzk_ctx* ctx, int slot, size_t bytes, void** out);
 int zk_pinned_reserve(amdzk_ctx* ctx, size_t bytes, void** out);

@@ -45,10 +45,16 @@ struct amdzk_srs {
   // [basis] -> W x n affine points, window-major: T[w][i] = 2^(c*w) * bases[i]. Coordinates are packed
   // canonical integers in Montgomery radix 2^261 (fp29.cuh) — the form the level-1 accumulation kernel
   // multiplies in; (0, 0) is still the identity.
-  G1Affine* table[2] = {nullptr, nullptr};
+  G1Affine* table[AMDZK_NUM_BASES] = {nullptr, nullptr, nullptr};
   // [basis] -> the n bases themselves in halo2curves' radix-2^256 form (ParamsKZG::get_g, write, downsize)
-  G1Affine* base[2] = {nullptr, nullptr};
+  G1Affine* base[AMDZK_NUM_BASES] = {nullptr, nullptr, nullptr};
+  // Slot AMDZK_BASIS_G_LAGRANGE_PREFIX — S_i = g_lagrange[0] + ... + g_lagrange[i] — is derived, never uploaded or stored:
+  // zk_srs_ensure_prefix builds it once, under this guard, when the first proving key with permutation columns is made.
+  std::mutex prefix_guard;
+  double prefix_build_ms = 0;  // what that one build took (host wall clock, kernels included)
 };
+// device bytes of one basis slot: the window table and the bases
+static size_t srs_basis_bytes(const amdzk_srs* s) { return ((size_t)s->W + 1) * s->n * sizeof(G1Affine); }
 
 uint32_t zk_srs_k(const amdzk_srs* srs) { return srs->k; }
 
@@ -945,6 +951,17 @@ __global__ __launch_bounds__(64) void msm_window_combine_kernel(const G1X* win, 
 }  // namespace
 
 // ---------------------------------------------------------------------------------- host side
+// table <- the W window multiples of the n points at base (both on the device), radix 2^261; on ctx's stream
+static int srs_fill_table(amdzk_ctx* ctx, const amdzk_srs* s, const G1Affine* base, G1Affine* table) {
+  ZK_HIP(ctx, hipMemcpyAsync(table, base, s->n * sizeof(G1Affine), hipMemcpyDeviceToDevice, ctx->stream));
+  dim3 grid((unsigned)((s->n + 255) / 256)), block(256);
+  for (uint32_t w = 1; w < s->W; w++)
+    ZK_LAUNCH(ctx, "msm_table_next", table_next_kernel, grid, block, 0, table + (size_t)(w - 1) * s->n, table + (size_t)w * s->n, s->n, s->c);
+  const size_t count = (size_t)s->W * s->n;  // all windows are built: switch the whole table to radix 2^261
+  ZK_LAUNCH(ctx, "msm_table_to_r261", table_to_r261_kernel, dim3((unsigned)((count + 255) / 256)), block, 0, table, count);
+  return AMDZK_OK;
+}
+
 static int srs_build(amdzk_ctx* ctx, const void* g, const void* g_lagrange, bool src_on_device, uint32_t k, amdzk_srs** out) {
   if (!out || (!g && !g_lagrange)) ZK_FAIL(ctx, AMDZK_E_INVALID, "srs: null argument");
   if (k > 26) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "srs: k %u > 26", k);
@@ -975,13 +992,7 @@ static int srs_build(amdzk_ctx* ctx, const void* g, const void* g_lagrange, bool
     }
     ZK_HIP(ctx, hipMemcpyAsync(s->base[b], src[b], s->n * sizeof(G1Affine), src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
                                ctx->stream));
-    ZK_HIP(ctx, hipMemcpyAsync(s->table[b], s->base[b], s->n * sizeof(G1Affine), hipMemcpyDeviceToDevice, ctx->stream));
-    dim3 grid((unsigned)((s->n + 255) / 256)), block(256);
-    for (uint32_t w = 1; w < s->W; w++)
-      ZK_LAUNCH(ctx, "msm_table_next", table_next_kernel, grid, block, 0, s->table[b] + (size_t)(w - 1) * s->n,
-                s->table[b] + (size_t)w * s->n, s->n, s->c);
-    const size_t count = (size_t)s->W * s->n;  // all windows are built: switch the whole table to radix 2^261
-    ZK_LAUNCH(ctx, "msm_table_to_r261", table_to_r261_kernel, dim3((unsigned)((count + 255) / 256)), block, 0, s->table[b], count);
+    ZK_TRY(srs_fill_table(ctx, s, s->base[b], s->table[b]));
   }
   ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));  // source buffers may be released by the caller
   *out = s;
@@ -1339,9 +1350,127 @@ int zk_srs_get(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, uint64_t* out) {
   return AMDZK_OK;
 }
 
+// ---- the prefix-sum basis S_i = g_lagrange[0] + ... + g_lagrange[i] (AMDZK_BASIS_G_LAGRANGE_PREFIX).
+// Abel summation: sum_i z[i] L_i = sum_i d[i] S_i with d[i] = z[i] - z[i+1], d[n-1] = z[n-1] — a column that is constant
+// over long runs of rows (a permutation product away from the copy cycles) has as few non-zero d[i] as it has jumps, and
+// the counting sort drops zero scalars before they become entries. S depends on the SRS alone.
+// An EC prefix scan in chunks of PREFIX_CHUNK: one thread sums a chunk serially (its total), the totals are scanned the same
+// way one level up (in place, XYZZ) until one chunk is left, and on the way down every thread redoes its chunk from the
+// scanned total in front of it. Two additions per point and one inversion (the affine form the window table is built
+// from); start-up work, once per SRS. x_add / x_add_affine are complete (equal points, opposite points, the identity).
+namespace {
+constexpr uint32_t PREFIX_CHUNK = 16;
+__device__ __forceinline__ G1X prefix_step(const G1X& acc, const G1Affine* in, size_t i) { return x_add_affine(acc, ld_aff(in + i)); }
+__device__ __forceinline__ G1X prefix_step(const G1X& acc, const G1X* in, size_t i) { return x_add(acc, ld_x(in + i)); }
+// totals[t] = in[t * CHUNK] + ... + in[min((t + 1) * CHUNK, m) - 1]
+template <class P>
+__global__ __launch_bounds__(64) void prefix_chunk_total_kernel(const P* in, size_t m, G1X* totals) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x, lo = t * PREFIX_CHUNK;
+  if (lo >= m) return;
+  const size_t hi = lo + PREFIX_CHUNK < m ? lo + PREFIX_CHUNK : m;
+  G1X acc = G1X::inf();
+#pragma unroll 1
+  for (size_t i = lo; i < hi; i++) acc = prefix_step(acc, in, i);
+  st_x(totals + t, acc);
+}
+// Inclusive scan of chunk t, started from carry[t - 1] (the scanned totals; null: one chunk, nothing in front).
+// XYZZ, in place (the upper levels): a[i] <- carry + a[lo] + ... + a[i].
+__global__ __launch_bounds__(64) void prefix_apply_x_kernel(G1X* a, size_t m, const G1X* carry) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x, lo = t * PREFIX_CHUNK;
+  if (lo >= m) return;
+  const size_t hi = lo + PREFIX_CHUNK < m ? lo + PREFIX_CHUNK : m;
+  G1X acc = (carry && t) ? ld_x(carry + t - 1) : G1X::inf();
+#pragma unroll 1
+  for (size_t i = lo; i < hi; i++) {
+    acc = prefix_step(acc, a, i);
+    st_x(a + i, acc);
+  }
+}
+// The bottom level: affine in, affine out (one inversion per point, as ecfft_finish_kernel does).
+__global__ __launch_bounds__(64) void prefix_apply_affine_kernel(const G1Affine* in, size_t m, const G1X* carry, G1Affine* out) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x, lo = t * PREFIX_CHUNK;
+  if (lo >= m) return;
+  const size_t hi = lo + PREFIX_CHUNK < m ? lo + PREFIX_CHUNK : m;
+  G1X acc = (carry && t) ? ld_x(carry + t - 1) : G1X::inf();
+#pragma unroll 1
+  for (size_t i = lo; i < hi; i++) {
+    acc = prefix_step(acc, in, i);
+    st_aff(out + i, x_to_affine(acc));
+  }
+}
+inline size_t prefix_chunks(size_t m) { return (m + PREFIX_CHUNK - 1) / PREFIX_CHUNK; }
+inline dim3 prefix_grid(size_t m) { return dim3((unsigned)((prefix_chunks(m) + 63) / 64)); }
+
+// d_out[i] = d_in[0] + ... + d_in[i], n affine points each (may not alias), on ctx's stream.
+int ec_prefix_sums(amdzk_ctx* ctx, const G1Affine* d_in, size_t n, G1Affine* d_out) {
+  // the levels' totals, one behind the other: level l holds prefix_chunks(size of level l - 1) points
+  std::vector<size_t> sizes;
+  size_t total = 0;
+  for (size_t m = n; m > PREFIX_CHUNK;) {
+    m = prefix_chunks(m);
+    sizes.push_back(m);
+    total += m;
+  }
+  G1X* tot = nullptr;
+  if (total) ZK_TRY(zk_ws_reserve(ctx, 3, total * sizeof(G1X), (void**)&tot));
+  std::vector<G1X*> lvl;
+  for (size_t l = 0, o = 0; l < sizes.size(); o += sizes[l], l++) lvl.push_back(tot + o);
+  const dim3 block(64);
+  // up: chunk totals of every level that has more than one chunk
+  for (size_t l = 0; l < sizes.size(); l++) {
+    if (l == 0) ZK_LAUNCH(ctx, "srs_prefix_total", prefix_chunk_total_kernel<G1Affine>, prefix_grid(n), block, 0, d_in, n, lvl[0]);
+    else ZK_LAUNCH(ctx, "srs_prefix_total", prefix_chunk_total_kernel<G1X>, prefix_grid(sizes[l - 1]), block, 0, (const G1X*)lvl[l - 1], sizes[l - 1], lvl[l]);
+  }
+  // down: the top level is one chunk; every level below starts its chunks from the scanned totals above it
+  for (size_t l = sizes.size(); l-- > 0;)
+    ZK_LAUNCH(ctx, "srs_prefix_apply", prefix_apply_x_kernel, prefix_grid(sizes[l]), block, 0, lvl[l], sizes[l],
+              l + 1 < sizes.size() ? (const G1X*)lvl[l + 1] : (const G1X*)nullptr);
+  ZK_LAUNCH(ctx, "srs_prefix_apply", prefix_apply_affine_kernel, prefix_grid(n), block, 0, d_in, n,
+            sizes.empty() ? (const G1X*)nullptr : (const G1X*)lvl[0], d_out);
+  return AMDZK_OK;
+}
+}  // namespace
+
+static int srs_fill_table(amdzk_ctx* ctx, const amdzk_srs* s, const G1Affine* base, G1Affine* table);
+
+int zk_srs_ensure_prefix(amdzk_ctx* ctx, const amdzk_srs* srs_c) {
+  if (!srs_c) ZK_FAIL(ctx, AMDZK_E_INVALID, "srs: null argument");
+  amdzk_srs* s = const_cast<amdzk_srs*>(srs_c);  // the derived slot is the one thing a key adds to the parameters it is made on
+  const int P = AMDZK_BASIS_G_LAGRANGE_PREFIX;
+  std::lock_guard<std::mutex> lock(s->prefix_guard);
+  if (s->table[P]) return AMDZK_OK;
+  if (!s->base[AMDZK_BASIS_G_LAGRANGE]) ZK_FAIL(ctx, AMDZK_E_INVALID, "srs: the prefix-sum basis needs g_lagrange, which was not uploaded");
+  const auto t0 = std::chrono::steady_clock::now();
+  G1Affine *base = nullptr, *table = nullptr;
+  hipError_t e = hipMalloc((void**)&base, s->n * sizeof(G1Affine));
+  if (e == hipSuccess) e = hipMalloc((void**)&table, (size_t)s->W * s->n * sizeof(G1Affine));
+  if (e != hipSuccess) {
+    if (base) hipFree(base);
+    ZK_FAIL(ctx, AMDZK_E_NOMEM, "srs: hipMalloc(%zu) for the prefix-sum basis failed: %s", srs_basis_bytes(s), hipGetErrorString(e));
+  }
+  int r = ec_prefix_sums(ctx, s->base[AMDZK_BASIS_G_LAGRANGE], s->n, base);
+  if (r == AMDZK_OK) r = srs_fill_table(ctx, s, base, table);
+  if (r == AMDZK_OK && zk_host_wait(ctx, ctx->stream) != hipSuccess) {
+    ctx->err = "srs: building the prefix-sum basis failed on the device";
+    r = AMDZK_E_HIP;
+  }
+  if (r != AMDZK_OK) {
+    (void)hipStreamSynchronize(ctx->stream);
+    hipFree(table);
+    hipFree(base);
+    return r;
+  }
+  s->base[P] = base;
+  s->table[P] = table;  // published last: complete on the device
+  s->prefix_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (getenv("AMDZK_TRACE_TIME"))
+    fprintf(stderr, "[amdzk-time] srs prefix-sum basis k=%u: %.3f ms, %zu bytes\n", s->k, s->prefix_build_ms, srs_basis_bytes(s));
+  return AMDZK_OK;
+}
+
 void zk_srs_free(amdzk_ctx*, amdzk_srs* s) {
   if (!s) return;
-  for (int b = 0; b < 2; b++) {
+  for (int b = 0; b < AMDZK_NUM_BASES; b++) {
     if (s->table[b]) hipFree(s->table[b]);
     if (s->base[b]) hipFree(s->base[b]);
   }
@@ -1533,11 +1662,19 @@ static int msm_group(amdzk_ctx* ctx, const G1Affine* table, uint32_t table_n, bo
   return AMDZK_OK;
 }
 
+static int msm_check_basis(amdzk_ctx* ctx, const amdzk_srs* srs, int basis) {
+  if (!srs || basis < 0 || basis >= AMDZK_NUM_BASES) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm: no parameters or basis %d unknown", basis);
+  if (srs->table[basis]) return AMDZK_OK;
+  if (basis == AMDZK_BASIS_G_LAGRANGE_PREFIX)
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "msm: the prefix-sum basis has not been built (it is made with the first proving key that has permutation columns)");
+  ZK_FAIL(ctx, AMDZK_E_INVALID, "msm: basis %d not uploaded", basis);
+}
+
 // ncols MSMs of length len over srs->table[basis]; results (XYZZ) land in d_out[ncols]. ctx->msm_l1_evt is recorded
 // when the level-1 kernel ends (zk_stream_after_l1).
 int zk_msm_dev_xyzz(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const Fr* d_scalars, size_t ncols,
                     size_t len, size_t col_stride, G1X** d_out) {
-  if (!srs || basis < 0 || basis > 1 || !srs->table[basis]) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm: basis %d not uploaded", basis);
+  ZK_TRY(msm_check_basis(ctx, srs, basis));
   if (len > srs->n) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm: len %zu > 2^k = %zu", len, srs->n);
   if (ncols == 0 || ncols > 65535) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm: ncols %zu out of range", ncols);
   if ((uint64_t)srs->W * srs->n >= (1ull << 31)) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "msm: table too large for 31-bit ids");
@@ -1567,7 +1704,7 @@ int zk_msm_dev_xyzz(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const Fr* d
 static constexpr size_t MSM_COLS_WS_BYTES = (size_t)16 << 30;
 int zk_msm_dev_xyzz_cols(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const Fr* const* d_col_ptrs, size_t ncols, size_t len,
                          size_t max_ws_bytes, G1X** d_out) {
-  if (!srs || basis < 0 || basis > 1 || !srs->table[basis]) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm: basis %d not uploaded", basis);
+  ZK_TRY(msm_check_basis(ctx, srs, basis));
   if (len > srs->n) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm: len %zu > 2^k = %zu", len, srs->n);
   if (!d_col_ptrs || ncols == 0) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm: no column pointer table or ncols == 0");
   if ((uint64_t)srs->W * srs->n >= (1ull << 31)) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "msm: table too large for 31-bit ids");

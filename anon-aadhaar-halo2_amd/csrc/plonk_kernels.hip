@@ -446,6 +446,17 @@ __global__ __launch_bounds__(256) void mul_elem_kernel(Fr* a, const Fr* b, size_
     st_fr(a + i, fr29_mul_std(ld_fr(a + i), ld_fr(b + i)));
 }
 
+// d[c][i] = z[c][i] - z[c][i + 1] for i < n - 1, d[c][n - 1] = z[c][n - 1]: the scalars of a column's commitment over the
+// prefix sums of the Lagrange basis (msm.hip, AMDZK_BASIS_G_LAGRANGE_PREFIX). Zero wherever the column does not change.
+__global__ __launch_bounds__(256) void row_diff_kernel(const Fr* z, Fr* d, size_t n, size_t z_stride, size_t d_stride) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const Fr* zc = z + (size_t)blockIdx.y * z_stride;
+  Fr v = ld_fr(zc + i);
+  if (i + 1 < n) v = sub(v, ld_fr(zc + i + 1));
+  st_fr(d + (size_t)blockIdx.y * d_stride + i, v);
+}
+
 // ------------------------------------------------------------------------------ running products
 // Exclusive prefix product of each column, three steps. Block = 256 threads x SCAN_E elements.
 constexpr int SCAN_E = 8;
@@ -1020,6 +1031,14 @@ int zk_mul_elem(amdzk_ctx* ctx, Fr* d_a, const Fr* d_b, size_t total) {
   unsigned gx = (unsigned)((total + 255) / 256);
   if (gx > 4096) gx = 4096;
   if (total) ZK_LAUNCH(ctx, "mul_elem", mul_elem_kernel, dim3(gx), dim3(256), 0, d_a, d_b, total);
+  return AMDZK_OK;
+}
+
+// d_d[c] = the row differences of d_z[c] (row_diff_kernel), ncols columns of n rows; the two may not overlap
+int zk_row_diff(amdzk_ctx* ctx, const Fr* d_z, Fr* d_d, size_t ncols, size_t n, size_t z_stride, size_t d_stride) {
+  if (ncols == 0 || n == 0) return AMDZK_OK;
+  if (ncols > 65535) ZK_FAIL(ctx, AMDZK_E_INVALID, "row_diff: %zu columns > 65535", ncols);
+  ZK_LAUNCH(ctx, "row_diff", row_diff_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)ncols), dim3(256), 0, d_z, d_d, n, z_stride, d_stride);
   return AMDZK_OK;
 }
 

@@ -86,6 +86,7 @@ int zk_chacha20_blind_rows(amdzk_ctx* ctx, bn254::Fr* d_cols, size_t col_stride,
                            uint64_t counter0, uint32_t draw_stride, const bn254::Fr& r3);
 int zk_batch_invert(amdzk_ctx* ctx, bn254::Fr* d_a, bn254::Fr* d_scratch, size_t total);
 int zk_mul_elem(amdzk_ctx* ctx, bn254::Fr* d_a, const bn254::Fr* d_b, size_t total);
+int zk_row_diff(amdzk_ctx* ctx, const bn254::Fr* d_z, bn254::Fr* d_d, size_t ncols, size_t n, size_t z_stride, size_t d_stride);
 size_t zk_scan_totals_elems(size_t n, size_t ncols);
 int zk_running_product(amdzk_ctx* ctx, bn254::Fr* d_cols, size_t ncols, size_t n, size_t col_stride, bool chain, size_t u,
                        bn254::Fr* d_tmp);

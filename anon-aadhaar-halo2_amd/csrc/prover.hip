@@ -1153,6 +1153,7 @@ static int keygen_common(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circu
   pk->chunk = pk->degree - 2;
   pk->nsets = (pk->S + pk->chunk - 1) / pk->chunk;
   pk->qdeg = pk->degree - 1;
+  if (pk->S) KG_TRY(zk_srs_ensure_prefix(ctx, srs));  // the permutation products are committed over it (Prover::perm_commit)
   if (ph) {
     pk->nphases = nphases;
     pk->num_challenges = ph->num_challenges;
@@ -2222,12 +2223,16 @@ struct Prover {
     ZK_TRY(zk_mul_elem(ctx, pk->zp(), pk->frac, (size_t)ns * n));
     ZK_TRY(zk_running_product(ctx, pk->zp(), ns, n, n, true, usable, pk->scan_tmp));
     tick("  perm: running product");
-    return blind(M, pk->zp(), ns, n - bf, bf, draws.perm_product(ci), draws.col);
+    ZK_TRY(blind(M, pk->zp(), ns, n - bf, bf, draws.perm_product(ci), draws.col));
+    // What is committed is the columns' row differences, over the prefix sums of g_lagrange: the same points (Abel
+    // summation), and a product column only changes on the rows of a copy cycle and in its blinding tail. frac is free
+    // from the running product until the next proof's fractions; zp() keeps the values for the transforms and openings.
+    return zk_row_diff(M, pk->zp(), pk->frac, ns, n, n, n);
   }
   int perm_commit(size_t ci) {
     amdzk_pk* const pk = pks[ci];
     if (serial) ZK_TRY(transforms_on_B(pk, M, (size_t)A + I + 2 * L, ns));
-    return commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->zp(), ns, cm_zp[ci]);
+    return commit_begin(M, AMDZK_BASIS_G_LAGRANGE_PREFIX, pk->frac, ns, cm_zp[ci]);
   }
   // 3. + 4. permutation grand products on M, lookup grand products on C (they depend on beta and gamma only, not on
   // each other). (Several instances: every instance's permutation products are committed before the first lookup product.)
@@ -2673,10 +2678,11 @@ struct Gang {
   // the host-pointer MSM / NTT entry points, which no proof uses. Valid until the next call (the slot may grow).
   int scratch(size_t bytes, char** out) { return zk_ws_reserve(ctx, 2, bytes, (void**)out); }
 
-  // The commitment batches the live members left in their sinks, as ONE submission per basis (a step has one basis), then
+  // The commitment batches the live members left in their sinks, as ONE submission per basis (a step has one basis; the products' step
+  // two: the lookup products over g_lagrange, the permutation products' differences over its prefix sums), then
   // per member in the order it deferred them: into the Commit it named, or written to its transcript under the label.
   int commit_step() {
-    for (int basis = 0; basis <= 1; basis++) {
+    for (int basis = 0; basis < AMDZK_NUM_BASES; basis++) {
       std::vector<const Fr*> cols;
       for (auto& m : members)
         if (m->live)
@@ -2786,7 +2792,7 @@ struct Gang {
       ZK_TRY(m.P->put_consts({{&amdzk_pk::c_beta, beta}, {&amdzk_pk::c_gamma, gamma}, {&amdzk_pk::c_betainv, inv(beta)}}));
       return m.P->products_enqueue_serial();
     }));
-    GANG_TRY(commit_step());  // permutation and lookup products together: both over g_lagrange
+    GANG_TRY(commit_step());  // the lookup products over g_lagrange, the permutation products' differences over its prefix sums
     GANG_TRY(each([&](Member& m) -> int {
       ZK_TRY(m.P->products_write());
       ZK_TRY(m.P->write_points(m.P->cm_rnd.pts, "random_poly"));

@@ -8,6 +8,7 @@ from . import arithmetic
 
 BASIS_G = 0
 BASIS_G_LAGRANGE = 1
+BASIS_G_LAGRANGE_PREFIX = 2  # prefix sums of g_lagrange: resident once a key with permutation columns exists (MSM only)
 
 
 class ParamsKZG:

@@ -49,6 +49,13 @@ typedef enum {
 /* basis selector for MSM: ParamsKZG.g (monomial) or ParamsKZG.g_lagrange */
 #define AMDZK_BASIS_G 0
 #define AMDZK_BASIS_G_LAGRANGE 1
+/* The inclusive prefix sums of g_lagrange, S_i = g_lagrange[0] + ... + g_lagrange[i]: sum_i z[i] g_lagrange[i] =
+ * sum_i d[i] S_i with d[i] = z[i] - z[i+1] (d[n-1] = z[n-1]), so a column that rarely changes from row to row is
+ * committed through its few non-zero differences (the permutation products, create_proof). Derived, not uploaded and not
+ * in the SRS file: built once per amdzk_srs when the first proving key whose circuit has permutation columns is made on
+ * it (amdzk_keygen*, amdzk_pk_read); until then an MSM over this basis fails with AMDZK_E_INVALID. MSM only:
+ * amdzk_srs_get does not serve it. */
+#define AMDZK_BASIS_G_LAGRANGE_PREFIX 2
 
 /* flags for amdzk_ntt_fr* */
 #define AMDZK_NTT_SCALE_NINV 1u /* multiply the result by 1/2^log_n (EvaluationDomain::ifft's divisor) */
