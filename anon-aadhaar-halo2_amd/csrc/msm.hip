@@ -57,6 +57,8 @@ struct amdzk_srs {
 static size_t srs_basis_bytes(const amdzk_srs* s) { return ((size_t)s->W + 1) * s->n * sizeof(G1Affine); }
 
 uint32_t zk_srs_k(const amdzk_srs* srs) { return srs->k; }
+// an MSM over this basis can run (multiopen.hip asks before it touches the caller's transcript)
+bool zk_srs_has_basis(const amdzk_srs* srs, int basis) { return srs && basis >= 0 && basis < AMDZK_NUM_BASES && srs->table[basis]; }
 
 namespace {
 

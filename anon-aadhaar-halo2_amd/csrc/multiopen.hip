@@ -1,0 +1,586 @@
+// poly::kzg::multiopen::{ProverSHPLONK, ProverGWC}::create_proof [UP] over the CALLER's
+// polynomials, points and transcript: amdzk_multiopen_dev / amdzk_multiopen_plan (include/amdzk.h).
+//
+// The arithmetic is the proof path's (prover.hip Prover::{gwc, shplonk, shplonk_final}) on the same kernels — zk_poly_eval,
+// zk_lincomb, zk_kate_div_from, the MSM over AMDZK_BASIS_G — with its own host side: points are arbitrary field elements
+// instead of rotations of x, polynomials are the caller's buffers instead of a key's workspace, scratch is the ctx's
+// (workspace slot 6, one reservation per call whose size the plan reports) instead of a key's, and nothing is capped at 16
+// sets or points or at a key's pointer table: launches whose grid.y would pass 65535 are cut into runs by the host.
+// Everything runs on the caller's stream. No kernel lives here.
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <array>
+#include <map>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "hostcrypto.hpp"
+#include "plonk_kernels.hpp"
+
+using namespace bn254;
+
+struct amdzk_srs;
+uint32_t zk_srs_k(const amdzk_srs* srs);
+bool zk_srs_has_basis(const amdzk_srs* srs, int basis);
+int zk_msm_dev_xyzz(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const Fr* d_scalars, size_t ncols, size_t len, size_t col_stride,
+                    G1X** d_out);
+int zk_msm_finish(amdzk_ctx* ctx, const G1X* d_res, size_t ncols, uint64_t* out_jac);
+
+namespace {
+
+constexpr size_t MO_MAX_GRID_Y = 65535;  // polynomials per division launch, columns per commitment batch
+constexpr int MO_WS_SLOT = 6;            // the function-by-function calls' slot (plonk_kernels.hip upload_ptrs_and_frs)
+
+using Canon = std::array<uint32_t, 8>;
+Canon canon_of(const uint64_t* mont) {
+  Fr a;
+  memcpy(a.l, mont, 32);
+  const Fr c = from_mont(a);
+  Canon o;
+  memcpy(o.data(), c.l, 32);
+  return o;
+}
+bool canon_less(const Canon& a, const Canon& b) {
+  for (int i = 7; i >= 0; i--)
+    if (a[i] != b[i]) return a[i] < b[i];
+  return false;
+}
+struct CanonLess {
+  bool operator()(const Canon& a, const Canon& b) const { return canon_less(a, b); }
+};
+
+// What both schemes are built from: the distinct point VALUES the queries name (ids in first-seen query order, which is
+// GWC's output order; rank = position in ascending canonical order, which is the order of upstream's BTreeSets), the
+// distinct queried polynomials ("commitments", first seen first) and the distinct (polynomial, point) pairs, whose
+// evaluations the call needs once each.
+struct MoSets {
+  size_t n = 0;
+  bool gwc = false;
+  std::vector<uint32_t> dp_index;  // distinct point -> one point index that carries its value
+  std::vector<uint32_t> dp_rank, rank_dp;
+  std::vector<uint32_t> q_dp;    // query -> distinct point
+  std::vector<uint32_t> q_pair;  // query -> (polynomial, point) pair
+  std::vector<std::pair<uint32_t, uint32_t>> pairs;  // pair -> (polynomial index, distinct point)
+  std::vector<uint32_t> pair_query;                  // pair -> its first query
+  // SHPLONK: construct_intermediate_sets
+  std::vector<uint32_t> com_poly;                                        // commitment -> polynomial index
+  std::vector<std::vector<std::pair<uint32_t, uint32_t>>> com_pts;       // commitment -> (rank, pair), ascending rank
+  struct Set {
+    std::vector<uint32_t> ranks;  // its points, ascending
+    std::vector<uint32_t> coms;   // its commitments, first seen first
+  };
+  std::vector<Set> sets;
+  size_t set_points = 0, maxm = 0;  // sum_i |S_i|, max_i |S_i|
+  // GWC: the queries of every distinct point, in their original order
+  std::vector<std::vector<uint32_t>> gw;
+  uint32_t n_sets = 0, n_out = 0;
+  // the call's one reservation: polynomials first, then the pointer tables, then the field-element tables
+  size_t poly_count = 0, ptr_count = 0, fr_count = 0, ptr_bytes = 0, scratch_bytes = 0;
+};
+
+bool mul_ok(size_t a, size_t b, size_t* out) { return !__builtin_mul_overflow(a, b, out); }
+bool add_ok(size_t a, size_t b, size_t* out) { return !__builtin_add_overflow(a, b, out); }
+
+// The sets and sizes of one call. why: the refusal's text behind "multiopen: ".
+int mo_build(const uint64_t* points, size_t n_points, const amdzk_open_query* queries, size_t n_queries, size_t n_polys, uint32_t k, int scheme,
+             MoSets& s, uint32_t* set_of_poly, char why[200]) {
+  why[0] = 0;
+  if (!points || !queries) return snprintf(why, 200, "null argument"), AMDZK_E_INVALID;
+  if (scheme != 0 && scheme != AMDZK_MULTIOPEN_GWC) return snprintf(why, 200, "unknown scheme %d", scheme), AMDZK_E_INVALID;
+  if (n_queries == 0) return snprintf(why, 200, "no queries"), AMDZK_E_INVALID;
+  if (k > 30) return snprintf(why, 200, "k = %u out of range", k), AMDZK_E_INVALID;
+  if (n_queries >= UINT32_MAX || n_polys >= UINT32_MAX || n_points >= UINT32_MAX)
+    return snprintf(why, 200, "more than 2^32 - 2 queries, polynomials or points"), AMDZK_E_INVALID;
+  for (size_t i = 0; i < n_queries; i++)
+    if (queries[i].poly >= n_polys || queries[i].point >= n_points)
+      return snprintf(why, 200, "query %zu names polynomial %u of %zu, point %u of %zu", i, queries[i].poly, n_polys, queries[i].point, n_points),
+             AMDZK_E_INVALID;
+  s.n = (size_t)1 << k;
+  s.gwc = scheme == AMDZK_MULTIOPEN_GWC;
+  // distinct point values among the queried indices
+  std::vector<uint32_t> dp_of_index(n_points, UINT32_MAX);
+  std::map<Canon, uint32_t, CanonLess> dp_of_value;
+  std::vector<Canon> dp_canon;
+  s.q_dp.resize(n_queries);
+  for (size_t i = 0; i < n_queries; i++) {
+    const uint32_t pi = queries[i].point;
+    if (dp_of_index[pi] == UINT32_MAX) {
+      const Canon c = canon_of(points + 4 * (size_t)pi);
+      auto it = dp_of_value.find(c);
+      if (it == dp_of_value.end()) {
+        it = dp_of_value.emplace(c, (uint32_t)s.dp_index.size()).first;
+        s.dp_index.push_back(pi);
+        dp_canon.push_back(c);
+      }
+      dp_of_index[pi] = it->second;
+    }
+    s.q_dp[i] = dp_of_index[pi];
+  }
+  const size_t ndp = s.dp_index.size();
+  s.dp_rank.resize(ndp);
+  s.rank_dp.resize(ndp);
+  {
+    uint32_t r = 0;
+    for (auto& e : dp_of_value) s.rank_dp[r] = e.second, s.dp_rank[e.second] = r++;  // the map iterates in ascending canonical order
+  }
+  // distinct (polynomial, point) pairs
+  std::map<std::pair<uint32_t, uint32_t>, uint32_t> pair_of;
+  s.q_pair.resize(n_queries);
+  for (size_t i = 0; i < n_queries; i++) {
+    const std::pair<uint32_t, uint32_t> key{queries[i].poly, s.q_dp[i]};
+    auto it = pair_of.find(key);
+    if (it == pair_of.end()) {
+      it = pair_of.emplace(key, (uint32_t)s.pairs.size()).first;
+      s.pairs.push_back(key);
+      s.pair_query.push_back((uint32_t)i);
+    }
+    s.q_pair[i] = it->second;
+  }
+  const size_t E = s.pairs.size();
+  if (set_of_poly)
+    for (size_t i = 0; i < n_polys; i++) set_of_poly[i] = UINT32_MAX;
+  size_t ptrs = 0, frs = 0, polys = 0;
+  bool ok = true;
+  if (s.gwc) {
+    s.gw.resize(ndp);
+    for (size_t i = 0; i < n_queries; i++) {
+      s.gw[s.q_dp[i]].push_back((uint32_t)i);
+      if (set_of_poly) set_of_poly[queries[i].poly] = std::min(set_of_poly[queries[i].poly], s.q_dp[i]);
+    }
+    s.n_sets = s.n_out = (uint32_t)ndp;
+    // pointers: the pairs to evaluate | every query's polynomial | the W_z;  elements: points and results of the
+    // evaluations | v^j per query | sum_j v^j eval per point | the points
+    polys = ndp;
+    ptrs = E + n_queries + ndp;
+    frs = 2 * E + n_queries + 2 * ndp;
+  } else {
+    std::vector<uint32_t> com_of_poly(n_polys, UINT32_MAX);
+    for (size_t i = 0; i < n_queries; i++) {
+      const uint32_t p = queries[i].poly;
+      if (com_of_poly[p] == UINT32_MAX) {
+        com_of_poly[p] = (uint32_t)s.com_poly.size();
+        s.com_poly.push_back(p);
+        s.com_pts.emplace_back();
+      }
+      auto& v = s.com_pts[com_of_poly[p]];
+      const std::pair<uint32_t, uint32_t> e{s.dp_rank[s.q_dp[i]], s.q_pair[i]};
+      auto pos = std::lower_bound(v.begin(), v.end(), e, [](const auto& a, const auto& b) { return a.first < b.first; });
+      if (pos == v.end() || pos->first != e.first) v.insert(pos, e);
+    }
+    std::map<std::vector<uint32_t>, uint32_t> set_of_ranks;
+    for (size_t c = 0; c < s.com_poly.size(); c++) {
+      std::vector<uint32_t> ranks;
+      for (auto& e : s.com_pts[c]) ranks.push_back(e.first);
+      auto it = set_of_ranks.find(ranks);
+      if (it == set_of_ranks.end()) {
+        it = set_of_ranks.emplace(ranks, (uint32_t)s.sets.size()).first;
+        s.sets.emplace_back();
+        s.sets.back().ranks = ranks;
+      }
+      s.sets[it->second].coms.push_back((uint32_t)c);
+      if (set_of_poly) set_of_poly[s.com_poly[c]] = it->second;
+    }
+    for (auto& st : s.sets) s.set_points += st.ranks.size(), s.maxm = std::max(s.maxm, st.ranks.size());
+    s.n_sets = (uint32_t)s.sets.size();
+    s.n_out = 2;
+    const size_t S = s.sets.size(), C = s.com_poly.size(), P = s.set_points;
+    // pointers: the pairs to evaluate | the polynomials set after set | destinations and sources of the P divisions |
+    // the L_i and h(X) | l(X);  elements: points and results of the evaluations | y^j per commitment | the roots, the
+    // R_i (maxm coefficients each) and the v^i c_it of the P divisions | the S + 1 final coefficients, the constant term, u
+    size_t low = 0;
+    ok = mul_ok(P, s.maxm, &low);
+    polys = S + P + 1;
+    ptrs = E + C + 2 * P + S + 2;
+    ok = ok && add_ok(2 * E + C + 2 * P + S + 3, low, &frs);
+  }
+  size_t poly_bytes = 0, fr_bytes = 0;
+  ok = ok && mul_ok(polys, s.n * 32, &poly_bytes) && mul_ok(frs, 32, &fr_bytes);
+  s.poly_count = polys;
+  s.ptr_count = ptrs;
+  s.fr_count = frs;
+  s.ptr_bytes = (ptrs * sizeof(void*) + 255) / 256 * 256;
+  ok = ok && add_ok(poly_bytes, s.ptr_bytes, &s.scratch_bytes) && add_ok(s.scratch_bytes, fr_bytes, &s.scratch_bytes);
+  if (!ok) return snprintf(why, 200, "the scratch size of this shape does not fit 64 bits"), AMDZK_E_NOMEM;
+  return AMDZK_OK;
+}
+
+// The call's tables on the device: pointers and field elements are appended to a host image in the order the launches
+// use them and uploaded run by run; the image lives as long as the call, so no copy outlives its source.
+struct MoTables {
+  void** d_ptrs = nullptr;
+  Fr* d_frs = nullptr;
+  std::vector<const void*> ptrs;
+  std::vector<Fr> frs;
+  size_t ptrs_up = 0, frs_up = 0;  // what has been uploaded
+  size_t ptr_cap = 0, fr_cap = 0;
+  size_t put(const void* p) { return ptrs.push_back(p), ptrs.size() - 1; }
+  size_t put(const Fr& f) { return frs.push_back(f), frs.size() - 1; }
+  size_t skip_frs(size_t cnt) {  // room the device fills
+    const size_t at = frs.size();
+    frs.resize(at + cnt, Fr::zero());
+    return at;
+  }
+  int upload(amdzk_ctx* ctx) {
+    if (ptrs.size() > ptr_cap || frs.size() > fr_cap) ZK_FAIL(ctx, AMDZK_E_INVALID, "multiopen: internal error: the tables outgrew the plan");
+    if (ptrs.size() > ptrs_up)
+      ZK_HIP(ctx, hipMemcpyAsync(d_ptrs + ptrs_up, ptrs.data() + ptrs_up, (ptrs.size() - ptrs_up) * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
+    if (frs.size() > frs_up)
+      ZK_HIP(ctx, hipMemcpyAsync(d_frs + frs_up, frs.data() + frs_up, (frs.size() - frs_up) * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+    ptrs_up = ptrs.size();
+    frs_up = frs.size();
+    return AMDZK_OK;
+  }
+};
+
+Fr eval_small(const std::vector<Fr>& poly, const Fr& x) {
+  Fr acc = Fr::zero();
+  for (size_t i = poly.size(); i-- > 0;) acc = add(mul(acc, x), poly[i]);
+  return acc;
+}
+
+struct Call {
+  amdzk_ctx* ctx;
+  const amdzk_srs* srs;
+  const void* const* d_polys;
+  const uint64_t* points;
+  const MoSets& s;
+  zkhost::CallbackWrite T;
+  MoTables tab;
+  Fr* d_poly = nullptr;        // poly_count x n
+  std::vector<Fr> pair_eval;   // per (polynomial, point) pair
+  std::vector<Fr> query_eval;  // per query (GWC)
+  std::vector<G1Affine> written;
+  const size_t n;
+
+  Call(amdzk_ctx* ctx, const amdzk_srs* srs, const void* const* d_polys, const uint64_t* points, const MoSets& s, const amdzk_transcript& t)
+      : ctx(ctx), srs(srs), d_polys(d_polys), points(points), s(s), T(t), n(s.n) {
+    // the reservations are exact: a vector that grew would move under a copy in flight
+    tab.ptrs.reserve(s.ptr_count);
+    tab.frs.reserve(s.fr_count);
+    tab.ptr_cap = s.ptr_count;
+    tab.fr_cap = s.fr_count;
+  }
+  Fr point(uint32_t dp) const {
+    Fr z;
+    memcpy(z.l, points + 4 * (size_t)s.dp_index[dp], 32);
+    return z;
+  }
+  int t_ok() {
+    if (T.failed) ZK_FAIL(ctx, AMDZK_E_INVALID, "multiopen: the caller's transcript reported an error");
+    return AMDZK_OK;
+  }
+  int challenge(Fr* c) {
+    *c = T.squeeze_challenge();
+    return t_ok();
+  }
+  // commit ncols consecutive polynomials over AMDZK_BASIS_G and write them in order
+  int commit_write(const Fr* d_cols, size_t ncols, const char* label) {
+    for (size_t first = 0; first < ncols; first += MO_MAX_GRID_Y) {
+      const size_t cnt = std::min(MO_MAX_GRID_Y, ncols - first);
+      G1X* d_res = nullptr;
+      ZK_TRY(zk_msm_dev_xyzz(ctx, srs, AMDZK_BASIS_G, d_cols + first * n, cnt, n, n, &d_res));
+      std::vector<uint64_t> jac(12 * cnt);
+      ZK_TRY(zk_msm_finish(ctx, d_res, cnt, jac.data()));
+      for (size_t i = 0; i < cnt; i++) {
+        const G1Jac* j = reinterpret_cast<const G1Jac*>(&jac[12 * i]);
+        G1Affine p;
+        p.x = j->z.is_zero() ? Fq::zero() : j->x;
+        p.y = j->z.is_zero() ? Fq::zero() : j->y;
+        if (!T.write_point(p))
+          ZK_FAIL(ctx, AMDZK_E_INVALID, "multiopen: %s commitment %zu is the identity (cannot write points at infinity to the transcript)", label,
+                  first + i);
+        ZK_TRY(t_ok());
+        written.push_back(p);
+      }
+    }
+    return AMDZK_OK;
+  }
+  // (d_dst[i] = (d_src[i] - low_i) / (X - root_i)) for cnt polynomials, in runs the grid takes
+  int divide(size_t dst_at, bool with_src, size_t src_at, size_t root_at, size_t low_at, uint32_t low_stride, size_t cnt) {
+    for (size_t first = 0; first < cnt; first += MO_MAX_GRID_Y) {
+      const size_t run = std::min(MO_MAX_GRID_Y, cnt - first);
+      ZK_TRY(zk_kate_div_from(ctx, (Fr* const*)(tab.d_ptrs + dst_at + first), with_src ? (const Fr* const*)(tab.d_ptrs + src_at + first) : nullptr,
+                              tab.d_frs + root_at + first, tab.d_frs + low_at + first * low_stride, low_stride, run, (uint32_t)n));
+    }
+    return AMDZK_OK;
+  }
+
+  // the evaluations of every (polynomial, point) pair: zk_poly_eval, or the caller's (the pair's first query; GWC: every
+  // query its own)
+  int evaluations(const amdzk_open_query* queries, size_t n_queries, const uint64_t* evals) {
+    const size_t E = s.pairs.size();
+    pair_eval.resize(E);
+    if (evals) {
+      for (size_t e = 0; e < E; e++) memcpy(pair_eval[e].l, evals + 4 * (size_t)s.pair_query[e], 32);
+    } else {
+      const size_t p_at = tab.ptrs.size();
+      for (size_t e = 0; e < E; e++) tab.put(d_polys[s.pairs[e].first]);
+      const size_t z_at = tab.frs.size();
+      for (size_t e = 0; e < E; e++) tab.put(point(s.pairs[e].second));
+      const size_t o_at = tab.skip_frs(E);
+      ZK_TRY(tab.upload(ctx));
+      ZK_TRY(zk_poly_eval(ctx, (const Fr* const*)(tab.d_ptrs + p_at), tab.d_frs + z_at, tab.d_frs + o_at, E, (uint32_t)n));
+      ZK_HIP(ctx, hipMemcpyAsync(pair_eval.data(), tab.d_frs + o_at, E * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+      ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
+    }
+    if (s.gwc) {
+      query_eval.resize(n_queries);
+      for (size_t i = 0; i < n_queries; i++) {
+        if (evals) memcpy(query_eval[i].l, evals + 4 * i, 32);
+        else query_eval[i] = pair_eval[s.q_pair[i]];
+      }
+    }
+    return AMDZK_OK;
+  }
+
+  // multiopen/gwc/prover.rs [UP]: per point z, W_z = (sum_j v^j p_j - sum_j v^j p_j(z)) / (X - z). One linear combination
+  // per point; the subtraction of the constant rides in on the division's loads, and all divisions are one launch.
+  int gwc(const amdzk_open_query* queries) {
+    Fr v;
+    ZK_TRY(challenge(&v));
+    const size_t Z = s.gw.size();
+    std::vector<size_t> p_at(Z), c_at(Z);
+    for (size_t z = 0; z < Z; z++) {
+      p_at[z] = tab.ptrs.size();
+      for (uint32_t q : s.gw[z]) tab.put(d_polys[queries[q].poly]);
+    }
+    std::vector<Fr> eb(Z, Fr::zero());
+    for (size_t z = 0; z < Z; z++) {
+      c_at[z] = tab.frs.size();
+      Fr cur = Fr::one();
+      for (uint32_t q : s.gw[z]) {
+        tab.put(cur);
+        eb[z] = add(eb[z], mul(cur, query_eval[q]));
+        cur = mul(cur, v);
+      }
+    }
+    const size_t w_at = tab.ptrs.size();
+    for (size_t z = 0; z < Z; z++) tab.put(d_poly + z * n);
+    const size_t eb_at = tab.frs.size();
+    for (size_t z = 0; z < Z; z++) tab.put(eb[z]);
+    const size_t root_at = tab.frs.size();
+    for (size_t z = 0; z < Z; z++) tab.put(point((uint32_t)z));
+    ZK_TRY(tab.upload(ctx));
+    for (size_t z = 0; z < Z; z++)
+      ZK_TRY(zk_lincomb(ctx, (const Fr* const*)(tab.d_ptrs + p_at[z]), tab.d_frs + c_at[z], (uint32_t)s.gw[z].size(), d_poly + z * n, n, false));
+    ZK_TRY(divide(w_at, false, 0, root_at, eb_at, 1, Z));
+    return commit_write(d_poly, Z, "gwc_w");
+  }
+
+  // multiopen/shplonk/prover.rs [UP] in the proof path's formulation (prover.hip Prover::shplonk): L_i = sum_j y^j P_ij,
+  // R_i = the interpolation of E_i[t] = sum_j y^j P_ij(p_t) (interpolation is linear), and with c_it = 1 / prod_{s != t}
+  // (p_t - p_s): (L_i - R_i) / prod_t (X - p_t) = sum_t c_it (L_i - R_i) / (X - p_t) — the points of a set are distinct
+  // and L_i - R_i vanishes at each. All (set, point) quotients are one division; h(X) = sum_it v^i c_it Q_it.
+  int shplonk() {
+    Fr y, v;
+    ZK_TRY(challenge(&y));
+    ZK_TRY(challenge(&v));
+    const size_t S = s.sets.size(), P = s.set_points, maxm = s.maxm;
+    Fr* const d_L = d_poly;
+    Fr* const d_Q = d_poly + S * n;
+    Fr* const d_hx = d_poly + (S + P) * n;
+    std::vector<std::vector<Fr>> pts(S), cinv(S), low(S);
+    std::vector<Fr> dens;
+    for (size_t i = 0; i < S; i++) {
+      for (uint32_t r : s.sets[i].ranks) pts[i].push_back(point(s.rank_dp[r]));
+      const size_t m = pts[i].size();
+      for (size_t t = 0; t < m; t++) {
+        Fr den = Fr::one();
+        for (size_t t2 = 0; t2 < m; t2++)
+          if (t2 != t) den = mul(den, sub(pts[i][t], pts[i][t2]));
+        dens.push_back(den);  // non-zero: the points of a set are distinct values
+      }
+    }
+    {  // one inversion for all c_it (Montgomery's trick)
+      std::vector<Fr> pre(dens.size() + 1, Fr::one());
+      for (size_t j = 0; j < dens.size(); j++) pre[j + 1] = mul(pre[j], dens[j]);
+      Fr acc = inv(pre[dens.size()]);
+      size_t at = dens.size();
+      for (size_t i = S; i-- > 0;) {
+        cinv[i].resize(pts[i].size());
+        for (size_t t = pts[i].size(); t-- > 0;) {
+          at--;
+          cinv[i][t] = mul(acc, pre[at]);
+          acc = mul(acc, dens[at]);
+        }
+      }
+    }
+    for (size_t i = 0; i < S; i++) {
+      const size_t m = pts[i].size();
+      std::vector<Fr> E(m, Fr::zero());
+      Fr yp = Fr::one();
+      for (uint32_t c : s.sets[i].coms) {
+        for (size_t t = 0; t < m; t++) E[t] = add(E[t], mul(yp, pair_eval[s.com_pts[c][t].second]));
+        yp = mul(yp, y);
+      }
+      low[i].assign(m, Fr::zero());
+      for (size_t t = 0; t < m; t++) {
+        std::vector<Fr> num(1, Fr::one());  // prod_{s != t} (X - p_s), ascending coefficients
+        for (size_t t2 = 0; t2 < m; t2++) {
+          if (t2 == t) continue;
+          num.push_back(Fr::zero());
+          for (size_t d = num.size() - 1; d > 0; d--) num[d] = sub(num[d - 1], mul(pts[i][t2], num[d]));
+          num[0] = neg(mul(pts[i][t2], num[0]));
+        }
+        const Fr w = mul(E[t], cinv[i][t]);
+        for (size_t d = 0; d < m; d++) low[i][d] = add(low[i][d], mul(w, num[d]));
+      }
+    }
+    // tables of the first half
+    std::vector<size_t> p_at(S), c_at(S);
+    for (size_t i = 0; i < S; i++) {
+      p_at[i] = tab.ptrs.size();
+      for (uint32_t c : s.sets[i].coms) tab.put(d_polys[s.com_poly[c]]);
+    }
+    for (size_t i = 0; i < S; i++) {
+      c_at[i] = tab.frs.size();
+      Fr cur = Fr::one();
+      for (size_t j = 0; j < s.sets[i].coms.size(); j++) tab.put(cur), cur = mul(cur, y);
+    }
+    const size_t dst_at = tab.ptrs.size();
+    for (size_t q = 0; q < P; q++) tab.put(d_Q + q * n);
+    const size_t src_at = tab.ptrs.size();
+    for (size_t i = 0; i < S; i++)
+      for (size_t t = 0; t < pts[i].size(); t++) tab.put(d_L + i * n);
+    const size_t root_at = tab.frs.size();
+    for (size_t i = 0; i < S; i++)
+      for (const Fr& p : pts[i]) tab.put(p);
+    const size_t low_at = tab.frs.size();
+    for (size_t i = 0; i < S; i++)
+      for (size_t t = 0; t < pts[i].size(); t++)
+        for (size_t d = 0; d < maxm; d++) tab.put(d < low[i].size() ? low[i][d] : Fr::zero());
+    const size_t coef_at = tab.frs.size();
+    {
+      Fr vpow = Fr::one();
+      for (size_t i = 0; i < S; i++) {
+        for (size_t t = 0; t < pts[i].size(); t++) tab.put(mul(vpow, cinv[i][t]));
+        vpow = mul(vpow, v);
+      }
+    }
+    ZK_TRY(tab.upload(ctx));
+    for (size_t i = 0; i < S; i++)
+      ZK_TRY(zk_lincomb(ctx, (const Fr* const*)(tab.d_ptrs + p_at[i]), tab.d_frs + c_at[i], (uint32_t)s.sets[i].coms.size(), d_L + i * n, n, false));
+    ZK_TRY(divide(dst_at, true, src_at, root_at, low_at, (uint32_t)maxm, P));
+    ZK_TRY(zk_lincomb(ctx, (const Fr* const*)(tab.d_ptrs + dst_at), tab.d_frs + coef_at, (uint32_t)P, d_hx, n, false));
+    ZK_TRY(commit_write(d_hx, 1, "shplonk_h1"));
+
+    // second half: l(X) = sum_i v^i z_i(u) (L_i - R_i(u)) - Z_T(u) h(X), then / (X - u), with 1 / z_0(u) folded into
+    // the coefficients
+    Fr u;
+    ZK_TRY(challenge(&u));
+    const size_t ndp = s.rank_dp.size();
+    std::vector<Fr> diff(ndp);  // u - p by rank
+    Fr zt = Fr::one();
+    for (size_t r = 0; r < ndp; r++) diff[r] = sub(u, point(s.rank_dp[r])), zt = mul(zt, diff[r]);
+    std::vector<Fr> cf(S + 1);
+    Fr cur = Fr::one(), z0 = Fr::one(), cterm = Fr::zero();
+    for (size_t i = 0; i < S; i++) {
+      Fr zi = Fr::one();
+      size_t at = 0;  // ranks are ascending: walk them beside r
+      for (size_t r = 0; r < ndp; r++) {
+        if (at < s.sets[i].ranks.size() && s.sets[i].ranks[at] == r) at++;
+        else zi = mul(zi, diff[r]);
+      }
+      if (i == 0) z0 = zi;
+      const Fr w = mul(cur, zi);
+      cf[i] = w;
+      cterm = add(cterm, mul(w, eval_small(low[i], u)));
+      cur = mul(cur, v);
+    }
+    cf[S] = neg(zt);
+    if (z0.is_zero()) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "multiopen: the challenge u is one of the opening points (probability 2^-254)");
+    const Fr z0inv = inv(z0);
+    for (auto& c : cf) c = mul(c, z0inv);
+    cterm = mul(cterm, z0inv);
+    Fr* const d_lx = d_Q;  // the quotients are folded into h(X): their first buffer is free
+    const size_t fp_at = tab.ptrs.size();
+    for (size_t i = 0; i < S; i++) tab.put(d_L + i * n);
+    tab.put(d_hx);
+    const size_t lx_at = tab.put(d_lx);
+    const size_t fc_at = tab.frs.size();
+    for (auto& c : cf) tab.put(c);
+    const size_t ct_at = tab.put(cterm);
+    const size_t u_at = tab.put(u);
+    ZK_TRY(tab.upload(ctx));
+    ZK_TRY(zk_lincomb(ctx, (const Fr* const*)(tab.d_ptrs + fp_at), tab.d_frs + fc_at, (uint32_t)(S + 1), d_lx, n, false));
+    ZK_TRY(divide(lx_at, false, 0, u_at, ct_at, 1, 1));
+    return commit_write(d_lx, 1, "shplonk_h2");
+  }
+};
+
+int multiopen_body(amdzk_ctx* ctx, const amdzk_srs* srs, const void* const* d_polys, size_t n_polys, const uint64_t* points, size_t n_points,
+                   const amdzk_open_query* queries, size_t n_queries, const amdzk_multiopen_opts* opts, uint64_t* out_points, size_t out_cap,
+                   size_t* n_out, MoSets& s, std::unique_ptr<Call>& call) {
+  if (n_out) *n_out = 0;
+  if (!srs || !d_polys || !points || !queries || !opts) ZK_FAIL(ctx, AMDZK_E_INVALID, "multiopen: null argument");
+  if (opts->size < sizeof(amdzk_multiopen_opts))
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "multiopen: amdzk_multiopen_opts.size %zu < %zu", opts->size, sizeof(amdzk_multiopen_opts));
+  const amdzk_transcript* t = opts->transcript;
+  if (!t) ZK_FAIL(ctx, AMDZK_E_INVALID, "multiopen: a transcript is required");
+  if (!t->common_point || !t->common_scalar || !t->write_point || !t->write_scalar || !t->squeeze_challenge)
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "multiopen: amdzk_transcript has a null member");
+  char why[200];
+  const int pr = mo_build(points, n_points, queries, n_queries, n_polys, zk_srs_k(srs), opts->scheme, s, nullptr, why);
+  if (pr != AMDZK_OK) ZK_FAIL(ctx, pr, "multiopen: %s", why);
+  for (size_t i = 0; i < n_queries; i++)
+    if (!d_polys[queries[i].poly]) ZK_FAIL(ctx, AMDZK_E_INVALID, "multiopen: polynomial %u (query %zu) is a null pointer", queries[i].poly, i);
+  if (out_points && out_cap < s.n_out) ZK_FAIL(ctx, AMDZK_E_INVALID, "multiopen: room for %zu points, %u will be written", out_cap, s.n_out);
+  if (!zk_srs_has_basis(srs, AMDZK_BASIS_G)) ZK_FAIL(ctx, AMDZK_E_INVALID, "multiopen: the parameters have no basis g (AMDZK_BASIS_G)");
+  char* ws = nullptr;
+  {
+    const int r = zk_ws_reserve(ctx, MO_WS_SLOT, s.scratch_bytes, (void**)&ws);
+    if (r == AMDZK_E_NOMEM) {
+      (void)hipGetLastError();  // the failed allocation's sticky status
+      ZK_FAIL(ctx, AMDZK_E_NOMEM, "multiopen: %zu bytes of scratch cannot be allocated", s.scratch_bytes);
+    }
+    ZK_TRY(r);
+  }
+  call.reset(new Call(ctx, srs, d_polys, points, s, *t));
+  Call& c = *call;
+  c.d_poly = (Fr*)ws;
+  c.tab.d_ptrs = (void**)(ws + s.poly_count * s.n * 32);
+  c.tab.d_frs = (Fr*)(ws + s.poly_count * s.n * 32 + s.ptr_bytes);
+  ZK_TRY(c.evaluations(queries, n_queries, opts->evals));
+  if (s.gwc) ZK_TRY(c.gwc(queries));
+  else ZK_TRY(c.shplonk());
+  if (n_out) *n_out = c.written.size();
+  if (out_points) memcpy(out_points, c.written.data(), c.written.size() * sizeof(G1Affine));
+  return AMDZK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int amdzk_multiopen_plan(const uint64_t* points, size_t n_points, const amdzk_open_query* queries, size_t n_queries, size_t n_polys, uint32_t k,
+                         int scheme, uint32_t* n_sets, uint32_t* n_out, size_t* scratch_bytes, uint32_t* set_of_poly) {
+  MoSets s;
+  char why[200];
+  const int r = mo_build(points, n_points, queries, n_queries, n_polys, k, scheme, s, set_of_poly, why);
+  if (r != AMDZK_OK) return r;
+  if (n_sets) *n_sets = s.n_sets;
+  if (n_out) *n_out = s.n_out;
+  if (scratch_bytes) *scratch_bytes = s.scratch_bytes;
+  return AMDZK_OK;
+}
+
+int amdzk_multiopen_dev(amdzk_ctx* ctx, const amdzk_srs* srs, const void* const* d_polys, size_t n_polys, const uint64_t* points, size_t n_points,
+                        const amdzk_open_query* queries, size_t n_queries, const amdzk_multiopen_opts* opts, uint64_t* out_points, size_t out_cap,
+                        size_t* n_out) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  MoSets s;
+  std::unique_ptr<Call> call;  // owns the host images of the tables: it outlives every copy enqueued from them
+  const int r = multiopen_body(ctx, srs, d_polys, n_polys, points, n_points, queries, n_queries, opts, out_points, out_cap, n_out, s, call);
+  if (r != AMDZK_OK) {  // whatever the call enqueued has run before the caller sees the refusal
+    const std::string keep = ctx->err;
+    (void)zk_host_wait(ctx, ctx->stream);
+    ctx->err = keep;
+  }
+  return r;
+}
+
+}  // extern "C"

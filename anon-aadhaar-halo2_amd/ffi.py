@@ -113,6 +113,8 @@ def lib():
         "amdzk_eval_poly_dev": (i32, [vp, C.POINTER(vp), vp, sz, u32, vp]),
         "amdzk_poly_axpy_dev": (i32, [vp, C.POINTER(vp), vp, sz, vp, sz, i32]),
         "amdzk_kate_div_dev": (i32, [vp, C.POINTER(vp), vp, sz, u32]),
+        "amdzk_multiopen_dev": (i32, [vp, vp, C.POINTER(vp), sz, vp, sz, vp, sz, vp, vp, sz, C.POINTER(sz)]),
+        "amdzk_multiopen_plan": (i32, [vp, sz, vp, sz, sz, u32, i32, C.POINTER(u32), C.POINTER(u32), C.POINTER(sz), vp]),
         "amdzk_permute_expression_pair_dev": (i32, [vp, vp, vp, vp, sz, u32, u32]),
         "amdzk_quotient_eval_dev": (i32, [vp, vp, vp, sz, vp, vp, vp, vp, vp]),
         "amdzk_pk_inspect": (i32, [vp, vp, i32, vp, sz, C.POINTER(sz)]),
@@ -156,6 +158,13 @@ class ProofOpts(C.Structure):
 class BatchOpts(C.Structure):
     _fields_ = [("size", C.c_size_t), ("transcript_kind", C.c_int), ("rng_seeds", C.c_void_p), ("scalars", C.POINTER(C.c_void_p)),
                 ("scalar_count", C.c_size_t)]
+
+
+class MultiopenOpts(C.Structure):
+    _fields_ = [("size", C.c_size_t), ("scheme", C.c_int), ("transcript", C.POINTER(Transcript)), ("evals", C.c_void_p)]
+
+
+OPEN_QUERY = np.dtype([("poly", np.uint32), ("point", np.uint32)])  # amdzk_open_query
 
 
 def build_info():

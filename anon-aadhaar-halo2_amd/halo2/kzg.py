@@ -3,6 +3,7 @@ import ctypes as C
 
 import numpy as np
 
+from .. import ffi as _ffi
 from ..ffi import _ptr
 from . import arithmetic
 
@@ -97,3 +98,105 @@ class ParamsKZG:
         if self.h:
             self.ctx.L.amdzk_srs_free(self.ctx.h, self.h)
             self.h = None
+
+
+# ---- poly::kzg::multiopen: the opening arguments over the caller's polynomials (amdzk_multiopen_dev)
+MULTIOPEN_SHPLONK = 0
+MULTIOPEN_GWC = 0x100
+
+
+def index_queries(queries):
+    """[(polynomial, point)] -> (polynomials, points (P, 4) uint64, amdzk_open_query array). A polynomial is a device buffer
+    (anything with .ptr, or an address); its identity is its address, as upstream's PolynomialPointer compares. A point is
+    (4,) uint64 Montgomery; equal words share an index."""
+    polys, poly_of, points, point_of = [], {}, [], {}
+    q = np.zeros(len(queries), dtype=_ffi.OPEN_QUERY)
+    for i, (poly, point) in enumerate(queries):
+        addr = getattr(poly, "ptr", poly)
+        addr = int(getattr(addr, "value", addr) or 0)
+        if addr not in poly_of:
+            poly_of[addr] = len(polys)
+            polys.append(addr)
+        pt = np.ascontiguousarray(point, dtype=np.uint64).reshape(4)
+        key = pt.tobytes()
+        if key not in point_of:
+            point_of[key] = len(points)
+            points.append(pt)
+        q[i] = (poly_of[addr], point_of[key])
+    return polys, np.array(points, dtype=np.uint64).reshape(-1, 4), q
+
+
+def multiopen_plan(points, queries, n_polys, k, scheme=MULTIOPEN_SHPLONK):
+    """amdzk_multiopen_plan (host only, no device): points (P, 4) uint64 Montgomery, queries [(polynomial index, point
+    index)] or an amdzk_open_query array. Returns {"n_sets", "n_out", "scratch_bytes", "set_of_poly"}; raises AmdzkError
+    with the call's status for a shape amdzk_multiopen_dev refuses."""
+    L = _ffi.lib()
+    pts = None if points is None else np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 4)
+    if queries is not None and not (isinstance(queries, np.ndarray) and queries.dtype == _ffi.OPEN_QUERY):
+        queries = np.array([tuple(int(v) for v in qq) for qq in queries], dtype=_ffi.OPEN_QUERY).reshape(-1)
+    n_sets, n_out, scratch = C.c_uint32(0), C.c_uint32(0), C.c_size_t(0)
+    sop = np.zeros(max(1, n_polys), np.uint32)
+    rc = L.amdzk_multiopen_plan(None if pts is None else _ptr(pts), 0 if pts is None else pts.shape[0],
+                                None if queries is None else _ptr(queries), 0 if queries is None else queries.shape[0], n_polys, k, scheme,
+                                C.byref(n_sets), C.byref(n_out), C.byref(scratch), _ptr(sop))
+    if rc != 0:
+        raise _ffi.AmdzkError(rc, "multiopen: the plan refuses this shape")
+    return {"n_sets": n_sets.value, "n_out": n_out.value, "scratch_bytes": scratch.value, "set_of_poly": sop[:n_polys].copy()}
+
+
+class _ProverMultiopen:
+    """poly::commitment::Prover for KZG: create_proof(transcript, queries) writes the opening proof to the caller's
+    transcript object (write_point takes (8,) uint64 affine Montgomery words, squeeze_challenge returns (4,)) and returns
+    the written points, (n_out, 8) uint64."""
+    scheme = MULTIOPEN_SHPLONK
+
+    def __init__(self, params):
+        self.params = params
+
+    def create_proof(self, transcript, queries, evals=None, **kw):
+        """queries: [(device buffer of 2^k coefficients, point (4,) uint64)] in upstream's order. evals: None (computed
+        on the device) or (len(queries), 4) uint64, the evaluation each query claims — trusted, not checked."""
+        polys, points, q = index_queries(queries)
+        return multiopen(self.params, polys, points, q, transcript, self.scheme, evals=evals, **kw)
+
+
+def multiopen(params, polys, points, queries, transcript, scheme=MULTIOPEN_SHPLONK, evals=None, want_points=True, out_cap=None, opts_size=None):
+    """amdzk_multiopen_dev over indexed queries: polys = device addresses (or buffers with .ptr), points (P, 4) uint64,
+    queries = amdzk_open_query array or [(polynomial index, point index)]. Returns the written points (n_out, 8), or
+    their number with want_points=False. out_cap / opts_size: what to report to the library (tests)."""
+    from . import plonk  # the transcript trampolines (late: plonk imports this module)
+    ctx = params.ctx
+    addrs = []
+    for p in polys:
+        p = getattr(p, "ptr", p)
+        addrs.append(int(getattr(p, "value", p) or 0) or None)
+    d_polys = (C.c_void_p * max(1, len(addrs)))(*addrs)
+    points = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 4)
+    if not (isinstance(queries, np.ndarray) and queries.dtype == _ffi.OPEN_QUERY):
+        queries = np.array([tuple(int(v) for v in qq) for qq in queries], dtype=_ffi.OPEN_QUERY).reshape(-1)
+    errors = []
+    _phase, tr, keep = plonk._trampolines(None, transcript, errors)
+    ev = None if evals is None else np.ascontiguousarray(evals, dtype=np.uint64).reshape(len(queries), 4)
+    opts = _ffi.MultiopenOpts(C.sizeof(_ffi.MultiopenOpts) if opts_size is None else opts_size, scheme,
+                              C.pointer(tr) if tr is not None else None, None if ev is None else ev.ctypes.data)
+    cap = (2 if scheme == MULTIOPEN_SHPLONK else max(1, len(points))) if out_cap is None else out_cap
+    out = np.zeros((max(1, cap), 8), np.uint64)
+    n_out = C.c_size_t(0)
+    rc = ctx.L.amdzk_multiopen_dev(ctx.h, params.h, d_polys, len(addrs), _ptr(points) if len(points) else None, len(points),
+                                   _ptr(queries) if len(queries) else None, len(queries), C.byref(opts), _ptr(out) if want_points else None, cap,
+                                   C.byref(n_out))
+    del keep
+    if errors and rc != 0:
+        raise errors[0]
+    ctx._chk(rc)
+    return out[: n_out.value].copy() if want_points else n_out.value
+
+
+class ProverSHPLONK(_ProverMultiopen):
+    """poly::kzg::multiopen::ProverSHPLONK."""
+    scheme = MULTIOPEN_SHPLONK
+
+
+class ProverGWC(_ProverMultiopen):
+    """poly::kzg::multiopen::ProverGWC."""
+    scheme = MULTIOPEN_GWC

@@ -539,6 +539,64 @@ int amdzk_poly_axpy_dev(amdzk_ctx* ctx, const void* const* d_polys, const uint64
                         void* d_out, size_t n, int accumulate);
 /* arithmetic::kate_division [UP] in place: a(X) -> (a(X) - a(root)) / (X - root); n coefficients, the top one 0. */
 int amdzk_kate_div_dev(amdzk_ctx* ctx, void* const* d_polys, const uint64_t* roots, size_t npolys, uint32_t n);
+/* poly::kzg::multiopen::{ProverSHPLONK, ProverGWC}::create_proof(params, rng, transcript, queries) [UP] (row a12) over the
+ * CALLER's polynomials and points: the opening argument on its own, for a fork that keeps upstream's create_proof and swaps
+ * only this, and for any use of the resident SRS as a KZG commitment scheme (commit, then open).
+ * d_polys: host array of n_polys device pointers, 2^k coefficients each (k the SRS's), Montgomery; read only, may alias. A
+ * polynomial's identity is its INDEX (upstream's PolynomialPointer compares addresses: map addresses to indices). points:
+ * n_points x 4 words, Montgomery Fr, any values; two indices with equal values are one point. queries: (polynomial index,
+ * point index) pairs in upstream's query order; duplicates are allowed. Entries of d_polys no query names are not read.
+ * SHPLONK (scheme 0): queries are grouped commitment -> point set (first seen first), point set -> commitments (sets
+ * compared as sorted values, first seen first), the super point set in ascending canonical order; squeeze y, squeeze v,
+ * write [h(X)] with h = sum_i v^i (sum_j y^j (P_ij - R_ij)) / Z_{S_i}; squeeze u; write
+ * [(sum_i v^i z_i(u) (L_i - R_i(u)) - Z_T(u) h) / (X - u) / z_0(u)]. Two points.
+ * GWC (scheme AMDZK_MULTIOPEN_GWC): squeeze v; queries grouped by point value, points first seen first, a point's queries
+ * in their order, duplicates kept; per point z write [(sum_j v^j p_j - sum_j v^j p_j(z)) / (X - z)]. One point per
+ * distinct point value.
+ * transcript: required; only squeeze_challenge and write_point are called, in the order above. evals: NULL, and the
+ * evaluations p(z) are computed on the device; or n_queries x 4 words, evals[i] = the evaluation query i claims. Supplied
+ * evaluations are TRUSTED, NOT CHECKED — as upstream trusts ProverQuery::eval: a wrong value gives no error here (and, since
+ * every division drops its remainder as upstream's kate_division does, not even other points: what the verifier checks the
+ * points against is the evaluation the CALLER wrote to the transcript, which this call never sees). SHPLONK reads the first
+ * query of every (polynomial, point value) pair, GWC every query's own.
+ * out_points (may be NULL): the written points, G1Affine, in write order, out_cap of them at most; *n_out (may be NULL)
+ * their number. Scratch is the ctx's: one reservation of amdzk_multiopen_plan's scratch_bytes, grown on demand and kept
+ * (shared with the other calls of this section); the call runs on the ctx's stream only and returns with it idle. No cap
+ * on sets, points or queries but memory.
+ * Refused with a message that starts "multiopen:", the ctx stays usable and the stream is idle: AMDZK_E_INVALID for null
+ * arguments, a missing transcript or transcript member, a too-small opts->size, n_queries = 0, an index out of range, a
+ * queried null polynomial, out_cap < n_out with out_points set, an SRS without AMDZK_BASIS_G, a non-zero return of a
+ * transcript member, and a commitment that is the identity (e.g. every queried polynomial zero: the library refuses to
+ * write the identity, as upstream's transcripts do); AMDZK_E_NOMEM when the scratch cannot be allocated. A refusal after
+ * the first squeeze leaves the caller's transcript advanced by what was called. */
+typedef struct amdzk_open_query {
+  uint32_t poly;  /* index into d_polys */
+  uint32_t point; /* index into points */
+} amdzk_open_query;
+typedef struct amdzk_multiopen_opts {
+  size_t size;                        /* sizeof(amdzk_multiopen_opts) as the caller compiled it; too small is refused */
+  int scheme;                         /* 0 SHPLONK, AMDZK_MULTIOPEN_GWC for GWC */
+  const amdzk_transcript* transcript; /* required */
+  const uint64_t* evals;              /* optional, n_queries x 4 Montgomery: trusted, not checked; NULL = computed */
+} amdzk_multiopen_opts;
+int amdzk_multiopen_dev(amdzk_ctx* ctx, const amdzk_srs* srs, const void* const* d_polys, size_t n_polys,
+                        const uint64_t* points, size_t n_points, const amdzk_open_query* queries,
+                        size_t n_queries, const amdzk_multiopen_opts* opts,
+                        uint64_t* out_points /* may be NULL; n_out x 8 */, size_t out_cap, size_t* n_out);
+/* What amdzk_multiopen_dev will do for these queries over polynomials of 2^k coefficients; pure host code, callable without
+ * a device (like amdzk_msm_g1_bases_plan), the sets built exactly as the call builds them, and the call's status for a
+ * shape it refuses. n_sets: SHPLONK's point sets, or GWC's distinct points. n_out: points written (2, or n_sets).
+ * set_of_poly (may be NULL, n_polys entries): SHPLONK, the set polynomial i falls in; GWC, the first point (in write
+ * order) polynomial i is opened at; UINT32_MAX for a polynomial no query names. Any output pointer may be NULL.
+ * scratch_bytes = polys * 2^k * 32 + round_up(ptrs * 8, 256) + frs * 32, where with Q queries, E distinct (polynomial,
+ * point value) pairs, C distinct queried polynomials, S = n_sets, P = sum_i |S_i| and M = max_i |S_i|:
+ *   SHPLONK: polys = S + P + 1 (the L_i, the (set, point) quotients, h), ptrs = E + C + 2 P + S + 2,
+ *            frs = 2 E + C + 2 P + P M + S + 3;
+ *   GWC:     polys = S (the W_z), ptrs = E + Q + S, frs = 2 E + Q + 2 S.
+ * (The MSM's and the kernels' own temporaries are the ctx's usual workspaces and are not in this figure.) */
+int amdzk_multiopen_plan(const uint64_t* points, size_t n_points, const amdzk_open_query* queries,
+                         size_t n_queries, size_t n_polys, uint32_t k, int scheme, uint32_t* n_sets,
+                         uint32_t* n_out, size_t* scratch_bytes, uint32_t* set_of_poly);
 /* lookup::prover::permute_expression_pair [UP] for nlookups pairs of n rows (column l at + l*n, Montgomery form):
  * d_inputs is sorted in place into A', d_permuted_tables_out receives S' (first occurrences aligned, leftovers in
  * ascending order assigned from the last repeated row backwards); rows >= usable come back zero for the caller to

@@ -21,6 +21,7 @@
 #ifndef AMDZK_HALO2_HPP
 #define AMDZK_HALO2_HPP
 
+#include <array>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -984,6 +985,98 @@ inline std::vector<uint8_t> create_proof(const Context& ctx, const ProvingKey& p
   amdzk_dev_free(ctx.get(), d);
   return proof;
 }
+
+// ------------------------------------------------------------------------------------------ multiopen on its own
+// poly::kzg::multiopen::{ProverSHPLONK, ProverGWC} over the caller's polynomials (amdzk_multiopen_dev): for a fork that
+// keeps upstream's create_proof and swaps the opening argument, and for KZG outside PLONK (commit, then open).
+// poly::query::ProverQuery: `poly` = 2^k coefficients on the device (Montgomery); its identity is its address, as
+// upstream's PolynomialPointer compares. `point` is any field element; equal values are one point. `eval` is only read
+// by create_proof(.., use_evals = true) and is then TRUSTED, NOT CHECKED, as upstream trusts it.
+struct ProverQuery {
+  const void* poly;
+  Fr point;
+  Fr eval;
+};
+
+namespace detail {
+inline amdzk_transcript c_transcript(Trampoline* tr) {
+  amdzk_transcript ct;
+  ct.user = tr;
+  ct.common_point = [](void* u, const uint64_t* xy) { auto* t = (Trampoline*)u; return t->guard([&] { G1Affine p; std::memcpy(&p, xy, 64); t->t->common_point(p); }); };
+  ct.common_scalar = [](void* u, const uint64_t* s) { auto* t = (Trampoline*)u; return t->guard([&] { Fr v; std::memcpy(v.l, s, 32); t->t->common_scalar(v); }); };
+  ct.write_point = [](void* u, const uint64_t* xy) { auto* t = (Trampoline*)u; return t->guard([&] { G1Affine p; std::memcpy(&p, xy, 64); t->t->write_point(p); }); };
+  ct.write_scalar = [](void* u, const uint64_t* s) { auto* t = (Trampoline*)u; return t->guard([&] { Fr v; std::memcpy(v.l, s, 32); t->t->write_scalar(v); }); };
+  ct.squeeze_challenge = [](void* u, uint64_t* out) { auto* t = (Trampoline*)u; return t->guard([&] { Fr v = t->t->squeeze_challenge(); std::memcpy(out, v.l, 32); }); };
+  return ct;
+}
+
+// Prover::create_proof(params, rng, transcript, queries) of poly::commitment; returns the points it wrote
+inline std::vector<G1Affine> multiopen(const Context& ctx, const ParamsKZG& params, Multiopen scheme, TranscriptWrite& transcript,
+                                       const std::vector<ProverQuery>& queries, bool use_evals) {
+  std::vector<const void*> polys;
+  std::vector<Fr> points;
+  std::map<const void*, uint32_t> poly_of;
+  std::map<std::array<uint64_t, 4>, uint32_t> point_of;
+  std::vector<amdzk_open_query> q(queries.size());
+  std::vector<Fr> evals(queries.size());
+  for (size_t i = 0; i < queries.size(); i++) {
+    auto pi = poly_of.find(queries[i].poly);
+    if (pi == poly_of.end()) {
+      pi = poly_of.emplace(queries[i].poly, (uint32_t)polys.size()).first;
+      polys.push_back(queries[i].poly);
+    }
+    const std::array<uint64_t, 4> key{{queries[i].point.l[0], queries[i].point.l[1], queries[i].point.l[2], queries[i].point.l[3]}};
+    auto zi = point_of.find(key);
+    if (zi == point_of.end()) {
+      zi = point_of.emplace(key, (uint32_t)points.size()).first;
+      points.push_back(queries[i].point);
+    }
+    q[i].poly = pi->second;
+    q[i].point = zi->second;
+    evals[i] = queries[i].eval;
+  }
+  Trampoline tr{nullptr, &transcript, nullptr};
+  const amdzk_transcript ct = c_transcript(&tr);
+  amdzk_multiopen_opts opts;
+  std::memset(&opts, 0, sizeof(opts));
+  opts.size = sizeof(opts);
+  opts.scheme = (int)scheme;
+  opts.transcript = &ct;
+  opts.evals = use_evals ? (const uint64_t*)evals.data() : nullptr;
+  std::vector<G1Affine> out(scheme == Multiopen::Shplonk ? 2 : std::max<size_t>(1, points.size()));
+  size_t n_out = 0;
+  const int rc = amdzk_multiopen_dev(ctx.get(), params.handle(), polys.data(), polys.size(), (const uint64_t*)points.data(), points.size(), q.data(),
+                                     q.size(), &opts, (uint64_t*)out.data(), out.size(), &n_out);
+  if (rc != AMDZK_OK && tr.err) std::rethrow_exception(tr.err);
+  ctx.check(rc);
+  out.resize(n_out);
+  return out;
+}
+}  // namespace detail
+
+class ProverSHPLONK {
+ public:
+  ProverSHPLONK(const Context& ctx, const ParamsKZG& params) : ctx_(ctx), params_(params) {}
+  std::vector<G1Affine> create_proof(TranscriptWrite& transcript, const std::vector<ProverQuery>& queries, bool use_evals = false) const {
+    return detail::multiopen(ctx_, params_, Multiopen::Shplonk, transcript, queries, use_evals);
+  }
+
+ private:
+  const Context& ctx_;
+  const ParamsKZG& params_;
+};
+
+class ProverGWC {
+ public:
+  ProverGWC(const Context& ctx, const ParamsKZG& params) : ctx_(ctx), params_(params) {}
+  std::vector<G1Affine> create_proof(TranscriptWrite& transcript, const std::vector<ProverQuery>& queries, bool use_evals = false) const {
+    return detail::multiopen(ctx_, params_, Multiopen::Gwc, transcript, queries, use_evals);
+  }
+
+ private:
+  const Context& ctx_;
+  const ParamsKZG& params_;
+};
 
 // One witness per proof from the host (what a caller does after Circuit::synthesize, /root/reference/src/lib.rs:328-397):
 // the advice columns are synthesized into pinned memory, and the upload of proof i+1's witness runs on the ctx's copy
