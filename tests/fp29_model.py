@@ -467,6 +467,56 @@ def x29_add(a, b):
     return (ox, oy, f29_mul(F, f29_mul(F, a[2], b[2]), pp), f29_mul(F, f29_mul(F, a[3], b[3]), ppp))
 
 
+# ---- the same formulas spread over the four lanes of a quad (csrc/fp29_quad.cuh). Lane `role` multiplies the role-th pair of
+# every round (quad_sel) and a broadcast (quad_bcast<J>) is lane J's product, so reference B evaluates all four products of
+# a round — the duplicates that fill idle lanes too: every f29_mul precondition of every lane is enforced — and the four
+# lanes end with the same point.
+def _quad_round(F, a4, b4):
+    return [f29_mul(F, a, b) for a, b in zip(a4, b4)]
+
+
+def x29_dbl_quad(pt):
+    F = FQ
+    if not any(pt[2]):
+        return pt
+    px, py, pzz, pzzz = pt
+    u = f29_add(py, py)
+    res = _quad_round(F, (u, px, u, px), (u, px, u, px))
+    v, xx = res[0], res[1]
+    m = f29_add(f29_add_lazy(xx, xx), xx)
+    res = _quad_round(F, (u, px, m, m), (v, v, m, m))
+    w, sv, mm = res[0], res[1], res[2]
+    rx = f29_sub(F, 5, mm, f29_add(sv, sv))
+    d = f29_sub(F, 8, sv, rx)
+    res = _quad_round(F, (m, f29_neg(F, 3, w), v, w), (d, py, pzz, pzzz))
+    return (rx, f29_add(res[0], res[1]), res[2], res[3])
+
+
+def x29_add_quad(a, b):
+    F = FQ
+    if not any(b[2]):
+        return a
+    if not any(a[2]):
+        return b
+    res = _quad_round(F, (a[0], b[0], a[1], b[1]), (b[2], a[2], b[3], a[3]))
+    u1, s1 = res[0], res[2]
+    p = f29_sub(F, 3, res[1], u1)
+    r = f29_sub(F, 3, res[3], s1)
+    res = _quad_round(F, (p, r, a[2], a[3]), (p, r, b[2], b[3]))
+    pp, rr, zz12, zzz12 = res
+    if f29_is_zero_mod_p(F, pp):
+        if f29_is_zero_mod_p(F, rr):
+            return x29_dbl_quad(a)
+        return x29_inf()
+    res = _quad_round(F, (p, u1, zz12, zz12), (pp, pp, pp, pp))
+    ppp, q, ozz = res[0], res[1], res[2]
+    sq = f29_add(ppp, f29_add_lazy(q, q))
+    ox = f29_sub(F, 7, rr, sq)
+    t = f29_sub(F, 10, q, ox)
+    res = _quad_round(F, (r, f29_neg(F, 3, s1), zzz12, zzz12), (t, ppp, ppp, ppp))
+    return (ox, f29_add(res[0], res[1]), ozz, res[2])
+
+
 def x29_to_r256(a):
     if not any(a[2]):
         return [0] * 32
@@ -710,9 +760,12 @@ def class_points(seed=43, n=6):
 IN_WORDS, OUT_WORDS = 112, 320  # data words of one record (the largest: six operand pairs in; eight XYZZ points out)
 (F_MUL, F_SQR, F_MUL2, F_MUL_CHAIN, F_SQR_CHAIN, F_MUL2_CHAIN, F_WIDE, F_REDUCE_WEAK, F_SUB_MUL, F_NEG_MUL2, F_LAZY_MUL,
  F_LAZY2_MUL, F_LAZY_MUL2, F_UNPACK_PACK, F_FROM_TO_R256, F_TO_R256, F_MUL_CONST, F_MUL_RR, F_MUL_STD, F_FROM_MONT, F_INV29,
- F_BN_MUL, F_BN_INV, F_DBL_AFFINE, F_ADD_AFFINE, F_DBL, F_ADD, F_ADD_CHAIN) = range(1, 29)
+ F_BN_MUL, F_BN_INV, F_DBL_AFFINE, F_ADD_AFFINE, F_DBL, F_ADD, F_ADD_CHAIN, F_DBL_QUAD, F_ADD_QUAD, F_QUAD_CHAIN) = range(1, 32)
 FUNC_NAMES = {v: k[2:].lower() for k, v in list(globals().items()) if k.startswith("F_") and isinstance(v, int)}
 CHAIN_STEPS, CHAIN_EVERY = 64, 8
+QUAD_FUNCS = (F_DBL_QUAD, F_ADD_QUAD, F_QUAD_CHAIN)  # one record per QUAD of lanes (the others: one record per lane)
+AUX_SIT_OUT = 1  # quad functions: this record's quad does not call the formula and writes nothing
+QUAD_CHAIN_STEPS, QUAD_CHAIN_EVERY = 16, 4
 
 
 class Case:
@@ -898,13 +951,15 @@ def _pt_words(pt):
     return pt[0] + pt[1] + pt[2] + pt[3]
 
 
-def _pt_check(want):
+def _pt_check(want, y_bound=2):
+    """y_bound: 2 where y leaves a formula as one reduced product, 4 for the quad formulas (the sum of two), 5 where the
+    formula hands a (lifted) operand back unchanged: the documented bound of an accumulator that comes IN."""
     def check(o):
         pt = tuple(_vecs(o[:36]))
         assert x29_affine(pt) == want, "raw XYZZ: wrong point"
         if want is not None:
             assert all(x < 1 << 29 for c in pt for x in c[:8])
-            assert val(pt[0]) < 9 * Q and max(val(pt[1]), val(pt[2]), val(pt[3])) < 2 * Q, "outside the accumulator bounds"
+            assert val(pt[0]) < 9 * Q and val(pt[1]) < y_bound * Q and max(val(pt[2]), val(pt[3])) < 2 * Q, "outside the accumulator bounds"
         assert xyzz_words_affine(o[36:68]) == want, "packed XYZZ: wrong point"
         assert all(from_words(o[36 + 8 * i:44 + 8 * i]) < Q for i in range(4))
     return check
@@ -917,6 +972,24 @@ def x29_from_affine(P1):
     return (x, y, list(FQ.one), list(FQ.one))
 
 
+ACC_BOUNDS = (9, 5, 2, 2)  # fp29.cuh "XYZZ on Fq29": what the formulas accept of an accumulator, in units of p
+
+
+def x29_lift(pt):
+    """The same point with every coordinate at the top of the documented accumulator bounds: the largest v + k p below
+    9p / 5p / 2p / 2p, limbs 0..7 normalised. The identity (zz all zero) has one representation and stays."""
+    if not any(pt[2]):
+        return pt
+    out = tuple(digits(val(c) % Q + (b * Q - 1 - val(c) % Q) // Q * Q) for c, b in zip(pt, ACC_BOUNDS))
+    assert all((b - 1) * Q <= val(c) < b * Q and max(c[:8]) <= MASK for c, b in zip(out, ACC_BOUNDS))
+    return out
+
+
+def _passes_through(r, operands):
+    """The formula returned one of its operands as it came (identity on the other side): the bounds of what came in hold."""
+    return any(r == o for o in operands)
+
+
 def case_dbl_affine(what, P1):
     qx, qy = affine_to_r261(P1)
     r = x29_dbl_affine(qx, qy)
@@ -926,7 +999,8 @@ def case_dbl_affine(what, P1):
 def case_add_affine(what, acc, acc_affine, P2):
     qx, qy = affine_to_r261(P2) if P2 is not None else ([0] * 9, [0] * 9)
     r = x29_add_affine(acc, qx, qy, P2 is None)
-    return Case(F_ADD_AFFINE, FQ, what, _pt_words(acc) + qx + qy, _pt_words(r) + x29_to_r256(r), _pt_check(affine_add(acc_affine, P2)), aux=int(P2 is None))
+    return Case(F_ADD_AFFINE, FQ, what, _pt_words(acc) + qx + qy, _pt_words(r) + x29_to_r256(r),
+                _pt_check(affine_add(acc_affine, P2), 5 if _passes_through(r, [acc]) else 2), aux=int(P2 is None))
 
 
 def case_dbl(what, pt, pt_affine):
@@ -936,7 +1010,91 @@ def case_dbl(what, pt, pt_affine):
 
 def case_add(what, a, a_affine, b, b_affine):
     r = x29_add(a, b)
-    return Case(F_ADD, FQ, what, _pt_words(a) + _pt_words(b), _pt_words(r) + x29_to_r256(r), _pt_check(affine_add(a_affine, b_affine)))
+    return Case(F_ADD, FQ, what, _pt_words(a) + _pt_words(b), _pt_words(r) + x29_to_r256(r),
+                _pt_check(affine_add(a_affine, b_affine), 5 if _passes_through(r, [a, b]) else 2))
+
+
+# ---- the quad formulas: one record per quad; every lane returns its 36 words, lane 0 the packed form as well
+def _quad_check(want, y_bound):
+    one = _pt_check(want, y_bound)
+
+    def check(o):
+        copies = _vecs(o[:144], 36)
+        assert all(c == copies[0] for c in copies[1:]), "the four lanes of the quad hold different points"
+        one(copies[0] + o[144:176])
+    return check
+
+
+def _quad_expect(r):
+    return _pt_words(r) * 4 + x29_to_r256(r)
+
+
+def case_dbl_quad(what, pt, pt_affine, kind):
+    r = x29_dbl_quad(pt)
+    c = Case(F_DBL_QUAD, FQ, what, _pt_words(pt), _quad_expect(r), _quad_check(affine_add(pt_affine, pt_affine), 4))
+    c.kind = kind
+    return c
+
+
+def case_add_quad(what, a, a_affine, b, b_affine, kind):
+    r = x29_add_quad(a, b)
+    c = Case(F_ADD_QUAD, FQ, what, _pt_words(a) + _pt_words(b), _quad_expect(r),
+             _quad_check(affine_add(a_affine, b_affine), 5 if _passes_through(r, [a, b]) else 4))
+    c.kind = kind
+    return c
+
+
+def case_quad_sits_out(func, data):
+    """A quad that does not call the formula (the quads at and above `s` in a round of msm_rowcol_quad_kernel) beside quads
+    that do: nothing may come back from it, and its neighbours' DPP moves must not notice."""
+    c = Case(func, FQ, "sits out", data, [], lambda o: None, aux=AUX_SIT_OUT)
+    c.kind = "sits out"
+    return c
+
+
+def case_quad_chain(what, pts):
+    """msm_window_combine_kernel's shape: 16 steps of three doublings and one addition of pts[j % 4] (affine, zz = zzz = 1),
+    from the identity, outputs (y below 4p) fed back in. The running point after steps 4, 8 and 12 from lane 0, after step 16
+    from all four lanes, then its packed form."""
+    assert len(pts) == 4
+    acc, acc_a, cps, wants, kinds = x29_inf(), None, [], [], set()
+    for j in range(QUAD_CHAIN_STEPS):
+        for _ in range(3):
+            acc, acc_a = x29_dbl_quad(acc), affine_add(acc_a, acc_a)
+        P2 = pts[j % 4]
+        kinds.add("restart" if acc_a is None else "doubling" if acc_a == P2 else "cancellation" if acc_a == affine_neg(P2) else "generic")
+        acc, acc_a = x29_add_quad(acc, x29_from_affine(P2)), affine_add(acc_a, P2)
+        if j % QUAD_CHAIN_EVERY == QUAD_CHAIN_EVERY - 1:
+            cps.append(acc)
+            wants.append(acc_a)
+    last = _quad_check(wants[3], 4)
+
+    def check(o):
+        for i in range(3):
+            pt = tuple(_vecs(o[36 * i:36 * i + 36]))
+            assert x29_affine(pt) == wants[i], "checkpoint %d: wrong point" % i
+            assert wants[i] is None or (val(pt[0]) < 9 * Q and val(pt[1]) < 4 * Q and max(val(pt[2]), val(pt[3])) < 2 * Q
+                                        and all(x < 1 << 29 for c in pt for x in c[:8])), "checkpoint %d: outside the bounds" % i
+        last(o[108:])
+    c = Case(F_QUAD_CHAIN, FQ, what, sum((sum(affine_to_r261(P2), []) for P2 in pts), []),
+             sum((_pt_words(cp) for cp in cps[:3]), []) + _quad_expect(cps[3]), check)
+    c.kind, c.kinds = "chain", kinds
+    return c
+
+
+def quad_order(by_kind, filler, every=5):
+    """Round-robin over the kinds, so that neighbouring quads of a wavefront take different branches; every `every`-th
+    record gets a quad that sits out on both sides."""
+    lists = [list(v) for v in by_kind.values()]
+    out = []
+    while any(lists):
+        for l in lists:
+            if l:
+                out.append(l.pop(0))
+    fenced = []
+    for i, c in enumerate(out):
+        fenced += [filler, c, filler] if i % every == every - 1 else [c]
+    return fenced
 
 
 def case_add_chain(what, pts):
@@ -1084,6 +1242,56 @@ def build_cases(n_random=64):
         cs.append(case_add("P + (-P)", T, Ta, x29_from_affine(affine_neg(Ta)), affine_neg(Ta)))
         cs.append(case_add("identity + P", x29_inf(), None, S, Sa))
         cs.append(case_add("P + identity", S, Sa, x29_inf(), None))
+    # the same formulas with the accumulator at the top of its documented bounds (x29_lift), and the quad formulas on all of it
+    dq = {"generic": [], "identity": []}
+    aq = {}  # round-robin lists (the two doublings apart, so that every list is equally long) -> cases
+    for i, P1 in enumerate(pts):
+        P2, P3, P4 = pts[(i + 1) % len(pts)], pts[(i + 2) % len(pts)], pts[(i + 3) % len(pts)]
+        S = x29_add_affine(x29_from_affine(P1), *affine_to_r261(P2), False)
+        Sa = affine_add(P1, P2)
+        T, Ta = x29_dbl(S), affine_add(Sa, Sa)
+        U, Ua = x29_add_affine(x29_from_affine(P2), *affine_to_r261(P4), False), affine_add(P2, P4)
+        SS = x29_add(S, S)  # 2 (P1 + P2) again, another representation than T
+        negT = x29_from_affine(affine_neg(Ta))
+        LS, LT, LU, LSS, LnegT = (x29_lift(X) for X in (S, T, U, SS, negT))
+        top = "operands at the top of 9p / 5p / 2p / 2p: "
+        cs.append(case_add_affine(top + "random", LS, Sa, P3))
+        cs.append(case_add_affine(top + "P + P", LS, Sa, Sa))
+        cs.append(case_add_affine(top + "P + (-P)", LS, Sa, affine_neg(Sa)))
+        cs.append(case_add_affine(top + "P + identity", LS, Sa, None))
+        cs.append(case_dbl(top + "random", LS, Sa))
+        pairs = [("generic", "random", S, Sa, U, Ua, LS, LU),
+                 ("doubling", "P + P, two representations", T, Ta, SS, Ta, LT, LSS),
+                 ("doubling", "P + P, same representation", S, Sa, S, Sa, LS, LS),
+                 ("cancellation", "P + (-P)", T, Ta, negT, affine_neg(Ta), LT, LnegT),
+                 ("identity", "identity + P", x29_inf(), None, S, Sa, x29_inf(), LS),
+                 ("identity", "P + identity", S, Sa, x29_inf(), None, LS, x29_inf())]
+        for kind, what, a, aa, b, ba, la, lb in pairs:
+            cs.append(case_add(top + what, la, aa, lb, ba))
+            mine = aq.setdefault(kind + what[:12], [])
+            mine.append(case_add_quad(what, a, aa, b, ba, kind))
+            mine.append(case_add_quad(top + what, la, aa, lb, ba, kind))
+            if kind != "identity":
+                cs.append(case_add("top of the bounds + canonical: " + what, la, aa, b, ba))
+                mine.append(case_add_quad("top of the bounds + canonical: " + what, la, aa, b, ba, kind))
+                mine.append(case_add_quad("canonical + top of the bounds: " + what, a, aa, lb, ba, kind))
+        dq["generic"] += [case_dbl_quad("random", S, Sa, "generic"), case_dbl_quad(top + "random", LS, Sa, "generic"),
+                          case_dbl_quad("random, zz = 1", x29_from_affine(P1), P1, "generic")]
+        dq["identity"].append(case_dbl_quad("identity", x29_inf(), None, "identity"))
+    S0 = x29_add_affine(x29_from_affine(A), *affine_to_r261(B_), False)
+    dbl_q = quad_order(dq, case_quad_sits_out(F_DBL_QUAD, _pt_words(S0)), every=3)
+    add_q = quad_order(aq, case_quad_sits_out(F_ADD_QUAD, _pt_words(S0) + _pt_words(x29_dbl(S0))))
+    for w in range(0, len(add_q), 16):  # sixteen quads are one wavefront
+        assert len({c.kind for c in add_q[w:w + 16]} - {"sits out"}) >= 3, "a wavefront of add_quad cases with fewer than three branch kinds"
+    assert all(any(c.kind == "sits out" for c in q[w:w + 16]) for q in (dbl_q, add_q) for w in range(0, len(q) - 15, 16))
+    cs += dbl_q + add_q
+    # A, -8A, D, 8D: A; 8A - 8A = identity (cancellation); 8 * identity + D (restart); 8D + 8D (the addition doubles); generic after
+    qchain = case_quad_chain("A, -8A, D, 8D repeated: cancellation, identity, restart and doubling", [A, affine_neg(affine_mul(8, A)), D, affine_mul(8, D)])
+    assert qchain.kinds == {"restart", "cancellation", "doubling", "generic"}
+    cs += [qchain, case_quad_sits_out(F_QUAD_CHAIN, qchain.data), case_quad_chain("four random points", [A, B_, C, D]),
+           case_quad_chain("three random points and one of them again", [B_, C, D, C]),
+           # the point set of the lane-serial chain below; with three doublings a step it meets no special case here
+           case_quad_chain("A, B, -(A+B), D repeated", [A, B_, affine_neg(affine_add(A, B_)), D])]
     chain = case_add_chain("A, B, -(A+B), D repeated: identity, restart and doubling", [A, B_, affine_neg(affine_add(A, B_)), D])
     assert chain.seen_inf
     cs.append(chain)

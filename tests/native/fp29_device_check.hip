@@ -10,7 +10,13 @@
 //
 // Three compile contexts surround the asm block: (i) one product per thread, operands straight from memory (OpMul, OpSqr);
 // (ii) dependent chains, eight blocks back to back between two stores (OpMulChain, OpSqrChain, OpMul2Chain); (iii) the
-// point formulas (OpDblAffine ... OpAddChain), four live 9-limb values around every block.
+// point formulas (OpDblAffine ... OpAddChain), four live 9-limb values around every block; (iv) the quad formulas, selects and
+// DPP moves around every block.
+//
+// The quad formulas of csrc/fp29_quad.cuh (OpDblQuad, OpAddQuad, OpQuadChain) take one QUAD of lanes per record: lane
+// `role` = t & 3 calls the formula with its role, every lane writes the point it ends with, neighbouring quads of a wavefront
+// hold different records (different branches), and a record whose aux has bit 0 set sits out: its quad returns before the
+// call, so that the DPP moves of the quads beside it run with idle neighbours, as in the rounds of msm_rowcol_quad_kernel.
 //
 // Exit status: 0 results written; 2 HIP error; 3 not a gfx950 device; 4 malformed case file.
 #include <hip/hip_runtime.h>
@@ -23,11 +29,14 @@
 #include <vector>
 
 #include "../../anon-aadhaar-halo2_amd/csrc/fp29.cuh"
+#include "../../anon-aadhaar-halo2_amd/csrc/fp29_quad.cuh"
 using namespace bn254;
 
 constexpr uint32_t MAGIC = 0x43393246u;  // "F29C"
 constexpr uint32_t IN_WORDS = 112, OUT_WORDS = 320, REC_WORDS = 4 + IN_WORDS, REPLICAS = 2, WAVE = 64;
 constexpr int CHAIN_STEPS = 64, CHAIN_EVERY = 8;
+constexpr uint32_t FIRST_QUAD_FUNC = 29, AUX_SIT_OUT = 1;  // F_DBL_QUAD ... of tests/fp29_model.py: one record per quad
+constexpr int QUAD_CHAIN_STEPS = 16, QUAD_CHAIN_EVERY = 4;
 
 #define HIP_OK(call)                                                                         \
   do {                                                                                       \
@@ -268,6 +277,46 @@ template <class P, class B> struct OpAddChain {
   }
 };
 
+// ---- the quad formulas: o + 36 * role receives this lane's copy of the result, o + 144 lane 0's packed form
+__device__ __forceinline__ void st_quad(uint32_t* o, const G1X29& r, uint32_t role) {
+  stpt(o + 36 * role, r, false);
+  if (role == 0) {
+    const G1X g = x29_to_r256(r);
+    st8(o + 144, g.x);
+    st8(o + 152, g.y);
+    st8(o + 160, g.zz);
+    st8(o + 168, g.zzz);
+  }
+}
+template <class P, class B> struct OpDblQuad {
+  static __device__ void run(const uint32_t* d, uint32_t, uint32_t* o, uint32_t role) { st_quad(o, x29_dbl_quad(ldpt(d), role), role); }
+};
+template <class P, class B> struct OpAddQuad {
+  static __device__ void run(const uint32_t* d, uint32_t, uint32_t* o, uint32_t role) { st_quad(o, x29_add_quad(ldpt(d), ldpt(d + 36), role), role); }
+};
+// msm_window_combine_kernel's loop: 16 steps of three doublings and one addition of the affine point j % 4 (zz = zzz = 1), from
+// the identity. Lane 0 stores the running point after steps 4, 8 and 12, all four lanes after step 16.
+template <class P, class B> struct OpQuadChain {
+  static __device__ void run(const uint32_t* d, uint32_t, uint32_t* o, uint32_t role) {
+    G1X29 acc = G1X29::inf();
+#pragma unroll 1
+    for (int j = 0; j < QUAD_CHAIN_STEPS; j++) {
+#pragma unroll 1
+      for (int i = 0; i < 3; i++) acc = x29_dbl_quad(acc, role);
+      const uint32_t* q = d + 18 * (j % 4);
+      G1X29 v;
+      v.x = ld9<Fq29P>(q);
+      v.y = ld9<Fq29P>(q + 9);
+      v.zz = v.zzz = f29_one<Fq29P>();
+      acc = x29_add_quad(acc, v, role);
+      if (j % QUAD_CHAIN_EVERY == QUAD_CHAIN_EVERY - 1) {
+        if (j == QUAD_CHAIN_STEPS - 1) st_quad(o + 108, acc, role);
+        else if (role == 0) stpt(o + 36 * (j / QUAD_CHAIN_EVERY), acc, false);
+      }
+    }
+  }
+};
+
 // One launch per run of records with the same (function, field). Thread t: replica t / stride, record t % stride; stride is
 // the record count rounded up to whole wavefronts, so the replicas of a record sit in different wavefronts.
 template <class Op> __global__ void __launch_bounds__(WAVE) run_kernel(const uint32_t* in, uint32_t* out, uint32_t count, uint32_t stride, uint32_t total) {
@@ -278,17 +327,31 @@ template <class Op> __global__ void __launch_bounds__(WAVE) run_kernel(const uin
   Op::run(rec + 4, rec[2], out + ((size_t)rep * total + idx) * OUT_WORDS);
 }
 
+// The same for the quad functions: quad t / 4 is the record, lane t & 3 its role; stride counts quads and is a whole number of
+// wavefronts (16 quads each). A record that sits out leaves here, before the call: whole quads leave together.
+template <class Op> __global__ void __launch_bounds__(WAVE) run_kernel_quad(const uint32_t* in, uint32_t* out, uint32_t count, uint32_t stride, uint32_t total) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, quad = t >> 2, role = t & 3u;
+  const uint32_t rep = quad / stride, idx = quad % stride;
+  if (rep >= REPLICAS || idx >= count) return;
+  const uint32_t* rec = in + (size_t)idx * REC_WORDS;
+  if (rec[2] & AUX_SIT_OUT) return;
+  Op::run(rec + 4, rec[2], out + ((size_t)rep * total + idx) * OUT_WORDS, role);
+}
+
 typedef void (*kernel_t)(const uint32_t*, uint32_t*, uint32_t, uint32_t, uint32_t);
 #define BOTH(Op) {run_kernel<Op<Fq29P, FqP>>, run_kernel<Op<Fr29P, FrP>>}
 #define FQ_ONLY(Op) {run_kernel<Op<Fq29P, FqP>>, nullptr}
 #define FR_ONLY(Op) {nullptr, run_kernel<Op<Fr29P, FrP>>}
+#define FQ_QUAD(Op) {run_kernel_quad<Op<Fq29P, FqP>>, nullptr}
 // index = function id of tests/fp29_model.py (F_MUL = 1 ...)
 static const kernel_t KERNELS[][2] = {
     {nullptr, nullptr},    BOTH(OpMul),          BOTH(OpSqr),         BOTH(OpMul2),       BOTH(OpMulChain),     BOTH(OpSqrChain),
     BOTH(OpMul2Chain),     BOTH(OpWide),         BOTH(OpReduceWeak),  BOTH(OpSubMul),     BOTH(OpNegMul2),      BOTH(OpLazyMul),
     BOTH(OpLazy2Mul),      BOTH(OpLazyMul2),     BOTH(OpUnpackPack),  FQ_ONLY(OpFromToR256), FQ_ONLY(OpToR256), FR_ONLY(OpMulConst),
     FR_ONLY(OpMulRR),      FR_ONLY(OpMulStd),    FR_ONLY(OpFromMont), FR_ONLY(OpInv29),   BOTH(OpBnMul),        BOTH(OpBnInv),
-    FQ_ONLY(OpDblAffine),  FQ_ONLY(OpAddAffine), FQ_ONLY(OpDbl),      FQ_ONLY(OpAdd),     FQ_ONLY(OpAddChain)};
+    FQ_ONLY(OpDblAffine),  FQ_ONLY(OpAddAffine), FQ_ONLY(OpDbl),      FQ_ONLY(OpAdd),     FQ_ONLY(OpAddChain),
+    FQ_QUAD(OpDblQuad),    FQ_QUAD(OpAddQuad),   FQ_QUAD(OpQuadChain)};
+static_assert(sizeof(KERNELS) / sizeof(KERNELS[0]) == FIRST_QUAD_FUNC + 3, "the quad functions are the last three of the table");
 constexpr uint32_t N_FUNCS = sizeof(KERNELS) / sizeof(KERNELS[0]);
 
 static int bad_file(const char* what) {
@@ -338,8 +401,9 @@ int main(int argc, char** argv) {
     const uint32_t func = in[(size_t)first * REC_WORDS], field = in[(size_t)first * REC_WORDS + 1];
     uint32_t count = 1;
     while (first + count < n && in[(size_t)(first + count) * REC_WORDS] == func && in[(size_t)(first + count) * REC_WORDS + 1] == field) count++;
-    const uint32_t stride = (count + WAVE - 1) / WAVE * WAVE;
-    KERNELS[func][field]<<<dim3(REPLICAS * stride / WAVE), dim3(WAVE)>>>(d_in + (size_t)first * REC_WORDS, d_out + (size_t)first * OUT_WORDS, count, stride, n);
+    const uint32_t per_wave = func >= FIRST_QUAD_FUNC ? WAVE / 4 : WAVE;  // records of one wavefront
+    const uint32_t stride = (count + per_wave - 1) / per_wave * per_wave;
+    KERNELS[func][field]<<<dim3(REPLICAS * stride / per_wave), dim3(WAVE)>>>(d_in + (size_t)first * REC_WORDS, d_out + (size_t)first * OUT_WORDS, count, stride, n);
     HIP_OK(hipGetLastError());
     HIP_OK(hipDeviceSynchronize());  // a fault is reported at the launch that caused it
     first += count;

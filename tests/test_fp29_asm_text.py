@@ -224,6 +224,33 @@ def test_reference_b_agrees_with_reference_a_on_every_case():
     assert funcs == set(M.FUNC_NAMES), "a harness function without cases: %s" % (set(M.FUNC_NAMES) - funcs)
 
 
+def test_point_formula_cases_reach_the_top_of_the_accumulator_bounds_and_every_quad_branch():
+    """What the case list promises about the point formulas, counted: every formula that takes an accumulator sees one with
+    x, y, zz, zzz in the last p below 9p, 5p, 2p, 2p; x29_add_quad sees each branch with canonical, lifted and mixed
+    operands; the quad chain feeds its own outputs (y not canonical: the unreduced sum of two products) back in. (That B stays inside its own preconditions on all of them is what
+    building the list asserts; that A accepts B's output is the test above.)"""
+    def top(words):
+        c = [M.val(words[9 * i:9 * i + 9]) for i in range(4)]
+        return all((b - 1) * M.Q <= v < b * M.Q for v, b in zip(c, M.ACC_BOUNDS))
+    for func in (M.F_ADD_AFFINE, M.F_DBL, M.F_ADD, M.F_DBL_QUAD, M.F_ADD_QUAD):
+        assert sum(top(c.data[:36]) for c in CASES if c.func == func) >= 6, M.FUNC_NAMES[func]
+    for func in (M.F_ADD, M.F_ADD_QUAD):
+        mine = [c for c in CASES if c.func == func and c.aux == 0]
+        both = [c for c in mine if top(c.data[:36]) and top(c.data[36:72])]
+        mixed = [c for c in mine if top(c.data[:36]) != top(c.data[36:72]) and any(c.data[18:27]) and any(c.data[54:63])]
+        for group in (both, mixed):
+            results = {"identity" if not any(c.expect[18:27]) else "point" for c in group}
+            assert results == {"identity", "point"} and len(group) >= 18, M.FUNC_NAMES[func]
+    quads = [c for c in CASES if c.func == M.F_ADD_QUAD]
+    assert {c.kind for c in quads} == {"generic", "doubling", "cancellation", "identity", "sits out"}
+    fed_back = [c for c in CASES if c.func == M.F_QUAD_CHAIN and c.expect]
+    assert len(fed_back) == 4 and any(M.val(c.expect[36 * i + 9:36 * i + 18]) >= M.Q for c in fed_back for i in range(3))
+    with pytest.raises(M.ContractError):  # one p more in x is outside x29_add_quad's contract, and B says so: 10p * 2p... s2 - s1
+        S = M.x29_lift(M.x29_add_affine(M.x29_from_affine(M.G1), *M.affine_to_r261(M.affine_mul(5, M.G1)), False))
+        far = (M.digits(M.val(S[0]) + 160 * M.Q),) + S[1:]
+        M.x29_add_quad(far, M.x29_lift(M.x29_dbl(S)))
+
+
 @pytest.mark.parametrize("F", [M.FQ, M.FR], ids=repr)
 def test_reference_b_refuses_operands_one_step_outside_the_contract(F):
     """Classes 3-5 once more with the top limb one higher: a*b (a*b + c*d) reaches 169 p^2 and B's own precondition says so."""

@@ -4,7 +4,7 @@ The asm products (fp29_asm.inc), the 8 x 32-bit CIOS `mul` and the Fermat `inv` 
 rest of the suite reaches them only through whole MSMs, NTTs and proofs on random or witness-like data. Here
 tests/native/fp29_device_check.hip — the two headers, the library's compile flags, nothing else — runs every case of
 tests/fp29_model.py (operands at the documented bounds, one hot limb, chosen Montgomery factors, lazy limbs, chains, the
-point formulas with all their branches) in two lanes of different wavefronts, and the words that come back must equal the
+point formulas with all their branches) in two lanes (quads) of different wavefronts, and the words that come back must equal the
 model's limb-exact restatement of the C code (reference B); then integer arithmetic (reference A) judges them as residues
 with the documented bound. Bit-exact, no tolerance. One child process for the whole file; if it fails, times out or is not
 on a gfx950 device, every test here fails and nothing is started again.
@@ -13,7 +13,12 @@ Also here, without a GPU: the disassembly of the harness shows that its one-prod
 multiply-adds of one asm block between the inline-asm markers (the harness tests the asm path, not the C fallback) and
 that no harness kernel uses scratch memory.
 
-3295 cases x 2 replicas in 44 launches; the whole file takes under 2 s on an MI355X, most of it the child process' start-up."""
+The quad-lane formulas of csrc/fp29_quad.cuh (x29_dbl_quad, x29_add_quad, and the two chained as msm_window_combine_kernel
+chains them) take one quad of lanes per case: the four lanes' results must be word-equal and equal to reference B, with quads
+of other branches, and quads that sit out, beside them in the wavefront. Every point formula, lane-serial or quad, also gets
+its operands at the top of the documented accumulator bounds (x below 9p, y below 5p, zz and zzz below 2p).
+
+3598 cases x 2 replicas in 47 launches; the whole file takes under 2 s on an MI355X, most of it the child process' start-up."""
 import os
 import re
 import shutil
@@ -28,14 +33,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "anon-aadhaar-halo2_amd", "csrc")
 NATIVE = os.path.join(ROOT, "tests", "native")
 SRC, EXE = os.path.join(NATIVE, "fp29_device_check.hip"), os.path.join(NATIVE, "fp29_device_check")
-DEPS = [SRC, os.path.join(CSRC, "fp29.cuh"), os.path.join(CSRC, "fp29_asm.inc"), os.path.join(CSRC, "bn254.cuh")]
+DEPS = [SRC, os.path.join(CSRC, "fp29.cuh"), os.path.join(CSRC, "fp29_quad.cuh"), os.path.join(CSRC, "fp29_asm.inc"), os.path.join(CSRC, "bn254.cuh")]
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 MAGIC = 0x43393246
 REPLICAS = 2
 # which compile context of the asm block a function exercises (the module docstring of the harness)
 CONTEXT = {M.F_MUL: "(i) one product per thread", M.F_SQR: "(i) one product per thread", M.F_MUL_CHAIN: "(ii) dependent chain",
            M.F_SQR_CHAIN: "(ii) dependent chain", M.F_MUL2_CHAIN: "(ii) dependent chain", M.F_DBL_AFFINE: "(iii) point formula",
-           M.F_ADD_AFFINE: "(iii) point formula", M.F_DBL: "(iii) point formula", M.F_ADD: "(iii) point formula", M.F_ADD_CHAIN: "(iii) point formula"}
+           M.F_ADD_AFFINE: "(iii) point formula", M.F_DBL: "(iii) point formula", M.F_ADD: "(iii) point formula", M.F_ADD_CHAIN: "(iii) point formula",
+           M.F_DBL_QUAD: "(iv) quad formula", M.F_ADD_QUAD: "(iv) quad formula", M.F_QUAD_CHAIN: "(iv) quad formula"}
 
 
 def library_flags():
@@ -128,7 +134,7 @@ def test_harness_runs_the_asm_blocks_and_uses_no_scratch(tmp_path):
                    stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     asm = open(out).read()
     meta = {k: v for k, v in kernel_meta(asm).items() if "run_kernel" in k}
-    assert len(meta) == 44, "one kernel per (function, field) of the harness table"
+    assert len(meta) == 47, "one kernel per (function, field) of the harness table"
     for name, (priv, spills) in meta.items():
         assert (priv, spills) == (0, 0), "harness kernel %s uses scratch memory (%d bytes, %d spills)" % (name, priv, spills)
     bodies = _kernel_bodies(asm)
