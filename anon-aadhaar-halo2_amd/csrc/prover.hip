@@ -26,6 +26,7 @@
 
 #include "hostcrypto.hpp"
 #include "pkblob.hpp"
+#include "check_kernels.hpp"
 #include "plonk_kernels.hpp"
 
 using namespace bn254;
@@ -252,6 +253,26 @@ struct amdzk_pk {
   Multiopen mo_multi;
   std::vector<const amdzk_pk*> mo_multi_keys;
   std::vector<const Fr*> h_cols_lag, h_cols_ext;  // host copies of the slot tables (program resolution)
+  // amdzk_check_witness, per handle, made by the handle's first check (the instructions carry this workspace's column
+  // addresses): the gate polynomials as one Lagrange-domain program, gate g ending in OP_CHECK g; the base addresses of
+  // the permutation columns; the counters, count[ncon] (u64) followed by first[ncon] (u32), constraints in report order
+  // (gates, lookups, permutation columns).
+  struct Check {
+    bool built = false;
+    Program prog_gates;
+    const Fr** d_perm_cols = nullptr;
+    unsigned long long* d_count = nullptr;
+    uint32_t* d_first = nullptr;
+  } chk;
+  // ... and per ROOT key, shared with its clones: the sigma columns decoded to (column, row), 2 x u32 per cell
+  // ([S][n]), derived by the first check on any handle of the key — under the guard, as zk_srs_ensure_prefix derives its
+  // basis — and freed with the root key. Never in the key file.
+  struct CheckShared {
+    std::mutex guard;
+    bool decoded = false;
+    uint2* d_cells = nullptr;
+  };
+  std::shared_ptr<CheckShared> chk_shared;
   // pinned host staging (bump allocator, reset whenever the stream is known to be idle)
   char* pin = nullptr;
   size_t pin_cap = 0, pin_off = 0;
@@ -823,8 +844,8 @@ int upload_program(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, bool extended) {
   return AMDZK_OK;
 }
 
-int run_program(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, bool extended, Fr* const* d_outs, Fr* h_out, const char* name) {
-  ExprArgs a;
+// the launch arguments of a program of this key: its pieces, its column table, where it stores
+int program_args(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, bool extended, Fr* const* d_outs, Fr* h_out, ExprArgs& a) {
   a.prog = pr.d_instr;
   a.prog_len = (uint32_t)pr.words.size();
   a.cols = extended ? pk->d_cols_ext : pk->d_cols_lag;
@@ -867,6 +888,12 @@ int run_program(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, bool extended, Fr* co
     a.hot[2] = pk->se_lactive();
     a.hot[3] = pk->se_x();
   }
+  return AMDZK_OK;
+}
+
+int run_program(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, bool extended, Fr* const* d_outs, Fr* h_out, const char* name) {
+  ExprArgs a;
+  ZK_TRY(program_args(ctx, pk, pr, extended, d_outs, h_out, a));
   // LDS stack slots: the limb interpreter keeps the top of the stack in registers, so a program whose stack holds at most
   // pr.depth - 1 values (finalize_limb_program) needs pr.depth - 2 slots: pr.depth - 1 leaves one spare
   return extended ? zk_expr_eval_limbs(ctx, a, pr.depth > 1 ? pr.depth - 1 : 1, name) : zk_expr_eval(ctx, a, pr.depth + 1, name);
@@ -1049,6 +1076,7 @@ void amdzk_pk_free(amdzk_ctx* ctx, amdzk_pk* pk) {
   if (!pk) return;
   if (ctx) zk_host_wait(ctx, ctx->stream);
   for (void* p : pk->allocs) hipFree(p);
+  if (!pk->clone_of && pk->chk_shared && pk->chk_shared->d_cells) hipFree(pk->chk_shared->d_cells);
   if (pk->pin) hipHostFree(pk->pin);
   if (pk->dom && !pk->clone_of) amdzk_domain_free(ctx, pk->dom);
   delete pk;
@@ -1141,6 +1169,7 @@ static int keygen_common(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circu
     }                              \
   } while (0)
   pk->srs = srs;
+  pk->chk_shared = std::make_shared<amdzk_pk::CheckShared>();
   pk->k = c->k;
   pk->n = (size_t)1 << c->k;
   pk->bf = c->blinding_factors;
@@ -2912,6 +2941,7 @@ int amdzk_pk_clone_workspace(amdzk_ctx* ctx, const amdzk_pk* src, amdzk_pk** out
   pk->sets_Q = nullptr;
   pk->sets_Q_pairs = 0;
   pk->prog_compress.d_instr = pk->prog_pfrac.d_instr = pk->prog_lfrac.d_instr = pk->prog_h.d_instr = nullptr;
+  pk->chk = amdzk_pk::Check();  // built by the clone's own first check
 #define CL_TRY(x)                \
   do {                           \
     int _r = (x);                \
@@ -3254,6 +3284,195 @@ int amdzk_pk_read(amdzk_ctx* ctx, const amdzk_srs* srs, const uint8_t* data, siz
   }
   *out = pk;
   return AMDZK_OK;
+}
+
+// ---- amdzk_check_witness: MockProver::verify's constraint checks on the device (include/amdzk.h has the semantics).
+// What this handle needs beyond what a proof uses, made by its first check: the gate program, the permutation columns'
+// addresses in this workspace, the counters.
+static int check_build(amdzk_ctx* ctx, amdzk_pk* pk) {
+  amdzk_pk::Check& ck = pk->chk;
+  if (ck.built) return AMDZK_OK;
+  const uint32_t ncon = pk->num_gates + pk->L + pk->S;
+  if (!ck.prog_gates.d_instr) {
+    Program pr;
+    const RotTable rots_before = pk->rots;  // the gates' rotations are all in the table already: the h(X) program queried them
+    for (uint32_t g = 0; g < pk->num_gates; g++) {
+      pr.piece();
+      ZK_TRY(emit_expr(ctx, pk, pr, pk->exprs[g]));
+      pr.op(OP_CHECK, g);
+      pr.pop();
+    }
+    if (pk->rots.rots.size() != rots_before.rots.size()) {  // cannot happen for a key keygen made; the table stays what the uploaded programs index
+      pk->rots = rots_before;
+      ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: a gate polynomial queries a rotation the key's programs do not");
+    }
+    ck.prog_gates = pr;
+    ZK_TRY(upload_program(ctx, pk, ck.prog_gates, false));
+  }
+  if (pk->S && !ck.d_perm_cols) {
+    std::vector<const Fr*> cols(pk->S);
+    for (uint32_t i = 0; i < pk->S; i++) {
+      const std::pair<int, int>& kc = pk->perm_cols[i];
+      cols[i] = pk->h_cols_lag[kc.first == 0 ? pk->sl_adv(kc.second) : kc.first == 1 ? pk->sl_fixed(kc.second) : pk->sl_inst(kc.second)];
+    }
+    ZK_TRY(dalloc(ctx, pk, &ck.d_perm_cols, cols.size()));
+    ZK_TRY(h2d(ctx, ck.d_perm_cols, cols.data(), cols.size() * sizeof(Fr*)));
+    ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));  // `cols` is a host temporary
+  }
+  if (!ck.d_count) {
+    ZK_TRY(dalloc(ctx, pk, &ck.d_count, (size_t)ncon + ((size_t)ncon + 1) / 2 + 1));  // u64 counts, then u32 first rows
+    ck.d_first = reinterpret_cast<uint32_t*>(ck.d_count + ncon);
+  }
+  ck.built = true;
+  return AMDZK_OK;
+}
+
+// The root key's sigma columns back to (column, row), once: S * n * 8 bytes that every handle of the key reads.
+static int check_decode_sigma(amdzk_ctx* ctx, amdzk_pk* pk) {
+  amdzk_pk::CheckShared& sh = *pk->chk_shared;
+  std::lock_guard<std::mutex> lock(sh.guard);
+  if (sh.decoded || !pk->S) return AMDZK_OK;
+  const uint32_t S = pk->S, k = pk->k;
+  const size_t n = pk->n;
+  if (!sh.d_cells) {
+    void* q = nullptr;
+    if (hipMalloc(&q, (size_t)S * n * sizeof(uint2)) != hipSuccess) ZK_FAIL(ctx, AMDZK_E_NOMEM, "check_witness: hipMalloc of the decoded permutation failed");
+    sh.d_cells = (uint2*)q;
+  }
+  // delta^(i 2^k), delta^(-i) for i < S, omega^(-(2^b)) for b < k
+  std::vector<Fr> tab(2 * (size_t)S + k);
+  const Fr delta = fr_delta(), delta_inv = inv(delta);
+  Fr d2k = delta;
+  for (uint32_t i = 0; i < k; i++) d2k = mul(d2k, d2k);
+  Fr a = Fr::one(), b = Fr::one();
+  for (uint32_t i = 0; i < S; i++) {
+    tab[i] = a;
+    tab[S + i] = b;
+    a = mul(a, d2k);
+    b = mul(b, delta_inv);
+  }
+  Fr w = pk->omega_inv;
+  for (uint32_t i = 0; i < k; i++) {
+    tab[2 * (size_t)S + i] = w;
+    w = mul(w, w);
+  }
+  void* d_tab = nullptr;
+  if (hipMalloc(&d_tab, tab.size() * 32 + 8) != hipSuccess) ZK_FAIL(ctx, AMDZK_E_NOMEM, "check_witness: hipMalloc failed");
+  unsigned long long* d_bad = reinterpret_cast<unsigned long long*>((Fr*)d_tab + tab.size());
+  unsigned long long bad = 0;
+  int r = h2d(ctx, d_tab, tab.data(), tab.size() * 32);
+  if (r == AMDZK_OK && hipMemsetAsync(d_bad, 0xFF, 8, ctx->stream) != hipSuccess) r = AMDZK_E_HIP;
+  if (r == AMDZK_OK) r = zk_sigma_decode(ctx, pk->sigma_lag, S, k, (const Fr*)d_tab, sh.d_cells, d_bad);
+  if (r == AMDZK_OK) r = d2h(ctx, &bad, d_bad, 8);
+  else (void)zk_host_wait(ctx, ctx->stream);  // `tab` is a host temporary
+  hipFree(d_tab);
+  ZK_TRY(r);
+  if (bad != ~0ull) {
+    const unsigned long long cell = bad - 1;
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: sigma column %u row %u is not delta^i omega^j for a column i < %u of this circuit",
+            (uint32_t)(cell >> 32), (uint32_t)cell, S);
+  }
+  sh.decoded = true;
+  return AMDZK_OK;
+}
+
+static int check_witness_run(amdzk_ctx* ctx, amdzk_pk* pk, const uint64_t* const* instances, const size_t* instance_lens, const void* d_advice,
+                             size_t advice_stride, const amdzk_check_opts* opts, amdzk_check_failure* out, size_t cap, size_t* n_failures) {
+  if (!pk || !n_failures || (pk->A && !d_advice)) ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: null argument");
+  if (opts && opts->size < sizeof(amdzk_check_opts))
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: amdzk_check_opts.size is %zu, this library needs %zu", opts->size, sizeof(amdzk_check_opts));
+  const size_t n = pk->n, usable = n - (pk->bf + 1);
+  const uint32_t A = pk->A, I = pk->I, L = pk->L, S = pk->S, G = pk->num_gates, ncon = G + L + S;
+  if (pk->A && advice_stride < n) ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: advice stride < n");
+  const uint32_t given = opts && opts->challenges ? opts->num_challenges : 0;
+  if (pk->num_challenges && !given) ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: the key has %u challenges and none were given", pk->num_challenges);
+  if ((opts ? opts->num_challenges : 0) != pk->num_challenges)
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: %u challenges given, the key has %u", opts ? opts->num_challenges : 0, pk->num_challenges);
+  for (uint32_t c = 0; c < I; c++) {
+    const size_t len = instance_lens ? instance_lens[c] : 0;
+    if (len > usable) ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: instance column %u too long (InstanceTooLarge)", c);
+    if (len && (!instances || !instances[c])) ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: null argument (instance column %u)", c);
+  }
+  amdzk_pk* const root = const_cast<amdzk_pk*>(pk->clone_of ? pk->clone_of : pk);
+  ZK_TRY(check_build(ctx, pk));
+  ZK_TRY(check_decode_sigma(ctx, root));
+  const amdzk_pk::Check& ck = pk->chk;
+  const CheckCounters counters = {ck.d_count, ck.d_first};
+  *n_failures = 0;
+  if (!ncon) return AMDZK_OK;
+  ZK_HIP(ctx, hipMemsetAsync(ck.d_count, 0, (size_t)ncon * 8, ctx->stream));
+  ZK_HIP(ctx, hipMemsetAsync(ck.d_first, 0xFF, (size_t)ncon * 4, ctx->stream));
+  // the witness into the workspace as create_proof copies it, unblinded: instance columns zero behind the caller's values
+  if (I) {
+    ZK_HIP(ctx, hipMemsetAsync(pk->inst(), 0, (size_t)I * n * 32, ctx->stream));
+    for (uint32_t c = 0; c < I; c++) {
+      const size_t len = instance_lens ? instance_lens[c] : 0;
+      if (!len) continue;
+      ZK_TRY(h2d_staged(ctx, pk, pk->inst() + (size_t)c * n, instances[c], len * 32));
+    }
+  }
+  if (A) ZK_HIP(ctx, hipMemcpy2DAsync(pk->adv(), n * 32, d_advice, advice_stride * 32, n * 32, A, hipMemcpyDeviceToDevice, ctx->stream));
+  {  // theta and the phase challenges into their slots of the constant table
+    ChaCha20Rng rng(opts ? opts->theta_seed : 0);
+    pk->consts[pk->c_theta] = rng.fr();
+    ZK_TRY(h2d_staged(ctx, pk, pk->d_consts + pk->c_theta, &pk->consts[pk->c_theta], 32));
+    if (pk->num_challenges) {
+      memcpy(pk->consts[pk->c_chal0].l, opts->challenges, (size_t)pk->num_challenges * 32);
+      ZK_TRY(h2d_staged(ctx, pk, pk->d_consts + pk->c_chal0, &pk->consts[pk->c_chal0], (size_t)pk->num_challenges * 32));
+    }
+  }
+  if (G) {
+    ExprArgs a;
+    ZK_TRY(program_args(ctx, pk, pk->chk.prog_gates, false, nullptr, nullptr, a));
+    ZK_TRY(zk_check_expr(ctx, a, ck.prog_gates.depth + 1, (uint32_t)usable, counters, "expr_check_gates"));
+  }
+  if (L) {  // compressed inputs and tables as canonical keys, the tables sorted (constant ones were sorted at keygen)
+    ZK_TRY(run_program(ctx, pk, pk->prog_compress, false, pk->d_outs_compress, nullptr, "expr_lookup_compress"));
+    ZK_TRY(d2d(ctx, pk->la(), pk->ci, (size_t)L * n * 32));
+    ZK_TRY(amdzk_fr_to_repr_dev(ctx, pk->la(), (size_t)L * n));
+    const uint32_t pre = pk->lk_const, rest = L - pre;
+    if (pre) ZK_TRY(d2d(ctx, pk->lk_ts, pk->lk_ts_const, (size_t)pre * n * 32));
+    if (rest) {
+      Fr* Tr = pk->lk_ts + (size_t)pre * n;
+      ZK_TRY(d2d(ctx, Tr, pk->ct + (size_t)pre * n, (size_t)rest * n * 32));
+      ZK_TRY(amdzk_fr_to_repr_dev(ctx, Tr, (size_t)rest * n));
+      ZK_HIP(ctx, hipMemset2DAsync(Tr + usable, n * 32, 0xFF, (n - usable) * 32, rest, ctx->stream));
+      ZK_TRY(zk_sort_keys(ctx, Tr, rest, (uint32_t)n, n));
+    }
+    ZK_TRY(zk_check_lookups(ctx, pk->la(), pk->lk_ts, L, (uint32_t)n, (uint32_t)usable, G, counters));
+  }
+  if (S) ZK_TRY(zk_check_copies(ctx, ck.d_perm_cols, root->chk_shared->d_cells, S, (uint32_t)n, G + L, counters));
+  std::vector<unsigned long long> host((size_t)ncon + ((size_t)ncon + 1) / 2);
+  ZK_TRY(d2h(ctx, host.data(), ck.d_count, (size_t)ncon * 12));
+  const uint32_t* first = reinterpret_cast<const uint32_t*>(host.data() + ncon);
+  size_t nf = 0;
+  for (uint32_t c = 0; c < ncon; c++) {
+    if (!host[c]) continue;
+    if (out && nf < cap) {
+      amdzk_check_failure& f = out[nf];
+      f.kind = c < G ? AMDZK_CHECK_GATE : c < G + L ? AMDZK_CHECK_LOOKUP : AMDZK_CHECK_COPY;
+      f.index = c < G ? c : c < G + L ? c - G : c - G - L;
+      f.first_row = first[c];
+      f.reserved = 0;
+      f.count = host[c];
+    }
+    nf++;
+  }
+  *n_failures = nf;
+  return AMDZK_OK;
+}
+
+int amdzk_check_witness(amdzk_ctx* ctx, amdzk_pk* pk, const uint64_t* const* instances, const size_t* instance_lens, const void* d_advice,
+                        size_t advice_stride, const amdzk_check_opts* opts, amdzk_check_failure* out, size_t cap, size_t* n_failures) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  const int r = check_witness_run(ctx, pk, instances, instance_lens, d_advice, advice_stride, opts, out, cap, n_failures);
+  if (r != AMDZK_OK) {  // whatever was enqueued (copies from the caller's memory among it) is finished before the call returns
+    const std::string keep = ctx->err;
+    (void)zk_host_wait(ctx, ctx->stream);
+    ctx->err = keep;
+  }
+  return r;
 }
 
 // Test hooks for the host pass that prepares quotient-domain programs for the limb-resident interpreter

@@ -118,6 +118,7 @@ def lib():
         "amdzk_permute_expression_pair_dev": (i32, [vp, vp, vp, vp, sz, u32, u32]),
         "amdzk_quotient_eval_dev": (i32, [vp, vp, vp, sz, vp, vp, vp, vp, vp]),
         "amdzk_pk_inspect": (i32, [vp, vp, i32, vp, sz, C.POINTER(sz)]),
+        "amdzk_check_witness": (i32, [vp, vp, C.POINTER(vp), C.POINTER(sz), vp, sz, vp, vp, sz, C.POINTER(sz)]),
         "amdzk_debug_limb_program": (i32, [vp, sz, vp, sz, C.POINTER(sz), C.POINTER(u32)]),
         "amdzk_pk_h_program": (i32, [vp, vp, sz, C.POINTER(sz)]),
         "amdzk_timer_start": (i32, [vp]),
@@ -162,6 +163,14 @@ class BatchOpts(C.Structure):
 
 class MultiopenOpts(C.Structure):
     _fields_ = [("size", C.c_size_t), ("scheme", C.c_int), ("transcript", C.POINTER(Transcript)), ("evals", C.c_void_p)]
+
+
+class CheckFailure(C.Structure):  # amdzk_check_failure
+    _fields_ = [("kind", C.c_uint32), ("index", C.c_uint32), ("first_row", C.c_uint32), ("reserved", C.c_uint32), ("count", C.c_uint64)]
+
+
+class CheckOpts(C.Structure):  # amdzk_check_opts
+    _fields_ = [("size", C.c_size_t), ("theta_seed", C.c_uint64), ("challenges", C.c_void_p), ("num_challenges", C.c_uint32)]
 
 
 OPEN_QUERY = np.dtype([("poly", np.uint32), ("point", np.uint32)])  # amdzk_open_query

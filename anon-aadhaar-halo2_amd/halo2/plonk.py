@@ -11,6 +11,7 @@ permutation exactly the way upstream's ConstraintSystem does (query indices in f
 Selectors are modelled after upstream's selector compression has run, i.e. as fixed columns.
 Field constants are Python ints (canonical); they are converted to Montgomery limbs at export.
 """
+import collections
 from dataclasses import dataclass, field
 from typing import List, Tuple
 
@@ -754,6 +755,52 @@ def create_proof_batch(ctx, pks, instances_list, d_advice_list, seeds, advice_st
         else:  # the library keeps the first failing proof's message; a later one gets its index and status
             out.append(_ffi.AmdzkError(st[b], msg if msg.startswith("proof %d:" % b) else "proof %d: failed" % b))
     return out
+
+
+CHECK_GATE, CHECK_LOOKUP, CHECK_COPY = 0, 1, 2  # include/amdzk.h AMDZK_CHECK_*
+CheckFailure = collections.namedtuple("CheckFailure", "kind index first_row count")
+
+
+class WitnessReport:
+    """What check_witness found: `failures`, one CheckFailure per failing constraint (kind: CHECK_GATE / CHECK_LOOKUP /
+    CHECK_COPY; index: the gate polynomial, the lookup, the position in the permutation's columns; first_row: the smallest
+    failing row; count: how many rows fail), ordered by kind and index; `ok` iff there is none."""
+
+    def __init__(self, failures):
+        self.failures = list(failures)
+
+    @property
+    def ok(self):
+        return not self.failures
+
+    def __bool__(self):
+        return self.ok
+
+    def __repr__(self):
+        return "WitnessReport(ok)" if self.ok else "WitnessReport(%r)" % (self.failures,)
+
+
+def check_witness(ctx, pk, instances, d_advice, theta_seed=0, challenges=None, advice_stride=None):
+    """amdzk_check_witness: MockProver::verify's constraint checks on the device — every gate polynomial on the usable
+    rows, every lookup input against its table, every copy constraint (include/amdzk.h has the exact semantics).
+    instances / d_advice / advice_stride as for create_proof (the advice is read unblinded); theta_seed seeds the theta
+    that compresses multi-expression lookups; challenges: (num_challenges, 4) uint64 Montgomery for a key with challenge
+    phases. Overwrites the key's per-proof workspace. One call of the library, with room for every constraint of the key
+    (gate polynomials + lookups + permutation columns). Returns a WitnessReport."""
+    n = 1 << pk.desc["k"]
+    cols = [np.ascontiguousarray(c, dtype=np.uint64).reshape(-1, 4) for c in instances]
+    ptrs = (C.c_void_p * max(1, len(cols)))(*[c.ctypes.data if c.size else None for c in cols])
+    lens = (C.c_size_t * max(1, len(cols)))(*[c.shape[0] for c in cols])
+    ch = np.ascontiguousarray(challenges, dtype=np.uint64).reshape(-1, 4) if challenges is not None else None
+    opts = _ffi.CheckOpts(C.sizeof(_ffi.CheckOpts), C.c_uint64(theta_seed), ch.ctypes.data if ch is not None and ch.size else None,
+                          ch.shape[0] if ch is not None else 0)
+    cap = len(pk.desc["gates"]) + len(pk.desc["lookups"]) + len(pk.desc["permutation_columns"])
+    buf = (_ffi.CheckFailure * max(1, cap))()
+    total = C.c_size_t(0)
+    ctx._chk(ctx.L.amdzk_check_witness(ctx.h, pk.h, ptrs, lens, d_advice.ptr if d_advice is not None else None, advice_stride or n,
+                                       C.byref(opts), buf, cap, C.byref(total)))
+    assert total.value <= cap
+    return WitnessReport(CheckFailure(f.kind, f.index, f.first_row, f.count) for f in buf[:total.value])
 
 
 def proof_size_multi(ctx, pk, n_circuits, transcript=TRANSCRIPT_BLAKE2B):

@@ -616,6 +616,61 @@ int amdzk_quotient_eval_dev(amdzk_ctx* ctx, amdzk_pk* pk, const void* d_polys, s
  * num_challenges phase challenges of the last proof (amdzk_keygen_phased). out may be NULL to query *count (in Fr elements). */
 int amdzk_pk_inspect(amdzk_ctx* ctx, const amdzk_pk* pk, int what, uint64_t* out, size_t cap, size_t* count);
 
+/* ---- check a witness: the constraint checks of dev::MockProver::verify [UP] on the device — does this witness satisfy this
+ * circuit, and if not, which constraints fail and where? What every test of the reference calls (MockProver::run + verify)
+ * before any proof is made; instances / instance_lens / d_advice / advice_stride as for amdzk_create_proof (the advice is
+ * read as it is: no blinding). The call returns AMDZK_OK whenever the check RAN, whether or not the witness is good:
+ * *n_failures is the number of constraints with at least one failing row (the witness satisfies the circuit iff it is 0),
+ * and `out` receives the first min(cap, *n_failures) entries ordered by kind, then by index; out = NULL only queries the
+ * count. One entry per failing constraint, never per row: `count` failing rows and the smallest of them, `first_row`;
+ * `reserved` is 0.
+ *
+ * Semantics: upstream's MockProver::verify_at_rows(usable, usable) without its region and cell-assignment bookkeeping,
+ * which does not cross this boundary. n = 2^k and u = n - (blinding_factors + 1).
+ *   Gates. Gate polynomial g fails at row r < u when it evaluates to a non-zero residue there. Rotations wrap modulo n.
+ *     Cells at rows >= u are read as they are: the key's fixed values, the caller's advice, and 0 for instance columns
+ *     beyond instance_lens. A gate failing only at rows >= u is not reported. (Upstream would call a usable-row gate that
+ *     reads such cells "poisoned" and fail it; this check does not: it evaluates what is there.)
+ *   Lookups. Lookup l fails at row r < u when the tuple of its input expressions at r equals no tuple of its table
+ *     expressions at any row < u. The search runs on theta-compressed values, with theta taken from theta_seed. A
+ *     single-expression lookup is exact. With m expressions a false accept needs a root of a degree-(m - 1) polynomial in
+ *     a theta chosen independently of the witness: at most u (m - 1) / r per row (r the order of the field, about 2^254).
+ *     There are no false rejects.
+ *   Copies. Permutation column i fails at row j, over all n rows, when the value of cell (i, j) differs from the value of
+ *     the cell (i', j') that sigma_i(omega^j) = delta^i' omega^j' names. A broken two-cycle therefore reports both of its
+ *     columns.
+ *   Phases and instances. A phased key (amdzk_keygen_phased) takes the caller's challenge values, so a fork can check phase
+ *     by phase. The call checks one circuit instance; for N instances the caller loops.
+ *   Workspace. The call overwrites the key's per-proof workspace, as amdzk_quotient_eval_dev does. It runs on the ctx's
+ *     stream only and returns with that stream idle. It works on root keys, workspace clones, keys from amdzk_keygen_sigma,
+ *     and keys read from a key file. The first check on a key decodes its sigma columns back to (column, row) pairs —
+ *     2^k x num_perm_columns x 8 bytes, kept with the root key, shared by its clones, never written to the key file.
+ * Field values (advice, instances, challenges) must be below the modulus, as everywhere in this header.
+ * Refused with a message that starts "check_witness:", the ctx and the key stay usable — AMDZK_E_INVALID for: null arguments;
+ * an instance column longer than u ("instance column <c> too long (InstanceTooLarge)", create_proof's wording); missing
+ * challenges, or challenges of the wrong number, for a key that has them (and challenges for a key that has none); a
+ * too-small opts->size; a sigma value that is not delta^i omega^j for a column and row of this circuit (amdzk_keygen_sigma
+ * does not check its input) — the message names the column and the row. */
+#define AMDZK_CHECK_GATE   0  /* index = gate polynomial (expression e < num_gates) */
+#define AMDZK_CHECK_LOOKUP 1  /* index = lookup l */
+#define AMDZK_CHECK_COPY   2  /* index = position in perm_columns */
+typedef struct amdzk_check_failure {
+  uint32_t kind;
+  uint32_t index;
+  uint32_t first_row;
+  uint32_t reserved;
+  uint64_t count;
+} amdzk_check_failure;
+typedef struct amdzk_check_opts {
+  size_t size;                 /* sizeof(amdzk_check_opts) as compiled by the caller; too small is refused */
+  uint64_t theta_seed;         /* the theta that compresses multi-expression lookups: first Fr::random of ChaCha20Rng::seed_from_u64 */
+  const uint64_t* challenges;  /* num_challenges x 4, Montgomery; required iff the key has challenges */
+  uint32_t num_challenges;
+} amdzk_check_opts;
+int amdzk_check_witness(amdzk_ctx* ctx, amdzk_pk* pk, const uint64_t* const* instances, const size_t* instance_lens,
+                        const void* d_advice, size_t advice_stride, const amdzk_check_opts* opts /* NULL: defaults */,
+                        amdzk_check_failure* out, size_t cap, size_t* n_failures);
+
 /* Test hooks for the host pass that prepares quotient-domain programs for the limb-resident interpreter (bounds in
  * units of p, placement of the weak reductions, fusion of `t*x` with the accumulate): the pass on caller-supplied words
  * `op << 24 | arg` (opcodes: csrc/plonk_kernels.hpp ExprOp) — pure host code, callable without a device — and the

@@ -628,6 +628,20 @@ inline G1 best_multiexp(const Context& ctx, const std::vector<Fr>& coeffs, const
 }
 
 // ------------------------------------------------------------------------------------------ keys and proofs
+// What ProvingKey::check_witness found (amdzk_check_witness: MockProver::verify's constraint checks on the device): one
+// entry per failing constraint — a gate polynomial, a lookup, a column of the permutation — with the number of failing
+// rows and the smallest of them, ordered by kind, then index. ok() iff there is none.
+struct CheckFailure {
+  enum Kind : uint32_t { Gate = AMDZK_CHECK_GATE, Lookup = AMDZK_CHECK_LOOKUP, Copy = AMDZK_CHECK_COPY };
+  Kind kind;
+  uint32_t index, first_row;
+  uint64_t count;
+};
+struct WitnessReport {
+  std::vector<CheckFailure> failures;
+  bool ok() const { return failures.empty(); }
+};
+
 // plonk::keygen_vk + keygen_pk: fixed[c] = the 2^k Lagrange values of fixed column c (selectors included).
 class ProvingKey {
  public:
@@ -728,6 +742,39 @@ class ProvingKey {
     fixed.assign(num_fixed_, G1Affine{});
     permutation.assign(num_perm_, G1Affine{});
     ctx_.check(amdzk_pk_commitments(h_, num_fixed_ ? (uint64_t*)fixed.data() : nullptr, num_perm_ ? (uint64_t*)permutation.data() : nullptr));
+  }
+  // dev::MockProver::run(k, &circuit, instances) followed by verify(), for a witness that is already resident: does it
+  // satisfy the circuit, and if not, which gates, lookups and copy constraints fail and where (include/amdzk.h has the
+  // semantics). d_advice: the witness columns on the GPU (column c at d_advice + c * advice_stride Fr), read unblinded.
+  // theta_seed seeds the theta that compresses multi-expression lookups; challenges: the values of a phased key's
+  // challenges. Overwrites the key's per-proof workspace (one call at a time per key, as for create_proof).
+  WitnessReport check_witness(const std::vector<std::vector<Fr>>& instances, const void* d_advice, size_t advice_stride, uint64_t theta_seed = 0,
+                              const std::vector<Fr>& challenges = {}) const {
+    std::vector<const uint64_t*> ptrs(std::max<size_t>(1, instances.size()), nullptr);
+    std::vector<size_t> lens(std::max<size_t>(1, instances.size()), 0);
+    for (size_t i = 0; i < instances.size(); i++) {
+      ptrs[i] = instances[i].empty() ? nullptr : (const uint64_t*)instances[i].data();
+      lens[i] = instances[i].size();
+    }
+    amdzk_check_opts opts = {};
+    opts.size = sizeof(opts);
+    opts.theta_seed = theta_seed;
+    opts.challenges = challenges.empty() ? nullptr : (const uint64_t*)challenges.data();
+    opts.num_challenges = (uint32_t)challenges.size();
+    // one call in the common cases (a satisfying witness, or up to kFirst failing constraints); a longer report is fetched
+    // by a second call with room for all of it
+    constexpr size_t kFirst = 64;
+    std::vector<amdzk_check_failure> raw(kFirst);
+    size_t total = 0;
+    ctx_.check(amdzk_check_witness(ctx_.get(), h_, ptrs.data(), lens.data(), d_advice, advice_stride, &opts, raw.data(), raw.size(), &total));
+    if (total > raw.size()) {
+      raw.resize(total);
+      ctx_.check(amdzk_check_witness(ctx_.get(), h_, ptrs.data(), lens.data(), d_advice, advice_stride, &opts, raw.data(), raw.size(), &total));
+    }
+    raw.resize(std::min(total, raw.size()));
+    WitnessReport rep;
+    for (const amdzk_check_failure& f : raw) rep.failures.push_back(CheckFailure{(CheckFailure::Kind)f.kind, f.index, f.first_row, f.count});
+    return rep;
   }
   amdzk_pk* handle() const { return h_; }
   uint32_t k() const { return k_; }
