@@ -11,28 +11,6 @@
 
 using namespace bn254;
 
-struct amdzk_srs;
-int zk_srs_upload(amdzk_ctx* ctx, const uint64_t* g, const uint64_t* g_lagrange, uint32_t k, amdzk_srs** out);
-void zk_srs_free(amdzk_ctx*, amdzk_srs* s);
-int zk_msm_dev_xyzz(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const Fr* d_scalars, size_t ncols,
-                    size_t len, size_t col_stride, G1X** d_out);
-int zk_msm_dev_xyzz_cols(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const Fr* const* d_col_ptrs, size_t ncols, size_t len,
-                         size_t max_ws_bytes, G1X** d_out);
-int zk_msm_finish(amdzk_ctx* ctx, const G1X* d_res, size_t ncols, uint64_t* out_jac);
-int zk_msm_bases_dev_xyzz(amdzk_ctx* ctx, const Fr* d_scalars, size_t ncols, size_t len, size_t col_stride, const G1Affine* d_bases, G1X** d_out);
-int zk_msm_bases_plan_host(size_t ncols, size_t len, uint32_t* window_bits, uint32_t* windows, size_t* scratch_bytes, char why[160]);
-int zk_srs_setup(amdzk_ctx* ctx, uint32_t k, const uint64_t s_mont[4], const uint64_t omega_mont[4], amdzk_srs** out, uint64_t* g_out,
-                 uint64_t* g_lagrange_out);
-size_t zk_srs_serialized_size(uint32_t k);
-int zk_g_to_lagrange(amdzk_ctx* ctx, const uint64_t* g, uint32_t k, const uint64_t omega_inv[4], const uint64_t n_inv[4], uint64_t* out);
-int zk_srs_downsize(amdzk_ctx* ctx, const amdzk_srs* srs, uint32_t new_k, const uint64_t omega_inv[4], const uint64_t n_inv[4], amdzk_srs** out);
-int zk_srs_get(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, uint64_t* out);
-int zk_srs_write(amdzk_ctx* ctx, const amdzk_srs* s, const uint8_t g2[64], const uint8_t s_g2[64], uint8_t* out, size_t cap);
-int zk_srs_read(amdzk_ctx* ctx, const uint8_t* data, size_t len, amdzk_srs** out, uint8_t g2_out[64], uint8_t s_g2_out[64]);
-extern "C" int amdzk_domain_new(amdzk_ctx* ctx, uint32_t j, uint32_t k, struct amdzk_domain** out);
-extern "C" void amdzk_domain_free(amdzk_ctx* ctx, struct amdzk_domain* d);
-extern "C" int amdzk_domain_constant(const struct amdzk_domain* d, int what, uint64_t out[4]);
-
 static thread_local std::string g_init_err;
 
 int zk_ws_reserve(amdzk_ctx* ctx, int slot, size_t bytes, void** out) {

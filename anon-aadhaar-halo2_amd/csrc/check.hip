@@ -1,4 +1,5 @@
-// Device kernels of amdzk_check_witness (MockProver::verify's constraint checks [UP], without its region bookkeeping):
+// amdzk_check_witness (MockProver::verify's constraint checks [UP], without its region bookkeeping): its device kernels,
+// their launch wrappers and, behind them, its host side.
 //
 //   expr_check_kernel    — the gate polynomials as one Lagrange-domain stack program (the interpreter of
 //                          plonk_kernels.hip's expr_eval_kernel, one row per lane, operand stack in LDS) whose values are
@@ -10,10 +11,30 @@
 // A satisfying witness is the common case and pays nothing for the bookkeeping: a wavefront without a failing lane
 // issues no atomic. Where lanes fail, the lowest failing lane of the wavefront adds the wavefront's count and its own
 // row — rows grow with the lane, so it is the wavefront's smallest — with two vector atomics.
-#include "check_kernels.hpp"
+#include <stdlib.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
 #include "fp29.cuh"
+#include "hostcrypto.hpp"
+#include "pk.hpp"
 
 using namespace bn254;
+using zkhost::ChaCha20Rng;
+
+// One more instruction of Lagrange-domain programs, executed by expr_check_kernel only: pop the top of stack; where it is
+// a non-zero residue on a row < usable, constraint `arg` has one more failing row. (Beside plonk_kernels.hpp's ExprOp,
+// whose interpreters ignore it.)
+constexpr uint32_t OP_CHECK = 24;
+
+// What a check leaves per constraint: count[c] failing rows, the smallest of them in first[c] (UINT32_MAX: none). The
+// caller clears both before the kernels run (count to 0, first to 0xFF bytes).
+struct CheckCounters {
+  unsigned long long* count;
+  uint32_t* first;
+};
 
 namespace {
 
@@ -198,6 +219,7 @@ __global__ __launch_bounds__(256) void copy_check_kernel(const Fr* const* cols, 
 }  // namespace
 
 // ------------------------------------------------------------------------------ launch wrappers
+// A Lagrange-domain program (ExprArgs as for zk_expr_eval, radix 2^256) whose values end in OP_CHECK instead of OP_STORE.
 int zk_check_expr(amdzk_ctx* ctx, const ExprArgs& a, uint32_t depth, uint32_t usable, CheckCounters out, const char* name) {
   const size_t shmem = (size_t)(depth ? depth : 1) * EXPR_THREADS * sizeof(Fr);
   const dim3 grid((unsigned)((a.nrows + EXPR_THREADS - 1) / EXPR_THREADS), a.nparts ? a.nparts : 1u), block(EXPR_THREADS);
@@ -209,6 +231,9 @@ int zk_check_expr(amdzk_ctx* ctx, const ExprArgs& a, uint32_t depth, uint32_t us
   return AMDZK_OK;
 }
 
+// inputs / tables: [L][n] canonical keys (Fr::to_repr), every table sorted ascending with its rows >= usable padded by
+// all-ones keys (zk_sort_keys' convention): input row r < usable of lookup l fails constraint first_constraint + l when
+// its key is none of the table's first `usable` keys.
 int zk_check_lookups(amdzk_ctx* ctx, const Fr* d_inputs, const Fr* d_tables, size_t L, uint32_t n, uint32_t usable, uint32_t first_constraint,
                      CheckCounters out) {
   if (!L || !usable) return AMDZK_OK;
@@ -218,6 +243,9 @@ int zk_check_lookups(amdzk_ctx* ctx, const Fr* d_inputs, const Fr* d_tables, siz
   return AMDZK_OK;
 }
 
+// sigma: [S][n] Montgomery values delta^i' omega^j' -> cells[c * n + j] = (i', j'). d_tab: S values delta^(i * 2^k), S values
+// delta^(-i), k values omega^(-(2^b)). A value that is no delta^i omega^j with i < S leaves (c << 32 | j) + 1 of the smallest
+// such cell in *d_bad (the caller sets it to all ones: none).
 int zk_sigma_decode(amdzk_ctx* ctx, const Fr* d_sigma, uint32_t S, uint32_t k, const Fr* d_tab, uint2* d_cells, unsigned long long* d_bad) {
   if (!S) return AMDZK_OK;
   if (S > 65535 || k > 31) ZK_FAIL(ctx, AMDZK_E_INVALID, "sigma_decode: bad shape");
@@ -226,10 +254,202 @@ int zk_sigma_decode(amdzk_ctx* ctx, const Fr* d_sigma, uint32_t S, uint32_t k, c
   return AMDZK_OK;
 }
 
+// cell (c, j) of the permutation fails constraint first_constraint + c when its value differs from the value of the cell
+// d_cells names for it; d_cols[c]: the Lagrange values of permutation column c (n rows).
 int zk_check_copies(amdzk_ctx* ctx, const Fr* const* d_cols, const uint2* d_cells, uint32_t S, uint32_t n, uint32_t first_constraint,
                     CheckCounters out) {
   if (!S) return AMDZK_OK;
   if (S > 65535) ZK_FAIL(ctx, AMDZK_E_INVALID, "check_copies: bad shape");
   ZK_LAUNCH(ctx, "check_copies", copy_check_kernel, dim3((n + 255) / 256, S), dim3(256), 0, d_cols, d_cells, n, first_constraint, out);
   return AMDZK_OK;
+}
+
+// ------------------------------------------------------------------------------ host side
+// ---- amdzk_check_witness: MockProver::verify's constraint checks on the device (include/amdzk.h has the semantics).
+// What this handle needs beyond what a proof uses, made by its first check: the gate program, the permutation columns'
+// addresses in this workspace, the counters.
+static int check_build(amdzk_ctx* ctx, amdzk_pk* pk) {
+  amdzk_pk::Check& ck = pk->chk;
+  if (ck.built) return AMDZK_OK;
+  const uint32_t ncon = pk->num_gates + pk->L + pk->S;
+  if (!ck.prog_gates.d_instr) {
+    Program pr;
+    const RotTable rots_before = pk->rots;  // the gates' rotations are all in the table already: the h(X) program queried them
+    for (uint32_t g = 0; g < pk->num_gates; g++) {
+      pr.piece();
+      ZK_TRY(emit_expr(ctx, pk, pr, pk->exprs[g]));
+      pr.op(OP_CHECK, g);
+      pr.pop();
+    }
+    if (pk->rots.rots.size() != rots_before.rots.size()) {  // cannot happen for a key keygen made; the table stays what the uploaded programs index
+      pk->rots = rots_before;
+      ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: a gate polynomial queries a rotation the key's programs do not");
+    }
+    ck.prog_gates = pr;
+    ZK_TRY(upload_program(ctx, pk, ck.prog_gates, false));
+  }
+  if (pk->S && !ck.d_perm_cols) {
+    std::vector<const Fr*> cols(pk->S);
+    for (uint32_t i = 0; i < pk->S; i++) {
+      const std::pair<int, int>& kc = pk->perm_cols[i];
+      cols[i] = pk->h_cols_lag[kc.first == 0 ? pk->sl_adv(kc.second) : kc.first == 1 ? pk->sl_fixed(kc.second) : pk->sl_inst(kc.second)];
+    }
+    ZK_TRY(dalloc(ctx, pk, &ck.d_perm_cols, cols.size()));
+    ZK_TRY(h2d(ctx, ck.d_perm_cols, cols.data(), cols.size() * sizeof(Fr*)));
+    ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));  // `cols` is a host temporary
+  }
+  if (!ck.d_count) {
+    ZK_TRY(dalloc(ctx, pk, &ck.d_count, (size_t)ncon + ((size_t)ncon + 1) / 2 + 1));  // u64 counts, then u32 first rows
+    ck.d_first = reinterpret_cast<uint32_t*>(ck.d_count + ncon);
+  }
+  ck.built = true;
+  return AMDZK_OK;
+}
+
+// The root key's sigma columns back to (column, row), once: S * n * 8 bytes that every handle of the key reads.
+static int check_decode_sigma(amdzk_ctx* ctx, amdzk_pk* pk) {
+  amdzk_pk::CheckShared& sh = *pk->chk_shared;
+  std::lock_guard<std::mutex> lock(sh.guard);
+  if (sh.decoded || !pk->S) return AMDZK_OK;
+  const uint32_t S = pk->S, k = pk->k;
+  const size_t n = pk->n;
+  if (!sh.d_cells) {
+    void* q = nullptr;
+    if (hipMalloc(&q, (size_t)S * n * sizeof(uint2)) != hipSuccess) ZK_FAIL(ctx, AMDZK_E_NOMEM, "check_witness: hipMalloc of the decoded permutation failed");
+    sh.d_cells = (uint2*)q;
+  }
+  // delta^(i 2^k), delta^(-i) for i < S, omega^(-(2^b)) for b < k
+  std::vector<Fr> tab(2 * (size_t)S + k);
+  const Fr delta = fr_delta(), delta_inv = inv(delta);
+  Fr d2k = delta;
+  for (uint32_t i = 0; i < k; i++) d2k = mul(d2k, d2k);
+  Fr a = Fr::one(), b = Fr::one();
+  for (uint32_t i = 0; i < S; i++) {
+    tab[i] = a;
+    tab[S + i] = b;
+    a = mul(a, d2k);
+    b = mul(b, delta_inv);
+  }
+  Fr w = pk->omega_inv;
+  for (uint32_t i = 0; i < k; i++) {
+    tab[2 * (size_t)S + i] = w;
+    w = mul(w, w);
+  }
+  void* d_tab = nullptr;
+  if (hipMalloc(&d_tab, tab.size() * 32 + 8) != hipSuccess) ZK_FAIL(ctx, AMDZK_E_NOMEM, "check_witness: hipMalloc failed");
+  unsigned long long* d_bad = reinterpret_cast<unsigned long long*>((Fr*)d_tab + tab.size());
+  unsigned long long bad = 0;
+  int r = h2d(ctx, d_tab, tab.data(), tab.size() * 32);
+  if (r == AMDZK_OK && hipMemsetAsync(d_bad, 0xFF, 8, ctx->stream) != hipSuccess) r = AMDZK_E_HIP;
+  if (r == AMDZK_OK) r = zk_sigma_decode(ctx, pk->sigma_lag, S, k, (const Fr*)d_tab, sh.d_cells, d_bad);
+  if (r == AMDZK_OK) r = d2h(ctx, &bad, d_bad, 8);
+  else (void)zk_host_wait(ctx, ctx->stream);  // `tab` is a host temporary
+  hipFree(d_tab);
+  ZK_TRY(r);
+  if (bad != ~0ull) {
+    const unsigned long long cell = bad - 1;
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: sigma column %u row %u is not delta^i omega^j for a column i < %u of this circuit",
+            (uint32_t)(cell >> 32), (uint32_t)cell, S);
+  }
+  sh.decoded = true;
+  return AMDZK_OK;
+}
+
+static int check_witness_run(amdzk_ctx* ctx, amdzk_pk* pk, const uint64_t* const* instances, const size_t* instance_lens, const void* d_advice,
+                             size_t advice_stride, const amdzk_check_opts* opts, amdzk_check_failure* out, size_t cap, size_t* n_failures) {
+  if (!pk || !n_failures || (pk->A && !d_advice)) ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: null argument");
+  if (opts && opts->size < sizeof(amdzk_check_opts))
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: amdzk_check_opts.size is %zu, this library needs %zu", opts->size, sizeof(amdzk_check_opts));
+  const size_t n = pk->n, usable = n - (pk->bf + 1);
+  const uint32_t A = pk->A, I = pk->I, L = pk->L, S = pk->S, G = pk->num_gates, ncon = G + L + S;
+  if (pk->A && advice_stride < n) ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: advice stride < n");
+  const uint32_t given = opts && opts->challenges ? opts->num_challenges : 0;
+  if (pk->num_challenges && !given) ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: the key has %u challenges and none were given", pk->num_challenges);
+  if ((opts ? opts->num_challenges : 0) != pk->num_challenges)
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: %u challenges given, the key has %u", opts ? opts->num_challenges : 0, pk->num_challenges);
+  for (uint32_t c = 0; c < I; c++) {
+    const size_t len = instance_lens ? instance_lens[c] : 0;
+    if (len > usable) ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: instance column %u too long (InstanceTooLarge)", c);
+    if (len && (!instances || !instances[c])) ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: null argument (instance column %u)", c);
+  }
+  amdzk_pk* const root = const_cast<amdzk_pk*>(pk->clone_of ? pk->clone_of : pk);
+  ZK_TRY(check_build(ctx, pk));
+  ZK_TRY(check_decode_sigma(ctx, root));
+  const amdzk_pk::Check& ck = pk->chk;
+  const CheckCounters counters = {ck.d_count, ck.d_first};
+  *n_failures = 0;
+  if (!ncon) return AMDZK_OK;
+  ZK_HIP(ctx, hipMemsetAsync(ck.d_count, 0, (size_t)ncon * 8, ctx->stream));
+  ZK_HIP(ctx, hipMemsetAsync(ck.d_first, 0xFF, (size_t)ncon * 4, ctx->stream));
+  // the witness into the workspace as create_proof copies it, unblinded: instance columns zero behind the caller's values
+  if (I) {
+    ZK_HIP(ctx, hipMemsetAsync(pk->inst(), 0, (size_t)I * n * 32, ctx->stream));
+    for (uint32_t c = 0; c < I; c++) {
+      const size_t len = instance_lens ? instance_lens[c] : 0;
+      if (!len) continue;
+      ZK_TRY(h2d_staged(ctx, pk, pk->inst() + (size_t)c * n, instances[c], len * 32));
+    }
+  }
+  if (A) ZK_HIP(ctx, hipMemcpy2DAsync(pk->adv(), n * 32, d_advice, advice_stride * 32, n * 32, A, hipMemcpyDeviceToDevice, ctx->stream));
+  {  // theta and the phase challenges into their slots of the constant table
+    ChaCha20Rng rng(opts ? opts->theta_seed : 0);
+    pk->consts[pk->c_theta] = rng.fr();
+    ZK_TRY(h2d_staged(ctx, pk, pk->d_consts + pk->c_theta, &pk->consts[pk->c_theta], 32));
+    if (pk->num_challenges) {
+      memcpy(pk->consts[pk->c_chal0].l, opts->challenges, (size_t)pk->num_challenges * 32);
+      ZK_TRY(h2d_staged(ctx, pk, pk->d_consts + pk->c_chal0, &pk->consts[pk->c_chal0], (size_t)pk->num_challenges * 32));
+    }
+  }
+  if (G) {
+    ExprArgs a;
+    ZK_TRY(program_args(ctx, pk, pk->chk.prog_gates, false, nullptr, nullptr, a));
+    ZK_TRY(zk_check_expr(ctx, a, ck.prog_gates.depth + 1, (uint32_t)usable, counters, "expr_check_gates"));
+  }
+  if (L) {  // compressed inputs and tables as canonical keys, the tables sorted (constant ones were sorted at keygen)
+    ZK_TRY(run_program(ctx, pk, pk->prog_compress, false, pk->d_outs_compress, nullptr, "expr_lookup_compress"));
+    ZK_TRY(d2d(ctx, pk->la(), pk->ci, (size_t)L * n * 32));
+    ZK_TRY(amdzk_fr_to_repr_dev(ctx, pk->la(), (size_t)L * n));
+    const uint32_t pre = pk->lk_const, rest = L - pre;
+    if (pre) ZK_TRY(d2d(ctx, pk->lk_ts, pk->lk_ts_const, (size_t)pre * n * 32));
+    if (rest) {
+      Fr* Tr = pk->lk_ts + (size_t)pre * n;
+      ZK_TRY(d2d(ctx, Tr, pk->ct + (size_t)pre * n, (size_t)rest * n * 32));
+      ZK_TRY(amdzk_fr_to_repr_dev(ctx, Tr, (size_t)rest * n));
+      ZK_HIP(ctx, hipMemset2DAsync(Tr + usable, n * 32, 0xFF, (n - usable) * 32, rest, ctx->stream));
+      ZK_TRY(zk_sort_keys(ctx, Tr, rest, (uint32_t)n, n));
+    }
+    ZK_TRY(zk_check_lookups(ctx, pk->la(), pk->lk_ts, L, (uint32_t)n, (uint32_t)usable, G, counters));
+  }
+  if (S) ZK_TRY(zk_check_copies(ctx, ck.d_perm_cols, root->chk_shared->d_cells, S, (uint32_t)n, G + L, counters));
+  std::vector<unsigned long long> host((size_t)ncon + ((size_t)ncon + 1) / 2);
+  ZK_TRY(d2h(ctx, host.data(), ck.d_count, (size_t)ncon * 12));
+  const uint32_t* first = reinterpret_cast<const uint32_t*>(host.data() + ncon);
+  size_t nf = 0;
+  for (uint32_t c = 0; c < ncon; c++) {
+    if (!host[c]) continue;
+    if (out && nf < cap) {
+      amdzk_check_failure& f = out[nf];
+      f.kind = c < G ? AMDZK_CHECK_GATE : c < G + L ? AMDZK_CHECK_LOOKUP : AMDZK_CHECK_COPY;
+      f.index = c < G ? c : c < G + L ? c - G : c - G - L;
+      f.first_row = first[c];
+      f.reserved = 0;
+      f.count = host[c];
+    }
+    nf++;
+  }
+  *n_failures = nf;
+  return AMDZK_OK;
+}
+
+extern "C" int amdzk_check_witness(amdzk_ctx* ctx, amdzk_pk* pk, const uint64_t* const* instances, const size_t* instance_lens, const void* d_advice,
+                        size_t advice_stride, const amdzk_check_opts* opts, amdzk_check_failure* out, size_t cap, size_t* n_failures) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  const int r = check_witness_run(ctx, pk, instances, instance_lens, d_advice, advice_stride, opts, out, cap, n_failures);
+  if (r != AMDZK_OK) {  // whatever was enqueued (copies from the caller's memory among it) is finished before the call returns
+    const std::string keep = ctx->err;
+    (void)zk_host_wait(ctx, ctx->stream);
+    ctx->err = keep;
+  }
+  return r;
 }

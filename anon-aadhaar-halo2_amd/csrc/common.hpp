@@ -234,6 +234,45 @@ struct NttTables {
   size_t out_z_stride = 0;
 };
 
-// entry points implemented in the kernel translation units
+// ---- what one translation unit calls in another: declared here and nowhere else
+
+// ntt.hip
 int zk_ntt_dev(amdzk_ctx* ctx, bn254::Fr* d_a, uint32_t log_n, const uint64_t omega[4],
                uint32_t flags, size_t ncols, size_t col_stride);
+int zk_ntt_ex(amdzk_ctx* ctx, const bn254::Fr* d_in, size_t in_stride, bn254::Fr* d_out, size_t out_stride, uint32_t log_n,
+              const uint64_t omega[4], size_t ncols, uint32_t in_len, const bn254::Fr* in_coset, const bn254::Fr* out_mul,
+              const bn254::Fr* in_first, const NttTables* tabs);
+bn254::Fr zk_fr_inv_pow2(uint32_t log_n);
+
+// msm.hip
+int zk_srs_upload(amdzk_ctx* ctx, const uint64_t* g, const uint64_t* g_lagrange, uint32_t k, amdzk_srs** out);
+void zk_srs_free(amdzk_ctx*, amdzk_srs* s);
+uint32_t zk_srs_k(const amdzk_srs* srs);
+bool zk_srs_has_basis(const amdzk_srs* srs, int basis);
+int zk_msm_dev_xyzz(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const bn254::Fr* d_scalars, size_t ncols, size_t len, size_t col_stride,
+                    bn254::G1X** d_out);
+int zk_msm_dev_xyzz_cols(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const bn254::Fr* const* d_col_ptrs, size_t ncols, size_t len,
+                         size_t max_ws_bytes, bn254::G1X** d_out);
+int zk_msm_finish(amdzk_ctx* ctx, const bn254::G1X* d_res, size_t ncols, uint64_t* out_jac);
+int zk_msm_bases_dev_xyzz(amdzk_ctx* ctx, const bn254::Fr* d_scalars, size_t ncols, size_t len, size_t col_stride, const bn254::G1Affine* d_bases,
+                          bn254::G1X** d_out);
+int zk_msm_bases_plan_host(size_t ncols, size_t len, uint32_t* window_bits, uint32_t* windows, size_t* scratch_bytes, char why[160]);
+int zk_srs_setup(amdzk_ctx* ctx, uint32_t k, const uint64_t s_mont[4], const uint64_t omega_mont[4], amdzk_srs** out, uint64_t* g_out,
+                 uint64_t* g_lagrange_out);
+size_t zk_srs_serialized_size(uint32_t k);
+int zk_g_to_lagrange(amdzk_ctx* ctx, const uint64_t* g, uint32_t k, const uint64_t omega_inv[4], const uint64_t n_inv[4], uint64_t* out);
+int zk_srs_downsize(amdzk_ctx* ctx, const amdzk_srs* srs, uint32_t new_k, const uint64_t omega_inv[4], const uint64_t n_inv[4], amdzk_srs** out);
+int zk_srs_get(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, uint64_t* out);
+int zk_srs_write(amdzk_ctx* ctx, const amdzk_srs* s, const uint8_t g2[64], const uint8_t s_g2[64], uint8_t* out, size_t cap);
+int zk_srs_read(amdzk_ctx* ctx, const uint8_t* data, size_t len, amdzk_srs** out, uint8_t g2_out[64], uint8_t s_g2_out[64]);
+
+// poly.hip
+int zk_lagrange_to_coeff(amdzk_ctx* ctx, const amdzk_domain* d, const bn254::Fr* d_in, size_t in_stride, bn254::Fr* d_out, size_t out_stride,
+                         size_t ncols);
+// prover-private: the quotient domain = nc cosets of the size-n subgroup, data in Montgomery radix 2^261 (poly.hip) —
+// what the h(X) program multiplies in
+int zk_quotient_plan(amdzk_ctx* ctx, amdzk_domain* d, uint32_t nc);
+bn254::Fr zk_quotient_coset_g(const amdzk_domain* d, uint32_t c);
+int zk_coeff_to_cosets_r261(amdzk_ctx* ctx, const amdzk_domain* d, const bn254::Fr* d_coeff, size_t in_stride, bn254::Fr* d_out, size_t out_stride,
+                            size_t ncols);
+int zk_cosets_to_pieces(amdzk_ctx* ctx, const amdzk_domain* d, bn254::Fr* d_h, bn254::Fr* d_pieces, uint32_t npieces);

@@ -1,0 +1,1004 @@
+// A proving key's life: keygen (plonk::keygen::{keygen_vk, keygen_pk} [UP]) from a circuit description and its fixed
+// columns with either the copy-constraint mapping or the sigma columns, workspace clones, the key file (pkblob.hpp has its
+// layout), inspection and export, and the release of all of it. The circuit arrives as a plain-data description of its
+// ConstraintSystem (amdzk_circuit). Control flow and the O(columns) bookkeeping are host code; every O(n) step is a kernel
+// of another unit on resident columns. No kernel lives here.
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <map>
+#include <memory>
+#include <string>
+
+#include "pk.hpp"
+
+using namespace bn254;
+
+int h2d(amdzk_ctx* ctx, void* d, const void* h, size_t bytes) {
+  if (bytes) ZK_HIP(ctx, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, ctx->stream));
+  return AMDZK_OK;
+}
+// host -> device through the key's pinned staging area: the source may be a temporary, and the copy
+// is truly asynchronous (no pageable-memory staging inside the runtime).
+int h2d_staged(amdzk_ctx* ctx, amdzk_pk* pk, void* d, const void* h, size_t bytes) {
+  if (!bytes) return AMDZK_OK;
+  if (!pk->pin || bytes > pk->pin_cap) return h2d(ctx, d, h, bytes);
+  size_t off = (pk->pin_off + 63) & ~(size_t)63;
+  if (off + bytes > pk->pin_cap) {  // wrap: every stream that may still be reading the staging area must be done with it
+    ZK_TRY(zk_sync_all(ctx));
+    off = 0;
+  }
+  memcpy(pk->pin + off, h, bytes);
+  pk->pin_off = off + bytes;
+  ZK_HIP(ctx, hipMemcpyAsync(d, pk->pin + off, bytes, hipMemcpyHostToDevice, ctx->stream));
+  return AMDZK_OK;
+}
+int d2h(amdzk_ctx* ctx, void* h, const void* d, size_t bytes) {
+  if (bytes) {
+    ZK_HIP(ctx, hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
+  }
+  return AMDZK_OK;
+}
+int d2d(amdzk_ctx* ctx, void* dst, const void* src, size_t bytes) {
+  if (bytes) ZK_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  return AMDZK_OK;
+}
+
+namespace {
+
+// Owns a key from `new amdzk_pk` until it is handed to the caller: an early return in between frees what the key holds by
+// then. (ZK_FAIL has set ctx->err before the return runs this; amdzk_pk_free leaves ctx->err alone.)
+struct PkFree {
+  amdzk_ctx* ctx;
+  void operator()(amdzk_pk* pk) const { amdzk_pk_free(ctx, pk); }
+};
+using PkOwner = std::unique_ptr<amdzk_pk, PkFree>;
+
+}  // namespace
+
+// The per-proof workspace of ONE circuit instance (arenas, lookup / product scratch, multiopen buffers, small staging):
+// what a key owns besides its key material, and all a workspace clone allocates.
+static int alloc_proof_workspace(amdzk_ctx* ctx, amdzk_pk* pk) {
+  const size_t n = pk->n, ext = pk->ext;
+  const uint32_t A = pk->A, I = pk->I, L = pk->L, ns = pk->nsets;
+  pk->NP = (size_t)A + I + 2 * L + ns + L;
+  ZK_TRY(dalloc(ctx, pk, &pk->P, pk->NP * n));
+  ZK_TRY(dalloc(ctx, pk, &pk->PQ, pk->NP * n));
+  ZK_TRY(dalloc(ctx, pk, &pk->PC, pk->NP * ext));
+  ZK_TRY(dalloc(ctx, pk, &pk->ci, (size_t)L * n));
+  ZK_TRY(dalloc(ctx, pk, &pk->ct, (size_t)L * n));
+  ZK_TRY(dalloc(ctx, pk, &pk->lk_ts, (size_t)L * n));
+  ZK_TRY(dalloc(ctx, pk, &pk->lk_left, (size_t)L * n));
+  ZK_TRY(dalloc(ctx, pk, &pk->lk_flags, (size_t)4 * L * (n + 8)));
+  ZK_TRY(dalloc(ctx, pk, &pk->d_err, 1));
+  ZK_TRY(dalloc(ctx, pk, &pk->rnd, n));
+  ZK_TRY(dalloc(ctx, pk, &pk->hq, (size_t)H_PARTS_MAX * ext));  // one h per piece of the cut h(X) program (finalize_limb_program)
+  ZK_TRY(dalloc(ctx, pk, &pk->hpieces, (size_t)pk->qdeg * n));
+  ZK_TRY(dalloc(ctx, pk, &pk->hpoly, n));
+  const size_t nfrac = std::max<size_t>(std::max<size_t>(ns, L), 1);
+  ZK_TRY(dalloc(ctx, pk, &pk->frac, nfrac * n));
+  ZK_TRY(dalloc(ctx, pk, &pk->scratch, std::max(nfrac * n, ext)));
+  ZK_TRY(dalloc(ctx, pk, &pk->scan_tmp, zk_scan_totals_elems(n, nfrac) + 2 * nfrac + 8));
+  ZK_TRY(dalloc(ctx, pk, &pk->frac2, std::max<size_t>(L, 1) * n));
+  ZK_TRY(dalloc(ctx, pk, &pk->scratch2, std::max<size_t>(L, 1) * n));
+  ZK_TRY(dalloc(ctx, pk, &pk->scan_tmp2, zk_scan_totals_elems(n, std::max<size_t>(L, 1)) + 2 * std::max<size_t>(L, 1) + 8));
+  const size_t max_rsets = pk->max_sets;
+  ZK_TRY(dalloc(ctx, pk, &pk->sets_L, max_rsets * n));
+  ZK_TRY(dalloc(ctx, pk, &pk->sets_N, max_rsets * n));
+  ZK_TRY(dalloc(ctx, pk, &pk->hx, n));
+  pk->small_cap = std::max<size_t>((size_t)pk->NP * (pk->bf + 2) + 4096, 8192);
+  for (int l = 0; l < 3; l++) ZK_TRY(dalloc(ctx, pk, &pk->small_l[l], pk->small_cap));
+  pk->small = pk->small_l[0];
+  pk->pin_cap = std::max<size_t>((size_t)8 << 20, 2 * n * 32);
+  if (hipHostMalloc((void**)&pk->pin, pk->pin_cap + 64, hipHostMallocDefault) != hipSuccess) {
+    pk->pin = nullptr;
+    pk->pin_cap = 0;
+    ZK_FAIL(ctx, AMDZK_E_NOMEM, "prover: hipHostMalloc of the pinned staging area failed");
+  }
+  pk->h_err = (int*)(pk->pin + pk->pin_cap);  // behind the staging ring
+  pk->ptrs_cap = 8192;
+  for (int l = 0; l < 3; l++) {
+    void** pp = nullptr;
+    ZK_TRY(dalloc(ctx, pk, &pp, pk->ptrs_cap));
+    pk->ptrs_l[l] = pp;
+  }
+  pk->ptrs = pk->ptrs_l[0];
+
+  return AMDZK_OK;
+}
+
+// The slot -> column pointer tables the interpreters read (Lagrange and quotient domain): key columns and this
+// workspace's arenas.
+static int build_column_tables(amdzk_ctx* ctx, amdzk_pk* pk) {
+  const size_t n = pk->n, ext = pk->ext;
+  const uint32_t F = pk->F, A = pk->A, I = pk->I, S = pk->S, L = pk->L, ns = pk->nsets;
+  // ---- column pointer tables
+  {
+    std::vector<const Fr*> lag(pk->nslots_lag()), ex(pk->nslots_ext());
+    for (uint32_t i = 0; i < F; i++) lag[pk->sl_fixed(i)] = pk->fixed_lag + (size_t)i * n, ex[i] = pk->fixed_coset + (size_t)i * ext;
+    for (uint32_t i = 0; i < A; i++) lag[pk->sl_adv(i)] = pk->adv() + (size_t)i * n, ex[pk->sl_adv(i)] = pk->PC + (size_t)i * ext;
+    for (uint32_t i = 0; i < I; i++) lag[pk->sl_inst(i)] = pk->inst() + (size_t)i * n, ex[pk->sl_inst(i)] = pk->PC + (size_t)(A + i) * ext;
+    for (uint32_t i = 0; i < S; i++) lag[pk->sl_sigma(i)] = pk->sigma_lag + (size_t)i * n, ex[pk->se_sigma(i)] = pk->sigma_coset + (size_t)i * ext;
+    for (uint32_t i = 0; i < S; i++) lag[pk->sl_dxw(i)] = pk->dxw_lag + (size_t)i * n, ex[pk->se_dx(i)] = pk->dx_coset + (size_t)i * ext;
+    for (uint32_t l = 0; l < L; l++) {
+      lag[pk->sl_ci(l)] = pk->ci + (size_t)l * n;
+      lag[pk->sl_ct(l)] = pk->ct + (size_t)l * n;
+      lag[pk->sl_la(l)] = pk->la() + (size_t)l * n;
+      lag[pk->sl_ls(l)] = pk->ls() + (size_t)l * n;
+      ex[pk->se_la(l)] = pk->PC + (size_t)(A + I + l) * ext;
+      ex[pk->se_ls(l)] = pk->PC + (size_t)(A + I + L + l) * ext;
+      ex[pk->se_zl(l)] = pk->PC + (size_t)(A + I + 2 * L + ns + l) * ext;
+    }
+    for (uint32_t s = 0; s < ns; s++) ex[pk->se_zp(s)] = pk->PC + (size_t)(A + I + 2 * L + s) * ext;
+    lag[pk->sl_omega()] = pk->omega_pow;
+    ex[pk->se_l0()] = pk->l0_c;
+    ex[pk->se_llast()] = pk->llast_c;
+    ex[pk->se_lactive()] = pk->lactive_c;
+    ex[pk->se_x()] = pk->x_coset;
+    pk->h_cols_lag = lag;
+    pk->h_cols_ext = ex;
+    ZK_TRY(dalloc(ctx, pk, &pk->d_cols_lag, lag.size()));
+    ZK_TRY(dalloc(ctx, pk, &pk->d_cols_ext, ex.size()));
+    ZK_TRY(h2d(ctx, pk->d_cols_lag, lag.data(), lag.size() * sizeof(Fr*)));
+    ZK_TRY(h2d(ctx, pk->d_cols_ext, ex.data(), ex.size() * sizeof(Fr*)));
+    ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
+  }
+
+  return AMDZK_OK;
+}
+
+// Where the Lagrange-domain programs store: compressed lookup inputs / tables, permutation fractions, lookup fractions.
+static int build_output_tables(amdzk_ctx* ctx, amdzk_pk* pk) {
+  const size_t n = pk->n;
+  const uint32_t L = pk->L, ns = pk->nsets;
+  {
+    std::vector<Fr*> outs(2 * L);
+    for (uint32_t l = 0; l < L; l++) outs[2 * l] = pk->ci + (size_t)l * n, outs[2 * l + 1] = pk->ct + (size_t)l * n;
+    ZK_TRY(dalloc(ctx, pk, &pk->d_outs_compress, outs.size()));
+    ZK_TRY(h2d(ctx, pk->d_outs_compress, outs.data(), outs.size() * sizeof(Fr*)));
+    ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
+  }
+  {
+    std::vector<Fr*> outs(2 * ns);
+    for (uint32_t s = 0; s < ns; s++) outs[2 * s] = pk->frac + (size_t)s * n, outs[2 * s + 1] = pk->zp() + (size_t)s * n;
+    ZK_TRY(dalloc(ctx, pk, &pk->d_outs_pfrac, outs.size()));
+    ZK_TRY(h2d(ctx, pk->d_outs_pfrac, outs.data(), outs.size() * sizeof(Fr*)));
+    ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
+  }
+  {
+    std::vector<Fr*> outs(2 * L);
+    for (uint32_t l = 0; l < L; l++) outs[2 * l] = pk->frac2 + (size_t)l * n, outs[2 * l + 1] = pk->zl() + (size_t)l * n;  // frac2: beside the permutation products
+    ZK_TRY(dalloc(ctx, pk, &pk->d_outs_lfrac, outs.size()));
+    ZK_TRY(h2d(ctx, pk->d_outs_lfrac, outs.data(), outs.size() * sizeof(Fr*)));
+    ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
+  }
+  return AMDZK_OK;
+}
+
+// What a key handle holds for ITS workspace besides the arenas: the pointer tables, the constant tables, the powers of
+// y, and the four programs resolved to this workspace's addresses. Keygen and amdzk_pk_clone_workspace both go through it.
+static int bind_workspace(amdzk_ctx* ctx, amdzk_pk* pk) {
+  ZK_TRY(build_column_tables(ctx, pk));
+  ZK_TRY(build_output_tables(ctx, pk));
+  ZK_TRY(dalloc(ctx, pk, &pk->d_consts, pk->consts.size()));
+  ZK_TRY(h2d(ctx, pk->d_consts, pk->consts.data(), pk->consts.size() * 32));
+  ZK_TRY(dalloc(ctx, pk, &pk->d_consts261, pk->consts.size()));
+  ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
+  ZK_TRY(upload_program(ctx, pk, pk->prog_compress, false));
+  ZK_TRY(upload_program(ctx, pk, pk->prog_pfrac, false));
+  ZK_TRY(upload_program(ctx, pk, pk->prog_lfrac, false));
+  ZK_TRY(dalloc(ctx, pk, &pk->d_ypow, (size_t)std::max<uint32_t>(pk->h_terms, 1)));
+  ZK_TRY(upload_program(ctx, pk, pk->prog_h, true));
+  return upload_consts261(ctx, pk);
+}
+
+// ---- keygen, step by step (keygen_common below runs them in this order)
+
+// The phase table the way ConstraintSystem::{advice_column_in, challenge_usable_after} assert [UP], the flags and the null
+// arguments: pure checks, before anything is allocated. *nphases: the number of phases the table uses (1 without one).
+static int check_keygen_args(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* c, const amdzk_phases* ph,
+                             const uint64_t transcript_repr[4], uint32_t flags, amdzk_pk** out, uint32_t* nphases) {
+  *nphases = 1;
+  if (ph && c) {
+    if ((c->num_advice && !ph->advice_phase) || (ph->num_challenges && !ph->challenge_phase))
+      ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: phase table has a null array");
+    bool has[3] = {false, false, false};
+    for (uint32_t a = 0; a < c->num_advice; a++) {
+      if (ph->advice_phase[a] > 2) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: advice column %u is in phase %u (phases are 0, 1, 2)", a, ph->advice_phase[a]);
+      has[ph->advice_phase[a]] = true;
+    }
+    for (uint32_t p = 1; p < 3; p++)
+      if (has[p]) {
+        if (!has[p - 1]) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: phase %u has advice columns but phase %u has none", p, p - 1);
+        *nphases = p + 1;
+      }
+    for (uint32_t i = 0; i < ph->num_challenges; i++) {
+      const uint32_t p = ph->challenge_phase[i];
+      if (p > 2) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: challenge %u is usable after phase %u (phases are 0, 1, 2)", i, p);
+      if (!has[p]) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: challenge %u is usable after phase %u, which has no advice column", i, p);
+    }
+    if (c->expr_offsets && c->expr_words)
+      for (uint32_t i = 0; i < c->expr_offsets[c->num_exprs]; i++)
+        if ((c->expr_words[i] >> 24) == XOP_CHALLENGE && (c->expr_words[i] & 0xffffffu) >= ph->num_challenges)
+          ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: challenge index %u out of range (num_challenges = %u)", c->expr_words[i] & 0xffffffu,
+                  ph->num_challenges);
+  }
+  if (flags & ~(uint32_t)(AMDZK_KEYGEN_FULL_COSETS | AMDZK_KEYGEN_SERIAL)) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: unknown flags %#x", flags);
+  if (!srs || !c || !out || !transcript_repr) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: null argument");
+  if (c->cs_degree < 3) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: cs_degree %u < 3", c->cs_degree);
+  return AMDZK_OK;
+}
+
+// The circuit description into the key — shape, domain, queries, expressions, the key file's header — and the layout of
+// the constant table.
+static int describe_circuit(amdzk_ctx* ctx, amdzk_pk* pk, const amdzk_srs* srs, const amdzk_circuit* c, const amdzk_phases* ph, uint32_t nphases,
+                            const uint64_t transcript_repr[4], uint32_t flags) {
+  pk->srs = srs;
+  pk->chk_shared = std::make_shared<amdzk_pk::CheckShared>();
+  pk->k = c->k;
+  pk->n = (size_t)1 << c->k;
+  pk->bf = c->blinding_factors;
+  pk->degree = c->cs_degree;
+  pk->F = c->num_fixed;
+  pk->A = c->num_advice;
+  pk->I = c->num_instance;
+  pk->S = c->num_perm_columns;
+  pk->L = c->num_lookups;
+  pk->chunk = pk->degree - 2;
+  pk->nsets = (pk->S + pk->chunk - 1) / pk->chunk;
+  pk->qdeg = pk->degree - 1;
+  if (pk->S) ZK_TRY(zk_srs_ensure_prefix(ctx, srs));  // the permutation products are committed over it (Prover::perm_commit)
+  if (ph) {
+    pk->nphases = nphases;
+    pk->num_challenges = ph->num_challenges;
+    pk->advice_phase.assign(ph->advice_phase, ph->advice_phase + (c->num_advice ? c->num_advice : 0));
+    pk->challenge_phase.assign(ph->challenge_phase, ph->challenge_phase + ph->num_challenges);
+  }
+  if (pk->n < pk->bf + 3) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: not enough rows (n = %zu, blinding factors = %u)", pk->n, pk->bf);
+  memcpy(pk->transcript_repr.l, transcript_repr, 32);
+  ZK_TRY(amdzk_domain_new(ctx, pk->degree, pk->k, &pk->dom));
+  pk->ek = amdzk_domain_extended_k(pk->dom);
+  // h(X) has qdeg = degree - 1 pieces: that many cosets pin it down (AMDZK_FULL_COSETS=1: all 2^(ek-k), upstream's own
+  // computation — identical output for satisfying witnesses, and the way to reproduce upstream's bytes for others)
+  pk->nc = (flags & AMDZK_KEYGEN_FULL_COSETS) ? (1u << (pk->ek - pk->k)) : pk->qdeg;
+  pk->use_lanes = !(flags & AMDZK_KEYGEN_SERIAL);
+  ZK_TRY(zk_quotient_plan(ctx, pk->dom, pk->nc));
+  pk->ext = (size_t)pk->nc * pk->n;
+  amdzk_domain_constant(pk->dom, 0, (uint64_t*)pk->omega.l);
+  amdzk_domain_constant(pk->dom, 1, (uint64_t*)pk->omega_inv.l);
+  for (uint32_t i = 0; i < c->num_advice_queries; i++) pk->advice_queries.push_back({c->advice_queries[2 * i], c->advice_queries[2 * i + 1]});
+  for (uint32_t i = 0; i < c->num_fixed_queries; i++) pk->fixed_queries.push_back({c->fixed_queries[2 * i], c->fixed_queries[2 * i + 1]});
+  for (uint32_t i = 0; i < c->num_instance_queries; i++)
+    pk->instance_queries.push_back({c->instance_queries[2 * i], c->instance_queries[2 * i + 1]});
+  for (uint32_t i = 0; i < pk->S; i++) pk->perm_cols.push_back({(int)c->perm_columns[2 * i], (int)c->perm_columns[2 * i + 1]});
+  pk->num_gates = c->num_gates;
+  uint32_t nexpr = c->num_gates;
+  for (uint32_t l = 0; l < pk->L; l++) {
+    pk->lookup_shape.push_back({c->lookup_shape[2 * l], c->lookup_shape[2 * l + 1]});
+    nexpr += c->lookup_shape[2 * l] + c->lookup_shape[2 * l + 1];
+  }
+  if (nexpr != c->num_exprs) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: expression count mismatch (%u vs %u)", nexpr, c->num_exprs);
+  for (uint32_t e = 0; e < c->num_exprs; e++)
+    pk->exprs.emplace_back(c->expr_words + c->expr_offsets[e], c->expr_words + c->expr_offsets[e + 1]);
+  {
+    auto desc = std::make_shared<pkblob::Desc>();
+    desc->assign(*c, ph);
+    pk->src_desc = desc;
+  }
+  // constants: circuit | one theta beta gamma y 1/beta
+  pk->consts.resize(c->num_constants);
+  if (c->num_constants) memcpy(pk->consts.data(), c->constants, (size_t)c->num_constants * 32);
+  pk->c_one = c->num_constants;
+  pk->c_theta = pk->c_one + 1;
+  pk->c_beta = pk->c_one + 2;
+  pk->c_gamma = pk->c_one + 3;
+  pk->c_y = pk->c_one + 4;
+  pk->c_betainv = pk->c_one + 5;
+  pk->c_chal0 = pk->c_betainv + 1;
+  pk->consts.resize((size_t)pk->c_chal0 + pk->num_challenges, Fr::zero());
+  pk->consts[pk->c_one] = Fr::one();
+  return AMDZK_OK;
+}
+
+// The key material's device buffers — fixed and permutation columns in their three forms, the domain columns — and the
+// key's own per-proof workspace.
+static int alloc_key_material(amdzk_ctx* ctx, amdzk_pk* pk) {
+  const size_t n = pk->n, ext = pk->ext;
+  const uint32_t F = pk->F, S = pk->S;
+  ZK_TRY(dalloc(ctx, pk, &pk->fixed_lag, (size_t)F * n));
+  ZK_TRY(dalloc(ctx, pk, &pk->fixed_poly, (size_t)F * n));
+  ZK_TRY(dalloc(ctx, pk, &pk->fixed_coset, (size_t)F * ext));
+  ZK_TRY(dalloc(ctx, pk, &pk->sigma_lag, (size_t)S * n));
+  ZK_TRY(dalloc(ctx, pk, &pk->sigma_poly, (size_t)S * n));
+  ZK_TRY(dalloc(ctx, pk, &pk->sigma_coset, (size_t)S * ext));
+  ZK_TRY(dalloc(ctx, pk, &pk->l0_c, ext));
+  ZK_TRY(dalloc(ctx, pk, &pk->llast_c, ext));
+  ZK_TRY(dalloc(ctx, pk, &pk->lactive_c, ext));
+  ZK_TRY(dalloc(ctx, pk, &pk->x_coset, ext));
+  ZK_TRY(dalloc(ctx, pk, &pk->omega_pow, n));
+  ZK_TRY(dalloc(ctx, pk, &pk->dxw_lag, (size_t)S * n));
+  ZK_TRY(dalloc(ctx, pk, &pk->dx_coset, (size_t)S * ext));
+  return alloc_proof_workspace(ctx, pk);
+}
+
+// The columns that depend on the domain alone: omega powers; l_0, l_last and l_blind on the cosets (l_blind in lactive_c,
+// until finish_l_active); the cosets' points; the identity permutation.
+static int build_domain_columns(amdzk_ctx* ctx, amdzk_pk* pk) {
+  const size_t n = pk->n, ext = pk->ext;
+  std::vector<Fr> op(n), l0(n, Fr::zero()), ll(n, Fr::zero()), lb(n, Fr::zero()), xc(ext);
+  // the copies below read these vectors asynchronously: a step that fails between a copy and its wait still leaves the
+  // stream idle before they go away
+  struct IdleOnExit {
+    amdzk_ctx* ctx;
+    ~IdleOnExit() { (void)zk_host_wait(ctx, ctx->stream); }
+  } idle{ctx};
+  Fr cur = Fr::one();
+  for (size_t i = 0; i < n; i++) {
+    op[i] = cur;
+    cur = mul(cur, pk->omega);
+  }
+  ZK_TRY(h2d(ctx, pk->omega_pow, op.data(), n * 32));
+  l0[0] = Fr::one();
+  ll[n - pk->bf - 1] = Fr::one();
+  for (size_t i = n - pk->bf; i < n; i++) lb[i] = Fr::one();
+  // to cosets via the same device path as every other polynomial, one column at a time through pk->scratch
+  Fr* tmp = pk->scratch;
+  Fr* dst[3] = {pk->l0_c, pk->llast_c, pk->lactive_c};
+  std::vector<Fr>* src[3] = {&l0, &ll, &lb};
+  for (int t = 0; t < 3; t++) {
+    ZK_TRY(h2d(ctx, tmp, src[t]->data(), n * 32));
+    ZK_TRY(amdzk_lagrange_to_coeff_dev(ctx, pk->dom, tmp, 1, n));
+    ZK_TRY(zk_coeff_to_cosets_r261(ctx, pk->dom, tmp, n, dst[t], ext, 1));
+    ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
+  }
+  for (uint32_t c = 0; c < pk->nc; c++) {
+    cur = zk_quotient_coset_g(pk->dom, c);
+    for (int i = 0; i < 5; i++) cur = add(cur, cur);  // 32 * g_c * omega^i: the points of coset c in radix 2^261
+    for (size_t i = 0; i < n; i++) {
+      xc[(size_t)c * n + i] = cur;
+      cur = mul(cur, pk->omega);
+    }
+  }
+  ZK_TRY(h2d(ctx, pk->x_coset, xc.data(), ext * 32));
+  ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
+  // the identity permutation: delta^j * omega^i (Lagrange) and delta^j * X on the cosets (same radix as x_coset)
+  Fr dj = Fr::one();
+  const Fr delta = fr_delta();
+  for (uint32_t j = 0; j < pk->S; j++) {
+    ZK_TRY(d2d(ctx, pk->dxw_lag + (size_t)j * n, pk->omega_pow, n * 32));
+    ZK_TRY(d2d(ctx, pk->dx_coset + (size_t)j * ext, pk->x_coset, ext * 32));
+    if (j) {
+      ZK_TRY(zk_scale(ctx, pk->dxw_lag + (size_t)j * n, n, dj));
+      ZK_TRY(zk_scale(ctx, pk->dx_coset + (size_t)j * ext, ext, dj));
+    }
+    dj = mul(dj, delta);
+  }
+  ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
+  return AMDZK_OK;
+}
+
+// The fixed columns: Lagrange values as given, coefficients, cosets, commitments.
+static int load_fixed_columns(amdzk_ctx* ctx, amdzk_pk* pk, const void* fixed_values) {
+  const size_t n = pk->n;
+  const uint32_t F = pk->F;
+  if (!F) return AMDZK_OK;
+  if (!fixed_values) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: fixed_values is null");
+  ZK_TRY(h2d(ctx, pk->fixed_lag, fixed_values, (size_t)F * n * 32));
+  ZK_TRY(d2d(ctx, pk->fixed_poly, pk->fixed_lag, (size_t)F * n * 32));
+  ZK_TRY(amdzk_lagrange_to_coeff_dev(ctx, pk->dom, pk->fixed_poly, F, n));
+  ZK_TRY(zk_coeff_to_cosets_r261(ctx, pk->dom, pk->fixed_poly, n, pk->fixed_coset, pk->ext, F));
+  return commit_cols(ctx, pk, AMDZK_BASIS_G_LAGRANGE, pk->fixed_lag, F, pk->fixed_commitments);
+}
+
+// The permutation columns: their Lagrange values from the mapping or as given, then what both routes share.
+static int load_sigma_columns(amdzk_ctx* ctx, amdzk_pk* pk, const uint32_t* perm_mapping, const void* sigma_values, bool from_sigma) {
+  const size_t n = pk->n;
+  const uint32_t S = pk->S;
+  if (!S) return AMDZK_OK;
+  if (from_sigma) {
+    if (!sigma_values) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: sigma_values is null");
+    ZK_TRY(h2d(ctx, pk->sigma_lag, sigma_values, (size_t)S * n * 32));
+    ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
+  } else {
+    if (!perm_mapping) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: perm_mapping is null");
+    // sigma_i(omega^j) = delta^(i') * omega^(j'), (i', j') = mapping[i][j]
+    std::vector<Fr> dpow(S), op(n), sig((size_t)S * n);
+    Fr delta = fr_delta(), cur = Fr::one();
+    for (uint32_t i = 0; i < S; i++) {
+      dpow[i] = cur;
+      cur = mul(cur, delta);
+    }
+    cur = Fr::one();
+    for (size_t i = 0; i < n; i++) {
+      op[i] = cur;
+      cur = mul(cur, pk->omega);
+    }
+    for (uint32_t i = 0; i < S; i++)
+      for (size_t j = 0; j < n; j++) {
+        uint32_t pi = perm_mapping[2 * ((size_t)i * n + j)], pj = perm_mapping[2 * ((size_t)i * n + j) + 1];
+        if (pi >= S || pj >= n) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: permutation mapping out of range");
+        sig[(size_t)i * n + j] = mul(dpow[pi], op[pj]);
+      }
+    ZK_TRY(h2d(ctx, pk->sigma_lag, sig.data(), (size_t)S * n * 32));
+    ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
+  }
+  ZK_TRY(d2d(ctx, pk->sigma_poly, pk->sigma_lag, (size_t)S * n * 32));
+  ZK_TRY(amdzk_lagrange_to_coeff_dev(ctx, pk->dom, pk->sigma_poly, S, n));
+  ZK_TRY(zk_coeff_to_cosets_r261(ctx, pk->dom, pk->sigma_poly, n, pk->sigma_coset, pk->ext, S));
+  return commit_cols(ctx, pk, AMDZK_BASIS_G_LAGRANGE, pk->sigma_lag, S, pk->perm_commitments);
+}
+
+// ---- the four programs of a key. A column operand is slot << 8 | index into the key's rotation table; fixed, advice and
+// instance columns have the same slot in the Lagrange and in the extended table.
+static uint32_t COL(uint32_t slot, uint32_t r) { return (slot << 8) | r; }
+static uint32_t perm_col_slot(amdzk_pk* pk, uint32_t j) {
+  const std::pair<int, int> kc = pk->perm_cols[j];
+  return kc.first == 0 ? pk->sl_adv(kc.second) : kc.first == 1 ? pk->sl_fixed(kc.second) : pk->sl_inst(kc.second);
+}
+// w_j = (v_j + gamma) / beta of the permutation columns lo <= j < hi, one after the other onto the stack
+static void emit_perm_w(amdzk_pk* pk, Program& pr, uint32_t lo, uint32_t hi) {
+  for (uint32_t j = lo; j < hi; j++) {
+    pr.op(OP_PUSH_COL, COL(perm_col_slot(pk, j), pk->rots.index(0)));
+    pr.push();
+    pr.op(OP_ADD_CONST, pk->c_gamma);
+    pr.op(OP_MUL_CONST, pk->c_betainv);
+  }
+}
+
+// (1) lookup compression: ci[l], ct[l]. Leading lookups whose table is one expression over fixed columns and constants
+// (amdzk_pk::lk_const) get ct[l] once, in build_constant_tables.
+static int emit_compress_program(amdzk_ctx* ctx, amdzk_pk* pk) {
+  Program& pr = pk->prog_compress;
+  const uint32_t L = pk->L;
+  uint32_t e = pk->num_gates;
+  for (uint32_t l = 0; l < L && !getenv("AMDZK_NO_TABLE_CACHE"); l++) {
+    const uint32_t ni = pk->lookup_shape[l].first, nt = pk->lookup_shape[l].second;
+    bool constant = nt == 1;
+    if (constant)
+      for (uint32_t w : pk->exprs[e + ni]) constant = constant && (w >> 24) != XOP_ADVICE && (w >> 24) != XOP_INSTANCE && (w >> 24) != XOP_CHALLENGE;
+    if (!constant) break;
+    pk->lk_const++;
+    e += ni + nt;
+  }
+  e = pk->num_gates;
+  for (uint32_t l = 0; l < L; l++) {
+    pr.piece();
+    ZK_TRY(emit_compressed(ctx, pk, pr, e, pk->lookup_shape[l].first));
+    pr.op(OP_STORE, 2 * l);
+    pr.pop();
+    e += pk->lookup_shape[l].first;
+    if (l >= pk->lk_const) {
+      ZK_TRY(emit_compressed(ctx, pk, pr, e, pk->lookup_shape[l].second));
+      pr.op(OP_STORE, 2 * l + 1);
+      pr.pop();
+    }
+    e += pk->lookup_shape[l].second;
+  }
+  return AMDZK_OK;
+}
+
+// (2) permutation fractions: den[s] -> frac column s (inverted later), num[s] -> zp column s. Per set: the columns'
+// w_j = (v_j + gamma) / beta stay on the stack and serve both products, prod_j (sigma_j + w_j) and
+// prod_j (delta^j omega^row + w_j); the common factor beta^m of numerator and denominator cancels in num / den.
+static void emit_pfrac_program(amdzk_pk* pk) {
+  Program& pr = pk->prog_pfrac;
+  const uint32_t r0 = pk->rots.index(0);
+  for (uint32_t s = 0; s < pk->nsets; s++) {
+    const uint32_t lo = s * pk->chunk, hi = std::min(pk->S, lo + pk->chunk), m = hi - lo;
+    pr.piece();
+    emit_perm_w(pk, pr, lo, hi);
+    for (int side = 0; side < 2; side++) {  // 0: denominator (sigma columns), 1: numerator (identity-permutation columns)
+      for (uint32_t j = lo; j < hi; j++) {
+        // the stack holds the m values w, then (from the second factor on) the running product
+        pr.op(OP_PICK, j == lo ? m - 1 : m - (j - lo));
+        pr.push();
+        pr.op(OP_ADD_COL, COL(side == 0 ? pk->sl_sigma(j) : pk->sl_dxw(j), r0));
+        if (j > lo) {
+          pr.op(OP_MUL);
+          pr.pop();
+        }
+      }
+      if (side == 1) {
+        pr.op(OP_NIP, m);
+        pr.cur -= m;
+      }
+      pr.op(OP_STORE, 2 * s + side);
+      pr.pop();
+    }
+  }
+}
+
+// (3) lookup fractions: den = (a'+beta)(s'+gamma) -> frac2[l]; num = (ci+beta)(ct+gamma) -> zl[l]
+static void emit_lfrac_program(amdzk_pk* pk) {
+  Program& pr = pk->prog_lfrac;
+  const uint32_t r0 = pk->rots.index(0);
+  for (uint32_t l = 0; l < pk->L; l++) {
+    pr.piece();
+    pr.op(OP_PUSH_COL, COL(pk->sl_la(l), r0));
+    pr.push();
+    pr.op(OP_ADD_CONST, pk->c_beta);
+    pr.op(OP_PUSH_COL, COL(pk->sl_ls(l), r0));
+    pr.push();
+    pr.op(OP_ADD_CONST, pk->c_gamma);
+    pr.op(OP_MUL);
+    pr.pop();
+    pr.op(OP_STORE, 2 * l);
+    pr.pop();
+    pr.op(OP_PUSH_COL, COL(pk->sl_ci(l), r0));
+    pr.push();
+    pr.op(OP_ADD_CONST, pk->c_beta);
+    pr.op(OP_PUSH_COL, COL(pk->sl_ct(l), r0));
+    pr.push();
+    pr.op(OP_ADD_CONST, pk->c_gamma);
+    pr.op(OP_MUL);
+    pr.pop();
+    pr.op(OP_STORE, 2 * l + 1);
+    pr.pop();
+  }
+}
+
+// (4) the h(X) numerator: gates, permutation, lookups — evaluation.rs evaluate_h order — then the pass that readies it
+// for the limb-resident interpreter and cuts it into pieces.
+static int emit_h_program(amdzk_ctx* ctx, amdzk_pk* pk) {
+  Program& pr = pk->prog_h;
+  const uint32_t S = pk->S, L = pk->L, ns = pk->nsets;
+  const uint32_t r0 = pk->rots.index(0), r1 = pk->rots.index(1), rm1 = pk->rots.index(-1), rlast = pk->rots.index(-(int32_t)(pk->bf + 1));
+  pr.uses_hot = true;
+  for (uint32_t g = 0; g < pk->num_gates; g++) {
+    ZK_TRY(emit_expr(ctx, pk, pr, pk->exprs[g]));
+    pr.op(OP_ACC);
+    pr.pop();
+  }
+  if (ns > 0) {
+    // l_0 * (1 - z_0)
+    pr.op(OP_PUSH_CONST, pk->c_one); pr.push();
+    pr.op(OP_SUB_COL, COL(pk->se_zp(0), r0));
+    pr.op(OP_MUL_HOT, 0);
+    pr.op(OP_ACC); pr.pop();
+    // l_last * (z_l^2 - z_l)
+    pr.op(OP_PUSH_COL, COL(pk->se_zp(ns - 1), r0)); pr.push();
+    pr.op(OP_SQR);
+    pr.op(OP_SUB_COL, COL(pk->se_zp(ns - 1), r0));
+    pr.op(OP_MUL_HOT, 1);
+    pr.op(OP_ACC); pr.pop();
+    // l_0 * (z_i - z_{i-1}(omega^last X))
+    for (uint32_t s = 1; s < ns; s++) {
+      pr.op(OP_PUSH_COL, COL(pk->se_zp(s), r0)); pr.push();
+      pr.op(OP_SUB_COL, COL(pk->se_zp(s - 1), rlast));
+      pr.op(OP_MUL_HOT, 0);
+      pr.op(OP_ACC); pr.pop();
+    }
+    // l_active * (z_i(omega X) prod(v + beta sigma + gamma) - z_i(X) prod(v + beta delta^j X + gamma))
+    //   = beta^m * l_active * (z_i(omega X) prod(sigma_j + w_j) - z_i(X) prod(delta^j X + w_j)),  w_j = (v_j + gamma) / beta:
+    // the w_j stay on the stack for both products (one product per column instead of two), delta^j X is a key column,
+    // and beta^m goes into the term's power of y (h_term_beta_pow, upload_ypow)
+    for (uint32_t s = 0; s < ns; s++) {
+      const uint32_t lo = s * pk->chunk, hi = std::min(S, lo + pk->chunk), m = hi - lo;
+      emit_perm_w(pk, pr, lo, hi);
+      pr.op(OP_PUSH_COL, COL(pk->se_zp(s), r1)); pr.push();
+      for (uint32_t j = lo; j < hi; j++) {
+        pr.op(OP_PICK, m - (j - lo)); pr.push();
+        pr.op(OP_ADD_COL, COL(pk->se_sigma(j), r0));
+        pr.op(OP_MUL); pr.pop();
+      }
+      pr.op(OP_PUSH_COL, COL(pk->se_zp(s), r0)); pr.push();
+      for (uint32_t j = lo; j < hi; j++) {
+        pr.op(OP_PICK, 1 + m - (j - lo)); pr.push();
+        pr.op(OP_ADD_COL, COL(pk->se_dx(j), r0));
+        pr.op(OP_MUL); pr.pop();
+      }
+      pr.op(OP_SUB); pr.pop();
+      pr.op(OP_NIP, m); pr.cur -= m;
+      pr.op(OP_MUL_HOT, 2);
+      pr.next_beta = m;
+      pr.op(OP_ACC); pr.pop();
+    }
+  }
+  uint32_t e = pk->num_gates;
+  for (uint32_t l = 0; l < L; l++) {
+    const uint32_t ni = pk->lookup_shape[l].first, nt = pk->lookup_shape[l].second;
+    // l_0 * (1 - z)
+    pr.op(OP_PUSH_CONST, pk->c_one); pr.push();
+    pr.op(OP_SUB_COL, COL(pk->se_zl(l), r0));
+    pr.op(OP_MUL_HOT, 0);
+    pr.op(OP_ACC); pr.pop();
+    // l_last * (z^2 - z)
+    pr.op(OP_PUSH_COL, COL(pk->se_zl(l), r0)); pr.push();
+    pr.op(OP_SQR);
+    pr.op(OP_SUB_COL, COL(pk->se_zl(l), r0));
+    pr.op(OP_MUL_HOT, 1);
+    pr.op(OP_ACC); pr.pop();
+    // l_active * (z(wX)(a'+beta)(s'+gamma) - z(X)(ci+beta)(ct+gamma))
+    pr.op(OP_PUSH_COL, COL(pk->se_zl(l), r1)); pr.push();
+    pr.op(OP_PUSH_COL, COL(pk->se_la(l), r0)); pr.push();
+    pr.op(OP_ADD_CONST, pk->c_beta);
+    pr.op(OP_MUL); pr.pop();
+    pr.op(OP_PUSH_COL, COL(pk->se_ls(l), r0)); pr.push();
+    pr.op(OP_ADD_CONST, pk->c_gamma);
+    pr.op(OP_MUL); pr.pop();
+    pr.op(OP_PUSH_COL, COL(pk->se_zl(l), r0)); pr.push();
+    ZK_TRY(emit_compressed(ctx, pk, pr, e, ni));
+    pr.op(OP_ADD_CONST, pk->c_beta);
+    pr.op(OP_MUL); pr.pop();
+    ZK_TRY(emit_compressed(ctx, pk, pr, e + ni, nt));
+    pr.op(OP_ADD_CONST, pk->c_gamma);
+    pr.op(OP_MUL); pr.pop();
+    pr.op(OP_SUB); pr.pop();
+    pr.op(OP_MUL_HOT, 2);
+    pr.op(OP_ACC); pr.pop();
+    // l_0 * (a' - s')
+    pr.op(OP_PUSH_COL, COL(pk->se_la(l), r0)); pr.push();
+    pr.op(OP_SUB_COL, COL(pk->se_ls(l), r0));
+    pr.op(OP_MUL_HOT, 0);
+    pr.op(OP_ACC); pr.pop();
+    // l_active * (a' - s')(a' - a'(w^-1 X))
+    pr.op(OP_PUSH_COL, COL(pk->se_la(l), r0)); pr.push();
+    pr.op(OP_SUB_COL, COL(pk->se_ls(l), r0));
+    pr.op(OP_PUSH_COL, COL(pk->se_la(l), r0)); pr.push();
+    pr.op(OP_SUB_COL, COL(pk->se_la(l), rm1));
+    pr.op(OP_MUL); pr.pop();
+    pr.op(OP_MUL_HOT, 2);
+    pr.op(OP_ACC); pr.pop();
+    e += ni + nt;
+  }
+  // pieces of the h(X) program: 6 by default. One piece is 1.5 wavefronts per SIMD at k = 15 (3 cosets x 2^15 rows) and
+  // the interpreter alone took 2.30 ms of a lone proof's critical path; 8 pieces 1.70 ms. Latency of one proof, median
+  // of 15, two runs each on one box: 1 piece 18.34 / 18.39 ms, 4: 17.71 / 17.86, 6: 17.61 / 17.78, 8: 17.63 / 17.46;
+  // 10 proofs in flight: 78.0 / 76.7, 77.8 / 78.3, 78.2 / 78.5, 78.0 / 77.6 proofs/s (no difference).
+  // AMDZK_H_PARTS=1..8 for experiments.
+  const char* env = getenv("AMDZK_H_PARTS");
+  uint32_t parts = env ? (uint32_t)atoi(env) : 6u;
+  parts = parts < 1 ? 1 : parts > H_PARTS_MAX ? H_PARTS_MAX : parts;
+  pk->h_terms = finalize_limb_program(pr, parts);
+  pk->h_term_beta_pow = pr.term_beta;
+  return AMDZK_OK;
+}
+
+// AMDZK_DUMP_PROG, a debugging aid: what the compiled h(X) program is made of
+static void dump_h_program(const amdzk_pk* pk) {
+  static const char* names[] = {"END", "PUSH_COL", "PUSH_CONST", "ADD", "SUB", "MUL", "NEG", "MUL_CONST", "ADD_CONST", "MUL_COL",
+                                "ADD_COL", "SUB_COL", "ACC", "STORE", "SQR", "PUSH_HOT", "MUL_HOT", "REDUCE", "SUB_BIG", "NEG_BIG",
+                                "WACC", "WFLUSH"};
+  std::map<uint32_t, size_t> hist;
+  std::map<std::pair<uint32_t, uint32_t>, size_t> pairs;
+  const auto& w = pk->prog_h.words;
+  for (size_t i = 0; i < w.size(); i++) {
+    hist[w[i] >> 24]++;
+    if (i + 1 < w.size()) pairs[{w[i] >> 24, w[i + 1] >> 24}]++;
+  }
+  fprintf(stderr, "[amdzk] prog_h: %zu instructions, stack depth %u\n", w.size(), pk->prog_h.depth);
+  for (auto& kv : hist) fprintf(stderr, "[amdzk]   %-10s %zu\n", kv.first < 22 ? names[kv.first] : "?", kv.second);
+  auto is_mul = [](uint32_t o) { return o == OP_MUL || o == OP_MUL_CONST || o == OP_MUL_COL || o == OP_MUL_HOT || o == OP_SQR || o == OP_WACC; };
+  size_t mm = 0;
+  for (auto& kv : pairs)
+    if (is_mul(kv.first.first) && is_mul(kv.first.second)) {
+      mm += kv.second;
+      fprintf(stderr, "[amdzk]   product -> product: %s -> %s x %zu\n", names[kv.first.first], names[kv.first.second], kv.second);
+    }
+  fprintf(stderr, "[amdzk]   products directly followed by a product: %zu\n", mm);
+}
+
+// Constant tables (amdzk_pk::lk_const): ct[l] evaluated here, once, and its canonical, padded, sorted form kept
+static int build_constant_tables(amdzk_ctx* ctx, amdzk_pk* pk) {
+  if (!pk->lk_const) return AMDZK_OK;
+  const size_t n = pk->n;
+  const uint32_t cnt = pk->lk_const, usable = (uint32_t)n - (pk->bf + 1);
+  ZK_TRY(dalloc(ctx, pk, &pk->lk_ts_const, (size_t)cnt * n));
+  Program pr;
+  uint32_t e = pk->num_gates;
+  for (uint32_t l = 0; l < cnt; l++) {
+    pr.piece();
+    ZK_TRY(emit_expr(ctx, pk, pr, pk->exprs[e + pk->lookup_shape[l].first]));
+    pr.op(OP_STORE, 2 * l + 1);
+    pr.pop();
+    e += pk->lookup_shape[l].first + 1;
+  }
+  ZK_TRY(upload_program(ctx, pk, pr, false));
+  ZK_TRY(run_program(ctx, pk, pr, false, pk->d_outs_compress, nullptr, "expr_const_tables"));
+  ZK_TRY(d2d(ctx, pk->lk_ts_const, pk->ct, (size_t)cnt * n * 32));
+  ZK_TRY(amdzk_fr_to_repr_dev(ctx, pk->lk_ts_const, (size_t)cnt * n));
+  ZK_HIP(ctx, hipMemset2DAsync(pk->lk_ts_const + usable, (size_t)n * 32, 0xFF, (size_t)(n - usable) * 32, cnt, ctx->stream));
+  ZK_TRY(zk_sort_keys(ctx, pk->lk_ts_const, cnt, n, n));
+  ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
+  return AMDZK_OK;
+}
+
+// l_active = 1 - (l_last + l_blind) on the cosets: lactive_c holds l_blind's coset (build_domain_columns); a tiny one-off
+// program over the extended table, whose constants bind_workspace has uploaded
+static int finish_l_active(amdzk_ctx* ctx, amdzk_pk* pk) {
+  const uint32_t r0 = pk->rots.index(0);
+  ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
+  Program pr;
+  pr.op(OP_PUSH_CONST, pk->c_one); pr.push();
+  pr.op(OP_SUB_COL, COL(pk->se_llast(), r0));
+  pr.op(OP_SUB_COL, COL(pk->se_lactive(), r0));
+  pr.op(OP_STORE, 0); pr.pop();
+  (void)finalize_limb_program(pr);
+  ZK_TRY(upload_program(ctx, pk, pr, true));
+  Fr** d_out = nullptr;
+  ZK_TRY(dalloc(ctx, pk, &d_out, 1));
+  Fr* tgt = pk->lactive_c;
+  ZK_TRY(h2d(ctx, d_out, &tgt, sizeof(Fr*)));
+  ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
+  ZK_TRY(run_program(ctx, pk, pr, true, d_out, nullptr, "expr_l_active"));
+  ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
+  return AMDZK_OK;
+}
+
+// keygen with ConstraintSystem::{advice_column_in, challenge_usable_after}'s phase table (NULL: every column in phase 0,
+// no challenges). One of perm_mapping (Assembly::mapping: the sigma values are computed here) and sigma_values (the
+// Lagrange values themselves, amdzk_keygen_sigma / amdzk_pk_read) feeds the permutation columns; everything behind their
+// upload is shared. fixed_values / sigma_values are only copied to the device: any alignment (amdzk_pk_read passes
+// pointers into the file). The key belongs to `owner` until it is handed to *out: every refusal and every failed call
+// on the way frees it.
+static int keygen_common(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* c, const amdzk_phases* ph, const void* fixed_values,
+                         const uint32_t* perm_mapping, const void* sigma_values, bool from_sigma, const uint64_t transcript_repr[4],
+                         uint32_t flags, amdzk_pk** out) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  uint32_t nphases = 1;
+  ZK_TRY(check_keygen_args(ctx, srs, c, ph, transcript_repr, flags, out, &nphases));
+  PkOwner owner(new amdzk_pk(), PkFree{ctx});
+  amdzk_pk* pk = owner.get();
+  ZK_TRY(describe_circuit(ctx, pk, srs, c, ph, nphases, transcript_repr, flags));
+  ZK_TRY(alloc_key_material(ctx, pk));
+  ZK_TRY(build_domain_columns(ctx, pk));
+  ZK_TRY(load_fixed_columns(ctx, pk, fixed_values));
+  ZK_TRY(load_sigma_columns(ctx, pk, perm_mapping, sigma_values, from_sigma));
+  // rotations 0, 1, -1 and -(bf + 1) open the rotation table of every key, ahead of what its expressions query
+  for (int32_t r : {0, 1, -1, -(int32_t)(pk->bf + 1)}) pk->rots.index(r);
+  ZK_TRY(emit_compress_program(ctx, pk));
+  emit_pfrac_program(pk);
+  emit_lfrac_program(pk);
+  ZK_TRY(emit_h_program(ctx, pk));
+  if (pk->rots.rots.size() > 255) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "keygen: more than 255 distinct rotations");
+  ZK_TRY(bind_workspace(ctx, pk));
+  if (getenv("AMDZK_DUMP_PROG")) dump_h_program(pk);
+  ZK_TRY(build_constant_tables(ctx, pk));
+  ZK_TRY(finish_l_active(ctx, pk));
+  *out = owner.release();
+  return AMDZK_OK;
+}
+
+extern "C" {
+
+void amdzk_pk_free(amdzk_ctx* ctx, amdzk_pk* pk) {
+  ZK_ENTER(ctx);
+  if (!pk) return;
+  if (ctx) zk_host_wait(ctx, ctx->stream);
+  for (void* p : pk->allocs) hipFree(p);
+  if (!pk->clone_of && pk->chk_shared && pk->chk_shared->d_cells) hipFree(pk->chk_shared->d_cells);
+  if (pk->pin) hipHostFree(pk->pin);
+  if (pk->dom && !pk->clone_of) amdzk_domain_free(ctx, pk->dom);
+  delete pk;
+}
+
+// Every device allocation of the key (columns, cosets, per-proof workspace) must live on ctx's device.
+int amdzk_pk_check_affinity(amdzk_ctx* ctx, const amdzk_pk* pk) {
+  ZK_ENTER(ctx);
+  if (!ctx || !pk) return AMDZK_E_INVALID;
+  for (void* p : pk->allocs) ZK_TRY(zk_ptr_on_device(ctx, p, "proving-key buffer"));
+  return AMDZK_OK;
+}
+
+// keygen with the environment's defaults for the key's modes (AMDZK_FULL_COSETS, AMDZK_SERIAL); amdzk_keygen_ex takes
+// them as explicit flags, so that two keys of one process can differ.
+int amdzk_keygen(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* c, const uint64_t* fixed_values, const uint32_t* perm_mapping,
+                 const uint64_t transcript_repr[4], amdzk_pk** out) {
+  uint32_t flags = 0;
+  if (const char* e = getenv("AMDZK_FULL_COSETS")) flags |= atoi(e) != 0 || !*e ? AMDZK_KEYGEN_FULL_COSETS : 0u;
+  if (const char* e = getenv("AMDZK_SERIAL")) flags |= atoi(e) != 0 ? AMDZK_KEYGEN_SERIAL : 0u;
+  return amdzk_keygen_ex(ctx, srs, c, fixed_values, perm_mapping, transcript_repr, flags, out);
+}
+
+int amdzk_keygen_ex(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* c, const uint64_t* fixed_values, const uint32_t* perm_mapping,
+                    const uint64_t transcript_repr[4], uint32_t flags, amdzk_pk** out) {
+  return amdzk_keygen_phased(ctx, srs, c, nullptr, fixed_values, perm_mapping, transcript_repr, flags, out);
+}
+
+int amdzk_keygen_phased(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* c, const amdzk_phases* ph, const uint64_t* fixed_values,
+                        const uint32_t* perm_mapping, const uint64_t transcript_repr[4], uint32_t flags, amdzk_pk** out) {
+  return keygen_common(ctx, srs, c, ph, fixed_values, perm_mapping, nullptr, false, transcript_repr, flags, out);
+}
+
+// keygen from the sigma columns (permutation::ProvingKey::permutations, Lagrange form) instead of the mapping: what a
+// process that has read a cached key holds. The values are taken as they are (upstream's read does not check them either).
+int amdzk_keygen_sigma(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* c, const amdzk_phases* ph, const uint64_t* fixed_values,
+                       const uint64_t* sigma_values, const uint64_t transcript_repr[4], uint32_t flags, amdzk_pk** out) {
+  return keygen_common(ctx, srs, c, ph, fixed_values, nullptr, sigma_values, true, transcript_repr, flags, out);
+}
+
+// VK material a verifier needs: commitments of the fixed columns and of the permutation polynomials.
+int amdzk_pk_commitments(const amdzk_pk* pk, uint64_t* fixed_out /* F x 8 */, uint64_t* perm_out /* S x 8 */) {
+  if (!pk) return AMDZK_E_INVALID;
+  if (fixed_out && pk->F) memcpy(fixed_out, pk->fixed_commitments.data(), (size_t)pk->F * 64);
+  if (perm_out && pk->S) memcpy(perm_out, pk->perm_commitments.data(), (size_t)pk->S * 64);
+  return AMDZK_OK;
+}
+
+// One more circuit instance's workspace for `src`'s circuit: a key handle that shares src's key material (fixed and
+// permutation columns in all three forms, the domain, the compiled programs' text, constant lookup tables — read-only
+// during proofs) and owns its own per-proof workspace, pointer tables and uploaded programs (their instructions carry
+// absolute column addresses). What amdzk_create_proof_multi takes for its second, third, ... instance — and, since a
+// clone is a complete key for create_proof, the cheap way to keep several proofs of one circuit in flight: a
+// clone costs the workspace (the arenas), not the key (354 + 354 MiB of permutation cosets at the metric's shape).
+// Free it with amdzk_pk_free BEFORE the key it was made from.
+int amdzk_pk_clone_workspace(amdzk_ctx* ctx, const amdzk_pk* src, amdzk_pk** out) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  if (!src || !out) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_clone_workspace: null argument");
+  PkOwner owner(new amdzk_pk(*src), PkFree{ctx});
+  amdzk_pk* pk = owner.get();
+  pk->clone_of = src->clone_of ? src->clone_of : src;
+  pk->allocs.clear();
+  pk->pin = nullptr;
+  pk->pin_cap = pk->pin_off = 0;
+  pk->mo = amdzk_pk::Multiopen();
+  pk->mo_multi = amdzk_pk::Multiopen();
+  pk->mo_multi_keys.clear();
+  pk->sets_Q = nullptr;
+  pk->sets_Q_pairs = 0;
+  pk->prog_compress.d_instr = pk->prog_pfrac.d_instr = pk->prog_lfrac.d_instr = pk->prog_h.d_instr = nullptr;
+  pk->chk = amdzk_pk::Check();  // built by the clone's own first check
+  ZK_TRY(alloc_proof_workspace(ctx, pk));
+  ZK_TRY(bind_workspace(ctx, pk));
+  // the compressed constant tables (amdzk_pk::lk_const) are written once, at keygen, into the key's ct columns — the
+  // per-proof compression program skips them — so a new workspace starts with a copy
+  if (pk->lk_const) ZK_TRY(d2d(ctx, pk->ct, src->ct, (size_t)pk->lk_const * pk->n * 32));
+  ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
+  *out = owner.release();
+  return AMDZK_OK;
+}
+
+// What the last create_proof on this key left in its workspace, for tests that check one stage at a time against the
+// oracle: what = 0 the NP committed polynomials in coefficient form ([NP][n], arena order as above); 1 the
+// challenges theta, beta, gamma, y; 2 the pieces of h(X) ([cs_degree - 1][n]); 3 the phase challenges. `out` holds cap Fr elements;
+// *count = elements available.
+int amdzk_pk_inspect(amdzk_ctx* ctx, const amdzk_pk* pk, int what, uint64_t* out, size_t cap, size_t* count) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  if (!pk || !count) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_inspect: null argument");
+  const Fr* src = nullptr;
+  size_t cnt = 0;
+  Fr ch[4];
+  if (what == 0) {
+    src = pk->PQ;
+    cnt = pk->NP * pk->n;
+  } else if (what == 2) {
+    src = pk->hpieces;
+    cnt = (size_t)pk->qdeg * pk->n;
+  } else if (what == 1) {
+    ch[0] = pk->consts[pk->c_theta];
+    ch[1] = pk->consts[pk->c_beta];
+    ch[2] = pk->consts[pk->c_gamma];
+    ch[3] = pk->consts[pk->c_y];
+    cnt = 4;
+  } else if (what == 3) {
+    cnt = pk->num_challenges;
+  } else {
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_inspect: unknown selector %d", what);
+  }
+  *count = cnt;
+  if (!out) return AMDZK_OK;
+  if (cap < cnt) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_inspect: buffer holds %zu elements, %zu needed", cap, cnt);
+  if (what == 1) memcpy(out, ch, sizeof(ch));
+  else if (what == 3) memcpy(out, pk->consts.data() + pk->c_chal0, cnt * 32);
+  else ZK_TRY(d2h(ctx, out, src, cnt * 32));
+  return AMDZK_OK;
+}
+
+// The key's own columns, for a fork whose ProvingKey::write stores a key that was made on the device: what = 0 the fixed
+// columns (Lagrange), 1 the sigma columns (Lagrange), 2 / 3 the same as coefficients. A workspace clone shares these
+// buffers with its root key, so it returns the root's columns.
+int amdzk_pk_export(amdzk_ctx* ctx, const amdzk_pk* pk, int what, uint64_t* out, size_t cap, size_t* count) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  if (!pk || !count) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_export: null argument");
+  if (what < 0 || what > 3) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_export: unknown selector %d", what);
+  const Fr* src[4] = {pk->fixed_lag, pk->sigma_lag, pk->fixed_poly, pk->sigma_poly};
+  const size_t cnt = (size_t)((what & 1) ? pk->S : pk->F) * pk->n;
+  *count = cnt;
+  if (!out) return AMDZK_OK;
+  if (cap < cnt) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_export: buffer holds %zu elements, %zu needed", cap, cnt);
+  return d2h(ctx, out, src[what], cnt * 32);
+}
+
+// ---- the key file (csrc/pkblob.hpp has the layout, the header's writer and the host-only parser)
+// keygen takes a circuit on trust where pkblob::validate() does not (a query that no expression uses may name any column,
+// for one): such a key proves, but its file would be refused by amdzk_pk_read, so it is not written at all.
+size_t amdzk_pk_serialized_size(const amdzk_pk* pk) {
+  return pk && pk->src_desc && pkblob::validate(*pk->src_desc, nullptr) == AMDZK_OK ? pk->src_desc->serialized_size() : 0;
+}
+
+int amdzk_pk_write(amdzk_ctx* ctx, const amdzk_pk* pk, uint8_t* out, size_t cap, size_t* written) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  if (!pk || !pk->src_desc || (!out && !written)) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_write: null argument");
+  const pkblob::Desc& d = *pk->src_desc;
+  std::string why;
+  if (pkblob::validate(d, &why) != AMDZK_OK)
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_write: amdzk_pk_read would refuse this key's circuit (%s)", why.c_str());
+  const size_t need = d.serialized_size();
+  if (written) *written = need;
+  if (!out) return AMDZK_OK;
+  if (cap < need) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_write: buffer holds %zu bytes, %zu needed", cap, need);
+  d.write_header(out);
+  uint8_t* p = out + d.header_bytes();
+  memcpy(p, pk->transcript_repr.l, 32);
+  p += 32;
+  if (pk->F) memcpy(p, pk->fixed_commitments.data(), (size_t)pk->F * 64);
+  p += (size_t)pk->F * 64;
+  if (pk->S) memcpy(p, pk->perm_commitments.data(), (size_t)pk->S * 64);
+  p += (size_t)pk->S * 64;
+  ZK_TRY(d2h(ctx, p, pk->fixed_lag, (size_t)pk->F * pk->n * 32));
+  p += (size_t)pk->F * pk->n * 32;
+  ZK_TRY(d2h(ctx, p, pk->sigma_lag, (size_t)pk->S * pk->n * 32));
+  p += (size_t)pk->S * pk->n * 32;
+  pkblob::digest(out, (size_t)(p - out), p);
+  return AMDZK_OK;
+}
+
+// Pure host code: every check amdzk_pk_read makes before it touches the device.
+int amdzk_pk_blob_info(const uint8_t* data, size_t len, uint32_t* k, uint32_t* num_fixed, uint32_t* num_advice, uint32_t* num_perm_columns,
+                       uint32_t* num_challenges) {
+  pkblob::Desc d;
+  if (int rc = pkblob::parse(data, len, &d, nullptr, nullptr)) return rc;
+  if (k) *k = d.k;
+  if (num_fixed) *num_fixed = d.num_fixed;
+  if (num_advice) *num_advice = d.num_advice;
+  if (num_perm_columns) *num_perm_columns = d.num_perm_columns();
+  if (num_challenges) *num_challenges = d.num_challenges;
+  return AMDZK_OK;
+}
+
+// amdzk_pk_blob_info's verdict with its reason: the message amdzk_pk_read would leave in the ctx ("pk_read: digest mismatch
+// ..."), for a host without a device. msg (may be NULL) receives at most msg_cap bytes, NUL-terminated; "" for a good file.
+int amdzk_pk_blob_check(const uint8_t* data, size_t len, char* msg, size_t msg_cap) {
+  pkblob::Desc d;
+  std::string err;
+  const int rc = pkblob::parse(data, len, &d, nullptr, &err);
+  if (msg && msg_cap) snprintf(msg, msg_cap, "%s", err.c_str());
+  return rc;
+}
+
+// The file's header and columns through the tail keygen shares (keygen_common), then the commitments it computed against
+// the stored ones: they differ exactly when the parameters are not the ones the key was made under.
+int amdzk_pk_read(amdzk_ctx* ctx, const amdzk_srs* srs, const uint8_t* data, size_t len, uint32_t flags, amdzk_pk** out) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  if (!srs || !data || !out) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_read: null argument");
+  pkblob::Desc d;
+  pkblob::Layout lay;
+  std::string err;
+  if (int rc = pkblob::parse(data, len, &d, &lay, &err)) {
+    ctx->err = err;
+    return rc;
+  }
+  if (d.k != zk_srs_k(srs)) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_read: the key is for k = %u, the parameters are for k = %u", d.k, zk_srs_k(srs));
+  amdzk_circuit c;
+  amdzk_phases ph;
+  d.view(&c, &ph);
+  uint64_t repr[4];
+  memcpy(repr, data + lay.transcript_repr, 32);
+  amdzk_pk* pk = nullptr;
+  const int rc = keygen_common(ctx, srs, &c, d.has_phases ? &ph : nullptr, data + lay.fixed_values, nullptr, data + lay.sigma_values, true, repr,
+                               flags, &pk);
+  if (rc != AMDZK_OK) {
+    if (rc == AMDZK_E_INVALID) ctx->err = "pk_read: " + ctx->err;
+    return rc;
+  }
+  const bool same = (!pk->F || memcmp(pk->fixed_commitments.data(), data + lay.fixed_commitments, (size_t)pk->F * 64) == 0) &&
+                    (!pk->S || memcmp(pk->perm_commitments.data(), data + lay.perm_commitments, (size_t)pk->S * 64) == 0);
+  if (!same) {
+    amdzk_pk_free(ctx, pk);
+    ZK_FAIL(ctx, AMDZK_E_INVALID,
+            "pk_read: the commitments in the file are not those of its columns under these parameters: the key was made under other "
+            "parameters (another SRS)");
+  }
+  *out = pk;
+  return AMDZK_OK;
+}
+
+}  // extern "C"

@@ -35,6 +35,7 @@
 #include "common.hpp"
 #include "fp29.cuh"
 #include "fp29_quad.cuh"
+#include "plonk_kernels.hpp"  // zk_batch_invert
 
 using namespace bn254;
 
@@ -1012,8 +1013,6 @@ __global__ void mul2_kernel(Fr* a, const Fr* w, Fr c, size_t n) {
   o[1] = make_uint4(r.l[4], r.l[5], r.l[6], r.l[7]);
 }
 }  // namespace
-
-int zk_batch_invert(amdzk_ctx* ctx, Fr* d_a, Fr* d_scratch, size_t total);
 
 // ---- ParamsKZG::{write, read} [UP]: k as u32 LE, then the n points of g and
 // of g_lagrange in halo2curves' 32-byte compressed form, then g2 and s_g2 (64 bytes each, passed

@@ -22,13 +22,6 @@
 
 using namespace bn254;
 
-struct amdzk_srs;
-uint32_t zk_srs_k(const amdzk_srs* srs);
-bool zk_srs_has_basis(const amdzk_srs* srs, int basis);
-int zk_msm_dev_xyzz(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const Fr* d_scalars, size_t ncols, size_t len, size_t col_stride,
-                    G1X** d_out);
-int zk_msm_finish(amdzk_ctx* ctx, const G1X* d_res, size_t ncols, uint64_t* out_jac);
-
 namespace {
 
 constexpr size_t MO_MAX_GRID_Y = 65535;  // polynomials per division launch, columns per commitment batch

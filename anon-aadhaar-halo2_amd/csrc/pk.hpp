@@ -1,0 +1,262 @@
+// The proving key as every host unit of the PLONK layer sees it (keygen.hip makes and frees it, program.hip compiles and
+// runs its programs, prover.hip proves with it, check.hip checks a witness against it): struct amdzk_pk, the programs it
+// holds, and the small helpers all of them use.
+#pragma once
+#include <memory>
+#include <mutex>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "pkblob.hpp"
+#include "plonk_kernels.hpp"
+
+using namespace bn254;  // (every unit that includes this header says so itself)
+
+// host-format expression words (include/amdzk.h)
+enum : uint32_t { XOP_CONST = 1, XOP_FIXED = 2, XOP_ADVICE = 3, XOP_INSTANCE = 4, XOP_NEG = 5, XOP_ADD = 6, XOP_MUL = 7, XOP_SCALE = 8, XOP_CHALLENGE = 9 };
+
+inline Fr fr_delta() {  // Fr::DELTA = 7^(2^28)  (contract.sol:440)
+  Fr r;
+  uint64_t v[4] = {0x870e56bbe533e9a2ULL, 0x5b5f898e5e963f25ULL, 0x64ec26aad4c86e71ULL, 0x09226b6e22c6f0caULL};
+  memcpy(r.l, v, 32);
+  return to_mont(r);
+}
+
+struct Program {
+  std::vector<uint32_t> words;
+  uint32_t depth = 0, cur = 0;
+  bool uses_hot = false;
+  ExprInstr* d_instr = nullptr;  // resolved instructions (device)
+  // Lagrange-domain programs: instruction indices at which an independent piece starts (the stack is empty there):
+  // run_program cuts the program there into up to EXPR_MAX_PARTS parts that run side by side (ExprArgs::nparts)
+  std::vector<uint32_t> piece_starts;
+  void piece() { piece_starts.push_back((uint32_t)words.size()); }
+  // h(X) programs: term j (closed by the j-th OP_ACC) carries the factor beta^term_beta[j] in its power of y
+  std::vector<uint32_t> term_beta;
+  uint32_t next_beta = 0;
+  void op(uint32_t o, uint32_t arg = 0) {
+    words.push_back((o << 24) | (arg & 0xffffffu));
+    if (o == OP_ACC) {
+      term_beta.push_back(next_beta);
+      next_beta = 0;
+    }
+  }
+  void push() {
+    cur++;
+    if (cur > depth) depth = cur;
+  }
+  void pop() { cur--; }
+};
+
+struct RotTable {
+  std::vector<int32_t> rots;
+  uint32_t index(int32_t r) {
+    for (size_t i = 0; i < rots.size(); i++)
+      if (rots[i] == r) return (uint32_t)i;
+    rots.push_back(r);
+    return (uint32_t)rots.size() - 1;
+  }
+};
+
+struct amdzk_pk {
+  uint32_t k = 0, ek = 0, bf = 0, degree = 0, F = 0, A = 0, I = 0, S = 0, L = 0, nsets = 0, chunk = 0, qdeg = 0;
+  uint32_t nc = 0;       // cosets of the quotient domain (poly.hip zk_quotient_plan): qdeg of the 2^(ek-k) upstream uses
+  size_t n = 0, ext = 0;  // ext = nc * n rows: every "extended" column holds [coset][row]
+  std::vector<std::pair<int, int>> advice_queries, fixed_queries, instance_queries;
+  std::vector<std::pair<int, int>> perm_cols;  // (kind, index)
+  std::vector<std::vector<uint32_t>> exprs;
+  uint32_t num_gates = 0;
+  std::vector<std::pair<uint32_t, uint32_t>> lookup_shape;  // (#inputs, #tables); expressions follow the gates in order
+  std::vector<Fr> consts;                                   // circuit constants, then the dynamic ones
+  uint32_t c_one = 0, c_theta = 0, c_beta = 0, c_gamma = 0, c_y = 0, c_betainv = 0;
+  // Challenge phases (amdzk_keygen_phased): challenge i lives in slot c_chal0 + i of the constant table, refreshed per
+  // proof like theta ... y; nothing made at keygen reads those slots. nphases = 1 and no challenges: a phase-0 key.
+  uint32_t num_challenges = 0, c_chal0 = 0, nphases = 1;
+  std::vector<uint8_t> advice_phase, challenge_phase;
+  bool phased() const { return nphases > 1 || num_challenges > 0; }
+  amdzk_domain* dom = nullptr;
+  const amdzk_srs* srs = nullptr;
+  Fr transcript_repr, omega, omega_inv;
+  std::vector<G1Affine> fixed_commitments, perm_commitments;
+  // What keygen was given, as the caller passed it (the flattened amdzk_circuit arrays and the phase table): the header of
+  // the key file (amdzk_pk_write). Shared with workspace clones.
+  std::shared_ptr<const pkblob::Desc> src_desc;
+
+  // device: key material
+  Fr *fixed_lag = nullptr, *fixed_poly = nullptr, *fixed_coset = nullptr;
+  Fr *sigma_lag = nullptr, *sigma_poly = nullptr, *sigma_coset = nullptr;
+  Fr *l0_c = nullptr, *llast_c = nullptr, *lactive_c = nullptr, *x_coset = nullptr, *omega_pow = nullptr;
+  // delta^j * omega^i ([S][n], Lagrange) and delta^j * X on the quotient cosets ([S][ext], radix 2^261): the identity
+  // permutation's columns. With them v + beta delta^j X + gamma = beta (delta^j X + w), w = (v + gamma) / beta — the SAME w
+  // that serves v + beta sigma + gamma = beta (sigma + w): three products per permutation column instead of four, in
+  // the Lagrange-domain fractions and in h(X) (the beta^m of a set cancels in a fraction and rides on the term's power of y).
+  Fr *dxw_lag = nullptr, *dx_coset = nullptr;
+  std::vector<uint32_t> h_term_beta_pow;  // per term of the h(X) program: the power of beta its power of y is multiplied by
+  // device: per-proof workspace. poly arena order: adv | inst | la | ls | zp | zl
+  size_t NP = 0;
+  // P: the committed columns' Lagrange values [NP][n] (what commit_lagrange and the Lagrange-domain programs read);
+  // PQ: their coefficients [NP][n] (evaluations, multiopen); PC: their values on the quotient domain [NP][ext].
+  // Out of place, so that a phase's transforms run on a lane while its commitments and the next phase's programs
+  // still read the Lagrange values.
+  Fr *P = nullptr, *PQ = nullptr, *PC = nullptr;
+  Fr *ci = nullptr, *ct = nullptr;  // [L][n] compressed lookup input / table
+  Fr *rnd = nullptr, *hq = nullptr, *hpieces = nullptr, *hpoly = nullptr, *frac = nullptr, *scratch = nullptr, *scan_tmp = nullptr;
+  Fr *frac2 = nullptr, *scratch2 = nullptr, *scan_tmp2 = nullptr;  // the lookup products' own scratch: they run beside the permutation products
+  Fr *sets_L = nullptr, *sets_N = nullptr, *sets_Q = nullptr, *hx = nullptr;  // SHPLONK buffers
+  size_t sets_Q_pairs = 0;  // (set, point) pairs sets_Q holds n coefficients for
+  // Lanes (common.hpp): 0 = the caller's ctx, 1 and 2 = its auxiliary streams. AMDZK_KEYGEN_SERIAL / AMDZK_SERIAL=1
+  // keeps everything on the caller's stream (one proof's kernels strictly one after another, as in rounds 1-2).
+  bool use_lanes = true;
+  uint32_t max_sets = 16, max_set_points = 0;
+  // What the multiopen argument derives from the key alone, built by the first proof (the polynomials live at fixed
+  // addresses in this key's workspace): the evaluation list, the query list and SHPLONK's rotation sets in terms of
+  // rotations. Only the ORDER of a set's points (upstream keeps them in a BTreeSet of field elements) depends on x.
+  struct Multiopen {
+    bool built = false;
+    std::vector<std::pair<const Fr*, int>> ev;      // (polynomial, rotation) in the order the evaluations are written
+    size_t n_written = 0;                           // ... of which the first n_written go to the transcript
+    std::vector<int> rots;                          // distinct rotations, first seen first
+    std::vector<uint32_t> ev_rot;                   // per evaluation: index into rots
+    std::vector<const Fr*> q_poly;                  // the queries, upstream order
+    std::vector<uint32_t> q_rot, q_ev;              // per query: index into rots / into ev
+    struct Set {
+      std::vector<uint32_t> rot_ids;                // the set's rotations (ascending index into rots)
+      std::vector<const Fr*> polys;                 // its polynomials, first seen first
+      std::vector<std::vector<uint32_t>> ev_idx;    // [poly][k]: evaluation of polys[poly] at rots[rot_ids[k]]
+    };
+    std::vector<Set> sets;                          // first seen first
+  } mo;
+  Fr *lk_ts = nullptr, *lk_left = nullptr;  // lookup permutation: sorted tables, leftovers [L][n]
+  // The first lk_const lookups have ONE table expression over fixed columns and constants only: their compressed table
+  // does not depend on theta or on the witness, so its sorted canonical form is made once at keygen ([lk_const][n]).
+  uint32_t lk_const = 0;
+  Fr* lk_ts_const = nullptr;
+  // (Permuting the lookups among them that also have ONE input expression before theta exists, on lane C beside the advice
+  // commitment, was measured and dropped: a proof alone took 19.1-19.3 ms with it against 18.7-19.0 without, 21
+  // proofs x 3 alternating runs, profiles/r03q_constant_tables_and_early_lookups.txt — the small sort kernels stretch the
+  // chip-filling commitment by more than they save behind theta; started behind its level-1 kernel instead they stretch
+  // its bucket reduction and lane B's transforms: 18.0-18.2 ms against 17.6-17.95.)
+  uint32_t* lk_flags = nullptr;              // [4][L][n+8]
+  int* d_err = nullptr;
+  int* h_err = nullptr;                      // pinned: where create_proof reads d_err (the first word of `pin`'s tail block)
+  // misc small device buffers (blinding uploads, points, evals, coefs) and pointer-table scratch, one slice per lane:
+  // a slice is reused in stream order by the lane that owns it
+  Fr* small_l[3] = {nullptr, nullptr, nullptr};
+  void* ptrs_l[3] = {nullptr, nullptr, nullptr};
+  Fr* small = nullptr;   // = small_l[0]
+  void* ptrs = nullptr;  // = ptrs_l[0]
+  size_t small_cap = 0, ptrs_cap = 0;
+  // programs
+  Program prog_compress, prog_pfrac, prog_lfrac, prog_h;
+  RotTable rots;
+  Fr* d_consts = nullptr;
+  Fr* d_consts261 = nullptr;  // the same table times 32 (= radix 2^261): constants of programs run on the extended domain
+  uint32_t h_terms = 0;       // terms of the h(X) program = powers of y its OP_WACC ops index
+  Fr* d_ypow = nullptr;       // [h_terms]: y^(h_terms-1-j) in radix 2^261, refreshed per proof
+  const Fr** d_cols_lag = nullptr;
+  const Fr** d_cols_ext = nullptr;
+  Fr** d_outs_compress = nullptr;
+  Fr** d_outs_pfrac = nullptr;
+  Fr** d_outs_lfrac = nullptr;
+  std::vector<void*> allocs;
+  // A workspace clone (amdzk_pk_clone_workspace) shares the key material above — columns, cosets, compiled programs,
+  // domain, constant tables — with the key it was made from and owns one more circuit instance's per-proof workspace and
+  // pointer tables: `allocs` holds only what the clone itself allocated.
+  const amdzk_pk* clone_of = nullptr;
+  // create_proof over several circuit instances (amdzk_create_proof_multi): the evaluation / query lists over all of
+  // them, built by the first such proof on this key for a given list of instance keys
+  Multiopen mo_multi;
+  std::vector<const amdzk_pk*> mo_multi_keys;
+  std::vector<const Fr*> h_cols_lag, h_cols_ext;  // host copies of the slot tables (program resolution)
+  // amdzk_check_witness, per handle, made by the handle's first check (the instructions carry this workspace's column
+  // addresses): the gate polynomials as one Lagrange-domain program, gate g ending in OP_CHECK g; the base addresses of
+  // the permutation columns; the counters, count[ncon] (u64) followed by first[ncon] (u32), constraints in report order
+  // (gates, lookups, permutation columns).
+  struct Check {
+    bool built = false;
+    Program prog_gates;
+    const Fr** d_perm_cols = nullptr;
+    unsigned long long* d_count = nullptr;
+    uint32_t* d_first = nullptr;
+  } chk;
+  // ... and per ROOT key, shared with its clones: the sigma columns decoded to (column, row), 2 x u32 per cell
+  // ([S][n]), derived by the first check on any handle of the key — under the guard, as zk_srs_ensure_prefix derives its
+  // basis — and freed with the root key. Never in the key file.
+  struct CheckShared {
+    std::mutex guard;
+    bool decoded = false;
+    uint2* d_cells = nullptr;
+  };
+  std::shared_ptr<CheckShared> chk_shared;
+  // pinned host staging (bump allocator, reset whenever the stream is known to be idle)
+  char* pin = nullptr;
+  size_t pin_cap = 0, pin_off = 0;
+
+  Fr* adv() { return P; }
+  Fr* inst() { return P + (size_t)A * n; }
+  Fr* la() { return P + (size_t)(A + I) * n; }
+  Fr* ls() { return P + (size_t)(A + I + L) * n; }
+  Fr* zp() { return P + (size_t)(A + I + 2 * L) * n; }
+  Fr* zl() { return P + (size_t)(A + I + 2 * L + nsets) * n; }
+  Fr* q_adv() { return PQ; }
+  Fr* q_la() { return PQ + (size_t)(A + I) * n; }
+  Fr* q_ls() { return PQ + (size_t)(A + I + L) * n; }
+  Fr* q_zp() { return PQ + (size_t)(A + I + 2 * L) * n; }
+  Fr* q_zl() { return PQ + (size_t)(A + I + 2 * L + nsets) * n; }
+  // slots, Lagrange table
+  uint32_t sl_fixed(uint32_t c) { return c; }
+  uint32_t sl_adv(uint32_t c) { return F + c; }
+  uint32_t sl_inst(uint32_t c) { return F + A + c; }
+  uint32_t sl_sigma(uint32_t c) { return F + A + I + c; }
+  uint32_t sl_ci(uint32_t l) { return F + A + I + S + l; }
+  uint32_t sl_ct(uint32_t l) { return F + A + I + S + L + l; }
+  uint32_t sl_la(uint32_t l) { return F + A + I + S + 2 * L + l; }
+  uint32_t sl_ls(uint32_t l) { return F + A + I + S + 3 * L + l; }
+  uint32_t sl_omega() { return F + A + I + S + 4 * L; }
+  uint32_t sl_dxw(uint32_t c) { return F + A + I + S + 4 * L + 1 + c; }
+  uint32_t nslots_lag() { return F + A + I + 2 * S + 4 * L + 1; }
+  // slots, extended table
+  uint32_t se_sigma(uint32_t c) { return F + A + I + c; }
+  uint32_t se_zp(uint32_t s) { return F + A + I + S + s; }
+  uint32_t se_zl(uint32_t l) { return F + A + I + S + nsets + l; }
+  uint32_t se_la(uint32_t l) { return F + A + I + S + nsets + L + l; }
+  uint32_t se_ls(uint32_t l) { return F + A + I + S + nsets + 2 * L + l; }
+  uint32_t se_l0() { return F + A + I + S + nsets + 3 * L; }
+  uint32_t se_llast() { return se_l0() + 1; }
+  uint32_t se_lactive() { return se_l0() + 2; }
+  uint32_t se_x() { return se_l0() + 3; }
+  uint32_t se_dx(uint32_t c) { return se_l0() + 4 + c; }
+  uint32_t nslots_ext() { return se_l0() + 4 + S; }
+};
+
+template <class T>
+int dalloc(amdzk_ctx* ctx, amdzk_pk* pk, T** p, size_t count) {
+  void* q = nullptr;
+  hipError_t e = hipMalloc(&q, (count ? count : 1) * sizeof(T));
+  if (e != hipSuccess) ZK_FAIL(ctx, AMDZK_E_NOMEM, "prover: hipMalloc(%zu) failed: %s", count * sizeof(T), hipGetErrorString(e));
+  pk->allocs.push_back(q);
+  *p = (T*)q;
+  return AMDZK_OK;
+}
+
+// stream-ordered copies on ctx's stream (keygen.hip); d2h also waits for it
+int h2d(amdzk_ctx* ctx, void* d, const void* h, size_t bytes);
+// host -> device through the key's pinned staging area: the source may be a temporary, and the copy
+// is truly asynchronous (no pageable-memory staging inside the runtime).
+int h2d_staged(amdzk_ctx* ctx, amdzk_pk* pk, void* d, const void* h, size_t bytes);
+int d2h(amdzk_ctx* ctx, void* h, const void* d, size_t bytes);
+int d2d(amdzk_ctx* ctx, void* dst, const void* src, size_t bytes);
+// MSM of ncols resident columns of the key's n rows -> affine points on the host (prover.hip)
+int commit_cols(amdzk_ctx* ctx, amdzk_pk* pk, int basis, const Fr* d_cols, size_t ncols, std::vector<G1Affine>& out);
+
+// ---- programs (program.hip)
+constexpr uint32_t H_PARTS_MAX = 8;  // pieces finalize_limb_program cuts an h(X) program into, at most: one h each (amdzk_pk::hq)
+int emit_expr(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, const std::vector<uint32_t>& words);
+int emit_compressed(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, uint32_t first, uint32_t count);
+uint32_t finalize_limb_program(Program& pr, uint32_t nparts = 1);
+int upload_consts261(amdzk_ctx* ctx, amdzk_pk* pk);
+int upload_ypow(amdzk_ctx* ctx, amdzk_pk* pk);
+int upload_program(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, bool extended);
+int program_args(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, bool extended, Fr* const* d_outs, Fr* h_out, ExprArgs& a);
+int run_program(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, bool extended, Fr* const* d_outs, Fr* h_out, const char* name);

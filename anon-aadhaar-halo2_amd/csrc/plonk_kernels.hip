@@ -44,7 +44,7 @@ __device__ __forceinline__ void st_fr(Fr* p, const Fr& v) {
 //  * the instruction stream is read through the CONSTANT address space: wave-uniform 16-byte scalar loads straight into
 //    SGPRs, two instructions ahead, no vector load + wait + readfirstlane in front of every instruction;
 //  * the operand of the NEXT instruction (a column's row, or a constant every lane reads alike) is ALWAYS fetched
-//    while the current one executes — instructions without an operand name a dummy constant (prover.hip
+//    while the current one executes — instructions without an operand name a dummy constant (program.hip
 //    upload_program), and the program ends in two END instructions, so neither fetch is conditional;
 //  * hipcc structurizes the (uniform) dispatch, and every loop-carried register is then copied twice per interpreted
 //    instruction at the merge blocks: only the top of stack and the operand in flight are loop-carried registers.
@@ -156,7 +156,7 @@ __global__ __launch_bounds__(EXPR_THREADS) void expr_eval_kernel(ExprArgs a) {
 // top of stack and the coset's X values live on 9 x 29-bit limbs (fp29.cuh), lazily reduced: sums
 // and differences are limb-wise with a carry pass, products reset the bound to 2p, and the host — which knows the
 // whole (wave-uniform) program — tracks every value's bound and inserts OP_REDUCE where a product or a difference
-// would leave its range (prover.hip finalize_limb_program). The fold with y, h = sum_j y^(K-1-j) term_j, is a sum of
+// would leave its range (program.hip finalize_limb_program). The fold with y, h = sum_j y^(K-1-j) term_j, is a sum of
 // products with ONE reduction per group of terms (fp29.cuh f29_wide_*): the host groups the terms by the hot column
 // that multiplies them (l_0, l_last, l_active, or none), each term is added as term_j * y^(K-1-j) — 81 multiply-adds
 // into 17 un-carried columns, the power a per-proof constant — and a group is reduced, multiplied by its hot column
@@ -199,7 +199,7 @@ __global__ __launch_bounds__(EXPR_THREADS) void expr_eval_limbs_kernel(ExprArgs 
   auto hot = [&](uint32_t k) -> Fr29 { return fr29_unpack(ld_fr(a.cols[a.hot[k]] + row)); };
   uint32_t sp = 0;  // elements on the stack, including tos
   const size_t blk_base = row & ~a.mask;
-  // piece blockIdx.y of the program (prover.hip finalize_limb_program) accumulates into its own h
+  // piece blockIdx.y of the program (program.hip finalize_limb_program) accumulates into its own h
   const uint32_t first = a.nparts ? a.part_start[blockIdx.y] : 0u, prog_len = a.nparts ? a.part_len[blockIdx.y] : a.prog_len;
   const ExprProgPtr prog = (ExprProgPtr)a.prog + first;
   Fr* const h_out = a.h_out + (size_t)blockIdx.y * a.nrows;

@@ -1,4 +1,4 @@
-// Interfaces of plonk_kernels.hip used by the prover driver (prover.hip).
+// Interfaces of plonk_kernels.hip used by the host units of the PLONK layer (program.hip, keygen.hip, prover.hip, multiopen.hip).
 #pragma once
 #include "common.hpp"
 
@@ -18,7 +18,7 @@ enum ExprOp : uint32_t {
   OP_MUL_COL = 9,
   OP_ADD_COL = 10,
   OP_SUB_COL = 11,
-  OP_ACC = 12,    // h = h*y + pop(): host-side programs only (prover.hip finalize_limb_program turns the fold into
+  OP_ACC = 12,    // h = h*y + pop(): host-side programs only (program.hip finalize_limb_program turns the fold into
                   // OP_WACC / OP_WFLUSH); neither interpreter executes it
   OP_STORE = 13,  // outs[arg][row] = pop()
   OP_SQR = 14,
@@ -78,7 +78,7 @@ struct ExprArgs {
 };
 
 int zk_expr_eval(amdzk_ctx* ctx, const ExprArgs& a, uint32_t depth, const char* name);
-// the same for a radix-2^261 program finalised by the host for the limb-resident interpreter (prover.hip finalize_limb_program)
+// the same for a radix-2^261 program finalised by the host for the limb-resident interpreter (program.hip finalize_limb_program)
 int zk_expr_eval_limbs(amdzk_ctx* ctx, const ExprArgs& a, uint32_t depth, const char* name);
 // d_out[i] = Fr::random of ChaCha20 block counter0 + i under `key` (rand_chacha's ChaCha20Rng, halo2curves' from_u512)
 int zk_chacha20_fr_random(amdzk_ctx* ctx, bn254::Fr* d_out, size_t n, const uint32_t key[8], uint64_t counter0, const bn254::Fr& r3);

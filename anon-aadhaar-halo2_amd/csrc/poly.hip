@@ -14,11 +14,6 @@
 
 using namespace bn254;
 
-int zk_ntt_ex(amdzk_ctx* ctx, const Fr* d_in, size_t in_stride, Fr* d_out, size_t out_stride, uint32_t log_n,
-              const uint64_t omega[4], size_t ncols, uint32_t in_len, const Fr* in_coset, const Fr* out_mul, const Fr* in_first,
-              const NttTables* tabs);
-Fr zk_fr_inv_pow2(uint32_t log_n);
-
 struct amdzk_domain {
   uint32_t k = 0, extended_k = 0, j = 0;
   uint64_t quotient_poly_degree = 0;
@@ -252,6 +247,8 @@ int amdzk_coeff_to_extended_dev(amdzk_ctx* ctx, const amdzk_domain* d, const voi
                    (const uint64_t*)d->extended_omega.l, ncols, 1u << d->k, ic, nullptr, nullptr, nullptr);
 }
 
+}  // extern "C"
+
 // ---- the quotient on nc cosets instead of the whole extended domain (prover-private).
 // h(X) = numerator / (X^n - 1) has degree below (j-1) n, so its j-1 pieces h_t (h = sum_t X^(t n) h_t) are pinned
 // down by the numerator on ANY j-1 cosets g_c H on which X^n - 1 does not vanish — upstream evaluates on all
@@ -370,6 +367,8 @@ int zk_cosets_to_pieces(amdzk_ctx* ctx, const amdzk_domain* d, Fr* d_h, Fr* d_pi
 #undef COMBINE
   return AMDZK_OK;
 }
+
+extern "C" {
 
 int amdzk_extended_to_coeff_dev(amdzk_ctx* ctx, const amdzk_domain* d, void* d_ext, size_t ncols, size_t col_stride) {
   ZK_ENTER(ctx);

@@ -1,10 +1,8 @@
-// Prover driver: keygen_pk and create_proof for KZG + SHPLONK + Blake2b, one circuit instance,
-// phase 0 — halo2_proofs 0.2.0 @ PSE v2023_01_20 [UP] (/root/reference/Cargo.lock:469-471):
-//   plonk::keygen::{keygen_vk, keygen_pk}, plonk::prover::create_proof,
-//   plonk::{permutation,lookup,vanishing}::prover, poly::kzg::multiopen::shplonk::ProverSHPLONK.
-// This is the function the reference's circuits are handed to; the circuit itself
-// arrives as a plain-data description of its ConstraintSystem (amdzk_circuit) plus its fixed
-// columns, copy-constraint mapping and witness columns. The order of transcript operations and RNG
+// The proof path: create_proof for KZG + SHPLONK or GWC + Blake2b or Keccak, one or several circuit instances, up to
+// three phases — halo2_proofs 0.2.0 @ PSE v2023_01_20 [UP]:
+//   plonk::prover::create_proof, plonk::{permutation,lookup,vanishing}::prover,
+//   poly::kzg::multiopen::{shplonk::ProverSHPLONK, gwc::ProverGWC}.
+// The key it proves with is keygen.hip's (pk.hpp), its programs program.hip's. The order of transcript operations and RNG
 // draws follows SURVEY.md Appendix A.
 //
 // Control flow, Fiat-Shamir and the O(columns) bookkeeping stay on the host; every O(n) step is a
@@ -25,92 +23,13 @@
 #include <string>
 
 #include "hostcrypto.hpp"
-#include "pkblob.hpp"
-#include "check_kernels.hpp"
-#include "plonk_kernels.hpp"
+#include "pk.hpp"
 
 using namespace bn254;
 using zkhost::Blake2bWrite;
 using zkhost::ChaCha20Rng;
 
-// from the other translation units
-struct amdzk_srs;
-struct amdzk_domain;
-int zk_msm_dev_xyzz(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const Fr* d_scalars, size_t ncols, size_t len, size_t col_stride,
-                    G1X** d_out);
-int zk_msm_dev_xyzz_cols(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const Fr* const* d_col_ptrs, size_t ncols, size_t len,
-                         size_t max_ws_bytes, G1X** d_out);
-int zk_msm_finish(amdzk_ctx* ctx, const G1X* d_res, size_t ncols, uint64_t* out_jac);
-uint32_t zk_srs_k(const amdzk_srs* srs);
-int zk_lagrange_to_coeff(amdzk_ctx* ctx, const amdzk_domain* d, const Fr* d_in, size_t in_stride, Fr* d_out, size_t out_stride, size_t ncols);
-extern "C" {
-int amdzk_domain_new(amdzk_ctx* ctx, uint32_t j, uint32_t k, amdzk_domain** out);
-void amdzk_domain_free(amdzk_ctx* ctx, amdzk_domain* d);
-uint32_t amdzk_domain_extended_k(const amdzk_domain* d);
-int amdzk_domain_constant(const amdzk_domain* d, int what, uint64_t out[4]);
-int amdzk_lagrange_to_coeff_dev(amdzk_ctx* ctx, const amdzk_domain* d, void* d_cols, size_t ncols, size_t col_stride);
-int amdzk_coeff_to_extended_dev(amdzk_ctx* ctx, const amdzk_domain* d, const void* d_coeff, size_t in_stride, void* d_ext, size_t out_stride,
-                                size_t ncols);
-int amdzk_extended_to_coeff_dev(amdzk_ctx* ctx, const amdzk_domain* d, void* d_ext, size_t ncols, size_t col_stride);
-int amdzk_divide_by_vanishing_dev(amdzk_ctx* ctx, const amdzk_domain* d, void* d_ext, size_t ncols, size_t col_stride);
-// prover-private: the quotient domain = nc cosets of the size-n subgroup, data in Montgomery radix 2^261 (poly.hip) —
-// what the h(X) program multiplies in
-int zk_quotient_plan(amdzk_ctx* ctx, amdzk_domain* d, uint32_t nc);
-Fr zk_quotient_coset_g(const amdzk_domain* d, uint32_t c);
-int zk_coeff_to_cosets_r261(amdzk_ctx* ctx, const amdzk_domain* d, const Fr* d_coeff, size_t in_stride, Fr* d_out, size_t out_stride,
-                            size_t ncols);
-int zk_cosets_to_pieces(amdzk_ctx* ctx, const amdzk_domain* d, Fr* d_h, Fr* d_pieces, uint32_t npieces);
-int amdzk_fr_to_repr_dev(amdzk_ctx* ctx, void* d_a, size_t n);
-int amdzk_fr_from_raw_dev(amdzk_ctx* ctx, void* d_a, size_t n);
-}
-
 namespace {
-
-// host-format expression words (include/amdzk.h)
-enum : uint32_t { XOP_CONST = 1, XOP_FIXED = 2, XOP_ADVICE = 3, XOP_INSTANCE = 4, XOP_NEG = 5, XOP_ADD = 6, XOP_MUL = 7, XOP_SCALE = 8, XOP_CHALLENGE = 9 };
-
-Fr fr_delta() {  // Fr::DELTA = 7^(2^28)  (contract.sol:440)
-  Fr r;
-  uint64_t v[4] = {0x870e56bbe533e9a2ULL, 0x5b5f898e5e963f25ULL, 0x64ec26aad4c86e71ULL, 0x09226b6e22c6f0caULL};
-  memcpy(r.l, v, 32);
-  return to_mont(r);
-}
-
-struct Program {
-  std::vector<uint32_t> words;
-  uint32_t depth = 0, cur = 0;
-  bool uses_hot = false;
-  ExprInstr* d_instr = nullptr;  // resolved instructions (device)
-  // Lagrange-domain programs: instruction indices at which an independent piece starts (the stack is empty there):
-  // run_program cuts the program there into up to EXPR_MAX_PARTS parts that run side by side (ExprArgs::nparts)
-  std::vector<uint32_t> piece_starts;
-  void piece() { piece_starts.push_back((uint32_t)words.size()); }
-  // h(X) programs: term j (closed by the j-th OP_ACC) carries the factor beta^term_beta[j] in its power of y
-  std::vector<uint32_t> term_beta;
-  uint32_t next_beta = 0;
-  void op(uint32_t o, uint32_t arg = 0) {
-    words.push_back((o << 24) | (arg & 0xffffffu));
-    if (o == OP_ACC) {
-      term_beta.push_back(next_beta);
-      next_beta = 0;
-    }
-  }
-  void push() {
-    cur++;
-    if (cur > depth) depth = cur;
-  }
-  void pop() { cur--; }
-};
-
-struct RotTable {
-  std::vector<int32_t> rots;
-  uint32_t index(int32_t r) {
-    for (size_t i = 0; i < rots.size(); i++)
-      if (rots[i] == r) return (uint32_t)i;
-    rots.push_back(r);
-    return (uint32_t)rots.size() - 1;
-  }
-};
 
 bool fr_less_canon(const std::array<uint64_t, 4>& a, const std::array<uint64_t, 4>& b) {
   for (int i = 3; i >= 0; i--)
@@ -143,219 +62,7 @@ struct RandomSource {
   }
 };
 
-struct amdzk_pk {
-  uint32_t k = 0, ek = 0, bf = 0, degree = 0, F = 0, A = 0, I = 0, S = 0, L = 0, nsets = 0, chunk = 0, qdeg = 0;
-  uint32_t nc = 0;       // cosets of the quotient domain (poly.hip zk_quotient_plan): qdeg of the 2^(ek-k) upstream uses
-  size_t n = 0, ext = 0;  // ext = nc * n rows: every "extended" column holds [coset][row]
-  std::vector<std::pair<int, int>> advice_queries, fixed_queries, instance_queries;
-  std::vector<std::pair<int, int>> perm_cols;  // (kind, index)
-  std::vector<std::vector<uint32_t>> exprs;
-  uint32_t num_gates = 0;
-  std::vector<std::pair<uint32_t, uint32_t>> lookup_shape;  // (#inputs, #tables); expressions follow the gates in order
-  std::vector<Fr> consts;                                   // circuit constants, then the dynamic ones
-  uint32_t c_one = 0, c_theta = 0, c_beta = 0, c_gamma = 0, c_y = 0, c_betainv = 0;
-  // Challenge phases (amdzk_keygen_phased): challenge i lives in slot c_chal0 + i of the constant table, refreshed per
-  // proof like theta ... y; nothing made at keygen reads those slots. nphases = 1 and no challenges: a phase-0 key.
-  uint32_t num_challenges = 0, c_chal0 = 0, nphases = 1;
-  std::vector<uint8_t> advice_phase, challenge_phase;
-  bool phased() const { return nphases > 1 || num_challenges > 0; }
-  amdzk_domain* dom = nullptr;
-  const amdzk_srs* srs = nullptr;
-  Fr transcript_repr, omega, omega_inv;
-  std::vector<G1Affine> fixed_commitments, perm_commitments;
-  // What keygen was given, as the caller passed it (the flattened amdzk_circuit arrays and the phase table): the header of
-  // the key file (amdzk_pk_write). Shared with workspace clones.
-  std::shared_ptr<const pkblob::Desc> src_desc;
-
-  // device: key material
-  Fr *fixed_lag = nullptr, *fixed_poly = nullptr, *fixed_coset = nullptr;
-  Fr *sigma_lag = nullptr, *sigma_poly = nullptr, *sigma_coset = nullptr;
-  Fr *l0_c = nullptr, *llast_c = nullptr, *lactive_c = nullptr, *x_coset = nullptr, *omega_pow = nullptr;
-  // delta^j * omega^i ([S][n], Lagrange) and delta^j * X on the quotient cosets ([S][ext], radix 2^261): the identity
-  // permutation's columns. With them v + beta delta^j X + gamma = beta (delta^j X + w), w = (v + gamma) / beta — the SAME w
-  // that serves v + beta sigma + gamma = beta (sigma + w): three products per permutation column instead of four, in
-  // the Lagrange-domain fractions and in h(X) (the beta^m of a set cancels in a fraction and rides on the term's power of y).
-  Fr *dxw_lag = nullptr, *dx_coset = nullptr;
-  std::vector<uint32_t> h_term_beta_pow;  // per term of the h(X) program: the power of beta its power of y is multiplied by
-  // device: per-proof workspace. poly arena order: adv | inst | la | ls | zp | zl
-  size_t NP = 0;
-  // P: the committed columns' Lagrange values [NP][n] (what commit_lagrange and the Lagrange-domain programs read);
-  // PQ: their coefficients [NP][n] (evaluations, multiopen); PC: their values on the quotient domain [NP][ext].
-  // Out of place, so that a phase's transforms run on a lane while its commitments and the next phase's programs
-  // still read the Lagrange values.
-  Fr *P = nullptr, *PQ = nullptr, *PC = nullptr;
-  Fr *ci = nullptr, *ct = nullptr;  // [L][n] compressed lookup input / table
-  Fr *rnd = nullptr, *hq = nullptr, *hpieces = nullptr, *hpoly = nullptr, *frac = nullptr, *scratch = nullptr, *scan_tmp = nullptr;
-  Fr *frac2 = nullptr, *scratch2 = nullptr, *scan_tmp2 = nullptr;  // the lookup products' own scratch: they run beside the permutation products
-  Fr *sets_L = nullptr, *sets_N = nullptr, *sets_Q = nullptr, *hx = nullptr;  // SHPLONK buffers
-  size_t sets_Q_pairs = 0;  // (set, point) pairs sets_Q holds n coefficients for
-  // Lanes (common.hpp): 0 = the caller's ctx, 1 and 2 = its auxiliary streams. AMDZK_KEYGEN_SERIAL / AMDZK_SERIAL=1
-  // keeps everything on the caller's stream (one proof's kernels strictly one after another, as in rounds 1-2).
-  bool use_lanes = true;
-  uint32_t max_sets = 16, max_set_points = 0;
-  // What the multiopen argument derives from the key alone, built by the first proof (the polynomials live at fixed
-  // addresses in this key's workspace): the evaluation list, the query list and SHPLONK's rotation sets in terms of
-  // rotations. Only the ORDER of a set's points (upstream keeps them in a BTreeSet of field elements) depends on x.
-  struct Multiopen {
-    bool built = false;
-    std::vector<std::pair<const Fr*, int>> ev;      // (polynomial, rotation) in the order the evaluations are written
-    size_t n_written = 0;                           // ... of which the first n_written go to the transcript
-    std::vector<int> rots;                          // distinct rotations, first seen first
-    std::vector<uint32_t> ev_rot;                   // per evaluation: index into rots
-    std::vector<const Fr*> q_poly;                  // the queries, upstream order
-    std::vector<uint32_t> q_rot, q_ev;              // per query: index into rots / into ev
-    struct Set {
-      std::vector<uint32_t> rot_ids;                // the set's rotations (ascending index into rots)
-      std::vector<const Fr*> polys;                 // its polynomials, first seen first
-      std::vector<std::vector<uint32_t>> ev_idx;    // [poly][k]: evaluation of polys[poly] at rots[rot_ids[k]]
-    };
-    std::vector<Set> sets;                          // first seen first
-  } mo;
-  Fr *lk_ts = nullptr, *lk_left = nullptr;  // lookup permutation: sorted tables, leftovers [L][n]
-  // The first lk_const lookups have ONE table expression over fixed columns and constants only: their compressed table
-  // does not depend on theta or on the witness, so its sorted canonical form is made once at keygen ([lk_const][n]).
-  uint32_t lk_const = 0;
-  Fr* lk_ts_const = nullptr;
-  // (Permuting the lookups among them that also have ONE input expression before theta exists, on lane C beside the advice
-  // commitment, was measured and dropped: a proof alone took 19.1-19.3 ms with it against 18.7-19.0 without, 21
-  // proofs x 3 alternating runs, profiles/r03q_constant_tables_and_early_lookups.txt — the small sort kernels stretch the
-  // chip-filling commitment by more than they save behind theta; started behind its level-1 kernel instead they stretch
-  // its bucket reduction and lane B's transforms: 18.0-18.2 ms against 17.6-17.95.)
-  uint32_t* lk_flags = nullptr;              // [4][L][n+8]
-  int* d_err = nullptr;
-  int* h_err = nullptr;                      // pinned: where create_proof reads d_err (the first word of `pin`'s tail block)
-  // misc small device buffers (blinding uploads, points, evals, coefs) and pointer-table scratch, one slice per lane:
-  // a slice is reused in stream order by the lane that owns it
-  Fr* small_l[3] = {nullptr, nullptr, nullptr};
-  void* ptrs_l[3] = {nullptr, nullptr, nullptr};
-  Fr* small = nullptr;   // = small_l[0]
-  void* ptrs = nullptr;  // = ptrs_l[0]
-  size_t small_cap = 0, ptrs_cap = 0;
-  // programs
-  Program prog_compress, prog_pfrac, prog_lfrac, prog_h;
-  RotTable rots;
-  Fr* d_consts = nullptr;
-  Fr* d_consts261 = nullptr;  // the same table times 32 (= radix 2^261): constants of programs run on the extended domain
-  uint32_t h_terms = 0;       // terms of the h(X) program = powers of y its OP_WACC ops index
-  Fr* d_ypow = nullptr;       // [h_terms]: y^(h_terms-1-j) in radix 2^261, refreshed per proof
-  const Fr** d_cols_lag = nullptr;
-  const Fr** d_cols_ext = nullptr;
-  Fr** d_outs_compress = nullptr;
-  Fr** d_outs_pfrac = nullptr;
-  Fr** d_outs_lfrac = nullptr;
-  std::vector<void*> allocs;
-  // A workspace clone (amdzk_pk_clone_workspace) shares the key material above — columns, cosets, compiled programs,
-  // domain, constant tables — with the key it was made from and owns one more circuit instance's per-proof workspace and
-  // pointer tables: `allocs` holds only what the clone itself allocated.
-  const amdzk_pk* clone_of = nullptr;
-  // create_proof over several circuit instances (amdzk_create_proof_multi): the evaluation / query lists over all of
-  // them, built by the first such proof on this key for a given list of instance keys
-  Multiopen mo_multi;
-  std::vector<const amdzk_pk*> mo_multi_keys;
-  std::vector<const Fr*> h_cols_lag, h_cols_ext;  // host copies of the slot tables (program resolution)
-  // amdzk_check_witness, per handle, made by the handle's first check (the instructions carry this workspace's column
-  // addresses): the gate polynomials as one Lagrange-domain program, gate g ending in OP_CHECK g; the base addresses of
-  // the permutation columns; the counters, count[ncon] (u64) followed by first[ncon] (u32), constraints in report order
-  // (gates, lookups, permutation columns).
-  struct Check {
-    bool built = false;
-    Program prog_gates;
-    const Fr** d_perm_cols = nullptr;
-    unsigned long long* d_count = nullptr;
-    uint32_t* d_first = nullptr;
-  } chk;
-  // ... and per ROOT key, shared with its clones: the sigma columns decoded to (column, row), 2 x u32 per cell
-  // ([S][n]), derived by the first check on any handle of the key — under the guard, as zk_srs_ensure_prefix derives its
-  // basis — and freed with the root key. Never in the key file.
-  struct CheckShared {
-    std::mutex guard;
-    bool decoded = false;
-    uint2* d_cells = nullptr;
-  };
-  std::shared_ptr<CheckShared> chk_shared;
-  // pinned host staging (bump allocator, reset whenever the stream is known to be idle)
-  char* pin = nullptr;
-  size_t pin_cap = 0, pin_off = 0;
-
-  Fr* adv() { return P; }
-  Fr* inst() { return P + (size_t)A * n; }
-  Fr* la() { return P + (size_t)(A + I) * n; }
-  Fr* ls() { return P + (size_t)(A + I + L) * n; }
-  Fr* zp() { return P + (size_t)(A + I + 2 * L) * n; }
-  Fr* zl() { return P + (size_t)(A + I + 2 * L + nsets) * n; }
-  Fr* q_adv() { return PQ; }
-  Fr* q_la() { return PQ + (size_t)(A + I) * n; }
-  Fr* q_ls() { return PQ + (size_t)(A + I + L) * n; }
-  Fr* q_zp() { return PQ + (size_t)(A + I + 2 * L) * n; }
-  Fr* q_zl() { return PQ + (size_t)(A + I + 2 * L + nsets) * n; }
-  // slots, Lagrange table
-  uint32_t sl_fixed(uint32_t c) { return c; }
-  uint32_t sl_adv(uint32_t c) { return F + c; }
-  uint32_t sl_inst(uint32_t c) { return F + A + c; }
-  uint32_t sl_sigma(uint32_t c) { return F + A + I + c; }
-  uint32_t sl_ci(uint32_t l) { return F + A + I + S + l; }
-  uint32_t sl_ct(uint32_t l) { return F + A + I + S + L + l; }
-  uint32_t sl_la(uint32_t l) { return F + A + I + S + 2 * L + l; }
-  uint32_t sl_ls(uint32_t l) { return F + A + I + S + 3 * L + l; }
-  uint32_t sl_omega() { return F + A + I + S + 4 * L; }
-  uint32_t sl_dxw(uint32_t c) { return F + A + I + S + 4 * L + 1 + c; }
-  uint32_t nslots_lag() { return F + A + I + 2 * S + 4 * L + 1; }
-  // slots, extended table
-  uint32_t se_sigma(uint32_t c) { return F + A + I + c; }
-  uint32_t se_zp(uint32_t s) { return F + A + I + S + s; }
-  uint32_t se_zl(uint32_t l) { return F + A + I + S + nsets + l; }
-  uint32_t se_la(uint32_t l) { return F + A + I + S + nsets + L + l; }
-  uint32_t se_ls(uint32_t l) { return F + A + I + S + nsets + 2 * L + l; }
-  uint32_t se_l0() { return F + A + I + S + nsets + 3 * L; }
-  uint32_t se_llast() { return se_l0() + 1; }
-  uint32_t se_lactive() { return se_l0() + 2; }
-  uint32_t se_x() { return se_l0() + 3; }
-  uint32_t se_dx(uint32_t c) { return se_l0() + 4 + c; }
-  uint32_t nslots_ext() { return se_l0() + 4 + S; }
-};
-
 namespace {
-
-template <class T>
-int dalloc(amdzk_ctx* ctx, amdzk_pk* pk, T** p, size_t count) {
-  void* q = nullptr;
-  hipError_t e = hipMalloc(&q, (count ? count : 1) * sizeof(T));
-  if (e != hipSuccess) ZK_FAIL(ctx, AMDZK_E_NOMEM, "prover: hipMalloc(%zu) failed: %s", count * sizeof(T), hipGetErrorString(e));
-  pk->allocs.push_back(q);
-  *p = (T*)q;
-  return AMDZK_OK;
-}
-
-int h2d(amdzk_ctx* ctx, void* d, const void* h, size_t bytes) {
-  if (bytes) ZK_HIP(ctx, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, ctx->stream));
-  return AMDZK_OK;
-}
-// host -> device through the key's pinned staging area: the source may be a temporary, and the copy
-// is truly asynchronous (no pageable-memory staging inside the runtime).
-int h2d_staged(amdzk_ctx* ctx, amdzk_pk* pk, void* d, const void* h, size_t bytes) {
-  if (!bytes) return AMDZK_OK;
-  if (!pk->pin || bytes > pk->pin_cap) return h2d(ctx, d, h, bytes);
-  size_t off = (pk->pin_off + 63) & ~(size_t)63;
-  if (off + bytes > pk->pin_cap) {  // wrap: every stream that may still be reading the staging area must be done with it
-    ZK_TRY(zk_sync_all(ctx));
-    off = 0;
-  }
-  memcpy(pk->pin + off, h, bytes);
-  pk->pin_off = off + bytes;
-  ZK_HIP(ctx, hipMemcpyAsync(d, pk->pin + off, bytes, hipMemcpyHostToDevice, ctx->stream));
-  return AMDZK_OK;
-}
-int d2h(amdzk_ctx* ctx, void* h, const void* d, size_t bytes) {
-  if (bytes) {
-    ZK_HIP(ctx, hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
-  }
-  return AMDZK_OK;
-}
-int d2d(amdzk_ctx* ctx, void* dst, const void* src, size_t bytes) {
-  if (bytes) ZK_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, ctx->stream));
-  return AMDZK_OK;
-}
 
 // lookup::prover::permute_expression_pair for L lookups at once, on Montgomery-form columns of n rows each:
 // A (compressed inputs, [L][n]) is sorted in place into A', S ([L][n]) receives the aligned table S'; rows >= usable
@@ -431,473 +138,6 @@ int commit_finish(PendingCommit& pc, std::vector<G1Affine>& out) {
   }
   return AMDZK_OK;
 }
-int commit_cols(amdzk_ctx* ctx, amdzk_pk* pk, int basis, const Fr* d_cols, size_t ncols, std::vector<G1Affine>& out) {
-  PendingCommit pc;
-  ZK_TRY(commit_launch(ctx, pk, basis, d_cols, ncols, pc));
-  return commit_finish(pc, out);
-}
-
-// Translate a host-format postfix expression into device ops. The postfix words are first rebuilt
-// into a tree so that a binary operation with a leaf operand (a column or a constant) becomes ONE
-// fused instruction on the top of stack (MUL_COL / ADD_COL / SUB_COL / MUL_CONST / ADD_CONST) instead
-// of push + pop through the LDS stack. Field addition and multiplication are exact and commutative,
-// so the value is the one upstream's Expression::evaluate produces. Lagrange and extended programs
-// share slot numbers for fixed/advice/instance columns.
-struct ENode {
-  uint32_t op, payload;
-  int l, r;
-};
-
-int emit_tree(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, const std::vector<ENode>& t, int i) {
-  const ENode& n = t[i];
-  auto is_col = [&](int j) { return t[j].op == XOP_FIXED || t[j].op == XOP_ADVICE || t[j].op == XOP_INSTANCE; };
-  auto col_arg = [&](int j) -> uint32_t {
-    const ENode& c = t[j];
-    uint32_t col = c.payload >> 8;
-    int32_t rot = (int32_t)(c.payload & 0xff) - 128;
-    uint32_t slot = c.op == XOP_FIXED ? pk->sl_fixed(col) : c.op == XOP_ADVICE ? pk->sl_adv(col) : pk->sl_inst(col);
-    return (slot << 8) | pk->rots.index(rot);
-  };
-  switch (n.op) {
-    case XOP_CONST:
-      pr.op(OP_PUSH_CONST, n.payload);
-      pr.push();
-      return AMDZK_OK;
-    case XOP_FIXED:
-    case XOP_ADVICE:
-    case XOP_INSTANCE:
-      pr.op(OP_PUSH_COL, col_arg(i));
-      pr.push();
-      return AMDZK_OK;
-    case XOP_NEG:
-      ZK_TRY(emit_tree(ctx, pk, pr, t, n.l));
-      pr.op(OP_NEG);
-      return AMDZK_OK;
-    case XOP_SCALE:
-      ZK_TRY(emit_tree(ctx, pk, pr, t, n.l));
-      pr.op(OP_MUL_CONST, n.payload);
-      return AMDZK_OK;
-    case XOP_ADD: {
-      int a = n.l, b = n.r;
-      if (t[b].op == XOP_NEG && is_col(t[b].l)) {  // a + (-col) -> a - col
-        ZK_TRY(emit_tree(ctx, pk, pr, t, a));
-        pr.op(OP_SUB_COL, col_arg(t[b].l));
-        return AMDZK_OK;
-      }
-      if (!is_col(b) && t[b].op != XOP_CONST && (is_col(a) || t[a].op == XOP_CONST)) std::swap(a, b);
-      if (is_col(b)) {
-        ZK_TRY(emit_tree(ctx, pk, pr, t, a));
-        pr.op(OP_ADD_COL, col_arg(b));
-        return AMDZK_OK;
-      }
-      if (t[b].op == XOP_CONST) {
-        ZK_TRY(emit_tree(ctx, pk, pr, t, a));
-        pr.op(OP_ADD_CONST, t[b].payload);
-        return AMDZK_OK;
-      }
-      ZK_TRY(emit_tree(ctx, pk, pr, t, a));
-      ZK_TRY(emit_tree(ctx, pk, pr, t, b));
-      pr.op(OP_ADD);
-      pr.pop();
-      return AMDZK_OK;
-    }
-    case XOP_MUL: {
-      int a = n.l, b = n.r;
-      if (!is_col(b) && t[b].op != XOP_CONST && (is_col(a) || t[a].op == XOP_CONST)) std::swap(a, b);
-      if (is_col(b)) {
-        ZK_TRY(emit_tree(ctx, pk, pr, t, a));
-        pr.op(OP_MUL_COL, col_arg(b));
-        return AMDZK_OK;
-      }
-      if (t[b].op == XOP_CONST) {
-        ZK_TRY(emit_tree(ctx, pk, pr, t, a));
-        pr.op(OP_MUL_CONST, t[b].payload);
-        return AMDZK_OK;
-      }
-      ZK_TRY(emit_tree(ctx, pk, pr, t, a));
-      ZK_TRY(emit_tree(ctx, pk, pr, t, b));
-      pr.op(OP_MUL);
-      pr.pop();
-      return AMDZK_OK;
-    }
-    default:
-      ZK_FAIL(ctx, AMDZK_E_INVALID, "circuit: bad expression node %u", n.op);
-  }
-}
-
-int emit_expr(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, const std::vector<uint32_t>& words) {
-  std::vector<ENode> t;
-  std::vector<int> st;
-  for (uint32_t w : words) {
-    uint32_t op = w >> 24, pl = w & 0xffffffu;
-    switch (op) {
-      case XOP_CONST:
-        if (pl >= pk->c_one) ZK_FAIL(ctx, AMDZK_E_INVALID, "circuit: constant index %u out of range", pl);
-        t.push_back(ENode{op, pl, -1, -1});
-        st.push_back((int)t.size() - 1);
-        break;
-      case XOP_FIXED:
-      case XOP_ADVICE:
-      case XOP_INSTANCE: {
-        uint32_t col = pl >> 8;
-        uint32_t lim = op == XOP_FIXED ? pk->F : op == XOP_ADVICE ? pk->A : pk->I;
-        if (col >= lim) ZK_FAIL(ctx, AMDZK_E_INVALID, "circuit: column %u out of range", col);
-        t.push_back(ENode{op, pl, -1, -1});
-        st.push_back((int)t.size() - 1);
-      } break;
-      case XOP_CHALLENGE:  // one more constant operand: its slot is written per proof, so nothing here may read its value
-        if (pl >= pk->num_challenges) ZK_FAIL(ctx, AMDZK_E_INVALID, "circuit: bad expression word %08x", w);
-        t.push_back(ENode{XOP_CONST, pk->c_chal0 + pl, -1, -1});
-        st.push_back((int)t.size() - 1);
-        break;
-      case XOP_NEG:
-      case XOP_SCALE:
-        if (st.empty()) ZK_FAIL(ctx, AMDZK_E_INVALID, "circuit: malformed expression");
-        if (op == XOP_SCALE && pl >= pk->c_one) ZK_FAIL(ctx, AMDZK_E_INVALID, "circuit: constant index %u out of range", pl);
-        t.push_back(ENode{op, pl, st.back(), -1});
-        st.back() = (int)t.size() - 1;
-        break;
-      case XOP_ADD:
-      case XOP_MUL: {
-        if (st.size() < 2) ZK_FAIL(ctx, AMDZK_E_INVALID, "circuit: malformed expression");
-        int r = st.back();
-        st.pop_back();
-        int l = st.back();
-        t.push_back(ENode{op, 0, l, r});
-        st.back() = (int)t.size() - 1;
-      } break;
-      default:
-        ZK_FAIL(ctx, AMDZK_E_INVALID, "circuit: bad expression word %08x", w);
-    }
-  }
-  if (st.size() != 1) ZK_FAIL(ctx, AMDZK_E_INVALID, "circuit: malformed expression");
-  return emit_tree(ctx, pk, pr, t, st[0]);
-}
-
-// fold(acc * theta + expr) over a lookup's expressions (first term: 0*theta + e0 = e0)
-int emit_compressed(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, uint32_t first, uint32_t count) {
-  for (uint32_t i = 0; i < count; i++) {
-    if (i > 0) pr.op(OP_MUL_CONST, pk->c_theta);
-    ZK_TRY(emit_expr(ctx, pk, pr, pk->exprs[first + i]));
-    if (i > 0) {
-      pr.op(OP_ADD);
-      pr.pop();
-    }
-  }
-  return AMDZK_OK;
-}
-
-// Quotient-domain programs run on the limb-resident interpreter (plonk_kernels.hip expr_eval_limbs_kernel): values are
-// 9 x 29-bit limbs, lazily reduced. This pass walks the (straight-line, wave-uniform) program once with the bound of
-// every stack entry in units of p and
-//   * inserts OP_REDUCE where a product would leave f29_mul's range (a*b < 169 p^2), where a subtrahend is too large
-//     for the K*p constants (below 2p: K = 3, below 9p: K = 10), before a value sinks into the LDS stack with a bound
-//     above 8, and before OP_STORE (packing needs a value below 2p);
-//   * picks OP_SUB / OP_SUB_BIG and OP_NEG / OP_NEG_BIG by the subtrahend's bound;
-//   * replaces the Horner fold h = h*y + term (OP_ACC) by a sum of products with one reduction per group: the program
-//     is cut into its terms (the stack is empty at every OP_ACC), a term that ends in `* hot[k]` loses that factor
-//     and joins group k, the others group 4; term j of the original order adds term_j * y^(K-1-j) to the wide
-//     accumulator (OP_WACC j; every sixth term of a group also moves the columns' carries up), and each group ends
-//     with OP_WFLUSH k: h (+)= reduce(wide) * hot[k], h canonical in its output row. A group is split when its sum of
-//     bounds would leave the reduction's range.
-// Bounds: a column, constant or hot value is below 1 (canonical); a product is below 2; a sum adds the bounds; a
-// difference a - b adds K to a's; the weak reduction gives 1.0002; a flushed group sum(bounds) / 169.3 + 1.
-// nparts > 1 cuts the finalised program into that many independent pieces of about equal length (Program::piece_starts):
-// a piece is a run of terms of the group order, closed by its own flush, and its first flush overwrites ITS h (bit 4) —
-// the interpreter runs piece p on the workgroups with blockIdx.y = p into h + p * rows, and the pieces' sums are added
-// afterwards (h is linear in the terms). One proof alone fills the chip's wavefront slots only that way.
-// Returns the number of terms (= the powers of y of amdzk_pk::d_ypow that the OP_WACC instructions point at).
-constexpr uint32_t H_PARTS_MAX = 8;
-uint32_t finalize_limb_program(Program& pr, uint32_t nparts = 1) {
-  const double LIM = 160.0, RED = 1.01, GROUP_LIM = 169.0 * 30.0;  // a flushed group stays below ~31 p (+ h, canonical)
-  struct Term {
-    std::vector<uint32_t> words;
-    double bound = 0;
-    uint32_t index = 0, group = 4;
-  };
-  std::vector<Term> terms;
-  std::vector<uint32_t> tail;  // programs without OP_ACC (OP_STORE only) keep their order
-  std::vector<uint32_t> out;
-  std::vector<double> st;  // bounds, st.back() = top of stack
-  auto emit = [&](uint32_t op, uint32_t arg = 0) { out.push_back((op << 24) | (arg & 0xffffffu)); };
-  auto reduce_tos = [&]() {
-    emit(OP_REDUCE);
-    st.back() = RED;
-  };
-  uint32_t depth = 0, nterms = 0;
-  for (size_t wi = 0; wi < pr.words.size(); wi++) {
-    const uint32_t w = pr.words[wi], op = w >> 24, arg = w & 0xffffffu;
-    switch (op) {
-      case OP_PUSH_COL:
-      case OP_PUSH_CONST:
-      case OP_PUSH_HOT:
-        if (!st.empty() && st.back() > 8.0) reduce_tos();
-        emit(op, arg);
-        st.push_back(1.0);
-        break;
-      case OP_MUL_HOT:
-        // the closing `* hot[k]` of a term is factored out of its group instead of being multiplied in
-        if (st.size() == 1 && wi + 1 < pr.words.size() && (pr.words[wi + 1] >> 24) == OP_ACC) {
-          Term t;
-          t.group = arg;
-          t.bound = st.back();
-          t.index = nterms++;
-          t.words.swap(out);
-          terms.push_back(std::move(t));
-          st.clear();
-          wi++;  // the OP_ACC is consumed
-          break;
-        }
-        [[fallthrough]];
-      case OP_MUL_COL:
-      case OP_MUL_CONST:
-        if (st.back() >= LIM) reduce_tos();
-        emit(op, arg);
-        st.back() = 2.0;
-        break;
-      case OP_ADD_COL:
-      case OP_ADD_CONST:
-        if (st.back() + 1.0 > 40.0) reduce_tos();
-        emit(op, arg);
-        st.back() += 1.0;
-        break;
-      case OP_SUB_COL:
-        if (st.back() + 3.0 > 40.0) reduce_tos();
-        emit(op, arg);
-        st.back() += 3.0;
-        break;
-      case OP_ADD: {
-        if (st[st.size() - 2] + st.back() > 40.0) reduce_tos();
-        const double b = st.back();
-        st.pop_back();
-        emit(op);
-        st.back() += b;
-      } break;
-      case OP_SUB: {
-        if (st.back() >= 9.0) reduce_tos();
-        const double b = st.back();
-        st.pop_back();
-        emit(b < 2.0 ? OP_SUB : OP_SUB_BIG);
-        st.back() += b < 2.0 ? 3.0 : 10.0;
-      } break;
-      case OP_MUL: {
-        if (st[st.size() - 2] * st.back() >= LIM) reduce_tos();
-        st.pop_back();
-        emit(op);
-        st.back() = 2.0;
-      } break;
-      case OP_NEG:
-        if (st.back() >= 9.0) reduce_tos();
-        emit(st.back() < 2.0 ? OP_NEG : OP_NEG_BIG);
-        st.back() = st.back() < 2.0 ? 3.0 : 10.0;
-        break;
-      case OP_SQR:
-        if (st.back() * st.back() >= LIM) reduce_tos();
-        emit(op);
-        st.back() = 2.0;
-        break;
-      case OP_ACC: {  // end of a term without a hot factor
-        Term t;
-        t.group = 4;
-        t.bound = st.back();
-        t.index = nterms++;
-        t.words.swap(out);
-        terms.push_back(std::move(t));
-        st.clear();
-      } break;
-      case OP_STORE:
-        if (st.back() >= 2.0) reduce_tos();
-        emit(op, arg);
-        st.pop_back();
-        tail.insert(tail.end(), out.begin(), out.end());
-        out.clear();
-        break;
-      case OP_PICK:  // a copy of the entry `arg` below the top; the top sinks into the LDS stack
-        if (st.back() > 8.0) reduce_tos();
-        emit(op, arg);
-        st.push_back(st[st.size() - 1 - arg]);
-        break;
-      case OP_NIP:
-        emit(op, arg);
-        st.erase(st.end() - 1 - arg, st.end() - 1);
-        break;
-      default:
-        emit(op, arg);
-        break;
-    }
-    if (st.size() > depth) depth = (uint32_t)st.size();
-  }
-  tail.insert(tail.end(), out.begin(), out.end());
-  std::vector<uint32_t> fin;
-  bool first = true;
-  auto flush = [&](uint32_t g) {
-    fin.push_back((OP_WFLUSH << 24) | g | (first ? 16u : 0u));
-    first = false;
-  };
-  size_t term_words = 0;
-  for (const Term& t : terms) term_words += t.words.size() + 1;
-  if (terms.empty() || !tail.empty()) nparts = 1;  // (programs that store columns are not cut)
-  pr.piece_starts.clear();
-  uint32_t part = 0;
-  size_t part_begin = 0;
-  if (nparts > 1) pr.piece_starts.push_back(0);
-  for (uint32_t g = 0; g <= 4; g++) {
-    double sum = 0;
-    uint32_t since_carry = 0;
-    bool open = false;
-    for (const Term& t : terms) {
-      if (t.group != g) continue;
-      if (open && sum + t.bound > GROUP_LIM) {
-        flush(g);
-        sum = 0;
-        since_carry = 0;
-        open = false;
-      }
-      // the next piece starts where this one has its share of the instructions
-      if (part + 1 < nparts && fin.size() - part_begin >= (term_words + nparts - 1) / nparts) {
-        if (open) flush(g);
-        sum = 0;
-        since_carry = 0;
-        open = false;
-        part++;
-        part_begin = fin.size();
-        pr.piece_starts.push_back((uint32_t)fin.size());
-        first = true;
-      }
-      fin.insert(fin.end(), t.words.begin(), t.words.end());
-      const bool carry = ++since_carry == 6;  // a column holds six un-carried terms
-      if (carry) since_carry = 0;
-      fin.push_back((OP_WACC << 24) | (carry ? 1u << 23 : 0u) | t.index);
-      sum += t.bound;
-      open = true;
-    }
-    if (open) flush(g);
-  }
-  fin.insert(fin.end(), tail.begin(), tail.end());
-  pr.words.swap(fin);
-  pr.depth = depth + 1;
-  return nterms;
-}
-
-// d_consts261[i] = 32 * consts[i] in the ordinary form, i.e. consts[i] in radix 2^261 (a few hundred values).
-int upload_consts261(amdzk_ctx* ctx, amdzk_pk* pk) {
-  Fr k32 = Fr::one();
-  for (int i = 0; i < 5; i++) k32 = add(k32, k32);
-  std::vector<Fr> c(pk->consts.size());
-  for (size_t i = 0; i < c.size(); i++) c[i] = mul(pk->consts[i], k32);
-  ZK_TRY(h2d_staged(ctx, pk, pk->d_consts261, c.data(), c.size() * 32));
-  // without the pinned staging area the copy above reads `c` asynchronously: finish it before `c` goes away
-  if (!pk->pin || c.size() * 32 > pk->pin_cap) ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
-  return AMDZK_OK;
-}
-
-// d_ypow[j] = y^(K-1-j) for the K terms of the h(X) program, radix 2^261 (upstream folds the constraint values with
-// Horner, h = h*y + value, in the same order: term j carries y^(K-1-j)).
-int upload_ypow(amdzk_ctx* ctx, amdzk_pk* pk) {
-  const uint32_t K = pk->h_terms;
-  if (!K) return AMDZK_OK;
-  Fr k32 = Fr::one();
-  for (int i = 0; i < 5; i++) k32 = add(k32, k32);
-  std::vector<Fr> pw(K);
-  Fr cur = k32;
-  const Fr y = pk->consts[pk->c_y], beta = pk->consts[pk->c_beta];
-  std::vector<Fr> bpow = {Fr::one()};  // beta^m for the terms whose factor beta^m was taken out (the permutation products)
-  for (uint32_t j = K; j-- > 0;) {
-    const uint32_t m = j < pk->h_term_beta_pow.size() ? pk->h_term_beta_pow[j] : 0;
-    while (bpow.size() <= m) bpow.push_back(mul(bpow.back(), beta));
-    pw[j] = m ? mul(cur, bpow[m]) : cur;
-    cur = mul(cur, y);
-  }
-  ZK_TRY(h2d_staged(ctx, pk, pk->d_ypow, pw.data(), pw.size() * 32));
-  if (!pk->pin || pw.size() * 32 > pk->pin_cap) ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
-  return AMDZK_OK;
-}
-
-// Resolve slots / rotation indices / constant indices into addresses and row offsets for one domain
-// and upload the 16-byte instructions.
-int upload_program(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, bool extended) {
-  const std::vector<const Fr*>& cols = extended ? pk->h_cols_ext : pk->h_cols_lag;
-  // The interpreters fetch every instruction's operand, and the instruction two ahead, unconditionally: an
-  // instruction without an operand names the first constant, and two END instructions close the program.
-  const Fr* dummy = extended ? pk->d_consts261 : pk->d_consts;
-  std::vector<ExprInstr> ins(pr.words.size() + 2);
-  for (size_t i = 0; i < ins.size(); i++) {
-    const uint32_t w = i < pr.words.size() ? pr.words[i] : (uint32_t)OP_END << 24, op = w >> 24, arg = w & 0xffffffu;
-    ins[i].op_arg = w;
-    ins[i].rot = 0;
-    ins[i].ptr = dummy;
-    if (op == OP_PUSH_COL || op == OP_MUL_COL || op == OP_ADD_COL || op == OP_SUB_COL) {
-      if ((arg >> 8) >= cols.size() || (arg & 0xff) >= pk->rots.rots.size()) ZK_FAIL(ctx, AMDZK_E_INVALID, "program: bad column operand");
-      ins[i].ptr = cols[arg >> 8];
-      ins[i].rot = pk->rots.rots[arg & 0xff];  // rows of one coset are consecutive: a rotation is a row offset in both domains
-    } else if (op == OP_PUSH_CONST || op == OP_MUL_CONST || op == OP_ADD_CONST) {
-      if (arg >= pk->consts.size()) ZK_FAIL(ctx, AMDZK_E_INVALID, "program: bad constant operand");
-      ins[i].ptr = (extended ? pk->d_consts261 : pk->d_consts) + arg;
-    } else if (op == OP_WACC) {
-      if (!extended || (arg & 0x7fffffu) >= pk->h_terms) ZK_FAIL(ctx, AMDZK_E_INVALID, "program: bad power of y");
-      ins[i].ptr = pk->d_ypow + (arg & 0x7fffffu);
-    }
-  }
-  ZK_TRY(dalloc(ctx, pk, &pr.d_instr, ins.size()));
-  ZK_TRY(h2d(ctx, pr.d_instr, ins.data(), ins.size() * sizeof(ExprInstr)));
-  ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));  // `ins` is a host temporary
-  return AMDZK_OK;
-}
-
-// the launch arguments of a program of this key: its pieces, its column table, where it stores
-int program_args(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, bool extended, Fr* const* d_outs, Fr* h_out, ExprArgs& a) {
-  a.prog = pr.d_instr;
-  a.prog_len = (uint32_t)pr.words.size();
-  a.cols = extended ? pk->d_cols_ext : pk->d_cols_lag;
-  a.outs = d_outs;
-  a.h_out = h_out;
-  a.nrows = extended ? pk->ext : pk->n;
-  a.mask = pk->n - 1;
-  // Quotient-domain programs (h(X), l_active) run in radix 2^261: their columns come from
-  // zk_coeff_to_cosets_r261, their constants from d_consts261, and the result goes back through
-  // zk_cosets_to_pieces. Lagrange-domain programs read the caller's radix-2^256 witness as is.
-  a.radix261 = extended ? 1u : 0u;
-  a.nparts = 0;
-  if (!extended && pr.piece_starts.size() > 1) {  // balanced by instruction count, cut at piece boundaries only
-    const uint32_t total = (uint32_t)pr.words.size(), want = std::min<uint32_t>(EXPR_MAX_PARTS, (uint32_t)pr.piece_starts.size());
-    uint32_t begin = 0;
-    for (size_t i = 1; i <= pr.piece_starts.size() && a.nparts < want; i++) {
-      const uint32_t end = i < pr.piece_starts.size() ? pr.piece_starts[i] : total;
-      const bool last_part = a.nparts + 1 == want;
-      if ((!last_part && end >= (uint64_t)total * (a.nparts + 1) / want) || (last_part && end == total)) {
-        a.part_start[a.nparts] = begin;
-        a.part_len[a.nparts] = end - begin;
-        a.nparts++;
-        begin = end;
-      }
-    }
-    if (begin != total) a.nparts = 0;  // (cannot happen: the last part runs to the end) — fall back to one part
-  }
-  if (extended && pr.piece_starts.size() > 1) {  // the pieces finalize_limb_program cut: one per blockIdx.y, h_out + p * rows each
-    if (pr.piece_starts.size() > (size_t)EXPR_MAX_PARTS) ZK_FAIL(ctx, AMDZK_E_INVALID, "program: too many pieces");
-    for (size_t i = 0; i < pr.piece_starts.size(); i++) {
-      a.part_start[i] = pr.piece_starts[i];
-      a.part_len[i] = (i + 1 < pr.piece_starts.size() ? pr.piece_starts[i + 1] : (uint32_t)pr.words.size()) - pr.piece_starts[i];
-    }
-    a.nparts = (uint32_t)pr.piece_starts.size();
-  }
-  for (int i = 0; i < EXPR_HOT; i++) a.hot[i] = EXPR_NO_SLOT;
-  if (extended && pr.uses_hot) {
-    a.hot[0] = pk->se_l0();
-    a.hot[1] = pk->se_llast();
-    a.hot[2] = pk->se_lactive();
-    a.hot[3] = pk->se_x();
-  }
-  return AMDZK_OK;
-}
-
-int run_program(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, bool extended, Fr* const* d_outs, Fr* h_out, const char* name) {
-  ExprArgs a;
-  ZK_TRY(program_args(ctx, pk, pr, extended, d_outs, h_out, a));
-  // LDS stack slots: the limb interpreter keeps the top of the stack in registers, so a program whose stack holds at most
-  // pr.depth - 1 values (finalize_limb_program) needs pr.depth - 2 slots: pr.depth - 1 leaves one spare
-  return extended ? zk_expr_eval_limbs(ctx, a, pr.depth > 1 ? pr.depth - 1 : 1, name) : zk_expr_eval(ctx, a, pr.depth + 1, name);
-}
 
 Fr rotate_omega(const amdzk_pk* pk, const Fr& x, int rot) {
   return rot >= 0 ? mul(x, pow_u64(pk->omega, (uint64_t)rot)) : mul(x, pow_u64(pk->omega_inv, (uint64_t)(-rot)));
@@ -928,6 +168,12 @@ void trace_pt(const char* label, const G1Affine& p) {
 
 }  // namespace
 
+int commit_cols(amdzk_ctx* ctx, amdzk_pk* pk, int basis, const Fr* d_cols, size_t ncols, std::vector<G1Affine>& out) {
+  PendingCommit pc;
+  ZK_TRY(commit_launch(ctx, pk, basis, d_cols, ncols, pc));
+  return commit_finish(pc, out);
+}
+
 // plonk::evaluation::Evaluator::evaluate_h + divide_by_vanishing_poly + extended_to_coeff + the split into pieces
 // (SURVEY.md §8(a) rows a6, a7, a10): from the committed polynomials in coefficient form (pk->PQ, arena order) and the
 // challenges in pk->consts to the degree-1 pieces of h(X) in pk->hpieces. The numerator is evaluated on nc cosets of
@@ -945,729 +191,6 @@ static int quotient_pieces(amdzk_ctx* ctx, amdzk_pk* pk) {
   ZK_TRY(zk_coeff_to_cosets_r261(ctx, pk->dom, pk->PQ, pk->n, pk->PC, pk->ext, pk->NP));
   return quotient_from_cosets(ctx, pk);
 }
-
-// The per-proof workspace of ONE circuit instance (arenas, lookup / product scratch, multiopen buffers, small staging):
-// what a key owns besides its key material, and all a workspace clone allocates.
-static int alloc_proof_workspace(amdzk_ctx* ctx, amdzk_pk* pk) {
-  const size_t n = pk->n, ext = pk->ext;
-  const uint32_t A = pk->A, I = pk->I, L = pk->L, ns = pk->nsets;
-#define KG_TRY(x) ZK_TRY(x)
-  pk->NP = (size_t)A + I + 2 * L + ns + L;
-  KG_TRY(dalloc(ctx, pk, &pk->P, pk->NP * n));
-  KG_TRY(dalloc(ctx, pk, &pk->PQ, pk->NP * n));
-  KG_TRY(dalloc(ctx, pk, &pk->PC, pk->NP * ext));
-  KG_TRY(dalloc(ctx, pk, &pk->ci, (size_t)L * n));
-  KG_TRY(dalloc(ctx, pk, &pk->ct, (size_t)L * n));
-  KG_TRY(dalloc(ctx, pk, &pk->lk_ts, (size_t)L * n));
-  KG_TRY(dalloc(ctx, pk, &pk->lk_left, (size_t)L * n));
-  KG_TRY(dalloc(ctx, pk, &pk->lk_flags, (size_t)4 * L * (n + 8)));
-  KG_TRY(dalloc(ctx, pk, &pk->d_err, 1));
-  KG_TRY(dalloc(ctx, pk, &pk->rnd, n));
-  KG_TRY(dalloc(ctx, pk, &pk->hq, (size_t)H_PARTS_MAX * ext));  // one h per piece of the cut h(X) program (finalize_limb_program)
-  KG_TRY(dalloc(ctx, pk, &pk->hpieces, (size_t)pk->qdeg * n));
-  KG_TRY(dalloc(ctx, pk, &pk->hpoly, n));
-  const size_t nfrac = std::max<size_t>(std::max<size_t>(ns, L), 1);
-  KG_TRY(dalloc(ctx, pk, &pk->frac, nfrac * n));
-  KG_TRY(dalloc(ctx, pk, &pk->scratch, std::max(nfrac * n, ext)));
-  KG_TRY(dalloc(ctx, pk, &pk->scan_tmp, zk_scan_totals_elems(n, nfrac) + 2 * nfrac + 8));
-  KG_TRY(dalloc(ctx, pk, &pk->frac2, std::max<size_t>(L, 1) * n));
-  KG_TRY(dalloc(ctx, pk, &pk->scratch2, std::max<size_t>(L, 1) * n));
-  KG_TRY(dalloc(ctx, pk, &pk->scan_tmp2, zk_scan_totals_elems(n, std::max<size_t>(L, 1)) + 2 * std::max<size_t>(L, 1) + 8));
-  const size_t max_rsets = pk->max_sets;
-  KG_TRY(dalloc(ctx, pk, &pk->sets_L, max_rsets * n));
-  KG_TRY(dalloc(ctx, pk, &pk->sets_N, max_rsets * n));
-  KG_TRY(dalloc(ctx, pk, &pk->hx, n));
-  pk->small_cap = std::max<size_t>((size_t)pk->NP * (pk->bf + 2) + 4096, 8192);
-  for (int l = 0; l < 3; l++) KG_TRY(dalloc(ctx, pk, &pk->small_l[l], pk->small_cap));
-  pk->small = pk->small_l[0];
-  pk->pin_cap = std::max<size_t>((size_t)8 << 20, 2 * n * 32);
-  if (hipHostMalloc((void**)&pk->pin, pk->pin_cap + 64, hipHostMallocDefault) != hipSuccess) {
-    pk->pin = nullptr;
-    pk->pin_cap = 0;
-    ZK_FAIL(ctx, AMDZK_E_NOMEM, "prover: hipHostMalloc of the pinned staging area failed");
-  }
-  pk->h_err = (int*)(pk->pin + pk->pin_cap);  // behind the staging ring
-  pk->ptrs_cap = 8192;
-  for (int l = 0; l < 3; l++) {
-    void** pp = nullptr;
-    KG_TRY(dalloc(ctx, pk, &pp, pk->ptrs_cap));
-    pk->ptrs_l[l] = pp;
-  }
-  pk->ptrs = pk->ptrs_l[0];
-
-#undef KG_TRY
-  return AMDZK_OK;
-}
-
-// The slot -> column pointer tables the interpreters read (Lagrange and quotient domain): key columns and this
-// workspace's arenas.
-static int build_column_tables(amdzk_ctx* ctx, amdzk_pk* pk) {
-  const size_t n = pk->n, ext = pk->ext;
-  const uint32_t F = pk->F, A = pk->A, I = pk->I, S = pk->S, L = pk->L, ns = pk->nsets;
-#define KG_TRY(x) ZK_TRY(x)
-  // ---- column pointer tables
-  {
-    std::vector<const Fr*> lag(pk->nslots_lag()), ex(pk->nslots_ext());
-    for (uint32_t i = 0; i < F; i++) lag[pk->sl_fixed(i)] = pk->fixed_lag + (size_t)i * n, ex[i] = pk->fixed_coset + (size_t)i * ext;
-    for (uint32_t i = 0; i < A; i++) lag[pk->sl_adv(i)] = pk->adv() + (size_t)i * n, ex[pk->sl_adv(i)] = pk->PC + (size_t)i * ext;
-    for (uint32_t i = 0; i < I; i++) lag[pk->sl_inst(i)] = pk->inst() + (size_t)i * n, ex[pk->sl_inst(i)] = pk->PC + (size_t)(A + i) * ext;
-    for (uint32_t i = 0; i < S; i++) lag[pk->sl_sigma(i)] = pk->sigma_lag + (size_t)i * n, ex[pk->se_sigma(i)] = pk->sigma_coset + (size_t)i * ext;
-    for (uint32_t i = 0; i < S; i++) lag[pk->sl_dxw(i)] = pk->dxw_lag + (size_t)i * n, ex[pk->se_dx(i)] = pk->dx_coset + (size_t)i * ext;
-    for (uint32_t l = 0; l < L; l++) {
-      lag[pk->sl_ci(l)] = pk->ci + (size_t)l * n;
-      lag[pk->sl_ct(l)] = pk->ct + (size_t)l * n;
-      lag[pk->sl_la(l)] = pk->la() + (size_t)l * n;
-      lag[pk->sl_ls(l)] = pk->ls() + (size_t)l * n;
-      ex[pk->se_la(l)] = pk->PC + (size_t)(A + I + l) * ext;
-      ex[pk->se_ls(l)] = pk->PC + (size_t)(A + I + L + l) * ext;
-      ex[pk->se_zl(l)] = pk->PC + (size_t)(A + I + 2 * L + ns + l) * ext;
-    }
-    for (uint32_t s = 0; s < ns; s++) ex[pk->se_zp(s)] = pk->PC + (size_t)(A + I + 2 * L + s) * ext;
-    lag[pk->sl_omega()] = pk->omega_pow;
-    ex[pk->se_l0()] = pk->l0_c;
-    ex[pk->se_llast()] = pk->llast_c;
-    ex[pk->se_lactive()] = pk->lactive_c;
-    ex[pk->se_x()] = pk->x_coset;
-    pk->h_cols_lag = lag;
-    pk->h_cols_ext = ex;
-    KG_TRY(dalloc(ctx, pk, &pk->d_cols_lag, lag.size()));
-    KG_TRY(dalloc(ctx, pk, &pk->d_cols_ext, ex.size()));
-    KG_TRY(h2d(ctx, pk->d_cols_lag, lag.data(), lag.size() * sizeof(Fr*)));
-    KG_TRY(h2d(ctx, pk->d_cols_ext, ex.data(), ex.size() * sizeof(Fr*)));
-    ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
-  }
-
-#undef KG_TRY
-  return AMDZK_OK;
-}
-
-// Where the Lagrange-domain programs store: compressed lookup inputs / tables, permutation fractions, lookup fractions.
-static int build_output_tables(amdzk_ctx* ctx, amdzk_pk* pk) {
-  const size_t n = pk->n;
-  const uint32_t L = pk->L, ns = pk->nsets;
-  {
-    std::vector<Fr*> outs(2 * L);
-    for (uint32_t l = 0; l < L; l++) outs[2 * l] = pk->ci + (size_t)l * n, outs[2 * l + 1] = pk->ct + (size_t)l * n;
-    ZK_TRY(dalloc(ctx, pk, &pk->d_outs_compress, outs.size()));
-    ZK_TRY(h2d(ctx, pk->d_outs_compress, outs.data(), outs.size() * sizeof(Fr*)));
-    ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
-  }
-  {
-    std::vector<Fr*> outs(2 * ns);
-    for (uint32_t s = 0; s < ns; s++) outs[2 * s] = pk->frac + (size_t)s * n, outs[2 * s + 1] = pk->zp() + (size_t)s * n;
-    ZK_TRY(dalloc(ctx, pk, &pk->d_outs_pfrac, outs.size()));
-    ZK_TRY(h2d(ctx, pk->d_outs_pfrac, outs.data(), outs.size() * sizeof(Fr*)));
-    ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
-  }
-  {
-    std::vector<Fr*> outs(2 * L);
-    for (uint32_t l = 0; l < L; l++) outs[2 * l] = pk->frac2 + (size_t)l * n, outs[2 * l + 1] = pk->zl() + (size_t)l * n;  // frac2: beside the permutation products
-    ZK_TRY(dalloc(ctx, pk, &pk->d_outs_lfrac, outs.size()));
-    ZK_TRY(h2d(ctx, pk->d_outs_lfrac, outs.data(), outs.size() * sizeof(Fr*)));
-    ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
-  }
-  return AMDZK_OK;
-}
-
-extern "C" {
-
-void amdzk_pk_free(amdzk_ctx* ctx, amdzk_pk* pk) {
-  ZK_ENTER(ctx);
-  if (!pk) return;
-  if (ctx) zk_host_wait(ctx, ctx->stream);
-  for (void* p : pk->allocs) hipFree(p);
-  if (!pk->clone_of && pk->chk_shared && pk->chk_shared->d_cells) hipFree(pk->chk_shared->d_cells);
-  if (pk->pin) hipHostFree(pk->pin);
-  if (pk->dom && !pk->clone_of) amdzk_domain_free(ctx, pk->dom);
-  delete pk;
-}
-
-// Every device allocation of the key (columns, cosets, per-proof workspace) must live on ctx's device.
-int amdzk_pk_check_affinity(amdzk_ctx* ctx, const amdzk_pk* pk) {
-  ZK_ENTER(ctx);
-  if (!ctx || !pk) return AMDZK_E_INVALID;
-  for (void* p : pk->allocs) ZK_TRY(zk_ptr_on_device(ctx, p, "proving-key buffer"));
-  return AMDZK_OK;
-}
-
-// keygen with the environment's defaults for the key's modes (AMDZK_FULL_COSETS, AMDZK_SERIAL); amdzk_keygen_ex takes
-// them as explicit flags, so that two keys of one process can differ.
-int amdzk_keygen(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* c, const uint64_t* fixed_values, const uint32_t* perm_mapping,
-                 const uint64_t transcript_repr[4], amdzk_pk** out) {
-  uint32_t flags = 0;
-  if (const char* e = getenv("AMDZK_FULL_COSETS")) flags |= atoi(e) != 0 || !*e ? AMDZK_KEYGEN_FULL_COSETS : 0u;
-  if (const char* e = getenv("AMDZK_SERIAL")) flags |= atoi(e) != 0 ? AMDZK_KEYGEN_SERIAL : 0u;
-  return amdzk_keygen_ex(ctx, srs, c, fixed_values, perm_mapping, transcript_repr, flags, out);
-}
-
-int amdzk_keygen_ex(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* c, const uint64_t* fixed_values, const uint32_t* perm_mapping,
-                    const uint64_t transcript_repr[4], uint32_t flags, amdzk_pk** out) {
-  return amdzk_keygen_phased(ctx, srs, c, nullptr, fixed_values, perm_mapping, transcript_repr, flags, out);
-}
-
-// keygen with ConstraintSystem::{advice_column_in, challenge_usable_after}'s phase table (NULL: every column in phase 0,
-// no challenges). The table is checked the way upstream's two functions assert, before anything is allocated.
-// One of perm_mapping (Assembly::mapping: the sigma values are computed here) and sigma_values (the Lagrange values
-// themselves, amdzk_keygen_sigma / amdzk_pk_read) feeds the permutation columns; everything behind their upload is shared.
-// fixed_values / sigma_values are only copied to the device: any alignment (amdzk_pk_read passes pointers into the file).
-static int keygen_common(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* c, const amdzk_phases* ph, const void* fixed_values,
-                         const uint32_t* perm_mapping, const void* sigma_values, bool from_sigma, const uint64_t transcript_repr[4],
-                         uint32_t flags, amdzk_pk** out);
-
-int amdzk_keygen_phased(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* c, const amdzk_phases* ph, const uint64_t* fixed_values,
-                        const uint32_t* perm_mapping, const uint64_t transcript_repr[4], uint32_t flags, amdzk_pk** out) {
-  return keygen_common(ctx, srs, c, ph, fixed_values, perm_mapping, nullptr, false, transcript_repr, flags, out);
-}
-
-// keygen from the sigma columns (permutation::ProvingKey::permutations, Lagrange form) instead of the mapping: what a
-// process that has read a cached key holds. The values are taken as they are (upstream's read does not check them either).
-int amdzk_keygen_sigma(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* c, const amdzk_phases* ph, const uint64_t* fixed_values,
-                       const uint64_t* sigma_values, const uint64_t transcript_repr[4], uint32_t flags, amdzk_pk** out) {
-  return keygen_common(ctx, srs, c, ph, fixed_values, nullptr, sigma_values, true, transcript_repr, flags, out);
-}
-
-static int keygen_common(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* c, const amdzk_phases* ph, const void* fixed_values,
-                         const uint32_t* perm_mapping, const void* sigma_values, bool from_sigma, const uint64_t transcript_repr[4],
-                         uint32_t flags, amdzk_pk** out) {
-  ZK_ENTER(ctx);
-  if (!ctx) return AMDZK_E_INVALID;
-  uint32_t nphases = 1;
-  if (ph && c) {
-    if ((c->num_advice && !ph->advice_phase) || (ph->num_challenges && !ph->challenge_phase))
-      ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: phase table has a null array");
-    bool has[3] = {false, false, false};
-    for (uint32_t a = 0; a < c->num_advice; a++) {
-      if (ph->advice_phase[a] > 2) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: advice column %u is in phase %u (phases are 0, 1, 2)", a, ph->advice_phase[a]);
-      has[ph->advice_phase[a]] = true;
-    }
-    for (uint32_t p = 1; p < 3; p++)
-      if (has[p]) {
-        if (!has[p - 1]) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: phase %u has advice columns but phase %u has none", p, p - 1);
-        nphases = p + 1;
-      }
-    for (uint32_t i = 0; i < ph->num_challenges; i++) {
-      const uint32_t p = ph->challenge_phase[i];
-      if (p > 2) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: challenge %u is usable after phase %u (phases are 0, 1, 2)", i, p);
-      if (!has[p]) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: challenge %u is usable after phase %u, which has no advice column", i, p);
-    }
-    if (c->expr_offsets && c->expr_words)
-      for (uint32_t i = 0; i < c->expr_offsets[c->num_exprs]; i++)
-        if ((c->expr_words[i] >> 24) == XOP_CHALLENGE && (c->expr_words[i] & 0xffffffu) >= ph->num_challenges)
-          ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: challenge index %u out of range (num_challenges = %u)", c->expr_words[i] & 0xffffffu,
-                  ph->num_challenges);
-  }
-  if (flags & ~(uint32_t)(AMDZK_KEYGEN_FULL_COSETS | AMDZK_KEYGEN_SERIAL)) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: unknown flags %#x", flags);
-  if (!srs || !c || !out || !transcript_repr) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: null argument");
-  if (c->cs_degree < 3) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: cs_degree %u < 3", c->cs_degree);
-  amdzk_pk* pk = new amdzk_pk();
-#define KG_TRY(x)                  \
-  do {                             \
-    int _r = (x);                  \
-    if (_r != AMDZK_OK) {          \
-      amdzk_pk_free(ctx, pk);      \
-      return _r;                   \
-    }                              \
-  } while (0)
-  pk->srs = srs;
-  pk->chk_shared = std::make_shared<amdzk_pk::CheckShared>();
-  pk->k = c->k;
-  pk->n = (size_t)1 << c->k;
-  pk->bf = c->blinding_factors;
-  pk->degree = c->cs_degree;
-  pk->F = c->num_fixed;
-  pk->A = c->num_advice;
-  pk->I = c->num_instance;
-  pk->S = c->num_perm_columns;
-  pk->L = c->num_lookups;
-  pk->chunk = pk->degree - 2;
-  pk->nsets = (pk->S + pk->chunk - 1) / pk->chunk;
-  pk->qdeg = pk->degree - 1;
-  if (pk->S) KG_TRY(zk_srs_ensure_prefix(ctx, srs));  // the permutation products are committed over it (Prover::perm_commit)
-  if (ph) {
-    pk->nphases = nphases;
-    pk->num_challenges = ph->num_challenges;
-    pk->advice_phase.assign(ph->advice_phase, ph->advice_phase + (c->num_advice ? c->num_advice : 0));
-    pk->challenge_phase.assign(ph->challenge_phase, ph->challenge_phase + ph->num_challenges);
-  }
-  if (pk->n < pk->bf + 3) {
-    amdzk_pk_free(ctx, pk);
-    ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: not enough rows (n = %zu, blinding factors = %u)", pk->n, pk->bf);
-  }
-  memcpy(pk->transcript_repr.l, transcript_repr, 32);
-  KG_TRY(amdzk_domain_new(ctx, pk->degree, pk->k, &pk->dom));
-  pk->ek = amdzk_domain_extended_k(pk->dom);
-  // h(X) has qdeg = degree - 1 pieces: that many cosets pin it down (AMDZK_FULL_COSETS=1: all 2^(ek-k), upstream's own
-  // computation — identical output for satisfying witnesses, and the way to reproduce upstream's bytes for others)
-  pk->nc = (flags & AMDZK_KEYGEN_FULL_COSETS) ? (1u << (pk->ek - pk->k)) : pk->qdeg;
-  pk->use_lanes = !(flags & AMDZK_KEYGEN_SERIAL);
-  KG_TRY(zk_quotient_plan(ctx, pk->dom, pk->nc));
-  pk->ext = (size_t)pk->nc * pk->n;
-  amdzk_domain_constant(pk->dom, 0, (uint64_t*)pk->omega.l);
-  amdzk_domain_constant(pk->dom, 1, (uint64_t*)pk->omega_inv.l);
-  for (uint32_t i = 0; i < c->num_advice_queries; i++) pk->advice_queries.push_back({c->advice_queries[2 * i], c->advice_queries[2 * i + 1]});
-  for (uint32_t i = 0; i < c->num_fixed_queries; i++) pk->fixed_queries.push_back({c->fixed_queries[2 * i], c->fixed_queries[2 * i + 1]});
-  for (uint32_t i = 0; i < c->num_instance_queries; i++)
-    pk->instance_queries.push_back({c->instance_queries[2 * i], c->instance_queries[2 * i + 1]});
-  for (uint32_t i = 0; i < pk->S; i++) pk->perm_cols.push_back({(int)c->perm_columns[2 * i], (int)c->perm_columns[2 * i + 1]});
-  pk->num_gates = c->num_gates;
-  uint32_t nexpr = c->num_gates;
-  for (uint32_t l = 0; l < pk->L; l++) {
-    pk->lookup_shape.push_back({c->lookup_shape[2 * l], c->lookup_shape[2 * l + 1]});
-    nexpr += c->lookup_shape[2 * l] + c->lookup_shape[2 * l + 1];
-  }
-  if (nexpr != c->num_exprs) {
-    amdzk_pk_free(ctx, pk);
-    ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: expression count mismatch (%u vs %u)", nexpr, c->num_exprs);
-  }
-  for (uint32_t e = 0; e < c->num_exprs; e++)
-    pk->exprs.emplace_back(c->expr_words + c->expr_offsets[e], c->expr_words + c->expr_offsets[e + 1]);
-  {
-    auto desc = std::make_shared<pkblob::Desc>();
-    desc->assign(*c, ph);
-    pk->src_desc = desc;
-  }
-  // constants: circuit | one theta beta gamma y 1/beta
-  pk->consts.resize(c->num_constants);
-  if (c->num_constants) memcpy(pk->consts.data(), c->constants, (size_t)c->num_constants * 32);
-  pk->c_one = c->num_constants;
-  pk->c_theta = pk->c_one + 1;
-  pk->c_beta = pk->c_one + 2;
-  pk->c_gamma = pk->c_one + 3;
-  pk->c_y = pk->c_one + 4;
-  pk->c_betainv = pk->c_one + 5;
-  pk->c_chal0 = pk->c_betainv + 1;
-  pk->consts.resize((size_t)pk->c_chal0 + pk->num_challenges, Fr::zero());
-  pk->consts[pk->c_one] = Fr::one();
-
-  const size_t n = pk->n, ext = pk->ext;
-  const uint32_t F = pk->F, A = pk->A, I = pk->I, S = pk->S, L = pk->L, ns = pk->nsets;
-  // ---- device allocations
-  KG_TRY(dalloc(ctx, pk, &pk->fixed_lag, (size_t)F * n));
-  KG_TRY(dalloc(ctx, pk, &pk->fixed_poly, (size_t)F * n));
-  KG_TRY(dalloc(ctx, pk, &pk->fixed_coset, (size_t)F * ext));
-  KG_TRY(dalloc(ctx, pk, &pk->sigma_lag, (size_t)S * n));
-  KG_TRY(dalloc(ctx, pk, &pk->sigma_poly, (size_t)S * n));
-  KG_TRY(dalloc(ctx, pk, &pk->sigma_coset, (size_t)S * ext));
-  KG_TRY(dalloc(ctx, pk, &pk->l0_c, ext));
-  KG_TRY(dalloc(ctx, pk, &pk->llast_c, ext));
-  KG_TRY(dalloc(ctx, pk, &pk->lactive_c, ext));
-  KG_TRY(dalloc(ctx, pk, &pk->x_coset, ext));
-  KG_TRY(dalloc(ctx, pk, &pk->omega_pow, n));
-  KG_TRY(dalloc(ctx, pk, &pk->dxw_lag, (size_t)S * n));
-  KG_TRY(dalloc(ctx, pk, &pk->dx_coset, (size_t)S * ext));
-  KG_TRY(alloc_proof_workspace(ctx, pk));
-
-  // ---- host-side tables: omega powers, coset points, l0 / l_last / l_blind (Lagrange)
-  {
-    std::vector<Fr> op(n), l0(n, Fr::zero()), ll(n, Fr::zero()), lb(n, Fr::zero());
-    Fr cur = Fr::one();
-    for (size_t i = 0; i < n; i++) {
-      op[i] = cur;
-      cur = mul(cur, pk->omega);
-    }
-    KG_TRY(h2d(ctx, pk->omega_pow, op.data(), n * 32));
-    l0[0] = Fr::one();
-    ll[n - pk->bf - 1] = Fr::one();
-    for (size_t i = n - pk->bf; i < n; i++) lb[i] = Fr::one();
-    // to cosets via the same device path as every other polynomial: pack [l0 | l_last | l_blind] into hq-sized temp
-    Fr* tmp = pk->scratch;  // >= ext >= 3n? ext >= 2n only when degree >= 4; use three separate passes
-    Fr* dst[3] = {pk->l0_c, pk->llast_c, pk->lactive_c};
-    std::vector<Fr>* src[3] = {&l0, &ll, &lb};
-    for (int t = 0; t < 3; t++) {
-      KG_TRY(h2d(ctx, tmp, src[t]->data(), n * 32));
-      KG_TRY(amdzk_lagrange_to_coeff_dev(ctx, pk->dom, tmp, 1, n));
-      KG_TRY(zk_coeff_to_cosets_r261(ctx, pk->dom, tmp, n, dst[t], ext, 1));
-      ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
-    }
-    std::vector<Fr> xc(ext);
-    for (uint32_t c = 0; c < pk->nc; c++) {
-      cur = zk_quotient_coset_g(pk->dom, c);
-      for (int i = 0; i < 5; i++) cur = add(cur, cur);  // 32 * g_c * omega^i: the points of coset c in radix 2^261
-      for (size_t i = 0; i < n; i++) {
-        xc[(size_t)c * n + i] = cur;
-        cur = mul(cur, pk->omega);
-      }
-    }
-    KG_TRY(h2d(ctx, pk->x_coset, xc.data(), ext * 32));
-    ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
-    // the identity permutation: delta^j * omega^i (Lagrange) and delta^j * X on the cosets (same radix as x_coset)
-    Fr dj = Fr::one();
-    const Fr delta = fr_delta();
-    for (uint32_t j = 0; j < S; j++) {
-      KG_TRY(d2d(ctx, pk->dxw_lag + (size_t)j * n, pk->omega_pow, n * 32));
-      KG_TRY(d2d(ctx, pk->dx_coset + (size_t)j * ext, pk->x_coset, ext * 32));
-      if (j) {
-        KG_TRY(zk_scale(ctx, pk->dxw_lag + (size_t)j * n, n, dj));
-        KG_TRY(zk_scale(ctx, pk->dx_coset + (size_t)j * ext, ext, dj));
-      }
-      dj = mul(dj, delta);
-    }
-    ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
-  }
-  // ---- fixed columns and permutation polynomials
-  if (F) {
-    if (!fixed_values) {
-      amdzk_pk_free(ctx, pk);
-      ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: fixed_values is null");
-    }
-    KG_TRY(h2d(ctx, pk->fixed_lag, fixed_values, (size_t)F * n * 32));
-    KG_TRY(d2d(ctx, pk->fixed_poly, pk->fixed_lag, (size_t)F * n * 32));
-    KG_TRY(amdzk_lagrange_to_coeff_dev(ctx, pk->dom, pk->fixed_poly, F, n));
-    KG_TRY(zk_coeff_to_cosets_r261(ctx, pk->dom, pk->fixed_poly, n, pk->fixed_coset, ext, F));
-    KG_TRY(commit_cols(ctx, pk, AMDZK_BASIS_G_LAGRANGE, pk->fixed_lag, F, pk->fixed_commitments));
-  }
-  if (S && from_sigma) {
-    if (!sigma_values) {
-      amdzk_pk_free(ctx, pk);
-      ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: sigma_values is null");
-    }
-    KG_TRY(h2d(ctx, pk->sigma_lag, sigma_values, (size_t)S * n * 32));
-    ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
-  } else if (S) {
-    if (!perm_mapping) {
-      amdzk_pk_free(ctx, pk);
-      ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: perm_mapping is null");
-    }
-    // sigma_i(omega^j) = delta^(i') * omega^(j'), (i', j') = mapping[i][j]
-    std::vector<Fr> dpow(S), op(n), sig((size_t)S * n);
-    Fr delta = fr_delta(), cur = Fr::one();
-    for (uint32_t i = 0; i < S; i++) {
-      dpow[i] = cur;
-      cur = mul(cur, delta);
-    }
-    cur = Fr::one();
-    for (size_t i = 0; i < n; i++) {
-      op[i] = cur;
-      cur = mul(cur, pk->omega);
-    }
-    for (uint32_t i = 0; i < S; i++)
-      for (size_t j = 0; j < n; j++) {
-        uint32_t pi = perm_mapping[2 * ((size_t)i * n + j)], pj = perm_mapping[2 * ((size_t)i * n + j) + 1];
-        if (pi >= S || pj >= n) {
-          amdzk_pk_free(ctx, pk);
-          ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: permutation mapping out of range");
-        }
-        sig[(size_t)i * n + j] = mul(dpow[pi], op[pj]);
-      }
-    KG_TRY(h2d(ctx, pk->sigma_lag, sig.data(), (size_t)S * n * 32));
-    ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
-  }
-  if (S) {  // shared by both routes from here on
-    KG_TRY(d2d(ctx, pk->sigma_poly, pk->sigma_lag, (size_t)S * n * 32));
-    KG_TRY(amdzk_lagrange_to_coeff_dev(ctx, pk->dom, pk->sigma_poly, S, n));
-    KG_TRY(zk_coeff_to_cosets_r261(ctx, pk->dom, pk->sigma_poly, n, pk->sigma_coset, ext, S));
-    KG_TRY(commit_cols(ctx, pk, AMDZK_BASIS_G_LAGRANGE, pk->sigma_lag, S, pk->perm_commitments));
-  }
-  // l_active = 1 - (l_last + l_blind) on the coset: lactive_c currently holds l_blind's coset
-  {
-    // prog: one - l_last - l_blind, stored into lactive_c. Done with a tiny dedicated program below, after tables exist.
-  }
-
-  KG_TRY(build_column_tables(ctx, pk));
-
-  // ---- programs
-  auto colkind_slot_lag = [&](std::pair<int, int> kc) { return kc.first == 0 ? pk->sl_adv(kc.second) : kc.first == 1 ? pk->sl_fixed(kc.second) : pk->sl_inst(kc.second); };
-  const uint32_t r0 = pk->rots.index(0), r1 = pk->rots.index(1), rm1 = pk->rots.index(-1), rlast = pk->rots.index(-(int32_t)(pk->bf + 1));
-  auto COL = [&](uint32_t slot, uint32_t r) { return (slot << 8) | r; };
-  // (1) lookup compression: ci[l], ct[l]. Leading lookups whose table is one expression over fixed columns and constants
-  // (amdzk_pk::lk_const) get ct[l] once, below.
-  {
-    Program& pr = pk->prog_compress;
-    uint32_t e = pk->num_gates;
-    for (uint32_t l = 0; l < L && !getenv("AMDZK_NO_TABLE_CACHE"); l++) {
-      const uint32_t ni = pk->lookup_shape[l].first, nt = pk->lookup_shape[l].second;
-      bool constant = nt == 1;
-      if (constant)
-        for (uint32_t w : pk->exprs[e + ni]) constant = constant && (w >> 24) != XOP_ADVICE && (w >> 24) != XOP_INSTANCE && (w >> 24) != XOP_CHALLENGE;
-      if (!constant) break;
-      pk->lk_const++;
-      e += ni + nt;
-    }
-    e = pk->num_gates;
-    for (uint32_t l = 0; l < L; l++) {
-      pr.piece();
-      KG_TRY(emit_compressed(ctx, pk, pr, e, pk->lookup_shape[l].first));
-      pr.op(OP_STORE, 2 * l);
-      pr.pop();
-      e += pk->lookup_shape[l].first;
-      if (l >= pk->lk_const) {
-        KG_TRY(emit_compressed(ctx, pk, pr, e, pk->lookup_shape[l].second));
-        pr.op(OP_STORE, 2 * l + 1);
-        pr.pop();
-      }
-      e += pk->lookup_shape[l].second;
-    }
-  }
-  // (2) permutation fractions: den[s] -> frac column s (inverted later), num[s] -> zp column s. Per set: the columns'
-  // w_j = (v_j + gamma) / beta stay on the stack and serve both products, prod_j (sigma_j + w_j) and
-  // prod_j (delta^j omega^row + w_j); the common factor beta^m of numerator and denominator cancels in num / den.
-  {
-    Program& pr = pk->prog_pfrac;
-    for (uint32_t s = 0; s < ns; s++) {
-      const uint32_t lo = s * pk->chunk, hi = std::min(S, lo + pk->chunk), m = hi - lo;
-      pr.piece();
-      for (uint32_t j = lo; j < hi; j++) {
-        pr.op(OP_PUSH_COL, COL(colkind_slot_lag(pk->perm_cols[j]), r0));
-        pr.push();
-        pr.op(OP_ADD_CONST, pk->c_gamma);
-        pr.op(OP_MUL_CONST, pk->c_betainv);
-      }
-      for (int side = 0; side < 2; side++) {  // 0: denominator (sigma columns), 1: numerator (identity-permutation columns)
-        for (uint32_t j = lo; j < hi; j++) {
-          // the stack holds the m values w, then (from the second factor on) the running product
-          pr.op(OP_PICK, j == lo ? m - 1 : m - (j - lo));
-          pr.push();
-          pr.op(OP_ADD_COL, COL(side == 0 ? pk->sl_sigma(j) : pk->sl_dxw(j), r0));
-          if (j > lo) {
-            pr.op(OP_MUL);
-            pr.pop();
-          }
-        }
-        if (side == 1) {
-          pr.op(OP_NIP, m);
-          pr.cur -= m;
-        }
-        pr.op(OP_STORE, 2 * s + side);
-        pr.pop();
-      }
-    }
-  }
-  // (3) lookup fractions: den = (a'+beta)(s'+gamma) -> frac2[l]; num = (ci+beta)(ct+gamma) -> zl[l]
-  {
-    Program& pr = pk->prog_lfrac;
-    for (uint32_t l = 0; l < L; l++) {
-      pr.piece();
-      pr.op(OP_PUSH_COL, COL(pk->sl_la(l), r0));
-      pr.push();
-      pr.op(OP_ADD_CONST, pk->c_beta);
-      pr.op(OP_PUSH_COL, COL(pk->sl_ls(l), r0));
-      pr.push();
-      pr.op(OP_ADD_CONST, pk->c_gamma);
-      pr.op(OP_MUL);
-      pr.pop();
-      pr.op(OP_STORE, 2 * l);
-      pr.pop();
-      pr.op(OP_PUSH_COL, COL(pk->sl_ci(l), r0));
-      pr.push();
-      pr.op(OP_ADD_CONST, pk->c_beta);
-      pr.op(OP_PUSH_COL, COL(pk->sl_ct(l), r0));
-      pr.push();
-      pr.op(OP_ADD_CONST, pk->c_gamma);
-      pr.op(OP_MUL);
-      pr.pop();
-      pr.op(OP_STORE, 2 * l + 1);
-      pr.pop();
-    }
-  }
-  // (4) the h(X) numerator: gates, permutation, lookups — evaluation.rs evaluate_h order
-  {
-    Program& pr = pk->prog_h;
-    pr.uses_hot = true;
-    auto colkind_slot_ext = colkind_slot_lag;  // fixed/advice/instance share slot numbers in both tables
-    for (uint32_t g = 0; g < pk->num_gates; g++) {
-      KG_TRY(emit_expr(ctx, pk, pr, pk->exprs[g]));
-      pr.op(OP_ACC);
-      pr.pop();
-    }
-    if (ns > 0) {
-      // l_0 * (1 - z_0)
-      pr.op(OP_PUSH_CONST, pk->c_one); pr.push();
-      pr.op(OP_SUB_COL, COL(pk->se_zp(0), r0));
-      pr.op(OP_MUL_HOT, 0);
-      pr.op(OP_ACC); pr.pop();
-      // l_last * (z_l^2 - z_l)
-      pr.op(OP_PUSH_COL, COL(pk->se_zp(ns - 1), r0)); pr.push();
-      pr.op(OP_SQR);
-      pr.op(OP_SUB_COL, COL(pk->se_zp(ns - 1), r0));
-      pr.op(OP_MUL_HOT, 1);
-      pr.op(OP_ACC); pr.pop();
-      // l_0 * (z_i - z_{i-1}(omega^last X))
-      for (uint32_t s = 1; s < ns; s++) {
-        pr.op(OP_PUSH_COL, COL(pk->se_zp(s), r0)); pr.push();
-        pr.op(OP_SUB_COL, COL(pk->se_zp(s - 1), rlast));
-        pr.op(OP_MUL_HOT, 0);
-        pr.op(OP_ACC); pr.pop();
-      }
-      // l_active * (z_i(omega X) prod(v + beta sigma + gamma) - z_i(X) prod(v + beta delta^j X + gamma))
-      //   = beta^m * l_active * (z_i(omega X) prod(sigma_j + w_j) - z_i(X) prod(delta^j X + w_j)),  w_j = (v_j + gamma) / beta:
-      // the w_j stay on the stack for both products (one product per column instead of two), delta^j X is a key column,
-      // and beta^m goes into the term's power of y (h_term_beta_pow, upload_ypow)
-      for (uint32_t s = 0; s < ns; s++) {
-        const uint32_t lo = s * pk->chunk, hi = std::min(S, lo + pk->chunk), m = hi - lo;
-        for (uint32_t j = lo; j < hi; j++) {
-          pr.op(OP_PUSH_COL, COL(colkind_slot_ext(pk->perm_cols[j]), r0)); pr.push();
-          pr.op(OP_ADD_CONST, pk->c_gamma);
-          pr.op(OP_MUL_CONST, pk->c_betainv);
-        }
-        pr.op(OP_PUSH_COL, COL(pk->se_zp(s), r1)); pr.push();
-        for (uint32_t j = lo; j < hi; j++) {
-          pr.op(OP_PICK, m - (j - lo)); pr.push();
-          pr.op(OP_ADD_COL, COL(pk->se_sigma(j), r0));
-          pr.op(OP_MUL); pr.pop();
-        }
-        pr.op(OP_PUSH_COL, COL(pk->se_zp(s), r0)); pr.push();
-        for (uint32_t j = lo; j < hi; j++) {
-          pr.op(OP_PICK, 1 + m - (j - lo)); pr.push();
-          pr.op(OP_ADD_COL, COL(pk->se_dx(j), r0));
-          pr.op(OP_MUL); pr.pop();
-        }
-        pr.op(OP_SUB); pr.pop();
-        pr.op(OP_NIP, m); pr.cur -= m;
-        pr.op(OP_MUL_HOT, 2);
-        pr.next_beta = m;
-        pr.op(OP_ACC); pr.pop();
-      }
-    }
-    uint32_t e = pk->num_gates;
-    for (uint32_t l = 0; l < L; l++) {
-      const uint32_t ni = pk->lookup_shape[l].first, nt = pk->lookup_shape[l].second;
-      // l_0 * (1 - z)
-      pr.op(OP_PUSH_CONST, pk->c_one); pr.push();
-      pr.op(OP_SUB_COL, COL(pk->se_zl(l), r0));
-      pr.op(OP_MUL_HOT, 0);
-      pr.op(OP_ACC); pr.pop();
-      // l_last * (z^2 - z)
-      pr.op(OP_PUSH_COL, COL(pk->se_zl(l), r0)); pr.push();
-      pr.op(OP_SQR);
-      pr.op(OP_SUB_COL, COL(pk->se_zl(l), r0));
-      pr.op(OP_MUL_HOT, 1);
-      pr.op(OP_ACC); pr.pop();
-      // l_active * (z(wX)(a'+beta)(s'+gamma) - z(X)(ci+beta)(ct+gamma))
-      pr.op(OP_PUSH_COL, COL(pk->se_zl(l), r1)); pr.push();
-      pr.op(OP_PUSH_COL, COL(pk->se_la(l), r0)); pr.push();
-      pr.op(OP_ADD_CONST, pk->c_beta);
-      pr.op(OP_MUL); pr.pop();
-      pr.op(OP_PUSH_COL, COL(pk->se_ls(l), r0)); pr.push();
-      pr.op(OP_ADD_CONST, pk->c_gamma);
-      pr.op(OP_MUL); pr.pop();
-      pr.op(OP_PUSH_COL, COL(pk->se_zl(l), r0)); pr.push();
-      KG_TRY(emit_compressed(ctx, pk, pr, e, ni));
-      pr.op(OP_ADD_CONST, pk->c_beta);
-      pr.op(OP_MUL); pr.pop();
-      KG_TRY(emit_compressed(ctx, pk, pr, e + ni, nt));
-      pr.op(OP_ADD_CONST, pk->c_gamma);
-      pr.op(OP_MUL); pr.pop();
-      pr.op(OP_SUB); pr.pop();
-      pr.op(OP_MUL_HOT, 2);
-      pr.op(OP_ACC); pr.pop();
-      // l_0 * (a' - s')
-      pr.op(OP_PUSH_COL, COL(pk->se_la(l), r0)); pr.push();
-      pr.op(OP_SUB_COL, COL(pk->se_ls(l), r0));
-      pr.op(OP_MUL_HOT, 0);
-      pr.op(OP_ACC); pr.pop();
-      // l_active * (a' - s')(a' - a'(w^-1 X))
-      pr.op(OP_PUSH_COL, COL(pk->se_la(l), r0)); pr.push();
-      pr.op(OP_SUB_COL, COL(pk->se_ls(l), r0));
-      pr.op(OP_PUSH_COL, COL(pk->se_la(l), r0)); pr.push();
-      pr.op(OP_SUB_COL, COL(pk->se_la(l), rm1));
-      pr.op(OP_MUL); pr.pop();
-      pr.op(OP_MUL_HOT, 2);
-      pr.op(OP_ACC); pr.pop();
-      e += ni + nt;
-    }
-  }
-  if (pk->rots.rots.size() > 255) {
-    amdzk_pk_free(ctx, pk);
-    ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "keygen: more than 255 distinct rotations");
-  }
-  KG_TRY(build_output_tables(ctx, pk));
-  KG_TRY(dalloc(ctx, pk, &pk->d_consts, pk->consts.size()));
-  KG_TRY(h2d(ctx, pk->d_consts, pk->consts.data(), pk->consts.size() * 32));
-  KG_TRY(dalloc(ctx, pk, &pk->d_consts261, pk->consts.size()));
-  ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
-  KG_TRY(upload_program(ctx, pk, pk->prog_compress, false));
-  KG_TRY(upload_program(ctx, pk, pk->prog_pfrac, false));
-  KG_TRY(upload_program(ctx, pk, pk->prog_lfrac, false));
-  {
-    // pieces of the h(X) program: 6 by default. One piece is 1.5 wavefronts per SIMD at k = 15 (3 cosets x 2^15 rows) and
-    // the interpreter alone took 2.30 ms of a lone proof's critical path; 8 pieces 1.70 ms. Latency of one proof, median
-    // of 15, two runs each on one box: 1 piece 18.34 / 18.39 ms, 4: 17.71 / 17.86, 6: 17.61 / 17.78, 8: 17.63 / 17.46;
-    // 10 proofs in flight: 78.0 / 76.7, 77.8 / 78.3, 78.2 / 78.5, 78.0 / 77.6 proofs/s (no difference).
-    // AMDZK_H_PARTS=1..8 for experiments.
-    const char* e = getenv("AMDZK_H_PARTS");
-    uint32_t parts = e ? (uint32_t)atoi(e) : 6u;
-    parts = parts < 1 ? 1 : parts > H_PARTS_MAX ? H_PARTS_MAX : parts;
-    pk->h_terms = finalize_limb_program(pk->prog_h, parts);
-  }
-  pk->h_term_beta_pow = pk->prog_h.term_beta;
-  KG_TRY(dalloc(ctx, pk, &pk->d_ypow, (size_t)std::max<uint32_t>(pk->h_terms, 1)));
-  KG_TRY(upload_program(ctx, pk, pk->prog_h, true));
-  if (getenv("AMDZK_DUMP_PROG")) {  // debugging aid: what the compiled h(X) program is made of
-    static const char* names[] = {"END", "PUSH_COL", "PUSH_CONST", "ADD", "SUB", "MUL", "NEG", "MUL_CONST", "ADD_CONST", "MUL_COL",
-                                  "ADD_COL", "SUB_COL", "ACC", "STORE", "SQR", "PUSH_HOT", "MUL_HOT", "REDUCE", "SUB_BIG", "NEG_BIG",
-                                  "WACC", "WFLUSH"};
-    std::map<uint32_t, size_t> hist;
-    std::map<std::pair<uint32_t, uint32_t>, size_t> pairs;
-    const auto& w = pk->prog_h.words;
-    for (size_t i = 0; i < w.size(); i++) {
-      hist[w[i] >> 24]++;
-      if (i + 1 < w.size()) pairs[{w[i] >> 24, w[i + 1] >> 24}]++;
-    }
-    fprintf(stderr, "[amdzk] prog_h: %zu instructions, stack depth %u\n", w.size(), pk->prog_h.depth);
-    for (auto& kv : hist) fprintf(stderr, "[amdzk]   %-10s %zu\n", kv.first < 22 ? names[kv.first] : "?", kv.second);
-    auto is_mul = [](uint32_t o) { return o == OP_MUL || o == OP_MUL_CONST || o == OP_MUL_COL || o == OP_MUL_HOT || o == OP_SQR || o == OP_WACC; };
-    size_t mm = 0;
-    for (auto& kv : pairs)
-      if (is_mul(kv.first.first) && is_mul(kv.first.second)) {
-        mm += kv.second;
-        fprintf(stderr, "[amdzk]   product -> product: %s -> %s x %zu\n", names[kv.first.first], names[kv.first.second], kv.second);
-      }
-    fprintf(stderr, "[amdzk]   products directly followed by a product: %zu\n", mm);
-  }
-  // Constant tables (amdzk_pk::lk_const): ct[l] evaluated here, once, and its canonical, padded, sorted form kept
-  if (pk->lk_const) {
-    const uint32_t cnt = pk->lk_const, usable = (uint32_t)n - (pk->bf + 1);
-    KG_TRY(dalloc(ctx, pk, &pk->lk_ts_const, (size_t)cnt * n));
-    Program pr;
-    uint32_t e = pk->num_gates;
-    for (uint32_t l = 0; l < cnt; l++) {
-      pr.piece();
-      KG_TRY(emit_expr(ctx, pk, pr, pk->exprs[e + pk->lookup_shape[l].first]));
-      pr.op(OP_STORE, 2 * l + 1);
-      pr.pop();
-      e += pk->lookup_shape[l].first + 1;
-    }
-    KG_TRY(upload_program(ctx, pk, pr, false));
-    KG_TRY(run_program(ctx, pk, pr, false, pk->d_outs_compress, nullptr, "expr_const_tables"));
-    KG_TRY(d2d(ctx, pk->lk_ts_const, pk->ct, (size_t)cnt * n * 32));
-    KG_TRY(amdzk_fr_to_repr_dev(ctx, pk->lk_ts_const, (size_t)cnt * n));
-    ZK_HIP(ctx, hipMemset2DAsync(pk->lk_ts_const + usable, (size_t)n * 32, 0xFF, (size_t)(n - usable) * 32, cnt, ctx->stream));
-    KG_TRY(zk_sort_keys(ctx, pk->lk_ts_const, cnt, n, n));
-    ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
-  }
-  // l_active coset = 1 - (l_last + l_blind): lactive_c holds l_blind's coset; tiny one-off program
-  {
-    KG_TRY(upload_consts261(ctx, pk));
-    ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
-    Program pr;
-    pr.op(OP_PUSH_CONST, pk->c_one); pr.push();
-    pr.op(OP_SUB_COL, COL(pk->se_llast(), r0));
-    pr.op(OP_SUB_COL, COL(pk->se_lactive(), r0));
-    pr.op(OP_STORE, 0); pr.pop();
-    (void)finalize_limb_program(pr);
-    KG_TRY(upload_program(ctx, pk, pr, true));
-    Fr** d_out = nullptr;
-    KG_TRY(dalloc(ctx, pk, &d_out, 1));
-    Fr* tgt = pk->lactive_c;
-    KG_TRY(h2d(ctx, d_out, &tgt, sizeof(Fr*)));
-    ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
-    KG_TRY(run_program(ctx, pk, pr, true, d_out, nullptr, "expr_l_active"));
-    ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
-  }
-#undef KG_TRY
-  *out = pk;
-  return AMDZK_OK;
-}
-
-// VK material a verifier needs: commitments of the fixed columns and of the permutation polynomials.
-int amdzk_pk_commitments(const amdzk_pk* pk, uint64_t* fixed_out /* F x 8 */, uint64_t* perm_out /* S x 8 */) {
-  if (!pk) return AMDZK_E_INVALID;
-  if (fixed_out && pk->F) memcpy(fixed_out, pk->fixed_commitments.data(), (size_t)pk->F * 64);
-  if (perm_out && pk->S) memcpy(perm_out, pk->perm_commitments.data(), (size_t)pk->S * 64);
-  return AMDZK_OK;
-}
-
-}  // extern "C"
 
 namespace {
 
@@ -2919,59 +1442,6 @@ int amdzk_create_proof_ex(amdzk_ctx* ctx, amdzk_pk* pk, const uint64_t* const* i
                            proof_cap, proof_len);
 }
 
-// One more circuit instance's workspace for `src`'s circuit: a key handle that shares src's key material (fixed and
-// permutation columns in all three forms, the domain, the compiled programs' text, constant lookup tables — read-only
-// during proofs) and owns its own per-proof workspace, pointer tables and uploaded programs (their instructions carry
-// absolute column addresses). What amdzk_create_proof_multi takes for its second, third, ... instance — and, since a
-// clone is a complete key for create_proof, the cheap way to keep several proofs of one circuit in flight: a
-// clone costs the workspace (the arenas), not the key (354 + 354 MiB of permutation cosets at the metric's shape).
-// Free it with amdzk_pk_free BEFORE the key it was made from.
-int amdzk_pk_clone_workspace(amdzk_ctx* ctx, const amdzk_pk* src, amdzk_pk** out) {
-  ZK_ENTER(ctx);
-  if (!ctx) return AMDZK_E_INVALID;
-  if (!src || !out) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_clone_workspace: null argument");
-  amdzk_pk* pk = new amdzk_pk(*src);
-  pk->clone_of = src->clone_of ? src->clone_of : src;
-  pk->allocs.clear();
-  pk->pin = nullptr;
-  pk->pin_cap = pk->pin_off = 0;
-  pk->mo = amdzk_pk::Multiopen();
-  pk->mo_multi = amdzk_pk::Multiopen();
-  pk->mo_multi_keys.clear();
-  pk->sets_Q = nullptr;
-  pk->sets_Q_pairs = 0;
-  pk->prog_compress.d_instr = pk->prog_pfrac.d_instr = pk->prog_lfrac.d_instr = pk->prog_h.d_instr = nullptr;
-  pk->chk = amdzk_pk::Check();  // built by the clone's own first check
-#define CL_TRY(x)                \
-  do {                           \
-    int _r = (x);                \
-    if (_r != AMDZK_OK) {        \
-      amdzk_pk_free(ctx, pk);    \
-      return _r;                 \
-    }                            \
-  } while (0)
-  CL_TRY(alloc_proof_workspace(ctx, pk));
-  CL_TRY(build_column_tables(ctx, pk));
-  CL_TRY(build_output_tables(ctx, pk));
-  CL_TRY(dalloc(ctx, pk, &pk->d_consts, pk->consts.size()));
-  CL_TRY(h2d(ctx, pk->d_consts, pk->consts.data(), pk->consts.size() * 32));
-  CL_TRY(dalloc(ctx, pk, &pk->d_consts261, pk->consts.size()));
-  CL_TRY(dalloc(ctx, pk, &pk->d_ypow, (size_t)std::max<uint32_t>(pk->h_terms, 1)));
-  ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
-  CL_TRY(upload_program(ctx, pk, pk->prog_compress, false));
-  CL_TRY(upload_program(ctx, pk, pk->prog_pfrac, false));
-  CL_TRY(upload_program(ctx, pk, pk->prog_lfrac, false));
-  CL_TRY(upload_program(ctx, pk, pk->prog_h, true));
-  CL_TRY(upload_consts261(ctx, pk));
-  // the compressed constant tables (amdzk_pk::lk_const) are written once, at keygen, into the key's ct columns — the
-  // per-proof compression program skips them — so a new workspace starts with a copy
-  if (pk->lk_const) CL_TRY(d2d(ctx, pk->ct, src->ct, (size_t)pk->lk_const * pk->n * 32));
-  ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
-#undef CL_TRY
-  *out = pk;
-  return AMDZK_OK;
-}
-
 // plonk::create_proof(params, pk, &[circuit; N], &[instances; N], rng, transcript) [UP]: n_circuits instances of the
 // key's circuit in ONE proof. pks[c]: instance c's workspace — pks[0] the key (or a clone), the others workspace clones of
 // the same key, all different. instances[c][col] / instance_lens[c][col] and d_advice[c] as for amdzk_create_proof_ex.
@@ -3134,370 +1604,6 @@ int amdzk_quotient_eval_dev(amdzk_ctx* ctx, amdzk_pk* pk, const void* d_polys, s
   ZK_TRY(quotient_pieces(ctx, pk));
   ZK_TRY(d2d(ctx, d_pieces_out, pk->hpieces, (size_t)pk->qdeg * pk->n * 32));
   ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
-  return AMDZK_OK;
-}
-
-// What the last create_proof on this key left in its workspace, for tests that check one stage at a time against the
-// oracle: what = 0 the NP committed polynomials in coefficient form ([NP][n], arena order as above); 1 the
-// challenges theta, beta, gamma, y; 2 the pieces of h(X) ([cs_degree - 1][n]); 3 the phase challenges. `out` holds cap Fr elements;
-// *count = elements available.
-int amdzk_pk_inspect(amdzk_ctx* ctx, const amdzk_pk* pk, int what, uint64_t* out, size_t cap, size_t* count) {
-  ZK_ENTER(ctx);
-  if (!ctx) return AMDZK_E_INVALID;
-  if (!pk || !count) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_inspect: null argument");
-  const Fr* src = nullptr;
-  size_t cnt = 0;
-  Fr ch[4];
-  if (what == 0) {
-    src = pk->PQ;
-    cnt = pk->NP * pk->n;
-  } else if (what == 2) {
-    src = pk->hpieces;
-    cnt = (size_t)pk->qdeg * pk->n;
-  } else if (what == 1) {
-    ch[0] = pk->consts[pk->c_theta];
-    ch[1] = pk->consts[pk->c_beta];
-    ch[2] = pk->consts[pk->c_gamma];
-    ch[3] = pk->consts[pk->c_y];
-    cnt = 4;
-  } else if (what == 3) {
-    cnt = pk->num_challenges;
-  } else {
-    ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_inspect: unknown selector %d", what);
-  }
-  *count = cnt;
-  if (!out) return AMDZK_OK;
-  if (cap < cnt) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_inspect: buffer holds %zu elements, %zu needed", cap, cnt);
-  if (what == 1) memcpy(out, ch, sizeof(ch));
-  else if (what == 3) memcpy(out, pk->consts.data() + pk->c_chal0, cnt * 32);
-  else ZK_TRY(d2h(ctx, out, src, cnt * 32));
-  return AMDZK_OK;
-}
-
-// The key's own columns, for a fork whose ProvingKey::write stores a key that was made on the device: what = 0 the fixed
-// columns (Lagrange), 1 the sigma columns (Lagrange), 2 / 3 the same as coefficients. A workspace clone shares these
-// buffers with its root key, so it returns the root's columns.
-int amdzk_pk_export(amdzk_ctx* ctx, const amdzk_pk* pk, int what, uint64_t* out, size_t cap, size_t* count) {
-  ZK_ENTER(ctx);
-  if (!ctx) return AMDZK_E_INVALID;
-  if (!pk || !count) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_export: null argument");
-  if (what < 0 || what > 3) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_export: unknown selector %d", what);
-  const Fr* src[4] = {pk->fixed_lag, pk->sigma_lag, pk->fixed_poly, pk->sigma_poly};
-  const size_t cnt = (size_t)((what & 1) ? pk->S : pk->F) * pk->n;
-  *count = cnt;
-  if (!out) return AMDZK_OK;
-  if (cap < cnt) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_export: buffer holds %zu elements, %zu needed", cap, cnt);
-  return d2h(ctx, out, src[what], cnt * 32);
-}
-
-// ---- the key file (csrc/pkblob.hpp has the layout, the header's writer and the host-only parser)
-// keygen takes a circuit on trust where pkblob::validate() does not (a query that no expression uses may name any column,
-// for one): such a key proves, but its file would be refused by amdzk_pk_read, so it is not written at all.
-size_t amdzk_pk_serialized_size(const amdzk_pk* pk) {
-  return pk && pk->src_desc && pkblob::validate(*pk->src_desc, nullptr) == AMDZK_OK ? pk->src_desc->serialized_size() : 0;
-}
-
-int amdzk_pk_write(amdzk_ctx* ctx, const amdzk_pk* pk, uint8_t* out, size_t cap, size_t* written) {
-  ZK_ENTER(ctx);
-  if (!ctx) return AMDZK_E_INVALID;
-  if (!pk || !pk->src_desc || (!out && !written)) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_write: null argument");
-  const pkblob::Desc& d = *pk->src_desc;
-  std::string why;
-  if (pkblob::validate(d, &why) != AMDZK_OK)
-    ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_write: amdzk_pk_read would refuse this key's circuit (%s)", why.c_str());
-  const size_t need = d.serialized_size();
-  if (written) *written = need;
-  if (!out) return AMDZK_OK;
-  if (cap < need) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_write: buffer holds %zu bytes, %zu needed", cap, need);
-  d.write_header(out);
-  uint8_t* p = out + d.header_bytes();
-  memcpy(p, pk->transcript_repr.l, 32);
-  p += 32;
-  if (pk->F) memcpy(p, pk->fixed_commitments.data(), (size_t)pk->F * 64);
-  p += (size_t)pk->F * 64;
-  if (pk->S) memcpy(p, pk->perm_commitments.data(), (size_t)pk->S * 64);
-  p += (size_t)pk->S * 64;
-  ZK_TRY(d2h(ctx, p, pk->fixed_lag, (size_t)pk->F * pk->n * 32));
-  p += (size_t)pk->F * pk->n * 32;
-  ZK_TRY(d2h(ctx, p, pk->sigma_lag, (size_t)pk->S * pk->n * 32));
-  p += (size_t)pk->S * pk->n * 32;
-  pkblob::digest(out, (size_t)(p - out), p);
-  return AMDZK_OK;
-}
-
-// Pure host code: every check amdzk_pk_read makes before it touches the device.
-int amdzk_pk_blob_info(const uint8_t* data, size_t len, uint32_t* k, uint32_t* num_fixed, uint32_t* num_advice, uint32_t* num_perm_columns,
-                       uint32_t* num_challenges) {
-  pkblob::Desc d;
-  if (int rc = pkblob::parse(data, len, &d, nullptr, nullptr)) return rc;
-  if (k) *k = d.k;
-  if (num_fixed) *num_fixed = d.num_fixed;
-  if (num_advice) *num_advice = d.num_advice;
-  if (num_perm_columns) *num_perm_columns = d.num_perm_columns();
-  if (num_challenges) *num_challenges = d.num_challenges;
-  return AMDZK_OK;
-}
-
-// amdzk_pk_blob_info's verdict with its reason: the message amdzk_pk_read would leave in the ctx ("pk_read: digest mismatch
-// ..."), for a host without a device. msg (may be NULL) receives at most msg_cap bytes, NUL-terminated; "" for a good file.
-int amdzk_pk_blob_check(const uint8_t* data, size_t len, char* msg, size_t msg_cap) {
-  pkblob::Desc d;
-  std::string err;
-  const int rc = pkblob::parse(data, len, &d, nullptr, &err);
-  if (msg && msg_cap) snprintf(msg, msg_cap, "%s", err.c_str());
-  return rc;
-}
-
-// The file's header and columns through the tail keygen shares (keygen_common), then the commitments it computed against
-// the stored ones: they differ exactly when the parameters are not the ones the key was made under.
-int amdzk_pk_read(amdzk_ctx* ctx, const amdzk_srs* srs, const uint8_t* data, size_t len, uint32_t flags, amdzk_pk** out) {
-  ZK_ENTER(ctx);
-  if (!ctx) return AMDZK_E_INVALID;
-  if (!srs || !data || !out) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_read: null argument");
-  pkblob::Desc d;
-  pkblob::Layout lay;
-  std::string err;
-  if (int rc = pkblob::parse(data, len, &d, &lay, &err)) {
-    ctx->err = err;
-    return rc;
-  }
-  if (d.k != zk_srs_k(srs)) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_read: the key is for k = %u, the parameters are for k = %u", d.k, zk_srs_k(srs));
-  amdzk_circuit c;
-  amdzk_phases ph;
-  d.view(&c, &ph);
-  uint64_t repr[4];
-  memcpy(repr, data + lay.transcript_repr, 32);
-  amdzk_pk* pk = nullptr;
-  const int rc = keygen_common(ctx, srs, &c, d.has_phases ? &ph : nullptr, data + lay.fixed_values, nullptr, data + lay.sigma_values, true, repr,
-                               flags, &pk);
-  if (rc != AMDZK_OK) {
-    if (rc == AMDZK_E_INVALID) ctx->err = "pk_read: " + ctx->err;
-    return rc;
-  }
-  const bool same = (!pk->F || memcmp(pk->fixed_commitments.data(), data + lay.fixed_commitments, (size_t)pk->F * 64) == 0) &&
-                    (!pk->S || memcmp(pk->perm_commitments.data(), data + lay.perm_commitments, (size_t)pk->S * 64) == 0);
-  if (!same) {
-    amdzk_pk_free(ctx, pk);
-    ZK_FAIL(ctx, AMDZK_E_INVALID,
-            "pk_read: the commitments in the file are not those of its columns under these parameters: the key was made under other "
-            "parameters (another SRS)");
-  }
-  *out = pk;
-  return AMDZK_OK;
-}
-
-// ---- amdzk_check_witness: MockProver::verify's constraint checks on the device (include/amdzk.h has the semantics).
-// What this handle needs beyond what a proof uses, made by its first check: the gate program, the permutation columns'
-// addresses in this workspace, the counters.
-static int check_build(amdzk_ctx* ctx, amdzk_pk* pk) {
-  amdzk_pk::Check& ck = pk->chk;
-  if (ck.built) return AMDZK_OK;
-  const uint32_t ncon = pk->num_gates + pk->L + pk->S;
-  if (!ck.prog_gates.d_instr) {
-    Program pr;
-    const RotTable rots_before = pk->rots;  // the gates' rotations are all in the table already: the h(X) program queried them
-    for (uint32_t g = 0; g < pk->num_gates; g++) {
-      pr.piece();
-      ZK_TRY(emit_expr(ctx, pk, pr, pk->exprs[g]));
-      pr.op(OP_CHECK, g);
-      pr.pop();
-    }
-    if (pk->rots.rots.size() != rots_before.rots.size()) {  // cannot happen for a key keygen made; the table stays what the uploaded programs index
-      pk->rots = rots_before;
-      ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: a gate polynomial queries a rotation the key's programs do not");
-    }
-    ck.prog_gates = pr;
-    ZK_TRY(upload_program(ctx, pk, ck.prog_gates, false));
-  }
-  if (pk->S && !ck.d_perm_cols) {
-    std::vector<const Fr*> cols(pk->S);
-    for (uint32_t i = 0; i < pk->S; i++) {
-      const std::pair<int, int>& kc = pk->perm_cols[i];
-      cols[i] = pk->h_cols_lag[kc.first == 0 ? pk->sl_adv(kc.second) : kc.first == 1 ? pk->sl_fixed(kc.second) : pk->sl_inst(kc.second)];
-    }
-    ZK_TRY(dalloc(ctx, pk, &ck.d_perm_cols, cols.size()));
-    ZK_TRY(h2d(ctx, ck.d_perm_cols, cols.data(), cols.size() * sizeof(Fr*)));
-    ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));  // `cols` is a host temporary
-  }
-  if (!ck.d_count) {
-    ZK_TRY(dalloc(ctx, pk, &ck.d_count, (size_t)ncon + ((size_t)ncon + 1) / 2 + 1));  // u64 counts, then u32 first rows
-    ck.d_first = reinterpret_cast<uint32_t*>(ck.d_count + ncon);
-  }
-  ck.built = true;
-  return AMDZK_OK;
-}
-
-// The root key's sigma columns back to (column, row), once: S * n * 8 bytes that every handle of the key reads.
-static int check_decode_sigma(amdzk_ctx* ctx, amdzk_pk* pk) {
-  amdzk_pk::CheckShared& sh = *pk->chk_shared;
-  std::lock_guard<std::mutex> lock(sh.guard);
-  if (sh.decoded || !pk->S) return AMDZK_OK;
-  const uint32_t S = pk->S, k = pk->k;
-  const size_t n = pk->n;
-  if (!sh.d_cells) {
-    void* q = nullptr;
-    if (hipMalloc(&q, (size_t)S * n * sizeof(uint2)) != hipSuccess) ZK_FAIL(ctx, AMDZK_E_NOMEM, "check_witness: hipMalloc of the decoded permutation failed");
-    sh.d_cells = (uint2*)q;
-  }
-  // delta^(i 2^k), delta^(-i) for i < S, omega^(-(2^b)) for b < k
-  std::vector<Fr> tab(2 * (size_t)S + k);
-  const Fr delta = fr_delta(), delta_inv = inv(delta);
-  Fr d2k = delta;
-  for (uint32_t i = 0; i < k; i++) d2k = mul(d2k, d2k);
-  Fr a = Fr::one(), b = Fr::one();
-  for (uint32_t i = 0; i < S; i++) {
-    tab[i] = a;
-    tab[S + i] = b;
-    a = mul(a, d2k);
-    b = mul(b, delta_inv);
-  }
-  Fr w = pk->omega_inv;
-  for (uint32_t i = 0; i < k; i++) {
-    tab[2 * (size_t)S + i] = w;
-    w = mul(w, w);
-  }
-  void* d_tab = nullptr;
-  if (hipMalloc(&d_tab, tab.size() * 32 + 8) != hipSuccess) ZK_FAIL(ctx, AMDZK_E_NOMEM, "check_witness: hipMalloc failed");
-  unsigned long long* d_bad = reinterpret_cast<unsigned long long*>((Fr*)d_tab + tab.size());
-  unsigned long long bad = 0;
-  int r = h2d(ctx, d_tab, tab.data(), tab.size() * 32);
-  if (r == AMDZK_OK && hipMemsetAsync(d_bad, 0xFF, 8, ctx->stream) != hipSuccess) r = AMDZK_E_HIP;
-  if (r == AMDZK_OK) r = zk_sigma_decode(ctx, pk->sigma_lag, S, k, (const Fr*)d_tab, sh.d_cells, d_bad);
-  if (r == AMDZK_OK) r = d2h(ctx, &bad, d_bad, 8);
-  else (void)zk_host_wait(ctx, ctx->stream);  // `tab` is a host temporary
-  hipFree(d_tab);
-  ZK_TRY(r);
-  if (bad != ~0ull) {
-    const unsigned long long cell = bad - 1;
-    ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: sigma column %u row %u is not delta^i omega^j for a column i < %u of this circuit",
-            (uint32_t)(cell >> 32), (uint32_t)cell, S);
-  }
-  sh.decoded = true;
-  return AMDZK_OK;
-}
-
-static int check_witness_run(amdzk_ctx* ctx, amdzk_pk* pk, const uint64_t* const* instances, const size_t* instance_lens, const void* d_advice,
-                             size_t advice_stride, const amdzk_check_opts* opts, amdzk_check_failure* out, size_t cap, size_t* n_failures) {
-  if (!pk || !n_failures || (pk->A && !d_advice)) ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: null argument");
-  if (opts && opts->size < sizeof(amdzk_check_opts))
-    ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: amdzk_check_opts.size is %zu, this library needs %zu", opts->size, sizeof(amdzk_check_opts));
-  const size_t n = pk->n, usable = n - (pk->bf + 1);
-  const uint32_t A = pk->A, I = pk->I, L = pk->L, S = pk->S, G = pk->num_gates, ncon = G + L + S;
-  if (pk->A && advice_stride < n) ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: advice stride < n");
-  const uint32_t given = opts && opts->challenges ? opts->num_challenges : 0;
-  if (pk->num_challenges && !given) ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: the key has %u challenges and none were given", pk->num_challenges);
-  if ((opts ? opts->num_challenges : 0) != pk->num_challenges)
-    ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: %u challenges given, the key has %u", opts ? opts->num_challenges : 0, pk->num_challenges);
-  for (uint32_t c = 0; c < I; c++) {
-    const size_t len = instance_lens ? instance_lens[c] : 0;
-    if (len > usable) ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: instance column %u too long (InstanceTooLarge)", c);
-    if (len && (!instances || !instances[c])) ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: null argument (instance column %u)", c);
-  }
-  amdzk_pk* const root = const_cast<amdzk_pk*>(pk->clone_of ? pk->clone_of : pk);
-  ZK_TRY(check_build(ctx, pk));
-  ZK_TRY(check_decode_sigma(ctx, root));
-  const amdzk_pk::Check& ck = pk->chk;
-  const CheckCounters counters = {ck.d_count, ck.d_first};
-  *n_failures = 0;
-  if (!ncon) return AMDZK_OK;
-  ZK_HIP(ctx, hipMemsetAsync(ck.d_count, 0, (size_t)ncon * 8, ctx->stream));
-  ZK_HIP(ctx, hipMemsetAsync(ck.d_first, 0xFF, (size_t)ncon * 4, ctx->stream));
-  // the witness into the workspace as create_proof copies it, unblinded: instance columns zero behind the caller's values
-  if (I) {
-    ZK_HIP(ctx, hipMemsetAsync(pk->inst(), 0, (size_t)I * n * 32, ctx->stream));
-    for (uint32_t c = 0; c < I; c++) {
-      const size_t len = instance_lens ? instance_lens[c] : 0;
-      if (!len) continue;
-      ZK_TRY(h2d_staged(ctx, pk, pk->inst() + (size_t)c * n, instances[c], len * 32));
-    }
-  }
-  if (A) ZK_HIP(ctx, hipMemcpy2DAsync(pk->adv(), n * 32, d_advice, advice_stride * 32, n * 32, A, hipMemcpyDeviceToDevice, ctx->stream));
-  {  // theta and the phase challenges into their slots of the constant table
-    ChaCha20Rng rng(opts ? opts->theta_seed : 0);
-    pk->consts[pk->c_theta] = rng.fr();
-    ZK_TRY(h2d_staged(ctx, pk, pk->d_consts + pk->c_theta, &pk->consts[pk->c_theta], 32));
-    if (pk->num_challenges) {
-      memcpy(pk->consts[pk->c_chal0].l, opts->challenges, (size_t)pk->num_challenges * 32);
-      ZK_TRY(h2d_staged(ctx, pk, pk->d_consts + pk->c_chal0, &pk->consts[pk->c_chal0], (size_t)pk->num_challenges * 32));
-    }
-  }
-  if (G) {
-    ExprArgs a;
-    ZK_TRY(program_args(ctx, pk, pk->chk.prog_gates, false, nullptr, nullptr, a));
-    ZK_TRY(zk_check_expr(ctx, a, ck.prog_gates.depth + 1, (uint32_t)usable, counters, "expr_check_gates"));
-  }
-  if (L) {  // compressed inputs and tables as canonical keys, the tables sorted (constant ones were sorted at keygen)
-    ZK_TRY(run_program(ctx, pk, pk->prog_compress, false, pk->d_outs_compress, nullptr, "expr_lookup_compress"));
-    ZK_TRY(d2d(ctx, pk->la(), pk->ci, (size_t)L * n * 32));
-    ZK_TRY(amdzk_fr_to_repr_dev(ctx, pk->la(), (size_t)L * n));
-    const uint32_t pre = pk->lk_const, rest = L - pre;
-    if (pre) ZK_TRY(d2d(ctx, pk->lk_ts, pk->lk_ts_const, (size_t)pre * n * 32));
-    if (rest) {
-      Fr* Tr = pk->lk_ts + (size_t)pre * n;
-      ZK_TRY(d2d(ctx, Tr, pk->ct + (size_t)pre * n, (size_t)rest * n * 32));
-      ZK_TRY(amdzk_fr_to_repr_dev(ctx, Tr, (size_t)rest * n));
-      ZK_HIP(ctx, hipMemset2DAsync(Tr + usable, n * 32, 0xFF, (n - usable) * 32, rest, ctx->stream));
-      ZK_TRY(zk_sort_keys(ctx, Tr, rest, (uint32_t)n, n));
-    }
-    ZK_TRY(zk_check_lookups(ctx, pk->la(), pk->lk_ts, L, (uint32_t)n, (uint32_t)usable, G, counters));
-  }
-  if (S) ZK_TRY(zk_check_copies(ctx, ck.d_perm_cols, root->chk_shared->d_cells, S, (uint32_t)n, G + L, counters));
-  std::vector<unsigned long long> host((size_t)ncon + ((size_t)ncon + 1) / 2);
-  ZK_TRY(d2h(ctx, host.data(), ck.d_count, (size_t)ncon * 12));
-  const uint32_t* first = reinterpret_cast<const uint32_t*>(host.data() + ncon);
-  size_t nf = 0;
-  for (uint32_t c = 0; c < ncon; c++) {
-    if (!host[c]) continue;
-    if (out && nf < cap) {
-      amdzk_check_failure& f = out[nf];
-      f.kind = c < G ? AMDZK_CHECK_GATE : c < G + L ? AMDZK_CHECK_LOOKUP : AMDZK_CHECK_COPY;
-      f.index = c < G ? c : c < G + L ? c - G : c - G - L;
-      f.first_row = first[c];
-      f.reserved = 0;
-      f.count = host[c];
-    }
-    nf++;
-  }
-  *n_failures = nf;
-  return AMDZK_OK;
-}
-
-int amdzk_check_witness(amdzk_ctx* ctx, amdzk_pk* pk, const uint64_t* const* instances, const size_t* instance_lens, const void* d_advice,
-                        size_t advice_stride, const amdzk_check_opts* opts, amdzk_check_failure* out, size_t cap, size_t* n_failures) {
-  ZK_ENTER(ctx);
-  if (!ctx) return AMDZK_E_INVALID;
-  const int r = check_witness_run(ctx, pk, instances, instance_lens, d_advice, advice_stride, opts, out, cap, n_failures);
-  if (r != AMDZK_OK) {  // whatever was enqueued (copies from the caller's memory among it) is finished before the call returns
-    const std::string keep = ctx->err;
-    (void)zk_host_wait(ctx, ctx->stream);
-    ctx->err = keep;
-  }
-  return r;
-}
-
-// Test hooks for the host pass that prepares quotient-domain programs for the limb-resident interpreter
-// (finalize_limb_program): (a) the pass on caller-supplied program words — pure host code, no device — and (b) the
-// finalised h(X) program of a key. Words are `op << 24 | arg` with the opcodes of csrc/plonk_kernels.hpp.
-int amdzk_debug_limb_program(const uint32_t* words, size_t n, uint32_t* out, size_t cap, size_t* out_n, uint32_t* depth) {
-  if ((!words && n) || !out_n) return AMDZK_E_INVALID;
-  Program pr;
-  pr.words.assign(words, words + n);
-  (void)finalize_limb_program(pr);
-  *out_n = pr.words.size();
-  if (depth) *depth = pr.depth;
-  if (out) {
-    if (cap < pr.words.size()) return AMDZK_E_INVALID;
-    memcpy(out, pr.words.data(), pr.words.size() * sizeof(uint32_t));
-  }
-  return AMDZK_OK;
-}
-int amdzk_pk_h_program(const amdzk_pk* pk, uint32_t* out, size_t cap, size_t* out_n) {
-  if (!pk || !out_n) return AMDZK_E_INVALID;
-  *out_n = pk->prog_h.words.size();
-  if (out) {
-    if (cap < pk->prog_h.words.size()) return AMDZK_E_INVALID;
-    memcpy(out, pk->prog_h.words.data(), pk->prog_h.words.size() * sizeof(uint32_t));
-  }
   return AMDZK_OK;
 }
 

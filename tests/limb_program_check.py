@@ -1,7 +1,7 @@
 """Independent checker for programs finalised for the limb-resident interpreter (csrc/plonk_kernels.hip
 expr_eval_limbs_kernel): walks the words with every value's bound in units of p, exactly by the rules fp29.cuh
 documents for each function, and asserts every precondition — the safety net behind the host pass
-(prover.hip finalize_limb_program) that places the weak reductions."""
+(program.hip finalize_limb_program) that places the weak reductions."""
 
 OPS = dict(END=0, PUSH_COL=1, PUSH_CONST=2, ADD=3, SUB=4, MUL=5, NEG=6, MUL_CONST=7, ADD_CONST=8, MUL_COL=9, ADD_COL=10, SUB_COL=11, ACC=12,
            STORE=13, SQR=14, PUSH_HOT=15, MUL_HOT=16, REDUCE=17, SUB_BIG=18, NEG_BIG=19, WACC=20, WFLUSH=21, PICK=22, NIP=23)
@@ -68,7 +68,7 @@ def check(words):
             k = w & 7
             assert k <= 4 and (w & 0xFFFFFF) & ~0x17 == 0, where
             # bit 4: this flush overwrites h — the first flush of the program, or of a further piece of a cut program
-            # (pieces run side by side into their own h and are summed afterwards: prover.hip finalize_limb_program)
+            # (pieces run side by side into their own h and are summed afterwards: program.hip finalize_limb_program)
             assert (w & 16) or flushes > 0, where + ": the first flush must overwrite h"
             pieces += 1 if w & 16 else 0
             flushes += 1

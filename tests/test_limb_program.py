@@ -1,4 +1,4 @@
-"""CPU: the host pass that prepares quotient-domain programs for the limb-resident interpreter (prover.hip
+"""CPU: the host pass that prepares quotient-domain programs for the limb-resident interpreter (program.hip
 finalize_limb_program, reached through amdzk_debug_limb_program — pure host code) on synthetic programs that force each
 of its decisions, checked by the independent bound walker in limb_program_check.py."""
 import ctypes as C
