@@ -449,6 +449,36 @@ struct alignas(16) G1Affine {
   ZK_HD bool is_inf() const { return x.is_zero() && y.is_zero(); }
 };
 
+// ---- what decoding a point from bytes needs (msm.hip g1_decompress_kernel, verify.hip proof_decode_kernel)
+// a plain 256-bit integer is a canonical residue (< p)
+template <class P>
+ZK_HD bool is_canonical(const Fp<P>& a) {
+  uint32_t borrow = 0;
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    uint64_t t = (uint64_t)a.l[j] - P::p(j) - borrow;
+    borrow = (uint32_t)(t >> 63);
+  }
+  return borrow == 1;
+}
+// x^3 + 3 (Montgomery in and out)
+ZK_HD Fq g1_curve_rhs(const Fq& xm) {
+  const Fq three = add(add(Fq::one(), Fq::one()), Fq::one());
+  return add(mul(sqr(xm), xm), three);
+}
+// The square root of a (Montgomery) as a^((q+1)/4), q = 3 mod 4, CHECKED: false when a is a non-residue.
+ZK_HD bool fq_sqrt_checked(const Fq& a, Fq* y) {
+  const uint32_t e[8] = {0xb61f3f52u, 0x4f082305u, 0x5a1c72a3u, 0x65e05aa4u, 0xa0605617u, 0x6e14116du, 0xb84c680au, 0x0c19139cu};  // (q+1)/4
+  *y = pow_u256(a, e);
+  return sqr(*y) == a;
+}
+// y of the curve point with this x (Montgomery) and this parity of the canonical y; false when there is none
+ZK_HD bool g1_y_from_x(const Fq& xm, uint32_t ysign, Fq* y) {
+  if (!fq_sqrt_checked(g1_curve_rhs(xm), y)) return false;
+  if ((from_mont(*y).l[0] & 1u) != ysign) *y = neg(*y);
+  return true;
+}
+
 // Jacobian point as halo2curves G1 {x,y,z}; z = 0 is the identity.
 struct alignas(16) G1Jac {
   Fq x, y, z;

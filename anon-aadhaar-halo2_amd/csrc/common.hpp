@@ -249,6 +249,7 @@ int zk_srs_upload(amdzk_ctx* ctx, const uint64_t* g, const uint64_t* g_lagrange,
 void zk_srs_free(amdzk_ctx*, amdzk_srs* s);
 uint32_t zk_srs_k(const amdzk_srs* srs);
 bool zk_srs_has_basis(const amdzk_srs* srs, int basis);
+const bn254::G1Affine* zk_srs_base_dev(const amdzk_srs* srs, int basis);
 int zk_msm_dev_xyzz(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const bn254::Fr* d_scalars, size_t ncols, size_t len, size_t col_stride,
                     bn254::G1X** d_out);
 int zk_msm_dev_xyzz_cols(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const bn254::Fr* const* d_col_ptrs, size_t ncols, size_t len,

@@ -142,6 +142,13 @@ inline void fq_to_repr(const Fq& a, uint8_t out[32]) {
   Fq c = bn254::from_mont(a);
   memcpy(out, c.l, 32);
 }
+// Fr::DELTA = 7^(2^28)  (contract.sol:440): the permutation argument's coset generator
+inline Fr fr_delta() {
+  Fr r;
+  uint64_t v[4] = {0x870e56bbe533e9a2ULL, 0x5b5f898e5e963f25ULL, 0x64ec26aad4c86e71ULL, 0x09226b6e22c6f0caULL};
+  memcpy(r.l, v, 32);
+  return bn254::to_mont(r);
+}
 // halo2curves 0.3.1 G1Affine::to_bytes [UP recall]: x little-endian; bit 7 of byte 31 = y & 1.
 inline void g1_compress(const bn254::G1Affine& p, uint8_t out[32]) {
   if (p.is_inf()) {

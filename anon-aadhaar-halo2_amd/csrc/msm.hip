@@ -61,6 +61,8 @@ static size_t srs_basis_bytes(const amdzk_srs* s) { return ((size_t)s->W + 1) * 
 uint32_t zk_srs_k(const amdzk_srs* srs) { return srs->k; }
 // an MSM over this basis can run (multiopen.hip asks before it touches the caller's transcript)
 bool zk_srs_has_basis(const amdzk_srs* srs, int basis) { return srs && basis >= 0 && basis < AMDZK_NUM_BASES && srs->table[basis]; }
+// the n bases of a slot on the device, radix 2^256 (verify.hip takes G = g[0] from here); null when not resident
+const G1Affine* zk_srs_base_dev(const amdzk_srs* srs, int basis) { return srs && basis >= 0 && basis < AMDZK_NUM_BASES ? srs->base[basis] : nullptr; }
 
 namespace {
 
@@ -1048,29 +1050,12 @@ __global__ __launch_bounds__(256) void g1_decompress_kernel(const uint8_t* in, G
   G1Affine p;
   p.x = Fq::zero();
   p.y = Fq::zero();
-  bool ok = true;
-  // x must be canonical (< q)
-  {
-    uint32_t borrow = 0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      uint64_t t = (uint64_t)x.l[j] - FqP::p(j) - borrow;
-      borrow = (uint32_t)(t >> 63);
-    }
-    ok = borrow == 1;
-  }
+  bool ok = is_canonical(x);  // x must be canonical (< q)
   if (ok && !(x.is_zero() && ysign == 0)) {
-    Fq xm = to_mont(x);
-    Fq three = add(add(Fq::one(), Fq::one()), Fq::one());
-    Fq rhs = add(mul(sqr(xm), xm), three);
-    // (q+1)/4
-    const uint32_t e[8] = {0xb61f3f52u, 0x4f082305u, 0x5a1c72a3u, 0x65e05aa4u, 0xa0605617u, 0x6e14116du, 0xb84c680au, 0x0c19139cu};
-    Fq y = pow_u256(rhs, e);
-    if (sqr(y) != rhs) {
-      ok = false;
-    } else {
-      Fq yc = from_mont(y);
-      if ((yc.l[0] & 1u) != ysign) y = neg(y);
+    const Fq xm = to_mont(x);
+    Fq y;
+    ok = g1_y_from_x(xm, ysign, &y);
+    if (ok) {
       p.x = xm;
       p.y = y;
     }

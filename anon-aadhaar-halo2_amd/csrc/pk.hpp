@@ -16,12 +16,7 @@ using namespace bn254;  // (every unit that includes this header says so itself)
 // host-format expression words (include/amdzk.h)
 enum : uint32_t { XOP_CONST = 1, XOP_FIXED = 2, XOP_ADVICE = 3, XOP_INSTANCE = 4, XOP_NEG = 5, XOP_ADD = 6, XOP_MUL = 7, XOP_SCALE = 8, XOP_CHALLENGE = 9 };
 
-inline Fr fr_delta() {  // Fr::DELTA = 7^(2^28)  (contract.sol:440)
-  Fr r;
-  uint64_t v[4] = {0x870e56bbe533e9a2ULL, 0x5b5f898e5e963f25ULL, 0x64ec26aad4c86e71ULL, 0x09226b6e22c6f0caULL};
-  memcpy(r.l, v, 32);
-  return to_mont(r);
-}
+using zkhost::fr_delta;  // Fr::DELTA (hostcrypto.hpp)
 
 struct Program {
   std::vector<uint32_t> words;

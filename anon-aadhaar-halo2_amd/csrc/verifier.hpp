@@ -1,0 +1,505 @@
+// The host half of amdzk_verify_proofs (include/amdzk.h): plonk::verify_proof [UP] from the decoded proof
+// elements up to one scalar per base for each of the two sums of the final pairing check. Host-only: no HIP include,
+// compiles with g++ (tests/native/verifier_check.cpp runs it alone, also under ASan + UBSan).
+//
+// Inputs are plain data: the circuit as keygen was given it (pkblob::Desc), the number of circuit instances per proof, the
+// transcript kind, transcript_repr, omega, the public inputs, the proof's points and scalars already decoded (affine /
+// Montgomery: verify.hip's decode kernel, or a test) and the proof's weight rho. Output: for every base one scalar of
+//   L = z_0(u) h2                                                   (SHPLONK)      L = sum_i u^i W_i                    (GWC)
+//   R = sum_i v^i z_i(u) sum_j y^j (C_ij - r_ij(u) G) - Z_T(u) h1 + u z_0(u) h2    R = sum_i u^i (z_i W_i + C_i - e_i G)
+// both times rho, so that the proof is valid iff e(L, [s]_2) = e(R, [1]_2). Bases are numbered
+//   [0, NP)  the proof's own points in the order they are read | NP + c  fixed commitment c | NP + F + i  permutation
+//   commitment i | NP + F + S  G = g[0] of the SRS.
+// The h(X) commitment is no base: its scalar is spread over the pieces with powers of x^n.
+#pragma once
+#include <stdint.h>
+#include <string.h>
+
+#include <map>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "pkblob.hpp"
+
+namespace verifier {
+
+using bn254::Fr;
+using bn254::G1Affine;
+
+constexpr uint32_t NO_SCALAR = 0xffffffffu;
+
+// Where everything is: the byte layout of a proof (a function of the circuit, the number of instances and the transcript
+// kind alone), the read order, the query list in the prover's order and its grouping for the opening argument.
+struct Plan {
+  const pkblob::Desc* d = nullptr;
+  uint32_t N = 1;
+  bool evm = false, gwc = false;
+  uint32_t k = 0, A = 0, F = 0, I = 0, S = 0, L = 0, nsets = 0, chunk = 0, qdeg = 0, bf = 0, nphases = 1;
+  uint64_t n = 0;
+  std::vector<uint8_t> adv_phase;  // per advice column (all 0 for a key without phases)
+  struct Elem {
+    uint32_t offset;    // byte offset in the proof
+    uint32_t is_point;  // 1: a point (32 bytes compressed, or 64 bytes x | y), 0: a scalar (32 bytes)
+    uint32_t index;     // among the proof's points / scalars, in read order
+  };
+  std::vector<Elem> elems;  // in read order
+  uint32_t NP = 0, NS = 0;  // points and scalars of one proof
+  size_t proof_bytes = 0;
+  // points
+  std::vector<uint32_t> adv_pt, la_pt, ls_pt, z_pt, lz_pt;  // [c * A + col], [c * L + l] x 2, [c * nsets + s], [c * L + l]
+  uint32_t rand_pt = 0, h_pt = 0, open_pt = 0;              // h_pt: first of qdeg pieces; open_pt: h1, h2 or the W_z
+  // scalars
+  std::vector<uint32_t> adv_sc, z_sc, lk_sc;  // [c] first advice evaluation; [c * nsets + s] first of 2 or 3; [c * L + l] first of 5
+  uint32_t fix_sc = 0, rand_sc = 0, sig_sc = 0;
+  std::map<std::pair<int, int>, uint32_t> advice_q, fixed_q, instance_q;  // (column, rotation) -> query index
+  // bases
+  uint32_t base_fixed = 0, base_perm = 0, base_g = 0, key_h = 0, n_bases = 0;
+  struct Query {
+    uint32_t key;  // base index, or key_h
+    int32_t rot;
+    uint32_t sc;   // scalar index of the claimed evaluation, NO_SCALAR: the vanishing identity's
+    uint32_t rot_id;
+  };
+  std::vector<Query> queries;
+  std::vector<int32_t> rots;  // distinct evaluation points as rotations of x, first seen first
+  struct Set {                // SHPLONK's rotation sets, first seen first
+    std::vector<uint32_t> rot_ids;                 // ascending
+    std::vector<uint32_t> keys;                    // first seen first
+    std::vector<std::vector<uint32_t>> key_query;  // [key][k]: the query of keys[key] at rots[rot_ids[k]]
+  };
+  std::vector<Set> sets;
+  std::vector<std::vector<uint32_t>> gw;  // GWC: the queries of every distinct point, in their original order
+};
+
+inline int plan_fail(std::string* err, const char* msg) {
+  if (err) *err = std::string("verify_proofs: ") + msg;
+  return AMDZK_E_INVALID;
+}
+
+// d must have passed pkblob::validate (every key has). transcript_kind as for amdzk_create_proof_ex.
+inline int make_plan(const pkblob::Desc& d, uint32_t n_circuits, int transcript_kind, Plan* out, std::string* err) {
+  Plan& p = *out;
+  p = Plan();
+  const int tk = transcript_kind & 0xff;
+  if ((transcript_kind & ~(0xff | AMDZK_MULTIOPEN_GWC)) || (tk != AMDZK_TRANSCRIPT_BLAKE2B && tk != AMDZK_TRANSCRIPT_KECCAK256_EVM))
+    return plan_fail(err, "unknown transcript kind");
+  if (n_circuits == 0 || n_circuits > (1u << 16)) return plan_fail(err, "n_circuits out of range");
+  p.d = &d, p.N = n_circuits, p.evm = tk == AMDZK_TRANSCRIPT_KECCAK256_EVM, p.gwc = (transcript_kind & AMDZK_MULTIOPEN_GWC) != 0;
+  p.k = d.k, p.n = (uint64_t)1 << d.k, p.A = d.num_advice, p.F = d.num_fixed, p.I = d.num_instance, p.S = d.num_perm_columns();
+  p.L = d.num_lookups, p.chunk = d.cs_degree - 2, p.nsets = (p.S + p.chunk - 1) / p.chunk, p.qdeg = d.cs_degree - 1, p.bf = d.blinding_factors;
+  p.adv_phase.assign(p.A, 0);
+  if (d.has_phases) p.adv_phase = d.advice_phase;
+  p.nphases = 1;
+  for (uint8_t ph : p.adv_phase) p.nphases = ph + 1u > p.nphases ? ph + 1u : p.nphases;
+  for (uint8_t ph : d.challenge_phase) p.nphases = ph + 1u > p.nphases ? ph + 1u : p.nphases;
+  const uint32_t N = p.N, psz = p.evm ? 64 : 32;
+  size_t off = 0;
+  auto point = [&]() {
+    p.elems.push_back({(uint32_t)off, 1, p.NP});
+    off += psz;
+    return p.NP++;
+  };
+  auto scalar = [&]() {
+    p.elems.push_back({(uint32_t)off, 0, p.NS});
+    off += 32;
+    return p.NS++;
+  };
+  for (size_t i = 0; i < d.advice_queries.size(); i += 2) p.advice_q[{d.advice_queries[i], d.advice_queries[i + 1]}] = (uint32_t)(i / 2);
+  for (size_t i = 0; i < d.fixed_queries.size(); i += 2) p.fixed_q[{d.fixed_queries[i], d.fixed_queries[i + 1]}] = (uint32_t)(i / 2);
+  for (size_t i = 0; i < d.instance_queries.size(); i += 2) p.instance_q[{d.instance_queries[i], d.instance_queries[i + 1]}] = (uint32_t)(i / 2);
+  // everything a later index must find
+  for (size_t i = 0; i < d.perm_columns.size(); i += 2) {
+    const uint32_t kind = d.perm_columns[i];
+    const std::pair<int, int> key{(int)d.perm_columns[i + 1], 0};
+    const auto& m = kind == 0 ? p.advice_q : kind == 1 ? p.fixed_q : p.instance_q;
+    if (!m.count(key)) return plan_fail(err, "a permutation column is not queried at rotation 0");
+  }
+  for (uint32_t w : d.expr_words) {
+    const uint32_t op = w >> 24, pl = w & 0xffffffu;
+    if (op < 2 || op > 4) continue;
+    const std::pair<int, int> key{(int)(pl >> 8), (int)(pl & 0xff) - 128};
+    const auto& m = op == 3 ? p.advice_q : op == 2 ? p.fixed_q : p.instance_q;
+    if (!m.count(key)) return plan_fail(err, "an expression reads a cell that is in no query list");
+  }
+  const size_t nq_adv = d.advice_queries.size() / 2, nq_fix = d.fixed_queries.size() / 2;
+  // read order: advice commitments phase after phase, inside a phase instance after instance
+  p.adv_pt.assign((size_t)N * p.A, 0);
+  for (uint32_t ph = 0; ph < p.nphases; ph++)
+    for (uint32_t c = 0; c < N; c++)
+      for (uint32_t a = 0; a < p.A; a++)
+        if (p.adv_phase[a] == ph) p.adv_pt[(size_t)c * p.A + a] = point();
+  p.la_pt.resize((size_t)N * p.L), p.ls_pt.resize((size_t)N * p.L), p.lz_pt.resize((size_t)N * p.L), p.z_pt.resize((size_t)N * p.nsets);
+  for (uint32_t c = 0; c < N; c++)
+    for (uint32_t l = 0; l < p.L; l++) p.la_pt[(size_t)c * p.L + l] = point(), p.ls_pt[(size_t)c * p.L + l] = point();
+  for (uint32_t c = 0; c < N; c++)
+    for (uint32_t s = 0; s < p.nsets; s++) p.z_pt[(size_t)c * p.nsets + s] = point();
+  for (uint32_t c = 0; c < N; c++)
+    for (uint32_t l = 0; l < p.L; l++) p.lz_pt[(size_t)c * p.L + l] = point();
+  p.rand_pt = point();
+  p.h_pt = p.NP;
+  for (uint32_t i = 0; i < p.qdeg; i++) point();
+  p.adv_sc.resize(N), p.z_sc.resize((size_t)N * p.nsets), p.lk_sc.resize((size_t)N * p.L);
+  for (uint32_t c = 0; c < N; c++) {
+    p.adv_sc[c] = p.NS;
+    for (size_t q = 0; q < nq_adv; q++) scalar();
+  }
+  p.fix_sc = p.NS;
+  for (size_t q = 0; q < nq_fix; q++) scalar();
+  p.rand_sc = scalar();
+  p.sig_sc = p.NS;
+  for (uint32_t i = 0; i < p.S; i++) scalar();
+  for (uint32_t c = 0; c < N; c++)
+    for (uint32_t s = 0; s < p.nsets; s++) {
+      p.z_sc[(size_t)c * p.nsets + s] = scalar();
+      scalar();
+      if (s + 1 < p.nsets) scalar();
+    }
+  for (uint32_t c = 0; c < N; c++)
+    for (uint32_t l = 0; l < p.L; l++) {
+      p.lk_sc[(size_t)c * p.L + l] = scalar();
+      for (int i = 0; i < 4; i++) scalar();
+    }
+  // bases behind the proof's points (the opening points are appended to NP below)
+  // queries, in the prover's order
+  const int32_t last_rot = -(int32_t)(p.bf + 1);
+  std::vector<Plan::Query> qs;
+  auto Q = [&](uint32_t key, int32_t rot, uint32_t sc) { qs.push_back({key, rot, sc, 0}); };
+  // keys of the VK and of h are patched once NP is final: mark them with the top bits
+  constexpr uint32_t VK = 0x80000000u, HK = 0xc0000000u;
+  for (uint32_t c = 0; c < N; c++) {
+    for (size_t q = 0; q < nq_adv; q++) Q(p.adv_pt[(size_t)c * p.A + d.advice_queries[2 * q]], d.advice_queries[2 * q + 1], p.adv_sc[c] + (uint32_t)q);
+    for (uint32_t s = 0; s < p.nsets; s++) {
+      const uint32_t z = p.z_pt[(size_t)c * p.nsets + s], e = p.z_sc[(size_t)c * p.nsets + s];
+      Q(z, 0, e);
+      Q(z, 1, e + 1);
+    }
+    for (uint32_t s = p.nsets > 0 ? p.nsets - 1 : 0; s-- > 0;) Q(p.z_pt[(size_t)c * p.nsets + s], last_rot, p.z_sc[(size_t)c * p.nsets + s] + 2);
+    for (uint32_t l = 0; l < p.L; l++) {
+      const size_t i = (size_t)c * p.L + l;
+      const uint32_t e = p.lk_sc[i];  // lz(x), lz(wx), la(x), la(w^-1 x), ls(x)
+      Q(p.lz_pt[i], 0, e);
+      Q(p.la_pt[i], 0, e + 2);
+      Q(p.ls_pt[i], 0, e + 4);
+      Q(p.la_pt[i], -1, e + 3);
+      Q(p.lz_pt[i], 1, e + 1);
+    }
+  }
+  for (size_t q = 0; q < nq_fix; q++) Q(VK | (uint32_t)d.fixed_queries[2 * q], d.fixed_queries[2 * q + 1], p.fix_sc + (uint32_t)q);
+  for (uint32_t i = 0; i < p.S; i++) Q(VK | (p.F + i), 0, p.sig_sc + i);
+  Q(HK, 0, NO_SCALAR);
+  Q(p.rand_pt, 0, p.rand_sc);
+  // distinct points: rotations that differ by a multiple of n name the same point
+  auto rot_mod = [&](int32_t r) { return (uint64_t)(((int64_t)r % (int64_t)p.n + (int64_t)p.n) % (int64_t)p.n); };
+  for (auto& q : qs) {
+    uint32_t id = 0;
+    for (; id < p.rots.size(); id++)
+      if (rot_mod(p.rots[id]) == rot_mod(q.rot)) break;
+    if (id == p.rots.size()) p.rots.push_back(q.rot);
+    q.rot_id = id;
+  }
+  p.open_pt = p.NP;
+  const uint32_t n_open = p.gwc ? (uint32_t)p.rots.size() : 2;
+  for (uint32_t i = 0; i < n_open; i++) point();
+  p.proof_bytes = off;
+  p.base_fixed = p.NP, p.base_perm = p.NP + p.F, p.base_g = p.NP + p.F + p.S, p.key_h = p.base_g + 1, p.n_bases = p.base_g + 1;
+  for (auto& q : qs) {
+    if ((q.key & HK) == HK) q.key = p.key_h;
+    else if (q.key & VK) q.key = p.base_fixed + (q.key & ~VK);
+  }
+  p.queries = qs;
+  // grouping (the verifier's side of multiopen's intermediate sets: only membership matters here, the order of a set's
+  // points does not change r_ij(u) or z_i(u))
+  if (p.gwc) {
+    p.gw.resize(p.rots.size());
+    for (size_t i = 0; i < qs.size(); i++) p.gw[qs[i].rot_id].push_back((uint32_t)i);
+  } else {
+    std::vector<uint32_t> coms;                       // keys, first seen first
+    std::vector<std::vector<uint32_t>> com_rots, com_qs;  // per key: ascending rot ids and the query of each
+    for (size_t i = 0; i < qs.size(); i++) {
+      size_t c = 0;
+      for (; c < coms.size(); c++)
+        if (coms[c] == qs[i].key) break;
+      if (c == coms.size()) coms.push_back(qs[i].key), com_rots.emplace_back(), com_qs.emplace_back();
+      auto& r = com_rots[c];
+      size_t pos = 0;
+      while (pos < r.size() && r[pos] < qs[i].rot_id) pos++;
+      if (pos < r.size() && r[pos] == qs[i].rot_id) continue;  // the same (commitment, point) twice: one evaluation
+      r.insert(r.begin() + pos, qs[i].rot_id);
+      com_qs[c].insert(com_qs[c].begin() + pos, (uint32_t)i);
+    }
+    for (size_t c = 0; c < coms.size(); c++) {
+      size_t s = 0;
+      for (; s < p.sets.size(); s++)
+        if (p.sets[s].rot_ids == com_rots[c]) break;
+      if (s == p.sets.size()) p.sets.emplace_back(), p.sets.back().rot_ids = com_rots[c];
+      p.sets[s].keys.push_back(coms[c]);
+      p.sets[s].key_query.push_back(com_qs[c]);
+    }
+  }
+  return AMDZK_OK;
+}
+
+// ---- small field helpers
+inline Fr fr_small(uint64_t v) {
+  Fr a = Fr::zero();
+  a.l[0] = (uint32_t)v, a.l[1] = (uint32_t)(v >> 32);
+  return bn254::to_mont(a);
+}
+inline bool fr_canonical_words(const uint64_t w[4]) {  // Montgomery or not: a residue below the modulus
+  Fr a;
+  memcpy(a.l, w, 32);
+  return bn254::reduce_once(a) == a;
+}
+inline Fr fr_pow2k(Fr a, uint32_t k) {
+  for (uint32_t i = 0; i < k; i++) a = bn254::sqr(a);
+  return a;
+}
+inline Fr fr_pow_signed(const Fr& w, const Fr& winv, int64_t e) { return e >= 0 ? bn254::pow_u64(w, (uint64_t)e) : bn254::pow_u64(winv, (uint64_t)(-e)); }
+
+// ---- transcripts that read: the write classes absorb what the device has already decoded (no decompression here)
+class Blake2bRead : public zkhost::Blake2bWrite {
+ public:
+  void read_point(const G1Affine& p) { common_point(p); }
+  void read_scalar(const Fr& s) { common_scalar(s); }
+};
+class Keccak256Read : public zkhost::Keccak256Write {
+ public:
+  void read_point(const G1Affine& p) { common_point(p); }
+  void read_scalar(const Fr& s) { common_scalar(s); }
+};
+
+// AMDZK_PROOF_BAD_INSTANCE: a value >= r, or a column longer than the usable rows. cols / lens: N x num_instance.
+inline bool instances_ok(const Plan& p, const uint64_t* const* const* inst, const size_t* const* lens, uint32_t* bad_col) {
+  const uint64_t usable = p.n - (p.bf + 1);
+  for (uint32_t c = 0; c < p.N; c++)
+    for (uint32_t i = 0; i < p.I; i++) {
+      const size_t len = lens[c][i];
+      bool ok = len <= usable && (len == 0 || inst[c][i] != nullptr);
+      for (size_t j = 0; ok && j < len; j++) ok = fr_canonical_words(inst[c][i] + 4 * j);
+      if (!ok) {
+        if (bad_col) *bad_col = i;
+        return false;
+      }
+    }
+  return true;
+}
+
+// One proof. pts: NP affine points, scs: NS scalars (Montgomery), both in read order and well formed; inst / lens: the
+// N circuit instances' public inputs (instances_ok). Lout / Rout: n_bases scalars each, overwritten.
+inline void fold_proof(const Plan& p, const Fr& transcript_repr, const Fr& omega, const uint64_t* const* const* inst, const size_t* const* lens,
+                       const G1Affine* pts, const Fr* scs, const Fr& rho, Fr* Lout, Fr* Rout) {
+  using namespace bn254;
+  const pkblob::Desc& d = *p.d;
+  const uint32_t N = p.N;
+  Blake2bRead tb;
+  Keccak256Read tk;
+  zkhost::TranscriptWrite& T = p.evm ? (zkhost::TranscriptWrite&)tk : (zkhost::TranscriptWrite&)tb;
+  T.common_scalar(transcript_repr);
+  for (uint32_t c = 0; c < N; c++)
+    for (uint32_t i = 0; i < p.I; i++)
+      for (size_t j = 0; j < lens[c][i]; j++) {
+        Fr v;
+        memcpy(v.l, inst[c][i] + 4 * j, 32);
+        T.common_scalar(v);
+      }
+  // ---- the transcript, element after element in read order, challenges where the prover squeezed them
+  size_t e = 0;
+  auto take = [&](size_t count) {
+    for (size_t i = 0; i < count; i++, e++) {
+      const Plan::Elem& el = p.elems[e];
+      if (el.is_point) T.common_point(pts[el.index]);
+      else T.common_scalar(scs[el.index]);
+    }
+  };
+  std::vector<Fr> chal(d.num_challenges, Fr::zero());
+  for (uint32_t ph = 0; ph < p.nphases; ph++) {
+    size_t cnt = 0;
+    for (uint8_t a : p.adv_phase) cnt += a == ph;
+    take(cnt * N);
+    for (uint32_t i = 0; i < d.num_challenges; i++)
+      if (d.challenge_phase[i] == ph) chal[i] = T.squeeze_challenge();
+  }
+  const Fr theta = T.squeeze_challenge();
+  take(2 * (size_t)N * p.L);
+  const Fr beta = T.squeeze_challenge();
+  const Fr gamma = T.squeeze_challenge();
+  take((size_t)N * p.nsets + (size_t)N * p.L + 1);
+  const Fr y = T.squeeze_challenge();
+  take(p.qdeg);
+  const Fr x = T.squeeze_challenge();
+  take(p.NS);
+  // ---- the vanishing identity at x
+  const Fr one = Fr::one(), omega_inv = inv(omega);
+  const Fr xn = fr_pow2k(x, p.k);
+  const Fr xn1 = sub(xn, one);
+  const Fr xn1_over_n = mul(xn1, inv(fr_small(p.n)));
+  auto lagrange_at = [&](const Fr& pt, int64_t row) {  // l_row(pt) = w^row (pt^n - 1) / (n (pt - w^row)); pt^n = x^n for a rotation of x
+    const Fr wi = fr_pow_signed(omega, omega_inv, row);
+    return mul(mul(wi, xn1_over_n), inv(sub(pt, wi)));
+  };
+  const Fr l0 = lagrange_at(x, 0), l_last = lagrange_at(x, -(int64_t)(p.bf + 1));
+  Fr l_blind = Fr::zero();
+  for (uint32_t i = 1; i <= p.bf; i++) l_blind = add(l_blind, lagrange_at(x, -(int64_t)i));
+  const Fr l_active = sub(one, add(l_last, l_blind));
+  const Fr delta = zkhost::fr_delta();
+  const size_t nq_inst = d.instance_queries.size() / 2;
+  Fr acc = Fr::zero();
+  std::vector<Fr> stack, inst_e(nq_inst);
+  for (uint32_t c = 0; c < N; c++) {
+    for (size_t q = 0; q < nq_inst; q++) {  // instance columns at x from the public inputs
+      const uint32_t col = (uint32_t)d.instance_queries[2 * q];
+      const Fr pt = mul(x, fr_pow_signed(omega, omega_inv, d.instance_queries[2 * q + 1]));
+      Fr s = Fr::zero(), wj = one;
+      for (size_t j = 0; j < lens[c][col]; j++) {
+        Fr v;
+        memcpy(v.l, inst[c][col] + 4 * j, 32);
+        s = add(s, mul(mul(v, wj), inv(sub(pt, wj))));
+        wj = mul(wj, omega);
+      }
+      inst_e[q] = mul(s, xn1_over_n);
+    }
+    const Fr* adv_e = scs + p.adv_sc[c];
+    const Fr* fix_e = scs + p.fix_sc;
+    auto cell = [&](uint32_t kind, int col, int rot) -> Fr {  // kind: 0 advice, 1 fixed, 2 instance
+      const std::pair<int, int> key{col, rot};
+      if (kind == 0) return adv_e[p.advice_q.find(key)->second];
+      if (kind == 1) return fix_e[p.fixed_q.find(key)->second];
+      return inst_e[p.instance_q.find(key)->second];
+    };
+    auto expr = [&](uint32_t ei) -> Fr {  // the postfix words of expression ei at x
+      stack.clear();
+      for (uint32_t i = d.expr_offsets[ei]; i < d.expr_offsets[ei + 1]; i++) {
+        const uint32_t w = d.expr_words[i], op = w >> 24, pl = w & 0xffffffu;
+        Fr cst;
+        switch (op) {
+          case 1: memcpy(cst.l, d.constants.data() + 4 * (size_t)pl, 32), stack.push_back(cst); break;
+          case 2: stack.push_back(cell(1, (int)(pl >> 8), (int)(pl & 0xff) - 128)); break;
+          case 3: stack.push_back(cell(0, (int)(pl >> 8), (int)(pl & 0xff) - 128)); break;
+          case 4: stack.push_back(cell(2, (int)(pl >> 8), (int)(pl & 0xff) - 128)); break;
+          case 5: stack.back() = neg(stack.back()); break;
+          case 6: cst = stack.back(), stack.pop_back(), stack.back() = add(stack.back(), cst); break;
+          case 7: cst = stack.back(), stack.pop_back(), stack.back() = mul(stack.back(), cst); break;
+          case 8: memcpy(cst.l, d.constants.data() + 4 * (size_t)pl, 32), stack.back() = mul(stack.back(), cst); break;
+          default: stack.push_back(chal[pl]); break;  // 9 CHALLENGE (validate admits nothing else)
+        }
+      }
+      return stack.back();
+    };
+    auto term = [&](const Fr& v) { acc = add(mul(acc, y), v); };
+    for (uint32_t g = 0; g < d.num_gates; g++) term(expr(g));
+    if (p.nsets) {
+      auto Z = [&](uint32_t s, int which) { return scs[p.z_sc[(size_t)c * p.nsets + s] + which]; };  // 0: x, 1: wx, 2: w^last x
+      term(mul(sub(one, Z(0, 0)), l0));
+      const Fr zl = Z(p.nsets - 1, 0);
+      term(mul(sub(sqr(zl), zl), l_last));
+      for (uint32_t s = 1; s < p.nsets; s++) term(mul(sub(Z(s, 0), Z(s - 1, 2)), l0));
+      Fr cur = mul(beta, x);
+      for (uint32_t s = 0; s < p.nsets; s++) {
+        const uint32_t c0 = s * p.chunk, c1 = c0 + p.chunk < p.S ? c0 + p.chunk : p.S;
+        Fr left = Z(s, 1), right = Z(s, 0);
+        for (uint32_t j = c0; j < c1; j++) {
+          const Fr v = cell(d.perm_columns[2 * j], (int)d.perm_columns[2 * j + 1], 0);
+          left = mul(left, add(add(v, mul(beta, scs[p.sig_sc + j])), gamma));
+          right = mul(right, add(add(v, cur), gamma));
+          cur = mul(cur, delta);
+        }
+        term(mul(sub(left, right), l_active));
+      }
+    }
+    uint32_t ei = d.num_gates;
+    for (uint32_t l = 0; l < p.L; l++) {
+      Fr ci = Fr::zero(), ct = Fr::zero();
+      for (uint32_t i = 0; i < d.lookup_shape[2 * l]; i++) ci = add(mul(ci, theta), expr(ei++));
+      for (uint32_t i = 0; i < d.lookup_shape[2 * l + 1]; i++) ct = add(mul(ct, theta), expr(ei++));
+      const Fr* le = scs + p.lk_sc[(size_t)c * p.L + l];
+      const Fr z = le[0], znext = le[1], a = le[2], aprev = le[3], s = le[4];
+      term(mul(sub(one, z), l0));
+      term(mul(sub(sqr(z), z), l_last));
+      term(mul(sub(mul(mul(znext, add(a, beta)), add(s, gamma)), mul(z, mul(add(ci, beta), add(ct, gamma)))), l_active));
+      term(mul(sub(a, s), l0));
+      term(mul(mul(sub(a, s), sub(a, aprev)), l_active));
+    }
+  }
+  const Fr expected_h = mul(acc, inv(xn1));
+  // ---- the opening argument's scalars
+  for (uint32_t i = 0; i < p.n_bases; i++) Lout[i] = Rout[i] = Fr::zero();
+  auto add_key = [&](uint32_t key, const Fr& s) {  // R += s * commitment(key)
+    if (key != p.key_h) {
+      Rout[key] = add(Rout[key], s);
+      return;
+    }
+    Fr t = s;  // h = sum_i x^(n i) h_i
+    for (uint32_t i = 0; i < p.qdeg; i++) {
+      Rout[p.h_pt + i] = add(Rout[p.h_pt + i], t);
+      t = mul(t, xn);
+    }
+  };
+  auto eval_of = [&](const Plan::Query& q) { return q.sc == NO_SCALAR ? expected_h : scs[q.sc]; };
+  std::vector<Fr> pt(p.rots.size());
+  for (size_t i = 0; i < pt.size(); i++) pt[i] = mul(x, fr_pow_signed(omega, omega_inv, p.rots[i]));
+  if (p.gwc) {
+    const Fr v = T.squeeze_challenge();
+    take(p.gw.size());
+    const Fr u = T.squeeze_challenge();
+    Fr up = rho;
+    for (size_t i = 0; i < p.gw.size(); i++) {
+      const uint32_t W = p.open_pt + (uint32_t)i;
+      Lout[W] = add(Lout[W], up);
+      Rout[W] = add(Rout[W], mul(up, pt[i]));
+      Fr vp = up, eb = Fr::zero();
+      for (uint32_t qi : p.gw[i]) {
+        add_key(p.queries[qi].key, vp);
+        eb = add(eb, mul(vp, eval_of(p.queries[qi])));
+        vp = mul(vp, v);
+      }
+      Rout[p.base_g] = sub(Rout[p.base_g], eb);
+      up = mul(up, u);
+    }
+    return;
+  }
+  const Fr yy = T.squeeze_challenge();
+  const Fr v = T.squeeze_challenge();
+  take(1);
+  const Fr u = T.squeeze_challenge();
+  take(1);
+  std::vector<Fr> um(pt.size());  // u - point
+  Fr zt = one;
+  for (size_t i = 0; i < pt.size(); i++) um[i] = sub(u, pt[i]), zt = mul(zt, um[i]);
+  Fr vp = rho, z0 = one;
+  for (size_t si = 0; si < p.sets.size(); si++) {
+    const Plan::Set& st = p.sets[si];
+    Fr zi = one;  // the points outside the set
+    for (size_t i = 0, k = 0; i < pt.size(); i++) {
+      while (k < st.rot_ids.size() && st.rot_ids[k] < i) k++;
+      if (k < st.rot_ids.size() && st.rot_ids[k] == i) continue;
+      zi = mul(zi, um[i]);
+    }
+    if (si == 0) z0 = zi;
+    // Lagrange weights of the set's points at u: prod_{q != p} (u - pt_q) / (pt_p - pt_q)
+    const size_t m = st.rot_ids.size();
+    std::vector<Fr> wgt(m);
+    for (size_t a = 0; a < m; a++) {
+      Fr num = one, den = one;
+      for (size_t b = 0; b < m; b++)
+        if (b != a) num = mul(num, um[st.rot_ids[b]]), den = mul(den, sub(pt[st.rot_ids[a]], pt[st.rot_ids[b]]));
+      wgt[a] = mul(num, inv(den));
+    }
+    Fr coef = mul(vp, zi);
+    for (size_t kq = 0; kq < st.keys.size(); kq++) {
+      Fr ru = Fr::zero();
+      for (size_t a = 0; a < m; a++) ru = add(ru, mul(wgt[a], eval_of(p.queries[st.key_query[kq][a]])));
+      add_key(st.keys[kq], coef);
+      Rout[p.base_g] = sub(Rout[p.base_g], mul(coef, ru));
+      coef = mul(coef, yy);
+    }
+    vp = mul(vp, v);
+  }
+  const uint32_t h1 = p.open_pt, h2 = p.open_pt + 1;
+  const Fr rz0 = mul(rho, z0);
+  Rout[h1] = sub(Rout[h1], mul(rho, zt));
+  Rout[h2] = add(Rout[h2], mul(rz0, u));
+  Lout[h2] = add(Lout[h2], rz0);
+}
+
+}  // namespace verifier

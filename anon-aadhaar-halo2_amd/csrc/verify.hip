@@ -1,0 +1,223 @@
+// amdzk_verify_proofs (include/amdzk.h): plonk::verify_proof [UP] for one proof or a batch, up to the two G1
+// sums of the final pairing check. The device decodes every element of every proof in one launch (decompression with its
+// curve check, range checks, Montgomery conversion) and runs the one two-column MSM; the transcript, the vanishing
+// identity and the per-base scalars are the host half's (verifier.hpp). Two host waits per call. Nothing here touches the
+// key's per-proof workspace.
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "common.hpp"
+#include "pk.hpp"
+#include "verifier.hpp"
+
+using namespace bn254;
+
+namespace {
+
+constexpr int VERIFY_WS_SLOT = 3;  // the start-up calls' slot (SRS read / write / setup): none of them runs inside this call
+constexpr uint32_t DECODE_THREADS = 64;
+constexpr uint32_t STATUS_CLEAN = 0xffffffffu;
+
+struct DecodeArgs {
+  const uint8_t* staging;  // proof b at + b * stride; every element at a multiple of 32 bytes
+  size_t stride;
+  const uint2* elems;  // per element of one proof: (byte offset, is_point << 31 | index among the points / scalars)
+  uint32_t E, NP, NS;
+  size_t total;  // n_proofs * E
+  G1Affine* points;  // [b * NP + index]
+  Fr* scalars;       // [b * NS + index]
+  uint32_t* status;  // per proof: min over its bad elements of offset << 2 | class, STATUS_CLEAN when there is none
+  int evm;
+};
+
+// 32 bytes at a 32-byte-aligned address as a 256-bit integer, little- or big-endian
+template <class F>
+__device__ __forceinline__ F load_u256(const uint8_t* p, bool big_endian) {
+  const uint4* q = reinterpret_cast<const uint4*>(p);
+  const uint4 a = q[0], b = q[1];
+  uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+  F r;
+#pragma unroll
+  for (int j = 0; j < 8; j++) r.l[j] = big_endian ? __builtin_bswap32(w[7 - j]) : w[j];
+  return r;
+}
+__device__ __forceinline__ void store_fq(Fq* p, const Fq& v) {
+  uint4* q = reinterpret_cast<uint4*>(p);
+  q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
+  q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
+}
+
+// One thread per (proof, element). A point costs one Fq square-root chain (254 dependent squarings, Blake2b form) or a
+// curve check (EVM form), a scalar one product: the launch is latency-bound, so the blocks are single waves that the
+// dispatcher spreads over the CUs, and a wave that holds only scalars retires at once.
+__global__ __launch_bounds__(DECODE_THREADS) void proof_decode_kernel(DecodeArgs a) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= a.total) return;
+  const size_t b = t / a.E;
+  const uint2 el = a.elems[t - b * a.E];
+  const uint8_t* src = a.staging + b * a.stride + el.x;
+  const uint32_t index = el.y & 0x7fffffffu;
+  bool ok;
+  uint32_t cls;
+  if (el.y >> 31) {
+    cls = AMDZK_PROOF_BAD_POINT;
+    G1Affine p;
+    p.x = Fq::zero();
+    p.y = Fq::zero();
+    if (a.evm) {  // x | y, big-endian: both canonical, on the curve (which the identity's encoding (0, 0) is not)
+      const Fq x = load_u256<Fq>(src, true), y = load_u256<Fq>(src + 32, true);
+      ok = is_canonical(x) && is_canonical(y);
+      if (ok) {
+        const Fq xm = to_mont(x), ym = to_mont(y);
+        ok = sqr(ym) == g1_curve_rhs(xm);
+        if (ok) p.x = xm, p.y = ym;
+      }
+    } else {  // x little-endian, bit 7 of byte 31 = parity of y; all zero is the identity, which the transcripts refuse
+      Fq x = load_u256<Fq>(src, false);
+      const uint32_t ysign = x.l[7] >> 31;
+      x.l[7] &= 0x7fffffffu;
+      ok = is_canonical(x) && !(x.is_zero() && ysign == 0);
+      if (ok) {
+        const Fq xm = to_mont(x);
+        Fq y;
+        ok = g1_y_from_x(xm, ysign, &y);
+        if (ok) p.x = xm, p.y = y;
+      }
+    }
+    G1Affine* o = a.points + b * a.NP + index;
+    store_fq(&o->x, p.x);
+    store_fq(&o->y, p.y);
+  } else {
+    cls = AMDZK_PROOF_BAD_SCALAR;
+    const Fr s = load_u256<Fr>(src, a.evm != 0);
+    ok = is_canonical(s);
+    const Fr m = ok ? to_mont(s) : Fr::zero();
+    uint4* o = reinterpret_cast<uint4*>(a.scalars + b * a.NS + index);
+    o[0] = make_uint4(m.l[0], m.l[1], m.l[2], m.l[3]);
+    o[1] = make_uint4(m.l[4], m.l[5], m.l[6], m.l[7]);
+  }
+  if (!ok) atomicMin(a.status + b, (el.x << 2) | cls);
+}
+
+size_t pad256(size_t v) { return (v + 255) / 256 * 256; }
+
+}  // namespace
+
+extern "C" int amdzk_verify_proofs(amdzk_ctx* ctx, const amdzk_pk* pk, size_t n_proofs, const uint64_t* const* const* instances,
+                                   const size_t* const* instance_lens, const uint8_t* const* proofs, const size_t* proof_lens,
+                                   const amdzk_verify_opts* opts, amdzk_proof_status* statuses, uint64_t pair_out[16]) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  if (!pk || !proofs || !proof_lens || !statuses || !pair_out) ZK_FAIL(ctx, AMDZK_E_INVALID, "verify_proofs: null argument");
+  if (n_proofs == 0) ZK_FAIL(ctx, AMDZK_E_INVALID, "verify_proofs: n_proofs is 0");
+  if (n_proofs > (1u << 20)) ZK_FAIL(ctx, AMDZK_E_INVALID, "verify_proofs: more than 2^20 proofs in one call");
+  if (opts && opts->size < sizeof(amdzk_verify_opts))
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "verify_proofs: amdzk_verify_opts.size is %zu, this library needs %zu", opts->size, sizeof(amdzk_verify_opts));
+  if (!pk->src_desc || !pk->srs) ZK_FAIL(ctx, AMDZK_E_INVALID, "verify_proofs: the key has no circuit description");
+  const int kind = opts ? opts->transcript_kind : 0;
+  const uint32_t N = opts && opts->n_circuits ? opts->n_circuits : 1;
+  verifier::Plan plan;
+  {
+    std::string why;
+    if (verifier::make_plan(*pk->src_desc, N, kind, &plan, &why) != AMDZK_OK) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s", why.c_str());
+  }
+  if (plan.I && (!instances || !instance_lens)) ZK_FAIL(ctx, AMDZK_E_INVALID, "verify_proofs: null argument (instances)");
+  for (size_t i = 0; plan.I && i < n_proofs * N; i++)
+    if (!instances[i] || !instance_lens[i]) ZK_FAIL(ctx, AMDZK_E_INVALID, "verify_proofs: null argument (instances of circuit %zu)", i);
+  for (size_t b = 0; b < n_proofs; b++)
+    if (!proofs[b]) ZK_FAIL(ctx, AMDZK_E_INVALID, "verify_proofs: null argument (proof %zu)", b);
+  if (plan.proof_bytes != amdzk_proof_size_multi(pk, N, kind) || plan.proof_bytes >= ((size_t)1 << 30))
+    ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "verify_proofs: proof layout of %zu bytes disagrees with amdzk_proof_size_multi or is too large", plan.proof_bytes);
+  std::vector<Fr> rho(n_proofs, Fr::one());
+  if (opts && opts->combine_scalars) {
+    for (size_t b = 0; b < n_proofs; b++) {
+      if (!verifier::fr_canonical_words(opts->combine_scalars + 4 * b)) ZK_FAIL(ctx, AMDZK_E_INVALID, "verify_proofs: combine_scalars[%zu] is not below the modulus", b);
+      memcpy(rho[b].l, opts->combine_scalars + 4 * b, 32);
+    }
+  } else if (n_proofs > 1) {
+    zkhost::ChaCha20Rng rng(opts ? opts->combine_seed : 0);
+    for (size_t b = 0; b < n_proofs; b++) rho[b] = rng.fr();
+  }
+  // ---- what the host can see: lengths and public inputs
+  size_t live = 0;
+  for (size_t b = 0; b < n_proofs; b++) {
+    statuses[b].status = AMDZK_PROOF_WELL_FORMED, statuses[b].offset = 0;
+    uint32_t col = 0;
+    if (proof_lens[b] != plan.proof_bytes) statuses[b].status = AMDZK_PROOF_BAD_LENGTH;
+    else if (plan.I && !verifier::instances_ok(plan, instances + b * N, instance_lens + b * N, &col))
+      statuses[b].status = AMDZK_PROOF_BAD_INSTANCE, statuses[b].offset = col;
+    else live++;
+  }
+  memset(pair_out, 0, 16 * sizeof(uint64_t));
+  if (live == 0) return AMDZK_OK;
+  // ---- one reservation: staging | element table | status words | key commitments | G | decoded points | decoded scalars | MSM scalars
+  const size_t psize = plan.proof_bytes, E = plan.elems.size(), NP = plan.NP, NS = plan.NS, nvk = (size_t)plan.F + plan.S;
+  const size_t nbases = nvk + 1 + n_proofs * NP;
+  const size_t o_elems = pad256(n_proofs * psize), o_status = o_elems + pad256(E * sizeof(uint2)), o_vk = o_status + pad256(n_proofs * 4);
+  const size_t o_g = o_vk + nvk * sizeof(G1Affine), o_points = o_g + sizeof(G1Affine), o_dsc = o_points + n_proofs * NP * sizeof(G1Affine);
+  const size_t o_msm = pad256(o_dsc + n_proofs * NS * 32), total = o_msm + 2 * nbases * 32;
+  const size_t up_bytes = o_g, down_bytes = o_msm - o_status;
+  char* ws = nullptr;
+  ZK_TRY(zk_ws_reserve(ctx, VERIFY_WS_SLOT, total, (void**)&ws));
+  char* pin = nullptr;
+  ZK_TRY(zk_pinned_reserve(ctx, up_bytes + down_bytes, (void**)&pin));
+  char* h_down = pin + up_bytes;
+  memset(pin, 0, up_bytes);
+  for (size_t b = 0; b < n_proofs; b++) {
+    if (statuses[b].status == AMDZK_PROOF_WELL_FORMED) memcpy(pin + b * psize, proofs[b], psize);
+    ((uint32_t*)(pin + o_status))[b] = STATUS_CLEAN;
+  }
+  for (size_t e = 0; e < E; e++) ((uint2*)(pin + o_elems))[e] = make_uint2(plan.elems[e].offset, (plan.elems[e].is_point << 31) | plan.elems[e].index);
+  if (plan.F) memcpy(pin + o_vk, pk->fixed_commitments.data(), (size_t)plan.F * sizeof(G1Affine));
+  if (plan.S) memcpy(pin + o_vk + (size_t)plan.F * sizeof(G1Affine), pk->perm_commitments.data(), (size_t)plan.S * sizeof(G1Affine));
+  const G1Affine* d_g = zk_srs_base_dev(pk->srs, AMDZK_BASIS_G);
+  if (!d_g) ZK_FAIL(ctx, AMDZK_E_INVALID, "verify_proofs: the key's SRS has no monomial basis");
+  ZK_HIP(ctx, hipMemcpyAsync(ws, pin, up_bytes, hipMemcpyHostToDevice, ctx->stream));
+  ZK_HIP(ctx, hipMemcpyAsync(ws + o_g, d_g, sizeof(G1Affine), hipMemcpyDeviceToDevice, ctx->stream));
+  DecodeArgs da;
+  da.staging = (const uint8_t*)ws, da.stride = psize, da.elems = (const uint2*)(ws + o_elems);
+  da.E = (uint32_t)E, da.NP = (uint32_t)NP, da.NS = (uint32_t)NS, da.total = n_proofs * E;
+  da.points = (G1Affine*)(ws + o_points), da.scalars = (Fr*)(ws + o_dsc), da.status = (uint32_t*)(ws + o_status), da.evm = plan.evm ? 1 : 0;
+  const size_t blocks = (da.total + DECODE_THREADS - 1) / DECODE_THREADS;
+  if (blocks > 0x7fffffffu) ZK_FAIL(ctx, AMDZK_E_INVALID, "verify_proofs: batch too large");
+  ZK_LAUNCH(ctx, "proof_decode", proof_decode_kernel, dim3((unsigned)blocks), dim3(DECODE_THREADS), 0, da);
+  ZK_HIP(ctx, hipMemcpyAsync(h_down, ws + o_status, down_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));  // wait 1 of 2
+  // ---- the host half: per proof one scalar per base for L and for R, summed over the batch
+  const uint32_t* h_status = (const uint32_t*)h_down;
+  const G1Affine* h_points = (const G1Affine*)(h_down + (o_points - o_status));
+  const Fr* h_scalars = (const Fr*)(h_down + (o_dsc - o_status));
+  std::vector<Fr> msm(2 * nbases, Fr::zero()), Lb(plan.n_bases), Rb(plan.n_bases);
+  live = 0;
+  for (size_t b = 0; b < n_proofs; b++) {
+    if (statuses[b].status != AMDZK_PROOF_WELL_FORMED) continue;
+    if (h_status[b] != STATUS_CLEAN) {
+      statuses[b].status = h_status[b] & 3u, statuses[b].offset = h_status[b] >> 2;
+      continue;
+    }
+    live++;
+    verifier::fold_proof(plan, pk->transcript_repr, pk->omega, plan.I ? instances + b * N : nullptr, plan.I ? instance_lens + b * N : nullptr,
+                         h_points + b * NP, h_scalars + b * NS, rho[b], Lb.data(), Rb.data());
+    for (uint32_t i = 0; i < plan.n_bases; i++) {
+      const size_t g = i < NP ? nvk + 1 + b * NP + i : i - NP;  // the proof's own points | fixed, permutation, G
+      msm[g] = add(msm[g], Lb[i]);
+      msm[nbases + g] = add(msm[nbases + g], Rb[i]);
+    }
+  }
+  if (live == 0) return AMDZK_OK;
+  // ---- L and R: one MSM of two columns over the decoded points, the key's commitments and G (zero scalars cost nothing)
+  ZK_HIP(ctx, hipMemcpyAsync(ws + o_msm, msm.data(), 2 * nbases * 32, hipMemcpyHostToDevice, ctx->stream));
+  G1X* d_res = nullptr;
+  ZK_TRY(zk_msm_bases_dev_xyzz(ctx, (const Fr*)(ws + o_msm), 2, nbases, nbases, (const G1Affine*)(ws + o_vk), &d_res));
+  uint64_t jac[24];
+  ZK_TRY(zk_msm_finish(ctx, d_res, 2, jac));  // wait 2 of 2
+  for (int c = 0; c < 2; c++) {
+    const G1Jac* j = reinterpret_cast<const G1Jac*>(jac + 12 * c);
+    if (j->z.is_zero()) continue;  // the identity stays (0, 0)
+    memcpy(pair_out + 8 * c, &j->x, 32);
+    memcpy(pair_out + 8 * c + 4, &j->y, 32);
+  }
+  return AMDZK_OK;
+}

@@ -119,6 +119,7 @@ def lib():
         "amdzk_quotient_eval_dev": (i32, [vp, vp, vp, sz, vp, vp, vp, vp, vp]),
         "amdzk_pk_inspect": (i32, [vp, vp, i32, vp, sz, C.POINTER(sz)]),
         "amdzk_check_witness": (i32, [vp, vp, C.POINTER(vp), C.POINTER(sz), vp, sz, vp, vp, sz, C.POINTER(sz)]),
+        "amdzk_verify_proofs": (i32, [vp, vp, sz, C.POINTER(C.POINTER(vp)), C.POINTER(C.POINTER(sz)), C.POINTER(vp), C.POINTER(sz), vp, vp, vp]),
         "amdzk_debug_limb_program": (i32, [vp, sz, vp, sz, C.POINTER(sz), C.POINTER(u32)]),
         "amdzk_pk_h_program": (i32, [vp, vp, sz, C.POINTER(sz)]),
         "amdzk_timer_start": (i32, [vp]),
@@ -171,6 +172,15 @@ class CheckFailure(C.Structure):  # amdzk_check_failure
 
 class CheckOpts(C.Structure):  # amdzk_check_opts
     _fields_ = [("size", C.c_size_t), ("theta_seed", C.c_uint64), ("challenges", C.c_void_p), ("num_challenges", C.c_uint32)]
+
+
+class ProofStatus(C.Structure):  # amdzk_proof_status
+    _fields_ = [("status", C.c_uint32), ("offset", C.c_uint32)]
+
+
+class VerifyOpts(C.Structure):  # amdzk_verify_opts
+    _fields_ = [("size", C.c_size_t), ("transcript_kind", C.c_int), ("n_circuits", C.c_uint32), ("combine_seed", C.c_uint64),
+                ("combine_scalars", C.c_void_p)]
 
 
 OPEN_QUERY = np.dtype([("poly", np.uint32), ("point", np.uint32)])  # amdzk_open_query

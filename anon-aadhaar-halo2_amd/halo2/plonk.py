@@ -803,6 +803,73 @@ def check_witness(ctx, pk, instances, d_advice, theta_seed=0, challenges=None, a
     return WitnessReport(CheckFailure(f.kind, f.index, f.first_row, f.count) for f in buf[:total.value])
 
 
+# include/amdzk.h AMDZK_PROOF_*
+PROOF_WELL_FORMED, PROOF_BAD_LENGTH, PROOF_BAD_POINT, PROOF_BAD_SCALAR, PROOF_BAD_INSTANCE = 0, 1, 2, 3, 4
+PROOF_STATUS_NAMES = ("WELL_FORMED", "BAD_LENGTH", "BAD_POINT", "BAD_SCALAR", "BAD_INSTANCE")
+ProofStatus = collections.namedtuple("ProofStatus", "status offset")
+
+
+class Guard:
+    """What verify_proof / verify_proofs return, upstream's GuardKZG up to the pairing: `lhs`, `rhs` — (8,) uint64 G1Affine
+    words, Montgomery, all zero = the identity — with "every well-formed proof is valid iff e(lhs, [s]_2) = e(rhs, [1]_2)",
+    and `statuses`, one ProofStatus per proof (malformed proofs are in neither sum). The pairing is the caller's."""
+
+    def __init__(self, lhs, rhs, statuses):
+        self.lhs, self.rhs, self.statuses = lhs, rhs, list(statuses)
+
+    @property
+    def well_formed(self):
+        return all(s.status == PROOF_WELL_FORMED for s in self.statuses)
+
+    def __repr__(self):
+        return "Guard(statuses=%r)" % (self.statuses,)
+
+
+def verify_proofs(ctx, pk, instances_list, proofs, transcript=TRANSCRIPT_BLAKE2B, n_circuits=1, combine_seed=0, combine_scalars=None,
+                  opts_size=None):
+    """amdzk_verify_proofs: plonk::verify_proof for a batch up to the one pairing. proofs[b]: bytes; instances_list[b]: proof
+    b's instance columns as for create_proof — or, with n_circuits > 1, a list of n_circuits such lists (create_proof_multi).
+    combine_scalars: (len(proofs), 4) uint64 Montgomery weights of the caller's; else they are drawn from combine_seed, which
+    must then be unpredictable to whoever made the proofs (a single proof has weight 1). Returns a Guard; a refused call raises.
+    opts_size: amdzk_verify_opts.size to report (tests)."""
+    B, N = len(proofs), n_circuits
+    assert len(instances_list) == B
+    keep, inst_pp, lens_pp = [], (C.POINTER(C.c_void_p) * max(1, B * N))(), (C.POINTER(C.c_size_t) * max(1, B * N))()
+    for b, per_proof in enumerate(instances_list):
+        per_circuit = [per_proof] if N == 1 else list(per_proof)
+        assert len(per_circuit) == N
+        for c, instances in enumerate(per_circuit):
+            cols = [np.ascontiguousarray(col, dtype=np.uint64).reshape(-1, 4) for col in instances]
+            ptrs = (C.c_void_p * max(1, len(cols)))(*[col.ctypes.data if col.size else None for col in cols])
+            lens = (C.c_size_t * max(1, len(cols)))(*[col.shape[0] for col in cols])
+            keep += [cols, ptrs, lens]
+            inst_pp[b * N + c] = C.cast(ptrs, C.POINTER(C.c_void_p))
+            lens_pp[b * N + c] = C.cast(lens, C.POINTER(C.c_size_t))
+    bufs = [(C.c_uint8 * max(1, len(p))).from_buffer_copy(bytes(p) if len(p) else b"\0") for p in proofs]
+    pp = (C.c_void_p * max(1, B))(*[C.addressof(b_) for b_ in bufs])
+    pl = (C.c_size_t * max(1, B))(*[len(p) for p in proofs])
+    sc = np.ascontiguousarray(combine_scalars, dtype=np.uint64).reshape(-1, 4) if combine_scalars is not None else None
+    assert sc is None or sc.shape[0] == B
+    opts = _ffi.VerifyOpts(C.sizeof(_ffi.VerifyOpts) if opts_size is None else opts_size, transcript, N, C.c_uint64(combine_seed),
+                           sc.ctypes.data if sc is not None else None)
+    st = (_ffi.ProofStatus * max(1, B))()
+    pair = np.zeros(16, dtype=np.uint64)
+    ctx._chk(ctx.L.amdzk_verify_proofs(ctx.h, pk.h, B, inst_pp, lens_pp, pp, pl, C.byref(opts), st, pair.ctypes.data))
+    del keep
+    return Guard(pair[:8].copy(), pair[8:].copy(), [ProofStatus(s.status, s.offset) for s in st[:B]])
+
+
+def verify_proof(ctx, pk, instances, proof, transcript=TRANSCRIPT_BLAKE2B, n_circuits=1):
+    """plonk::verify_proof(params, vk, SingleStrategy, &[instances], transcript) up to the pairing: one proof, weight 1.
+    Raises ValueError naming the status and the offset when the proof is malformed; returns its Guard otherwise (the proof
+    is valid iff the caller's pairing check of guard.lhs / guard.rhs holds)."""
+    g = verify_proofs(ctx, pk, [instances], [proof], transcript=transcript, n_circuits=n_circuits)
+    s = g.statuses[0]
+    if s.status != PROOF_WELL_FORMED:
+        raise ValueError("malformed proof: status %d (%s), offset %d" % (s.status, PROOF_STATUS_NAMES[s.status], s.offset))
+    return g
+
+
 def proof_size_multi(ctx, pk, n_circuits, transcript=TRANSCRIPT_BLAKE2B):
     return int(ctx.L.amdzk_proof_size_multi(pk.h, n_circuits, transcript))
 

@@ -671,6 +671,57 @@ int amdzk_check_witness(amdzk_ctx* ctx, amdzk_pk* pk, const uint64_t* const* ins
                         const void* d_advice, size_t advice_stride, const amdzk_check_opts* opts /* NULL: defaults */,
                         amdzk_check_failure* out, size_t cap, size_t* n_failures);
 
+/* ---- verify proofs up to the pairing: plonk::verify_proof [UP] for one proof or a batch, everything except the one pairing.
+ * For every well-formed proof b the call re-derives the transcript, computes the vanishing identity at x from the proof's
+ * evaluations (l_0, l_last, l_blind in closed form, instance columns from the public inputs) and folds the opening
+ * argument into two G1 sums, as upstream's verifier does before it hands a guard to its strategy:
+ *   SHPLONK  L_b = z_0(u) h2      R_b = sum_i v^i z_i(u) sum_j y^j (C_ij - r_ij(u) G) - Z_T(u) h1 + u z_0(u) h2
+ *   GWC      L_b = sum_i u^i W_i  R_b = sum_i u^i (z_i W_i + C_i - e_i G)
+ * with G = g[0] of the key's SRS and the h(X) commitment expanded into its pieces with powers of x^n. The result is
+ * L = sum_b rho_b L_b and R = sum_b rho_b R_b in pair_out (L then R, G1Affine, (0, 0) = the identity):
+ *   every well-formed proof of the batch is valid  <=>  e(L, [s]_2) = e(R, [1]_2)     (up to the choice of rho)
+ * The pairing stays with the caller, who holds s_g2 (AccumulatorStrategy / BatchVerifier pair once per batch, SingleStrategy
+ * once per proof); G2 stays opaque to this library. rho_b belongs to position b of the batch, whichever proofs drop out.
+ * rho MUST be unpredictable to whoever made the proofs: take combine_seed from the operating system's generator for every
+ * call, or pass your own combine_scalars. (n_proofs = 1 without combine_scalars uses rho_0 = 1: one proof's pair is
+ * deterministic.) After a failed pairing, find the culprit by calling again on subsets of the batch.
+ *
+ * instances[b * n_circuits + c][col] / instance_lens[...][col]: the public inputs of circuit instance c of proof b, as for
+ * amdzk_create_proof_multi. proofs[b] / proof_lens[b]: the bytes amdzk_create_proof* wrote (built-in transcripts only).
+ * Keys with challenge phases are read in upstream's phased order; n_circuits > 1 reads what amdzk_create_proof_multi wrote.
+ *
+ * The call returns AMDZK_OK whenever it RAN, as amdzk_check_witness does. A malformed proof gets its status and offset in
+ * statuses[b] and drops out of both sums; the others are unaffected. If no proof is well formed both points are the
+ * identity. A well-formed proof that is FALSE is not detected here: it makes the pair fail the caller's pairing.
+ * Decoding (point decompression with its curve check, range checks, Montgomery conversion) runs in one launch over every
+ * (proof, element) pair; the sums are one two-column MSM over the decoded points, the key's commitments and G. Two host
+ * waits per call. The call does not touch the key's per-proof workspace (a proof may be running on the key from another
+ * ctx); it uses only the ctx's scratch, runs on the ctx's stream and returns with it idle. Works on root keys, workspace
+ * clones and keys read from a key file.
+ * Refused with a message that starts "verify_proofs:", the ctx and the key stay usable — AMDZK_E_INVALID for: null
+ * arguments; n_proofs = 0; a too-small opts->size; an unknown transcript kind; a combine_scalars entry >= r.
+ * opts = NULL: Blake2b + SHPLONK, one circuit instance, combine_seed 0 (one proof, or tests). */
+#define AMDZK_PROOF_WELL_FORMED 0
+#define AMDZK_PROOF_BAD_LENGTH 1   /* proof_lens[b] != amdzk_proof_size_multi(pk, n_circuits, transcript_kind) */
+#define AMDZK_PROOF_BAD_POINT 2    /* x or y >= q, not on the curve, or the identity's encoding */
+#define AMDZK_PROOF_BAD_SCALAR 3   /* an evaluation >= r */
+#define AMDZK_PROOF_BAD_INSTANCE 4 /* an instance value >= r, or a column longer than the usable rows */
+typedef struct amdzk_proof_status {
+  uint32_t status;
+  uint32_t offset; /* byte offset of the first offending element in the proof (BAD_POINT, BAD_SCALAR); the column index for BAD_INSTANCE; else 0 */
+} amdzk_proof_status;
+typedef struct amdzk_verify_opts {
+  size_t size;                     /* sizeof(amdzk_verify_opts) as compiled by the caller; too small is refused */
+  int transcript_kind;             /* as amdzk_create_proof_ex, AMDZK_MULTIOPEN_GWC included */
+  uint32_t n_circuits;             /* circuit instances per proof (amdzk_create_proof_multi); 0 means 1 */
+  uint64_t combine_seed;           /* rho_b = the b-th Fr::random of ChaCha20Rng::seed_from_u64(combine_seed) ... */
+  const uint64_t* combine_scalars; /* ... or the caller's own: n_proofs x 4 words, Montgomery; wins if set */
+} amdzk_verify_opts;
+int amdzk_verify_proofs(amdzk_ctx* ctx, const amdzk_pk* pk, size_t n_proofs, const uint64_t* const* const* instances,
+                        const size_t* const* instance_lens, const uint8_t* const* proofs, const size_t* proof_lens,
+                        const amdzk_verify_opts* opts /* NULL: defaults */, amdzk_proof_status* statuses /* n_proofs */,
+                        uint64_t pair_out[16]);
+
 /* Test hooks for the host pass that prepares quotient-domain programs for the limb-resident interpreter (bounds in
  * units of p, placement of the weak reductions, fusion of `t*x` with the accumulate): the pass on caller-supplied words
  * `op << 24 | arg` (opcodes: csrc/plonk_kernels.hpp ExprOp) — pure host code, callable without a device — and the

@@ -1184,6 +1184,86 @@ class WitnessStream {
   void* pin_[2] = {nullptr, nullptr};
 };
 
+// ------------------------------------------------------------------------------------------ verify_proof up to the pairing
+// plonk::verify_proof [UP] without its last step (amdzk_verify_proofs): what upstream's verifier hands to its strategy as a
+// GuardKZG. Every well-formed proof that went in is valid iff e(lhs, [s]_2) = e(rhs, [1]_2) — ONE pairing check, which stays
+// with the caller (params.s_g2() and halo2curves' pairing on the Rust side). (0, 0) is the identity.
+struct ProofStatus {
+  enum Status : uint32_t {
+    WellFormed = AMDZK_PROOF_WELL_FORMED, BadLength = AMDZK_PROOF_BAD_LENGTH, BadPoint = AMDZK_PROOF_BAD_POINT,
+    BadScalar = AMDZK_PROOF_BAD_SCALAR, BadInstance = AMDZK_PROOF_BAD_INSTANCE
+  };
+  Status status;
+  uint32_t offset;  // byte offset of the first offending element (BadPoint, BadScalar), the column (BadInstance), else 0
+};
+struct Guard {
+  G1Affine lhs, rhs;
+  std::vector<ProofStatus> statuses;  // one per proof; malformed proofs are in neither sum
+  bool well_formed() const {
+    for (const ProofStatus& s : statuses)
+      if (s.status != ProofStatus::WellFormed) return false;
+    return true;
+  }
+};
+
+// AccumulatorStrategy / BatchVerifier: one call per batch. instances[b][c][col]: the public inputs of circuit instance c of
+// proof b (n_circuits instances per proof, as create_proof_multi wrote them). combine_scalars: one weight per proof, or
+// empty to draw them from combine_seed — which must then be unpredictable to whoever made the proofs (seed it from the OS).
+// After a failed pairing, call again on subsets to find the culprit.
+inline Guard verify_proofs(const Context& ctx, const ProvingKey& pk, const std::vector<std::vector<std::vector<std::vector<Fr>>>>& instances,
+                           const std::vector<std::vector<uint8_t>>& proofs, Transcript transcript = Transcript::Blake2b,
+                           Multiopen multiopen = Multiopen::Shplonk, uint64_t combine_seed = 0, const std::vector<Fr>& combine_scalars = {}) {
+  const size_t B = proofs.size();
+  if (instances.size() != B) throw Error(AMDZK_E_INVALID, "verify_proofs: one instance list per proof");
+  if (!combine_scalars.empty() && combine_scalars.size() != B) throw Error(AMDZK_E_INVALID, "verify_proofs: one weight per proof");
+  const size_t N = B ? instances[0].size() : 1;
+  std::vector<std::vector<const uint64_t*>> ptrs;
+  std::vector<std::vector<size_t>> lens;
+  for (size_t b = 0; b < B; b++) {
+    if (instances[b].size() != N || N == 0) throw Error(AMDZK_E_INVALID, "verify_proofs: every proof has the same number of circuit instances");
+    for (size_t c = 0; c < N; c++) {
+      const auto& cols = instances[b][c];
+      ptrs.emplace_back(std::max<size_t>(1, cols.size()), nullptr);
+      lens.emplace_back(std::max<size_t>(1, cols.size()), 0);
+      for (size_t i = 0; i < cols.size(); i++) {
+        ptrs.back()[i] = cols[i].empty() ? nullptr : (const uint64_t*)cols[i].data();
+        lens.back()[i] = cols[i].size();
+      }
+    }
+  }
+  std::vector<const uint64_t* const*> inst_pp(std::max<size_t>(1, B * N), nullptr);
+  std::vector<const size_t*> lens_pp(std::max<size_t>(1, B * N), nullptr);
+  for (size_t i = 0; i < ptrs.size(); i++) inst_pp[i] = ptrs[i].data(), lens_pp[i] = lens[i].data();
+  static const uint8_t none = 0;
+  std::vector<const uint8_t*> pp(std::max<size_t>(1, B), nullptr);
+  std::vector<size_t> pl(std::max<size_t>(1, B), 0);
+  for (size_t b = 0; b < B; b++) pp[b] = proofs[b].empty() ? &none : proofs[b].data(), pl[b] = proofs[b].size();
+  amdzk_verify_opts opts = {};
+  opts.size = sizeof(opts);
+  opts.transcript_kind = (int)transcript | (int)multiopen;
+  opts.n_circuits = (uint32_t)N;
+  opts.combine_seed = combine_seed;
+  opts.combine_scalars = combine_scalars.empty() ? nullptr : (const uint64_t*)combine_scalars.data();
+  std::vector<amdzk_proof_status> raw(std::max<size_t>(1, B));
+  uint64_t pair[16];
+  ctx.check(amdzk_verify_proofs(ctx.get(), pk.handle(), B, inst_pp.data(), lens_pp.data(), pp.data(), pl.data(), &opts, raw.data(), pair));
+  Guard g;
+  std::memcpy(&g.lhs, pair, sizeof(G1Affine));
+  std::memcpy(&g.rhs, pair + 8, sizeof(G1Affine));
+  for (size_t b = 0; b < B; b++) g.statuses.push_back(ProofStatus{(ProofStatus::Status)raw[b].status, raw[b].offset});
+  return g;
+}
+
+// SingleStrategy: one proof (weight 1), one call, one pairing. A malformed proof throws, naming status and offset.
+inline Guard verify_proof(const Context& ctx, const ProvingKey& pk, const std::vector<std::vector<Fr>>& instances, const std::vector<uint8_t>& proof,
+                          Transcript transcript = Transcript::Blake2b, Multiopen multiopen = Multiopen::Shplonk) {
+  Guard g = verify_proofs(ctx, pk, {{instances}}, {proof}, transcript, multiopen);
+  if (!g.well_formed())
+    throw Error(AMDZK_E_INVALID, "verify_proof: malformed proof, status " + std::to_string((unsigned)g.statuses[0].status) + ", offset " +
+                                     std::to_string(g.statuses[0].offset));
+  return g;
+}
+
 }  // namespace halo2
 }  // namespace amdzk
 #endif /* AMDZK_HALO2_HPP */
