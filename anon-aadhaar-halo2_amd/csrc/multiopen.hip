@@ -1,8 +1,9 @@
 // poly::kzg::multiopen::{ProverSHPLONK, ProverGWC}::create_proof [UP] over the CALLER's
 // polynomials, points and transcript: amdzk_multiopen_dev / amdzk_multiopen_plan (include/amdzk.h).
 //
-// The arithmetic is the proof path's (prover.hip Prover::{gwc, shplonk, shplonk_final}) on the same kernels — zk_poly_eval,
-// zk_lincomb, zk_kate_div_from, the MSM over AMDZK_BASIS_G — with its own host side: points are arbitrary field elements
+// The grouping and the scalars are opening.hpp's, shared with the proof path (prover.hip Prover::{gwc, shplonk,
+// shplonk_final}) and the verifier; the kernels are the proof path's too — zk_poly_eval, zk_lincomb, zk_kate_div_from, the
+// MSM over AMDZK_BASIS_G. The driver is this file's own: points are arbitrary field elements
 // instead of rotations of x, polynomials are the caller's buffers instead of a key's workspace, scratch is the ctx's
 // (workspace slot 6, one reservation per call whose size the plan reports) instead of a key's, and nothing is capped at 16
 // sets or points or at a key's pointer table: launches whose grid.y would pass 65535 are cut into runs by the host.
@@ -11,13 +12,13 @@
 #include <string.h>
 
 #include <algorithm>
-#include <array>
 #include <map>
 #include <memory>
 #include <string>
 #include <vector>
 
 #include "hostcrypto.hpp"
+#include "opening.hpp"
 #include "plonk_kernels.hpp"
 
 using namespace bn254;
@@ -27,22 +28,13 @@ namespace {
 constexpr size_t MO_MAX_GRID_Y = 65535;  // polynomials per division launch, columns per commitment batch
 constexpr int MO_WS_SLOT = 6;            // the function-by-function calls' slot (plonk_kernels.hip upload_ptrs_and_frs)
 
-using Canon = std::array<uint32_t, 8>;
-Canon canon_of(const uint64_t* mont) {
+Fr canon_of(const uint64_t* mont) {
   Fr a;
   memcpy(a.l, mont, 32);
-  const Fr c = from_mont(a);
-  Canon o;
-  memcpy(o.data(), c.l, 32);
-  return o;
-}
-bool canon_less(const Canon& a, const Canon& b) {
-  for (int i = 7; i >= 0; i--)
-    if (a[i] != b[i]) return a[i] < b[i];
-  return false;
+  return from_mont(a);
 }
 struct CanonLess {
-  bool operator()(const Canon& a, const Canon& b) const { return canon_less(a, b); }
+  bool operator()(const Fr& a, const Fr& b) const { return opening::canon_less(a, b); }
 };
 
 // What both schemes are built from: the distinct point VALUES the queries name (ids in first-seen query order, which is
@@ -58,17 +50,7 @@ struct MoSets {
   std::vector<uint32_t> q_pair;  // query -> (polynomial, point) pair
   std::vector<std::pair<uint32_t, uint32_t>> pairs;  // pair -> (polynomial index, distinct point)
   std::vector<uint32_t> pair_query;                  // pair -> its first query
-  // SHPLONK: construct_intermediate_sets
-  std::vector<uint32_t> com_poly;                                        // commitment -> polynomial index
-  std::vector<std::vector<std::pair<uint32_t, uint32_t>>> com_pts;       // commitment -> (rank, pair), ascending rank
-  struct Set {
-    std::vector<uint32_t> ranks;  // its points, ascending
-    std::vector<uint32_t> coms;   // its commitments, first seen first
-  };
-  std::vector<Set> sets;
-  size_t set_points = 0, maxm = 0;  // sum_i |S_i|, max_i |S_i|
-  // GWC: the queries of every distinct point, in their original order
-  std::vector<std::vector<uint32_t>> gw;
+  opening::Grouping g;  // over (polynomial index, rank): SHPLONK's sets, GWC's queries per point
   uint32_t n_sets = 0, n_out = 0;
   // the call's one reservation: polynomials first, then the pointer tables, then the field-element tables
   size_t poly_count = 0, ptr_count = 0, fr_count = 0, ptr_bytes = 0, scratch_bytes = 0;
@@ -95,18 +77,16 @@ int mo_build(const uint64_t* points, size_t n_points, const amdzk_open_query* qu
   s.gwc = scheme == AMDZK_MULTIOPEN_GWC;
   // distinct point values among the queried indices
   std::vector<uint32_t> dp_of_index(n_points, UINT32_MAX);
-  std::map<Canon, uint32_t, CanonLess> dp_of_value;
-  std::vector<Canon> dp_canon;
+  std::map<Fr, uint32_t, CanonLess> dp_of_value;
   s.q_dp.resize(n_queries);
   for (size_t i = 0; i < n_queries; i++) {
     const uint32_t pi = queries[i].point;
     if (dp_of_index[pi] == UINT32_MAX) {
-      const Canon c = canon_of(points + 4 * (size_t)pi);
+      const Fr c = canon_of(points + 4 * (size_t)pi);
       auto it = dp_of_value.find(c);
       if (it == dp_of_value.end()) {
         it = dp_of_value.emplace(c, (uint32_t)s.dp_index.size()).first;
         s.dp_index.push_back(pi);
-        dp_canon.push_back(c);
       }
       dp_of_index[pi] = it->second;
     }
@@ -133,16 +113,16 @@ int mo_build(const uint64_t* points, size_t n_points, const amdzk_open_query* qu
     s.q_pair[i] = it->second;
   }
   const size_t E = s.pairs.size();
+  std::vector<opening::Query> q(n_queries);
+  for (size_t i = 0; i < n_queries; i++) q[i] = {queries[i].poly, s.dp_rank[s.q_dp[i]]};
+  s.g = opening::group(q.data(), n_queries, n_polys, ndp);
   if (set_of_poly)
     for (size_t i = 0; i < n_polys; i++) set_of_poly[i] = UINT32_MAX;
   size_t ptrs = 0, frs = 0, polys = 0;
   bool ok = true;
   if (s.gwc) {
-    s.gw.resize(ndp);
-    for (size_t i = 0; i < n_queries; i++) {
-      s.gw[s.q_dp[i]].push_back((uint32_t)i);
-      if (set_of_poly) set_of_poly[queries[i].poly] = std::min(set_of_poly[queries[i].poly], s.q_dp[i]);
-    }
+    if (set_of_poly)
+      for (size_t i = 0; i < n_queries; i++) set_of_poly[queries[i].poly] = std::min(set_of_poly[queries[i].poly], s.q_dp[i]);
     s.n_sets = s.n_out = (uint32_t)ndp;
     // pointers: the pairs to evaluate | every query's polynomial | the W_z;  elements: points and results of the
     // evaluations | v^j per query | sum_j v^j eval per point | the points
@@ -150,41 +130,17 @@ int mo_build(const uint64_t* points, size_t n_points, const amdzk_open_query* qu
     ptrs = E + n_queries + ndp;
     frs = 2 * E + n_queries + 2 * ndp;
   } else {
-    std::vector<uint32_t> com_of_poly(n_polys, UINT32_MAX);
-    for (size_t i = 0; i < n_queries; i++) {
-      const uint32_t p = queries[i].poly;
-      if (com_of_poly[p] == UINT32_MAX) {
-        com_of_poly[p] = (uint32_t)s.com_poly.size();
-        s.com_poly.push_back(p);
-        s.com_pts.emplace_back();
-      }
-      auto& v = s.com_pts[com_of_poly[p]];
-      const std::pair<uint32_t, uint32_t> e{s.dp_rank[s.q_dp[i]], s.q_pair[i]};
-      auto pos = std::lower_bound(v.begin(), v.end(), e, [](const auto& a, const auto& b) { return a.first < b.first; });
-      if (pos == v.end() || pos->first != e.first) v.insert(pos, e);
-    }
-    std::map<std::vector<uint32_t>, uint32_t> set_of_ranks;
-    for (size_t c = 0; c < s.com_poly.size(); c++) {
-      std::vector<uint32_t> ranks;
-      for (auto& e : s.com_pts[c]) ranks.push_back(e.first);
-      auto it = set_of_ranks.find(ranks);
-      if (it == set_of_ranks.end()) {
-        it = set_of_ranks.emplace(ranks, (uint32_t)s.sets.size()).first;
-        s.sets.emplace_back();
-        s.sets.back().ranks = ranks;
-      }
-      s.sets[it->second].coms.push_back((uint32_t)c);
-      if (set_of_poly) set_of_poly[s.com_poly[c]] = it->second;
-    }
-    for (auto& st : s.sets) s.set_points += st.ranks.size(), s.maxm = std::max(s.maxm, st.ranks.size());
-    s.n_sets = (uint32_t)s.sets.size();
+    if (set_of_poly)
+      for (size_t i = 0; i < s.g.sets.size(); i++)
+        for (uint32_t c : s.g.sets[i].coms) set_of_poly[s.g.coms[c]] = (uint32_t)i;
+    s.n_sets = (uint32_t)s.g.sets.size();
     s.n_out = 2;
-    const size_t S = s.sets.size(), C = s.com_poly.size(), P = s.set_points;
+    const size_t S = s.g.sets.size(), C = s.g.coms.size(), P = s.g.set_points;
     // pointers: the pairs to evaluate | the polynomials set after set | destinations and sources of the P divisions |
     // the L_i and h(X) | l(X);  elements: points and results of the evaluations | y^j per commitment | the roots, the
     // R_i (maxm coefficients each) and the v^i c_it of the P divisions | the S + 1 final coefficients, the constant term, u
     size_t low = 0;
-    ok = mul_ok(P, s.maxm, &low);
+    ok = mul_ok(P, s.g.maxm, &low);
     polys = S + P + 1;
     ptrs = E + C + 2 * P + S + 2;
     ok = ok && add_ok(2 * E + C + 2 * P + S + 3, low, &frs);
@@ -227,12 +183,6 @@ struct MoTables {
     return AMDZK_OK;
   }
 };
-
-Fr eval_small(const std::vector<Fr>& poly, const Fr& x) {
-  Fr acc = Fr::zero();
-  for (size_t i = poly.size(); i-- > 0;) acc = add(mul(acc, x), poly[i]);
-  return acc;
-}
 
 struct Call {
   amdzk_ctx* ctx;
@@ -334,17 +284,18 @@ struct Call {
   int gwc(const amdzk_open_query* queries) {
     Fr v;
     ZK_TRY(challenge(&v));
-    const size_t Z = s.gw.size();
+    const size_t Z = s.dp_index.size();
+    auto gw = [&](size_t z) -> const std::vector<uint32_t>& { return s.g.gw[s.dp_rank[z]]; };  // output order: first seen first
     std::vector<size_t> p_at(Z), c_at(Z);
     for (size_t z = 0; z < Z; z++) {
       p_at[z] = tab.ptrs.size();
-      for (uint32_t q : s.gw[z]) tab.put(d_polys[queries[q].poly]);
+      for (uint32_t q : gw(z)) tab.put(d_polys[queries[q].poly]);
     }
     std::vector<Fr> eb(Z, Fr::zero());
     for (size_t z = 0; z < Z; z++) {
       c_at[z] = tab.frs.size();
       Fr cur = Fr::one();
-      for (uint32_t q : s.gw[z]) {
+      for (uint32_t q : gw(z)) {
         tab.put(cur);
         eb[z] = add(eb[z], mul(cur, query_eval[q]));
         cur = mul(cur, v);
@@ -358,104 +309,49 @@ struct Call {
     for (size_t z = 0; z < Z; z++) tab.put(point((uint32_t)z));
     ZK_TRY(tab.upload(ctx));
     for (size_t z = 0; z < Z; z++)
-      ZK_TRY(zk_lincomb(ctx, (const Fr* const*)(tab.d_ptrs + p_at[z]), tab.d_frs + c_at[z], (uint32_t)s.gw[z].size(), d_poly + z * n, n, false));
+      ZK_TRY(zk_lincomb(ctx, (const Fr* const*)(tab.d_ptrs + p_at[z]), tab.d_frs + c_at[z], (uint32_t)gw(z).size(), d_poly + z * n, n, false));
     ZK_TRY(divide(w_at, false, 0, root_at, eb_at, 1, Z));
     return commit_write(d_poly, Z, "gwc_w");
   }
 
-  // multiopen/shplonk/prover.rs [UP] in the proof path's formulation (prover.hip Prover::shplonk): L_i = sum_j y^j P_ij,
-  // R_i = the interpolation of E_i[t] = sum_j y^j P_ij(p_t) (interpolation is linear), and with c_it = 1 / prod_{s != t}
-  // (p_t - p_s): (L_i - R_i) / prod_t (X - p_t) = sum_t c_it (L_i - R_i) / (X - p_t) — the points of a set are distinct
-  // and L_i - R_i vanishes at each. All (set, point) quotients are one division; h(X) = sum_it v^i c_it Q_it.
+  // multiopen/shplonk/prover.rs [UP] in opening.hpp's formulation: L_i = sum_j y^j P_ij, all (set, point) quotients
+  // Q_it = (L_i - R_i) / (X - p_t) in one division, h(X) = sum_it v^i c_it Q_it.
   int shplonk() {
     Fr y, v;
     ZK_TRY(challenge(&y));
     ZK_TRY(challenge(&v));
-    const size_t S = s.sets.size(), P = s.set_points, maxm = s.maxm;
+    const opening::Grouping& g = s.g;
+    const size_t S = g.sets.size(), P = g.set_points, maxm = g.maxm;
     Fr* const d_L = d_poly;
     Fr* const d_Q = d_poly + S * n;
     Fr* const d_hx = d_poly + (S + P) * n;
-    std::vector<std::vector<Fr>> pts(S), cinv(S), low(S);
-    std::vector<Fr> dens;
-    for (size_t i = 0; i < S; i++) {
-      for (uint32_t r : s.sets[i].ranks) pts[i].push_back(point(s.rank_dp[r]));
-      const size_t m = pts[i].size();
-      for (size_t t = 0; t < m; t++) {
-        Fr den = Fr::one();
-        for (size_t t2 = 0; t2 < m; t2++)
-          if (t2 != t) den = mul(den, sub(pts[i][t], pts[i][t2]));
-        dens.push_back(den);  // non-zero: the points of a set are distinct values
-      }
-    }
-    {  // one inversion for all c_it (Montgomery's trick)
-      std::vector<Fr> pre(dens.size() + 1, Fr::one());
-      for (size_t j = 0; j < dens.size(); j++) pre[j + 1] = mul(pre[j], dens[j]);
-      Fr acc = inv(pre[dens.size()]);
-      size_t at = dens.size();
-      for (size_t i = S; i-- > 0;) {
-        cinv[i].resize(pts[i].size());
-        for (size_t t = pts[i].size(); t-- > 0;) {
-          at--;
-          cinv[i][t] = mul(acc, pre[at]);
-          acc = mul(acc, dens[at]);
-        }
-      }
-    }
-    for (size_t i = 0; i < S; i++) {
-      const size_t m = pts[i].size();
-      std::vector<Fr> E(m, Fr::zero());
-      Fr yp = Fr::one();
-      for (uint32_t c : s.sets[i].coms) {
-        for (size_t t = 0; t < m; t++) E[t] = add(E[t], mul(yp, pair_eval[s.com_pts[c][t].second]));
-        yp = mul(yp, y);
-      }
-      low[i].assign(m, Fr::zero());
-      for (size_t t = 0; t < m; t++) {
-        std::vector<Fr> num(1, Fr::one());  // prod_{s != t} (X - p_s), ascending coefficients
-        for (size_t t2 = 0; t2 < m; t2++) {
-          if (t2 == t) continue;
-          num.push_back(Fr::zero());
-          for (size_t d = num.size() - 1; d > 0; d--) num[d] = sub(num[d - 1], mul(pts[i][t2], num[d]));
-          num[0] = neg(mul(pts[i][t2], num[0]));
-        }
-        const Fr w = mul(E[t], cinv[i][t]);
-        for (size_t d = 0; d < m; d++) low[i][d] = add(low[i][d], mul(w, num[d]));
-      }
-    }
+    std::vector<Fr> rank_pt(s.rank_dp.size());
+    for (size_t r = 0; r < rank_pt.size(); r++) rank_pt[r] = point(s.rank_dp[r]);
+    const opening::Shplonk sh = opening::shplonk_sets(g, rank_pt.data(), [&](uint32_t q) { return pair_eval[s.q_pair[q]]; }, y, v);
     // tables of the first half
     std::vector<size_t> p_at(S), c_at(S);
     for (size_t i = 0; i < S; i++) {
       p_at[i] = tab.ptrs.size();
-      for (uint32_t c : s.sets[i].coms) tab.put(d_polys[s.com_poly[c]]);
+      for (uint32_t c : g.sets[i].coms) tab.put(d_polys[g.coms[c]]);
     }
     for (size_t i = 0; i < S; i++) {
       c_at[i] = tab.frs.size();
       Fr cur = Fr::one();
-      for (size_t j = 0; j < s.sets[i].coms.size(); j++) tab.put(cur), cur = mul(cur, y);
+      for (size_t j = 0; j < g.sets[i].coms.size(); j++) tab.put(cur), cur = mul(cur, y);
     }
     const size_t dst_at = tab.ptrs.size();
     for (size_t q = 0; q < P; q++) tab.put(d_Q + q * n);
     const size_t src_at = tab.ptrs.size();
-    for (size_t i = 0; i < S; i++)
-      for (size_t t = 0; t < pts[i].size(); t++) tab.put(d_L + i * n);
+    for (size_t q = 0; q < P; q++) tab.put(d_L + sh.row_set[q] * n);
     const size_t root_at = tab.frs.size();
-    for (size_t i = 0; i < S; i++)
-      for (const Fr& p : pts[i]) tab.put(p);
+    for (const Fr& f : sh.root) tab.put(f);
     const size_t low_at = tab.frs.size();
-    for (size_t i = 0; i < S; i++)
-      for (size_t t = 0; t < pts[i].size(); t++)
-        for (size_t d = 0; d < maxm; d++) tab.put(d < low[i].size() ? low[i][d] : Fr::zero());
+    for (const Fr& f : sh.row_low) tab.put(f);
     const size_t coef_at = tab.frs.size();
-    {
-      Fr vpow = Fr::one();
-      for (size_t i = 0; i < S; i++) {
-        for (size_t t = 0; t < pts[i].size(); t++) tab.put(mul(vpow, cinv[i][t]));
-        vpow = mul(vpow, v);
-      }
-    }
+    for (const Fr& f : sh.coef) tab.put(f);
     ZK_TRY(tab.upload(ctx));
     for (size_t i = 0; i < S; i++)
-      ZK_TRY(zk_lincomb(ctx, (const Fr* const*)(tab.d_ptrs + p_at[i]), tab.d_frs + c_at[i], (uint32_t)s.sets[i].coms.size(), d_L + i * n, n, false));
+      ZK_TRY(zk_lincomb(ctx, (const Fr* const*)(tab.d_ptrs + p_at[i]), tab.d_frs + c_at[i], (uint32_t)g.sets[i].coms.size(), d_L + i * n, n, false));
     ZK_TRY(divide(dst_at, true, src_at, root_at, low_at, (uint32_t)maxm, P));
     ZK_TRY(zk_lincomb(ctx, (const Fr* const*)(tab.d_ptrs + dst_at), tab.d_frs + coef_at, (uint32_t)P, d_hx, n, false));
     ZK_TRY(commit_write(d_hx, 1, "shplonk_h1"));
@@ -464,38 +360,16 @@ struct Call {
     // the coefficients
     Fr u;
     ZK_TRY(challenge(&u));
-    const size_t ndp = s.rank_dp.size();
-    std::vector<Fr> diff(ndp);  // u - p by rank
-    Fr zt = Fr::one();
-    for (size_t r = 0; r < ndp; r++) diff[r] = sub(u, point(s.rank_dp[r])), zt = mul(zt, diff[r]);
-    std::vector<Fr> cf(S + 1);
-    Fr cur = Fr::one(), z0 = Fr::one(), cterm = Fr::zero();
-    for (size_t i = 0; i < S; i++) {
-      Fr zi = Fr::one();
-      size_t at = 0;  // ranks are ascending: walk them beside r
-      for (size_t r = 0; r < ndp; r++) {
-        if (at < s.sets[i].ranks.size() && s.sets[i].ranks[at] == r) at++;
-        else zi = mul(zi, diff[r]);
-      }
-      if (i == 0) z0 = zi;
-      const Fr w = mul(cur, zi);
-      cf[i] = w;
-      cterm = add(cterm, mul(w, eval_small(low[i], u)));
-      cur = mul(cur, v);
-    }
-    cf[S] = neg(zt);
-    if (z0.is_zero()) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "multiopen: the challenge u is one of the opening points (probability 2^-254)");
-    const Fr z0inv = inv(z0);
-    for (auto& c : cf) c = mul(c, z0inv);
-    cterm = mul(cterm, z0inv);
+    const opening::Final f = opening::shplonk_final(g, sh, rank_pt.data(), v, u);
+    if (f.z0_zero) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "multiopen: the challenge u is one of the opening points (probability 2^-254)");
     Fr* const d_lx = d_Q;  // the quotients are folded into h(X): their first buffer is free
     const size_t fp_at = tab.ptrs.size();
     for (size_t i = 0; i < S; i++) tab.put(d_L + i * n);
     tab.put(d_hx);
     const size_t lx_at = tab.put(d_lx);
     const size_t fc_at = tab.frs.size();
-    for (auto& c : cf) tab.put(c);
-    const size_t ct_at = tab.put(cterm);
+    for (const Fr& c : f.cf) tab.put(c);
+    const size_t ct_at = tab.put(f.cterm);
     const size_t u_at = tab.put(u);
     ZK_TRY(tab.upload(ctx));
     ZK_TRY(zk_lincomb(ctx, (const Fr* const*)(tab.d_ptrs + fp_at), tab.d_frs + fc_at, (uint32_t)(S + 1), d_lx, n, false));

@@ -8,6 +8,7 @@
 #include <utility>
 #include <vector>
 
+#include "opening.hpp"
 #include "pkblob.hpp"
 #include "plonk_kernels.hpp"
 
@@ -105,7 +106,7 @@ struct amdzk_pk {
   bool use_lanes = true;
   uint32_t max_sets = 16, max_set_points = 0;
   // What the multiopen argument derives from the key alone, built by the first proof (the polynomials live at fixed
-  // addresses in this key's workspace): the evaluation list, the query list and SHPLONK's rotation sets in terms of
+  // addresses in this key's workspace): the evaluation list, the query list and its grouping (opening.hpp) in terms of
   // rotations. Only the ORDER of a set's points (upstream keeps them in a BTreeSet of field elements) depends on x.
   struct Multiopen {
     bool built = false;
@@ -113,14 +114,10 @@ struct amdzk_pk {
     size_t n_written = 0;                           // ... of which the first n_written go to the transcript
     std::vector<int> rots;                          // distinct rotations, first seen first
     std::vector<uint32_t> ev_rot;                   // per evaluation: index into rots
-    std::vector<const Fr*> q_poly;                  // the queries, upstream order
-    std::vector<uint32_t> q_rot, q_ev;              // per query: index into rots / into ev
-    struct Set {
-      std::vector<uint32_t> rot_ids;                // the set's rotations (ascending index into rots)
-      std::vector<const Fr*> polys;                 // its polynomials, first seen first
-      std::vector<std::vector<uint32_t>> ev_idx;    // [poly][k]: evaluation of polys[poly] at rots[rot_ids[k]]
-    };
-    std::vector<Set> sets;                          // first seen first
+    std::vector<const Fr*> com_poly;                // the queried polynomials, first seen first: grp's commitment ids
+    std::vector<opening::Query> q;                  // the queries, upstream order: (index into com_poly, index into rots)
+    std::vector<uint32_t> q_ev;                     // per query: index into ev
+    opening::Grouping grp;                          // SHPLONK's rotation sets and GWC's point sets over q
   } mo;
   Fr *lk_ts = nullptr, *lk_left = nullptr;  // lookup permutation: sorted tables, leftovers [L][n]
   // The first lk_const lookups have ONE table expression over fixed columns and constants only: their compressed table

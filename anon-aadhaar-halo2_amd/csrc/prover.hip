@@ -16,34 +16,18 @@
 #include <string.h>
 
 #include <algorithm>
-#include <array>
 #include <chrono>
 #include <map>
 #include <memory>
 #include <string>
 
 #include "hostcrypto.hpp"
+#include "opening.hpp"
 #include "pk.hpp"
 
 using namespace bn254;
 using zkhost::Blake2bWrite;
 using zkhost::ChaCha20Rng;
-
-namespace {
-
-bool fr_less_canon(const std::array<uint64_t, 4>& a, const std::array<uint64_t, 4>& b) {
-  for (int i = 3; i >= 0; i--)
-    if (a[i] != b[i]) return a[i] < b[i];
-  return false;
-}
-std::array<uint64_t, 4> canon(const Fr& a) {
-  Fr c = from_mont(a);
-  std::array<uint64_t, 4> o;
-  memcpy(o.data(), c.l, 32);
-  return o;
-}
-
-}  // namespace
 
 // Source of the prover's Fr::random draws, addressed by position in upstream's draw order (DrawLayout): draw j is
 // either block ctr0 + j of ChaCha20Rng::seed_from_u64's key stream — every Fr::random this prover makes is exactly one
@@ -143,12 +127,6 @@ Fr rotate_omega(const amdzk_pk* pk, const Fr& x, int rot) {
   return rot >= 0 ? mul(x, pow_u64(pk->omega, (uint64_t)rot)) : mul(x, pow_u64(pk->omega_inv, (uint64_t)(-rot)));
 }
 
-Fr eval_small(const std::vector<Fr>& poly, const Fr& x) {
-  Fr acc = Fr::zero();
-  for (size_t i = poly.size(); i-- > 0;) acc = add(mul(acc, x), poly[i]);
-  return acc;
-}
-
 void trace_fr(const char* label, const Fr& v) {
   if (!getenv("AMDZK_TRACE")) return;
   uint8_t b[32];
@@ -240,7 +218,7 @@ struct DeferredCommit {
 };
 
 // The multiopen argument's lists for pks[0..NC) (amdzk_pk::Multiopen): the evaluations in proof order, then h_poly's;
-// the queries in upstream order; SHPLONK's rotation sets. Built once per key (per list of instance keys).
+// the queries in upstream order and their grouping (opening.hpp). Built once per key (per list of instance keys).
 int build_multiopen(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, amdzk_pk::Multiopen& mo) {
   amdzk_pk* const pk = pks[0];
   const size_t n = pk->n;
@@ -251,10 +229,7 @@ int build_multiopen(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, amdzk_pk::M
     mo.rots.push_back(rot);
     return (uint32_t)mo.rots.size() - 1;
   };
-  auto addq = [&](const Fr* p, int rot) {
-    mo.ev.push_back({p, rot});
-    mo.ev_rot.push_back(rot_id(rot));
-  };
+  auto addq = [&](const Fr* p, int rot) { mo.ev.push_back({p, rot}); };
   // written evaluations: advice (instance after instance), fixed, random, sigma, permutation products (instance after
   // instance), lookups (instance after instance)
   for (size_t ci = 0; ci < NC; ci++)
@@ -281,6 +256,7 @@ int build_multiopen(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, amdzk_pk::M
   // 8. multiopen queries in upstream order
   std::map<std::pair<const Fr*, int>, uint32_t> where;
   for (size_t i = 0; i < mo.ev.size(); i++) where.emplace(mo.ev[i], (uint32_t)i);
+  std::map<const Fr*, uint32_t> com_of;  // polynomial -> commitment id, first seen first
   bool missing = false;
   auto addpq = [&](const Fr* p, int rot) {
     auto it = where.find({p, rot});
@@ -288,8 +264,9 @@ int build_multiopen(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, amdzk_pk::M
       missing = true;
       return;
     }
-    mo.q_poly.push_back(p);
-    mo.q_rot.push_back(rot_id(rot));
+    const uint32_t com = com_of.emplace(p, (uint32_t)mo.com_poly.size()).first->second;
+    if (com == mo.com_poly.size()) mo.com_poly.push_back(p);
+    mo.q.push_back({com, rot_id(rot)});
     mo.q_ev.push_back(it->second);
   };
   // per instance: advice queries, the permutation argument's openings, the lookups' openings; then what exists once
@@ -318,40 +295,11 @@ int build_multiopen(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, amdzk_pk::M
     pk->mo_multi_keys.clear();
     ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: a multiopen query has no evaluation");
   }
-  // shplonk construct_intermediate_sets, in terms of rotations: the polynomials with their sets of rotations
-  // (first seen first), then the distinct sets with their polynomials (first seen first)
-  std::vector<const Fr*> cr_poly;
-  std::vector<std::vector<std::pair<uint32_t, uint32_t>>> cr_rots;  // (rot id, ev index), ascending rot id
-  std::map<const Fr*, uint32_t> cr_of;
-  for (size_t i = 0; i < mo.q_poly.size(); i++) {
-    auto it = cr_of.find(mo.q_poly[i]);
-    if (it == cr_of.end()) {
-      it = cr_of.emplace(mo.q_poly[i], (uint32_t)cr_poly.size()).first;
-      cr_poly.push_back(mo.q_poly[i]);
-      cr_rots.emplace_back();
-    }
-    auto& v = cr_rots[it->second];
-    const std::pair<uint32_t, uint32_t> e{mo.q_rot[i], mo.q_ev[i]};
-    auto pos = std::lower_bound(v.begin(), v.end(), e, [](const auto& x1, const auto& x2) { return x1.first < x2.first; });
-    if (pos == v.end() || pos->first != e.first) v.insert(pos, e);
-  }
-  for (size_t c = 0; c < cr_poly.size(); c++) {
-    std::vector<uint32_t> ids, evs;
-    for (auto& e : cr_rots[c]) ids.push_back(e.first), evs.push_back(e.second);
-    amdzk_pk::Multiopen::Set* hit = nullptr;
-    for (auto& st : mo.sets)
-      if (st.rot_ids == ids) hit = &st;
-    if (!hit) {
-      mo.sets.emplace_back();
-      hit = &mo.sets.back();
-      hit->rot_ids = ids;
-    }
-    hit->polys.push_back(cr_poly[c]);
-    hit->ev_idx.push_back(evs);
-  }
-  size_t pairs = 0;
-  for (auto& st : mo.sets) pairs += st.rot_ids.size();
-  if (mo.sets.size() > pk->max_sets) {
+  // rotation ids are first seen first among the QUERIES: that is GWC's output order
+  mo.grp = opening::group(mo.q.data(), mo.q.size(), mo.com_poly.size(), mo.rots.size());
+  for (auto& e : mo.ev) mo.ev_rot.push_back(rot_id(e.second));
+  const size_t pairs = mo.grp.set_points;
+  if (mo.grp.sets.size() > pk->max_sets) {
     mo = amdzk_pk::Multiopen();
     ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "create_proof: more than %u rotation sets", pk->max_sets);
   }
@@ -361,81 +309,6 @@ int build_multiopen(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, amdzk_pk::M
   }
   mo.built = true;
   return AMDZK_OK;
-}
-
-// SHPLONK's host side (multiopen/shplonk/prover.rs [UP]) for the sets of `mo`, whose points (rot_pt, canonical form
-// rot_canon) are kept in ascending order of the canonical field elements as upstream's BTreeSets do.
-// Per set i with points p_t (ascending): R_i(X) = sum_j y^j R_ij(X), R_ij the interpolation of polynomial j's
-// evaluations. Interpolation is linear, so R_i is the interpolation of E_i[t] = sum_j y^j eval_ij[t]:
-// R_i = sum_t E_i[t] c_it prod_{s != t} (X - p_s), c_it = 1 / prod_{s != t} (p_t - p_s) — one host product per
-// evaluation instead of one small interpolation per polynomial, and ONE field inversion (batched over all c_it)
-// instead of one per basis polynomial and point: the host used to spend 0.26 ms here with the GPU idle.
-struct ShplonkSets {
-  std::vector<std::vector<Fr>> pts;  // per set: its points, ascending
-  std::vector<std::vector<Fr>> c;    // c_it
-  std::vector<std::vector<Fr>> low;  // R_i, coefficients
-};
-ShplonkSets shplonk_interpolate(const amdzk_pk::Multiopen& mo, const std::vector<Fr>& rot_pt,
-                                const std::vector<std::array<uint64_t, 4>>& rot_canon, const std::vector<Fr>& evals, const Fr& ys) {
-  const size_t nr = mo.sets.size();
-  ShplonkSets sh;
-  sh.pts.resize(nr);
-  sh.c.resize(nr);
-  sh.low.resize(nr);
-  std::vector<std::vector<uint32_t>> set_order(nr);  // positions in rot_ids, by ascending point
-  std::vector<Fr> dens;
-  for (size_t i = 0; i < nr; i++) {
-    const amdzk_pk::Multiopen::Set& st = mo.sets[i];
-    const size_t m = st.rot_ids.size();
-    std::vector<uint32_t>& order = set_order[i];
-    order.resize(m);
-    for (size_t t = 0; t < m; t++) order[t] = (uint32_t)t;
-    std::sort(order.begin(), order.end(),
-              [&](uint32_t t1, uint32_t t2) { return fr_less_canon(rot_canon[st.rot_ids[t1]], rot_canon[st.rot_ids[t2]]); });
-    for (size_t t = 0; t < m; t++) sh.pts[i].push_back(rot_pt[st.rot_ids[order[t]]]);
-    for (size_t t = 0; t < m; t++) {
-      Fr den = Fr::one();
-      for (size_t s2 = 0; s2 < m; s2++)
-        if (s2 != t) den = mul(den, sub(sh.pts[i][t], sh.pts[i][s2]));
-      dens.push_back(den);  // non-zero: the points of a set are distinct
-    }
-  }
-  // Montgomery's trick: prefix products, one inversion, walk back
-  std::vector<Fr> pre(dens.size() + 1, Fr::one());
-  for (size_t k2 = 0; k2 < dens.size(); k2++) pre[k2 + 1] = mul(pre[k2], dens[k2]);
-  Fr acc = inv(pre[dens.size()]);
-  std::vector<Fr> dinv(dens.size());
-  for (size_t k2 = dens.size(); k2-- > 0;) {
-    dinv[k2] = mul(acc, pre[k2]);
-    acc = mul(acc, dens[k2]);
-  }
-  size_t at = 0;
-  for (size_t i = 0; i < nr; i++)
-    for (size_t t = 0; t < sh.pts[i].size(); t++) sh.c[i].push_back(dinv[at++]);
-  for (size_t i = 0; i < nr; i++) {
-    const amdzk_pk::Multiopen::Set& st = mo.sets[i];
-    const std::vector<Fr>& pts = sh.pts[i];
-    const size_t np = pts.size();
-    std::vector<Fr> E(np, Fr::zero());
-    Fr yp = Fr::one();
-    for (size_t j = 0; j < st.polys.size(); j++) {
-      for (size_t t = 0; t < np; t++) E[t] = add(E[t], mul(yp, evals[st.ev_idx[j][set_order[i][t]]]));
-      yp = mul(yp, ys);
-    }
-    sh.low[i].assign(np, Fr::zero());
-    for (size_t t = 0; t < np; t++) {
-      std::vector<Fr> num(1, Fr::one());  // prod_{s != t} (X - p_s), ascending coefficients
-      for (size_t s2 = 0; s2 < np; s2++) {
-        if (s2 == t) continue;
-        num.push_back(Fr::zero());
-        for (size_t d = num.size() - 1; d > 0; d--) num[d] = sub(num[d - 1], mul(pts[s2], num[d]));
-        num[0] = neg(mul(pts[s2], num[0]));
-      }
-      const Fr w = mul(E[t], sh.c[i][t]);
-      for (size_t d = 0; d < np; d++) sh.low[i][d] = add(sh.low[i][d], mul(w, num[d]));
-    }
-  }
-  return sh;
 }
 
 // One create_proof in flight: what its phases share, and the phases themselves (create_proof_body runs them in order).
@@ -465,8 +338,7 @@ struct Prover {
   // the multiopen lists (the key's) and what evaluations() leaves for the opening argument
   amdzk_pk::Multiopen* mo = nullptr;
   std::vector<Fr> rot_pt, evals;  // the points x * omega^rot, once per distinct rotation; the evaluations
-  std::vector<std::array<uint64_t, 4>> rot_canon;
-  ShplonkSets sh;
+  opening::Shplonk sh;
   amdzk_phase_fn phase_fn = nullptr;  // amdzk_proof_opts: the caller's synthesize of phases >= 1
   void* phase_user = nullptr;
   // Member of a gang (serial, one instance): commit_begin / commit_write leave their batch here instead of launching it
@@ -887,11 +759,7 @@ struct Prover {
     if (!mo->built) ZK_TRY(build_multiopen(ctx, pks, NC, *mo));
     const size_t nrot = mo->rots.size();
     rot_pt.resize(nrot);
-    rot_canon.resize(nrot);
-    for (size_t r = 0; r < nrot; r++) {
-      rot_pt[r] = rotate_omega(pk, x, mo->rots[r]);
-      rot_canon[r] = canon(rot_pt[r]);
-    }
+    for (size_t r = 0; r < nrot; r++) rot_pt[r] = rotate_omega(pk, x, mo->rots[r]);
     const size_t nq = mo->ev.size();
     if (nq > pk->ptrs_cap || 2 * nq > pk->small_cap) ZK_FAIL(ctx, AMDZK_E_NOMEM, "create_proof: too many queries (%zu)", nq);
     ev_pp.resize(nq);
@@ -907,44 +775,30 @@ struct Prover {
   // 9a. GWC (multiopen/gwc/prover.rs [UP]): queries grouped by point in first-seen order;
   // per point z:  W_z = (sum_j v^j p_j - sum_j v^j p_j(z)) / (X - z), committed and written in that order.
   int gwc(const Fr& v) {
-    struct PS {
-      Fr z;
-      std::vector<const Fr*> polys;
-      std::vector<Fr> evals;
-    };
-    std::vector<PS> psets;  // one per distinct point (= distinct rotation), first seen first
-    std::vector<int> ps_of_rot(rot_pt.size(), -1);
-    for (size_t i = 0; i < mo->q_poly.size(); i++) {
-      const uint32_t r = mo->q_rot[i];
-      if (ps_of_rot[r] < 0) {
-        ps_of_rot[r] = (int)psets.size();
-        psets.push_back(PS{rot_pt[r], {}, {}});
-      }
-      PS& hit = psets[ps_of_rot[r]];
-      hit.polys.push_back(mo->q_poly[i]);
-      hit.evals.push_back(evals[mo->q_ev[i]]);
-    }
-    const size_t np = psets.size();
+    const std::vector<std::vector<uint32_t>>& gw = mo->grp.gw;  // one per distinct point (= distinct rotation), first seen first
+    const size_t np = gw.size();
     if (np > 16) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "create_proof: more than 16 opening points");
     for (size_t i = 0; i < np; i++) {
-      const size_t m = psets[i].polys.size();
+      const size_t m = gw[i].size();
       if (m > pk->ptrs_cap || m + 1 > pk->small_cap) ZK_FAIL(ctx, AMDZK_E_NOMEM, "create_proof: opening set too large");
+      std::vector<const Fr*> polys(m);
       std::vector<Fr> cf(m);
       Fr cur = Fr::one(), eb = Fr::zero();
       for (size_t j = 0; j < m; j++) {
+        polys[j] = mo->com_poly[mo->q[gw[i][j]].com];
         cf[j] = cur;
-        eb = add(eb, mul(cur, psets[i].evals[j]));
+        eb = add(eb, mul(cur, evals[mo->q_ev[gw[i][j]]]));
         cur = mul(cur, v);
       }
       Fr* Wi = pk->sets_N + i * n;
-      ZK_TRY(lincomb(M, psets[i].polys, cf, Wi, n, {eb}));
+      ZK_TRY(lincomb(M, polys, cf, Wi, n, {eb}));
       ZK_TRY(zk_sub_low(ctx, Wi, pk->small + m, 1));
     }
     std::vector<Fr*> pp(np);
     std::vector<Fr> roots(np);
     for (size_t i = 0; i < np; i++) {
       pp[i] = pk->sets_N + i * n;
-      roots[i] = psets[i].z;
+      roots[i] = rot_pt[i];
     }
     ZK_TRY(h2d_staged(ctx, pk, pk->ptrs, pp.data(), np * sizeof(Fr*)));
     ZK_TRY(upload_small_on(M, roots, 0));
@@ -953,88 +807,58 @@ struct Prover {
   }
   // 9b. SHPLONK (multiopen/shplonk/prover.rs [UP]), up to its first commitment h(X)
   int shplonk(const Fr& ys, const Fr& v) {
-    const size_t nr = mo->sets.size();
+    const opening::Grouping& g = mo->grp;
+    const size_t nr = g.sets.size(), maxm = g.maxm;
     if (nr > 16) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "create_proof: more than 16 rotation sets");
-    sh = shplonk_interpolate(*mo, rot_pt, rot_canon, evals, ys);
+    sh = opening::shplonk_sets(g, rot_pt.data(), [&](uint32_t q) { return evals[mo->q_ev[q]]; }, ys, v);
     // L_i = sum_j y^j P_ij ; N_i = (L_i - R_i) / prod_t (X - p_t), R_i = sum_j y^j R_ij. The division runs once, not once
     // per point: 1 / prod_t (X - p_t) = sum_t c_t / (X - p_t) with c_t = 1 / prod_{s != t} (p_t - p_s) (the points of a
     // set are distinct), and L_i - R_i vanishes at every p_t, so N_i = sum_t c_t Q_it with Q_it = (L_i - R_i) / (X - p_t)
     // — all (set, point) quotients in ONE division launch, then h(X) = sum_i v^i N_i = sum_it (v^i c_it) Q_it in one
     // linear combination. Exact arithmetic, same polynomial. The L_i of different sets are independent: one lane each.
-    size_t maxm = 0;
-    for (size_t i = 0; i < nr; i++) maxm = std::max(maxm, sh.pts[i].size());
-    std::vector<const Fr*> q_src;
-    std::vector<Fr*> q_dst;
-    std::vector<Fr> q_root, q_low, q_coef;
     amdzk_ctx* lanes3[3] = {M, B, C};
-    Fr vpow = Fr::one();
     for (size_t i = 0; i < nr; i++) {
-      const size_t m = mo->sets[i].polys.size(), np = sh.pts[i].size();
+      const size_t m = g.sets[i].coms.size();
       if (m > pk->ptrs_cap || m > pk->small_cap / 2) ZK_FAIL(ctx, AMDZK_E_NOMEM, "create_proof: rotation set too large");
+      std::vector<const Fr*> polys(m);
       std::vector<Fr> cf(m);
       Fr cur = Fr::one();
       for (size_t j = 0; j < m; j++) {
+        polys[j] = mo->com_poly[g.coms[g.sets[i].coms[j]]];
         cf[j] = cur;
         cur = mul(cur, ys);
       }
       amdzk_ctx* ln = lanes3[i % 3];
       if (ln != M && i < 3) ZK_TRY(zk_stream_after(ln, M));  // the evaluations above came off M; hpoly is in place
-      Fr* Li = pk->sets_L + i * n;
-      ZK_TRY(lincomb(ln, mo->sets[i].polys, cf, Li, n));
-      for (size_t t = 0; t < np; t++) {
-        q_src.push_back(Li);
-        q_dst.push_back(pk->sets_Q + q_dst.size() * n);
-        q_root.push_back(sh.pts[i][t]);
-        q_coef.push_back(mul(vpow, sh.c[i][t]));
-        for (size_t d = 0; d < maxm; d++) q_low.push_back(d < np ? sh.low[i][d] : Fr::zero());
-      }
-      vpow = mul(vpow, v);
+      ZK_TRY(lincomb(ln, polys, cf, pk->sets_L + i * n, n));
     }
     ZK_TRY(zk_stream_after(M, B));
     ZK_TRY(zk_stream_after(M, C));
-    const size_t nq = q_dst.size();
+    const size_t nq = sh.root.size();
     if (2 * nq > pk->ptrs_cap || nq * (maxm + 2) > pk->small_cap) ZK_FAIL(ctx, AMDZK_E_NOMEM, "create_proof: too many opening points");
+    std::vector<const Fr*> q_src(nq);
+    std::vector<Fr*> q_dst(nq);
+    for (size_t q = 0; q < nq; q++) q_src[q] = pk->sets_L + sh.row_set[q] * n, q_dst[q] = pk->sets_Q + q * n;
     void** pt = (void**)pk->ptrs;
     ZK_TRY(h2d_staged(ctx, pk, pt, q_dst.data(), nq * sizeof(Fr*)));
     ZK_TRY(h2d_staged(ctx, pk, pt + nq, q_src.data(), nq * sizeof(Fr*)));
-    ZK_TRY(upload_small_on(M, q_root, 0));
-    ZK_TRY(upload_small_on(M, q_low, nq));
-    ZK_TRY(upload_small_on(M, q_coef, nq + q_low.size()));
+    ZK_TRY(upload_small_on(M, sh.root, 0));
+    ZK_TRY(upload_small_on(M, sh.row_low, nq));
+    ZK_TRY(upload_small_on(M, sh.coef, nq + sh.row_low.size()));
     ZK_TRY(zk_kate_div_from(ctx, (Fr* const*)pt, (const Fr* const*)(pt + nq), pk->small, pk->small + nq, (uint32_t)maxm, nq, (uint32_t)n));
-    ZK_TRY(zk_lincomb(ctx, (const Fr* const*)pt, pk->small + nq + q_low.size(), (uint32_t)nq, pk->hx, n, false));
+    ZK_TRY(zk_lincomb(ctx, (const Fr* const*)pt, pk->small + nq + sh.row_low.size(), (uint32_t)nq, pk->hx, n, false));
     return commit_write(AMDZK_BASIS_G, pk->hx, 1, "shplonk_h1");
   }
   // ... and its second: l(X) = sum_i v^i z_i (L_i - r_i) - zt(u) h(X);  then / (X - u) / z_0 — the factor 1 / z_0 rides
-  // in on the coefficients. The super point set is kept in ascending order of the canonical field elements.
+  // in on the coefficients (opening::shplonk_final).
   int shplonk_final(const Fr& v, const Fr& u) {
-    const size_t nr = mo->sets.size();
-    std::vector<uint32_t> super(rot_pt.size());
-    for (size_t r = 0; r < super.size(); r++) super[r] = (uint32_t)r;
-    std::sort(super.begin(), super.end(), [&](uint32_t r1, uint32_t r2) { return fr_less_canon(rot_canon[r1], rot_canon[r2]); });
-    Fr zt = Fr::one();
-    for (uint32_t r : super) zt = mul(zt, sub(u, rot_pt[r]));
+    const size_t nr = mo->grp.sets.size();
+    const opening::Final f = opening::shplonk_final(mo->grp, sh, rot_pt.data(), v, u);
     std::vector<const Fr*> pp(nr + 1);
-    std::vector<Fr> cf(nr + 1);
-    Fr cur = Fr::one(), z0 = Fr::one(), cterm = Fr::zero();
-    for (size_t i = 0; i < nr; i++) {
-      Fr zi = Fr::one();
-      for (uint32_t r : super)
-        if (!std::binary_search(mo->sets[i].rot_ids.begin(), mo->sets[i].rot_ids.end(), r)) zi = mul(zi, sub(u, rot_pt[r]));
-      if (i == 0) z0 = zi;
-      const Fr ri = eval_small(sh.low[i], u);  // R_i(u) = sum_j y^j R_ij(u)
-      Fr w = mul(cur, zi);
-      pp[i] = pk->sets_L + i * n;
-      cf[i] = w;
-      cterm = add(cterm, mul(w, ri));
-      cur = mul(cur, v);
-    }
+    for (size_t i = 0; i < nr; i++) pp[i] = pk->sets_L + i * n;
     pp[nr] = pk->hx;
-    cf[nr] = neg(zt);
-    const Fr z0inv = inv(z0);
-    for (auto& c : cf) c = mul(c, z0inv);
-    cterm = mul(cterm, z0inv);
     Fr* lx = pk->sets_Q;  // reuse
-    ZK_TRY(lincomb(M, pp, cf, lx, n, {cterm, u}));
+    ZK_TRY(lincomb(M, pp, f.cf, lx, n, {f.cterm, u}));
     std::vector<Fr*> one_p = {lx};
     ZK_TRY(h2d_staged(ctx, pk, (void**)pk->ptrs + nr + 1, one_p.data(), sizeof(Fr*)));
     ZK_TRY(zk_kate_div_from(ctx, (Fr* const*)((void**)pk->ptrs + nr + 1), nullptr, pk->small + nr + 2, pk->small + nr + 1, 1, 1, (uint32_t)n));

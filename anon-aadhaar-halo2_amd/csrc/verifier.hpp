@@ -20,6 +20,7 @@
 #include <utility>
 #include <vector>
 
+#include "opening.hpp"
 #include "pkblob.hpp"
 
 namespace verifier {
@@ -30,7 +31,7 @@ using bn254::G1Affine;
 constexpr uint32_t NO_SCALAR = 0xffffffffu;
 
 // Where everything is: the byte layout of a proof (a function of the circuit, the number of instances and the transcript
-// kind alone), the read order, the query list in the prover's order and its grouping for the opening argument.
+// kind alone), the read order, the query list in the prover's order and its grouping for the opening argument (opening.hpp).
 struct Plan {
   const pkblob::Desc* d = nullptr;
   uint32_t N = 1;
@@ -63,13 +64,7 @@ struct Plan {
   };
   std::vector<Query> queries;
   std::vector<int32_t> rots;  // distinct evaluation points as rotations of x, first seen first
-  struct Set {                // SHPLONK's rotation sets, first seen first
-    std::vector<uint32_t> rot_ids;                 // ascending
-    std::vector<uint32_t> keys;                    // first seen first
-    std::vector<std::vector<uint32_t>> key_query;  // [key][k]: the query of keys[key] at rots[rot_ids[k]]
-  };
-  std::vector<Set> sets;
-  std::vector<std::vector<uint32_t>> gw;  // GWC: the queries of every distinct point, in their original order
+  opening::Grouping grp;      // over (key, rot_id): SHPLONK's rotation sets, GWC's queries of every distinct point
 };
 
 inline int plan_fail(std::string* err, const char* msg) {
@@ -208,35 +203,9 @@ inline int make_plan(const pkblob::Desc& d, uint32_t n_circuits, int transcript_
     else if (q.key & VK) q.key = p.base_fixed + (q.key & ~VK);
   }
   p.queries = qs;
-  // grouping (the verifier's side of multiopen's intermediate sets: only membership matters here, the order of a set's
-  // points does not change r_ij(u) or z_i(u))
-  if (p.gwc) {
-    p.gw.resize(p.rots.size());
-    for (size_t i = 0; i < qs.size(); i++) p.gw[qs[i].rot_id].push_back((uint32_t)i);
-  } else {
-    std::vector<uint32_t> coms;                       // keys, first seen first
-    std::vector<std::vector<uint32_t>> com_rots, com_qs;  // per key: ascending rot ids and the query of each
-    for (size_t i = 0; i < qs.size(); i++) {
-      size_t c = 0;
-      for (; c < coms.size(); c++)
-        if (coms[c] == qs[i].key) break;
-      if (c == coms.size()) coms.push_back(qs[i].key), com_rots.emplace_back(), com_qs.emplace_back();
-      auto& r = com_rots[c];
-      size_t pos = 0;
-      while (pos < r.size() && r[pos] < qs[i].rot_id) pos++;
-      if (pos < r.size() && r[pos] == qs[i].rot_id) continue;  // the same (commitment, point) twice: one evaluation
-      r.insert(r.begin() + pos, qs[i].rot_id);
-      com_qs[c].insert(com_qs[c].begin() + pos, (uint32_t)i);
-    }
-    for (size_t c = 0; c < coms.size(); c++) {
-      size_t s = 0;
-      for (; s < p.sets.size(); s++)
-        if (p.sets[s].rot_ids == com_rots[c]) break;
-      if (s == p.sets.size()) p.sets.emplace_back(), p.sets.back().rot_ids = com_rots[c];
-      p.sets[s].keys.push_back(coms[c]);
-      p.sets[s].key_query.push_back(com_qs[c]);
-    }
-  }
+  std::vector<opening::Query> oq;
+  for (auto& q : qs) oq.push_back({q.key, q.rot_id});
+  p.grp = opening::group(oq.data(), oq.size(), p.key_h + 1, p.rots.size());
   return AMDZK_OK;
 }
 
@@ -440,15 +409,15 @@ inline void fold_proof(const Plan& p, const Fr& transcript_repr, const Fr& omega
   for (size_t i = 0; i < pt.size(); i++) pt[i] = mul(x, fr_pow_signed(omega, omega_inv, p.rots[i]));
   if (p.gwc) {
     const Fr v = T.squeeze_challenge();
-    take(p.gw.size());
+    take(p.rots.size());
     const Fr u = T.squeeze_challenge();
     Fr up = rho;
-    for (size_t i = 0; i < p.gw.size(); i++) {
+    for (size_t i = 0; i < p.rots.size(); i++) {
       const uint32_t W = p.open_pt + (uint32_t)i;
       Lout[W] = add(Lout[W], up);
       Rout[W] = add(Rout[W], mul(up, pt[i]));
       Fr vp = up, eb = Fr::zero();
-      for (uint32_t qi : p.gw[i]) {
+      for (uint32_t qi : p.grp.gw[i]) {
         add_key(p.queries[qi].key, vp);
         eb = add(eb, mul(vp, eval_of(p.queries[qi])));
         vp = mul(vp, v);
@@ -463,38 +432,22 @@ inline void fold_proof(const Plan& p, const Fr& transcript_repr, const Fr& omega
   take(1);
   const Fr u = T.squeeze_challenge();
   take(1);
-  std::vector<Fr> um(pt.size());  // u - point
-  Fr zt = one;
-  for (size_t i = 0; i < pt.size(); i++) um[i] = sub(u, pt[i]), zt = mul(zt, um[i]);
-  Fr vp = rho, z0 = one;
-  for (size_t si = 0; si < p.sets.size(); si++) {
-    const Plan::Set& st = p.sets[si];
-    Fr zi = one;  // the points outside the set
-    for (size_t i = 0, k = 0; i < pt.size(); i++) {
-      while (k < st.rot_ids.size() && st.rot_ids[k] < i) k++;
-      if (k < st.rot_ids.size() && st.rot_ids[k] == i) continue;
-      zi = mul(zi, um[i]);
-    }
-    if (si == 0) z0 = zi;
-    // Lagrange weights of the set's points at u: prod_{q != p} (u - pt_q) / (pt_p - pt_q)
-    const size_t m = st.rot_ids.size();
-    std::vector<Fr> wgt(m);
-    for (size_t a = 0; a < m; a++) {
-      Fr num = one, den = one;
-      for (size_t b = 0; b < m; b++)
-        if (b != a) num = mul(num, um[st.rot_ids[b]]), den = mul(den, sub(pt[st.rot_ids[a]], pt[st.rot_ids[b]]));
-      wgt[a] = mul(num, inv(den));
-    }
-    Fr coef = mul(vp, zi);
-    for (size_t kq = 0; kq < st.keys.size(); kq++) {
-      Fr ru = Fr::zero();
-      for (size_t a = 0; a < m; a++) ru = add(ru, mul(wgt[a], eval_of(p.queries[st.key_query[kq][a]])));
-      add_key(st.keys[kq], coef);
-      Rout[p.base_g] = sub(Rout[p.base_g], mul(coef, ru));
+  const opening::Grouping& g = p.grp;
+  const opening::Shplonk sh = opening::shplonk_sets(g, pt.data(), [&](uint32_t qi) { return eval_of(p.queries[qi]); }, yy, v);
+  const opening::AtU at = opening::at_u(g, pt.data(), u);
+  Fr vp = rho;
+  for (size_t si = 0; si < g.sets.size(); si++) {
+    const std::vector<Fr> wgt = opening::weights_at(sh, si, u);  // sum_j y^j r_ij(u) = sum_t wgt[t] E_i[t]
+    Fr ru = Fr::zero(), coef = mul(vp, at.z[si]);
+    for (size_t t = 0; t < wgt.size(); t++) ru = add(ru, mul(wgt[t], sh.E[si][t]));
+    Rout[p.base_g] = sub(Rout[p.base_g], mul(coef, ru));
+    for (uint32_t c : g.sets[si].coms) {
+      add_key(g.coms[c], coef);
       coef = mul(coef, yy);
     }
     vp = mul(vp, v);
   }
+  const Fr zt = at.zt, z0 = at.z0;
   const uint32_t h1 = p.open_pt, h2 = p.open_pt + 1;
   const Fr rz0 = mul(rho, z0);
   Rout[h1] = sub(Rout[h1], mul(rho, zt));
