@@ -288,16 +288,6 @@ static int check_build(amdzk_ctx* ctx, amdzk_pk* pk) {
     ck.prog_gates = pr;
     ZK_TRY(upload_program(ctx, pk, ck.prog_gates, false));
   }
-  if (pk->S && !ck.d_perm_cols) {
-    std::vector<const Fr*> cols(pk->S);
-    for (uint32_t i = 0; i < pk->S; i++) {
-      const std::pair<int, int>& kc = pk->perm_cols[i];
-      cols[i] = pk->h_cols_lag[kc.first == 0 ? pk->sl_adv(kc.second) : kc.first == 1 ? pk->sl_fixed(kc.second) : pk->sl_inst(kc.second)];
-    }
-    ZK_TRY(dalloc(ctx, pk, &ck.d_perm_cols, cols.size()));
-    ZK_TRY(h2d(ctx, ck.d_perm_cols, cols.data(), cols.size() * sizeof(Fr*)));
-    ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));  // `cols` is a host temporary
-  }
   if (!ck.d_count) {
     ZK_TRY(dalloc(ctx, pk, &ck.d_count, (size_t)ncon + ((size_t)ncon + 1) / 2 + 1));  // u64 counts, then u32 first rows
     ck.d_first = reinterpret_cast<uint32_t*>(ck.d_count + ncon);
@@ -420,7 +410,7 @@ static int check_witness_run(amdzk_ctx* ctx, amdzk_pk* pk, const uint64_t* const
     }
     ZK_TRY(zk_check_lookups(ctx, pk->la(), pk->lk_ts, L, (uint32_t)n, (uint32_t)usable, G, counters));
   }
-  if (S) ZK_TRY(zk_check_copies(ctx, ck.d_perm_cols, root->chk_shared->d_cells, S, (uint32_t)n, G + L, counters));
+  if (S) ZK_TRY(zk_check_copies(ctx, pk->d_perm_cols, root->chk_shared->d_cells, S, (uint32_t)n, G + L, counters));
   std::vector<unsigned long long> host((size_t)ncon + ((size_t)ncon + 1) / 2);
   ZK_TRY(d2h(ctx, host.data(), ck.d_count, (size_t)ncon * 12));
   const uint32_t* first = reinterpret_cast<const uint32_t*>(host.data() + ncon);

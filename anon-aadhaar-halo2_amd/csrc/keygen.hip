@@ -143,6 +143,14 @@ static int build_column_tables(amdzk_ctx* ctx, amdzk_pk* pk) {
     ZK_TRY(dalloc(ctx, pk, &pk->d_cols_ext, ex.size()));
     ZK_TRY(h2d(ctx, pk->d_cols_lag, lag.data(), lag.size() * sizeof(Fr*)));
     ZK_TRY(h2d(ctx, pk->d_cols_ext, ex.data(), ex.size() * sizeof(Fr*)));
+    // the permutation columns' values, in the permutation's order (the sparse products and the copy check read them by row)
+    std::vector<const Fr*> pv(S);
+    for (uint32_t i = 0; i < S; i++) {
+      const std::pair<int, int>& kc = pk->perm_cols[i];
+      pv[i] = lag[kc.first == 0 ? pk->sl_adv(kc.second) : kc.first == 1 ? pk->sl_fixed(kc.second) : pk->sl_inst(kc.second)];
+    }
+    ZK_TRY(dalloc(ctx, pk, &pk->d_perm_cols, pv.size()));
+    ZK_TRY(h2d(ctx, pk->d_perm_cols, pv.data(), pv.size() * sizeof(Fr*)));
     ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
   }
 
@@ -428,6 +436,44 @@ static int load_sigma_columns(amdzk_ctx* ctx, amdzk_pk* pk, const uint32_t* perm
   ZK_TRY(amdzk_lagrange_to_coeff_dev(ctx, pk->dom, pk->sigma_poly, S, n));
   ZK_TRY(zk_coeff_to_cosets_r261(ctx, pk->dom, pk->sigma_poly, n, pk->sigma_coset, pk->ext, S));
   return commit_cols(ctx, pk, AMDZK_BASIS_G_LAGRANGE, pk->sigma_lag, S, pk->perm_commitments);
+}
+
+// The cells that can change a permutation product (amdzk_pk::perm_rank / perm_off / perm_list), from the sigma columns
+// against the identity permutation's, on the device: flags, one scan per set, the sets' totals to the host for the
+// offsets, compaction. Every maker of a key comes through here, so a key read from a file or built from sigma has them too.
+static int build_perm_lists(amdzk_ctx* ctx, amdzk_pk* pk) {
+  const uint32_t S = pk->S, ns = pk->nsets, u = (uint32_t)(pk->n - pk->bf - 1);
+  if (!S) return AMDZK_OK;
+  const size_t cells = (size_t)ns * (u + 1);
+  uint32_t* flags = nullptr;  // only needed here
+  if (hipMalloc((void**)&flags, cells * sizeof(uint32_t)) != hipSuccess) ZK_FAIL(ctx, AMDZK_E_NOMEM, "keygen: hipMalloc of the permutation flags failed");
+  struct FreeOnExit {
+    amdzk_ctx* ctx;
+    void* p;
+    ~FreeOnExit() {
+      (void)zk_host_wait(ctx, ctx->stream);
+      hipFree(p);
+    }
+  } guard{ctx, flags};
+  ZK_TRY(dalloc(ctx, pk, &pk->perm_rank, cells));
+  ZK_TRY(dalloc(ctx, pk, &pk->perm_off, (size_t)ns + 1));
+  ZK_TRY(zk_perm_rank(ctx, pk->sigma_lag, pk->dxw_lag, pk->n, u, S, pk->chunk, ns, flags, pk->perm_rank));
+  std::vector<uint32_t> off((size_t)ns + 1, 0);  // the sets' totals (rank[s][u]), then their running sum
+  ZK_HIP(ctx, hipMemcpy2DAsync(off.data() + 1, sizeof(uint32_t), pk->perm_rank + u, ((size_t)u + 1) * sizeof(uint32_t), sizeof(uint32_t), ns,
+                               hipMemcpyDeviceToHost, ctx->stream));
+  ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
+  for (uint32_t s = 0; s < ns; s++) off[s + 1] += off[s];
+  pk->perm_m = off[ns];
+  // Per listed cell the sparse route costs about what the dense one costs per row: it runs up to half the cells. Its
+  // arrays (m + 1 numerators and as many denominators) live in the dense route's fraction columns, ns * n elements.
+  pk->perm_sparse = 2 * pk->perm_m <= (size_t)ns * u && 2 * (pk->perm_m + 1) <= (size_t)ns * pk->n;
+  ZK_TRY(h2d(ctx, pk->perm_off, off.data(), off.size() * sizeof(uint32_t)));
+  if (pk->perm_sparse) {
+    ZK_TRY(dalloc(ctx, pk, &pk->perm_list, pk->perm_m));
+    ZK_TRY(zk_perm_compact(ctx, flags, pk->perm_rank, pk->perm_off, u, ns, pk->perm_list));
+  }
+  ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));  // `off` is a host temporary
+  return AMDZK_OK;
 }
 
 // ---- the four programs of a key. A column operand is slot << 8 | index into the key's rotation table; fixed, advice and
@@ -747,6 +793,7 @@ static int keygen_common(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circu
   ZK_TRY(build_domain_columns(ctx, pk));
   ZK_TRY(load_fixed_columns(ctx, pk, fixed_values));
   ZK_TRY(load_sigma_columns(ctx, pk, perm_mapping, sigma_values, from_sigma));
+  ZK_TRY(build_perm_lists(ctx, pk));
   // rotations 0, 1, -1 and -(bf + 1) open the rotation table of every key, ahead of what its expressions query
   for (int32_t r : {0, 1, -1, -(int32_t)(pk->bf + 1)}) pk->rots.index(r);
   ZK_TRY(emit_compress_program(ctx, pk));

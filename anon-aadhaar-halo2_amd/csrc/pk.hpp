@@ -88,6 +88,17 @@ struct amdzk_pk {
   // that serves v + beta sigma + gamma = beta (sigma + w): three products per permutation column instead of four, in
   // the Lagrange-domain fractions and in h(X) (the beta^m of a set cancels in a fraction and rides on the term's power of y).
   Fr *dxw_lag = nullptr, *dx_coset = nullptr;
+  // The cells of the permutation products that can change them (keygen.hip build_perm_lists): per column set s the usable
+  // rows i < u where some column c of the set has sigma_c(omega^i) != delta^c omega^i, ascending — on every other row the
+  // set's fraction is 1 whatever the witness. perm_rank[s][i], i <= u (stride u + 1): the set's listed rows below i;
+  // perm_off[s]: the listed cells of the sets before s (perm_off[nsets] = perm_m, all of them); perm_list: the cells as
+  // (set, row), set after set. Key material of the root key like the sigma columns — clones share it, amdzk_pk_free
+  // frees it with the key — and derived from them, so never in the key file. perm_sparse: Prover::perm_products walks the
+  // list instead of the columns (perm_m <= nsets * u / 2); the list is kept only then.
+  uint32_t *perm_rank = nullptr, *perm_off = nullptr;
+  uint2* perm_list = nullptr;
+  size_t perm_m = 0;
+  bool perm_sparse = false;
   std::vector<uint32_t> h_term_beta_pow;  // per term of the h(X) program: the power of beta its power of y is multiplied by
   // device: per-proof workspace. poly arena order: adv | inst | la | ls | zp | zl
   size_t NP = 0;
@@ -148,6 +159,7 @@ struct amdzk_pk {
   Fr* d_ypow = nullptr;       // [h_terms]: y^(h_terms-1-j) in radix 2^261, refreshed per proof
   const Fr** d_cols_lag = nullptr;
   const Fr** d_cols_ext = nullptr;
+  const Fr** d_perm_cols = nullptr;  // [S]: the permutation columns' values (advice, fixed or instance) in this workspace
   Fr** d_outs_compress = nullptr;
   Fr** d_outs_pfrac = nullptr;
   Fr** d_outs_lfrac = nullptr;
@@ -162,13 +174,12 @@ struct amdzk_pk {
   std::vector<const amdzk_pk*> mo_multi_keys;
   std::vector<const Fr*> h_cols_lag, h_cols_ext;  // host copies of the slot tables (program resolution)
   // amdzk_check_witness, per handle, made by the handle's first check (the instructions carry this workspace's column
-  // addresses): the gate polynomials as one Lagrange-domain program, gate g ending in OP_CHECK g; the base addresses of
-  // the permutation columns; the counters, count[ncon] (u64) followed by first[ncon] (u32), constraints in report order
-  // (gates, lookups, permutation columns).
+  // addresses): the gate polynomials as one Lagrange-domain program, gate g ending in OP_CHECK g; the counters,
+  // count[ncon] (u64) followed by first[ncon] (u32), constraints in report order (gates, lookups, permutation columns).
+  // (The copy check reads the permutation columns through d_perm_cols above.)
   struct Check {
     bool built = false;
     Program prog_gates;
-    const Fr** d_perm_cols = nullptr;
     unsigned long long* d_count = nullptr;
     uint32_t* d_first = nullptr;
   } chk;

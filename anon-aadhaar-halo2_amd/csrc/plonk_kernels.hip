@@ -457,6 +457,72 @@ __global__ __launch_bounds__(256) void row_diff_kernel(const Fr* z, Fr* d, size_
   st_fr(d + (size_t)blockIdx.y * d_stride + i, v);
 }
 
+// ------------------------------------------------------------------------------ permutation products from the rows that have copies
+// A set's fraction prod_c (v_c + beta delta^c omega^i + gamma) / prod_c (v_c + beta sigma_c(omega^i) + gamma) is 1 on every
+// row where sigma is the identity label on all the set's columns, whatever the witness: the key lists the other cells
+// (keygen.hip build_perm_lists), set after set and ascending inside a set, and with last_z chaining the sets the product
+// column Z[s][i] is the product of the fractions of ALL listed cells in front of (s, i) in that order — one running
+// product over the list instead of nsets columns.
+
+// flags[s][i] = 1 where some column of set s has sigma != identity on row i < u (flag stride u + 1; the scan's total sits at u)
+__global__ __launch_bounds__(256) void perm_flag_kernel(const Fr* sigma, const Fr* ident, size_t n, uint32_t u, uint32_t S, uint32_t chunk,
+                                                        uint32_t* flags) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, s = blockIdx.y;
+  if (i >= u) return;
+  const uint32_t lo = s * chunk, hi = lo + chunk < S ? lo + chunk : S;
+  uint32_t f = 0;
+  for (uint32_t c = lo; c < hi; c++) {
+    const Fr a = ld_fr(sigma + (size_t)c * n + i), b = ld_fr(ident + (size_t)c * n + i);
+#pragma unroll
+    for (int j = 0; j < 8; j++) f |= a.l[j] ^ b.l[j];
+  }
+  flags[(size_t)s * (u + 1) + i] = f ? 1u : 0u;
+}
+
+// list[off[s] + rank[s][i]] = (s, i) for every flagged cell
+__global__ __launch_bounds__(256) void perm_compact_kernel(const uint32_t* flags, const uint32_t* rank, const uint32_t* off, uint32_t u, uint2* list) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, s = blockIdx.y;
+  if (i >= u) return;
+  const size_t at = (size_t)s * (u + 1) + i;
+  if (flags[at]) list[off[s] + rank[at]] = make_uint2(s, i);
+}
+
+// One lane per listed cell j < m: num[j], den[j] = the two products of its set on its row. Lane m writes the pair (1, 1)
+// that closes the arrays: the exclusive running product over m + 1 elements ends in the product of all m.
+__global__ __launch_bounds__(256) void perm_frac_sparse_kernel(const uint2* list, uint32_t m, const Fr* const* vals, const Fr* sigma, const Fr* ident,
+                                                               size_t n, uint32_t S, uint32_t chunk, const Fr* beta_p, const Fr* gamma_p, Fr* num,
+                                                               Fr* den) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j > m) return;
+  if (j == m) {
+    st_fr(num + j, Fr::one());
+    st_fr(den + j, Fr::one());
+    return;
+  }
+  const uint2 cell = list[j];
+  const uint32_t lo = cell.x * chunk, hi = lo + chunk < S ? lo + chunk : S;
+  const size_t i = cell.y;
+  const Fr beta = ld_fr(beta_p), gamma = ld_fr(gamma_p);
+  Fr pn = Fr::one(), pd = Fr::one();
+#pragma unroll 1
+  for (uint32_t c = lo; c < hi; c++) {
+    const Fr w = add(ld_fr(vals[c] + i), gamma);
+    const Fr fn = add(w, fr29_mul_std(beta, ld_fr(ident + (size_t)c * n + i)));
+    const Fr fd = add(w, fr29_mul_std(beta, ld_fr(sigma + (size_t)c * n + i)));
+    pn = c == lo ? fn : fr29_mul_std(pn, fn);
+    pd = c == lo ? fd : fr29_mul_std(pd, fd);
+  }
+  st_fr(num + j, pn);
+  st_fr(den + j, pd);
+}
+
+// z[s][i] = run[off[s] + rank[s][i]] for i <= u: run = the exclusive running product over the list (run[0] = 1)
+__global__ __launch_bounds__(256) void perm_fill_kernel(const Fr* run, const uint32_t* rank, const uint32_t* off, uint32_t u, Fr* z, size_t z_stride) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, s = blockIdx.y;
+  if (i > u) return;
+  st_fr(z + (size_t)s * z_stride + i, ld_fr(run + off[s] + rank[(size_t)s * (u + 1) + i]));
+}
+
 // ------------------------------------------------------------------------------ running products
 // Exclusive prefix product of each column, three steps. Block = 256 threads x SCAN_E elements.
 constexpr int SCAN_E = 8;
@@ -1039,6 +1105,35 @@ int zk_row_diff(amdzk_ctx* ctx, const Fr* d_z, Fr* d_d, size_t ncols, size_t n, 
   if (ncols == 0 || n == 0) return AMDZK_OK;
   if (ncols > 65535) ZK_FAIL(ctx, AMDZK_E_INVALID, "row_diff: %zu columns > 65535", ncols);
   ZK_LAUNCH(ctx, "row_diff", row_diff_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)ncols), dim3(256), 0, d_z, d_d, n, z_stride, d_stride);
+  return AMDZK_OK;
+}
+
+// The key-build half of the sparse permutation products: d_flags[s][i] (stride u + 1) marks the rows i < u where a column
+// of set s is off the identity permutation, d_rank[s][i], i <= u, counts the set's marked rows below i.
+int zk_perm_rank(amdzk_ctx* ctx, const Fr* d_sigma, const Fr* d_ident, size_t n, uint32_t u, uint32_t S, uint32_t chunk, uint32_t nsets,
+                 uint32_t* d_flags, uint32_t* d_rank) {
+  if (!nsets) return AMDZK_OK;
+  if (nsets > 65535) ZK_FAIL(ctx, AMDZK_E_INVALID, "perm_rank: %u column sets > 65535", nsets);
+  if (u) ZK_LAUNCH(ctx, "perm_flag", perm_flag_kernel, dim3((u + 255) / 256, nsets), dim3(256), 0, d_sigma, d_ident, n, u, S, chunk, d_flags);
+  ZK_LAUNCH(ctx, "perm_flag_scan", flag_scan_kernel, dim3(nsets), dim3(1024), 0, (const uint32_t*)d_flags, d_rank, u, (size_t)u + 1, 0);
+  return AMDZK_OK;
+}
+// ... and the marked cells as (set, row) at d_list[d_off[s] + d_rank[s][i]]
+int zk_perm_compact(amdzk_ctx* ctx, const uint32_t* d_flags, const uint32_t* d_rank, const uint32_t* d_off, uint32_t u, uint32_t nsets, uint2* d_list) {
+  if (nsets && u) ZK_LAUNCH(ctx, "perm_compact", perm_compact_kernel, dim3((u + 255) / 256, nsets), dim3(256), 0, d_flags, d_rank, d_off, u, d_list);
+  return AMDZK_OK;
+}
+// The proof's half: numerators and denominators of the m listed cells (and the closing pair of ones, m + 1 elements each) ...
+int zk_perm_frac_sparse(amdzk_ctx* ctx, const uint2* d_list, uint32_t m, const Fr* const* d_vals, const Fr* d_sigma, const Fr* d_ident, size_t n,
+                        uint32_t S, uint32_t chunk, const Fr* d_beta, const Fr* d_gamma, Fr* d_num, Fr* d_den) {
+  ZK_LAUNCH(ctx, "perm_frac_sparse", perm_frac_sparse_kernel, dim3(m / 256 + 1), dim3(256), 0, d_list, m, d_vals, d_sigma, d_ident, n, S, chunk, d_beta,
+            d_gamma, d_num, d_den);
+  return AMDZK_OK;
+}
+// ... and rows 0 ... u of the nsets product columns from the running product over the list
+int zk_perm_fill(amdzk_ctx* ctx, const Fr* d_run, const uint32_t* d_rank, const uint32_t* d_off, uint32_t u, uint32_t nsets, Fr* d_z, size_t z_stride) {
+  if (nsets > 65535) ZK_FAIL(ctx, AMDZK_E_INVALID, "perm_fill: %u column sets > 65535", nsets);
+  if (nsets) ZK_LAUNCH(ctx, "perm_fill", perm_fill_kernel, dim3(u / 256 + 1, nsets), dim3(256), 0, d_run, d_rank, d_off, u, d_z, z_stride);
   return AMDZK_OK;
 }
 

@@ -87,6 +87,15 @@ int zk_chacha20_blind_rows(amdzk_ctx* ctx, bn254::Fr* d_cols, size_t col_stride,
 int zk_batch_invert(amdzk_ctx* ctx, bn254::Fr* d_a, bn254::Fr* d_scratch, size_t total);
 int zk_mul_elem(amdzk_ctx* ctx, bn254::Fr* d_a, const bn254::Fr* d_b, size_t total);
 int zk_row_diff(amdzk_ctx* ctx, const bn254::Fr* d_z, bn254::Fr* d_d, size_t ncols, size_t n, size_t z_stride, size_t d_stride);
+// permutation products from the rows that have copies: the key's lists (keygen.hip build_perm_lists) and a proof's two steps
+int zk_perm_rank(amdzk_ctx* ctx, const bn254::Fr* d_sigma, const bn254::Fr* d_ident, size_t n, uint32_t u, uint32_t S, uint32_t chunk, uint32_t nsets,
+                 uint32_t* d_flags, uint32_t* d_rank);
+int zk_perm_compact(amdzk_ctx* ctx, const uint32_t* d_flags, const uint32_t* d_rank, const uint32_t* d_off, uint32_t u, uint32_t nsets, uint2* d_list);
+int zk_perm_frac_sparse(amdzk_ctx* ctx, const uint2* d_list, uint32_t m, const bn254::Fr* const* d_vals, const bn254::Fr* d_sigma,
+                        const bn254::Fr* d_ident, size_t n, uint32_t S, uint32_t chunk, const bn254::Fr* d_beta, const bn254::Fr* d_gamma,
+                        bn254::Fr* d_num, bn254::Fr* d_den);
+int zk_perm_fill(amdzk_ctx* ctx, const bn254::Fr* d_run, const uint32_t* d_rank, const uint32_t* d_off, uint32_t u, uint32_t nsets, bn254::Fr* d_z,
+                 size_t z_stride);
 size_t zk_scan_totals_elems(size_t n, size_t ncols);
 int zk_running_product(amdzk_ctx* ctx, bn254::Fr* d_cols, size_t ncols, size_t n, size_t col_stride, bool chain, size_t u,
                        bn254::Fr* d_tmp);

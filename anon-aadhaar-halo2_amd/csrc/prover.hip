@@ -123,6 +123,30 @@ int commit_finish(PendingCommit& pc, std::vector<G1Affine>& out) {
   return AMDZK_OK;
 }
 
+// permutation::prover::Argument::commit up to the blinding: rows 0 ... usable of the nsets product columns into pk->zp(), from
+// the workspace's columns and the beta and gamma of its constant table, on ctx's stream.
+// Dense: the fraction program over every row, the inversion of nsets * n denominators and a running product per column,
+// chained through last_z. Sparse (keys whose lists say so, amdzk_pk::perm_sparse): the same values from the perm_m listed
+// cells alone — their numerators and denominators side by side in the fraction columns, which are free until the row
+// differences are written there, ONE running product over all of them (last_z makes the sets one chain) and a gather.
+int perm_products_unblinded(amdzk_ctx* ctx, amdzk_pk* pk, bool sparse) {
+  const size_t n = pk->n, ns = pk->nsets, usable = n - (pk->bf + 1);
+  if (!sparse) {
+    ZK_TRY(run_program(ctx, pk, pk->prog_pfrac, false, pk->d_outs_pfrac, nullptr, "expr_perm_fractions"));
+    ZK_TRY(zk_batch_invert(ctx, pk->frac, pk->scratch, ns * n));
+    ZK_TRY(zk_mul_elem(ctx, pk->zp(), pk->frac, ns * n));
+    return zk_running_product(ctx, pk->zp(), ns, n, n, true, usable, pk->scan_tmp);
+  }
+  const size_t m = pk->perm_m;
+  Fr *den = pk->frac, *num = pk->frac + m + 1;
+  ZK_TRY(zk_perm_frac_sparse(ctx, pk->perm_list, (uint32_t)m, pk->d_perm_cols, pk->sigma_lag, pk->dxw_lag, n, pk->S, pk->chunk, pk->d_consts + pk->c_beta,
+                             pk->d_consts + pk->c_gamma, num, den));
+  ZK_TRY(zk_batch_invert(ctx, den, pk->scratch, m));
+  ZK_TRY(zk_mul_elem(ctx, num, den, m));
+  ZK_TRY(zk_running_product(ctx, num, 1, m + 1, m + 1, false, 0, pk->scan_tmp));
+  return zk_perm_fill(ctx, num, pk->perm_rank, pk->perm_off, (uint32_t)usable, (uint32_t)ns, pk->zp(), n);
+}
+
 Fr rotate_omega(const amdzk_pk* pk, const Fr& x, int rot) {
   return rot >= 0 ? mul(x, pow_u64(pk->omega, (uint64_t)rot)) : mul(x, pow_u64(pk->omega_inv, (uint64_t)(-rot)));
 }
@@ -640,13 +664,8 @@ struct Prover {
   }
   int perm_products(size_t ci) {  // fractions, inversion, running products, blinding: everything in front of the commitment
     amdzk_pk* const pk = pks[ci];
-    ZK_TRY(run_program(ctx, pk, pk->prog_pfrac, false, pk->d_outs_pfrac, nullptr, "expr_perm_fractions"));
-    tick("  perm: fractions program");
-    ZK_TRY(zk_batch_invert(ctx, pk->frac, pk->scratch, (size_t)ns * n));
-    tick("  perm: batch invert");
-    ZK_TRY(zk_mul_elem(ctx, pk->zp(), pk->frac, (size_t)ns * n));
-    ZK_TRY(zk_running_product(ctx, pk->zp(), ns, n, n, true, usable, pk->scan_tmp));
-    tick("  perm: running product");
+    ZK_TRY(perm_products_unblinded(ctx, pk, pk->perm_sparse));
+    tick("  perm: fractions, inversion, running product");
     ZK_TRY(blind(M, pk->zp(), ns, n - bf, bf, draws.perm_product(ci), draws.col));
     // What is committed is the columns' row differences, over the prefix sums of g_lagrange: the same points (Abel
     // summation), and a product column only changes on the rows of a copy cycle and in its blinding tail. frac is free
@@ -1427,6 +1446,36 @@ int amdzk_quotient_eval_dev(amdzk_ctx* ctx, amdzk_pk* pk, const void* d_polys, s
   pk->consts[pk->c_betainv] = inv(pk->consts[pk->c_beta]);
   ZK_TRY(quotient_pieces(ctx, pk));
   ZK_TRY(d2d(ctx, d_pieces_out, pk->hpieces, (size_t)pk->qdeg * pk->n * 32));
+  ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
+  return AMDZK_OK;
+}
+
+// permutation::prover::Argument::commit before the blinding, on the columns the key's workspace holds (the advice and
+// instance columns of its last proof): rows 0 ... usable (= n - blinding_factors - 1) of the nsets product columns to `out`,
+// nsets x (usable + 1) Fr on the host, column after column. route 0: the fraction program over every row; 1: from the
+// key's list of cells that are off the identity permutation (refused for a key that keeps none: more than half of its
+// cells are listed); -1: the route the key's proofs take. *cells_out = the listed cells, *sparse_out = whether proofs
+// take route 1 (either may be NULL; out = NULL only queries them). Overwrites the key's per-proof workspace.
+int amdzk_perm_products_dev(amdzk_ctx* ctx, amdzk_pk* pk, const uint64_t beta[4], const uint64_t gamma[4], int route, uint64_t* out,
+                            size_t* cells_out, int* sparse_out) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  if (!pk) ZK_FAIL(ctx, AMDZK_E_INVALID, "perm_products: null key");
+  if (cells_out) *cells_out = pk->perm_m;
+  if (sparse_out) *sparse_out = pk->perm_sparse ? 1 : 0;
+  if (!out) return AMDZK_OK;
+  if (!beta || !gamma) ZK_FAIL(ctx, AMDZK_E_INVALID, "perm_products: null argument");
+  if (route < -1 || route > 1) ZK_FAIL(ctx, AMDZK_E_INVALID, "perm_products: unknown route %d", route);
+  if (route == 1 && !pk->perm_sparse) ZK_FAIL(ctx, AMDZK_E_INVALID, "perm_products: the key keeps no list of cells (%zu listed)", pk->perm_m);
+  if (!pk->S) return AMDZK_OK;
+  memcpy(pk->consts[pk->c_beta].l, beta, 32);
+  memcpy(pk->consts[pk->c_gamma].l, gamma, 32);
+  if (pk->consts[pk->c_beta].is_zero()) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "perm_products: beta is zero");
+  pk->consts[pk->c_betainv] = inv(pk->consts[pk->c_beta]);
+  ZK_TRY(h2d(ctx, pk->d_consts + pk->c_beta, &pk->consts[pk->c_beta], (size_t)(pk->c_betainv + 1 - pk->c_beta) * 32));
+  ZK_TRY(perm_products_unblinded(ctx, pk, route < 0 ? pk->perm_sparse : route == 1));
+  const size_t rows = pk->n - pk->bf;  // usable + 1
+  ZK_HIP(ctx, hipMemcpy2DAsync(out, rows * 32, pk->zp(), pk->n * 32, rows * 32, pk->nsets, hipMemcpyDeviceToHost, ctx->stream));
   ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
   return AMDZK_OK;
 }

@@ -110,6 +110,7 @@ def lib():
         "amdzk_batch_invert_dev": (i32, [vp, vp, sz]),
         "amdzk_batch_invert_assigned_dev": (i32, [vp, vp, vp, sz, vp]),
         "amdzk_grand_product_dev": (i32, [vp, vp, sz, sz, sz, i32, sz]),
+        "amdzk_perm_products_dev": (i32, [vp, vp, vp, vp, i32, vp, C.POINTER(sz), C.POINTER(i32)]),
         "amdzk_eval_poly_dev": (i32, [vp, C.POINTER(vp), vp, sz, u32, vp]),
         "amdzk_poly_axpy_dev": (i32, [vp, C.POINTER(vp), vp, sz, vp, sz, i32]),
         "amdzk_kate_div_dev": (i32, [vp, C.POINTER(vp), vp, sz, u32]),

@@ -511,6 +511,25 @@ class ProvingKey:
         finally:
             d_in.free(); d_out.free()
 
+    def perm_cells(self):
+        """(listed cells, sparse): the cells of the permutation products that are off the identity permutation, and whether
+        this key's proofs form the products from them alone (amdzk_perm_products_dev's query)."""
+        m, sp = C.c_size_t(0), C.c_int32(0)
+        self.ctx._chk(self.ctx.L.amdzk_perm_products_dev(self.ctx.h, self.h, None, None, -1, None, C.byref(m), C.byref(sp)))
+        return m.value, bool(sp.value)
+
+    def perm_products(self, beta, gamma, route=-1):
+        """amdzk_perm_products_dev: the permutation product columns before blinding, rows 0 ... usable, (nsets, usable + 1, 4),
+        from the columns of the key's last proof. route 0: every row; 1: the listed cells alone; -1: as the key's proofs."""
+        chunk = self.desc["cs_degree"] - 2
+        nsets = (len(self.desc["permutation_columns"]) + chunk - 1) // chunk
+        rows = (1 << self.desc["k"]) - self.desc["blinding_factors"]
+        out = np.zeros((nsets, rows, 4), np.uint64)
+        b, g = (np.ascontiguousarray(c, dtype=np.uint64).reshape(4) for c in (beta, gamma))
+        self.ctx._chk(self.ctx.L.amdzk_perm_products_dev(self.ctx.h, self.h, b.ctypes.data, g.ctypes.data, int(route),
+                                                         out.ctypes.data if out.size else None, None, None))
+        return out
+
     def free(self):
         if self.h:
             self.ctx.L.amdzk_pk_free(self.ctx.h, self.h)

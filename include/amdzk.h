@@ -529,6 +529,15 @@ int amdzk_batch_invert_assigned_dev(amdzk_ctx* ctx, const void* d_num, const voi
  * permutation argument's last_z is threaded through the columns: z_c[0] = z_{c-1}[chain_row]. */
 int amdzk_grand_product_dev(amdzk_ctx* ctx, void* d_cols, size_t ncols, size_t n, size_t col_stride,
                             int chain, size_t chain_row);
+/* permutation::prover::Argument::commit [UP] up to the blinding, on the columns pk's workspace holds (the advice and instance
+ * columns of its last proof) and the given beta and gamma (Montgomery Fr): rows 0 ... usable (= 2^k - blinding_factors - 1)
+ * of the product columns, nsets x (usable + 1) Fr, column after column, to `out` on the host. route 0: fractions, inversion
+ * and running products over every row; 1: from the cells that are off the identity permutation alone, which a key lists
+ * when they are at most half of its usable cells (refused otherwise); -1: the route pk's proofs take. Both give the same
+ * words. *cells_out: the listed cells; *sparse_out: 1 when proofs take route 1 (either may be NULL; out = NULL only
+ * queries them). Overwrites pk's per-proof workspace. */
+int amdzk_perm_products_dev(amdzk_ctx* ctx, amdzk_pk* pk, const uint64_t beta[4], const uint64_t gamma[4], int route,
+                            uint64_t* out, size_t* cells_out, int* sparse_out);
 /* arithmetic::eval_polynomial [UP] for nq (polynomial, point) pairs: out[q] = d_polys[q](points[q]). d_polys: host
  * array of device pointers to n coefficients; points and out on the host. */
 int amdzk_eval_poly_dev(amdzk_ctx* ctx, const void* const* d_polys, const uint64_t* points, size_t nq,
