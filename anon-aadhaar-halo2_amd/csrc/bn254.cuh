@@ -449,7 +449,7 @@ struct alignas(16) G1Affine {
   ZK_HD bool is_inf() const { return x.is_zero() && y.is_zero(); }
 };
 
-// ---- what decoding a point from bytes needs (msm.hip g1_decompress_kernel, verify.hip proof_decode_kernel)
+// ---- what decoding a point from bytes needs (srs.hip g1_decompress_kernel, verify.hip proof_decode_kernel)
 // a plain 256-bit integer is a canonical residue (< p)
 template <class P>
 ZK_HD bool is_canonical(const Fp<P>& a) {
@@ -620,5 +620,46 @@ ZK_HD G1Affine x_to_affine(const G1X& p) {
   r.y = mul(p.y, izzz);
   return r;
 }
+
+#if defined(__HIPCC__)
+// ---- 16-byte device loads and stores of the types above (msm.hip, srs.hip): two dwordx4 per field element
+ZK_D Fq ld_fq(const Fq* p) {
+  const uint4* q = reinterpret_cast<const uint4*>(p);
+  uint4 a = q[0], b = q[1];
+  Fq r;
+  r.l[0] = a.x; r.l[1] = a.y; r.l[2] = a.z; r.l[3] = a.w;
+  r.l[4] = b.x; r.l[5] = b.y; r.l[6] = b.z; r.l[7] = b.w;
+  return r;
+}
+ZK_D void st_fq(Fq* p, const Fq& v) {
+  uint4* q = reinterpret_cast<uint4*>(p);
+  q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
+  q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
+}
+ZK_D G1Affine ld_aff(const G1Affine* p) {
+  G1Affine r;
+  r.x = ld_fq(&p->x);
+  r.y = ld_fq(&p->y);
+  return r;
+}
+ZK_D void st_aff(G1Affine* p, const G1Affine& v) {
+  st_fq(&p->x, v.x);
+  st_fq(&p->y, v.y);
+}
+ZK_D G1X ld_x(const G1X* p) {
+  G1X r;
+  r.x = ld_fq(&p->x);
+  r.y = ld_fq(&p->y);
+  r.zz = ld_fq(&p->zz);
+  r.zzz = ld_fq(&p->zzz);
+  return r;
+}
+ZK_D void st_x(G1X* p, const G1X& v) {
+  st_fq(&p->x, v.x);
+  st_fq(&p->y, v.y);
+  st_fq(&p->zz, v.zz);
+  st_fq(&p->zzz, v.zzz);
+}
+#endif
 
 }  // namespace bn254

@@ -1,5 +1,5 @@
 // C ABI of libamdzk (include/amdzk.h): context, device memory, and the host-pointer forms of the
-// hot-path entry points. Kernels live in ntt.hip / msm.hip. There is no CPU fallback here: every
+// hot-path entry points. Kernels live in ntt.hip / msm.hip / srs.hip. There is no CPU fallback here: every
 // entry point either runs on the gfx950 device or fails with a status code.
 #include <stdlib.h>
 #include <string.h>

@@ -182,7 +182,7 @@ inline hipError_t zk_host_wait_event(amdzk_ctx* ctx, hipEvent_t evt) { return zk
 
 // basis slots of an amdzk_srs: AMDZK_BASIS_G, AMDZK_BASIS_G_LAGRANGE, AMDZK_BASIS_G_LAGRANGE_PREFIX
 constexpr int AMDZK_NUM_BASES = 3;
-// The prefix-sum basis of srs (msm.hip), built on ctx's stream the first time it is asked for and resident from then on:
+// The prefix-sum basis of srs (srs.hip), built on ctx's stream the first time it is asked for and resident from then on:
 // every maker of a proving key with permutation columns calls this. Safe from several threads (one guard in the SRS).
 int zk_srs_ensure_prefix(amdzk_ctx* ctx, const amdzk_srs* srs);
 
@@ -245,11 +245,6 @@ int zk_ntt_ex(amdzk_ctx* ctx, const bn254::Fr* d_in, size_t in_stride, bn254::Fr
 bn254::Fr zk_fr_inv_pow2(uint32_t log_n);
 
 // msm.hip
-int zk_srs_upload(amdzk_ctx* ctx, const uint64_t* g, const uint64_t* g_lagrange, uint32_t k, amdzk_srs** out);
-void zk_srs_free(amdzk_ctx*, amdzk_srs* s);
-uint32_t zk_srs_k(const amdzk_srs* srs);
-bool zk_srs_has_basis(const amdzk_srs* srs, int basis);
-const bn254::G1Affine* zk_srs_base_dev(const amdzk_srs* srs, int basis);
 int zk_msm_dev_xyzz(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const bn254::Fr* d_scalars, size_t ncols, size_t len, size_t col_stride,
                     bn254::G1X** d_out);
 int zk_msm_dev_xyzz_cols(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const bn254::Fr* const* d_col_ptrs, size_t ncols, size_t len,
@@ -258,6 +253,13 @@ int zk_msm_finish(amdzk_ctx* ctx, const bn254::G1X* d_res, size_t ncols, uint64_
 int zk_msm_bases_dev_xyzz(amdzk_ctx* ctx, const bn254::Fr* d_scalars, size_t ncols, size_t len, size_t col_stride, const bn254::G1Affine* d_bases,
                           bn254::G1X** d_out);
 int zk_msm_bases_plan_host(size_t ncols, size_t len, uint32_t* window_bits, uint32_t* windows, size_t* scratch_bytes, char why[160]);
+
+// srs.hip (struct amdzk_srs itself: srs.hpp, for srs.hip and msm.hip alone)
+int zk_srs_upload(amdzk_ctx* ctx, const uint64_t* g, const uint64_t* g_lagrange, uint32_t k, amdzk_srs** out);
+void zk_srs_free(amdzk_ctx*, amdzk_srs* s);
+uint32_t zk_srs_k(const amdzk_srs* srs);
+bool zk_srs_has_basis(const amdzk_srs* srs, int basis);
+const bn254::G1Affine* zk_srs_base_dev(const amdzk_srs* srs, int basis);
 int zk_srs_setup(amdzk_ctx* ctx, uint32_t k, const uint64_t s_mont[4], const uint64_t omega_mont[4], amdzk_srs** out, uint64_t* g_out,
                  uint64_t* g_lagrange_out);
 size_t zk_srs_serialized_size(uint32_t k);

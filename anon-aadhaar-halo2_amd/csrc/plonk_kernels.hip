@@ -447,7 +447,7 @@ __global__ __launch_bounds__(256) void mul_elem_kernel(Fr* a, const Fr* b, size_
 }
 
 // d[c][i] = z[c][i] - z[c][i + 1] for i < n - 1, d[c][n - 1] = z[c][n - 1]: the scalars of a column's commitment over the
-// prefix sums of the Lagrange basis (msm.hip, AMDZK_BASIS_G_LAGRANGE_PREFIX). Zero wherever the column does not change.
+// prefix sums of the Lagrange basis (srs.hip, AMDZK_BASIS_G_LAGRANGE_PREFIX). Zero wherever the column does not change.
 __global__ __launch_bounds__(256) void row_diff_kernel(const Fr* z, Fr* d, size_t n, size_t z_stride, size_t d_stride) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
