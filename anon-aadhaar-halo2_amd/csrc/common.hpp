@@ -269,6 +269,10 @@ int zk_srs_get(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, uint64_t* out);
 int zk_srs_write(amdzk_ctx* ctx, const amdzk_srs* s, const uint8_t g2[64], const uint8_t s_g2[64], uint8_t* out, size_t cap);
 int zk_srs_read(amdzk_ctx* ctx, const uint8_t* data, size_t len, amdzk_srs** out, uint8_t g2_out[64], uint8_t s_g2_out[64]);
 
+// pairing.hip: amdzk_pairing_products on host G1 points, refusals prefixed with `who`
+int zk_pairing_products(amdzk_ctx* ctx, const char* who, const amdzk_g2* const* qs, size_t m, const bn254::G1Affine* h_g1, size_t n, uint8_t* is_one,
+                        uint64_t* gt_out);
+
 // poly.hip
 int zk_lagrange_to_coeff(amdzk_ctx* ctx, const amdzk_domain* d, const bn254::Fr* d_in, size_t in_stride, bn254::Fr* d_out, size_t out_stride,
                          size_t ncols);

@@ -1,0 +1,221 @@
+// The pairing unit (include/amdzk.h "pairing"): amdzk_g2_prepare / amdzk_g2_setup (host half, pairing.hpp)
+// and amdzk_pairing_products — n independent products of m pairings over the same m prepared G2 points — as two launches:
+// one lane per (check, pair) runs the Miller program over that pair's prepared lines (no G2 arithmetic on the device), one
+// lane per check multiplies its m Miller values, runs the final-exponentiation program and compares with one. A lane's
+// running values are Fq2 registers in a slab of global memory, contiguous per lane; the programs (pairing.hpp) and the
+// executor (fq12.cuh) are the same ones the host check runs. Both kernels are latency-bound chains of about 10^4 dependent
+// Fq products per lane, so the blocks are single waves with FEW active lanes (pairing_active_lanes): the lanes spread
+// over every SIMD of the chip before any wave gets a second one, as proof_decode_kernel's single-wave blocks do.
+#include <string.h>
+
+#include <vector>
+
+#include "common.hpp"
+#include "pairing.hpp"
+
+using namespace bn254;
+
+// ONE prepared point: constants | lines | the three programs (the same in every handle: a handle is self-contained)
+struct amdzk_g2 {
+  int device = 0;
+  char* d = nullptr;
+};
+
+namespace {
+
+constexpr int PAIRING_WS_SLOT = 3;  // verify's slot: amdzk_verify_proofs_decide pairs after the last read of its reservation
+constexpr uint32_t PAIRING_THREADS = 64;
+constexpr size_t PAIRING_CHUNK_LANES = 16384;  // Miller lanes per launch: bounds the register slabs (about 2 KB a Miller lane, 5 KB a check)
+
+size_t pad256(size_t v) { return (v + 255) / 256 * 256; }
+
+struct Programs {
+  pairing::Prog miller, mul, fin;
+  size_t o_lines, o_miller, o_mul, o_fin, bytes;
+  uint32_t final_regs;
+};
+const Programs& programs() {
+  static const Programs P = [] {
+    Programs q;
+    q.miller = pairing::miller_program(), q.mul = pairing::mul_program(), q.fin = pairing::final_exp_program();
+    q.o_lines = pad256(pairing::K_COUNT * sizeof(Fq2x));
+    q.o_miller = q.o_lines + pad256(4 * (size_t)PAIRING_NUM_LINES * sizeof(Fq));
+    q.o_mul = q.o_miller + pad256(q.miller.w.size() * 4);
+    q.o_fin = q.o_mul + pad256(q.mul.w.size() * 4);
+    q.bytes = q.o_fin + pad256(q.fin.w.size() * 4);
+    q.final_regs = (uint32_t)(q.mul.regs > q.fin.regs ? q.mul.regs : q.fin.regs);
+    return q;
+  }();
+  return P;
+}
+
+struct MillerArgs {
+  const uint32_t* prog;
+  uint32_t prog_len, regs, m, active;
+  const Fq2x* K;
+  const Fq* const* lines;  // [m]
+  const G1Affine* g1;      // [total], this launch's first lane at 0
+  Fq2x* slab;              // [total][regs]
+  size_t total;
+};
+// lane t = blockIdx.x * active + threadIdx.x, for threadIdx.x < active
+__global__ __launch_bounds__(PAIRING_THREADS) void pairing_miller_kernel(MillerArgs a) {
+  if (threadIdx.x >= a.active) return;
+  const size_t t = (size_t)blockIdx.x * a.active + threadIdx.x;
+  if (t >= a.total) return;
+  const G1Affine p = ld_aff(a.g1 + t);
+  Fq2x* R = a.slab + t * a.regs;
+  if (p.is_inf()) {  // the identity contributes the factor 1
+    R[pairing::MILLER_F] = fq2x_one();
+    for (int k = 1; k < 6; k++) R[pairing::MILLER_F + k] = fq2x_zero();
+    return;
+  }
+  R[pairing::MILLER_XP] = Fq2x{fq29_from_r256(p.x), fqx_zero()};
+  R[pairing::MILLER_YP] = Fq2x{fq29_from_r256(p.y), fqx_zero()};
+  pairing_exec(a.prog, a.prog_len, R, a.K, a.lines[t % a.m]);
+}
+
+struct FinalArgs {
+  const uint32_t *mul_prog, *fin_prog;
+  uint32_t mul_len, fin_len, regs, miller_regs, m, active;
+  const Fq2x* K;
+  const Fq2x* miller_slab;  // [n * m][miller_regs]
+  Fq2x* slab;               // [n][regs]
+  size_t n;
+  Fq* gt_out;        // [n][12]
+  uint8_t* is_one;   // [n]
+};
+__global__ __launch_bounds__(PAIRING_THREADS) void pairing_final_kernel(FinalArgs a) {
+  if (threadIdx.x >= a.active) return;
+  const size_t i = (size_t)blockIdx.x * a.active + threadIdx.x;
+  if (i >= a.n) return;
+  Fq2x* R = a.slab + i * a.regs;
+  const Fq2x* M = a.miller_slab + i * a.m * a.miller_regs + pairing::MILLER_F;
+  for (int k = 0; k < 6; k++) R[pairing::FINAL_A + k] = M[k];
+#pragma unroll 1
+  for (uint32_t j = 1; j <= a.m; j++) {  // m - 1 products, then the exponentiation: one site of the executor
+    const bool last = j == a.m;
+    if (!last)
+      for (int k = 0; k < 6; k++) R[pairing::FINAL_B + k] = M[(size_t)j * a.miller_regs + k];
+    pairing_exec(last ? a.fin_prog : a.mul_prog, last ? a.fin_len : a.mul_len, R, a.K, nullptr);
+  }
+  Fq out[12];
+  fq12x_to_r256(out, R + pairing::FINAL_A);
+  for (int k = 0; k < 12; k++) st_fq(a.gt_out + i * 12 + k, out[k]);
+  a.is_one[i] = gt_is_one(out) ? 1 : 0;
+}
+
+// lanes per single-wave block: one until every SIMD of the chip has a wave, then as many as it takes
+uint32_t pairing_active_lanes(const amdzk_ctx* ctx, size_t total) {
+  const size_t simds = (size_t)(ctx->num_cu > 0 ? ctx->num_cu : 1) * 4;
+  const size_t a = (total + simds - 1) / simds;
+  return (uint32_t)(a < 1 ? 1 : a > PAIRING_THREADS ? PAIRING_THREADS : a);
+}
+
+}  // namespace
+
+int zk_pairing_products(amdzk_ctx* ctx, const char* who, const amdzk_g2* const* qs, size_t m, const G1Affine* h_g1, size_t n, uint8_t* is_one,
+                        uint64_t* gt_out) {
+  if (!qs || !h_g1) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: null argument", who);
+  if (m == 0 || n == 0) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: m or n is 0", who);
+  if (m > AMDZK_PAIRING_MAX_M) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: m = %zu is above AMDZK_PAIRING_MAX_M = %d", who, m, AMDZK_PAIRING_MAX_M);
+  if (n > ((size_t)1 << 20)) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: more than 2^20 products in one call", who);
+  for (size_t j = 0; j < m; j++) {
+    if (!qs[j] || !qs[j]->d) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: null argument (prepared point %zu)", who, j);
+    if (qs[j]->device != ctx->device) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: prepared point %zu lives on device %d, the ctx on %d", who, j, qs[j]->device, ctx->device);
+  }
+  const Programs& P = programs();
+  const size_t total = n * m, chunk = PAIRING_CHUNK_LANES / m < n ? PAIRING_CHUNK_LANES / m : n;  // checks per launch (m <= 16: at least 1024)
+  const size_t o_g1 = pad256(AMDZK_PAIRING_MAX_M * sizeof(Fq*)), o_ms = o_g1 + pad256(total * sizeof(G1Affine));
+  const size_t o_fs = o_ms + pad256(chunk * m * P.miller.regs * sizeof(Fq2x)), o_gt = o_fs + pad256(chunk * P.final_regs * sizeof(Fq2x));
+  const size_t o_one = o_gt + n * 12 * sizeof(Fq), bytes = o_one + pad256(n);
+  const size_t up = o_ms, down = n * 12 * sizeof(Fq) + n;
+  char* ws = nullptr;
+  ZK_TRY(zk_ws_reserve(ctx, PAIRING_WS_SLOT, bytes, (void**)&ws));
+  char* pin = nullptr;
+  ZK_TRY(zk_pinned_reserve(ctx, up > down ? up : down, (void**)&pin));
+  memset(pin, 0, o_g1);
+  for (size_t j = 0; j < m; j++) ((const Fq**)pin)[j] = (const Fq*)(qs[j]->d + P.o_lines);
+  memcpy(pin + o_g1, h_g1, total * sizeof(G1Affine));
+  ZK_HIP(ctx, hipMemcpyAsync(ws, pin, up, hipMemcpyHostToDevice, ctx->stream));
+  const char* q0 = qs[0]->d;  // constants and programs: any handle's copy
+  for (size_t c0 = 0; c0 < n; c0 += chunk) {
+    const size_t nc = c0 + chunk < n ? chunk : n - c0, lanes = nc * m;
+    MillerArgs ma;
+    ma.prog = (const uint32_t*)(q0 + P.o_miller), ma.prog_len = (uint32_t)P.miller.w.size(), ma.regs = (uint32_t)P.miller.regs, ma.m = (uint32_t)m;
+    ma.active = pairing_active_lanes(ctx, lanes), ma.K = (const Fq2x*)q0, ma.lines = (const Fq* const*)ws;
+    ma.g1 = (const G1Affine*)(ws + o_g1) + c0 * m, ma.slab = (Fq2x*)(ws + o_ms), ma.total = lanes;
+    ZK_LAUNCH(ctx, "pairing_miller", pairing_miller_kernel, dim3((unsigned)((lanes + ma.active - 1) / ma.active)), dim3(PAIRING_THREADS), 0, ma);
+    FinalArgs fa;
+    fa.mul_prog = (const uint32_t*)(q0 + P.o_mul), fa.fin_prog = (const uint32_t*)(q0 + P.o_fin), fa.mul_len = (uint32_t)P.mul.w.size();
+    fa.fin_len = (uint32_t)P.fin.w.size(), fa.regs = P.final_regs, fa.miller_regs = (uint32_t)P.miller.regs, fa.m = (uint32_t)m;
+    fa.active = pairing_active_lanes(ctx, nc), fa.K = (const Fq2x*)q0, fa.miller_slab = (const Fq2x*)(ws + o_ms), fa.slab = (Fq2x*)(ws + o_fs);
+    fa.n = nc, fa.gt_out = (Fq*)(ws + o_gt) + c0 * 12, fa.is_one = (uint8_t*)(ws + o_one) + c0;
+    ZK_LAUNCH(ctx, "pairing_final", pairing_final_kernel, dim3((unsigned)((nc + fa.active - 1) / fa.active)), dim3(PAIRING_THREADS), 0, fa);
+  }
+  ZK_HIP(ctx, hipMemcpyAsync(pin, ws + o_gt, down, hipMemcpyDeviceToHost, ctx->stream));
+  ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
+  if (gt_out) memcpy(gt_out, pin, n * 12 * sizeof(Fq));
+  if (is_one) memcpy(is_one, pin + n * 12 * sizeof(Fq), n);
+  return AMDZK_OK;
+}
+
+extern "C" int amdzk_g2_prepare(amdzk_ctx* ctx, const uint64_t q[16], amdzk_g2** out) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  if (!q || !out) ZK_FAIL(ctx, AMDZK_E_INVALID, "g2_prepare: null argument");
+  *out = nullptr;
+  const pairing::G2Affine p = pairing::g2_from_words(q);
+  if (!is_canonical(p.x.c0) || !is_canonical(p.x.c1) || !is_canonical(p.y.c0) || !is_canonical(p.y.c1))
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "g2_prepare: a coordinate is not below the modulus");
+  if (p.is_inf()) ZK_FAIL(ctx, AMDZK_E_INVALID, "g2_prepare: the identity has no prepared form");
+  if (!pairing::g2_on_twist(p)) ZK_FAIL(ctx, AMDZK_E_INVALID, "g2_prepare: the point is not on the twist");
+  const Programs& P = programs();
+  std::vector<char> host(P.bytes, 0);
+  pairing::device_consts((Fq2x*)host.data());
+  pairing::g2_prepare(p, (Fq*)(host.data() + P.o_lines));
+  memcpy(host.data() + P.o_miller, P.miller.w.data(), P.miller.w.size() * 4);
+  memcpy(host.data() + P.o_mul, P.mul.w.data(), P.mul.w.size() * 4);
+  memcpy(host.data() + P.o_fin, P.fin.w.data(), P.fin.w.size() * 4);
+  amdzk_g2* g = new amdzk_g2();
+  g->device = ctx->device;
+  hipError_t e = hipMalloc((void**)&g->d, P.bytes);
+  if (e == hipSuccess) e = hipMemcpyAsync(g->d, host.data(), P.bytes, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = zk_host_wait(ctx, ctx->stream);
+  if (e != hipSuccess) {
+    if (g->d) (void)hipFree(g->d);
+    delete g;
+    ZK_FAIL(ctx, e == hipErrorOutOfMemory ? AMDZK_E_NOMEM : AMDZK_E_HIP, "g2_prepare: %s", hipGetErrorString(e));
+  }
+  *out = g;
+  return AMDZK_OK;
+}
+
+extern "C" void amdzk_g2_free(amdzk_ctx* ctx, amdzk_g2* g) {
+  ZK_ENTER(ctx);
+  if (!g) return;
+  if (g->d) (void)hipFree(g->d);
+  delete g;
+}
+
+extern "C" int amdzk_g2_setup(amdzk_ctx* ctx, const uint64_t s[4], uint64_t g2_out[16], uint64_t s_g2_out[16]) {
+  if (!ctx) return AMDZK_E_INVALID;
+  if (!s || !g2_out || !s_g2_out) ZK_FAIL(ctx, AMDZK_E_INVALID, "g2_setup: null argument");
+  Fr sm;
+  memcpy(sm.l, s, 32);
+  if (!is_canonical(sm)) ZK_FAIL(ctx, AMDZK_E_INVALID, "g2_setup: s is not below the modulus");
+  const Fr k = from_mont(sm);
+  uint64_t kw[4];
+  memcpy(kw, k.l, 32);
+  const pairing::G2Affine g = pairing::g2_generator();
+  pairing::g2_to_words(g, g2_out);
+  pairing::g2_to_words(pairing::g2_mul(g, kw), s_g2_out);
+  return AMDZK_OK;
+}
+
+extern "C" int amdzk_pairing_products(amdzk_ctx* ctx, const amdzk_g2* const* qs, size_t m, const uint64_t* g1, size_t n, uint8_t* is_one,
+                                      uint64_t* gt_out) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  return zk_pairing_products(ctx, "pairing_products", qs, m, (const G1Affine*)g1, n, is_one, gt_out);
+}

@@ -103,37 +103,43 @@ __global__ __launch_bounds__(DECODE_THREADS) void proof_decode_kernel(DecodeArgs
 
 size_t pad256(size_t v) { return (v + 255) / 256 * 256; }
 
-}  // namespace
-
-extern "C" int amdzk_verify_proofs(amdzk_ctx* ctx, const amdzk_pk* pk, size_t n_proofs, const uint64_t* const* const* instances,
-                                   const size_t* const* instance_lens, const uint8_t* const* proofs, const size_t* proof_lens,
-                                   const amdzk_verify_opts* opts, amdzk_proof_status* statuses, uint64_t pair_out[16]) {
-  ZK_ENTER(ctx);
-  if (!ctx) return AMDZK_E_INVALID;
-  if (!pk || !proofs || !proof_lens || !statuses || !pair_out) ZK_FAIL(ctx, AMDZK_E_INVALID, "verify_proofs: null argument");
-  if (n_proofs == 0) ZK_FAIL(ctx, AMDZK_E_INVALID, "verify_proofs: n_proofs is 0");
-  if (n_proofs > (1u << 20)) ZK_FAIL(ctx, AMDZK_E_INVALID, "verify_proofs: more than 2^20 proofs in one call");
+// What amdzk_verify_proofs and amdzk_verify_proofs_decide share: everything up to the G1 sums. `who` prefixes the refusals.
+// pairs == nullptr: the batch's ONE pair, sum_b rho_b (L_b, R_b), in pair_out — amdzk_verify_proofs as documented.
+// pairs != nullptr: every proof by itself with weight 1 — (L_b, R_b) in (*pairs)[2b], [2b + 1], identities for a malformed
+// proof; opts->combine_* are not read and pair_out is not written. The MSMs run over AMDZK_DECIDE_RUN proofs at a time.
+int verify_core(amdzk_ctx* ctx, const char* who, const amdzk_pk* pk, size_t n_proofs, const uint64_t* const* const* instances,
+                const size_t* const* instance_lens, const uint8_t* const* proofs, const size_t* proof_lens, const amdzk_verify_opts* opts,
+                amdzk_proof_status* statuses, uint64_t* pair_out, std::vector<G1Affine>* pairs) {
+  const bool per_proof = pairs != nullptr;
+  if (!pk || !proofs || !proof_lens || !statuses || (!per_proof && !pair_out)) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: null argument", who);
+  if (n_proofs == 0) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: n_proofs is 0", who);
+  if (n_proofs > (1u << 20)) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: more than 2^20 proofs in one call", who);
   if (opts && opts->size < sizeof(amdzk_verify_opts))
-    ZK_FAIL(ctx, AMDZK_E_INVALID, "verify_proofs: amdzk_verify_opts.size is %zu, this library needs %zu", opts->size, sizeof(amdzk_verify_opts));
-  if (!pk->src_desc || !pk->srs) ZK_FAIL(ctx, AMDZK_E_INVALID, "verify_proofs: the key has no circuit description");
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: amdzk_verify_opts.size is %zu, this library needs %zu", who, opts->size, sizeof(amdzk_verify_opts));
+  if (!pk->src_desc || !pk->srs) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: the key has no circuit description", who);
   const int kind = opts ? opts->transcript_kind : 0;
   const uint32_t N = opts && opts->n_circuits ? opts->n_circuits : 1;
   verifier::Plan plan;
   {
     std::string why;
-    if (verifier::make_plan(*pk->src_desc, N, kind, &plan, &why) != AMDZK_OK) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s", why.c_str());
+    if (verifier::make_plan(*pk->src_desc, N, kind, &plan, &why) != AMDZK_OK) {
+      const std::string own = "verify_proofs: ";  // verifier.hpp's prefix
+      ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: %s", who, why.compare(0, own.size(), own) == 0 ? why.c_str() + own.size() : why.c_str());
+    }
   }
-  if (plan.I && (!instances || !instance_lens)) ZK_FAIL(ctx, AMDZK_E_INVALID, "verify_proofs: null argument (instances)");
+  if (plan.I && (!instances || !instance_lens)) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: null argument (instances)", who);
   for (size_t i = 0; plan.I && i < n_proofs * N; i++)
-    if (!instances[i] || !instance_lens[i]) ZK_FAIL(ctx, AMDZK_E_INVALID, "verify_proofs: null argument (instances of circuit %zu)", i);
+    if (!instances[i] || !instance_lens[i]) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: null argument (instances of circuit %zu)", who, i);
   for (size_t b = 0; b < n_proofs; b++)
-    if (!proofs[b]) ZK_FAIL(ctx, AMDZK_E_INVALID, "verify_proofs: null argument (proof %zu)", b);
+    if (!proofs[b]) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: null argument (proof %zu)", who, b);
   if (plan.proof_bytes != amdzk_proof_size_multi(pk, N, kind) || plan.proof_bytes >= ((size_t)1 << 30))
-    ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "verify_proofs: proof layout of %zu bytes disagrees with amdzk_proof_size_multi or is too large", plan.proof_bytes);
+    ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "%s: proof layout of %zu bytes disagrees with amdzk_proof_size_multi or is too large", who, plan.proof_bytes);
   std::vector<Fr> rho(n_proofs, Fr::one());
-  if (opts && opts->combine_scalars) {
+  if (per_proof) {
+    // weight 1 for every proof: nothing of opts->combine_* is read
+  } else if (opts && opts->combine_scalars) {
     for (size_t b = 0; b < n_proofs; b++) {
-      if (!verifier::fr_canonical_words(opts->combine_scalars + 4 * b)) ZK_FAIL(ctx, AMDZK_E_INVALID, "verify_proofs: combine_scalars[%zu] is not below the modulus", b);
+      if (!verifier::fr_canonical_words(opts->combine_scalars + 4 * b)) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: combine_scalars[%zu] is not below the modulus", who, b);
       memcpy(rho[b].l, opts->combine_scalars + 4 * b, 32);
     }
   } else if (n_proofs > 1) {
@@ -150,14 +156,20 @@ extern "C" int amdzk_verify_proofs(amdzk_ctx* ctx, const amdzk_pk* pk, size_t n_
       statuses[b].status = AMDZK_PROOF_BAD_INSTANCE, statuses[b].offset = col;
     else live++;
   }
-  memset(pair_out, 0, 16 * sizeof(uint64_t));
+  G1Affine g1_inf;
+  g1_inf.x = g1_inf.y = Fq::zero();
+  if (per_proof) pairs->assign(2 * n_proofs, g1_inf);
+  else memset(pair_out, 0, 16 * sizeof(uint64_t));
   if (live == 0) return AMDZK_OK;
   // ---- one reservation: staging | element table | status words | key commitments | G | decoded points | decoded scalars | MSM scalars
   const size_t psize = plan.proof_bytes, E = plan.elems.size(), NP = plan.NP, NS = plan.NS, nvk = (size_t)plan.F + plan.S;
   const size_t nbases = nvk + 1 + n_proofs * NP;
   const size_t o_elems = pad256(n_proofs * psize), o_status = o_elems + pad256(E * sizeof(uint2)), o_vk = o_status + pad256(n_proofs * 4);
   const size_t o_g = o_vk + nvk * sizeof(G1Affine), o_points = o_g + sizeof(G1Affine), o_dsc = o_points + n_proofs * NP * sizeof(G1Affine);
-  const size_t o_msm = pad256(o_dsc + n_proofs * NS * 32), total = o_msm + 2 * nbases * 32;
+  // per proof: the MSM scalars of ONE run (2 columns per proof over the key's commitments, G and the run's points) | that run's bases
+  const size_t run = n_proofs < AMDZK_DECIDE_RUN ? n_proofs : AMDZK_DECIDE_RUN, run_len = nvk + 1 + run * NP;
+  const size_t o_msm = pad256(o_dsc + n_proofs * NS * 32), o_rb = pad256(o_msm + 2 * run * run_len * 32);
+  const size_t total = per_proof ? o_rb + run_len * sizeof(G1Affine) : o_msm + 2 * nbases * 32;
   const size_t up_bytes = o_g, down_bytes = o_msm - o_status;
   char* ws = nullptr;
   ZK_TRY(zk_ws_reserve(ctx, VERIFY_WS_SLOT, total, (void**)&ws));
@@ -173,7 +185,7 @@ extern "C" int amdzk_verify_proofs(amdzk_ctx* ctx, const amdzk_pk* pk, size_t n_
   if (plan.F) memcpy(pin + o_vk, pk->fixed_commitments.data(), (size_t)plan.F * sizeof(G1Affine));
   if (plan.S) memcpy(pin + o_vk + (size_t)plan.F * sizeof(G1Affine), pk->perm_commitments.data(), (size_t)plan.S * sizeof(G1Affine));
   const G1Affine* d_g = zk_srs_base_dev(pk->srs, AMDZK_BASIS_G);
-  if (!d_g) ZK_FAIL(ctx, AMDZK_E_INVALID, "verify_proofs: the key's SRS has no monomial basis");
+  if (!d_g) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: the key's SRS has no monomial basis", who);
   ZK_HIP(ctx, hipMemcpyAsync(ws, pin, up_bytes, hipMemcpyHostToDevice, ctx->stream));
   ZK_HIP(ctx, hipMemcpyAsync(ws + o_g, d_g, sizeof(G1Affine), hipMemcpyDeviceToDevice, ctx->stream));
   DecodeArgs da;
@@ -181,7 +193,7 @@ extern "C" int amdzk_verify_proofs(amdzk_ctx* ctx, const amdzk_pk* pk, size_t n_
   da.E = (uint32_t)E, da.NP = (uint32_t)NP, da.NS = (uint32_t)NS, da.total = n_proofs * E;
   da.points = (G1Affine*)(ws + o_points), da.scalars = (Fr*)(ws + o_dsc), da.status = (uint32_t*)(ws + o_status), da.evm = plan.evm ? 1 : 0;
   const size_t blocks = (da.total + DECODE_THREADS - 1) / DECODE_THREADS;
-  if (blocks > 0x7fffffffu) ZK_FAIL(ctx, AMDZK_E_INVALID, "verify_proofs: batch too large");
+  if (blocks > 0x7fffffffu) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: batch too large", who);
   ZK_LAUNCH(ctx, "proof_decode", proof_decode_kernel, dim3((unsigned)blocks), dim3(DECODE_THREADS), 0, da);
   ZK_HIP(ctx, hipMemcpyAsync(h_down, ws + o_status, down_bytes, hipMemcpyDeviceToHost, ctx->stream));
   ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));  // wait 1 of 2
@@ -189,7 +201,9 @@ extern "C" int amdzk_verify_proofs(amdzk_ctx* ctx, const amdzk_pk* pk, size_t n_
   const uint32_t* h_status = (const uint32_t*)h_down;
   const G1Affine* h_points = (const G1Affine*)(h_down + (o_points - o_status));
   const Fr* h_scalars = (const Fr*)(h_down + (o_dsc - o_status));
-  std::vector<Fr> msm(2 * nbases, Fr::zero()), Lb(plan.n_bases), Rb(plan.n_bases);
+  std::vector<Fr> msm(per_proof ? 0 : 2 * nbases, Fr::zero()), Lb(plan.n_bases), Rb(plan.n_bases);
+  std::vector<Fr> own;       // per proof: the live proofs' (Lb | Rb), in batch order
+  std::vector<size_t> who_b;  // ... and their positions
   live = 0;
   for (size_t b = 0; b < n_proofs; b++) {
     if (statuses[b].status != AMDZK_PROOF_WELL_FORMED) continue;
@@ -200,6 +214,12 @@ extern "C" int amdzk_verify_proofs(amdzk_ctx* ctx, const amdzk_pk* pk, size_t n_
     live++;
     verifier::fold_proof(plan, pk->transcript_repr, pk->omega, plan.I ? instances + b * N : nullptr, plan.I ? instance_lens + b * N : nullptr,
                          h_points + b * NP, h_scalars + b * NS, rho[b], Lb.data(), Rb.data());
+    if (per_proof) {
+      own.insert(own.end(), Lb.begin(), Lb.end());
+      own.insert(own.end(), Rb.begin(), Rb.end());
+      who_b.push_back(b);
+      continue;
+    }
     for (uint32_t i = 0; i < plan.n_bases; i++) {
       const size_t g = i < NP ? nvk + 1 + b * NP + i : i - NP;  // the proof's own points | fixed, permutation, G
       msm[g] = add(msm[g], Lb[i]);
@@ -207,6 +227,43 @@ extern "C" int amdzk_verify_proofs(amdzk_ctx* ctx, const amdzk_pk* pk, size_t n_
     }
   }
   if (live == 0) return AMDZK_OK;
+  if (per_proof) {
+    // ---- (L_b, R_b) for every live proof: per run of AMDZK_DECIDE_RUN batch positions one MSM of 2 columns per live proof
+    // over the key's commitments, G and the run's decoded points (a proof's columns are zero on its neighbours' points,
+    // and zero scalars cost nothing). One host wait per run.
+    ZK_HIP(ctx, hipMemcpyAsync(ws + o_rb, ws + o_vk, (nvk + 1) * sizeof(G1Affine), hipMemcpyDeviceToDevice, ctx->stream));
+    std::vector<uint64_t> jac(24 * run);
+    for (size_t lo = 0, b0 = 0; b0 < n_proofs; b0 += run) {
+      const size_t b1 = b0 + run < n_proofs ? b0 + run : n_proofs, len = nvk + 1 + (b1 - b0) * NP;
+      size_t hi = lo;
+      while (hi < who_b.size() && who_b[hi] < b1) hi++;
+      const size_t nl = hi - lo;
+      if (nl == 0) continue;
+      msm.assign(2 * nl * len, Fr::zero());
+      for (size_t q = 0; q < nl; q++) {
+        const size_t b = who_b[lo + q];
+        for (int side = 0; side < 2; side++) {
+          const Fr* src = own.data() + ((lo + q) * 2 + side) * plan.n_bases;
+          Fr* col = msm.data() + (2 * q + side) * len;
+          for (uint32_t i = 0; i < plan.n_bases; i++) col[i < NP ? nvk + 1 + (b - b0) * NP + i : i - NP] = src[i];
+        }
+      }
+      ZK_HIP(ctx, hipMemcpyAsync(ws + o_rb + (nvk + 1) * sizeof(G1Affine), ws + o_points + b0 * NP * sizeof(G1Affine), (b1 - b0) * NP * sizeof(G1Affine),
+                                 hipMemcpyDeviceToDevice, ctx->stream));
+      ZK_HIP(ctx, hipMemcpyAsync(ws + o_msm, msm.data(), msm.size() * 32, hipMemcpyHostToDevice, ctx->stream));
+      G1X* d_res = nullptr;
+      ZK_TRY(zk_msm_bases_dev_xyzz(ctx, (const Fr*)(ws + o_msm), 2 * nl, len, len, (const G1Affine*)(ws + o_rb), &d_res));
+      ZK_TRY(zk_msm_finish(ctx, d_res, 2 * nl, jac.data()));
+      for (size_t q = 0; q < 2 * nl; q++) {
+        const G1Jac* j = reinterpret_cast<const G1Jac*>(jac.data() + 12 * q);
+        if (j->z.is_zero()) continue;  // the identity stays (0, 0)
+        G1Affine& o = (*pairs)[2 * who_b[lo + q / 2] + (q & 1)];
+        o.x = j->x, o.y = j->y;
+      }
+      lo = hi;
+    }
+    return AMDZK_OK;
+  }
   // ---- L and R: one MSM of two columns over the decoded points, the key's commitments and G (zero scalars cost nothing)
   ZK_HIP(ctx, hipMemcpyAsync(ws + o_msm, msm.data(), 2 * nbases * 32, hipMemcpyHostToDevice, ctx->stream));
   G1X* d_res = nullptr;
@@ -219,5 +276,60 @@ extern "C" int amdzk_verify_proofs(amdzk_ctx* ctx, const amdzk_pk* pk, size_t n_
     memcpy(pair_out + 8 * c, &j->x, 32);
     memcpy(pair_out + 8 * c + 4, &j->y, 32);
   }
+  return AMDZK_OK;
+}
+
+}  // namespace
+
+extern "C" int amdzk_verify_proofs(amdzk_ctx* ctx, const amdzk_pk* pk, size_t n_proofs, const uint64_t* const* const* instances,
+                                   const size_t* const* instance_lens, const uint8_t* const* proofs, const size_t* proof_lens,
+                                   const amdzk_verify_opts* opts, amdzk_proof_status* statuses, uint64_t pair_out[16]) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  if (!pair_out) ZK_FAIL(ctx, AMDZK_E_INVALID, "verify_proofs: null argument");
+  return verify_core(ctx, "verify_proofs", pk, n_proofs, instances, instance_lens, proofs, proof_lens, opts, statuses, pair_out, nullptr);
+}
+
+// amdzk_verify_proofs and the pairing behind it (include/amdzk.h): per proof (flags = 0) one launch of n_live checks with
+// m = 2, P = (L_b, -R_b) over (s_g2, g2); combined, one check of the batch's pair.
+extern "C" int amdzk_verify_proofs_decide(amdzk_ctx* ctx, const amdzk_pk* pk, const amdzk_g2* s_g2, const amdzk_g2* g2, uint32_t flags,
+                                          size_t n_proofs, const uint64_t* const* const* instances, const size_t* const* instance_lens,
+                                          const uint8_t* const* proofs, const size_t* proof_lens, const amdzk_verify_opts* opts,
+                                          amdzk_proof_status* statuses, uint8_t* verdicts, size_t* n_valid) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  const char* who = "verify_proofs_decide";
+  if (!s_g2 || !g2 || !verdicts) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: null argument", who);
+  if (flags & ~AMDZK_DECIDE_COMBINED) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: unknown flags 0x%x", who, flags);
+  const bool combined = (flags & AMDZK_DECIDE_COMBINED) != 0;
+  std::vector<G1Affine> pairs;
+  uint64_t pair[16];
+  ZK_TRY(verify_core(ctx, who, pk, n_proofs, instances, instance_lens, proofs, proof_lens, opts, statuses, pair, combined ? nullptr : &pairs));
+  if (combined) {
+    pairs.resize(2);
+    memcpy(&pairs[0], pair, 64);
+    memcpy(&pairs[1], pair + 8, 64);
+  }
+  // the checks worth a pairing: both points finite (a pair of identities must not read as valid; one identity cannot pass)
+  std::vector<G1Affine> g1;
+  std::vector<size_t> at;
+  for (size_t c = 0; c < pairs.size() / 2; c++) {
+    if (pairs[2 * c].is_inf() || pairs[2 * c + 1].is_inf()) continue;
+    g1.push_back(pairs[2 * c]);
+    g1.push_back(a_neg(pairs[2 * c + 1]));
+    at.push_back(c);
+  }
+  std::vector<uint8_t> one(at.size(), 0), holds(pairs.size() / 2, 0);
+  if (!at.empty()) {
+    const amdzk_g2* qs[2] = {s_g2, g2};
+    ZK_TRY(zk_pairing_products(ctx, who, qs, 2, g1.data(), at.size(), one.data(), nullptr));
+  }
+  for (size_t c = 0; c < at.size(); c++) holds[at[c]] = one[c];
+  size_t valid = 0;
+  for (size_t b = 0; b < n_proofs; b++) {
+    verdicts[b] = statuses[b].status == AMDZK_PROOF_WELL_FORMED && holds[combined ? 0 : b] ? 1 : 0;
+    valid += verdicts[b];
+  }
+  if (n_valid) *n_valid = valid;
   return AMDZK_OK;
 }

@@ -121,6 +121,12 @@ def lib():
         "amdzk_pk_inspect": (i32, [vp, vp, i32, vp, sz, C.POINTER(sz)]),
         "amdzk_check_witness": (i32, [vp, vp, C.POINTER(vp), C.POINTER(sz), vp, sz, vp, vp, sz, C.POINTER(sz)]),
         "amdzk_verify_proofs": (i32, [vp, vp, sz, C.POINTER(C.POINTER(vp)), C.POINTER(C.POINTER(sz)), C.POINTER(vp), C.POINTER(sz), vp, vp, vp]),
+        "amdzk_g2_prepare": (i32, [vp, vp, C.POINTER(vp)]),
+        "amdzk_g2_free": (None, [vp, vp]),
+        "amdzk_g2_setup": (i32, [vp, vp, vp, vp]),
+        "amdzk_pairing_products": (i32, [vp, C.POINTER(vp), sz, vp, sz, vp, vp]),
+        "amdzk_verify_proofs_decide": (i32, [vp, vp, vp, vp, u32, sz, C.POINTER(C.POINTER(vp)), C.POINTER(C.POINTER(sz)), C.POINTER(vp), C.POINTER(sz),
+                                             vp, vp, vp, C.POINTER(sz)]),
         "amdzk_debug_limb_program": (i32, [vp, sz, vp, sz, C.POINTER(sz), C.POINTER(u32)]),
         "amdzk_pk_h_program": (i32, [vp, vp, sz, C.POINTER(sz)]),
         "amdzk_timer_start": (i32, [vp]),

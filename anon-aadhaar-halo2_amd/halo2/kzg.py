@@ -100,6 +100,72 @@ class ParamsKZG:
             self.h = None
 
 
+# ---- the G2 side and the pairing (include/amdzk.h "pairing"; conventions: csrc/fq12.cuh)
+PAIRING_MAX_M = 16  # AMDZK_PAIRING_MAX_M
+
+
+class G2Prepared:
+    """halo2curves' G2Prepared: ONE finite G2 point ((16,) uint64: x.c0, x.c1, y.c0, y.c1, Montgomery) as the line
+    coefficients of the Miller loop, resident on the ctx's device. Refused: a coordinate >= q, a point off the twist, the
+    identity. Subgroup membership is not checked."""
+
+    def __init__(self, ctx, q):
+        self.ctx = ctx
+        q = np.ascontiguousarray(q, dtype=np.uint64).reshape(16)
+        h = C.c_void_p()
+        ctx._chk(ctx.L.amdzk_g2_prepare(ctx.h, _ptr(q), C.byref(h)))
+        self.h = h
+
+    def free(self):
+        if self.h:
+            self.ctx.L.amdzk_g2_free(self.ctx.h, self.h)
+            self.h = None
+
+
+def g2_setup(ctx, s):
+    """The G2 half of ParamsKZG::setup with the trapdoor `s` ((4,) uint64 Montgomery Fr; as unsafe as ParamsKZG.setup):
+    (g2, s_g2), (16,) uint64 each."""
+    s = np.ascontiguousarray(s, dtype=np.uint64).reshape(4)
+    g2, s_g2 = np.zeros(16, np.uint64), np.zeros(16, np.uint64)
+    ctx._chk(ctx.L.amdzk_g2_setup(ctx.h, _ptr(s), _ptr(g2), _ptr(s_g2)))
+    return g2, s_g2
+
+
+def pairing_products(ctx, qs, g1, want_gt=True):
+    """amdzk_pairing_products: qs = m G2Prepared, g1 = (n, m, 8) or (n * m, 8) uint64 G1Affine ((0, 0) = identity, factor 1).
+    Returns (is_one (n,) bool, gt (n, 48) uint64 or None): gt[i] = prod_j e(g1[i, j], qs[j]) as halo2curves' Fq12."""
+    m = len(qs)
+    g1 = np.ascontiguousarray(g1, dtype=np.uint64).reshape(-1, 8)
+    assert m and g1.shape[0] % m == 0
+    n = g1.shape[0] // m
+    handles = (C.c_void_p * m)(*[q.h for q in qs])
+    one = np.zeros(max(1, n), np.uint8)
+    gt = np.zeros((max(1, n), 48), np.uint64) if want_gt else None
+    ctx._chk(ctx.L.amdzk_pairing_products(ctx.h, handles, m, _ptr(g1), n, _ptr(one), None if gt is None else _ptr(gt)))
+    return one[:n].astype(bool), None if gt is None else gt[:n]
+
+
+class ParamsVerifierKZG:
+    """The verifier's part of ParamsKZG: the prepared [1]_2 and [s]_2 ((16,) uint64 points, e.g. from g2_setup)."""
+
+    def __init__(self, ctx, g2, s_g2):
+        self.ctx = ctx
+        self.g2 = G2Prepared(ctx, g2)
+        try:
+            self.s_g2 = G2Prepared(ctx, s_g2)
+        except Exception:
+            self.g2.free()
+            raise
+
+    @classmethod
+    def setup(cls, ctx, s):
+        return cls(ctx, *g2_setup(ctx, s))
+
+    def free(self):
+        self.g2.free()
+        self.s_g2.free()
+
+
 # ---- poly::kzg::multiopen: the opening arguments over the caller's polynomials (amdzk_multiopen_dev)
 MULTIOPEN_SHPLONK = 0
 MULTIOPEN_GWC = 0x100

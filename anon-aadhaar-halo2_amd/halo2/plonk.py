@@ -844,13 +844,9 @@ class Guard:
         return "Guard(statuses=%r)" % (self.statuses,)
 
 
-def verify_proofs(ctx, pk, instances_list, proofs, transcript=TRANSCRIPT_BLAKE2B, n_circuits=1, combine_seed=0, combine_scalars=None,
-                  opts_size=None):
-    """amdzk_verify_proofs: plonk::verify_proof for a batch up to the one pairing. proofs[b]: bytes; instances_list[b]: proof
-    b's instance columns as for create_proof — or, with n_circuits > 1, a list of n_circuits such lists (create_proof_multi).
-    combine_scalars: (len(proofs), 4) uint64 Montgomery weights of the caller's; else they are drawn from combine_seed, which
-    must then be unpredictable to whoever made the proofs (a single proof has weight 1). Returns a Guard; a refused call raises.
-    opts_size: amdzk_verify_opts.size to report (tests)."""
+def _verify_args(instances_list, proofs, transcript, n_circuits, combine_seed, combine_scalars, opts_size):
+    """The arguments amdzk_verify_proofs and amdzk_verify_proofs_decide share: (instances, instance_lens, proofs, proof_lens,
+    opts, statuses, keep-alive)."""
     B, N = len(proofs), n_circuits
     assert len(instances_list) == B
     keep, inst_pp, lens_pp = [], (C.POINTER(C.c_void_p) * max(1, B * N))(), (C.POINTER(C.c_size_t) * max(1, B * N))()
@@ -872,10 +868,56 @@ def verify_proofs(ctx, pk, instances_list, proofs, transcript=TRANSCRIPT_BLAKE2B
     opts = _ffi.VerifyOpts(C.sizeof(_ffi.VerifyOpts) if opts_size is None else opts_size, transcript, N, C.c_uint64(combine_seed),
                            sc.ctypes.data if sc is not None else None)
     st = (_ffi.ProofStatus * max(1, B))()
+    keep += [bufs, sc]
+    return inst_pp, lens_pp, pp, pl, opts, st, keep
+
+
+def verify_proofs(ctx, pk, instances_list, proofs, transcript=TRANSCRIPT_BLAKE2B, n_circuits=1, combine_seed=0, combine_scalars=None,
+                  opts_size=None):
+    """amdzk_verify_proofs: plonk::verify_proof for a batch up to the one pairing. proofs[b]: bytes; instances_list[b]: proof
+    b's instance columns as for create_proof — or, with n_circuits > 1, a list of n_circuits such lists (create_proof_multi).
+    combine_scalars: (len(proofs), 4) uint64 Montgomery weights of the caller's; else they are drawn from combine_seed, which
+    must then be unpredictable to whoever made the proofs (a single proof has weight 1). Returns a Guard; a refused call raises.
+    opts_size: amdzk_verify_opts.size to report (tests)."""
+    B = len(proofs)
+    inst_pp, lens_pp, pp, pl, opts, st, keep = _verify_args(instances_list, proofs, transcript, n_circuits, combine_seed, combine_scalars, opts_size)
     pair = np.zeros(16, dtype=np.uint64)
     ctx._chk(ctx.L.amdzk_verify_proofs(ctx.h, pk.h, B, inst_pp, lens_pp, pp, pl, C.byref(opts), st, pair.ctypes.data))
     del keep
     return Guard(pair[:8].copy(), pair[8:].copy(), [ProofStatus(s.status, s.offset) for s in st[:B]])
+
+
+DECIDE_COMBINED = 1  # AMDZK_DECIDE_COMBINED
+DECIDE_RUN = 16      # AMDZK_DECIDE_RUN
+
+
+def decide_proofs(ctx, pk, vparams, instances_list, proofs, transcript=TRANSCRIPT_BLAKE2B, n_circuits=1, combined=False, combine_seed=0,
+                  combine_scalars=None, opts_size=None):
+    """amdzk_verify_proofs_decide: plonk::verify_proof for a batch WITH the pairing. vparams: kzg.ParamsVerifierKZG of the SRS
+    the key was made on. combined=False: every proof by itself (SingleStrategy; deterministic, combine_* ignored);
+    combined=True: upstream's BatchVerifier — one check with the weights of combine_seed / combine_scalars, which must be
+    unpredictable to whoever made the proofs; every well-formed proof gets that check's result. Returns (verdicts, statuses):
+    a list of bool and a list of ProofStatus; a malformed proof has verdict False. A refused call raises."""
+    B = len(proofs)
+    inst_pp, lens_pp, pp, pl, opts, st, keep = _verify_args(instances_list, proofs, transcript, n_circuits, combine_seed, combine_scalars, opts_size)
+    verdicts = np.zeros(max(1, B), np.uint8)
+    n_valid = C.c_size_t(0)
+    ctx._chk(ctx.L.amdzk_verify_proofs_decide(ctx.h, pk.h, vparams.s_g2.h, vparams.g2.h, DECIDE_COMBINED if combined else 0, B, inst_pp, lens_pp,
+                                              pp, pl, C.byref(opts), st, verdicts.ctypes.data, C.byref(n_valid)))
+    del keep
+    out = [bool(v) for v in verdicts[:B]]
+    assert sum(out) == n_valid.value
+    return out, [ProofStatus(s.status, s.offset) for s in st[:B]]
+
+
+def decide_proof(ctx, pk, vparams, instances, proof, transcript=TRANSCRIPT_BLAKE2B, n_circuits=1):
+    """plonk::verify_proof(params, vk, SingleStrategy, &[instances], transcript).is_ok(): True iff the proof is valid. Raises
+    ValueError naming the status and the offset when the proof is malformed, as verify_proof does."""
+    verdicts, statuses = decide_proofs(ctx, pk, vparams, [instances], [proof], transcript=transcript, n_circuits=n_circuits)
+    s = statuses[0]
+    if s.status != PROOF_WELL_FORMED:
+        raise ValueError("malformed proof: status %d (%s), offset %d" % (s.status, PROOF_STATUS_NAMES[s.status], s.offset))
+    return verdicts[0]
 
 
 def verify_proof(ctx, pk, instances, proof, transcript=TRANSCRIPT_BLAKE2B, n_circuits=1):

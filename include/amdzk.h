@@ -731,6 +731,59 @@ int amdzk_verify_proofs(amdzk_ctx* ctx, const amdzk_pk* pk, size_t n_proofs, con
                         const amdzk_verify_opts* opts /* NULL: defaults */, amdzk_proof_status* statuses /* n_proofs */,
                         uint64_t pair_out[16]);
 
+/* ---- pairing: BN254 optimal ate on the device, and proofs DECIDED in one call.
+ * Conventions are the published BN254 / EIP-197 ones (csrc/fq12.cuh states them; the reference repository holds no G2 data, so
+ * parity is unpinned): Fq2 = Fq[u]/(u^2 + 1), xi = 9 + u, Fq6 = Fq2[v]/(v^3 - xi), Fq12 = Fq6[w]/(w^2 - v); G2 = the order-r
+ * subgroup of the twist y^2 = x^3 + 3/xi; EIP-197's G2 generator; e(P, Q) = f^((p^12 - 1)/r) with the EXACT exponent (the fixed
+ * power c of a Fuentes-Castaneda style chain is c = 1), so a GT value is canonical and comparable across implementations.
+ * In-memory formats are halo2curves':
+ *   G2Affine : {x.c0, x.c1, y.c0, y.c1}, 16 x u64, Montgomery R = 2^256; all zero is the identity            (128 B)
+ *   Gt / Fq12: 12 Fq in declaration order c0.c0.c0, c0.c0.c1, c0.c1.c0, ..., c1.c2.c1, 48 x u64               (384 B)
+ *
+ * amdzk_g2: ONE G2 point prepared for pairing — the line coefficients of every step of the Miller loop (halo2curves'
+ * G2Prepared), computed on the host and resident on the ctx's device. amdzk_g2_prepare refuses, with AMDZK_E_INVALID and a
+ * message that starts "g2_prepare:": null arguments, a coordinate >= q, a point that is not on the twist, the identity.
+ * Membership in the order-r subgroup is NOT checked (as for in-memory points upstream): a point of the twist outside G2
+ * gives a meaningless GT value, never a fault. Free with amdzk_g2_free once no call is using it. */
+typedef struct amdzk_g2 amdzk_g2;
+int amdzk_g2_prepare(amdzk_ctx* ctx, const uint64_t q[16], amdzk_g2** out);
+void amdzk_g2_free(amdzk_ctx* ctx, amdzk_g2* g2);
+/* The G2 half of ParamsKZG::setup [UP] with the caller's trapdoor s (Montgomery, as for amdzk_srs_setup, and as unsafe):
+ * g2 = the generator, s_g2 = s * g2. Host work. The 64-byte compressed G2 encoding of the SRS file is NOT produced here:
+ * amdzk_srs_write / amdzk_srs_read keep passing those fields through. */
+int amdzk_g2_setup(amdzk_ctx* ctx, const uint64_t s[4], uint64_t g2_out[16], uint64_t s_g2_out[16]);
+/* n independent products over the same m prepared points: gt_i = prod_{j<m} e(P[i*m + j], Q_j).
+ * g1: n*m G1Affine (host); (0,0) = the identity, which contributes the factor 1 — so a product whose G1 entries are ALL the
+ * identity is 1 and reads is_one = 1. Points are NOT checked to be on the curve (as the MSM's bases).
+ * is_one (n bytes, may be NULL): gt_i == 1.  gt_out (n x 48 words, may be NULL).
+ * One lane per (product, pair) for the Miller loops, one lane per product for the final exponentiation: a lone product is
+ * SLOWER than a CPU's pairing; n products cost about the latency of one while n stays below the chip's lane count
+ * (profiles/pairing.txt). Refused with AMDZK_E_INVALID and "pairing_products:": nulls, m = 0, n = 0, m above
+ * AMDZK_PAIRING_MAX_M, n above 2^20; the ctx stays usable. Runs on the ctx's stream and returns with it idle. */
+#define AMDZK_PAIRING_MAX_M 16
+int amdzk_pairing_products(amdzk_ctx* ctx, const amdzk_g2* const* qs, size_t m, const uint64_t* g1, size_t n, uint8_t* is_one,
+                           uint64_t* gt_out);
+/* plonk::verify_proof [UP] with a verdict per proof, in one call: amdzk_verify_proofs and the pairing(s) behind it.
+ * s_g2, g2: the prepared [s]_2 and [1]_2 of the SRS the key was made on (amdzk_g2_setup, or the caller's own points).
+ * flags = 0 — every proof by itself with weight 1, as SingleStrategy would:
+ *   verdicts[b] = 1  iff  proof b is well formed and e(L_b, s_g2) = e(R_b, g2);  *n_valid (may be NULL) counts them.
+ *   opts->combine_* are ignored: no random weight enters a verdict, the result is deterministic. The decode launch and the
+ *   host half are amdzk_verify_proofs' own, once for the batch; the per-proof pairs come from the caller-supplied-bases MSM
+ *   in runs of at most AMDZK_DECIDE_RUN proofs (2 columns per proof over the key's commitments, G and that run's decoded
+ *   points: scratch is linear in the batch, one host wait more per run); ONE pairing launch over all proofs finishes.
+ * flags = AMDZK_DECIDE_COMBINED — upstream's BatchVerifier: the two-column path of amdzk_verify_proofs with rho from opts
+ *   (which must then be unpredictable, see above) and ONE check; every well-formed proof's verdict is that check's result.
+ * In both modes a malformed proof has verdict 0 and its status in statuses[b] (as amdzk_verify_proofs); a pair with L or R
+ * the identity has verdict 0 (a pair of identities must not read as valid), so a batch without a well-formed proof has
+ * n_valid = 0. Refusals are amdzk_verify_proofs' own plus null s_g2 / g2 / verdicts and unknown flag bits, with the prefix
+ * "verify_proofs_decide:". Not checked: subgroup membership of the G2 points, and that s_g2 / g2 belong to the key's SRS. */
+#define AMDZK_DECIDE_COMBINED 1u
+#define AMDZK_DECIDE_RUN 16
+int amdzk_verify_proofs_decide(amdzk_ctx* ctx, const amdzk_pk* pk, const amdzk_g2* s_g2, const amdzk_g2* g2, uint32_t flags,
+                               size_t n_proofs, const uint64_t* const* const* instances, const size_t* const* instance_lens,
+                               const uint8_t* const* proofs, const size_t* proof_lens, const amdzk_verify_opts* opts,
+                               amdzk_proof_status* statuses, uint8_t* verdicts /* n_proofs */, size_t* n_valid);
+
 /* Test hooks for the host pass that prepares quotient-domain programs for the limb-resident interpreter (bounds in
  * units of p, placement of the weak reductions, fusion of `t*x` with the accumulate): the pass on caller-supplied words
  * `op << 24 | arg` (opcodes: csrc/plonk_kernels.hpp ExprOp) — pure host code, callable without a device — and the

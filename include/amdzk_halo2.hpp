@@ -1206,6 +1206,58 @@ struct Guard {
   }
 };
 
+// The arguments amdzk_verify_proofs and amdzk_verify_proofs_decide share, built from the mirrors' containers (which must
+// outlive it).
+struct VerifyArgs {
+  size_t B = 0, N = 1;
+  std::vector<std::vector<const uint64_t*>> ptrs;
+  std::vector<std::vector<size_t>> lens;
+  std::vector<const uint64_t* const*> inst_pp;
+  std::vector<const size_t*> lens_pp;
+  std::vector<const uint8_t*> pp;
+  std::vector<size_t> pl;
+  amdzk_verify_opts opts = {};
+  std::vector<amdzk_proof_status> raw;
+  VerifyArgs(const char* who, const std::vector<std::vector<std::vector<std::vector<Fr>>>>& instances, const std::vector<std::vector<uint8_t>>& proofs,
+             Transcript transcript, Multiopen multiopen, uint64_t combine_seed, const std::vector<Fr>& combine_scalars) {
+    const std::string w(who);
+    B = proofs.size();
+    if (instances.size() != B) throw Error(AMDZK_E_INVALID, w + ": one instance list per proof");
+    if (!combine_scalars.empty() && combine_scalars.size() != B) throw Error(AMDZK_E_INVALID, w + ": one weight per proof");
+    N = B ? instances[0].size() : 1;
+    for (size_t b = 0; b < B; b++) {
+      if (instances[b].size() != N || N == 0) throw Error(AMDZK_E_INVALID, w + ": every proof has the same number of circuit instances");
+      for (size_t c = 0; c < N; c++) {
+        const auto& cols = instances[b][c];
+        ptrs.emplace_back(std::max<size_t>(1, cols.size()), nullptr);
+        lens.emplace_back(std::max<size_t>(1, cols.size()), 0);
+        for (size_t i = 0; i < cols.size(); i++) {
+          ptrs.back()[i] = cols[i].empty() ? nullptr : (const uint64_t*)cols[i].data();
+          lens.back()[i] = cols[i].size();
+        }
+      }
+    }
+    inst_pp.assign(std::max<size_t>(1, B * N), nullptr);
+    lens_pp.assign(std::max<size_t>(1, B * N), nullptr);
+    for (size_t i = 0; i < ptrs.size(); i++) inst_pp[i] = ptrs[i].data(), lens_pp[i] = lens[i].data();
+    static const uint8_t none = 0;
+    pp.assign(std::max<size_t>(1, B), nullptr);
+    pl.assign(std::max<size_t>(1, B), 0);
+    for (size_t b = 0; b < B; b++) pp[b] = proofs[b].empty() ? &none : proofs[b].data(), pl[b] = proofs[b].size();
+    opts.size = sizeof(opts);
+    opts.transcript_kind = (int)transcript | (int)multiopen;
+    opts.n_circuits = (uint32_t)N;
+    opts.combine_seed = combine_seed;
+    opts.combine_scalars = combine_scalars.empty() ? nullptr : (const uint64_t*)combine_scalars.data();
+    raw.resize(std::max<size_t>(1, B));
+  }
+  std::vector<ProofStatus> statuses() const {
+    std::vector<ProofStatus> out;
+    for (size_t b = 0; b < B; b++) out.push_back(ProofStatus{(ProofStatus::Status)raw[b].status, raw[b].offset});
+    return out;
+  }
+};
+
 // AccumulatorStrategy / BatchVerifier: one call per batch. instances[b][c][col]: the public inputs of circuit instance c of
 // proof b (n_circuits instances per proof, as create_proof_multi wrote them). combine_scalars: one weight per proof, or
 // empty to draw them from combine_seed — which must then be unpredictable to whoever made the proofs (seed it from the OS).
@@ -1213,44 +1265,13 @@ struct Guard {
 inline Guard verify_proofs(const Context& ctx, const ProvingKey& pk, const std::vector<std::vector<std::vector<std::vector<Fr>>>>& instances,
                            const std::vector<std::vector<uint8_t>>& proofs, Transcript transcript = Transcript::Blake2b,
                            Multiopen multiopen = Multiopen::Shplonk, uint64_t combine_seed = 0, const std::vector<Fr>& combine_scalars = {}) {
-  const size_t B = proofs.size();
-  if (instances.size() != B) throw Error(AMDZK_E_INVALID, "verify_proofs: one instance list per proof");
-  if (!combine_scalars.empty() && combine_scalars.size() != B) throw Error(AMDZK_E_INVALID, "verify_proofs: one weight per proof");
-  const size_t N = B ? instances[0].size() : 1;
-  std::vector<std::vector<const uint64_t*>> ptrs;
-  std::vector<std::vector<size_t>> lens;
-  for (size_t b = 0; b < B; b++) {
-    if (instances[b].size() != N || N == 0) throw Error(AMDZK_E_INVALID, "verify_proofs: every proof has the same number of circuit instances");
-    for (size_t c = 0; c < N; c++) {
-      const auto& cols = instances[b][c];
-      ptrs.emplace_back(std::max<size_t>(1, cols.size()), nullptr);
-      lens.emplace_back(std::max<size_t>(1, cols.size()), 0);
-      for (size_t i = 0; i < cols.size(); i++) {
-        ptrs.back()[i] = cols[i].empty() ? nullptr : (const uint64_t*)cols[i].data();
-        lens.back()[i] = cols[i].size();
-      }
-    }
-  }
-  std::vector<const uint64_t* const*> inst_pp(std::max<size_t>(1, B * N), nullptr);
-  std::vector<const size_t*> lens_pp(std::max<size_t>(1, B * N), nullptr);
-  for (size_t i = 0; i < ptrs.size(); i++) inst_pp[i] = ptrs[i].data(), lens_pp[i] = lens[i].data();
-  static const uint8_t none = 0;
-  std::vector<const uint8_t*> pp(std::max<size_t>(1, B), nullptr);
-  std::vector<size_t> pl(std::max<size_t>(1, B), 0);
-  for (size_t b = 0; b < B; b++) pp[b] = proofs[b].empty() ? &none : proofs[b].data(), pl[b] = proofs[b].size();
-  amdzk_verify_opts opts = {};
-  opts.size = sizeof(opts);
-  opts.transcript_kind = (int)transcript | (int)multiopen;
-  opts.n_circuits = (uint32_t)N;
-  opts.combine_seed = combine_seed;
-  opts.combine_scalars = combine_scalars.empty() ? nullptr : (const uint64_t*)combine_scalars.data();
-  std::vector<amdzk_proof_status> raw(std::max<size_t>(1, B));
+  VerifyArgs a("verify_proofs", instances, proofs, transcript, multiopen, combine_seed, combine_scalars);
   uint64_t pair[16];
-  ctx.check(amdzk_verify_proofs(ctx.get(), pk.handle(), B, inst_pp.data(), lens_pp.data(), pp.data(), pl.data(), &opts, raw.data(), pair));
+  ctx.check(amdzk_verify_proofs(ctx.get(), pk.handle(), a.B, a.inst_pp.data(), a.lens_pp.data(), a.pp.data(), a.pl.data(), &a.opts, a.raw.data(), pair));
   Guard g;
   std::memcpy(&g.lhs, pair, sizeof(G1Affine));
   std::memcpy(&g.rhs, pair + 8, sizeof(G1Affine));
-  for (size_t b = 0; b < B; b++) g.statuses.push_back(ProofStatus{(ProofStatus::Status)raw[b].status, raw[b].offset});
+  g.statuses = a.statuses();
   return g;
 }
 
@@ -1262,6 +1283,70 @@ inline Guard verify_proof(const Context& ctx, const ProvingKey& pk, const std::v
     throw Error(AMDZK_E_INVALID, "verify_proof: malformed proof, status " + std::to_string((unsigned)g.statuses[0].status) + ", offset " +
                                      std::to_string(g.statuses[0].offset));
   return g;
+}
+
+// ------------------------------------------------------------------------------------------ verify_proof WITH the pairing
+// The G2 side (include/amdzk.h "pairing"; conventions: csrc/fq12.cuh). G2Affine is halo2curves' {x.c0, x.c1, y.c0, y.c1},
+// Montgomery; all zero is the identity.
+struct G2Affine {
+  uint64_t w[16];
+};
+// halo2curves' G2Prepared: one finite point's line coefficients, resident on the device. Subgroup membership is not checked.
+class G2Prepared {
+ public:
+  G2Prepared(const Context& ctx, const G2Affine& q) : ctx_(ctx) { ctx_.check(amdzk_g2_prepare(ctx_.get(), q.w, &h_)); }
+  ~G2Prepared() {
+    if (h_) amdzk_g2_free(ctx_.get(), h_);
+  }
+  G2Prepared(G2Prepared&& o) noexcept : ctx_(o.ctx_), h_(o.h_) { o.h_ = nullptr; }
+  G2Prepared(const G2Prepared&) = delete;
+  G2Prepared& operator=(const G2Prepared&) = delete;
+  const amdzk_g2* handle() const { return h_; }
+
+ private:
+  const Context& ctx_;
+  amdzk_g2* h_ = nullptr;
+};
+// The verifier's part of ParamsKZG: the prepared [1]_2 and [s]_2.
+struct ParamsVerifierKZG {
+  G2Prepared g2, s_g2;
+  ParamsVerifierKZG(const Context& ctx, const G2Affine& g2_, const G2Affine& s_g2_) : g2(ctx, g2_), s_g2(ctx, s_g2_) {}
+  // the G2 half of ParamsKZG::setup with the trapdoor given explicitly (tests / benchmarks, as unsafe as ParamsKZG::setup)
+  static ParamsVerifierKZG setup(const Context& ctx, const Fr& s) {
+    G2Affine g, sg;
+    ctx.check(amdzk_g2_setup(ctx.get(), s.l, g.w, sg.w));
+    return ParamsVerifierKZG(ctx, g, sg);
+  }
+};
+struct Decision {
+  std::vector<bool> verdicts;         // one per proof; a malformed proof is false
+  std::vector<ProofStatus> statuses;  // as verify_proofs'
+  size_t n_valid = 0;
+};
+// amdzk_verify_proofs_decide. combined = false: every proof by itself (SingleStrategy; deterministic, the weights are not
+// read). combined = true: upstream's BatchVerifier — ONE check with the weights of combine_seed / combine_scalars, which must
+// be unpredictable to whoever made the proofs; every well-formed proof gets that check's result.
+inline Decision decide_proofs(const Context& ctx, const ProvingKey& pk, const ParamsVerifierKZG& vparams,
+                              const std::vector<std::vector<std::vector<std::vector<Fr>>>>& instances, const std::vector<std::vector<uint8_t>>& proofs,
+                              Transcript transcript = Transcript::Blake2b, Multiopen multiopen = Multiopen::Shplonk, bool combined = false,
+                              uint64_t combine_seed = 0, const std::vector<Fr>& combine_scalars = {}) {
+  VerifyArgs a("decide_proofs", instances, proofs, transcript, multiopen, combine_seed, combine_scalars);
+  std::vector<uint8_t> v(std::max<size_t>(1, a.B), 0);
+  Decision d;
+  ctx.check(amdzk_verify_proofs_decide(ctx.get(), pk.handle(), vparams.s_g2.handle(), vparams.g2.handle(), combined ? AMDZK_DECIDE_COMBINED : 0u, a.B,
+                                       a.inst_pp.data(), a.lens_pp.data(), a.pp.data(), a.pl.data(), &a.opts, a.raw.data(), v.data(), &d.n_valid));
+  for (size_t b = 0; b < a.B; b++) d.verdicts.push_back(v[b] != 0);
+  d.statuses = a.statuses();
+  return d;
+}
+// plonk::verify_proof(params, vk, SingleStrategy, ...).is_ok(). A malformed proof throws, naming status and offset.
+inline bool decide_proof(const Context& ctx, const ProvingKey& pk, const ParamsVerifierKZG& vparams, const std::vector<std::vector<Fr>>& instances,
+                         const std::vector<uint8_t>& proof, Transcript transcript = Transcript::Blake2b, Multiopen multiopen = Multiopen::Shplonk) {
+  const Decision d = decide_proofs(ctx, pk, vparams, {{instances}}, {proof}, transcript, multiopen);
+  if (d.statuses[0].status != ProofStatus::WellFormed)
+    throw Error(AMDZK_E_INVALID, "decide_proof: malformed proof, status " + std::to_string((unsigned)d.statuses[0].status) + ", offset " +
+                                     std::to_string(d.statuses[0].offset));
+  return d.verdicts[0];
 }
 
 }  // namespace halo2

@@ -45,7 +45,7 @@ def main():
         def resident(cols):  # canonical limbs up, Fr::from_raw on the device
             host = np.ascontiguousarray(wl.canon_limbs(cols))
             d = ctx.alloc(host.nbytes).upload(host)
-            ctx._chk(ctx.L.amdzk_fr_from_raw_dev(ctx.h, d.ptr, len(cols) * n))
+            ctx._chk(ctx.L.amdzk_fr_from_raw_dev(ctx.h, d.ptr, host.size // 4))  # the buffer's own element count: an instance column is shorter than n
             return d
 
         d_fixed = resident(c.fixed)
