@@ -149,6 +149,20 @@ inline Fr fr_delta() {
   memcpy(r.l, v, 32);
   return bn254::to_mont(r);
 }
+// halo2curves bn256 Fr::ROOT_OF_UNITY = 7^((r-1)/2^28) [UP], S = 28, and the generator of the 2^k-element subgroup it gives
+// (EvaluationDomain's omega): FR_S - k squarings. k <= FR_S.
+constexpr uint32_t FR_S = 28;
+inline Fr fr_root_of_unity() {
+  Fr r;
+  uint64_t v[4] = {0xd34f1ed960c37c9cULL, 0x3215cf6dd39329c8ULL, 0x98865ea93dd31f74ULL, 0x03ddb9f5166d18b7ULL};
+  memcpy(r.l, v, 32);
+  return bn254::to_mont(r);
+}
+inline Fr fr_omega(uint32_t k) {
+  Fr w = fr_root_of_unity();
+  for (uint32_t i = k; i < FR_S; i++) w = bn254::sqr(w);
+  return w;
+}
 // halo2curves 0.3.1 G1Affine::to_bytes [UP recall]: x little-endian; bit 7 of byte 31 = y & 1.
 inline void g1_compress(const bn254::G1Affine& p, uint8_t out[32]) {
   if (p.is_inf()) {

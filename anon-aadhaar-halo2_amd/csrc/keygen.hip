@@ -202,12 +202,13 @@ static int bind_workspace(amdzk_ctx* ctx, amdzk_pk* pk) {
   return upload_consts261(ctx, pk);
 }
 
-// ---- keygen, step by step (keygen_common below runs them in this order)
+// ---- keygen, step by step (keygen_common below runs them in this order; amdzk_keygen_vk, vk.hip, runs the ones pk.hpp
+// declares, with vk_only set)
 
 // The phase table the way ConstraintSystem::{advice_column_in, challenge_usable_after} assert [UP], the flags and the null
 // arguments: pure checks, before anything is allocated. *nphases: the number of phases the table uses (1 without one).
-static int check_keygen_args(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* c, const amdzk_phases* ph,
-                             const uint64_t transcript_repr[4], uint32_t flags, amdzk_pk** out, uint32_t* nphases) {
+int check_keygen_args(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* c, const amdzk_phases* ph, const uint64_t transcript_repr[4],
+                      uint32_t flags, amdzk_pk** out, uint32_t* nphases) {
   *nphases = 1;
   if (ph && c) {
     if ((c->num_advice && !ph->advice_phase) || (ph->num_challenges && !ph->challenge_phase))
@@ -240,9 +241,10 @@ static int check_keygen_args(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_c
 }
 
 // The circuit description into the key — shape, domain, queries, expressions, the key file's header — and the layout of
-// the constant table.
-static int describe_circuit(amdzk_ctx* ctx, amdzk_pk* pk, const amdzk_srs* srs, const amdzk_circuit* c, const amdzk_phases* ph, uint32_t nphases,
-                            const uint64_t transcript_repr[4], uint32_t flags) {
+// the constant table. vk_only (amdzk_keygen_vk, vk.hip): the key will only commit to its fixed and permutation columns —
+// no prefix basis, no quotient plan, no extended domain (ext stays 0).
+int describe_circuit(amdzk_ctx* ctx, amdzk_pk* pk, const amdzk_srs* srs, const amdzk_circuit* c, const amdzk_phases* ph, uint32_t nphases,
+                     const uint64_t transcript_repr[4], uint32_t flags, bool vk_only) {
   pk->srs = srs;
   pk->chk_shared = std::make_shared<amdzk_pk::CheckShared>();
   pk->k = c->k;
@@ -257,7 +259,7 @@ static int describe_circuit(amdzk_ctx* ctx, amdzk_pk* pk, const amdzk_srs* srs, 
   pk->chunk = pk->degree - 2;
   pk->nsets = (pk->S + pk->chunk - 1) / pk->chunk;
   pk->qdeg = pk->degree - 1;
-  if (pk->S) ZK_TRY(zk_srs_ensure_prefix(ctx, srs));  // the permutation products are committed over it (Prover::perm_commit)
+  if (pk->S && !vk_only) ZK_TRY(zk_srs_ensure_prefix(ctx, srs));  // the permutation products are committed over it (Prover::perm_commit)
   if (ph) {
     pk->nphases = nphases;
     pk->num_challenges = ph->num_challenges;
@@ -272,8 +274,10 @@ static int describe_circuit(amdzk_ctx* ctx, amdzk_pk* pk, const amdzk_srs* srs, 
   // computation — identical output for satisfying witnesses, and the way to reproduce upstream's bytes for others)
   pk->nc = (flags & AMDZK_KEYGEN_FULL_COSETS) ? (1u << (pk->ek - pk->k)) : pk->qdeg;
   pk->use_lanes = !(flags & AMDZK_KEYGEN_SERIAL);
-  ZK_TRY(zk_quotient_plan(ctx, pk->dom, pk->nc));
-  pk->ext = (size_t)pk->nc * pk->n;
+  if (!vk_only) {
+    ZK_TRY(zk_quotient_plan(ctx, pk->dom, pk->nc));
+    pk->ext = (size_t)pk->nc * pk->n;
+  }
   amdzk_domain_constant(pk->dom, 0, (uint64_t*)pk->omega.l);
   amdzk_domain_constant(pk->dom, 1, (uint64_t*)pk->omega_inv.l);
   for (uint32_t i = 0; i < c->num_advice_queries; i++) pk->advice_queries.push_back({c->advice_queries[2 * i], c->advice_queries[2 * i + 1]});
@@ -387,21 +391,25 @@ static int build_domain_columns(amdzk_ctx* ctx, amdzk_pk* pk) {
   return AMDZK_OK;
 }
 
-// The fixed columns: Lagrange values as given, coefficients, cosets, commitments.
-static int load_fixed_columns(amdzk_ctx* ctx, amdzk_pk* pk, const void* fixed_values) {
+// The fixed columns: Lagrange values as given, coefficients, cosets, commitments. vk_only: the Lagrange values (the one
+// buffer the key then has to have) and the commitments.
+int load_fixed_columns(amdzk_ctx* ctx, amdzk_pk* pk, const void* fixed_values, bool vk_only) {
   const size_t n = pk->n;
   const uint32_t F = pk->F;
   if (!F) return AMDZK_OK;
   if (!fixed_values) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: fixed_values is null");
   ZK_TRY(h2d(ctx, pk->fixed_lag, fixed_values, (size_t)F * n * 32));
-  ZK_TRY(d2d(ctx, pk->fixed_poly, pk->fixed_lag, (size_t)F * n * 32));
-  ZK_TRY(amdzk_lagrange_to_coeff_dev(ctx, pk->dom, pk->fixed_poly, F, n));
-  ZK_TRY(zk_coeff_to_cosets_r261(ctx, pk->dom, pk->fixed_poly, n, pk->fixed_coset, pk->ext, F));
+  if (!vk_only) {
+    ZK_TRY(d2d(ctx, pk->fixed_poly, pk->fixed_lag, (size_t)F * n * 32));
+    ZK_TRY(amdzk_lagrange_to_coeff_dev(ctx, pk->dom, pk->fixed_poly, F, n));
+    ZK_TRY(zk_coeff_to_cosets_r261(ctx, pk->dom, pk->fixed_poly, n, pk->fixed_coset, pk->ext, F));
+  }
   return commit_cols(ctx, pk, AMDZK_BASIS_G_LAGRANGE, pk->fixed_lag, F, pk->fixed_commitments);
 }
 
-// The permutation columns: their Lagrange values from the mapping or as given, then what both routes share.
-static int load_sigma_columns(amdzk_ctx* ctx, amdzk_pk* pk, const uint32_t* perm_mapping, const void* sigma_values, bool from_sigma) {
+// The permutation columns: their Lagrange values from the mapping or as given, then what both routes share. vk_only: as
+// for the fixed columns.
+int load_sigma_columns(amdzk_ctx* ctx, amdzk_pk* pk, const uint32_t* perm_mapping, const void* sigma_values, bool from_sigma, bool vk_only) {
   const size_t n = pk->n;
   const uint32_t S = pk->S;
   if (!S) return AMDZK_OK;
@@ -432,9 +440,11 @@ static int load_sigma_columns(amdzk_ctx* ctx, amdzk_pk* pk, const uint32_t* perm
     ZK_TRY(h2d(ctx, pk->sigma_lag, sig.data(), (size_t)S * n * 32));
     ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
   }
-  ZK_TRY(d2d(ctx, pk->sigma_poly, pk->sigma_lag, (size_t)S * n * 32));
-  ZK_TRY(amdzk_lagrange_to_coeff_dev(ctx, pk->dom, pk->sigma_poly, S, n));
-  ZK_TRY(zk_coeff_to_cosets_r261(ctx, pk->dom, pk->sigma_poly, n, pk->sigma_coset, pk->ext, S));
+  if (!vk_only) {
+    ZK_TRY(d2d(ctx, pk->sigma_poly, pk->sigma_lag, (size_t)S * n * 32));
+    ZK_TRY(amdzk_lagrange_to_coeff_dev(ctx, pk->dom, pk->sigma_poly, S, n));
+    ZK_TRY(zk_coeff_to_cosets_r261(ctx, pk->dom, pk->sigma_poly, n, pk->sigma_coset, pk->ext, S));
+  }
   return commit_cols(ctx, pk, AMDZK_BASIS_G_LAGRANGE, pk->sigma_lag, S, pk->perm_commitments);
 }
 
@@ -788,11 +798,11 @@ static int keygen_common(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circu
   ZK_TRY(check_keygen_args(ctx, srs, c, ph, transcript_repr, flags, out, &nphases));
   PkOwner owner(new amdzk_pk(), PkFree{ctx});
   amdzk_pk* pk = owner.get();
-  ZK_TRY(describe_circuit(ctx, pk, srs, c, ph, nphases, transcript_repr, flags));
+  ZK_TRY(describe_circuit(ctx, pk, srs, c, ph, nphases, transcript_repr, flags, false));
   ZK_TRY(alloc_key_material(ctx, pk));
   ZK_TRY(build_domain_columns(ctx, pk));
-  ZK_TRY(load_fixed_columns(ctx, pk, fixed_values));
-  ZK_TRY(load_sigma_columns(ctx, pk, perm_mapping, sigma_values, from_sigma));
+  ZK_TRY(load_fixed_columns(ctx, pk, fixed_values, false));
+  ZK_TRY(load_sigma_columns(ctx, pk, perm_mapping, sigma_values, from_sigma, false));
   ZK_TRY(build_perm_lists(ctx, pk));
   // rotations 0, 1, -1 and -(bf + 1) open the rotation table of every key, ahead of what its expressions query
   for (int32_t r : {0, 1, -1, -(int32_t)(pk->bf + 1)}) pk->rots.index(r);

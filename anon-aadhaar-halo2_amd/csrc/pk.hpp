@@ -253,6 +253,15 @@ int d2d(amdzk_ctx* ctx, void* dst, const void* src, size_t bytes);
 // MSM of ncols resident columns of the key's n rows -> affine points on the host (prover.hip)
 int commit_cols(amdzk_ctx* ctx, amdzk_pk* pk, int basis, const Fr* d_cols, size_t ncols, std::vector<G1Affine>& out);
 
+// ---- keygen's steps that amdzk_keygen_vk (vk.hip) runs too (keygen.hip has them in keygen's order). vk_only: the key is a
+// scratch object that holds the description and the F + S Lagrange columns, and nothing sized by the extended domain.
+int check_keygen_args(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* c, const amdzk_phases* ph, const uint64_t transcript_repr[4],
+                      uint32_t flags, amdzk_pk** out, uint32_t* nphases);
+int describe_circuit(amdzk_ctx* ctx, amdzk_pk* pk, const amdzk_srs* srs, const amdzk_circuit* c, const amdzk_phases* ph, uint32_t nphases,
+                     const uint64_t transcript_repr[4], uint32_t flags, bool vk_only);
+int load_fixed_columns(amdzk_ctx* ctx, amdzk_pk* pk, const void* fixed_values, bool vk_only);
+int load_sigma_columns(amdzk_ctx* ctx, amdzk_pk* pk, const uint32_t* perm_mapping, const void* sigma_values, bool from_sigma, bool vk_only);
+
 // ---- programs (program.hip)
 constexpr uint32_t H_PARTS_MAX = 8;  // pieces finalize_limb_program cuts an h(X) program into, at most: one h each (amdzk_pk::hq)
 int emit_expr(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, const std::vector<uint32_t>& words);

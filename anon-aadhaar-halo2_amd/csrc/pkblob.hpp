@@ -95,19 +95,28 @@ struct Desc {
     c->num_perm_columns = num_perm_columns(), c->perm_columns = perm_columns.data();
     ph->num_challenges = num_challenges, ph->advice_phase = advice_phase.data(), ph->challenge_phase = challenge_phase.data();
   }
-  size_t header_bytes() const {  // magic .. phase table
-    size_t b = MAGIC_BYTES + 4 + 6 * 4;
+  // amdzk_circuit .. phase table: the sections the verifying-key file (vkblob.hpp) shares with this one, byte for byte
+  size_t circuit_bytes() const {
+    size_t b = 6 * 4;
     b += 3 * 4 + 4 * (advice_queries.size() + fixed_queries.size() + instance_queries.size());
     b += 3 * 4 + 4 * (lookup_shape.size() + expr_offsets.size() + expr_words.size());
     b += 4 + 8 * constants.size() + 4 + 4 * perm_columns.size();
     b += 1 + (has_phases ? 4 + advice_phase.size() + challenge_phase.size() : 0);
     return b;
   }
+  size_t header_bytes() const { return MAGIC_BYTES + 4 + circuit_bytes(); }  // magic .. phase table
   size_t columns() const { return (size_t)num_fixed + num_perm_columns(); }
   // bytes of the whole file, for a description that passed validate(): at most 2^17 columns of 2^28 rows, below 2^51
   size_t serialized_size() const { return header_bytes() + 32 + columns() * 64 + (columns() << k) * 32 + DIGEST_BYTES; }
   // writes header_bytes() bytes
   void write_header(uint8_t* out) const {
+    memcpy(out, magic(), MAGIC_BYTES);
+    const uint32_t version = FORMAT_VERSION;
+    memcpy(out + MAGIC_BYTES, &version, 4);
+    write_circuit(out + MAGIC_BYTES + 4);
+  }
+  // writes circuit_bytes() bytes
+  void write_circuit(uint8_t* out) const {
     uint8_t* p = out;
     auto put = [&](const void* s, size_t n) {
       if (n) memcpy(p, s, n);
@@ -115,8 +124,6 @@ struct Desc {
     };
     auto u32 = [&](uint32_t v) { put(&v, 4); };
     auto arr = [&](const auto& v) { put(v.data(), v.size() * sizeof(v[0])); };
-    put(magic(), MAGIC_BYTES);
-    u32(FORMAT_VERSION);
     u32(k), u32(num_fixed), u32(num_advice), u32(num_instance), u32(blinding_factors), u32(cs_degree);
     u32((uint32_t)(advice_queries.size() / 2)), arr(advice_queries);
     u32((uint32_t)(fixed_queries.size() / 2)), arr(fixed_queries);
@@ -164,6 +171,34 @@ inline int fail(std::string* err, const char* fmt, unsigned long long a = 0, uns
     *err = std::string("pk_read: ") + buf;
   }
   return AMDZK_E_INVALID;
+}
+// amdzk_circuit .. phase table at r.pos into *d (the sections Desc::write_circuit writes): every count is checked against the
+// bytes that are left before anything is sized by it. Shared with the verifying-key file's parser (vkblob.hpp).
+inline int read_circuit(Reader& r, Desc* d, std::string* err) {
+  const size_t len = r.len;
+  uint32_t cnt = 0;
+#define PKB_GET(x) \
+  if (!(x)) return fail(err, "truncated: the header runs past the %llu bytes given", len)
+  PKB_GET(r.u32(&d->k) && r.u32(&d->num_fixed) && r.u32(&d->num_advice) && r.u32(&d->num_instance) && r.u32(&d->blinding_factors) &&
+          r.u32(&d->cs_degree));
+  PKB_GET(r.u32(&cnt) && r.arr(d->advice_queries, 2 * (uint64_t)cnt));
+  PKB_GET(r.u32(&cnt) && r.arr(d->fixed_queries, 2 * (uint64_t)cnt));
+  PKB_GET(r.u32(&cnt) && r.arr(d->instance_queries, 2 * (uint64_t)cnt));
+  PKB_GET(r.u32(&d->num_gates) && r.u32(&d->num_lookups) && r.u32(&d->num_exprs));
+  PKB_GET(r.arr(d->lookup_shape, 2 * (uint64_t)d->num_lookups));
+  PKB_GET(r.arr(d->expr_offsets, (uint64_t)d->num_exprs + 1));
+  PKB_GET(r.arr(d->expr_words, d->expr_offsets.back()));
+  PKB_GET(r.u32(&cnt) && r.arr(d->constants, 4 * (uint64_t)cnt));
+  PKB_GET(r.u32(&cnt) && r.arr(d->perm_columns, 2 * (uint64_t)cnt));
+  std::vector<uint8_t> hp;
+  PKB_GET(r.arr(hp, 1));
+  if (hp[0] > 1) return fail(err, "has-phases byte is %llu", hp[0]);
+  d->has_phases = hp[0] == 1;
+  d->num_challenges = 0;
+  d->advice_phase.clear(), d->challenge_phase.clear();
+  if (d->has_phases) PKB_GET(r.u32(&d->num_challenges) && r.arr(d->advice_phase, d->num_advice) && r.arr(d->challenge_phase, d->num_challenges));
+#undef PKB_GET
+  return AMDZK_OK;
 }
 }  // namespace detail
 
@@ -245,30 +280,10 @@ inline int parse(const uint8_t* data, size_t len, Desc* d, Layout* lay, std::str
   if (len < MAGIC_BYTES + 4 + DIGEST_BYTES) return fail(err, "%llu bytes are too few for a key file", len);
   if (memcmp(data, magic(), MAGIC_BYTES) != 0) return fail(err, "bad magic: not a proving-key file");
   r.pos = MAGIC_BYTES;
-  uint32_t version = 0, cnt = 0;
+  uint32_t version = 0;
   r.u32(&version);
   if (version != FORMAT_VERSION) return fail(err, "format version %llu, this library reads version %llu", version, FORMAT_VERSION);
-#define PKB_GET(x) \
-  if (!(x)) return fail(err, "truncated: the header runs past the %llu bytes given", len)
-  PKB_GET(r.u32(&d->k) && r.u32(&d->num_fixed) && r.u32(&d->num_advice) && r.u32(&d->num_instance) && r.u32(&d->blinding_factors) &&
-          r.u32(&d->cs_degree));
-  PKB_GET(r.u32(&cnt) && r.arr(d->advice_queries, 2 * (uint64_t)cnt));
-  PKB_GET(r.u32(&cnt) && r.arr(d->fixed_queries, 2 * (uint64_t)cnt));
-  PKB_GET(r.u32(&cnt) && r.arr(d->instance_queries, 2 * (uint64_t)cnt));
-  PKB_GET(r.u32(&d->num_gates) && r.u32(&d->num_lookups) && r.u32(&d->num_exprs));
-  PKB_GET(r.arr(d->lookup_shape, 2 * (uint64_t)d->num_lookups));
-  PKB_GET(r.arr(d->expr_offsets, (uint64_t)d->num_exprs + 1));
-  PKB_GET(r.arr(d->expr_words, d->expr_offsets.back()));
-  PKB_GET(r.u32(&cnt) && r.arr(d->constants, 4 * (uint64_t)cnt));
-  PKB_GET(r.u32(&cnt) && r.arr(d->perm_columns, 2 * (uint64_t)cnt));
-  std::vector<uint8_t> hp;
-  PKB_GET(r.arr(hp, 1));
-  if (hp[0] > 1) return fail(err, "has-phases byte is %llu", hp[0]);
-  d->has_phases = hp[0] == 1;
-  d->num_challenges = 0;
-  d->advice_phase.clear(), d->challenge_phase.clear();
-  if (d->has_phases) PKB_GET(r.u32(&d->num_challenges) && r.arr(d->advice_phase, d->num_advice) && r.arr(d->challenge_phase, d->num_challenges));
-#undef PKB_GET
+  if (int rc = detail::read_circuit(r, d, err)) return rc;
   if (d->k < 1 || d->k > MAX_K) return fail(err, "k = %llu out of range (1 .. 28)", d->k);
   // sections behind the header: with both counts bounded, F + S <= 2^17 columns of 2^k <= 2^28 rows of 32 bytes are at
   // most 2^50 bytes, so `want` cannot wrap (unbounded, 2^33 columns would reach 2^66)

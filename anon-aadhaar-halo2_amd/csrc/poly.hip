@@ -11,6 +11,7 @@
 
 #include "common.hpp"
 #include "fp29.cuh"
+#include "hostcrypto.hpp"
 
 using namespace bn254;
 
@@ -41,14 +42,12 @@ Fr fr_from_canonical(uint64_t a3, uint64_t a2, uint64_t a1, uint64_t a0) {
   memcpy(r.l, v, 32);
   return to_mont(r);
 }
-// halo2curves bn256 Fr::ROOT_OF_UNITY = 7^((r-1)/2^28) and Fr::ZETA [UP]; S = 28.
-Fr fr_root_of_unity() {
-  return fr_from_canonical(0x03ddb9f5166d18b7ULL, 0x98865ea93dd31f74ULL, 0x3215cf6dd39329c8ULL, 0xd34f1ed960c37c9cULL);
-}
+// halo2curves bn256 Fr::ZETA [UP]; Fr::ROOT_OF_UNITY and S = 28 are hostcrypto.hpp's (zkhost::fr_root_of_unity, FR_S)
+using zkhost::FR_S;
+using zkhost::fr_root_of_unity;
 Fr fr_zeta() {
   return fr_from_canonical(0x30644e72e131a029ULL, 0x048b6e193fd84104ULL, 0xcc37a73fec2bc5e9ULL, 0xb8ca0b2d36636f23ULL);
 }
-constexpr uint32_t FR_S = 28;
 
 __device__ __forceinline__ Fr ld_fr(const Fr* p) {
   const uint4* q = reinterpret_cast<const uint4*>(p);

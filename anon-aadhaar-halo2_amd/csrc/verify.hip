@@ -2,7 +2,8 @@
 // sums of the final pairing check. The device decodes every element of every proof in one launch (decompression with its
 // curve check, range checks, Montgomery conversion) and runs the one two-column MSM; the transcript, the vanishing
 // identity and the per-base scalars are the host half's (verifier.hpp). Two host waits per call. Nothing here touches the
-// key's per-proof workspace.
+// key's per-proof workspace. The key is read through a view (vk.hpp) that a proving key or a verifying key fills:
+// amdzk_verify_proofs_vk and amdzk_verify_proofs_decide_vk are the same code over the same operands.
 #include <string.h>
 
 #include <string>
@@ -11,6 +12,7 @@
 #include "common.hpp"
 #include "pk.hpp"
 #include "verifier.hpp"
+#include "vk.hpp"
 
 using namespace bn254;
 
@@ -103,26 +105,27 @@ __global__ __launch_bounds__(DECODE_THREADS) void proof_decode_kernel(DecodeArgs
 
 size_t pad256(size_t v) { return (v + 255) / 256 * 256; }
 
-// What amdzk_verify_proofs and amdzk_verify_proofs_decide share: everything up to the G1 sums. `who` prefixes the refusals.
+// What amdzk_verify_proofs, amdzk_verify_proofs_decide and their _vk forms share: everything up to the G1 sums, over a view
+// of the key (vk.hpp; key == nullptr: the caller passed no key). `who` prefixes the refusals.
 // pairs == nullptr: the batch's ONE pair, sum_b rho_b (L_b, R_b), in pair_out — amdzk_verify_proofs as documented.
 // pairs != nullptr: every proof by itself with weight 1 — (L_b, R_b) in (*pairs)[2b], [2b + 1], identities for a malformed
 // proof; opts->combine_* are not read and pair_out is not written. The MSMs run over AMDZK_DECIDE_RUN proofs at a time.
-int verify_core(amdzk_ctx* ctx, const char* who, const amdzk_pk* pk, size_t n_proofs, const uint64_t* const* const* instances,
+int verify_core(amdzk_ctx* ctx, const char* who, const zk_key_view* key, size_t n_proofs, const uint64_t* const* const* instances,
                 const size_t* const* instance_lens, const uint8_t* const* proofs, const size_t* proof_lens, const amdzk_verify_opts* opts,
                 amdzk_proof_status* statuses, uint64_t* pair_out, std::vector<G1Affine>* pairs) {
   const bool per_proof = pairs != nullptr;
-  if (!pk || !proofs || !proof_lens || !statuses || (!per_proof && !pair_out)) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: null argument", who);
+  if (!key || !proofs || !proof_lens || !statuses || (!per_proof && !pair_out)) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: null argument", who);
   if (n_proofs == 0) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: n_proofs is 0", who);
   if (n_proofs > (1u << 20)) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: more than 2^20 proofs in one call", who);
   if (opts && opts->size < sizeof(amdzk_verify_opts))
     ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: amdzk_verify_opts.size is %zu, this library needs %zu", who, opts->size, sizeof(amdzk_verify_opts));
-  if (!pk->src_desc || !pk->srs) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: the key has no circuit description", who);
+  if (!key->desc) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: the key has no circuit description", who);
   const int kind = opts ? opts->transcript_kind : 0;
   const uint32_t N = opts && opts->n_circuits ? opts->n_circuits : 1;
   verifier::Plan plan;
   {
     std::string why;
-    if (verifier::make_plan(*pk->src_desc, N, kind, &plan, &why) != AMDZK_OK) {
+    if (verifier::make_plan(*key->desc, N, kind, &plan, &why) != AMDZK_OK) {
       const std::string own = "verify_proofs: ";  // verifier.hpp's prefix
       ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: %s", who, why.compare(0, own.size(), own) == 0 ? why.c_str() + own.size() : why.c_str());
     }
@@ -132,7 +135,7 @@ int verify_core(amdzk_ctx* ctx, const char* who, const amdzk_pk* pk, size_t n_pr
     if (!instances[i] || !instance_lens[i]) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: null argument (instances of circuit %zu)", who, i);
   for (size_t b = 0; b < n_proofs; b++)
     if (!proofs[b]) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: null argument (proof %zu)", who, b);
-  if (plan.proof_bytes != amdzk_proof_size_multi(pk, N, kind) || plan.proof_bytes >= ((size_t)1 << 30))
+  if ((key->sized_by && plan.proof_bytes != amdzk_proof_size_multi(key->sized_by, N, kind)) || plan.proof_bytes >= ((size_t)1 << 30))
     ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "%s: proof layout of %zu bytes disagrees with amdzk_proof_size_multi or is too large", who, plan.proof_bytes);
   std::vector<Fr> rho(n_proofs, Fr::one());
   if (per_proof) {
@@ -170,7 +173,7 @@ int verify_core(amdzk_ctx* ctx, const char* who, const amdzk_pk* pk, size_t n_pr
   const size_t run = n_proofs < AMDZK_DECIDE_RUN ? n_proofs : AMDZK_DECIDE_RUN, run_len = nvk + 1 + run * NP;
   const size_t o_msm = pad256(o_dsc + n_proofs * NS * 32), o_rb = pad256(o_msm + 2 * run * run_len * 32);
   const size_t total = per_proof ? o_rb + run_len * sizeof(G1Affine) : o_msm + 2 * nbases * 32;
-  const size_t up_bytes = o_g, down_bytes = o_msm - o_status;
+  const size_t up_bytes = key->h_g ? o_points : o_g, down_bytes = o_msm - o_status;  // a verifying key's G goes up with its commitments
   char* ws = nullptr;
   ZK_TRY(zk_ws_reserve(ctx, VERIFY_WS_SLOT, total, (void**)&ws));
   char* pin = nullptr;
@@ -182,12 +185,12 @@ int verify_core(amdzk_ctx* ctx, const char* who, const amdzk_pk* pk, size_t n_pr
     ((uint32_t*)(pin + o_status))[b] = STATUS_CLEAN;
   }
   for (size_t e = 0; e < E; e++) ((uint2*)(pin + o_elems))[e] = make_uint2(plan.elems[e].offset, (plan.elems[e].is_point << 31) | plan.elems[e].index);
-  if (plan.F) memcpy(pin + o_vk, pk->fixed_commitments.data(), (size_t)plan.F * sizeof(G1Affine));
-  if (plan.S) memcpy(pin + o_vk + (size_t)plan.F * sizeof(G1Affine), pk->perm_commitments.data(), (size_t)plan.S * sizeof(G1Affine));
-  const G1Affine* d_g = zk_srs_base_dev(pk->srs, AMDZK_BASIS_G);
-  if (!d_g) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: the key's SRS has no monomial basis", who);
+  if (plan.F) memcpy(pin + o_vk, key->fixed_commitments, (size_t)plan.F * sizeof(G1Affine));
+  if (plan.S) memcpy(pin + o_vk + (size_t)plan.F * sizeof(G1Affine), key->perm_commitments, (size_t)plan.S * sizeof(G1Affine));
+  if (!key->d_g && !key->h_g) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: the key's SRS has no monomial basis", who);
+  if (key->h_g) memcpy(pin + o_g, key->h_g, sizeof(G1Affine));
   ZK_HIP(ctx, hipMemcpyAsync(ws, pin, up_bytes, hipMemcpyHostToDevice, ctx->stream));
-  ZK_HIP(ctx, hipMemcpyAsync(ws + o_g, d_g, sizeof(G1Affine), hipMemcpyDeviceToDevice, ctx->stream));
+  if (key->d_g) ZK_HIP(ctx, hipMemcpyAsync(ws + o_g, key->d_g, sizeof(G1Affine), hipMemcpyDeviceToDevice, ctx->stream));
   DecodeArgs da;
   da.staging = (const uint8_t*)ws, da.stride = psize, da.elems = (const uint2*)(ws + o_elems);
   da.E = (uint32_t)E, da.NP = (uint32_t)NP, da.NS = (uint32_t)NS, da.total = n_proofs * E;
@@ -212,7 +215,7 @@ int verify_core(amdzk_ctx* ctx, const char* who, const amdzk_pk* pk, size_t n_pr
       continue;
     }
     live++;
-    verifier::fold_proof(plan, pk->transcript_repr, pk->omega, plan.I ? instances + b * N : nullptr, plan.I ? instance_lens + b * N : nullptr,
+    verifier::fold_proof(plan, *key->transcript_repr, *key->omega, plan.I ? instances + b * N : nullptr, plan.I ? instance_lens + b * N : nullptr,
                          h_points + b * NP, h_scalars + b * NS, rho[b], Lb.data(), Rb.data());
     if (per_proof) {
       own.insert(own.end(), Lb.begin(), Lb.end());
@@ -279,32 +282,38 @@ int verify_core(amdzk_ctx* ctx, const char* who, const amdzk_pk* pk, size_t n_pr
   return AMDZK_OK;
 }
 
-}  // namespace
-
-extern "C" int amdzk_verify_proofs(amdzk_ctx* ctx, const amdzk_pk* pk, size_t n_proofs, const uint64_t* const* const* instances,
-                                   const size_t* const* instance_lens, const uint8_t* const* proofs, const size_t* proof_lens,
-                                   const amdzk_verify_opts* opts, amdzk_proof_status* statuses, uint64_t pair_out[16]) {
-  ZK_ENTER(ctx);
-  if (!ctx) return AMDZK_E_INVALID;
-  if (!pair_out) ZK_FAIL(ctx, AMDZK_E_INVALID, "verify_proofs: null argument");
-  return verify_core(ctx, "verify_proofs", pk, n_proofs, instances, instance_lens, proofs, proof_lens, opts, statuses, pair_out, nullptr);
+// The view of a proving key: G stays where the key's SRS keeps it. A key without a description or an SRS gives a view
+// without a description, which verify_core refuses.
+zk_key_view view_of(const amdzk_pk* pk) {
+  zk_key_view v;
+  if (pk->src_desc && pk->srs) v.desc = pk->src_desc.get();
+  v.transcript_repr = &pk->transcript_repr, v.omega = &pk->omega;
+  v.fixed_commitments = pk->fixed_commitments.data(), v.perm_commitments = pk->perm_commitments.data();
+  v.d_g = zk_srs_base_dev(pk->srs, AMDZK_BASIS_G);
+  v.sized_by = pk;
+  return v;
+}
+// ... and of a verifying key, which holds G itself
+zk_key_view view_of(const amdzk_vk* vk) {
+  zk_key_view v;
+  v.desc = vk->desc.get();
+  v.transcript_repr = &vk->transcript_repr, v.omega = &vk->omega;
+  v.fixed_commitments = vk->fixed_commitments.data(), v.perm_commitments = vk->perm_commitments.data();
+  v.h_g = &vk->g;
+  return v;
 }
 
-// amdzk_verify_proofs and the pairing behind it (include/amdzk.h): per proof (flags = 0) one launch of n_live checks with
-// m = 2, P = (L_b, -R_b) over (s_g2, g2); combined, one check of the batch's pair.
-extern "C" int amdzk_verify_proofs_decide(amdzk_ctx* ctx, const amdzk_pk* pk, const amdzk_g2* s_g2, const amdzk_g2* g2, uint32_t flags,
-                                          size_t n_proofs, const uint64_t* const* const* instances, const size_t* const* instance_lens,
-                                          const uint8_t* const* proofs, const size_t* proof_lens, const amdzk_verify_opts* opts,
-                                          amdzk_proof_status* statuses, uint8_t* verdicts, size_t* n_valid) {
-  ZK_ENTER(ctx);
-  if (!ctx) return AMDZK_E_INVALID;
-  const char* who = "verify_proofs_decide";
+// amdzk_verify_proofs_decide over a view: verify_core and the pairing(s) behind it — per proof (flags = 0) one launch of
+// n_live checks with m = 2, P = (L_b, -R_b) over (s_g2, g2); combined, one check of the batch's pair.
+int decide_core(amdzk_ctx* ctx, const char* who, const zk_key_view* key, const amdzk_g2* s_g2, const amdzk_g2* g2, uint32_t flags, size_t n_proofs,
+                const uint64_t* const* const* instances, const size_t* const* instance_lens, const uint8_t* const* proofs, const size_t* proof_lens,
+                const amdzk_verify_opts* opts, amdzk_proof_status* statuses, uint8_t* verdicts, size_t* n_valid) {
   if (!s_g2 || !g2 || !verdicts) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: null argument", who);
   if (flags & ~AMDZK_DECIDE_COMBINED) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: unknown flags 0x%x", who, flags);
   const bool combined = (flags & AMDZK_DECIDE_COMBINED) != 0;
   std::vector<G1Affine> pairs;
   uint64_t pair[16];
-  ZK_TRY(verify_core(ctx, who, pk, n_proofs, instances, instance_lens, proofs, proof_lens, opts, statuses, pair, combined ? nullptr : &pairs));
+  ZK_TRY(verify_core(ctx, who, key, n_proofs, instances, instance_lens, proofs, proof_lens, opts, statuses, pair, combined ? nullptr : &pairs));
   if (combined) {
     pairs.resize(2);
     memcpy(&pairs[0], pair, 64);
@@ -332,4 +341,52 @@ extern "C" int amdzk_verify_proofs_decide(amdzk_ctx* ctx, const amdzk_pk* pk, co
   }
   if (n_valid) *n_valid = valid;
   return AMDZK_OK;
+}
+
+}  // namespace
+
+extern "C" int amdzk_verify_proofs(amdzk_ctx* ctx, const amdzk_pk* pk, size_t n_proofs, const uint64_t* const* const* instances,
+                                   const size_t* const* instance_lens, const uint8_t* const* proofs, const size_t* proof_lens,
+                                   const amdzk_verify_opts* opts, amdzk_proof_status* statuses, uint64_t pair_out[16]) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  if (!pair_out) ZK_FAIL(ctx, AMDZK_E_INVALID, "verify_proofs: null argument");
+  zk_key_view key;
+  if (pk) key = view_of(pk);
+  return verify_core(ctx, "verify_proofs", pk ? &key : nullptr, n_proofs, instances, instance_lens, proofs, proof_lens, opts, statuses, pair_out, nullptr);
+}
+
+extern "C" int amdzk_verify_proofs_vk(amdzk_ctx* ctx, const amdzk_vk* vk, size_t n_proofs, const uint64_t* const* const* instances,
+                                      const size_t* const* instance_lens, const uint8_t* const* proofs, const size_t* proof_lens,
+                                      const amdzk_verify_opts* opts, amdzk_proof_status* statuses, uint64_t pair_out[16]) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  if (!pair_out) ZK_FAIL(ctx, AMDZK_E_INVALID, "verify_proofs: null argument");
+  zk_key_view key;
+  if (vk) key = view_of(vk);
+  return verify_core(ctx, "verify_proofs", vk ? &key : nullptr, n_proofs, instances, instance_lens, proofs, proof_lens, opts, statuses, pair_out, nullptr);
+}
+
+extern "C" int amdzk_verify_proofs_decide(amdzk_ctx* ctx, const amdzk_pk* pk, const amdzk_g2* s_g2, const amdzk_g2* g2, uint32_t flags,
+                                          size_t n_proofs, const uint64_t* const* const* instances, const size_t* const* instance_lens,
+                                          const uint8_t* const* proofs, const size_t* proof_lens, const amdzk_verify_opts* opts,
+                                          amdzk_proof_status* statuses, uint8_t* verdicts, size_t* n_valid) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  zk_key_view key;
+  if (pk) key = view_of(pk);
+  return decide_core(ctx, "verify_proofs_decide", pk ? &key : nullptr, s_g2, g2, flags, n_proofs, instances, instance_lens, proofs, proof_lens, opts,
+                     statuses, verdicts, n_valid);
+}
+
+extern "C" int amdzk_verify_proofs_decide_vk(amdzk_ctx* ctx, const amdzk_vk* vk, const amdzk_g2* s_g2, const amdzk_g2* g2, uint32_t flags,
+                                             size_t n_proofs, const uint64_t* const* const* instances, const size_t* const* instance_lens,
+                                             const uint8_t* const* proofs, const size_t* proof_lens, const amdzk_verify_opts* opts,
+                                             amdzk_proof_status* statuses, uint8_t* verdicts, size_t* n_valid) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  zk_key_view key;
+  if (vk) key = view_of(vk);
+  return decide_core(ctx, "verify_proofs_decide", vk ? &key : nullptr, s_g2, g2, flags, n_proofs, instances, instance_lens, proofs, proof_lens, opts,
+                     statuses, verdicts, n_valid);
 }

@@ -1,0 +1,183 @@
+// A verifying key's life (include/amdzk.h "verifying keys"): plonk::keygen_vk [UP] without a proving key,
+// ProvingKey::get_vk [UP], the key file (vkblob.hpp has its layout and every check of its reader) and the release.
+// amdzk_keygen_vk runs keygen's own steps (keygen.hip, declared in pk.hpp) on a scratch key that holds the description and
+// the F + S Lagrange columns and is gone when the call returns: no coset, no program, no per-proof workspace. No kernel
+// lives here; verifying with the key is verify.hip's.
+#include <string.h>
+
+#include <memory>
+#include <string>
+
+#include "pk.hpp"
+#include "verifier.hpp"
+#include "vk.hpp"
+
+using namespace bn254;
+
+namespace {
+
+// The verifier's host half (verifier.hpp) indexes by the description's queries and expression words without checking
+// them: a description reaches an amdzk_vk only through pkblob::validate — here, and in the file's reader. Keygen takes
+// some circuits on trust that validate() does not (a query no expression uses may name any column): such a proving key
+// proves, but has no verifying key.
+int refuse_unvalidated(amdzk_ctx* ctx, const char* prefix, const pkblob::Desc& d) {
+  std::string why;
+  if (pkblob::validate(d, &why) == AMDZK_OK) return AMDZK_OK;
+  const std::string own = "pk_read: ";
+  ZK_FAIL(ctx, AMDZK_E_INVALID, "%s%s", prefix, why.compare(0, own.size(), own) == 0 ? why.c_str() + own.size() : why.c_str());
+}
+
+// amdzk_vk_from_pk's body: also how amdzk_keygen_vk takes the key out of its scratch key
+int vk_of(amdzk_ctx* ctx, const char* who, const amdzk_pk* pk, amdzk_vk** out) {
+  if (!pk->src_desc || !pk->srs) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: the key has no circuit description", who);
+  ZK_TRY(refuse_unvalidated(ctx, (std::string(who) + ": the key's circuit is not one a verifier can read: ").c_str(), *pk->src_desc));
+  const G1Affine* d_g = zk_srs_base_dev(pk->srs, AMDZK_BASIS_G);
+  if (!d_g) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: the key's SRS has no monomial basis", who);
+  std::unique_ptr<amdzk_vk> vk(new amdzk_vk());
+  vk->desc = pk->src_desc;
+  vk->transcript_repr = pk->transcript_repr, vk->omega = pk->omega;
+  vk->fixed_commitments = pk->fixed_commitments, vk->perm_commitments = pk->perm_commitments;
+  ZK_TRY(d2h(ctx, &vk->g, d_g, sizeof(G1Affine)));
+  *out = vk.release();
+  return AMDZK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int amdzk_keygen_vk(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* c, const amdzk_phases* ph, const uint64_t* fixed_values,
+                    const uint32_t* perm_mapping, const uint64_t* sigma_values, const uint64_t transcript_repr[4], amdzk_vk** out) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  uint32_t nphases = 1;
+  amdzk_pk* unused = nullptr;
+  ZK_TRY(check_keygen_args(ctx, srs, c, ph, transcript_repr, 0, out ? &unused : nullptr, &nphases));
+  if (c->num_perm_columns && (perm_mapping != nullptr) == (sigma_values != nullptr))
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen_vk: exactly one of perm_mapping and sigma_values feeds the permutation columns, %s given",
+            perm_mapping ? "both" : "neither");
+  if (!zk_srs_has_basis(srs, AMDZK_BASIS_G) || !zk_srs_has_basis(srs, AMDZK_BASIS_G_LAGRANGE))
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen_vk: the parameters need both bases, g (AMDZK_BASIS_G) and g_lagrange (AMDZK_BASIS_G_LAGRANGE)");
+  if (c->k != zk_srs_k(srs)) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen_vk: the circuit is for k = %u, the parameters are for k = %u", c->k, zk_srs_k(srs));
+  // the scratch key: freed on every way out, with its two columns and its domain (amdzk_pk_free waits for the stream first)
+  auto drop = [ctx](amdzk_pk* pk) { amdzk_pk_free(ctx, pk); };
+  std::unique_ptr<amdzk_pk, decltype(drop)> owner(new amdzk_pk(), drop);
+  amdzk_pk* pk = owner.get();
+  ZK_TRY(describe_circuit(ctx, pk, srs, c, ph, nphases, transcript_repr, 0, true));
+  // what keygen's expression compiler refuses ("circuit: ..."), refused here without compiling: before anything goes up
+  ZK_TRY(refuse_unvalidated(ctx, "circuit: ", *pk->src_desc));
+  ZK_TRY(dalloc(ctx, pk, &pk->fixed_lag, (size_t)pk->F * pk->n));
+  ZK_TRY(dalloc(ctx, pk, &pk->sigma_lag, (size_t)pk->S * pk->n));
+  ZK_TRY(load_fixed_columns(ctx, pk, fixed_values, true));
+  ZK_TRY(load_sigma_columns(ctx, pk, perm_mapping, sigma_values, sigma_values != nullptr, true));
+  return vk_of(ctx, "keygen_vk", pk, out);
+}
+
+int amdzk_vk_from_pk(amdzk_ctx* ctx, const amdzk_pk* pk, amdzk_vk** out) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  if (!pk || !out) ZK_FAIL(ctx, AMDZK_E_INVALID, "vk_from_pk: null argument");
+  return vk_of(ctx, "vk_from_pk", pk, out);
+}
+
+void amdzk_vk_free(amdzk_ctx*, amdzk_vk* vk) { delete vk; }
+
+int amdzk_vk_commitments(const amdzk_vk* vk, uint64_t* fixed_out /* F x 8 */, uint64_t* perm_out /* S x 8 */) {
+  if (!vk) return AMDZK_E_INVALID;
+  if (fixed_out && !vk->fixed_commitments.empty()) memcpy(fixed_out, vk->fixed_commitments.data(), vk->fixed_commitments.size() * 64);
+  if (perm_out && !vk->perm_commitments.empty()) memcpy(perm_out, vk->perm_commitments.data(), vk->perm_commitments.size() * 64);
+  return AMDZK_OK;
+}
+
+// The length the verifier's own plan of the proof has (verifier.hpp) — which amdzk_verify_proofs holds
+// amdzk_proof_size_multi to on every call.
+size_t amdzk_vk_proof_size_multi(const amdzk_vk* vk, size_t n_circuits, int transcript_kind) {
+  if (!vk || !vk->desc || n_circuits == 0 || n_circuits > 0xffffffffu) return 0;
+  verifier::Plan plan;
+  std::string why;
+  return verifier::make_plan(*vk->desc, (uint32_t)n_circuits, transcript_kind, &plan, &why) == AMDZK_OK ? plan.proof_bytes : 0;
+}
+
+// ---- the key file. As for the proving key's: a circuit that pkblob::validate() refuses is not written at all.
+size_t amdzk_vk_serialized_size(const amdzk_vk* vk, int with_g2) {
+  return vk && vk->desc && pkblob::validate(*vk->desc, nullptr) == AMDZK_OK ? vkblob::serialized_size(*vk->desc, with_g2 != 0) : 0;
+}
+
+int amdzk_vk_write(amdzk_ctx* ctx, const amdzk_vk* vk, const uint64_t g2[16], const uint64_t s_g2[16], uint8_t* out, size_t cap, size_t* written) {
+  if (!ctx) return AMDZK_E_INVALID;
+  if (!vk || !vk->desc || (!out && !written)) ZK_FAIL(ctx, AMDZK_E_INVALID, "vk_write: null argument");
+  if ((g2 == nullptr) != (s_g2 == nullptr)) ZK_FAIL(ctx, AMDZK_E_INVALID, "vk_write: g2 and s_g2 go together, one of them is null");
+  const pkblob::Desc& d = *vk->desc;
+  std::string why;
+  if (pkblob::validate(d, &why) != AMDZK_OK) ZK_FAIL(ctx, AMDZK_E_INVALID, "vk_write: amdzk_vk_read would refuse this key's circuit (%s)", why.c_str());
+  const vkblob::Layout L = vkblob::layout(d, g2 != nullptr);
+  if (written) *written = L.total;
+  if (!out) return AMDZK_OK;
+  if (cap < L.total) ZK_FAIL(ctx, AMDZK_E_INVALID, "vk_write: buffer holds %zu bytes, %zu needed", cap, L.total);
+  vkblob::write_frame(d, L, out);
+  memcpy(out + L.transcript_repr, vk->transcript_repr.l, 32);
+  if (d.num_fixed) memcpy(out + L.fixed_commitments, vk->fixed_commitments.data(), (size_t)d.num_fixed * 64);
+  if (d.num_perm_columns()) memcpy(out + L.perm_commitments, vk->perm_commitments.data(), (size_t)d.num_perm_columns() * 64);
+  memcpy(out + L.g, &vk->g, 64);
+  if (g2) memcpy(out + L.g2, g2, 128), memcpy(out + L.s_g2, s_g2, 128);
+  vkblob::seal(L, out);
+  // what is written must read back: the caller's G2 pair and the SRS's g[0] have not come through a check yet
+  pkblob::Desc back;
+  if (vkblob::parse(out, L.total, &back, nullptr, &why) != AMDZK_OK) {
+    const std::string own = "vk_read: ";
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "vk_write: %s", why.compare(0, own.size(), own) == 0 ? why.c_str() + own.size() : why.c_str());
+  }
+  return AMDZK_OK;
+}
+
+// Pure host code: every check amdzk_vk_read makes.
+int amdzk_vk_blob_info(const uint8_t* data, size_t len, uint32_t* k, uint32_t* num_fixed, uint32_t* num_advice, uint32_t* num_perm_columns,
+                       uint32_t* num_challenges, int* has_g2) {
+  pkblob::Desc d;
+  vkblob::Layout L;
+  if (int rc = vkblob::parse(data, len, &d, &L, nullptr)) return rc;
+  if (k) *k = d.k;
+  if (num_fixed) *num_fixed = d.num_fixed;
+  if (num_advice) *num_advice = d.num_advice;
+  if (num_perm_columns) *num_perm_columns = d.num_perm_columns();
+  if (num_challenges) *num_challenges = d.num_challenges;
+  if (has_g2) *has_g2 = L.with_g2 ? 1 : 0;
+  return AMDZK_OK;
+}
+
+int amdzk_vk_blob_check(const uint8_t* data, size_t len, char* msg, size_t msg_cap) {
+  pkblob::Desc d;
+  std::string err;
+  const int rc = vkblob::parse(data, len, &d, nullptr, &err);
+  if (msg && msg_cap) snprintf(msg, msg_cap, "%s", err.c_str());
+  return rc;
+}
+
+// Host work only: the ctx receives the refusal's message.
+int amdzk_vk_read(amdzk_ctx* ctx, const uint8_t* data, size_t len, amdzk_vk** out, uint64_t g2_out[16], uint64_t s_g2_out[16], int* has_g2) {
+  if (!ctx) return AMDZK_E_INVALID;
+  if (!data || !out) ZK_FAIL(ctx, AMDZK_E_INVALID, "vk_read: null argument");
+  auto desc = std::make_shared<pkblob::Desc>();
+  vkblob::Layout L;
+  std::string err;
+  if (int rc = vkblob::parse(data, len, desc.get(), &L, &err)) {
+    ctx->err = err;
+    return rc;
+  }
+  std::unique_ptr<amdzk_vk> vk(new amdzk_vk());
+  vk->omega = zkhost::fr_omega(desc->k);  // EvaluationDomain's omega: a few host squarings, no domain and no device call
+  memcpy(vk->transcript_repr.l, data + L.transcript_repr, 32);
+  vk->fixed_commitments.resize(desc->num_fixed);
+  vk->perm_commitments.resize(desc->num_perm_columns());
+  if (desc->num_fixed) memcpy(vk->fixed_commitments.data(), data + L.fixed_commitments, (size_t)desc->num_fixed * 64);
+  if (desc->num_perm_columns()) memcpy(vk->perm_commitments.data(), data + L.perm_commitments, (size_t)desc->num_perm_columns() * 64);
+  memcpy(&vk->g, data + L.g, 64);
+  if (has_g2) *has_g2 = L.with_g2 ? 1 : 0;
+  if (L.with_g2 && g2_out) memcpy(g2_out, data + L.g2, 128);
+  if (L.with_g2 && s_g2_out) memcpy(s_g2_out, data + L.s_g2, 128);
+  vk->desc = desc;
+  *out = vk.release();
+  return AMDZK_OK;
+}
+
+}  // extern "C"

@@ -127,6 +127,19 @@ def lib():
         "amdzk_pairing_products": (i32, [vp, C.POINTER(vp), sz, vp, sz, vp, vp]),
         "amdzk_verify_proofs_decide": (i32, [vp, vp, vp, vp, u32, sz, C.POINTER(C.POINTER(vp)), C.POINTER(C.POINTER(sz)), C.POINTER(vp), C.POINTER(sz),
                                              vp, vp, vp, C.POINTER(sz)]),
+        "amdzk_keygen_vk": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]),
+        "amdzk_vk_from_pk": (i32, [vp, vp, C.POINTER(vp)]),
+        "amdzk_vk_free": (None, [vp, vp]),
+        "amdzk_vk_commitments": (i32, [vp, vp, vp]),
+        "amdzk_vk_proof_size_multi": (sz, [vp, sz, i32]),
+        "amdzk_vk_serialized_size": (sz, [vp, i32]),
+        "amdzk_vk_write": (i32, [vp, vp, vp, vp, vp, sz, C.POINTER(sz)]),
+        "amdzk_vk_read": (i32, [vp, vp, sz, C.POINTER(vp), vp, vp, C.POINTER(i32)]),
+        "amdzk_vk_blob_info": (i32, [vp, sz, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(i32)]),
+        "amdzk_vk_blob_check": (i32, [vp, sz, vp, sz]),
+        "amdzk_verify_proofs_vk": (i32, [vp, vp, sz, C.POINTER(C.POINTER(vp)), C.POINTER(C.POINTER(sz)), C.POINTER(vp), C.POINTER(sz), vp, vp, vp]),
+        "amdzk_verify_proofs_decide_vk": (i32, [vp, vp, vp, vp, u32, sz, C.POINTER(C.POINTER(vp)), C.POINTER(C.POINTER(sz)), C.POINTER(vp),
+                                                C.POINTER(sz), vp, vp, vp, C.POINTER(sz)]),
         "amdzk_debug_limb_program": (i32, [vp, sz, vp, sz, C.POINTER(sz), C.POINTER(u32)]),
         "amdzk_pk_h_program": (i32, [vp, vp, sz, C.POINTER(sz)]),
         "amdzk_timer_start": (i32, [vp]),

@@ -146,10 +146,12 @@ def pairing_products(ctx, qs, g1, want_gt=True):
 
 
 class ParamsVerifierKZG:
-    """The verifier's part of ParamsKZG: the prepared [1]_2 and [s]_2 ((16,) uint64 points, e.g. from g2_setup)."""
+    """The verifier's part of ParamsKZG: the prepared [1]_2 and [s]_2 ((16,) uint64 points, e.g. from g2_setup or from a
+    verifying-key file, plonk.VerifyingKey.read). `points` keeps the two as given, for VerifyingKey.write."""
 
     def __init__(self, ctx, g2, s_g2):
         self.ctx = ctx
+        self.points = tuple(np.array(p, dtype=np.uint64).reshape(16) for p in (g2, s_g2))
         self.g2 = G2Prepared(ctx, g2)
         try:
             self.s_g2 = G2Prepared(ctx, s_g2)

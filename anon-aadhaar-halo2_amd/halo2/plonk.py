@@ -530,10 +530,80 @@ class ProvingKey:
                                                          out.ctypes.data if out.size else None, None, None))
         return out
 
+    def get_vk(self):
+        """ProvingKey::get_vk (amdzk_vk_from_pk): the key's VerifyingKey, which outlives this key and its params."""
+        h = C.c_void_p()
+        self.ctx._chk(self.ctx.L.amdzk_vk_from_pk(self.ctx.h, self.h, C.byref(h)))
+        return VerifyingKey(self.ctx, h, self.desc)
+
     def free(self):
         if self.h:
             self.ctx.L.amdzk_pk_free(self.ctx.h, self.h)
             self.h = None
+
+
+class VerifyingKey:
+    """plonk::VerifyingKey with the G of its params (amdzk_vk): all verify_proofs / decide_proofs read of a key. Host data
+    only; it refers to no ParamsKZG and no ProvingKey. Made by keygen_vk, ProvingKey.get_vk or VerifyingKey.read."""
+
+    def __init__(self, ctx, h, desc):
+        self.ctx, self.h, self.desc = ctx, h, desc
+
+    def commitments(self):
+        """(fixed_commitments, permutation_commitments) as (m, 8) uint64 affine points."""
+        f = np.zeros((self.desc["num_fixed"], 8), np.uint64)
+        p = np.zeros((len(self.desc["permutation_columns"]), 8), np.uint64)
+        self.ctx._chk(self.ctx.L.amdzk_vk_commitments(self.h, f.ctypes.data if f.size else None, p.ctypes.data if p.size else None))
+        return f, p
+
+    def write(self, vparams=None):
+        """amdzk_vk_write: the key file (include/amdzk.h has the layout) as bytes; with vparams (kzg.ParamsVerifierKZG) the
+        file carries [1]_2 and [s]_2 too, and is then all a verifier process needs."""
+        g2, s_g2 = (None, None) if vparams is None else vparams.points
+        size = int(self.ctx.L.amdzk_vk_serialized_size(self.h, 0 if vparams is None else 1))
+        out = np.zeros(max(1, size), np.uint8)
+        written = C.c_size_t(0)
+        self.ctx._chk(self.ctx.L.amdzk_vk_write(self.ctx.h, self.h, None if g2 is None else g2.ctypes.data, None if s_g2 is None else s_g2.ctypes.data,
+                                                out.ctypes.data, size, C.byref(written)))
+        assert written.value == size
+        return out[:size].tobytes()
+
+    @classmethod
+    def read(cls, ctx, data):
+        """amdzk_vk_read: (vk, g2, s_g2) of a file made by write(); g2 / s_g2 are (16,) uint64 or None when the file has no
+        pair. Needs no params. `desc` is rebuilt from the file."""
+        buf = None if data is None else np.frombuffer(data, dtype=np.uint8)
+        h, has = C.c_void_p(), C.c_int(0)
+        g2, s_g2 = np.zeros(16, np.uint64), np.zeros(16, np.uint64)
+        ctx._chk(ctx.L.amdzk_vk_read(ctx.h, buf.ctypes.data if buf is not None and buf.size else None, buf.size if buf is not None else 0, C.byref(h),
+                                     g2.ctypes.data, s_g2.ctypes.data, C.byref(has)))
+        return cls(ctx, h, blob_desc(data)), (g2 if has.value else None), (s_g2 if has.value else None)
+
+    def free(self):
+        if self.h:
+            self.ctx.L.amdzk_vk_free(self.ctx.h, self.h)
+            self.h = None
+
+
+def keygen_vk(ctx, params, desc, fixed_values, mapping=None, sigma_values=None, transcript_repr=None, phases=None):
+    """plonk::keygen_vk (amdzk_keygen_vk): the VerifyingKey alone, from Assembly.mapping or from the sigma columns (exactly
+    one of the two when the circuit has permutation columns), without making a proving key: the device holds the fixed and
+    sigma columns while the call runs and nothing afterwards. The key ProvingKey(...).get_vk() gives for the same inputs."""
+    if transcript_repr is None:
+        raise ValueError("keygen_vk: transcript_repr is required ((4,) uint64 Montgomery Fr, as for ProvingKey)")
+    n = 1 << desc["k"]
+    cc, keep = flatten_circuit(desc)
+    fv = np.ascontiguousarray(fixed_values, dtype=np.uint64).reshape(desc["num_fixed"], n, 4) if desc["num_fixed"] else np.zeros((0, n, 4), np.uint64)
+    mp = None if mapping is None else np.ascontiguousarray(np.array(mapping, dtype=np.uint32).reshape(-1, n, 2))
+    sg = None if sigma_values is None else np.ascontiguousarray(sigma_values, dtype=np.uint64).reshape(-1, n, 4)
+    tr = np.ascontiguousarray(transcript_repr, dtype=np.uint64).reshape(4)
+    ph, keep_ph = flatten_phases(desc) if phases is None else (phases, None)
+    h = C.c_void_p()
+    ctx._chk(ctx.L.amdzk_keygen_vk(ctx.h, params.h, C.byref(cc), C.byref(ph) if ph is not None else None, fv.ctypes.data if fv.size else None,
+                                   mp.ctypes.data if mp is not None and mp.size else None, sg.ctypes.data if sg is not None and sg.size else None,
+                                   tr.ctypes.data, C.byref(h)))
+    del keep, keep_ph
+    return VerifyingKey(ctx, h, desc)
 
 
 KEYGEN_FULL_COSETS, KEYGEN_SERIAL = 1, 2  # include/amdzk.h AMDZK_KEYGEN_*
@@ -556,9 +626,26 @@ def blob_info(data):
     return dict(zip(("k", "num_fixed", "num_advice", "num_perm_columns", "num_challenges"), (o.value for o in out)))
 
 
+def vk_blob_info(data):
+    """amdzk_vk_blob_info: the shape of a verifying-key file and whether it carries the G2 pair — pure host code, no device
+    needed, every check VerifyingKey.read makes; AmdzkError with amdzk_vk_blob_check's reason ("vk_read: ...") for a file it
+    refuses."""
+    buf = np.frombuffer(data, dtype=np.uint8) if data is not None else None
+    ptr, size = (buf.ctypes.data, buf.size) if buf is not None and buf.size else (None, 0)
+    out, has = [C.c_uint32(0) for _ in range(5)], C.c_int(0)
+    rc = _ffi.lib().amdzk_vk_blob_info(ptr, size, *[C.byref(o) for o in out], C.byref(has))
+    if rc != 0:
+        msg = C.create_string_buffer(256)
+        _ffi.lib().amdzk_vk_blob_check(ptr, size, msg, len(msg))
+        raise _ffi.AmdzkError(rc, msg.value.decode())
+    info = dict(zip(("k", "num_fixed", "num_advice", "num_perm_columns", "num_challenges"), (o.value for o in out)))
+    info["has_g2"] = bool(has.value)
+    return info
+
+
 def blob_desc(data):
     """The describe() dict in a key file's header (what flatten_circuit / flatten_phases had flattened), for a file
-    blob_info / ProvingKey.read accepted."""
+    blob_info / ProvingKey.read accepted — or vk_blob_info / VerifyingKey.read: the two files share these sections."""
     mv, pos = memoryview(data), [12]  # behind the magic and the format version
 
     def arr(count, dtype=np.uint32):
@@ -874,7 +961,8 @@ def _verify_args(instances_list, proofs, transcript, n_circuits, combine_seed, c
 
 def verify_proofs(ctx, pk, instances_list, proofs, transcript=TRANSCRIPT_BLAKE2B, n_circuits=1, combine_seed=0, combine_scalars=None,
                   opts_size=None):
-    """amdzk_verify_proofs: plonk::verify_proof for a batch up to the one pairing. proofs[b]: bytes; instances_list[b]: proof
+    """amdzk_verify_proofs (amdzk_verify_proofs_vk when pk is a VerifyingKey): plonk::verify_proof for a batch up to the one
+    pairing. proofs[b]: bytes; instances_list[b]: proof
     b's instance columns as for create_proof — or, with n_circuits > 1, a list of n_circuits such lists (create_proof_multi).
     combine_scalars: (len(proofs), 4) uint64 Montgomery weights of the caller's; else they are drawn from combine_seed, which
     must then be unpredictable to whoever made the proofs (a single proof has weight 1). Returns a Guard; a refused call raises.
@@ -882,7 +970,8 @@ def verify_proofs(ctx, pk, instances_list, proofs, transcript=TRANSCRIPT_BLAKE2B
     B = len(proofs)
     inst_pp, lens_pp, pp, pl, opts, st, keep = _verify_args(instances_list, proofs, transcript, n_circuits, combine_seed, combine_scalars, opts_size)
     pair = np.zeros(16, dtype=np.uint64)
-    ctx._chk(ctx.L.amdzk_verify_proofs(ctx.h, pk.h, B, inst_pp, lens_pp, pp, pl, C.byref(opts), st, pair.ctypes.data))
+    fn = ctx.L.amdzk_verify_proofs_vk if isinstance(pk, VerifyingKey) else ctx.L.amdzk_verify_proofs
+    ctx._chk(fn(ctx.h, pk.h, B, inst_pp, lens_pp, pp, pl, C.byref(opts), st, pair.ctypes.data))
     del keep
     return Guard(pair[:8].copy(), pair[8:].copy(), [ProofStatus(s.status, s.offset) for s in st[:B]])
 
@@ -893,7 +982,8 @@ DECIDE_RUN = 16      # AMDZK_DECIDE_RUN
 
 def decide_proofs(ctx, pk, vparams, instances_list, proofs, transcript=TRANSCRIPT_BLAKE2B, n_circuits=1, combined=False, combine_seed=0,
                   combine_scalars=None, opts_size=None):
-    """amdzk_verify_proofs_decide: plonk::verify_proof for a batch WITH the pairing. vparams: kzg.ParamsVerifierKZG of the SRS
+    """amdzk_verify_proofs_decide (amdzk_verify_proofs_decide_vk when pk is a VerifyingKey): plonk::verify_proof for a batch WITH
+    the pairing. vparams: kzg.ParamsVerifierKZG of the SRS
     the key was made on. combined=False: every proof by itself (SingleStrategy; deterministic, combine_* ignored);
     combined=True: upstream's BatchVerifier — one check with the weights of combine_seed / combine_scalars, which must be
     unpredictable to whoever made the proofs; every well-formed proof gets that check's result. Returns (verdicts, statuses):
@@ -902,8 +992,9 @@ def decide_proofs(ctx, pk, vparams, instances_list, proofs, transcript=TRANSCRIP
     inst_pp, lens_pp, pp, pl, opts, st, keep = _verify_args(instances_list, proofs, transcript, n_circuits, combine_seed, combine_scalars, opts_size)
     verdicts = np.zeros(max(1, B), np.uint8)
     n_valid = C.c_size_t(0)
-    ctx._chk(ctx.L.amdzk_verify_proofs_decide(ctx.h, pk.h, vparams.s_g2.h, vparams.g2.h, DECIDE_COMBINED if combined else 0, B, inst_pp, lens_pp,
-                                              pp, pl, C.byref(opts), st, verdicts.ctypes.data, C.byref(n_valid)))
+    fn = ctx.L.amdzk_verify_proofs_decide_vk if isinstance(pk, VerifyingKey) else ctx.L.amdzk_verify_proofs_decide
+    ctx._chk(fn(ctx.h, pk.h, vparams.s_g2.h, vparams.g2.h, DECIDE_COMBINED if combined else 0, B, inst_pp, lens_pp,
+                pp, pl, C.byref(opts), st, verdicts.ctypes.data, C.byref(n_valid)))
     del keep
     out = [bool(v) for v in verdicts[:B]]
     assert sum(out) == n_valid.value
@@ -932,11 +1023,12 @@ def verify_proof(ctx, pk, instances, proof, transcript=TRANSCRIPT_BLAKE2B, n_cir
 
 
 def proof_size_multi(ctx, pk, n_circuits, transcript=TRANSCRIPT_BLAKE2B):
-    return int(ctx.L.amdzk_proof_size_multi(pk.h, n_circuits, transcript))
+    fn = ctx.L.amdzk_vk_proof_size_multi if isinstance(pk, VerifyingKey) else ctx.L.amdzk_proof_size_multi
+    return int(fn(pk.h, n_circuits, transcript))
 
 
 def proof_size(ctx, pk, transcript=TRANSCRIPT_BLAKE2B):
-    return int(ctx.L.amdzk_proof_size(pk.h, transcript))
+    return proof_size_multi(ctx, pk, 1, transcript) if isinstance(pk, VerifyingKey) else int(ctx.L.amdzk_proof_size(pk.h, transcript))
 
 
 def proof_random_count(ctx, pk):

@@ -784,6 +784,73 @@ int amdzk_verify_proofs_decide(amdzk_ctx* ctx, const amdzk_pk* pk, const amdzk_g
                                const uint8_t* const* proofs, const size_t* proof_lens, const amdzk_verify_opts* opts,
                                amdzk_proof_status* statuses, uint8_t* verdicts /* n_proofs */, size_t* n_valid);
 
+/* ---- verifying keys: verify and decide proofs without a proving key.
+ * amdzk_vk is what plonk::verify_proof [UP] reads of its VerifyingKey and its params: the circuit description,
+ * transcript_repr, omega, the commitments of the fixed and the permutation columns, and G = g[0] of the SRS the key was made
+ * on. Host data only, a few KB: it holds no device buffer and no pointer to an amdzk_srs or an amdzk_pk — both may be freed
+ * before the key is used. A verifier process is a ctx and a key file: no amdzk_srs, no amdzk_pk.
+ *
+ * amdzk_keygen_vk — plonk::keygen_vk [UP]: the verifying key alone. Arguments as amdzk_keygen_phased / amdzk_keygen_sigma;
+ * with num_perm_columns > 0 EXACTLY ONE of perm_mapping and sigma_values is non-NULL (both or neither: AMDZK_E_INVALID,
+ * "keygen_vk:"). There are no mode flags: AMDZK_KEYGEN_* say how to prove. Device work: the upload of the F + S Lagrange
+ * columns (the sigma columns computed from the mapping as keygen does) and their commitments over AMDZK_BASIS_G_LAGRANGE —
+ * keygen's own steps, without the rest of keygen. Nothing proportional to the extended domain is allocated: no coset, no
+ * compiled program, no per-proof workspace; (F + S) * 2^k * 32 bytes while the call runs, nothing but the key after it.
+ * Runs on the ctx's stream and returns with it idle. Refusals are keygen's own checks with keygen's own prefixes
+ * ("keygen: ...", and "circuit: ..." for a query, a constant or challenge index or an expression word out of range and for a
+ * malformed expression: the expressions are not compiled here, the checks of the key file's reader stand in for the
+ * compiler's, before anything is uploaded), plus, with "keygen_vk:", the rule above, an SRS without AMDZK_BASIS_G or without
+ * AMDZK_BASIS_G_LAGRANGE, and an SRS of another k; the ctx stays usable. The verifier indexes by a key's queries and
+ * expression words unchecked, so NO amdzk_vk exists whose description those checks refuse: amdzk_vk_from_pk refuses, with
+ * "vk_from_pk:", the proving key of a circuit that keygen took on trust (a query that no expression uses may name any column). The key is the key amdzk_vk_from_pk gives for
+ * amdzk_keygen_phased / amdzk_keygen_sigma on the same inputs: amdzk_vk_write gives equal bytes for the two.
+ * amdzk_vk_from_pk — ProvingKey::get_vk [UP]: works on root keys, workspace clones, keys from amdzk_keygen_sigma and keys
+ * read from a key file. */
+typedef struct amdzk_vk amdzk_vk;
+int amdzk_keygen_vk(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* circuit, const amdzk_phases* phases /* may be NULL */,
+                    const uint64_t* fixed_values, const uint32_t* perm_mapping /* or NULL */, const uint64_t* sigma_values /* or NULL */,
+                    const uint64_t transcript_repr[4], amdzk_vk** out);
+int amdzk_vk_from_pk(amdzk_ctx* ctx, const amdzk_pk* pk, amdzk_vk** out);
+void amdzk_vk_free(amdzk_ctx* ctx, amdzk_vk* vk);
+int amdzk_vk_commitments(const amdzk_vk* vk, uint64_t* fixed_out, uint64_t* perm_out);        /* as amdzk_pk_commitments */
+size_t amdzk_vk_proof_size_multi(const amdzk_vk* vk, size_t n_circuits, int transcript_kind); /* = amdzk_proof_size_multi */
+/* The verifying-key file: this library's own format (not upstream's VerifyingKey::write, which stores no circuit).
+ * Little-endian, no padding, deterministic, self-delimiting (csrc/vkblob.hpp):
+ *   "AMDZKVK\0" | version u32 = 1 | the proving-key file's sections from amdzk_circuit through the permutation commitments,
+ *   byte for byte (circuit, has-phases and phase table, transcript_repr, fixed commitments, permutation commitments) |
+ *   G (64 B, G1Affine, Montgomery) | has-g2 u8 | if 1: g2 then s_g2, 128 B each, G2Affine as above |
+ *   BLAKE2b-512 of every byte before it, personalisation "amdzk_vk_blob_v1".
+ * amdzk_vk_write: g2 / s_g2 (both or neither) are the SRS's [1]_2 and [s]_2, so that the file is all a verifier needs;
+ * out = NULL queries *written. amdzk_vk_read needs no SRS and makes no device call; g2_out / s_g2_out / has_g2 may be NULL, the points are written
+ * only when the file has them. amdzk_vk_blob_info and amdzk_vk_blob_check are pure host code, callable without a device:
+ * every check amdzk_vk_read makes, and the reason as amdzk_vk_read would word it ("" for a good file).
+ * Refused with AMDZK_E_INVALID and a message that starts "vk_read:", the ctx stays usable: bad magic or version; any
+ * truncation or length mismatch; a digest mismatch; every header inconsistency amdzk_pk_read refuses; a commitment
+ * coordinate >= q; a commitment that is neither on the curve nor (0, 0) (an all-zero fixed column commits to the identity,
+ * which is legal); a G off the curve or the identity; a has-g2 byte other than 0 or 1; with has-g2 = 1 a G2 coordinate >= q,
+ * a point off the twist or the identity (amdzk_g2_prepare's checks). Membership of the G2 points in the order-r subgroup is
+ * NOT checked, as everywhere in this library. amdzk_vk_write checks what it wrote with the same reader, so a written file
+ * always reads back, and writing what was read gives the same bytes. */
+size_t amdzk_vk_serialized_size(const amdzk_vk* vk, int with_g2);
+int amdzk_vk_write(amdzk_ctx* ctx, const amdzk_vk* vk, const uint64_t g2[16] /* may be NULL */, const uint64_t s_g2[16] /* NULL iff g2 is */,
+                   uint8_t* out, size_t cap, size_t* written);
+int amdzk_vk_read(amdzk_ctx* ctx, const uint8_t* data, size_t len, amdzk_vk** out, uint64_t g2_out[16], uint64_t s_g2_out[16], int* has_g2);
+int amdzk_vk_blob_info(const uint8_t* data, size_t len, uint32_t* k, uint32_t* num_fixed, uint32_t* num_advice,
+                       uint32_t* num_perm_columns, uint32_t* num_challenges, int* has_g2);
+int amdzk_vk_blob_check(const uint8_t* data, size_t len, char* msg, size_t msg_cap);
+/* amdzk_verify_proofs and amdzk_verify_proofs_decide with a verifying key in the proving key's place: the same code over the
+ * same operands (the key's G is uploaded with its commitments instead of being copied from the SRS), hence the same
+ * contracts word for word — message prefixes, statuses, the run length, the weights, the identity rule — and, for the same
+ * circuit, SRS, proofs and options, equal pair_out, equal statuses and equal verdicts. */
+int amdzk_verify_proofs_vk(amdzk_ctx* ctx, const amdzk_vk* vk, size_t n_proofs, const uint64_t* const* const* instances,
+                           const size_t* const* instance_lens, const uint8_t* const* proofs, const size_t* proof_lens,
+                           const amdzk_verify_opts* opts /* NULL: defaults */, amdzk_proof_status* statuses /* n_proofs */,
+                           uint64_t pair_out[16]);
+int amdzk_verify_proofs_decide_vk(amdzk_ctx* ctx, const amdzk_vk* vk, const amdzk_g2* s_g2, const amdzk_g2* g2, uint32_t flags,
+                                  size_t n_proofs, const uint64_t* const* const* instances, const size_t* const* instance_lens,
+                                  const uint8_t* const* proofs, const size_t* proof_lens, const amdzk_verify_opts* opts,
+                                  amdzk_proof_status* statuses, uint8_t* verdicts /* n_proofs */, size_t* n_valid);
+
 /* Test hooks for the host pass that prepares quotient-domain programs for the limb-resident interpreter (bounds in
  * units of p, placement of the weak reductions, fusion of `t*x` with the accumulate): the pass on caller-supplied words
  * `op << 24 | arg` (opcodes: csrc/plonk_kernels.hpp ExprOp) — pure host code, callable without a device — and the

@@ -642,6 +642,8 @@ struct WitnessReport {
   bool ok() const { return failures.empty(); }
 };
 
+class VerifyingKey;  // below, beside the verifier
+
 // plonk::keygen_vk + keygen_pk: fixed[c] = the 2^k Lagrange values of fixed column c (selectors included).
 class ProvingKey {
  public:
@@ -776,6 +778,8 @@ class ProvingKey {
     for (const amdzk_check_failure& f : raw) rep.failures.push_back(CheckFailure{(CheckFailure::Kind)f.kind, f.index, f.first_row, f.count});
     return rep;
   }
+  // ProvingKey::get_vk (amdzk_vk_from_pk): the key's VerifyingKey, which may outlive this key and its params
+  std::unique_ptr<VerifyingKey> get_vk() const;
   amdzk_pk* handle() const { return h_; }
   uint32_t k() const { return k_; }
   size_t num_advice() const { return num_advice_; }
@@ -1262,27 +1266,48 @@ struct VerifyArgs {
 // proof b (n_circuits instances per proof, as create_proof_multi wrote them). combine_scalars: one weight per proof, or
 // empty to draw them from combine_seed — which must then be unpredictable to whoever made the proofs (seed it from the OS).
 // After a failed pairing, call again on subsets to find the culprit.
-inline Guard verify_proofs(const Context& ctx, const ProvingKey& pk, const std::vector<std::vector<std::vector<std::vector<Fr>>>>& instances,
-                           const std::vector<std::vector<uint8_t>>& proofs, Transcript transcript = Transcript::Blake2b,
-                           Multiopen multiopen = Multiopen::Shplonk, uint64_t combine_seed = 0, const std::vector<Fr>& combine_scalars = {}) {
+// Every function below takes the key as a ProvingKey or as a VerifyingKey (further down): the C entry points differ in the
+// key's type alone.
+namespace detail {
+inline int c_verify(amdzk_ctx* c, const amdzk_pk* key, VerifyArgs& a, uint64_t pair[16]) {
+  return amdzk_verify_proofs(c, key, a.B, a.inst_pp.data(), a.lens_pp.data(), a.pp.data(), a.pl.data(), &a.opts, a.raw.data(), pair);
+}
+inline int c_verify(amdzk_ctx* c, const amdzk_vk* key, VerifyArgs& a, uint64_t pair[16]) {
+  return amdzk_verify_proofs_vk(c, key, a.B, a.inst_pp.data(), a.lens_pp.data(), a.pp.data(), a.pl.data(), &a.opts, a.raw.data(), pair);
+}
+template <class Key>
+Guard verify_proofs(const Context& ctx, const Key& key, const std::vector<std::vector<std::vector<std::vector<Fr>>>>& instances,
+                    const std::vector<std::vector<uint8_t>>& proofs, Transcript transcript, Multiopen multiopen, uint64_t combine_seed,
+                    const std::vector<Fr>& combine_scalars) {
   VerifyArgs a("verify_proofs", instances, proofs, transcript, multiopen, combine_seed, combine_scalars);
   uint64_t pair[16];
-  ctx.check(amdzk_verify_proofs(ctx.get(), pk.handle(), a.B, a.inst_pp.data(), a.lens_pp.data(), a.pp.data(), a.pl.data(), &a.opts, a.raw.data(), pair));
+  ctx.check(c_verify(ctx.get(), key.handle(), a, pair));
   Guard g;
   std::memcpy(&g.lhs, pair, sizeof(G1Affine));
   std::memcpy(&g.rhs, pair + 8, sizeof(G1Affine));
   g.statuses = a.statuses();
   return g;
 }
-
-// SingleStrategy: one proof (weight 1), one call, one pairing. A malformed proof throws, naming status and offset.
-inline Guard verify_proof(const Context& ctx, const ProvingKey& pk, const std::vector<std::vector<Fr>>& instances, const std::vector<uint8_t>& proof,
-                          Transcript transcript = Transcript::Blake2b, Multiopen multiopen = Multiopen::Shplonk) {
-  Guard g = verify_proofs(ctx, pk, {{instances}}, {proof}, transcript, multiopen);
+template <class Key>
+Guard verify_proof(const Context& ctx, const Key& key, const std::vector<std::vector<Fr>>& instances, const std::vector<uint8_t>& proof,
+                   Transcript transcript, Multiopen multiopen) {
+  Guard g = detail::verify_proofs(ctx, key, {{instances}}, {proof}, transcript, multiopen, 0, {});
   if (!g.well_formed())
     throw Error(AMDZK_E_INVALID, "verify_proof: malformed proof, status " + std::to_string((unsigned)g.statuses[0].status) + ", offset " +
                                      std::to_string(g.statuses[0].offset));
   return g;
+}
+}  // namespace detail
+inline Guard verify_proofs(const Context& ctx, const ProvingKey& pk, const std::vector<std::vector<std::vector<std::vector<Fr>>>>& instances,
+                           const std::vector<std::vector<uint8_t>>& proofs, Transcript transcript = Transcript::Blake2b,
+                           Multiopen multiopen = Multiopen::Shplonk, uint64_t combine_seed = 0, const std::vector<Fr>& combine_scalars = {}) {
+  return detail::verify_proofs(ctx, pk, instances, proofs, transcript, multiopen, combine_seed, combine_scalars);
+}
+
+// SingleStrategy: one proof (weight 1), one call, one pairing. A malformed proof throws, naming status and offset.
+inline Guard verify_proof(const Context& ctx, const ProvingKey& pk, const std::vector<std::vector<Fr>>& instances, const std::vector<uint8_t>& proof,
+                          Transcript transcript = Transcript::Blake2b, Multiopen multiopen = Multiopen::Shplonk) {
+  return detail::verify_proof(ctx, pk, instances, proof, transcript, multiopen);
 }
 
 // ------------------------------------------------------------------------------------------ verify_proof WITH the pairing
@@ -1326,27 +1351,166 @@ struct Decision {
 // amdzk_verify_proofs_decide. combined = false: every proof by itself (SingleStrategy; deterministic, the weights are not
 // read). combined = true: upstream's BatchVerifier — ONE check with the weights of combine_seed / combine_scalars, which must
 // be unpredictable to whoever made the proofs; every well-formed proof gets that check's result.
-inline Decision decide_proofs(const Context& ctx, const ProvingKey& pk, const ParamsVerifierKZG& vparams,
-                              const std::vector<std::vector<std::vector<std::vector<Fr>>>>& instances, const std::vector<std::vector<uint8_t>>& proofs,
-                              Transcript transcript = Transcript::Blake2b, Multiopen multiopen = Multiopen::Shplonk, bool combined = false,
-                              uint64_t combine_seed = 0, const std::vector<Fr>& combine_scalars = {}) {
+namespace detail {
+inline int c_decide(amdzk_ctx* c, const amdzk_pk* key, const ParamsVerifierKZG& vp, uint32_t flags, VerifyArgs& a, uint8_t* v, size_t* n_valid) {
+  return amdzk_verify_proofs_decide(c, key, vp.s_g2.handle(), vp.g2.handle(), flags, a.B, a.inst_pp.data(), a.lens_pp.data(), a.pp.data(), a.pl.data(),
+                                    &a.opts, a.raw.data(), v, n_valid);
+}
+inline int c_decide(amdzk_ctx* c, const amdzk_vk* key, const ParamsVerifierKZG& vp, uint32_t flags, VerifyArgs& a, uint8_t* v, size_t* n_valid) {
+  return amdzk_verify_proofs_decide_vk(c, key, vp.s_g2.handle(), vp.g2.handle(), flags, a.B, a.inst_pp.data(), a.lens_pp.data(), a.pp.data(),
+                                       a.pl.data(), &a.opts, a.raw.data(), v, n_valid);
+}
+template <class Key>
+Decision decide_proofs(const Context& ctx, const Key& key, const ParamsVerifierKZG& vparams,
+                       const std::vector<std::vector<std::vector<std::vector<Fr>>>>& instances, const std::vector<std::vector<uint8_t>>& proofs,
+                       Transcript transcript, Multiopen multiopen, bool combined, uint64_t combine_seed, const std::vector<Fr>& combine_scalars) {
   VerifyArgs a("decide_proofs", instances, proofs, transcript, multiopen, combine_seed, combine_scalars);
   std::vector<uint8_t> v(std::max<size_t>(1, a.B), 0);
   Decision d;
-  ctx.check(amdzk_verify_proofs_decide(ctx.get(), pk.handle(), vparams.s_g2.handle(), vparams.g2.handle(), combined ? AMDZK_DECIDE_COMBINED : 0u, a.B,
-                                       a.inst_pp.data(), a.lens_pp.data(), a.pp.data(), a.pl.data(), &a.opts, a.raw.data(), v.data(), &d.n_valid));
+  ctx.check(c_decide(ctx.get(), key.handle(), vparams, combined ? AMDZK_DECIDE_COMBINED : 0u, a, v.data(), &d.n_valid));
   for (size_t b = 0; b < a.B; b++) d.verdicts.push_back(v[b] != 0);
   d.statuses = a.statuses();
   return d;
 }
-// plonk::verify_proof(params, vk, SingleStrategy, ...).is_ok(). A malformed proof throws, naming status and offset.
-inline bool decide_proof(const Context& ctx, const ProvingKey& pk, const ParamsVerifierKZG& vparams, const std::vector<std::vector<Fr>>& instances,
-                         const std::vector<uint8_t>& proof, Transcript transcript = Transcript::Blake2b, Multiopen multiopen = Multiopen::Shplonk) {
-  const Decision d = decide_proofs(ctx, pk, vparams, {{instances}}, {proof}, transcript, multiopen);
+template <class Key>
+bool decide_proof(const Context& ctx, const Key& key, const ParamsVerifierKZG& vparams, const std::vector<std::vector<Fr>>& instances,
+                  const std::vector<uint8_t>& proof, Transcript transcript, Multiopen multiopen) {
+  const Decision d = detail::decide_proofs(ctx, key, vparams, {{instances}}, {proof}, transcript, multiopen, false, 0, {});
   if (d.statuses[0].status != ProofStatus::WellFormed)
     throw Error(AMDZK_E_INVALID, "decide_proof: malformed proof, status " + std::to_string((unsigned)d.statuses[0].status) + ", offset " +
                                      std::to_string(d.statuses[0].offset));
   return d.verdicts[0];
+}
+}  // namespace detail
+inline Decision decide_proofs(const Context& ctx, const ProvingKey& pk, const ParamsVerifierKZG& vparams,
+                              const std::vector<std::vector<std::vector<std::vector<Fr>>>>& instances, const std::vector<std::vector<uint8_t>>& proofs,
+                              Transcript transcript = Transcript::Blake2b, Multiopen multiopen = Multiopen::Shplonk, bool combined = false,
+                              uint64_t combine_seed = 0, const std::vector<Fr>& combine_scalars = {}) {
+  return detail::decide_proofs(ctx, pk, vparams, instances, proofs, transcript, multiopen, combined, combine_seed, combine_scalars);
+}
+// plonk::verify_proof(params, vk, SingleStrategy, ...).is_ok(). A malformed proof throws, naming status and offset.
+inline bool decide_proof(const Context& ctx, const ProvingKey& pk, const ParamsVerifierKZG& vparams, const std::vector<std::vector<Fr>>& instances,
+                         const std::vector<uint8_t>& proof, Transcript transcript = Transcript::Blake2b, Multiopen multiopen = Multiopen::Shplonk) {
+  return detail::decide_proof(ctx, pk, vparams, instances, proof, transcript, multiopen);
+}
+
+// ------------------------------------------------------------------------------------------ the verifying key
+// plonk::VerifyingKey with the G of its params (amdzk_vk): all the verifier reads of a key. Host data only; it refers to no
+// ParamsKZG and no ProvingKey, so a verifier process holds a Context, this and a ParamsVerifierKZG — which read() can give it.
+class VerifyingKey {
+ public:
+  // plonk::keygen_vk (amdzk_keygen_vk): the key alone, without making a proving key — the fixed columns and the Assembly
+  // as for ProvingKey; the device holds the F + S Lagrange columns while the call runs and nothing afterwards.
+  static std::unique_ptr<VerifyingKey> keygen_vk(const Context& ctx, const ParamsKZG& params, const ConstraintSystem& cs,
+                                                 const std::vector<std::vector<Fr>>& fixed, const Assembly& assembly, const Fr& transcript_repr) {
+    const size_t n = (size_t)1 << params.k(), np = cs.permutation_columns.size();
+    if (fixed.size() != cs.num_fixed) throw Error(AMDZK_E_INVALID, "keygen_vk: fixed column count");
+    if (assembly.n() != n || assembly.num_columns() != np) throw Error(AMDZK_E_INVALID, "keygen_vk: assembly shape");
+    std::vector<Fr> flat(fixed.size() * n, Fr::zero());
+    for (size_t c = 0; c < fixed.size(); c++) {
+      if (fixed[c].size() > n) throw Error(AMDZK_E_INVALID, "keygen_vk: fixed column longer than 2^k");
+      std::copy(fixed[c].begin(), fixed[c].end(), flat.begin() + c * n);
+    }
+    CircuitData cd(cs, params.k());
+    std::unique_ptr<VerifyingKey> vk(new VerifyingKey(ctx, cs.num_fixed, np));
+    ctx.check(amdzk_keygen_vk(ctx.get(), params.handle(), &cd.c, cd.phased ? &cd.phases : nullptr, flat.empty() ? nullptr : (const uint64_t*)flat.data(),
+                              np ? assembly.mapping() : nullptr, nullptr, transcript_repr.l, &vk->h_));
+    return vk;
+  }
+  // ... from the sigma columns (one vector of 2^k per permutation column), as ProvingKey::from_sigma
+  static std::unique_ptr<VerifyingKey> keygen_vk_sigma(const Context& ctx, const ParamsKZG& params, const ConstraintSystem& cs,
+                                                       const std::vector<std::vector<Fr>>& fixed, const std::vector<std::vector<Fr>>& sigma,
+                                                       const Fr& transcript_repr) {
+    const size_t n = (size_t)1 << params.k();
+    if (fixed.size() != cs.num_fixed || sigma.size() != cs.permutation_columns.size()) throw Error(AMDZK_E_INVALID, "keygen_vk: column count");
+    auto flatten = [n](const std::vector<std::vector<Fr>>& cols) {
+      std::vector<Fr> flat(cols.size() * n, Fr::zero());
+      for (size_t c = 0; c < cols.size(); c++) {
+        if (cols[c].size() > n) throw Error(AMDZK_E_INVALID, "keygen_vk: column longer than 2^k");
+        std::copy(cols[c].begin(), cols[c].end(), flat.begin() + c * n);
+      }
+      return flat;
+    };
+    const std::vector<Fr> fx = flatten(fixed), sg = flatten(sigma);
+    CircuitData cd(cs, params.k());
+    std::unique_ptr<VerifyingKey> vk(new VerifyingKey(ctx, fixed.size(), sigma.size()));
+    ctx.check(amdzk_keygen_vk(ctx.get(), params.handle(), &cd.c, cd.phased ? &cd.phases : nullptr, fx.empty() ? nullptr : (const uint64_t*)fx.data(), nullptr,
+                              sg.empty() ? nullptr : (const uint64_t*)sg.data(), transcript_repr.l, &vk->h_));
+    return vk;
+  }
+  // The key file (include/amdzk.h has the layout). With g2 and s_g2 (both or neither) the file carries the SRS's [1]_2 and
+  // [s]_2 too and is all a verifier needs.
+  std::vector<uint8_t> write(const G2Affine* g2 = nullptr, const G2Affine* s_g2 = nullptr) const {
+    std::vector<uint8_t> out(amdzk_vk_serialized_size(h_, g2 ? 1 : 0));
+    size_t written = 0;
+    ctx_.check(amdzk_vk_write(ctx_.get(), h_, g2 ? g2->w : nullptr, s_g2 ? s_g2->w : nullptr, out.data(), out.size(), &written));
+    out.resize(written);
+    return out;
+  }
+  // The key of a file write() made (amdzk_vk_read); needs no ParamsKZG. A damaged, truncated or inconsistent file is refused
+  // with a message that starts "vk_read:". *has_g2 (may be null) says whether g2 / s_g2 (may be null) were in the file.
+  static std::unique_ptr<VerifyingKey> read(const Context& ctx, const std::vector<uint8_t>& data, G2Affine* g2 = nullptr, G2Affine* s_g2 = nullptr,
+                                            bool* has_g2 = nullptr) {
+    std::unique_ptr<VerifyingKey> vk(new VerifyingKey(ctx, 0, 0));
+    int has = 0;
+    ctx.check(amdzk_vk_read(ctx.get(), data.data(), data.size(), &vk->h_, g2 ? g2->w : nullptr, s_g2 ? s_g2->w : nullptr, &has));
+    uint32_t nf = 0, np = 0;
+    ctx.check(amdzk_vk_blob_info(data.data(), data.size(), nullptr, &nf, nullptr, &np, nullptr, nullptr));
+    vk->num_fixed_ = nf, vk->num_perm_ = np;
+    if (has_g2) *has_g2 = has != 0;
+    return vk;
+  }
+  ~VerifyingKey() {
+    if (h_) amdzk_vk_free(ctx_.get(), h_);
+  }
+  VerifyingKey(const VerifyingKey&) = delete;
+  VerifyingKey& operator=(const VerifyingKey&) = delete;
+  // VerifyingKey::{fixed_commitments, permutation.commitments}
+  void commitments(std::vector<G1Affine>& fixed, std::vector<G1Affine>& permutation) const {
+    fixed.assign(num_fixed_, G1Affine{});
+    permutation.assign(num_perm_, G1Affine{});
+    ctx_.check(amdzk_vk_commitments(h_, num_fixed_ ? (uint64_t*)fixed.data() : nullptr, num_perm_ ? (uint64_t*)permutation.data() : nullptr));
+  }
+  size_t proof_size(size_t n_circuits = 1, Transcript transcript = Transcript::Blake2b, Multiopen multiopen = Multiopen::Shplonk) const {
+    return amdzk_vk_proof_size_multi(h_, n_circuits, (int)transcript | (int)multiopen);
+  }
+  const amdzk_vk* handle() const { return h_; }
+
+ private:
+  friend class ProvingKey;
+  VerifyingKey(const Context& ctx, size_t nf, size_t np) : ctx_(ctx), num_fixed_(nf), num_perm_(np) {}
+  const Context& ctx_;
+  size_t num_fixed_, num_perm_;
+  amdzk_vk* h_ = nullptr;
+};
+inline std::unique_ptr<VerifyingKey> ProvingKey::get_vk() const {
+  std::unique_ptr<VerifyingKey> vk(new VerifyingKey(ctx_, num_fixed_, num_perm_));
+  ctx_.check(amdzk_vk_from_pk(ctx_.get(), h_, &vk->h_));
+  return vk;
+}
+inline std::unique_ptr<VerifyingKey> keygen_vk(const Context& ctx, const ParamsKZG& params, const ConstraintSystem& cs,
+                                               const std::vector<std::vector<Fr>>& fixed, const Assembly& assembly, const Fr& transcript_repr) {
+  return VerifyingKey::keygen_vk(ctx, params, cs, fixed, assembly, transcript_repr);
+}
+// The verifier's calls over a VerifyingKey: the contracts above, word for word.
+inline Guard verify_proofs(const Context& ctx, const VerifyingKey& vk, const std::vector<std::vector<std::vector<std::vector<Fr>>>>& instances,
+                           const std::vector<std::vector<uint8_t>>& proofs, Transcript transcript = Transcript::Blake2b,
+                           Multiopen multiopen = Multiopen::Shplonk, uint64_t combine_seed = 0, const std::vector<Fr>& combine_scalars = {}) {
+  return detail::verify_proofs(ctx, vk, instances, proofs, transcript, multiopen, combine_seed, combine_scalars);
+}
+inline Guard verify_proof(const Context& ctx, const VerifyingKey& vk, const std::vector<std::vector<Fr>>& instances, const std::vector<uint8_t>& proof,
+                          Transcript transcript = Transcript::Blake2b, Multiopen multiopen = Multiopen::Shplonk) {
+  return detail::verify_proof(ctx, vk, instances, proof, transcript, multiopen);
+}
+inline Decision decide_proofs(const Context& ctx, const VerifyingKey& vk, const ParamsVerifierKZG& vparams,
+                              const std::vector<std::vector<std::vector<std::vector<Fr>>>>& instances, const std::vector<std::vector<uint8_t>>& proofs,
+                              Transcript transcript = Transcript::Blake2b, Multiopen multiopen = Multiopen::Shplonk, bool combined = false,
+                              uint64_t combine_seed = 0, const std::vector<Fr>& combine_scalars = {}) {
+  return detail::decide_proofs(ctx, vk, vparams, instances, proofs, transcript, multiopen, combined, combine_seed, combine_scalars);
+}
+inline bool decide_proof(const Context& ctx, const VerifyingKey& vk, const ParamsVerifierKZG& vparams, const std::vector<std::vector<Fr>>& instances,
+                         const std::vector<uint8_t>& proof, Transcript transcript = Transcript::Blake2b, Multiopen multiopen = Multiopen::Shplonk) {
+  return detail::decide_proof(ctx, vk, vparams, instances, proof, transcript, multiopen);
 }
 
 }  // namespace halo2

@@ -13,7 +13,7 @@ HEADER = os.path.join(ROOT, "include", "amdzk.h")
 DOC = os.path.join(ROOT, "INTEGRATION.md")
 BEGIN, END = "<!-- BEGIN GENERATED FFI (tools/gen_rust_ffi.py) -->", "<!-- END GENERATED FFI -->"
 
-OPAQUE = {"amdzk_ctx": "Ctx", "amdzk_srs": "Srs", "amdzk_domain": "Domain", "amdzk_pk": "Pk", "amdzk_g2": "G2Prepared", "amdzk_circuit": "AmdzkCircuit",
+OPAQUE = {"amdzk_ctx": "Ctx", "amdzk_srs": "Srs", "amdzk_domain": "Domain", "amdzk_pk": "Pk", "amdzk_vk": "Vk", "amdzk_g2": "G2Prepared", "amdzk_circuit": "AmdzkCircuit",
           "amdzk_phases": "AmdzkPhases", "amdzk_transcript": "AmdzkTranscript", "amdzk_proof_opts": "AmdzkProofOpts",
           "amdzk_phase_fn": "AmdzkPhaseFn", "amdzk_batch_opts": "AmdzkBatchOpts", "amdzk_open_query": "AmdzkOpenQuery",
           "amdzk_multiopen_opts": "AmdzkMultiopenOpts", "amdzk_check_failure": "AmdzkCheckFailure", "amdzk_check_opts": "AmdzkCheckOpts",

@@ -2,13 +2,18 @@
 """Time amdzk_verify_proofs at the metric shape (workloads.full_aadhaar_shape, k = 15) on one GPU and write
 profiles/verify_batch.txt.
 
-    python tools/verify_bench.py [--k 15] [--reps 5] [--batches 1,8,64] [--out FILE]
+    python tools/verify_bench.py [--k 15] [--reps 5] [--batches 1,8,64] [--vk] [--out FILE] [--append]
 
 The proofs are made by the device prover in the same process (distinct seeds). For every batch size: the host wall clock
 around the blocking call (median of --reps after one warm-up), in total and per proof; and, from one more call with every
 kernel event-bracketed (amdzk_prof_*), the device time of the decode kernel and of the MSM's kernels, and that call's host
 time (its wall clock minus both; bracketed kernels run one at a time). No pairing is computed and no pair is checked: that
-is the test suite's business. Every status must be "well formed" or the run stops."""
+is the test suite's business. Every status must be "well formed" or the run stops.
+
+--vk adds the same calls through a verifying key (amdzk_verify_proofs_vk with pk.get_vk()), alternating with the pk route
+rep by rep, as a second table: wall clock of both routes side by side. The two pairs must be equal word for word or the
+run stops. --append adds the report to --out behind a blank line instead of replacing the file (profiles/vk.txt:
+tools/vk_bench.py, then this tool with --vk --batches 1,64 --out profiles/vk.txt --append)."""
 import argparse
 import os
 import statistics
@@ -33,6 +38,8 @@ def main():
     ap.add_argument("--k", type=int, default=15)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--batches", default="1,8,64")
+    ap.add_argument("--vk", action="store_true", help="also time the verifying-key route beside the proving key's")
+    ap.add_argument("--append", action="store_true", help="add the report to --out instead of replacing it")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "verify_batch.txt"))
     args = ap.parse_args()
     batches = [int(v) for v in args.batches.split(",")]
@@ -96,11 +103,28 @@ def main():
             msm = sum(ms for name, (_, ms) in prof.items() if name != "proof_decode")
             w = statistics.median(wall)
             lines.append("%8d %12.3f %14.3f %12.3f %12.3f %12.3f" % (nb, w, w / nb, decode, msm, prof_wall - decode - msm))
+        if args.vk:
+            vk = pk.get_vk()
+            lines += ["", "amdzk_verify_proofs_vk beside amdzk_verify_proofs: the same calls, the routes alternating rep by rep; wall ms, median of %d" % args.reps,
+                      "%8s %12s %12s %16s %16s" % ("n_proofs", "pk wall ms", "vk wall ms", "pk ms/proof", "vk ms/proof")]
+            for nb in batches:
+                proofs = [made[b % distinct] for b in range(nb)]
+                runs = {key: (lambda key=key: plonk.verify_proofs(ctx, key, [inst] * nb, proofs, combine_seed=12345)) for key in (pk, vk)}
+                a, b = runs[pk](), runs[vk]()
+                if not (np.array_equal(a.lhs, b.lhs) and np.array_equal(a.rhs, b.rhs) and a.statuses == b.statuses and b.well_formed):
+                    raise SystemExit("the verifying key's route disagrees with the proving key's: refusing to time it")
+                wall = {pk: [], vk: []}
+                for _ in range(args.reps):
+                    for key in (pk, vk):
+                        wall[key].append(timed(runs[key])[0])
+                wp, wv = statistics.median(wall[pk]), statistics.median(wall[vk])
+                lines.append("%8d %12.3f %12.3f %16.3f %16.3f" % (nb, wp, wv, wp / nb, wv / nb))
+            vk.free()
         text = "\n".join(lines) + "\n"
         sys.stdout.write(text)
         os.makedirs(os.path.dirname(args.out), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text)
+        with open(args.out, "a" if args.append else "w") as f:
+            f.write(("\n" if args.append else "") + text)
         d_adv.free()
         pk.free()
         params.free()
