@@ -187,6 +187,16 @@ def f12_to_tower(a):
     return out
 
 
+def f12_from_tower(t):
+    """The inverse of f12_to_tower: c_i.c_j = (x, y) contributes (x - 9 y) w^e + y w^(e + 6), e = i + 2j."""
+    a = [0] * 12
+    for i in range(2):
+        for j in range(3):
+            e, k = i + 2 * j, 2 * (3 * i + j)
+            a[e], a[e + 6] = (t[k] - 9 * t[k + 1]) % P, t[k + 1] % P
+    return tuple(a)
+
+
 # ---------------------------------------------------------------- the pairing
 def _line(t, q, p):
     """The line through t and q (the tangent when t == q) on the twist, untwisted and evaluated at the G1 point p:

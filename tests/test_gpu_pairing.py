@@ -1,6 +1,7 @@
 """GPU: the pairing unit — amdzk_g2_setup, amdzk_g2_prepare, amdzk_pairing_products — against tests/pairing_ref.py: GT limb
 for limb for m = 1, 2, 3 with identity entries in every position and for batches across the wave boundary and the
-lanes-per-block threshold; is_one on pairs that cancel and pairs that do not; s * G2; refusals that leave the ctx usable."""
+lanes-per-block threshold, and for calls of more than one chunk of 16384 Miller lanes (m = 16 and m = 3, values on both
+sides of the boundary); is_one on pairs that cancel and pairs that do not; s * G2; refusals that leave the ctx usable."""
 import ctypes as C
 
 import numpy as np
@@ -73,6 +74,47 @@ def test_batches_across_the_wave_boundary_and_the_lanes_per_block_threshold(ctx,
     for i, k in enumerate(ks):
         assert gt[i] == ref[k], i
     assert not any(one)
+
+
+def _row16(a, b, c):
+    """m = 16: the identity everywhere but at positions 0, 7 and 15."""
+    row = [None] * 16
+    row[0], row[7], row[15] = a, b, c
+    return tuple(row)
+
+
+# (m, n, the common row, {index: another row}, the index of the row that cancels). PAIRING_CHUNK_LANES = 16384 Miller lanes
+# go into one pair of launches, so a call is cut into chunks of 16384 / m checks.
+CHUNKED = {
+    # 16400 lanes, chunks of 1024 + 1 checks; handle j is prepared point j % 3, so positions 0 and 15 pair with the same point
+    # and row 1024, the first of the second chunk, is e(5 P, Q) e(-5 P, Q) = 1 (A3 = r - 5)
+    "m16": (16, 1025, _row16(A1, A2, A3), {0: _row16(1, A2, A3), 517: _row16(A1, A2, 1), 1023: _row16(A1, 1, A3), 1024: _row16(5, None, A3)}, 1024),
+    # chunks of 5461 + 1 checks: 16384 is no multiple of 3; row 5461 is e(2 P, Q) e(P, -2 Q) = 1 (B2 = r - 2)
+    "m3": (3, 5462, (A1, A2, A3), {0: (1, A2, A3), 5460: (A1, 1, A3), 5461: (2, None, 1)}, 5461),
+}
+
+
+@pytest.mark.parametrize("want_gt", [True, False], ids=["gt", "is_one_only"])
+@pytest.mark.parametrize("shape", sorted(CHUNKED))
+def test_calls_of_more_than_one_chunk(ctx, kzg, prepared, shape, want_gt):
+    """Values checked on both sides of a chunk boundary: the second chunk's G1 rows, GT rows and is_one bytes start where the
+    first chunk's end, its lanes pick their lines by (lane % m) counted from the chunk's first lane, and its launches reuse
+    the two register slabs. GT limb for limb for every row; is_one for the row that cancels, the first of the second chunk."""
+    m, n, common, special, cancels = CHUNKED[shape]
+    rows = [special.get(i, common) for i in range(n)]
+    distinct = sorted(set(rows), key=str)
+    ref = {row: X.pairing_product([(P(k), QS[j % 3]) for j, k in enumerate(row)]) for row in distinct}
+    assert len(set(ref.values())) == len(distinct) == len(special) + 1 and ref[rows[cancels]] == X.F12_ONE
+    point = {k: np.array(X.g1_words(P(k)), dtype=np.uint64) for row in distinct for k in row}
+    g1 = np.stack([point[k] for row in rows for k in row])
+    one, gt = kzg.pairing_products(ctx, [prepared[j % 3] for j in range(m)], g1, want_gt=want_gt)
+    assert [i for i in range(n) if one[i]] == [cancels]
+    if not want_gt:
+        assert gt is None
+        return
+    expect = {row: np.array(X.gt_words(f), dtype=np.uint64) for row, f in ref.items()}
+    wrong = [i for i in range(n) if not np.array_equal(gt[i], expect[rows[i]])]
+    assert not wrong, "GT differs from the reference in rows %s ... (%d rows)" % (wrong[:8], len(wrong))
 
 
 @pytest.mark.parametrize("a", [1, X.R - 1])
