@@ -269,23 +269,20 @@ int zk_check_copies(amdzk_ctx* ctx, const Fr* const* d_cols, const uint2* d_cell
 // What this handle needs beyond what a proof uses, made by its first check: the gate program, the permutation columns'
 // addresses in this workspace, the counters.
 static int check_build(amdzk_ctx* ctx, amdzk_pk* pk) {
+  const KeyMaterial& K = *pk->key;
   amdzk_pk::Check& ck = pk->chk;
   if (ck.built) return AMDZK_OK;
-  const uint32_t ncon = pk->num_gates + pk->L + pk->S;
+  const uint32_t ncon = K.num_gates + K.L + K.S;
   if (!ck.prog_gates.d_instr) {
-    Program pr;
-    const RotTable rots_before = pk->rots;  // the gates' rotations are all in the table already: the h(X) program queried them
-    for (uint32_t g = 0; g < pk->num_gates; g++) {
+    ProgramText pr;  // the gates' rotations are all in the key's table already (the h(X) program queried them): emit_expr refuses any other
+    for (uint32_t g = 0; g < K.num_gates; g++) {
       pr.piece();
-      ZK_TRY(emit_expr(ctx, pk, pr, pk->exprs[g]));
+      ZK_TRY(emit_expr(ctx, K, nullptr, pr, K.exprs[g]));
       pr.op(OP_CHECK, g);
       pr.pop();
     }
-    if (pk->rots.rots.size() != rots_before.rots.size()) {  // cannot happen for a key keygen made; the table stays what the uploaded programs index
-      pk->rots = rots_before;
-      ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: a gate polynomial queries a rotation the key's programs do not");
-    }
-    ck.prog_gates = pr;
+    ck.gates = std::move(pr);
+    ck.prog_gates.text = &ck.gates;
     ZK_TRY(upload_program(ctx, pk, ck.prog_gates, false));
   }
   if (!ck.d_count) {
@@ -296,13 +293,13 @@ static int check_build(amdzk_ctx* ctx, amdzk_pk* pk) {
   return AMDZK_OK;
 }
 
-// The root key's sigma columns back to (column, row), once: S * n * 8 bytes that every handle of the key reads.
-static int check_decode_sigma(amdzk_ctx* ctx, amdzk_pk* pk) {
-  amdzk_pk::CheckShared& sh = *pk->chk_shared;
+// The key's sigma columns back to (column, row), once: S * n * 8 bytes that every handle of the key reads.
+static int check_decode_sigma(amdzk_ctx* ctx, const KeyMaterial& K) {
+  KeyMaterial::CheckShared& sh = *K.chk_shared;
   std::lock_guard<std::mutex> lock(sh.guard);
-  if (sh.decoded || !pk->S) return AMDZK_OK;
-  const uint32_t S = pk->S, k = pk->k;
-  const size_t n = pk->n;
+  if (sh.decoded || !K.S) return AMDZK_OK;
+  const uint32_t S = K.S, k = K.k;
+  const size_t n = K.n;
   if (!sh.d_cells) {
     void* q = nullptr;
     if (hipMalloc(&q, (size_t)S * n * sizeof(uint2)) != hipSuccess) ZK_FAIL(ctx, AMDZK_E_NOMEM, "check_witness: hipMalloc of the decoded permutation failed");
@@ -320,7 +317,7 @@ static int check_decode_sigma(amdzk_ctx* ctx, amdzk_pk* pk) {
     a = mul(a, d2k);
     b = mul(b, delta_inv);
   }
-  Fr w = pk->omega_inv;
+  Fr w = K.omega_inv;
   for (uint32_t i = 0; i < k; i++) {
     tab[2 * (size_t)S + i] = w;
     w = mul(w, w);
@@ -331,7 +328,7 @@ static int check_decode_sigma(amdzk_ctx* ctx, amdzk_pk* pk) {
   unsigned long long bad = 0;
   int r = h2d(ctx, d_tab, tab.data(), tab.size() * 32);
   if (r == AMDZK_OK && hipMemsetAsync(d_bad, 0xFF, 8, ctx->stream) != hipSuccess) r = AMDZK_E_HIP;
-  if (r == AMDZK_OK) r = zk_sigma_decode(ctx, pk->sigma_lag, S, k, (const Fr*)d_tab, sh.d_cells, d_bad);
+  if (r == AMDZK_OK) r = zk_sigma_decode(ctx, K.sigma_lag, S, k, (const Fr*)d_tab, sh.d_cells, d_bad);
   if (r == AMDZK_OK) r = d2h(ctx, &bad, d_bad, 8);
   else (void)zk_host_wait(ctx, ctx->stream);  // `tab` is a host temporary
   hipFree(d_tab);
@@ -347,24 +344,24 @@ static int check_decode_sigma(amdzk_ctx* ctx, amdzk_pk* pk) {
 
 static int check_witness_run(amdzk_ctx* ctx, amdzk_pk* pk, const uint64_t* const* instances, const size_t* instance_lens, const void* d_advice,
                              size_t advice_stride, const amdzk_check_opts* opts, amdzk_check_failure* out, size_t cap, size_t* n_failures) {
-  if (!pk || !n_failures || (pk->A && !d_advice)) ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: null argument");
+  if (!pk || !n_failures || (pk->key->A && !d_advice)) ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: null argument");
+  const KeyMaterial& K = *pk->key;
   if (opts && opts->size < sizeof(amdzk_check_opts))
     ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: amdzk_check_opts.size is %zu, this library needs %zu", opts->size, sizeof(amdzk_check_opts));
-  const size_t n = pk->n, usable = n - (pk->bf + 1);
-  const uint32_t A = pk->A, I = pk->I, L = pk->L, S = pk->S, G = pk->num_gates, ncon = G + L + S;
-  if (pk->A && advice_stride < n) ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: advice stride < n");
+  const size_t n = K.n, usable = n - (K.bf + 1);
+  const uint32_t A = K.A, I = K.I, L = K.L, S = K.S, G = K.num_gates, ncon = G + L + S;
+  if (K.A && advice_stride < n) ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: advice stride < n");
   const uint32_t given = opts && opts->challenges ? opts->num_challenges : 0;
-  if (pk->num_challenges && !given) ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: the key has %u challenges and none were given", pk->num_challenges);
-  if ((opts ? opts->num_challenges : 0) != pk->num_challenges)
-    ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: %u challenges given, the key has %u", opts ? opts->num_challenges : 0, pk->num_challenges);
+  if (K.num_challenges && !given) ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: the key has %u challenges and none were given", K.num_challenges);
+  if ((opts ? opts->num_challenges : 0) != K.num_challenges)
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: %u challenges given, the key has %u", opts ? opts->num_challenges : 0, K.num_challenges);
   for (uint32_t c = 0; c < I; c++) {
     const size_t len = instance_lens ? instance_lens[c] : 0;
     if (len > usable) ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: instance column %u too long (InstanceTooLarge)", c);
     if (len && (!instances || !instances[c])) ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: null argument (instance column %u)", c);
   }
-  amdzk_pk* const root = const_cast<amdzk_pk*>(pk->clone_of ? pk->clone_of : pk);
   ZK_TRY(check_build(ctx, pk));
-  ZK_TRY(check_decode_sigma(ctx, root));
+  ZK_TRY(check_decode_sigma(ctx, K));
   const amdzk_pk::Check& ck = pk->chk;
   const CheckCounters counters = {ck.d_count, ck.d_first};
   *n_failures = 0;
@@ -383,24 +380,24 @@ static int check_witness_run(amdzk_ctx* ctx, amdzk_pk* pk, const uint64_t* const
   if (A) ZK_HIP(ctx, hipMemcpy2DAsync(pk->adv(), n * 32, d_advice, advice_stride * 32, n * 32, A, hipMemcpyDeviceToDevice, ctx->stream));
   {  // theta and the phase challenges into their slots of the constant table
     ChaCha20Rng rng(opts ? opts->theta_seed : 0);
-    pk->consts[pk->c_theta] = rng.fr();
-    ZK_TRY(h2d_staged(ctx, pk, pk->d_consts + pk->c_theta, &pk->consts[pk->c_theta], 32));
-    if (pk->num_challenges) {
-      memcpy(pk->consts[pk->c_chal0].l, opts->challenges, (size_t)pk->num_challenges * 32);
-      ZK_TRY(h2d_staged(ctx, pk, pk->d_consts + pk->c_chal0, &pk->consts[pk->c_chal0], (size_t)pk->num_challenges * 32));
+    pk->consts[K.c_theta] = rng.fr();
+    ZK_TRY(h2d_staged(ctx, pk, pk->d_consts + K.c_theta, &pk->consts[K.c_theta], 32));
+    if (K.num_challenges) {
+      memcpy(pk->consts[K.c_chal0].l, opts->challenges, (size_t)K.num_challenges * 32);
+      ZK_TRY(h2d_staged(ctx, pk, pk->d_consts + K.c_chal0, &pk->consts[K.c_chal0], (size_t)K.num_challenges * 32));
     }
   }
   if (G) {
     ExprArgs a;
     ZK_TRY(program_args(ctx, pk, pk->chk.prog_gates, false, nullptr, nullptr, a));
-    ZK_TRY(zk_check_expr(ctx, a, ck.prog_gates.depth + 1, (uint32_t)usable, counters, "expr_check_gates"));
+    ZK_TRY(zk_check_expr(ctx, a, ck.gates.depth + 1, (uint32_t)usable, counters, "expr_check_gates"));
   }
   if (L) {  // compressed inputs and tables as canonical keys, the tables sorted (constant ones were sorted at keygen)
     ZK_TRY(run_program(ctx, pk, pk->prog_compress, false, pk->d_outs_compress, nullptr, "expr_lookup_compress"));
     ZK_TRY(d2d(ctx, pk->la(), pk->ci, (size_t)L * n * 32));
     ZK_TRY(amdzk_fr_to_repr_dev(ctx, pk->la(), (size_t)L * n));
-    const uint32_t pre = pk->lk_const, rest = L - pre;
-    if (pre) ZK_TRY(d2d(ctx, pk->lk_ts, pk->lk_ts_const, (size_t)pre * n * 32));
+    const uint32_t pre = K.lk_const, rest = L - pre;
+    if (pre) ZK_TRY(d2d(ctx, pk->lk_ts, K.lk_ts_const, (size_t)pre * n * 32));
     if (rest) {
       Fr* Tr = pk->lk_ts + (size_t)pre * n;
       ZK_TRY(d2d(ctx, Tr, pk->ct + (size_t)pre * n, (size_t)rest * n * 32));
@@ -410,7 +407,7 @@ static int check_witness_run(amdzk_ctx* ctx, amdzk_pk* pk, const uint64_t* const
     }
     ZK_TRY(zk_check_lookups(ctx, pk->la(), pk->lk_ts, L, (uint32_t)n, (uint32_t)usable, G, counters));
   }
-  if (S) ZK_TRY(zk_check_copies(ctx, pk->d_perm_cols, root->chk_shared->d_cells, S, (uint32_t)n, G + L, counters));
+  if (S) ZK_TRY(zk_check_copies(ctx, pk->d_perm_cols, K.chk_shared->d_cells, S, (uint32_t)n, G + L, counters));
   std::vector<unsigned long long> host((size_t)ncon + ((size_t)ncon + 1) / 2);
   ZK_TRY(d2h(ctx, host.data(), ck.d_count, (size_t)ncon * 12));
   const uint32_t* first = reinterpret_cast<const uint32_t*>(host.data() + ncon);

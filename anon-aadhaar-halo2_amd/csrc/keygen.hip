@@ -59,14 +59,14 @@ using PkOwner = std::unique_ptr<amdzk_pk, PkFree>;
 }  // namespace
 
 // The per-proof workspace of ONE circuit instance (arenas, lookup / product scratch, multiopen buffers, small staging):
-// what a key owns besides its key material, and all a workspace clone allocates.
+// what a handle allocates, keygen's and a clone's alike.
 static int alloc_proof_workspace(amdzk_ctx* ctx, amdzk_pk* pk) {
-  const size_t n = pk->n, ext = pk->ext;
-  const uint32_t A = pk->A, I = pk->I, L = pk->L, ns = pk->nsets;
-  pk->NP = (size_t)A + I + 2 * L + ns + L;
-  ZK_TRY(dalloc(ctx, pk, &pk->P, pk->NP * n));
-  ZK_TRY(dalloc(ctx, pk, &pk->PQ, pk->NP * n));
-  ZK_TRY(dalloc(ctx, pk, &pk->PC, pk->NP * ext));
+  const KeyMaterial& K = *pk->key;
+  const size_t n = K.n, ext = K.ext;
+  const uint32_t L = K.L, ns = K.nsets;
+  ZK_TRY(dalloc(ctx, pk, &pk->P, K.NP * n));
+  ZK_TRY(dalloc(ctx, pk, &pk->PQ, K.NP * n));
+  ZK_TRY(dalloc(ctx, pk, &pk->PC, K.NP * ext));
   ZK_TRY(dalloc(ctx, pk, &pk->ci, (size_t)L * n));
   ZK_TRY(dalloc(ctx, pk, &pk->ct, (size_t)L * n));
   ZK_TRY(dalloc(ctx, pk, &pk->lk_ts, (size_t)L * n));
@@ -75,7 +75,7 @@ static int alloc_proof_workspace(amdzk_ctx* ctx, amdzk_pk* pk) {
   ZK_TRY(dalloc(ctx, pk, &pk->d_err, 1));
   ZK_TRY(dalloc(ctx, pk, &pk->rnd, n));
   ZK_TRY(dalloc(ctx, pk, &pk->hq, (size_t)H_PARTS_MAX * ext));  // one h per piece of the cut h(X) program (finalize_limb_program)
-  ZK_TRY(dalloc(ctx, pk, &pk->hpieces, (size_t)pk->qdeg * n));
+  ZK_TRY(dalloc(ctx, pk, &pk->hpieces, (size_t)K.qdeg * n));
   ZK_TRY(dalloc(ctx, pk, &pk->hpoly, n));
   const size_t nfrac = std::max<size_t>(std::max<size_t>(ns, L), 1);
   ZK_TRY(dalloc(ctx, pk, &pk->frac, nfrac * n));
@@ -84,11 +84,11 @@ static int alloc_proof_workspace(amdzk_ctx* ctx, amdzk_pk* pk) {
   ZK_TRY(dalloc(ctx, pk, &pk->frac2, std::max<size_t>(L, 1) * n));
   ZK_TRY(dalloc(ctx, pk, &pk->scratch2, std::max<size_t>(L, 1) * n));
   ZK_TRY(dalloc(ctx, pk, &pk->scan_tmp2, zk_scan_totals_elems(n, std::max<size_t>(L, 1)) + 2 * std::max<size_t>(L, 1) + 8));
-  const size_t max_rsets = pk->max_sets;
+  const size_t max_rsets = K.max_sets;
   ZK_TRY(dalloc(ctx, pk, &pk->sets_L, max_rsets * n));
   ZK_TRY(dalloc(ctx, pk, &pk->sets_N, max_rsets * n));
   ZK_TRY(dalloc(ctx, pk, &pk->hx, n));
-  pk->small_cap = std::max<size_t>((size_t)pk->NP * (pk->bf + 2) + 4096, 8192);
+  pk->small_cap = std::max<size_t>((size_t)K.NP * (K.bf + 2) + 4096, 8192);
   for (int l = 0; l < 3; l++) ZK_TRY(dalloc(ctx, pk, &pk->small_l[l], pk->small_cap));
   pk->small = pk->small_l[0];
   pk->pin_cap = std::max<size_t>((size_t)8 << 20, 2 * n * 32);
@@ -112,31 +112,32 @@ static int alloc_proof_workspace(amdzk_ctx* ctx, amdzk_pk* pk) {
 // The slot -> column pointer tables the interpreters read (Lagrange and quotient domain): key columns and this
 // workspace's arenas.
 static int build_column_tables(amdzk_ctx* ctx, amdzk_pk* pk) {
-  const size_t n = pk->n, ext = pk->ext;
-  const uint32_t F = pk->F, A = pk->A, I = pk->I, S = pk->S, L = pk->L, ns = pk->nsets;
+  const KeyMaterial& K = *pk->key;
+  const size_t n = K.n, ext = K.ext;
+  const uint32_t F = K.F, A = K.A, I = K.I, S = K.S, L = K.L, ns = K.nsets;
   // ---- column pointer tables
   {
-    std::vector<const Fr*> lag(pk->nslots_lag()), ex(pk->nslots_ext());
-    for (uint32_t i = 0; i < F; i++) lag[pk->sl_fixed(i)] = pk->fixed_lag + (size_t)i * n, ex[i] = pk->fixed_coset + (size_t)i * ext;
-    for (uint32_t i = 0; i < A; i++) lag[pk->sl_adv(i)] = pk->adv() + (size_t)i * n, ex[pk->sl_adv(i)] = pk->PC + (size_t)i * ext;
-    for (uint32_t i = 0; i < I; i++) lag[pk->sl_inst(i)] = pk->inst() + (size_t)i * n, ex[pk->sl_inst(i)] = pk->PC + (size_t)(A + i) * ext;
-    for (uint32_t i = 0; i < S; i++) lag[pk->sl_sigma(i)] = pk->sigma_lag + (size_t)i * n, ex[pk->se_sigma(i)] = pk->sigma_coset + (size_t)i * ext;
-    for (uint32_t i = 0; i < S; i++) lag[pk->sl_dxw(i)] = pk->dxw_lag + (size_t)i * n, ex[pk->se_dx(i)] = pk->dx_coset + (size_t)i * ext;
+    std::vector<const Fr*> lag(K.nslots_lag()), ex(K.nslots_ext());
+    for (uint32_t i = 0; i < F; i++) lag[K.sl_fixed(i)] = K.fixed_lag + (size_t)i * n, ex[i] = K.fixed_coset + (size_t)i * ext;
+    for (uint32_t i = 0; i < A; i++) lag[K.sl_adv(i)] = pk->adv() + (size_t)i * n, ex[K.sl_adv(i)] = pk->PC + (size_t)i * ext;
+    for (uint32_t i = 0; i < I; i++) lag[K.sl_inst(i)] = pk->inst() + (size_t)i * n, ex[K.sl_inst(i)] = pk->PC + (size_t)(A + i) * ext;
+    for (uint32_t i = 0; i < S; i++) lag[K.sl_sigma(i)] = K.sigma_lag + (size_t)i * n, ex[K.se_sigma(i)] = K.sigma_coset + (size_t)i * ext;
+    for (uint32_t i = 0; i < S; i++) lag[K.sl_dxw(i)] = K.dxw_lag + (size_t)i * n, ex[K.se_dx(i)] = K.dx_coset + (size_t)i * ext;
     for (uint32_t l = 0; l < L; l++) {
-      lag[pk->sl_ci(l)] = pk->ci + (size_t)l * n;
-      lag[pk->sl_ct(l)] = pk->ct + (size_t)l * n;
-      lag[pk->sl_la(l)] = pk->la() + (size_t)l * n;
-      lag[pk->sl_ls(l)] = pk->ls() + (size_t)l * n;
-      ex[pk->se_la(l)] = pk->PC + (size_t)(A + I + l) * ext;
-      ex[pk->se_ls(l)] = pk->PC + (size_t)(A + I + L + l) * ext;
-      ex[pk->se_zl(l)] = pk->PC + (size_t)(A + I + 2 * L + ns + l) * ext;
+      lag[K.sl_ci(l)] = pk->ci + (size_t)l * n;
+      lag[K.sl_ct(l)] = pk->ct + (size_t)l * n;
+      lag[K.sl_la(l)] = pk->la() + (size_t)l * n;
+      lag[K.sl_ls(l)] = pk->ls() + (size_t)l * n;
+      ex[K.se_la(l)] = pk->PC + (size_t)(A + I + l) * ext;
+      ex[K.se_ls(l)] = pk->PC + (size_t)(A + I + L + l) * ext;
+      ex[K.se_zl(l)] = pk->PC + (size_t)(A + I + 2 * L + ns + l) * ext;
     }
-    for (uint32_t s = 0; s < ns; s++) ex[pk->se_zp(s)] = pk->PC + (size_t)(A + I + 2 * L + s) * ext;
-    lag[pk->sl_omega()] = pk->omega_pow;
-    ex[pk->se_l0()] = pk->l0_c;
-    ex[pk->se_llast()] = pk->llast_c;
-    ex[pk->se_lactive()] = pk->lactive_c;
-    ex[pk->se_x()] = pk->x_coset;
+    for (uint32_t s = 0; s < ns; s++) ex[K.se_zp(s)] = pk->PC + (size_t)(A + I + 2 * L + s) * ext;
+    lag[K.sl_omega()] = K.omega_pow;
+    ex[K.se_l0()] = K.l0_c;
+    ex[K.se_llast()] = K.llast_c;
+    ex[K.se_lactive()] = K.lactive_c;
+    ex[K.se_x()] = K.x_coset;
     pk->h_cols_lag = lag;
     pk->h_cols_ext = ex;
     ZK_TRY(dalloc(ctx, pk, &pk->d_cols_lag, lag.size()));
@@ -146,8 +147,8 @@ static int build_column_tables(amdzk_ctx* ctx, amdzk_pk* pk) {
     // the permutation columns' values, in the permutation's order (the sparse products and the copy check read them by row)
     std::vector<const Fr*> pv(S);
     for (uint32_t i = 0; i < S; i++) {
-      const std::pair<int, int>& kc = pk->perm_cols[i];
-      pv[i] = lag[kc.first == 0 ? pk->sl_adv(kc.second) : kc.first == 1 ? pk->sl_fixed(kc.second) : pk->sl_inst(kc.second)];
+      const std::pair<int, int>& kc = K.perm_cols[i];
+      pv[i] = lag[kc.first == 0 ? K.sl_adv(kc.second) : kc.first == 1 ? K.sl_fixed(kc.second) : K.sl_inst(kc.second)];
     }
     ZK_TRY(dalloc(ctx, pk, &pk->d_perm_cols, pv.size()));
     ZK_TRY(h2d(ctx, pk->d_perm_cols, pv.data(), pv.size() * sizeof(Fr*)));
@@ -159,8 +160,9 @@ static int build_column_tables(amdzk_ctx* ctx, amdzk_pk* pk) {
 
 // Where the Lagrange-domain programs store: compressed lookup inputs / tables, permutation fractions, lookup fractions.
 static int build_output_tables(amdzk_ctx* ctx, amdzk_pk* pk) {
-  const size_t n = pk->n;
-  const uint32_t L = pk->L, ns = pk->nsets;
+  const KeyMaterial& K = *pk->key;
+  const size_t n = K.n;
+  const uint32_t L = K.L, ns = K.nsets;
   {
     std::vector<Fr*> outs(2 * L);
     for (uint32_t l = 0; l < L; l++) outs[2 * l] = pk->ci + (size_t)l * n, outs[2 * l + 1] = pk->ct + (size_t)l * n;
@@ -188,6 +190,9 @@ static int build_output_tables(amdzk_ctx* ctx, amdzk_pk* pk) {
 // What a key handle holds for ITS workspace besides the arenas: the pointer tables, the constant tables, the powers of
 // y, and the four programs resolved to this workspace's addresses. Keygen and amdzk_pk_clone_workspace both go through it.
 static int bind_workspace(amdzk_ctx* ctx, amdzk_pk* pk) {
+  const KeyMaterial& K = *pk->key;
+  pk->consts = K.consts;
+  pk->prog_compress.text = &K.prog_compress, pk->prog_pfrac.text = &K.prog_pfrac, pk->prog_lfrac.text = &K.prog_lfrac, pk->prog_h.text = &K.prog_h;
   ZK_TRY(build_column_tables(ctx, pk));
   ZK_TRY(build_output_tables(ctx, pk));
   ZK_TRY(dalloc(ctx, pk, &pk->d_consts, pk->consts.size()));
@@ -197,18 +202,18 @@ static int bind_workspace(amdzk_ctx* ctx, amdzk_pk* pk) {
   ZK_TRY(upload_program(ctx, pk, pk->prog_compress, false));
   ZK_TRY(upload_program(ctx, pk, pk->prog_pfrac, false));
   ZK_TRY(upload_program(ctx, pk, pk->prog_lfrac, false));
-  ZK_TRY(dalloc(ctx, pk, &pk->d_ypow, (size_t)std::max<uint32_t>(pk->h_terms, 1)));
+  ZK_TRY(dalloc(ctx, pk, &pk->d_ypow, (size_t)std::max<uint32_t>(K.h_terms, 1)));
   ZK_TRY(upload_program(ctx, pk, pk->prog_h, true));
   return upload_consts261(ctx, pk);
 }
 
 // ---- keygen, step by step (keygen_common below runs them in this order; amdzk_keygen_vk, vk.hip, runs the ones pk.hpp
-// declares, with vk_only set)
+// declares). K: the material under construction; pk: the handle keygen will return, where a step works in its workspace.
 
 // The phase table the way ConstraintSystem::{advice_column_in, challenge_usable_after} assert [UP], the flags and the null
 // arguments: pure checks, before anything is allocated. *nphases: the number of phases the table uses (1 without one).
 int check_keygen_args(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* c, const amdzk_phases* ph, const uint64_t transcript_repr[4],
-                      uint32_t flags, amdzk_pk** out, uint32_t* nphases) {
+                      uint32_t flags, const void* out, uint32_t* nphases) {
   *nphases = 1;
   if (ph && c) {
     if ((c->num_advice && !ph->advice_phase) || (ph->num_challenges && !ph->challenge_phase))
@@ -243,102 +248,102 @@ int check_keygen_args(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit*
 // The circuit description into the key — shape, domain, queries, expressions, the key file's header — and the layout of
 // the constant table. vk_only (amdzk_keygen_vk, vk.hip): the key will only commit to its fixed and permutation columns —
 // no prefix basis, no quotient plan, no extended domain (ext stays 0).
-int describe_circuit(amdzk_ctx* ctx, amdzk_pk* pk, const amdzk_srs* srs, const amdzk_circuit* c, const amdzk_phases* ph, uint32_t nphases,
+int describe_circuit(amdzk_ctx* ctx, KeyMaterial& K, const amdzk_srs* srs, const amdzk_circuit* c, const amdzk_phases* ph, uint32_t nphases,
                      const uint64_t transcript_repr[4], uint32_t flags, bool vk_only) {
-  pk->srs = srs;
-  pk->chk_shared = std::make_shared<amdzk_pk::CheckShared>();
-  pk->k = c->k;
-  pk->n = (size_t)1 << c->k;
-  pk->bf = c->blinding_factors;
-  pk->degree = c->cs_degree;
-  pk->F = c->num_fixed;
-  pk->A = c->num_advice;
-  pk->I = c->num_instance;
-  pk->S = c->num_perm_columns;
-  pk->L = c->num_lookups;
-  pk->chunk = pk->degree - 2;
-  pk->nsets = (pk->S + pk->chunk - 1) / pk->chunk;
-  pk->qdeg = pk->degree - 1;
-  if (pk->S && !vk_only) ZK_TRY(zk_srs_ensure_prefix(ctx, srs));  // the permutation products are committed over it (Prover::perm_commit)
+  K.srs = srs;
+  K.k = c->k;
+  K.n = (size_t)1 << c->k;
+  K.bf = c->blinding_factors;
+  K.degree = c->cs_degree;
+  K.F = c->num_fixed;
+  K.A = c->num_advice;
+  K.I = c->num_instance;
+  K.S = c->num_perm_columns;
+  K.L = c->num_lookups;
+  K.chunk = K.degree - 2;
+  K.nsets = (K.S + K.chunk - 1) / K.chunk;
+  K.qdeg = K.degree - 1;
+  K.NP = (size_t)K.A + K.I + 2 * K.L + K.nsets + K.L;
+  if (K.S && !vk_only) ZK_TRY(zk_srs_ensure_prefix(ctx, srs));  // the permutation products are committed over it (Prover::perm_commit)
   if (ph) {
-    pk->nphases = nphases;
-    pk->num_challenges = ph->num_challenges;
-    pk->advice_phase.assign(ph->advice_phase, ph->advice_phase + (c->num_advice ? c->num_advice : 0));
-    pk->challenge_phase.assign(ph->challenge_phase, ph->challenge_phase + ph->num_challenges);
+    K.nphases = nphases;
+    K.num_challenges = ph->num_challenges;
+    K.advice_phase.assign(ph->advice_phase, ph->advice_phase + (c->num_advice ? c->num_advice : 0));
+    K.challenge_phase.assign(ph->challenge_phase, ph->challenge_phase + ph->num_challenges);
   }
-  if (pk->n < pk->bf + 3) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: not enough rows (n = %zu, blinding factors = %u)", pk->n, pk->bf);
-  memcpy(pk->transcript_repr.l, transcript_repr, 32);
-  ZK_TRY(amdzk_domain_new(ctx, pk->degree, pk->k, &pk->dom));
-  pk->ek = amdzk_domain_extended_k(pk->dom);
+  if (K.n < K.bf + 3) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: not enough rows (n = %zu, blinding factors = %u)", K.n, K.bf);
+  memcpy(K.transcript_repr.l, transcript_repr, 32);
+  ZK_TRY(amdzk_domain_new(ctx, K.degree, K.k, &K.dom));
+  K.ek = amdzk_domain_extended_k(K.dom);
   // h(X) has qdeg = degree - 1 pieces: that many cosets pin it down (AMDZK_FULL_COSETS=1: all 2^(ek-k), upstream's own
   // computation — identical output for satisfying witnesses, and the way to reproduce upstream's bytes for others)
-  pk->nc = (flags & AMDZK_KEYGEN_FULL_COSETS) ? (1u << (pk->ek - pk->k)) : pk->qdeg;
-  pk->use_lanes = !(flags & AMDZK_KEYGEN_SERIAL);
+  K.nc = (flags & AMDZK_KEYGEN_FULL_COSETS) ? (1u << (K.ek - K.k)) : K.qdeg;
+  K.use_lanes = !(flags & AMDZK_KEYGEN_SERIAL);
   if (!vk_only) {
-    ZK_TRY(zk_quotient_plan(ctx, pk->dom, pk->nc));
-    pk->ext = (size_t)pk->nc * pk->n;
+    ZK_TRY(zk_quotient_plan(ctx, K.dom, K.nc));
+    K.ext = (size_t)K.nc * K.n;
   }
-  amdzk_domain_constant(pk->dom, 0, (uint64_t*)pk->omega.l);
-  amdzk_domain_constant(pk->dom, 1, (uint64_t*)pk->omega_inv.l);
-  for (uint32_t i = 0; i < c->num_advice_queries; i++) pk->advice_queries.push_back({c->advice_queries[2 * i], c->advice_queries[2 * i + 1]});
-  for (uint32_t i = 0; i < c->num_fixed_queries; i++) pk->fixed_queries.push_back({c->fixed_queries[2 * i], c->fixed_queries[2 * i + 1]});
+  amdzk_domain_constant(K.dom, 0, (uint64_t*)K.omega.l);
+  amdzk_domain_constant(K.dom, 1, (uint64_t*)K.omega_inv.l);
+  for (uint32_t i = 0; i < c->num_advice_queries; i++) K.advice_queries.push_back({c->advice_queries[2 * i], c->advice_queries[2 * i + 1]});
+  for (uint32_t i = 0; i < c->num_fixed_queries; i++) K.fixed_queries.push_back({c->fixed_queries[2 * i], c->fixed_queries[2 * i + 1]});
   for (uint32_t i = 0; i < c->num_instance_queries; i++)
-    pk->instance_queries.push_back({c->instance_queries[2 * i], c->instance_queries[2 * i + 1]});
-  for (uint32_t i = 0; i < pk->S; i++) pk->perm_cols.push_back({(int)c->perm_columns[2 * i], (int)c->perm_columns[2 * i + 1]});
-  pk->num_gates = c->num_gates;
+    K.instance_queries.push_back({c->instance_queries[2 * i], c->instance_queries[2 * i + 1]});
+  for (uint32_t i = 0; i < K.S; i++) K.perm_cols.push_back({(int)c->perm_columns[2 * i], (int)c->perm_columns[2 * i + 1]});
+  K.num_gates = c->num_gates;
   uint32_t nexpr = c->num_gates;
-  for (uint32_t l = 0; l < pk->L; l++) {
-    pk->lookup_shape.push_back({c->lookup_shape[2 * l], c->lookup_shape[2 * l + 1]});
+  for (uint32_t l = 0; l < K.L; l++) {
+    K.lookup_shape.push_back({c->lookup_shape[2 * l], c->lookup_shape[2 * l + 1]});
     nexpr += c->lookup_shape[2 * l] + c->lookup_shape[2 * l + 1];
   }
   if (nexpr != c->num_exprs) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: expression count mismatch (%u vs %u)", nexpr, c->num_exprs);
   for (uint32_t e = 0; e < c->num_exprs; e++)
-    pk->exprs.emplace_back(c->expr_words + c->expr_offsets[e], c->expr_words + c->expr_offsets[e + 1]);
+    K.exprs.emplace_back(c->expr_words + c->expr_offsets[e], c->expr_words + c->expr_offsets[e + 1]);
   {
     auto desc = std::make_shared<pkblob::Desc>();
     desc->assign(*c, ph);
-    pk->src_desc = desc;
+    K.src_desc = desc;
   }
   // constants: circuit | one theta beta gamma y 1/beta
-  pk->consts.resize(c->num_constants);
-  if (c->num_constants) memcpy(pk->consts.data(), c->constants, (size_t)c->num_constants * 32);
-  pk->c_one = c->num_constants;
-  pk->c_theta = pk->c_one + 1;
-  pk->c_beta = pk->c_one + 2;
-  pk->c_gamma = pk->c_one + 3;
-  pk->c_y = pk->c_one + 4;
-  pk->c_betainv = pk->c_one + 5;
-  pk->c_chal0 = pk->c_betainv + 1;
-  pk->consts.resize((size_t)pk->c_chal0 + pk->num_challenges, Fr::zero());
-  pk->consts[pk->c_one] = Fr::one();
+  K.consts.resize(c->num_constants);
+  if (c->num_constants) memcpy(K.consts.data(), c->constants, (size_t)c->num_constants * 32);
+  K.c_one = c->num_constants;
+  K.c_theta = K.c_one + 1;
+  K.c_beta = K.c_one + 2;
+  K.c_gamma = K.c_one + 3;
+  K.c_y = K.c_one + 4;
+  K.c_betainv = K.c_one + 5;
+  K.c_chal0 = K.c_betainv + 1;
+  K.consts.resize((size_t)K.c_chal0 + K.num_challenges, Fr::zero());
+  K.consts[K.c_one] = Fr::one();
   return AMDZK_OK;
 }
 
 // The key material's device buffers — fixed and permutation columns in their three forms, the domain columns — and the
-// key's own per-proof workspace.
-static int alloc_key_material(amdzk_ctx* ctx, amdzk_pk* pk) {
-  const size_t n = pk->n, ext = pk->ext;
-  const uint32_t F = pk->F, S = pk->S;
-  ZK_TRY(dalloc(ctx, pk, &pk->fixed_lag, (size_t)F * n));
-  ZK_TRY(dalloc(ctx, pk, &pk->fixed_poly, (size_t)F * n));
-  ZK_TRY(dalloc(ctx, pk, &pk->fixed_coset, (size_t)F * ext));
-  ZK_TRY(dalloc(ctx, pk, &pk->sigma_lag, (size_t)S * n));
-  ZK_TRY(dalloc(ctx, pk, &pk->sigma_poly, (size_t)S * n));
-  ZK_TRY(dalloc(ctx, pk, &pk->sigma_coset, (size_t)S * ext));
-  ZK_TRY(dalloc(ctx, pk, &pk->l0_c, ext));
-  ZK_TRY(dalloc(ctx, pk, &pk->llast_c, ext));
-  ZK_TRY(dalloc(ctx, pk, &pk->lactive_c, ext));
-  ZK_TRY(dalloc(ctx, pk, &pk->x_coset, ext));
-  ZK_TRY(dalloc(ctx, pk, &pk->omega_pow, n));
-  ZK_TRY(dalloc(ctx, pk, &pk->dxw_lag, (size_t)S * n));
-  ZK_TRY(dalloc(ctx, pk, &pk->dx_coset, (size_t)S * ext));
+// per-proof workspace of keygen's handle, which the steps below borrow.
+static int alloc_key_material(amdzk_ctx* ctx, KeyMaterial& K, amdzk_pk* pk) {
+  const size_t n = K.n, ext = K.ext;
+  const uint32_t F = K.F, S = K.S;
+  ZK_TRY(dalloc(ctx, &K, &K.fixed_lag, (size_t)F * n));
+  ZK_TRY(dalloc(ctx, &K, &K.fixed_poly, (size_t)F * n));
+  ZK_TRY(dalloc(ctx, &K, &K.fixed_coset, (size_t)F * ext));
+  ZK_TRY(dalloc(ctx, &K, &K.sigma_lag, (size_t)S * n));
+  ZK_TRY(dalloc(ctx, &K, &K.sigma_poly, (size_t)S * n));
+  ZK_TRY(dalloc(ctx, &K, &K.sigma_coset, (size_t)S * ext));
+  ZK_TRY(dalloc(ctx, &K, &K.l0_c, ext));
+  ZK_TRY(dalloc(ctx, &K, &K.llast_c, ext));
+  ZK_TRY(dalloc(ctx, &K, &K.lactive_c, ext));
+  ZK_TRY(dalloc(ctx, &K, &K.x_coset, ext));
+  ZK_TRY(dalloc(ctx, &K, &K.omega_pow, n));
+  ZK_TRY(dalloc(ctx, &K, &K.dxw_lag, (size_t)S * n));
+  ZK_TRY(dalloc(ctx, &K, &K.dx_coset, (size_t)S * ext));
   return alloc_proof_workspace(ctx, pk);
 }
 
 // The columns that depend on the domain alone: omega powers; l_0, l_last and l_blind on the cosets (l_blind in lactive_c,
 // until finish_l_active); the cosets' points; the identity permutation.
-static int build_domain_columns(amdzk_ctx* ctx, amdzk_pk* pk) {
-  const size_t n = pk->n, ext = pk->ext;
+static int build_domain_columns(amdzk_ctx* ctx, KeyMaterial& K, amdzk_pk* pk) {
+  const size_t n = K.n, ext = K.ext;
   std::vector<Fr> op(n), l0(n, Fr::zero()), ll(n, Fr::zero()), lb(n, Fr::zero()), xc(ext);
   // the copies below read these vectors asynchronously: a step that fails between a copy and its wait still leaves the
   // stream idle before they go away
@@ -349,41 +354,41 @@ static int build_domain_columns(amdzk_ctx* ctx, amdzk_pk* pk) {
   Fr cur = Fr::one();
   for (size_t i = 0; i < n; i++) {
     op[i] = cur;
-    cur = mul(cur, pk->omega);
+    cur = mul(cur, K.omega);
   }
-  ZK_TRY(h2d(ctx, pk->omega_pow, op.data(), n * 32));
+  ZK_TRY(h2d(ctx, K.omega_pow, op.data(), n * 32));
   l0[0] = Fr::one();
-  ll[n - pk->bf - 1] = Fr::one();
-  for (size_t i = n - pk->bf; i < n; i++) lb[i] = Fr::one();
+  ll[n - K.bf - 1] = Fr::one();
+  for (size_t i = n - K.bf; i < n; i++) lb[i] = Fr::one();
   // to cosets via the same device path as every other polynomial, one column at a time through pk->scratch
   Fr* tmp = pk->scratch;
-  Fr* dst[3] = {pk->l0_c, pk->llast_c, pk->lactive_c};
+  Fr* dst[3] = {K.l0_c, K.llast_c, K.lactive_c};
   std::vector<Fr>* src[3] = {&l0, &ll, &lb};
   for (int t = 0; t < 3; t++) {
     ZK_TRY(h2d(ctx, tmp, src[t]->data(), n * 32));
-    ZK_TRY(amdzk_lagrange_to_coeff_dev(ctx, pk->dom, tmp, 1, n));
-    ZK_TRY(zk_coeff_to_cosets_r261(ctx, pk->dom, tmp, n, dst[t], ext, 1));
+    ZK_TRY(amdzk_lagrange_to_coeff_dev(ctx, K.dom, tmp, 1, n));
+    ZK_TRY(zk_coeff_to_cosets_r261(ctx, K.dom, tmp, n, dst[t], ext, 1));
     ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
   }
-  for (uint32_t c = 0; c < pk->nc; c++) {
-    cur = zk_quotient_coset_g(pk->dom, c);
+  for (uint32_t c = 0; c < K.nc; c++) {
+    cur = zk_quotient_coset_g(K.dom, c);
     for (int i = 0; i < 5; i++) cur = add(cur, cur);  // 32 * g_c * omega^i: the points of coset c in radix 2^261
     for (size_t i = 0; i < n; i++) {
       xc[(size_t)c * n + i] = cur;
-      cur = mul(cur, pk->omega);
+      cur = mul(cur, K.omega);
     }
   }
-  ZK_TRY(h2d(ctx, pk->x_coset, xc.data(), ext * 32));
+  ZK_TRY(h2d(ctx, K.x_coset, xc.data(), ext * 32));
   ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
   // the identity permutation: delta^j * omega^i (Lagrange) and delta^j * X on the cosets (same radix as x_coset)
   Fr dj = Fr::one();
   const Fr delta = fr_delta();
-  for (uint32_t j = 0; j < pk->S; j++) {
-    ZK_TRY(d2d(ctx, pk->dxw_lag + (size_t)j * n, pk->omega_pow, n * 32));
-    ZK_TRY(d2d(ctx, pk->dx_coset + (size_t)j * ext, pk->x_coset, ext * 32));
+  for (uint32_t j = 0; j < K.S; j++) {
+    ZK_TRY(d2d(ctx, K.dxw_lag + (size_t)j * n, K.omega_pow, n * 32));
+    ZK_TRY(d2d(ctx, K.dx_coset + (size_t)j * ext, K.x_coset, ext * 32));
     if (j) {
-      ZK_TRY(zk_scale(ctx, pk->dxw_lag + (size_t)j * n, n, dj));
-      ZK_TRY(zk_scale(ctx, pk->dx_coset + (size_t)j * ext, ext, dj));
+      ZK_TRY(zk_scale(ctx, K.dxw_lag + (size_t)j * n, n, dj));
+      ZK_TRY(zk_scale(ctx, K.dx_coset + (size_t)j * ext, ext, dj));
     }
     dj = mul(dj, delta);
   }
@@ -391,31 +396,31 @@ static int build_domain_columns(amdzk_ctx* ctx, amdzk_pk* pk) {
   return AMDZK_OK;
 }
 
-// The fixed columns: Lagrange values as given, coefficients, cosets, commitments. vk_only: the Lagrange values (the one
-// buffer the key then has to have) and the commitments.
-int load_fixed_columns(amdzk_ctx* ctx, amdzk_pk* pk, const void* fixed_values, bool vk_only) {
-  const size_t n = pk->n;
-  const uint32_t F = pk->F;
+// The fixed columns: Lagrange values as given, coefficients and cosets where the material has them (a verifying key's
+// has the Lagrange values alone), commitments.
+int load_fixed_columns(amdzk_ctx* ctx, KeyMaterial& K, const void* fixed_values) {
+  const size_t n = K.n;
+  const uint32_t F = K.F;
   if (!F) return AMDZK_OK;
   if (!fixed_values) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: fixed_values is null");
-  ZK_TRY(h2d(ctx, pk->fixed_lag, fixed_values, (size_t)F * n * 32));
-  if (!vk_only) {
-    ZK_TRY(d2d(ctx, pk->fixed_poly, pk->fixed_lag, (size_t)F * n * 32));
-    ZK_TRY(amdzk_lagrange_to_coeff_dev(ctx, pk->dom, pk->fixed_poly, F, n));
-    ZK_TRY(zk_coeff_to_cosets_r261(ctx, pk->dom, pk->fixed_poly, n, pk->fixed_coset, pk->ext, F));
+  ZK_TRY(h2d(ctx, K.fixed_lag, fixed_values, (size_t)F * n * 32));
+  if (K.fixed_poly) {
+    ZK_TRY(d2d(ctx, K.fixed_poly, K.fixed_lag, (size_t)F * n * 32));
+    ZK_TRY(amdzk_lagrange_to_coeff_dev(ctx, K.dom, K.fixed_poly, F, n));
+    ZK_TRY(zk_coeff_to_cosets_r261(ctx, K.dom, K.fixed_poly, n, K.fixed_coset, K.ext, F));
   }
-  return commit_cols(ctx, pk, AMDZK_BASIS_G_LAGRANGE, pk->fixed_lag, F, pk->fixed_commitments);
+  return commit_cols(ctx, K, AMDZK_BASIS_G_LAGRANGE, K.fixed_lag, F, K.fixed_commitments);
 }
 
-// The permutation columns: their Lagrange values from the mapping or as given, then what both routes share. vk_only: as
-// for the fixed columns.
-int load_sigma_columns(amdzk_ctx* ctx, amdzk_pk* pk, const uint32_t* perm_mapping, const void* sigma_values, bool from_sigma, bool vk_only) {
-  const size_t n = pk->n;
-  const uint32_t S = pk->S;
+// The permutation columns: their Lagrange values from the mapping or as given, then what both routes share, as for the
+// fixed columns.
+int load_sigma_columns(amdzk_ctx* ctx, KeyMaterial& K, const uint32_t* perm_mapping, const void* sigma_values, bool from_sigma) {
+  const size_t n = K.n;
+  const uint32_t S = K.S;
   if (!S) return AMDZK_OK;
   if (from_sigma) {
     if (!sigma_values) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: sigma_values is null");
-    ZK_TRY(h2d(ctx, pk->sigma_lag, sigma_values, (size_t)S * n * 32));
+    ZK_TRY(h2d(ctx, K.sigma_lag, sigma_values, (size_t)S * n * 32));
     ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
   } else {
     if (!perm_mapping) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: perm_mapping is null");
@@ -429,7 +434,7 @@ int load_sigma_columns(amdzk_ctx* ctx, amdzk_pk* pk, const uint32_t* perm_mappin
     cur = Fr::one();
     for (size_t i = 0; i < n; i++) {
       op[i] = cur;
-      cur = mul(cur, pk->omega);
+      cur = mul(cur, K.omega);
     }
     for (uint32_t i = 0; i < S; i++)
       for (size_t j = 0; j < n; j++) {
@@ -437,22 +442,22 @@ int load_sigma_columns(amdzk_ctx* ctx, amdzk_pk* pk, const uint32_t* perm_mappin
         if (pi >= S || pj >= n) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen: permutation mapping out of range");
         sig[(size_t)i * n + j] = mul(dpow[pi], op[pj]);
       }
-    ZK_TRY(h2d(ctx, pk->sigma_lag, sig.data(), (size_t)S * n * 32));
+    ZK_TRY(h2d(ctx, K.sigma_lag, sig.data(), (size_t)S * n * 32));
     ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
   }
-  if (!vk_only) {
-    ZK_TRY(d2d(ctx, pk->sigma_poly, pk->sigma_lag, (size_t)S * n * 32));
-    ZK_TRY(amdzk_lagrange_to_coeff_dev(ctx, pk->dom, pk->sigma_poly, S, n));
-    ZK_TRY(zk_coeff_to_cosets_r261(ctx, pk->dom, pk->sigma_poly, n, pk->sigma_coset, pk->ext, S));
+  if (K.sigma_poly) {
+    ZK_TRY(d2d(ctx, K.sigma_poly, K.sigma_lag, (size_t)S * n * 32));
+    ZK_TRY(amdzk_lagrange_to_coeff_dev(ctx, K.dom, K.sigma_poly, S, n));
+    ZK_TRY(zk_coeff_to_cosets_r261(ctx, K.dom, K.sigma_poly, n, K.sigma_coset, K.ext, S));
   }
-  return commit_cols(ctx, pk, AMDZK_BASIS_G_LAGRANGE, pk->sigma_lag, S, pk->perm_commitments);
+  return commit_cols(ctx, K, AMDZK_BASIS_G_LAGRANGE, K.sigma_lag, S, K.perm_commitments);
 }
 
-// The cells that can change a permutation product (amdzk_pk::perm_rank / perm_off / perm_list), from the sigma columns
+// The cells that can change a permutation product (KeyMaterial::perm_rank / perm_off / perm_list), from the sigma columns
 // against the identity permutation's, on the device: flags, one scan per set, the sets' totals to the host for the
 // offsets, compaction. Every maker of a key comes through here, so a key read from a file or built from sigma has them too.
-static int build_perm_lists(amdzk_ctx* ctx, amdzk_pk* pk) {
-  const uint32_t S = pk->S, ns = pk->nsets, u = (uint32_t)(pk->n - pk->bf - 1);
+static int build_perm_lists(amdzk_ctx* ctx, KeyMaterial& K) {
+  const uint32_t S = K.S, ns = K.nsets, u = (uint32_t)(K.n - K.bf - 1);
   if (!S) return AMDZK_OK;
   const size_t cells = (size_t)ns * (u + 1);
   uint32_t* flags = nullptr;  // only needed here
@@ -465,22 +470,22 @@ static int build_perm_lists(amdzk_ctx* ctx, amdzk_pk* pk) {
       hipFree(p);
     }
   } guard{ctx, flags};
-  ZK_TRY(dalloc(ctx, pk, &pk->perm_rank, cells));
-  ZK_TRY(dalloc(ctx, pk, &pk->perm_off, (size_t)ns + 1));
-  ZK_TRY(zk_perm_rank(ctx, pk->sigma_lag, pk->dxw_lag, pk->n, u, S, pk->chunk, ns, flags, pk->perm_rank));
+  ZK_TRY(dalloc(ctx, &K, &K.perm_rank, cells));
+  ZK_TRY(dalloc(ctx, &K, &K.perm_off, (size_t)ns + 1));
+  ZK_TRY(zk_perm_rank(ctx, K.sigma_lag, K.dxw_lag, K.n, u, S, K.chunk, ns, flags, K.perm_rank));
   std::vector<uint32_t> off((size_t)ns + 1, 0);  // the sets' totals (rank[s][u]), then their running sum
-  ZK_HIP(ctx, hipMemcpy2DAsync(off.data() + 1, sizeof(uint32_t), pk->perm_rank + u, ((size_t)u + 1) * sizeof(uint32_t), sizeof(uint32_t), ns,
+  ZK_HIP(ctx, hipMemcpy2DAsync(off.data() + 1, sizeof(uint32_t), K.perm_rank + u, ((size_t)u + 1) * sizeof(uint32_t), sizeof(uint32_t), ns,
                                hipMemcpyDeviceToHost, ctx->stream));
   ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
   for (uint32_t s = 0; s < ns; s++) off[s + 1] += off[s];
-  pk->perm_m = off[ns];
+  K.perm_m = off[ns];
   // Per listed cell the sparse route costs about what the dense one costs per row: it runs up to half the cells. Its
   // arrays (m + 1 numerators and as many denominators) live in the dense route's fraction columns, ns * n elements.
-  pk->perm_sparse = 2 * pk->perm_m <= (size_t)ns * u && 2 * (pk->perm_m + 1) <= (size_t)ns * pk->n;
-  ZK_TRY(h2d(ctx, pk->perm_off, off.data(), off.size() * sizeof(uint32_t)));
-  if (pk->perm_sparse) {
-    ZK_TRY(dalloc(ctx, pk, &pk->perm_list, pk->perm_m));
-    ZK_TRY(zk_perm_compact(ctx, flags, pk->perm_rank, pk->perm_off, u, ns, pk->perm_list));
+  K.perm_sparse = 2 * K.perm_m <= (size_t)ns * u && 2 * (K.perm_m + 1) <= (size_t)ns * K.n;
+  ZK_TRY(h2d(ctx, K.perm_off, off.data(), off.size() * sizeof(uint32_t)));
+  if (K.perm_sparse) {
+    ZK_TRY(dalloc(ctx, &K, &K.perm_list, K.perm_m));
+    ZK_TRY(zk_perm_compact(ctx, flags, K.perm_rank, K.perm_off, u, ns, K.perm_list));
   }
   ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));  // `off` is a host temporary
   return AMDZK_OK;
@@ -489,48 +494,48 @@ static int build_perm_lists(amdzk_ctx* ctx, amdzk_pk* pk) {
 // ---- the four programs of a key. A column operand is slot << 8 | index into the key's rotation table; fixed, advice and
 // instance columns have the same slot in the Lagrange and in the extended table.
 static uint32_t COL(uint32_t slot, uint32_t r) { return (slot << 8) | r; }
-static uint32_t perm_col_slot(amdzk_pk* pk, uint32_t j) {
-  const std::pair<int, int> kc = pk->perm_cols[j];
-  return kc.first == 0 ? pk->sl_adv(kc.second) : kc.first == 1 ? pk->sl_fixed(kc.second) : pk->sl_inst(kc.second);
+static uint32_t perm_col_slot(const KeyMaterial& K, uint32_t j) {
+  const std::pair<int, int> kc = K.perm_cols[j];
+  return kc.first == 0 ? K.sl_adv(kc.second) : kc.first == 1 ? K.sl_fixed(kc.second) : K.sl_inst(kc.second);
 }
 // w_j = (v_j + gamma) / beta of the permutation columns lo <= j < hi, one after the other onto the stack
-static void emit_perm_w(amdzk_pk* pk, Program& pr, uint32_t lo, uint32_t hi) {
+static void emit_perm_w(KeyMaterial& K, ProgramText& pr, uint32_t lo, uint32_t hi) {
   for (uint32_t j = lo; j < hi; j++) {
-    pr.op(OP_PUSH_COL, COL(perm_col_slot(pk, j), pk->rots.index(0)));
+    pr.op(OP_PUSH_COL, COL(perm_col_slot(K, j), K.rots.index(0)));
     pr.push();
-    pr.op(OP_ADD_CONST, pk->c_gamma);
-    pr.op(OP_MUL_CONST, pk->c_betainv);
+    pr.op(OP_ADD_CONST, K.c_gamma);
+    pr.op(OP_MUL_CONST, K.c_betainv);
   }
 }
 
 // (1) lookup compression: ci[l], ct[l]. Leading lookups whose table is one expression over fixed columns and constants
-// (amdzk_pk::lk_const) get ct[l] once, in build_constant_tables.
-static int emit_compress_program(amdzk_ctx* ctx, amdzk_pk* pk) {
-  Program& pr = pk->prog_compress;
-  const uint32_t L = pk->L;
-  uint32_t e = pk->num_gates;
+// (KeyMaterial::lk_const) get ct[l] once, in build_constant_tables.
+static int emit_compress_program(amdzk_ctx* ctx, KeyMaterial& K) {
+  ProgramText& pr = K.prog_compress;
+  const uint32_t L = K.L;
+  uint32_t e = K.num_gates;
   for (uint32_t l = 0; l < L && !getenv("AMDZK_NO_TABLE_CACHE"); l++) {
-    const uint32_t ni = pk->lookup_shape[l].first, nt = pk->lookup_shape[l].second;
+    const uint32_t ni = K.lookup_shape[l].first, nt = K.lookup_shape[l].second;
     bool constant = nt == 1;
     if (constant)
-      for (uint32_t w : pk->exprs[e + ni]) constant = constant && (w >> 24) != XOP_ADVICE && (w >> 24) != XOP_INSTANCE && (w >> 24) != XOP_CHALLENGE;
+      for (uint32_t w : K.exprs[e + ni]) constant = constant && (w >> 24) != XOP_ADVICE && (w >> 24) != XOP_INSTANCE && (w >> 24) != XOP_CHALLENGE;
     if (!constant) break;
-    pk->lk_const++;
+    K.lk_const++;
     e += ni + nt;
   }
-  e = pk->num_gates;
+  e = K.num_gates;
   for (uint32_t l = 0; l < L; l++) {
     pr.piece();
-    ZK_TRY(emit_compressed(ctx, pk, pr, e, pk->lookup_shape[l].first));
+    ZK_TRY(emit_compressed(ctx, K, pr, e, K.lookup_shape[l].first));
     pr.op(OP_STORE, 2 * l);
     pr.pop();
-    e += pk->lookup_shape[l].first;
-    if (l >= pk->lk_const) {
-      ZK_TRY(emit_compressed(ctx, pk, pr, e, pk->lookup_shape[l].second));
+    e += K.lookup_shape[l].first;
+    if (l >= K.lk_const) {
+      ZK_TRY(emit_compressed(ctx, K, pr, e, K.lookup_shape[l].second));
       pr.op(OP_STORE, 2 * l + 1);
       pr.pop();
     }
-    e += pk->lookup_shape[l].second;
+    e += K.lookup_shape[l].second;
   }
   return AMDZK_OK;
 }
@@ -538,19 +543,19 @@ static int emit_compress_program(amdzk_ctx* ctx, amdzk_pk* pk) {
 // (2) permutation fractions: den[s] -> frac column s (inverted later), num[s] -> zp column s. Per set: the columns'
 // w_j = (v_j + gamma) / beta stay on the stack and serve both products, prod_j (sigma_j + w_j) and
 // prod_j (delta^j omega^row + w_j); the common factor beta^m of numerator and denominator cancels in num / den.
-static void emit_pfrac_program(amdzk_pk* pk) {
-  Program& pr = pk->prog_pfrac;
-  const uint32_t r0 = pk->rots.index(0);
-  for (uint32_t s = 0; s < pk->nsets; s++) {
-    const uint32_t lo = s * pk->chunk, hi = std::min(pk->S, lo + pk->chunk), m = hi - lo;
+static void emit_pfrac_program(KeyMaterial& K) {
+  ProgramText& pr = K.prog_pfrac;
+  const uint32_t r0 = K.rots.index(0);
+  for (uint32_t s = 0; s < K.nsets; s++) {
+    const uint32_t lo = s * K.chunk, hi = std::min(K.S, lo + K.chunk), m = hi - lo;
     pr.piece();
-    emit_perm_w(pk, pr, lo, hi);
+    emit_perm_w(K, pr, lo, hi);
     for (int side = 0; side < 2; side++) {  // 0: denominator (sigma columns), 1: numerator (identity-permutation columns)
       for (uint32_t j = lo; j < hi; j++) {
         // the stack holds the m values w, then (from the second factor on) the running product
         pr.op(OP_PICK, j == lo ? m - 1 : m - (j - lo));
         pr.push();
-        pr.op(OP_ADD_COL, COL(side == 0 ? pk->sl_sigma(j) : pk->sl_dxw(j), r0));
+        pr.op(OP_ADD_COL, COL(side == 0 ? K.sl_sigma(j) : K.sl_dxw(j), r0));
         if (j > lo) {
           pr.op(OP_MUL);
           pr.pop();
@@ -567,27 +572,27 @@ static void emit_pfrac_program(amdzk_pk* pk) {
 }
 
 // (3) lookup fractions: den = (a'+beta)(s'+gamma) -> frac2[l]; num = (ci+beta)(ct+gamma) -> zl[l]
-static void emit_lfrac_program(amdzk_pk* pk) {
-  Program& pr = pk->prog_lfrac;
-  const uint32_t r0 = pk->rots.index(0);
-  for (uint32_t l = 0; l < pk->L; l++) {
+static void emit_lfrac_program(KeyMaterial& K) {
+  ProgramText& pr = K.prog_lfrac;
+  const uint32_t r0 = K.rots.index(0);
+  for (uint32_t l = 0; l < K.L; l++) {
     pr.piece();
-    pr.op(OP_PUSH_COL, COL(pk->sl_la(l), r0));
+    pr.op(OP_PUSH_COL, COL(K.sl_la(l), r0));
     pr.push();
-    pr.op(OP_ADD_CONST, pk->c_beta);
-    pr.op(OP_PUSH_COL, COL(pk->sl_ls(l), r0));
+    pr.op(OP_ADD_CONST, K.c_beta);
+    pr.op(OP_PUSH_COL, COL(K.sl_ls(l), r0));
     pr.push();
-    pr.op(OP_ADD_CONST, pk->c_gamma);
+    pr.op(OP_ADD_CONST, K.c_gamma);
     pr.op(OP_MUL);
     pr.pop();
     pr.op(OP_STORE, 2 * l);
     pr.pop();
-    pr.op(OP_PUSH_COL, COL(pk->sl_ci(l), r0));
+    pr.op(OP_PUSH_COL, COL(K.sl_ci(l), r0));
     pr.push();
-    pr.op(OP_ADD_CONST, pk->c_beta);
-    pr.op(OP_PUSH_COL, COL(pk->sl_ct(l), r0));
+    pr.op(OP_ADD_CONST, K.c_beta);
+    pr.op(OP_PUSH_COL, COL(K.sl_ct(l), r0));
     pr.push();
-    pr.op(OP_ADD_CONST, pk->c_gamma);
+    pr.op(OP_ADD_CONST, K.c_gamma);
     pr.op(OP_MUL);
     pr.pop();
     pr.op(OP_STORE, 2 * l + 1);
@@ -597,32 +602,32 @@ static void emit_lfrac_program(amdzk_pk* pk) {
 
 // (4) the h(X) numerator: gates, permutation, lookups — evaluation.rs evaluate_h order — then the pass that readies it
 // for the limb-resident interpreter and cuts it into pieces.
-static int emit_h_program(amdzk_ctx* ctx, amdzk_pk* pk) {
-  Program& pr = pk->prog_h;
-  const uint32_t S = pk->S, L = pk->L, ns = pk->nsets;
-  const uint32_t r0 = pk->rots.index(0), r1 = pk->rots.index(1), rm1 = pk->rots.index(-1), rlast = pk->rots.index(-(int32_t)(pk->bf + 1));
+static int emit_h_program(amdzk_ctx* ctx, KeyMaterial& K) {
+  ProgramText& pr = K.prog_h;
+  const uint32_t S = K.S, L = K.L, ns = K.nsets;
+  const uint32_t r0 = K.rots.index(0), r1 = K.rots.index(1), rm1 = K.rots.index(-1), rlast = K.rots.index(-(int32_t)(K.bf + 1));
   pr.uses_hot = true;
-  for (uint32_t g = 0; g < pk->num_gates; g++) {
-    ZK_TRY(emit_expr(ctx, pk, pr, pk->exprs[g]));
+  for (uint32_t g = 0; g < K.num_gates; g++) {
+    ZK_TRY(emit_expr(ctx, K, &K.rots, pr, K.exprs[g]));
     pr.op(OP_ACC);
     pr.pop();
   }
   if (ns > 0) {
     // l_0 * (1 - z_0)
-    pr.op(OP_PUSH_CONST, pk->c_one); pr.push();
-    pr.op(OP_SUB_COL, COL(pk->se_zp(0), r0));
+    pr.op(OP_PUSH_CONST, K.c_one); pr.push();
+    pr.op(OP_SUB_COL, COL(K.se_zp(0), r0));
     pr.op(OP_MUL_HOT, 0);
     pr.op(OP_ACC); pr.pop();
     // l_last * (z_l^2 - z_l)
-    pr.op(OP_PUSH_COL, COL(pk->se_zp(ns - 1), r0)); pr.push();
+    pr.op(OP_PUSH_COL, COL(K.se_zp(ns - 1), r0)); pr.push();
     pr.op(OP_SQR);
-    pr.op(OP_SUB_COL, COL(pk->se_zp(ns - 1), r0));
+    pr.op(OP_SUB_COL, COL(K.se_zp(ns - 1), r0));
     pr.op(OP_MUL_HOT, 1);
     pr.op(OP_ACC); pr.pop();
     // l_0 * (z_i - z_{i-1}(omega^last X))
     for (uint32_t s = 1; s < ns; s++) {
-      pr.op(OP_PUSH_COL, COL(pk->se_zp(s), r0)); pr.push();
-      pr.op(OP_SUB_COL, COL(pk->se_zp(s - 1), rlast));
+      pr.op(OP_PUSH_COL, COL(K.se_zp(s), r0)); pr.push();
+      pr.op(OP_SUB_COL, COL(K.se_zp(s - 1), rlast));
       pr.op(OP_MUL_HOT, 0);
       pr.op(OP_ACC); pr.pop();
     }
@@ -631,18 +636,18 @@ static int emit_h_program(amdzk_ctx* ctx, amdzk_pk* pk) {
     // the w_j stay on the stack for both products (one product per column instead of two), delta^j X is a key column,
     // and beta^m goes into the term's power of y (h_term_beta_pow, upload_ypow)
     for (uint32_t s = 0; s < ns; s++) {
-      const uint32_t lo = s * pk->chunk, hi = std::min(S, lo + pk->chunk), m = hi - lo;
-      emit_perm_w(pk, pr, lo, hi);
-      pr.op(OP_PUSH_COL, COL(pk->se_zp(s), r1)); pr.push();
+      const uint32_t lo = s * K.chunk, hi = std::min(S, lo + K.chunk), m = hi - lo;
+      emit_perm_w(K, pr, lo, hi);
+      pr.op(OP_PUSH_COL, COL(K.se_zp(s), r1)); pr.push();
       for (uint32_t j = lo; j < hi; j++) {
         pr.op(OP_PICK, m - (j - lo)); pr.push();
-        pr.op(OP_ADD_COL, COL(pk->se_sigma(j), r0));
+        pr.op(OP_ADD_COL, COL(K.se_sigma(j), r0));
         pr.op(OP_MUL); pr.pop();
       }
-      pr.op(OP_PUSH_COL, COL(pk->se_zp(s), r0)); pr.push();
+      pr.op(OP_PUSH_COL, COL(K.se_zp(s), r0)); pr.push();
       for (uint32_t j = lo; j < hi; j++) {
         pr.op(OP_PICK, 1 + m - (j - lo)); pr.push();
-        pr.op(OP_ADD_COL, COL(pk->se_dx(j), r0));
+        pr.op(OP_ADD_COL, COL(K.se_dx(j), r0));
         pr.op(OP_MUL); pr.pop();
       }
       pr.op(OP_SUB); pr.pop();
@@ -652,48 +657,48 @@ static int emit_h_program(amdzk_ctx* ctx, amdzk_pk* pk) {
       pr.op(OP_ACC); pr.pop();
     }
   }
-  uint32_t e = pk->num_gates;
+  uint32_t e = K.num_gates;
   for (uint32_t l = 0; l < L; l++) {
-    const uint32_t ni = pk->lookup_shape[l].first, nt = pk->lookup_shape[l].second;
+    const uint32_t ni = K.lookup_shape[l].first, nt = K.lookup_shape[l].second;
     // l_0 * (1 - z)
-    pr.op(OP_PUSH_CONST, pk->c_one); pr.push();
-    pr.op(OP_SUB_COL, COL(pk->se_zl(l), r0));
+    pr.op(OP_PUSH_CONST, K.c_one); pr.push();
+    pr.op(OP_SUB_COL, COL(K.se_zl(l), r0));
     pr.op(OP_MUL_HOT, 0);
     pr.op(OP_ACC); pr.pop();
     // l_last * (z^2 - z)
-    pr.op(OP_PUSH_COL, COL(pk->se_zl(l), r0)); pr.push();
+    pr.op(OP_PUSH_COL, COL(K.se_zl(l), r0)); pr.push();
     pr.op(OP_SQR);
-    pr.op(OP_SUB_COL, COL(pk->se_zl(l), r0));
+    pr.op(OP_SUB_COL, COL(K.se_zl(l), r0));
     pr.op(OP_MUL_HOT, 1);
     pr.op(OP_ACC); pr.pop();
     // l_active * (z(wX)(a'+beta)(s'+gamma) - z(X)(ci+beta)(ct+gamma))
-    pr.op(OP_PUSH_COL, COL(pk->se_zl(l), r1)); pr.push();
-    pr.op(OP_PUSH_COL, COL(pk->se_la(l), r0)); pr.push();
-    pr.op(OP_ADD_CONST, pk->c_beta);
+    pr.op(OP_PUSH_COL, COL(K.se_zl(l), r1)); pr.push();
+    pr.op(OP_PUSH_COL, COL(K.se_la(l), r0)); pr.push();
+    pr.op(OP_ADD_CONST, K.c_beta);
     pr.op(OP_MUL); pr.pop();
-    pr.op(OP_PUSH_COL, COL(pk->se_ls(l), r0)); pr.push();
-    pr.op(OP_ADD_CONST, pk->c_gamma);
+    pr.op(OP_PUSH_COL, COL(K.se_ls(l), r0)); pr.push();
+    pr.op(OP_ADD_CONST, K.c_gamma);
     pr.op(OP_MUL); pr.pop();
-    pr.op(OP_PUSH_COL, COL(pk->se_zl(l), r0)); pr.push();
-    ZK_TRY(emit_compressed(ctx, pk, pr, e, ni));
-    pr.op(OP_ADD_CONST, pk->c_beta);
+    pr.op(OP_PUSH_COL, COL(K.se_zl(l), r0)); pr.push();
+    ZK_TRY(emit_compressed(ctx, K, pr, e, ni));
+    pr.op(OP_ADD_CONST, K.c_beta);
     pr.op(OP_MUL); pr.pop();
-    ZK_TRY(emit_compressed(ctx, pk, pr, e + ni, nt));
-    pr.op(OP_ADD_CONST, pk->c_gamma);
+    ZK_TRY(emit_compressed(ctx, K, pr, e + ni, nt));
+    pr.op(OP_ADD_CONST, K.c_gamma);
     pr.op(OP_MUL); pr.pop();
     pr.op(OP_SUB); pr.pop();
     pr.op(OP_MUL_HOT, 2);
     pr.op(OP_ACC); pr.pop();
     // l_0 * (a' - s')
-    pr.op(OP_PUSH_COL, COL(pk->se_la(l), r0)); pr.push();
-    pr.op(OP_SUB_COL, COL(pk->se_ls(l), r0));
+    pr.op(OP_PUSH_COL, COL(K.se_la(l), r0)); pr.push();
+    pr.op(OP_SUB_COL, COL(K.se_ls(l), r0));
     pr.op(OP_MUL_HOT, 0);
     pr.op(OP_ACC); pr.pop();
     // l_active * (a' - s')(a' - a'(w^-1 X))
-    pr.op(OP_PUSH_COL, COL(pk->se_la(l), r0)); pr.push();
-    pr.op(OP_SUB_COL, COL(pk->se_ls(l), r0));
-    pr.op(OP_PUSH_COL, COL(pk->se_la(l), r0)); pr.push();
-    pr.op(OP_SUB_COL, COL(pk->se_la(l), rm1));
+    pr.op(OP_PUSH_COL, COL(K.se_la(l), r0)); pr.push();
+    pr.op(OP_SUB_COL, COL(K.se_ls(l), r0));
+    pr.op(OP_PUSH_COL, COL(K.se_la(l), r0)); pr.push();
+    pr.op(OP_SUB_COL, COL(K.se_la(l), rm1));
     pr.op(OP_MUL); pr.pop();
     pr.op(OP_MUL_HOT, 2);
     pr.op(OP_ACC); pr.pop();
@@ -707,24 +712,24 @@ static int emit_h_program(amdzk_ctx* ctx, amdzk_pk* pk) {
   const char* env = getenv("AMDZK_H_PARTS");
   uint32_t parts = env ? (uint32_t)atoi(env) : 6u;
   parts = parts < 1 ? 1 : parts > H_PARTS_MAX ? H_PARTS_MAX : parts;
-  pk->h_terms = finalize_limb_program(pr, parts);
-  pk->h_term_beta_pow = pr.term_beta;
+  K.h_terms = finalize_limb_program(pr, parts);
+  K.h_term_beta_pow = pr.term_beta;
   return AMDZK_OK;
 }
 
 // AMDZK_DUMP_PROG, a debugging aid: what the compiled h(X) program is made of
-static void dump_h_program(const amdzk_pk* pk) {
+static void dump_h_program(const KeyMaterial& K) {
   static const char* names[] = {"END", "PUSH_COL", "PUSH_CONST", "ADD", "SUB", "MUL", "NEG", "MUL_CONST", "ADD_CONST", "MUL_COL",
                                 "ADD_COL", "SUB_COL", "ACC", "STORE", "SQR", "PUSH_HOT", "MUL_HOT", "REDUCE", "SUB_BIG", "NEG_BIG",
                                 "WACC", "WFLUSH"};
   std::map<uint32_t, size_t> hist;
   std::map<std::pair<uint32_t, uint32_t>, size_t> pairs;
-  const auto& w = pk->prog_h.words;
+  const auto& w = K.prog_h.words;
   for (size_t i = 0; i < w.size(); i++) {
     hist[w[i] >> 24]++;
     if (i + 1 < w.size()) pairs[{w[i] >> 24, w[i + 1] >> 24}]++;
   }
-  fprintf(stderr, "[amdzk] prog_h: %zu instructions, stack depth %u\n", w.size(), pk->prog_h.depth);
+  fprintf(stderr, "[amdzk] prog_h: %zu instructions, stack depth %u\n", w.size(), K.prog_h.depth);
   for (auto& kv : hist) fprintf(stderr, "[amdzk]   %-10s %zu\n", kv.first < 22 ? names[kv.first] : "?", kv.second);
   auto is_mul = [](uint32_t o) { return o == OP_MUL || o == OP_MUL_CONST || o == OP_MUL_COL || o == OP_MUL_HOT || o == OP_SQR || o == OP_WACC; };
   size_t mm = 0;
@@ -736,46 +741,49 @@ static void dump_h_program(const amdzk_pk* pk) {
   fprintf(stderr, "[amdzk]   products directly followed by a product: %zu\n", mm);
 }
 
-// Constant tables (amdzk_pk::lk_const): ct[l] evaluated here, once, and its canonical, padded, sorted form kept
-static int build_constant_tables(amdzk_ctx* ctx, amdzk_pk* pk) {
-  if (!pk->lk_const) return AMDZK_OK;
-  const size_t n = pk->n;
-  const uint32_t cnt = pk->lk_const, usable = (uint32_t)n - (pk->bf + 1);
-  ZK_TRY(dalloc(ctx, pk, &pk->lk_ts_const, (size_t)cnt * n));
-  Program pr;
-  uint32_t e = pk->num_gates;
+// Constant tables (KeyMaterial::lk_const): ct[l] evaluated here, once, in the handle's workspace, and its canonical, padded,
+// sorted form kept
+static int build_constant_tables(amdzk_ctx* ctx, KeyMaterial& K, amdzk_pk* pk) {
+  if (!K.lk_const) return AMDZK_OK;
+  const size_t n = K.n;
+  const uint32_t cnt = K.lk_const, usable = (uint32_t)n - (K.bf + 1);
+  ZK_TRY(dalloc(ctx, &K, &K.lk_ts_const, (size_t)cnt * n));
+  ProgramText tx;
+  uint32_t e = K.num_gates;
   for (uint32_t l = 0; l < cnt; l++) {
-    pr.piece();
-    ZK_TRY(emit_expr(ctx, pk, pr, pk->exprs[e + pk->lookup_shape[l].first]));
-    pr.op(OP_STORE, 2 * l + 1);
-    pr.pop();
-    e += pk->lookup_shape[l].first + 1;
+    tx.piece();
+    ZK_TRY(emit_expr(ctx, K, &K.rots, tx, K.exprs[e + K.lookup_shape[l].first]));
+    tx.op(OP_STORE, 2 * l + 1);
+    tx.pop();
+    e += K.lookup_shape[l].first + 1;
   }
+  Program pr{&tx};
   ZK_TRY(upload_program(ctx, pk, pr, false));
   ZK_TRY(run_program(ctx, pk, pr, false, pk->d_outs_compress, nullptr, "expr_const_tables"));
-  ZK_TRY(d2d(ctx, pk->lk_ts_const, pk->ct, (size_t)cnt * n * 32));
-  ZK_TRY(amdzk_fr_to_repr_dev(ctx, pk->lk_ts_const, (size_t)cnt * n));
-  ZK_HIP(ctx, hipMemset2DAsync(pk->lk_ts_const + usable, (size_t)n * 32, 0xFF, (size_t)(n - usable) * 32, cnt, ctx->stream));
-  ZK_TRY(zk_sort_keys(ctx, pk->lk_ts_const, cnt, n, n));
+  ZK_TRY(d2d(ctx, K.lk_ts_const, pk->ct, (size_t)cnt * n * 32));
+  ZK_TRY(amdzk_fr_to_repr_dev(ctx, K.lk_ts_const, (size_t)cnt * n));
+  ZK_HIP(ctx, hipMemset2DAsync(K.lk_ts_const + usable, (size_t)n * 32, 0xFF, (size_t)(n - usable) * 32, cnt, ctx->stream));
+  ZK_TRY(zk_sort_keys(ctx, K.lk_ts_const, cnt, n, n));
   ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
   return AMDZK_OK;
 }
 
 // l_active = 1 - (l_last + l_blind) on the cosets: lactive_c holds l_blind's coset (build_domain_columns); a tiny one-off
 // program over the extended table, whose constants bind_workspace has uploaded
-static int finish_l_active(amdzk_ctx* ctx, amdzk_pk* pk) {
-  const uint32_t r0 = pk->rots.index(0);
+static int finish_l_active(amdzk_ctx* ctx, KeyMaterial& K, amdzk_pk* pk) {
+  const uint32_t r0 = K.rots.index(0);
   ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
-  Program pr;
-  pr.op(OP_PUSH_CONST, pk->c_one); pr.push();
-  pr.op(OP_SUB_COL, COL(pk->se_llast(), r0));
-  pr.op(OP_SUB_COL, COL(pk->se_lactive(), r0));
-  pr.op(OP_STORE, 0); pr.pop();
-  (void)finalize_limb_program(pr);
+  ProgramText tx;
+  tx.op(OP_PUSH_CONST, K.c_one); tx.push();
+  tx.op(OP_SUB_COL, COL(K.se_llast(), r0));
+  tx.op(OP_SUB_COL, COL(K.se_lactive(), r0));
+  tx.op(OP_STORE, 0); tx.pop();
+  (void)finalize_limb_program(tx);
+  Program pr{&tx};
   ZK_TRY(upload_program(ctx, pk, pr, true));
   Fr** d_out = nullptr;
   ZK_TRY(dalloc(ctx, pk, &d_out, 1));
-  Fr* tgt = pk->lactive_c;
+  Fr* tgt = K.lactive_c;
   ZK_TRY(h2d(ctx, d_out, &tgt, sizeof(Fr*)));
   ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
   ZK_TRY(run_program(ctx, pk, pr, true, d_out, nullptr, "expr_l_active"));
@@ -798,44 +806,65 @@ static int keygen_common(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circu
   ZK_TRY(check_keygen_args(ctx, srs, c, ph, transcript_repr, flags, out, &nphases));
   PkOwner owner(new amdzk_pk(), PkFree{ctx});
   amdzk_pk* pk = owner.get();
-  ZK_TRY(describe_circuit(ctx, pk, srs, c, ph, nphases, transcript_repr, flags, false));
-  ZK_TRY(alloc_key_material(ctx, pk));
-  ZK_TRY(build_domain_columns(ctx, pk));
-  ZK_TRY(load_fixed_columns(ctx, pk, fixed_values, false));
-  ZK_TRY(load_sigma_columns(ctx, pk, perm_mapping, sigma_values, from_sigma, false));
-  ZK_TRY(build_perm_lists(ctx, pk));
+  // The material under construction: the handle is its one owner from the start (so that a failed step frees both), and
+  // K is the only way to write it. It ends with this function: from here on the material is frozen.
+  KeyMaterial& K = *new KeyMaterial();
+  pk->key.reset(&K);
+  ZK_TRY(describe_circuit(ctx, K, srs, c, ph, nphases, transcript_repr, flags, false));
+  ZK_TRY(alloc_key_material(ctx, K, pk));
+  ZK_TRY(build_domain_columns(ctx, K, pk));
+  ZK_TRY(load_fixed_columns(ctx, K, fixed_values));
+  ZK_TRY(load_sigma_columns(ctx, K, perm_mapping, sigma_values, from_sigma));
+  ZK_TRY(build_perm_lists(ctx, K));
   // rotations 0, 1, -1 and -(bf + 1) open the rotation table of every key, ahead of what its expressions query
-  for (int32_t r : {0, 1, -1, -(int32_t)(pk->bf + 1)}) pk->rots.index(r);
-  ZK_TRY(emit_compress_program(ctx, pk));
-  emit_pfrac_program(pk);
-  emit_lfrac_program(pk);
-  ZK_TRY(emit_h_program(ctx, pk));
-  if (pk->rots.rots.size() > 255) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "keygen: more than 255 distinct rotations");
+  for (int32_t r : {0, 1, -1, -(int32_t)(K.bf + 1)}) K.rots.index(r);
+  ZK_TRY(emit_compress_program(ctx, K));
+  emit_pfrac_program(K);
+  emit_lfrac_program(K);
+  ZK_TRY(emit_h_program(ctx, K));
+  if (K.rots.rots.size() > 255) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "keygen: more than 255 distinct rotations");
   ZK_TRY(bind_workspace(ctx, pk));
-  if (getenv("AMDZK_DUMP_PROG")) dump_h_program(pk);
-  ZK_TRY(build_constant_tables(ctx, pk));
-  ZK_TRY(finish_l_active(ctx, pk));
+  if (getenv("AMDZK_DUMP_PROG")) dump_h_program(K);
+  ZK_TRY(build_constant_tables(ctx, K, pk));
+  ZK_TRY(finish_l_active(ctx, K, pk));
   *out = owner.release();
   return AMDZK_OK;
 }
 
+// The one release of key material: whoever drops the last pointer to it runs this. The domain's free takes a ctx — the
+// one of the call that lets go (amdzk_pk_free, KeyFree), which leaves it here for its own thread.
+static thread_local amdzk_ctx* t_release_ctx = nullptr;
+KeyMaterial::~KeyMaterial() {
+  for (void* p : allocs) hipFree(p);
+  if (chk_shared->d_cells) hipFree(chk_shared->d_cells);
+  if (dom) amdzk_domain_free(t_release_ctx, dom);
+}
+void KeyFree::operator()(KeyMaterial* K) const {
+  if (ctx) zk_host_wait(ctx, ctx->stream);
+  t_release_ctx = ctx;
+  delete K;
+  t_release_ctx = nullptr;
+}
+
 extern "C" {
 
+// The handle's workspace, and the key material if this was its last handle.
 void amdzk_pk_free(amdzk_ctx* ctx, amdzk_pk* pk) {
   ZK_ENTER(ctx);
   if (!pk) return;
   if (ctx) zk_host_wait(ctx, ctx->stream);
   for (void* p : pk->allocs) hipFree(p);
-  if (!pk->clone_of && pk->chk_shared && pk->chk_shared->d_cells) hipFree(pk->chk_shared->d_cells);
   if (pk->pin) hipHostFree(pk->pin);
-  if (pk->dom && !pk->clone_of) amdzk_domain_free(ctx, pk->dom);
+  t_release_ctx = ctx;
   delete pk;
+  t_release_ctx = nullptr;
 }
 
-// Every device allocation of the key (columns, cosets, per-proof workspace) must live on ctx's device.
+// Every device allocation of the handle (per-proof workspace) and of its key (columns, cosets) must live on ctx's device.
 int amdzk_pk_check_affinity(amdzk_ctx* ctx, const amdzk_pk* pk) {
   ZK_ENTER(ctx);
   if (!ctx || !pk) return AMDZK_E_INVALID;
+  for (void* p : pk->key->allocs) ZK_TRY(zk_ptr_on_device(ctx, p, "proving-key buffer"));
   for (void* p : pk->allocs) ZK_TRY(zk_ptr_on_device(ctx, p, "proving-key buffer"));
   return AMDZK_OK;
 }
@@ -870,40 +899,32 @@ int amdzk_keygen_sigma(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit
 // VK material a verifier needs: commitments of the fixed columns and of the permutation polynomials.
 int amdzk_pk_commitments(const amdzk_pk* pk, uint64_t* fixed_out /* F x 8 */, uint64_t* perm_out /* S x 8 */) {
   if (!pk) return AMDZK_E_INVALID;
-  if (fixed_out && pk->F) memcpy(fixed_out, pk->fixed_commitments.data(), (size_t)pk->F * 64);
-  if (perm_out && pk->S) memcpy(perm_out, pk->perm_commitments.data(), (size_t)pk->S * 64);
+  const KeyMaterial& K = *pk->key;
+  if (fixed_out && K.F) memcpy(fixed_out, K.fixed_commitments.data(), (size_t)K.F * 64);
+  if (perm_out && K.S) memcpy(perm_out, K.perm_commitments.data(), (size_t)K.S * 64);
   return AMDZK_OK;
 }
 
-// One more circuit instance's workspace for `src`'s circuit: a key handle that shares src's key material (fixed and
-// permutation columns in all three forms, the domain, the compiled programs' text, constant lookup tables — read-only
-// during proofs) and owns its own per-proof workspace, pointer tables and uploaded programs (their instructions carry
+// One more circuit instance's workspace for `src`'s circuit: a key handle that holds src's key material (fixed and
+// permutation columns in all three forms, the domain, the compiled programs' text, constant lookup tables — const behind
+// every handle) and owns its own per-proof workspace, pointer tables and uploaded programs (their instructions carry
 // absolute column addresses). What amdzk_create_proof_multi takes for its second, third, ... instance — and, since a
 // clone is a complete key for create_proof, the cheap way to keep several proofs of one circuit in flight: a
 // clone costs the workspace (the arenas), not the key (354 + 354 MiB of permutation cosets at the metric's shape).
-// Free it with amdzk_pk_free BEFORE the key it was made from.
+// Free it with amdzk_pk_free; handles of one key are freed in any order, and the last one frees the key material.
 int amdzk_pk_clone_workspace(amdzk_ctx* ctx, const amdzk_pk* src, amdzk_pk** out) {
   ZK_ENTER(ctx);
   if (!ctx) return AMDZK_E_INVALID;
   if (!src || !out) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_clone_workspace: null argument");
-  PkOwner owner(new amdzk_pk(*src), PkFree{ctx});
+  PkOwner owner(new amdzk_pk(), PkFree{ctx});
   amdzk_pk* pk = owner.get();
-  pk->clone_of = src->clone_of ? src->clone_of : src;
-  pk->allocs.clear();
-  pk->pin = nullptr;
-  pk->pin_cap = pk->pin_off = 0;
-  pk->mo = amdzk_pk::Multiopen();
-  pk->mo_multi = amdzk_pk::Multiopen();
-  pk->mo_multi_keys.clear();
-  pk->sets_Q = nullptr;
-  pk->sets_Q_pairs = 0;
-  pk->prog_compress.d_instr = pk->prog_pfrac.d_instr = pk->prog_lfrac.d_instr = pk->prog_h.d_instr = nullptr;
-  pk->chk = amdzk_pk::Check();  // built by the clone's own first check
+  pk->key = src->key;
+  const KeyMaterial& K = *pk->key;
   ZK_TRY(alloc_proof_workspace(ctx, pk));
   ZK_TRY(bind_workspace(ctx, pk));
-  // the compressed constant tables (amdzk_pk::lk_const) are written once, at keygen, into the key's ct columns — the
-  // per-proof compression program skips them — so a new workspace starts with a copy
-  if (pk->lk_const) ZK_TRY(d2d(ctx, pk->ct, src->ct, (size_t)pk->lk_const * pk->n * 32));
+  // the compressed constant tables (KeyMaterial::lk_const) are written once, at keygen, into the workspace's ct columns —
+  // the per-proof compression program skips them — so a new workspace starts with a copy
+  if (K.lk_const) ZK_TRY(d2d(ctx, pk->ct, src->ct, (size_t)K.lk_const * K.n * 32));
   ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
   *out = owner.release();
   return AMDZK_OK;
@@ -917,23 +938,24 @@ int amdzk_pk_inspect(amdzk_ctx* ctx, const amdzk_pk* pk, int what, uint64_t* out
   ZK_ENTER(ctx);
   if (!ctx) return AMDZK_E_INVALID;
   if (!pk || !count) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_inspect: null argument");
+  const KeyMaterial& K = *pk->key;
   const Fr* src = nullptr;
   size_t cnt = 0;
   Fr ch[4];
   if (what == 0) {
     src = pk->PQ;
-    cnt = pk->NP * pk->n;
+    cnt = K.NP * K.n;
   } else if (what == 2) {
     src = pk->hpieces;
-    cnt = (size_t)pk->qdeg * pk->n;
+    cnt = (size_t)K.qdeg * K.n;
   } else if (what == 1) {
-    ch[0] = pk->consts[pk->c_theta];
-    ch[1] = pk->consts[pk->c_beta];
-    ch[2] = pk->consts[pk->c_gamma];
-    ch[3] = pk->consts[pk->c_y];
+    ch[0] = pk->consts[K.c_theta];
+    ch[1] = pk->consts[K.c_beta];
+    ch[2] = pk->consts[K.c_gamma];
+    ch[3] = pk->consts[K.c_y];
     cnt = 4;
   } else if (what == 3) {
-    cnt = pk->num_challenges;
+    cnt = K.num_challenges;
   } else {
     ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_inspect: unknown selector %d", what);
   }
@@ -941,21 +963,22 @@ int amdzk_pk_inspect(amdzk_ctx* ctx, const amdzk_pk* pk, int what, uint64_t* out
   if (!out) return AMDZK_OK;
   if (cap < cnt) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_inspect: buffer holds %zu elements, %zu needed", cap, cnt);
   if (what == 1) memcpy(out, ch, sizeof(ch));
-  else if (what == 3) memcpy(out, pk->consts.data() + pk->c_chal0, cnt * 32);
+  else if (what == 3) memcpy(out, pk->consts.data() + K.c_chal0, cnt * 32);
   else ZK_TRY(d2h(ctx, out, src, cnt * 32));
   return AMDZK_OK;
 }
 
 // The key's own columns, for a fork whose ProvingKey::write stores a key that was made on the device: what = 0 the fixed
-// columns (Lagrange), 1 the sigma columns (Lagrange), 2 / 3 the same as coefficients. A workspace clone shares these
-// buffers with its root key, so it returns the root's columns.
+// columns (Lagrange), 1 the sigma columns (Lagrange), 2 / 3 the same as coefficients: key material, the same through
+// every handle of the key.
 int amdzk_pk_export(amdzk_ctx* ctx, const amdzk_pk* pk, int what, uint64_t* out, size_t cap, size_t* count) {
   ZK_ENTER(ctx);
   if (!ctx) return AMDZK_E_INVALID;
   if (!pk || !count) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_export: null argument");
+  const KeyMaterial& K = *pk->key;
   if (what < 0 || what > 3) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_export: unknown selector %d", what);
-  const Fr* src[4] = {pk->fixed_lag, pk->sigma_lag, pk->fixed_poly, pk->sigma_poly};
-  const size_t cnt = (size_t)((what & 1) ? pk->S : pk->F) * pk->n;
+  const Fr* src[4] = {K.fixed_lag, K.sigma_lag, K.fixed_poly, K.sigma_poly};
+  const size_t cnt = (size_t)((what & 1) ? K.S : K.F) * K.n;
   *count = cnt;
   if (!out) return AMDZK_OK;
   if (cap < cnt) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_export: buffer holds %zu elements, %zu needed", cap, cnt);
@@ -966,14 +989,15 @@ int amdzk_pk_export(amdzk_ctx* ctx, const amdzk_pk* pk, int what, uint64_t* out,
 // keygen takes a circuit on trust where pkblob::validate() does not (a query that no expression uses may name any column,
 // for one): such a key proves, but its file would be refused by amdzk_pk_read, so it is not written at all.
 size_t amdzk_pk_serialized_size(const amdzk_pk* pk) {
-  return pk && pk->src_desc && pkblob::validate(*pk->src_desc, nullptr) == AMDZK_OK ? pk->src_desc->serialized_size() : 0;
+  return pk && pk->key->src_desc && pkblob::validate(*pk->key->src_desc, nullptr) == AMDZK_OK ? pk->key->src_desc->serialized_size() : 0;
 }
 
 int amdzk_pk_write(amdzk_ctx* ctx, const amdzk_pk* pk, uint8_t* out, size_t cap, size_t* written) {
   ZK_ENTER(ctx);
   if (!ctx) return AMDZK_E_INVALID;
-  if (!pk || !pk->src_desc || (!out && !written)) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_write: null argument");
-  const pkblob::Desc& d = *pk->src_desc;
+  if (!pk || !pk->key->src_desc || (!out && !written)) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_write: null argument");
+  const KeyMaterial& K = *pk->key;
+  const pkblob::Desc& d = *K.src_desc;
   std::string why;
   if (pkblob::validate(d, &why) != AMDZK_OK)
     ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_write: amdzk_pk_read would refuse this key's circuit (%s)", why.c_str());
@@ -983,16 +1007,16 @@ int amdzk_pk_write(amdzk_ctx* ctx, const amdzk_pk* pk, uint8_t* out, size_t cap,
   if (cap < need) ZK_FAIL(ctx, AMDZK_E_INVALID, "pk_write: buffer holds %zu bytes, %zu needed", cap, need);
   d.write_header(out);
   uint8_t* p = out + d.header_bytes();
-  memcpy(p, pk->transcript_repr.l, 32);
+  memcpy(p, K.transcript_repr.l, 32);
   p += 32;
-  if (pk->F) memcpy(p, pk->fixed_commitments.data(), (size_t)pk->F * 64);
-  p += (size_t)pk->F * 64;
-  if (pk->S) memcpy(p, pk->perm_commitments.data(), (size_t)pk->S * 64);
-  p += (size_t)pk->S * 64;
-  ZK_TRY(d2h(ctx, p, pk->fixed_lag, (size_t)pk->F * pk->n * 32));
-  p += (size_t)pk->F * pk->n * 32;
-  ZK_TRY(d2h(ctx, p, pk->sigma_lag, (size_t)pk->S * pk->n * 32));
-  p += (size_t)pk->S * pk->n * 32;
+  if (K.F) memcpy(p, K.fixed_commitments.data(), (size_t)K.F * 64);
+  p += (size_t)K.F * 64;
+  if (K.S) memcpy(p, K.perm_commitments.data(), (size_t)K.S * 64);
+  p += (size_t)K.S * 64;
+  ZK_TRY(d2h(ctx, p, K.fixed_lag, (size_t)K.F * K.n * 32));
+  p += (size_t)K.F * K.n * 32;
+  ZK_TRY(d2h(ctx, p, K.sigma_lag, (size_t)K.S * K.n * 32));
+  p += (size_t)K.S * K.n * 32;
   pkblob::digest(out, (size_t)(p - out), p);
   return AMDZK_OK;
 }
@@ -1046,8 +1070,9 @@ int amdzk_pk_read(amdzk_ctx* ctx, const amdzk_srs* srs, const uint8_t* data, siz
     if (rc == AMDZK_E_INVALID) ctx->err = "pk_read: " + ctx->err;
     return rc;
   }
-  const bool same = (!pk->F || memcmp(pk->fixed_commitments.data(), data + lay.fixed_commitments, (size_t)pk->F * 64) == 0) &&
-                    (!pk->S || memcmp(pk->perm_commitments.data(), data + lay.perm_commitments, (size_t)pk->S * 64) == 0);
+  const KeyMaterial& K = *pk->key;
+  const bool same = (!K.F || memcmp(K.fixed_commitments.data(), data + lay.fixed_commitments, (size_t)K.F * 64) == 0) &&
+                    (!K.S || memcmp(K.perm_commitments.data(), data + lay.perm_commitments, (size_t)K.S * 64) == 0);
   if (!same) {
     amdzk_pk_free(ctx, pk);
     ZK_FAIL(ctx, AMDZK_E_INVALID,

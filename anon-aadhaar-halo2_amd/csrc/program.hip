@@ -22,15 +22,20 @@ struct ENode {
   int l, r;
 };
 
-int emit_tree(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, const std::vector<ENode>& t, int i) {
+int emit_tree(amdzk_ctx* ctx, const KeyMaterial& K, RotTable* grow, ProgramText& pr, const std::vector<ENode>& t, int i) {
   const ENode& n = t[i];
   auto is_col = [&](int j) { return t[j].op == XOP_FIXED || t[j].op == XOP_ADVICE || t[j].op == XOP_INSTANCE; };
-  auto col_arg = [&](int j) -> uint32_t {
+  // the fused or pushing instruction `op` on column node j
+  auto col_op = [&](uint32_t op, int j) -> int {
     const ENode& c = t[j];
     uint32_t col = c.payload >> 8;
     int32_t rot = (int32_t)(c.payload & 0xff) - 128;
-    uint32_t slot = c.op == XOP_FIXED ? pk->sl_fixed(col) : c.op == XOP_ADVICE ? pk->sl_adv(col) : pk->sl_inst(col);
-    return (slot << 8) | pk->rots.index(rot);
+    uint32_t slot = c.op == XOP_FIXED ? K.sl_fixed(col) : c.op == XOP_ADVICE ? K.sl_adv(col) : K.sl_inst(col);
+    const int r = grow ? (int)grow->index(rot) : K.rots.find(rot);
+    // (the one caller on a frozen key is the witness check; cannot happen for a key keygen made: the h(X) program queried the gates' rotations)
+    if (r < 0) ZK_FAIL(ctx, AMDZK_E_INVALID, "check_witness: a gate polynomial queries a rotation the key's programs do not");
+    pr.op(op, (slot << 8) | (uint32_t)r);
+    return AMDZK_OK;
   };
   switch (n.op) {
     case XOP_CONST:
@@ -40,37 +45,37 @@ int emit_tree(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, const std::vector<ENode
     case XOP_FIXED:
     case XOP_ADVICE:
     case XOP_INSTANCE:
-      pr.op(OP_PUSH_COL, col_arg(i));
+      ZK_TRY(col_op(OP_PUSH_COL, i));
       pr.push();
       return AMDZK_OK;
     case XOP_NEG:
-      ZK_TRY(emit_tree(ctx, pk, pr, t, n.l));
+      ZK_TRY(emit_tree(ctx, K, grow, pr, t, n.l));
       pr.op(OP_NEG);
       return AMDZK_OK;
     case XOP_SCALE:
-      ZK_TRY(emit_tree(ctx, pk, pr, t, n.l));
+      ZK_TRY(emit_tree(ctx, K, grow, pr, t, n.l));
       pr.op(OP_MUL_CONST, n.payload);
       return AMDZK_OK;
     case XOP_ADD: {
       int a = n.l, b = n.r;
       if (t[b].op == XOP_NEG && is_col(t[b].l)) {  // a + (-col) -> a - col
-        ZK_TRY(emit_tree(ctx, pk, pr, t, a));
-        pr.op(OP_SUB_COL, col_arg(t[b].l));
+        ZK_TRY(emit_tree(ctx, K, grow, pr, t, a));
+        ZK_TRY(col_op(OP_SUB_COL, t[b].l));
         return AMDZK_OK;
       }
       if (!is_col(b) && t[b].op != XOP_CONST && (is_col(a) || t[a].op == XOP_CONST)) std::swap(a, b);
       if (is_col(b)) {
-        ZK_TRY(emit_tree(ctx, pk, pr, t, a));
-        pr.op(OP_ADD_COL, col_arg(b));
+        ZK_TRY(emit_tree(ctx, K, grow, pr, t, a));
+        ZK_TRY(col_op(OP_ADD_COL, b));
         return AMDZK_OK;
       }
       if (t[b].op == XOP_CONST) {
-        ZK_TRY(emit_tree(ctx, pk, pr, t, a));
+        ZK_TRY(emit_tree(ctx, K, grow, pr, t, a));
         pr.op(OP_ADD_CONST, t[b].payload);
         return AMDZK_OK;
       }
-      ZK_TRY(emit_tree(ctx, pk, pr, t, a));
-      ZK_TRY(emit_tree(ctx, pk, pr, t, b));
+      ZK_TRY(emit_tree(ctx, K, grow, pr, t, a));
+      ZK_TRY(emit_tree(ctx, K, grow, pr, t, b));
       pr.op(OP_ADD);
       pr.pop();
       return AMDZK_OK;
@@ -79,17 +84,17 @@ int emit_tree(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, const std::vector<ENode
       int a = n.l, b = n.r;
       if (!is_col(b) && t[b].op != XOP_CONST && (is_col(a) || t[a].op == XOP_CONST)) std::swap(a, b);
       if (is_col(b)) {
-        ZK_TRY(emit_tree(ctx, pk, pr, t, a));
-        pr.op(OP_MUL_COL, col_arg(b));
+        ZK_TRY(emit_tree(ctx, K, grow, pr, t, a));
+        ZK_TRY(col_op(OP_MUL_COL, b));
         return AMDZK_OK;
       }
       if (t[b].op == XOP_CONST) {
-        ZK_TRY(emit_tree(ctx, pk, pr, t, a));
+        ZK_TRY(emit_tree(ctx, K, grow, pr, t, a));
         pr.op(OP_MUL_CONST, t[b].payload);
         return AMDZK_OK;
       }
-      ZK_TRY(emit_tree(ctx, pk, pr, t, a));
-      ZK_TRY(emit_tree(ctx, pk, pr, t, b));
+      ZK_TRY(emit_tree(ctx, K, grow, pr, t, a));
+      ZK_TRY(emit_tree(ctx, K, grow, pr, t, b));
       pr.op(OP_MUL);
       pr.pop();
       return AMDZK_OK;
@@ -101,14 +106,14 @@ int emit_tree(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, const std::vector<ENode
 
 }  // namespace
 
-int emit_expr(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, const std::vector<uint32_t>& words) {
+int emit_expr(amdzk_ctx* ctx, const KeyMaterial& K, RotTable* grow, ProgramText& pr, const std::vector<uint32_t>& words) {
   std::vector<ENode> t;
   std::vector<int> st;
   for (uint32_t w : words) {
     uint32_t op = w >> 24, pl = w & 0xffffffu;
     switch (op) {
       case XOP_CONST:
-        if (pl >= pk->c_one) ZK_FAIL(ctx, AMDZK_E_INVALID, "circuit: constant index %u out of range", pl);
+        if (pl >= K.c_one) ZK_FAIL(ctx, AMDZK_E_INVALID, "circuit: constant index %u out of range", pl);
         t.push_back(ENode{op, pl, -1, -1});
         st.push_back((int)t.size() - 1);
         break;
@@ -116,20 +121,20 @@ int emit_expr(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, const std::vector<uint3
       case XOP_ADVICE:
       case XOP_INSTANCE: {
         uint32_t col = pl >> 8;
-        uint32_t lim = op == XOP_FIXED ? pk->F : op == XOP_ADVICE ? pk->A : pk->I;
+        uint32_t lim = op == XOP_FIXED ? K.F : op == XOP_ADVICE ? K.A : K.I;
         if (col >= lim) ZK_FAIL(ctx, AMDZK_E_INVALID, "circuit: column %u out of range", col);
         t.push_back(ENode{op, pl, -1, -1});
         st.push_back((int)t.size() - 1);
       } break;
       case XOP_CHALLENGE:  // one more constant operand: its slot is written per proof, so nothing here may read its value
-        if (pl >= pk->num_challenges) ZK_FAIL(ctx, AMDZK_E_INVALID, "circuit: bad expression word %08x", w);
-        t.push_back(ENode{XOP_CONST, pk->c_chal0 + pl, -1, -1});
+        if (pl >= K.num_challenges) ZK_FAIL(ctx, AMDZK_E_INVALID, "circuit: bad expression word %08x", w);
+        t.push_back(ENode{XOP_CONST, K.c_chal0 + pl, -1, -1});
         st.push_back((int)t.size() - 1);
         break;
       case XOP_NEG:
       case XOP_SCALE:
         if (st.empty()) ZK_FAIL(ctx, AMDZK_E_INVALID, "circuit: malformed expression");
-        if (op == XOP_SCALE && pl >= pk->c_one) ZK_FAIL(ctx, AMDZK_E_INVALID, "circuit: constant index %u out of range", pl);
+        if (op == XOP_SCALE && pl >= K.c_one) ZK_FAIL(ctx, AMDZK_E_INVALID, "circuit: constant index %u out of range", pl);
         t.push_back(ENode{op, pl, st.back(), -1});
         st.back() = (int)t.size() - 1;
         break;
@@ -147,14 +152,14 @@ int emit_expr(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, const std::vector<uint3
     }
   }
   if (st.size() != 1) ZK_FAIL(ctx, AMDZK_E_INVALID, "circuit: malformed expression");
-  return emit_tree(ctx, pk, pr, t, st[0]);
+  return emit_tree(ctx, K, grow, pr, t, st[0]);
 }
 
 // fold(acc * theta + expr) over a lookup's expressions (first term: 0*theta + e0 = e0)
-int emit_compressed(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, uint32_t first, uint32_t count) {
+int emit_compressed(amdzk_ctx* ctx, KeyMaterial& K, ProgramText& pr, uint32_t first, uint32_t count) {
   for (uint32_t i = 0; i < count; i++) {
-    if (i > 0) pr.op(OP_MUL_CONST, pk->c_theta);
-    ZK_TRY(emit_expr(ctx, pk, pr, pk->exprs[first + i]));
+    if (i > 0) pr.op(OP_MUL_CONST, K.c_theta);
+    ZK_TRY(emit_expr(ctx, K, &K.rots, pr, K.exprs[first + i]));
     if (i > 0) {
       pr.op(OP_ADD);
       pr.pop();
@@ -178,12 +183,12 @@ int emit_compressed(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, uint32_t first, u
 //     bounds would leave the reduction's range.
 // Bounds: a column, constant or hot value is below 1 (canonical); a product is below 2; a sum adds the bounds; a
 // difference a - b adds K to a's; the weak reduction gives 1.0002; a flushed group sum(bounds) / 169.3 + 1.
-// nparts > 1 cuts the finalised program into that many independent pieces of about equal length (Program::piece_starts):
+// nparts > 1 cuts the finalised program into that many independent pieces of about equal length (ProgramText::piece_starts):
 // a piece is a run of terms of the group order, closed by its own flush, and its first flush overwrites ITS h (bit 4) —
 // the interpreter runs piece p on the workgroups with blockIdx.y = p into h + p * rows, and the pieces' sums are added
 // afterwards (h is linear in the terms). One proof alone fills the chip's wavefront slots only that way.
 // Returns the number of terms (= the powers of y of amdzk_pk::d_ypow that the OP_WACC instructions point at).
-uint32_t finalize_limb_program(Program& pr, uint32_t nparts) {
+uint32_t finalize_limb_program(ProgramText& pr, uint32_t nparts) {
   const double LIM = 160.0, RED = 1.01, GROUP_LIM = 169.0 * 30.0;  // a flushed group stays below ~31 p (+ h, canonical)
   struct Term {
     std::vector<uint32_t> words;
@@ -369,16 +374,17 @@ int upload_consts261(amdzk_ctx* ctx, amdzk_pk* pk) {
 // d_ypow[j] = y^(K-1-j) for the K terms of the h(X) program, radix 2^261 (upstream folds the constraint values with
 // Horner, h = h*y + value, in the same order: term j carries y^(K-1-j)).
 int upload_ypow(amdzk_ctx* ctx, amdzk_pk* pk) {
-  const uint32_t K = pk->h_terms;
-  if (!K) return AMDZK_OK;
+  const KeyMaterial& K = *pk->key;
+  const uint32_t nt = K.h_terms;
+  if (!nt) return AMDZK_OK;
   Fr k32 = Fr::one();
   for (int i = 0; i < 5; i++) k32 = add(k32, k32);
-  std::vector<Fr> pw(K);
+  std::vector<Fr> pw(nt);
   Fr cur = k32;
-  const Fr y = pk->consts[pk->c_y], beta = pk->consts[pk->c_beta];
+  const Fr y = pk->consts[K.c_y], beta = pk->consts[K.c_beta];
   std::vector<Fr> bpow = {Fr::one()};  // beta^m for the terms whose factor beta^m was taken out (the permutation products)
-  for (uint32_t j = K; j-- > 0;) {
-    const uint32_t m = j < pk->h_term_beta_pow.size() ? pk->h_term_beta_pow[j] : 0;
+  for (uint32_t j = nt; j-- > 0;) {
+    const uint32_t m = j < K.h_term_beta_pow.size() ? K.h_term_beta_pow[j] : 0;
     while (bpow.size() <= m) bpow.push_back(mul(bpow.back(), beta));
     pw[j] = m ? mul(cur, bpow[m]) : cur;
     cur = mul(cur, y);
@@ -391,25 +397,27 @@ int upload_ypow(amdzk_ctx* ctx, amdzk_pk* pk) {
 // Resolve slots / rotation indices / constant indices into addresses and row offsets for one domain
 // and upload the 16-byte instructions.
 int upload_program(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, bool extended) {
+  const KeyMaterial& K = *pk->key;
+  const std::vector<uint32_t>& words = pr.text->words;
   const std::vector<const Fr*>& cols = extended ? pk->h_cols_ext : pk->h_cols_lag;
   // The interpreters fetch every instruction's operand, and the instruction two ahead, unconditionally: an
   // instruction without an operand names the first constant, and two END instructions close the program.
   const Fr* dummy = extended ? pk->d_consts261 : pk->d_consts;
-  std::vector<ExprInstr> ins(pr.words.size() + 2);
+  std::vector<ExprInstr> ins(words.size() + 2);
   for (size_t i = 0; i < ins.size(); i++) {
-    const uint32_t w = i < pr.words.size() ? pr.words[i] : (uint32_t)OP_END << 24, op = w >> 24, arg = w & 0xffffffu;
+    const uint32_t w = i < words.size() ? words[i] : (uint32_t)OP_END << 24, op = w >> 24, arg = w & 0xffffffu;
     ins[i].op_arg = w;
     ins[i].rot = 0;
     ins[i].ptr = dummy;
     if (op == OP_PUSH_COL || op == OP_MUL_COL || op == OP_ADD_COL || op == OP_SUB_COL) {
-      if ((arg >> 8) >= cols.size() || (arg & 0xff) >= pk->rots.rots.size()) ZK_FAIL(ctx, AMDZK_E_INVALID, "program: bad column operand");
+      if ((arg >> 8) >= cols.size() || (arg & 0xff) >= K.rots.rots.size()) ZK_FAIL(ctx, AMDZK_E_INVALID, "program: bad column operand");
       ins[i].ptr = cols[arg >> 8];
-      ins[i].rot = pk->rots.rots[arg & 0xff];  // rows of one coset are consecutive: a rotation is a row offset in both domains
+      ins[i].rot = K.rots.rots[arg & 0xff];  // rows of one coset are consecutive: a rotation is a row offset in both domains
     } else if (op == OP_PUSH_CONST || op == OP_MUL_CONST || op == OP_ADD_CONST) {
       if (arg >= pk->consts.size()) ZK_FAIL(ctx, AMDZK_E_INVALID, "program: bad constant operand");
       ins[i].ptr = (extended ? pk->d_consts261 : pk->d_consts) + arg;
     } else if (op == OP_WACC) {
-      if (!extended || (arg & 0x7fffffu) >= pk->h_terms) ZK_FAIL(ctx, AMDZK_E_INVALID, "program: bad power of y");
+      if (!extended || (arg & 0x7fffffu) >= K.h_terms) ZK_FAIL(ctx, AMDZK_E_INVALID, "program: bad power of y");
       ins[i].ptr = pk->d_ypow + (arg & 0x7fffffu);
     }
   }
@@ -420,14 +428,16 @@ int upload_program(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, bool extended) {
 }
 
 // the launch arguments of a program of this key: its pieces, its column table, where it stores
-int program_args(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, bool extended, Fr* const* d_outs, Fr* h_out, ExprArgs& a) {
-  a.prog = pr.d_instr;
+int program_args(amdzk_ctx* ctx, const amdzk_pk* pk, const Program& bound, bool extended, Fr* const* d_outs, Fr* h_out, ExprArgs& a) {
+  const KeyMaterial& K = *pk->key;
+  const ProgramText& pr = *bound.text;
+  a.prog = bound.d_instr;
   a.prog_len = (uint32_t)pr.words.size();
   a.cols = extended ? pk->d_cols_ext : pk->d_cols_lag;
   a.outs = d_outs;
   a.h_out = h_out;
-  a.nrows = extended ? pk->ext : pk->n;
-  a.mask = pk->n - 1;
+  a.nrows = extended ? K.ext : K.n;
+  a.mask = K.n - 1;
   // Quotient-domain programs (h(X), l_active) run in radix 2^261: their columns come from
   // zk_coeff_to_cosets_r261, their constants from d_consts261, and the result goes back through
   // zk_cosets_to_pieces. Lagrange-domain programs read the caller's radix-2^256 witness as is.
@@ -458,17 +468,18 @@ int program_args(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, bool extended, Fr* c
   }
   for (int i = 0; i < EXPR_HOT; i++) a.hot[i] = EXPR_NO_SLOT;
   if (extended && pr.uses_hot) {
-    a.hot[0] = pk->se_l0();
-    a.hot[1] = pk->se_llast();
-    a.hot[2] = pk->se_lactive();
-    a.hot[3] = pk->se_x();
+    a.hot[0] = K.se_l0();
+    a.hot[1] = K.se_llast();
+    a.hot[2] = K.se_lactive();
+    a.hot[3] = K.se_x();
   }
   return AMDZK_OK;
 }
 
-int run_program(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, bool extended, Fr* const* d_outs, Fr* h_out, const char* name) {
+int run_program(amdzk_ctx* ctx, const amdzk_pk* pk, const Program& bound, bool extended, Fr* const* d_outs, Fr* h_out, const char* name) {
+  const ProgramText& pr = *bound.text;
   ExprArgs a;
-  ZK_TRY(program_args(ctx, pk, pr, extended, d_outs, h_out, a));
+  ZK_TRY(program_args(ctx, pk, bound, extended, d_outs, h_out, a));
   // LDS stack slots: the limb interpreter keeps the top of the stack in registers, so a program whose stack holds at most
   // pr.depth - 1 values (finalize_limb_program) needs pr.depth - 2 slots: pr.depth - 1 leaves one spare
   return extended ? zk_expr_eval_limbs(ctx, a, pr.depth > 1 ? pr.depth - 1 : 1, name) : zk_expr_eval(ctx, a, pr.depth + 1, name);
@@ -481,7 +492,7 @@ extern "C" {
 // finalised h(X) program of a key. Words are `op << 24 | arg` with the opcodes of csrc/plonk_kernels.hpp.
 int amdzk_debug_limb_program(const uint32_t* words, size_t n, uint32_t* out, size_t cap, size_t* out_n, uint32_t* depth) {
   if ((!words && n) || !out_n) return AMDZK_E_INVALID;
-  Program pr;
+  ProgramText pr;
   pr.words.assign(words, words + n);
   (void)finalize_limb_program(pr);
   *out_n = pr.words.size();
@@ -494,10 +505,11 @@ int amdzk_debug_limb_program(const uint32_t* words, size_t n, uint32_t* out, siz
 }
 int amdzk_pk_h_program(const amdzk_pk* pk, uint32_t* out, size_t cap, size_t* out_n) {
   if (!pk || !out_n) return AMDZK_E_INVALID;
-  *out_n = pk->prog_h.words.size();
+  const std::vector<uint32_t>& words = pk->key->prog_h.words;
+  *out_n = words.size();
   if (out) {
-    if (cap < pk->prog_h.words.size()) return AMDZK_E_INVALID;
-    memcpy(out, pk->prog_h.words.data(), pk->prog_h.words.size() * sizeof(uint32_t));
+    if (cap < words.size()) return AMDZK_E_INVALID;
+    memcpy(out, words.data(), words.size() * sizeof(uint32_t));
   }
   return AMDZK_OK;
 }

@@ -96,12 +96,12 @@ struct PendingCommit {
   G1X* d_res = nullptr;
   size_t ncols = 0;
 };
-int commit_launch(amdzk_ctx* ctx, amdzk_pk* pk, int basis, const Fr* d_cols, size_t ncols, PendingCommit& pc) {
+int commit_launch(amdzk_ctx* ctx, const KeyMaterial& K, int basis, const Fr* d_cols, size_t ncols, PendingCommit& pc) {
   pc.ctx = ctx;
   pc.ncols = ncols;
   pc.d_res = nullptr;
   if (ncols == 0) return AMDZK_OK;
-  return zk_msm_dev_xyzz(ctx, pk->srs, basis, d_cols, ncols, pk->n, pk->n, &pc.d_res);
+  return zk_msm_dev_xyzz(ctx, K.srs, basis, d_cols, ncols, K.n, K.n, &pc.d_res);
 }
 int commit_finish(PendingCommit& pc, std::vector<G1Affine>& out) {
   amdzk_ctx* ctx = pc.ctx;
@@ -126,29 +126,30 @@ int commit_finish(PendingCommit& pc, std::vector<G1Affine>& out) {
 // permutation::prover::Argument::commit up to the blinding: rows 0 ... usable of the nsets product columns into pk->zp(), from
 // the workspace's columns and the beta and gamma of its constant table, on ctx's stream.
 // Dense: the fraction program over every row, the inversion of nsets * n denominators and a running product per column,
-// chained through last_z. Sparse (keys whose lists say so, amdzk_pk::perm_sparse): the same values from the perm_m listed
+// chained through last_z. Sparse (keys whose lists say so, KeyMaterial::perm_sparse): the same values from the perm_m listed
 // cells alone — their numerators and denominators side by side in the fraction columns, which are free until the row
 // differences are written there, ONE running product over all of them (last_z makes the sets one chain) and a gather.
-int perm_products_unblinded(amdzk_ctx* ctx, amdzk_pk* pk, bool sparse) {
-  const size_t n = pk->n, ns = pk->nsets, usable = n - (pk->bf + 1);
+int perm_products_unblinded(amdzk_ctx* ctx, const amdzk_pk* pk, bool sparse) {
+  const KeyMaterial& K = *pk->key;
+  const size_t n = K.n, ns = K.nsets, usable = n - (K.bf + 1);
   if (!sparse) {
     ZK_TRY(run_program(ctx, pk, pk->prog_pfrac, false, pk->d_outs_pfrac, nullptr, "expr_perm_fractions"));
     ZK_TRY(zk_batch_invert(ctx, pk->frac, pk->scratch, ns * n));
     ZK_TRY(zk_mul_elem(ctx, pk->zp(), pk->frac, ns * n));
     return zk_running_product(ctx, pk->zp(), ns, n, n, true, usable, pk->scan_tmp);
   }
-  const size_t m = pk->perm_m;
+  const size_t m = K.perm_m;
   Fr *den = pk->frac, *num = pk->frac + m + 1;
-  ZK_TRY(zk_perm_frac_sparse(ctx, pk->perm_list, (uint32_t)m, pk->d_perm_cols, pk->sigma_lag, pk->dxw_lag, n, pk->S, pk->chunk, pk->d_consts + pk->c_beta,
-                             pk->d_consts + pk->c_gamma, num, den));
+  ZK_TRY(zk_perm_frac_sparse(ctx, K.perm_list, (uint32_t)m, pk->d_perm_cols, K.sigma_lag, K.dxw_lag, n, K.S, K.chunk, pk->d_consts + K.c_beta,
+                             pk->d_consts + K.c_gamma, num, den));
   ZK_TRY(zk_batch_invert(ctx, den, pk->scratch, m));
   ZK_TRY(zk_mul_elem(ctx, num, den, m));
   ZK_TRY(zk_running_product(ctx, num, 1, m + 1, m + 1, false, 0, pk->scan_tmp));
-  return zk_perm_fill(ctx, num, pk->perm_rank, pk->perm_off, (uint32_t)usable, (uint32_t)ns, pk->zp(), n);
+  return zk_perm_fill(ctx, num, K.perm_rank, K.perm_off, (uint32_t)usable, (uint32_t)ns, pk->zp(), n);
 }
 
-Fr rotate_omega(const amdzk_pk* pk, const Fr& x, int rot) {
-  return rot >= 0 ? mul(x, pow_u64(pk->omega, (uint64_t)rot)) : mul(x, pow_u64(pk->omega_inv, (uint64_t)(-rot)));
+Fr rotate_omega(const KeyMaterial& K, const Fr& x, int rot) {
+  return rot >= 0 ? mul(x, pow_u64(K.omega, (uint64_t)rot)) : mul(x, pow_u64(K.omega_inv, (uint64_t)(-rot)));
 }
 
 void trace_fr(const char* label, const Fr& v) {
@@ -170,9 +171,9 @@ void trace_pt(const char* label, const G1Affine& p) {
 
 }  // namespace
 
-int commit_cols(amdzk_ctx* ctx, amdzk_pk* pk, int basis, const Fr* d_cols, size_t ncols, std::vector<G1Affine>& out) {
+int commit_cols(amdzk_ctx* ctx, const KeyMaterial& K, int basis, const Fr* d_cols, size_t ncols, std::vector<G1Affine>& out) {
   PendingCommit pc;
-  ZK_TRY(commit_launch(ctx, pk, basis, d_cols, ncols, pc));
+  ZK_TRY(commit_launch(ctx, K, basis, d_cols, ncols, pc));
   return commit_finish(pc, out);
 }
 
@@ -181,16 +182,18 @@ int commit_cols(amdzk_ctx* ctx, amdzk_pk* pk, int basis, const Fr* d_cols, size_
 // challenges in pk->consts to the degree-1 pieces of h(X) in pk->hpieces. The numerator is evaluated on nc cosets of
 // the size-n subgroup (poly.hip, zk_quotient_plan), then divided by X^n - 1, interpolated per coset and recombined.
 static int quotient_from_cosets(amdzk_ctx* ctx, amdzk_pk* pk) {
+  const KeyMaterial& K = *pk->key;
   ZK_TRY(upload_consts261(ctx, pk));
   ZK_TRY(upload_ypow(ctx, pk));
   // the program writes h where its first group of terms is flushed: a constraint system without a single term has none
-  if (!pk->h_terms) ZK_HIP(ctx, hipMemsetAsync(pk->hq, 0, (size_t)pk->ext * 32, ctx->stream));
+  if (!K.h_terms) ZK_HIP(ctx, hipMemsetAsync(pk->hq, 0, (size_t)K.ext * 32, ctx->stream));
   ZK_TRY(run_program(ctx, pk, pk->prog_h, true, nullptr, pk->hq, "expr_evaluate_h"));
-  ZK_TRY(zk_cosets_to_pieces(ctx, pk->dom, pk->hq, pk->hpieces, pk->qdeg));
+  ZK_TRY(zk_cosets_to_pieces(ctx, K.dom, pk->hq, pk->hpieces, K.qdeg));
   return AMDZK_OK;
 }
 static int quotient_pieces(amdzk_ctx* ctx, amdzk_pk* pk) {
-  ZK_TRY(zk_coeff_to_cosets_r261(ctx, pk->dom, pk->PQ, pk->n, pk->PC, pk->ext, pk->NP));
+  const KeyMaterial& K = *pk->key;
+  ZK_TRY(zk_coeff_to_cosets_r261(ctx, K.dom, pk->PQ, K.n, pk->PC, K.ext, K.NP));
   return quotient_from_cosets(ctx, pk);
 }
 
@@ -206,10 +209,10 @@ struct DrawLayout {
   size_t lk_col;                           // stride of a lookup's draws in the lookups block
   size_t per_adv, per_lk, per_pz, per_lz;  // one instance's share of each block
   size_t adv, lk, pz, lz, rnd, h, total;   // first draw of each block; all draws
-  DrawLayout(const amdzk_pk* pk, size_t NC)
-      : col((size_t)pk->bf + 1), lk_col(2 * col + 2), per_adv((size_t)pk->A * (col + 1)), per_lk((size_t)pk->L * lk_col),
-        per_pz((size_t)pk->nsets * col), per_lz((size_t)pk->L * col), adv(0), lk(NC * per_adv), pz(lk + NC * per_lk),
-        lz(pz + NC * per_pz), rnd(lz + NC * per_lz), h(rnd + pk->n + 1), total(h + pk->qdeg) {}
+  DrawLayout(const KeyMaterial& K, size_t NC)
+      : col((size_t)K.bf + 1), lk_col(2 * col + 2), per_adv((size_t)K.A * (col + 1)), per_lk((size_t)K.L * lk_col),
+        per_pz((size_t)K.nsets * col), per_lz((size_t)K.L * col), adv(0), lk(NC * per_adv), pz(lk + NC * per_lk),
+        lz(pz + NC * per_pz), rnd(lz + NC * per_lz), h(rnd + K.n + 1), total(h + K.qdeg) {}
   size_t advice(size_t ci) const { return adv + ci * per_adv; }
   // A key with challenge phases (upstream loops over cs.phases() outside the loop over the circuits): the advice block is
   // phase, then instance, then the bf + 1 tails of each of the phase's columns in column order, then one blind per column.
@@ -245,8 +248,9 @@ struct DeferredCommit {
 // the queries in upstream order and their grouping (opening.hpp). Built once per key (per list of instance keys).
 int build_multiopen(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, amdzk_pk::Multiopen& mo) {
   amdzk_pk* const pk = pks[0];
-  const size_t n = pk->n;
-  const uint32_t S = pk->S, L = pk->L, ns = pk->nsets, bf = pk->bf;
+  const KeyMaterial& K = *pk->key;
+  const size_t n = K.n;
+  const uint32_t S = K.S, L = K.L, ns = K.nsets, bf = K.bf;
   auto rot_id = [&](int rot) -> uint32_t {
     for (size_t i = 0; i < mo.rots.size(); i++)
       if (mo.rots[i] == rot) return (uint32_t)i;
@@ -257,10 +261,10 @@ int build_multiopen(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, amdzk_pk::M
   // written evaluations: advice (instance after instance), fixed, random, sigma, permutation products (instance after
   // instance), lookups (instance after instance)
   for (size_t ci = 0; ci < NC; ci++)
-    for (auto& q : pk->advice_queries) addq(pks[ci]->q_adv() + (size_t)q.first * n, q.second);
-  for (auto& q : pk->fixed_queries) addq(pk->fixed_poly + (size_t)q.first * n, q.second);
+    for (auto& q : K.advice_queries) addq(pks[ci]->q_adv() + (size_t)q.first * n, q.second);
+  for (auto& q : K.fixed_queries) addq(K.fixed_poly + (size_t)q.first * n, q.second);
   addq(pk->rnd, 0);
-  for (uint32_t i = 0; i < S; i++) addq(pk->sigma_poly + (size_t)i * n, 0);
+  for (uint32_t i = 0; i < S; i++) addq(K.sigma_poly + (size_t)i * n, 0);
   for (size_t ci = 0; ci < NC; ci++)
     for (uint32_t s = 0; s < ns; s++) {
       addq(pks[ci]->q_zp() + (size_t)s * n, 0);
@@ -296,7 +300,7 @@ int build_multiopen(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, amdzk_pk::M
   // per instance: advice queries, the permutation argument's openings, the lookups' openings; then what exists once
   for (size_t ci = 0; ci < NC; ci++) {
     amdzk_pk* const pk = pks[ci];
-    for (auto& q : pk->advice_queries) addpq(pk->q_adv() + (size_t)q.first * n, q.second);
+    for (auto& q : K.advice_queries) addpq(pk->q_adv() + (size_t)q.first * n, q.second);
     for (uint32_t s = 0; s < ns; s++) {
       addpq(pk->q_zp() + (size_t)s * n, 0);
       addpq(pk->q_zp() + (size_t)s * n, 1);
@@ -310,8 +314,8 @@ int build_multiopen(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, amdzk_pk::M
       addpq(pk->q_zl() + (size_t)l * n, 1);
     }
   }
-  for (auto& q : pk->fixed_queries) addpq(pk->fixed_poly + (size_t)q.first * n, q.second);
-  for (uint32_t i = 0; i < S; i++) addpq(pk->sigma_poly + (size_t)i * n, 0);
+  for (auto& q : K.fixed_queries) addpq(K.fixed_poly + (size_t)q.first * n, q.second);
+  for (uint32_t i = 0; i < S; i++) addpq(K.sigma_poly + (size_t)i * n, 0);
   addpq(pk->hpoly, 0);
   addpq(pk->rnd, 0);
   if (missing) {
@@ -323,9 +327,9 @@ int build_multiopen(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, amdzk_pk::M
   mo.grp = opening::group(mo.q.data(), mo.q.size(), mo.com_poly.size(), mo.rots.size());
   for (auto& e : mo.ev) mo.ev_rot.push_back(rot_id(e.second));
   const size_t pairs = mo.grp.set_points;
-  if (mo.grp.sets.size() > pk->max_sets) {
+  if (mo.grp.sets.size() > K.max_sets) {
     mo = amdzk_pk::Multiopen();
-    ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "create_proof: more than %u rotation sets", pk->max_sets);
+    ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "create_proof: more than %u rotation sets", K.max_sets);
   }
   if (std::max<size_t>(pairs, 1) > pk->sets_Q_pairs) {
     ZK_TRY(dalloc(ctx, pk, &pk->sets_Q, std::max<size_t>(pairs, 1) * n));
@@ -350,6 +354,7 @@ struct Prover {
   amdzk_ctx* const ctx;
   amdzk_pk* const* const pks;
   amdzk_pk* const pk;
+  const KeyMaterial& K;
   const size_t NC, n, usable;
   const uint32_t A, I, L, ns, bf;
   amdzk_ctx *const M, *const B, *const C;
@@ -374,8 +379,8 @@ struct Prover {
   double tlast;
 
   Prover(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, amdzk_ctx* B, amdzk_ctx* C, zkhost::TranscriptWrite& T, const RandomSource& rng)
-      : ctx(ctx), pks(pks), pk(pks[0]), NC(NC), n(pk->n), usable(pk->n - (pk->bf + 1)), A(pk->A), I(pk->I), L(pk->L), ns(pk->nsets),
-        bf(pk->bf), M(ctx), B(B), C(C), serial(B == ctx), T(T), rng(rng), draws(pk, NC), cm_zp(NC), cm_zl(NC), tlast(now_ms()) {}
+      : ctx(ctx), pks(pks), pk(pks[0]), K(*pk->key), NC(NC), n(K.n), usable(K.n - (K.bf + 1)), A(K.A), I(K.I), L(K.L), ns(K.nsets),
+        bf(K.bf), M(ctx), B(B), C(C), serial(B == ctx), T(T), rng(rng), draws(K, NC), cm_zp(NC), cm_zl(NC), tlast(now_ms()) {}
 
   static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
   void tick(const char* label) {
@@ -430,7 +435,7 @@ struct Prover {
       else c.done = true;
       return AMDZK_OK;
     }
-    ZK_TRY(on_lane(l, commit_launch(l, pk, basis, d_cols, ncols, c.pc)));
+    ZK_TRY(on_lane(l, commit_launch(l, K, basis, d_cols, ncols, c.pc)));
     c.begun = true;
     if (serial) ZK_TRY(commit_end(c));
     return AMDZK_OK;
@@ -442,7 +447,7 @@ struct Prover {
       return AMDZK_OK;
     }
     std::vector<G1Affine> cm;
-    ZK_TRY(commit_cols(ctx, pk, basis, d_cols, ncols, cm));
+    ZK_TRY(commit_cols(ctx, K, basis, d_cols, ncols, cm));
     return write_points(cm, label);
   }
   // columns [first, first + count) of the arena, blinded on lane `after`: coefficients (PQ) and quotient-domain values (PC) on B
@@ -453,8 +458,8 @@ struct Prover {
     if (!count) return AMDZK_OK;
     if (after_l1) ZK_TRY(zk_stream_after_l1(B, after));
     else ZK_TRY(zk_stream_after(B, after));
-    ZK_TRY(on_lane(B, zk_lagrange_to_coeff(B, pk->dom, pk->P + first * n, n, pk->PQ + first * n, n, count)));
-    return on_lane(B, zk_coeff_to_cosets_r261(B, pk->dom, pk->PQ + first * n, n, pk->PC + first * pk->ext, pk->ext, count));
+    ZK_TRY(on_lane(B, zk_lagrange_to_coeff(B, K.dom, pk->P + first * n, n, pk->PQ + first * n, n, count)));
+    return on_lane(B, zk_coeff_to_cosets_r261(B, K.dom, pk->PQ + first * n, n, pk->PC + first * K.ext, K.ext, count));
   }
   // d_out = sum_j coefs[j] polys[j] (len elements each) on lane l, through l's pointer-table and small slices; `extra`
   // follows the coefficients in the small slice, for the kernel the caller launches next
@@ -467,12 +472,12 @@ struct Prover {
     return on_lane(l, zk_lincomb(l, (const Fr* const*)pk->ptrs_l[li], pk->small_l[li], (uint32_t)polys.size(), d_out, len, false));
   }
   // challenges into their slots of every instance's constant table, and the span of slots they cover up to the device
-  int put_consts(std::initializer_list<std::pair<uint32_t amdzk_pk::*, Fr>> vals) {
+  int put_consts(std::initializer_list<std::pair<uint32_t KeyMaterial::*, Fr>> vals) {
     for (size_t ci = 0; ci < NC; ci++) {
       amdzk_pk* const pk = pks[ci];
       uint32_t lo = UINT32_MAX, hi = 0;
       for (auto& v : vals) {
-        const uint32_t s = pk->*v.first;
+        const uint32_t s = K.*v.first;
         pk->consts[s] = v.second;
         lo = std::min(lo, s);
         hi = std::max(hi, s);
@@ -484,7 +489,7 @@ struct Prover {
 
   // 0. vk, instances
   int instances(const uint64_t* const* const* instances_all, const size_t* const* instance_lens_all) {
-    T.common_scalar(pk->transcript_repr);
+    T.common_scalar(K.transcript_repr);
     for (size_t ci = 0; ci < NC && I; ci++) {  // columns are zero beyond the caller's values: clear on the device, upload only what was given
       amdzk_pk* const pk = pks[ci];
       const uint64_t* const* instances = instances_all ? instances_all[ci] : nullptr;
@@ -520,7 +525,7 @@ struct Prover {
   int put_challenge(uint32_t i, const Fr& v) {
     for (size_t ci = 0; ci < NC; ci++) {
       amdzk_pk* const pk = pks[ci];
-      const uint32_t s = pk->c_chal0 + i;
+      const uint32_t s = K.c_chal0 + i;
       pk->consts[s] = v;
       ZK_TRY(h2d_staged(ctx, pk, pk->d_consts + s, &pk->consts[s], 32));
     }
@@ -531,15 +536,15 @@ struct Prover {
   // committed and written; then the phase's challenges are squeezed into their constant slots. Phases >= 1 start with the
   // caller's callback, which fills their columns of d_advice from the challenges so far.
   int advice_phased(const void* const* d_advice_all, size_t advice_stride) {
-    const uint32_t NCH = pk->num_challenges;
+    const uint32_t NCH = K.num_challenges;
     std::vector<Fr> chal(NCH, Fr::zero());
     for (uint32_t i = 0; i < NCH; i++) ZK_TRY(put_challenge(i, chal[i]));  // the last proof's values are gone
     size_t before = 0;  // advice columns in the phases below p
-    for (uint32_t p = 0; p < pk->nphases; p++) {
+    for (uint32_t p = 0; p < K.nphases; p++) {
       std::vector<std::pair<uint32_t, uint32_t>> runs;  // (first column, count)
       size_t in_phase = 0;
       for (uint32_t c = 0; c < A; c++)
-        if (pk->advice_phase[c] == p) {
+        if (K.advice_phase[c] == p) {
           if (!runs.empty() && runs.back().first + runs.back().second == c) runs.back().second++;
           else runs.push_back({c, 1});
           in_phase++;
@@ -568,7 +573,7 @@ struct Prover {
         if (p == 0) ZK_TRY(transforms_on_B(pk, M, A, I));  // the instance columns ride with the first phase
       }
       for (uint32_t i = 0; i < NCH; i++)
-        if (pk->challenge_phase[i] == p) {
+        if (K.challenge_phase[i] == p) {
           chal[i] = challenge("phase challenge");
           ZK_TRY(put_challenge(i, chal[i]));
         }
@@ -580,7 +585,7 @@ struct Prover {
   }
   // 1. advice: copy in, blind the unusable rows of every column, commit
   int advice(const void* const* d_advice_all, size_t advice_stride) {
-    if (pk->phased()) return advice_phased(d_advice_all, advice_stride);
+    if (K.phased()) return advice_phased(d_advice_all, advice_stride);
     for (size_t ci = 0; ci < NC; ci++) {
       ZK_TRY(advice_enqueue(ci, d_advice_all ? d_advice_all[ci] : nullptr, advice_stride));
       ZK_TRY(commit_end(cm_adv));
@@ -621,7 +626,7 @@ struct Prover {
     ZK_TRY(run_program(ctx, pk, pk->prog_compress, false, pk->d_outs_compress, nullptr, "expr_lookup_compress"));
     ZK_TRY(d2d(ctx, pk->la(), pk->ci, (size_t)L * n * 32));
     ZK_TRY(zk_permute_expression_pairs(ctx, pk->la(), pk->ct, pk->lk_ts, pk->ls(), pk->lk_left, pk->lk_flags, pk->d_err, L, (uint32_t)n,
-                                       (uint32_t)usable, pk->lk_ts_const, pk->lk_const));
+                                       (uint32_t)usable, K.lk_ts_const, K.lk_const));
     // the "input not in table" word comes down behind the permutation and is read once the host has waited for this
     // phase's commitment anyway (it used to be a host wait of its own in the middle of the phase: 0.1 ms of idle device)
     *pk->h_err = 0;
@@ -664,7 +669,7 @@ struct Prover {
   }
   int perm_products(size_t ci) {  // fractions, inversion, running products, blinding: everything in front of the commitment
     amdzk_pk* const pk = pks[ci];
-    ZK_TRY(perm_products_unblinded(ctx, pk, pk->perm_sparse));
+    ZK_TRY(perm_products_unblinded(ctx, pk, K.perm_sparse));
     tick("  perm: fractions, inversion, running product");
     ZK_TRY(blind(M, pk->zp(), ns, n - bf, bf, draws.perm_product(ci), draws.col));
     // What is committed is the columns' row differences, over the prefix sums of g_lagrange: the same points (Abel
@@ -725,18 +730,18 @@ struct Prover {
       // into pieces are linear — so the pieces are the same combination of the instances' pieces.
       std::vector<const Fr*> pp(NC);
       std::vector<Fr> cf(NC);
-      const Fr yK = pow_u64(y, pk->h_terms);
+      const Fr yK = pow_u64(y, K.h_terms);
       Fr cur = Fr::one();
       for (size_t ci = NC; ci-- > 0;) {
         pp[ci] = pks[ci]->hpieces;
         cf[ci] = cur;
         cur = mul(cur, yK);
       }
-      const size_t len = (size_t)pk->qdeg * n;
+      const size_t len = (size_t)K.qdeg * n;
       ZK_TRY(lincomb(M, pp, cf, pk->scratch, len));  // scratch holds >= ext >= qdeg * n
       ZK_TRY(d2d(ctx, pk->hpieces, pk->scratch, len * 32));
     }
-    ZK_TRY(commit_write(AMDZK_BASIS_G, pk->hpieces, pk->qdeg, "h_piece"));  // consecutive n-blocks
+    ZK_TRY(commit_write(AMDZK_BASIS_G, pk->hpieces, K.qdeg, "h_piece"));  // consecutive n-blocks
     tick("h_eval+commit");
     return AMDZK_OK;
   }
@@ -757,10 +762,10 @@ struct Prover {
   int evaluations_prepare(const Fr& x) {
     {
       const Fr xn = pow_u64(x, n);
-      std::vector<const Fr*> pp(pk->qdeg);
-      std::vector<Fr> cf(pk->qdeg);
+      std::vector<const Fr*> pp(K.qdeg);
+      std::vector<Fr> cf(K.qdeg);
       Fr cur = Fr::one();
-      for (uint32_t i = 0; i < pk->qdeg; i++) {
+      for (uint32_t i = 0; i < K.qdeg; i++) {
         pp[i] = pk->hpieces + (size_t)i * n;
         cf[i] = cur;
         cur = mul(cur, xn);
@@ -778,7 +783,7 @@ struct Prover {
     if (!mo->built) ZK_TRY(build_multiopen(ctx, pks, NC, *mo));
     const size_t nrot = mo->rots.size();
     rot_pt.resize(nrot);
-    for (size_t r = 0; r < nrot; r++) rot_pt[r] = rotate_omega(pk, x, mo->rots[r]);
+    for (size_t r = 0; r < nrot; r++) rot_pt[r] = rotate_omega(K, x, mo->rots[r]);
     const size_t nq = mo->ev.size();
     if (nq > pk->ptrs_cap || 2 * nq > pk->small_cap) ZK_FAIL(ctx, AMDZK_E_NOMEM, "create_proof: too many queries (%zu)", nq);
     ev_pp.resize(nq);
@@ -885,6 +890,15 @@ struct Prover {
   }
 };
 
+// pks[i] is a handle of pks[0]'s key and none of the handles before it: what every entry point over several handles asks
+// of each, under its own prefix and its own noun for what a handle stands for.
+int check_handle(amdzk_ctx* ctx, const char* who, const char* noun, amdzk_pk* const* pks, size_t i) {
+  if (pks[i]->key != pks[0]->key) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: %s %zu's key is not the first key or a workspace clone of it", who, noun, i);
+  for (size_t d = 0; d < i; d++)
+    if (pks[d] == pks[i]) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: %ss %zu and %zu share one workspace", who, noun, d, i);
+  return AMDZK_OK;
+}
+
 // What amdzk_create_proof_opts adds to a proof: the caller's transcript and its synthesize of the later phases.
 struct ProofExtras {
   const amdzk_transcript* transcript = nullptr;
@@ -900,19 +914,15 @@ struct ProofExtras {
 int create_proof_body(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, const uint64_t* const* const* instances_all,
                       const size_t* const* instance_lens_all, const void* const* d_advice_all, size_t advice_stride, const RandomSource& rng,
                       int transcript_kind, uint8_t* proof_out, size_t proof_cap, size_t* proof_len, const ProofExtras& ex) {
-  amdzk_pk* const pk = pks[0];
+  const KeyMaterial& K = *pks[0]->key;
   if (!proof_len) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: null argument");
   for (size_t c = 0; c < NC; c++) {
-    if (!pks[c] || (pk->A && (!d_advice_all || !d_advice_all[c]))) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: null argument (circuit %zu)", c);
-    const amdzk_pk* root_c = pks[c]->clone_of ? pks[c]->clone_of : pks[c];
-    const amdzk_pk* root_0 = pk->clone_of ? pk->clone_of : pk;
-    if (root_c != root_0) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: circuit %zu's key is not the first key or a workspace clone of it", c);
-    for (size_t d = 0; d < c; d++)
-      if (pks[d] == pks[c]) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: circuits %zu and %zu share one workspace", d, c);
+    if (!pks[c] || (K.A && (!d_advice_all || !d_advice_all[c]))) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: null argument (circuit %zu)", c);
+    ZK_TRY(check_handle(ctx, "create_proof", "circuit", pks, c));
   }
-  if (advice_stride < pk->n) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: advice stride < n");
-  if (pk->nphases > 1 && !ex.phase_fn)
-    ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: the key has advice in %u phases: amdzk_create_proof_opts with a phase callback is needed", pk->nphases);
+  if (advice_stride < K.n) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: advice stride < n");
+  if (K.nphases > 1 && !ex.phase_fn)
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: the key has advice in %u phases: amdzk_create_proof_opts with a phase callback is needed", K.nphases);
   const bool use_gwc = (transcript_kind & AMDZK_MULTIOPEN_GWC) != 0;
   transcript_kind &= ~AMDZK_MULTIOPEN_GWC;
   zkhost::Blake2bWrite t_blake;
@@ -933,7 +943,7 @@ int create_proof_body(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, const uin
     if (T.failed) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: the caller's transcript reported an error");     \
   } while (0)
   amdzk_ctx *B = ctx, *C = ctx;  // the lanes (Prover)
-  if (pk->use_lanes && NC == 1) {  // several instances: one stream (each lane holds one commitment batch's result at a time)
+  if (K.use_lanes && NC == 1) {  // several instances: one stream (each lane holds one commitment batch's result at a time)
     ZK_TRY(zk_lane(ctx, 0, &B));
     ZK_TRY(zk_lane(ctx, 1, &C));
   }
@@ -959,20 +969,20 @@ int create_proof_body(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, const uin
   ZK_TRY(P.advice(d_advice_all, advice_stride));
   T_OK();
   const Fr theta = P.challenge("theta");
-  ZK_TRY(P.put_consts({{&amdzk_pk::c_theta, theta}}));
+  ZK_TRY(P.put_consts({{&KeyMaterial::c_theta, theta}}));
   ZK_TRY(P.lookups());
   const Fr beta = P.challenge("beta");
   const Fr gamma = P.challenge("gamma");
   T_OK();
   // the permutation factors are evaluated as beta (sigma + w) and beta (delta^j X + w) with w = (v + gamma) / beta
-  if (pk->S && beta.is_zero()) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "create_proof: the challenge beta is zero (probability 2^-254): the factored permutation terms need 1 / beta");
-  ZK_TRY(P.put_consts({{&amdzk_pk::c_beta, beta}, {&amdzk_pk::c_gamma, gamma}, {&amdzk_pk::c_betainv, inv(beta)}}));
+  if (K.S && beta.is_zero()) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "create_proof: the challenge beta is zero (probability 2^-254): the factored permutation terms need 1 / beta");
+  ZK_TRY(P.put_consts({{&KeyMaterial::c_beta, beta}, {&KeyMaterial::c_gamma, gamma}, {&KeyMaterial::c_betainv, inv(beta)}}));
   P.tick("  perm: challenges+consts");
   ZK_TRY(P.products());
   ZK_TRY(P.write_points(P.cm_rnd.pts, "random_poly"));  // 5. vanishing: the random polynomial, committed at the start
   const Fr y = P.challenge("y");
   T_OK();
-  ZK_TRY(P.put_consts({{&amdzk_pk::c_y, y}}));
+  ZK_TRY(P.put_consts({{&KeyMaterial::c_y, y}}));
   ZK_TRY(P.vanishing(y));
   const Fr x = P.challenge("x");
   T_OK();
@@ -1083,14 +1093,14 @@ struct Gang {
         if (m->live)
           for (auto& d : m->deferred)
             if (d.basis == basis)
-              for (size_t c = 0; c < d.ncols; c++) cols.push_back(d.cols + c * m->pk->n);
+              for (size_t c = 0; c < d.ncols; c++) cols.push_back(d.cols + c * m->pk->key->n);
       if (cols.empty()) continue;
       amdzk_pk* const pk0 = members[0]->pk;  // srs, n and the staging ring: any member's
       char* d_tab = nullptr;
       ZK_TRY(scratch(cols.size() * sizeof(Fr*), &d_tab));
       ZK_TRY(h2d_staged(ctx, pk0, d_tab, cols.data(), cols.size() * sizeof(Fr*)));
       G1X* d_res = nullptr;
-      ZK_TRY(zk_msm_dev_xyzz_cols(ctx, pk0->srs, basis, (const Fr* const*)d_tab, cols.size(), pk0->n, 0, &d_res));
+      ZK_TRY(zk_msm_dev_xyzz_cols(ctx, pk0->key->srs, basis, (const Fr* const*)d_tab, cols.size(), pk0->key->n, 0, &d_res));
       PendingCommit pc;
       pc.ctx = ctx;
       pc.d_res = d_res;
@@ -1142,7 +1152,7 @@ struct Gang {
     Fr* d_pts = (Fr*)(d + o_pts);
     ZK_TRY(h2d_staged(ctx, pk0, d, pp.data(), nq * sizeof(Fr*)));
     ZK_TRY(h2d_staged(ctx, pk0, d_pts, pts.data(), nq * 32));
-    ZK_TRY(zk_poly_eval(ctx, (const Fr* const*)d, d_pts, d_pts + nq, nq, (uint32_t)pk0->n));
+    ZK_TRY(zk_poly_eval(ctx, (const Fr* const*)d, d_pts, d_pts + nq, nq, (uint32_t)pk0->key->n));
     std::vector<Fr> out(nq);
     ZK_TRY(d2h(ctx, out.data(), d_pts + nq, nq * 32));
     size_t at = 0;
@@ -1175,7 +1185,7 @@ struct Gang {
     GANG_TRY(each([&](Member& m) -> int {
       ZK_TRY(m.P->advice_write());
       const Fr theta = m.P->challenge("theta");
-      ZK_TRY(m.P->put_consts({{&amdzk_pk::c_theta, theta}}));
+      ZK_TRY(m.P->put_consts({{&KeyMaterial::c_theta, theta}}));
       return m.P->lookups_enqueue(0);
     }));
     GANG_TRY(commit_step());
@@ -1183,8 +1193,8 @@ struct Gang {
       ZK_TRY(m.P->lookups_write(0));
       const Fr beta = m.P->challenge("beta");
       const Fr gamma = m.P->challenge("gamma");
-      if (m.pk->S && beta.is_zero()) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "create_proof: the challenge beta is zero (probability 2^-254): the factored permutation terms need 1 / beta");
-      ZK_TRY(m.P->put_consts({{&amdzk_pk::c_beta, beta}, {&amdzk_pk::c_gamma, gamma}, {&amdzk_pk::c_betainv, inv(beta)}}));
+      if (m.pk->key->S && beta.is_zero()) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "create_proof: the challenge beta is zero (probability 2^-254): the factored permutation terms need 1 / beta");
+      ZK_TRY(m.P->put_consts({{&KeyMaterial::c_beta, beta}, {&KeyMaterial::c_gamma, gamma}, {&KeyMaterial::c_betainv, inv(beta)}}));
       return m.P->products_enqueue_serial();
     }));
     GANG_TRY(commit_step());  // the lookup products over g_lagrange, the permutation products' differences over its prefix sums
@@ -1192,7 +1202,7 @@ struct Gang {
       ZK_TRY(m.P->products_write());
       ZK_TRY(m.P->write_points(m.P->cm_rnd.pts, "random_poly"));
       const Fr y = m.P->challenge("y");
-      ZK_TRY(m.P->put_consts({{&amdzk_pk::c_y, y}}));
+      ZK_TRY(m.P->put_consts({{&KeyMaterial::c_y, y}}));
       return m.P->vanishing(y);
     }));
     GANG_TRY(commit_step());  // the h pieces, written as they come back
@@ -1228,7 +1238,7 @@ struct Gang {
 extern "C" {
 
 // Number of Fr::random draws one create_proof makes for this key (DrawLayout).
-size_t amdzk_proof_random_count(const amdzk_pk* pk) { return pk ? DrawLayout(pk, 1).total : 0; }
+size_t amdzk_proof_random_count(const amdzk_pk* pk) { return pk ? DrawLayout(*pk->key, 1).total : 0; }
 
 // Length of the proof create_proof writes for this key: commitments — advice, 2 per lookup (A', S'), one per
 // permutation set, one per lookup product, the random polynomial, the h pieces, SHPLONK's two — then the
@@ -1236,16 +1246,16 @@ size_t amdzk_proof_random_count(const amdzk_pk* pk) { return pk ? DrawLayout(pk,
 // for the last, 5 per lookup. With AMDZK_MULTIOPEN_GWC the two SHPLONK points become one per opening point.
 // Distinct evaluation points of the proof's queries = distinct rotations (omega^r x are pairwise different
 // for the |r| << n that occur): what ProverGWC writes one witness commitment for.
-static size_t opening_point_count(const amdzk_pk* pk) {
+static size_t opening_point_count(const KeyMaterial& K) {
   std::vector<int> rots = {0};  // sigma columns, h(X), the random polynomial
   auto note = [&](int r) {
     if (std::find(rots.begin(), rots.end(), r) == rots.end()) rots.push_back(r);
   };
-  for (auto& q : pk->advice_queries) note(q.second);
-  for (auto& q : pk->fixed_queries) note(q.second);
-  if (pk->nsets) note(1);
-  if (pk->nsets > 1) note(-(int)(pk->bf + 1));
-  if (pk->L) {
+  for (auto& q : K.advice_queries) note(q.second);
+  for (auto& q : K.fixed_queries) note(q.second);
+  if (K.nsets) note(1);
+  if (K.nsets > 1) note(-(int)(K.bf + 1));
+  if (K.L) {
     note(1);
     note(-1);
   }
@@ -1311,7 +1321,7 @@ int amdzk_create_proof_opts(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_circu
     ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_opts: amdzk_proof_opts.size is %zu, this library needs %zu", opts->size, sizeof(amdzk_proof_opts));
   RandomSource rs;
   if (opts->scalars) {
-    const size_t need = DrawLayout(pks[0], n_circuits).total;
+    const size_t need = DrawLayout(*pks[0]->key, n_circuits).total;
     if (opts->scalar_count < need) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_opts: %zu scalars given, %zu needed", opts->scalar_count, need);
     rs.scalars = opts->scalars;
   } else {
@@ -1338,26 +1348,23 @@ static int proof_batch(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_proofs, co
   if (!opts->rng_seeds && !opts->scalars) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: neither rng_seeds nor scalars");
   for (size_t b = 0; b < n_proofs; b++) {
     if (!pks[b]) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: null key (proof %zu)", b);
-    const amdzk_pk* root_b = pks[b]->clone_of ? pks[b]->clone_of : pks[b];
-    const amdzk_pk* root_0 = pks[0]->clone_of ? pks[0]->clone_of : pks[0];
-    if (root_b != root_0) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: proof %zu's key is not the first key or a workspace clone of it", b);
-    for (size_t d = 0; d < b; d++)
-      if (pks[d] == pks[b]) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: proofs %zu and %zu share one workspace", d, b);
-    if (pks[0]->A && (!d_advice || !d_advice[b])) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: null advice (proof %zu)", b);
+    ZK_TRY(check_handle(ctx, "create_proof_batch", "proof", pks, b));
+    if (pks[0]->key->A && (!d_advice || !d_advice[b])) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: null advice (proof %zu)", b);
     if (opts->scalars && !opts->scalars[b]) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: null scalars (proof %zu)", b);
   }
   amdzk_pk* const pk = pks[0];
-  if (pk->phased())
+  const KeyMaterial& K = *pk->key;
+  if (K.phased())
     ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "create_proof_batch: the key has challenge phases or challenges: prove it with amdzk_create_proof_opts");
-  if (advice_stride < pk->n) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: advice stride < n");
+  if (advice_stride < K.n) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: advice stride < n");
   const bool use_gwc = (opts->transcript_kind & AMDZK_MULTIOPEN_GWC) != 0;
   const int kind = opts->transcript_kind & ~AMDZK_MULTIOPEN_GWC;
   if (kind != AMDZK_TRANSCRIPT_BLAKE2B && kind != AMDZK_TRANSCRIPT_KECCAK256_EVM)
     ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: unknown transcript kind %d", kind);
   const size_t psize = amdzk_proof_size(pk, opts->transcript_kind);
   if (proof_stride < psize) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: proof_stride %zu < proof size %zu", proof_stride, psize);
-  if (opts->scalars && opts->scalar_count < DrawLayout(pk, 1).total)
-    ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: %zu scalars given, %zu needed", opts->scalar_count, DrawLayout(pk, 1).total);
+  if (opts->scalars && opts->scalar_count < DrawLayout(K, 1).total)
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: %zu scalars given, %zu needed", opts->scalar_count, DrawLayout(K, 1).total);
 
   *ran = true;
   Gang g(ctx);
@@ -1416,11 +1423,12 @@ int amdzk_create_proof_batch(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_proo
 // Byte length of the proof amdzk_create_proof_multi writes for n_circuits instances (amdzk_proof_size for one).
 size_t amdzk_proof_size_multi(const amdzk_pk* pk, size_t n_circuits, int format) {
   if (!pk || n_circuits == 0) return 0;
+  const KeyMaterial& K = *pk->key;
   const int transcript_kind = format & 0xff;
-  const size_t openings = (format & AMDZK_MULTIOPEN_GWC) ? opening_point_count(pk) : 2;
-  const size_t points = n_circuits * ((size_t)pk->A + 2 * (size_t)pk->L + pk->nsets + pk->L) + 1 + pk->qdeg + openings;
-  const size_t scalars = n_circuits * (pk->advice_queries.size() + (pk->nsets ? 3 * (size_t)pk->nsets - 1 : 0) + 5 * (size_t)pk->L) +
-                         pk->fixed_queries.size() + 1 + pk->S;
+  const size_t openings = (format & AMDZK_MULTIOPEN_GWC) ? opening_point_count(K) : 2;
+  const size_t points = n_circuits * ((size_t)K.A + 2 * (size_t)K.L + K.nsets + K.L) + 1 + K.qdeg + openings;
+  const size_t scalars = n_circuits * (K.advice_queries.size() + (K.nsets ? 3 * (size_t)K.nsets - 1 : 0) + 5 * (size_t)K.L) +
+                         K.fixed_queries.size() + 1 + K.S;
   return points * (transcript_kind == AMDZK_TRANSCRIPT_KECCAK256_EVM ? 64 : 32) + scalars * 32;
 }
 
@@ -1436,16 +1444,17 @@ int amdzk_quotient_eval_dev(amdzk_ctx* ctx, amdzk_pk* pk, const void* d_polys, s
   ZK_ENTER(ctx);
   if (!ctx) return AMDZK_E_INVALID;
   if (!pk || !d_polys || !theta || !beta || !gamma || !y || !d_pieces_out) ZK_FAIL(ctx, AMDZK_E_INVALID, "quotient_eval: null argument");
-  if (poly_stride < pk->n) ZK_FAIL(ctx, AMDZK_E_INVALID, "quotient_eval: stride < n");
-  ZK_HIP(ctx, hipMemcpy2DAsync(pk->PQ, pk->n * 32, d_polys, poly_stride * 32, pk->n * 32, pk->NP, hipMemcpyDeviceToDevice, ctx->stream));
-  memcpy(pk->consts[pk->c_theta].l, theta, 32);
-  memcpy(pk->consts[pk->c_beta].l, beta, 32);
-  memcpy(pk->consts[pk->c_gamma].l, gamma, 32);
-  memcpy(pk->consts[pk->c_y].l, y, 32);
-  if (pk->S && pk->consts[pk->c_beta].is_zero()) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "quotient_eval: beta is zero");
-  pk->consts[pk->c_betainv] = inv(pk->consts[pk->c_beta]);
+  const KeyMaterial& K = *pk->key;
+  if (poly_stride < K.n) ZK_FAIL(ctx, AMDZK_E_INVALID, "quotient_eval: stride < n");
+  ZK_HIP(ctx, hipMemcpy2DAsync(pk->PQ, K.n * 32, d_polys, poly_stride * 32, K.n * 32, K.NP, hipMemcpyDeviceToDevice, ctx->stream));
+  memcpy(pk->consts[K.c_theta].l, theta, 32);
+  memcpy(pk->consts[K.c_beta].l, beta, 32);
+  memcpy(pk->consts[K.c_gamma].l, gamma, 32);
+  memcpy(pk->consts[K.c_y].l, y, 32);
+  if (K.S && pk->consts[K.c_beta].is_zero()) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "quotient_eval: beta is zero");
+  pk->consts[K.c_betainv] = inv(pk->consts[K.c_beta]);
   ZK_TRY(quotient_pieces(ctx, pk));
-  ZK_TRY(d2d(ctx, d_pieces_out, pk->hpieces, (size_t)pk->qdeg * pk->n * 32));
+  ZK_TRY(d2d(ctx, d_pieces_out, pk->hpieces, (size_t)K.qdeg * K.n * 32));
   ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
   return AMDZK_OK;
 }
@@ -1461,21 +1470,22 @@ int amdzk_perm_products_dev(amdzk_ctx* ctx, amdzk_pk* pk, const uint64_t beta[4]
   ZK_ENTER(ctx);
   if (!ctx) return AMDZK_E_INVALID;
   if (!pk) ZK_FAIL(ctx, AMDZK_E_INVALID, "perm_products: null key");
-  if (cells_out) *cells_out = pk->perm_m;
-  if (sparse_out) *sparse_out = pk->perm_sparse ? 1 : 0;
+  const KeyMaterial& K = *pk->key;
+  if (cells_out) *cells_out = K.perm_m;
+  if (sparse_out) *sparse_out = K.perm_sparse ? 1 : 0;
   if (!out) return AMDZK_OK;
   if (!beta || !gamma) ZK_FAIL(ctx, AMDZK_E_INVALID, "perm_products: null argument");
   if (route < -1 || route > 1) ZK_FAIL(ctx, AMDZK_E_INVALID, "perm_products: unknown route %d", route);
-  if (route == 1 && !pk->perm_sparse) ZK_FAIL(ctx, AMDZK_E_INVALID, "perm_products: the key keeps no list of cells (%zu listed)", pk->perm_m);
-  if (!pk->S) return AMDZK_OK;
-  memcpy(pk->consts[pk->c_beta].l, beta, 32);
-  memcpy(pk->consts[pk->c_gamma].l, gamma, 32);
-  if (pk->consts[pk->c_beta].is_zero()) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "perm_products: beta is zero");
-  pk->consts[pk->c_betainv] = inv(pk->consts[pk->c_beta]);
-  ZK_TRY(h2d(ctx, pk->d_consts + pk->c_beta, &pk->consts[pk->c_beta], (size_t)(pk->c_betainv + 1 - pk->c_beta) * 32));
-  ZK_TRY(perm_products_unblinded(ctx, pk, route < 0 ? pk->perm_sparse : route == 1));
-  const size_t rows = pk->n - pk->bf;  // usable + 1
-  ZK_HIP(ctx, hipMemcpy2DAsync(out, rows * 32, pk->zp(), pk->n * 32, rows * 32, pk->nsets, hipMemcpyDeviceToHost, ctx->stream));
+  if (route == 1 && !K.perm_sparse) ZK_FAIL(ctx, AMDZK_E_INVALID, "perm_products: the key keeps no list of cells (%zu listed)", K.perm_m);
+  if (!K.S) return AMDZK_OK;
+  memcpy(pk->consts[K.c_beta].l, beta, 32);
+  memcpy(pk->consts[K.c_gamma].l, gamma, 32);
+  if (pk->consts[K.c_beta].is_zero()) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "perm_products: beta is zero");
+  pk->consts[K.c_betainv] = inv(pk->consts[K.c_beta]);
+  ZK_TRY(h2d(ctx, pk->d_consts + K.c_beta, &pk->consts[K.c_beta], (size_t)(K.c_betainv + 1 - K.c_beta) * 32));
+  ZK_TRY(perm_products_unblinded(ctx, pk, route < 0 ? K.perm_sparse : route == 1));
+  const size_t rows = K.n - K.bf;  // usable + 1
+  ZK_HIP(ctx, hipMemcpy2DAsync(out, rows * 32, pk->zp(), K.n * 32, rows * 32, K.nsets, hipMemcpyDeviceToHost, ctx->stream));
   ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
   return AMDZK_OK;
 }

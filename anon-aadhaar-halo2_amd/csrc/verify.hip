@@ -285,11 +285,12 @@ int verify_core(amdzk_ctx* ctx, const char* who, const zk_key_view* key, size_t 
 // The view of a proving key: G stays where the key's SRS keeps it. A key without a description or an SRS gives a view
 // without a description, which verify_core refuses.
 zk_key_view view_of(const amdzk_pk* pk) {
+  const KeyMaterial& K = *pk->key;
   zk_key_view v;
-  if (pk->src_desc && pk->srs) v.desc = pk->src_desc.get();
-  v.transcript_repr = &pk->transcript_repr, v.omega = &pk->omega;
-  v.fixed_commitments = pk->fixed_commitments.data(), v.perm_commitments = pk->perm_commitments.data();
-  v.d_g = zk_srs_base_dev(pk->srs, AMDZK_BASIS_G);
+  if (K.src_desc && K.srs) v.desc = K.src_desc.get();
+  v.transcript_repr = &K.transcript_repr, v.omega = &K.omega;
+  v.fixed_commitments = K.fixed_commitments.data(), v.perm_commitments = K.perm_commitments.data();
+  v.d_g = zk_srs_base_dev(K.srs, AMDZK_BASIS_G);
   v.sized_by = pk;
   return v;
 }

@@ -1,8 +1,8 @@
 // A verifying key's life (include/amdzk.h "verifying keys"): plonk::keygen_vk [UP] without a proving key,
 // ProvingKey::get_vk [UP], the key file (vkblob.hpp has its layout and every check of its reader) and the release.
-// amdzk_keygen_vk runs keygen's own steps (keygen.hip, declared in pk.hpp) on a scratch key that holds the description and
-// the F + S Lagrange columns and is gone when the call returns: no coset, no program, no per-proof workspace. No kernel
-// lives here; verifying with the key is verify.hip's.
+// amdzk_keygen_vk runs keygen's own steps (keygen.hip, declared in pk.hpp) on key material of its own that holds the
+// description and the F + S Lagrange columns and is gone when the call returns: no coset, no program, and no handle, so no
+// per-proof workspace. No kernel lives here; verifying with the key is verify.hip's.
 #include <string.h>
 
 #include <memory>
@@ -27,16 +27,16 @@ int refuse_unvalidated(amdzk_ctx* ctx, const char* prefix, const pkblob::Desc& d
   ZK_FAIL(ctx, AMDZK_E_INVALID, "%s%s", prefix, why.compare(0, own.size(), own) == 0 ? why.c_str() + own.size() : why.c_str());
 }
 
-// amdzk_vk_from_pk's body: also how amdzk_keygen_vk takes the key out of its scratch key
-int vk_of(amdzk_ctx* ctx, const char* who, const amdzk_pk* pk, amdzk_vk** out) {
-  if (!pk->src_desc || !pk->srs) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: the key has no circuit description", who);
-  ZK_TRY(refuse_unvalidated(ctx, (std::string(who) + ": the key's circuit is not one a verifier can read: ").c_str(), *pk->src_desc));
-  const G1Affine* d_g = zk_srs_base_dev(pk->srs, AMDZK_BASIS_G);
+// amdzk_vk_from_pk's body: also how amdzk_keygen_vk takes the key out of its material
+int vk_of(amdzk_ctx* ctx, const char* who, const KeyMaterial& K, amdzk_vk** out) {
+  if (!K.src_desc || !K.srs) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: the key has no circuit description", who);
+  ZK_TRY(refuse_unvalidated(ctx, (std::string(who) + ": the key's circuit is not one a verifier can read: ").c_str(), *K.src_desc));
+  const G1Affine* d_g = zk_srs_base_dev(K.srs, AMDZK_BASIS_G);
   if (!d_g) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: the key's SRS has no monomial basis", who);
   std::unique_ptr<amdzk_vk> vk(new amdzk_vk());
-  vk->desc = pk->src_desc;
-  vk->transcript_repr = pk->transcript_repr, vk->omega = pk->omega;
-  vk->fixed_commitments = pk->fixed_commitments, vk->perm_commitments = pk->perm_commitments;
+  vk->desc = K.src_desc;
+  vk->transcript_repr = K.transcript_repr, vk->omega = K.omega;
+  vk->fixed_commitments = K.fixed_commitments, vk->perm_commitments = K.perm_commitments;
   ZK_TRY(d2h(ctx, &vk->g, d_g, sizeof(G1Affine)));
   *out = vk.release();
   return AMDZK_OK;
@@ -51,33 +51,31 @@ int amdzk_keygen_vk(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* c
   ZK_ENTER(ctx);
   if (!ctx) return AMDZK_E_INVALID;
   uint32_t nphases = 1;
-  amdzk_pk* unused = nullptr;
-  ZK_TRY(check_keygen_args(ctx, srs, c, ph, transcript_repr, 0, out ? &unused : nullptr, &nphases));
+  ZK_TRY(check_keygen_args(ctx, srs, c, ph, transcript_repr, 0, out, &nphases));
   if (c->num_perm_columns && (perm_mapping != nullptr) == (sigma_values != nullptr))
     ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen_vk: exactly one of perm_mapping and sigma_values feeds the permutation columns, %s given",
             perm_mapping ? "both" : "neither");
   if (!zk_srs_has_basis(srs, AMDZK_BASIS_G) || !zk_srs_has_basis(srs, AMDZK_BASIS_G_LAGRANGE))
     ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen_vk: the parameters need both bases, g (AMDZK_BASIS_G) and g_lagrange (AMDZK_BASIS_G_LAGRANGE)");
   if (c->k != zk_srs_k(srs)) ZK_FAIL(ctx, AMDZK_E_INVALID, "keygen_vk: the circuit is for k = %u, the parameters are for k = %u", c->k, zk_srs_k(srs));
-  // the scratch key: freed on every way out, with its two columns and its domain (amdzk_pk_free waits for the stream first)
-  auto drop = [ctx](amdzk_pk* pk) { amdzk_pk_free(ctx, pk); };
-  std::unique_ptr<amdzk_pk, decltype(drop)> owner(new amdzk_pk(), drop);
-  amdzk_pk* pk = owner.get();
-  ZK_TRY(describe_circuit(ctx, pk, srs, c, ph, nphases, transcript_repr, 0, true));
+  // freed on every way out, with its two columns and its domain (KeyFree waits for the stream first)
+  std::unique_ptr<KeyMaterial, KeyFree> owner(new KeyMaterial(), KeyFree{ctx});
+  KeyMaterial& K = *owner;
+  ZK_TRY(describe_circuit(ctx, K, srs, c, ph, nphases, transcript_repr, 0, true));
   // what keygen's expression compiler refuses ("circuit: ..."), refused here without compiling: before anything goes up
-  ZK_TRY(refuse_unvalidated(ctx, "circuit: ", *pk->src_desc));
-  ZK_TRY(dalloc(ctx, pk, &pk->fixed_lag, (size_t)pk->F * pk->n));
-  ZK_TRY(dalloc(ctx, pk, &pk->sigma_lag, (size_t)pk->S * pk->n));
-  ZK_TRY(load_fixed_columns(ctx, pk, fixed_values, true));
-  ZK_TRY(load_sigma_columns(ctx, pk, perm_mapping, sigma_values, sigma_values != nullptr, true));
-  return vk_of(ctx, "keygen_vk", pk, out);
+  ZK_TRY(refuse_unvalidated(ctx, "circuit: ", *K.src_desc));
+  ZK_TRY(dalloc(ctx, &K, &K.fixed_lag, (size_t)K.F * K.n));
+  ZK_TRY(dalloc(ctx, &K, &K.sigma_lag, (size_t)K.S * K.n));
+  ZK_TRY(load_fixed_columns(ctx, K, fixed_values));
+  ZK_TRY(load_sigma_columns(ctx, K, perm_mapping, sigma_values, sigma_values != nullptr));
+  return vk_of(ctx, "keygen_vk", K, out);
 }
 
 int amdzk_vk_from_pk(amdzk_ctx* ctx, const amdzk_pk* pk, amdzk_vk** out) {
   ZK_ENTER(ctx);
   if (!ctx) return AMDZK_E_INVALID;
   if (!pk || !out) ZK_FAIL(ctx, AMDZK_E_INVALID, "vk_from_pk: null argument");
-  return vk_of(ctx, "vk_from_pk", pk, out);
+  return vk_of(ctx, "vk_from_pk", *pk->key, out);
 }
 
 void amdzk_vk_free(amdzk_ctx*, amdzk_vk* vk) { delete vk; }

@@ -450,7 +450,7 @@ class ProvingKey:
 
     def export(self, what):
         """amdzk_pk_export: the key's own columns as (columns, n, 4) uint64 Montgomery. 0: fixed (Lagrange), 1: sigma
-        (Lagrange), 2: fixed coefficients, 3: sigma coefficients. A clone returns its root key's columns."""
+        (Lagrange), 2: fixed coefficients, 3: sigma coefficients. Every handle of a key returns the same columns."""
         cnt = C.c_size_t(0)
         self.ctx._chk(self.ctx.L.amdzk_pk_export(self.ctx.h, self.h, what, None, 0, C.byref(cnt)))
         out = np.zeros((cnt.value, 4), np.uint64)
@@ -469,7 +469,7 @@ class ProvingKey:
     def clone_workspace(self):
         """amdzk_pk_clone_workspace: a key that shares this key's material and owns one more circuit instance's per-proof
         workspace — the second, third, ... instance of create_proof_multi, or one more proof of this circuit in flight.
-        Free it before this key."""
+        Free it and this key in any order: the last handle frees the key material."""
         c = object.__new__(ProvingKey)
         c.ctx, c.params, c.desc = self.ctx, self.params, self.desc
         h = C.c_void_p()

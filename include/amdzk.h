@@ -404,8 +404,8 @@ int amdzk_create_proof_ex(amdzk_ctx* ctx, amdzk_pk* pk, const uint64_t* const* i
  * instances' terms in one chain with y).
  * A key owns ONE instance's per-proof workspace: amdzk_pk_clone_workspace makes a handle that shares `pk`'s key material
  * (fixed / permutation columns and cosets, programs, domain) and owns one more workspace. It is a complete key for
- * amdzk_create_proof* too (the cheap way to several proofs of one circuit in flight). Free clones (amdzk_pk_free) BEFORE
- * the key they were made from. */
+ * amdzk_create_proof* too (the cheap way to several proofs of one circuit in flight). The handles of one key — the one
+ * keygen returned and its clones — are freed (amdzk_pk_free) in any order: the last one frees the key material. */
 int amdzk_pk_clone_workspace(amdzk_ctx* ctx, const amdzk_pk* pk, amdzk_pk** out);
 /* pks[c]: instance c's workspace — the key or clones of it, pairwise different, all on this ctx's device.
  * instances[c][col] / instance_lens[c][col] and d_advice[c] (+ advice_stride) as for amdzk_create_proof_ex; one RNG stream

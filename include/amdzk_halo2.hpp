@@ -732,8 +732,8 @@ class ProvingKey {
     return out;
   }
   // amdzk_pk_clone_workspace: a key sharing this key's material that owns one more circuit instance's per-proof
-  // workspace (the second, third, ... instance of a multi-circuit create_proof, or one more proof in flight). Must not
-  // outlive this key.
+  // workspace (the second, third, ... instance of a multi-circuit create_proof, or one more proof in flight). It and
+  // this key are freed in any order: the last handle frees the key material.
   std::unique_ptr<ProvingKey> clone_workspace() const {
     std::unique_ptr<ProvingKey> c(new ProvingKey(ctx_, num_fixed_, num_perm_, num_advice_, k_));
     ctx_.check(amdzk_pk_clone_workspace(ctx_.get(), h_, &c->h_));

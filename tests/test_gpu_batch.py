@@ -264,6 +264,8 @@ def test_refusals_leave_the_ctx_usable(ctx, pkg, plonk, oracle):
     refused(INVALID, "share one workspace", lambda: plonk.create_proof_batch(ctx, [B.pk, B.pk], B.inst, B.d_adv, [3, 4]))
     refused(INVALID, "not the first key or a workspace clone",
             lambda: plonk.create_proof_batch(ctx, [B.pk, other.pks[1]], B.inst, B.d_adv, [3, 4]))
+    refused(INVALID, "create_proof_batch: proof 1's key is not the first key or a workspace clone of it",  # a clone of one key, the other key
+            lambda: plonk.create_proof_batch(ctx, [B.pks[1], other.pk], B.inst, B.d_adv, [3, 4]))
     refused(INVALID, "proof_stride", lambda: B.batch([3, 4], proof_stride=plonk.proof_size(ctx, B.pk) - 1))
     refused(INVALID, "amdzk_batch_opts.size", lambda: B.batch([3, 4], opts_size=8))
     refused(INVALID, "neither rng_seeds nor scalars", lambda: B.batch(None))
@@ -281,6 +283,17 @@ def test_refusals_leave_the_ctx_usable(ctx, pkg, plonk, oracle):
     assert ctx.L.amdzk_last_error(ctx.h).decode().startswith("create_proof_batch:")
     assert B.batch([3, 4]) == want
     other.free()
+    B.free()
+
+
+def test_a_batch_on_two_clones_after_the_first_handle_is_freed(ctx, pkg, plonk, oracle):
+    """The handles of a key are equals: a batch of two proofs on two clones, with the handle keygen returned already freed,
+    gives the oracle's bytes (k = 5: a constant table, a permutation and both lookup kinds)."""
+    c = circuits.lookup_circuit(plonk, 5, seed=2)
+    B = Batch(ctx, pkg, plonk, oracle, c, [(c.advice, c.instances)] * 3)
+    B.pk.free()
+    opk = PR.keygen(c.desc, c.fixed, c.assembly.mapping, TAU, transcript_repr=REPR)
+    assert B.batch([3, 4], idx=[1, 2]) == [PR.create_proof(opk, c.instances, c.advice, seed=s) for s in (3, 4)]
     B.free()
 
 

@@ -238,6 +238,27 @@ def test_keys_of_every_origin_give_the_same_reports(ctx, pkg, plonk, oracle, srs
     dev.free()
 
 
+def test_clones_outlive_the_handle_keygen_returned(ctx, pkg, plonk, oracle, srs):
+    """Keygen, two clones, and the handle keygen returned is freed first: each clone proves the oracle's bytes for its seed
+    (k = 5 with a constant table, whose compressed column a clone copies, a permutation and both lookup kinds), and a
+    clone's check of the witness — the first check on any handle of this key, so the sigma columns are decoded after the
+    original handle is gone — reports nothing."""
+    import plonk_ref as PR
+
+    c = circuits.lookup_circuit(plonk, 5, seed=2)
+    dev = Dev(ctx, plonk, oracle, srs, c)
+    clones = [dev.pk.clone_workspace(), dev.pk.clone_workspace()]
+    dev.pk.free()
+    opk = PR.keygen(c.desc, c.fixed, c.assembly.mapping, TAU, transcript_repr=REPR)
+    d_adv, inst = dev.upload(), fr_inst(oracle, c.instances)
+    for clone, seed in zip(clones, (41, 42)):
+        assert plonk.create_proof(ctx, clone, inst, d_adv, seed=seed) == PR.create_proof(opk, c.instances, c.advice, seed=seed)
+    assert dev.report(pk=clones[1]) == []
+    for clone in clones:
+        clone.free()
+    dev.free()
+
+
 # ---------------------------------------------------------------------------------------------- phased keys
 @pytest.mark.parametrize("name", ["rlc", "rlc-three", "random-0", "random-1"])
 def test_phased_keys_take_the_callers_challenges(ctx, pkg, plonk, oracle, name):

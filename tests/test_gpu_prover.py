@@ -42,7 +42,7 @@ def setup(ctx, pkg, plonk, oracle, c, transcript_repr_int=123456789, flags=None)
 @pytest.mark.parametrize("tables", ["range_first", "pair_first", "range_expr"])
 def test_constant_tables_sorted_at_keygen(ctx, pkg, plonk, oracle, tables, monkeypatch):
     """A leading lookup whose table is one expression over fixed columns has its sorted table made at keygen
-    (amdzk_pk::lk_const). The proof bytes are the oracle's with such a lookup in front, with it behind a theta-compressed
+    (KeyMaterial::lk_const). The proof bytes are the oracle's with such a lookup in front, with it behind a theta-compressed
     one (so the cache does not apply), with a table expression rather than a plain column — and with the cache off."""
     c = circuits.lookup_circuit(plonk, 6, seed=21, tables=tables)
     opk = PR.keygen(c.desc, c.fixed, c.assembly.mapping, TAU, transcript_repr=123456789)
@@ -460,11 +460,82 @@ def test_several_circuit_instances_in_one_proof(ctx, pkg, plonk, oracle, k, ncir
     # the same workspace twice is refused
     with pytest.raises(pkg.AmdzkError):
         plonk.create_proof_multi(ctx, [pk, pk], inst[:2], d_adv[:2], seed=17, transcript=tk)
+    # ... and so is a clone of this key together with another key of the same circuit
+    params2, pk2, d_adv2, _ = setup(ctx, pkg, plonk, oracle, c)
+    with pytest.raises(pkg.AmdzkError, match="create_proof: circuit 1's key is not the first key or a workspace clone of it"):
+        plonk.create_proof_multi(ctx, [pks[1], pk2], inst[:2], d_adv[:2], seed=17, transcript=tk)
+    assert plonk.create_proof_multi(ctx, pks, inst, d_adv, seed=17, transcript=tk) == got
+    d_adv2.free(); pk2.free(); params2.free()
     for d in d_adv:
         d.free()
     for q in pks[1:]:
         q.free()
     pk.free(); params.free()
+
+
+def test_two_clones_in_one_proof_after_the_first_handle_is_freed(ctx, pkg, plonk, oracle):
+    """The handles of a key are equals: create_proof_multi over two clones, with the handle keygen returned already freed,
+    gives the oracle's bytes (N = 2, k = 5: a constant table, a permutation and both lookup kinds)."""
+    c = circuits.lookup_circuit(plonk, 5, seed=2)
+    wit = [(c.advice, c.instances)] * 2
+    params, pk, d_adv, inst = setup(ctx, pkg, plonk, oracle, c)
+    clones = [pk.clone_workspace(), pk.clone_workspace()]
+    pk.free()
+    opk = PR.keygen(c.desc, c.fixed, c.assembly.mapping, TAU, transcript_repr=123456789)
+    want = PR.create_proof_multi(opk, [i for _, i in wit], [a for a, _ in wit], seed=17)
+    assert plonk.create_proof_multi(ctx, clones, [inst, inst], [d_adv, d_adv], seed=17) == want
+    for q in clones:
+        q.free()
+    d_adv.free(); params.free()
+
+
+def test_a_clone_of_a_clone_after_the_middle_one_is_freed(ctx, pkg, plonk, oracle):
+    """a, b = a.clone, c = b.clone, b freed: c and a prove the oracle's bytes (nothing of c hangs on b)."""
+    circ = circuits.lookup_circuit(plonk, 5, seed=2)
+    params, a, d_adv, inst = setup(ctx, pkg, plonk, oracle, circ)
+    b = a.clone_workspace()
+    c = b.clone_workspace()
+    b.free()
+    opk = PR.keygen(circ.desc, circ.fixed, circ.assembly.mapping, TAU, transcript_repr=123456789)
+    assert plonk.create_proof(ctx, c, inst, d_adv, seed=31) == PR.create_proof(opk, circ.instances, circ.advice, seed=31)
+    assert plonk.create_proof(ctx, a, inst, d_adv, seed=32) == PR.create_proof(opk, circ.instances, circ.advice, seed=32)
+    c.free(); a.free()
+    d_adv.free(); params.free()
+
+
+def test_key_material_is_freed_exactly_once(ctx, pkg, plonk, oracle):
+    """16 rounds of keygen, one clone, free both — the clone first in even rounds, the key first in odd ones — leave the
+    device's free memory where it was, to within less than ONE key's material: a material that was never freed would take
+    16 times that, one freed twice would fault. The material's bytes are what keygen allocates for the shape (keygen.hip
+    alloc_key_material): per row of n the fixed columns' Lagrange values and coefficients, the sigma columns' likewise, the
+    identity permutation and the powers of omega; per row of ext = (cs_degree - 1) * n the cosets of the fixed, sigma and
+    identity columns and l_0, l_last, l_active and X. k = 12 makes that more than 8 MiB, far above the allocator's
+    granularity. One round runs before the first reading: the ctx's own scratch only grows, and has grown by then."""
+    import torch
+
+    k = 12
+    c = circuits.lookup_circuit(plonk, k, seed=2)
+    F, S, n = c.desc["num_fixed"], len(c.desc["permutation_columns"]), 1 << k
+    ext = (c.desc["cs_degree"] - 1) * n
+    material = 32 * ((2 * F + 3 * S + 1) * n + (F + 2 * S + 4) * ext)
+    assert material >= 8 << 20
+    params = pkg.kzg.ParamsKZG.setup(ctx, k, zu.fr_from_int(TAU))
+    fixed = np.stack([zu.ints_to_fr(oracle, col) for col in c.fixed])
+
+    def one_round(key_first):
+        pk = plonk.ProvingKey(ctx, params, c.desc, fixed, c.assembly.mapping, zu.fr_from_int(123456789))
+        clone = pk.clone_workspace()
+        for h in ((pk, clone) if key_first else (clone, pk)):
+            h.free()
+
+    one_round(False)
+    before = torch.cuda.mem_get_info(0)[0]
+    for r in range(16):
+        one_round(r % 2 == 1)
+    after = torch.cuda.mem_get_info(0)[0]
+    print("free before %d, after %d, one key's material %d" % (before, after, material))
+    assert before - after < material
+    params.free()
 
 
 def test_create_proof_argument_errors_leave_the_context_usable(ctx, pkg, plonk, oracle):
