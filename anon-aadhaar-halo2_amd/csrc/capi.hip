@@ -208,11 +208,11 @@ static std::atomic<bool> g_blocking_note_given{false};
 
 extern "C" {
 
-int amdzk_version(void) { return 1011; }
+int amdzk_version(void) { return 1012; }
 
 // "amdzk <abi> src=<hash of the comment-stripped kernel sources and the Makefile> arch=gfx950": what this binary was built
 // from. bench.py refuses a library whose stamp is not its tree's bench.kernel_src_hash().
-const char* amdzk_build_info(void) { return "amdzk 1011 src=" AMDZK_SRC_HASH " arch=gfx950"; }
+const char* amdzk_build_info(void) { return "amdzk 1012 src=" AMDZK_SRC_HASH " arch=gfx950"; }
 
 int amdzk_init(int device_id, amdzk_ctx** out) {
   if (!out) return AMDZK_E_INVALID;
@@ -433,6 +433,12 @@ int amdzk_srs_read(amdzk_ctx* ctx, const uint8_t* data, size_t len, amdzk_srs** 
   ZK_ENTER(ctx);
   if (!ctx) return AMDZK_E_INVALID;
   return zk_srs_read(ctx, data, len, out, g2_out, s_g2_out);
+}
+int amdzk_srs_check(amdzk_ctx* ctx, const amdzk_srs* srs, const uint64_t g2[16], const uint64_t s_g2[16], const amdzk_srs_check_opts* opts,
+                    amdzk_srs_report* report) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  return zk_srs_check(ctx, srs, g2, s_g2, opts, report);
 }
 void amdzk_srs_free(amdzk_ctx* ctx, amdzk_srs* srs) {
   ZK_ENTER(ctx);

@@ -268,6 +268,8 @@ int zk_srs_downsize(amdzk_ctx* ctx, const amdzk_srs* srs, uint32_t new_k, const 
 int zk_srs_get(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, uint64_t* out);
 int zk_srs_write(amdzk_ctx* ctx, const amdzk_srs* s, const uint8_t g2[64], const uint8_t s_g2[64], uint8_t* out, size_t cap);
 int zk_srs_read(amdzk_ctx* ctx, const uint8_t* data, size_t len, amdzk_srs** out, uint8_t g2_out[64], uint8_t s_g2_out[64]);
+int zk_srs_check(amdzk_ctx* ctx, const amdzk_srs* s, const uint64_t g2[16], const uint64_t s_g2[16], const amdzk_srs_check_opts* opts,
+                 amdzk_srs_report* rep);
 
 // pairing.hip: amdzk_pairing_products on host G1 points, refusals prefixed with `who`
 int zk_pairing_products(amdzk_ctx* ctx, const char* who, const amdzk_g2* const* qs, size_t m, const bn254::G1Affine* h_g1, size_t n, uint8_t* is_one,

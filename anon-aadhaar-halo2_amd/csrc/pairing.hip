@@ -1,4 +1,5 @@
-// The pairing unit (include/amdzk.h "pairing"): amdzk_g2_prepare / amdzk_g2_setup (host half, pairing.hpp)
+// The pairing unit (include/amdzk.h "pairing"): amdzk_g2_prepare / amdzk_g2_setup (host half, pairing.hpp),
+// the SRS file's G2 codec and membership test (amdzk_g2_compress / _decompress / _check: host only, g2codec.hpp)
 // and amdzk_pairing_products — n independent products of m pairings over the same m prepared G2 points — as two launches:
 // one lane per (check, pair) runs the Miller program over that pair's prepared lines (no G2 arithmetic on the device), one
 // lane per check multiplies its m Miller values, runs the final-exponentiation program and compares with one. A lane's
@@ -11,6 +12,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "g2codec.hpp"
 #include "pairing.hpp"
 
 using namespace bn254;
@@ -210,6 +212,28 @@ extern "C" int amdzk_g2_setup(amdzk_ctx* ctx, const uint64_t s[4], uint64_t g2_o
   const pairing::G2Affine g = pairing::g2_generator();
   pairing::g2_to_words(g, g2_out);
   pairing::g2_to_words(pairing::g2_mul(g, kw), s_g2_out);
+  return AMDZK_OK;
+}
+
+// ---- the SRS file's G2 fields and membership in G2: g2codec.hpp behind the C ABI. No ctx, no device.
+static int g2_codec_result(const char* who, const char* why, char* msg, size_t msg_cap) {
+  if (msg && msg_cap) {
+    if (why) snprintf(msg, msg_cap, "%s: %s", who, why);
+    else msg[0] = 0;
+  }
+  return why ? AMDZK_E_INVALID : AMDZK_OK;
+}
+extern "C" int amdzk_g2_compress(const uint64_t q[16], uint8_t out[64], char* msg, size_t msg_cap) {
+  if (!q || !out) return g2_codec_result("g2_compress", "null argument", msg, msg_cap);
+  return g2_codec_result("g2_compress", g2codec::g2_compress(q, out), msg, msg_cap);
+}
+extern "C" int amdzk_g2_decompress(const uint8_t in[64], uint64_t q_out[16], char* msg, size_t msg_cap) {
+  if (!in || !q_out) return g2_codec_result("g2_decompress", "null argument", msg, msg_cap);
+  return g2_codec_result("g2_decompress", g2codec::g2_decompress(in, q_out), msg, msg_cap);
+}
+extern "C" int amdzk_g2_check(const uint64_t q[16], int* status) {
+  if (!q || !status) return AMDZK_E_INVALID;
+  *status = g2codec::g2_status(q);
   return AMDZK_OK;
 }
 

@@ -1,10 +1,12 @@
 // The whole life of an amdzk_srs (srs.hpp): poly::kzg::commitment::ParamsKZG::{new, setup, write, read, downsize, get_g}
-// and arithmetic::g_to_lagrange of halo2_proofs 0.2.0 [UP], and the prefix-sum basis
-// the permutation products are committed over. Start-up work, all of it on the device, in the 32-bit radix-2^256 form of
-// bn254.cuh; the window tables behind the bases are msm.hip's (zk_msm_fill_table) and so is their radix.
+// and arithmetic::g_to_lagrange of halo2_proofs 0.2.0 [UP], the prefix-sum basis
+// the permutation products are committed over, and the check that an SRS is one (amdzk_srs_check). Start-up work, all of
+// it on the device, in the 32-bit radix-2^256 form of bn254.cuh; the window tables behind the bases are msm.hip's
+// (zk_msm_fill_table) and so is their radix.
 #include <stdlib.h>
 #include <string.h>
 
+#include "hostcrypto.hpp"     // ChaCha20Rng, fr_omega
 #include "plonk_kernels.hpp"  // zk_batch_invert
 #include "srs.hpp"
 
@@ -253,6 +255,46 @@ __global__ __launch_bounds__(256) void g1_decompress_kernel(const uint8_t* in, G
   if (!ok) atomicExch(err, 1);
   st_aff(out + i, p);
 }
+
+// amdzk_srs_check, CURVE: thread t < n tests g[t], thread n + t tests g_lagrange[t] (a basis that is not resident is null
+// and its threads leave): coordinates below q, y^2 = x^3 + 3, not (0, 0). *first, preset to all ones, receives the smallest
+// basis << 32 | index of an offending point. Memory-bound: four 16-byte loads and five products a point.
+__global__ __launch_bounds__(256) void srs_check_curve_kernel(const G1Affine* g, const G1Affine* g_lagrange, size_t n, unsigned long long* first) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= 2 * n) return;
+  const unsigned long long basis = t >= n ? 1 : 0, i = t - basis * n;
+  const G1Affine* src = basis ? g_lagrange : g;
+  if (!src) return;
+  const G1Affine p = ld_aff(src + i);
+  const bool ok = is_canonical(p.x) && is_canonical(p.y) && !p.is_inf() && sqr(p.y) == g1_curve_rhs(p.x);
+  if (!ok) atomicMin(first, basis << 32 | i);
+}
+
+// amdzk_srs_check's scalar columns, n each, from E[i] = rho^i: colA = (E[0] ... E[n-2], 0), colB = (0, E[0] ... E[n-2]),
+// colC = colE = E (colC then goes through the inverse NTT). A thread takes `chunk` consecutive i, as in powers_kernel.
+__device__ __forceinline__ void st_fr(Fr* p, const Fr& v) {
+  uint4* q = reinterpret_cast<uint4*>(p);
+  q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
+  q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
+}
+__global__ void srs_check_columns_kernel(Fr* colA, Fr* colB, Fr* colC, Fr* colE, Fr rho, size_t n, uint32_t chunk) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x, start = t * chunk;
+  if (start >= n) return;
+  const size_t end = start + chunk < n ? start + chunk : n;
+  Fr cur = pow_u64(rho, start);
+  if (start == 0) st_fr(colB, Fr::zero());
+  for (size_t i = start; i < end; i++) {
+    st_fr(colC + i, cur);
+    st_fr(colE + i, cur);
+    if (i + 1 < n) {  // the pairs (g[i], g[i+1]) end at i = n - 2
+      st_fr(colA + i, cur);
+      st_fr(colB + i + 1, cur);
+    } else {
+      st_fr(colA + i, Fr::zero());
+    }
+    cur = mul(cur, rho);
+  }
+}
 }  // namespace
 
 size_t zk_srs_serialized_size(uint32_t k) { return 4 + 2 * ((size_t)32 << k) + 128; }
@@ -297,6 +339,128 @@ int zk_srs_read(amdzk_ctx* ctx, const uint8_t* data, size_t len, amdzk_srs** out
   if (g2_out) memcpy(g2_out, data + 4 + 2 * n * 32, 64);
   if (s_g2_out) memcpy(s_g2_out, data + 4 + 2 * n * 32 + 64, 64);
   return srs_build(ctx, pts, pts + n, true, k, out);
+}
+
+// ---- amdzk_srs_check (include/amdzk.h states the checks, their order and the soundness bound): the curve test
+// above, four scalar columns, the inverse NTT of one of them, the table MSM (A, B, C over g in one submission, E over
+// g_lagrange), and one product of two pairings with g2 / s_g2 prepared and freed here.
+namespace {
+void jac_to_affine_words(const uint64_t jac[12], uint64_t out[8]) {  // zk_msm_finish's normal form: z = 1, or the identity
+  const G1Jac* p = reinterpret_cast<const G1Jac*>(jac);
+  if (p->z.is_zero()) memset(out, 0, 64);
+  else memcpy(out, jac, 64);
+}
+
+int srs_check_run(amdzk_ctx* ctx, const amdzk_srs* s, const uint64_t g2[16], const uint64_t s_g2[16], uint32_t checks, const Fr& rho,
+                  amdzk_srs_report* rep) {
+  const size_t n = s->n;
+  const G1Affine *g = s->base[AMDZK_BASIS_G], *gl = s->base[AMDZK_BASIS_G_LAGRANGE];
+  {  // G2: host. The statuses are filled either way: POWERS depends on them.
+    int st[2] = {0, 0};
+    amdzk_g2_check(g2, &st[0]);
+    amdzk_g2_check(s_g2, &st[1]);
+    rep->g2_status[0] = (uint32_t)st[0], rep->g2_status[1] = (uint32_t)st[1];
+    if (checks & AMDZK_SRS_CHECK_G2) {
+      rep->ran |= AMDZK_SRS_CHECK_G2;
+      if (st[0] || st[1]) rep->failed |= AMDZK_SRS_CHECK_G2;
+    }
+  }
+  // slot 2, not this unit's slot 3: the pairing reserves that one while colE is still to be read
+  char* ws = nullptr;  // first offender (256 bytes) | colA[n] | colB[n] | colC[n] | colE[n]
+  ZK_TRY(zk_ws_reserve(ctx, 2, 256 + 4 * n * sizeof(Fr), (void**)&ws));
+  unsigned long long* d_first = (unsigned long long*)ws;
+  Fr *colA = (Fr*)(ws + 256), *colB = colA + n, *colC = colB + n, *colE = colC + n;
+  if (checks & AMDZK_SRS_CHECK_CURVE) {
+    unsigned long long first = ~0ull;
+    ZK_HIP(ctx, hipMemsetAsync(d_first, 0xFF, sizeof(first), ctx->stream));
+    ZK_LAUNCH(ctx, "srs_check_curve", srs_check_curve_kernel, dim3((unsigned)((2 * n + 255) / 256)), dim3(256), 0, g, gl, n, d_first);
+    ZK_HIP(ctx, hipMemcpyAsync(&first, d_first, sizeof(first), hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
+    rep->ran |= AMDZK_SRS_CHECK_CURVE;
+    if (first != ~0ull) {
+      rep->failed |= AMDZK_SRS_CHECK_CURVE;
+      rep->curve_basis = (uint32_t)(first >> 32);
+      rep->curve_index = first & 0xFFFFFFFFull;
+      return AMDZK_OK;  // the sums over off-curve points mean nothing
+    }
+  }
+  const bool powers = (checks & AMDZK_SRS_CHECK_POWERS) && g && !rep->g2_status[0] && !rep->g2_status[1];
+  if (!powers) return AMDZK_OK;  // and LAGRANGE is sound only given POWERS
+  const bool lagrange = (checks & AMDZK_SRS_CHECK_LAGRANGE) && gl;
+  const uint32_t chunk = 64;
+  ZK_LAUNCH(ctx, "srs_check_columns", srs_check_columns_kernel, dim3((unsigned)(((n + chunk - 1) / chunk + 63) / 64)), dim3(64), 0, colA, colB, colC,
+            colE, rho, n, chunk);
+  if (lagrange) {
+    const Fr omega_inv = inv(zkhost::fr_omega(s->k));
+    uint64_t w[4];
+    memcpy(w, omega_inv.l, 32);
+    ZK_TRY(zk_ntt_dev(ctx, colC, s->k, w, AMDZK_NTT_SCALE_NINV, 1, n));
+  }
+  alignas(16) uint64_t jac[3 * 12];
+  G1X* d_res = nullptr;
+  ZK_TRY(zk_msm_dev_xyzz(ctx, s, AMDZK_BASIS_G, colA, lagrange ? 3 : 2, n, n, &d_res));
+  ZK_TRY(zk_msm_finish(ctx, d_res, lagrange ? 3 : 2, jac));
+  for (int j = 0; j < (lagrange ? 3 : 2); j++) jac_to_affine_words(jac + 12 * j, rep->points + 8 * j);
+  G1Affine ab[2];  // A, -B
+  memcpy(&ab[0], rep->points, 64);
+  memcpy(&ab[1], rep->points + 8, 64);
+  ab[1] = a_neg(ab[1]);
+  rep->ran |= AMDZK_SRS_CHECK_POWERS;
+  if (n > 1) {  // n = 1 has no pair (g[i], g[i+1]): passes vacuously
+    bool ok = !ab[0].is_inf() && !ab[1].is_inf();
+    if (ok) {
+      amdzk_g2* q[2] = {nullptr, nullptr};  // e(A, s_g2) e(-B, g2)
+      int r = amdzk_g2_prepare(ctx, s_g2, &q[0]);
+      if (r == AMDZK_OK) r = amdzk_g2_prepare(ctx, g2, &q[1]);
+      uint8_t one = 0;
+      if (r == AMDZK_OK) r = zk_pairing_products(ctx, "srs_check", q, 2, ab, 1, &one, nullptr);
+      const std::string keep = ctx->err;
+      if (r != AMDZK_OK) (void)zk_host_wait(ctx, ctx->stream);
+      amdzk_g2_free(ctx, q[0]);
+      amdzk_g2_free(ctx, q[1]);
+      ctx->err = keep;
+      ZK_TRY(r);
+      ok = one != 0;
+    }
+    if (!ok) {
+      rep->failed |= AMDZK_SRS_CHECK_POWERS;
+      return AMDZK_OK;
+    }
+  }
+  if (!lagrange) return AMDZK_OK;
+  ZK_TRY(zk_msm_dev_xyzz(ctx, s, AMDZK_BASIS_G_LAGRANGE, colE, 1, n, n, &d_res));
+  ZK_TRY(zk_msm_finish(ctx, d_res, 1, jac));
+  jac_to_affine_words(jac, rep->points + 24);
+  rep->ran |= AMDZK_SRS_CHECK_LAGRANGE;
+  if (memcmp(rep->points + 16, rep->points + 24, 64) != 0) rep->failed |= AMDZK_SRS_CHECK_LAGRANGE;
+  return AMDZK_OK;
+}
+}  // namespace
+
+int zk_srs_check(amdzk_ctx* ctx, const amdzk_srs* s, const uint64_t g2[16], const uint64_t s_g2[16], const amdzk_srs_check_opts* opts,
+                 amdzk_srs_report* rep) {
+  if (!s || !g2 || !s_g2 || !rep) ZK_FAIL(ctx, AMDZK_E_INVALID, "srs_check: null argument");
+  if (opts && opts->size < sizeof(amdzk_srs_check_opts))
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "srs_check: amdzk_srs_check_opts.size is %zu, this library needs %zu", opts->size, sizeof(amdzk_srs_check_opts));
+  const uint32_t all = AMDZK_SRS_CHECK_G2 | AMDZK_SRS_CHECK_CURVE | AMDZK_SRS_CHECK_POWERS | AMDZK_SRS_CHECK_LAGRANGE;
+  const uint32_t checks = opts && opts->checks ? opts->checks : all;
+  if (checks & ~all) ZK_FAIL(ctx, AMDZK_E_INVALID, "srs_check: unknown check bits 0x%x", checks & ~all);
+  Fr rho;
+  if (opts && opts->rho) {
+    memcpy(rho.l, opts->rho, 32);
+    if (!is_canonical(rho)) ZK_FAIL(ctx, AMDZK_E_INVALID, "srs_check: rho is not below the modulus (rho >= r)");
+  } else {
+    zkhost::ChaCha20Rng rng(opts ? opts->seed : 0);
+    rho = rng.fr();
+  }
+  memset(rep, 0, sizeof(*rep));
+  const int r = srs_check_run(ctx, s, g2, s_g2, checks, rho, rep);
+  if (r != AMDZK_OK) {  // whatever was enqueued is finished before the call returns
+    const std::string keep = ctx->err;
+    (void)zk_host_wait(ctx, ctx->stream);
+    ctx->err = keep;
+  }
+  return r;
 }
 
 // ---- arithmetic::g_to_lagrange(g, k) and ParamsKZG::downsize(k) [UP]:

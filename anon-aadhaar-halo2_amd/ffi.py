@@ -124,7 +124,11 @@ def lib():
         "amdzk_g2_prepare": (i32, [vp, vp, C.POINTER(vp)]),
         "amdzk_g2_free": (None, [vp, vp]),
         "amdzk_g2_setup": (i32, [vp, vp, vp, vp]),
+        "amdzk_g2_compress": (i32, [vp, vp, vp, sz]),
+        "amdzk_g2_decompress": (i32, [vp, vp, vp, sz]),
+        "amdzk_g2_check": (i32, [vp, C.POINTER(i32)]),
         "amdzk_pairing_products": (i32, [vp, C.POINTER(vp), sz, vp, sz, vp, vp]),
+        "amdzk_srs_check": (i32, [vp, vp, vp, vp, vp, vp]),
         "amdzk_verify_proofs_decide": (i32, [vp, vp, vp, vp, u32, sz, C.POINTER(C.POINTER(vp)), C.POINTER(C.POINTER(sz)), C.POINTER(vp), C.POINTER(sz),
                                              vp, vp, vp, C.POINTER(sz)]),
         "amdzk_keygen_vk": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]),
@@ -192,6 +196,15 @@ class CheckFailure(C.Structure):  # amdzk_check_failure
 
 class CheckOpts(C.Structure):  # amdzk_check_opts
     _fields_ = [("size", C.c_size_t), ("theta_seed", C.c_uint64), ("challenges", C.c_void_p), ("num_challenges", C.c_uint32)]
+
+
+class SrsCheckOpts(C.Structure):  # amdzk_srs_check_opts
+    _fields_ = [("size", C.c_size_t), ("checks", C.c_uint32), ("seed", C.c_uint64), ("rho", C.c_void_p)]
+
+
+class SrsReport(C.Structure):  # amdzk_srs_report
+    _fields_ = [("ran", C.c_uint32), ("failed", C.c_uint32), ("g2_status", C.c_uint32 * 2), ("curve_basis", C.c_uint32), ("reserved", C.c_uint32),
+                ("curve_index", C.c_uint64), ("points", C.c_uint64 * 32)]
 
 
 class ProofStatus(C.Structure):  # amdzk_proof_status

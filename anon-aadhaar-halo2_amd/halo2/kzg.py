@@ -1,5 +1,6 @@
 """Mirror of halo2_proofs::poly::kzg::commitment::ParamsKZG (v2023_01_20 [UP]) — the resident part."""
 import ctypes as C
+import secrets
 
 import numpy as np
 
@@ -65,6 +66,20 @@ class ParamsKZG:
         self.h = h
         return self, bytes(g2), bytes(s_g2)
 
+    def check(self, g2, s_g2, seed=None, rho=None, checks=0):
+        """amdzk_srs_check: is this SRS an SRS? g2, s_g2: (16,) uint64 points, e.g. g2_from_bytes of the file's fields.
+        checks: SRS_CHECK_* bits, 0 = all. rho ((4,) uint64 Montgomery Fr, < r) wins over seed; seed=None draws 64 bits from
+        the OS generator (`secrets`). Returns the report (ffi.SrsReport): consistent iff report.failed == 0 and report.ran
+        covers what was asked; report.points holds A, B, C, E as four G1Affine."""
+        g2 = np.ascontiguousarray(g2, dtype=np.uint64).reshape(16)
+        s_g2 = np.ascontiguousarray(s_g2, dtype=np.uint64).reshape(16)
+        r = None if rho is None else np.ascontiguousarray(rho, dtype=np.uint64).reshape(4)
+        opts = _ffi.SrsCheckOpts(C.sizeof(_ffi.SrsCheckOpts), checks, secrets.randbits(64) if seed is None else seed,
+                                 None if r is None else r.ctypes.data)
+        rep = _ffi.SrsReport()
+        self.ctx._chk(self.ctx.L.amdzk_srs_check(self.ctx.h, self.h, _ptr(g2), _ptr(s_g2), C.byref(opts), C.byref(rep)))
+        return rep
+
     def downsize(self, k):
         """ParamsKZG::downsize(k): shrink in place to 2^k — g truncated, g_lagrange recomputed on the
         device with g_to_lagrange."""
@@ -102,6 +117,48 @@ class ParamsKZG:
 
 # ---- the G2 side and the pairing (include/amdzk.h "pairing"; conventions: csrc/fq12.cuh)
 PAIRING_MAX_M = 16  # AMDZK_PAIRING_MAX_M
+SRS_CHECK_G2, SRS_CHECK_CURVE, SRS_CHECK_POWERS, SRS_CHECK_LAGRANGE = 1, 2, 4, 8  # AMDZK_SRS_CHECK_*
+SRS_CHECK_ALL = 15
+# amdzk_g2_check's statuses
+G2_IN_GROUP, G2_COORD_TOO_LARGE, G2_OFF_TWIST, G2_IDENTITY, G2_OUTSIDE_SUBGROUP = range(5)
+_G2_STATUS = ("in G2", "a coordinate is not below the modulus", "not on the twist", "the identity", "on the twist, outside the order-r subgroup")
+
+
+def _g2_codec(fn, arg):
+    msg = C.create_string_buffer(256)
+    rc = fn(arg, msg)
+    if rc != 0:
+        raise _ffi.AmdzkError(rc, msg.value.decode())
+
+
+def g2_to_bytes(q):
+    """G2Affine::to_bytes (halo2curves' G2Compressed, the g2 / s_g2 fields of the ParamsKZG file): (16,) uint64 -> 64 bytes.
+    Host only, no Context. Refused: a coordinate >= q, a point off the twist. The identity is 64 zero bytes."""
+    q = np.ascontiguousarray(q, dtype=np.uint64).reshape(16)
+    out = (C.c_uint8 * 64)()
+    _g2_codec(lambda a, msg: _ffi.lib().amdzk_g2_compress(a, out, msg, 256), _ptr(q))
+    return bytes(out)
+
+
+def g2_from_bytes(b):
+    """G2Affine::from_bytes: 64 bytes -> (16,) uint64 (all zero = the identity). Host only. Refused: x >= q, x = 0 with the
+    sign bit set, an x no point of the twist has. The point is on the twist; membership in G2 is g2_check's business."""
+    if len(b) != 64:
+        raise _ffi.AmdzkError(-2, "g2_decompress: %d bytes given, 64 needed" % len(b))
+    raw = (C.c_uint8 * 64).from_buffer_copy(bytes(b))
+    q = np.zeros(16, np.uint64)
+    _g2_codec(lambda a, msg: _ffi.lib().amdzk_g2_decompress(a, _ptr(q), msg, 256), raw)
+    return q
+
+
+def g2_check(q):
+    """amdzk_g2_check: G2_IN_GROUP (0), G2_COORD_TOO_LARGE, G2_OFF_TWIST, G2_IDENTITY or G2_OUTSIDE_SUBGROUP. Host only."""
+    q = np.ascontiguousarray(q, dtype=np.uint64).reshape(16)
+    st = C.c_int(-1)
+    rc = _ffi.lib().amdzk_g2_check(_ptr(q), C.byref(st))
+    if rc != 0:
+        raise _ffi.AmdzkError(rc, "g2_check: null argument")
+    return st.value
 
 
 class G2Prepared:
@@ -162,6 +219,19 @@ class ParamsVerifierKZG:
     @classmethod
     def setup(cls, ctx, s):
         return cls(ctx, *g2_setup(ctx, s))
+
+    @classmethod
+    def from_bytes(cls, ctx, g2_bytes, s_g2_bytes):
+        """From the two 64-byte fields of a ParamsKZG file (ParamsKZG.read): both are decompressed and must be in G2
+        (g2_check status 0) — the zero fields of a file written without G2 points are refused as the identity."""
+        pts = []
+        for name, b in (("g2", g2_bytes), ("s_g2", s_g2_bytes)):
+            q = g2_from_bytes(b)
+            st = g2_check(q)
+            if st != G2_IN_GROUP:
+                raise _ffi.AmdzkError(-2, "ParamsVerifierKZG.from_bytes: %s is %s" % (name, _G2_STATUS[st]))
+            pts.append(q)
+        return cls(ctx, *pts)
 
     def free(self):
         self.g2.free()

@@ -749,9 +749,25 @@ typedef struct amdzk_g2 amdzk_g2;
 int amdzk_g2_prepare(amdzk_ctx* ctx, const uint64_t q[16], amdzk_g2** out);
 void amdzk_g2_free(amdzk_ctx* ctx, amdzk_g2* g2);
 /* The G2 half of ParamsKZG::setup [UP] with the caller's trapdoor s (Montgomery, as for amdzk_srs_setup, and as unsafe):
- * g2 = the generator, s_g2 = s * g2. Host work. The 64-byte compressed G2 encoding of the SRS file is NOT produced here:
- * amdzk_srs_write / amdzk_srs_read keep passing those fields through. */
+ * g2 = the generator, s_g2 = s * g2. Host work. The 64-byte compressed G2 encoding of the SRS file is NOT produced here
+ * (amdzk_g2_compress below makes it): amdzk_srs_write / amdzk_srs_read keep passing those fields through. */
 int amdzk_g2_setup(amdzk_ctx* ctx, const uint64_t s[4], uint64_t g2_out[16], uint64_t s_g2_out[16]);
+/* The 64-byte G2 fields of the SRS file <-> G2Affine words, and membership in G2. Pure host code with no ctx,
+ * callable without a device (csrc/g2codec.hpp). The format is halo2curves 0.3.1's G2Compressed, made by the macro that makes the
+ * 32-byte G1 form of amdzk_srs_write: bytes 0-31 x.c0 and bytes 32-63 x.c1, canonical little-endian; bit 7 of byte 63 = the
+ * parity of the canonical y.c0; bit 6 of byte 63 is always 0 (x.c1 < q < 2^254); 64 zero bytes <-> the identity (16 zero words).
+ * Like the G1 sign bit the convention is recalled, not pinned by a fixture.
+ * amdzk_g2_compress refuses what amdzk_g2_prepare refuses except the identity: a coordinate >= q, a point off the twist.
+ * amdzk_g2_decompress clears bit 7, refuses an x.c0 or x.c1 >= q (a set bit 6 is one), gives the identity for x = 0 with a clear
+ * sign bit and refuses x = 0 with the bit set; otherwise y = sqrt(x^3 + 3/xi) in Fq2 with the root whose y.c0 has the bit's
+ * parity, and a non-residue is refused. The result is on the twist; membership in G2 is amdzk_g2_check's business.
+ * Every refusal is AMDZK_E_INVALID with a message that starts "g2_compress:" / "g2_decompress:", written NUL-terminated into
+ * msg (msg_cap bytes; msg may be NULL); "" on success.
+ * amdzk_g2_check: *status = 0 in G2 | 1 a coordinate >= q | 2 not on the twist | 3 the identity | 4 on the twist, outside the
+ * order-r subgroup ([r]Q != O: the definition, 254 doublings on the host). Returns AMDZK_E_INVALID for a null argument only. */
+int amdzk_g2_compress(const uint64_t q[16], uint8_t out[64], char* msg, size_t msg_cap);
+int amdzk_g2_decompress(const uint8_t in[64], uint64_t q_out[16], char* msg, size_t msg_cap);
+int amdzk_g2_check(const uint64_t q[16], int* status);
 /* n independent products over the same m prepared points: gt_i = prod_{j<m} e(P[i*m + j], Q_j).
  * g1: n*m G1Affine (host); (0,0) = the identity, which contributes the factor 1 — so a product whose G1 entries are ALL the
  * identity is 1 and reads is_one = 1. Points are NOT checked to be on the curve (as the MSM's bases).
@@ -763,6 +779,54 @@ int amdzk_g2_setup(amdzk_ctx* ctx, const uint64_t s[4], uint64_t g2_out[16], uin
 #define AMDZK_PAIRING_MAX_M 16
 int amdzk_pairing_products(amdzk_ctx* ctx, const amdzk_g2* const* qs, size_t m, const uint64_t* g1, size_t n, uint8_t* is_one,
                            uint64_t* gt_out);
+/* Is this SRS an SRS? The structure of the resident g / g_lagrange against the file's g2 / s_g2 (G2Affine words, e.g. from
+ * amdzk_g2_decompress), checked on the device with the table MSM, the NTT and the pairing. With n = 2^k and a
+ * random rho:  A = sum_{i<=n-2} rho^i g[i],  B = sum_{i<=n-2} rho^i g[i+1],  C = sum_j c_j g[j] with c = the coefficients of the
+ * polynomial that is rho^i at omega^i (inverse NTT with the domain's omega^-1 and 1/n),  E = sum_i rho^i g_lagrange[i].
+ *   AMDZK_SRS_CHECK_G2       amdzk_g2_check gives status 0 for g2 and for s_g2 (host).
+ *   AMDZK_SRS_CHECK_CURVE    every resident g[i], g_lagrange[i] has coordinates < q, is on y^2 = x^3 + 3 and is not (0, 0);
+ *                            report->curve_basis / curve_index name the first offender, G before G_LAGRANGE, smallest index.
+ *   AMDZK_SRS_CHECK_POWERS   A and B are not the identity and e(A, s_g2) e(-B, g2) = 1. n = 1 has no pair g[i], g[i+1]: the
+ *                            check ran and passes vacuously (A = B = the identity).
+ *   AMDZK_SRS_CHECK_LAGRANGE C = E as points.
+ * Order and dependence: G2, then CURVE, then POWERS, then LAGRANGE. A check that cannot mean anything is NOT RUN, its bit of
+ * report->ran stays clear: POWERS and LAGRANGE when CURVE was run and failed (an MSM over off-curve points means nothing);
+ * POWERS when g2 or s_g2 has a non-zero amdzk_g2_check status (report->g2_status is filled whether or not G2 was asked for);
+ * LAGRANGE when POWERS was not run or failed (it is sound only given POWERS); and any check that reads a basis which is not
+ * resident (amdzk_srs_upload with a NULL pointer) — CURVE goes over the bases that are. The SRS is consistent iff
+ * report->failed == 0 and report->ran covers what was asked. report->points: A, B, C, E as G1Affine, (0, 0) = the identity,
+ * zero where the sum was not computed: for tests and diagnosis.
+ * Soundness (derived, not measured). If some g[i+1] != s g[i] (s defined by s_g2 = s g2), the discrete logarithm of B - s A is
+ * a non-zero polynomial of degree <= n - 2 in rho. Given POWERS, g[j] = s^j g[0] and C = p(s) g[0] for the polynomial p above,
+ * while E = sum_i rho^i g_lagrange[i]: a wrong g_lagrange[i] makes E - C a non-zero polynomial of degree <= n - 1 in rho. So a
+ * bad SRS passes with probability at most (2n - 3)/r over rho — for a rho that whoever made the file could not know. rho is the
+ * first Fr::random of ChaCha20Rng::seed_from_u64(opts->seed) (as amdzk_check_opts.theta_seed), so a 64-bit seed from the OS
+ * generator bounds a guessing adversary at 2^-64; pass opts->rho (4 words, Montgomery, < r; wins if set) for the full bound.
+ * Not checked: the derived prefix-sum basis and the window tables, which are the library's own work.
+ * Returns AMDZK_OK whenever it ran, whatever it found (as amdzk_check_witness). Refused with AMDZK_E_INVALID and "srs_check:":
+ * null srs / g2 / s_g2 / report, an opts->size below this library's, unknown check bits, rho >= r; the ctx stays usable. Runs
+ * on the ctx's stream and returns with it idle. */
+#define AMDZK_SRS_CHECK_G2       1u
+#define AMDZK_SRS_CHECK_CURVE    2u
+#define AMDZK_SRS_CHECK_POWERS   4u
+#define AMDZK_SRS_CHECK_LAGRANGE 8u
+typedef struct amdzk_srs_check_opts {
+  size_t size;         /* sizeof(amdzk_srs_check_opts) as compiled by the caller; too small is refused */
+  uint32_t checks;     /* AMDZK_SRS_CHECK_* bits; 0 = all */
+  uint64_t seed;       /* rho = first Fr::random of ChaCha20Rng::seed_from_u64(seed) ... */
+  const uint64_t* rho; /* ... or the caller's own, 4 words Montgomery, < r; wins if set */
+} amdzk_srs_check_opts;
+typedef struct amdzk_srs_report {
+  uint32_t ran;           /* bit per check that ran */
+  uint32_t failed;        /* bit per check that ran and failed */
+  uint32_t g2_status[2];  /* amdzk_g2_check of g2, s_g2 */
+  uint32_t curve_basis;   /* CURVE failed: AMDZK_BASIS_G or AMDZK_BASIS_G_LAGRANGE of the first offending point ... */
+  uint32_t reserved;
+  uint64_t curve_index;   /* ... and its index; 0, 0 otherwise */
+  uint64_t points[32];    /* A, B, C, E */
+} amdzk_srs_report;
+int amdzk_srs_check(amdzk_ctx* ctx, const amdzk_srs* srs, const uint64_t g2[16], const uint64_t s_g2[16],
+                    const amdzk_srs_check_opts* opts /* NULL: all checks, seed 0 */, amdzk_srs_report* report);
 /* plonk::verify_proof [UP] with a verdict per proof, in one call: amdzk_verify_proofs and the pairing(s) behind it.
  * s_g2, g2: the prepared [s]_2 and [1]_2 of the SRS the key was made on (amdzk_g2_setup, or the caller's own points).
  * flags = 0 — every proof by itself with weight 1, as SingleStrategy would:

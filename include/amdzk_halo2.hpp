@@ -28,6 +28,7 @@
 #include <exception>
 #include <functional>
 #include <map>
+#include <random>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -554,6 +555,8 @@ struct G1 {
   uint64_t x[4], y[4], z[4];  // Jacobian, z = 0 identity; results come back with z = 1
 };
 
+struct G2Affine;  // below, beside the pairing
+
 class ParamsKZG {
  public:
   ParamsKZG(const Context& ctx, uint32_t k, const G1Affine* g, const G1Affine* g_lagrange) : ctx_(ctx), k_(k) {
@@ -585,6 +588,11 @@ class ParamsKZG {
     h_ = h;
     k_ = k;
   }
+  // amdzk_srs_check: is this SRS an SRS? g2 / s_g2 e.g. G2Affine::from_bytes of the file's two fields. rho (< r) wins over
+  // seed; with neither, 64 bits from std::random_device. checks: AMDZK_SRS_CHECK_* bits, 0 = all. Consistent iff
+  // report.failed == 0 and report.ran covers what was asked.
+  amdzk_srs_report check(const G2Affine& g2, const G2Affine& s_g2, const uint64_t* seed = nullptr, const Fr* rho = nullptr,
+                         uint32_t checks = 0) const;
   std::vector<G1Affine> get_g() const { return get(0); }
   std::vector<G1Affine> get_g_lagrange() const { return get(1); }
   G1 commit(const std::vector<Fr>& poly) const { return msm(0, poly); }            // blind ignored for KZG
@@ -1315,7 +1323,44 @@ inline Guard verify_proof(const Context& ctx, const ProvingKey& pk, const std::v
 // Montgomery; all zero is the identity.
 struct G2Affine {
   uint64_t w[16];
+  // halo2curves' G2Compressed, the g2 / s_g2 fields of the ParamsKZG file (amdzk_g2_compress / amdzk_g2_decompress): host only
+  std::array<uint8_t, 64> to_bytes() const {
+    std::array<uint8_t, 64> out;
+    char msg[256];
+    const int rc = amdzk_g2_compress(w, out.data(), msg, sizeof(msg));
+    if (rc != AMDZK_OK) throw Error(rc, msg);
+    return out;
+  }
+  static G2Affine from_bytes(const uint8_t bytes[64]) {
+    G2Affine q;
+    char msg[256];
+    const int rc = amdzk_g2_decompress(bytes, q.w, msg, sizeof(msg));
+    if (rc != AMDZK_OK) throw Error(rc, msg);
+    return q;
+  }
+  // amdzk_g2_check: 0 in G2 | 1 a coordinate >= q | 2 not on the twist | 3 the identity | 4 outside the order-r subgroup
+  int check() const {
+    int status = -1;
+    if (amdzk_g2_check(w, &status) != AMDZK_OK) throw Error(AMDZK_E_INVALID, "g2_check: null argument");
+    return status;
+  }
+  bool is_on_curve_and_in_subgroup() const { return check() == 0; }
 };
+inline amdzk_srs_report ParamsKZG::check(const G2Affine& g2, const G2Affine& s_g2, const uint64_t* seed, const Fr* rho, uint32_t checks) const {
+  amdzk_srs_check_opts opts;
+  opts.size = sizeof(opts);
+  opts.checks = checks;
+  opts.rho = rho ? rho->l : nullptr;
+  if (seed) {
+    opts.seed = *seed;
+  } else {
+    std::random_device rd;
+    opts.seed = ((uint64_t)rd() << 32) | (uint64_t)(uint32_t)rd();
+  }
+  amdzk_srs_report rep;
+  ctx_.check(amdzk_srs_check(ctx_.get(), h_, g2.w, s_g2.w, &opts, &rep));
+  return rep;
+}
 // halo2curves' G2Prepared: one finite point's line coefficients, resident on the device. Subgroup membership is not checked.
 class G2Prepared {
  public:
@@ -1336,6 +1381,18 @@ class G2Prepared {
 struct ParamsVerifierKZG {
   G2Prepared g2, s_g2;
   ParamsVerifierKZG(const Context& ctx, const G2Affine& g2_, const G2Affine& s_g2_) : g2(ctx, g2_), s_g2(ctx, s_g2_) {}
+  // from the two 64-byte fields of a ParamsKZG file (ParamsKZG::read): both decompressed, and both must be in G2 — the zero
+  // fields of a file written without G2 points are refused as the identity
+  ParamsVerifierKZG(const Context& ctx, const uint8_t g2_bytes[64], const uint8_t s_g2_bytes[64])
+      : ParamsVerifierKZG(ctx, member(g2_bytes, "g2"), member(s_g2_bytes, "s_g2")) {}
+  static G2Affine member(const uint8_t bytes[64], const char* name) {
+    static const char* const why[5] = {"in G2", "a coordinate is not below the modulus", "not on the twist", "the identity",
+                                       "on the twist, outside the order-r subgroup"};
+    const G2Affine q = G2Affine::from_bytes(bytes);
+    const int st = q.check();
+    if (st != 0) throw Error(AMDZK_E_INVALID, std::string("ParamsVerifierKZG: ") + name + " is " + why[st >= 0 && st < 5 ? st : 1]);
+    return q;
+  }
   // the G2 half of ParamsKZG::setup with the trapdoor given explicitly (tests / benchmarks, as unsafe as ParamsKZG::setup)
   static ParamsVerifierKZG setup(const Context& ctx, const Fr& s) {
     G2Affine g, sg;

@@ -17,11 +17,12 @@ OPAQUE = {"amdzk_ctx": "Ctx", "amdzk_srs": "Srs", "amdzk_domain": "Domain", "amd
           "amdzk_phases": "AmdzkPhases", "amdzk_transcript": "AmdzkTranscript", "amdzk_proof_opts": "AmdzkProofOpts",
           "amdzk_phase_fn": "AmdzkPhaseFn", "amdzk_batch_opts": "AmdzkBatchOpts", "amdzk_open_query": "AmdzkOpenQuery",
           "amdzk_multiopen_opts": "AmdzkMultiopenOpts", "amdzk_check_failure": "AmdzkCheckFailure", "amdzk_check_opts": "AmdzkCheckOpts",
-          "amdzk_proof_status": "AmdzkProofStatus", "amdzk_verify_opts": "AmdzkVerifyOpts"}
+          "amdzk_proof_status": "AmdzkProofStatus", "amdzk_verify_opts": "AmdzkVerifyOpts", "amdzk_srs_check_opts": "AmdzkSrsCheckOpts",
+          "amdzk_srs_report": "AmdzkSrsReport"}
 # structs and function-pointer types of the header that the block spells out as #[repr(C)] Rust (amdzk_circuit's
 # counterpart is written by hand in INTEGRATION.md, beside the code that fills it)
 GENERATED_TYPES = ("amdzk_phases", "amdzk_transcript", "amdzk_proof_opts", "amdzk_batch_opts", "amdzk_open_query", "amdzk_multiopen_opts",
-                   "amdzk_check_failure", "amdzk_check_opts", "amdzk_proof_status", "amdzk_verify_opts")
+                   "amdzk_check_failure", "amdzk_check_opts", "amdzk_proof_status", "amdzk_verify_opts", "amdzk_srs_check_opts", "amdzk_srs_report")
 SCALAR = {"int": "c_int", "uint32_t": "u32", "int32_t": "i32", "uint64_t": "u64", "size_t": "usize", "uint8_t": "u8", "float": "f32",
           "double": "f64", "char": "c_char", "void": "c_void"}
 
@@ -108,8 +109,9 @@ def types():
             if fp:
                 lines.append("    pub %s: %s," % (fp.group(2), fn_pointer(fp.group(1).strip(), fp.group(3))))
             else:
-                (name, rt), = params(field)
-                lines.append("    pub %s: %s," % (name, rt))
+                arr = re.search(r"\[\s*(\d+)\s*\]$", field)  # an array field is an array, not the pointer a parameter decays to
+                (name, rt), = params(field[:arr.start()] if arr else field)
+                lines.append("    pub %s: %s," % (name, "[%s; %s]" % (rt, arr.group(1)) if arr else rt))
         lines.append("}")
         out.append((m.start(), lines))
     return [lines for _, lines in sorted(out)]
