@@ -275,6 +275,12 @@ int zk_srs_check(amdzk_ctx* ctx, const amdzk_srs* s, const uint64_t g2[16], cons
 int zk_pairing_products(amdzk_ctx* ctx, const char* who, const amdzk_g2* const* qs, size_t m, const bn254::G1Affine* h_g1, size_t n, uint8_t* is_one,
                         uint64_t* gt_out);
 
+// verify.hip: n points as G1Affine Montgomery words at d_pts, checked in ONE launch of the proof decoder's third element form
+// (coordinates < q, on the curve; the first inf_below may also be (0, 0)), n < 2^30 (the status word). d_status: one word of device memory;
+// it comes back 0xffffffff, or index << 2 | AMDZK_PROOF_BAD_POINT of the first offender. A point that fails is overwritten
+// with (0, 0). Enqueues on the ctx's stream and does not wait.
+int zk_points_check_dev(amdzk_ctx* ctx, bn254::G1Affine* d_pts, size_t n, size_t inf_below, uint32_t* d_status);
+
 // poly.hip
 int zk_lagrange_to_coeff(amdzk_ctx* ctx, const amdzk_domain* d, const bn254::Fr* d_in, size_t in_stride, bn254::Fr* d_out, size_t out_stride,
                          size_t ncols);

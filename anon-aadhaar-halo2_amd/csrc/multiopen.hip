@@ -418,9 +418,194 @@ int multiopen_body(amdzk_ctx* ctx, const amdzk_srs* srs, const void* const* d_po
   return AMDZK_OK;
 }
 
+// ---- the verifier's side: multiopen/{shplonk, gwc}/verifier.rs [UP] over the caller's commitments (amdzk_multiopen_verify).
+// The grouping is mo_build's, the scalars are opening.hpp's, exactly as verifier.hpp folds a proof's opening argument — with
+// the caller's commitments as the bases, no h(X) expansion and weight 1. Everything the transcript decides is read on the
+// host first; the device then checks the points and runs the one MSM. Bases: the commitments | the read points | g.
+bool fr_words_canonical(const uint64_t* w) {
+  Fr a;
+  memcpy(a.l, w, 32);
+  return reduce_once(a) == a;
+}
+
+int mo_verify_body(amdzk_ctx* ctx, const uint64_t* g, const uint64_t* commitments, size_t n_coms, const uint64_t* points, size_t n_points,
+                   const amdzk_open_query* queries, const uint64_t* evals, size_t n_queries, const amdzk_multiopen_verify_opts* opts, G1Affine pair[2],
+                   std::vector<G1Affine>& bases, std::vector<Fr>& sc, uint32_t& status) {
+  if (!g || !commitments || !points || !queries || !evals || !opts || !pair) ZK_FAIL(ctx, AMDZK_E_INVALID, "multiopen_verify: null argument");
+  if (opts->size < sizeof(amdzk_multiopen_verify_opts))
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "multiopen_verify: amdzk_multiopen_verify_opts.size %zu < %zu", opts->size, sizeof(amdzk_multiopen_verify_opts));
+  const amdzk_transcript_read* t = opts->transcript;
+  if (!t) ZK_FAIL(ctx, AMDZK_E_INVALID, "multiopen_verify: a transcript is required");
+  if (!t->common_point || !t->common_scalar || !t->read_point || !t->read_scalar || !t->squeeze_challenge)
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "multiopen_verify: amdzk_transcript_read has a null member");
+  MoSets s;
+  char why[200];
+  const int pr = mo_build(points, n_points, queries, n_queries, n_coms, 0, opts->scheme, s, nullptr, why);
+  if (pr != AMDZK_OK) ZK_FAIL(ctx, pr, "multiopen_verify: %s", why);
+  for (size_t i = 0; i < n_points; i++)
+    if (!fr_words_canonical(points + 4 * i)) ZK_FAIL(ctx, AMDZK_E_INVALID, "multiopen_verify: point %zu is not below the modulus", i);
+  for (size_t i = 0; i < n_queries; i++)
+    if (!fr_words_canonical(evals + 4 * i)) ZK_FAIL(ctx, AMDZK_E_INVALID, "multiopen_verify: evaluation %zu is not below the modulus", i);
+  const size_t n_read = s.n_out, nb = n_coms + n_read + 1, G = nb - 1;
+  if (nb >= ((size_t)1 << 30)) ZK_FAIL(ctx, AMDZK_E_INVALID, "multiopen_verify: more than 2^30 - 2 commitments and points");
+  bases.assign(nb, G1Affine());
+  memcpy((void*)bases.data(), commitments, n_coms * sizeof(G1Affine));
+  memcpy((void*)&bases[G], g, sizeof(G1Affine));
+  sc.assign(2 * nb, Fr::zero());
+  Fr* const Lc = sc.data();
+  Fr* const Rc = sc.data() + nb;
+  auto squeeze = [&](Fr* c) -> int {
+    uint64_t w[4] = {0, 0, 0, 0};
+    if (t->squeeze_challenge(t->user, w) != 0) ZK_FAIL(ctx, AMDZK_E_INVALID, "multiopen_verify: the caller's transcript reported an error");
+    if (!fr_words_canonical(w)) ZK_FAIL(ctx, AMDZK_E_INVALID, "multiopen_verify: a squeezed challenge is not below the modulus");
+    memcpy(c->l, w, 32);
+    return (int)AMDZK_OK;
+  };
+  auto read = [&](size_t i) -> int {
+    uint64_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (t->read_point(t->user, w) != 0) ZK_FAIL(ctx, AMDZK_E_INVALID, "multiopen_verify: the caller's transcript reported an error");
+    memcpy((void*)&bases[n_coms + i], w, sizeof(G1Affine));
+    return (int)AMDZK_OK;
+  };
+  auto point = [&](uint32_t dp) {
+    Fr z;
+    memcpy(z.l, points + 4 * (size_t)s.dp_index[dp], 32);
+    return z;
+  };
+  auto eval = [&](uint32_t q) {
+    Fr e;
+    memcpy(e.l, evals + 4 * (size_t)q, 32);
+    return e;
+  };
+  Fr v, u;
+  if (s.gwc) {
+    ZK_TRY(squeeze(&v));
+    for (size_t z = 0; z < n_read; z++) ZK_TRY(read(z));
+    ZK_TRY(squeeze(&u));
+    Fr up = Fr::one();
+    for (size_t z = 0; z < n_read; z++) {  // L = sum_z u^z W_z, R = sum_z u^z (p_z W_z + sum_j v^j (C_j - e_j g))
+      const size_t W = n_coms + z;
+      Lc[W] = up;
+      Rc[W] = mul(up, point((uint32_t)z));
+      Fr vp = up, eb = Fr::zero();
+      for (uint32_t q : s.g.gw[s.dp_rank[z]]) {
+        Rc[queries[q].poly] = add(Rc[queries[q].poly], vp);
+        eb = add(eb, mul(vp, eval(q)));
+        vp = mul(vp, v);
+      }
+      Rc[G] = sub(Rc[G], eb);
+      up = mul(up, u);
+    }
+  } else {
+    Fr y;
+    ZK_TRY(squeeze(&y));
+    ZK_TRY(squeeze(&v));
+    ZK_TRY(read(0));
+    ZK_TRY(squeeze(&u));
+    ZK_TRY(read(1));
+    const opening::Grouping& gr = s.g;
+    std::vector<Fr> rank_pt(s.rank_dp.size());
+    for (size_t r = 0; r < rank_pt.size(); r++) rank_pt[r] = point(s.rank_dp[r]);
+    const opening::Shplonk sh = opening::shplonk_sets(gr, rank_pt.data(), [&](uint32_t q) { return eval(s.pair_query[s.q_pair[q]]); }, y, v);
+    const opening::AtU at = opening::at_u(gr, rank_pt.data(), u);
+    Fr vp = Fr::one();
+    for (size_t si = 0; si < gr.sets.size(); si++) {  // R = sum_i v^i z_i(u) sum_j y^j (C_ij - r_ij(u) g) - Z_T(u) h1 + u z_0(u) h2
+      const std::vector<Fr> wgt = opening::weights_at(sh, si, u);
+      Fr ru = Fr::zero(), coef = mul(vp, at.z[si]);
+      for (size_t k = 0; k < wgt.size(); k++) ru = add(ru, mul(wgt[k], sh.E[si][k]));
+      Rc[G] = sub(Rc[G], mul(coef, ru));
+      for (uint32_t c : gr.sets[si].coms) {
+        Rc[gr.coms[c]] = add(Rc[gr.coms[c]], coef);
+        coef = mul(coef, y);
+      }
+      vp = mul(vp, v);
+    }
+    const size_t h1 = n_coms, h2 = n_coms + 1;
+    Rc[h1] = sub(Rc[h1], at.zt);
+    Rc[h2] = add(Rc[h2], mul(at.z0, u));
+    Lc[h2] = at.z0;  // L = z_0(u) h2
+  }
+  // ---- the device: bases | status word | the two columns
+  const size_t o_status = nb * sizeof(G1Affine), o_sc = o_status + 256, total = o_sc + 2 * nb * sizeof(Fr);
+  char* ws = nullptr;
+  {
+    const int r = zk_ws_reserve(ctx, MO_WS_SLOT, total, (void**)&ws);
+    if (r == AMDZK_E_NOMEM) {
+      (void)hipGetLastError();
+      ZK_FAIL(ctx, AMDZK_E_NOMEM, "multiopen_verify: %zu bytes of scratch cannot be allocated", total);
+    }
+    ZK_TRY(r);
+  }
+  ZK_HIP(ctx, hipMemcpyAsync(ws, bases.data(), nb * sizeof(G1Affine), hipMemcpyHostToDevice, ctx->stream));
+  ZK_HIP(ctx, hipMemcpyAsync(ws + o_sc, sc.data(), 2 * nb * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+  ZK_TRY(zk_points_check_dev(ctx, (G1Affine*)ws, nb, n_coms, (uint32_t*)(ws + o_status)));
+  ZK_HIP(ctx, hipMemcpyAsync(&status, ws + o_status, sizeof(status), hipMemcpyDeviceToHost, ctx->stream));
+  G1X* d_res = nullptr;
+  ZK_TRY(zk_msm_bases_dev_xyzz(ctx, (const Fr*)(ws + o_sc), 2, nb, nb, (const G1Affine*)ws, &d_res));
+  uint64_t jac[24];
+  ZK_TRY(zk_msm_finish(ctx, d_res, 2, jac));  // the call's one host wait
+  if (status != 0xffffffffu) {
+    const size_t i = status >> 2;
+    if (i < n_coms) ZK_FAIL(ctx, AMDZK_E_INVALID, "multiopen_verify: commitment %zu has a coordinate >= q or is not on the curve", i);
+    if (i < G) ZK_FAIL(ctx, AMDZK_E_INVALID, "multiopen_verify: read point %zu has a coordinate >= q, is not on the curve or is the identity", i - n_coms);
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "multiopen_verify: g has a coordinate >= q, is not on the curve or is the identity");
+  }
+  for (int c = 0; c < 2; c++) {
+    const G1Jac* j = reinterpret_cast<const G1Jac*>(jac + 12 * c);
+    pair[c].x = j->z.is_zero() ? Fq::zero() : j->x;
+    pair[c].y = j->z.is_zero() ? Fq::zero() : j->y;
+  }
+  return AMDZK_OK;
+}
+
+// the body, and a stream left idle whatever it said (the host images of the tables outlive every copy enqueued from them)
+int mo_verify(amdzk_ctx* ctx, const uint64_t* g, const uint64_t* commitments, size_t n_coms, const uint64_t* points, size_t n_points,
+              const amdzk_open_query* queries, const uint64_t* evals, size_t n_queries, const amdzk_multiopen_verify_opts* opts, G1Affine pair[2]) {
+  std::vector<G1Affine> bases;
+  std::vector<Fr> sc;
+  uint32_t status = 0;
+  const int r = mo_verify_body(ctx, g, commitments, n_coms, points, n_points, queries, evals, n_queries, opts, pair, bases, sc, status);
+  if (r != AMDZK_OK) {
+    const std::string keep = ctx->err;
+    (void)zk_host_wait(ctx, ctx->stream);
+    ctx->err = keep;
+  }
+  return r;
+}
+
 }  // namespace
 
 extern "C" {
+
+int amdzk_multiopen_verify(amdzk_ctx* ctx, const uint64_t g[8], const uint64_t* commitments, size_t n_coms, const uint64_t* points, size_t n_points,
+                           const amdzk_open_query* queries, const uint64_t* evals, size_t n_queries, const amdzk_multiopen_verify_opts* opts,
+                           uint64_t pair_out[16]) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  if (!pair_out) ZK_FAIL(ctx, AMDZK_E_INVALID, "multiopen_verify: null argument");
+  G1Affine pair[2];
+  ZK_TRY(mo_verify(ctx, g, commitments, n_coms, points, n_points, queries, evals, n_queries, opts, pair));
+  memcpy(pair_out, pair, sizeof(pair));
+  return AMDZK_OK;
+}
+
+int amdzk_multiopen_decide(amdzk_ctx* ctx, const uint64_t g[8], const uint64_t* commitments, size_t n_coms, const uint64_t* points, size_t n_points,
+                           const amdzk_open_query* queries, const uint64_t* evals, size_t n_queries, const amdzk_multiopen_verify_opts* opts,
+                           const amdzk_g2* s_g2, const amdzk_g2* g2, uint8_t* verdict) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  if (!s_g2 || !g2 || !verdict) ZK_FAIL(ctx, AMDZK_E_INVALID, "multiopen_verify: null argument");
+  *verdict = 0;
+  G1Affine pair[2];
+  ZK_TRY(mo_verify(ctx, g, commitments, n_coms, points, n_points, queries, evals, n_queries, opts, pair));
+  if (pair[0].is_inf() || pair[1].is_inf()) return AMDZK_OK;  // a pair with the identity must not read as valid
+  const G1Affine g1[2] = {pair[0], a_neg(pair[1])};
+  const amdzk_g2* qs[2] = {s_g2, g2};
+  uint8_t one = 0;
+  ZK_TRY(zk_pairing_products(ctx, "multiopen_verify", qs, 2, g1, 1, &one, nullptr));
+  *verdict = one;
+  return AMDZK_OK;
+}
 
 int amdzk_multiopen_plan(const uint64_t* points, size_t n_points, const amdzk_open_query* queries, size_t n_queries, size_t n_polys, uint32_t k,
                          int scheme, uint32_t* n_sets, uint32_t* n_out, size_t* scratch_bytes, uint32_t* set_of_poly) {

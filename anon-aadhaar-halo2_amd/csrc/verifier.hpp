@@ -1,6 +1,8 @@
 // The host half of amdzk_verify_proofs (include/amdzk.h): plonk::verify_proof [UP] from the decoded proof
 // elements up to one scalar per base for each of the two sums of the final pairing check. Host-only: no HIP include,
-// compiles with g++ (tests/native/verifier_check.cpp runs it alone, also under ASan + UBSan).
+// compiles with g++ (tests/native/verifier_check.cpp runs it alone, also under ASan + UBSan; tests/native/
+// verifier_read_check.cpp through the caller's read transcript). A proof is walked in read order once (run_transcript) over
+// a Source — the built-in transcripts or the caller's callbacks — which leaves its Challenges; fold_challenges is the rest.
 //
 // Inputs are plain data: the circuit as keygen was given it (pkblob::Desc), the number of circuit instances per proof, the
 // transcript kind, transcript_repr, omega, the public inputs, the proof's points and scalars already decoded (affine /
@@ -226,16 +228,79 @@ inline Fr fr_pow2k(Fr a, uint32_t k) {
 }
 inline Fr fr_pow_signed(const Fr& w, const Fr& winv, int64_t e) { return e >= 0 ? bn254::pow_u64(w, (uint64_t)e) : bn254::pow_u64(winv, (uint64_t)(-e)); }
 
-// ---- transcripts that read: the write classes absorb what the device has already decoded (no decompression here)
-class Blake2bRead : public zkhost::Blake2bWrite {
+// ---- where a proof's challenges come from. The verifier walks a proof in read order once (run_transcript) and hands every
+// step to a Source: the public inputs, the elements, the squeezes. A member returns false when the source failed; the walk
+// ends there.
+class Source {
  public:
-  void read_point(const G1Affine& p) { common_point(p); }
-  void read_scalar(const Fr& s) { common_scalar(s); }
+  virtual ~Source() {}
+  virtual bool common_scalar(const Fr& s) = 0;
+  virtual bool element(size_t e, const Plan::Elem& el) = 0;  // element e of the read order is next
+  virtual bool squeeze(Fr* out) = 0;
 };
-class Keccak256Read : public zkhost::Keccak256Write {
+
+// The built-in transcripts: the write classes absorb what the device has already decoded (no decompression here).
+class BuiltinSource : public Source {
  public:
-  void read_point(const G1Affine& p) { common_point(p); }
-  void read_scalar(const Fr& s) { common_scalar(s); }
+  BuiltinSource(bool evm, const G1Affine* pts, const Fr* scs) : T_(evm ? (zkhost::TranscriptWrite&)tk_ : (zkhost::TranscriptWrite&)tb_), pts_(pts), scs_(scs) {}
+  bool common_scalar(const Fr& s) override { return T_.common_scalar(s), true; }
+  bool element(size_t, const Plan::Elem& el) override {
+    if (el.is_point) T_.common_point(pts_[el.index]);
+    else T_.common_scalar(scs_[el.index]);
+    return true;
+  }
+  bool squeeze(Fr* out) override { return *out = T_.squeeze_challenge(), true; }
+
+ private:
+  zkhost::Blake2bWrite tb_;
+  zkhost::Keccak256Write tk_;
+  zkhost::TranscriptWrite& T_;
+  const G1Affine* pts_;
+  const Fr* scs_;
+};
+
+// The caller's TranscriptRead (include/amdzk.h, amdzk_transcript_read): elements are READ from it, 64 bytes of Montgomery words
+// per point and 32 per scalar, to raw + raw_offset[e] — unchecked: the decode launch checks them (verify.hip, the third
+// element form). reads: read_* calls completed, which is AMDZK_PROOF_BAD_TRANSCRIPT's offset.
+class CallbackSource : public Source {
+ public:
+  CallbackSource(const amdzk_transcript_read* t, uint8_t* raw, const uint32_t* raw_offset) : t_(t), raw_(raw), off_(raw_offset) {}
+  bool usable() const { return t_ && t_->common_point && t_->common_scalar && t_->read_point && t_->read_scalar && t_->squeeze_challenge; }
+  bool common_scalar(const Fr& s) override { return t_->common_scalar(t_->user, (const uint64_t*)s.l) == 0; }
+  bool element(size_t e, const Plan::Elem& el) override {
+    uint64_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if ((el.is_point ? t_->read_point(t_->user, w) : t_->read_scalar(t_->user, w)) != 0) return false;
+    memcpy(raw_ + off_[e], w, el.is_point ? 64 : 32);
+    reads++;
+    return true;
+  }
+  bool squeeze(Fr* out) override {
+    uint64_t w[4] = {0, 0, 0, 0};
+    if (t_->squeeze_challenge(t_->user, w) != 0 || !fr_canonical_words(w)) return false;
+    memcpy(out->l, w, 32);
+    return true;
+  }
+  uint32_t reads = 0;
+
+ private:
+  const amdzk_transcript_read* t_;
+  uint8_t* raw_;
+  const uint32_t* off_;
+};
+
+// Byte offsets of a proof's elements in the callback form: 64 bytes per point, 32 per scalar, in read order.
+inline size_t raw_offsets(const Plan& p, std::vector<uint32_t>* off) {
+  size_t at = 0;
+  off->clear();
+  for (const Plan::Elem& el : p.elems) off->push_back((uint32_t)at), at += el.is_point ? 64 : 32;
+  return at;
+}
+
+// Everything a proof's transcript decides.
+struct Challenges {
+  std::vector<Fr> chal;  // the circuit's own, by challenge index
+  Fr theta, beta, gamma, y, x;
+  Fr v, u, yy;  // the opening argument's (yy: SHPLONK only)
 };
 
 // AMDZK_PROOF_BAD_INSTANCE: a value >= r, or a column longer than the usable rows. cols / lens: N x num_instance.
@@ -254,50 +319,51 @@ inline bool instances_ok(const Plan& p, const uint64_t* const* const* inst, cons
   return true;
 }
 
-// One proof. pts: NP affine points, scs: NS scalars (Montgomery), both in read order and well formed; inst / lens: the
-// N circuit instances' public inputs (instances_ok). Lout / Rout: n_bases scalars each, overwritten.
-inline void fold_proof(const Plan& p, const Fr& transcript_repr, const Fr& omega, const uint64_t* const* const* inst, const size_t* const* lens,
-                       const G1Affine* pts, const Fr* scs, const Fr& rho, Fr* Lout, Fr* Rout) {
-  using namespace bn254;
+// One proof's transcript from its first byte to its last, element after element in read order, challenges where the prover
+// squeezed them. inst / lens: the N circuit instances' public inputs (instances_ok). false: the source failed (never the
+// built-in one), *out is then unusable.
+inline bool run_transcript(const Plan& p, Source& T, const Fr& transcript_repr, const uint64_t* const* const* inst, const size_t* const* lens,
+                           Challenges* out) {
   const pkblob::Desc& d = *p.d;
   const uint32_t N = p.N;
-  Blake2bRead tb;
-  Keccak256Read tk;
-  zkhost::TranscriptWrite& T = p.evm ? (zkhost::TranscriptWrite&)tk : (zkhost::TranscriptWrite&)tb;
-  T.common_scalar(transcript_repr);
+  if (!T.common_scalar(transcript_repr)) return false;
   for (uint32_t c = 0; c < N; c++)
     for (uint32_t i = 0; i < p.I; i++)
       for (size_t j = 0; j < lens[c][i]; j++) {
         Fr v;
         memcpy(v.l, inst[c][i] + 4 * j, 32);
-        T.common_scalar(v);
+        if (!T.common_scalar(v)) return false;
       }
-  // ---- the transcript, element after element in read order, challenges where the prover squeezed them
   size_t e = 0;
   auto take = [&](size_t count) {
-    for (size_t i = 0; i < count; i++, e++) {
-      const Plan::Elem& el = p.elems[e];
-      if (el.is_point) T.common_point(pts[el.index]);
-      else T.common_scalar(scs[el.index]);
-    }
+    for (size_t i = 0; i < count; i++, e++)
+      if (!T.element(e, p.elems[e])) return false;
+    return true;
   };
-  std::vector<Fr> chal(d.num_challenges, Fr::zero());
+  out->chal.assign(d.num_challenges, Fr::zero());
   for (uint32_t ph = 0; ph < p.nphases; ph++) {
     size_t cnt = 0;
     for (uint8_t a : p.adv_phase) cnt += a == ph;
-    take(cnt * N);
+    if (!take(cnt * N)) return false;
     for (uint32_t i = 0; i < d.num_challenges; i++)
-      if (d.challenge_phase[i] == ph) chal[i] = T.squeeze_challenge();
+      if (d.challenge_phase[i] == ph && !T.squeeze(&out->chal[i])) return false;
   }
-  const Fr theta = T.squeeze_challenge();
-  take(2 * (size_t)N * p.L);
-  const Fr beta = T.squeeze_challenge();
-  const Fr gamma = T.squeeze_challenge();
-  take((size_t)N * p.nsets + (size_t)N * p.L + 1);
-  const Fr y = T.squeeze_challenge();
-  take(p.qdeg);
-  const Fr x = T.squeeze_challenge();
-  take(p.NS);
+  if (!T.squeeze(&out->theta) || !take(2 * (size_t)N * p.L) || !T.squeeze(&out->beta) || !T.squeeze(&out->gamma)) return false;
+  if (!take((size_t)N * p.nsets + (size_t)N * p.L + 1) || !T.squeeze(&out->y) || !take(p.qdeg) || !T.squeeze(&out->x) || !take(p.NS)) return false;
+  out->yy = Fr::zero();
+  if (p.gwc) return T.squeeze(&out->v) && take(p.rots.size()) && T.squeeze(&out->u);
+  return T.squeeze(&out->yy) && T.squeeze(&out->v) && take(1) && T.squeeze(&out->u) && take(1);
+}
+
+// One proof behind its transcript. pts: NP affine points, scs: NS scalars (Montgomery), both in read order and well formed;
+// ch: what run_transcript gave for them. Lout / Rout: n_bases scalars each, overwritten.
+inline void fold_challenges(const Plan& p, const Fr& omega, const uint64_t* const* const* inst, const size_t* const* lens, const Fr* scs,
+                            const Fr& rho, const Challenges& ch, Fr* Lout, Fr* Rout) {
+  using namespace bn254;
+  const pkblob::Desc& d = *p.d;
+  const uint32_t N = p.N;
+  const std::vector<Fr>& chal = ch.chal;
+  const Fr theta = ch.theta, beta = ch.beta, gamma = ch.gamma, y = ch.y, x = ch.x;
   // ---- the vanishing identity at x
   const Fr one = Fr::one(), omega_inv = inv(omega);
   const Fr xn = fr_pow2k(x, p.k);
@@ -407,10 +473,8 @@ inline void fold_proof(const Plan& p, const Fr& transcript_repr, const Fr& omega
   auto eval_of = [&](const Plan::Query& q) { return q.sc == NO_SCALAR ? expected_h : scs[q.sc]; };
   std::vector<Fr> pt(p.rots.size());
   for (size_t i = 0; i < pt.size(); i++) pt[i] = mul(x, fr_pow_signed(omega, omega_inv, p.rots[i]));
+  const Fr v = ch.v, u = ch.u;
   if (p.gwc) {
-    const Fr v = T.squeeze_challenge();
-    take(p.rots.size());
-    const Fr u = T.squeeze_challenge();
     Fr up = rho;
     for (size_t i = 0; i < p.rots.size(); i++) {
       const uint32_t W = p.open_pt + (uint32_t)i;
@@ -427,11 +491,7 @@ inline void fold_proof(const Plan& p, const Fr& transcript_repr, const Fr& omega
     }
     return;
   }
-  const Fr yy = T.squeeze_challenge();
-  const Fr v = T.squeeze_challenge();
-  take(1);
-  const Fr u = T.squeeze_challenge();
-  take(1);
+  const Fr yy = ch.yy;
   const opening::Grouping& g = p.grp;
   const opening::Shplonk sh = opening::shplonk_sets(g, pt.data(), [&](uint32_t qi) { return eval_of(p.queries[qi]); }, yy, v);
   const opening::AtU at = opening::at_u(g, pt.data(), u);
@@ -453,6 +513,15 @@ inline void fold_proof(const Plan& p, const Fr& transcript_repr, const Fr& omega
   Rout[h1] = sub(Rout[h1], mul(rho, zt));
   Rout[h2] = add(Rout[h2], mul(rz0, u));
   Lout[h2] = add(Lout[h2], rz0);
+}
+
+// One proof read with the built-in transcript of the plan: run_transcript over the decoded elements, then fold_challenges.
+inline void fold_proof(const Plan& p, const Fr& transcript_repr, const Fr& omega, const uint64_t* const* const* inst, const size_t* const* lens,
+                       const G1Affine* pts, const Fr* scs, const Fr& rho, Fr* Lout, Fr* Rout) {
+  BuiltinSource T(p.evm, pts, scs);
+  Challenges ch;
+  run_transcript(p, T, transcript_repr, inst, lens, &ch);
+  fold_challenges(p, omega, inst, lens, scs, rho, ch, Lout, Rout);
 }
 
 }  // namespace verifier

@@ -4,6 +4,7 @@
 // identity and the per-base scalars are the host half's (verifier.hpp). Two host waits per call. Nothing here touches the
 // key's per-proof workspace. The key is read through a view (vk.hpp) that a proving key or a verifying key fills:
 // amdzk_verify_proofs_vk and amdzk_verify_proofs_decide_vk are the same code over the same operands.
+#include <stddef.h>
 #include <string.h>
 
 #include <string>
@@ -32,6 +33,14 @@ struct DecodeArgs {
   Fr* scalars;       // [b * NS + index]
   uint32_t* status;  // per proof: min over its bad elements of offset << 2 | class, STATUS_CLEAN when there is none
   int evm;
+  // The third element form, per proof (raw[b] != 0; raw == nullptr: no proof has it): what a caller's read transcript handed
+  // back, Montgomery words at elems_raw's offsets — 64 bytes per point, 32 per scalar. Checked, not converted; the status
+  // word then carries the element's index in read order instead of a byte offset. Points whose index is below
+  // raw_inf_below may be (0, 0) (amdzk_multiopen_verify's commitments).
+  const uint8_t* raw;
+  int raw_all;             // every proof has it (zk_points_check_dev)
+  const uint2* elems_raw;  // nullptr: points alone, element e is point e at byte 64 e
+  uint32_t raw_inf_below;
 };
 
 // 32 bytes at a 32-byte-aligned address as a 256-bit integer, little- or big-endian
@@ -51,14 +60,45 @@ __device__ __forceinline__ void store_fq(Fq* p, const Fq& v) {
   q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
 }
 
-// One thread per (proof, element). A point costs one Fq square-root chain (254 dependent squarings, Blake2b form) or a
+// One thread per (proof, element), the element's form chosen per proof: the bytes of a built-in transcript (compressed or EVM,
+// a.evm) or the words a caller's read transcript handed back (a.raw). A point costs one Fq square-root chain (254 dependent squarings, Blake2b form) or a
 // curve check (EVM form), a scalar one product: the launch is latency-bound, so the blocks are single waves that the
 // dispatcher spreads over the CUs, and a wave that holds only scalars retires at once.
 __global__ __launch_bounds__(DECODE_THREADS) void proof_decode_kernel(DecodeArgs a) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= a.total) return;
   const size_t b = t / a.E;
-  const uint2 el = a.elems[t - b * a.E];
+  const uint32_t e = (uint32_t)(t - b * a.E);
+  if (a.raw_all || (a.raw && a.raw[b])) {
+    const uint2 el = a.elems_raw ? a.elems_raw[e] : make_uint2(0, 0x80000000u | e);  // no table: points alone, 64 bytes each
+    const uint8_t* src = a.staging + b * a.stride + (a.elems_raw ? (size_t)el.x : (size_t)e * 64);
+    const uint32_t index = el.y & 0x7fffffffu;
+    bool ok;
+    uint32_t cls;
+    if (el.y >> 31) {  // both coordinates canonical, on the curve (which (0, 0) is not) or, where allowed, the identity
+      cls = AMDZK_PROOF_BAD_POINT;
+      G1Affine p;
+      p.x = load_u256<Fq>(src, false);
+      p.y = load_u256<Fq>(src + 32, false);
+      ok = is_canonical(p.x) && is_canonical(p.y);
+      if (ok) ok = (index < a.raw_inf_below && p.x.is_zero() && p.y.is_zero()) || sqr(p.y) == g1_curve_rhs(p.x);
+      if (!ok) p.x = Fq::zero(), p.y = Fq::zero();
+      G1Affine* o = a.points + b * a.NP + index;
+      store_fq(&o->x, p.x);
+      store_fq(&o->y, p.y);
+    } else {
+      cls = AMDZK_PROOF_BAD_SCALAR;
+      Fr s = load_u256<Fr>(src, false);
+      ok = is_canonical(s);
+      if (!ok) s = Fr::zero();
+      uint4* o = reinterpret_cast<uint4*>(a.scalars + b * a.NS + index);
+      o[0] = make_uint4(s.l[0], s.l[1], s.l[2], s.l[3]);
+      o[1] = make_uint4(s.l[4], s.l[5], s.l[6], s.l[7]);
+    }
+    if (!ok) atomicMin(a.status + b, (e << 2) | cls);
+    return;
+  }
+  const uint2 el = a.elems[e];
   const uint8_t* src = a.staging + b * a.stride + el.x;
   const uint32_t index = el.y & 0x7fffffffu;
   bool ok;
@@ -114,13 +154,21 @@ int verify_core(amdzk_ctx* ctx, const char* who, const zk_key_view* key, size_t 
                 const size_t* const* instance_lens, const uint8_t* const* proofs, const size_t* proof_lens, const amdzk_verify_opts* opts,
                 amdzk_proof_status* statuses, uint64_t* pair_out, std::vector<G1Affine>* pairs) {
   const bool per_proof = pairs != nullptr;
-  if (!key || !proofs || !proof_lens || !statuses || (!per_proof && !pair_out)) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: null argument", who);
+  if (!key || !statuses || (!per_proof && !pair_out)) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: null argument", who);
   if (n_proofs == 0) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: n_proofs is 0", who);
   if (n_proofs > (1u << 20)) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: more than 2^20 proofs in one call", who);
-  if (opts && opts->size < sizeof(amdzk_verify_opts))
+  // the struct as it was before `transcripts` is still a caller's right: exactly that size, or this library's
+  constexpr size_t LEGACY_OPTS = offsetof(amdzk_verify_opts, transcripts);
+  if (opts && opts->size != LEGACY_OPTS && opts->size < sizeof(amdzk_verify_opts))
     ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: amdzk_verify_opts.size is %zu, this library needs %zu", who, opts->size, sizeof(amdzk_verify_opts));
+  const amdzk_transcript_read* const* trs = opts && opts->size >= sizeof(amdzk_verify_opts) ? opts->transcripts : nullptr;
+  auto tr_of = [&](size_t b) { return trs ? trs[b] : nullptr; };
+  size_t n_tr = 0;
+  for (size_t b = 0; trs && b < n_proofs; b++) n_tr += trs[b] != nullptr;
+  if (n_tr < n_proofs && (!proofs || !proof_lens)) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: null argument", who);
   if (!key->desc) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: the key has no circuit description", who);
-  const int kind = opts ? opts->transcript_kind : 0;
+  // a batch of transcript proofs alone: only the opening scheme's bit counts
+  const int kind = (opts ? opts->transcript_kind : 0) & (n_tr == n_proofs ? ~0xff : ~0);
   const uint32_t N = opts && opts->n_circuits ? opts->n_circuits : 1;
   verifier::Plan plan;
   {
@@ -134,7 +182,7 @@ int verify_core(amdzk_ctx* ctx, const char* who, const zk_key_view* key, size_t 
   for (size_t i = 0; plan.I && i < n_proofs * N; i++)
     if (!instances[i] || !instance_lens[i]) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: null argument (instances of circuit %zu)", who, i);
   for (size_t b = 0; b < n_proofs; b++)
-    if (!proofs[b]) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: null argument (proof %zu)", who, b);
+    if (!tr_of(b) && !proofs[b]) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: null argument (proof %zu)", who, b);
   if ((key->sized_by && plan.proof_bytes != amdzk_proof_size_multi(key->sized_by, N, kind)) || plan.proof_bytes >= ((size_t)1 << 30))
     ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "%s: proof layout of %zu bytes disagrees with amdzk_proof_size_multi or is too large", who, plan.proof_bytes);
   std::vector<Fr> rho(n_proofs, Fr::one());
@@ -154,7 +202,7 @@ int verify_core(amdzk_ctx* ctx, const char* who, const zk_key_view* key, size_t 
   for (size_t b = 0; b < n_proofs; b++) {
     statuses[b].status = AMDZK_PROOF_WELL_FORMED, statuses[b].offset = 0;
     uint32_t col = 0;
-    if (proof_lens[b] != plan.proof_bytes) statuses[b].status = AMDZK_PROOF_BAD_LENGTH;
+    if (!tr_of(b) && proof_lens[b] != plan.proof_bytes) statuses[b].status = AMDZK_PROOF_BAD_LENGTH;
     else if (plan.I && !verifier::instances_ok(plan, instances + b * N, instance_lens + b * N, &col))
       statuses[b].status = AMDZK_PROOF_BAD_INSTANCE, statuses[b].offset = col;
     else live++;
@@ -164,10 +212,16 @@ int verify_core(amdzk_ctx* ctx, const char* who, const zk_key_view* key, size_t 
   if (per_proof) pairs->assign(2 * n_proofs, g1_inf);
   else memset(pair_out, 0, 16 * sizeof(uint64_t));
   if (live == 0) return AMDZK_OK;
-  // ---- one reservation: staging | element table | status words | key commitments | G | decoded points | decoded scalars | MSM scalars
-  const size_t psize = plan.proof_bytes, E = plan.elems.size(), NP = plan.NP, NS = plan.NS, nvk = (size_t)plan.F + plan.S;
+  // ---- one reservation: staging | element table | with transcripts: their element table and the per-proof form bytes |
+  // status words | key commitments | G | decoded points | decoded scalars | MSM scalars
+  const size_t E = plan.elems.size(), NP = plan.NP, NS = plan.NS, nvk = (size_t)plan.F + plan.S;
+  std::vector<uint32_t> raw_off;
+  const size_t raw_size = n_tr ? verifier::raw_offsets(plan, &raw_off) : 0;
+  const size_t psize = plan.proof_bytes > raw_size ? plan.proof_bytes : raw_size;  // the staging stride: the larger form's
+  if (psize >= ((size_t)1 << 30)) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "%s: proof layout of %zu bytes is too large", who, psize);
   const size_t nbases = nvk + 1 + n_proofs * NP;
-  const size_t o_elems = pad256(n_proofs * psize), o_status = o_elems + pad256(E * sizeof(uint2)), o_vk = o_status + pad256(n_proofs * 4);
+  const size_t o_elems = pad256(n_proofs * psize), o_eraw = o_elems + pad256(E * sizeof(uint2)), o_form = o_eraw + (n_tr ? pad256(E * sizeof(uint2)) : 0);
+  const size_t o_status = o_form + (n_tr ? pad256(n_proofs) : 0), o_vk = o_status + pad256(n_proofs * 4);
   const size_t o_g = o_vk + nvk * sizeof(G1Affine), o_points = o_g + sizeof(G1Affine), o_dsc = o_points + n_proofs * NP * sizeof(G1Affine);
   // per proof: the MSM scalars of ONE run (2 columns per proof over the key's commitments, G and the run's points) | that run's bases
   const size_t run = n_proofs < AMDZK_DECIDE_RUN ? n_proofs : AMDZK_DECIDE_RUN, run_len = nvk + 1 + run * NP;
@@ -180,11 +234,30 @@ int verify_core(amdzk_ctx* ctx, const char* who, const zk_key_view* key, size_t 
   ZK_TRY(zk_pinned_reserve(ctx, up_bytes + down_bytes, (void**)&pin));
   char* h_down = pin + up_bytes;
   memset(pin, 0, up_bytes);
+  // a transcript proof is read here, through the caller's callbacks, in ascending b: its elements go to the staging area
+  // in the third form and its challenges are kept for the host half
+  std::vector<verifier::Challenges> read_ch(n_tr ? n_proofs : 0);
   for (size_t b = 0; b < n_proofs; b++) {
-    if (statuses[b].status == AMDZK_PROOF_WELL_FORMED) memcpy(pin + b * psize, proofs[b], psize);
     ((uint32_t*)(pin + o_status))[b] = STATUS_CLEAN;
+    if (n_tr) pin[o_form + b] = tr_of(b) ? 1 : 0;
+    if (statuses[b].status != AMDZK_PROOF_WELL_FORMED) continue;
+    if (!tr_of(b)) {
+      memcpy(pin + b * psize, proofs[b], plan.proof_bytes);
+      continue;
+    }
+    verifier::CallbackSource src(tr_of(b), (uint8_t*)pin + b * psize, raw_off.data());
+    if (!src.usable() || !verifier::run_transcript(plan, src, *key->transcript_repr, plan.I ? instances + b * N : nullptr,
+                                                   plan.I ? instance_lens + b * N : nullptr, &read_ch[b])) {
+      statuses[b].status = AMDZK_PROOF_BAD_TRANSCRIPT, statuses[b].offset = src.reads;
+      memset(pin + b * psize, 0, psize);
+      live--;
+    }
   }
-  for (size_t e = 0; e < E; e++) ((uint2*)(pin + o_elems))[e] = make_uint2(plan.elems[e].offset, (plan.elems[e].is_point << 31) | plan.elems[e].index);
+  if (live == 0) return AMDZK_OK;
+  for (size_t e = 0; e < E; e++) {
+    ((uint2*)(pin + o_elems))[e] = make_uint2(plan.elems[e].offset, (plan.elems[e].is_point << 31) | plan.elems[e].index);
+    if (n_tr) ((uint2*)(pin + o_eraw))[e] = make_uint2(raw_off[e], (plan.elems[e].is_point << 31) | plan.elems[e].index);
+  }
   if (plan.F) memcpy(pin + o_vk, key->fixed_commitments, (size_t)plan.F * sizeof(G1Affine));
   if (plan.S) memcpy(pin + o_vk + (size_t)plan.F * sizeof(G1Affine), key->perm_commitments, (size_t)plan.S * sizeof(G1Affine));
   if (!key->d_g && !key->h_g) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: the key's SRS has no monomial basis", who);
@@ -195,6 +268,7 @@ int verify_core(amdzk_ctx* ctx, const char* who, const zk_key_view* key, size_t 
   da.staging = (const uint8_t*)ws, da.stride = psize, da.elems = (const uint2*)(ws + o_elems);
   da.E = (uint32_t)E, da.NP = (uint32_t)NP, da.NS = (uint32_t)NS, da.total = n_proofs * E;
   da.points = (G1Affine*)(ws + o_points), da.scalars = (Fr*)(ws + o_dsc), da.status = (uint32_t*)(ws + o_status), da.evm = plan.evm ? 1 : 0;
+  da.raw = n_tr ? (const uint8_t*)(ws + o_form) : nullptr, da.raw_all = 0, da.elems_raw = (const uint2*)(ws + o_eraw), da.raw_inf_below = 0;
   const size_t blocks = (da.total + DECODE_THREADS - 1) / DECODE_THREADS;
   if (blocks > 0x7fffffffu) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: batch too large", who);
   ZK_LAUNCH(ctx, "proof_decode", proof_decode_kernel, dim3((unsigned)blocks), dim3(DECODE_THREADS), 0, da);
@@ -215,8 +289,10 @@ int verify_core(amdzk_ctx* ctx, const char* who, const zk_key_view* key, size_t 
       continue;
     }
     live++;
-    verifier::fold_proof(plan, *key->transcript_repr, *key->omega, plan.I ? instances + b * N : nullptr, plan.I ? instance_lens + b * N : nullptr,
-                         h_points + b * NP, h_scalars + b * NS, rho[b], Lb.data(), Rb.data());
+    const uint64_t* const* const* inst_b = plan.I ? instances + b * N : nullptr;
+    const size_t* const* lens_b = plan.I ? instance_lens + b * N : nullptr;
+    if (tr_of(b)) verifier::fold_challenges(plan, *key->omega, inst_b, lens_b, h_scalars + b * NS, rho[b], read_ch[b], Lb.data(), Rb.data());
+    else verifier::fold_proof(plan, *key->transcript_repr, *key->omega, inst_b, lens_b, h_points + b * NP, h_scalars + b * NS, rho[b], Lb.data(), Rb.data());
     if (per_proof) {
       own.insert(own.end(), Lb.begin(), Lb.end());
       own.insert(own.end(), Rb.begin(), Rb.end());
@@ -345,6 +421,17 @@ int decide_core(amdzk_ctx* ctx, const char* who, const zk_key_view* key, const a
 }
 
 }  // namespace
+
+int zk_points_check_dev(amdzk_ctx* ctx, G1Affine* d_pts, size_t n, size_t inf_below, uint32_t* d_status) {
+  if (n == 0 || n >= ((size_t)1 << 30)) ZK_FAIL(ctx, AMDZK_E_INVALID, "points_check: %zu points", n);
+  ZK_HIP(ctx, hipMemsetAsync(d_status, 0xff, sizeof(uint32_t), ctx->stream));
+  DecodeArgs da;
+  da.staging = (const uint8_t*)d_pts, da.stride = 0, da.elems = nullptr, da.E = (uint32_t)n, da.NP = (uint32_t)n, da.NS = 0, da.total = n;
+  da.points = d_pts, da.scalars = nullptr, da.status = d_status, da.evm = 0;
+  da.raw = nullptr, da.raw_all = 1, da.elems_raw = nullptr, da.raw_inf_below = (uint32_t)(inf_below < n ? inf_below : n);
+  ZK_LAUNCH(ctx, "proof_decode", proof_decode_kernel, dim3((unsigned)((n + DECODE_THREADS - 1) / DECODE_THREADS)), dim3(DECODE_THREADS), 0, da);
+  return AMDZK_OK;
+}
 
 extern "C" int amdzk_verify_proofs(amdzk_ctx* ctx, const amdzk_pk* pk, size_t n_proofs, const uint64_t* const* const* instances,
                                    const size_t* const* instance_lens, const uint8_t* const* proofs, const size_t* proof_lens,

@@ -131,6 +131,8 @@ def lib():
         "amdzk_srs_check": (i32, [vp, vp, vp, vp, vp, vp]),
         "amdzk_verify_proofs_decide": (i32, [vp, vp, vp, vp, u32, sz, C.POINTER(C.POINTER(vp)), C.POINTER(C.POINTER(sz)), C.POINTER(vp), C.POINTER(sz),
                                              vp, vp, vp, C.POINTER(sz)]),
+        "amdzk_multiopen_verify": (i32, [vp, vp, vp, sz, vp, sz, vp, vp, sz, vp, vp]),
+        "amdzk_multiopen_decide": (i32, [vp, vp, vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, vp]),
         "amdzk_keygen_vk": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]),
         "amdzk_vk_from_pk": (i32, [vp, vp, C.POINTER(vp)]),
         "amdzk_vk_free": (None, [vp, vp]),
@@ -211,9 +213,57 @@ class ProofStatus(C.Structure):  # amdzk_proof_status
     _fields_ = [("status", C.c_uint32), ("offset", C.c_uint32)]
 
 
+class TranscriptRead(C.Structure):  # amdzk_transcript_read
+    _fields_ = [("user", C.c_void_p), ("common_point", _T_IN), ("common_scalar", _T_IN), ("read_point", _T_IN), ("read_scalar", _T_IN),
+                ("squeeze_challenge", _T_IN)]
+
+
 class VerifyOpts(C.Structure):  # amdzk_verify_opts
     _fields_ = [("size", C.c_size_t), ("transcript_kind", C.c_int), ("n_circuits", C.c_uint32), ("combine_seed", C.c_uint64),
-                ("combine_scalars", C.c_void_p)]
+                ("combine_scalars", C.c_void_p), ("transcripts", C.POINTER(C.POINTER(TranscriptRead)))]
+
+
+VERIFY_OPTS_LEGACY_SIZE = VerifyOpts.transcripts.offset  # the struct before `transcripts`: still accepted, means no transcripts
+
+
+class MultiopenVerifyOpts(C.Structure):  # amdzk_multiopen_verify_opts
+    _fields_ = [("size", C.c_size_t), ("scheme", C.c_int), ("transcript", C.POINTER(TranscriptRead))]
+
+
+def read_transcript(tobj, errors):
+    """An amdzk_transcript_read around a Python object with upstream's TranscriptRead method names: common_point((8,) uint64),
+    common_scalar((4,)), read_point() -> (8,), read_scalar() -> (4,), squeeze_challenge() -> (4,), all Montgomery words. An
+    exception is kept in `errors` and turned into a non-zero return (nothing may unwind through the library). Returns
+    (struct, keep-alive); a member the object lacks is a NULL member."""
+    def guard(fn):
+        def run(*a):
+            try:
+                return int(fn(*a) or 0)
+            except BaseException as e:  # noqa: B902 - reported by the caller
+                errors.append(e)
+                return 1
+        return run
+
+    def taking(name, cnt):
+        fn = getattr(tobj, name, None)
+        if fn is None:
+            return _T_IN()
+        return _T_IN(guard(lambda _u, p: fn(np.array([p[i] for i in range(cnt)], dtype=np.uint64))))
+
+    def giving(name, cnt):
+        fn = getattr(tobj, name, None)
+        if fn is None:
+            return _T_IN()
+
+        def give(_u, out):
+            v = np.ascontiguousarray(fn(), dtype=np.uint64).reshape(cnt)
+            for i in range(cnt):
+                out[i] = int(v[i])
+        return _T_IN(guard(give))
+
+    cbs = [taking("common_point", 8), taking("common_scalar", 4), giving("read_point", 8), giving("read_scalar", 4), giving("squeeze_challenge", 4)]
+    tr = TranscriptRead(None, *cbs)
+    return tr, cbs + [tr]
 
 
 OPEN_QUERY = np.dtype([("poly", np.uint32), ("point", np.uint32)])  # amdzk_open_query

@@ -338,3 +338,82 @@ class ProverSHPLONK(_ProverMultiopen):
 class ProverGWC(_ProverMultiopen):
     """poly::kzg::multiopen::ProverGWC."""
     scheme = MULTIOPEN_GWC
+
+
+# ---- poly::kzg::multiopen: the opening arguments verified over the caller's commitments (amdzk_multiopen_verify / _decide)
+def index_commitment_queries(queries):
+    """[(commitment (8,) uint64, point (4,) uint64, eval (4,) uint64)] in upstream's VerifierQuery order -> (commitments (n, 8),
+    points (P, 4), amdzk_open_query array, evals (Q, 4)). A commitment's identity is its words, as upstream compares
+    CommitmentReference::Commitment; equal point words share an index."""
+    coms, com_of, points, point_of = [], {}, [], {}
+    q = np.zeros(len(queries), dtype=_ffi.OPEN_QUERY)
+    evals = np.zeros((len(queries), 4), np.uint64)
+    for i, (com, point, ev) in enumerate(queries):
+        cm = np.ascontiguousarray(com, dtype=np.uint64).reshape(8)
+        pt = np.ascontiguousarray(point, dtype=np.uint64).reshape(4)
+        ci = com_of.setdefault(cm.tobytes(), len(coms))
+        if ci == len(coms):
+            coms.append(cm)
+        pi = point_of.setdefault(pt.tobytes(), len(points))
+        if pi == len(points):
+            points.append(pt)
+        q[i] = (ci, pi)
+        evals[i] = np.ascontiguousarray(ev, dtype=np.uint64).reshape(4)
+    return np.array(coms, dtype=np.uint64).reshape(-1, 8), np.array(points, dtype=np.uint64).reshape(-1, 4), q, evals
+
+
+def multiopen_verify(ctx, g, commitments, points, queries, evals, transcript, scheme=MULTIOPEN_SHPLONK, vparams=None, opts_size=None):
+    """amdzk_multiopen_verify (vparams None: returns (lhs, rhs), (8,) uint64 each, valid iff e(lhs, [s]_2) = e(rhs, [1]_2)) or
+    amdzk_multiopen_decide (vparams a ParamsVerifierKZG: returns the verdict). g: (8,) uint64, the SRS's g[0]; commitments
+    (n, 8); points (P, 4); queries an amdzk_open_query array or [(commitment index, point index)]; evals (Q, 4); transcript: the
+    caller's TranscriptRead object (read_point() -> (8,) uint64, squeeze_challenge() -> (4,)). A refused call raises; an
+    exception inside the transcript is re-raised."""
+    arr = lambda a, w: None if a is None else np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, w)
+    g, commitments, points, evals = arr(g, 8), arr(commitments, 8), arr(points, 4), arr(evals, 4)
+    if queries is not None and not (isinstance(queries, np.ndarray) and queries.dtype == _ffi.OPEN_QUERY):
+        queries = np.array([tuple(int(v) for v in qq) for qq in queries], dtype=_ffi.OPEN_QUERY).reshape(-1)
+    errors = []
+    tr, keep = (None, None) if transcript is None else _ffi.read_transcript(transcript, errors)
+    opts = _ffi.MultiopenVerifyOpts(C.sizeof(_ffi.MultiopenVerifyOpts) if opts_size is None else opts_size, scheme,
+                                    C.pointer(tr) if tr is not None else None)
+    p = lambda a: None if a is None else _ptr(a)
+    n = lambda a: 0 if a is None else a.shape[0]
+    args = (ctx.h, p(g), p(commitments), n(commitments), p(points), n(points), p(queries), p(evals), n(queries), C.byref(opts))
+    if vparams is None:
+        pair = np.zeros(16, np.uint64)
+        rc = ctx.L.amdzk_multiopen_verify(*args, _ptr(pair))
+    else:
+        verdict = C.c_uint8(0)
+        rc = ctx.L.amdzk_multiopen_decide(*args, vparams.s_g2.h, vparams.g2.h, C.byref(verdict))
+    del keep
+    if errors and rc != 0:
+        raise errors[0]
+    ctx._chk(rc)
+    return (pair[:8].copy(), pair[8:].copy()) if vparams is None else bool(verdict.value)
+
+
+class _VerifierMultiopen:
+    """poly::commitment::Verifier for KZG over the caller's commitments: verify_proof(transcript, queries) reads the opening
+    proof from the caller's TranscriptRead object and returns the guard's pair (lhs, rhs); decide(...) pairs it too."""
+    scheme = MULTIOPEN_SHPLONK
+
+    def __init__(self, ctx, g):
+        self.ctx, self.g = ctx, np.ascontiguousarray(g, dtype=np.uint64).reshape(8)
+
+    def verify_proof(self, transcript, queries, vparams=None):
+        """queries: [(commitment (8,) uint64, point (4,), eval (4,))] in upstream's order."""
+        coms, points, q, evals = index_commitment_queries(queries)
+        return multiopen_verify(self.ctx, self.g, coms, points, q, evals, transcript, self.scheme, vparams=vparams)
+
+    def decide(self, transcript, queries, vparams):
+        return self.verify_proof(transcript, queries, vparams=vparams)
+
+
+class VerifierSHPLONK(_VerifierMultiopen):
+    """poly::kzg::multiopen::VerifierSHPLONK."""
+    scheme = MULTIOPEN_SHPLONK
+
+
+class VerifierGWC(_VerifierMultiopen):
+    """poly::kzg::multiopen::VerifierGWC."""
+    scheme = MULTIOPEN_GWC

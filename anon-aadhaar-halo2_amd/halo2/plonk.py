@@ -910,8 +910,8 @@ def check_witness(ctx, pk, instances, d_advice, theta_seed=0, challenges=None, a
 
 
 # include/amdzk.h AMDZK_PROOF_*
-PROOF_WELL_FORMED, PROOF_BAD_LENGTH, PROOF_BAD_POINT, PROOF_BAD_SCALAR, PROOF_BAD_INSTANCE = 0, 1, 2, 3, 4
-PROOF_STATUS_NAMES = ("WELL_FORMED", "BAD_LENGTH", "BAD_POINT", "BAD_SCALAR", "BAD_INSTANCE")
+PROOF_WELL_FORMED, PROOF_BAD_LENGTH, PROOF_BAD_POINT, PROOF_BAD_SCALAR, PROOF_BAD_INSTANCE, PROOF_BAD_TRANSCRIPT = 0, 1, 2, 3, 4, 5
+PROOF_STATUS_NAMES = ("WELL_FORMED", "BAD_LENGTH", "BAD_POINT", "BAD_SCALAR", "BAD_INSTANCE", "BAD_TRANSCRIPT")
 ProofStatus = collections.namedtuple("ProofStatus", "status offset")
 
 
@@ -922,6 +922,7 @@ class Guard:
 
     def __init__(self, lhs, rhs, statuses):
         self.lhs, self.rhs, self.statuses = lhs, rhs, list(statuses)
+        self.errors = []  # exceptions raised inside the caller's read transcripts (their proofs are PROOF_BAD_TRANSCRIPT)
 
     @property
     def well_formed(self):
@@ -931,10 +932,12 @@ class Guard:
         return "Guard(statuses=%r)" % (self.statuses,)
 
 
-def _verify_args(instances_list, proofs, transcript, n_circuits, combine_seed, combine_scalars, opts_size):
+def _verify_args(instances_list, proofs, transcript, n_circuits, combine_seed, combine_scalars, opts_size, transcripts=None, errors=None):
     """The arguments amdzk_verify_proofs and amdzk_verify_proofs_decide share: (instances, instance_lens, proofs, proof_lens,
-    opts, statuses, keep-alive)."""
+    opts, statuses, keep-alive). transcripts: None, or per proof None / a TranscriptRead object (ffi.read_transcript), whose
+    exceptions land in `errors`; a proof that has one may be None."""
     B, N = len(proofs), n_circuits
+    proofs = [b"" if p is None else p for p in proofs]
     assert len(instances_list) == B
     keep, inst_pp, lens_pp = [], (C.POINTER(C.c_void_p) * max(1, B * N))(), (C.POINTER(C.c_size_t) * max(1, B * N))()
     for b, per_proof in enumerate(instances_list):
@@ -952,28 +955,44 @@ def _verify_args(instances_list, proofs, transcript, n_circuits, combine_seed, c
     pl = (C.c_size_t * max(1, B))(*[len(p) for p in proofs])
     sc = np.ascontiguousarray(combine_scalars, dtype=np.uint64).reshape(-1, 4) if combine_scalars is not None else None
     assert sc is None or sc.shape[0] == B
+    trs = None
+    if transcripts is not None:
+        assert len(transcripts) == B
+        trs = (C.POINTER(_ffi.TranscriptRead) * max(1, B))()
+        for b, tobj in enumerate(transcripts):
+            if tobj is not None:
+                tr, alive = _ffi.read_transcript(tobj, errors if errors is not None else [])
+                trs[b] = C.pointer(tr)
+                keep.append(alive)
     opts = _ffi.VerifyOpts(C.sizeof(_ffi.VerifyOpts) if opts_size is None else opts_size, transcript, N, C.c_uint64(combine_seed),
-                           sc.ctypes.data if sc is not None else None)
+                           sc.ctypes.data if sc is not None else None, trs)
     st = (_ffi.ProofStatus * max(1, B))()
-    keep += [bufs, sc]
+    keep += [bufs, sc, trs]
     return inst_pp, lens_pp, pp, pl, opts, st, keep
 
 
 def verify_proofs(ctx, pk, instances_list, proofs, transcript=TRANSCRIPT_BLAKE2B, n_circuits=1, combine_seed=0, combine_scalars=None,
-                  opts_size=None):
+                  opts_size=None, transcripts=None):
     """amdzk_verify_proofs (amdzk_verify_proofs_vk when pk is a VerifyingKey): plonk::verify_proof for a batch up to the one
     pairing. proofs[b]: bytes; instances_list[b]: proof
     b's instance columns as for create_proof — or, with n_circuits > 1, a list of n_circuits such lists (create_proof_multi).
     combine_scalars: (len(proofs), 4) uint64 Montgomery weights of the caller's; else they are drawn from combine_seed, which
     must then be unpredictable to whoever made the proofs (a single proof has weight 1). Returns a Guard; a refused call raises.
+    transcripts: None, or per proof None (the bytes proofs[b]) or the caller's TranscriptRead object — common_scalar((4,) uint64),
+    read_point() -> (8,), read_scalar() -> (4,), squeeze_challenge() -> (4,), Montgomery words; proofs[b] may then be None and of
+    `transcript` only MULTIOPEN_GWC counts. An exception in a method makes that proof PROOF_BAD_TRANSCRIPT; Guard.errors keeps them.
     opts_size: amdzk_verify_opts.size to report (tests)."""
     B = len(proofs)
-    inst_pp, lens_pp, pp, pl, opts, st, keep = _verify_args(instances_list, proofs, transcript, n_circuits, combine_seed, combine_scalars, opts_size)
+    errors = []
+    inst_pp, lens_pp, pp, pl, opts, st, keep = _verify_args(instances_list, proofs, transcript, n_circuits, combine_seed, combine_scalars, opts_size,
+                                                            transcripts, errors)
     pair = np.zeros(16, dtype=np.uint64)
     fn = ctx.L.amdzk_verify_proofs_vk if isinstance(pk, VerifyingKey) else ctx.L.amdzk_verify_proofs
     ctx._chk(fn(ctx.h, pk.h, B, inst_pp, lens_pp, pp, pl, C.byref(opts), st, pair.ctypes.data))
     del keep
-    return Guard(pair[:8].copy(), pair[8:].copy(), [ProofStatus(s.status, s.offset) for s in st[:B]])
+    g = Guard(pair[:8].copy(), pair[8:].copy(), [ProofStatus(s.status, s.offset) for s in st[:B]])
+    g.errors = errors
+    return g
 
 
 DECIDE_COMBINED = 1  # AMDZK_DECIDE_COMBINED
@@ -981,15 +1000,17 @@ DECIDE_RUN = 16      # AMDZK_DECIDE_RUN
 
 
 def decide_proofs(ctx, pk, vparams, instances_list, proofs, transcript=TRANSCRIPT_BLAKE2B, n_circuits=1, combined=False, combine_seed=0,
-                  combine_scalars=None, opts_size=None):
+                  combine_scalars=None, opts_size=None, transcripts=None):
     """amdzk_verify_proofs_decide (amdzk_verify_proofs_decide_vk when pk is a VerifyingKey): plonk::verify_proof for a batch WITH
     the pairing. vparams: kzg.ParamsVerifierKZG of the SRS
     the key was made on. combined=False: every proof by itself (SingleStrategy; deterministic, combine_* ignored);
     combined=True: upstream's BatchVerifier — one check with the weights of combine_seed / combine_scalars, which must be
     unpredictable to whoever made the proofs; every well-formed proof gets that check's result. Returns (verdicts, statuses):
-    a list of bool and a list of ProofStatus; a malformed proof has verdict False. A refused call raises."""
+    a list of bool and a list of ProofStatus; a malformed proof has verdict False. A refused call raises. transcripts: as for
+    verify_proofs."""
     B = len(proofs)
-    inst_pp, lens_pp, pp, pl, opts, st, keep = _verify_args(instances_list, proofs, transcript, n_circuits, combine_seed, combine_scalars, opts_size)
+    inst_pp, lens_pp, pp, pl, opts, st, keep = _verify_args(instances_list, proofs, transcript, n_circuits, combine_seed, combine_scalars, opts_size,
+                                                            transcripts)
     verdicts = np.zeros(max(1, B), np.uint8)
     n_valid = C.c_size_t(0)
     fn = ctx.L.amdzk_verify_proofs_decide_vk if isinstance(pk, VerifyingKey) else ctx.L.amdzk_verify_proofs_decide
@@ -1001,21 +1022,33 @@ def decide_proofs(ctx, pk, vparams, instances_list, proofs, transcript=TRANSCRIP
     return out, [ProofStatus(s.status, s.offset) for s in st[:B]]
 
 
-def decide_proof(ctx, pk, vparams, instances, proof, transcript=TRANSCRIPT_BLAKE2B, n_circuits=1):
+def _kind_or_object(transcript, multiopen):
+    """transcript= of verify_proof / decide_proof: the kind flags, or the caller's TranscriptRead object (then `multiopen`,
+    0 or MULTIOPEN_GWC, names the opening scheme). Returns (flags, transcripts argument)."""
+    if isinstance(transcript, (int, np.integer)):
+        return int(transcript) | multiopen, None
+    return multiopen | getattr(transcript, "multiopen", 0), [transcript]
+
+
+def decide_proof(ctx, pk, vparams, instances, proof, transcript=TRANSCRIPT_BLAKE2B, n_circuits=1, multiopen=0):
     """plonk::verify_proof(params, vk, SingleStrategy, &[instances], transcript).is_ok(): True iff the proof is valid. Raises
-    ValueError naming the status and the offset when the proof is malformed, as verify_proof does."""
-    verdicts, statuses = decide_proofs(ctx, pk, vparams, [instances], [proof], transcript=transcript, n_circuits=n_circuits)
+    ValueError naming the status and the offset when the proof is malformed, as verify_proof does. transcript: the kind flags
+    of the bytes `proof`, or the caller's TranscriptRead object (verify_proofs; `proof` may be None, multiopen = MULTIOPEN_GWC
+    for GWC)."""
+    flags, trs = _kind_or_object(transcript, multiopen)
+    verdicts, statuses = decide_proofs(ctx, pk, vparams, [instances], [proof], transcript=flags, n_circuits=n_circuits, transcripts=trs)
     s = statuses[0]
     if s.status != PROOF_WELL_FORMED:
         raise ValueError("malformed proof: status %d (%s), offset %d" % (s.status, PROOF_STATUS_NAMES[s.status], s.offset))
     return verdicts[0]
 
 
-def verify_proof(ctx, pk, instances, proof, transcript=TRANSCRIPT_BLAKE2B, n_circuits=1):
+def verify_proof(ctx, pk, instances, proof, transcript=TRANSCRIPT_BLAKE2B, n_circuits=1, multiopen=0):
     """plonk::verify_proof(params, vk, SingleStrategy, &[instances], transcript) up to the pairing: one proof, weight 1.
     Raises ValueError naming the status and the offset when the proof is malformed; returns its Guard otherwise (the proof
-    is valid iff the caller's pairing check of guard.lhs / guard.rhs holds)."""
-    g = verify_proofs(ctx, pk, [instances], [proof], transcript=transcript, n_circuits=n_circuits)
+    is valid iff the caller's pairing check of guard.lhs / guard.rhs holds). transcript: as for decide_proof."""
+    flags, trs = _kind_or_object(transcript, multiopen)
+    g = verify_proofs(ctx, pk, [instances], [proof], transcript=flags, n_circuits=n_circuits, transcripts=trs)
     s = g.statuses[0]
     if s.status != PROOF_WELL_FORMED:
         raise ValueError("malformed proof: status %d (%s), offset %d" % (s.status, PROOF_STATUS_NAMES[s.status], s.offset))

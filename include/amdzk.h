@@ -696,7 +696,8 @@ int amdzk_check_witness(amdzk_ctx* ctx, amdzk_pk* pk, const uint64_t* const* ins
  * deterministic.) After a failed pairing, find the culprit by calling again on subsets of the batch.
  *
  * instances[b * n_circuits + c][col] / instance_lens[...][col]: the public inputs of circuit instance c of proof b, as for
- * amdzk_create_proof_multi. proofs[b] / proof_lens[b]: the bytes amdzk_create_proof* wrote (built-in transcripts only).
+ * amdzk_create_proof_multi. proofs[b] / proof_lens[b]: the bytes amdzk_create_proof* wrote with a built-in transcript; a proof
+ * made with any other transcript is read through opts->transcripts[b] (amdzk_transcript_read, below).
  * Keys with challenge phases are read in upstream's phased order; n_circuits > 1 reads what amdzk_create_proof_multi wrote.
  *
  * The call returns AMDZK_OK whenever it RAN, as amdzk_check_witness does. A malformed proof gets its status and offset in
@@ -717,14 +718,48 @@ int amdzk_check_witness(amdzk_ctx* ctx, amdzk_pk* pk, const uint64_t* const* ins
 #define AMDZK_PROOF_BAD_INSTANCE 4 /* an instance value >= r, or a column longer than the usable rows */
 typedef struct amdzk_proof_status {
   uint32_t status;
-  uint32_t offset; /* byte offset of the first offending element in the proof (BAD_POINT, BAD_SCALAR); the column index for BAD_INSTANCE; else 0 */
+  uint32_t offset; /* byte offset of the first offending element in the proof (BAD_POINT, BAD_SCALAR; for a proof read through a
+                      transcript: the element's index in read order); the column index for BAD_INSTANCE; the completed read_*
+                      calls for BAD_TRANSCRIPT; else 0 */
 } amdzk_proof_status;
+/* A caller-owned TranscriptRead (`&mut T: TranscriptRead` on the other side; ABI 1013), the mirror image of amdzk_transcript:
+ * the library asks the caller's transcript for every element of the proof and for every challenge, keeps no hash of its own for
+ * such a proof and uses the challenges the callback returns — the Fiat-Shamir binding is the caller's transcript's business,
+ * as upstream. read_point writes a G1Affine (8 words, Montgomery), read_scalar and squeeze_challenge a Montgomery Fr (4 words).
+ * Every member returns 0 on success. For proof b with opts->transcripts[b] set the library calls, from the calling thread,
+ * proof after proof in ascending b and never concurrently: common_scalar(transcript_repr); one common_scalar per public input
+ * (circuit instance, then column, then row); then read_point / read_scalar / squeeze_challenge in exactly the order
+ * amdzk_create_proof_opts documents for write_point / write_scalar / squeeze_challenge (phases, N circuit instances, SHPLONK
+ * or GWC). common_point is part of the interface and is not called by the verifier.
+ * What read_point / read_scalar hand back is NOT trusted: it is checked in the same decode launch as the bytes of the other
+ * proofs — a point must have both coordinates < q, be on y^2 = x^3 + 3 and not be (0, 0) (AMDZK_PROOF_BAD_POINT), a scalar
+ * must be < r (AMDZK_PROOF_BAD_SCALAR); `offset` is then the element's index in read order. There is no conversion.
+ * AMDZK_PROOF_BAD_TRANSCRIPT: a member returned non-zero, a member is NULL, or a squeezed challenge is >= r; `offset` = the
+ * number of read_* calls completed for that proof, and no further member is called for it. The proof drops out like any
+ * malformed proof. */
+typedef struct amdzk_transcript_read {
+  void* user;
+  int (*common_point)(void* user, const uint64_t xy[8]);
+  int (*common_scalar)(void* user, const uint64_t s[4]);
+  int (*read_point)(void* user, uint64_t xy_out[8]);
+  int (*read_scalar)(void* user, uint64_t s_out[4]);
+  int (*squeeze_challenge)(void* user, uint64_t out[4]);
+} amdzk_transcript_read;
+#define AMDZK_PROOF_BAD_TRANSCRIPT 5 /* the caller's read transcript failed (amdzk_transcript_read) */
+/* size: sizeof(amdzk_verify_opts) as compiled by the caller. The size of the struct before `transcripts` was added (every
+ * field in front of it) stays accepted and means transcripts = NULL; any other smaller value is refused.
+ * transcripts: NULL, or n_proofs entries. transcripts[b] == NULL: proof b is the bytes proofs[b] / proof_lens[b] read with the
+ * built-in transcript of transcript_kind; else proof b comes from that transcript, proofs[b] / proof_lens[b] are not read
+ * (proofs / proof_lens may be NULL when every proof has a transcript) and of transcript_kind only AMDZK_MULTIOPEN_GWC counts.
+ * One batch may mix both. With transcripts == NULL nothing changes: pair_out, statuses and verdicts are word for word those
+ * of a library without the field. */
 typedef struct amdzk_verify_opts {
-  size_t size;                     /* sizeof(amdzk_verify_opts) as compiled by the caller; too small is refused */
+  size_t size;
   int transcript_kind;             /* as amdzk_create_proof_ex, AMDZK_MULTIOPEN_GWC included */
   uint32_t n_circuits;             /* circuit instances per proof (amdzk_create_proof_multi); 0 means 1 */
   uint64_t combine_seed;           /* rho_b = the b-th Fr::random of ChaCha20Rng::seed_from_u64(combine_seed) ... */
   const uint64_t* combine_scalars; /* ... or the caller's own: n_proofs x 4 words, Montgomery; wins if set */
+  const amdzk_transcript_read* const* transcripts; /* NULL, or n_proofs caller-owned read transcripts (NULL entries: bytes) */
 } amdzk_verify_opts;
 int amdzk_verify_proofs(amdzk_ctx* ctx, const amdzk_pk* pk, size_t n_proofs, const uint64_t* const* const* instances,
                         const size_t* const* instance_lens, const uint8_t* const* proofs, const size_t* proof_lens,
@@ -847,6 +882,42 @@ int amdzk_verify_proofs_decide(amdzk_ctx* ctx, const amdzk_pk* pk, const amdzk_g
                                size_t n_proofs, const uint64_t* const* const* instances, const size_t* const* instance_lens,
                                const uint8_t* const* proofs, const size_t* proof_lens, const amdzk_verify_opts* opts,
                                amdzk_proof_status* statuses, uint8_t* verdicts /* n_proofs */, size_t* n_valid);
+
+/* ---- the opening argument verified alone (ABI 1013): poly::kzg::multiopen::{VerifierSHPLONK, VerifierGWC}::verify_proof [UP]
+ * over the CALLER's commitments, the counterpart of amdzk_multiopen_dev ("commit, then open" over a resident SRS, checked
+ * without a PLONK proof around it).
+ * g: the G of the SRS the commitments were made over (g[0], G1Affine). commitments: n_coms x 8 words, G1Affine, (0, 0) = the
+ * identity (a zero polynomial's commitment) is allowed. points / queries as for amdzk_multiopen_dev with `poly` indexing
+ * commitments; grouping, point ordering and the duplicate rule are the prover's (csrc/opening.hpp): equal point values are
+ * one point, SHPLONK uses the first query of each (commitment, point value) pair, GWC every query's own. evals: required,
+ * n_queries x 4 words, evals[i] = the evaluation query i claims.
+ * Read order (only squeeze_challenge and read_point are called): SHPLONK squeeze y, squeeze v, read h1, squeeze u, read h2;
+ * GWC squeeze v, read one W per distinct point value in first-seen order, squeeze u.
+ * pair_out: L then R, G1Affine, (0, 0) = the identity, with "the openings are valid iff e(L, [s]_2) = e(R, [1]_2)" — the two
+ * sums of amdzk_verify_proofs' comment with C_ij the caller's commitments, g in G's place and no h(X) expansion.
+ * Device work: one launch checks every commitment and every point that was read (coordinates < q, on the curve; a read point
+ * may not be (0, 0)), one two-column MSM over the commitments, the read points and g. amdzk_multiopen_decide adds one
+ * amdzk_pairing_products call with m = 2: *verdict = 1 iff the check holds; a pair containing the identity gives 0.
+ * No cap on sets, points or queries but memory (commitments and read points together stay below 2^30, where the check's
+ * status word ends: 64 GiB of points). Commitments given as linear combinations of other commitments (upstream's
+ * CommitmentReference::MSM) are NOT built: pass plain commitments.
+ * Refused with a message that starts "multiopen_verify:", the ctx stays usable and the stream is idle: AMDZK_E_INVALID for null
+ * arguments, a too-small opts->size, a missing transcript or member, n_queries = 0, an index out of range, an eval or a point
+ * value >= r, a commitment or a read point that fails its check (the message names which), a non-zero return of a transcript
+ * member, a squeezed challenge >= r; AMDZK_E_NOMEM when scratch cannot be allocated. */
+typedef struct amdzk_multiopen_verify_opts {
+  size_t size;                             /* sizeof(amdzk_multiopen_verify_opts) as the caller compiled it; too small is refused */
+  int scheme;                              /* 0 SHPLONK, AMDZK_MULTIOPEN_GWC for GWC */
+  const amdzk_transcript_read* transcript; /* required */
+} amdzk_multiopen_verify_opts;
+int amdzk_multiopen_verify(amdzk_ctx* ctx, const uint64_t g[8], const uint64_t* commitments, size_t n_coms,
+                           const uint64_t* points, size_t n_points, const amdzk_open_query* queries,
+                           const uint64_t* evals, size_t n_queries, const amdzk_multiopen_verify_opts* opts,
+                           uint64_t pair_out[16]);
+int amdzk_multiopen_decide(amdzk_ctx* ctx, const uint64_t g[8], const uint64_t* commitments, size_t n_coms,
+                           const uint64_t* points, size_t n_points, const amdzk_open_query* queries,
+                           const uint64_t* evals, size_t n_queries, const amdzk_multiopen_verify_opts* opts,
+                           const amdzk_g2* s_g2, const amdzk_g2* g2, uint8_t* verdict);
 
 /* ---- verifying keys: verify and decide proofs without a proving key.
  * amdzk_vk is what plonk::verify_proof [UP] reads of its VerifyingKey and its params: the circuit description,

@@ -1203,10 +1203,12 @@ class WitnessStream {
 struct ProofStatus {
   enum Status : uint32_t {
     WellFormed = AMDZK_PROOF_WELL_FORMED, BadLength = AMDZK_PROOF_BAD_LENGTH, BadPoint = AMDZK_PROOF_BAD_POINT,
-    BadScalar = AMDZK_PROOF_BAD_SCALAR, BadInstance = AMDZK_PROOF_BAD_INSTANCE
+    BadScalar = AMDZK_PROOF_BAD_SCALAR, BadInstance = AMDZK_PROOF_BAD_INSTANCE, BadTranscript = AMDZK_PROOF_BAD_TRANSCRIPT
   };
   Status status;
-  uint32_t offset;  // byte offset of the first offending element (BadPoint, BadScalar), the column (BadInstance), else 0
+  // byte offset of the first offending element (BadPoint, BadScalar; its index in read order for a proof read through a
+  // TranscriptRead), the column (BadInstance), the read_* calls completed (BadTranscript), else 0
+  uint32_t offset;
 };
 struct Guard {
   G1Affine lhs, rhs;
@@ -1569,6 +1571,233 @@ inline bool decide_proof(const Context& ctx, const VerifyingKey& vk, const Param
                          const std::vector<uint8_t>& proof, Transcript transcript = Transcript::Blake2b, Multiopen multiopen = Multiopen::Shplonk) {
   return detail::decide_proof(ctx, vk, vparams, instances, proof, transcript, multiopen);
 }
+
+// ------------------------------------------------------------------------------------------ the caller's read transcript
+// transcript::TranscriptRead as far as verify_proof uses it: implement it to own the transcript (`&mut T: TranscriptRead`
+// upstream; amdzk_transcript_read). Values are Montgomery. The library keeps no hash of its own for such a proof and uses the
+// challenges squeeze_challenge returns; what read_point / read_scalar return is checked on the device like a proof's bytes.
+// A member that throws makes its proof ProofStatus::BadTranscript; the single-proof calls rethrow the exception.
+class TranscriptRead {
+ public:
+  virtual ~TranscriptRead() {}
+  virtual void common_point(const G1Affine& p) = 0;
+  virtual void common_scalar(const Fr& s) = 0;
+  virtual G1Affine read_point() = 0;
+  virtual Fr read_scalar() = 0;
+  virtual Fr squeeze_challenge() = 0;
+};
+
+namespace detail {
+struct ReadTrampoline {
+  TranscriptRead* t;
+  std::exception_ptr err;
+  template <class F>
+  int guard(F&& f) {
+    try {
+      f();
+      return 0;
+    } catch (...) {
+      if (!err) err = std::current_exception();
+      return 1;
+    }
+  }
+};
+inline amdzk_transcript_read c_transcript_read(ReadTrampoline* tr) {
+  amdzk_transcript_read ct;
+  ct.user = tr;
+  ct.common_point = [](void* u, const uint64_t* xy) { auto* t = (ReadTrampoline*)u; return t->guard([&] { G1Affine p; std::memcpy(&p, xy, 64); t->t->common_point(p); }); };
+  ct.common_scalar = [](void* u, const uint64_t* s) { auto* t = (ReadTrampoline*)u; return t->guard([&] { Fr v; std::memcpy(v.l, s, 32); t->t->common_scalar(v); }); };
+  ct.read_point = [](void* u, uint64_t* out) { auto* t = (ReadTrampoline*)u; return t->guard([&] { const G1Affine p = t->t->read_point(); std::memcpy(out, &p, 64); }); };
+  ct.read_scalar = [](void* u, uint64_t* out) { auto* t = (ReadTrampoline*)u; return t->guard([&] { const Fr v = t->t->read_scalar(); std::memcpy(out, v.l, 32); }); };
+  ct.squeeze_challenge = [](void* u, uint64_t* out) { auto* t = (ReadTrampoline*)u; return t->guard([&] { const Fr v = t->t->squeeze_challenge(); std::memcpy(out, v.l, 32); }); };
+  return ct;
+}
+// the C side of a batch of read transcripts; must outlive the call
+struct ReadBatch {
+  std::vector<ReadTrampoline> tramp;
+  std::vector<amdzk_transcript_read> c;
+  std::vector<const amdzk_transcript_read*> ptrs;
+  explicit ReadBatch(const std::vector<TranscriptRead*>& ts) : tramp(ts.size()), c(ts.size()), ptrs(std::max<size_t>(1, ts.size()), nullptr) {
+    for (size_t b = 0; b < ts.size(); b++) {
+      if (!ts[b]) throw Error(AMDZK_E_INVALID, "verify_proofs: null transcript");
+      tramp[b] = ReadTrampoline{ts[b], nullptr};
+      c[b] = c_transcript_read(&tramp[b]);
+      ptrs[b] = &c[b];
+    }
+  }
+  void rethrow_first() const {
+    for (const ReadTrampoline& t : tramp)
+      if (t.err) std::rethrow_exception(t.err);
+  }
+};
+template <class Key>
+Guard verify_proofs_read(const Context& ctx, const Key& key, const std::vector<std::vector<std::vector<std::vector<Fr>>>>& instances,
+                         const std::vector<TranscriptRead*>& transcripts, Multiopen multiopen, uint64_t combine_seed,
+                         const std::vector<Fr>& combine_scalars, bool rethrow) {
+  ReadBatch rb(transcripts);
+  VerifyArgs a("verify_proofs", instances, std::vector<std::vector<uint8_t>>(transcripts.size()), Transcript::Blake2b, multiopen, combine_seed, combine_scalars);
+  a.opts.transcripts = rb.ptrs.data();
+  uint64_t pair[16];
+  const int rc = c_verify(ctx.get(), key.handle(), a, pair);
+  if (rethrow) rb.rethrow_first();
+  ctx.check(rc);
+  Guard g;
+  std::memcpy(&g.lhs, pair, sizeof(G1Affine));
+  std::memcpy(&g.rhs, pair + 8, sizeof(G1Affine));
+  g.statuses = a.statuses();
+  return g;
+}
+template <class Key>
+Decision decide_proofs_read(const Context& ctx, const Key& key, const ParamsVerifierKZG& vparams,
+                            const std::vector<std::vector<std::vector<std::vector<Fr>>>>& instances, const std::vector<TranscriptRead*>& transcripts,
+                            Multiopen multiopen, bool combined, uint64_t combine_seed, const std::vector<Fr>& combine_scalars, bool rethrow) {
+  ReadBatch rb(transcripts);
+  VerifyArgs a("decide_proofs", instances, std::vector<std::vector<uint8_t>>(transcripts.size()), Transcript::Blake2b, multiopen, combine_seed, combine_scalars);
+  a.opts.transcripts = rb.ptrs.data();
+  std::vector<uint8_t> v(std::max<size_t>(1, a.B), 0);
+  Decision d;
+  const int rc = c_decide(ctx.get(), key.handle(), vparams, combined ? AMDZK_DECIDE_COMBINED : 0u, a, v.data(), &d.n_valid);
+  if (rethrow) rb.rethrow_first();
+  ctx.check(rc);
+  for (size_t b = 0; b < a.B; b++) d.verdicts.push_back(v[b] != 0);
+  d.statuses = a.statuses();
+  return d;
+}
+inline void throw_malformed(const char* who, const ProofStatus& s) {
+  if (s.status != ProofStatus::WellFormed)
+    throw Error(AMDZK_E_INVALID, std::string(who) + ": malformed proof, status " + std::to_string((unsigned)s.status) + ", offset " + std::to_string(s.offset));
+}
+}  // namespace detail
+
+// verify_proofs / verify_proof / decide_proofs / decide_proof generic over `T: TranscriptRead`: one transcript per proof in
+// the place of the bytes (Key = ProvingKey or VerifyingKey). Of the built-in kinds only `multiopen` remains to be named.
+template <class Key>
+Guard verify_proofs(const Context& ctx, const Key& key, const std::vector<std::vector<std::vector<std::vector<Fr>>>>& instances,
+                    const std::vector<TranscriptRead*>& transcripts, Multiopen multiopen = Multiopen::Shplonk, uint64_t combine_seed = 0,
+                    const std::vector<Fr>& combine_scalars = {}) {
+  return detail::verify_proofs_read(ctx, key, instances, transcripts, multiopen, combine_seed, combine_scalars, false);
+}
+template <class Key>
+Guard verify_proof(const Context& ctx, const Key& key, const std::vector<std::vector<Fr>>& instances, TranscriptRead& transcript,
+                   Multiopen multiopen = Multiopen::Shplonk) {
+  Guard g = detail::verify_proofs_read(ctx, key, {{instances}}, {&transcript}, multiopen, 0, {}, true);
+  detail::throw_malformed("verify_proof", g.statuses[0]);
+  return g;
+}
+template <class Key>
+Decision decide_proofs(const Context& ctx, const Key& key, const ParamsVerifierKZG& vparams,
+                       const std::vector<std::vector<std::vector<std::vector<Fr>>>>& instances, const std::vector<TranscriptRead*>& transcripts,
+                       Multiopen multiopen = Multiopen::Shplonk, bool combined = false, uint64_t combine_seed = 0,
+                       const std::vector<Fr>& combine_scalars = {}) {
+  return detail::decide_proofs_read(ctx, key, vparams, instances, transcripts, multiopen, combined, combine_seed, combine_scalars, false);
+}
+template <class Key>
+bool decide_proof(const Context& ctx, const Key& key, const ParamsVerifierKZG& vparams, const std::vector<std::vector<Fr>>& instances,
+                  TranscriptRead& transcript, Multiopen multiopen = Multiopen::Shplonk) {
+  const Decision d = detail::decide_proofs_read(ctx, key, vparams, {{instances}}, {&transcript}, multiopen, false, 0, {}, true);
+  detail::throw_malformed("decide_proof", d.statuses[0]);
+  return d.verdicts[0];
+}
+
+// ------------------------------------------------------------------------------------------ multiopen verified on its own
+// poly::kzg::multiopen::{VerifierSHPLONK, VerifierGWC} over the caller's commitments (amdzk_multiopen_verify / _decide).
+// poly::query::VerifierQuery with a plain commitment (upstream's CommitmentReference::MSM is not built): a commitment's
+// identity is its words, equal point values are one point, `eval` is the evaluation the query claims.
+struct VerifierQuery {
+  G1Affine commitment;
+  Fr point;
+  Fr eval;
+};
+struct OpeningGuard {
+  G1Affine lhs, rhs;  // valid iff e(lhs, [s]_2) = e(rhs, [1]_2); (0, 0) is the identity
+};
+
+namespace detail {
+// verify_proof of poly::commitment::Verifier; vparams == nullptr: up to the pairing
+inline bool multiopen_verify(const Context& ctx, const G1Affine& g, Multiopen scheme, TranscriptRead& transcript, const std::vector<VerifierQuery>& queries,
+                             const ParamsVerifierKZG* vparams, OpeningGuard* guard) {
+  std::vector<G1Affine> coms;
+  std::vector<Fr> points, evals(queries.size());
+  std::map<std::array<uint64_t, 8>, uint32_t> com_of;
+  std::map<std::array<uint64_t, 4>, uint32_t> point_of;
+  std::vector<amdzk_open_query> q(queries.size());
+  for (size_t i = 0; i < queries.size(); i++) {
+    std::array<uint64_t, 8> ck;
+    std::memcpy(ck.data(), &queries[i].commitment, 64);
+    auto ci = com_of.find(ck);
+    if (ci == com_of.end()) {
+      ci = com_of.emplace(ck, (uint32_t)coms.size()).first;
+      coms.push_back(queries[i].commitment);
+    }
+    const std::array<uint64_t, 4> key{{queries[i].point.l[0], queries[i].point.l[1], queries[i].point.l[2], queries[i].point.l[3]}};
+    auto zi = point_of.find(key);
+    if (zi == point_of.end()) {
+      zi = point_of.emplace(key, (uint32_t)points.size()).first;
+      points.push_back(queries[i].point);
+    }
+    q[i].poly = ci->second;
+    q[i].point = zi->second;
+    evals[i] = queries[i].eval;
+  }
+  ReadTrampoline tr{&transcript, nullptr};
+  const amdzk_transcript_read ct = c_transcript_read(&tr);
+  amdzk_multiopen_verify_opts opts;
+  std::memset(&opts, 0, sizeof(opts));
+  opts.size = sizeof(opts);
+  opts.scheme = (int)scheme;
+  opts.transcript = &ct;
+  uint64_t pair[16];
+  uint8_t verdict = 0;
+  const int rc = vparams ? amdzk_multiopen_decide(ctx.get(), (const uint64_t*)&g, (const uint64_t*)coms.data(), coms.size(), (const uint64_t*)points.data(),
+                                                  points.size(), q.data(), (const uint64_t*)evals.data(), q.size(), &opts, vparams->s_g2.handle(),
+                                                  vparams->g2.handle(), &verdict)
+                         : amdzk_multiopen_verify(ctx.get(), (const uint64_t*)&g, (const uint64_t*)coms.data(), coms.size(), (const uint64_t*)points.data(),
+                                                  points.size(), q.data(), (const uint64_t*)evals.data(), q.size(), &opts, pair);
+  if (rc != AMDZK_OK && tr.err) std::rethrow_exception(tr.err);
+  ctx.check(rc);
+  if (guard && !vparams) {
+    std::memcpy(&guard->lhs, pair, sizeof(G1Affine));
+    std::memcpy(&guard->rhs, pair + 8, sizeof(G1Affine));
+  }
+  return verdict != 0;
+}
+}  // namespace detail
+
+// g: the SRS's g[0] (ParamsKZG::get_g()[0], or a verifying key's). verify_proof leaves the pairing to the caller; decide
+// makes it on the device.
+class VerifierSHPLONK {
+ public:
+  VerifierSHPLONK(const Context& ctx, const G1Affine& g) : ctx_(ctx), g_(g) {}
+  OpeningGuard verify_proof(TranscriptRead& transcript, const std::vector<VerifierQuery>& queries) const {
+    OpeningGuard out;
+    detail::multiopen_verify(ctx_, g_, Multiopen::Shplonk, transcript, queries, nullptr, &out);
+    return out;
+  }
+  bool decide(TranscriptRead& transcript, const std::vector<VerifierQuery>& queries, const ParamsVerifierKZG& vparams) const {
+    return detail::multiopen_verify(ctx_, g_, Multiopen::Shplonk, transcript, queries, &vparams, nullptr);
+  }
+
+ private:
+  const Context& ctx_;
+  G1Affine g_;
+};
+
+class VerifierGWC {
+ public:
+  VerifierGWC(const Context& ctx, const G1Affine& g) : ctx_(ctx), g_(g) {}
+  OpeningGuard verify_proof(TranscriptRead& transcript, const std::vector<VerifierQuery>& queries) const {
+    OpeningGuard out;
+    detail::multiopen_verify(ctx_, g_, Multiopen::Gwc, transcript, queries, nullptr, &out);
+    return out;
+  }
+  bool decide(TranscriptRead& transcript, const std::vector<VerifierQuery>& queries, const ParamsVerifierKZG& vparams) const {
+    return detail::multiopen_verify(ctx_, g_, Multiopen::Gwc, transcript, queries, &vparams, nullptr);
+  }
+
+ private:
+  const Context& ctx_;
+  G1Affine g_;
+};
 
 }  // namespace halo2
 }  // namespace amdzk
