@@ -146,6 +146,11 @@ def lib():
         "amdzk_verify_proofs_vk": (i32, [vp, vp, sz, C.POINTER(C.POINTER(vp)), C.POINTER(C.POINTER(sz)), C.POINTER(vp), C.POINTER(sz), vp, vp, vp]),
         "amdzk_verify_proofs_decide_vk": (i32, [vp, vp, vp, vp, u32, sz, C.POINTER(C.POINTER(vp)), C.POINTER(C.POINTER(sz)), C.POINTER(vp),
                                                 C.POINTER(sz), vp, vp, vp, C.POINTER(sz)]),
+        "amdzk_witness_plan": (i32, [vp, sz, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(sz), C.c_char_p, sz]),
+        "amdzk_witness_compile": (i32, [vp, vp, C.POINTER(vp)]),
+        "amdzk_witness_free": (None, [vp, vp]),
+        "amdzk_witness_run": (i32, [vp, vp, sz, C.POINTER(vp), C.POINTER(vp), sz, u32, sz, vp]),
+        "amdzk_witness_run_dev": (i32, [vp, vp, sz, vp, sz, C.POINTER(vp), sz, u32, sz, vp]),
         "amdzk_debug_limb_program": (i32, [vp, sz, vp, sz, C.POINTER(sz), C.POINTER(u32)]),
         "amdzk_pk_h_program": (i32, [vp, vp, sz, C.POINTER(sz)]),
         "amdzk_timer_start": (i32, [vp]),
@@ -266,6 +271,14 @@ def read_transcript(tobj, errors):
     return tr, cbs + [tr]
 
 
+class WitnessDesc(C.Structure):  # amdzk_witness_desc
+    _fields_ = [("size", C.c_size_t), ("k", C.c_uint32), ("num_advice", C.c_uint32), ("n_inputs", C.c_uint32), ("n_constants", C.c_uint32),
+                ("constants", C.c_void_p), ("n_nodes", C.c_uint32), ("nodes", C.c_void_p), ("n_cells", C.c_uint32), ("cells", C.c_void_p),
+                ("n_publics", C.c_uint32), ("publics", C.c_void_p)]
+
+
+WNODE = np.dtype([("op", np.uint32), ("a", np.uint32), ("b", np.uint32), ("c", np.uint32)])  # amdzk_wnode
+WCELL = np.dtype([("node", np.uint32), ("column", np.uint32), ("row", np.uint32)])  # amdzk_wcell
 OPEN_QUERY = np.dtype([("poly", np.uint32), ("point", np.uint32)])  # amdzk_open_query
 
 

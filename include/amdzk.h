@@ -986,6 +986,127 @@ int amdzk_verify_proofs_decide_vk(amdzk_ctx* ctx, const amdzk_vk* vk, const amdz
                                   const uint8_t* const* proofs, const size_t* proof_lens, const amdzk_verify_opts* opts,
                                   amdzk_proof_status* statuses, uint8_t* verdicts /* n_proofs */, size_t* n_valid);
 
+/* ---- witness programs: the advice cells of a batch of proofs computed on the device (ABI 1014).
+ * Every create_proof starts from the advice columns, and every entry point above takes them as given (d_advice). For the
+ * halo2-base style circuits of the reference, `synthesize` is a fixed straight-line computation over a few per-proof inputs:
+ * field additions and products, bit and limb decompositions, carries, selects, landing in cells that are fixed per circuit.
+ * A witness program carries that arithmetic across this boundary as DATA, the way amdzk_circuit carries the constraint
+ * system: compiled once per circuit, then run for a whole batch, writing straight into the buffers that
+ * amdzk_create_proof_batch (or amdzk_check_witness) reads. What is not field arithmetic — the quotient and remainder of a big
+ * product, a native hash — is computed by the host per proof and enters as an input (a "hint").
+ *
+ * A program is a list of nodes in SSA order: node i names only nodes < i. A node's value is one Fr per proof of the batch.
+ * All ops are total; canon(x) is the canonical integer of x in [0, r). Fields of amdzk_wnode an op does not use are ignored.
+ *   AMDZK_W_INPUT   a        input a of this proof (a < n_inputs)
+ *   AMDZK_W_CONST   a        constants[a] (a < n_constants)
+ *   AMDZK_W_ADD     a b      a + b            AMDZK_W_SUB a b   a - b          (in Fr; a, b, c below are node indices)
+ *   AMDZK_W_MUL     a b      a * b            AMDZK_W_NEG a     -a
+ *   AMDZK_W_INV     a        a^-1, and 0 for 0 (as amdzk_batch_invert_dev)
+ *   AMDZK_W_SELECT  a b c    b if a != 0, else c
+ *   AMDZK_W_IS_ZERO a        1 if a == 0, else 0
+ *   AMDZK_W_EQ      a b      1 if a == b, else 0
+ *   AMDZK_W_LT      a b      1 if canon(a) < canon(b), else 0
+ *   AMDZK_W_BITS    a, b = lo, c = len    (canon(a) >> lo) mod 2^len; lo and len are immediates, len >= 1, lo + len <= 256
+ *                            (bit extraction, limb decomposition, and >> for carries)
+ *   AMDZK_W_AND     a b      canon(a) & canon(b)
+ *   AMDZK_W_XOR     a b      (canon(a) ^ canon(b)) mod r
+ * There is no division by a variable and no op that serves one gadget: those are compositions of the above, or hints.
+ * Phase-dependent programs need nothing more: a later phase's program can be run from an amdzk_phase_fn callback with the
+ * challenges among its inputs.
+ *
+ * amdzk_witness_compile validates the description, levelizes it (INPUT and CONST are level 0, every other node is one level
+ * above its highest operand), orders the nodes by level, uploads the tables and keeps no pointer into the caller's arrays.
+ * Refused with AMDZK_E_INVALID and a message that starts "witness:" — null arguments (an array pointer may be NULL only when
+ * its count is 0), a too-small desc->size, k > 31, an unknown op, an operand >= its own node index, an input or constant
+ * index out of range, a constant >= r, BITS with len = 0 or lo + len > 256, a cell with column >= num_advice or
+ * row >= 2^k or node >= n_nodes, a cell named twice, a public node >= n_nodes. Because every index a kernel follows is checked
+ * here, a run reads and writes nothing outside its tables, its workspace and the named cells.
+ *
+ * amdzk_witness_run: inputs[b] = the n_inputs x 4 words of proof b on the host (Montgomery, < r). d_advice[b] (a HOST array of
+ * n_proofs device pointers) and advice_stride (Fr per column, >= 2^k) are as for amdzk_create_proof_batch: column c of proof
+ * b at d_advice[b] + c * advice_stride; the buffers are pairwise different, non-null and on this ctx's device. The value of
+ * cells[j].node is written to its (column, row) of every proof. With AMDZK_WITNESS_ZERO_FILL all num_advice x 2^k cells of
+ * every proof are zeroed first; without it, cells that no amdzk_wcell names keep what they hold. The (advice_stride - 2^k)
+ * elements between two columns are never written. publics_out (may be NULL): n_proofs x n_publics x 4 words, proof-major,
+ * the values of the nodes in `publics` (the instance values of the proof), Montgomery.
+ * Workspace: one run of P proofs holds (n_nodes + n_publics) x P x 32 + 256 bytes (every node's value for every proof of the
+ * run, the publics gathered for the copy back, a status word); the host-pointer form stages n_proofs x n_inputs x 32 bytes
+ * more. The workspace belongs to the amdzk_witness handle and only grows. max_scratch_bytes bounds the first figure; 0 = the
+ * library's default (16 GiB). A batch that needs more is cut into the fewest equal runs of proofs that fit — R runs of
+ * P = ceil(n_proofs / R) proofs, the last one shorter — and a run is also held below 2^31 (node, proof) items per level.
+ * The results do not depend on the cut. A bound below one proof's workspace is refused (AMDZK_E_INVALID).
+ * Execution: one work item per (node of a level, proof); a level wider than fused_width items is one kernel launch, and every
+ * maximal stretch of consecutive levels of at most fused_width items each is ONE launch of a single workgroup that puts a
+ * workgroup barrier between levels; then one launch scatters the cells and one gathers the publics. Ordering between
+ * launches is stream order alone. The call runs on the ctx's stream and returns with it idle: work submitted afterwards on
+ * the ctx sees the cells. One amdzk_witness is used by one call at a time.
+ * Refused with a message that starts "witness:", the ctx stays usable and NOTHING has been written to any d_advice —
+ * AMDZK_E_INVALID: null arguments, n_proofs = 0, a null or repeated d_advice pointer or one that is not device memory of this
+ * ctx's GPU, advice_stride < 2^k, input_stride < n_inputs, unknown flag bits, an input value >= r (host form: checked on the
+ * host; _dev form: by a check launch before anything else, whose status word names the first offender); AMDZK_E_UNSUPPORTED:
+ * sizes whose workspace arithmetic would overflow, or a program of which one proof does not fit the default workspace.
+ *
+ * amdzk_witness_run_dev: the same with the inputs resident: input a of proof b at d_inputs + (b * input_stride + a) Fr.
+ * The host-pointer form stages its inputs and runs the same code.
+ *
+ * amdzk_witness_plan: pure host code, callable without a device (like amdzk_msm_g1_bases_plan). Runs every validation of
+ * amdzk_witness_compile and reports, for a run of n_proofs with the default max_scratch_bytes: *levels = the number of
+ * levels (1 + the longest operand path; 0 for an empty program); *launches = the kernel launches amdzk_witness_run makes for
+ * the levels, the scatter (if n_cells > 0) and the gather (if n_publics > 0), summed over its runs — the zero fill adds one
+ * per call and the _dev form's input check one per call; *fused_width = the widest level, in (node, proof) items, that still
+ * goes into a single-workgroup launch; *scratch_bytes = the workspace formula above for the run's P. Any output pointer may
+ * be NULL; msg (may be NULL) receives the refusal's message, truncated to msg_cap. */
+#define AMDZK_W_INPUT 0
+#define AMDZK_W_CONST 1
+#define AMDZK_W_ADD 2
+#define AMDZK_W_SUB 3
+#define AMDZK_W_MUL 4
+#define AMDZK_W_NEG 5
+#define AMDZK_W_INV 6
+#define AMDZK_W_SELECT 7
+#define AMDZK_W_IS_ZERO 8
+#define AMDZK_W_EQ 9
+#define AMDZK_W_LT 10
+#define AMDZK_W_BITS 11
+#define AMDZK_W_AND 12
+#define AMDZK_W_XOR 13
+#define AMDZK_WITNESS_ZERO_FILL 1u
+typedef struct amdzk_witness amdzk_witness;
+typedef struct amdzk_wnode { /* 16 bytes */
+  uint32_t op;
+  uint32_t a;
+  uint32_t b;
+  uint32_t c;
+} amdzk_wnode;
+typedef struct amdzk_wcell {
+  uint32_t node;
+  uint32_t column; /* advice column < num_advice */
+  uint32_t row;    /* < 2^k */
+} amdzk_wcell;
+typedef struct amdzk_witness_desc {
+  size_t size;               /* sizeof(amdzk_witness_desc) as compiled by the caller; too small is refused */
+  uint32_t k;                /* rows = 2^k: the bound of amdzk_wcell.row */
+  uint32_t num_advice;       /* the bound of amdzk_wcell.column */
+  uint32_t n_inputs;         /* per-proof inputs (Montgomery Fr, < r) */
+  uint32_t n_constants;
+  const uint64_t* constants; /* n_constants x 4 words, Montgomery, < r */
+  uint32_t n_nodes;
+  const amdzk_wnode* nodes;
+  uint32_t n_cells;
+  const amdzk_wcell* cells;  /* node -> advice cell; a cell named twice is refused; a node may go to several cells */
+  uint32_t n_publics;
+  const uint32_t* publics;   /* nodes returned to the host per proof (instance values); repeats allowed */
+} amdzk_witness_desc;
+int amdzk_witness_plan(const amdzk_witness_desc* desc, size_t n_proofs, uint32_t* levels, uint32_t* launches, uint32_t* fused_width,
+                       size_t* scratch_bytes, char* msg, size_t msg_cap);
+int amdzk_witness_compile(amdzk_ctx* ctx, const amdzk_witness_desc* desc, amdzk_witness** out);
+void amdzk_witness_free(amdzk_ctx* ctx, amdzk_witness* w);
+int amdzk_witness_run(amdzk_ctx* ctx, amdzk_witness* w, size_t n_proofs, const uint64_t* const* inputs, void* const* d_advice,
+                      size_t advice_stride, uint32_t flags, size_t max_scratch_bytes, uint64_t* publics_out);
+int amdzk_witness_run_dev(amdzk_ctx* ctx, amdzk_witness* w, size_t n_proofs, const void* d_inputs, size_t input_stride,
+                          void* const* d_advice, size_t advice_stride, uint32_t flags, size_t max_scratch_bytes,
+                          uint64_t* publics_out);
+
 /* Test hooks for the host pass that prepares quotient-domain programs for the limb-resident interpreter (bounds in
  * units of p, placement of the weak reductions, fusion of `t*x` with the accumulate): the pass on caller-supplied words
  * `op << 24 | arg` (opcodes: csrc/plonk_kernels.hpp ExprOp) — pure host code, callable without a device — and the

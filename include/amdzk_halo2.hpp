@@ -1196,6 +1196,144 @@ class WitnessStream {
   void* pin_[2] = {nullptr, nullptr};
 };
 
+// ------------------------------------------------------------------------------------------ witness programs
+// The advice cells of a batch computed on the device (amdzk.h "witness programs"): what Circuit::synthesize does for a
+// halo2-base style circuit — a fixed straight-line computation over a few per-proof inputs — recorded once as nodes, then
+// run for a whole batch straight into the buffers create_proof_batch reads. Every method returns the new node's index; what
+// is not field arithmetic the host computes per proof and passes as an input.
+class WitnessProgram {
+ public:
+  using Node = uint32_t;
+  WitnessProgram(uint32_t k, uint32_t num_advice) : k_(k), num_advice_(num_advice) {}
+
+  Node input() { return node(AMDZK_W_INPUT, n_inputs_++); }  // inputs are numbered in the order of these calls
+  Node constant(const Fr& v) {
+    auto it = const_idx_.find(v);
+    if (it == const_idx_.end()) {
+      it = const_idx_.emplace(v, (uint32_t)constants_.size()).first;
+      constants_.push_back(v);
+    }
+    return node(AMDZK_W_CONST, it->second);
+  }
+  Node add(Node a, Node b) { return node(AMDZK_W_ADD, a, b); }
+  Node sub(Node a, Node b) { return node(AMDZK_W_SUB, a, b); }
+  Node mul(Node a, Node b) { return node(AMDZK_W_MUL, a, b); }
+  Node neg(Node a) { return node(AMDZK_W_NEG, a); }
+  Node inv(Node a) { return node(AMDZK_W_INV, a); }
+  Node select(Node cond, Node then, Node otherwise) { return node(AMDZK_W_SELECT, cond, then, otherwise); }
+  Node is_zero(Node a) { return node(AMDZK_W_IS_ZERO, a); }
+  Node eq(Node a, Node b) { return node(AMDZK_W_EQ, a, b); }
+  Node lt(Node a, Node b) { return node(AMDZK_W_LT, a, b); }
+  Node bits(Node a, uint32_t lo, uint32_t len) { return node(AMDZK_W_BITS, a, lo, len); }  // (canon(a) >> lo) mod 2^len
+  Node and_(Node a, Node b) { return node(AMDZK_W_AND, a, b); }
+  Node xor_(Node a, Node b) { return node(AMDZK_W_XOR, a, b); }
+  // the value of `n` goes to advice cell (column, row) of every proof
+  Node assign(Node n, uint32_t column, uint32_t row) {
+    cells_.push_back(amdzk_wcell{n, column, row});
+    return n;
+  }
+  // `n` is returned to the host per proof (an instance value); its position among the publics
+  uint32_t expose(Node n) {
+    publics_.push_back(n);
+    return (uint32_t)publics_.size() - 1;
+  }
+
+  // valid while the program is alive and unchanged
+  amdzk_witness_desc desc() const {
+    amdzk_witness_desc d;
+    std::memset(&d, 0, sizeof(d));
+    d.size = sizeof(d);
+    d.k = k_;
+    d.num_advice = num_advice_;
+    d.n_inputs = n_inputs_;
+    d.n_constants = (uint32_t)constants_.size();
+    d.constants = constants_.empty() ? nullptr : constants_[0].l;
+    d.n_nodes = (uint32_t)nodes_.size();
+    d.nodes = nodes_.data();
+    d.n_cells = (uint32_t)cells_.size();
+    d.cells = cells_.data();
+    d.n_publics = (uint32_t)publics_.size();
+    d.publics = publics_.data();
+    return d;
+  }
+  struct Plan {
+    uint32_t levels, launches, fused_width;
+    size_t scratch_bytes;
+  };
+  Plan plan(size_t n_proofs) const {  // amdzk_witness_plan: no device needed
+    const amdzk_witness_desc d = desc();
+    Plan p{};
+    char msg[256] = "";
+    const int rc = amdzk_witness_plan(&d, n_proofs, &p.levels, &p.launches, &p.fused_width, &p.scratch_bytes, msg, sizeof(msg));
+    if (rc != AMDZK_OK) throw Error(rc, msg);
+    return p;
+  }
+  uint32_t k() const { return k_; }
+  uint32_t num_inputs() const { return n_inputs_; }
+  uint32_t num_publics() const { return (uint32_t)publics_.size(); }
+
+ private:
+  Node node(uint32_t op, uint32_t a = 0, uint32_t b = 0, uint32_t c = 0) {
+    nodes_.push_back(amdzk_wnode{op, a, b, c});
+    return (Node)nodes_.size() - 1;
+  }
+  uint32_t k_, num_advice_, n_inputs_ = 0;
+  std::vector<Fr> constants_;
+  std::map<Fr, uint32_t> const_idx_;
+  std::vector<amdzk_wnode> nodes_;
+  std::vector<amdzk_wcell> cells_;
+  std::vector<uint32_t> publics_;
+};
+
+// amdzk_witness: a program resident on the context's device. One run at a time.
+class CompiledWitness {
+ public:
+  CompiledWitness(const Context& ctx, const WitnessProgram& prog) : ctx_(ctx), k_(prog.k()), n_inputs_(prog.num_inputs()), n_publics_(prog.num_publics()) {
+    const amdzk_witness_desc d = prog.desc();
+    ctx_.check(amdzk_witness_compile(ctx_.get(), &d, &h_));
+  }
+  ~CompiledWitness() {
+    if (h_) amdzk_witness_free(ctx_.get(), h_);
+  }
+  CompiledWitness(const CompiledWitness&) = delete;
+  CompiledWitness& operator=(const CompiledWitness&) = delete;
+
+  // inputs[b]: the n_inputs values of proof b; d_advice[b]: its buffer (as for create_proof_batch; advice_stride 0 = 2^k).
+  // Returns the publics, one vector per proof.
+  std::vector<std::vector<Fr>> run(const std::vector<std::vector<Fr>>& inputs, const std::vector<void*>& d_advice, size_t advice_stride = 0,
+                                   uint32_t flags = 0, size_t max_scratch_bytes = 0) const {
+    if (inputs.size() != d_advice.size()) throw Error(AMDZK_E_INVALID, "witness: one input row and one buffer per proof");
+    std::vector<const uint64_t*> in(inputs.size());
+    for (size_t b = 0; b < inputs.size(); b++) {
+      if (inputs[b].size() != n_inputs_) throw Error(AMDZK_E_INVALID, "witness: input count");
+      in[b] = inputs[b].empty() ? nullptr : inputs[b][0].l;
+    }
+    std::vector<Fr> flat(inputs.size() * n_publics_);
+    ctx_.check(amdzk_witness_run(ctx_.get(), h_, inputs.size(), n_inputs_ ? in.data() : nullptr, d_advice.data(),
+                                 advice_stride ? advice_stride : (size_t)1 << k_, flags, max_scratch_bytes, flat.empty() ? nullptr : flat[0].l));
+    return split(flat, inputs.size());
+  }
+  // the inputs resident: proof b at d_inputs + b * input_stride Fr
+  std::vector<std::vector<Fr>> run_dev(const void* d_inputs, size_t input_stride, const std::vector<void*>& d_advice, size_t advice_stride = 0,
+                                       uint32_t flags = 0, size_t max_scratch_bytes = 0) const {
+    std::vector<Fr> flat(d_advice.size() * n_publics_);
+    ctx_.check(amdzk_witness_run_dev(ctx_.get(), h_, d_advice.size(), d_inputs, input_stride, d_advice.data(),
+                                     advice_stride ? advice_stride : (size_t)1 << k_, flags, max_scratch_bytes, flat.empty() ? nullptr : flat[0].l));
+    return split(flat, d_advice.size());
+  }
+  amdzk_witness* get() const { return h_; }
+
+ private:
+  std::vector<std::vector<Fr>> split(const std::vector<Fr>& flat, size_t n) const {
+    std::vector<std::vector<Fr>> out(n);
+    for (size_t b = 0; b < n; b++) out[b].assign(flat.begin() + b * n_publics_, flat.begin() + (b + 1) * n_publics_);
+    return out;
+  }
+  const Context& ctx_;
+  uint32_t k_, n_inputs_, n_publics_;
+  amdzk_witness* h_ = nullptr;
+};
+
 // ------------------------------------------------------------------------------------------ verify_proof up to the pairing
 // plonk::verify_proof [UP] without its last step (amdzk_verify_proofs): what upstream's verifier hands to its strategy as a
 // GuardKZG. Every well-formed proof that went in is valid iff e(lhs, [s]_2) = e(rhs, [1]_2) — ONE pairing check, which stays
