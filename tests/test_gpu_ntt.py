@@ -77,45 +77,9 @@ def test_ntt_linearity_at_full_size(ctx, pkg, oracle):
 # with negligible probability, so the composed kernel is run here on Montgomery words written directly (no conversion:
 # the word IS the operand), all below r: the largest word, the word with the most one-bits in its low limbs, and layouts
 # that make every butterfly of a round a maximal sum, a maximal difference, or both at once.
-RM1 = np.array(zu.limbs(zu.R - 1), dtype=np.uint64)
-T232M1 = np.array(zu.limbs((zu.R >> 232 << 232) - 1), dtype=np.uint64)  # T * 2^232 - 1, T = r >> 232: low eight limbs all ones
+# The builders live in zkutil.py (test_gpu_plonk_operands.py feeds the same columns to the PLONK-layer kernels).
+from zkutil import PATTERNS, RM1, T232M1  # noqa: E402,F401
 
-
-def _const(w):
-    return lambda n: np.tile(w, (n, 1))
-
-
-def _alternating(first):
-    def make(n):
-        a = np.zeros((n, 4), np.uint64)
-        a[(0 if first else 1)::2] = RM1
-        return a
-    return make
-
-
-def _half(n):
-    a = np.zeros((n, 4), np.uint64)
-    a[: n // 2] = RM1
-    return a
-
-
-def _single(last):
-    def make(n):
-        a = np.zeros((n, 4), np.uint64)
-        a[n - 1 if last else 0] = RM1
-        return a
-    return make
-
-
-def _random_with_rm1(n):
-    a = zu.random_fr(n, seed=31337 + n)
-    a[::8] = RM1
-    return a
-
-
-PATTERNS = {"const_rm1": _const(RM1), "const_t232m1": _const(T232M1), "alt_rm1_0": _alternating(True), "alt_0_rm1": _alternating(False),
-            "half_rm1_0": _half, "single_first": _single(False), "single_last": _single(True), "zero": lambda n: np.zeros((n, 4), np.uint64),
-            "random_8th_rm1": _random_with_rm1}
 # One size per plan class and per parity of the sub-transform length s (odd s: the single-round prologue; s >= 2 ends in
 # f29_dif4_last). One step: s = k. Two steps: 11 = 6 + 5, 14 = 7 + 7, 17 = 9 + 8, 18 = 9 + 9. Three steps: 19 = 7 + 6 + 6
 # (the first size with the half twiddle table), 21 = 7 + 7 + 7. From k = 17 up three patterns per size, dealt so that

@@ -44,9 +44,12 @@ def ar(pkg):
 @pytest.mark.parametrize("n", [1, 2, 127, 128, 129, 1000, 4097])
 def test_batch_invert(ctx, ar, oracle, n):
     a = zu.random_fr(n, seed=70 + n)
-    a[::7] = 0  # zeros stay zero, and do not poison their chunk (one inversion per 128 elements)
+    # zeros stay zero, and do not poison the product of their workgroup (one inversion per 256 threads x 8 = 2048 elements;
+    # element j of thread t sits at j * 256 + t). The sizes and the run of zeros below date from the layout of one
+    # inversion per 128 consecutive elements; this kernel's own boundaries are in test_gpu_plonk_operands.py.
+    a[::7] = 0
     if n > 200:
-        a[128:256] = 0  # a whole chunk of zeros
+        a[128:256] = 0  # the first element of threads 128 ... 255
     got = ar.batch_invert(ctx, a)
     assert np.array_equal(got, oracle.batch_invert(a))
     assert not got[::7].any()
@@ -117,7 +120,9 @@ def test_eval_polynomial(ctx, ar, oracle, n):
 
 @pytest.mark.parametrize("m,n", [(1, 1000), (3, 1000), (300, 513)])
 def test_poly_axpy(ctx, ar, oracle, m, n):
-    """m = 300 crosses the kernel's 256-coefficient LDS chunk."""
+    """One term, a few, and many terms over few rows: at m = 300, n = 513 zk_lincomb cuts the terms into 8 parts of 38
+    (3 workgroups of rows each) and lincomb_sum_parts_kernel adds the parts up, so no part reaches the kernel's second
+    256-coefficient LDS chunk. Chunk crossings, the accumulate flag and extreme operands: test_gpu_plonk_operands.py."""
     polys = [rand_ints(n, 5000 + 7 * j) for j in range(m)]
     coefs = rand_ints(m, 4242 + m)
     got = ar.poly_axpy(ctx, [zu.ints_to_fr(oracle, p) for p in polys], zu.ints_to_fr(oracle, coefs))

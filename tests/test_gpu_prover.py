@@ -165,11 +165,16 @@ def test_h_program_pieces_give_the_same_bytes(ctx, pkg, plonk, oracle, monkeypat
         monkeypatch.delenv("AMDZK_H_PARTS")
 
 
-@pytest.mark.parametrize("power,flags", [(9, 0), (9, 1), (4, 0), (16, 0)])
+@pytest.mark.parametrize("power,flags", [(9, 0), (9, 1), (4, 0), (16, 0), (6, 0), (7, 0), (6, 1), (12, 0)])
 def test_high_degree_gate_bytes_equal_oracle(ctx, pkg, plonk, oracle, power, flags):
     """Constraint degree 10 (9 quotient pieces: more cosets than the templated recombination kernel's 8 — the generic
     kernel; ADVICE r2: keygen used to refuse it), the same in full-coset mode (16 cosets), degree 5 (4 cosets = the
-    whole extended domain) and degree 17 (16 pieces on 16 cosets): byte-equal to the oracle prover, and verified."""
+    whole extended domain) and degree 17 (16 pieces on 16 cosets): byte-equal to the oracle prover, and verified.
+    Degree 7 has 6 pieces on 6 cosets: coset_combine_kernel<6>, which no other test instantiates.
+    Degree 8 has 7 pieces on 7 cosets: coset_combine_kernel<7>, likewise.
+    Degree 7 in full-coset mode takes 6 pieces from all 8 cosets: coset_combine_kernel<8> with fewer outputs than cosets.
+    Degree 13 has 12 pieces on 12 of the extended domain's 16 cosets: the generic kernel on a coset count that is no
+    power of two and not the whole domain."""
     c = circuits.high_degree_circuit(plonk, 5, power=power)
     assert c.desc["cs_degree"] == power + 1
     params, pk, d_adv, inst = setup(ctx, pkg, plonk, oracle, c, flags=flags)
@@ -177,6 +182,9 @@ def test_high_degree_gate_bytes_equal_oracle(ctx, pkg, plonk, oracle, power, fla
     opk = PR.keygen(c.desc, c.fixed, c.assembly.mapping, TAU, transcript_repr=123456789)
     assert got == PR.create_proof(opk, c.instances, c.advice, seed=17)
     assert PR.verify_proof(opk, c.instances, got)
+    # The key does not expose its coset count (keygen: the number of pieces, or with KEYGEN_FULL_COSETS the whole extended
+    # domain); it does expose the pieces the recombination wrote: without the flag there are as many cosets as pieces.
+    assert pk.inspect(2).shape[0] == power
     d_adv.free(); pk.free(); params.free()
 
 

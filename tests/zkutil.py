@@ -84,6 +84,51 @@ def skewed_fr(n, seed, oracle):
     return np.ascontiguousarray(out)
 
 
+# ------------------------------------------------------------------------------ extreme operands
+# Columns of Montgomery words written directly (no conversion: the word IS the operand), all below r: the largest word,
+# the word with the most one-bits in its low limbs, and layouts that put them beside zeros (test_gpu_ntt.py has the
+# reasoning; test_gpu_plonk_operands.py runs the PLONK-layer kernels on the same columns).
+RM1 = np.array(limbs(R - 1), dtype=np.uint64)
+T232M1 = np.array(limbs((R >> 232 << 232) - 1), dtype=np.uint64)  # T * 2^232 - 1, T = r >> 232: low eight limbs all ones
+
+
+def _const(w):
+    return lambda n: np.tile(w, (n, 1))
+
+
+def _alternating(first):
+    def make(n):
+        a = np.zeros((n, 4), np.uint64)
+        a[(0 if first else 1)::2] = RM1
+        return a
+    return make
+
+
+def _half(n):
+    a = np.zeros((n, 4), np.uint64)
+    a[: n // 2] = RM1
+    return a
+
+
+def _single(last):
+    def make(n):
+        a = np.zeros((n, 4), np.uint64)
+        a[n - 1 if last else 0] = RM1
+        return a
+    return make
+
+
+def _random_with_rm1(n):
+    a = random_fr(n, seed=31337 + n)
+    a[::8] = RM1
+    return a
+
+
+PATTERNS = {"const_rm1": _const(RM1), "const_t232m1": _const(T232M1), "alt_rm1_0": _alternating(True), "alt_0_rm1": _alternating(False),
+            "half_rm1_0": _half, "single_first": _single(False), "single_last": _single(True), "zero": lambda n: np.zeros((n, 4), np.uint64),
+            "random_8th_rm1": _random_with_rm1}
+
+
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
