@@ -13,7 +13,7 @@ using namespace bn254;
 
 static thread_local std::string g_init_err;
 
-int zk_ws_reserve(amdzk_ctx* ctx, int slot, size_t bytes, void** out) {
+int zk_ws_reserve(amdzk_ctx* ctx, ZkWs slot, size_t bytes, void** out) {
   amdzk_ctx::Ws& w = ctx->ws[slot];
   if (w.cap < bytes) {
     if (w.p) {
@@ -28,7 +28,7 @@ int zk_ws_reserve(amdzk_ctx* ctx, int slot, size_t bytes, void** out) {
       want = bytes;
       e = hipMalloc(&w.p, want);
     }
-    if (e != hipSuccess) ZK_FAIL(ctx, AMDZK_E_NOMEM, "workspace %d: hipMalloc(%zu) failed: %s", slot, bytes, hipGetErrorString(e));
+    if (e != hipSuccess) ZK_FAIL(ctx, AMDZK_E_NOMEM, "workspace %d: hipMalloc(%zu) failed: %s", (int)slot, bytes, hipGetErrorString(e));
     w.cap = want;
   }
   *out = w.p;
@@ -148,6 +148,15 @@ int zk_sync_all(amdzk_ctx* ctx) {
   for (amdzk_ctx* l : root->lanes)
     if (l) ZK_HIP(ctx, zk_host_wait(l, l->stream));
   return AMDZK_OK;
+}
+
+int zk_quiet_if_refused(amdzk_ctx* ctx, int r, bool lanes) {
+  if (r == AMDZK_OK) return r;
+  const std::string keep = ctx->err;
+  if (lanes) (void)zk_sync_all(ctx);
+  else (void)zk_host_wait(ctx, ctx->stream);
+  ctx->err = keep;
+  return r;
 }
 
 static void ctx_release(amdzk_ctx* ctx) {
@@ -466,17 +475,11 @@ int amdzk_msm_g1_cols_dev(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const
   for (size_t c = 0; c < ncols; c++)
     if (!d_cols[c]) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm_cols: column %zu is null", c);
   const Fr** d_tab = nullptr;
-  ZK_TRY(zk_ws_reserve(ctx, 2, ncols * sizeof(Fr*), (void**)&d_tab));
+  ZK_TRY(zk_ws_reserve(ctx, ZK_WS_STAGING, ncols * sizeof(Fr*), (void**)&d_tab));
   // the caller's array is read before the call returns: every path below waits for the stream
   ZK_HIP(ctx, hipMemcpyAsync(d_tab, d_cols, ncols * sizeof(Fr*), hipMemcpyHostToDevice, ctx->stream));
   G1X* d_res = nullptr;
-  const int r = zk_msm_dev_xyzz_cols(ctx, srs, basis, d_tab, ncols, len, max_scratch_bytes, &d_res);
-  if (r != AMDZK_OK) {  // refused: the copy above may still be reading the caller's array
-    const std::string keep = ctx->err;
-    (void)zk_host_wait(ctx, ctx->stream);
-    ctx->err = keep;
-    return r;
-  }
+  ZK_TRY(zk_quiet_if_refused(ctx, zk_msm_dev_xyzz_cols(ctx, srs, basis, d_tab, ncols, len, max_scratch_bytes, &d_res)));
   return zk_msm_finish(ctx, d_res, ncols, out_jacobian);
 }
 
@@ -485,14 +488,13 @@ int amdzk_msm_g1_batch(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const ui
   ZK_ENTER(ctx);
   if (!ctx) return AMDZK_E_INVALID;
   if (!scalars || !out_jacobian || ncols == 0) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm_batch: null pointer or ncols == 0");
+  for (size_t c = 0; c < ncols && len; c++)  // every column before the first copy: a refusal here leaves nothing in flight
+    if (!scalars[c]) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm_batch: column %zu is null", c);
   Fr* d = nullptr;
   size_t stride = len ? len : 1;
-  ZK_TRY(zk_ws_reserve(ctx, 2, ncols * stride * sizeof(Fr), (void**)&d));
-  for (size_t c = 0; c < ncols; c++) {
-    if (!scalars[c] && len) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm_batch: column %zu is null", c);
-    ZK_HIP(ctx, hipMemcpyAsync(d + c * stride, scalars[c], len * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
-  }
-  return amdzk_msm_g1_dev(ctx, srs, basis, d, ncols, len, stride, out_jacobian);
+  ZK_TRY(zk_ws_reserve(ctx, ZK_WS_STAGING, ncols * stride * sizeof(Fr), (void**)&d));
+  for (size_t c = 0; c < ncols; c++) ZK_HIP(ctx, hipMemcpyAsync(d + c * stride, scalars[c], len * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+  return zk_quiet_if_refused(ctx, amdzk_msm_g1_dev(ctx, srs, basis, d, ncols, len, stride, out_jacobian));
 }
 
 int amdzk_msm_g1(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const uint64_t* scalars, size_t len,
@@ -544,17 +546,16 @@ int amdzk_msm_g1_bases_batch(amdzk_ctx* ctx, const uint64_t* const* scalars, siz
     const int rc = zk_msm_bases_plan_host(ncols, len, nullptr, nullptr, nullptr, why);
     if (rc != AMDZK_OK) ZK_FAIL(ctx, rc, "%s", why);
   }
+  for (size_t c = 0; c < ncols && len; c++)  // every column before the first copy: a refusal here leaves nothing in flight
+    if (!scalars[c]) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm_bases_batch: column %zu is null", c);
   char* d = nullptr;  // scalars[ncols][len] | bases[len]
   const size_t stride = len ? len : 1;
-  ZK_TRY(zk_ws_reserve(ctx, 2, ncols * stride * sizeof(Fr) + stride * sizeof(G1Affine), (void**)&d));
+  ZK_TRY(zk_ws_reserve(ctx, ZK_WS_STAGING, ncols * stride * sizeof(Fr) + stride * sizeof(G1Affine), (void**)&d));
   Fr* d_scal = (Fr*)d;
   G1Affine* d_bases = (G1Affine*)(d + ncols * stride * sizeof(Fr));
-  for (size_t c = 0; c < ncols; c++) {
-    if (!scalars[c] && len) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm_bases_batch: column %zu is null", c);
-    if (len) ZK_HIP(ctx, hipMemcpyAsync(d_scal + c * stride, scalars[c], len * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
-  }
+  for (size_t c = 0; c < ncols && len; c++) ZK_HIP(ctx, hipMemcpyAsync(d_scal + c * stride, scalars[c], len * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
   if (len) ZK_HIP(ctx, hipMemcpyAsync(d_bases, bases, len * sizeof(G1Affine), hipMemcpyHostToDevice, ctx->stream));
-  return amdzk_msm_g1_bases_dev(ctx, d_scal, ncols, len, stride, d_bases, out_jacobian);
+  return zk_quiet_if_refused(ctx, amdzk_msm_g1_bases_dev(ctx, d_scal, ncols, len, stride, d_bases, out_jacobian));
 }
 
 int amdzk_msm_g1_bases(amdzk_ctx* ctx, const uint64_t* scalars, const uint64_t* bases, size_t len, uint64_t out_jacobian[12]) {
@@ -578,9 +579,9 @@ int amdzk_ntt_fr(amdzk_ctx* ctx, uint64_t* a, uint32_t log_n, const uint64_t ome
   if (log_n > 27) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "ntt: log_n %u > 27", log_n);
   size_t bytes = ((size_t)1 << log_n) * sizeof(Fr);
   Fr* d = nullptr;
-  ZK_TRY(zk_ws_reserve(ctx, 2, bytes, (void**)&d));
+  ZK_TRY(zk_ws_reserve(ctx, ZK_WS_STAGING, bytes, (void**)&d));
   ZK_HIP(ctx, hipMemcpyAsync(d, a, bytes, hipMemcpyHostToDevice, ctx->stream));
-  ZK_TRY(zk_ntt_dev(ctx, d, log_n, omega, flags, 1, (size_t)1 << log_n));
+  ZK_TRY(zk_quiet_if_refused(ctx, zk_ntt_dev(ctx, d, log_n, omega, flags, 1, (size_t)1 << log_n)));
   ZK_HIP(ctx, hipMemcpyAsync(a, d, bytes, hipMemcpyDeviceToHost, ctx->stream));
   ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
   return AMDZK_OK;
@@ -592,13 +593,13 @@ int amdzk_ctx_check_affinity(amdzk_ctx* ctx) {
   int dev = -1;
   ZK_HIP(ctx, hipStreamGetDevice(ctx->stream, &dev));
   if (dev != ctx->device) ZK_FAIL(ctx, AMDZK_E_INVALID, "affinity: stream is on device %d, ctx on %d", dev, ctx->device);
-  for (int i = 0; i < 8; i++) ZK_TRY(zk_ptr_on_device(ctx, ctx->ws[i].p, "workspace"));
+  for (int i = 0; i < ZK_WS_COUNT; i++) ZK_TRY(zk_ptr_on_device(ctx, ctx->ws[i].p, "workspace"));
   for (auto& kv : ctx->twiddles) ZK_TRY(zk_ptr_on_device(ctx, kv.second, "twiddle table"));
   for (amdzk_ctx* l : ctx->lanes)
     if (l) {
       ZK_HIP(ctx, hipStreamGetDevice(l->stream, &dev));
       if (dev != ctx->device) ZK_FAIL(ctx, AMDZK_E_INVALID, "affinity: a lane's stream is on device %d, ctx on %d", dev, ctx->device);
-      for (int i = 0; i < 8; i++) ZK_TRY(zk_ptr_on_device(ctx, l->ws[i].p, "lane workspace"));
+      for (int i = 0; i < ZK_WS_COUNT; i++) ZK_TRY(zk_ptr_on_device(ctx, l->ws[i].p, "lane workspace"));
       for (auto& kv : l->twiddles) ZK_TRY(zk_ptr_on_device(ctx, kv.second, "lane twiddle table"));
     }
   return AMDZK_OK;
@@ -616,14 +617,13 @@ int amdzk_ntt_fr_batch(amdzk_ctx* ctx, uint64_t* const* cols, size_t ncols, uint
   if (!ctx) return AMDZK_E_INVALID;
   if (!cols || !omega || ncols == 0) ZK_FAIL(ctx, AMDZK_E_INVALID, "ntt_batch: null pointer or ncols == 0");
   if (log_n > 27) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "ntt: log_n %u > 27", log_n);
+  for (size_t c = 0; c < ncols; c++)  // every column before the first copy: a refusal here leaves nothing in flight
+    if (!cols[c]) ZK_FAIL(ctx, AMDZK_E_INVALID, "ntt_batch: column %zu is null", c);
   const size_t n = (size_t)1 << log_n;
   Fr* d = nullptr;
-  ZK_TRY(zk_ws_reserve(ctx, 2, ncols * n * sizeof(Fr), (void**)&d));
-  for (size_t c = 0; c < ncols; c++) {
-    if (!cols[c]) ZK_FAIL(ctx, AMDZK_E_INVALID, "ntt_batch: column %zu is null", c);
-    ZK_HIP(ctx, hipMemcpyAsync(d + c * n, cols[c], n * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
-  }
-  ZK_TRY(zk_ntt_dev(ctx, d, log_n, omega, flags, ncols, n));
+  ZK_TRY(zk_ws_reserve(ctx, ZK_WS_STAGING, ncols * n * sizeof(Fr), (void**)&d));
+  for (size_t c = 0; c < ncols; c++) ZK_HIP(ctx, hipMemcpyAsync(d + c * n, cols[c], n * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+  ZK_TRY(zk_quiet_if_refused(ctx, zk_ntt_dev(ctx, d, log_n, omega, flags, ncols, n)));
   for (size_t c = 0; c < ncols; c++) ZK_HIP(ctx, hipMemcpyAsync(cols[c], d + c * n, n * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
   ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
   return AMDZK_OK;

@@ -432,11 +432,6 @@ extern "C" int amdzk_check_witness(amdzk_ctx* ctx, amdzk_pk* pk, const uint64_t*
                         size_t advice_stride, const amdzk_check_opts* opts, amdzk_check_failure* out, size_t cap, size_t* n_failures) {
   ZK_ENTER(ctx);
   if (!ctx) return AMDZK_E_INVALID;
-  const int r = check_witness_run(ctx, pk, instances, instance_lens, d_advice, advice_stride, opts, out, cap, n_failures);
-  if (r != AMDZK_OK) {  // whatever was enqueued (copies from the caller's memory among it) is finished before the call returns
-    const std::string keep = ctx->err;
-    (void)zk_host_wait(ctx, ctx->stream);
-    ctx->err = keep;
-  }
-  return r;
+  // whatever was enqueued (copies from the caller's memory among it) is finished before a refused call returns
+  return zk_quiet_if_refused(ctx, check_witness_run(ctx, pk, instances, instance_lens, d_advice, advice_stride, opts, out, cap, n_failures));
 }

@@ -808,8 +808,6 @@ int zk_msm_fill_table(amdzk_ctx* ctx, const G1Affine* base, G1Affine* table, siz
   return AMDZK_OK;
 }
 
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 // Geometry of one batch (msm_group): counting sort, level-1 accumulation, folds, bucket reduction.
 struct MsmGeom {
   uint32_t c, W, nb, T1, TL, chunk, nblk;
@@ -839,7 +837,7 @@ static MsmGeom msm_geometry_cw(uint32_t c, uint32_t W, bool per_window, size_t n
   g.c = c;
   g.W = W;
   g.nb = 1u << (g.c - 1);
-  g.ecap = align_up(len * dps ? len * dps : 1, 4);
+  g.ecap = ws_round_up(len * dps ? len * dps : 1, 4);
   // task sizes: level 1 adds T1 table points per thread, levels 2.. fold TL partial sums per thread;
   // all levels use the balanced segmented kernel. Every extra folding level costs a latency-bound launch, so two
   // folding levels; T1 = 12 for the large batches (profiles/r02j_msm_task_size.txt: T1 = 8 / 12 / 16 / 32 / 48 take
@@ -852,7 +850,7 @@ static MsmGeom msm_geometry_cw(uint32_t c, uint32_t W, bool per_window, size_t n
   if (e_total > (size_t)8 * 262144) g.T1 = 12;
   // one long column (k >= 19): tens of millions of entries keep the chip full whatever the task size, and every partial
   // sum a task leaves behind is one more addition in the folds (profiles/r04a_*: 2^22 points, T1 = 12 / 24 / 32 / 48 / 64: 7.48 / 7.44 / 7.36 / 7.32 / 7.28 ms)
-  const size_t col_digits = align_up(len * W ? len * W : 1, 4);  // of one column over all its windows (= ecap with a window table)
+  const size_t col_digits = ws_round_up(len * W ? len * W : 1, 4);  // of one column over all its windows (= ecap with a window table)
   if (col_digits >= ((size_t)1 << 23)) g.T1 = col_digits >= ((size_t)1 << 25) ? 64 : 32;  // 2^19 points: 1.53 ms with 32, 1.69 with 64; 2^22: 7.33 / 7.14
   if (const char* e = getenv("AMDZK_MSM_T1")) g.T1 = (uint32_t)atoi(e) > 0 ? (uint32_t)atoi(e) : g.T1;
   g.TL = 6;  // 4 / 6 / 8 / 12 / 16 prove at the same rate (76.7-78.0 proofs/s); 6 has the shortest proof (profiles/r02j_msm_task_size.txt)
@@ -883,19 +881,18 @@ static MsmGeom msm_geometry_cw(uint32_t c, uint32_t W, bool per_window, size_t n
   g.chunk = g.big_digits ? 4096 : 2048;
   while ((len + g.chunk - 1) / g.chunk > maxblk) g.chunk <<= 1;
   g.nblk = len ? (uint32_t)((len + g.chunk - 1) / g.chunk) : 1;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes, 256); return r; };
-  g.o_bh = take(ncols * (size_t)g.nblk * g.nb * 4);
-  g.o_cnt = take(ncols * g.nb * 4);
-  for (int l = 0; l <= MSM_NLEV; l++) g.o_off[l] = take(ncols * (g.nb + 1) * 4);
-  g.o_ent = take(ncols * g.ecap * 4);
+  WsLayout w;
+  g.o_bh = w.take(ncols * (size_t)g.nblk * g.nb * 4);
+  g.o_cnt = w.take(ncols * g.nb * 4);
+  for (int l = 0; l <= MSM_NLEV; l++) g.o_off[l] = w.take(ncols * (g.nb + 1) * 4);
+  g.o_ent = w.take(ncols * g.ecap * 4);
   g.o_list[0] = 0;
-  for (int l = 1; l <= MSM_NLEV; l++) g.o_list[l] = take(ncols * g.cap[l] * sizeof(G1X29));
-  g.o_dense = take(ncols * g.nb * sizeof(G1X29));
+  for (int l = 1; l <= MSM_NLEV; l++) g.o_list[l] = w.take(ncols * g.cap[l] * sizeof(G1X29));
+  g.o_dense = w.take(ncols * g.nb * sizeof(G1X29));
   g.G = g.nb >> 6;
-  g.o_rows = take(ncols * g.G * sizeof(G1X29));
-  g.o_cols = take(ncols * ((g.G + 63) / 64) * 64 * sizeof(G1X29));
-  g.bytes = o;
+  g.o_rows = w.take(ncols * g.G * sizeof(G1X29));
+  g.o_cols = w.take(ncols * ((g.G + 63) / 64) * 64 * sizeof(G1X29));
+  g.bytes = w.bytes();
   return g;
 }
 static MsmGeom msm_geometry(const amdzk_srs* srs, size_t ncols, size_t len, bool latency_mode) {
@@ -1028,9 +1025,11 @@ int zk_msm_dev_xyzz(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const Fr* d
   if (ncols == 0 || ncols > 65535) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm: ncols %zu out of range", ncols);
   ZK_TRY(msm_check_ids(ctx, srs));
   const MsmGeom g = msm_geometry(srs, ncols, len, ctx->msm_latency_mode);
-  const size_t o_out = align_up(g.bytes, 256);
+  WsLayout w;
+  w.take(g.bytes);
+  const size_t o_out = w.take(ncols * sizeof(G1X));
   char* ws = nullptr;
-  ZK_TRY(zk_ws_reserve(ctx, 1, o_out + align_up(ncols * sizeof(G1X), 256), (void**)&ws));
+  ZK_TRY(zk_ws_reserve(ctx, ZK_WS_MSM, w.bytes(), (void**)&ws));
   G1X* outp = (G1X*)(ws + o_out);
   ZK_TRY(msm_group(ctx, srs->table[basis], (uint32_t)srs->n, false, g, ws, MsmScalars{d_scalars, col_stride, nullptr}, ncols, len, outp));
   *d_out = outp;
@@ -1064,9 +1063,11 @@ int zk_msm_dev_xyzz_cols(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const 
     bytes = std::max(msm_geometry(srs, per, len, ctx->msm_latency_mode).bytes, msm_geometry(srs, last, len, ctx->msm_latency_mode).bytes);
     if (per == 1 || bytes <= cap) break;
   }
-  const size_t o_scratch = align_up(ncols * sizeof(G1X), 256);
+  WsLayout w;  // the results of all runs | one run's scratch
+  w.take(ncols * sizeof(G1X));
+  const size_t o_scratch = w.take(bytes);
   char* ws = nullptr;
-  ZK_TRY(zk_ws_reserve(ctx, 1, o_scratch + align_up(bytes, 256), (void**)&ws));
+  ZK_TRY(zk_ws_reserve(ctx, ZK_WS_MSM, w.bytes(), (void**)&ws));
   G1X* outp = (G1X*)ws;
   for (size_t first = 0; first < ncols; first += per) {
     const size_t cnt = std::min(per, ncols - first);
@@ -1135,10 +1136,10 @@ static int zk_msm_bases_plan(size_t ncols, size_t len, bool latency_mode, MsmBas
   }
   p->vcols = ncols * W;
   p->g = msm_geometry_cw(c, W, true, p->vcols, len, latency_mode);
-  p->o_win = align_up(p->g.bytes, 256);
-  p->o_out = p->o_win + align_up(p->vcols * sizeof(G1X), 256);
-  p->o_bases = p->o_out + align_up(ncols * sizeof(G1X), 256);
-  p->bytes = p->o_bases + align_up((len ? len : 1) * sizeof(G1Affine), 256);
+  WsLayout w;
+  w.take(p->g.bytes);
+  p->o_win = w.take(p->vcols * sizeof(G1X)), p->o_out = w.take(ncols * sizeof(G1X)), p->o_bases = w.take((len ? len : 1) * sizeof(G1Affine));
+  p->bytes = w.bytes();
   return AMDZK_OK;
 }
 
@@ -1164,7 +1165,7 @@ int zk_msm_bases_dev_xyzz(amdzk_ctx* ctx, const Fr* d_scalars, size_t ncols, siz
   if (!d_scalars || !d_bases || len == 0) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm_bases: null pointer or len == 0");
   if (ncols > 1 && col_stride < len) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm_bases: col_stride %zu < len %zu", col_stride, len);
   char* ws = nullptr;
-  ZK_TRY(zk_ws_reserve(ctx, 1, p.bytes, (void**)&ws));
+  ZK_TRY(zk_ws_reserve(ctx, ZK_WS_MSM, p.bytes, (void**)&ws));
   G1X *win = (G1X*)(ws + p.o_win), *outp = (G1X*)(ws + p.o_out);
   G1Affine* bases = (G1Affine*)(ws + p.o_bases);
   ZK_HIP(ctx, hipMemcpyAsync(bases, d_bases, len * sizeof(G1Affine), hipMemcpyDeviceToDevice, ctx->stream));

@@ -5,7 +5,7 @@
 // shplonk_final}) and the verifier; the kernels are the proof path's too — zk_poly_eval, zk_lincomb, zk_kate_div_from, the
 // MSM over AMDZK_BASIS_G. The driver is this file's own: points are arbitrary field elements
 // instead of rotations of x, polynomials are the caller's buffers instead of a key's workspace, scratch is the ctx's
-// (workspace slot 6, one reservation per call whose size the plan reports) instead of a key's, and nothing is capped at 16
+// (ZK_WS_TABLES, one reservation per call whose size the plan reports) instead of a key's, and nothing is capped at 16
 // sets or points or at a key's pointer table: launches whose grid.y would pass 65535 are cut into runs by the host.
 // Everything runs on the caller's stream. No kernel lives here.
 #include <stdlib.h>
@@ -26,7 +26,14 @@ using namespace bn254;
 namespace {
 
 constexpr size_t MO_MAX_GRID_Y = 65535;  // polynomials per division launch, columns per commitment batch
-constexpr int MO_WS_SLOT = 6;            // the function-by-function calls' slot (plonk_kernels.hip upload_ptrs_and_frs)
+
+// a call's one reservation; a size that cannot be had is the call's own refusal
+int mo_reserve(amdzk_ctx* ctx, const char* who, size_t bytes, char** ws) {
+  const int r = zk_ws_reserve(ctx, ZK_WS_TABLES, bytes, (void**)ws);
+  if (r != AMDZK_E_NOMEM) return r;
+  (void)hipGetLastError();  // the failed allocation's sticky status
+  ZK_FAIL(ctx, AMDZK_E_NOMEM, "%s: %zu bytes of scratch cannot be allocated", who, bytes);
+}
 
 Fr canon_of(const uint64_t* mont) {
   Fr a;
@@ -150,7 +157,7 @@ int mo_build(const uint64_t* points, size_t n_points, const amdzk_open_query* qu
   s.poly_count = polys;
   s.ptr_count = ptrs;
   s.fr_count = frs;
-  s.ptr_bytes = (ptrs * sizeof(void*) + 255) / 256 * 256;
+  s.ptr_bytes = ws_round_up(ptrs * sizeof(void*), 256);
   ok = ok && add_ok(poly_bytes, s.ptr_bytes, &s.scratch_bytes) && add_ok(s.scratch_bytes, fr_bytes, &s.scratch_bytes);
   if (!ok) return snprintf(why, 200, "the scratch size of this shape does not fit 64 bits"), AMDZK_E_NOMEM;
   return AMDZK_OK;
@@ -397,14 +404,7 @@ int multiopen_body(amdzk_ctx* ctx, const amdzk_srs* srs, const void* const* d_po
   if (out_points && out_cap < s.n_out) ZK_FAIL(ctx, AMDZK_E_INVALID, "multiopen: room for %zu points, %u will be written", out_cap, s.n_out);
   if (!zk_srs_has_basis(srs, AMDZK_BASIS_G)) ZK_FAIL(ctx, AMDZK_E_INVALID, "multiopen: the parameters have no basis g (AMDZK_BASIS_G)");
   char* ws = nullptr;
-  {
-    const int r = zk_ws_reserve(ctx, MO_WS_SLOT, s.scratch_bytes, (void**)&ws);
-    if (r == AMDZK_E_NOMEM) {
-      (void)hipGetLastError();  // the failed allocation's sticky status
-      ZK_FAIL(ctx, AMDZK_E_NOMEM, "multiopen: %zu bytes of scratch cannot be allocated", s.scratch_bytes);
-    }
-    ZK_TRY(r);
-  }
+  ZK_TRY(mo_reserve(ctx, "multiopen", s.scratch_bytes, &ws));
   call.reset(new Call(ctx, srs, d_polys, points, s, *t));
   Call& c = *call;
   c.d_poly = (Fr*)ws;
@@ -526,16 +526,11 @@ int mo_verify_body(amdzk_ctx* ctx, const uint64_t* g, const uint64_t* commitment
     Lc[h2] = at.z0;  // L = z_0(u) h2
   }
   // ---- the device: bases | status word | the two columns
-  const size_t o_status = nb * sizeof(G1Affine), o_sc = o_status + 256, total = o_sc + 2 * nb * sizeof(Fr);
+  WsLayout w;
+  w.take(nb * sizeof(G1Affine), 1);
+  const size_t o_status = w.take(256, 1), o_sc = w.take(2 * nb * sizeof(Fr), 1), total = w.bytes();
   char* ws = nullptr;
-  {
-    const int r = zk_ws_reserve(ctx, MO_WS_SLOT, total, (void**)&ws);
-    if (r == AMDZK_E_NOMEM) {
-      (void)hipGetLastError();
-      ZK_FAIL(ctx, AMDZK_E_NOMEM, "multiopen_verify: %zu bytes of scratch cannot be allocated", total);
-    }
-    ZK_TRY(r);
-  }
+  ZK_TRY(mo_reserve(ctx, "multiopen_verify", total, &ws));
   ZK_HIP(ctx, hipMemcpyAsync(ws, bases.data(), nb * sizeof(G1Affine), hipMemcpyHostToDevice, ctx->stream));
   ZK_HIP(ctx, hipMemcpyAsync(ws + o_sc, sc.data(), 2 * nb * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
   ZK_TRY(zk_points_check_dev(ctx, (G1Affine*)ws, nb, n_coms, (uint32_t*)(ws + o_status)));
@@ -564,13 +559,7 @@ int mo_verify(amdzk_ctx* ctx, const uint64_t* g, const uint64_t* commitments, si
   std::vector<G1Affine> bases;
   std::vector<Fr> sc;
   uint32_t status = 0;
-  const int r = mo_verify_body(ctx, g, commitments, n_coms, points, n_points, queries, evals, n_queries, opts, pair, bases, sc, status);
-  if (r != AMDZK_OK) {
-    const std::string keep = ctx->err;
-    (void)zk_host_wait(ctx, ctx->stream);
-    ctx->err = keep;
-  }
-  return r;
+  return zk_quiet_if_refused(ctx, mo_verify_body(ctx, g, commitments, n_coms, points, n_points, queries, evals, n_queries, opts, pair, bases, sc, status));
 }
 
 }  // namespace
@@ -626,13 +615,8 @@ int amdzk_multiopen_dev(amdzk_ctx* ctx, const amdzk_srs* srs, const void* const*
   if (!ctx) return AMDZK_E_INVALID;
   MoSets s;
   std::unique_ptr<Call> call;  // owns the host images of the tables: it outlives every copy enqueued from them
-  const int r = multiopen_body(ctx, srs, d_polys, n_polys, points, n_points, queries, n_queries, opts, out_points, out_cap, n_out, s, call);
-  if (r != AMDZK_OK) {  // whatever the call enqueued has run before the caller sees the refusal
-    const std::string keep = ctx->err;
-    (void)zk_host_wait(ctx, ctx->stream);
-    ctx->err = keep;
-  }
-  return r;
+  // whatever the call enqueued has run before the caller sees a refusal
+  return zk_quiet_if_refused(ctx, multiopen_body(ctx, srs, d_polys, n_polys, points, n_points, queries, n_queries, opts, out_points, out_cap, n_out, s, call));
 }
 
 }  // extern "C"

@@ -394,7 +394,7 @@ int zk_ntt_ex(amdzk_ctx* ctx, const Fr* d_in, size_t in_stride, Fr* d_out, size_
   if (nz > 1 && (in_coset || out_mul)) ZK_FAIL(ctx, AMDZK_E_INVALID, "ntt: the z dimension goes with multiplier tables only");
   if (nz > 65535) ZK_FAIL(ctx, AMDZK_E_INVALID, "ntt: nz too large");
   Fr* ws = nullptr;
-  if (plan.npass > 1) ZK_TRY(zk_ws_reserve(ctx, 0, ncols * nz * n * sizeof(Fr), (void**)&ws));
+  if (plan.npass > 1) ZK_TRY(zk_ws_reserve(ctx, ZK_WS_NTT, ncols * nz * n * sizeof(Fr), (void**)&ws));
 
   NttPassArgs a;
   memset(&a, 0, sizeof(a));

@@ -25,31 +25,7 @@ struct amdzk_g2 {
 
 namespace {
 
-constexpr int PAIRING_WS_SLOT = 3;  // verify's slot: amdzk_verify_proofs_decide pairs after the last read of its reservation
 constexpr uint32_t PAIRING_THREADS = 64;
-constexpr size_t PAIRING_CHUNK_LANES = 16384;  // Miller lanes per launch: bounds the register slabs (about 2 KB a Miller lane, 5 KB a check)
-
-size_t pad256(size_t v) { return (v + 255) / 256 * 256; }
-
-struct Programs {
-  pairing::Prog miller, mul, fin;
-  size_t o_lines, o_miller, o_mul, o_fin, bytes;
-  uint32_t final_regs;
-};
-const Programs& programs() {
-  static const Programs P = [] {
-    Programs q;
-    q.miller = pairing::miller_program(), q.mul = pairing::mul_program(), q.fin = pairing::final_exp_program();
-    q.o_lines = pad256(pairing::K_COUNT * sizeof(Fq2x));
-    q.o_miller = q.o_lines + pad256(4 * (size_t)PAIRING_NUM_LINES * sizeof(Fq));
-    q.o_mul = q.o_miller + pad256(q.miller.w.size() * 4);
-    q.o_fin = q.o_mul + pad256(q.mul.w.size() * 4);
-    q.bytes = q.o_fin + pad256(q.fin.w.size() * 4);
-    q.final_regs = (uint32_t)(q.mul.regs > q.fin.regs ? q.mul.regs : q.fin.regs);
-    return q;
-  }();
-  return P;
-}
 
 struct MillerArgs {
   const uint32_t* prog;
@@ -126,36 +102,34 @@ int zk_pairing_products(amdzk_ctx* ctx, const char* who, const amdzk_g2* const* 
     if (!qs[j] || !qs[j]->d) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: null argument (prepared point %zu)", who, j);
     if (qs[j]->device != ctx->device) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: prepared point %zu lives on device %d, the ctx on %d", who, j, qs[j]->device, ctx->device);
   }
-  const Programs& P = programs();
-  const size_t total = n * m, chunk = PAIRING_CHUNK_LANES / m < n ? PAIRING_CHUNK_LANES / m : n;  // checks per launch (m <= 16: at least 1024)
-  const size_t o_g1 = pad256(AMDZK_PAIRING_MAX_M * sizeof(Fq*)), o_ms = o_g1 + pad256(total * sizeof(G1Affine));
-  const size_t o_fs = o_ms + pad256(chunk * m * P.miller.regs * sizeof(Fq2x)), o_gt = o_fs + pad256(chunk * P.final_regs * sizeof(Fq2x));
-  const size_t o_one = o_gt + n * 12 * sizeof(Fq), bytes = o_one + pad256(n);
-  const size_t up = o_ms, down = n * 12 * sizeof(Fq) + n;
+  const pairing::Programs& P = pairing::programs();
+  const size_t total = n * m, chunk = pairing::pairing_chunk(n, m);  // checks per launch
+  const pairing::CallLayout L = pairing::call_layout(n, m, chunk, P.miller.regs, P.final_regs);
+  const size_t up = L.miller_slab, down = n * 12 * sizeof(Fq) + n;
   char* ws = nullptr;
-  ZK_TRY(zk_ws_reserve(ctx, PAIRING_WS_SLOT, bytes, (void**)&ws));
+  ZK_TRY(zk_ws_reserve(ctx, ZK_WS_STARTUP, L.bytes, (void**)&ws));
   char* pin = nullptr;
   ZK_TRY(zk_pinned_reserve(ctx, up > down ? up : down, (void**)&pin));
-  memset(pin, 0, o_g1);
-  for (size_t j = 0; j < m; j++) ((const Fq**)pin)[j] = (const Fq*)(qs[j]->d + P.o_lines);
-  memcpy(pin + o_g1, h_g1, total * sizeof(G1Affine));
+  memset(pin, 0, L.g1);
+  for (size_t j = 0; j < m; j++) ((const Fq**)pin)[j] = (const Fq*)(qs[j]->d + P.at.lines);
+  memcpy(pin + L.g1, h_g1, total * sizeof(G1Affine));
   ZK_HIP(ctx, hipMemcpyAsync(ws, pin, up, hipMemcpyHostToDevice, ctx->stream));
   const char* q0 = qs[0]->d;  // constants and programs: any handle's copy
   for (size_t c0 = 0; c0 < n; c0 += chunk) {
     const size_t nc = c0 + chunk < n ? chunk : n - c0, lanes = nc * m;
     MillerArgs ma;
-    ma.prog = (const uint32_t*)(q0 + P.o_miller), ma.prog_len = (uint32_t)P.miller.w.size(), ma.regs = (uint32_t)P.miller.regs, ma.m = (uint32_t)m;
+    ma.prog = (const uint32_t*)(q0 + P.at.miller), ma.prog_len = (uint32_t)P.miller.w.size(), ma.regs = (uint32_t)P.miller.regs, ma.m = (uint32_t)m;
     ma.active = pairing_active_lanes(ctx, lanes), ma.K = (const Fq2x*)q0, ma.lines = (const Fq* const*)ws;
-    ma.g1 = (const G1Affine*)(ws + o_g1) + c0 * m, ma.slab = (Fq2x*)(ws + o_ms), ma.total = lanes;
+    ma.g1 = (const G1Affine*)(ws + L.g1) + c0 * m, ma.slab = (Fq2x*)(ws + L.miller_slab), ma.total = lanes;
     ZK_LAUNCH(ctx, "pairing_miller", pairing_miller_kernel, dim3((unsigned)((lanes + ma.active - 1) / ma.active)), dim3(PAIRING_THREADS), 0, ma);
     FinalArgs fa;
-    fa.mul_prog = (const uint32_t*)(q0 + P.o_mul), fa.fin_prog = (const uint32_t*)(q0 + P.o_fin), fa.mul_len = (uint32_t)P.mul.w.size();
+    fa.mul_prog = (const uint32_t*)(q0 + P.at.mul), fa.fin_prog = (const uint32_t*)(q0 + P.at.fin), fa.mul_len = (uint32_t)P.mul.w.size();
     fa.fin_len = (uint32_t)P.fin.w.size(), fa.regs = P.final_regs, fa.miller_regs = (uint32_t)P.miller.regs, fa.m = (uint32_t)m;
-    fa.active = pairing_active_lanes(ctx, nc), fa.K = (const Fq2x*)q0, fa.miller_slab = (const Fq2x*)(ws + o_ms), fa.slab = (Fq2x*)(ws + o_fs);
-    fa.n = nc, fa.gt_out = (Fq*)(ws + o_gt) + c0 * 12, fa.is_one = (uint8_t*)(ws + o_one) + c0;
+    fa.active = pairing_active_lanes(ctx, nc), fa.K = (const Fq2x*)q0, fa.miller_slab = (const Fq2x*)(ws + L.miller_slab), fa.slab = (Fq2x*)(ws + L.final_slab);
+    fa.n = nc, fa.gt_out = (Fq*)(ws + L.gt) + c0 * 12, fa.is_one = (uint8_t*)(ws + L.is_one) + c0;
     ZK_LAUNCH(ctx, "pairing_final", pairing_final_kernel, dim3((unsigned)((nc + fa.active - 1) / fa.active)), dim3(PAIRING_THREADS), 0, fa);
   }
-  ZK_HIP(ctx, hipMemcpyAsync(pin, ws + o_gt, down, hipMemcpyDeviceToHost, ctx->stream));
+  ZK_HIP(ctx, hipMemcpyAsync(pin, ws + L.gt, down, hipMemcpyDeviceToHost, ctx->stream));
   ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
   if (gt_out) memcpy(gt_out, pin, n * 12 * sizeof(Fq));
   if (is_one) memcpy(is_one, pin + n * 12 * sizeof(Fq), n);
@@ -172,17 +146,17 @@ extern "C" int amdzk_g2_prepare(amdzk_ctx* ctx, const uint64_t q[16], amdzk_g2**
     ZK_FAIL(ctx, AMDZK_E_INVALID, "g2_prepare: a coordinate is not below the modulus");
   if (p.is_inf()) ZK_FAIL(ctx, AMDZK_E_INVALID, "g2_prepare: the identity has no prepared form");
   if (!pairing::g2_on_twist(p)) ZK_FAIL(ctx, AMDZK_E_INVALID, "g2_prepare: the point is not on the twist");
-  const Programs& P = programs();
-  std::vector<char> host(P.bytes, 0);
+  const pairing::Programs& P = pairing::programs();
+  std::vector<char> host(P.at.bytes, 0);
   pairing::device_consts((Fq2x*)host.data());
-  pairing::g2_prepare(p, (Fq*)(host.data() + P.o_lines));
-  memcpy(host.data() + P.o_miller, P.miller.w.data(), P.miller.w.size() * 4);
-  memcpy(host.data() + P.o_mul, P.mul.w.data(), P.mul.w.size() * 4);
-  memcpy(host.data() + P.o_fin, P.fin.w.data(), P.fin.w.size() * 4);
+  pairing::g2_prepare(p, (Fq*)(host.data() + P.at.lines));
+  memcpy(host.data() + P.at.miller, P.miller.w.data(), P.miller.w.size() * 4);
+  memcpy(host.data() + P.at.mul, P.mul.w.data(), P.mul.w.size() * 4);
+  memcpy(host.data() + P.at.fin, P.fin.w.data(), P.fin.w.size() * 4);
   amdzk_g2* g = new amdzk_g2();
   g->device = ctx->device;
-  hipError_t e = hipMalloc((void**)&g->d, P.bytes);
-  if (e == hipSuccess) e = hipMemcpyAsync(g->d, host.data(), P.bytes, hipMemcpyHostToDevice, ctx->stream);
+  hipError_t e = hipMalloc((void**)&g->d, P.at.bytes);
+  if (e == hipSuccess) e = hipMemcpyAsync(g->d, host.data(), P.at.bytes, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = zk_host_wait(ctx, ctx->stream);
   if (e != hipSuccess) {
     if (g->d) (void)hipFree(g->d);

@@ -12,7 +12,9 @@
 
 #include <vector>
 
+#include "../../include/amdzk.h"
 #include "fq12.cuh"
+#include "workspace.hpp"
 
 namespace pairing {
 using namespace bn254;
@@ -439,6 +441,45 @@ inline G2Affine g2_from_words(const uint64_t w[16]) {
 }
 inline void g2_to_words(const G2Affine& q, uint64_t w[16]) {
   memcpy(w, q.x.c0.l, 32), memcpy(w + 4, q.x.c1.l, 32), memcpy(w + 8, q.y.c0.l, 32), memcpy(w + 12, q.y.c1.l, 32);
+}
+
+// ---- byte layouts (a braced list is evaluated left to right). The device image of ONE prepared point (pairing.hip, amdzk_g2):
+// the executor's constants Fq2x[K_COUNT] at 0, g2_prepare's Fq[4 * PAIRING_NUM_LINES] at `lines`, then the three programs' words
+struct ImageLayout {
+  size_t lines, miller, mul, fin, bytes;
+};
+inline ImageLayout image_layout(size_t n_consts, size_t n_lines, size_t miller_len, size_t mul_len, size_t fin_len) {
+  WsLayout w;
+  w.take(n_consts * sizeof(Fq2x));
+  return ImageLayout{w.take(4 * n_lines * sizeof(Fq)), w.take(miller_len * 4), w.take(mul_len * 4), w.take(fin_len * 4), w.bytes()};
+}
+// The programs as every handle carries them, flattened once per process
+struct Programs {
+  Prog miller = miller_program(), mul = mul_program(), fin = final_exp_program();
+  ImageLayout at = image_layout(K_COUNT, PAIRING_NUM_LINES, miller.w.size(), mul.w.size(), fin.w.size());
+  uint32_t final_regs = (uint32_t)(mul.regs > fin.regs ? mul.regs : fin.regs);  // the slab of a lane of the final kernel: it runs mul and fin
+};
+inline const Programs& programs() {
+  static const Programs P;
+  return P;
+}
+// One amdzk_pairing_products call of n checks over m prepared points (ZK_WS_STARTUP), `chunk` checks per launch
+constexpr size_t PAIRING_CHUNK_LANES = 16384;  // Miller lanes per launch: bounds the register slabs (about 2 KB a Miller lane, 5 KB a check)
+inline size_t pairing_chunk(size_t n, size_t m) { return PAIRING_CHUNK_LANES / m < n ? PAIRING_CHUNK_LANES / m : n; }  // m <= 16: at least 1024
+struct CallLayout {
+  // [0, miller_slab) goes up from pinned memory: m pointers to the points' lines at 0 (room for AMDZK_PAIRING_MAX_M), then
+  size_t g1;           // G1Affine[n * m], check-major
+  size_t miller_slab;  // Fq2x[chunk * m][miller_regs]
+  size_t final_slab;   // Fq2x[chunk][final_regs]
+  size_t gt;           // Fq[n][12] and, without a gap, ...
+  size_t is_one;       // uint8_t[n]: [gt, is_one + n) comes down in one copy
+  size_t bytes;
+};
+inline CallLayout call_layout(size_t n, size_t m, size_t chunk, size_t miller_regs, size_t final_regs) {
+  WsLayout w;
+  w.take(AMDZK_PAIRING_MAX_M * sizeof(void*));
+  return CallLayout{w.take(n * m * sizeof(G1Affine)), w.take(chunk * m * miller_regs * sizeof(Fq2x)), w.take(chunk * final_regs * sizeof(Fq2x)),
+                    w.take(n * 12 * sizeof(Fq), 1), w.take(ws_round_up(n, 256), 1), w.bytes()};  // is_one starts at no multiple of 256
 }
 
 }  // namespace pairing

@@ -1166,7 +1166,7 @@ int zk_poly_eval(amdzk_ctx* ctx, const Fr* const* d_polys, const Fr* d_points, F
     return AMDZK_OK;
   }
   Fr* parts = nullptr;
-  ZK_TRY(zk_ws_reserve(ctx, 4, nq * nseg * sizeof(Fr), (void**)&parts));  // slot 4 is also kate_div's and lincomb's: stream order keeps them apart
+  ZK_TRY(zk_ws_reserve(ctx, ZK_WS_OPENING, nq * nseg * sizeof(Fr), (void**)&parts));
   ZK_LAUNCH(ctx, "poly_eval", poly_eval_kernel, dim3((unsigned)nq, nseg), dim3(256), 0, d_polys, d_points, d_out, n, parts);
   ZK_LAUNCH(ctx, "poly_eval_combine", poly_eval_combine_kernel, dim3((unsigned)((nq + 63) / 64)), dim3(64), 0, (const Fr*)parts, d_points, d_out, (uint32_t)nq,
             nseg);
@@ -1188,7 +1188,7 @@ int zk_lincomb(amdzk_ctx* ctx, const Fr* const* d_polys, const Fr* d_coefs, uint
     return AMDZK_OK;
   }
   Fr* parts = nullptr;
-  ZK_TRY(zk_ws_reserve(ctx, 4, (size_t)nparts * n * sizeof(Fr), (void**)&parts));  // slot 4 is also kate_div's: stream order keeps them apart
+  ZK_TRY(zk_ws_reserve(ctx, ZK_WS_OPENING, (size_t)nparts * n * sizeof(Fr), (void**)&parts));
   const uint32_t per_part = (m + nparts - 1) / nparts;
   ZK_LAUNCH(ctx, "lincomb", lincomb_kernel, dim3(gx, nparts), dim3(256), 0, d_polys, d_coefs, m, parts, n, 0, per_part, n);
   ZK_LAUNCH(ctx, "lincomb_sum_parts", lincomb_sum_parts_kernel, dim3(gx), dim3(256), 0, (const Fr*)parts, n, nparts, d_out, n, accumulate ? 1 : 0);
@@ -1224,7 +1224,7 @@ int zk_kate_div_from(amdzk_ctx* ctx, Fr* const* d_polys, const Fr* const* d_srcs
     return AMDZK_OK;
   }
   Fr* tmp = nullptr;  // totals | carries
-  ZK_TRY(zk_ws_reserve(ctx, 4, 2 * npolys * nblk * sizeof(Fr), (void**)&tmp));
+  ZK_TRY(zk_ws_reserve(ctx, ZK_WS_OPENING, 2 * npolys * nblk * sizeof(Fr), (void**)&tmp));
   Fr* totals = tmp;
   Fr* carries = tmp + npolys * nblk;
   ZK_LAUNCH(ctx, "kate_div_totals", kate_div_kernel<false>, grid, block, 0, d_polys, d_roots, n, nblk, totals, (const Fr*)nullptr, d_srcs, d_lows,
@@ -1295,8 +1295,8 @@ namespace {
 int upload_ptrs_and_frs(amdzk_ctx* ctx, const void* const* ptrs, size_t nptrs, const uint64_t* frs, size_t nfrs, size_t extra_frs, void*** d_ptrs,
                         Fr** d_frs) {
   char* ws = nullptr;
-  const size_t pbytes = (nptrs * sizeof(void*) + 255) / 256 * 256;
-  ZK_TRY(zk_ws_reserve(ctx, 6, pbytes + (nfrs + extra_frs) * sizeof(Fr) + 256, (void**)&ws));
+  const size_t pbytes = ws_round_up(nptrs * sizeof(void*), 256);
+  ZK_TRY(zk_ws_reserve(ctx, ZK_WS_TABLES, pbytes + (nfrs + extra_frs) * sizeof(Fr) + 256, (void**)&ws));
   if (nptrs) ZK_HIP(ctx, hipMemcpyAsync(ws, ptrs, nptrs * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
   if (nfrs) ZK_HIP(ctx, hipMemcpyAsync(ws + pbytes, frs, nfrs * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
   ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));  // the host arrays belong to the caller
@@ -1314,7 +1314,7 @@ int amdzk_batch_invert_dev(amdzk_ctx* ctx, void* d_a, size_t n) {
   if (!ctx) return AMDZK_E_INVALID;
   if (!d_a && n) ZK_FAIL(ctx, AMDZK_E_INVALID, "batch_invert: null pointer");
   Fr* scratch = nullptr;
-  ZK_TRY(zk_ws_reserve(ctx, 7, (n ? n : 1) * sizeof(Fr), (void**)&scratch));
+  ZK_TRY(zk_ws_reserve(ctx, ZK_WS_CALLS, (n ? n : 1) * sizeof(Fr), (void**)&scratch));
   return zk_batch_invert(ctx, (Fr*)d_a, scratch, n);
 }
 
@@ -1330,7 +1330,7 @@ int amdzk_batch_invert_assigned_dev(amdzk_ctx* ctx, const void* d_num, const voi
   if (d_out != d_num) ZK_HIP(ctx, hipMemcpyAsync(d_out, d_num, n * sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
   if (!d_den) return AMDZK_OK;
   Fr* ws = nullptr;
-  ZK_TRY(zk_ws_reserve(ctx, 7, 2 * n * sizeof(Fr), (void**)&ws));
+  ZK_TRY(zk_ws_reserve(ctx, ZK_WS_CALLS, 2 * n * sizeof(Fr), (void**)&ws));
   ZK_HIP(ctx, hipMemcpyAsync(ws, d_den, n * sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
   ZK_TRY(zk_batch_invert(ctx, ws, ws + n, n));
   return zk_mul_elem(ctx, (Fr*)d_out, ws, n);
@@ -1345,7 +1345,7 @@ int amdzk_grand_product_dev(amdzk_ctx* ctx, void* d_cols, size_t ncols, size_t n
   if (!d_cols && ncols) ZK_FAIL(ctx, AMDZK_E_INVALID, "grand_product: null pointer");
   if (ncols > 65535 || col_stride < n || (chain && chain_row >= n)) ZK_FAIL(ctx, AMDZK_E_INVALID, "grand_product: bad shape");
   Fr* tmp = nullptr;
-  ZK_TRY(zk_ws_reserve(ctx, 7, (zk_scan_totals_elems(n, ncols) + 2 * ncols + 8) * sizeof(Fr), (void**)&tmp));
+  ZK_TRY(zk_ws_reserve(ctx, ZK_WS_CALLS, (zk_scan_totals_elems(n, ncols) + 2 * ncols + 8) * sizeof(Fr), (void**)&tmp));
   return zk_running_product(ctx, (Fr*)d_cols, ncols, n, col_stride, chain != 0, chain_row, tmp);
 }
 

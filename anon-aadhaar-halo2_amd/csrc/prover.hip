@@ -1013,13 +1013,9 @@ int create_proof_impl(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t ncirc, const 
   ZK_ENTER(ctx);
   if (!ctx) return AMDZK_E_INVALID;
   if (!pks || ncirc == 0 || !pks[0]) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: no proving key");
-  const int r = create_proof_body(ctx, pks, ncirc, instances, instance_lens, d_advice, advice_stride, rng, transcript_kind, proof_out, proof_cap, proof_len, ex);
-  if (r != AMDZK_OK) {  // a failed proof may have left work on the lanes: the key's workspace must be quiet before it is used again
-    const std::string keep = ctx->err;
-    (void)zk_sync_all(ctx);
-    ctx->err = keep;
-  }
-  return r;
+  // a failed proof may have left work on the lanes: the key's workspace must be quiet before it is used again
+  return zk_quiet_if_refused(
+      ctx, create_proof_body(ctx, pks, ncirc, instances, instance_lens, d_advice, advice_stride, rng, transcript_kind, proof_out, proof_cap, proof_len, ex), true);
 }
 
 
@@ -1079,9 +1075,8 @@ struct Gang {
     for (auto& m : members) c += m->live ? 1 : 0;
     return c;
   }
-  // device scratch of the gang's own (pointer tables, evaluation points and results): workspace slot 2, the staging slot of
-  // the host-pointer MSM / NTT entry points, which no proof uses. Valid until the next call (the slot may grow).
-  int scratch(size_t bytes, char** out) { return zk_ws_reserve(ctx, 2, bytes, (void**)out); }
+  // device scratch of the gang's own (pointer tables, evaluation points and results). Valid until the next call (the slot may grow).
+  int scratch(size_t bytes, char** out) { return zk_ws_reserve(ctx, ZK_WS_STAGING, bytes, (void**)out); }
 
   // The commitment batches the live members left in their sinks, as ONE submission per basis (a step has one basis; the products' step
   // two: the lookup products over g_lagrange, the permutation products' differences over its prefix sums), then
@@ -1146,7 +1141,7 @@ struct Gang {
     const size_t nq = pp.size();
     if (!nq) return AMDZK_OK;
     amdzk_pk* const pk0 = members[0]->pk;
-    const size_t o_pts = (nq * sizeof(Fr*) + 255) / 256 * 256;
+    const size_t o_pts = ws_round_up(nq * sizeof(Fr*), 256);
     char* d = nullptr;
     ZK_TRY(scratch(o_pts + 2 * nq * 32, &d));
     Fr* d_pts = (Fr*)(d + o_pts);
@@ -1398,11 +1393,8 @@ static int proof_batch(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_proofs, co
     if (m->live) memcpy(proofs_out + m->index * proof_stride, m->T().proof.data(), m->T().proof.size());
     else if (first == AMDZK_OK) first = m->status, first_err = m->err;
   }
-  if (first != AMDZK_OK) {  // a failed proof may have left work behind: the workspaces must be quiet before they are used again
-    (void)zk_sync_all(ctx);
-    ctx->err = first_err;
-  }
-  return first;
+  if (first != AMDZK_OK) ctx->err = first_err;
+  return zk_quiet_if_refused(ctx, first, true);  // a failed proof may have left work behind: the workspaces must be quiet before they are used again
 }
 int amdzk_create_proof_batch(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_proofs, const uint64_t* const* const* instances,
                              const size_t* const* instance_lens, const void* const* d_advice, size_t advice_stride,
@@ -1501,7 +1493,7 @@ int amdzk_permute_expression_pair_dev(amdzk_ctx* ctx, void* d_inputs, const void
   if (n < 2 || (n & (n - 1)) || usable > n) ZK_FAIL(ctx, AMDZK_E_INVALID, "permute_expression_pair: n must be a power of two >= usable");
   char* ws = nullptr;  // Ts[L][n] | left[L][n] | flags 4 x L x (n + 8) | err
   const size_t L = nlookups, col = L * (size_t)n * 32, fl = 4 * L * ((size_t)n + 8) * 4;
-  ZK_TRY(zk_ws_reserve(ctx, 5, 2 * col + fl + 256, (void**)&ws));
+  ZK_TRY(zk_ws_reserve(ctx, ZK_WS_PERMUTE, 2 * col + fl + 256, (void**)&ws));
   if (L == 0) return AMDZK_OK;
   ZK_TRY(zk_permute_expression_pairs(ctx, (Fr*)d_inputs, (const Fr*)d_tables, (Fr*)ws, (Fr*)d_permuted_tables_out, (Fr*)(ws + col),
                                      (uint32_t*)(ws + 2 * col), (int*)(ws + 2 * col + fl), L, n, usable));

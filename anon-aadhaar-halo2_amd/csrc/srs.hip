@@ -169,10 +169,10 @@ int zk_srs_setup(amdzk_ctx* ctx, uint32_t k, const uint64_t s_mont[4], const uin
   Fr s, omega;
   memcpy(s.l, s_mont, 32);
   memcpy(omega.l, omega_mont, 32);
-  // workspace (slot 3): gtable[256] | scal[n] | w[n] | scratch[n] | g[n] | gl[n]
+  // workspace: gtable[256] | scal[n] | w[n] | scratch[n] | g[n] | gl[n]
   char* ws = nullptr;
   const size_t bytes = 256 * sizeof(G1Affine) + 3 * n * sizeof(Fr) + 2 * n * sizeof(G1Affine);
-  ZK_TRY(zk_ws_reserve(ctx, 3, bytes, (void**)&ws));
+  ZK_TRY(zk_ws_reserve(ctx, ZK_WS_STARTUP, bytes, (void**)&ws));
   G1Affine* gtab = (G1Affine*)ws;
   Fr* scal = (Fr*)(ws + 256 * sizeof(G1Affine));
   Fr* w = scal + n;
@@ -304,7 +304,7 @@ int zk_srs_write(amdzk_ctx* ctx, const amdzk_srs* s, const uint8_t g2[64], const
   const size_t need = zk_srs_serialized_size(s->k);
   if (cap < need) ZK_FAIL(ctx, AMDZK_E_INVALID, "srs_write: buffer too small (%zu < %zu)", cap, need);
   uint8_t* d = nullptr;
-  ZK_TRY(zk_ws_reserve(ctx, 3, 2 * s->n * 32, (void**)&d));
+  ZK_TRY(zk_ws_reserve(ctx, ZK_WS_STARTUP, 2 * s->n * 32, (void**)&d));
   dim3 grid((unsigned)((s->n + 255) / 256)), block(256);
   ZK_LAUNCH(ctx, "g1_compress", g1_compress_kernel, grid, block, 0, s->base[0], d, s->n);
   ZK_LAUNCH(ctx, "g1_compress", g1_compress_kernel, grid, block, 0, s->base[1], d + s->n * 32, s->n);
@@ -325,7 +325,7 @@ int zk_srs_read(amdzk_ctx* ctx, const uint8_t* data, size_t len, amdzk_srs** out
   const size_t n = (size_t)1 << k;
   if (len < zk_srs_serialized_size(k)) ZK_FAIL(ctx, AMDZK_E_INVALID, "srs_read: %zu bytes given, %zu needed for k = %u", len, zk_srs_serialized_size(k), k);
   char* ws = nullptr;
-  ZK_TRY(zk_ws_reserve(ctx, 3, 2 * n * 32 + 2 * n * sizeof(G1Affine) + 256, (void**)&ws));
+  ZK_TRY(zk_ws_reserve(ctx, ZK_WS_STARTUP, 2 * n * 32 + 2 * n * sizeof(G1Affine) + 256, (void**)&ws));
   uint8_t* d_in = (uint8_t*)ws;
   G1Affine* pts = (G1Affine*)(ws + 2 * n * 32);
   int* d_err = (int*)(ws + 2 * n * 32 + 2 * n * sizeof(G1Affine));
@@ -365,9 +365,8 @@ int srs_check_run(amdzk_ctx* ctx, const amdzk_srs* s, const uint64_t g2[16], con
       if (st[0] || st[1]) rep->failed |= AMDZK_SRS_CHECK_G2;
     }
   }
-  // slot 2, not this unit's slot 3: the pairing reserves that one while colE is still to be read
-  char* ws = nullptr;  // first offender (256 bytes) | colA[n] | colB[n] | colC[n] | colE[n]
-  ZK_TRY(zk_ws_reserve(ctx, 2, 256 + 4 * n * sizeof(Fr), (void**)&ws));
+  char* ws = nullptr;  // first offender (256 bytes) | colA[n] | colB[n] | colC[n] | colE[n]; not ZK_WS_STARTUP: workspace.hpp
+  ZK_TRY(zk_ws_reserve(ctx, ZK_WS_STAGING, 256 + 4 * n * sizeof(Fr), (void**)&ws));
   unsigned long long* d_first = (unsigned long long*)ws;
   Fr *colA = (Fr*)(ws + 256), *colB = colA + n, *colC = colB + n, *colE = colC + n;
   if (checks & AMDZK_SRS_CHECK_CURVE) {
@@ -414,11 +413,9 @@ int srs_check_run(amdzk_ctx* ctx, const amdzk_srs* s, const uint64_t g2[16], con
       if (r == AMDZK_OK) r = amdzk_g2_prepare(ctx, g2, &q[1]);
       uint8_t one = 0;
       if (r == AMDZK_OK) r = zk_pairing_products(ctx, "srs_check", q, 2, ab, 1, &one, nullptr);
-      const std::string keep = ctx->err;
-      if (r != AMDZK_OK) (void)zk_host_wait(ctx, ctx->stream);
+      (void)zk_quiet_if_refused(ctx, r);  // nothing reads the handles any more
       amdzk_g2_free(ctx, q[0]);
       amdzk_g2_free(ctx, q[1]);
-      ctx->err = keep;
       ZK_TRY(r);
       ok = one != 0;
     }
@@ -454,13 +451,7 @@ int zk_srs_check(amdzk_ctx* ctx, const amdzk_srs* s, const uint64_t g2[16], cons
     rho = rng.fr();
   }
   memset(rep, 0, sizeof(*rep));
-  const int r = srs_check_run(ctx, s, g2, s_g2, checks, rho, rep);
-  if (r != AMDZK_OK) {  // whatever was enqueued is finished before the call returns
-    const std::string keep = ctx->err;
-    (void)zk_host_wait(ctx, ctx->stream);
-    ctx->err = keep;
-  }
-  return r;
+  return zk_quiet_if_refused(ctx, srs_check_run(ctx, s, g2, s_g2, checks, rho, rep));  // whatever was enqueued is finished before the call returns
 }
 
 // ---- arithmetic::g_to_lagrange(g, k) and ParamsKZG::downsize(k) [UP]:
@@ -538,7 +529,7 @@ int zk_g_to_lagrange(amdzk_ctx* ctx, const uint64_t* g, uint32_t k, const uint64
   memcpy(wi.l, omega_inv, 32);
   memcpy(ni.l, n_inv, 32);
   char* ws = nullptr;  // g[n] | gl[n] | xyzz[n] | tw[n/2]
-  ZK_TRY(zk_ws_reserve(ctx, 3, 2 * n * sizeof(G1Affine) + n * sizeof(G1X) + (n / 2 + 1) * sizeof(Fr), (void**)&ws));
+  ZK_TRY(zk_ws_reserve(ctx, ZK_WS_STARTUP, 2 * n * sizeof(G1Affine) + n * sizeof(G1X) + (n / 2 + 1) * sizeof(Fr), (void**)&ws));
   G1Affine* dg = (G1Affine*)ws;
   G1Affine* dl = dg + n;
   G1X* dx = (G1X*)(dl + n);
@@ -560,7 +551,7 @@ int zk_srs_downsize(amdzk_ctx* ctx, const amdzk_srs* srs, uint32_t new_k, const 
   memcpy(wi.l, omega_inv, 32);
   memcpy(ni.l, n_inv, 32);
   char* ws = nullptr;  // gl[n] | xyzz[n] | tw[n/2]
-  ZK_TRY(zk_ws_reserve(ctx, 3, n * sizeof(G1Affine) + n * sizeof(G1X) + (n / 2 + 1) * sizeof(Fr), (void**)&ws));
+  ZK_TRY(zk_ws_reserve(ctx, ZK_WS_STARTUP, n * sizeof(G1Affine) + n * sizeof(G1X) + (n / 2 + 1) * sizeof(Fr), (void**)&ws));
   G1Affine* dl = (G1Affine*)ws;
   G1X* dx = (G1X*)(dl + n);
   Fr* tw = (Fr*)(dx + n);
@@ -630,7 +621,7 @@ int ec_prefix_sums(amdzk_ctx* ctx, const G1Affine* d_in, size_t n, G1Affine* d_o
     total += m;
   }
   G1X* tot = nullptr;
-  if (total) ZK_TRY(zk_ws_reserve(ctx, 3, total * sizeof(G1X), (void**)&tot));
+  if (total) ZK_TRY(zk_ws_reserve(ctx, ZK_WS_STARTUP, total * sizeof(G1X), (void**)&tot));
   std::vector<G1X*> lvl;
   for (size_t l = 0, o = 0; l < sizes.size(); o += sizes[l], l++) lvl.push_back(tot + o);
   const dim3 block(64);

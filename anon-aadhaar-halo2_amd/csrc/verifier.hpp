@@ -24,6 +24,7 @@
 
 #include "opening.hpp"
 #include "pkblob.hpp"
+#include "workspace.hpp"
 
 namespace verifier {
 
@@ -522,6 +523,40 @@ inline void fold_proof(const Plan& p, const Fr& transcript_repr, const Fr& omega
   Challenges ch;
   run_transcript(p, T, transcript_repr, inst, lens, &ch);
   fold_challenges(p, omega, inst, lens, scs, rho, ch, Lout, Rout);
+}
+
+// The ONE device reservation of a verify call (verify.hip, verify_core; ZK_WS_STARTUP) and its mirror in pinned memory: n_proofs
+// proofs of E elements each — NP points, NS scalars — staged `stride` bytes apart; nvk commitments of the key. [0, points) goes UP
+// in one copy (a proving key's G is on the device already: its copy ends at `g`, and G follows device to device); the decoder
+// fills points and scalars; [status, msm) comes DOWN in one copy of down_bytes.
+struct DeviceLayout {
+  size_t staging;    // n_proofs x stride: the proofs' bytes, or what a caller's read transcript handed back
+  size_t elems;      // uint2[E]: (byte offset, is_point << 31 | index) of a built-in transcript's elements
+  size_t elems_raw;  // uint2[E]: the same for a read transcript's form (no bytes when no proof has one)
+  size_t form;       // uint8_t[n_proofs]: 1 = this proof came through a read transcript (no bytes when none did)
+  size_t status;     // uint32_t[n_proofs]: the decoder's verdict per proof
+  // commitments | G | points are CONTIGUOUS: the base array G1Affine[nvk + 1 + n_proofs * NP] of the combined MSM
+  size_t vk;         // G1Affine[nvk]: the key's fixed and permutation commitments
+  size_t g;          // G1Affine: the SRS's G
+  size_t points;     // G1Affine[n_proofs * NP]: decoded
+  size_t scalars;    // Fr[n_proofs * NS]: decoded
+  size_t msm;        // Fr[2][nvk + 1 + n_proofs * NP] combined; per proof Fr[2 * run][run_len], ONE run's columns
+  size_t run_bases;  // per proof: G1Affine[run_len], that run's commitments | G | points (= bytes otherwise)
+  size_t bytes, up_bytes, down_bytes;
+  size_t run, run_len;  // per proof: proofs per MSM, at most AMDZK_DECIDE_RUN, and the bases of one
+};
+inline DeviceLayout device_layout(size_t n_proofs, size_t stride, size_t E, size_t NP, size_t NS, size_t nvk, bool transcripts, bool per_proof) {
+  DeviceLayout L;
+  WsLayout w;
+  L.run = n_proofs < AMDZK_DECIDE_RUN ? n_proofs : AMDZK_DECIDE_RUN, L.run_len = nvk + 1 + L.run * NP;
+  L.staging = w.take(n_proofs * stride), L.elems = w.take(E * 8);
+  L.elems_raw = w.take(transcripts ? E * 8 : 0), L.form = w.take(transcripts ? n_proofs : 0), L.status = w.take(n_proofs * 4);
+  L.vk = w.take(nvk * sizeof(G1Affine), 1), L.g = w.take(sizeof(G1Affine), 1), L.points = w.take(n_proofs * NP * sizeof(G1Affine), 1);
+  L.scalars = w.take(n_proofs * NS * sizeof(Fr));
+  L.msm = per_proof ? w.take(2 * L.run * L.run_len * sizeof(Fr)) : w.take(2 * (nvk + 1 + n_proofs * NP) * sizeof(Fr), 1);
+  L.run_bases = w.take(per_proof ? L.run_len * sizeof(G1Affine) : 0, 1);
+  L.bytes = w.bytes(), L.up_bytes = L.points, L.down_bytes = L.msm - L.status;
+  return L;
 }
 
 }  // namespace verifier

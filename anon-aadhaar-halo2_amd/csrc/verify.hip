@@ -19,7 +19,6 @@ using namespace bn254;
 
 namespace {
 
-constexpr int VERIFY_WS_SLOT = 3;  // the start-up calls' slot (SRS read / write / setup): none of them runs inside this call
 constexpr uint32_t DECODE_THREADS = 64;
 constexpr uint32_t STATUS_CLEAN = 0xffffffffu;
 
@@ -143,8 +142,6 @@ __global__ __launch_bounds__(DECODE_THREADS) void proof_decode_kernel(DecodeArgs
   if (!ok) atomicMin(a.status + b, (el.x << 2) | cls);
 }
 
-size_t pad256(size_t v) { return (v + 255) / 256 * 256; }
-
 // What amdzk_verify_proofs, amdzk_verify_proofs_decide and their _vk forms share: everything up to the G1 sums, over a view
 // of the key (vk.hpp; key == nullptr: the caller passed no key). `who` prefixes the refusals.
 // pairs == nullptr: the batch's ONE pair, sum_b rho_b (L_b, R_b), in pair_out — amdzk_verify_proofs as documented.
@@ -212,24 +209,17 @@ int verify_core(amdzk_ctx* ctx, const char* who, const zk_key_view* key, size_t 
   if (per_proof) pairs->assign(2 * n_proofs, g1_inf);
   else memset(pair_out, 0, 16 * sizeof(uint64_t));
   if (live == 0) return AMDZK_OK;
-  // ---- one reservation: staging | element table | with transcripts: their element table and the per-proof form bytes |
-  // status words | key commitments | G | decoded points | decoded scalars | MSM scalars
+  // ---- one reservation (verifier::DeviceLayout) and its mirror in pinned memory
   const size_t E = plan.elems.size(), NP = plan.NP, NS = plan.NS, nvk = (size_t)plan.F + plan.S;
   std::vector<uint32_t> raw_off;
   const size_t raw_size = n_tr ? verifier::raw_offsets(plan, &raw_off) : 0;
   const size_t psize = plan.proof_bytes > raw_size ? plan.proof_bytes : raw_size;  // the staging stride: the larger form's
   if (psize >= ((size_t)1 << 30)) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "%s: proof layout of %zu bytes is too large", who, psize);
   const size_t nbases = nvk + 1 + n_proofs * NP;
-  const size_t o_elems = pad256(n_proofs * psize), o_eraw = o_elems + pad256(E * sizeof(uint2)), o_form = o_eraw + (n_tr ? pad256(E * sizeof(uint2)) : 0);
-  const size_t o_status = o_form + (n_tr ? pad256(n_proofs) : 0), o_vk = o_status + pad256(n_proofs * 4);
-  const size_t o_g = o_vk + nvk * sizeof(G1Affine), o_points = o_g + sizeof(G1Affine), o_dsc = o_points + n_proofs * NP * sizeof(G1Affine);
-  // per proof: the MSM scalars of ONE run (2 columns per proof over the key's commitments, G and the run's points) | that run's bases
-  const size_t run = n_proofs < AMDZK_DECIDE_RUN ? n_proofs : AMDZK_DECIDE_RUN, run_len = nvk + 1 + run * NP;
-  const size_t o_msm = pad256(o_dsc + n_proofs * NS * 32), o_rb = pad256(o_msm + 2 * run * run_len * 32);
-  const size_t total = per_proof ? o_rb + run_len * sizeof(G1Affine) : o_msm + 2 * nbases * 32;
-  const size_t up_bytes = key->h_g ? o_points : o_g, down_bytes = o_msm - o_status;  // a verifying key's G goes up with its commitments
+  const verifier::DeviceLayout L = verifier::device_layout(n_proofs, psize, E, NP, NS, nvk, n_tr != 0, per_proof);
+  const size_t run = L.run, up_bytes = key->h_g ? L.up_bytes : L.g, down_bytes = L.down_bytes;  // a verifying key's G goes up with its commitments
   char* ws = nullptr;
-  ZK_TRY(zk_ws_reserve(ctx, VERIFY_WS_SLOT, total, (void**)&ws));
+  ZK_TRY(zk_ws_reserve(ctx, ZK_WS_STARTUP, L.bytes, (void**)&ws));
   char* pin = nullptr;
   ZK_TRY(zk_pinned_reserve(ctx, up_bytes + down_bytes, (void**)&pin));
   char* h_down = pin + up_bytes;
@@ -238,8 +228,8 @@ int verify_core(amdzk_ctx* ctx, const char* who, const zk_key_view* key, size_t 
   // in the third form and its challenges are kept for the host half
   std::vector<verifier::Challenges> read_ch(n_tr ? n_proofs : 0);
   for (size_t b = 0; b < n_proofs; b++) {
-    ((uint32_t*)(pin + o_status))[b] = STATUS_CLEAN;
-    if (n_tr) pin[o_form + b] = tr_of(b) ? 1 : 0;
+    ((uint32_t*)(pin + L.status))[b] = STATUS_CLEAN;
+    if (n_tr) pin[L.form + b] = tr_of(b) ? 1 : 0;
     if (statuses[b].status != AMDZK_PROOF_WELL_FORMED) continue;
     if (!tr_of(b)) {
       memcpy(pin + b * psize, proofs[b], plan.proof_bytes);
@@ -255,29 +245,29 @@ int verify_core(amdzk_ctx* ctx, const char* who, const zk_key_view* key, size_t 
   }
   if (live == 0) return AMDZK_OK;
   for (size_t e = 0; e < E; e++) {
-    ((uint2*)(pin + o_elems))[e] = make_uint2(plan.elems[e].offset, (plan.elems[e].is_point << 31) | plan.elems[e].index);
-    if (n_tr) ((uint2*)(pin + o_eraw))[e] = make_uint2(raw_off[e], (plan.elems[e].is_point << 31) | plan.elems[e].index);
+    ((uint2*)(pin + L.elems))[e] = make_uint2(plan.elems[e].offset, (plan.elems[e].is_point << 31) | plan.elems[e].index);
+    if (n_tr) ((uint2*)(pin + L.elems_raw))[e] = make_uint2(raw_off[e], (plan.elems[e].is_point << 31) | plan.elems[e].index);
   }
-  if (plan.F) memcpy(pin + o_vk, key->fixed_commitments, (size_t)plan.F * sizeof(G1Affine));
-  if (plan.S) memcpy(pin + o_vk + (size_t)plan.F * sizeof(G1Affine), key->perm_commitments, (size_t)plan.S * sizeof(G1Affine));
+  if (plan.F) memcpy(pin + L.vk, key->fixed_commitments, (size_t)plan.F * sizeof(G1Affine));
+  if (plan.S) memcpy(pin + L.vk + (size_t)plan.F * sizeof(G1Affine), key->perm_commitments, (size_t)plan.S * sizeof(G1Affine));
   if (!key->d_g && !key->h_g) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: the key's SRS has no monomial basis", who);
-  if (key->h_g) memcpy(pin + o_g, key->h_g, sizeof(G1Affine));
+  if (key->h_g) memcpy(pin + L.g, key->h_g, sizeof(G1Affine));
   ZK_HIP(ctx, hipMemcpyAsync(ws, pin, up_bytes, hipMemcpyHostToDevice, ctx->stream));
-  if (key->d_g) ZK_HIP(ctx, hipMemcpyAsync(ws + o_g, key->d_g, sizeof(G1Affine), hipMemcpyDeviceToDevice, ctx->stream));
+  if (key->d_g) ZK_HIP(ctx, hipMemcpyAsync(ws + L.g, key->d_g, sizeof(G1Affine), hipMemcpyDeviceToDevice, ctx->stream));
   DecodeArgs da;
-  da.staging = (const uint8_t*)ws, da.stride = psize, da.elems = (const uint2*)(ws + o_elems);
+  da.staging = (const uint8_t*)ws, da.stride = psize, da.elems = (const uint2*)(ws + L.elems);
   da.E = (uint32_t)E, da.NP = (uint32_t)NP, da.NS = (uint32_t)NS, da.total = n_proofs * E;
-  da.points = (G1Affine*)(ws + o_points), da.scalars = (Fr*)(ws + o_dsc), da.status = (uint32_t*)(ws + o_status), da.evm = plan.evm ? 1 : 0;
-  da.raw = n_tr ? (const uint8_t*)(ws + o_form) : nullptr, da.raw_all = 0, da.elems_raw = (const uint2*)(ws + o_eraw), da.raw_inf_below = 0;
+  da.points = (G1Affine*)(ws + L.points), da.scalars = (Fr*)(ws + L.scalars), da.status = (uint32_t*)(ws + L.status), da.evm = plan.evm ? 1 : 0;
+  da.raw = n_tr ? (const uint8_t*)(ws + L.form) : nullptr, da.raw_all = 0, da.elems_raw = (const uint2*)(ws + L.elems_raw), da.raw_inf_below = 0;
   const size_t blocks = (da.total + DECODE_THREADS - 1) / DECODE_THREADS;
   if (blocks > 0x7fffffffu) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: batch too large", who);
   ZK_LAUNCH(ctx, "proof_decode", proof_decode_kernel, dim3((unsigned)blocks), dim3(DECODE_THREADS), 0, da);
-  ZK_HIP(ctx, hipMemcpyAsync(h_down, ws + o_status, down_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  ZK_HIP(ctx, hipMemcpyAsync(h_down, ws + L.status, down_bytes, hipMemcpyDeviceToHost, ctx->stream));
   ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));  // wait 1 of 2
   // ---- the host half: per proof one scalar per base for L and for R, summed over the batch
   const uint32_t* h_status = (const uint32_t*)h_down;
-  const G1Affine* h_points = (const G1Affine*)(h_down + (o_points - o_status));
-  const Fr* h_scalars = (const Fr*)(h_down + (o_dsc - o_status));
+  const G1Affine* h_points = (const G1Affine*)(h_down + (L.points - L.status));
+  const Fr* h_scalars = (const Fr*)(h_down + (L.scalars - L.status));
   std::vector<Fr> msm(per_proof ? 0 : 2 * nbases, Fr::zero()), Lb(plan.n_bases), Rb(plan.n_bases);
   std::vector<Fr> own;       // per proof: the live proofs' (Lb | Rb), in batch order
   std::vector<size_t> who_b;  // ... and their positions
@@ -310,7 +300,7 @@ int verify_core(amdzk_ctx* ctx, const char* who, const zk_key_view* key, size_t 
     // ---- (L_b, R_b) for every live proof: per run of AMDZK_DECIDE_RUN batch positions one MSM of 2 columns per live proof
     // over the key's commitments, G and the run's decoded points (a proof's columns are zero on its neighbours' points,
     // and zero scalars cost nothing). One host wait per run.
-    ZK_HIP(ctx, hipMemcpyAsync(ws + o_rb, ws + o_vk, (nvk + 1) * sizeof(G1Affine), hipMemcpyDeviceToDevice, ctx->stream));
+    ZK_HIP(ctx, hipMemcpyAsync(ws + L.run_bases, ws + L.vk, (nvk + 1) * sizeof(G1Affine), hipMemcpyDeviceToDevice, ctx->stream));
     std::vector<uint64_t> jac(24 * run);
     for (size_t lo = 0, b0 = 0; b0 < n_proofs; b0 += run) {
       const size_t b1 = b0 + run < n_proofs ? b0 + run : n_proofs, len = nvk + 1 + (b1 - b0) * NP;
@@ -327,11 +317,11 @@ int verify_core(amdzk_ctx* ctx, const char* who, const zk_key_view* key, size_t 
           for (uint32_t i = 0; i < plan.n_bases; i++) col[i < NP ? nvk + 1 + (b - b0) * NP + i : i - NP] = src[i];
         }
       }
-      ZK_HIP(ctx, hipMemcpyAsync(ws + o_rb + (nvk + 1) * sizeof(G1Affine), ws + o_points + b0 * NP * sizeof(G1Affine), (b1 - b0) * NP * sizeof(G1Affine),
+      ZK_HIP(ctx, hipMemcpyAsync(ws + L.run_bases + (nvk + 1) * sizeof(G1Affine), ws + L.points + b0 * NP * sizeof(G1Affine), (b1 - b0) * NP * sizeof(G1Affine),
                                  hipMemcpyDeviceToDevice, ctx->stream));
-      ZK_HIP(ctx, hipMemcpyAsync(ws + o_msm, msm.data(), msm.size() * 32, hipMemcpyHostToDevice, ctx->stream));
+      ZK_HIP(ctx, hipMemcpyAsync(ws + L.msm, msm.data(), msm.size() * 32, hipMemcpyHostToDevice, ctx->stream));
       G1X* d_res = nullptr;
-      ZK_TRY(zk_msm_bases_dev_xyzz(ctx, (const Fr*)(ws + o_msm), 2 * nl, len, len, (const G1Affine*)(ws + o_rb), &d_res));
+      ZK_TRY(zk_msm_bases_dev_xyzz(ctx, (const Fr*)(ws + L.msm), 2 * nl, len, len, (const G1Affine*)(ws + L.run_bases), &d_res));
       ZK_TRY(zk_msm_finish(ctx, d_res, 2 * nl, jac.data()));
       for (size_t q = 0; q < 2 * nl; q++) {
         const G1Jac* j = reinterpret_cast<const G1Jac*>(jac.data() + 12 * q);
@@ -344,9 +334,9 @@ int verify_core(amdzk_ctx* ctx, const char* who, const zk_key_view* key, size_t 
     return AMDZK_OK;
   }
   // ---- L and R: one MSM of two columns over the decoded points, the key's commitments and G (zero scalars cost nothing)
-  ZK_HIP(ctx, hipMemcpyAsync(ws + o_msm, msm.data(), 2 * nbases * 32, hipMemcpyHostToDevice, ctx->stream));
+  ZK_HIP(ctx, hipMemcpyAsync(ws + L.msm, msm.data(), 2 * nbases * 32, hipMemcpyHostToDevice, ctx->stream));
   G1X* d_res = nullptr;
-  ZK_TRY(zk_msm_bases_dev_xyzz(ctx, (const Fr*)(ws + o_msm), 2, nbases, nbases, (const G1Affine*)(ws + o_vk), &d_res));
+  ZK_TRY(zk_msm_bases_dev_xyzz(ctx, (const Fr*)(ws + L.msm), 2, nbases, nbases, (const G1Affine*)(ws + L.vk), &d_res));
   uint64_t jac[24];
   ZK_TRY(zk_msm_finish(ctx, d_res, 2, jac));  // wait 2 of 2
   for (int c = 0; c < 2; c++) {
@@ -433,48 +423,50 @@ int zk_points_check_dev(amdzk_ctx* ctx, G1Affine* d_pts, size_t n, size_t inf_be
   return AMDZK_OK;
 }
 
+// The entry points over either key: the view (no key: no view, which verify_core refuses), the body, and — a refused call may
+// have copies in flight out of vectors that die with it — the stream idle before a refusal returns.
+template <class Key>
+static int verify_entry(amdzk_ctx* ctx, const Key* k, size_t n_proofs, const uint64_t* const* const* instances, const size_t* const* instance_lens,
+                        const uint8_t* const* proofs, const size_t* proof_lens, const amdzk_verify_opts* opts, amdzk_proof_status* statuses,
+                        uint64_t* pair_out) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  zk_key_view key;
+  if (k) key = view_of(k);
+  return zk_quiet_if_refused(
+      ctx, verify_core(ctx, "verify_proofs", k ? &key : nullptr, n_proofs, instances, instance_lens, proofs, proof_lens, opts, statuses, pair_out, nullptr));
+}
+template <class Key>
+static int decide_entry(amdzk_ctx* ctx, const Key* k, const amdzk_g2* s_g2, const amdzk_g2* g2, uint32_t flags, size_t n_proofs,
+                        const uint64_t* const* const* instances, const size_t* const* instance_lens, const uint8_t* const* proofs,
+                        const size_t* proof_lens, const amdzk_verify_opts* opts, amdzk_proof_status* statuses, uint8_t* verdicts, size_t* n_valid) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  zk_key_view key;
+  if (k) key = view_of(k);
+  return zk_quiet_if_refused(ctx, decide_core(ctx, "verify_proofs_decide", k ? &key : nullptr, s_g2, g2, flags, n_proofs, instances, instance_lens, proofs,
+                                              proof_lens, opts, statuses, verdicts, n_valid));
+}
+
 extern "C" int amdzk_verify_proofs(amdzk_ctx* ctx, const amdzk_pk* pk, size_t n_proofs, const uint64_t* const* const* instances,
                                    const size_t* const* instance_lens, const uint8_t* const* proofs, const size_t* proof_lens,
                                    const amdzk_verify_opts* opts, amdzk_proof_status* statuses, uint64_t pair_out[16]) {
-  ZK_ENTER(ctx);
-  if (!ctx) return AMDZK_E_INVALID;
-  if (!pair_out) ZK_FAIL(ctx, AMDZK_E_INVALID, "verify_proofs: null argument");
-  zk_key_view key;
-  if (pk) key = view_of(pk);
-  return verify_core(ctx, "verify_proofs", pk ? &key : nullptr, n_proofs, instances, instance_lens, proofs, proof_lens, opts, statuses, pair_out, nullptr);
+  return verify_entry(ctx, pk, n_proofs, instances, instance_lens, proofs, proof_lens, opts, statuses, pair_out);
 }
-
 extern "C" int amdzk_verify_proofs_vk(amdzk_ctx* ctx, const amdzk_vk* vk, size_t n_proofs, const uint64_t* const* const* instances,
                                       const size_t* const* instance_lens, const uint8_t* const* proofs, const size_t* proof_lens,
                                       const amdzk_verify_opts* opts, amdzk_proof_status* statuses, uint64_t pair_out[16]) {
-  ZK_ENTER(ctx);
-  if (!ctx) return AMDZK_E_INVALID;
-  if (!pair_out) ZK_FAIL(ctx, AMDZK_E_INVALID, "verify_proofs: null argument");
-  zk_key_view key;
-  if (vk) key = view_of(vk);
-  return verify_core(ctx, "verify_proofs", vk ? &key : nullptr, n_proofs, instances, instance_lens, proofs, proof_lens, opts, statuses, pair_out, nullptr);
+  return verify_entry(ctx, vk, n_proofs, instances, instance_lens, proofs, proof_lens, opts, statuses, pair_out);
 }
-
 extern "C" int amdzk_verify_proofs_decide(amdzk_ctx* ctx, const amdzk_pk* pk, const amdzk_g2* s_g2, const amdzk_g2* g2, uint32_t flags,
                                           size_t n_proofs, const uint64_t* const* const* instances, const size_t* const* instance_lens,
                                           const uint8_t* const* proofs, const size_t* proof_lens, const amdzk_verify_opts* opts,
                                           amdzk_proof_status* statuses, uint8_t* verdicts, size_t* n_valid) {
-  ZK_ENTER(ctx);
-  if (!ctx) return AMDZK_E_INVALID;
-  zk_key_view key;
-  if (pk) key = view_of(pk);
-  return decide_core(ctx, "verify_proofs_decide", pk ? &key : nullptr, s_g2, g2, flags, n_proofs, instances, instance_lens, proofs, proof_lens, opts,
-                     statuses, verdicts, n_valid);
+  return decide_entry(ctx, pk, s_g2, g2, flags, n_proofs, instances, instance_lens, proofs, proof_lens, opts, statuses, verdicts, n_valid);
 }
-
 extern "C" int amdzk_verify_proofs_decide_vk(amdzk_ctx* ctx, const amdzk_vk* vk, const amdzk_g2* s_g2, const amdzk_g2* g2, uint32_t flags,
                                              size_t n_proofs, const uint64_t* const* const* instances, const size_t* const* instance_lens,
                                              const uint8_t* const* proofs, const size_t* proof_lens, const amdzk_verify_opts* opts,
                                              amdzk_proof_status* statuses, uint8_t* verdicts, size_t* n_valid) {
-  ZK_ENTER(ctx);
-  if (!ctx) return AMDZK_E_INVALID;
-  zk_key_view key;
-  if (vk) key = view_of(vk);
-  return decide_core(ctx, "verify_proofs_decide", vk ? &key : nullptr, s_g2, g2, flags, n_proofs, instances, instance_lens, proofs, proof_lens, opts,
-                     statuses, verdicts, n_valid);
+  return decide_entry(ctx, vk, s_g2, g2, flags, n_proofs, instances, instance_lens, proofs, proof_lens, opts, statuses, verdicts, n_valid);
 }

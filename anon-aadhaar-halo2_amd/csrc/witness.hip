@@ -254,16 +254,6 @@ int wit_run(amdzk_ctx* ctx, amdzk_witness* w, size_t n_proofs, const Fr* d_input
   return AMDZK_OK;
 }
 
-// whatever was enqueued (copies from and to the caller's memory among it) is finished before a refused call returns
-int wit_finish(amdzk_ctx* ctx, int r) {
-  if (r != AMDZK_OK) {
-    const std::string keep = ctx->err;
-    (void)zk_host_wait(ctx, ctx->stream);
-    ctx->err = keep;
-  }
-  return r;
-}
-
 }  // namespace
 
 extern "C" int amdzk_witness_plan(const amdzk_witness_desc* desc, size_t n_proofs, uint32_t* levels, uint32_t* launches, uint32_t* fused_width,
@@ -320,7 +310,7 @@ extern "C" int amdzk_witness_run_dev(amdzk_ctx* ctx, amdzk_witness* w, size_t n_
   ZK_ENTER(ctx);
   if (!ctx) return AMDZK_E_INVALID;
   if (!w) ZK_FAIL(ctx, AMDZK_E_INVALID, "witness: null argument");
-  return wit_finish(ctx, wit_run(ctx, w, n_proofs, (const Fr*)d_inputs, input_stride, false, d_advice, advice_stride, flags, max_scratch_bytes, publics_out));
+  return zk_quiet_if_refused(ctx, wit_run(ctx, w, n_proofs, (const Fr*)d_inputs, input_stride, false, d_advice, advice_stride, flags, max_scratch_bytes, publics_out));
 }
 
 extern "C" int amdzk_witness_run(amdzk_ctx* ctx, amdzk_witness* w, size_t n_proofs, const uint64_t* const* inputs, void* const* d_advice,
@@ -344,5 +334,5 @@ extern "C" int amdzk_witness_run(amdzk_ctx* ctx, amdzk_witness* w, size_t n_proo
     for (size_t b = 0; b < n_proofs; b++)
       ZK_HIP(ctx, hipMemcpyAsync(w->d_inputs + b * ni, inputs[b], (size_t)ni * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
   }
-  return wit_finish(ctx, wit_run(ctx, w, n_proofs, w->d_inputs, ni, true, d_advice, advice_stride, flags, max_scratch_bytes, publics_out));
+  return zk_quiet_if_refused(ctx, wit_run(ctx, w, n_proofs, w->d_inputs, ni, true, d_advice, advice_stride, flags, max_scratch_bytes, publics_out));
 }

@@ -1,0 +1,73 @@
+// workspace.hpp — who owns which scratch buffer of an amdzk_ctx, and the one way a reservation is cut into regions.
+// Host-only and free of HIP, like witness.hpp, opening.hpp and verifier.hpp: a plain g++ program can include it
+// (tests/native/workspace_check.cpp).
+//
+// THE RULES. A context (amdzk_ctx: the caller's, or one of its lanes, which is a context of its own with its own eight
+// slots) holds ZK_WS_COUNT grow-only device buffers, handed out by zk_ws_reserve(ctx, slot, bytes, &p), and ONE grow-only
+// pinned host buffer, handed out by zk_pinned_reserve.
+//  * A reservation is a pointer, not a lock: the next reservation of the same slot on the same context gets the same
+//    memory, or — when it asks for more — new memory. Growth waits for the context's stream before it frees, so a device
+//    pointer from an earlier reservation stays good for the work already ENQUEUED with it, and is dead for the host: no
+//    further copy, launch or read may be issued through it.
+//  * Two users of one slot are therefore safe in exactly two cases:
+//      (S) stream order: both only enqueue on the context's stream, and the first one's kernels have the region to
+//          themselves until they have run, because the second one's come behind them;
+//      (N) nesting: the outer user has enqueued its last access to its reservation before it calls the inner one, and does
+//          not touch its own pointer afterwards.
+//    Anything else — an outer user that still reads its region after an inner call reserved the slot — needs another slot.
+//  * The pinned buffer has no stream order to lean on (the host reads it) and growth frees it at once: a pointer into it
+//    is dead after ANY call that may reserve it again. Its users are zk_msm_finish (msm.hip), verify_core (verify.hip),
+//    which has read everything it brought down before its first zk_msm_finish, and zk_pairing_products (pairing.hip),
+//    which calls nothing between its reservation and its last read.
+// The enum says for every shared slot which case holds and where. Nothing checks this at run time: a new driver picks its
+// slot by reading this file.
+#pragma once
+#include <stddef.h>
+
+enum ZkWs : int {
+  // ntt.hip, zk_ntt_ex: the ping-pong buffer of a multi-pass transform. One user.
+  ZK_WS_NTT = 0,
+  // msm.hip: the counting sort, bucket lists and results of zk_msm_dev_xyzz, zk_msm_dev_xyzz_cols and
+  // zk_msm_bases_dev_xyzz. (S) between MSMs — and the results live in the reservation: the caller brings them down
+  // (zk_msm_finish) or copies them on the stream before it enqueues the next MSM on the same context.
+  ZK_WS_MSM = 1,
+  // Staging of the host-pointer entry points (capi.hip: amdzk_msm_g1_batch, _cols_dev, _bases_batch, amdzk_ntt_fr, _batch),
+  // which return with the stream idle. Two more users:
+  //  * the lock-step batch's pointer tables (prover.hip, Gang::scratch) — (S) among its own steps; no proof calls a
+  //    host-pointer entry point, so the first group never runs inside it;
+  //  * srs_check_run (srs.hip) — it cannot use ZK_WS_STARTUP, its unit's slot: it still reads its column of combined
+  //    points after zk_pairing_products has reserved that one. Nothing it calls touches this slot.
+  ZK_WS_STAGING = 2,
+  // The start-up calls: SRS setup, read, write, g_to_lagrange, downsize and the prefix-sum basis (srs.hip), (S) one behind
+  // the other. Also verify_core (verify.hip) and zk_pairing_products (pairing.hip) — (N): amdzk_verify_proofs_decide pairs
+  // after verify_core has returned, having read all it brought down, and no start-up call runs inside either.
+  ZK_WS_STARTUP = 3,
+  // zk_poly_eval, zk_lincomb, zk_kate_div (plonk_kernels.hip): partial sums that live for two launches. (S).
+  ZK_WS_OPENING = 4,
+  // amdzk_permute_expression_pair_dev (prover.hip). One user.
+  ZK_WS_PERMUTE = 5,
+  // Pointer and scalar tables that go up with a call: upload_ptrs_and_frs (plonk_kernels.hip), amdzk_multiopen_dev and
+  // mo_verify_body (multiopen.hip). (S) between calls; amdzk_multiopen_dev hands zk_poly_eval, zk_lincomb and zk_kate_div
+  // tables out of ITS reservation and never goes through upload_ptrs_and_frs.
+  ZK_WS_TABLES = 6,
+  // amdzk_batch_invert_dev, amdzk_batch_invert_assigned_dev, amdzk_grand_product_dev (plonk_kernels.hip). (S).
+  ZK_WS_CALLS = 7,
+  ZK_WS_COUNT = 8
+};
+
+// v rounded up to a multiple of a (a > 0). The one rounding function of the library's byte layouts and element counts.
+constexpr size_t ws_round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// The byte layout of one reservation: an offset counter. take() returns where the region starts and moves on to the next
+// multiple of `pad` behind it; pad = 1 lets the next region follow without a gap. bytes(): the total so far.
+struct WsLayout {
+  size_t take(size_t bytes, size_t pad = 256) {
+    const size_t at = off;
+    off = ws_round_up(off + bytes, pad);
+    return at;
+  }
+  size_t bytes() const { return off; }
+
+ private:
+  size_t off = 0;
+};
