@@ -403,7 +403,7 @@ int amdzk_srs_setup(amdzk_ctx* ctx, uint32_t k, const uint64_t s[4], amdzk_srs**
   uint64_t omega[4];
   amdzk_domain_constant(dom, 0, omega);
   amdzk_domain_free(ctx, dom);
-  return zk_srs_setup(ctx, k, s, omega, out, g_out, g_lagrange_out);
+  return zk_quiet_if_refused(ctx, zk_srs_setup(ctx, k, s, omega, out, g_out, g_lagrange_out));
 }
 static int fft_constants(amdzk_ctx* ctx, uint32_t k, uint64_t omega_inv[4], uint64_t n_inv[4]) {
   amdzk_domain* dom = nullptr;

@@ -169,6 +169,11 @@ int zk_srs_setup(amdzk_ctx* ctx, uint32_t k, const uint64_t s_mont[4], const uin
   Fr s, omega;
   memcpy(s.l, s_mont, 32);
   memcpy(omega.l, omega_mont, 32);
+  // Two trapdoors mean nothing. Words at or above r are no field element. With s^n = 1, s is a point omega^i of the domain:
+  // s - omega^i = 0 has no inverse and (s^n - 1) / n = 0, so every L_i would come out 0 (upstream panics in invert().unwrap()).
+  if (!is_canonical(s)) ZK_FAIL(ctx, AMDZK_E_INVALID, "srs_setup: s is not below the modulus (s >= r)");
+  const Fr sn_minus_1 = sub(pow_u64(s, n), Fr::one());
+  if (sn_minus_1.is_zero()) ZK_FAIL(ctx, AMDZK_E_INVALID, "srs_setup: s^n = 1 for n = 2^%u: s is a point of the domain, the Lagrange basis has no value there", k);
   // workspace: gtable[256] | scal[n] | w[n] | scratch[n] | g[n] | gl[n]
   char* ws = nullptr;
   const size_t bytes = 256 * sizeof(G1Affine) + 3 * n * sizeof(Fr) + 2 * n * sizeof(G1Affine);
@@ -199,7 +204,7 @@ int zk_srs_setup(amdzk_ctx* ctx, uint32_t k, const uint64_t s_mont[4], const uin
   ZK_LAUNCH(ctx, "srs_sub", sub_from_const_kernel, eg, eb, 0, scal, w, s, n);
   ZK_TRY(zk_batch_invert(ctx, scal, scratch, n));
   Fr two = add(Fr::one(), Fr::one());
-  Fr mult = mul(sub(pow_u64(s, n), Fr::one()), inv(pow_u64(two, k)));  // (s^n - 1) / n
+  Fr mult = mul(sn_minus_1, inv(pow_u64(two, k)));  // (s^n - 1) / n
   ZK_LAUNCH(ctx, "srs_mul2", mul2_kernel, eg, eb, 0, scal, w, mult, n);
   ZK_LAUNCH(ctx, "srs_fixed_base_mul", fixed_base_mul_kernel, eg, eb, 0, scal, gtab, gl, n);
   if (g_out) ZK_HIP(ctx, hipMemcpyAsync(g_out, g, n * sizeof(G1Affine), hipMemcpyDeviceToHost, ctx->stream));

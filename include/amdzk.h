@@ -123,7 +123,11 @@ int amdzk_srs_upload(amdzk_ctx* ctx, const uint64_t* g, const uint64_t* g_lagran
                      amdzk_srs** out);
 /* ParamsKZG::setup(k, rng) [UP] with the trapdoor s supplied by the caller (as unsafe as upstream's
  * setup: tests and benchmarks only): g[i] = s^i G, g_lagrange[i] = L_i(s) G, built on the device.
- * g_out / g_lagrange_out (2^k G1Affine each, host) may be NULL. */
+ * g_out / g_lagrange_out (2^k G1Affine each, host) may be NULL.
+ * s: four Montgomery words. Refused with AMDZK_E_INVALID, *out untouched and the ctx usable afterwards:
+ *   - s >= r as words: no field element;
+ *   - s^n = 1 (n = 2^k; s = 1 at every k): s is a point omega^i of the domain, s - omega^i has no inverse and
+ *     every L_i(s) would come out 0. Upstream panics there (invert().unwrap()). */
 int amdzk_srs_setup(amdzk_ctx* ctx, uint32_t k, const uint64_t s[4], amdzk_srs** out, uint64_t* g_out,
                     uint64_t* g_lagrange_out);
 /* ParamsKZG::{write, read} [UP]: k (u32 LE) | n x g | n x g_lagrange (halo2curves 32-byte compressed

@@ -563,6 +563,7 @@ class ParamsKZG {
     ctx_.check(amdzk_srs_upload(ctx_.get(), (const uint64_t*)g, (const uint64_t*)g_lagrange, k, &h_));
   }
   // ParamsKZG::setup(k, rng) with the trapdoor given explicitly (tests / benchmarks, as unsafe as upstream's).
+  // Throws for s >= r and for s^n = 1 (amdzk_srs_setup).
   static ParamsKZG setup(const Context& ctx, uint32_t k, const Fr& s) {
     amdzk_srs* h = nullptr;
     ctx.check(amdzk_srs_setup(ctx.get(), k, s.l, &h, nullptr, nullptr));
