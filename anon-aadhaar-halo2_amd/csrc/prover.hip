@@ -17,6 +17,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <deque>
 #include <map>
 #include <memory>
 #include <string>
@@ -373,6 +374,11 @@ struct Prover {
   // Member of a gang (serial, one instance): commit_begin / commit_write leave their batch here instead of launching it
   std::vector<DeferredCommit>* sink = nullptr;
   Commit cm_adv, cm_lk;                     // the advice and permuted-lookup batches between their two halves (advice_enqueue / _write)
+  // a phased key between phases_begin and the last phase_write: the challenges so far (zero: not yet squeezed), the advice
+  // columns of the phases below and of the phase in flight, and that phase's batches, one per (instance, run of columns)
+  std::vector<Fr> chal;
+  size_t adv_before = 0, adv_in_phase = 0;
+  std::deque<Commit> cm_phase;
   std::vector<const Fr*> ev_pp;             // evaluations_prepare: the (polynomial, point) pairs
   std::vector<Fr> ev_pts;
   const bool ttrace = getenv("AMDZK_TRACE_TIME") != nullptr;
@@ -536,51 +542,71 @@ struct Prover {
   // committed and written; then the phase's challenges are squeezed into their constant slots. Phases >= 1 start with the
   // caller's callback, which fills their columns of d_advice from the challenges so far.
   int advice_phased(const void* const* d_advice_all, size_t advice_stride) {
-    const uint32_t NCH = K.num_challenges;
-    std::vector<Fr> chal(NCH, Fr::zero());
-    for (uint32_t i = 0; i < NCH; i++) ZK_TRY(put_challenge(i, chal[i]));  // the last proof's values are gone
-    size_t before = 0;  // advice columns in the phases below p
+    ZK_TRY(phases_begin());
     for (uint32_t p = 0; p < K.nphases; p++) {
-      std::vector<std::pair<uint32_t, uint32_t>> runs;  // (first column, count)
-      size_t in_phase = 0;
-      for (uint32_t c = 0; c < A; c++)
-        if (K.advice_phase[c] == p) {
-          if (!runs.empty() && runs.back().first + runs.back().second == c) runs.back().second++;
-          else runs.push_back({c, 1});
-          in_phase++;
-        }
       if (p > 0) {
-        const int r = phase_fn(phase_user, p, (const uint64_t*)chal.data(), NCH, (void*)ctx->stream);
+        const int r = phase_fn(phase_user, p, (const uint64_t*)chal.data(), K.num_challenges, (void*)ctx->stream);
         if (r != 0) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: the phase callback returned %d in phase %u", r, p);
       }
-      for (size_t ci = 0; ci < NC; ci++) {
-        amdzk_pk* const pk = pks[ci];
-        size_t j0 = 0;  // position of the run's first column among the phase's columns
-        for (auto& run : runs) {
-          const uint32_t c0 = run.first, cnt = run.second;
-          Fr* const cols = pk->adv() + (size_t)c0 * n;
-          ZK_HIP(ctx, hipMemcpy2DAsync(cols, n * 32, (const Fr*)d_advice_all[ci] + (size_t)c0 * advice_stride, advice_stride * 32, n * 32, cnt,
-                                       hipMemcpyDeviceToDevice, ctx->stream));
-          ZK_TRY(blind(M, cols, cnt, usable, bf + 1, draws.advice_phase(NC, before, in_phase, ci) + j0 * draws.col, draws.col));
-          Commit cm;
-          if (!serial) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, cols, cnt, cm));
-          ZK_TRY(transforms_on_B(pk, M, c0, cnt, cm.begun));
-          if (!cm.begun) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, cols, cnt, cm));
-          ZK_TRY(commit_end(cm));
-          ZK_TRY(write_points(cm.pts, "advice"));
-          j0 += cnt;
-        }
-        if (p == 0) ZK_TRY(transforms_on_B(pk, M, A, I));  // the instance columns ride with the first phase
-      }
-      for (uint32_t i = 0; i < NCH; i++)
-        if (K.challenge_phase[i] == p) {
-          chal[i] = challenge("phase challenge");
-          ZK_TRY(put_challenge(i, chal[i]));
-        }
-      before += in_phase;
+      ZK_TRY(phase_enqueue(p, d_advice_all, advice_stride));
+      ZK_TRY(phase_write(p));
     }
     ZK_TRY(commit_end(cm_rnd));
     tick("advice (phased)");
+    return AMDZK_OK;
+  }
+  // ... phase by phase in two halves, so that a gang (amdzk_create_proof_batch_opts) commits a phase's batches of all its
+  // provers between them and calls its own callback in front: the challenges start at zero (the last proof's values are
+  // gone); [the callback]; the phase's runs of columns copied in, blinded, transformed and their commitments launched —
+  // one batch per run, finished at once on this path (a context holds one batch's result at a time), handed to the gang
+  // with a sink; then the points written in that order and the phase's challenges squeezed.
+  int phases_begin() {
+    chal.assign(K.num_challenges, Fr::zero());
+    for (uint32_t i = 0; i < K.num_challenges; i++) ZK_TRY(put_challenge(i, chal[i]));
+    adv_before = 0;
+    return AMDZK_OK;
+  }
+  int phase_enqueue(uint32_t p, const void* const* d_advice_all, size_t advice_stride) {
+    std::vector<std::pair<uint32_t, uint32_t>> runs;  // (first column, count)
+    size_t in_phase = 0;
+    for (uint32_t c = 0; c < A; c++)
+      if (K.advice_phase[c] == p) {
+        if (!runs.empty() && runs.back().first + runs.back().second == c) runs.back().second++;
+        else runs.push_back({c, 1});
+        in_phase++;
+      }
+    cm_phase.clear();
+    for (size_t ci = 0; ci < NC; ci++) {
+      amdzk_pk* const pk = pks[ci];
+      size_t j0 = 0;  // position of the run's first column among the phase's columns
+      for (auto& run : runs) {
+        const uint32_t c0 = run.first, cnt = run.second;
+        Fr* const cols = pk->adv() + (size_t)c0 * n;
+        ZK_HIP(ctx, hipMemcpy2DAsync(cols, n * 32, (const Fr*)d_advice_all[ci] + (size_t)c0 * advice_stride, advice_stride * 32, n * 32, cnt,
+                                     hipMemcpyDeviceToDevice, ctx->stream));
+        ZK_TRY(blind(M, cols, cnt, usable, bf + 1, draws.advice_phase(NC, adv_before, in_phase, ci) + j0 * draws.col, draws.col));
+        cm_phase.emplace_back();
+        Commit& cm = cm_phase.back();
+        if (!serial) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, cols, cnt, cm));
+        ZK_TRY(transforms_on_B(pk, M, c0, cnt, cm.begun));
+        if (!cm.begun) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, cols, cnt, cm));
+        if (!sink) ZK_TRY(commit_end(cm));
+        j0 += cnt;
+      }
+      if (p == 0) ZK_TRY(transforms_on_B(pk, M, A, I));  // the instance columns ride with the first phase
+    }
+    adv_in_phase = in_phase;
+    return AMDZK_OK;
+  }
+  int phase_write(uint32_t p) {
+    for (auto& cm : cm_phase) ZK_TRY(write_points(cm.pts, "advice"));
+    cm_phase.clear();
+    for (uint32_t i = 0; i < K.num_challenges; i++)
+      if (K.challenge_phase[i] == p) {
+        chal[i] = challenge("phase challenge");
+        ZK_TRY(put_challenge(i, chal[i]));
+      }
+    adv_before += adv_in_phase;
     return AMDZK_OK;
   }
   // 1. advice: copy in, blind the unusable rows of every column, commit
@@ -1019,10 +1045,11 @@ int create_proof_impl(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t ncirc, const 
 }
 
 
-// amdzk_create_proof_batch: B independent proofs of one circuit advanced in lock-step on the caller's stream. Every member
-// is a Prover of its own (one instance, no lanes) with its own transcript, random source and workspace, and walks
+// amdzk_create_proof_batch / _batch_opts: B independent proofs — of one circuit, or of different circuits on one SRS —
+// advanced in lock-step on the caller's stream. Every member
+// is a Prover of its own (one instance, no lanes) with its own key, transcript, random source and workspace, and walks
 // create_proof_body's steps in their order; what the members of a step have in common is done once for all of them:
-//   * every commitment step — the random polynomial, advice, A' / S', the permutation and lookup products (together),
+//   * every commitment step — the random polynomial, advice (per challenge phase: one step each), A' / S', the permutation and lookup products (together),
 //     the h pieces, SHPLONK's two or GWC's witnesses — is ONE pointer-table MSM (zk_msm_dev_xyzz_cols) over the live
 //     members' columns, one host wait and one download, the points handed back per member (DeferredCommit);
 //   * the lookup permutations' error words are read behind that step's wait;
@@ -1038,6 +1065,7 @@ struct Gang {
     amdzk_pk* pk = nullptr;
     zkhost::Blake2bWrite t_blake;
     zkhost::Keccak256Write t_keccak;
+    std::unique_ptr<zkhost::CallbackWrite> t_caller;  // amdzk_batch_proof_opts::transcripts[index], if the proof has one
     RandomSource rng;
     std::unique_ptr<Prover> P;
     std::vector<DeferredCommit> deferred;
@@ -1066,9 +1094,16 @@ struct Gang {
       if (!m->live) continue;
       const int r = f(*m);
       if (r != AMDZK_OK) fail(*m, r);
+      else transcript_ok(*m);
       if (fatal != AMDZK_OK) return fatal;
     }
     return AMDZK_OK;
+  }
+  // a caller-owned transcript that reported an error ends its proof at the step boundary
+  void transcript_ok(Member& m) {
+    if (!m.live || !m.T().failed) return;
+    ctx->err = "create_proof: the caller's transcript reported an error";
+    fail(m, AMDZK_E_INVALID);
   }
   size_t live() const {
     size_t c = 0;
@@ -1125,8 +1160,39 @@ struct Gang {
         }
       }
     }
-    for (auto& m : members) m->deferred.clear();
+    for (auto& m : members) {
+      m->deferred.clear();
+      transcript_ok(*m);
+    }
     return fatal;
+  }
+
+  // The callback of phase p >= 1 (amdzk_batch_phase_fn), once for the whole batch, if some live member's key has the phase.
+  // The gang holds nothing across it: its device scratch is per step, and every member's work is on the stream.
+  int phase_callback(uint32_t p, amdzk_batch_phase_fn fn, void* user, size_t challenge_stride) {
+    const size_t N = members.size();
+    std::vector<uint8_t> wanted(N, 0);
+    std::vector<uint64_t> ch(std::max<size_t>(4 * N * challenge_stride, 1), 0);
+    std::vector<int> rc(N, 0);
+    bool any = false;
+    for (auto& m : members)
+      if (m->live && m->pk->key->nphases > p) {
+        wanted[m->index] = 1;
+        any = true;
+        if (!m->P->chal.empty()) memcpy(&ch[4 * m->index * challenge_stride], m->P->chal.data(), m->P->chal.size() * 32);
+      }
+    if (!any) return AMDZK_OK;
+    const int r = fn(user, p, N, wanted.data(), ch.data(), challenge_stride, rc.data(), (void*)ctx->stream);
+    for (auto& m : members) {
+      if (!m->live) continue;
+      char b[160];
+      if (r != 0 && wanted[m->index]) snprintf(b, sizeof(b), "create_proof: the phase callback returned %d in phase %u", r, p);
+      else if (r == 0 && rc[m->index] != 0) snprintf(b, sizeof(b), "create_proof: the phase callback refused it in phase %u", p);
+      else continue;
+      ctx->err = b;
+      fail(*m, AMDZK_E_INVALID);
+    }
+    return AMDZK_OK;
   }
 
   // all live members' evaluations (Prover::evaluations_prepare left the pairs) in one launch, one wait, one download
@@ -1166,8 +1232,11 @@ struct Gang {
     if (_g != AMDZK_OK) return _g;       \
   } while (0)
   // create_proof_body's steps, each for all live members
+  // phases: the largest phase count among the members' keys (1: no key has later phases); the members of a phased key walk
+  // Prover::advice_phased's halves, phase after phase with ONE submission each, the others commit their advice with phase 0
+  // and sit the later phases out
   int run(const uint64_t* const* const* instances, const size_t* const* instance_lens, const void* const* d_advice, size_t advice_stride,
-          bool use_gwc) {
+          bool use_gwc, uint32_t phases = 1, amdzk_batch_phase_fn phase_fn = nullptr, void* phase_user = nullptr, size_t challenge_stride = 0) {
     GANG_TRY(each([&](Member& m) -> int {
       const uint64_t* const* inst = instances ? instances[m.index] : nullptr;
       const size_t* lens = instance_lens ? instance_lens[m.index] : nullptr;
@@ -1175,10 +1244,21 @@ struct Gang {
       return m.P->random_poly();
     }));
     GANG_TRY(commit_step());  // the random polynomials (basis g)
-    GANG_TRY(each([&](Member& m) -> int { return m.P->advice_enqueue(0, d_advice ? d_advice[m.index] : nullptr, advice_stride); }));
-    GANG_TRY(commit_step());
+    for (uint32_t p = 0; p < phases; p++) {
+      if (p > 0) GANG_TRY(phase_callback(p, phase_fn, phase_user, challenge_stride));
+      GANG_TRY(each([&](Member& m) -> int {
+        const void* adv = d_advice ? d_advice[m.index] : nullptr;
+        if (!m.pk->key->phased()) return p == 0 ? m.P->advice_enqueue(0, adv, advice_stride) : AMDZK_OK;
+        if (p == 0) ZK_TRY(m.P->phases_begin());
+        return p < m.pk->key->nphases ? m.P->phase_enqueue(p, &adv, advice_stride) : AMDZK_OK;
+      }));
+      GANG_TRY(commit_step());
+      GANG_TRY(each([&](Member& m) -> int {
+        if (!m.pk->key->phased()) return p == 0 ? m.P->advice_write() : AMDZK_OK;
+        return p < m.pk->key->nphases ? m.P->phase_write(p) : AMDZK_OK;
+      }));
+    }
     GANG_TRY(each([&](Member& m) -> int {
-      ZK_TRY(m.P->advice_write());
       const Fr theta = m.P->challenge("theta");
       ZK_TRY(m.P->put_consts({{&KeyMaterial::c_theta, theta}}));
       return m.P->lookups_enqueue(0);
@@ -1330,6 +1410,63 @@ int amdzk_create_proof_opts(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_circu
                            proof_len, ex);
 }
 
+// What amdzk_create_proof_batch_opts adds to a batch: per-proof transcripts of the caller's and the batch's phase callback.
+struct BatchExtras {
+  const amdzk_transcript* const* transcripts = nullptr;
+  amdzk_batch_phase_fn phase_fn = nullptr;
+  void* phase_user = nullptr;
+};
+
+// The body of both batch entry points, behind their refusals: one Gang member per proof, the run, and every proof's bytes,
+// length and status. A proof with a transcript of its own has length 0: the bytes are its caller's.
+static int prove_gang(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_proofs, const uint64_t* const* const* instances,
+                      const size_t* const* instance_lens, const void* const* d_advice, size_t advice_stride, int transcript_kind,
+                      const uint64_t* rng_seeds, const uint64_t* const* scalars, const BatchExtras& ex, uint8_t* proofs_out, size_t proof_stride,
+                      size_t* proof_lens, int* statuses) {
+  const bool use_gwc = (transcript_kind & AMDZK_MULTIOPEN_GWC) != 0;
+  const int kind = transcript_kind & ~AMDZK_MULTIOPEN_GWC;
+  Gang g(ctx);
+  uint32_t phases = 1;
+  size_t challenge_stride = 0;
+  for (size_t b = 0; b < n_proofs; b++) {
+    std::unique_ptr<Gang::Member> m(new Gang::Member);
+    m->index = b;
+    m->pk = pks[b];
+    phases = std::max(phases, pks[b]->key->nphases);
+    challenge_stride = std::max<size_t>(challenge_stride, pks[b]->key->num_challenges);
+    if (scalars) m->rng.scalars = scalars[b];
+    else m->rng = RandomSource(rng_seeds[b]);
+    if (ex.transcripts && ex.transcripts[b]) m->t_caller.reset(new zkhost::CallbackWrite(*ex.transcripts[b]));
+    zkhost::TranscriptWrite& T = m->t_caller                          ? (zkhost::TranscriptWrite&)*m->t_caller
+                                 : kind == AMDZK_TRANSCRIPT_BLAKE2B ? (zkhost::TranscriptWrite&)m->t_blake
+                                                                     : (zkhost::TranscriptWrite&)m->t_keccak;
+    m->P.reset(new Prover(ctx, &pks[b], 1, ctx, ctx, T, m->rng));  // B = C = ctx: one stream, no lanes
+    m->P->sink = &m->deferred;
+    g.members.push_back(std::move(m));
+  }
+  const int run = g.run(instances, instance_lens, d_advice, advice_stride, use_gwc, phases, ex.phase_fn, ex.phase_user, challenge_stride);
+  int first = AMDZK_OK;
+  std::string first_err;
+  for (auto& m : g.members) {
+    if (m->live && run != AMDZK_OK) {  // the batch ended under it
+      m->live = false;
+      m->status = run;
+      m->err = ctx->err;
+    }
+    if (m->live && m->T().proof.size() > proof_stride) {  // (cannot happen: amdzk_proof_size is exact)
+      m->live = false;
+      m->status = AMDZK_E_INVALID;
+      m->err = "proof " + std::to_string(m->index) + ": create_proof: proof buffer too small";
+    }
+    if (statuses) statuses[m->index] = m->status;
+    proof_lens[m->index] = m->live ? m->T().proof.size() : 0;
+    if (m->live && !m->T().proof.empty()) memcpy(proofs_out + m->index * proof_stride, m->T().proof.data(), m->T().proof.size());
+    else if (!m->live && first == AMDZK_OK) first = m->status, first_err = m->err;
+  }
+  if (first != AMDZK_OK) ctx->err = first_err;
+  return zk_quiet_if_refused(ctx, first, true);  // a failed proof may have left work behind: the workspaces must be quiet before they are used again
+}
+
 // n_proofs independent proofs of one circuit from one host thread, advanced in lock-step (Gang above). pks[b]: proof b's
 // workspace — the key or workspace clones of it, pairwise different. Bytes: those of n_proofs amdzk_create_proof_ex /
 // amdzk_create_proof_scalars calls.
@@ -1352,7 +1489,6 @@ static int proof_batch(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_proofs, co
   if (K.phased())
     ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "create_proof_batch: the key has challenge phases or challenges: prove it with amdzk_create_proof_opts");
   if (advice_stride < K.n) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: advice stride < n");
-  const bool use_gwc = (opts->transcript_kind & AMDZK_MULTIOPEN_GWC) != 0;
   const int kind = opts->transcript_kind & ~AMDZK_MULTIOPEN_GWC;
   if (kind != AMDZK_TRANSCRIPT_BLAKE2B && kind != AMDZK_TRANSCRIPT_KECCAK256_EVM)
     ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: unknown transcript kind %d", kind);
@@ -1362,39 +1498,9 @@ static int proof_batch(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_proofs, co
     ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: %zu scalars given, %zu needed", opts->scalar_count, DrawLayout(K, 1).total);
 
   *ran = true;
-  Gang g(ctx);
-  for (size_t b = 0; b < n_proofs; b++) {
-    std::unique_ptr<Gang::Member> m(new Gang::Member);
-    m->index = b;
-    m->pk = pks[b];
-    if (opts->scalars) m->rng.scalars = opts->scalars[b];
-    else m->rng = RandomSource(opts->rng_seeds[b]);
-    zkhost::TranscriptWrite& T = kind == AMDZK_TRANSCRIPT_BLAKE2B ? (zkhost::TranscriptWrite&)m->t_blake : (zkhost::TranscriptWrite&)m->t_keccak;
-    m->P.reset(new Prover(ctx, &pks[b], 1, ctx, ctx, T, m->rng));  // B = C = ctx: one stream, no lanes
-    m->P->sink = &m->deferred;
-    g.members.push_back(std::move(m));
-  }
-  const int run = g.run(instances, instance_lens, d_advice, advice_stride, use_gwc);
-  int first = AMDZK_OK;
-  std::string first_err;
-  for (auto& m : g.members) {
-    if (m->live && run != AMDZK_OK) {  // the batch ended under it
-      m->live = false;
-      m->status = run;
-      m->err = ctx->err;
-    }
-    if (m->live && m->T().proof.size() > proof_stride) {  // (cannot happen: amdzk_proof_size is exact)
-      m->live = false;
-      m->status = AMDZK_E_INVALID;
-      m->err = "proof " + std::to_string(m->index) + ": create_proof: proof buffer too small";
-    }
-    if (statuses) statuses[m->index] = m->status;
-    proof_lens[m->index] = m->live ? m->T().proof.size() : 0;
-    if (m->live) memcpy(proofs_out + m->index * proof_stride, m->T().proof.data(), m->T().proof.size());
-    else if (first == AMDZK_OK) first = m->status, first_err = m->err;
-  }
-  if (first != AMDZK_OK) ctx->err = first_err;
-  return zk_quiet_if_refused(ctx, first, true);  // a failed proof may have left work behind: the workspaces must be quiet before they are used again
+  BatchExtras ex;
+  return prove_gang(ctx, pks, n_proofs, instances, instance_lens, d_advice, advice_stride, opts->transcript_kind, opts->rng_seeds, opts->scalars, ex,
+                    proofs_out, proof_stride, proof_lens, statuses);
 }
 int amdzk_create_proof_batch(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_proofs, const uint64_t* const* const* instances,
                              const size_t* const* instance_lens, const void* const* d_advice, size_t advice_stride,
@@ -1404,6 +1510,72 @@ int amdzk_create_proof_batch(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_proo
   bool ran = false;
   const int r = proof_batch(ctx, pks, n_proofs, instances, instance_lens, d_advice, advice_stride, opts, proofs_out, proof_stride, proof_lens,
                             statuses, &ran);
+  if (!ran)  // refused as a whole: no proof was started, and every proof says so
+    for (size_t b = 0; b < n_proofs; b++) {
+      if (statuses) statuses[b] = r;
+      if (proof_lens) proof_lens[b] = 0;
+    }
+  return r;
+}
+
+// amdzk_create_proof_batch for what it refuses: keys with challenge phases, proofs with the caller's transcript, and different
+// circuits on one SRS (include/amdzk.h). Its refusals; the proofs are prove_gang's.
+static int proof_batch_opts(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_proofs, const uint64_t* const* const* instances,
+                            const size_t* const* instance_lens, const void* const* d_advice, size_t advice_stride, const amdzk_batch_proof_opts* opts,
+                            uint8_t* proofs_out, size_t proof_stride, size_t* proof_lens, int* statuses, bool* ran) {
+#define WHO "create_proof_batch_opts: "
+  if (!pks || n_proofs == 0) ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "no proofs");
+  if (!opts || !proof_lens) ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "null argument");
+  if (opts->size < sizeof(amdzk_batch_proof_opts))
+    ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "amdzk_batch_proof_opts.size is %zu, this library needs %zu", opts->size, sizeof(amdzk_batch_proof_opts));
+  if (!opts->rng_seeds && !opts->scalars) ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "neither rng_seeds nor scalars");
+  const int kind = opts->transcript_kind & ~AMDZK_MULTIOPEN_GWC;
+  size_t psize = 0;
+  bool builtin = false;
+  for (size_t b = 0; b < n_proofs; b++) {
+    if (!pks[b]) ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "null key (proof %zu)", b);
+    const KeyMaterial& K = *pks[b]->key;
+    if (K.srs != pks[0]->key->srs)
+      ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "proof %zu's key was made on another amdzk_srs than proof 0's: the batch commits over one SRS", b);
+    for (size_t d = 0; d < b; d++)
+      if (pks[d] == pks[b]) ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "proofs %zu and %zu share one workspace", d, b);
+    if (K.A && (!d_advice || !d_advice[b])) ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "null advice (proof %zu)", b);
+    if (opts->scalars && !opts->scalars[b]) ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "null scalars (proof %zu)", b);
+    if (K.nphases > 1 && !opts->phase_fn)
+      ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "proof %zu's key has advice in %u phases: a phase callback is needed", b, K.nphases);
+    if (advice_stride < K.n) ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "advice stride < n");
+    if (opts->scalars && opts->scalar_count < DrawLayout(K, 1).total)
+      ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "%zu scalars given, proof %zu needs %zu", opts->scalar_count, b, DrawLayout(K, 1).total);
+    const amdzk_transcript* t = opts->transcripts ? opts->transcripts[b] : nullptr;
+    if (t && (!t->common_point || !t->common_scalar || !t->write_point || !t->write_scalar || !t->squeeze_challenge))
+      ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "amdzk_transcript of proof %zu has a null member", b);
+    if (!t) {
+      builtin = true;
+      psize = std::max(psize, amdzk_proof_size(pks[b], opts->transcript_kind));
+    }
+  }
+  if (builtin) {
+    if (kind != AMDZK_TRANSCRIPT_BLAKE2B && kind != AMDZK_TRANSCRIPT_KECCAK256_EVM) ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "unknown transcript kind %d", kind);
+    if (!proofs_out) ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "null argument");
+    if (proof_stride < psize) ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "proof_stride %zu < proof size %zu", proof_stride, psize);
+  }
+#undef WHO
+  *ran = true;
+  BatchExtras ex;
+  ex.transcripts = opts->transcripts;
+  ex.phase_fn = opts->phase_fn;
+  ex.phase_user = opts->phase_user;
+  return prove_gang(ctx, pks, n_proofs, instances, instance_lens, d_advice, advice_stride, opts->transcript_kind, opts->scalars ? nullptr : opts->rng_seeds,
+                    opts->scalars, ex, proofs_out, proof_stride, proof_lens, statuses);
+}
+int amdzk_create_proof_batch_opts(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_proofs, const uint64_t* const* const* instances,
+                                  const size_t* const* instance_lens, const void* const* d_advice, size_t advice_stride,
+                                  const amdzk_batch_proof_opts* opts, uint8_t* proofs_out, size_t proof_stride, size_t* proof_lens, int* statuses) {
+  ZK_ENTER(ctx);
+  if (!ctx) return AMDZK_E_INVALID;
+  bool ran = false;
+  const int r = proof_batch_opts(ctx, pks, n_proofs, instances, instance_lens, d_advice, advice_stride, opts, proofs_out, proof_stride, proof_lens,
+                                 statuses, &ran);
   if (!ran)  // refused as a whole: no proof was started, and every proof says so
     for (size_t b = 0; b < n_proofs; b++) {
       if (statuses) statuses[b] = r;

@@ -34,7 +34,9 @@ enum ZkWs : int {
   // Staging of the host-pointer entry points (capi.hip: amdzk_msm_g1_batch, _cols_dev, _bases_batch, amdzk_ntt_fr, _batch),
   // which return with the stream idle. Two more users:
   //  * the lock-step batch's pointer tables (prover.hip, Gang::scratch) — (S) among its own steps; no proof calls a
-  //    host-pointer entry point, so the first group never runs inside it;
+  //    host-pointer entry point, so the first group never runs inside it; the batch's phase callback
+  //    (amdzk_batch_phase_fn) runs BETWEEN two steps, when the gang has enqueued its last access to the reservation, and
+  //    what it may call — amdzk_witness_run keeps its scratch in its own handle — takes no slot of the ctx anyway;
   //  * srs_check_run (srs.hip) — it cannot use ZK_WS_STARTUP, its unit's slot: it still reads its column of combined
   //    points after zk_pairing_products has reserved that one. Nothing it calls touches this slot.
   ZK_WS_STAGING = 2,

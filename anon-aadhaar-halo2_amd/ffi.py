@@ -102,6 +102,8 @@ def lib():
                                           vp, sz, C.POINTER(sz)]),
         "amdzk_create_proof_batch": (i32, [vp, C.POINTER(vp), sz, C.POINTER(C.POINTER(vp)), C.POINTER(C.POINTER(sz)), C.POINTER(vp), sz, vp,
                                            vp, sz, C.POINTER(sz), C.POINTER(i32)]),
+        "amdzk_create_proof_batch_opts": (i32, [vp, C.POINTER(vp), sz, C.POINTER(C.POINTER(vp)), C.POINTER(C.POINTER(sz)), C.POINTER(vp), sz, vp,
+                                                vp, sz, C.POINTER(sz), C.POINTER(i32)]),
         "amdzk_proof_size_multi": (sz, [vp, sz, i32]),
         "amdzk_proof_random_count": (sz, [vp]),
         "amdzk_proof_size": (sz, [vp, i32]),
@@ -169,7 +171,8 @@ def lib():
     return L
 
 
-# include/amdzk.h: amdzk_phases, amdzk_phase_fn, amdzk_transcript, amdzk_proof_opts, amdzk_batch_opts
+# include/amdzk.h: amdzk_phases, amdzk_phase_fn, amdzk_transcript, amdzk_proof_opts, amdzk_batch_opts, amdzk_batch_phase_fn,
+# amdzk_batch_proof_opts
 class Phases(C.Structure):
     _fields_ = [("num_challenges", C.c_uint32), ("advice_phase", C.c_void_p), ("challenge_phase", C.c_void_p)]
 
@@ -191,6 +194,16 @@ class ProofOpts(C.Structure):
 class BatchOpts(C.Structure):
     _fields_ = [("size", C.c_size_t), ("transcript_kind", C.c_int), ("rng_seeds", C.c_void_p), ("scalars", C.POINTER(C.c_void_p)),
                 ("scalar_count", C.c_size_t)]
+
+
+BATCH_PHASE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_size_t, C.POINTER(C.c_uint8), C.POINTER(C.c_uint64), C.c_size_t,
+                             C.POINTER(C.c_int), C.c_void_p)
+
+
+class BatchProofOpts(C.Structure):
+    _fields_ = [("size", C.c_size_t), ("transcript_kind", C.c_int), ("rng_seeds", C.c_void_p), ("scalars", C.POINTER(C.c_void_p)),
+                ("scalar_count", C.c_size_t), ("transcripts", C.POINTER(C.POINTER(Transcript))), ("phase_fn", BATCH_PHASE_FN),
+                ("phase_user", C.c_void_p)]
 
 
 class MultiopenOpts(C.Structure):

@@ -697,9 +697,9 @@ def blob_desc(data):
             "lookups": lookups, "permutation_columns": perm}
 
 
-def _trampolines(synthesize, tobj, errors):
-    """The C callbacks of amdzk_create_proof_opts around Python callables. An exception is kept in `errors` and turned
-    into a non-zero return (nothing may unwind through the library)."""
+def _guard(errors):
+    """Wrap a Python callable for use as a C callback: an exception is kept in `errors` and turned into a non-zero return
+    (nothing may unwind through the library)."""
     def guard(fn):
         def run(*a):
             try:
@@ -708,7 +708,28 @@ def _trampolines(synthesize, tobj, errors):
                 errors.append(e)
                 return 1
         return run
+    return guard
 
+
+def _write_transcript(tobj, errors):
+    """An amdzk_transcript around the caller's TranscriptWrite object. Returns (struct, keep-alive)."""
+    guard = _guard(errors)
+    words = lambda p, cnt: np.array([p[i] for i in range(cnt)], dtype=np.uint64)
+
+    def squeeze(_user, out):
+        v = np.ascontiguousarray(tobj.squeeze_challenge(), dtype=np.uint64).reshape(4)
+        for i in range(4):
+            out[i] = int(v[i])
+    cbs = [_ffi._T_IN(guard(lambda _u, p: tobj.common_point(words(p, 8)))), _ffi._T_IN(guard(lambda _u, p: tobj.common_scalar(words(p, 4)))),
+           _ffi._T_IN(guard(lambda _u, p: tobj.write_point(words(p, 8)))), _ffi._T_IN(guard(lambda _u, p: tobj.write_scalar(words(p, 4)))),
+           _ffi._T_IN(guard(squeeze))]
+    tr = _ffi.Transcript(None, *cbs)
+    return tr, cbs + [tr]
+
+
+def _trampolines(synthesize, tobj, errors):
+    """The C callbacks of amdzk_create_proof_opts around Python callables (_guard)."""
+    guard = _guard(errors)
     phase_fn = _ffi.PHASE_FN()
     if synthesize is not None:
         def on_phase(_user, phase, ch, nch, stream):
@@ -716,17 +737,8 @@ def _trampolines(synthesize, tobj, errors):
         phase_fn = _ffi.PHASE_FN(guard(on_phase))
     tr, keep = None, [phase_fn]
     if tobj is not None:
-        words = lambda p, cnt: np.array([p[i] for i in range(cnt)], dtype=np.uint64)
-
-        def squeeze(_user, out):
-            v = np.ascontiguousarray(tobj.squeeze_challenge(), dtype=np.uint64).reshape(4)
-            for i in range(4):
-                out[i] = int(v[i])
-        cbs = [_ffi._T_IN(guard(lambda _u, p: tobj.common_point(words(p, 8)))), _ffi._T_IN(guard(lambda _u, p: tobj.common_scalar(words(p, 4)))),
-               _ffi._T_IN(guard(lambda _u, p: tobj.write_point(words(p, 8)))), _ffi._T_IN(guard(lambda _u, p: tobj.write_scalar(words(p, 4)))),
-               _ffi._T_IN(guard(squeeze))]
-        tr = _ffi.Transcript(None, *cbs)
-        keep += cbs + [tr]
+        tr, keep_t = _write_transcript(tobj, errors)
+        keep += keep_t
     return phase_fn, tr, keep
 
 
@@ -813,16 +825,10 @@ def create_proof_multi(ctx, pks, instances_list, d_advice_list, seed, advice_str
     return bytes(buf[: need.value])
 
 
-def create_proof_batch(ctx, pks, instances_list, d_advice_list, seeds, advice_stride=None, transcript=TRANSCRIPT_BLAKE2B, scalars=None,
-                       opts_size=None, proof_stride=None):
-    """amdzk_create_proof_batch: len(pks) independent proofs of one circuit in lock-step on ctx's stream — each step's
-    commitments of all proofs in one MSM, one host wait per step. pks: the key and workspace clones of it; instances_list[b],
-    d_advice_list[b], seeds[b]: proof b's, as for create_proof. scalars: per proof the caller's Fr::random draws
-    (create_proof_with_scalars) instead of seeds. Returns one entry per proof: its bytes — those of create_proof on the
-    same workspace — or the AmdzkError of a proof whose witness failed (the others are unaffected). A refused call
-    raises. opts_size / proof_stride: what to report to the library (tests)."""
+def _batch_args(pks, instances_list, d_advice_list, seeds, scalars):
+    """What both batch entry points take per proof, as ctypes arrays: (keys, instances, instance_lens, d_advice, seeds array or
+    None, scalars pointers or None, scalar count, keep-alive)."""
     N = len(pks)
-    n = 1 << pks[0].desc["k"] if N else 0
     assert len(instances_list) == N and len(d_advice_list) == N
     keep, inst_pp, lens_pp = [], (C.POINTER(C.c_void_p) * max(1, N))(), (C.POINTER(C.c_size_t) * max(1, N))()
     for c, instances in enumerate(instances_list):
@@ -843,14 +849,11 @@ def create_proof_batch(ctx, pks, instances_list, d_advice_list, seeds, advice_st
         sc_ptrs = (C.c_void_p * max(1, N))(*[a.ctypes.data for a in sc])
         sc_count = min(a.shape[0] for a in sc) if sc else 0
         keep += [sc]
-    opts = _ffi.BatchOpts(C.sizeof(_ffi.BatchOpts) if opts_size is None else opts_size, transcript,
-                          sd.ctypes.data if sd is not None and sd.size else None, sc_ptrs, sc_count)
-    stride = proof_stride if proof_stride is not None else (int(ctx.L.amdzk_proof_size(pks[0].h, transcript)) if N else 0)
-    buf = (C.c_uint8 * max(1, stride * N))()
-    lens_out = (C.c_size_t * max(1, N))()
-    st = (C.c_int * max(1, N))()
-    rc = ctx.L.amdzk_create_proof_batch(ctx.h, keys, N, inst_pp, lens_pp, adv, advice_stride or n, C.byref(opts), buf, stride, lens_out, st)
-    del keep
+    return keys, inst_pp, lens_pp, adv, sd, sc_ptrs, sc_count, keep
+
+
+def _batch_results(ctx, rc, N, buf, stride, lens_out, st):
+    """Per proof its bytes or the AmdzkError of a proof that dropped out; a call refused as a whole raises."""
     msg = ctx.L.amdzk_last_error(ctx.h).decode() if rc != 0 else ""
     if rc != 0 and not msg.startswith("proof "):  # refused as a whole, or ended for all by the device: not one proof's failure
         ctx._chk(rc)
@@ -861,6 +864,79 @@ def create_proof_batch(ctx, pks, instances_list, d_advice_list, seeds, advice_st
         else:  # the library keeps the first failing proof's message; a later one gets its index and status
             out.append(_ffi.AmdzkError(st[b], msg if msg.startswith("proof %d:" % b) else "proof %d: failed" % b))
     return out
+
+
+def create_proof_batch(ctx, pks, instances_list, d_advice_list, seeds, advice_stride=None, transcript=TRANSCRIPT_BLAKE2B, scalars=None,
+                       opts_size=None, proof_stride=None):
+    """amdzk_create_proof_batch: len(pks) independent proofs of one circuit in lock-step on ctx's stream — each step's
+    commitments of all proofs in one MSM, one host wait per step. pks: the key and workspace clones of it; instances_list[b],
+    d_advice_list[b], seeds[b]: proof b's, as for create_proof. scalars: per proof the caller's Fr::random draws
+    (create_proof_with_scalars) instead of seeds. Returns one entry per proof: its bytes — those of create_proof on the
+    same workspace — or the AmdzkError of a proof whose witness failed (the others are unaffected). A refused call
+    raises. opts_size / proof_stride: what to report to the library (tests)."""
+    N = len(pks)
+    n = 1 << pks[0].desc["k"] if N else 0
+    keys, inst_pp, lens_pp, adv, sd, sc_ptrs, sc_count, keep = _batch_args(pks, instances_list, d_advice_list, seeds, scalars)
+    opts = _ffi.BatchOpts(C.sizeof(_ffi.BatchOpts) if opts_size is None else opts_size, transcript,
+                          sd.ctypes.data if sd is not None and sd.size else None, sc_ptrs, sc_count)
+    stride = proof_stride if proof_stride is not None else (int(ctx.L.amdzk_proof_size(pks[0].h, transcript)) if N else 0)
+    buf = (C.c_uint8 * max(1, stride * N))()
+    lens_out = (C.c_size_t * max(1, N))()
+    st = (C.c_int * max(1, N))()
+    rc = ctx.L.amdzk_create_proof_batch(ctx.h, keys, N, inst_pp, lens_pp, adv, advice_stride or n, C.byref(opts), buf, stride, lens_out, st)
+    del keep
+    return _batch_results(ctx, rc, N, buf, stride, lens_out, st)
+
+
+def create_proof_batch_opts(ctx, pks, instances_list, d_advice_list, seeds=None, scalars=None, transcript=TRANSCRIPT_BLAKE2B, synthesize=None,
+                            transcript_objects=None, advice_stride=None, opts_size=None, proof_stride=None):
+    """amdzk_create_proof_batch_opts: create_proof_batch for keys with challenge phases, proofs with the caller's transcript
+    and different circuits on one ParamsKZG. pks[b] / instances_list[b] / d_advice_list[b] / seeds[b] / scalars[b]: proof b's.
+    synthesize(phase, wanted (n_proofs,) uint8, challenges (n_proofs, stride, 4) uint64 Montgomery, hip_stream): called once
+    per phase >= 1 for the whole batch, fills that phase's columns of every wanted proof on the device; returns None, a list of
+    per-proof codes (non-zero drops that proof alone) or a non-zero int (drops every wanted proof). transcript_objects: None,
+    or per proof None (the built-in `transcript`) or the caller's TranscriptWrite (create_proof_opts) — that proof's entry is
+    then b"". Returns what create_proof_batch returns: per proof its bytes or the AmdzkError of a proof that dropped out. An
+    exception in a callback is raised once the library has returned. opts_size / proof_stride: what to report (tests)."""
+    N = len(pks)
+    n = 1 << pks[0].desc["k"] if N else 0
+    keys, inst_pp, lens_pp, adv, sd, sc_ptrs, sc_count, keep = _batch_args(pks, instances_list, d_advice_list, seeds, scalars)
+    errors = []
+    guard = _guard(errors)
+    phase_fn = _ffi.BATCH_PHASE_FN()
+    if synthesize is not None:
+        def on_phase(_user, phase, nproofs, wanted, ch, stride, proof_rc, stream):
+            w = np.array([wanted[b] for b in range(nproofs)], dtype=np.uint8)
+            chal = np.array([ch[i] for i in range(4 * nproofs * stride)], dtype=np.uint64).reshape(nproofs, stride, 4)
+            r = synthesize(phase, w, chal, stream)
+            if r is None or isinstance(r, int):
+                return r
+            for b, code in enumerate(r):
+                proof_rc[b] = int(code or 0)
+            return 0
+        phase_fn = _ffi.BATCH_PHASE_FN(guard(on_phase))
+    tr_pp = None
+    if transcript_objects is not None:
+        assert len(transcript_objects) == N
+        tr_pp = (C.POINTER(_ffi.Transcript) * max(1, N))()
+        for b, tobj in enumerate(transcript_objects):
+            if tobj is not None:
+                tr, keep_t = _write_transcript(tobj, errors)
+                keep += keep_t
+                tr_pp[b] = C.pointer(tr)
+    opts = _ffi.BatchProofOpts(C.sizeof(_ffi.BatchProofOpts) if opts_size is None else opts_size, transcript,
+                               sd.ctypes.data if sd is not None and sd.size else None, sc_ptrs, sc_count, tr_pp, phase_fn, None)
+    own = [transcript_objects is not None and transcript_objects[b] is not None for b in range(N)]
+    sizes = [int(ctx.L.amdzk_proof_size(pks[b].h, transcript)) for b in range(N) if not own[b]]
+    stride = proof_stride if proof_stride is not None else max(sizes + [0])
+    buf = (C.c_uint8 * max(1, stride * N))()
+    lens_out = (C.c_size_t * max(1, N))()
+    st = (C.c_int * max(1, N))()
+    rc = ctx.L.amdzk_create_proof_batch_opts(ctx.h, keys, N, inst_pp, lens_pp, adv, advice_stride or n, C.byref(opts), buf, stride, lens_out, st)
+    del keep
+    if errors:
+        raise errors[0]
+    return _batch_results(ctx, rc, N, buf, stride, lens_out, st)
 
 
 CHECK_GATE, CHECK_LOOKUP, CHECK_COPY = 0, 1, 2  # include/amdzk.h AMDZK_CHECK_*

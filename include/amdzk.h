@@ -497,7 +497,7 @@ int amdzk_create_proof_opts(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_circu
  * size = sizeof(amdzk_batch_opts) as the caller compiled it. rng_seeds: n_proofs seeds (ChaCha20Rng::seed_from_u64 each), or
  * scalars: per proof amdzk_proof_random_count(pk) caller-drawn Fr (scalar_count of them each); scalars wins if both are set.
  * Refused with a message, the ctx stays usable: AMDZK_E_UNSUPPORTED for a key with later phases or challenges
- * (amdzk_create_proof_opts proves those); AMDZK_E_INVALID for n_proofs = 0, null arguments, a too-small `size`, duplicate or
+ * (amdzk_create_proof_opts proves those one at a time, amdzk_create_proof_batch_opts as a batch); AMDZK_E_INVALID for n_proofs = 0, null arguments, a too-small `size`, duplicate or
  * foreign workspaces, proof_stride too small, neither seeds nor scalars. A refused call starts no proof and says so for
  * every proof: statuses[b] (if given) = the returned status and proof_lens[b] (if given) = 0 for all b < n_proofs; its
  * message starts with "create_proof_batch:", never with "proof <b>:".
@@ -518,6 +518,58 @@ int amdzk_create_proof_batch(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_proo
                              const void* const* d_advice, size_t advice_stride, const amdzk_batch_opts* opts,
                              uint8_t* proofs_out, size_t proof_stride, size_t* proof_lens /* n_proofs */,
                              int* statuses /* n_proofs, may be NULL */);
+
+/* ---- the lock-step batch for what amdzk_create_proof_batch refuses (ABI 1015): keys with challenge phases, proofs with a
+ * caller-owned transcript, and DIFFERENT circuits in one batch. amdzk_create_proof_batch itself is unchanged.
+ * Keys: pks[b] may be any key or workspace clone on this ctx's device, the handles pairwise different, all keys made on the
+ * SAME amdzk_srs handle (hence the same k). Circuits, phase tables, proof sizes and random counts may differ from proof to
+ * proof: the small circuits' commitments ride in the big one's MSM submissions.
+ * Bytes: proof b's bytes, and the calls its caller's transcript receives, are exactly those of
+ *   amdzk_create_proof_opts(ctx, &pks[b], 1, ..) with seed or scalars b, transcripts[b] and a callback that fills proof b's columns
+ * (a key without phases: amdzk_create_proof_ex). A proof with its own transcript has proof_lens[b] = 0 and status 0.
+ * proof_stride >= the largest amdzk_proof_size among the proofs with a built-in transcript; scalar_count >= every key's
+ * amdzk_proof_random_count. transcript_kind: the built-in kind of the proofs without a transcript of their own; its
+ * AMDZK_MULTIOPEN_GWC bit counts for all proofs.
+ * Order: phases run p = 0 ... P - 1, P the largest phase count in the batch. In phase p every live proof whose key has the
+ * phase copies in, blinds and transforms its columns of the phase; ONE MSM submission and one host wait commit them for the
+ * whole batch; each proof then writes its points and squeezes its own challenges of phase p into its own constant table
+ * (amdzk_pk_inspect(pks[b], 3, ..) afterwards returns proof b's challenges). A proof with fewer phases sits the later ones
+ * out. Behind theta the batch is amdzk_create_proof_batch's. Host waits per batch: that call's, plus P - 1.
+ * amdzk_batch_phase_fn: called once per phase p >= 1 for the WHOLE batch — never per proof — before that phase's copy-in, if
+ * and only if some live proof's key has the phase. wanted[b] = 1: proof b is live and its key has advice columns in `phase`.
+ * challenges: proof b's at challenges + 4 * b * challenge_stride (Montgomery; challenge_stride = the largest num_challenges
+ * among the batch's keys): the values of the phases that have finished, zero elsewhere, all zero for proofs that dropped out
+ * or are not wanted. Work enqueued on hip_stream is ordered before the copy-in. The callback may call, on the same ctx,
+ * amdzk_dev_*, amdzk_upload_fence, amdzk_sync and amdzk_witness_run / amdzk_witness_run_dev on a handle of this ctx (one run
+ * computes a phase's cells of the whole batch, the challenges among its inputs); no proving function on a key of the batch.
+ * proof_rc (n_proofs, zero on entry): a non-zero proof_rc[b] drops proof b alone with AMDZK_E_INVALID ("proof b: .. the phase
+ * callback refused it in phase p"); a non-zero return drops every wanted proof. The other proofs finish with their exact bytes.
+ * transcripts: NULL, or n_proofs entries; a NULL entry = the built-in transcript. All five members must be set (checked up
+ * front). They are called from the calling thread only, proof after proof in ascending b within a step; a non-zero return
+ * drops that proof at the step boundary, as does a refusal to write the identity.
+ * Failures are amdzk_create_proof_batch's: a failing proof gets its status, length 0 and "proof <b>: ..", the others finish —
+ * proof 0 included; HIP and out-of-memory errors end the batch; the workspaces are quiet afterwards.
+ * Refused as a whole with AMDZK_E_INVALID (every status = the returned code, every length 0, the message starts with
+ * "create_proof_batch_opts:"): nulls, n_proofs = 0, a too-small `size`, neither seeds nor scalars, shared workspaces, a key
+ * made on another amdzk_srs (the message names the proof), a key with advice in later phases while phase_fn is NULL, a null
+ * transcript member, advice_stride < n, proof_stride or scalar_count too small, an unknown transcript kind. */
+typedef int (*amdzk_batch_phase_fn)(void* user, uint32_t phase, size_t n_proofs, const uint8_t* wanted, const uint64_t* challenges,
+                                    size_t challenge_stride, int* proof_rc, void* hip_stream);
+typedef struct amdzk_batch_proof_opts {
+  size_t size;
+  int transcript_kind;                        /* built-in kind for proofs without their own transcript; the GWC bit counts for all */
+  const uint64_t* rng_seeds;                  /* n_proofs seeds, or NULL if scalars is set */
+  const uint64_t* const* scalars;             /* optional: per proof, the caller's Fr::random draws */
+  size_t scalar_count;
+  const amdzk_transcript* const* transcripts; /* NULL, or n_proofs entries; a NULL entry = built-in */
+  amdzk_batch_phase_fn phase_fn;              /* NULL: every key must have phase-0 advice only */
+  void* phase_user;
+} amdzk_batch_proof_opts;
+int amdzk_create_proof_batch_opts(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_proofs,
+                                  const uint64_t* const* const* instances, const size_t* const* instance_lens,
+                                  const void* const* d_advice, size_t advice_stride, const amdzk_batch_proof_opts* opts,
+                                  uint8_t* proofs_out, size_t proof_stride, size_t* proof_lens /* n_proofs */,
+                                  int* statuses /* n_proofs, may be NULL */);
 
 /* ---- the PLONK layer function by function: the kernels create_proof runs,
  * callable on their own on device-resident columns — for a fork that replaces upstream one function at a time and
@@ -1016,7 +1068,8 @@ int amdzk_verify_proofs_decide_vk(amdzk_ctx* ctx, const amdzk_vk* vk, const amdz
  *   AMDZK_W_XOR     a b      (canon(a) ^ canon(b)) mod r
  * There is no division by a variable and no op that serves one gadget: those are compositions of the above, or hints.
  * Phase-dependent programs need nothing more: a later phase's program can be run from an amdzk_phase_fn callback with the
- * challenges among its inputs.
+ * challenges among its inputs — for a whole batch, from the amdzk_batch_phase_fn of amdzk_create_proof_batch_opts, which
+ * hands every proof's challenges to ONE call per phase.
  *
  * amdzk_witness_compile validates the description, levelizes it (INPUT and CONST are level 0, every other node is one level
  * above its highest operand), orders the nodes by level, uploads the tables and keeps no pointer into the caller's arrays.

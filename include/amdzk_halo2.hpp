@@ -10,7 +10,8 @@
 //   plonk::{keygen_pk -> ProvingKey, create_proof}
 //   plonk::{Challenge, ConstraintSystem::advice_column_in / challenge_usable_after, Expression::Challenge} and
 //   transcript::TranscriptWrite — challenge phases and a caller-owned transcript (amdzk_keygen_phased,
-//   amdzk_create_proof_opts); create_proof_batch: many independent proofs in lock-step (amdzk_create_proof_batch)
+//   amdzk_create_proof_opts); create_proof_batch: many independent proofs in lock-step (amdzk_create_proof_batch; with
+//   per-proof transcripts, a batch synthesize and different circuits: amdzk_create_proof_batch_opts)
 //
 // Header-only over the C ABI of include/amdzk.h (link libamdzk.so); the same names, argument meaning and
 // derived quantities (query order, degree(), blinding_factors()) as upstream. Everything O(n) runs on
@@ -958,6 +959,17 @@ struct Trampoline {
     }
   }
 };
+// the amdzk_transcript that forwards to tr->t
+inline amdzk_transcript c_transcript(Trampoline* tr) {
+  amdzk_transcript ct;
+  ct.user = tr;
+  ct.common_point = [](void* u, const uint64_t* xy) { auto* t = (Trampoline*)u; return t->guard([&] { G1Affine p; std::memcpy(&p, xy, 64); t->t->common_point(p); }); };
+  ct.common_scalar = [](void* u, const uint64_t* s) { auto* t = (Trampoline*)u; return t->guard([&] { Fr v; std::memcpy(v.l, s, 32); t->t->common_scalar(v); }); };
+  ct.write_point = [](void* u, const uint64_t* xy) { auto* t = (Trampoline*)u; return t->guard([&] { G1Affine p; std::memcpy(&p, xy, 64); t->t->write_point(p); }); };
+  ct.write_scalar = [](void* u, const uint64_t* s) { auto* t = (Trampoline*)u; return t->guard([&] { Fr v; std::memcpy(v.l, s, 32); t->t->write_scalar(v); }); };
+  ct.squeeze_challenge = [](void* u, uint64_t* out) { auto* t = (Trampoline*)u; return t->guard([&] { Fr v = t->t->squeeze_challenge(); std::memcpy(out, v.l, 32); }); };
+  return ct;
+}
 }  // namespace detail
 
 // plonk::create_proof for circuits with challenge phases and / or the caller's own transcript (amdzk_create_proof_opts).
@@ -971,13 +983,7 @@ inline std::vector<uint8_t> create_proof(const Context& ctx, const std::vector<c
   const size_t N = keys.size();
   if (N == 0 || instances.size() != N || d_advice.size() != N) throw Error(AMDZK_E_INVALID, "create_proof: one key, instance set and witness per circuit");
   detail::Trampoline tr{&synthesize, transcript_obj, nullptr};
-  amdzk_transcript ct;
-  ct.user = &tr;
-  ct.common_point = [](void* u, const uint64_t* xy) { auto* t = (detail::Trampoline*)u; return t->guard([&] { G1Affine p; std::memcpy(&p, xy, 64); t->t->common_point(p); }); };
-  ct.common_scalar = [](void* u, const uint64_t* s) { auto* t = (detail::Trampoline*)u; return t->guard([&] { Fr v; std::memcpy(v.l, s, 32); t->t->common_scalar(v); }); };
-  ct.write_point = [](void* u, const uint64_t* xy) { auto* t = (detail::Trampoline*)u; return t->guard([&] { G1Affine p; std::memcpy(&p, xy, 64); t->t->write_point(p); }); };
-  ct.write_scalar = [](void* u, const uint64_t* s) { auto* t = (detail::Trampoline*)u; return t->guard([&] { Fr v; std::memcpy(v.l, s, 32); t->t->write_scalar(v); }); };
-  ct.squeeze_challenge = [](void* u, uint64_t* out) { auto* t = (detail::Trampoline*)u; return t->guard([&] { Fr v = t->t->squeeze_challenge(); std::memcpy(out, v.l, 32); }); };
+  amdzk_transcript ct = detail::c_transcript(&tr);
   amdzk_proof_opts opts;
   std::memset(&opts, 0, sizeof(opts));
   opts.size = sizeof(opts);
@@ -1020,6 +1026,103 @@ inline std::vector<uint8_t> create_proof(const Context& ctx, const std::vector<c
   return proof;
 }
 
+// What `synthesize` of the later phases is for a BATCH (amdzk_batch_phase_fn): called once per phase >= 1 for all proofs
+// together. wanted[b] != 0: proof b is live and its circuit has advice columns in `phase`; challenges[b]: its challenges
+// known so far (those of unfinished phases, and all of a proof that is not wanted, are zero; every row has the largest
+// challenge count of the batch). It fills that phase's columns of every wanted proof on the device — a witness program
+// (WitnessProgram below) computes them for the whole batch in one run — and returns per-proof codes: empty or all zero for
+// success, a non-zero entry drops that proof alone. Throwing drops every wanted proof; the exception is rethrown.
+using BatchSynthesize = std::function<std::vector<int>(uint32_t phase, const std::vector<uint8_t>& wanted,
+                                                        const std::vector<std::vector<Fr>>& challenges, void* hip_stream)>;
+
+// amdzk_create_proof_batch_opts: create_proof_batch for circuits with challenge phases, proofs with the caller's transcript
+// and DIFFERENT circuits — keys[b] any key or workspace clone made on one ParamsKZG, pairwise different. transcripts: empty,
+// or one entry per proof (nullptr = the built-in `transcript`); a proof with its own transcript comes back with status 0 and
+// no bytes. Proof b's bytes, and the calls its transcript receives, are those of the opts overload of create_proof on
+// keys[b] alone. Failures as for create_proof_batch.
+inline std::vector<BatchProof> create_proof_batch(const Context& ctx, const std::vector<const ProvingKey*>& keys,
+                                                  const std::vector<std::vector<std::vector<Fr>>>& instances,
+                                                  const std::vector<const void*>& d_advice, size_t advice_stride,
+                                                  const std::vector<uint64_t>& rng_seeds, const std::vector<TranscriptWrite*>& transcripts,
+                                                  const BatchSynthesize& synthesize, Transcript transcript = Transcript::Blake2b,
+                                                  Multiopen multiopen = Multiopen::Shplonk) {
+  const size_t N = keys.size();
+  if (N == 0 || instances.size() != N || d_advice.size() != N || rng_seeds.size() != N || (!transcripts.empty() && transcripts.size() != N))
+    throw Error(AMDZK_E_INVALID, "create_proof_batch: one key, instance set, witness, seed and transcript entry per proof");
+  const int format = (int)transcript | (int)multiopen;
+  struct Shared {
+    const BatchSynthesize* syn;
+    std::exception_ptr err;
+  } shared{&synthesize, nullptr};
+  std::vector<detail::Trampoline> trs(N, detail::Trampoline{nullptr, nullptr, nullptr});
+  std::vector<amdzk_transcript> cts(N);
+  std::vector<const amdzk_transcript*> ctp(N, nullptr);
+  for (size_t b = 0; b < N && !transcripts.empty(); b++) {
+    if (!transcripts[b]) continue;
+    trs[b].t = transcripts[b];
+    cts[b] = detail::c_transcript(&trs[b]);
+    ctp[b] = &cts[b];
+  }
+  amdzk_batch_proof_opts opts;
+  std::memset(&opts, 0, sizeof(opts));
+  opts.size = sizeof(opts);
+  opts.transcript_kind = format;
+  opts.rng_seeds = rng_seeds.data();
+  opts.transcripts = transcripts.empty() ? nullptr : ctp.data();
+  opts.phase_user = &shared;
+  if (synthesize)
+    opts.phase_fn = [](void* u, uint32_t phase, size_t n_proofs, const uint8_t* wanted, const uint64_t* ch, size_t stride, int* proof_rc, void* stream) {
+      auto* s = (Shared*)u;
+      try {
+        std::vector<uint8_t> w(wanted, wanted + n_proofs);
+        std::vector<std::vector<Fr>> c(n_proofs, std::vector<Fr>(stride));
+        for (size_t b = 0; b < n_proofs && stride; b++) std::memcpy((void*)c[b].data(), ch + 4 * b * stride, stride * 32);
+        const std::vector<int> rc = (*s->syn)(phase, w, c, stream);
+        for (size_t b = 0; b < n_proofs && b < rc.size(); b++) proof_rc[b] = rc[b];
+        return 0;
+      } catch (...) {
+        if (!s->err) s->err = std::current_exception();
+        return 1;
+      }
+    };
+  std::vector<amdzk_pk*> pks(N);
+  std::vector<std::vector<const uint64_t*>> ptrs(N);
+  std::vector<std::vector<size_t>> lens(N);
+  std::vector<const uint64_t* const*> pp(N);
+  std::vector<const size_t*> lp(N);
+  size_t stride = 0;
+  for (size_t b = 0; b < N; b++) {
+    pks[b] = keys[b]->handle();
+    if (!ctp[b]) stride = std::max(stride, amdzk_proof_size(pks[b], format));
+    ptrs[b].assign(std::max<size_t>(1, instances[b].size()), nullptr);
+    lens[b].assign(std::max<size_t>(1, instances[b].size()), 0);
+    for (size_t i = 0; i < instances[b].size(); i++) {
+      ptrs[b][i] = instances[b][i].empty() ? nullptr : (const uint64_t*)instances[b][i].data();
+      lens[b][i] = instances[b][i].size();
+    }
+    pp[b] = ptrs[b].data();
+    lp[b] = lens[b].data();
+  }
+  std::vector<uint8_t> bytes(std::max<size_t>(1, stride * N));
+  std::vector<size_t> got(N, 0);
+  std::vector<int> st(N, AMDZK_OK);
+  const int rc = amdzk_create_proof_batch_opts(ctx.get(), pks.data(), N, pp.data(), lp.data(), d_advice.data(), advice_stride, &opts, bytes.data(),
+                                               stride, got.data(), st.data());
+  if (shared.err) std::rethrow_exception(shared.err);
+  for (auto& t : trs)
+    if (t.err) std::rethrow_exception(t.err);
+  // refused as a whole (or ended for all by the device): the message is not one proof's ("proof <b>: ...")
+  if (rc != AMDZK_OK && std::string(amdzk_last_error(ctx.get())).rfind("proof ", 0) != 0) ctx.check(rc);
+  std::vector<BatchProof> out(N);
+  bool first = true;
+  for (size_t b = 0; b < N; b++) {
+    out[b].status = st[b];
+    if (st[b] == AMDZK_OK) out[b].proof.assign(bytes.begin() + b * stride, bytes.begin() + b * stride + got[b]);
+    else if (first) out[b].error = amdzk_last_error(ctx.get()), first = false;
+  }
+  return out;
+}
+
 // Convenience for host-resident witnesses (what a WitnessCollection holds after synthesis): uploads the
 // advice columns (padded with zeros to 2^k rows), proves, frees.
 inline std::vector<uint8_t> create_proof(const Context& ctx, const ProvingKey& pk, const std::vector<std::vector<Fr>>& instances,
@@ -1059,17 +1162,6 @@ struct ProverQuery {
 };
 
 namespace detail {
-inline amdzk_transcript c_transcript(Trampoline* tr) {
-  amdzk_transcript ct;
-  ct.user = tr;
-  ct.common_point = [](void* u, const uint64_t* xy) { auto* t = (Trampoline*)u; return t->guard([&] { G1Affine p; std::memcpy(&p, xy, 64); t->t->common_point(p); }); };
-  ct.common_scalar = [](void* u, const uint64_t* s) { auto* t = (Trampoline*)u; return t->guard([&] { Fr v; std::memcpy(v.l, s, 32); t->t->common_scalar(v); }); };
-  ct.write_point = [](void* u, const uint64_t* xy) { auto* t = (Trampoline*)u; return t->guard([&] { G1Affine p; std::memcpy(&p, xy, 64); t->t->write_point(p); }); };
-  ct.write_scalar = [](void* u, const uint64_t* s) { auto* t = (Trampoline*)u; return t->guard([&] { Fr v; std::memcpy(v.l, s, 32); t->t->write_scalar(v); }); };
-  ct.squeeze_challenge = [](void* u, uint64_t* out) { auto* t = (Trampoline*)u; return t->guard([&] { Fr v = t->t->squeeze_challenge(); std::memcpy(out, v.l, 32); }); };
-  return ct;
-}
-
 // Prover::create_proof(params, rng, transcript, queries) of poly::commitment; returns the points it wrote
 inline std::vector<G1Affine> multiopen(const Context& ctx, const ParamsKZG& params, Multiopen scheme, TranscriptWrite& transcript,
                                        const std::vector<ProverQuery>& queries, bool use_evals) {
