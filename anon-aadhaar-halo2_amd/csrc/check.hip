@@ -221,7 +221,7 @@ __global__ __launch_bounds__(256) void copy_check_kernel(const Fr* const* cols, 
 // ------------------------------------------------------------------------------ launch wrappers
 // A Lagrange-domain program (ExprArgs as for zk_expr_eval, radix 2^256) whose values end in OP_CHECK instead of OP_STORE.
 int zk_check_expr(amdzk_ctx* ctx, const ExprArgs& a, uint32_t depth, uint32_t usable, CheckCounters out, const char* name) {
-  const size_t shmem = (size_t)(depth ? depth : 1) * EXPR_THREADS * sizeof(Fr);
+  const size_t shmem = expr_lds_bytes(depth);
   const dim3 grid((unsigned)((a.nrows + EXPR_THREADS - 1) / EXPR_THREADS), a.nparts ? a.nparts : 1u), block(EXPR_THREADS);
   if (a.radix261) ZK_FAIL(ctx, AMDZK_E_INVALID, "check_expr: a Lagrange-domain program is needed");
   if (a.nparts > (uint32_t)EXPR_MAX_PARTS) ZK_FAIL(ctx, AMDZK_E_INVALID, "check_expr: too many program parts");
@@ -268,19 +268,26 @@ int zk_check_copies(amdzk_ctx* ctx, const Fr* const* d_cols, const uint2* d_cell
 // ---- amdzk_check_witness: MockProver::verify's constraint checks on the device (include/amdzk.h has the semantics).
 // What this handle needs beyond what a proof uses, made by its first check: the gate program, the permutation columns'
 // addresses in this workspace, the counters.
+// The gate polynomials as one Lagrange-domain program, gate g ending in OP_CHECK g. The gates' rotations are all in the
+// key's table already (the h(X) program queried them): emit_expr refuses any other.
+int emit_check_gates(amdzk_ctx* ctx, const KeyMaterial& K, ProgramText& pr) {
+  for (uint32_t g = 0; g < K.num_gates; g++) {
+    pr.piece();
+    ZK_TRY(emit_expr(ctx, K, nullptr, pr, K.exprs[g]));
+    pr.op(OP_CHECK, g);
+    pr.pop();
+  }
+  return AMDZK_OK;
+}
+
 static int check_build(amdzk_ctx* ctx, amdzk_pk* pk) {
   const KeyMaterial& K = *pk->key;
   amdzk_pk::Check& ck = pk->chk;
   if (ck.built) return AMDZK_OK;
   const uint32_t ncon = K.num_gates + K.L + K.S;
   if (!ck.prog_gates.d_instr) {
-    ProgramText pr;  // the gates' rotations are all in the key's table already (the h(X) program queried them): emit_expr refuses any other
-    for (uint32_t g = 0; g < K.num_gates; g++) {
-      pr.piece();
-      ZK_TRY(emit_expr(ctx, K, nullptr, pr, K.exprs[g]));
-      pr.op(OP_CHECK, g);
-      pr.pop();
-    }
+    ProgramText pr;
+    ZK_TRY(emit_check_gates(ctx, K, pr));
     ck.gates = std::move(pr);
     ck.prog_gates.text = &ck.gates;
     ZK_TRY(upload_program(ctx, pk, ck.prog_gates, false));
@@ -390,7 +397,7 @@ static int check_witness_run(amdzk_ctx* ctx, amdzk_pk* pk, const uint64_t* const
   if (G) {
     ExprArgs a;
     ZK_TRY(program_args(ctx, pk, pk->chk.prog_gates, false, nullptr, nullptr, a));
-    ZK_TRY(zk_check_expr(ctx, a, ck.gates.depth + 1, (uint32_t)usable, counters, "expr_check_gates"));
+    ZK_TRY(zk_check_expr(ctx, a, lagrange_stack_slots(ck.gates), (uint32_t)usable, counters, "expr_check_gates"));
   }
   if (L) {  // compressed inputs and tables as canonical keys, the tables sorted (constant ones were sorted at keygen)
     ZK_TRY(run_program(ctx, pk, pk->prog_compress, false, pk->d_outs_compress, nullptr, "expr_lookup_compress"));

@@ -717,6 +717,29 @@ static int emit_h_program(amdzk_ctx* ctx, KeyMaterial& K) {
   return AMDZK_OK;
 }
 
+// Every program of the key must fit the LDS of the interpreter that runs it (program.hip check_program_fits): the h(X)
+// program, the Lagrange-domain programs, the constant tables' one-off program (build_constant_tables), and the witness
+// check's gates, which a handle compiles at its first check — compiled here once for their depth alone.
+static int check_program_depths(amdzk_ctx* ctx, const KeyMaterial& K) {
+  ZK_TRY(check_program_fits(ctx, K.prog_h, true, "h(X)"));
+  ZK_TRY(check_program_fits(ctx, K.prog_compress, false, "lookup compression"));
+  ZK_TRY(check_program_fits(ctx, K.prog_pfrac, false, "permutation fraction"));
+  ZK_TRY(check_program_fits(ctx, K.prog_lfrac, false, "lookup fraction"));
+  ProgramText tables;
+  uint32_t e = K.num_gates;
+  for (uint32_t l = 0; l < K.lk_const; l++) {
+    RotTable rots = K.rots;  // (emit_compress_program has queried these rotations: the copy does not grow)
+    ZK_TRY(emit_expr(ctx, K, &rots, tables, K.exprs[e + K.lookup_shape[l].first]));
+    tables.pop();
+    e += K.lookup_shape[l].first + 1;
+  }
+  ZK_TRY(check_program_fits(ctx, tables, false, "constant lookup table"));
+  ProgramText gates;
+  ZK_TRY(emit_check_gates(ctx, K, gates));
+  ZK_TRY(check_program_fits(ctx, gates, false, "witness-check gate"));
+  return AMDZK_OK;
+}
+
 // AMDZK_DUMP_PROG, a debugging aid: what the compiled h(X) program is made of
 static void dump_h_program(const KeyMaterial& K) {
   static const char* names[] = {"END", "PUSH_COL", "PUSH_CONST", "ADD", "SUB", "MUL", "NEG", "MUL_CONST", "ADD_CONST", "MUL_COL",
@@ -823,6 +846,7 @@ static int keygen_common(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circu
   emit_lfrac_program(K);
   ZK_TRY(emit_h_program(ctx, K));
   if (K.rots.rots.size() > 255) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "keygen: more than 255 distinct rotations");
+  ZK_TRY(check_program_depths(ctx, K));
   ZK_TRY(bind_workspace(ctx, pk));
   if (getenv("AMDZK_DUMP_PROG")) dump_h_program(K);
   ZK_TRY(build_constant_tables(ctx, K, pk));

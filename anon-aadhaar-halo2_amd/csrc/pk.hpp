@@ -316,3 +316,14 @@ int upload_ypow(amdzk_ctx* ctx, amdzk_pk* pk);
 int upload_program(amdzk_ctx* ctx, amdzk_pk* pk, Program& pr, bool extended);
 int program_args(amdzk_ctx* ctx, const amdzk_pk* pk, const Program& pr, bool extended, Fr* const* d_outs, Fr* h_out, ExprArgs& a);
 int run_program(amdzk_ctx* ctx, const amdzk_pk* pk, const Program& pr, bool extended, Fr* const* d_outs, Fr* h_out, const char* name);
+// The LDS stack slots a program is launched with. The limb interpreter keeps the top of the stack in registers, so a
+// program whose stack holds at most pr.depth - 1 values (finalize_limb_program) needs pr.depth - 2 slots: pr.depth - 1
+// leaves one spare. The Lagrange-domain interpreters (zk_expr_eval, zk_check_expr) get one slot above the recorded depth.
+inline uint32_t limb_stack_slots(const ProgramText& pr) { return pr.depth > 1 ? pr.depth - 1 : 1; }
+inline uint32_t lagrange_stack_slots(const ProgramText& pr) { return pr.depth + 1; }
+// Keygen's refusal of a program whose stack does not fit the device's LDS (AMDZK_E_UNSUPPORTED, naming the program, its
+// depth and the depth that fits): the bytes are those the launch wrappers ask for, the limit is the device's opt-in
+// maximum of shared memory per block.
+int check_program_fits(amdzk_ctx* ctx, const ProgramText& pr, bool extended, const char* name);
+// The witness check's gate program (check.hip builds it on a handle's first check; keygen compiles it once for its depth).
+int emit_check_gates(amdzk_ctx* ctx, const KeyMaterial& K, ProgramText& pr);

@@ -1038,7 +1038,7 @@ __global__ void scatter_rows_kernel(Fr* dst, size_t col_stride, size_t row0, con
 
 // ------------------------------------------------------------------------------ launch wrappers
 int zk_expr_eval(amdzk_ctx* ctx, const ExprArgs& a, uint32_t depth, const char* name) {
-  size_t shmem = (size_t)(depth ? depth : 1) * EXPR_THREADS * sizeof(Fr);
+  size_t shmem = expr_lds_bytes(depth);
   const dim3 grid((unsigned)((a.nrows + EXPR_THREADS - 1) / EXPR_THREADS), a.nparts ? a.nparts : 1u), block(EXPR_THREADS);
   if (a.radix261) ZK_FAIL(ctx, AMDZK_E_INVALID, "expr_eval: radix-2^261 programs run on the limb-resident interpreter");
   if (a.nparts > (uint32_t)EXPR_MAX_PARTS) ZK_FAIL(ctx, AMDZK_E_INVALID, "expr_eval: too many program parts");
@@ -1057,7 +1057,7 @@ __global__ void sum_parts_kernel(Fr* h, size_t rows, uint32_t nparts) {
 }
 
 int zk_expr_eval_limbs(amdzk_ctx* ctx, const ExprArgs& a, uint32_t depth, const char* name) {
-  size_t shmem = (size_t)(depth ? depth : 1) * EXPR_THREADS * 9 * sizeof(uint32_t) + (size_t)17 * EXPR_THREADS * sizeof(uint64_t);
+  size_t shmem = expr_limbs_lds_bytes(depth);
   if (a.nparts > (uint32_t)EXPR_MAX_PARTS) ZK_FAIL(ctx, AMDZK_E_INVALID, "expr_eval_limbs: too many program parts");
   if (a.nparts > 1 && !a.h_out) ZK_FAIL(ctx, AMDZK_E_INVALID, "expr_eval_limbs: a cut program needs h_out (nparts x nrows)");
   const dim3 grid((unsigned)((a.nrows + EXPR_THREADS - 1) / EXPR_THREADS), a.nparts ? a.nparts : 1u), block(EXPR_THREADS);

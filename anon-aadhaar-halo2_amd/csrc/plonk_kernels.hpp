@@ -77,6 +77,13 @@ struct ExprArgs {
   uint32_t part_start[EXPR_MAX_PARTS], part_len[EXPR_MAX_PARTS];
 };
 
+// LDS bytes a launch with `depth` stack slots asks for: zk_expr_eval and zk_check_expr keep [depth][EXPR_THREADS] values of
+// 32 bytes, zk_expr_eval_limbs [depth][9][EXPR_THREADS] limbs behind the 17 un-carried 64-bit columns of the wide
+// accumulator. The launch wrappers and keygen's depth check (program.hip check_program_fits) share them.
+inline size_t expr_lds_bytes(uint32_t depth) { return (size_t)(depth ? depth : 1) * EXPR_THREADS * sizeof(bn254::Fr); }
+inline size_t expr_limbs_lds_bytes(uint32_t depth) {
+  return (size_t)(depth ? depth : 1) * EXPR_THREADS * 9 * sizeof(uint32_t) + (size_t)17 * EXPR_THREADS * sizeof(uint64_t);
+}
 int zk_expr_eval(amdzk_ctx* ctx, const ExprArgs& a, uint32_t depth, const char* name);
 // the same for a radix-2^261 program finalised by the host for the limb-resident interpreter (program.hip finalize_limb_program)
 int zk_expr_eval_limbs(amdzk_ctx* ctx, const ExprArgs& a, uint32_t depth, const char* name);

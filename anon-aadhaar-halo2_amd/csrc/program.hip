@@ -480,9 +480,24 @@ int run_program(amdzk_ctx* ctx, const amdzk_pk* pk, const Program& bound, bool e
   const ProgramText& pr = *bound.text;
   ExprArgs a;
   ZK_TRY(program_args(ctx, pk, bound, extended, d_outs, h_out, a));
-  // LDS stack slots: the limb interpreter keeps the top of the stack in registers, so a program whose stack holds at most
-  // pr.depth - 1 values (finalize_limb_program) needs pr.depth - 2 slots: pr.depth - 1 leaves one spare
-  return extended ? zk_expr_eval_limbs(ctx, a, pr.depth > 1 ? pr.depth - 1 : 1, name) : zk_expr_eval(ctx, a, pr.depth + 1, name);
+  return extended ? zk_expr_eval_limbs(ctx, a, limb_stack_slots(pr), name) : zk_expr_eval(ctx, a, lagrange_stack_slots(pr), name);
+}
+
+// A right-nested expression, (a*b) + ((c*d) + (...)), adds a stack entry per level (emit_tree keeps the operands' order),
+// and nothing else bounds a program's depth: a key whose program does not fit would fail at proof time, in the launch.
+int check_program_fits(amdzk_ctx* ctx, const ProgramText& pr, bool extended, const char* name) {
+  int limit = 0;
+  if (hipDeviceGetAttribute(&limit, hipDeviceAttributeSharedMemPerBlockOptin, ctx->device) != hipSuccess || limit <= 0) {
+    (void)hipGetLastError();
+    ZK_HIP(ctx, hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device));
+  }
+  const uint32_t slots = extended ? limb_stack_slots(pr) : lagrange_stack_slots(pr);
+  auto bytes = [&](uint32_t s) { return extended ? expr_limbs_lds_bytes(s) : expr_lds_bytes(s); };
+  if (bytes(slots) <= (size_t)limit) return AMDZK_OK;
+  uint32_t fit = 0;  // the largest recorded depth whose launch fits
+  for (uint32_t s = 1; bytes(s) <= (size_t)limit; s++) fit = extended ? s + 1 : s - 1;
+  ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "keygen: the %s program has stack depth %u (%zu bytes of LDS); depth %u fits this device (%d bytes per workgroup)",
+          name, pr.depth, bytes(slots), fit, limit);
 }
 
 extern "C" {

@@ -252,9 +252,13 @@ int build_multiopen(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, amdzk_pk::M
   const KeyMaterial& K = *pk->key;
   const size_t n = K.n;
   const uint32_t S = K.S, L = K.L, ns = K.nsets, bf = K.bf;
+  // distinct POINTS: rotations that differ by a multiple of n name the same point x * omega^rot (upstream keeps a set's
+  // points in a BTreeSet of field elements), as in the verifier's plan (verifier.hpp); two of them in one set would make
+  // the set's interpolation divide by zero
+  auto rot_mod = [&](int rot) { return ((int64_t)rot % (int64_t)n + (int64_t)n) % (int64_t)n; };
   auto rot_id = [&](int rot) -> uint32_t {
     for (size_t i = 0; i < mo.rots.size(); i++)
-      if (mo.rots[i] == rot) return (uint32_t)i;
+      if (rot_mod(mo.rots[i]) == rot_mod(rot)) return (uint32_t)i;
     mo.rots.push_back(rot);
     return (uint32_t)mo.rots.size() - 1;
   };

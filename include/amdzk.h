@@ -283,7 +283,12 @@ typedef struct amdzk_pk amdzk_pk;
  * column i and row j the pair (i', j') of permutation::keygen::Assembly::mapping, as
  * perm_mapping[2*(i*n + j) + {0,1}]. transcript_repr: VerifyingKey::transcript_repr (upstream derives
  * it from the Debug string of the pinned VK; the caller supplies it). The proving key owns the
- * per-proof workspace: one proof at a time per key. */
+ * per-proof workspace: one proof at a time per key.
+ * An expression is compiled in the order it is written, so a right-nested one, (a*b) + ((c*d) + (...)), holds one stack
+ * entry per level; the stack lives in LDS. Every keygen (this one, _ex, _phased, _sigma, amdzk_pk_read) refuses a circuit
+ * whose compiled programs need more LDS than the device gives a workgroup (its opt-in maximum of shared memory per
+ * block) with AMDZK_E_UNSUPPORTED and a message that names the program, its depth and the depth that fits — about 30
+ * levels at 160 KiB; nest to the left, ((a*b) + (c*d)) + ..., to stay shallow. The ctx stays usable. */
 int amdzk_keygen(amdzk_ctx* ctx, const amdzk_srs* srs, const amdzk_circuit* circuit,
                  const uint64_t* fixed_values, const uint32_t* perm_mapping,
                  const uint64_t transcript_repr[4], amdzk_pk** out);

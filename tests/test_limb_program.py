@@ -160,3 +160,145 @@ def test_shared_values_are_picked_from_the_stack(pkg):
 def test_checker_rejects_a_pick_below_the_stack():
     with pytest.raises(AssertionError):
         LC.check([W("PUSH_COL", 1), W("PICK", 1), W("ADD"), W("WACC", 0), W("WFLUSH", 4 | 16)])
+
+
+# ------------------------------------------------------------------------- every threshold of the pass, from both sides
+def margins(pkg, prog):
+    out, _ = finalize(pkg, prog)
+    LC.check(out)
+    return ops(out), LC.check.margins
+
+
+def run_length(names):
+    out = []
+    for nm in names:
+        if out and out[-1][0] == nm:
+            out[-1][1] += 1
+        else:
+            out.append([nm, 1])
+    return " ".join(nm if cnt == 1 else "%s*%d" % (nm, cnt) for nm, cnt in out)
+
+
+def test_margins_report_the_largest_value_of_each_guarded_quantity():
+    prog = [W("PUSH_COL", 0), W("ADD_COL", 1), W("ADD_COL", 1), W("PUSH_COL", 2), W("ADD_COL", 3), W("MUL"),     # 3 * 2
+            W("PUSH_COL", 4), W("ADD_COL", 4), W("ADD_COL", 4), W("ADD_COL", 4), W("SUB_BIG"), W("NEG_BIG"),      # 2 - 4 = 12, -(12)
+            W("WACC", 0), W("WFLUSH", 4 | 16)]
+    with pytest.raises(AssertionError):
+        LC.check(prog)  # NEG_BIG of a value of bound 12
+    prog[11] = W("REDUCE")
+    LC.check(prog)
+    m = LC.check.margins
+    assert m["product"] == 6.0 and m["sub_big"] == 4.0 and m["sum"] == 4.0 and m["sink"] == 3.0 and m["stack"] == 12.0
+    assert m["wflush"] == 1.0002 and m["uncarried"] == 1 and m["sub"] == m["neg"] == m["neg_big"] == m["store"] == 0.0
+    LC.check([W("PUSH_COL", 0), W("STORE", 3)])
+    assert LC.check.margins["store"] == 1.0
+
+
+@pytest.mark.parametrize("fused", ["ADD_COL", "ADD_CONST"])
+def test_a_fused_sum_is_kept_at_40_and_reduced_before_41(pkg, fused):
+    tail = [W("MUL_COL", 9), W("ACC")]
+    o, m = margins(pkg, [W("PUSH_COL", 0)] + [W(fused, 1)] * 39 + tail)
+    assert run_length(o) == "PUSH_COL %s*39 MUL_COL WACC WFLUSH" % fused and m["sum"] == 40.0 and m["product"] == 40.0
+    o, m = margins(pkg, [W("PUSH_COL", 0)] + [W(fused, 1)] * 40 + tail)
+    assert run_length(o) == "PUSH_COL %s*39 REDUCE %s MUL_COL WACC WFLUSH" % (fused, fused) and m["sum"] == 40.0
+
+
+def test_sub_col_adds_three(pkg):
+    tail = [W("MUL_COL", 9), W("ACC")]
+    o, m = margins(pkg, [W("PUSH_COL", 0)] + [W("ADD_COL", 1)] * 36 + [W("SUB_COL", 2)] + tail)
+    assert "REDUCE" not in o and m["sum"] == 40.0
+    o, m = margins(pkg, [W("PUSH_COL", 0)] + [W("ADD_COL", 1)] * 37 + [W("SUB_COL", 2)] + tail)
+    assert run_length(o) == "PUSH_COL ADD_COL*37 REDUCE SUB_COL MUL_COL WACC WFLUSH" and m["sum"] == 38.0
+
+
+def test_the_sum_of_two_stack_entries_is_kept_at_40(pkg):
+    two = lambda a, b: [W("PUSH_COL", 0)] + [W("ADD_COL", 1)] * (a - 1) + [W("PUSH_COL", 2)] + [W("ADD_COL", 3)] * (b - 1) + [W("ADD"), W("MUL_COL", 9), W("ACC")]
+    o, m = margins(pkg, two(8, 32))
+    assert "REDUCE" not in o and m["sum"] == 40.0 and m["sink"] == 8.0
+    o, m = margins(pkg, two(8, 33))
+    assert run_length(o) == "PUSH_COL ADD_COL*7 PUSH_COL ADD_COL*32 REDUCE ADD MUL_COL WACC WFLUSH" and m["sink"] == 8.0
+
+
+@pytest.mark.parametrize("push", ["PUSH_COL", "PUSH_CONST", "PUSH_HOT", "PICK"])
+def test_a_value_sinks_at_8_and_is_reduced_at_9(pkg, push):
+    two = lambda a: [W("PUSH_COL", 0)] + [W("ADD_COL", 1)] * (a - 1) + [W(push, 0), W("MUL"), W("ACC")]
+    o, m = margins(pkg, two(8))
+    assert "REDUCE" not in o and m["sink"] == 8.0
+    o, m = margins(pkg, two(9))
+    assert run_length(o) == "PUSH_COL ADD_COL*8 REDUCE %s MUL WACC WFLUSH" % push and m["sink"] == 1.0002
+
+
+def test_products_are_kept_below_160(pkg):
+    two = lambda a, b: [W("PUSH_COL", 0)] + [W("ADD_COL", 1)] * (a - 1) + [W("PUSH_COL", 2)] + [W("ADD_COL", 3)] * (b - 1) + [W("MUL"), W("ACC")]
+    o, m = margins(pkg, two(8, 19))
+    assert "REDUCE" not in o and m["product"] == 152.0
+    o, m = margins(pkg, two(8, 20))
+    assert run_length(o) == "PUSH_COL ADD_COL*7 PUSH_COL ADD_COL*19 REDUCE MUL WACC WFLUSH" and 8.0 < m["product"] < 8.1
+    sq = lambda a: [W("PUSH_COL", 0)] + [W("ADD_COL", 1)] * (a - 1) + [W("SQR"), W("ACC")]
+    o, m = margins(pkg, sq(12))
+    assert "REDUCE" not in o and m["product"] == 144.0
+    assert run_length(margins(pkg, sq(13))[0]) == "PUSH_COL ADD_COL*12 REDUCE SQR WACC WFLUSH"  # 169 is out of f29_sqr's range
+
+
+def test_subtrahends_below_2_below_9_and_above(pkg):
+    sub = lambda b: [W("PUSH_COL", 0), W("PUSH_COL", 1)] + [W("ADD_COL", 2)] * (b - 1) + [W("SUB"), W("MUL_COL", 9), W("ACC")]
+    assert run_length(margins(pkg, sub(1))[0]) == "PUSH_COL*2 SUB MUL_COL WACC WFLUSH"
+    o, m = margins(pkg, sub(2))
+    assert run_length(o) == "PUSH_COL*2 ADD_COL SUB_BIG MUL_COL WACC WFLUSH" and m["sub_big"] == 2.0
+    o, m = margins(pkg, sub(8))
+    assert "REDUCE" not in o and "SUB_BIG" in o and m["sub_big"] == 8.0 and m["stack"] == 11.0
+    o, m = margins(pkg, sub(9))
+    assert run_length(o) == "PUSH_COL*2 ADD_COL*8 REDUCE SUB MUL_COL WACC WFLUSH" and m["sub"] == 1.0002
+    neg = lambda b: [W("PUSH_COL", 1)] + [W("ADD_COL", 2)] * (b - 1) + [W("NEG"), W("MUL_COL", 9), W("ACC")]
+    assert "NEG" in margins(pkg, neg(1))[0]
+    for b in (2, 8):
+        o, m = margins(pkg, neg(b))
+        assert "NEG_BIG" in o and "REDUCE" not in o and m["neg_big"] == float(b)
+    assert run_length(margins(pkg, neg(9))[0]) == "PUSH_COL ADD_COL*8 REDUCE NEG MUL_COL WACC WFLUSH"
+
+
+def test_a_group_is_flushed_within_one_term_of_its_limit(pkg):
+    """150 plain terms of bound 40: the plain group is split where the next term would pass 169 * 30, and two carries fall
+    inside 13 terms of a hot group."""
+    term = lambda i: [W("PUSH_COL", i)] + [W("ADD_COL", 1)] * 39 + [W("ACC")]
+    prog = []
+    for i in range(150):
+        prog += term(i)
+    o, m = margins(pkg, prog)
+    assert o.count("WFLUSH") == 2 and 169.0 * 30 - 40 < m["wflush"] <= 169.0 * 30 and m["uncarried"] == 5
+    hot = []
+    for i in range(13):
+        hot += [W("PUSH_COL", i), W("SUB_COL", 1), W("MUL_HOT", 2), W("ACC")]
+    out, _ = finalize(pkg, hot)
+    assert [bool(w & (1 << 23)) for w in out if LC.NAME[w >> 24] == "WACC"] == [False] * 5 + [True] + [False] * 5 + [True, False]
+    LC.check(out)
+    assert LC.check.margins["uncarried"] == 5
+
+
+# ------------------------------------------------------------------------------ the pass preserves the value: random programs
+@pytest.mark.parametrize("block", range(8))
+def test_the_pass_preserves_the_value_of_random_programs(pkg, block):
+    import limb_program_eval as LE
+
+    seen = set()
+    for seed in range(50 * block, 50 * block + 50):
+        prog = LE.random_program(seed)
+        out, depth = finalize(pkg, prog)
+        d, _, nterms = LC.check(out)
+        assert depth >= d and nterms == sum(1 for w in prog if LC.NAME[w >> 24] == "ACC"), seed
+        env = LE.Env(seed)
+        assert LE.evaluate(out, env) == LE.evaluate(prog, env), "seed %d: the finalised program computes another value" % seed
+        seen.update(ops(prog))
+        seen.update(ops(out))
+    assert {"PICK", "NIP", "SQR", "PUSH_HOT", "MUL_HOT", "STORE", "REDUCE", "SUB_BIG", "NEG_BIG", "WACC", "WFLUSH"} <= seen
+
+
+def test_the_evaluator_tells_a_dropped_factor_and_a_wrong_power():
+    import limb_program_eval as LE
+
+    env = LE.Env(1)
+    raw = [W("PUSH_COL", 1), W("MUL_HOT", 2), W("ACC"), W("PUSH_COL", 2), W("ACC")]
+    good = [W("PUSH_COL", 1), W("WACC", 0), W("WFLUSH", 2 | 16), W("PUSH_COL", 2), W("WACC", 1), W("WFLUSH", 4)]
+    assert LE.evaluate(good, env) == LE.evaluate(raw, env) == ((env.col(1) * env.hot[2] * env.y + env.col(2)) % LE.R, {})
+    for bad in (good[:2] + [W("WFLUSH", 4 | 16)] + good[3:], good[:1] + [W("WACC", 1)] + good[2:4] + [W("WACC", 0)] + good[5:]):
+        assert LE.evaluate(bad, env) != LE.evaluate(raw, env)
