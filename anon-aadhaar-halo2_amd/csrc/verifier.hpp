@@ -559,4 +559,130 @@ inline DeviceLayout device_layout(size_t n_proofs, size_t stride, size_t E, size
   return L;
 }
 
+// ---- a batch over DIFFERENT keys (amdzk_verify_proofs_mixed; verify.hip, verify_mixed_core). Items that name the same key
+// handle, the same number of circuit instances and the same transcript kind form a GROUP: one Plan, one element table, one
+// raw-form table and one block of commitments. Both functions below are pure: tests/native/verifier_mixed_check.cpp runs them
+// alone.
+struct MixedKey {
+  const void* key;  // the key handle the item names (a proving key's or a verifying key's)
+  uint32_t n_circuits;
+  int kind;  // the transcript kind that counts for the item (a read-transcript item: the opening scheme's bit alone)
+  bool operator<(const MixedKey& o) const {
+    return key != o.key ? key < o.key : n_circuits != o.n_circuits ? n_circuits < o.n_circuits : kind < o.kind;
+  }
+};
+// item -> group, groups numbered first seen first; firsts[g]: the first item of group g
+inline std::vector<uint32_t> group_items(const MixedKey* keys, size_t n_items, std::vector<size_t>* firsts) {
+  std::map<MixedKey, uint32_t> seen;
+  std::vector<uint32_t> of(n_items);
+  firsts->clear();
+  for (size_t b = 0; b < n_items; b++) {
+    auto it = seen.find(keys[b]);
+    if (it == seen.end()) {
+      it = seen.emplace(keys[b], (uint32_t)firsts->size()).first;
+      firsts->push_back(b);
+    }
+    of[b] = it->second;
+  }
+  return of;
+}
+
+// What the mixed decode launch reads (verify.hip, proof_decode_mixed_kernel). A block of MIXED_BLOCK threads decodes
+// elements [first, first + MIXED_BLOCK) of ONE item: no block straddles two items, so its records are wave-uniform.
+constexpr uint32_t MIXED_BLOCK = 64;
+struct MixedItemRec {
+  uint64_t staging;          // byte offset of the item's bytes (or read-transcript words) in the staging area, a multiple of 32
+  uint64_t points, scalars;  // its first decoded point / scalar
+  uint32_t group;
+  uint32_t raw;  // 1: the read-transcript form
+};
+struct MixedGroupRec {
+  uint32_t elems;  // the group's first entry in the element table and in the raw-form table
+  uint32_t E;
+  uint32_t evm;
+  uint32_t reserved;
+};
+struct MixedBlockRec {
+  uint32_t item, first;
+};
+static_assert(sizeof(MixedItemRec) == 32 && sizeof(MixedGroupRec) == 16 && sizeof(MixedBlockRec) == 8, "device records");
+
+struct MixedGroupShape {
+  size_t E, NP, NS, nvk;         // elements, points, scalars of one proof; fixed + permutation commitments of the key
+  size_t proof_bytes, raw_bytes;  // one proof in the byte form and in the read-transcript form
+};
+// The ONE device reservation of a mixed call, DeviceLayout's counterpart. [0, g) goes UP in one copy (the G of a proving key
+// then follows device to device into key_g); [status, msm) comes DOWN in one copy: the status words, one G per distinct
+// key — the "same G" rule is judged on what came down —, the commitments, the points and the scalars.
+struct MixedLayout {
+  size_t staging;    // the items' bytes, item b at item_staging[b], item_stride[b] bytes
+  size_t items;      // MixedItemRec[n_items]
+  size_t groups;     // MixedGroupRec[n_groups]
+  size_t blocks;     // MixedBlockRec[n_blocks]
+  size_t elems;      // uint2[n_elems]: every group's element table, group g at group_elems[g]
+  size_t elems_raw;  // the same in the read-transcript form (no bytes when no item has one)
+  size_t status;     // uint32_t[n_items]
+  size_t key_g;      // G1Affine[n_keys]: G of every distinct key, first seen first
+  // commitments | G | points are CONTIGUOUS: the base array of the combined MSM
+  size_t vk;         // G1Affine[nvk]: every group's fixed and permutation commitments, group g at group_vk[g]
+  size_t g;          // G1Affine: the G of item 0's key
+  size_t points;     // G1Affine[n_points], item b at item_points[b]
+  size_t scalars;    // Fr[n_scalars], item b at item_scalars[b]
+  size_t msm;        // Fr[2][nvk + 1 + n_points] combined; per proof Fr[2 * run][run_len], ONE run's columns
+  size_t run_bases;  // per proof: G1Affine[run_len], one run's commitments | G | points
+  size_t bytes, up_bytes, down_bytes;
+  size_t n_blocks, n_elems, n_points, n_scalars, nvk, staging_bytes;
+  size_t run, run_len;  // per proof: items per MSM, and the most bases one run has
+  std::vector<size_t> item_staging, item_stride, item_points, item_scalars;
+  std::vector<size_t> group_elems, group_vk;
+};
+// item_group[b] < n_groups; item_raw[b] != 0: item b comes through a read transcript (item_raw == nullptr: none does).
+inline MixedLayout mixed_layout(const MixedGroupShape* shapes, size_t n_groups, const uint32_t* item_group, const uint8_t* item_raw, size_t n_items,
+                                size_t n_keys, bool per_proof) {
+  MixedLayout L;
+  L.group_elems.resize(n_groups), L.group_vk.resize(n_groups);
+  L.n_elems = L.nvk = 0;
+  for (size_t g = 0; g < n_groups; g++) {
+    L.group_elems[g] = L.n_elems, L.n_elems += shapes[g].E;
+    L.group_vk[g] = L.nvk, L.nvk += shapes[g].nvk;
+  }
+  L.item_staging.resize(n_items), L.item_stride.resize(n_items), L.item_points.resize(n_items), L.item_scalars.resize(n_items);
+  L.n_blocks = L.n_points = L.n_scalars = L.staging_bytes = 0;
+  bool any_raw = false;
+  for (size_t b = 0; b < n_items; b++) {
+    const MixedGroupShape& s = shapes[item_group[b]];
+    const bool raw = item_raw && item_raw[b];
+    any_raw |= raw;
+    L.item_staging[b] = L.staging_bytes, L.item_stride[b] = ws_round_up(raw ? s.raw_bytes : s.proof_bytes, 32);
+    L.staging_bytes += L.item_stride[b];
+    L.item_points[b] = L.n_points, L.n_points += s.NP;
+    L.item_scalars[b] = L.n_scalars, L.n_scalars += s.NS;
+    L.n_blocks += (s.E + MIXED_BLOCK - 1) / MIXED_BLOCK;
+  }
+  // runs of AMDZK_DECIDE_RUN consecutive positions: the commitments of the groups present, G, the run's points
+  L.run = n_items < AMDZK_DECIDE_RUN ? n_items : AMDZK_DECIDE_RUN, L.run_len = 0;
+  std::vector<uint8_t> present(n_groups, 0);
+  for (size_t b0 = 0; per_proof && b0 < n_items; b0 += L.run) {
+    const size_t b1 = b0 + L.run < n_items ? b0 + L.run : n_items;
+    size_t len = 1;
+    for (size_t b = b0; b < b1; b++) {
+      const uint32_t g = item_group[b];
+      len += shapes[g].NP + (present[g] ? 0 : shapes[g].nvk);
+      present[g] = 1;
+    }
+    for (size_t b = b0; b < b1; b++) present[item_group[b]] = 0;
+    L.run_len = len > L.run_len ? len : L.run_len;
+  }
+  WsLayout w;
+  L.staging = w.take(L.staging_bytes), L.items = w.take(n_items * sizeof(MixedItemRec)), L.groups = w.take(n_groups * sizeof(MixedGroupRec));
+  L.blocks = w.take(L.n_blocks * sizeof(MixedBlockRec)), L.elems = w.take(L.n_elems * 8), L.elems_raw = w.take(any_raw ? L.n_elems * 8 : 0);
+  L.status = w.take(n_items * 4), L.key_g = w.take(n_keys * sizeof(G1Affine));
+  L.vk = w.take(L.nvk * sizeof(G1Affine), 1), L.g = w.take(sizeof(G1Affine), 1), L.points = w.take(L.n_points * sizeof(G1Affine), 1);
+  L.scalars = w.take(L.n_scalars * sizeof(Fr));
+  L.msm = per_proof ? w.take(2 * L.run * L.run_len * sizeof(Fr)) : w.take(2 * (L.nvk + 1 + L.n_points) * sizeof(Fr), 1);
+  L.run_bases = w.take(per_proof ? L.run_len * sizeof(G1Affine) : 0, 1);
+  L.bytes = w.bytes(), L.up_bytes = L.g, L.down_bytes = L.msm - L.status;
+  return L;
+}
+
 }  // namespace verifier

@@ -148,6 +148,8 @@ def lib():
         "amdzk_verify_proofs_vk": (i32, [vp, vp, sz, C.POINTER(C.POINTER(vp)), C.POINTER(C.POINTER(sz)), C.POINTER(vp), C.POINTER(sz), vp, vp, vp]),
         "amdzk_verify_proofs_decide_vk": (i32, [vp, vp, vp, vp, u32, sz, C.POINTER(C.POINTER(vp)), C.POINTER(C.POINTER(sz)), C.POINTER(vp),
                                                 C.POINTER(sz), vp, vp, vp, C.POINTER(sz)]),
+        "amdzk_verify_proofs_mixed": (i32, [vp, vp, sz, vp, vp, vp]),
+        "amdzk_verify_proofs_decide_mixed": (i32, [vp, vp, vp, u32, vp, sz, vp, vp, vp, C.POINTER(sz)]),
         "amdzk_witness_plan": (i32, [vp, sz, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(sz), C.c_char_p, sz]),
         "amdzk_witness_compile": (i32, [vp, vp, C.POINTER(vp)]),
         "amdzk_witness_free": (None, [vp, vp]),
@@ -242,6 +244,16 @@ class VerifyOpts(C.Structure):  # amdzk_verify_opts
 
 
 VERIFY_OPTS_LEGACY_SIZE = VerifyOpts.transcripts.offset  # the struct before `transcripts`: still accepted, means no transcripts
+
+
+class VerifyItem(C.Structure):  # amdzk_verify_item
+    _fields_ = [("pk", C.c_void_p), ("vk", C.c_void_p), ("transcript_kind", C.c_int), ("n_circuits", C.c_uint32),
+                ("instances", C.POINTER(C.POINTER(C.c_void_p))), ("instance_lens", C.POINTER(C.POINTER(C.c_size_t))), ("proof", C.c_void_p),
+                ("proof_len", C.c_size_t), ("transcript", C.POINTER(TranscriptRead))]
+
+
+class VerifyMixedOpts(C.Structure):  # amdzk_verify_mixed_opts
+    _fields_ = [("size", C.c_size_t), ("combine_seed", C.c_uint64), ("combine_scalars", C.c_void_p)]
 
 
 class MultiopenVerifyOpts(C.Structure):  # amdzk_multiopen_verify_opts

@@ -1098,6 +1098,81 @@ def decide_proofs(ctx, pk, vparams, instances_list, proofs, transcript=TRANSCRIP
     return out, [ProofStatus(s.status, s.offset) for s in st[:B]]
 
 
+class VerifyItem:
+    """One member of a mixed batch (amdzk_verify_item): `key` a ProvingKey or a VerifyingKey, `instances` the proof's instance
+    columns as for create_proof (with n_circuits > 1 a list of n_circuits such lists), `proof` the bytes, `transcript` the kind
+    flags of those bytes. reader: the caller's TranscriptRead object (verify_proofs); `proof` may then be None and of
+    `transcript` only MULTIOPEN_GWC counts."""
+
+    def __init__(self, key, instances, proof, transcript=TRANSCRIPT_BLAKE2B, n_circuits=1, reader=None):
+        self.key, self.instances, self.proof, self.transcript, self.n_circuits, self.reader = key, instances, proof, transcript, n_circuits, reader
+
+
+def _mixed_args(items, combine_seed, combine_scalars, opts_size, errors):
+    """(amdzk_verify_item array, opts, statuses, keep-alive) of the two mixed calls."""
+    B = len(items)
+    arr = (_ffi.VerifyItem * max(1, B))()
+    keep = []
+    for b, it in enumerate(items):
+        N = it.n_circuits or 1
+        per_circuit = [it.instances] if N == 1 else list(it.instances)
+        assert len(per_circuit) == N
+        inst_pp, lens_pp = (C.POINTER(C.c_void_p) * N)(), (C.POINTER(C.c_size_t) * N)()
+        for c, instances in enumerate(per_circuit):
+            cols = [np.ascontiguousarray(col, dtype=np.uint64).reshape(-1, 4) for col in instances]
+            ptrs = (C.c_void_p * max(1, len(cols)))(*[col.ctypes.data if col.size else None for col in cols])
+            lens = (C.c_size_t * max(1, len(cols)))(*[col.shape[0] for col in cols])
+            keep += [cols, ptrs, lens]
+            inst_pp[c] = C.cast(ptrs, C.POINTER(C.c_void_p))
+            lens_pp[c] = C.cast(lens, C.POINTER(C.c_size_t))
+        proof = b"" if it.proof is None else bytes(it.proof)
+        buf = (C.c_uint8 * max(1, len(proof))).from_buffer_copy(proof if len(proof) else b"\0")
+        tr = None
+        if it.reader is not None:
+            t, alive = _ffi.read_transcript(it.reader, errors)
+            tr = C.pointer(t)
+            keep.append(alive)
+        is_vk = isinstance(it.key, VerifyingKey)
+        arr[b] = _ffi.VerifyItem(None if is_vk else it.key.h, it.key.h if is_vk else None, it.transcript, it.n_circuits, inst_pp, lens_pp,
+                                 C.addressof(buf), len(proof), tr)
+        keep += [inst_pp, lens_pp, buf, tr]
+    sc = np.ascontiguousarray(combine_scalars, dtype=np.uint64).reshape(-1, 4) if combine_scalars is not None else None
+    assert sc is None or sc.shape[0] == B
+    opts = _ffi.VerifyMixedOpts(C.sizeof(_ffi.VerifyMixedOpts) if opts_size is None else opts_size, C.c_uint64(combine_seed),
+                                sc.ctypes.data if sc is not None else None)
+    keep.append(sc)
+    return arr, opts, (_ffi.ProofStatus * max(1, B))(), keep
+
+
+def verify_proofs_mixed(ctx, items, combine_seed=0, combine_scalars=None, opts_size=None):
+    """amdzk_verify_proofs_mixed: verify_proofs over VerifyItems that each bring their own key — different circuits, k, transcript
+    kinds and proof sizes in one call, all keys made over one G. Returns a Guard with sum_b rho_b (L_b, R_b); statuses[b] is what
+    verify_proofs gives item b under its key. A refused call raises ("verify_proofs_mixed: ...")."""
+    errors = []
+    arr, opts, st, keep = _mixed_args(items, combine_seed, combine_scalars, opts_size, errors)
+    pair = np.zeros(16, dtype=np.uint64)
+    ctx._chk(ctx.L.amdzk_verify_proofs_mixed(ctx.h, arr, len(items), C.byref(opts), st, pair.ctypes.data))
+    del keep
+    g = Guard(pair[:8].copy(), pair[8:].copy(), [ProofStatus(s.status, s.offset) for s in st[:len(items)]])
+    g.errors = errors
+    return g
+
+
+def decide_proofs_mixed(ctx, vparams, items, combined=False, combine_seed=0, combine_scalars=None, opts_size=None):
+    """amdzk_verify_proofs_decide_mixed: decide_proofs over VerifyItems with their own keys; one decode launch and one pairing
+    launch for the whole batch. Returns (verdicts, statuses) as decide_proofs does."""
+    B = len(items)
+    arr, opts, st, keep = _mixed_args(items, combine_seed, combine_scalars, opts_size, [])
+    verdicts = np.zeros(max(1, B), np.uint8)
+    n_valid = C.c_size_t(0)
+    ctx._chk(ctx.L.amdzk_verify_proofs_decide_mixed(ctx.h, vparams.s_g2.h, vparams.g2.h, DECIDE_COMBINED if combined else 0, arr, B, C.byref(opts), st,
+                                                    verdicts.ctypes.data, C.byref(n_valid)))
+    del keep
+    out = [bool(v) for v in verdicts[:B]]
+    assert sum(out) == n_valid.value
+    return out, [ProofStatus(s.status, s.offset) for s in st[:B]]
+
+
 def _kind_or_object(transcript, multiopen):
     """transcript= of verify_proof / decide_proof: the kind flags, or the caller's TranscriptRead object (then `multiopen`,
     0 or MULTIOPEN_GWC, names the opening scheme). Returns (flags, transcripts argument)."""

@@ -1047,6 +1047,53 @@ int amdzk_verify_proofs_decide_vk(amdzk_ctx* ctx, const amdzk_vk* vk, const amdz
                                   const uint8_t* const* proofs, const size_t* proof_lens, const amdzk_verify_opts* opts,
                                   amdzk_proof_status* statuses, uint8_t* verdicts /* n_proofs */, size_t* n_valid);
 
+/* ---- proofs of DIFFERENT circuits verified and decided in one call (ABI 1016): what
+ * amdzk_create_proof_batch_opts produces, taken back. Every item brings its own key — a proving key or a verifying key, exactly
+ * one of pk / vk —, its own transcript kind, instance count, public inputs and proof (bytes, or the caller's read transcript).
+ * Circuits, k, phase tables and proof sizes may differ from item to item. Upstream's AccumulatorStrategy fed by verify_proof
+ * calls under different verifying keys and paired once is amdzk_verify_proofs_decide_mixed with AMDZK_DECIDE_COMBINED.
+ * THE ONE RULE: every key was made over the same G (g[0] of its SRS) — compared by value, so keys over an SRS and over its
+ * amdzk_srs_downsize, and verifying keys read from files, go together; s_g2 / g2 are that setup's. The rule sees G, not the
+ * trapdoor: every amdzk_srs_setup starts from the same generator, so a key over ANOTHER trapdoor passes it — its items are
+ * well formed and fail their pairing, exactly as under amdzk_verify_proofs_decide with the wrong s_g2.
+ * Semantics are amdzk_verify_proofs' and amdzk_verify_proofs_decide's own, item by item: statuses[b] is the status and offset
+ * the single-key call gives that proof under that key (AMDZK_PROOF_BAD_LENGTH against the item's own layout); rho_b belongs to
+ * position b (the b-th draw of combine_seed, or combine_scalars[b]; one item without combine_scalars: 1);
+ * pair_out = sum_b rho_b (L_b, R_b). amdzk_verify_proofs_decide_mixed with flags = 0: verdicts[b] is item b's own check with
+ * weight 1 and ONE pairing launch serves all items; AMDZK_DECIDE_COMBINED: one check for the batch. The identity rule,
+ * AMDZK_DECIDE_RUN and the bound of 2^20 items stay. A batch whose items all name one key gives the single-key call's words.
+ * Device work: items are grouped by (key handle, n_circuits, transcript kind), first seen first; ONE decode launch covers every
+ * (item, element) pair of every group (blocks of 64 threads, no block straddles two items); the combined pair is ONE two-column
+ * MSM over every group's commitments, G and every item's decoded points; per proof, a run's MSM carries the commitments of the
+ * groups present in it. Two host waits per call plus one per run in per-proof mode. The G of every distinct key comes down with
+ * the status words: the rule costs no wait. Read transcripts are called in ascending b.
+ * Refused with AMDZK_E_INVALID and a message that starts "verify_proofs_mixed:" (both calls), naming the item, the ctx stays
+ * usable and the stream is idle: null arguments; n_items = 0 or > 2^20; both or neither of pk / vk; a too-small opts->size; an
+ * unknown transcript kind; a key without a circuit description; a combine_scalars entry >= r; unknown flags; and, before any
+ * MSM, the first item whose key's G differs from item 0's. Every item is validated before anything is uploaded. (A batch
+ * without a well-formed item returns before anything is uploaded: identities, n_valid = 0, the rule unjudged.) */
+typedef struct amdzk_verify_item {
+  const amdzk_pk* pk;                       /* exactly one of pk / vk is non-NULL */
+  const amdzk_vk* vk;
+  int transcript_kind;                      /* as amdzk_verify_opts.transcript_kind, AMDZK_MULTIOPEN_GWC included */
+  uint32_t n_circuits;                      /* circuit instances of this proof; 0 means 1 */
+  const uint64_t* const* const* instances;  /* [circuit][column], as one proof's slice of amdzk_verify_proofs' array */
+  const size_t* const* instance_lens;
+  const uint8_t* proof;                     /* not read when transcript != NULL */
+  size_t proof_len;
+  const amdzk_transcript_read* transcript;  /* NULL: the bytes above; else only AMDZK_MULTIOPEN_GWC of transcript_kind counts */
+} amdzk_verify_item;
+typedef struct amdzk_verify_mixed_opts {
+  size_t size;                     /* sizeof(amdzk_verify_mixed_opts) as the caller compiled it; too small is refused */
+  uint64_t combine_seed;           /* as amdzk_verify_opts */
+  const uint64_t* combine_scalars; /* n_items x 4 words, Montgomery; wins if set */
+} amdzk_verify_mixed_opts;
+int amdzk_verify_proofs_mixed(amdzk_ctx* ctx, const amdzk_verify_item* items, size_t n_items, const amdzk_verify_mixed_opts* opts /* NULL: seed 0 */,
+                              amdzk_proof_status* statuses /* n_items */, uint64_t pair_out[16]);
+int amdzk_verify_proofs_decide_mixed(amdzk_ctx* ctx, const amdzk_g2* s_g2, const amdzk_g2* g2, uint32_t flags, const amdzk_verify_item* items,
+                                     size_t n_items, const amdzk_verify_mixed_opts* opts, amdzk_proof_status* statuses,
+                                     uint8_t* verdicts /* n_items */, size_t* n_valid);
+
 /* ---- witness programs: the advice cells of a batch of proofs computed on the device (ABI 1014).
  * Every create_proof starts from the advice columns, and every entry point above takes them as given (d_advice). For the
  * halo2-base style circuits of the reference, `synthesize` is a fixed straight-line computation over a few per-proof inputs:
