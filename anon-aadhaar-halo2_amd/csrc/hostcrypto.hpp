@@ -187,16 +187,19 @@ class TranscriptWrite {
   virtual void write_scalar(const Fr& s) = 0;
   std::vector<uint8_t> proof;
   bool failed = false;  // a caller-owned transcript reported an error: the proof ends at the next step boundary
+  bool noncanonical = false;  // a caller-owned transcript squeezed words that are not below r: a refusal of its own, same boundary
 };
 
 // The caller's own TranscriptWrite (include/amdzk.h, amdzk_transcript): every call is forwarded, no byte is kept here.
-// Only the refusal to write the identity stays on this side.
+// What stays on this side: the refusal to write the identity, and the rule that a squeezed challenge is a residue.
 class CallbackWrite : public TranscriptWrite {
  public:
   explicit CallbackWrite(const amdzk_transcript& t) : t_(t) {}
   Fr squeeze_challenge() override {
     Fr c = Fr::zero();
     if (t_.squeeze_challenge(t_.user, (uint64_t*)c.l) != 0) failed = true;
+    else if (!bn254::is_canonical(c)) noncanonical = true;  // as the read transcripts refuse it (verifier.hpp CallbackSource)
+    if (failed || noncanonical) c = Fr::zero();                   // never computed with: the proof ends at the step boundary
     return c;
   }
   bool common_point(const bn254::G1Affine& p) override {

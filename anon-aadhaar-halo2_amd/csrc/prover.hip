@@ -344,6 +344,14 @@ int build_multiopen(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, amdzk_pk::M
   return AMDZK_OK;
 }
 
+// What a caller-owned transcript said so far: its own error, or a squeezed challenge that is no residue (CallbackWrite).
+// Asked at every step boundary, and before a challenge is looked at.
+int transcript_status(amdzk_ctx* ctx, const zkhost::TranscriptWrite& T) {
+  if (T.failed) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: the caller's transcript reported an error");
+  if (T.noncanonical) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: a squeezed challenge is not below the modulus");
+  return AMDZK_OK;
+}
+
 // One create_proof in flight: what its phases share, and the phases themselves (create_proof_body runs them in order).
 // pks[c] holds instance c's workspace; `pk` is pks[0]: what the proof has once (transcript representative, random
 // polynomial, h(X), multiopen buffers, staging); every per-circuit step runs in a loop over the instances with `pk`
@@ -608,6 +616,7 @@ struct Prover {
     for (uint32_t i = 0; i < K.num_challenges; i++)
       if (K.challenge_phase[i] == p) {
         chal[i] = challenge("phase challenge");
+        ZK_TRY(transcript_status(ctx, T));  // before the phase callback is handed it
         ZK_TRY(put_challenge(i, chal[i]));
       }
     adv_before += adv_in_phase;
@@ -908,6 +917,8 @@ struct Prover {
   int shplonk_final(const Fr& v, const Fr& u) {
     const size_t nr = mo->grp.sets.size();
     const opening::Final f = opening::shplonk_final(mo->grp, sh, rot_pt.data(), v, u);
+    // 1 / z_0(u) = 0 would zero every coefficient (upstream's invert().unwrap() panics here)
+    if (f.z0_zero) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "create_proof: the challenge u is one of the opening points (probability 2^-254)");
     std::vector<const Fr*> pp(nr + 1);
     for (size_t i = 0; i < nr; i++) pp[i] = pk->sets_L + i * n;
     pp[nr] = pk->hx;
@@ -919,6 +930,19 @@ struct Prover {
     return commit_write(AMDZK_BASIS_G, lx, 1, "shplonk_h2");
   }
 };
+
+// beta = 0 on a key with permutation columns: the permutation factors are evaluated as beta (sigma + w) and
+// beta (delta^j X + w) with w = (v + gamma) / beta
+int beta_usable(amdzk_ctx* ctx, const KeyMaterial& K, const Fr& beta) {
+  if (K.S && beta.is_zero()) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "create_proof: the challenge beta is zero (probability 2^-254): the factored permutation terms need 1 / beta");
+  return AMDZK_OK;
+}
+// x = 0: every rotation of x is the one point 0. Upstream merges opening points by value; the key's opening plan groups
+// them by rotation and would divide by p_t - p_s = 0 (opening::shplonk_sets).
+int x_usable(amdzk_ctx* ctx, const Fr& x) {
+  if (x.is_zero()) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "create_proof: the challenge x is zero (probability 2^-254): rotations of x coincide");
+  return AMDZK_OK;
+}
 
 // pks[i] is a handle of pks[0]'s key and none of the handles before it: what every entry point over several handles asks
 // of each, under its own prefix and its own noun for what a handle stands for.
@@ -967,11 +991,9 @@ int create_proof_body(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, const uin
   zkhost::TranscriptWrite& T = ex.transcript                                  ? (zkhost::TranscriptWrite&)t_caller
                                : transcript_kind == AMDZK_TRANSCRIPT_BLAKE2B ? (zkhost::TranscriptWrite&)t_blake
                                                                              : (zkhost::TranscriptWrite&)t_keccak;
-// a caller-owned transcript that reported an error ends the proof at the next step
-#define T_OK()                                                                                                   \
-  do {                                                                                                           \
-    if (T.failed) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: the caller's transcript reported an error");     \
-  } while (0)
+// a caller-owned transcript that reported an error, or squeezed words that are no residue, ends the proof: asked behind
+// every squeeze, before the challenge is used, and at the step boundaries
+#define T_OK() ZK_TRY(transcript_status(ctx, T))
   amdzk_ctx *B = ctx, *C = ctx;  // the lanes (Prover)
   if (K.use_lanes && NC == 1) {  // several instances: one stream (each lane holds one commitment batch's result at a time)
     ZK_TRY(zk_lane(ctx, 0, &B));
@@ -999,13 +1021,13 @@ int create_proof_body(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, const uin
   ZK_TRY(P.advice(d_advice_all, advice_stride));
   T_OK();
   const Fr theta = P.challenge("theta");
+  T_OK();
   ZK_TRY(P.put_consts({{&KeyMaterial::c_theta, theta}}));
   ZK_TRY(P.lookups());
   const Fr beta = P.challenge("beta");
   const Fr gamma = P.challenge("gamma");
   T_OK();
-  // the permutation factors are evaluated as beta (sigma + w) and beta (delta^j X + w) with w = (v + gamma) / beta
-  if (K.S && beta.is_zero()) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "create_proof: the challenge beta is zero (probability 2^-254): the factored permutation terms need 1 / beta");
+  ZK_TRY(beta_usable(ctx, K, beta));
   ZK_TRY(P.put_consts({{&KeyMaterial::c_beta, beta}, {&KeyMaterial::c_gamma, gamma}, {&KeyMaterial::c_betainv, inv(beta)}}));
   P.tick("  perm: challenges+consts");
   ZK_TRY(P.products());
@@ -1016,15 +1038,21 @@ int create_proof_body(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, const uin
   ZK_TRY(P.vanishing(y));
   const Fr x = P.challenge("x");
   T_OK();
+  ZK_TRY(x_usable(ctx, x));
   ZK_TRY(P.evaluations(x));
   T_OK();
   if (use_gwc) {
-    ZK_TRY(P.gwc(P.challenge("gwc_v")));
+    const Fr v = P.challenge("gwc_v");
+    T_OK();
+    ZK_TRY(P.gwc(v));
   } else {
     const Fr ys = P.challenge("shplonk_y");
     const Fr v = P.challenge("shplonk_v");
+    T_OK();
     ZK_TRY(P.shplonk(ys, v));
-    ZK_TRY(P.shplonk_final(v, P.challenge("u")));
+    const Fr u = P.challenge("u");
+    T_OK();
+    ZK_TRY(P.shplonk_final(v, u));
   }
   P.tick("multiopen");
   T_OK();
@@ -1105,9 +1133,9 @@ struct Gang {
   }
   // a caller-owned transcript that reported an error ends its proof at the step boundary
   void transcript_ok(Member& m) {
-    if (!m.live || !m.T().failed) return;
-    ctx->err = "create_proof: the caller's transcript reported an error";
-    fail(m, AMDZK_E_INVALID);
+    if (!m.live) return;
+    const int r = transcript_status(ctx, m.T());
+    if (r != AMDZK_OK) fail(m, r);
   }
   size_t live() const {
     size_t c = 0;
@@ -1264,6 +1292,7 @@ struct Gang {
     }
     GANG_TRY(each([&](Member& m) -> int {
       const Fr theta = m.P->challenge("theta");
+      ZK_TRY(transcript_status(ctx, m.T()));
       ZK_TRY(m.P->put_consts({{&KeyMaterial::c_theta, theta}}));
       return m.P->lookups_enqueue(0);
     }));
@@ -1272,7 +1301,8 @@ struct Gang {
       ZK_TRY(m.P->lookups_write(0));
       const Fr beta = m.P->challenge("beta");
       const Fr gamma = m.P->challenge("gamma");
-      if (m.pk->key->S && beta.is_zero()) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "create_proof: the challenge beta is zero (probability 2^-254): the factored permutation terms need 1 / beta");
+      ZK_TRY(transcript_status(ctx, m.T()));
+      ZK_TRY(beta_usable(ctx, *m.pk->key, beta));
       ZK_TRY(m.P->put_consts({{&KeyMaterial::c_beta, beta}, {&KeyMaterial::c_gamma, gamma}, {&KeyMaterial::c_betainv, inv(beta)}}));
       return m.P->products_enqueue_serial();
     }));
@@ -1281,19 +1311,24 @@ struct Gang {
       ZK_TRY(m.P->products_write());
       ZK_TRY(m.P->write_points(m.P->cm_rnd.pts, "random_poly"));
       const Fr y = m.P->challenge("y");
+      ZK_TRY(transcript_status(ctx, m.T()));
       ZK_TRY(m.P->put_consts({{&KeyMaterial::c_y, y}}));
       return m.P->vanishing(y);
     }));
     GANG_TRY(commit_step());  // the h pieces, written as they come back
     GANG_TRY(each([&](Member& m) -> int {
       m.x = m.P->challenge("x");
+      ZK_TRY(transcript_status(ctx, m.T()));
+      ZK_TRY(x_usable(ctx, m.x));
       return m.P->evaluations_prepare(m.x);
     }));
     GANG_TRY(evaluate_step());
     if (use_gwc) {
       GANG_TRY(each([&](Member& m) -> int {
         ZK_TRY(m.P->evaluations_write());
-        return m.P->gwc(m.P->challenge("gwc_v"));
+        const Fr v = m.P->challenge("gwc_v");
+        ZK_TRY(transcript_status(ctx, m.T()));
+        return m.P->gwc(v);
       }));
       GANG_TRY(commit_step());
     } else {
@@ -1301,10 +1336,15 @@ struct Gang {
         ZK_TRY(m.P->evaluations_write());
         const Fr ys = m.P->challenge("shplonk_y");
         m.v = m.P->challenge("shplonk_v");
+        ZK_TRY(transcript_status(ctx, m.T()));
         return m.P->shplonk(ys, m.v);
       }));
       GANG_TRY(commit_step());
-      GANG_TRY(each([&](Member& m) -> int { return m.P->shplonk_final(m.v, m.P->challenge("u")); }));
+      GANG_TRY(each([&](Member& m) -> int {
+        const Fr u = m.P->challenge("u");
+        ZK_TRY(transcript_status(ctx, m.T()));
+        return m.P->shplonk_final(m.v, u);
+      }));
       GANG_TRY(commit_step());
     }
     return AMDZK_OK;

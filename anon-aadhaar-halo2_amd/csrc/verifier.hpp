@@ -322,7 +322,9 @@ inline bool instances_ok(const Plan& p, const uint64_t* const* const* inst, cons
 
 // One proof's transcript from its first byte to its last, element after element in read order, challenges where the prover
 // squeezed them. inst / lens: the N circuit instances' public inputs (instances_ok). false: the source failed (never the
-// built-in one), *out is then unusable.
+// built-in one) or x is degenerate — x = 0, where the rotations of x coincide and the prover refuses too, or x^n = 1, where
+// the vanishing identity divides by x^n - 1 and upstream's verifier panics (a hash gives either with probability 2^-254 and
+// n 2^-254) — and the walk ends right behind x's squeeze; *out is then unusable.
 inline bool run_transcript(const Plan& p, Source& T, const Fr& transcript_repr, const uint64_t* const* const* inst, const size_t* const* lens,
                            Challenges* out) {
   const pkblob::Desc& d = *p.d;
@@ -350,8 +352,10 @@ inline bool run_transcript(const Plan& p, Source& T, const Fr& transcript_repr, 
       if (d.challenge_phase[i] == ph && !T.squeeze(&out->chal[i])) return false;
   }
   if (!T.squeeze(&out->theta) || !take(2 * (size_t)N * p.L) || !T.squeeze(&out->beta) || !T.squeeze(&out->gamma)) return false;
-  if (!take((size_t)N * p.nsets + (size_t)N * p.L + 1) || !T.squeeze(&out->y) || !take(p.qdeg) || !T.squeeze(&out->x) || !take(p.NS)) return false;
-  out->yy = Fr::zero();
+  out->yy = out->v = out->u = Fr::zero();
+  if (!take((size_t)N * p.nsets + (size_t)N * p.L + 1) || !T.squeeze(&out->y) || !take(p.qdeg) || !T.squeeze(&out->x)) return false;
+  if (out->x.is_zero() || fr_pow2k(out->x, p.k) == Fr::one()) return false;
+  if (!take(p.NS)) return false;
   if (p.gwc) return T.squeeze(&out->v) && take(p.rots.size()) && T.squeeze(&out->u);
   return T.squeeze(&out->yy) && T.squeeze(&out->v) && take(1) && T.squeeze(&out->u) && take(1);
 }

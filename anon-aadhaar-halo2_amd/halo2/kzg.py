@@ -299,7 +299,8 @@ class _ProverMultiopen:
 
 
 def multiopen(params, polys, points, queries, transcript, scheme=MULTIOPEN_SHPLONK, evals=None, want_points=True, out_cap=None, opts_size=None):
-    """amdzk_multiopen_dev over indexed queries: polys = device addresses (or buffers with .ptr), points (P, 4) uint64,
+    """amdzk_multiopen_dev over indexed queries: polys = device addresses (or buffers with .ptr), points (P, 4) uint64
+    below r (a point, a supplied evaluation or a squeezed challenge that is not raises AmdzkError, AMDZK_E_INVALID),
     queries = amdzk_open_query array or [(polynomial index, point index)]. Returns the written points (n_out, 8), or
     their number with want_points=False. out_cap / opts_size: what to report to the library (tests)."""
     from . import plonk  # the transcript trampolines (late: plonk imports this module)

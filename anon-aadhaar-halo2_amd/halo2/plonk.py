@@ -747,8 +747,10 @@ def create_proof_opts(ctx, pks, instances_list, d_advice_list, seed=0, scalars=N
     """amdzk_create_proof_opts. synthesize(phase, challenges (num_challenges, 4) uint64 Montgomery, hip_stream): fills the
     advice columns of `phase` (>= 1) of every instance on the device before it returns. transcript_object: the caller's
     TranscriptWrite — common_point / write_point take (8,) uint64 affine Montgomery words, common_scalar / write_scalar
-    (4,), squeeze_challenge returns (4,); the proof bytes are then the object's and b"" is returned. `transcript` keeps its
-    MULTIOPEN_GWC bit either way. opts_size: amdzk_proof_opts.size to report (tests)."""
+    (4,), squeeze_challenge returns (4,), a residue below r; the proof bytes are then the object's and b"" is returned.
+    The object's challenges are used as they are: words that are not below r raise AmdzkError (AMDZK_E_INVALID), beta = 0 on a
+    key with permutation columns, x = 0 and SHPLONK's u on an opening point outside the first set AMDZK_E_UNSUPPORTED
+    (include/amdzk.h, amdzk_transcript). `transcript` keeps its MULTIOPEN_GWC bit either way. opts_size: amdzk_proof_opts.size to report (tests)."""
     N = len(pks)
     assert N >= 1 and len(instances_list) == N and len(d_advice_list) == N
     n = 1 << pks[0].desc["k"]
@@ -1057,6 +1059,7 @@ def verify_proofs(ctx, pk, instances_list, proofs, transcript=TRANSCRIPT_BLAKE2B
     transcripts: None, or per proof None (the bytes proofs[b]) or the caller's TranscriptRead object — common_scalar((4,) uint64),
     read_point() -> (8,), read_scalar() -> (4,), squeeze_challenge() -> (4,), Montgomery words; proofs[b] may then be None and of
     `transcript` only MULTIOPEN_GWC counts. An exception in a method makes that proof PROOF_BAD_TRANSCRIPT; Guard.errors keeps them.
+    So does a squeezed challenge that is not below r, and a squeezed x that is 0 or has x^n = 1 (no exception is kept for those).
     opts_size: amdzk_verify_opts.size to report (tests)."""
     B = len(proofs)
     errors = []

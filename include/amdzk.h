@@ -457,7 +457,22 @@ typedef int (*amdzk_phase_fn)(void* user, uint32_t phase, const uint64_t* challe
 /* A caller-owned TranscriptWrite (`&mut T: TranscriptWrite` on the other side): the library forwards every call and keeps
  * no bytes. Scalars are Montgomery Fr (4 words), points G1Affine (8 words), never the identity (the library refuses to write
  * it, as upstream's transcripts do). Every member returns 0 on success; non-zero ends the proof with AMDZK_E_INVALID.
- * squeeze_challenge writes a Montgomery Fr below the modulus. */
+ * squeeze_challenge writes a Montgomery Fr below the modulus; words that are not below it end the proof with
+ * AMDZK_E_INVALID, "create_proof: a squeezed challenge is not below the modulus" ("multiopen: ..." for amdzk_multiopen_dev),
+ * before the value is used — as the read transcripts' squeezes are refused (AMDZK_PROOF_BAD_TRANSCRIPT).
+ * The challenges are then the CALLER's values, and some values have no proof here. Refused with AMDZK_E_UNSUPPORTED, the
+ * transcript advanced by what was called (everything in front of that squeeze has been written) and the workspace quiet:
+ *   beta = 0 on a key with permutation columns — "create_proof: the challenge beta is zero (probability 2^-254): the
+ *     factored permutation terms need 1 / beta" (upstream proves it);
+ *   x = 0 — "create_proof: the challenge x is zero (probability 2^-254): rotations of x coincide", before anything is
+ *     evaluated at x (upstream merges the coinciding points by value and proves; the key's opening plan tells points apart
+ *     by rotation mod n);
+ *   SHPLONK's u equal to an opening point that is not in the first point set — "create_proof: the challenge u is one of the
+ *     opening points (probability 2^-254)", behind the first opening commitment (upstream panics on 1 / z_0(u)); GWC has no
+ *     such value.
+ * y = 0 on a circuit whose last constraint vanishes is upstream's own refusal: an h(X) commitment is the identity. Every
+ * other value — 0, 1, r - 1, a root of unity (x^n = 1 included), equal challenges — gives upstream's bytes. With a built-in
+ * transcript each of these has the probability named. */
 typedef struct amdzk_transcript {
   void* user;
   int (*common_point)(void* user, const uint64_t xy[8]);
@@ -507,7 +522,7 @@ int amdzk_create_proof_opts(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_circu
  * every proof: statuses[b] (if given) = the returned status and proof_lens[b] (if given) = 0 for all b < n_proofs; its
  * message starts with "create_proof_batch:", never with "proof <b>:".
  * One bad witness does not cost the batch: a proof whose lookup input is not in its table, whose commitment is the identity
- * or whose beta is 0 gets its status in statuses[b] (may be NULL) and proof_lens[b] = 0 and drops out; the others finish
+ * or whose beta is 0 (with a caller's transcript: any refusal listed at amdzk_transcript) gets its status in statuses[b] (may be NULL) and proof_lens[b] = 0 and drops out; the others finish
  * with their exact bytes. Returns AMDZK_OK if every proof succeeded, else the status of the first failing proof, whose usual
  * message amdzk_last_error carries behind "proof <b>: ". After a failure the workspaces are quiet, as after a failed single
  * proof. A HIP or out-of-memory error ends the whole batch with that status for every unfinished proof. */
@@ -551,7 +566,8 @@ int amdzk_create_proof_batch(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_proo
  * callback refused it in phase p"); a non-zero return drops every wanted proof. The other proofs finish with their exact bytes.
  * transcripts: NULL, or n_proofs entries; a NULL entry = the built-in transcript. All five members must be set (checked up
  * front). They are called from the calling thread only, proof after proof in ascending b within a step; a non-zero return
- * drops that proof at the step boundary, as does a refusal to write the identity.
+ * drops that proof at the step boundary, as does a refusal to write the identity; a squeezed challenge that is not below
+ * the modulus, or one of the degenerate values listed at amdzk_transcript, drops that proof before the value is used.
  * Failures are amdzk_create_proof_batch's: a failing proof gets its status, length 0 and "proof <b>: ..", the others finish —
  * proof 0 included; HIP and out-of-memory errors end the batch; the workspaces are quiet afterwards.
  * Refused as a whole with AMDZK_E_INVALID (every status = the returned code, every length 0, the message starts with
@@ -614,7 +630,7 @@ int amdzk_kate_div_dev(amdzk_ctx* ctx, void* const* d_polys, const uint64_t* roo
  * only this, and for any use of the resident SRS as a KZG commitment scheme (commit, then open).
  * d_polys: host array of n_polys device pointers, 2^k coefficients each (k the SRS's), Montgomery; read only, may alias. A
  * polynomial's identity is its INDEX (upstream's PolynomialPointer compares addresses: map addresses to indices). points:
- * n_points x 4 words, Montgomery Fr, any values; two indices with equal values are one point. queries: (polynomial index,
+ * n_points x 4 words, Montgomery Fr, any values below r; two indices with equal values are one point. queries: (polynomial index,
  * point index) pairs in upstream's query order; duplicates are allowed. Entries of d_polys no query names are not read.
  * SHPLONK (scheme 0): queries are grouped commitment -> point set (first seen first), point set -> commitments (sets
  * compared as sorted values, first seen first), the super point set in ascending canonical order; squeeze y, squeeze v,
@@ -635,10 +651,15 @@ int amdzk_kate_div_dev(amdzk_ctx* ctx, void* const* d_polys, const uint64_t* roo
  * on sets, points or queries but memory.
  * Refused with a message that starts "multiopen:", the ctx stays usable and the stream is idle: AMDZK_E_INVALID for null
  * arguments, a missing transcript or transcript member, a too-small opts->size, n_queries = 0, an index out of range, a
- * queried null polynomial, out_cap < n_out with out_points set, an SRS without AMDZK_BASIS_G, a non-zero return of a
- * transcript member, and a commitment that is the identity (e.g. every queried polynomial zero: the library refuses to
- * write the identity, as upstream's transcripts do); AMDZK_E_NOMEM when the scratch cannot be allocated. A refusal after
- * the first squeeze leaves the caller's transcript advanced by what was called. */
+ * queried null polynomial, out_cap < n_out with out_points set, an SRS without AMDZK_BASIS_G, a point ("point <i> is not
+ * below the modulus": every one of the n_points, queried or not) or a supplied evaluation ("evaluation <i> ...") that is not
+ * below r — both before any scratch is reserved or the transcript touched —, a non-zero return of a transcript member, a
+ * squeezed challenge that is not below r, and a commitment that is the identity (e.g. every queried polynomial zero: the
+ * library refuses to write the identity, as upstream's transcripts do); AMDZK_E_UNSUPPORTED for SHPLONK's u equal to an
+ * opening point outside the first point set ("the challenge u is one of the opening points": upstream panics on
+ * 1 / z_0(u); behind the first written point); AMDZK_E_NOMEM when the scratch cannot be allocated. Every other challenge
+ * and point value — 0, 1, r - 1, roots of unity, u on a point of the first set only — gives upstream's points. A refusal
+ * after the first squeeze leaves the caller's transcript advanced by what was called. */
 typedef struct amdzk_open_query {
   uint32_t poly;  /* index into d_polys */
   uint32_t point; /* index into points */
@@ -795,9 +816,12 @@ typedef struct amdzk_proof_status {
  * What read_point / read_scalar hand back is NOT trusted: it is checked in the same decode launch as the bytes of the other
  * proofs — a point must have both coordinates < q, be on y^2 = x^3 + 3 and not be (0, 0) (AMDZK_PROOF_BAD_POINT), a scalar
  * must be < r (AMDZK_PROOF_BAD_SCALAR); `offset` is then the element's index in read order. There is no conversion.
- * AMDZK_PROOF_BAD_TRANSCRIPT: a member returned non-zero, a member is NULL, or a squeezed challenge is >= r; `offset` = the
- * number of read_* calls completed for that proof, and no further member is called for it. The proof drops out like any
- * malformed proof. */
+ * AMDZK_PROOF_BAD_TRANSCRIPT: a member returned non-zero, a member is NULL, a squeezed challenge is >= r, or the squeezed x
+ * is degenerate — x = 0 (the rotations of x coincide; the prover refuses it too) or x^n = 1 (the vanishing identity divides by
+ * x^n - 1: upstream's verifier panics); `offset` = the number of read_* calls completed for that proof (for a degenerate x:
+ * the reads in front of x's squeeze), and no further member is called for it. The proof drops out like any malformed
+ * proof; the single-key, _vk and _mixed calls and their decide forms report it alike. Every other challenge value is
+ * folded as upstream folds it: u on an opening point gives upstream's pair, whose L may be the identity (verdict 0). */
 typedef struct amdzk_transcript_read {
   void* user;
   int (*common_point)(void* user, const uint64_t xy[8]);
@@ -806,7 +830,7 @@ typedef struct amdzk_transcript_read {
   int (*read_scalar)(void* user, uint64_t s_out[4]);
   int (*squeeze_challenge)(void* user, uint64_t out[4]);
 } amdzk_transcript_read;
-#define AMDZK_PROOF_BAD_TRANSCRIPT 5 /* the caller's read transcript failed (amdzk_transcript_read) */
+#define AMDZK_PROOF_BAD_TRANSCRIPT 5 /* the caller's read transcript failed or squeezed x = 0 or an x with x^n = 1 (amdzk_transcript_read) */
 /* size: sizeof(amdzk_verify_opts) as compiled by the caller. The size of the struct before `transcripts` was added (every
  * field in front of it) stays accepted and means transcripts = NULL; any other smaller value is refused.
  * transcripts: NULL, or n_proofs entries. transcripts[b] == NULL: proof b is the bytes proofs[b] / proof_lens[b] read with the

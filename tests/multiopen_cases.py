@@ -62,6 +62,35 @@ def make_case(name):
         q = [(0, 0), (1, 2), (0, 1), (2, 5), (3, 4), (1, 1), (2, 0), (3, 0), (4, 3), (1, 3), (4, 5), (0, 0), (3, 1), (5, 1), (4, 2),
              (3, 2), (6, 0), (3, 3), (5, 0), (2, 5), (6, 0)]
         return Case(6, random_polys(rng, 7, 64), vals, q)
+    if name == "private":
+        # "shared" with a point f that only the polynomials of the FIRST set (0, 2, 5) are opened at: sets of 3, 3, 5 and 1
+        # points, and u = f is a challenge on an opening point at which z_0(u) != 0
+        base = make_case("shared")
+        f = rng.randrange(R)
+        return Case(6, base.polys, base.point_vals + [f], base.queries + [(5, 6), (0, 6), (2, 6)])
+    if name == "edge points":
+        # the set shapes of "shared" — {a, b} (0, 2, 5), {b, c, d} (1, 4), {a, b, c, d, e} (3), one point alone (6) — over
+        # a = 0, b = 1, c = r - 1, d = omega (the generator of the 2^6 roots of unity), e = z and -z alone; index 4 carries
+        # omega^32, which IS r - 1, and index 7 carries 0 again: two indices for one value, twice
+        w = PR.P.omega(6)
+        z = rng.randrange(2, R - 1)
+        vals = [0, 1, R - 1, w, pow(w, 32, R), z, R - z, 0]
+        q = [(0, 0), (1, 2), (0, 1), (2, 1), (3, 5), (1, 1), (2, 7), (3, 0), (4, 3), (1, 3), (4, 1), (0, 7), (3, 1), (5, 1), (4, 4),
+             (3, 2), (6, 6), (3, 3), (5, 0), (2, 1), (6, 6)]
+        return Case(6, random_polys(rng, 7, 64), vals, q)
+    if name == "edge polys":
+        # the queries of "shared" over: a constant (0), the upper half zero (1), X^(n-1) alone (2), random (3, 4), the zero
+        # polynomial in a set with non-zero ones (5: the set of 0 and 2) and a polynomial with a root at its only query point (6)
+        base = make_case("shared")
+        n, a = 64, base.point_vals[0]
+        polys = random_polys(rng, 7, n)
+        polys[0] = [rng.randrange(1, R)] + [0] * (n - 1)
+        polys[1] = polys[1][:n // 2] + [0] * (n // 2)
+        polys[2] = [0] * (n - 1) + [1]
+        polys[5] = [0] * n
+        g = [rng.randrange(1, R) for _ in range(n - 1)]  # (X - a) g(X)
+        polys[6] = [(-a * g[0]) % R] + [(g[i - 1] - a * g[i]) % R for i in range(1, n - 1)] + [g[n - 2]]
+        return Case(6, polys, base.point_vals, base.queries)
     if name == "17 sets":
         vals = [rng.randrange(R) for _ in range(18)]
         return Case(4, random_polys(rng, 17, 16), vals, [(i, i + d) for i in range(17) for d in (0, 1)])

@@ -64,6 +64,19 @@ def make_cases():
     c = with_ids("z0 = 0", rng, 2, vals, [(0, 0), (1, 1), (1, 0)], ranks=False)
     c.u = c.pts[1]
     out.append(c)
+    # degenerate challenges on the "shared" sets: y = 0 keeps the first commitment of a set alone, v = 0 the first set alone,
+    # u = 0 is a point like any other (no point of the case is 0: z_0(u) != 0)
+    c = MC.make_case("shared")
+    evals = [PR.P.eval_polynomial(c.polys[p], c.point_vals[z]) for p, z in c.queries]
+    for what in ("y", "v", "u"):
+        d = with_ids("shared, %s = 0" % what, rng, len(c.polys), c.point_vals, c.queries, ranks=what != "v", evals=evals)
+        setattr(d, what, 0)
+        out.append(d)
+    # the point values 0, 1, r - 1 (under two indices), omega, z, -z, and 0 under a second index
+    c = MC.make_case("edge points")
+    evals = [PR.P.eval_polynomial(c.polys[p], c.point_vals[z]) for p, z in c.queries]
+    out.append(with_ids("edge points", rng, len(c.polys), c.point_vals, c.queries, ranks=True, evals=evals))
+    out.append(with_ids("edge points, first seen", rng, len(c.polys), c.point_vals, c.queries, ranks=False, evals=evals))
     return out
 
 
