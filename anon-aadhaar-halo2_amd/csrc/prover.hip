@@ -1363,12 +1363,13 @@ size_t amdzk_proof_random_count(const amdzk_pk* pk) { return pk ? DrawLayout(*pk
 // permutation set, one per lookup product, the random polynomial, the h pieces, SHPLONK's two — then the
 // evaluations: advice and fixed queries, the random polynomial, sigma columns, 3 per permutation set but 2
 // for the last, 5 per lookup. With AMDZK_MULTIOPEN_GWC the two SHPLONK points become one per opening point.
-// Distinct evaluation points of the proof's queries = distinct rotations (omega^r x are pairwise different
-// for the |r| << n that occur): what ProverGWC writes one witness commitment for.
+// Distinct evaluation points of the proof's queries = distinct rotations modulo n (omega^r x and omega^(r + n) x are one
+// point, as in build_multiopen and the verifier's plan): what ProverGWC writes one witness commitment for.
 static size_t opening_point_count(const KeyMaterial& K) {
-  std::vector<int> rots = {0};  // sigma columns, h(X), the random polynomial
+  std::vector<int64_t> rots = {0};  // sigma columns, h(X), the random polynomial
   auto note = [&](int r) {
-    if (std::find(rots.begin(), rots.end(), r) == rots.end()) rots.push_back(r);
+    const int64_t m = ((int64_t)r % (int64_t)K.n + (int64_t)K.n) % (int64_t)K.n;
+    if (std::find(rots.begin(), rots.end(), m) == rots.end()) rots.push_back(m);
   };
   for (auto& q : K.advice_queries) note(q.second);
   for (auto& q : K.fixed_queries) note(q.second);

@@ -426,7 +426,8 @@ int amdzk_create_proof_multi(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_circ
                              int transcript_kind, uint8_t* proof_out, size_t proof_cap, size_t* proof_len);
 size_t amdzk_proof_size_multi(const amdzk_pk* pk, size_t n_circuits, int transcript_kind);
 /* Exact byte length of the proof for this key, transcript and multiopen scheme (transcript_kind as for
- * amdzk_create_proof_ex, including AMDZK_MULTIOPEN_GWC); a function of the circuit shape only. */
+ * amdzk_create_proof_ex, including AMDZK_MULTIOPEN_GWC); a function of the circuit shape only. (GWC writes one point per
+ * distinct opening point: rotations equal modulo n count once.) */
 size_t amdzk_proof_size(const amdzk_pk* pk, int transcript_kind);
 /* For callers whose `R: RngCore` is not ChaCha20Rng::seed_from_u64: draw
  * amdzk_proof_random_count(pk) scalars with Fr::random(&mut rng) and pass them (Montgomery Fr, in
