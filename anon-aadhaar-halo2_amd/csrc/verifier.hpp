@@ -529,44 +529,11 @@ inline void fold_proof(const Plan& p, const Fr& transcript_repr, const Fr& omega
   fold_challenges(p, omega, inst, lens, scs, rho, ch, Lout, Rout);
 }
 
-// The ONE device reservation of a verify call (verify.hip, verify_core; ZK_WS_STARTUP) and its mirror in pinned memory: n_proofs
-// proofs of E elements each — NP points, NS scalars — staged `stride` bytes apart; nvk commitments of the key. [0, points) goes UP
-// in one copy (a proving key's G is on the device already: its copy ends at `g`, and G follows device to device); the decoder
-// fills points and scalars; [status, msm) comes DOWN in one copy of down_bytes.
-struct DeviceLayout {
-  size_t staging;    // n_proofs x stride: the proofs' bytes, or what a caller's read transcript handed back
-  size_t elems;      // uint2[E]: (byte offset, is_point << 31 | index) of a built-in transcript's elements
-  size_t elems_raw;  // uint2[E]: the same for a read transcript's form (no bytes when no proof has one)
-  size_t form;       // uint8_t[n_proofs]: 1 = this proof came through a read transcript (no bytes when none did)
-  size_t status;     // uint32_t[n_proofs]: the decoder's verdict per proof
-  // commitments | G | points are CONTIGUOUS: the base array G1Affine[nvk + 1 + n_proofs * NP] of the combined MSM
-  size_t vk;         // G1Affine[nvk]: the key's fixed and permutation commitments
-  size_t g;          // G1Affine: the SRS's G
-  size_t points;     // G1Affine[n_proofs * NP]: decoded
-  size_t scalars;    // Fr[n_proofs * NS]: decoded
-  size_t msm;        // Fr[2][nvk + 1 + n_proofs * NP] combined; per proof Fr[2 * run][run_len], ONE run's columns
-  size_t run_bases;  // per proof: G1Affine[run_len], that run's commitments | G | points (= bytes otherwise)
-  size_t bytes, up_bytes, down_bytes;
-  size_t run, run_len;  // per proof: proofs per MSM, at most AMDZK_DECIDE_RUN, and the bases of one
-};
-inline DeviceLayout device_layout(size_t n_proofs, size_t stride, size_t E, size_t NP, size_t NS, size_t nvk, bool transcripts, bool per_proof) {
-  DeviceLayout L;
-  WsLayout w;
-  L.run = n_proofs < AMDZK_DECIDE_RUN ? n_proofs : AMDZK_DECIDE_RUN, L.run_len = nvk + 1 + L.run * NP;
-  L.staging = w.take(n_proofs * stride), L.elems = w.take(E * 8);
-  L.elems_raw = w.take(transcripts ? E * 8 : 0), L.form = w.take(transcripts ? n_proofs : 0), L.status = w.take(n_proofs * 4);
-  L.vk = w.take(nvk * sizeof(G1Affine), 1), L.g = w.take(sizeof(G1Affine), 1), L.points = w.take(n_proofs * NP * sizeof(G1Affine), 1);
-  L.scalars = w.take(n_proofs * NS * sizeof(Fr));
-  L.msm = per_proof ? w.take(2 * L.run * L.run_len * sizeof(Fr)) : w.take(2 * (nvk + 1 + n_proofs * NP) * sizeof(Fr), 1);
-  L.run_bases = w.take(per_proof ? L.run_len * sizeof(G1Affine) : 0, 1);
-  L.bytes = w.bytes(), L.up_bytes = L.points, L.down_bytes = L.msm - L.status;
-  return L;
-}
-
-// ---- a batch over DIFFERENT keys (amdzk_verify_proofs_mixed; verify.hip, verify_mixed_core). Items that name the same key
-// handle, the same number of circuit instances and the same transcript kind form a GROUP: one Plan, one element table, one
-// raw-form table and one block of commitments. Both functions below are pure: tests/native/verifier_mixed_check.cpp runs them
-// alone.
+// ---- a verify call (verify.hip, verify_core), possibly over DIFFERENT keys (amdzk_verify_proofs_mixed, whose name the types
+// below carry). Items that name the same key handle, the same number of circuit instances and the same transcript kind form a
+// GROUP: one Plan, one element table, one raw-form table and one block of commitments; a call over one key is one group and
+// does not need group_items. Both functions below are pure: tests/native/verifier_mixed_check.cpp and workspace_check.cpp run
+// them alone.
 struct MixedKey {
   const void* key;  // the key handle the item names (a proving key's or a verifying key's)
   uint32_t n_circuits;
@@ -591,7 +558,7 @@ inline std::vector<uint32_t> group_items(const MixedKey* keys, size_t n_items, s
   return of;
 }
 
-// What the mixed decode launch reads (verify.hip, proof_decode_mixed_kernel). A block of MIXED_BLOCK threads decodes
+// What the decode launch reads (verify.hip, proof_decode_kernel). A block of MIXED_BLOCK threads decodes
 // elements [first, first + MIXED_BLOCK) of ONE item: no block straddles two items, so its records are wave-uniform.
 constexpr uint32_t MIXED_BLOCK = 64;
 struct MixedItemRec {
@@ -615,9 +582,10 @@ struct MixedGroupShape {
   size_t E, NP, NS, nvk;         // elements, points, scalars of one proof; fixed + permutation commitments of the key
   size_t proof_bytes, raw_bytes;  // one proof in the byte form and in the read-transcript form
 };
-// The ONE device reservation of a mixed call, DeviceLayout's counterpart. [0, g) goes UP in one copy (the G of a proving key
-// then follows device to device into key_g); [status, msm) comes DOWN in one copy: the status words, one G per distinct
-// key — the "same G" rule is judged on what came down —, the commitments, the points and the scalars.
+// The ONE device reservation of a verify call (ZK_WS_STARTUP) and its mirror in pinned memory. [0, g) goes UP in one copy (the
+// G of a proving key then follows device to device into key_g, and key 0's from there into g); the decoder fills points and
+// scalars; [status, msm) comes DOWN in one copy: the status words, one G per distinct key — the "same G" rule is judged on
+// what came down —, the commitments, the points and the scalars.
 struct MixedLayout {
   size_t staging;    // the items' bytes, item b at item_staging[b], item_stride[b] bytes
   size_t items;      // MixedItemRec[n_items]

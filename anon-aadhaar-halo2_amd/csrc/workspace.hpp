@@ -16,8 +16,8 @@
 //          not touch its own pointer afterwards.
 //    Anything else — an outer user that still reads its region after an inner call reserved the slot — needs another slot.
 //  * The pinned buffer has no stream order to lean on (the host reads it) and growth frees it at once: a pointer into it
-//    is dead after ANY call that may reserve it again. Its users are zk_msm_finish (msm.hip), verify_core and
-//    verify_mixed_core (verify.hip), which have read everything they brought down before their first zk_msm_finish, and zk_pairing_products (pairing.hip),
+//    is dead after ANY call that may reserve it again. Its users are zk_msm_finish (msm.hip), verify_core
+//    (verify.hip), which has read everything it brought down before its first zk_msm_finish, and zk_pairing_products (pairing.hip),
 //    which calls nothing between its reservation and its last read.
 // The enum says for every shared slot which case holds and where. Nothing checks this at run time: a new driver picks its
 // slot by reading this file.
@@ -41,7 +41,7 @@ enum ZkWs : int {
   //    points after zk_pairing_products has reserved that one. Nothing it calls touches this slot.
   ZK_WS_STAGING = 2,
   // The start-up calls: SRS setup, read, write, g_to_lagrange, downsize and the prefix-sum basis (srs.hip), (S) one behind
-  // the other. Also verify_core / verify_mixed_core (verify.hip) and zk_pairing_products (pairing.hip) — (N): the decide calls pair
+  // the other. Also verify_core (verify.hip) and zk_pairing_products (pairing.hip) — (N): the decide calls pair
   // after the core has returned, having read all it brought down, and no start-up call runs inside either.
   ZK_WS_STARTUP = 3,
   // zk_poly_eval, zk_lincomb, zk_kate_div (plonk_kernels.hip): partial sums that live for two launches. (S).

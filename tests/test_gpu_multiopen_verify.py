@@ -6,6 +6,7 @@ index for one point value change nothing; amdzk_multiopen_dev followed by amdzk_
 in between; every documented refusal, with the ctx used again after each. The SRS is the test SRS of multiopen_cases.TAU."""
 import ctypes as C
 import os
+import random
 import sys
 
 import numpy as np
@@ -18,7 +19,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import opening_verify_ref as OV  # noqa: E402
 import plonk_ref as PR  # noqa: E402
 import pyref as P  # noqa: E402
-from multiopen_cases import TAU, caps_golden, make_case  # noqa: E402
+from multiopen_cases import TAU, Case, caps_golden, make_case, random_polys  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 E_INVALID, Q, R = -2, zu.Q, zu.R
@@ -193,6 +194,41 @@ def test_an_identity_commitment_is_allowed(ctx, pkg, vparams, scheme):
     o.ch, o.pts = OV.read(scheme, PR.Blake2bRead(o.proof), case.point_vals, case.queries)
     o.ref = OV.pair(scheme, o.coms, case.point_vals, case.queries, o.evals, o.ch, o.pts)
     assert verify(ctx, pkg, o) == o.ref and verify(ctx, pkg, o, vparams=vparams) is True
+
+
+@pytest.mark.parametrize("nb", [63, 64, 65])
+def test_the_points_check_around_one_block_of_64(ctx, pkg, vparams, nb):
+    """The check launch takes commitments | read points | g, one thread each in blocks of 64: nb = 63, 64 and 65 points in
+    all (SHPLONK reads two points: nb - 3 commitments, each opened at one point). The LAST commitment is the identity, the
+    last index below which it is allowed, and the opening holds; the identity one index on — read point 0 — is refused; and
+    when the only bad point is the last read point or g, the last of all at index nb - 1 = 62, 63, 64 (in a block of its own
+    for 65), the refusal names it. (The one other case of this file that is sure to cross 64 points, the 3000 of the caps case,
+    is an accepted opening: no test had a bad point beyond index 63.)"""
+    n_coms = nb - 3
+    rng = random.Random("points check %d" % nb)
+    case = Case(2, random_polys(rng, n_coms, 4), [rng.randrange(R)], [(i, 0) for i in range(n_coms)])
+    case.polys[n_coms - 1] = [0] * case.n
+    o = Opening.__new__(Opening)
+    o.case, o.scheme = case, "shplonk"
+    o.coms, o.evals, o.proof = OV.opening_of(case, "shplonk", TAU)
+    assert o.coms[n_coms - 1] is None and all(c is not None for c in o.coms[:-1])
+    o.ch, o.pts = OV.read("shplonk", PR.Blake2bRead(o.proof), case.point_vals, case.queries)
+    assert len(o.coms) + len(o.pts) + 1 == nb
+    o.ref = OV.pair("shplonk", o.coms, case.point_vals, case.queries, o.evals, o.ch, o.pts)
+    assert verify(ctx, pkg, o) == o.ref and verify(ctx, pkg, o, vparams=vparams) is True
+
+    def refused(expect, transcript=None, g=G):
+        coms, points, queries, evals = o.args()
+        with pytest.raises(pkg.ffi.AmdzkError) as e:
+            pkg.kzg.multiopen_verify(ctx, g, coms, points, queries, evals, transcript or Reading(PR.Blake2bRead(o.proof)), flag(pkg, "shplonk"))
+        assert e.value.code == E_INVALID and expect in str(e.value), e.value
+        assert verify(ctx, pkg, o) == o.ref  # the ctx is used again
+
+    refused("multiopen_verify: read point 0 ", Reading(PR.Blake2bRead(o.proof), replace={0: np.zeros(8, np.uint64)}))
+    off_curve = lambda p: words((p[0], (p[1] + 1) % Q))
+    refused("multiopen_verify: read point 1 ", Reading(PR.Blake2bRead(o.proof), replace={1: off_curve(o.pts[1])}))  # index nb - 2
+    refused("multiopen_verify: g has ", g=off_curve(P.G1_GEN))  # index nb - 1
+    refused("multiopen_verify: g has ", g=np.zeros(8, np.uint64))
 
 
 # ------------------------------------------------------------------------------------ prove, then verify: no oracle between

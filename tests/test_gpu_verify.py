@@ -210,6 +210,44 @@ def test_decode_classes_at_the_first_a_middle_and_the_last_element(plonk, rigs, 
         assert ints(one) == case.pair(m) and not VR.holds(ints(one), TAU)
 
 
+@pytest.mark.parametrize("target", [63, 65, 67])
+def test_a_bad_element_on_either_side_of_a_decode_block_in_a_single_key_batch(ctx, pkg, plonk, oracle, target):
+    """The decode launch takes one block per (proof, 64 elements): proofs of E = 63 elements (one block, not full), of
+    E = 65 (a second block of one element; elements 63 and 64 are the opening's two points) and of E = 67 (63 and 64 are scalars). In a batch of three, element 0, 63, 64 and E - 1 of the MIDDLE proof — those that
+    exist — are corrupted one at a time, as a point or as a scalar, whichever the element is: the status names that byte offset
+    and class, the neighbours stay well formed and the pair is that of the two good proofs under the same weights. Through a
+    proving key and through a verifying key."""
+    from test_gpu_verify_mixed import Own, padded_to  # that module imports this one
+    params = pkg.kzg.ParamsKZG.setup(ctx, 4, zu.fr_from_int(TAU))
+    rig = Own(ctx, pkg, plonk, oracle, "mixed_padded%d" % target, padded_to(plonk, target), params)
+    vk = rig.pk.get_vk()
+    try:
+        cases = [rig.case("blake2b", "shplonk", seed=40 + b) for b in range(3)]
+        proofs = [c.proof for c in cases]
+        kinds = VR.element_kinds(cases[0].desc, 1)
+        E = len(kinds)
+        assert E == target == len(proofs[1]) // 32 and len(set(proofs)) == 3
+        elements = sorted({e for e in (0, 63, 64, E - 1) if e < E})
+        assert [(e, kinds[e]) for e in elements] == {63: [(0, "p"), (62, "p")], 65: [(0, "p"), (63, "p"), (64, "p")],
+                                                     67: [(0, "p"), (63, "s"), (64, "s"), (66, "p")]}[target]
+        bad = {"p": [(bytes(32), 2), (nonresidue_x().to_bytes(32, "little"), 2)], "s": [(R.to_bytes(32, "little"), 3), ((2 ** 256 - 1).to_bytes(32, "little"), 3)]}
+        sc = np.stack([zu.fr_from_int(v) for v in (0x1357, R - 2, 0x2468ACE)])
+        for key in (rig.pk, vk):
+            want = rig.verify(cases[0], [proofs[0], proofs[2]], pk=key, combine_scalars=sc[[0, 2]])
+            assert want.well_formed and VR.holds(ints(want), TAU)
+            for e in elements:
+                for data, cls in bad[kinds[e]]:
+                    m = put(proofs[1], 32 * e, data)
+                    assert cases[1].decode(m) == (cls, 32 * e), "the reference decode disagrees with the expectation"
+                    g = rig.verify(cases[0], [proofs[0], m, proofs[2]], pk=key, combine_scalars=sc)
+                    assert [tuple(s) for s in g.statuses] == [(0, 0), (cls, 32 * e), (0, 0)], (e, cls)
+                    assert np.array_equal(g.lhs, want.lhs) and np.array_equal(g.rhs, want.rhs), (e, cls)
+    finally:
+        vk.free()
+        rig.free()
+        params.free()
+
+
 # ------------------------------------------------------------------------------------ random single-byte mutations
 @pytest.mark.parametrize("transcript,multiopen,seed", [("blake2b", "shplonk", 21), ("evm", "gwc", 2)])
 def test_random_single_byte_mutations_agree_with_the_oracle(plonk, rigs, transcript, multiopen, seed):

@@ -1,18 +1,20 @@
 """CPU: csrc/workspace.hpp's offset counter and the byte layouts built on it — verify_core's one reservation
-(verifier::device_layout) and the pairing's image and per-call layouts (pairing.hpp) — through a stand-alone program
-(tests/native/workspace_check.cpp, plain g++). Every offset is compared with the formulas the drivers carried before the
-layouts had a type, restated here; nothing is compared with a second call into the code under test. Once more in a build
-with ASan + UBSan (no sanitizer goes on anything loaded into Python)."""
+(verifier::mixed_layout, for a call of one group) and the pairing's image and per-call layouts (pairing.hpp) — through a
+stand-alone program (tests/native/workspace_check.cpp, plain g++). Every offset is compared with formulas restated in Python
+(the pairing's here, the verify call's in verify_layout_model.py); nothing is compared with a second call into the code under
+test. Once more in a build with ASan + UBSan (no sanitizer goes on anything loaded into Python)."""
 import os
 import subprocess
 
 import pytest
 
+from verify_layout_model import FR, G1, PER_GROUP, PER_ITEM, REGIONS, TOTALS, restate
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "native", "workspace_check.cpp")
 _exe = {}
 
-G1, FR, FQ, UINT2, PTR = 64, 32, 32, 8, 8  # bytes of G1Affine, Fr, Fq, uint2, a pointer
+FQ, PTR = 32, 8  # bytes of Fq, a pointer (G1Affine and Fr: verify_layout_model)
 FQ2X = 2 * 9 * 4  # an Fq2 of two stored-form Fq: nine 29-bit limbs each
 DECIDE_RUN, PAIRING_MAX_M, CHUNK_LANES, K_COUNT = 16, 16, 16384, 17  # include/amdzk.h, pairing.hip as it was, pairing.hpp
 NUM_LINES = 64 + bin(0x9D797039BE763BA8).count("1") + 2  # fq12.cuh: a line per doubling, per set bit of 6u + 2 below the top, two Frobenius lines
@@ -76,46 +78,44 @@ def test_round_up_of_element_counts_to_four(ask):
     assert ask(["round 256 0 1 256 257", "round 1 0 1 7"]) == [[0, 256, 256, 512], [0, 1, 7]]
 
 
-def verify_layout(n_proofs, psize, E, NP, NS, nvk, n_tr, per_proof):
-    """verify_core's offsets as it computed them itself (a verifying key: its G goes up with its commitments)"""
-    nbases = nvk + 1 + n_proofs * NP
-    o_elems = pad256(n_proofs * psize)
-    o_eraw = o_elems + pad256(E * UINT2)
-    o_form = o_eraw + (pad256(E * UINT2) if n_tr else 0)
-    o_status = o_form + (pad256(n_proofs) if n_tr else 0)
-    o_vk = o_status + pad256(n_proofs * 4)
-    o_g = o_vk + nvk * G1
-    o_points = o_g + G1
-    o_dsc = o_points + n_proofs * NP * G1
-    run = min(n_proofs, DECIDE_RUN)
-    run_len = nvk + 1 + run * NP
-    o_msm = pad256(o_dsc + n_proofs * NS * 32)
-    o_rb = pad256(o_msm + 2 * run * run_len * 32)
-    total = o_rb + run_len * G1 if per_proof else o_msm + 2 * nbases * 32
-    return {"staging": 0, "elems": o_elems, "elems_raw": o_eraw, "form": o_form, "status": o_status, "vk": o_vk, "g": o_g, "points": o_points,
-            "scalars": o_dsc, "msm": o_msm, "run_bases": o_rb if per_proof else total, "bytes": total, "up_bytes": o_points,
-            "down_bytes": o_msm - o_status, "run": run, "run_len": run_len}
-
-
-VERIFY_CASES = [(1, 1984, 70, 40, 30, 12, 0, 0), (3, 4160, 70, 40, 30, 12, 1, 0), (17, 1984, 70, 40, 30, 12, 0, 1), (16, 64, 1, 1, 0, 0, 1, 1)]
+# (n_proofs, stride, E, NP, NS, nvk, read transcripts, per proof): one proof, a batch through read transcripts, one past a run of
+# AMDZK_DECIDE_RUN, a run of one-point proofs, and element counts at and one past a decode block
+VERIFY_CASES = [(1, 1984, 70, 40, 30, 12, 0, 0), (3, 4160, 70, 40, 30, 12, 1, 0), (17, 1984, 70, 40, 30, 12, 0, 1), (16, 64, 1, 1, 0, 0, 1, 1),
+                (2, 2048, 64, 30, 34, 5, 0, 0), (2, 2080, 65, 31, 34, 6, 1, 1)]
 
 
 def test_verify_layout_offsets_totals_and_what_the_kernels_rely_on(ask):
+    """verify_core's one reservation for a call of ONE group, against the Python model of the layout (verify_layout_model,
+    shared with test_verifier_mixed_host.py, which covers many groups)."""
     rows = ask(["verify " + " ".join(map(str, c)) for c in VERIFY_CASES])
     for case, row in zip(VERIFY_CASES, rows):
-        want = verify_layout(*case)
-        got = dict(zip(want.keys(), row))
-        assert len(row) == len(want) and got == want, case
-        n, _stride, _E, NP, NS, nvk, _tr, _pp = case
+        n, stride, E, NP, NS, nvk, tr, pp = case
+        want = restate([(E, NP, NS, nvk, stride, stride)], [(0, tr)] * n, 1, pp)
+        fields = [(name, 1) for name in REGIONS + TOTALS] + [(name, n) for name in PER_ITEM] + [(name, 1) for name in PER_GROUP]
+        assert len(row) == sum(count for _, count in fields), case  # every field printed, none skipped
+        got, at = {}, 0
+        for name, count in fields:
+            got[name], at = row[at:at + count], at + count
+        assert [got[r][0] for r in REGIONS] == want["regions"] and [got[t][0] for t in TOTALS] == want["totals"], case
+        for name in PER_ITEM + PER_GROUP:
+            assert got[name] == want[name], (case, name)
+        got = {name: v[0] if name in REGIONS + TOTALS else v for name, v in got.items()}
         # commitments | G | points: the MSM's base array, no gap
         assert got["g"] == got["vk"] + nvk * G1 and got["points"] == got["g"] + G1 and got["scalars"] == got["points"] + n * NP * G1, case
-        # the decoder and the MSM load points and scalars as 32-byte words
-        for name in ("staging", "vk", "g", "points", "scalars", "msm", "run_bases"):
+        # the decoder and the MSM load points and scalars as 32-byte words: every region, and every proof in the staging area
+        for name in REGIONS:
             assert got[name] % 32 == 0, (case, name)
-        # the upload ends where the decoded regions begin; the download is status .. scalars, whole
-        assert got["up_bytes"] == got["points"], case
+        assert got["item_staging"] == [b * stride for b in range(n)] and stride % 32 == 0 and got["item_stride"] == [stride] * n, case
+        assert got["item_points"] == [b * NP for b in range(n)] and got["item_scalars"] == [b * NS for b in range(n)], case
+        # the upload ends where G begins (it follows device to device); the download is status .. scalars, whole
+        assert got["up_bytes"] == got["g"] and got["staging"] == 0, case
         assert got["status"] + got["down_bytes"] == got["msm"] >= got["scalars"] + n * NS * FR, case
-    assert verify_layout(*VERIFY_CASES[2])["run"] == DECIDE_RUN and VERIFY_CASES[2][0] == DECIDE_RUN + 1, "the case past one run"
+        assert got["bytes"] >= got["run_bases"] + (got["run_len"] * G1 if pp else 0) and got["run_bases"] >= got["msm"], case
+        # one single-wave block per (proof, 64 elements)
+        assert got["n_blocks"] == n * ((E + 63) // 64) and got["n_elems"] == E and got["n_points"] == n * NP and got["n_scalars"] == n * NS, case
+        assert got["run"] == min(n, DECIDE_RUN) and got["run_len"] == (nvk + 1 + got["run"] * NP if pp else 0), case
+    assert VERIFY_CASES[2][0] == DECIDE_RUN + 1 and VERIFY_CASES[2][7] == 1, "the case past one run"
+    assert [(c[2] + 63) // 64 for c in VERIFY_CASES[3:]] == [1, 1, 2], "one element, a full block, one past it"
 
 
 def test_pairing_image_and_call_layouts(ask):

@@ -2,13 +2,16 @@
 """Time amdzk_verify_proofs at the metric shape (workloads.full_aadhaar_shape, k = 15) on one GPU and write
 profiles/verify_batch.txt.
 
-    python tools/verify_bench.py [--k 15] [--reps 5] [--batches 1,8,64] [--vk] [--out FILE] [--append]
+    python tools/verify_bench.py [--shape full|gate] [--k 15] [--reps 5] [--batches 1,8,64] [--vk] [--out FILE] [--append]
 
 The proofs are made by the device prover in the same process (distinct seeds). For every batch size: the host wall clock
 around the blocking call (median of --reps after one warm-up), in total and per proof; and, from one more call with every
 kernel event-bracketed (amdzk_prof_*), the device time of the decode kernel and of the MSM's kernels, and that call's host
 time (its wall clock minus both; bracketed kernels run one at a time). No pairing is computed and no pair is checked: that
 is the test suite's business. Every status must be "well formed" or the run stops.
+
+--shape gate times the smallest proofs instead: the one-gate circuit of tools/verify_mixed_bench.py at k = 4 (480 bytes, 15
+elements), where the call is launches and host work and the decode launch takes one block per proof (--k is not read).
 
 --vk adds the same calls through a verifying key (amdzk_verify_proofs_vk with pk.get_vk()), alternating with the pk route
 rep by rep, as a second table: wall clock of both routes side by side. The two pairs must be equal word for word or the
@@ -35,6 +38,7 @@ def fr_from_int(x):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--shape", choices=["full", "gate"], default="full", help="full_aadhaar_shape at --k, or the k = 4 gate circuit")
     ap.add_argument("--k", type=int, default=15)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--batches", default="1,8,64")
@@ -47,7 +51,11 @@ def main():
 
     pkg = ge.load_package()
     plonk, wl = pkg.plonk, pkg.workloads
-    c = wl.full_aadhaar_shape(k=args.k)
+    if args.shape == "gate":
+        from verify_mixed_bench import small_circuit
+        c = small_circuit(plonk, wl, 4, 0, 0)
+    else:
+        c = wl.full_aadhaar_shape(k=args.k)
     n = c.n
     with pkg.Context(0) as ctx:
         params = pkg.kzg.ParamsKZG.setup(ctx, c.k, fr_from_int(0x1234567890ABCDEF1234567))
@@ -79,8 +87,8 @@ def main():
             return (time.perf_counter() - t0) * 1e3, out
 
         lines = ["amdzk_verify_proofs, %s" % pkg.build_info()["text"],
-                 "shape: full_aadhaar_shape k = %d: %d advice, %d fixed, %d instance columns, %d lookups, %d permutation columns; proof of %d bytes"
-                 % (c.k, len(c.advice), len(c.fixed), len(c.instances), len(c.desc["lookups"]), len(c.desc["permutation_columns"]), len(made[0])),
+                 "shape: %s k = %d: %d advice, %d fixed, %d instance columns, %d lookups, %d permutation columns; proof of %d bytes"
+                 % ("gate" if args.shape == "gate" else "full_aadhaar_shape", c.k, len(c.advice), len(c.fixed), len(c.instances), len(c.desc["lookups"]), len(c.desc["permutation_columns"]), len(made[0])),
                  "Blake2b transcript, SHPLONK; proofs by the device prover in the same process; one process, one GPU",
                  "wall: host wall clock around the blocking call, median of %d after one warm-up" % args.reps,
                  "decode / msm / host: one more call with every kernel event-bracketed (kernels then run one at a time):",
