@@ -3,7 +3,9 @@
 //   plonk::prover::create_proof, plonk::{permutation,lookup,vanishing}::prover,
 //   poly::kzg::multiopen::{shplonk::ProverSHPLONK, gwc::ProverGWC}.
 // The key it proves with is keygen.hip's (pk.hpp), its programs program.hip's. The order of transcript operations and RNG
-// draws follows SURVEY.md Appendix A.
+// draws follows SURVEY.md Appendix A and is stated in ONE place, prove_steps, over a driver: Solo runs it for one proof
+// (lanes, several instances, the caller's phase callback), Gang for a lock-step batch (merged MSMs and evaluations). The
+// steps themselves are Prover's; the two batch entry points share one refusal routine (batch_refusals) behind two adapters.
 //
 // Control flow, Fiat-Shamir and the O(columns) bookkeeping stay on the host; every O(n) step is a
 // kernel on resident columns: all committed columns of a phase go through ONE batched MSM, all
@@ -352,7 +354,10 @@ int transcript_status(amdzk_ctx* ctx, const zkhost::TranscriptWrite& T) {
   return AMDZK_OK;
 }
 
-// One create_proof in flight: what its phases share, and the phases themselves (create_proof_body runs them in order).
+// One create_proof in flight: what its steps share, and the steps themselves (prove_steps below states their order, for a
+// proof alone and for the members of a batch alike). A step the transcript waits for comes in two halves — *_enqueue: all
+// the work up to the commitments' launch; *_write: their points into the transcript — and the driver collects the
+// commitments in between (Solo: nothing to do, the halves launch and finish their own batches; Gang: one merged MSM).
 // pks[c] holds instance c's workspace; `pk` is pks[0]: what the proof has once (transcript representative, random
 // polynomial, h(X), multiopen buffers, staging); every per-circuit step runs in a loop over the instances with `pk`
 // shadowed by that instance's key.
@@ -376,16 +381,19 @@ struct Prover {
   const RandomSource& rng;
   const DrawLayout draws;
   Commit cm_rnd;
-  std::vector<Commit> cm_zp, cm_zl;  // per instance
-  // the multiopen lists (the key's) and what evaluations() leaves for the opening argument
+  std::vector<Commit> cm_adv, cm_lk, cm_zp, cm_zl;  // per instance, between the two halves of their step
+  // the multiopen lists (the key's) and what the evaluation step leaves for the opening argument
   amdzk_pk::Multiopen* mo = nullptr;
   std::vector<Fr> rot_pt, evals;  // the points x * omega^rot, once per distinct rotation; the evaluations
   opening::Shplonk sh;
-  amdzk_phase_fn phase_fn = nullptr;  // amdzk_proof_opts: the caller's synthesize of phases >= 1
-  void* phase_user = nullptr;
+  // the caller's columns: instances_all[ci][col] / instance_lens_all[ci][col] (either may be null), d_advice_all[ci]
+  const uint64_t* const* const* instances_all = nullptr;
+  const size_t* const* instance_lens_all = nullptr;
+  const void* const* d_advice_all = nullptr;
+  size_t advice_stride = 0;
+  Fr sh_v;  // SHPLONK's v, squeezed in front of its first commitment and used again for its second
   // Member of a gang (serial, one instance): commit_begin / commit_write leave their batch here instead of launching it
   std::vector<DeferredCommit>* sink = nullptr;
-  Commit cm_adv, cm_lk;                     // the advice and permuted-lookup batches between their two halves (advice_enqueue / _write)
   // a phased key between phases_begin and the last phase_write: the challenges so far (zero: not yet squeezed), the advice
   // columns of the phases below and of the phase in flight, and that phase's batches, one per (instance, run of columns)
   std::vector<Fr> chal;
@@ -398,7 +406,7 @@ struct Prover {
 
   Prover(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, amdzk_ctx* B, amdzk_ctx* C, zkhost::TranscriptWrite& T, const RandomSource& rng)
       : ctx(ctx), pks(pks), pk(pks[0]), K(*pk->key), NC(NC), n(K.n), usable(K.n - (K.bf + 1)), A(K.A), I(K.I), L(K.L), ns(K.nsets),
-        bf(K.bf), M(ctx), B(B), C(C), serial(B == ctx), T(T), rng(rng), draws(K, NC), cm_zp(NC), cm_zl(NC), tlast(now_ms()) {}
+        bf(K.bf), M(ctx), B(B), C(C), serial(B == ctx), T(T), rng(rng), draws(K, NC), cm_adv(NC), cm_lk(NC), cm_zp(NC), cm_zl(NC), tlast(now_ms()) {}
 
   static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
   void tick(const char* label) {
@@ -506,7 +514,7 @@ struct Prover {
   }
 
   // 0. vk, instances
-  int instances(const uint64_t* const* const* instances_all, const size_t* const* instance_lens_all) {
+  int instances() {
     T.common_scalar(K.transcript_repr);
     for (size_t ci = 0; ci < NC && I; ci++) {  // columns are zero beyond the caller's values: clear on the device, upload only what was given
       amdzk_pk* const pk = pks[ci];
@@ -549,36 +557,44 @@ struct Prover {
     }
     return AMDZK_OK;
   }
-  // 1. advice of a key with challenge phases (amdzk_keygen_phased), upstream's order: phase after phase, and inside a phase
-  // instance after instance, the phase's columns (runs of consecutive columns of the arena) are copied in, blinded,
-  // committed and written; then the phase's challenges are squeezed into their constant slots. Phases >= 1 start with the
-  // caller's callback, which fills their columns of d_advice from the challenges so far.
-  int advice_phased(const void* const* d_advice_all, size_t advice_stride) {
-    ZK_TRY(phases_begin());
-    for (uint32_t p = 0; p < K.nphases; p++) {
-      if (p > 0) {
-        const int r = phase_fn(phase_user, p, (const uint64_t*)chal.data(), K.num_challenges, (void*)ctx->stream);
-        if (r != 0) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: the phase callback returned %d in phase %u", r, p);
-      }
-      ZK_TRY(phase_enqueue(p, d_advice_all, advice_stride));
-      ZK_TRY(phase_write(p));
+  // 1. advice, phase after phase (a key without challenge phases: everything in phase 0). enqueue: copy in, blind the
+  // unusable rows of every column, launch the commitments; write: their points, then the phase's challenges.
+  int advice_enqueue(uint32_t p) {
+    if (!K.phased()) {
+      for (size_t ci = 0; ci < NC && p == 0; ci++) ZK_TRY(plain_enqueue(ci));
+      return AMDZK_OK;
     }
-    ZK_TRY(commit_end(cm_rnd));
-    tick("advice (phased)");
+    if (p == 0) ZK_TRY(phases_begin());
+    return p < K.nphases ? phase_enqueue(p) : AMDZK_OK;
+  }
+  int advice_write(uint32_t p) {
+    if (K.phased()) return p < K.nphases ? phase_write(p) : AMDZK_OK;
+    for (size_t ci = 0; ci < NC && p == 0; ci++) {
+      ZK_TRY(commit_end(cm_adv[ci]));
+      ZK_TRY(write_points(cm_adv[ci].pts, "advice"));
+    }
     return AMDZK_OK;
   }
-  // ... phase by phase in two halves, so that a gang (amdzk_create_proof_batch_opts) commits a phase's batches of all its
-  // provers between them and calls its own callback in front: the challenges start at zero (the last proof's values are
-  // gone); [the callback]; the phase's runs of columns copied in, blinded, transformed and their commitments launched —
-  // one batch per run, finished at once on this path (a context holds one batch's result at a time), handed to the gang
-  // with a sink; then the points written in that order and the phase's challenges squeezed.
+  int advice_done() {
+    ZK_TRY(commit_end(cm_rnd));  // long done; lane C's MSM workspace is free for the lookup products' commitment
+    tick(K.phased() ? "advice (phased)" : "advice");
+    return AMDZK_OK;
+  }
+  // A key with challenge phases (amdzk_keygen_phased), upstream's order: phase after phase, and inside a phase instance
+  // after instance, the phase's columns (runs of consecutive columns of the arena) are copied in, blinded, committed and
+  // written; then the phase's challenges are squeezed into their constant slots. Phases >= 1 start with the caller's
+  // callback (the driver's phase_callback), which fills their columns of d_advice from the challenges so far.
+  // The challenges start at zero (the last proof's values are gone); [the callback]; the phase's runs of columns copied
+  // in, blinded, transformed and their commitments launched — one batch per run, finished at once without a sink (a
+  // context holds one batch's result at a time), handed to the gang with one; then the points written in that order and
+  // the phase's challenges squeezed.
   int phases_begin() {
     chal.assign(K.num_challenges, Fr::zero());
     for (uint32_t i = 0; i < K.num_challenges; i++) ZK_TRY(put_challenge(i, chal[i]));
     adv_before = 0;
     return AMDZK_OK;
   }
-  int phase_enqueue(uint32_t p, const void* const* d_advice_all, size_t advice_stride) {
+  int phase_enqueue(uint32_t p) {
     std::vector<std::pair<uint32_t, uint32_t>> runs;  // (first column, count)
     size_t in_phase = 0;
     for (uint32_t c = 0; c < A; c++)
@@ -622,45 +638,31 @@ struct Prover {
     adv_before += adv_in_phase;
     return AMDZK_OK;
   }
-  // 1. advice: copy in, blind the unusable rows of every column, commit
-  int advice(const void* const* d_advice_all, size_t advice_stride) {
-    if (K.phased()) return advice_phased(d_advice_all, advice_stride);
-    for (size_t ci = 0; ci < NC; ci++) {
-      ZK_TRY(advice_enqueue(ci, d_advice_all ? d_advice_all[ci] : nullptr, advice_stride));
-      ZK_TRY(commit_end(cm_adv));
-      ZK_TRY(advice_write());
-    }
-    ZK_TRY(commit_end(cm_rnd));  // long done; lane C's MSM workspace is free for the lookup products' commitment
-    tick("advice");
-    return AMDZK_OK;
-  }
-  // ... in two halves per instance, so that a gang (amdzk_create_proof_batch) commits the batches of all its provers between
-  // them: everything up to the commitment's launch (with a sink: its hand-over to the gang), then the points' write
-  int advice_enqueue(size_t ci, const void* d_advice, size_t advice_stride) {
+  // an unphased key's advice, instance ci: everything up to the commitment's launch (with a sink: its hand-over to the gang)
+  int plain_enqueue(size_t ci) {
+    const void* d_advice = d_advice_all ? d_advice_all[ci] : nullptr;
     amdzk_pk* const pk = pks[ci];
     if (A) {
       ZK_HIP(ctx, hipMemcpy2DAsync(pk->adv(), n * 32, d_advice, advice_stride * 32, n * 32, A, hipMemcpyDeviceToDevice, ctx->stream));
       ZK_TRY(blind(M, pk->adv(), A, usable, bf + 1, draws.advice(ci), draws.col));
     }
-    cm_adv = Commit();
-    if (A && !serial) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->adv(), A, cm_adv));
-    ZK_TRY(transforms_on_B(pk, M, 0, (size_t)A + I, cm_adv.begun));
-    if (A && !cm_adv.begun) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->adv(), A, cm_adv));
+    Commit& cm = cm_adv[ci] = Commit();
+    if (A && !serial) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->adv(), A, cm));
+    ZK_TRY(transforms_on_B(pk, M, 0, (size_t)A + I, cm.begun));
+    if (A && !cm.begun) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->adv(), A, cm));
     return AMDZK_OK;
   }
-  int advice_write() { return write_points(cm_adv.pts, "advice"); }
-  // 2. lookups: compress, permute (on the device), blind, commit — the same two halves per instance
-  int lookups() {
-    for (size_t ci = 0; ci < NC && L; ci++) {
-      ZK_TRY(lookups_enqueue(ci));
-      ZK_TRY(commit_end(cm_lk));
-      ZK_TRY(lookups_write(ci));
-    }
+  // 2. lookups: compress, permute (on the device), blind, commit — every instance's enqueue, then every instance's write
+  int lookups_enqueue() {
+    for (size_t ci = 0; ci < NC && L; ci++) ZK_TRY(lookups_enqueue(ci));
+    return AMDZK_OK;
+  }
+  int lookups_write() {
+    for (size_t ci = 0; ci < NC && L; ci++) ZK_TRY(lookups_write(ci));
     tick("lookups_permuted");
     return AMDZK_OK;
   }
   int lookups_enqueue(size_t ci) {
-    if (!L) return AMDZK_OK;
     amdzk_pk* const pk = pks[ci];
     ZK_TRY(run_program(ctx, pk, pk->prog_compress, false, pk->d_outs_compress, nullptr, "expr_lookup_compress"));
     ZK_TRY(d2d(ctx, pk->la(), pk->ci, (size_t)L * n * 32));
@@ -673,17 +675,17 @@ struct Prover {
     tick("  lookup: device permute");
     ZK_TRY(blind(M, pk->la(), L, usable, bf + 1, draws.lookup(ci), draws.lk_col));
     ZK_TRY(blind(M, pk->ls(), L, usable, bf + 1, draws.lookup(ci) + draws.col, draws.lk_col));
-    cm_lk = Commit();
-    if (!serial) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->la(), 2 * L, cm_lk));
-    ZK_TRY(transforms_on_B(pk, M, (size_t)A + I, 2 * (size_t)L, cm_lk.begun));
-    if (!cm_lk.begun) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->la(), 2 * L, cm_lk));
+    Commit& cm = cm_lk[ci] = Commit();
+    if (!serial) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->la(), 2 * L, cm));
+    ZK_TRY(transforms_on_B(pk, M, (size_t)A + I, 2 * (size_t)L, cm.begun));
+    if (!cm.begun) ZK_TRY(commit_begin(M, AMDZK_BASIS_G_LAGRANGE, pk->la(), 2 * L, cm));
     return AMDZK_OK;
   }
   int lookups_write(size_t ci) {
-    if (!L) return AMDZK_OK;
     amdzk_pk* const pk = pks[ci];
+    ZK_TRY(commit_end(cm_lk[ci]));  // the wait behind which the error word is down
     if (*pk->h_err) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: lookup %d input not in table (ConstraintSystemFailure)", *pk->h_err - 1);
-    const std::vector<G1Affine>& cm = cm_lk.pts;
+    const std::vector<G1Affine>& cm = cm_lk[ci].pts;
     for (uint32_t l = 0; l < L; l++) {
       std::vector<G1Affine> two = {cm[l], cm[L + l]};
       ZK_TRY(write_points(two, "lookup_permuted"));
@@ -723,7 +725,7 @@ struct Prover {
   }
   // 3. + 4. permutation grand products on M, lookup grand products on C (they depend on beta and gamma only, not on
   // each other). (Several instances: every instance's permutation products are committed before the first lookup product.)
-  int products() {
+  int products_enqueue() {
     if (!serial) {
       // Lanes (one instance): the HOST enqueues M's chain first — seven launches the transcript waits for — and lane C's
       // lookup products (a dozen launches and a commitment batch's fourteen) while M's fractions and inversion run: the
@@ -732,13 +734,9 @@ struct Prover {
       if (ns) ZK_TRY(perm_products(0));
       if (L) ZK_TRY(lookup_products(0, true));
       if (ns) ZK_TRY(perm_commit(0));
-    } else {
-      ZK_TRY(products_enqueue_serial());
+      if (ns) ZK_TRY(transforms_on_B(pk, M, (size_t)A + I + 2 * L, ns, true));
+      return AMDZK_OK;
     }
-    if (ns && !serial) ZK_TRY(transforms_on_B(pk, M, (size_t)A + I + 2 * L, ns, true));  // lanes: one instance
-    return products_write();
-  }
-  int products_enqueue_serial() {
     for (size_t ci = 0; ci < NC && L; ci++) ZK_TRY(lookup_products(ci, false));
     for (size_t ci = 0; ci < NC && ns; ci++) {
       ZK_TRY(perm_products(ci));
@@ -786,18 +784,8 @@ struct Prover {
   }
   // 7. evaluations: h_poly = sum_i piece_i * x^(n i), then one list of (polynomial, rotation) in proof order and the
   //    extra evaluation SHPLONK needs (h_poly at x; random at x is already in the list)
-  int evaluations(const Fr& x) {
-    ZK_TRY(evaluations_prepare(x));
-    const size_t nq = ev_pp.size();
-    ZK_TRY(h2d_staged(ctx, pk, pk->ptrs, ev_pp.data(), nq * sizeof(Fr*)));
-    ZK_TRY(upload_small_on(M, ev_pts, 0));
-    ZK_TRY(zk_poly_eval(ctx, (const Fr* const*)pk->ptrs, pk->small, pk->small + nq, nq, (uint32_t)n));
-    evals.resize(nq);
-    ZK_TRY(d2h(ctx, evals.data(), pk->small + nq, nq * 32));
-    return evaluations_write();
-  }
-  // ... in three parts, so that a gang evaluates the pairs of all its provers in one launch behind one wait: h_poly and
-  // the pairs (ev_pp, ev_pts); [the evaluation into `evals`]; the written evaluations
+  //    — in three parts: h_poly and the pairs (ev_pp, ev_pts); [the driver's evaluate_step fills `evals`: one launch behind
+  //    one wait for this proof alone, or for all the members of a gang]; the written evaluations
   int evaluations_prepare(const Fr& x) {
     {
       const Fr xn = pow_u64(x, n);
@@ -953,6 +941,143 @@ int check_handle(amdzk_ctx* ctx, const char* who, const char* noun, amdzk_pk* co
   return AMDZK_OK;
 }
 
+// The transcript one proof writes to — the caller's, or the built-in one of `kind` — and its random source: owned
+// together, by a proof alone and by every member of a gang. The Prover keeps references into it.
+struct ProofIO {
+  zkhost::Blake2bWrite t_blake;
+  zkhost::Keccak256Write t_keccak;
+  std::unique_ptr<zkhost::CallbackWrite> t_caller;
+  RandomSource rng;
+  ProofIO(const amdzk_transcript* caller, const RandomSource& rng) : t_caller(caller ? new zkhost::CallbackWrite(*caller) : nullptr), rng(rng) {}
+  ProofIO(const ProofIO&) = delete;
+  zkhost::TranscriptWrite& T(int kind) {  // kind: without the AMDZK_MULTIOPEN_GWC bit
+    if (t_caller) return *t_caller;
+    return kind == AMDZK_TRANSCRIPT_BLAKE2B ? (zkhost::TranscriptWrite&)t_blake : (zkhost::TranscriptWrite&)t_keccak;
+  }
+};
+
+// THE ORDER of create_proof, stated once (plonk/prover.rs [UP]): instances, advice phase after
+// phase, theta, the permuted lookup columns, beta and gamma, the permutation and lookup products, the random polynomial,
+// y, h(X), x, the evaluations, the opening argument. Inside a step everything is written circuit instance after circuit
+// instance; the challenges, the random polynomial and h(X) exist once.
+// The driver says for whom and how the shared work is done:
+//   each(f)            f for every live prover; a failure ends that prover's proof, and so does its transcript's status
+//   commit_step()      collects the commitments the provers launched or deferred in the step before
+//   evaluate_step()    fills every prover's `evals` from the pairs evaluations_prepare left
+//   phase_callback(p)  the caller's synthesize of phase p >= 1
+// Solo (one proof, lanes or one stream, NC instances) and Gang (a lock-step batch) below are the two drivers.
+// A caller-owned transcript that reported an error, or squeezed words that are no residue, ends its proof: asked behind
+// every squeeze before the challenge is used, behind the written evaluations, and by the drivers at every step boundary.
+template <class Driver>
+int prove_steps(Driver& D, bool use_gwc, uint32_t phases) {
+  amdzk_ctx* const ctx = D.ctx;
+  ZK_TRY(D.each([&](Prover& P) -> int {
+    ZK_TRY(P.instances());
+    ZK_TRY(transcript_status(ctx, P.T));
+    return P.random_poly();
+  }));
+  ZK_TRY(D.commit_step());  // the random polynomial (a gang; alone it stays on lane C until the advice is written)
+  for (uint32_t p = 0; p < phases; p++) {
+    if (p > 0) ZK_TRY(D.phase_callback(p));
+    ZK_TRY(D.each([&](Prover& P) -> int { return P.advice_enqueue(p); }));
+    ZK_TRY(D.commit_step());
+    ZK_TRY(D.each([&](Prover& P) -> int {
+      ZK_TRY(P.advice_write(p));
+      return p + 1 == phases ? P.advice_done() : AMDZK_OK;
+    }));
+  }
+  ZK_TRY(D.each([&](Prover& P) -> int {
+    const Fr theta = P.challenge("theta");
+    ZK_TRY(transcript_status(ctx, P.T));
+    ZK_TRY(P.put_consts({{&KeyMaterial::c_theta, theta}}));
+    return P.lookups_enqueue();
+  }));
+  ZK_TRY(D.commit_step());
+  ZK_TRY(D.each([&](Prover& P) -> int {
+    ZK_TRY(P.lookups_write());
+    const Fr beta = P.challenge("beta");
+    const Fr gamma = P.challenge("gamma");
+    ZK_TRY(transcript_status(ctx, P.T));
+    ZK_TRY(beta_usable(ctx, P.K, beta));
+    ZK_TRY(P.put_consts({{&KeyMaterial::c_beta, beta}, {&KeyMaterial::c_gamma, gamma}, {&KeyMaterial::c_betainv, inv(beta)}}));
+    P.tick("  perm: challenges+consts");
+    return P.products_enqueue();
+  }));
+  ZK_TRY(D.commit_step());  // the lookup products over g_lagrange, the permutation products' differences over its prefix sums
+  ZK_TRY(D.each([&](Prover& P) -> int {
+    ZK_TRY(P.products_write());
+    ZK_TRY(P.write_points(P.cm_rnd.pts, "random_poly"));  // 5. vanishing: the random polynomial, committed at the start
+    const Fr y = P.challenge("y");
+    ZK_TRY(transcript_status(ctx, P.T));
+    ZK_TRY(P.put_consts({{&KeyMaterial::c_y, y}}));
+    return P.vanishing(y);
+  }));
+  ZK_TRY(D.commit_step());  // the h pieces, written as they come back
+  ZK_TRY(D.each([&](Prover& P) -> int {
+    const Fr x = P.challenge("x");
+    ZK_TRY(transcript_status(ctx, P.T));
+    ZK_TRY(x_usable(ctx, x));
+    return P.evaluations_prepare(x);
+  }));
+  ZK_TRY(D.evaluate_step());
+  ZK_TRY(D.each([&](Prover& P) -> int {
+    ZK_TRY(P.evaluations_write());
+    ZK_TRY(transcript_status(ctx, P.T));
+    if (use_gwc) {
+      const Fr v = P.challenge("gwc_v");
+      ZK_TRY(transcript_status(ctx, P.T));
+      return P.gwc(v);
+    }
+    const Fr ys = P.challenge("shplonk_y");
+    P.sh_v = P.challenge("shplonk_v");
+    ZK_TRY(transcript_status(ctx, P.T));
+    return P.shplonk(ys, P.sh_v);
+  }));
+  ZK_TRY(D.commit_step());
+  if (!use_gwc) {
+    ZK_TRY(D.each([&](Prover& P) -> int {
+      const Fr u = P.challenge("u");
+      ZK_TRY(transcript_status(ctx, P.T));
+      return P.shplonk_final(P.sh_v, u);
+    }));
+    ZK_TRY(D.commit_step());
+  }
+  return D.each([&](Prover& P) -> int {
+    P.tick("multiopen");
+    return AMDZK_OK;
+  });
+}
+
+// The driver of one proof on its own: one Prover with its lanes and its NC instances. Without a sink the halves of a step
+// launch their own commitment batches and finish them (commit_end) where they write them, so there is nothing to collect.
+struct Solo {
+  amdzk_ctx* const ctx;
+  Prover& P;
+  amdzk_phase_fn phase_fn;  // amdzk_proof_opts: the caller's synthesize of phases >= 1
+  void* phase_user;
+  template <class F>
+  int each(F f) {
+    ZK_TRY(f(P));
+    return transcript_status(ctx, P.T);
+  }
+  int commit_step() { return AMDZK_OK; }
+  int phase_callback(uint32_t p) {
+    const int r = phase_fn(phase_user, p, (const uint64_t*)P.chal.data(), P.K.num_challenges, (void*)ctx->stream);
+    if (r != 0) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: the phase callback returned %d in phase %u", r, p);
+    return AMDZK_OK;
+  }
+  // the pairs through the key's own pointer table and small buffer: one launch, one download
+  int evaluate_step() {
+    amdzk_pk* const pk = P.pk;
+    const size_t nq = P.ev_pp.size();
+    ZK_TRY(h2d_staged(ctx, pk, pk->ptrs, P.ev_pp.data(), nq * sizeof(Fr*)));
+    ZK_TRY(P.upload_small_on(P.M, P.ev_pts, 0));
+    ZK_TRY(zk_poly_eval(ctx, (const Fr* const*)pk->ptrs, pk->small, pk->small + nq, nq, (uint32_t)P.n));
+    P.evals.resize(nq);
+    return d2h(ctx, P.evals.data(), pk->small + nq, nq * 32);
+  }
+};
+
 // What amdzk_create_proof_opts adds to a proof: the caller's transcript and its synthesize of the later phases.
 struct ProofExtras {
   const amdzk_transcript* transcript = nullptr;
@@ -962,9 +1087,7 @@ struct ProofExtras {
 
 // One proof over NC instances of the circuit (upstream's `circuits: &[C]`, `instances: &[&[&[F]]]`): pks[c] holds
 // instance c's workspace — the key itself for c = 0, workspace clones of it for the others (amdzk_pk_clone_workspace).
-// Upstream's order (plonk/prover.rs [UP]): instances, advice, lookup permutations, permutation products and lookup
-// products are each written circuit after circuit; the challenges, the random polynomial and h(X) exist once; the
-// evaluations are advice (per circuit), fixed, random, sigma, permutation products (per circuit), lookups (per circuit).
+// Its refusals, its lanes and the Solo driver; the order is prove_steps'.
 int create_proof_body(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, const uint64_t* const* const* instances_all,
                       const size_t* const* instance_lens_all, const void* const* d_advice_all, size_t advice_stride, const RandomSource& rng,
                       int transcript_kind, uint8_t* proof_out, size_t proof_cap, size_t* proof_len, const ProofExtras& ex) {
@@ -979,21 +1102,11 @@ int create_proof_body(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, const uin
     ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: the key has advice in %u phases: amdzk_create_proof_opts with a phase callback is needed", K.nphases);
   const bool use_gwc = (transcript_kind & AMDZK_MULTIOPEN_GWC) != 0;
   transcript_kind &= ~AMDZK_MULTIOPEN_GWC;
-  zkhost::Blake2bWrite t_blake;
-  zkhost::Keccak256Write t_keccak;
   if (!ex.transcript && transcript_kind != AMDZK_TRANSCRIPT_BLAKE2B && transcript_kind != AMDZK_TRANSCRIPT_KECCAK256_EVM)
     ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: unknown transcript kind %d", transcript_kind);
   if (ex.transcript && (!ex.transcript->common_point || !ex.transcript->common_scalar || !ex.transcript->write_point ||
                         !ex.transcript->write_scalar || !ex.transcript->squeeze_challenge))
     ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: amdzk_transcript has a null member");
-  const amdzk_transcript no_transcript = {};
-  zkhost::CallbackWrite t_caller(ex.transcript ? *ex.transcript : no_transcript);
-  zkhost::TranscriptWrite& T = ex.transcript                                  ? (zkhost::TranscriptWrite&)t_caller
-                               : transcript_kind == AMDZK_TRANSCRIPT_BLAKE2B ? (zkhost::TranscriptWrite&)t_blake
-                                                                             : (zkhost::TranscriptWrite&)t_keccak;
-// a caller-owned transcript that reported an error, or squeezed words that are no residue, ends the proof: asked behind
-// every squeeze, before the challenge is used, and at the step boundaries
-#define T_OK() ZK_TRY(transcript_status(ctx, T))
   amdzk_ctx *B = ctx, *C = ctx;  // the lanes (Prover)
   if (K.use_lanes && NC == 1) {  // several instances: one stream (each lane holds one commitment batch's result at a time)
     ZK_TRY(zk_lane(ctx, 0, &B));
@@ -1012,51 +1125,15 @@ int create_proof_body(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, const uin
     }
   } latency_mode(ctx, B, C, !serial && !(getenv("AMDZK_LATENCY_MODE") && atoi(getenv("AMDZK_LATENCY_MODE")) == 0));
 
-  Prover P(ctx, pks, NC, B, C, T, rng);
-  P.phase_fn = ex.phase_fn;
-  P.phase_user = ex.phase_user;
-  ZK_TRY(P.instances(instances_all, instance_lens_all));
-  T_OK();
-  ZK_TRY(P.random_poly());
-  ZK_TRY(P.advice(d_advice_all, advice_stride));
-  T_OK();
-  const Fr theta = P.challenge("theta");
-  T_OK();
-  ZK_TRY(P.put_consts({{&KeyMaterial::c_theta, theta}}));
-  ZK_TRY(P.lookups());
-  const Fr beta = P.challenge("beta");
-  const Fr gamma = P.challenge("gamma");
-  T_OK();
-  ZK_TRY(beta_usable(ctx, K, beta));
-  ZK_TRY(P.put_consts({{&KeyMaterial::c_beta, beta}, {&KeyMaterial::c_gamma, gamma}, {&KeyMaterial::c_betainv, inv(beta)}}));
-  P.tick("  perm: challenges+consts");
-  ZK_TRY(P.products());
-  ZK_TRY(P.write_points(P.cm_rnd.pts, "random_poly"));  // 5. vanishing: the random polynomial, committed at the start
-  const Fr y = P.challenge("y");
-  T_OK();
-  ZK_TRY(P.put_consts({{&KeyMaterial::c_y, y}}));
-  ZK_TRY(P.vanishing(y));
-  const Fr x = P.challenge("x");
-  T_OK();
-  ZK_TRY(x_usable(ctx, x));
-  ZK_TRY(P.evaluations(x));
-  T_OK();
-  if (use_gwc) {
-    const Fr v = P.challenge("gwc_v");
-    T_OK();
-    ZK_TRY(P.gwc(v));
-  } else {
-    const Fr ys = P.challenge("shplonk_y");
-    const Fr v = P.challenge("shplonk_v");
-    T_OK();
-    ZK_TRY(P.shplonk(ys, v));
-    const Fr u = P.challenge("u");
-    T_OK();
-    ZK_TRY(P.shplonk_final(v, u));
-  }
-  P.tick("multiopen");
-  T_OK();
-#undef T_OK
+  ProofIO io(ex.transcript, rng);
+  zkhost::TranscriptWrite& T = io.T(transcript_kind);
+  Prover P(ctx, pks, NC, B, C, T, io.rng);
+  P.instances_all = instances_all;
+  P.instance_lens_all = instance_lens_all;
+  P.d_advice_all = d_advice_all;
+  P.advice_stride = advice_stride;
+  Solo solo{ctx, P, ex.phase_fn, ex.phase_user};
+  ZK_TRY(prove_steps(solo, use_gwc, std::max<uint32_t>(K.nphases, 1)));
   *proof_len = T.proof.size();
   if (proof_out) {
     if (proof_cap < T.proof.size()) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: proof buffer too small (%zu < %zu)", proof_cap, T.proof.size());
@@ -1078,9 +1155,9 @@ int create_proof_impl(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t ncirc, const 
 
 
 // amdzk_create_proof_batch / _batch_opts: B independent proofs — of one circuit, or of different circuits on one SRS —
-// advanced in lock-step on the caller's stream. Every member
-// is a Prover of its own (one instance, no lanes) with its own key, transcript, random source and workspace, and walks
-// create_proof_body's steps in their order; what the members of a step have in common is done once for all of them:
+// advanced in lock-step on the caller's stream: prove_steps' other driver. Every member is a Prover of its own (one
+// instance, no lanes, a sink for its commitments) with its own key, transcript, random source and workspace; what the
+// members of a step have in common is done once for all of them:
 //   * every commitment step — the random polynomial, advice (per challenge phase: one step each), A' / S', the permutation and lookup products (together),
 //     the h pieces, SHPLONK's two or GWC's witnesses — is ONE pointer-table MSM (zk_msm_dev_xyzz_cols) over the live
 //     members' columns, one host wait and one download, the points handed back per member (DeferredCommit);
@@ -1095,21 +1172,20 @@ struct Gang {
   struct Member {
     size_t index = 0;
     amdzk_pk* pk = nullptr;
-    zkhost::Blake2bWrite t_blake;
-    zkhost::Keccak256Write t_keccak;
-    std::unique_ptr<zkhost::CallbackWrite> t_caller;  // amdzk_batch_proof_opts::transcripts[index], if the proof has one
-    RandomSource rng;
+    std::unique_ptr<ProofIO> io;  // amdzk_batch_proof_opts::transcripts[index], if the proof has one, or the built-in kind
     std::unique_ptr<Prover> P;
     std::vector<DeferredCommit> deferred;
     bool live = true;
     int status = AMDZK_OK;
     std::string err;
-    Fr x, v;  // the challenges a later step of the same member needs again
     zkhost::TranscriptWrite& T() { return P->T; }
   };
   amdzk_ctx* const ctx;
   std::vector<std::unique_ptr<Member>> members;
   int fatal = AMDZK_OK;  // a status that is not one witness's: the batch ends
+  amdzk_batch_phase_fn phase_fn = nullptr;  // amdzk_batch_proof_opts: the batch's synthesize of phases >= 1
+  void* phase_user = nullptr;
+  size_t challenge_stride = 0;  // the largest number of challenges among the members' keys
   explicit Gang(amdzk_ctx* ctx) : ctx(ctx) {}
 
   void fail(Member& m, int r) {
@@ -1124,7 +1200,7 @@ struct Gang {
   int each(F f) {
     for (auto& m : members) {
       if (!m->live) continue;
-      const int r = f(*m);
+      const int r = f(*m->P);
       if (r != AMDZK_OK) fail(*m, r);
       else transcript_ok(*m);
       if (fatal != AMDZK_OK) return fatal;
@@ -1136,11 +1212,6 @@ struct Gang {
     if (!m.live) return;
     const int r = transcript_status(ctx, m.T());
     if (r != AMDZK_OK) fail(m, r);
-  }
-  size_t live() const {
-    size_t c = 0;
-    for (auto& m : members) c += m->live ? 1 : 0;
-    return c;
   }
   // device scratch of the gang's own (pointer tables, evaluation points and results). Valid until the next call (the slot may grow).
   int scratch(size_t bytes, char** out) { return zk_ws_reserve(ctx, ZK_WS_STAGING, bytes, (void**)out); }
@@ -1201,7 +1272,7 @@ struct Gang {
 
   // The callback of phase p >= 1 (amdzk_batch_phase_fn), once for the whole batch, if some live member's key has the phase.
   // The gang holds nothing across it: its device scratch is per step, and every member's work is on the stream.
-  int phase_callback(uint32_t p, amdzk_batch_phase_fn fn, void* user, size_t challenge_stride) {
+  int phase_callback(uint32_t p) {
     const size_t N = members.size();
     std::vector<uint8_t> wanted(N, 0);
     std::vector<uint64_t> ch(std::max<size_t>(4 * N * challenge_stride, 1), 0);
@@ -1214,7 +1285,7 @@ struct Gang {
         if (!m->P->chal.empty()) memcpy(&ch[4 * m->index * challenge_stride], m->P->chal.data(), m->P->chal.size() * 32);
       }
     if (!any) return AMDZK_OK;
-    const int r = fn(user, p, N, wanted.data(), ch.data(), challenge_stride, rc.data(), (void*)ctx->stream);
+    const int r = phase_fn(phase_user, p, N, wanted.data(), ch.data(), challenge_stride, rc.data(), (void*)ctx->stream);
     for (auto& m : members) {
       if (!m->live) continue;
       char b[160];
@@ -1258,98 +1329,6 @@ struct Gang {
     return AMDZK_OK;
   }
 
-#define GANG_TRY(x)                      \
-  do {                                   \
-    const int _g = (x);                  \
-    if (_g != AMDZK_OK) return _g;       \
-  } while (0)
-  // create_proof_body's steps, each for all live members
-  // phases: the largest phase count among the members' keys (1: no key has later phases); the members of a phased key walk
-  // Prover::advice_phased's halves, phase after phase with ONE submission each, the others commit their advice with phase 0
-  // and sit the later phases out
-  int run(const uint64_t* const* const* instances, const size_t* const* instance_lens, const void* const* d_advice, size_t advice_stride,
-          bool use_gwc, uint32_t phases = 1, amdzk_batch_phase_fn phase_fn = nullptr, void* phase_user = nullptr, size_t challenge_stride = 0) {
-    GANG_TRY(each([&](Member& m) -> int {
-      const uint64_t* const* inst = instances ? instances[m.index] : nullptr;
-      const size_t* lens = instance_lens ? instance_lens[m.index] : nullptr;
-      ZK_TRY(m.P->instances(&inst, &lens));
-      return m.P->random_poly();
-    }));
-    GANG_TRY(commit_step());  // the random polynomials (basis g)
-    for (uint32_t p = 0; p < phases; p++) {
-      if (p > 0) GANG_TRY(phase_callback(p, phase_fn, phase_user, challenge_stride));
-      GANG_TRY(each([&](Member& m) -> int {
-        const void* adv = d_advice ? d_advice[m.index] : nullptr;
-        if (!m.pk->key->phased()) return p == 0 ? m.P->advice_enqueue(0, adv, advice_stride) : AMDZK_OK;
-        if (p == 0) ZK_TRY(m.P->phases_begin());
-        return p < m.pk->key->nphases ? m.P->phase_enqueue(p, &adv, advice_stride) : AMDZK_OK;
-      }));
-      GANG_TRY(commit_step());
-      GANG_TRY(each([&](Member& m) -> int {
-        if (!m.pk->key->phased()) return p == 0 ? m.P->advice_write() : AMDZK_OK;
-        return p < m.pk->key->nphases ? m.P->phase_write(p) : AMDZK_OK;
-      }));
-    }
-    GANG_TRY(each([&](Member& m) -> int {
-      const Fr theta = m.P->challenge("theta");
-      ZK_TRY(transcript_status(ctx, m.T()));
-      ZK_TRY(m.P->put_consts({{&KeyMaterial::c_theta, theta}}));
-      return m.P->lookups_enqueue(0);
-    }));
-    GANG_TRY(commit_step());
-    GANG_TRY(each([&](Member& m) -> int {
-      ZK_TRY(m.P->lookups_write(0));
-      const Fr beta = m.P->challenge("beta");
-      const Fr gamma = m.P->challenge("gamma");
-      ZK_TRY(transcript_status(ctx, m.T()));
-      ZK_TRY(beta_usable(ctx, *m.pk->key, beta));
-      ZK_TRY(m.P->put_consts({{&KeyMaterial::c_beta, beta}, {&KeyMaterial::c_gamma, gamma}, {&KeyMaterial::c_betainv, inv(beta)}}));
-      return m.P->products_enqueue_serial();
-    }));
-    GANG_TRY(commit_step());  // the lookup products over g_lagrange, the permutation products' differences over its prefix sums
-    GANG_TRY(each([&](Member& m) -> int {
-      ZK_TRY(m.P->products_write());
-      ZK_TRY(m.P->write_points(m.P->cm_rnd.pts, "random_poly"));
-      const Fr y = m.P->challenge("y");
-      ZK_TRY(transcript_status(ctx, m.T()));
-      ZK_TRY(m.P->put_consts({{&KeyMaterial::c_y, y}}));
-      return m.P->vanishing(y);
-    }));
-    GANG_TRY(commit_step());  // the h pieces, written as they come back
-    GANG_TRY(each([&](Member& m) -> int {
-      m.x = m.P->challenge("x");
-      ZK_TRY(transcript_status(ctx, m.T()));
-      ZK_TRY(x_usable(ctx, m.x));
-      return m.P->evaluations_prepare(m.x);
-    }));
-    GANG_TRY(evaluate_step());
-    if (use_gwc) {
-      GANG_TRY(each([&](Member& m) -> int {
-        ZK_TRY(m.P->evaluations_write());
-        const Fr v = m.P->challenge("gwc_v");
-        ZK_TRY(transcript_status(ctx, m.T()));
-        return m.P->gwc(v);
-      }));
-      GANG_TRY(commit_step());
-    } else {
-      GANG_TRY(each([&](Member& m) -> int {
-        ZK_TRY(m.P->evaluations_write());
-        const Fr ys = m.P->challenge("shplonk_y");
-        m.v = m.P->challenge("shplonk_v");
-        ZK_TRY(transcript_status(ctx, m.T()));
-        return m.P->shplonk(ys, m.v);
-      }));
-      GANG_TRY(commit_step());
-      GANG_TRY(each([&](Member& m) -> int {
-        const Fr u = m.P->challenge("u");
-        ZK_TRY(transcript_status(ctx, m.T()));
-        return m.P->shplonk_final(m.v, u);
-      }));
-      GANG_TRY(commit_step());
-    }
-    return AMDZK_OK;
-  }
-#undef GANG_TRY
 };
 
 }  // namespace
@@ -1455,41 +1434,36 @@ int amdzk_create_proof_opts(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_circu
                            proof_len, ex);
 }
 
-// What amdzk_create_proof_batch_opts adds to a batch: per-proof transcripts of the caller's and the batch's phase callback.
-struct BatchExtras {
-  const amdzk_transcript* const* transcripts = nullptr;
-  amdzk_batch_phase_fn phase_fn = nullptr;
-  void* phase_user = nullptr;
-};
-
 // The body of both batch entry points, behind their refusals: one Gang member per proof, the run, and every proof's bytes,
 // length and status. A proof with a transcript of its own has length 0: the bytes are its caller's.
 static int prove_gang(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_proofs, const uint64_t* const* const* instances,
-                      const size_t* const* instance_lens, const void* const* d_advice, size_t advice_stride, int transcript_kind,
-                      const uint64_t* rng_seeds, const uint64_t* const* scalars, const BatchExtras& ex, uint8_t* proofs_out, size_t proof_stride,
-                      size_t* proof_lens, int* statuses) {
-  const bool use_gwc = (transcript_kind & AMDZK_MULTIOPEN_GWC) != 0;
-  const int kind = transcript_kind & ~AMDZK_MULTIOPEN_GWC;
+                      const size_t* const* instance_lens, const void* const* d_advice, size_t advice_stride,
+                      const amdzk_batch_proof_opts& o, uint8_t* proofs_out, size_t proof_stride, size_t* proof_lens, int* statuses) {
+  const bool use_gwc = (o.transcript_kind & AMDZK_MULTIOPEN_GWC) != 0;
+  const int kind = o.transcript_kind & ~AMDZK_MULTIOPEN_GWC;
   Gang g(ctx);
-  uint32_t phases = 1;
-  size_t challenge_stride = 0;
+  g.phase_fn = o.phase_fn;
+  g.phase_user = o.phase_user;
+  uint32_t phases = 1;  // the largest phase count among the members' keys: the others sit the later phases out
   for (size_t b = 0; b < n_proofs; b++) {
     std::unique_ptr<Gang::Member> m(new Gang::Member);
     m->index = b;
     m->pk = pks[b];
     phases = std::max(phases, pks[b]->key->nphases);
-    challenge_stride = std::max<size_t>(challenge_stride, pks[b]->key->num_challenges);
-    if (scalars) m->rng.scalars = scalars[b];
-    else m->rng = RandomSource(rng_seeds[b]);
-    if (ex.transcripts && ex.transcripts[b]) m->t_caller.reset(new zkhost::CallbackWrite(*ex.transcripts[b]));
-    zkhost::TranscriptWrite& T = m->t_caller                          ? (zkhost::TranscriptWrite&)*m->t_caller
-                                 : kind == AMDZK_TRANSCRIPT_BLAKE2B ? (zkhost::TranscriptWrite&)m->t_blake
-                                                                     : (zkhost::TranscriptWrite&)m->t_keccak;
-    m->P.reset(new Prover(ctx, &pks[b], 1, ctx, ctx, T, m->rng));  // B = C = ctx: one stream, no lanes
+    g.challenge_stride = std::max<size_t>(g.challenge_stride, pks[b]->key->num_challenges);
+    RandomSource rng;
+    if (o.scalars) rng.scalars = o.scalars[b];
+    else rng = RandomSource(o.rng_seeds[b]);
+    m->io.reset(new ProofIO(o.transcripts ? o.transcripts[b] : nullptr, rng));
+    m->P.reset(new Prover(ctx, &pks[b], 1, ctx, ctx, m->io->T(kind), m->io->rng));  // B = C = ctx: one stream, no lanes
     m->P->sink = &m->deferred;
+    m->P->instances_all = instances ? instances + b : nullptr;
+    m->P->instance_lens_all = instance_lens ? instance_lens + b : nullptr;
+    m->P->d_advice_all = d_advice ? d_advice + b : nullptr;
+    m->P->advice_stride = advice_stride;
     g.members.push_back(std::move(m));
   }
-  const int run = g.run(instances, instance_lens, d_advice, advice_stride, use_gwc, phases, ex.phase_fn, ex.phase_user, challenge_stride);
+  const int run = prove_steps(g, use_gwc, phases);
   int first = AMDZK_OK;
   std::string first_err;
   for (auto& m : g.members) {
@@ -1512,121 +1486,110 @@ static int prove_gang(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_proofs, con
   return zk_quiet_if_refused(ctx, first, true);  // a failed proof may have left work behind: the workspaces must be quiet before they are used again
 }
 
+// What either batch entry point was asked for, in amdzk_create_proof_batch_opts' terms. `who` prefixes the refusals.
+// strict (amdzk_create_proof_batch): every handle is the first key or a workspace clone of it, no challenge phases, and
+// therefore no callback and no transcripts of the caller's. opts_size: where the caller's options say their size (null: no
+// options were given); `o` holds their fields once that size is large enough.
+struct BatchCall {
+  const char* who;
+  bool strict;
+  const char* opts_name;
+  size_t opts_need;
+  const size_t* opts_size;
+  amdzk_batch_proof_opts o;
+};
+
+// The refusals of both batch entry points: AMDZK_OK, or the batch is refused as a whole.
+static int batch_refusals(amdzk_ctx* ctx, const BatchCall& c, amdzk_pk* const* pks, size_t n_proofs, const void* const* d_advice,
+                          size_t advice_stride, const uint8_t* proofs_out, size_t proof_stride, const size_t* proof_lens) {
+  const char* const who = c.who;
+  const amdzk_batch_proof_opts& o = c.o;
+  if (!pks || n_proofs == 0) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: no proofs", who);
+  if (!c.opts_size || !proof_lens) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: null argument", who);
+  if (*c.opts_size < c.opts_need)
+    ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: %s.size is %zu, this library needs %zu", who, c.opts_name, *c.opts_size, c.opts_need);
+  if (!o.rng_seeds && !o.scalars) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: neither rng_seeds nor scalars", who);
+  size_t psize = 0;
+  bool builtin = false;
+  for (size_t b = 0; b < n_proofs; b++) {
+    if (!pks[b]) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: null key (proof %zu)", who, b);
+    const KeyMaterial& K = *pks[b]->key;
+    if (c.strict) ZK_TRY(check_handle(ctx, who, "proof", pks, b));  // the first key's, and no handle twice
+    if (K.srs != pks[0]->key->srs)
+      ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: proof %zu's key was made on another amdzk_srs than proof 0's: the batch commits over one SRS", who, b);
+    for (size_t d = 0; d < b; d++)
+      if (pks[d] == pks[b]) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: proofs %zu and %zu share one workspace", who, d, b);
+    if (K.A && (!d_advice || !d_advice[b])) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: null advice (proof %zu)", who, b);
+    if (o.scalars && !o.scalars[b]) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: null scalars (proof %zu)", who, b);
+    if (c.strict && K.phased())
+      ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "%s: the key has challenge phases or challenges: prove it with amdzk_create_proof_opts", who);
+    if (K.nphases > 1 && !o.phase_fn)
+      ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: proof %zu's key has advice in %u phases: a phase callback is needed", who, b, K.nphases);
+    if (advice_stride < K.n) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: advice stride < n", who);
+    const size_t draws = DrawLayout(K, 1).total;
+    if (o.scalars && o.scalar_count < draws) {
+      if (c.strict) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: %zu scalars given, %zu needed", who, o.scalar_count, draws);
+      ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: %zu scalars given, proof %zu needs %zu", who, o.scalar_count, b, draws);
+    }
+    const amdzk_transcript* t = o.transcripts ? o.transcripts[b] : nullptr;
+    if (t && (!t->common_point || !t->common_scalar || !t->write_point || !t->write_scalar || !t->squeeze_challenge))
+      ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: amdzk_transcript of proof %zu has a null member", who, b);
+    if (!t) {
+      builtin = true;
+      psize = std::max(psize, amdzk_proof_size(pks[b], o.transcript_kind));
+    }
+  }
+  if (builtin) {  // some proof's bytes are written here
+    const int kind = o.transcript_kind & ~AMDZK_MULTIOPEN_GWC;
+    if (kind != AMDZK_TRANSCRIPT_BLAKE2B && kind != AMDZK_TRANSCRIPT_KECCAK256_EVM) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: unknown transcript kind %d", who, kind);
+    if (!proofs_out) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: null argument", who);
+    if (proof_stride < psize) ZK_FAIL(ctx, AMDZK_E_INVALID, "%s: proof_stride %zu < proof size %zu", who, proof_stride, psize);
+  }
+  return AMDZK_OK;
+}
+
+// Both batch entry points behind their adapters. A batch that is refused as a whole starts no proof, and every proof says so.
+static int proof_batch(amdzk_ctx* ctx, const BatchCall& c, amdzk_pk* const* pks, size_t n_proofs, const uint64_t* const* const* instances,
+                       const size_t* const* instance_lens, const void* const* d_advice, size_t advice_stride, uint8_t* proofs_out,
+                       size_t proof_stride, size_t* proof_lens, int* statuses) {
+  const int r = batch_refusals(ctx, c, pks, n_proofs, d_advice, advice_stride, proofs_out, proof_stride, proof_lens);
+  if (r == AMDZK_OK)
+    return prove_gang(ctx, pks, n_proofs, instances, instance_lens, d_advice, advice_stride, c.o, proofs_out, proof_stride, proof_lens, statuses);
+  for (size_t b = 0; b < n_proofs; b++) {
+    if (statuses) statuses[b] = r;
+    if (proof_lens) proof_lens[b] = 0;
+  }
+  return r;
+}
+
 // n_proofs independent proofs of one circuit from one host thread, advanced in lock-step (Gang above). pks[b]: proof b's
 // workspace — the key or workspace clones of it, pairwise different. Bytes: those of n_proofs amdzk_create_proof_ex /
 // amdzk_create_proof_scalars calls.
-static int proof_batch(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_proofs, const uint64_t* const* const* instances,
-                       const size_t* const* instance_lens, const void* const* d_advice, size_t advice_stride, const amdzk_batch_opts* opts,
-                       uint8_t* proofs_out, size_t proof_stride, size_t* proof_lens, int* statuses, bool* ran) {
-  if (!pks || n_proofs == 0) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: no proofs");
-  if (!opts || !proofs_out || !proof_lens) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: null argument");
-  if (opts->size < sizeof(amdzk_batch_opts))
-    ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: amdzk_batch_opts.size is %zu, this library needs %zu", opts->size, sizeof(amdzk_batch_opts));
-  if (!opts->rng_seeds && !opts->scalars) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: neither rng_seeds nor scalars");
-  for (size_t b = 0; b < n_proofs; b++) {
-    if (!pks[b]) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: null key (proof %zu)", b);
-    ZK_TRY(check_handle(ctx, "create_proof_batch", "proof", pks, b));
-    if (pks[0]->key->A && (!d_advice || !d_advice[b])) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: null advice (proof %zu)", b);
-    if (opts->scalars && !opts->scalars[b]) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: null scalars (proof %zu)", b);
-  }
-  amdzk_pk* const pk = pks[0];
-  const KeyMaterial& K = *pk->key;
-  if (K.phased())
-    ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "create_proof_batch: the key has challenge phases or challenges: prove it with amdzk_create_proof_opts");
-  if (advice_stride < K.n) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: advice stride < n");
-  const int kind = opts->transcript_kind & ~AMDZK_MULTIOPEN_GWC;
-  if (kind != AMDZK_TRANSCRIPT_BLAKE2B && kind != AMDZK_TRANSCRIPT_KECCAK256_EVM)
-    ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: unknown transcript kind %d", kind);
-  const size_t psize = amdzk_proof_size(pk, opts->transcript_kind);
-  if (proof_stride < psize) ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: proof_stride %zu < proof size %zu", proof_stride, psize);
-  if (opts->scalars && opts->scalar_count < DrawLayout(K, 1).total)
-    ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof_batch: %zu scalars given, %zu needed", opts->scalar_count, DrawLayout(K, 1).total);
-
-  *ran = true;
-  BatchExtras ex;
-  return prove_gang(ctx, pks, n_proofs, instances, instance_lens, d_advice, advice_stride, opts->transcript_kind, opts->rng_seeds, opts->scalars, ex,
-                    proofs_out, proof_stride, proof_lens, statuses);
-}
 int amdzk_create_proof_batch(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_proofs, const uint64_t* const* const* instances,
                              const size_t* const* instance_lens, const void* const* d_advice, size_t advice_stride,
                              const amdzk_batch_opts* opts, uint8_t* proofs_out, size_t proof_stride, size_t* proof_lens, int* statuses) {
   ZK_ENTER(ctx);
   if (!ctx) return AMDZK_E_INVALID;
-  bool ran = false;
-  const int r = proof_batch(ctx, pks, n_proofs, instances, instance_lens, d_advice, advice_stride, opts, proofs_out, proof_stride, proof_lens,
-                            statuses, &ran);
-  if (!ran)  // refused as a whole: no proof was started, and every proof says so
-    for (size_t b = 0; b < n_proofs; b++) {
-      if (statuses) statuses[b] = r;
-      if (proof_lens) proof_lens[b] = 0;
-    }
-  return r;
+  BatchCall c = {"create_proof_batch", true, "amdzk_batch_opts", sizeof(amdzk_batch_opts), opts ? &opts->size : nullptr, {}};
+  if (opts && opts->size >= sizeof(amdzk_batch_opts)) {
+    c.o.transcript_kind = opts->transcript_kind;
+    c.o.rng_seeds = opts->rng_seeds;
+    c.o.scalars = opts->scalars;
+    c.o.scalar_count = opts->scalar_count;
+  }
+  return proof_batch(ctx, c, pks, n_proofs, instances, instance_lens, d_advice, advice_stride, proofs_out, proof_stride, proof_lens, statuses);
 }
 
 // amdzk_create_proof_batch for what it refuses: keys with challenge phases, proofs with the caller's transcript, and different
-// circuits on one SRS (include/amdzk.h). Its refusals; the proofs are prove_gang's.
-static int proof_batch_opts(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_proofs, const uint64_t* const* const* instances,
-                            const size_t* const* instance_lens, const void* const* d_advice, size_t advice_stride, const amdzk_batch_proof_opts* opts,
-                            uint8_t* proofs_out, size_t proof_stride, size_t* proof_lens, int* statuses, bool* ran) {
-#define WHO "create_proof_batch_opts: "
-  if (!pks || n_proofs == 0) ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "no proofs");
-  if (!opts || !proof_lens) ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "null argument");
-  if (opts->size < sizeof(amdzk_batch_proof_opts))
-    ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "amdzk_batch_proof_opts.size is %zu, this library needs %zu", opts->size, sizeof(amdzk_batch_proof_opts));
-  if (!opts->rng_seeds && !opts->scalars) ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "neither rng_seeds nor scalars");
-  const int kind = opts->transcript_kind & ~AMDZK_MULTIOPEN_GWC;
-  size_t psize = 0;
-  bool builtin = false;
-  for (size_t b = 0; b < n_proofs; b++) {
-    if (!pks[b]) ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "null key (proof %zu)", b);
-    const KeyMaterial& K = *pks[b]->key;
-    if (K.srs != pks[0]->key->srs)
-      ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "proof %zu's key was made on another amdzk_srs than proof 0's: the batch commits over one SRS", b);
-    for (size_t d = 0; d < b; d++)
-      if (pks[d] == pks[b]) ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "proofs %zu and %zu share one workspace", d, b);
-    if (K.A && (!d_advice || !d_advice[b])) ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "null advice (proof %zu)", b);
-    if (opts->scalars && !opts->scalars[b]) ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "null scalars (proof %zu)", b);
-    if (K.nphases > 1 && !opts->phase_fn)
-      ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "proof %zu's key has advice in %u phases: a phase callback is needed", b, K.nphases);
-    if (advice_stride < K.n) ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "advice stride < n");
-    if (opts->scalars && opts->scalar_count < DrawLayout(K, 1).total)
-      ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "%zu scalars given, proof %zu needs %zu", opts->scalar_count, b, DrawLayout(K, 1).total);
-    const amdzk_transcript* t = opts->transcripts ? opts->transcripts[b] : nullptr;
-    if (t && (!t->common_point || !t->common_scalar || !t->write_point || !t->write_scalar || !t->squeeze_challenge))
-      ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "amdzk_transcript of proof %zu has a null member", b);
-    if (!t) {
-      builtin = true;
-      psize = std::max(psize, amdzk_proof_size(pks[b], opts->transcript_kind));
-    }
-  }
-  if (builtin) {
-    if (kind != AMDZK_TRANSCRIPT_BLAKE2B && kind != AMDZK_TRANSCRIPT_KECCAK256_EVM) ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "unknown transcript kind %d", kind);
-    if (!proofs_out) ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "null argument");
-    if (proof_stride < psize) ZK_FAIL(ctx, AMDZK_E_INVALID, WHO "proof_stride %zu < proof size %zu", proof_stride, psize);
-  }
-#undef WHO
-  *ran = true;
-  BatchExtras ex;
-  ex.transcripts = opts->transcripts;
-  ex.phase_fn = opts->phase_fn;
-  ex.phase_user = opts->phase_user;
-  return prove_gang(ctx, pks, n_proofs, instances, instance_lens, d_advice, advice_stride, opts->transcript_kind, opts->scalars ? nullptr : opts->rng_seeds,
-                    opts->scalars, ex, proofs_out, proof_stride, proof_lens, statuses);
-}
+// circuits on one SRS (include/amdzk.h).
 int amdzk_create_proof_batch_opts(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_proofs, const uint64_t* const* const* instances,
                                   const size_t* const* instance_lens, const void* const* d_advice, size_t advice_stride,
                                   const amdzk_batch_proof_opts* opts, uint8_t* proofs_out, size_t proof_stride, size_t* proof_lens, int* statuses) {
   ZK_ENTER(ctx);
   if (!ctx) return AMDZK_E_INVALID;
-  bool ran = false;
-  const int r = proof_batch_opts(ctx, pks, n_proofs, instances, instance_lens, d_advice, advice_stride, opts, proofs_out, proof_stride, proof_lens,
-                                 statuses, &ran);
-  if (!ran)  // refused as a whole: no proof was started, and every proof says so
-    for (size_t b = 0; b < n_proofs; b++) {
-      if (statuses) statuses[b] = r;
-      if (proof_lens) proof_lens[b] = 0;
-    }
-  return r;
+  BatchCall c = {"create_proof_batch_opts", false, "amdzk_batch_proof_opts", sizeof(amdzk_batch_proof_opts), opts ? &opts->size : nullptr, {}};
+  if (opts && opts->size >= sizeof(amdzk_batch_proof_opts)) c.o = *opts;
+  return proof_batch(ctx, c, pks, n_proofs, instances, instance_lens, d_advice, advice_stride, proofs_out, proof_stride, proof_lens, statuses);
 }
 
 // Byte length of the proof amdzk_create_proof_multi writes for n_circuits instances (amdzk_proof_size for one).

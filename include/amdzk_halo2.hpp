@@ -831,6 +831,38 @@ inline std::vector<uint8_t> create_proof(const Context& ctx, const ProvingKey& p
   return proof;
 }
 
+namespace detail {
+// instances[c][col] as the tables the C entry points read — pp[c][col]: column col of circuit (or proof) c, null if it is
+// empty; lp[c][col]: its length; a circuit without instance columns still has one (null, 0) entry — and, with keys, pks[c]:
+// their handles. The containers it was built from must outlive it.
+struct InstanceTables {
+  std::vector<std::vector<const uint64_t*>> ptrs;
+  std::vector<std::vector<size_t>> lens;
+  std::vector<const uint64_t* const*> pp;
+  std::vector<const size_t*> lp;
+  std::vector<amdzk_pk*> pks;
+  InstanceTables() = default;
+  InstanceTables(const std::vector<std::vector<std::vector<Fr>>>& instances, const std::vector<const ProvingKey*>& keys) {
+    for (const ProvingKey* k : keys) pks.push_back(k->handle());
+    for (const auto& cols : instances) add(cols);
+    finish();
+  }
+  void add(const std::vector<std::vector<Fr>>& cols) {
+    ptrs.emplace_back(std::max<size_t>(1, cols.size()), nullptr);
+    lens.emplace_back(std::max<size_t>(1, cols.size()), 0);
+    for (size_t i = 0; i < cols.size(); i++) {
+      ptrs.back()[i] = cols[i].empty() ? nullptr : (const uint64_t*)cols[i].data();
+      lens.back()[i] = cols[i].size();
+    }
+  }
+  void finish() {  // after the last add
+    pp.assign(std::max<size_t>(1, ptrs.size()), nullptr);
+    lp.assign(std::max<size_t>(1, ptrs.size()), nullptr);
+    for (size_t i = 0; i < ptrs.size(); i++) pp[i] = ptrs[i].data(), lp[i] = lens[i].data();
+  }
+};
+}  // namespace detail
+
 // plonk::create_proof(params, pk, &[circuit; N], &[instances; N], rng, transcript): N instances of the key's circuit in
 // ONE proof (upstream's slices). keys[c]: instance c's workspace — the key itself and ProvingKey::clone_workspace() handles,
 // pairwise different; instances[c], d_advice[c] as for one circuit.
@@ -841,25 +873,10 @@ inline std::vector<uint8_t> create_proof(const Context& ctx, const std::vector<c
   const size_t N = keys.size();
   if (N == 0 || instances.size() != N || d_advice.size() != N) throw Error(AMDZK_E_INVALID, "create_proof: one key, instance set and witness per circuit");
   const int format = (int)transcript | (int)multiopen;
-  std::vector<amdzk_pk*> pks(N);
-  std::vector<std::vector<const uint64_t*>> ptrs(N);
-  std::vector<std::vector<size_t>> lens(N);
-  std::vector<const uint64_t* const*> pp(N);
-  std::vector<const size_t*> lp(N);
-  for (size_t c = 0; c < N; c++) {
-    pks[c] = keys[c]->handle();
-    ptrs[c].assign(std::max<size_t>(1, instances[c].size()), nullptr);
-    lens[c].assign(std::max<size_t>(1, instances[c].size()), 0);
-    for (size_t i = 0; i < instances[c].size(); i++) {
-      ptrs[c][i] = instances[c][i].empty() ? nullptr : (const uint64_t*)instances[c][i].data();
-      lens[c][i] = instances[c][i].size();
-    }
-    pp[c] = ptrs[c].data();
-    lp[c] = lens[c].data();
-  }
+  const detail::InstanceTables in(instances, keys);
   size_t need = 0;
-  std::vector<uint8_t> proof(amdzk_proof_size_multi(pks[0], N, format));
-  ctx.check(amdzk_create_proof_multi(ctx.get(), pks.data(), N, pp.data(), lp.data(), d_advice.data(), advice_stride, rng_seed, format, proof.data(),
+  std::vector<uint8_t> proof(amdzk_proof_size_multi(in.pks[0], N, format));
+  ctx.check(amdzk_create_proof_multi(ctx.get(), in.pks.data(), N, in.pp.data(), in.lp.data(), d_advice.data(), advice_stride, rng_seed, format, proof.data(),
                                      proof.size(), &need));
   proof.resize(need);
   return proof;
@@ -876,6 +893,22 @@ struct BatchProof {
   std::vector<uint8_t> proof;
   std::string error;
 };
+namespace detail {
+// What a batch call left — rc, the proofs' bytes at `stride`, their lengths and statuses — as one BatchProof each. A call
+// that was refused as a whole (or ended for all by the device) throws: its message is not one proof's ("proof <b>: ...").
+inline std::vector<BatchProof> batch_proofs(const Context& ctx, int rc, const std::vector<uint8_t>& bytes, size_t stride,
+                                            const std::vector<size_t>& got, const std::vector<int>& st) {
+  if (rc != AMDZK_OK && std::string(amdzk_last_error(ctx.get())).rfind("proof ", 0) != 0) ctx.check(rc);
+  std::vector<BatchProof> out(st.size());
+  bool first = true;
+  for (size_t b = 0; b < st.size(); b++) {
+    out[b].status = st[b];
+    if (st[b] == AMDZK_OK) out[b].proof.assign(bytes.begin() + b * stride, bytes.begin() + b * stride + got[b]);
+    else if (first) out[b].error = amdzk_last_error(ctx.get()), first = false;
+  }
+  return out;
+}
+}  // namespace detail
 inline std::vector<BatchProof> create_proof_batch(const Context& ctx, const std::vector<const ProvingKey*>& keys,
                                                   const std::vector<std::vector<std::vector<Fr>>>& instances,
                                                   const std::vector<const void*>& d_advice, size_t advice_stride,
@@ -885,42 +918,18 @@ inline std::vector<BatchProof> create_proof_batch(const Context& ctx, const std:
   if (N == 0 || instances.size() != N || d_advice.size() != N || rng_seeds.size() != N)
     throw Error(AMDZK_E_INVALID, "create_proof_batch: one key, instance set, witness and seed per proof");
   const int format = (int)transcript | (int)multiopen;
-  std::vector<amdzk_pk*> pks(N);
-  std::vector<std::vector<const uint64_t*>> ptrs(N);
-  std::vector<std::vector<size_t>> lens(N);
-  std::vector<const uint64_t* const*> pp(N);
-  std::vector<const size_t*> lp(N);
-  for (size_t b = 0; b < N; b++) {
-    pks[b] = keys[b]->handle();
-    ptrs[b].assign(std::max<size_t>(1, instances[b].size()), nullptr);
-    lens[b].assign(std::max<size_t>(1, instances[b].size()), 0);
-    for (size_t i = 0; i < instances[b].size(); i++) {
-      ptrs[b][i] = instances[b][i].empty() ? nullptr : (const uint64_t*)instances[b][i].data();
-      lens[b][i] = instances[b][i].size();
-    }
-    pp[b] = ptrs[b].data();
-    lp[b] = lens[b].data();
-  }
+  const detail::InstanceTables in(instances, keys);
   amdzk_batch_opts opts = {};
   opts.size = sizeof(opts);
   opts.transcript_kind = format;
   opts.rng_seeds = rng_seeds.data();
-  const size_t stride = amdzk_proof_size(pks[0], format);
+  const size_t stride = amdzk_proof_size(in.pks[0], format);
   std::vector<uint8_t> bytes(stride * N);
   std::vector<size_t> got(N, 0);
   std::vector<int> st(N, AMDZK_OK);
-  const int rc = amdzk_create_proof_batch(ctx.get(), pks.data(), N, pp.data(), lp.data(), d_advice.data(), advice_stride, &opts, bytes.data(),
+  const int rc = amdzk_create_proof_batch(ctx.get(), in.pks.data(), N, in.pp.data(), in.lp.data(), d_advice.data(), advice_stride, &opts, bytes.data(),
                                           stride, got.data(), st.data());
-  // refused as a whole (or ended for all by the device): the message is not one proof's ("proof <b>: ...")
-  if (rc != AMDZK_OK && std::string(amdzk_last_error(ctx.get())).rfind("proof ", 0) != 0) ctx.check(rc);
-  std::vector<BatchProof> out(N);
-  bool first = true;
-  for (size_t b = 0; b < N; b++) {
-    out[b].status = st[b];
-    if (st[b] == AMDZK_OK) out[b].proof.assign(bytes.begin() + b * stride, bytes.begin() + b * stride + got[b]);
-    else if (first) out[b].error = amdzk_last_error(ctx.get()), first = false;
-  }
-  return out;
+  return detail::batch_proofs(ctx, rc, bytes, stride, got, st);
 }
 
 // transcript::TranscriptWrite as far as create_proof uses it: implement it to own the transcript (`&mut T:
@@ -1000,25 +1009,10 @@ inline std::vector<uint8_t> create_proof(const Context& ctx, const std::vector<c
       });
     };
   opts.rng_seed = rng_seed;
-  std::vector<amdzk_pk*> pks(N);
-  std::vector<std::vector<const uint64_t*>> ptrs(N);
-  std::vector<std::vector<size_t>> lens(N);
-  std::vector<const uint64_t* const*> pp(N);
-  std::vector<const size_t*> lp(N);
-  for (size_t c = 0; c < N; c++) {
-    pks[c] = keys[c]->handle();
-    ptrs[c].assign(std::max<size_t>(1, instances[c].size()), nullptr);
-    lens[c].assign(std::max<size_t>(1, instances[c].size()), 0);
-    for (size_t i = 0; i < instances[c].size(); i++) {
-      ptrs[c][i] = instances[c][i].empty() ? nullptr : (const uint64_t*)instances[c][i].data();
-      lens[c][i] = instances[c][i].size();
-    }
-    pp[c] = ptrs[c].data();
-    lp[c] = lens[c].data();
-  }
+  const detail::InstanceTables in(instances, keys);
   size_t need = 0;
-  std::vector<uint8_t> proof(transcript_obj ? 0 : amdzk_proof_size_multi(pks[0], N, opts.transcript_kind));
-  const int rc = amdzk_create_proof_opts(ctx.get(), pks.data(), N, pp.data(), lp.data(), d_advice.data(), advice_stride, &opts, proof.data(),
+  std::vector<uint8_t> proof(transcript_obj ? 0 : amdzk_proof_size_multi(in.pks[0], N, opts.transcript_kind));
+  const int rc = amdzk_create_proof_opts(ctx.get(), in.pks.data(), N, in.pp.data(), in.lp.data(), d_advice.data(), advice_stride, &opts, proof.data(),
                                          proof.size(), &need);
   if (rc != AMDZK_OK && tr.err) std::rethrow_exception(tr.err);
   ctx.check(rc);
@@ -1085,42 +1079,19 @@ inline std::vector<BatchProof> create_proof_batch(const Context& ctx, const std:
         return 1;
       }
     };
-  std::vector<amdzk_pk*> pks(N);
-  std::vector<std::vector<const uint64_t*>> ptrs(N);
-  std::vector<std::vector<size_t>> lens(N);
-  std::vector<const uint64_t* const*> pp(N);
-  std::vector<const size_t*> lp(N);
+  const detail::InstanceTables in(instances, keys);
   size_t stride = 0;
-  for (size_t b = 0; b < N; b++) {
-    pks[b] = keys[b]->handle();
-    if (!ctp[b]) stride = std::max(stride, amdzk_proof_size(pks[b], format));
-    ptrs[b].assign(std::max<size_t>(1, instances[b].size()), nullptr);
-    lens[b].assign(std::max<size_t>(1, instances[b].size()), 0);
-    for (size_t i = 0; i < instances[b].size(); i++) {
-      ptrs[b][i] = instances[b][i].empty() ? nullptr : (const uint64_t*)instances[b][i].data();
-      lens[b][i] = instances[b][i].size();
-    }
-    pp[b] = ptrs[b].data();
-    lp[b] = lens[b].data();
-  }
+  for (size_t b = 0; b < N; b++)
+    if (!ctp[b]) stride = std::max(stride, amdzk_proof_size(in.pks[b], format));
   std::vector<uint8_t> bytes(std::max<size_t>(1, stride * N));
   std::vector<size_t> got(N, 0);
   std::vector<int> st(N, AMDZK_OK);
-  const int rc = amdzk_create_proof_batch_opts(ctx.get(), pks.data(), N, pp.data(), lp.data(), d_advice.data(), advice_stride, &opts, bytes.data(),
+  const int rc = amdzk_create_proof_batch_opts(ctx.get(), in.pks.data(), N, in.pp.data(), in.lp.data(), d_advice.data(), advice_stride, &opts, bytes.data(),
                                                stride, got.data(), st.data());
   if (shared.err) std::rethrow_exception(shared.err);
   for (auto& t : trs)
     if (t.err) std::rethrow_exception(t.err);
-  // refused as a whole (or ended for all by the device): the message is not one proof's ("proof <b>: ...")
-  if (rc != AMDZK_OK && std::string(amdzk_last_error(ctx.get())).rfind("proof ", 0) != 0) ctx.check(rc);
-  std::vector<BatchProof> out(N);
-  bool first = true;
-  for (size_t b = 0; b < N; b++) {
-    out[b].status = st[b];
-    if (st[b] == AMDZK_OK) out[b].proof.assign(bytes.begin() + b * stride, bytes.begin() + b * stride + got[b]);
-    else if (first) out[b].error = amdzk_last_error(ctx.get()), first = false;
-  }
-  return out;
+  return detail::batch_proofs(ctx, rc, bytes, stride, got, st);
 }
 
 // Convenience for host-resident witnesses (what a WitnessCollection holds after synthesis): uploads the
@@ -1455,10 +1426,7 @@ struct Guard {
 // outlive it).
 struct VerifyArgs {
   size_t B = 0, N = 1;
-  std::vector<std::vector<const uint64_t*>> ptrs;
-  std::vector<std::vector<size_t>> lens;
-  std::vector<const uint64_t* const*> inst_pp;
-  std::vector<const size_t*> lens_pp;
+  detail::InstanceTables inst;  // one entry per (proof, circuit instance), proof after proof
   std::vector<const uint8_t*> pp;
   std::vector<size_t> pl;
   amdzk_verify_opts opts = {};
@@ -1472,19 +1440,9 @@ struct VerifyArgs {
     N = B ? instances[0].size() : 1;
     for (size_t b = 0; b < B; b++) {
       if (instances[b].size() != N || N == 0) throw Error(AMDZK_E_INVALID, w + ": every proof has the same number of circuit instances");
-      for (size_t c = 0; c < N; c++) {
-        const auto& cols = instances[b][c];
-        ptrs.emplace_back(std::max<size_t>(1, cols.size()), nullptr);
-        lens.emplace_back(std::max<size_t>(1, cols.size()), 0);
-        for (size_t i = 0; i < cols.size(); i++) {
-          ptrs.back()[i] = cols[i].empty() ? nullptr : (const uint64_t*)cols[i].data();
-          lens.back()[i] = cols[i].size();
-        }
-      }
+      for (size_t c = 0; c < N; c++) inst.add(instances[b][c]);
     }
-    inst_pp.assign(std::max<size_t>(1, B * N), nullptr);
-    lens_pp.assign(std::max<size_t>(1, B * N), nullptr);
-    for (size_t i = 0; i < ptrs.size(); i++) inst_pp[i] = ptrs[i].data(), lens_pp[i] = lens[i].data();
+    inst.finish();
     static const uint8_t none = 0;
     pp.assign(std::max<size_t>(1, B), nullptr);
     pl.assign(std::max<size_t>(1, B), 0);
@@ -1511,10 +1469,10 @@ struct VerifyArgs {
 // key's type alone.
 namespace detail {
 inline int c_verify(amdzk_ctx* c, const amdzk_pk* key, VerifyArgs& a, uint64_t pair[16]) {
-  return amdzk_verify_proofs(c, key, a.B, a.inst_pp.data(), a.lens_pp.data(), a.pp.data(), a.pl.data(), &a.opts, a.raw.data(), pair);
+  return amdzk_verify_proofs(c, key, a.B, a.inst.pp.data(), a.inst.lp.data(), a.pp.data(), a.pl.data(), &a.opts, a.raw.data(), pair);
 }
 inline int c_verify(amdzk_ctx* c, const amdzk_vk* key, VerifyArgs& a, uint64_t pair[16]) {
-  return amdzk_verify_proofs_vk(c, key, a.B, a.inst_pp.data(), a.lens_pp.data(), a.pp.data(), a.pl.data(), &a.opts, a.raw.data(), pair);
+  return amdzk_verify_proofs_vk(c, key, a.B, a.inst.pp.data(), a.inst.lp.data(), a.pp.data(), a.pl.data(), &a.opts, a.raw.data(), pair);
 }
 template <class Key>
 Guard verify_proofs(const Context& ctx, const Key& key, const std::vector<std::vector<std::vector<std::vector<Fr>>>>& instances,
@@ -1643,11 +1601,11 @@ struct Decision {
 // be unpredictable to whoever made the proofs; every well-formed proof gets that check's result.
 namespace detail {
 inline int c_decide(amdzk_ctx* c, const amdzk_pk* key, const ParamsVerifierKZG& vp, uint32_t flags, VerifyArgs& a, uint8_t* v, size_t* n_valid) {
-  return amdzk_verify_proofs_decide(c, key, vp.s_g2.handle(), vp.g2.handle(), flags, a.B, a.inst_pp.data(), a.lens_pp.data(), a.pp.data(), a.pl.data(),
+  return amdzk_verify_proofs_decide(c, key, vp.s_g2.handle(), vp.g2.handle(), flags, a.B, a.inst.pp.data(), a.inst.lp.data(), a.pp.data(), a.pl.data(),
                                     &a.opts, a.raw.data(), v, n_valid);
 }
 inline int c_decide(amdzk_ctx* c, const amdzk_vk* key, const ParamsVerifierKZG& vp, uint32_t flags, VerifyArgs& a, uint8_t* v, size_t* n_valid) {
-  return amdzk_verify_proofs_decide_vk(c, key, vp.s_g2.handle(), vp.g2.handle(), flags, a.B, a.inst_pp.data(), a.lens_pp.data(), a.pp.data(),
+  return amdzk_verify_proofs_decide_vk(c, key, vp.s_g2.handle(), vp.g2.handle(), flags, a.B, a.inst.pp.data(), a.inst.lp.data(), a.pp.data(),
                                        a.pl.data(), &a.opts, a.raw.data(), v, n_valid);
 }
 template <class Key>

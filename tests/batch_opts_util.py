@@ -168,18 +168,21 @@ class Batch:
 
 
 def raw_call(ctx, pkg, keys, adv, n, seeds=(), scalars=None, scalar_count=0, kind=0, transcripts=None, phase_fn=None, opts_size=None,
-             proof_stride=1 << 14, advice_stride=None, opts_null=False, keys_null=False, lens_null=False):
-    """amdzk_create_proof_batch_opts through ctypes with every argument as given (instances NULL). Returns (rc, statuses,
-    lengths, message); statuses and lengths start at 1 and 7."""
+             proof_stride=1 << 14, advice_stride=None, opts_null=False, keys_null=False, lens_null=False, out_null=False, strict=False):
+    """amdzk_create_proof_batch_opts (strict: amdzk_create_proof_batch, whose options end behind scalar_count) through ctypes
+    with every argument as given (instances NULL). Returns (rc, statuses, lengths, message); statuses and lengths start at 1
+    and 7."""
     N = len(keys)
     ffi = pkg.ffi
     karr = (C.c_void_p * max(1, N))(*keys)
     aarr = (C.c_void_p * max(1, N))(*adv)
     sd = np.array(list(seeds), np.uint64) if seeds is not None else None
-    opts = ffi.BatchProofOpts(C.sizeof(ffi.BatchProofOpts) if opts_size is None else opts_size, kind, sd.ctypes.data if sd is not None and sd.size else None,
-                              scalars, scalar_count, transcripts, phase_fn if phase_fn is not None else ffi.BATCH_PHASE_FN(), None)
+    S = ffi.BatchOpts if strict else ffi.BatchProofOpts
+    extra = () if strict else (transcripts, phase_fn if phase_fn is not None else ffi.BATCH_PHASE_FN(), None)
+    opts = S(C.sizeof(S) if opts_size is None else opts_size, kind, sd.ctypes.data if sd is not None and sd.size else None, scalars, scalar_count, *extra)
     buf = (C.c_uint8 * max(1, proof_stride * N))()
     lens_out, st = (C.c_size_t * max(1, N))(*[7] * N), (C.c_int * max(1, N))(*[1] * N)
-    rc = ctx.L.amdzk_create_proof_batch_opts(ctx.h, None if keys_null else karr, N, None, None, aarr, advice_stride if advice_stride is not None else n,
-                                             None if opts_null else C.byref(opts), buf, proof_stride, None if lens_null else lens_out, st)
+    fn = ctx.L.amdzk_create_proof_batch if strict else ctx.L.amdzk_create_proof_batch_opts
+    rc = fn(ctx.h, None if keys_null else karr, N, None, None, aarr, advice_stride if advice_stride is not None else n,
+            None if opts_null else C.byref(opts), None if out_null else buf, proof_stride, None if lens_null else lens_out, st)
     return rc, list(st)[:N], list(lens_out)[:N], ctx.L.amdzk_last_error(ctx.h).decode()

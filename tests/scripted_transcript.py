@@ -71,6 +71,42 @@ def scripted(base, script):
     return Scripted
 
 
+def recording(base, log):
+    """`base` (an oracle writer class) that also appends every call it receives to `log`, as (name, value): the call list of
+    the oracle's prover when the oracle constructs it, of the library when its callbacks feed it (DeviceWriter and the
+    ForwardedTranscript classes of the GPU tests)."""
+    class Recording(base):
+        _nested = False  # a writer's write_* absorbs through its own common_*: only the caller's call is one
+
+        def _call(self, name, value, fn):
+            outer, self._nested = not self._nested, True
+            try:
+                out = fn()
+            finally:
+                if outer:
+                    self._nested = False
+            if outer:
+                log.append((name, out if name == "squeeze_challenge" else value))
+            return out
+
+        def common_point(self, p):
+            return self._call("common_point", tuple(p), lambda: base.common_point(self, p))
+
+        def common_scalar(self, s):
+            return self._call("common_scalar", s % R, lambda: base.common_scalar(self, s))
+
+        def write_point(self, p):
+            return self._call("write_point", tuple(p), lambda: base.write_point(self, p))
+
+        def write_scalar(self, s):
+            return self._call("write_scalar", s % R, lambda: base.write_scalar(self, s))
+
+        def squeeze_challenge(self):
+            return self._call("squeeze_challenge", None, lambda: base.squeeze_challenge(self))
+    Recording.__name__ = "Recording" + base.__name__
+    return Recording
+
+
 def writer(transcript, script):
     return scripted(_ORIG[_NAMES[kind(transcript)][0]], script)()
 

@@ -349,3 +349,152 @@ def test_refusals(ctx, pkg, plonk, oracle):
     assert B.batch(seeds) == want
     other.free()
     B.free()
+
+
+class Stopped(Exception):
+    """Raised by StoppingTranscript at the call it was told to fail."""
+
+
+class StoppingTranscript(ForwardedTranscript):
+    """Fails (the callback returns non-zero) at call number `stop`, counted from 0 over all five members, and goes on
+    counting the calls it receives afterwards."""
+
+    def __init__(self, inner, stop):
+        super().__init__(inner)
+        self.stop = stop
+
+    def _tick(self):
+        if self.calls == self.stop:
+            self.calls += 1
+            raise Stopped(self.stop)
+
+    def common_point(self, w):
+        self._tick()
+        super().common_point(w)
+
+    def common_scalar(self, w):
+        self._tick()
+        super().common_scalar(w)
+
+    def write_point(self, w):
+        self._tick()
+        super().write_point(w)
+
+    def write_scalar(self, w):
+        self._tick()
+        super().write_scalar(w)
+
+    def squeeze_challenge(self):
+        self._tick()
+        return super().squeeze_challenge()
+
+
+@pytest.mark.parametrize("multiopen", ["shplonk", "gwc"])
+def test_a_proof_alone_and_a_batch_of_one_stop_at_the_same_call(ctx, pkg, plonk, oracle, multiopen):
+    """The caller's transcript reports an error at call j, for every j of the proof: amdzk_create_proof_opts and
+    amdzk_create_proof_batch_opts with that one proof end with the same message (the batch's behind "proof 0: ") after the
+    same number of calls — one statement of the order serves both. Behind the last call both give the proof's bytes."""
+    B = U.Batch(ctx, pkg, plonk, oracle, 5, [(circuits.lookup_circuit(plonk, 5, seed=2), None)])
+    tk = plonk.MULTIOPEN_GWC if multiopen == "gwc" else 0
+    whole = ForwardedTranscript(PR.Blake2bWrite())
+    assert B.single(0, 9, transcript=tk, transcript_object=whole) == b""
+    assert bytes(whole.inner.proof) == B.expected(None, 0, 9, multiopen=multiopen)
+    last_error = lambda: ctx.L.amdzk_last_error(ctx.h).decode()
+    for j in range(whole.calls):
+        alone, batched = StoppingTranscript(PR.Blake2bWrite(), j), StoppingTranscript(PR.Blake2bWrite(), j)
+        with pytest.raises(Stopped):
+            B.single(0, 9, transcript=tk, transcript_object=alone)
+        said = last_error()
+        with pytest.raises(Stopped):
+            B.batch([9], transcript=tk, transcript_objects=[batched])
+        assert said == "create_proof: the caller's transcript reported an error" and last_error() == "proof 0: " + said, "call %d" % j
+        assert alone.calls == batched.calls > j, "call %d" % j
+    alone, batched = StoppingTranscript(PR.Blake2bWrite(), whole.calls), StoppingTranscript(PR.Blake2bWrite(), whole.calls)
+    assert B.single(0, 9, transcript=tk, transcript_object=alone) == b"" and B.batch([9], transcript=tk, transcript_objects=[batched]) == [b""]
+    assert bytes(alone.inner.proof) == bytes(batched.inner.proof) == bytes(whole.inner.proof) and alone.calls == batched.calls == whole.calls
+    B.free()
+
+
+def test_every_single_fault_refusal_word_for_word(ctx, pkg, plonk, oracle):
+    """Both batch entry points, one fault per call: the whole message, the status in every proof's slot, every length 0,
+    and a good batch right after. amdzk_create_proof_batch_opts on three circuits of one SRS, amdzk_create_proof_batch on a
+    key and its clone."""
+    UNSUPPORTED = -5
+    ffi, n = pkg.ffi, 32
+    B = mixed(ctx, pkg, plonk, oracle)
+    other = mixed(ctx, pkg, plonk, oracle)  # the same circuits on another ParamsKZG
+    cl = circuits.lookup_circuit(plonk, 5, seed=2)
+    S = U.Batch(ctx, pkg, plonk, oracle, 5, [(cl, None), (cl, None)])  # one key, two workspaces
+    noop = ffi.BATCH_PHASE_FN(lambda *a: 0)
+    holed = ffi.Transcript(None, *[ffi._T_IN(lambda *a: 0) for _ in range(4)], ffi._T_IN())  # squeeze_challenge is NULL
+    draws = np.zeros((max(plonk.proof_random_count(ctx, pk) for pk in B.pks), 4), np.uint64)
+
+    def entry(batch, strict, who):
+        seeds = list(range(5, 5 + len(batch.pks)))
+        want = batch.batch(seeds)
+        keys, adv = [pk.h for pk in batch.pks], [d.ptr for d in batch.d_adv]
+        stride = max(plonk.proof_size(ctx, pk) for pk in batch.pks)
+        N = len(keys)
+
+        def refused(text, code=INVALID, **kw):
+            k, a = kw.pop("keys", keys), kw.pop("adv", adv)
+            kw.setdefault("seeds", seeds)
+            if not strict:
+                kw.setdefault("phase_fn", noop)
+            kw.setdefault("proof_stride", stride)
+            rc, st, lens, msg = U.raw_call(ctx, pkg, k, a, n, strict=strict, **kw)
+            assert (rc, msg) == (code, who + ": " + text)
+            assert st == [code] * len(k) and lens == ([7] * len(k) if kw.get("lens_null") else [0] * len(k))  # (no array: nothing to write)
+            assert batch.batch(seeds) == want
+        return refused, keys, adv, stride, N
+
+    refused, keys, adv, stride, N = entry(B, False, "create_proof_batch_opts")
+    counts = [plonk.proof_random_count(ctx, pk) for pk in B.pks]
+    short = max(counts) - 1
+    first_short = [b for b in range(N) if counts[b] > short][0]
+    sc = lambda *ptrs: (C.c_void_p * N)(*ptrs)
+    refused("no proofs", keys_null=True)
+    refused("no proofs", seeds=[], keys=[], adv=[])
+    refused("null argument", opts_null=True)
+    refused("null argument", lens_null=True)
+    refused("null argument", out_null=True)
+    refused("amdzk_batch_proof_opts.size is 8, this library needs %d" % C.sizeof(ffi.BatchProofOpts), opts_size=8)
+    refused("neither rng_seeds nor scalars", seeds=None)
+    refused("null key (proof 1)", keys=[keys[0], None, keys[2]])
+    refused("proofs 0 and 2 share one workspace", keys=[keys[0], keys[1], keys[0]])
+    refused("proof 1's key was made on another amdzk_srs than proof 0's: the batch commits over one SRS", keys=[keys[0], other.pks[1].h, keys[2]])
+    refused("null advice (proof 2)", adv=[adv[0], adv[1], None])
+    refused("null scalars (proof 1)", seeds=None, scalars=sc(draws.ctypes.data, None, draws.ctypes.data), scalar_count=len(draws))
+    refused("%d scalars given, proof %d needs %d" % (short, first_short, counts[first_short]), seeds=None, scalars=sc(*[draws.ctypes.data] * N),
+            scalar_count=short)
+    refused("advice stride < n", advice_stride=n - 1)
+    refused("unknown transcript kind 7", kind=7)
+    refused("proof_stride %d < proof size %d" % (stride - 1, stride), proof_stride=stride - 1)
+    refused("proof 1's key has advice in 3 phases: a phase callback is needed", phase_fn=ffi.BATCH_PHASE_FN())
+    refused("amdzk_transcript of proof 1 has a null member", transcripts=(C.POINTER(ffi.Transcript) * N)(None, C.pointer(holed), None))
+
+    phased_key = B.pks[1].h
+    refused, keys, adv, stride, N = entry(S, True, "create_proof_batch")
+    count = plonk.proof_random_count(ctx, S.pks[0])
+    sc = lambda *ptrs: (C.c_void_p * N)(*ptrs)
+    refused("no proofs", keys_null=True)
+    refused("no proofs", seeds=[], keys=[], adv=[])
+    refused("null argument", opts_null=True)
+    refused("null argument", lens_null=True)
+    refused("null argument", out_null=True)
+    refused("amdzk_batch_opts.size is 8, this library needs %d" % C.sizeof(ffi.BatchOpts), opts_size=8)
+    refused("neither rng_seeds nor scalars", seeds=None)
+    refused("null key (proof 1)", keys=[keys[0], None])
+    refused("proofs 0 and 1 share one workspace", keys=[keys[0], keys[0]])
+    refused("proof 1's key is not the first key or a workspace clone of it", keys=[keys[0], B.pks[0].h])  # the same circuit, another key
+    refused("null advice (proof 1)", adv=[adv[0], None])
+    refused("null scalars (proof 1)", seeds=None, scalars=sc(draws.ctypes.data, None), scalar_count=count)
+    refused("%d scalars given, %d needed" % (count - 1, count), seeds=None, scalars=sc(*[draws.ctypes.data] * N), scalar_count=count - 1)
+    refused("advice stride < n", advice_stride=n - 1)
+    refused("unknown transcript kind 7", kind=7)
+    refused("proof_stride %d < proof size %d" % (stride - 1, stride), proof_stride=stride - 1)
+    refused("the key has challenge phases or challenges: prove it with amdzk_create_proof_opts", code=UNSUPPORTED, keys=[phased_key], adv=[B.d_adv[1].ptr],
+            seeds=[5])
+    S.free()
+    other.free()
+    B.free()

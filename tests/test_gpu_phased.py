@@ -18,6 +18,7 @@ import circuits  # noqa: E402
 import phased_circuits as PC  # noqa: E402
 import phased_oracle as PO  # noqa: E402
 import plonk_ref as PR  # noqa: E402
+import scripted_transcript as ST  # noqa: E402
 from test_phased_oracle import RANDOM_SEEDS  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -405,3 +406,122 @@ def test_third_transcript_sha256_verifies_under_the_matching_reader(ctx, pkg, pl
     dev.prove(seed=8, transcript_object=t2)
     assert bytes(t2.inner.proof) == proof
     dev.free()
+
+
+# ---- two instances: every instance's work is enqueued before the first write, the writes keep upstream's order -----------
+class TwoInstances:
+    """An unphased circuit on a key and a workspace clone, instance 1's witness `adv1` (advice ints) in a buffer of its own."""
+
+    def __init__(self, ctx, pkg, plonk, oracle, c, adv1, flags=None):
+        self.ctx, self.plonk, self.oracle, self.c = ctx, plonk, oracle, c
+        g, gl = _srs_cache.setdefault(c.k, zu.test_srs(oracle, c.k, TAU))
+        self.params = pkg.kzg.ParamsKZG(ctx, c.k, g=g, g_lagrange=gl)
+        self.pk = plonk.ProvingKey(ctx, self.params, c.desc, np.stack([zu.ints_to_fr(oracle, col) for col in c.fixed]), c.assembly.mapping,
+                                   zu.fr_from_int(REPR), flags=flags)
+        self.pks = [self.pk, self.pk.clone_workspace()]
+        self.inst = [[zu.ints_to_fr(oracle, col) if col else np.zeros((0, 4), np.uint64) for col in c.instances]] * 2
+        self.inst_ints = [c.instances] * 2
+        self.d_adv = [ctx.alloc(len(c.advice) * c.n * 32) for _ in range(2)]
+        self.set(0, c.advice)
+        self.set(1, adv1)
+        self.opk = PR.keygen(c.desc, c.fixed, c.assembly.mapping, TAU, transcript_repr=REPR)
+
+    def set(self, ci, adv):
+        self.d_adv[ci].upload(np.stack([zu.ints_to_fr(self.oracle, col) for col in adv]))
+
+    def prove(self, seed, transcript=0, transcript_object=None):
+        return self.plonk.create_proof_opts(self.ctx, self.pks, self.inst, self.d_adv, seed=seed, transcript=transcript,
+                                            transcript_object=transcript_object)
+
+    def free(self):
+        for d in self.d_adv:
+            d.free()
+        self.pks[1].free()
+        self.pk.free()
+        self.params.free()
+
+
+def range_lookup_variants(c):
+    """Instance 1's witnesses of a circuits.lookup_circuit: one whose first range-checked cell is another value of the table
+    (gates and copies are not the prover's business), one whose cell is outside it (lookup 0 fails)."""
+    row = [r for r in range(c.usable) if c.fixed[2][r] == 1][0]  # fixed[2] = q_rng
+    good, bad = [list(col) for col in c.advice], [list(col) for col in c.advice]
+    good[0][row] = (good[0][row] + 1) % 8
+    bad[0][row] = 9
+    return good, bad
+
+
+NOT_IN_TABLE = "create_proof: lookup 0 input not in table (ConstraintSystemFailure)"
+
+
+def test_instance_one_fails_its_lookup_behind_instance_zeros_writes(ctx, pkg, plonk, oracle, monkeypatch):
+    """N = 2 with a caller's transcript, instance 1's lookup input outside its table: the transcript receives exactly the
+    calls the oracle's prover makes until it hits that lookup — both instances' inputs and advice, theta, instance 0's
+    permuted pairs — and nothing of instance 1's; status and message are the single proof's; the handles prove on."""
+    c = circuits.lookup_circuit(plonk, 5, seed=4)
+    good, bad = range_lookup_variants(c)
+    dev = TwoInstances(ctx, pkg, plonk, oracle, c, bad)
+    want = []
+    with monkeypatch.context() as m:
+        m.setattr(PR, "Blake2bWrite", ST.recording(PR.Blake2bWrite, want))
+        with pytest.raises(AssertionError, match="lookup input not in table"):
+            PR.create_proof_multi(dev.opk, dev.inst_ints, [c.advice, bad], seed=21)
+    A, L = len(c.advice), len(c.desc["lookups"])
+    assert [n for n, _ in want].count("write_point") == 2 * A + 2 * L and want[-1][0] == "write_point"  # ... and ends behind instance 0's pairs
+    got = []
+    with pytest.raises(pkg.AmdzkError) as e:
+        dev.prove(21, transcript_object=ForwardedTranscript(ST.recording(PR.Blake2bWrite, got)()))
+    assert e.value.code == -2 and str(e.value) == "amdzk error -2: " + NOT_IN_TABLE
+    assert got == want
+    dev.set(1, good)
+    assert dev.prove(21) == PR.create_proof_multi(dev.opk, dev.inst_ints, [c.advice, good], seed=21)
+    dev.free()
+
+
+def test_instance_one_fails_its_lookup_on_a_three_phase_key(ctx, pkg, plonk, oracle, monkeypatch):
+    """The same on a key with three phases: instance 1's phase-0 column `a` leaves the table at one row (a + ch * b is looked
+    up). Both callbacks have run, every phase's commitments of both instances and the phase challenges are in the
+    transcript, then theta and instance 0's pair."""
+    c = PC.rlc_circuit(plonk, 5, seed=6, three_phases=True)
+    dev = Device(ctx, pkg, plonk, oracle, c, N=2)
+    adv1, fill1 = dev.wit[1]
+    broken = [list(col) for col in adv1]
+    broken[0][3] = (broken[0][3] + 1) % zu.R  # (a + 1, b) is no pair of the table
+    dev.wit[1] = (broken, fill1)
+    got, want = [], []
+    with pytest.raises(pkg.AmdzkError) as e:
+        dev.prove(seed=12, transcript_object=ForwardedTranscript(ST.recording(PR.Blake2bWrite, got)()))
+    assert e.value.code == -2 and str(e.value) == "amdzk error -2: " + NOT_IN_TABLE
+    ch = dev.challenges()  # both callbacks came, with the challenges pk_inspect reports
+    PO.WRITERS["recording"] = ("Keccak256Write", "Keccak256Read", ST.recording(PR.Blake2bWrite, want), PR.Blake2bRead)
+    try:
+        with pytest.raises(AssertionError, match="lookup input not in table"):
+            PO.create_proof(monkeypatch, dev.opk(), c.desc, dev.inst_ints, dev.adv, 12, ch, transcript="recording")
+    finally:
+        del PO.WRITERS["recording"]
+    A = len(c.advice)
+    assert [n for n, _ in want].count("write_point") == 2 * A + 2 and [n for n, _ in want].count("squeeze_challenge") == len(ch) + 1
+    assert got == want
+    dev.wit[1] = (adv1, fill1)
+    proof = dev.prove(seed=12)
+    assert proof == expected(monkeypatch, dev, dev.opk(), 12, dev.challenges())
+    dev.free()
+
+
+@pytest.mark.parametrize("serial", [False, True])
+@pytest.mark.parametrize("transcript", ["blake2b", "keccak"])
+def test_two_instances_open_with_gwc(ctx, pkg, plonk, oracle, monkeypatch, serial, transcript):
+    """N = 2 with ProverGWC, on a three-phase key and on an unphased one, lanes keys and serial keys, both transcripts."""
+    flags = plonk.KEYGEN_SERIAL if serial else 0
+    tk = (plonk.TRANSCRIPT_BLAKE2B if transcript == "blake2b" else plonk.TRANSCRIPT_KECCAK256_EVM) | plonk.MULTIOPEN_GWC
+    c = PC.rlc_circuit(plonk, 5, seed=6, three_phases=True)
+    dev = Device(ctx, pkg, plonk, oracle, c, N=2, flags=flags)
+    got = dev.prove(seed=12, transcript=tk)
+    assert len(got) == plonk.proof_size_multi(ctx, dev.pk, 2, tk)
+    assert got == expected(monkeypatch, dev, dev.opk(), 12, dev.challenges(), transcript=transcript, multiopen="gwc")
+    dev.free()
+    c = circuits.lookup_circuit(plonk, 5, seed=4)
+    good, _ = range_lookup_variants(c)
+    two = TwoInstances(ctx, pkg, plonk, oracle, c, good, flags=flags)
+    assert two.prove(17, transcript=tk) == PR.create_proof_multi(two.opk, two.inst_ints, [c.advice, good], seed=17, transcript=transcript, multiopen="gwc")
+    two.free()

@@ -50,3 +50,19 @@ def test_cpp_mirror_configuration_is_clean_under_asan_and_ubsan(name, k):
     assert p.returncode == 0, (p.stdout[-1000:], p.stderr[-4000:])
     assert "runtime error" not in p.stderr and "AddressSanitizer" not in p.stderr, p.stderr[-4000:]
     assert p.stdout.startswith("shape %d " % k)
+
+
+def test_cpp_mirror_instance_tables_are_clean_under_asan_and_ubsan():
+    """detail::InstanceTables (what every multi-circuit and batch create_proof overload hands to the C ABI) and VerifyArgs
+    on top of it, from containers with empty columns, a circuit without columns and an empty proof
+    (tests/native/instance_tables_check.cpp: no GPU call): pointers, lengths and the one-entry minimum, under the sanitizers."""
+    libdir = os.path.join(ROOT, "anon-aadhaar-halo2_amd")
+    if not os.path.exists(os.path.join(libdir, "libamdzk.so")):
+        pytest.skip("libamdzk.so not built")
+    with tempfile.TemporaryDirectory() as d:
+        exe = os.path.join(d, "san_tables")
+        subprocess.check_call(["g++", *SAN, "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-o", exe,
+                               os.path.join(ROOT, "tests", "native", "instance_tables_check.cpp"), "-L", libdir, "-lamdzk", "-Wl,-rpath," + libdir])
+        p = subprocess.run([exe], text=True, capture_output=True, env=dict(ENV, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0"), timeout=600)
+    assert p.returncode == 0 and p.stdout == "bad 0\n", (p.stdout[-1000:], p.stderr[-4000:])
+    assert "runtime error" not in p.stderr and "AddressSanitizer" not in p.stderr, p.stderr[-4000:]
