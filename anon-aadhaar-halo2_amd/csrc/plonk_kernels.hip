@@ -877,10 +877,13 @@ __global__ __launch_bounds__(1024) void bitonic_lds_kernel(Fr* data, Fr* data_b,
   const uint32_t base = blockIdx.x * tile, t = threadIdx.x;
   Fr* col = blockIdx.y < ncols_a ? data + (size_t)blockIdx.y * col_stride : data_b + (size_t)(blockIdx.y - ncols_a) * col_stride;
   for (uint32_t i = t; i < tile; i += blockDim.x) L[i] = ld_fr(col + base + i);
-  // A stage with j <= 64 touches, from wavefront w, only elements [128 w', 128 w' + 128) for the two runs of 64 pairs it
-  // owns (p and p + blockDim.x): consecutive stages of that kind hand data from a wavefront to itself, and LDS executes a
-  // wavefront's accesses in order — the workgroup barrier is only needed next to a stage with j >= 128 (57 of the 78 stages
-  // of a 4096-key tile run without one). Needs blockDim.x to be a multiple of 64 and pairs p, p + blockDim.x, ... per thread.
+  // zk_sort_keys2 launches max(64, tile / 2) threads for a tile of at most SORT_TILE = 2048 keys: thread p owns the one
+  // pair p of every stage (the p loop below runs once; in a tile below 128 keys the threads p >= tile / 2 own none). A
+  // stage with j <= 64 pairs i = 2 (p & ~(j - 1)) | (p & (j - 1)) with i + j, and for the 64 pairs p of wavefront w both lie
+  // in [128 w, 128 w + 128): consecutive stages of that kind hand data from a wavefront to itself, and LDS executes a
+  // wavefront's accesses in order — the workgroup barrier is only needed next to a stage with j >= 128 (51 of the 66 stages
+  // that sort a 2048-key tile run without one). Needs blockDim.x to be a multiple of 64, so that wavefront w holds exactly
+  // the pairs [64 w, 64 w + 64).
   // The elision below is an argument about 64-lane wavefronts: refuse to build for anything else, and trap a launch whose
   // workgroup is not whole wavefronts (zk_sort_keys2 launches 64, 128, ..., 1024 threads).
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__GFX9__)
@@ -1269,9 +1272,10 @@ int zk_sort_keys(amdzk_ctx* ctx, Fr* d_cols, size_t ncols, uint32_t n, size_t co
 
 // permute_expression_pair for L lookups: A (sorted inputs, in place), Ts (sorted tables), S out.
 // flags: 4 u32 arrays of flag_stride per lookup: rep | used | rank_rep | rank_left (flag_stride >= u+1).
+// u = 0: no row to sort, mark or assign (a grid of (0, L) is a launch the runtime refuses); A, Ts and S stay as they are.
 int zk_lookup_permute(amdzk_ctx* ctx, Fr* A, Fr* Ts, Fr* S, Fr* left, size_t L, uint32_t n, uint32_t u, uint32_t* flags, size_t flag_stride,
                       int* d_err, size_t tables_presorted) {
-  if (L == 0) return AMDZK_OK;
+  if (L == 0 || u == 0) return AMDZK_OK;
   if (tables_presorted > L) ZK_FAIL(ctx, AMDZK_E_INVALID, "lookup_permute: more presorted tables than lookups");
   uint32_t* rep = flags;
   uint32_t* used = flags + L * flag_stride;

@@ -67,16 +67,20 @@ int zk_permute_expression_pairs(amdzk_ctx* ctx, Fr* A, const Fr* T, Fr* Ts, Fr* 
   Fr* Tr = Ts + presorted * n;
   if (presorted) ZK_TRY(d2d(ctx, Ts, Ts_sorted, presorted * n * 32));
   ZK_TRY(amdzk_fr_to_repr_dev(ctx, A, L * n));
-  ZK_HIP(ctx, hipMemset2DAsync(A + usable, (size_t)n * 32, 0xFF, (size_t)(n - usable) * 32, L, ctx->stream));
+  // rows >= usable of `cols` columns at p, to `byte`; usable == n leaves no such row, and no zero-width memset is issued
+  auto fill_tail = [&](Fr* p, int byte, size_t cols) {
+    return usable < n ? hipMemset2DAsync(p + usable, (size_t)n * 32, byte, (size_t)(n - usable) * 32, cols, ctx->stream) : hipSuccess;
+  };
+  ZK_HIP(ctx, fill_tail(A, 0xFF, L));
   if (rest) {
     ZK_TRY(d2d(ctx, Tr, T + presorted * n, rest * n * 32));
     ZK_TRY(amdzk_fr_to_repr_dev(ctx, Tr, rest * n));
-    ZK_HIP(ctx, hipMemset2DAsync(Tr + usable, (size_t)n * 32, 0xFF, (size_t)(n - usable) * 32, rest, ctx->stream));
+    ZK_HIP(ctx, fill_tail(Tr, 0xFF, rest));
   }
   ZK_HIP(ctx, hipMemsetAsync(d_err, 0, sizeof(int), ctx->stream));
   ZK_TRY(zk_lookup_permute(ctx, A, Ts, S, left, L, n, usable, flags, (size_t)n + 8, d_err, presorted));
-  ZK_HIP(ctx, hipMemset2DAsync(A + usable, (size_t)n * 32, 0, (size_t)(n - usable) * 32, L, ctx->stream));
-  ZK_HIP(ctx, hipMemset2DAsync(S + usable, (size_t)n * 32, 0, (size_t)(n - usable) * 32, L, ctx->stream));
+  ZK_HIP(ctx, fill_tail(A, 0, L));
+  ZK_HIP(ctx, fill_tail(S, 0, L));
   ZK_TRY(amdzk_fr_from_raw_dev(ctx, A, L * n));
   ZK_TRY(amdzk_fr_from_raw_dev(ctx, S, L * n));
   return AMDZK_OK;

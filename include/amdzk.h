@@ -692,7 +692,11 @@ int amdzk_multiopen_plan(const uint64_t* points, size_t n_points, const amdzk_op
 /* lookup::prover::permute_expression_pair [UP] for nlookups pairs of n rows (column l at + l*n, Montgomery form):
  * d_inputs is sorted in place into A', d_permuted_tables_out receives S' (first occurrences aligned, leftovers in
  * ascending order assigned from the last repeated row backwards); rows >= usable come back zero for the caller to
- * blind. AMDZK_E_INVALID "not in table" when an input value is missing from its table. */
+ * blind. Only rows < usable of either column count: an input value that none of its table's rows < usable holds is
+ * refused with AMDZK_E_INVALID "lookup <l> input not in table" (l: one of the failing lookups), the outputs are then
+ * unspecified and the ctx stays usable. n: a power of two >= 2, usable <= n. usable = 0: nothing is permuted, the call
+ * succeeds and both outputs are all zero. usable = n: the permutation of all n rows, no row is zeroed. nlookups = 0
+ * succeeds and touches nothing. d_tables is only read. */
 int amdzk_permute_expression_pair_dev(amdzk_ctx* ctx, void* d_inputs, const void* d_tables,
                                       void* d_permuted_tables_out, size_t nlookups, uint32_t n, uint32_t usable);
 /* evaluation::Evaluator::evaluate_h + divide_by_vanishing_poly + extended_to_coeff + the split into pieces [UP]:
