@@ -217,11 +217,11 @@ static std::atomic<bool> g_blocking_note_given{false};
 
 extern "C" {
 
-int amdzk_version(void) { return 1016; }
+int amdzk_version(void) { return 1017; }
 
 // "amdzk <abi> src=<hash of the comment-stripped kernel sources and the Makefile> arch=gfx950": what this binary was built
 // from. bench.py refuses a library whose stamp is not its tree's bench.kernel_src_hash().
-const char* amdzk_build_info(void) { return "amdzk 1016 src=" AMDZK_SRC_HASH " arch=gfx950"; }
+const char* amdzk_build_info(void) { return "amdzk 1017 src=" AMDZK_SRC_HASH " arch=gfx950"; }
 
 int amdzk_init(int device_id, amdzk_ctx** out) {
   if (!out) return AMDZK_E_INVALID;

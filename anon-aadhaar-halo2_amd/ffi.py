@@ -155,6 +155,12 @@ def lib():
         "amdzk_witness_free": (None, [vp, vp]),
         "amdzk_witness_run": (i32, [vp, vp, sz, C.POINTER(vp), C.POINTER(vp), sz, u32, sz, vp]),
         "amdzk_witness_run_dev": (i32, [vp, vp, sz, vp, sz, C.POINTER(vp), sz, u32, sz, vp]),
+        "amdzk_poseidon_check_desc": (i32, [vp, C.c_char_p, sz]),
+        "amdzk_poseidon_compile": (i32, [vp, vp, C.POINTER(vp)]),
+        "amdzk_poseidon_free": (None, [vp, vp]),
+        "amdzk_poseidon_permute_dev": (i32, [vp, vp, vp, sz, sz]),
+        "amdzk_poseidon_hash": (i32, [vp, vp, C.POINTER(vp), C.POINTER(sz), sz, vp]),
+        "amdzk_poseidon_hash_dev": (i32, [vp, vp, vp, sz, C.POINTER(sz), sz, sz, vp, sz]),
         "amdzk_debug_limb_program": (i32, [vp, sz, vp, sz, C.POINTER(sz), C.POINTER(u32)]),
         "amdzk_pk_h_program": (i32, [vp, vp, sz, C.POINTER(sz)]),
         "amdzk_timer_start": (i32, [vp]),
@@ -300,6 +306,11 @@ class WitnessDesc(C.Structure):  # amdzk_witness_desc
     _fields_ = [("size", C.c_size_t), ("k", C.c_uint32), ("num_advice", C.c_uint32), ("n_inputs", C.c_uint32), ("n_constants", C.c_uint32),
                 ("constants", C.c_void_p), ("n_nodes", C.c_uint32), ("nodes", C.c_void_p), ("n_cells", C.c_uint32), ("cells", C.c_void_p),
                 ("n_publics", C.c_uint32), ("publics", C.c_void_p)]
+
+
+class PoseidonDesc(C.Structure):  # amdzk_poseidon_desc
+    _fields_ = [("size", C.c_size_t), ("t", C.c_uint32), ("rate", C.c_uint32), ("r_f", C.c_uint32), ("r_p", C.c_uint32),
+                ("round_constants", C.c_void_p), ("mds", C.c_void_p), ("initial_state", C.c_void_p)]
 
 
 WNODE = np.dtype([("op", np.uint32), ("a", np.uint32), ("b", np.uint32), ("c", np.uint32)])  # amdzk_wnode

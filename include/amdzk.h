@@ -1130,7 +1130,8 @@ int amdzk_verify_proofs_decide_mixed(amdzk_ctx* ctx, const amdzk_g2* s_g2, const
  * A witness program carries that arithmetic across this boundary as DATA, the way amdzk_circuit carries the constraint
  * system: compiled once per circuit, then run for a whole batch, writing straight into the buffers that
  * amdzk_create_proof_batch (or amdzk_check_witness) reads. What is not field arithmetic — the quotient and remainder of a big
- * product, a native hash — is computed by the host per proof and enters as an input (a "hint").
+ * product, a native hash — is computed by the host per proof and enters as an input (a "hint"; a Poseidon digest can be
+ * written into the resident input table by amdzk_poseidon_hash_dev, below).
  *
  * A program is a list of nodes in SSA order: node i names only nodes < i. A node's value is one Fr per proof of the batch.
  * All ops are total; canon(x) is the canonical integer of x in [0, r). Fields of amdzk_wnode an op does not use are ignored.
@@ -1244,6 +1245,73 @@ int amdzk_witness_run(amdzk_ctx* ctx, amdzk_witness* w, size_t n_proofs, const u
 int amdzk_witness_run_dev(amdzk_ctx* ctx, amdzk_witness* w, size_t n_proofs, const void* d_inputs, size_t input_stride,
                           void* const* d_advice, size_t advice_stride, uint32_t flags, size_t max_scratch_bytes,
                           uint64_t* publics_out);
+
+/* ---- Poseidon over Fr: batched permutations and sponges on the device (ABI 1017).
+ * The reference computes its nullifier natively with the `poseidon` crate (Poseidon::<Fr, 5, 4>::new(8, 57), update over
+ * about 950 elements, squeeze). The spec crosses this boundary as DATA, the way amdzk_circuit does: the library generates no
+ * constants, and what it computes for the constants it is given is stated here in full. The S-box is x^5 only.
+ * Parity unpinned: the semantics below are the pinned crate's update / squeeze as recalled; the crate's source is not in
+ * this tree, and no test compares with it.
+ *
+ * Permutation. For round ρ = 0 .. r_f + r_p − 1:
+ * - `s[i] += rc[ρ][i]` for every i.
+ * - `s[i] = s[i]^5` for every i when ρ < r_f/2 or ρ ≥ r_f/2 + r_p. Otherwise for i = 0 only.
+ * - `s = M·s`, that is `s'[i] = Σ_j M[i][j]·s[j]`.
+ *
+ * Sponge.
+ * - The state starts as `initial_state`.
+ * - Inputs are taken in chunks of `rate`. Chunk element i is added to `s[1 + i]`, then the state is permuted.
+ * - The last chunk is the m = len mod rate left-over elements followed by ONE. That is m + 1 ≤ rate elements; positions
+ *   beyond them get nothing. One more permutation follows, also when m = 0 and when len = 0.
+ * - The output is `s[1]`.
+ * - A sponge of `len` inputs is ⌊len / rate⌋ + 1 permutations.
+ *
+ * Values in memory are halo2curves' Fr: 4 x u64 little-endian, Montgomery with R = 2^256, below r. Results are canonical
+ * (below r) and exact. The textbook round constants and the full MDS matrix are wanted, not the crate's optimised
+ * (sparse-matrix) form of the partial rounds.
+ *
+ * amdzk_poseidon_check_desc: pure host code, callable without a device (like amdzk_witness_plan). Runs every validation of
+ * amdzk_poseidon_compile; msg (may be NULL) receives the refusal's message, truncated to msg_cap.
+ * amdzk_poseidon_compile validates the description, converts the constants once to the form the kernels multiply by (Montgomery
+ * radix 2^261, as the NTT's twiddles), uploads them and keeps no pointer into the caller's arrays. amdzk_poseidon_free releases
+ * the handle (NULL is a no-op). One amdzk_poseidon is used by one call at a time, on the ctx's device it was compiled on.
+ * amdzk_poseidon_permute_dev: n_states states of t Fr, state b at d_states + b * state_stride Fr, permuted in place — the
+ * primitive under any other sponge convention. The (state_stride - t) elements between two states are never written.
+ * amdzk_poseidon_hash: inputs[b] = the lens[b] x 4 words of sponge b on the host (may be NULL when lens[b] = 0); out receives
+ * n x 4 words, digest b at out + 4 b. The host form checks its inputs (< r), stages them and runs the _dev form's code.
+ * amdzk_poseidon_hash_dev: the inputs resident, input a of sponge b at d_inputs + (b * input_stride + a) Fr (d_inputs may be
+ * NULL when every length is 0). lens: a HOST array of n lengths, or NULL for "all `len`" (`len` is ignored otherwise). Digest
+ * b goes to d_out + b * out_stride Fr and nothing else is written: d_out may be an instance buffer or the input table of
+ * amdzk_witness_run_dev. d_out must not overlap the inputs. Precondition: the resident values are below r (as
+ * amdzk_fr_to_repr_dev; they are not checked).
+ * Execution: one sponge (or state) per group of eight adjacent lanes, state element i in lane i, a 256-thread block carries
+ * 32; sponges of different lengths share a launch, a wavefront runs to its longest. The calls run on the ctx's stream and
+ * return with it idle.
+ * Refused with a message that starts "poseidon:", the ctx stays usable and nothing has been written — AMDZK_E_INVALID: null
+ * arguments (initial_state alone may be NULL), a too-small desc->size, t outside 2..8, rate outside 1..t-1, r_f odd or below
+ * 2, a round constant, MDS entry or initial-state element >= r, n = 0, state_stride < t, input_stride below the longest
+ * length, out_stride = 0, a device pointer that is not device memory of this ctx's GPU (amdzk_ptr_check_affinity's test), a
+ * handle compiled on another device, an input >= r in the host form; AMDZK_E_UNSUPPORTED: (r_f + r_p) * t > 1536 (the round
+ * constants of a spec stay in a block's LDS), a length of 2^31 or more, 2^31 or more sponges or states in one call, sizes
+ * whose byte counts overflow size_t. Cut larger calls into runs. */
+typedef struct amdzk_poseidon amdzk_poseidon;
+typedef struct amdzk_poseidon_desc {
+  size_t size;                      /* sizeof(amdzk_poseidon_desc) as compiled by the caller; too small is refused */
+  uint32_t t;                       /* 2 <= t <= 8 */
+  uint32_t rate;                    /* 1 <= rate <= t-1 */
+  uint32_t r_f;                     /* even and >= 2 */
+  uint32_t r_p;                     /* >= 0 */
+  const uint64_t* round_constants;  /* (r_f + r_p) x t Fr, Montgomery, < r */
+  const uint64_t* mds;              /* t x t Fr, row-major, Montgomery, < r */
+  const uint64_t* initial_state;    /* t Fr, or NULL = (2^64, 0, ..., 0) */
+} amdzk_poseidon_desc;
+int amdzk_poseidon_check_desc(const amdzk_poseidon_desc* desc, char* msg, size_t msg_cap);
+int amdzk_poseidon_compile(amdzk_ctx* ctx, const amdzk_poseidon_desc* desc, amdzk_poseidon** out);
+void amdzk_poseidon_free(amdzk_ctx* ctx, amdzk_poseidon* p);
+int amdzk_poseidon_permute_dev(amdzk_ctx* ctx, amdzk_poseidon* p, void* d_states, size_t n_states, size_t state_stride);
+int amdzk_poseidon_hash(amdzk_ctx* ctx, amdzk_poseidon* p, const uint64_t* const* inputs, const size_t* lens, size_t n, uint64_t* out);
+int amdzk_poseidon_hash_dev(amdzk_ctx* ctx, amdzk_poseidon* p, const void* d_inputs, size_t input_stride, const size_t* lens, size_t len,
+                            size_t n, void* d_out, size_t out_stride);
 
 /* Test hooks for the host pass that prepares quotient-domain programs for the limb-resident interpreter (bounds in
  * units of p, placement of the weak reductions, fusion of `t*x` with the accumulate): the pass on caller-supplied words

@@ -1398,6 +1398,86 @@ class CompiledWitness {
   amdzk_witness* h_ = nullptr;
 };
 
+// ------------------------------------------------------------------------------------------ Poseidon
+// The `poseidon` crate's Poseidon<Fr, T, RATE> on the device (amdzk.h "Poseidon over Fr"; parity unpinned): new / update /
+// squeeze for one sponge, hash_many and permute for batches. The spec is DATA: the textbook round constants ((r_f + r_p)
+// rows of t) and the full t x t MDS matrix — the crate's Spec stores the optimised form, so a caller carries its own copy of
+// the generator. initial_state empty = the crate's (2^64, 0, ..., 0).
+struct PoseidonSpec {
+  uint32_t t = 0, rate = 0, r_f = 0, r_p = 0;
+  std::vector<Fr> round_constants, mds, initial_state;
+  amdzk_poseidon_desc desc() const {
+    if (round_constants.size() != (size_t)(r_f + r_p) * t || mds.size() != (size_t)t * t || (!initial_state.empty() && initial_state.size() != t))
+      throw Error(AMDZK_E_INVALID, "poseidon: the spec's arrays do not have (r_f + r_p) * t, t * t and t (or no) elements");
+    amdzk_poseidon_desc d;
+    std::memset(&d, 0, sizeof(d));
+    d.size = sizeof(d);
+    d.t = t;
+    d.rate = rate;
+    d.r_f = r_f;
+    d.r_p = r_p;
+    d.round_constants = round_constants.empty() ? nullptr : round_constants[0].l;
+    d.mds = mds.empty() ? nullptr : mds[0].l;
+    d.initial_state = initial_state.empty() ? nullptr : initial_state[0].l;
+    return d;
+  }
+  // amdzk_poseidon_check_desc: every validation, without a device
+  void check() const {
+    const amdzk_poseidon_desc d = desc();
+    char msg[256] = "";
+    const int rc = amdzk_poseidon_check_desc(&d, msg, sizeof(msg));
+    if (rc != AMDZK_OK) throw Error(rc, msg);
+  }
+};
+
+class Poseidon {
+ public:
+  Poseidon(const Context& ctx, const PoseidonSpec& spec) : ctx_(ctx), t_(spec.t) {
+    const amdzk_poseidon_desc d = spec.desc();
+    ctx_.check(amdzk_poseidon_compile(ctx_.get(), &d, &h_));
+  }
+  ~Poseidon() {
+    if (h_) amdzk_poseidon_free(ctx_.get(), h_);
+  }
+  Poseidon(const Poseidon&) = delete;
+  Poseidon& operator=(const Poseidon&) = delete;
+
+  void update(const std::vector<Fr>& elements) { buf_.insert(buf_.end(), elements.begin(), elements.end()); }
+  // the digest of everything updated so far; the sponge starts afresh
+  Fr squeeze() {
+    const Fr out = hash_many({buf_})[0];
+    buf_.clear();
+    return out;
+  }
+  std::vector<Fr> hash_many(const std::vector<std::vector<Fr>>& inputs) const {
+    std::vector<const uint64_t*> in(inputs.size());
+    std::vector<size_t> lens(inputs.size());
+    for (size_t b = 0; b < inputs.size(); b++) {
+      in[b] = inputs[b].empty() ? nullptr : inputs[b][0].l;
+      lens[b] = inputs[b].size();
+    }
+    std::vector<Fr> out(inputs.size());
+    ctx_.check(amdzk_poseidon_hash(ctx_.get(), h_, in.data(), lens.data(), inputs.size(), out.empty() ? nullptr : out[0].l));
+    return out;
+  }
+  // the inputs resident (amdzk_poseidon_hash_dev): lens empty = every sponge has `len` inputs
+  void hash_many_dev(const void* d_inputs, size_t input_stride, const std::vector<size_t>& lens, size_t len, size_t n, void* d_out, size_t out_stride = 1) const {
+    if (!lens.empty() && lens.size() != n) throw Error(AMDZK_E_INVALID, "poseidon: one length per sponge");
+    ctx_.check(amdzk_poseidon_hash_dev(ctx_.get(), h_, d_inputs, input_stride, lens.empty() ? nullptr : lens.data(), len, n, d_out, out_stride));
+  }
+  // n_states resident states of t elements permuted in place (state_stride 0 = t)
+  void permute_dev(void* d_states, size_t n_states, size_t state_stride = 0) const {
+    ctx_.check(amdzk_poseidon_permute_dev(ctx_.get(), h_, d_states, n_states, state_stride ? state_stride : t_));
+  }
+  amdzk_poseidon* get() const { return h_; }
+
+ private:
+  const Context& ctx_;
+  uint32_t t_;
+  std::vector<Fr> buf_;
+  amdzk_poseidon* h_ = nullptr;
+};
+
 // ------------------------------------------------------------------------------------------ verify_proof up to the pairing
 // plonk::verify_proof [UP] without its last step (amdzk_verify_proofs): what upstream's verifier hands to its strategy as a
 // GuardKZG. Every well-formed proof that went in is valid iff e(lhs, [s]_2) = e(rhs, [1]_2) — ONE pairing check, which stays

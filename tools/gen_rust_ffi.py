@@ -21,13 +21,14 @@ OPAQUE = {"amdzk_ctx": "Ctx", "amdzk_srs": "Srs", "amdzk_domain": "Domain", "amd
           "amdzk_srs_report": "AmdzkSrsReport", "amdzk_transcript_read": "AmdzkTranscriptRead",
           "amdzk_multiopen_verify_opts": "AmdzkMultiopenVerifyOpts", "amdzk_witness": "Witness", "amdzk_wnode": "AmdzkWnode",
           "amdzk_wcell": "AmdzkWcell", "amdzk_witness_desc": "AmdzkWitnessDesc", "amdzk_batch_phase_fn": "AmdzkBatchPhaseFn",
-          "amdzk_batch_proof_opts": "AmdzkBatchProofOpts", "amdzk_verify_item": "AmdzkVerifyItem", "amdzk_verify_mixed_opts": "AmdzkVerifyMixedOpts"}
+          "amdzk_batch_proof_opts": "AmdzkBatchProofOpts", "amdzk_verify_item": "AmdzkVerifyItem", "amdzk_verify_mixed_opts": "AmdzkVerifyMixedOpts",
+          "amdzk_poseidon": "Poseidon", "amdzk_poseidon_desc": "AmdzkPoseidonDesc"}
 # structs and function-pointer types of the header that the block spells out as #[repr(C)] Rust (amdzk_circuit's
 # counterpart is written by hand in INTEGRATION.md, beside the code that fills it)
 GENERATED_TYPES = ("amdzk_phases", "amdzk_transcript", "amdzk_proof_opts", "amdzk_batch_opts", "amdzk_batch_proof_opts", "amdzk_open_query", "amdzk_multiopen_opts",
                    "amdzk_check_failure", "amdzk_check_opts", "amdzk_proof_status", "amdzk_verify_opts", "amdzk_srs_check_opts", "amdzk_srs_report",
                    "amdzk_transcript_read", "amdzk_multiopen_verify_opts", "amdzk_wnode", "amdzk_wcell", "amdzk_witness_desc",
-                   "amdzk_verify_item", "amdzk_verify_mixed_opts")
+                   "amdzk_verify_item", "amdzk_verify_mixed_opts", "amdzk_poseidon_desc")
 SCALAR = {"int": "c_int", "uint32_t": "u32", "int32_t": "i32", "uint64_t": "u64", "size_t": "usize", "uint8_t": "u8", "float": "f32",
           "double": "f64", "char": "c_char", "void": "c_void"}
 
