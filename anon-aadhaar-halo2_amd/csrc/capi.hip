@@ -13,7 +13,14 @@ using namespace bn254;
 
 static thread_local std::string g_init_err;
 
-int zk_ws_reserve(amdzk_ctx* ctx, ZkWs slot, size_t bytes, void** out) {
+int zk_ws_poison_fill(amdzk_ctx* ctx, void* d, size_t bytes) {
+  if (!d || bytes < 4) return AMDZK_OK;
+  ZK_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)d, (int)ZK_WS_POISON_WORD, bytes / 4, ctx->stream));
+  if (ctx->prof) ctx->prof_map["ws_poison"].launches++;
+  return AMDZK_OK;
+}
+
+int zk_ws_reserve(amdzk_ctx* ctx, ZkWs slot, size_t bytes, void** out, bool holds_addresses) {
   amdzk_ctx::Ws& w = ctx->ws[slot];
   if (w.cap < bytes) {
     if (w.p) {
@@ -32,6 +39,8 @@ int zk_ws_reserve(amdzk_ctx* ctx, ZkWs slot, size_t bytes, void** out) {
     w.cap = want;
   }
   *out = w.p;
+  // behind everything already enqueued on the stream, in front of everything the new user enqueues
+  if (ctx->ws_poison && !holds_addresses && slot != ZK_WS_TABLES) ZK_TRY(zk_ws_poison_fill(ctx, w.p, bytes));
   return AMDZK_OK;
 }
 
@@ -45,6 +54,11 @@ int zk_pinned_reserve(amdzk_ctx* ctx, size_t bytes, void** out) {
     ctx->h_pinned_cap = want;
   }
   *out = ctx->h_pinned;
+  if (ctx->ws_poison) {  // host memory: at once. A pointer still read after this reservation reads the pattern.
+    uint32_t* h = (uint32_t*)ctx->h_pinned;
+    for (size_t i = 0; i < bytes / 4; i++) h[i] = ZK_WS_POISON_WORD;
+    if (ctx->prof) ctx->prof_map["ws_poison"].launches++;
+  }
   return AMDZK_OK;
 }
 
@@ -109,6 +123,7 @@ int zk_lane(amdzk_ctx* ctx, int i, amdzk_ctx** out) {
     l->device = ctx->device;
     l->num_cu = ctx->num_cu;
     l->parent = ctx;
+    l->ws_poison = ctx->ws_poison;
     if (zk_stream_create(&l->own_stream, true) != hipSuccess) {
       delete l;
       ZK_FAIL(ctx, AMDZK_E_HIP, "lane %d: hipStreamCreate failed", i);
@@ -246,6 +261,7 @@ int amdzk_init(int device_id, amdzk_ctx** out) {
   }
   c->stream = c->own_stream;
   if (const char* e = getenv("AMDZK_HOST_WAIT")) c->host_wait_block = strcmp(e, "block") == 0;
+  if (const char* e = getenv("AMDZK_WS_POISON")) c->ws_poison = atoi(e) != 0;
   // A host that runs this device with hipDeviceScheduleBlockingSync: the runtime's own waits (hipStreamSynchronize from
   // one driver thread per proof in flight, on streams that share hardware queues) are the path that did not come back in
   // round 3's experiment, so this library then polls on every host wait and never enters them.
@@ -475,7 +491,7 @@ int amdzk_msm_g1_cols_dev(amdzk_ctx* ctx, const amdzk_srs* srs, int basis, const
   for (size_t c = 0; c < ncols; c++)
     if (!d_cols[c]) ZK_FAIL(ctx, AMDZK_E_INVALID, "msm_cols: column %zu is null", c);
   const Fr** d_tab = nullptr;
-  ZK_TRY(zk_ws_reserve(ctx, ZK_WS_STAGING, ncols * sizeof(Fr*), (void**)&d_tab));
+  ZK_TRY(zk_ws_reserve(ctx, ZK_WS_STAGING, ncols * sizeof(Fr*), (void**)&d_tab, true));
   // the caller's array is read before the call returns: every path below waits for the stream
   ZK_HIP(ctx, hipMemcpyAsync(d_tab, d_cols, ncols * sizeof(Fr*), hipMemcpyHostToDevice, ctx->stream));
   G1X* d_res = nullptr;

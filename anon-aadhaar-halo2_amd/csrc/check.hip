@@ -373,6 +373,7 @@ static int check_witness_run(amdzk_ctx* ctx, amdzk_pk* pk, const uint64_t* const
   const CheckCounters counters = {ck.d_count, ck.d_first};
   *n_failures = 0;
   if (!ncon) return AMDZK_OK;
+  ZK_TRY(zk_pk_poison(ctx, pk));
   ZK_HIP(ctx, hipMemsetAsync(ck.d_count, 0, (size_t)ncon * 8, ctx->stream));
   ZK_HIP(ctx, hipMemsetAsync(ck.d_first, 0xFF, (size_t)ncon * 4, ctx->stream));
   // the witness into the workspace as create_proof copies it, unblinded: instance columns zero behind the caller's values

@@ -67,6 +67,9 @@ struct amdzk_ctx {
   // pinned host staging for small results (workspace.hpp: dead after any call that may reserve it again)
   void* h_pinned = nullptr;
   size_t h_pinned_cap = 0;
+  // AMDZK_WS_POISON (read once by amdzk_init; lanes follow their parent): every reservation of scratch is filled with
+  // ZK_WS_POISON_WORD before its user gets it (workspace.hpp, WHAT CHECKS THE RULES). A test aid; off, it costs this branch.
+  bool ws_poison = false;
 
   // How the host waits for the device (zk_host_wait): spinning in hipStreamSynchronize — lowest latency, one busy core
   // per waiting thread — or POLLING a completion event (hipEventQuery, a few microseconds of yielding, then 50-us
@@ -187,8 +190,12 @@ constexpr int AMDZK_NUM_BASES = 3;
 // every maker of a proving key with permutation columns calls this. Safe from several threads (one guard in the SRS).
 int zk_srs_ensure_prefix(amdzk_ctx* ctx, const amdzk_srs* srs);
 
-int zk_ws_reserve(amdzk_ctx* ctx, ZkWs slot, size_t bytes, void** out);
+// holds_addresses: a kernel dereferences the region's content as device addresses, so it is never poisoned (workspace.hpp)
+int zk_ws_reserve(amdzk_ctx* ctx, ZkWs slot, size_t bytes, void** out, bool holds_addresses = false);
 int zk_pinned_reserve(amdzk_ctx* ctx, size_t bytes, void** out);
+// The poison fill itself (capi.hip): ZK_WS_POISON_WORD into every 32-bit word of [d, d + bytes) on ctx's stream, counted
+// as "ws_poison" in the profile map while profiling is on. Callers ask ctx->ws_poison first.
+int zk_ws_poison_fill(amdzk_ctx* ctx, void* d, size_t bytes);
 int zk_ptr_on_device(amdzk_ctx* ctx, const void* p, const char* what);
 hipEvent_t zk_evt_get(amdzk_ctx* ctx);
 // Lane i of ctx (created on first use). While per-kernel profiling is on, a lane IS the ctx: one stream, so that the

@@ -21,6 +21,12 @@ int h2d(amdzk_ctx* ctx, void* d, const void* h, size_t bytes) {
 }
 // host -> device through the key's pinned staging area: the source may be a temporary, and the copy
 // is truly asynchronous (no pageable-memory staging inside the runtime).
+// AMDZK_WS_POISON: the staging ring where its bump pointer goes back to 0 — host memory, filled at once (workspace.hpp): a copy
+// still reading the ring would now read the pattern. Counted like every fill.
+static void pin_poison(amdzk_ctx* ctx, amdzk_pk* pk) {
+  for (size_t i = 0; i < pk->pin_cap / 4; i++) ((uint32_t*)pk->pin)[i] = ZK_WS_POISON_WORD;
+  if (ctx->prof) ctx->prof_map["ws_poison"].launches++;
+}
 int h2d_staged(amdzk_ctx* ctx, amdzk_pk* pk, void* d, const void* h, size_t bytes) {
   if (!bytes) return AMDZK_OK;
   if (!pk->pin || bytes > pk->pin_cap) return h2d(ctx, d, h, bytes);
@@ -28,6 +34,7 @@ int h2d_staged(amdzk_ctx* ctx, amdzk_pk* pk, void* d, const void* h, size_t byte
   if (off + bytes > pk->pin_cap) {  // wrap: every stream that may still be reading the staging area must be done with it
     ZK_TRY(zk_sync_all(ctx));
     off = 0;
+    if (ctx->ws_poison) pin_poison(ctx, pk);
   }
   memcpy(pk->pin + off, h, bytes);
   pk->pin_off = off + bytes;
@@ -64,32 +71,38 @@ static int alloc_proof_workspace(amdzk_ctx* ctx, amdzk_pk* pk) {
   const KeyMaterial& K = *pk->key;
   const size_t n = K.n, ext = K.ext;
   const uint32_t L = K.L, ns = K.nsets;
-  ZK_TRY(dalloc(ctx, pk, &pk->P, K.NP * n));
-  ZK_TRY(dalloc(ctx, pk, &pk->PQ, K.NP * n));
-  ZK_TRY(dalloc(ctx, pk, &pk->PC, K.NP * ext));
-  ZK_TRY(dalloc(ctx, pk, &pk->ci, (size_t)L * n));
-  ZK_TRY(dalloc(ctx, pk, &pk->ct, (size_t)L * n));
-  ZK_TRY(dalloc(ctx, pk, &pk->lk_ts, (size_t)L * n));
-  ZK_TRY(dalloc(ctx, pk, &pk->lk_left, (size_t)L * n));
-  ZK_TRY(dalloc(ctx, pk, &pk->lk_flags, (size_t)4 * L * (n + 8)));
-  ZK_TRY(dalloc(ctx, pk, &pk->d_err, 1));
-  ZK_TRY(dalloc(ctx, pk, &pk->rnd, n));
-  ZK_TRY(dalloc(ctx, pk, &pk->hq, (size_t)H_PARTS_MAX * ext));  // one h per piece of the cut h(X) program (finalize_limb_program)
-  ZK_TRY(dalloc(ctx, pk, &pk->hpieces, (size_t)K.qdeg * n));
-  ZK_TRY(dalloc(ctx, pk, &pk->hpoly, n));
+  // a device buffer of the workspace whose content no kernel takes for an address: allocated, and listed for zk_pk_poison
+  auto arena = [&](auto** p, size_t count) {
+    ZK_TRY(dalloc(ctx, pk, p, count));
+    pk->arenas.push_back({(void*)*p, (count ? count : 1) * sizeof(**p)});
+    return (int)AMDZK_OK;
+  };
+  ZK_TRY(arena(&pk->P, K.NP * n));
+  ZK_TRY(arena(&pk->PQ, K.NP * n));
+  ZK_TRY(arena(&pk->PC, K.NP * ext));
+  ZK_TRY(arena(&pk->ci, (size_t)L * n));
+  ZK_TRY(arena(&pk->ct, (size_t)L * n));
+  ZK_TRY(arena(&pk->lk_ts, (size_t)L * n));
+  ZK_TRY(arena(&pk->lk_left, (size_t)L * n));
+  ZK_TRY(arena(&pk->lk_flags, (size_t)4 * L * (n + 8)));
+  ZK_TRY(arena(&pk->d_err, 1));
+  ZK_TRY(arena(&pk->rnd, n));
+  ZK_TRY(arena(&pk->hq, (size_t)H_PARTS_MAX * ext));  // one h per piece of the cut h(X) program (finalize_limb_program)
+  ZK_TRY(arena(&pk->hpieces, (size_t)K.qdeg * n));
+  ZK_TRY(arena(&pk->hpoly, n));
   const size_t nfrac = std::max<size_t>(std::max<size_t>(ns, L), 1);
-  ZK_TRY(dalloc(ctx, pk, &pk->frac, nfrac * n));
-  ZK_TRY(dalloc(ctx, pk, &pk->scratch, std::max(nfrac * n, ext)));
-  ZK_TRY(dalloc(ctx, pk, &pk->scan_tmp, zk_scan_totals_elems(n, nfrac) + 2 * nfrac + 8));
-  ZK_TRY(dalloc(ctx, pk, &pk->frac2, std::max<size_t>(L, 1) * n));
-  ZK_TRY(dalloc(ctx, pk, &pk->scratch2, std::max<size_t>(L, 1) * n));
-  ZK_TRY(dalloc(ctx, pk, &pk->scan_tmp2, zk_scan_totals_elems(n, std::max<size_t>(L, 1)) + 2 * std::max<size_t>(L, 1) + 8));
+  ZK_TRY(arena(&pk->frac, nfrac * n));
+  ZK_TRY(arena(&pk->scratch, std::max(nfrac * n, ext)));
+  ZK_TRY(arena(&pk->scan_tmp, zk_scan_totals_elems(n, nfrac) + 2 * nfrac + 8));
+  ZK_TRY(arena(&pk->frac2, std::max<size_t>(L, 1) * n));
+  ZK_TRY(arena(&pk->scratch2, std::max<size_t>(L, 1) * n));
+  ZK_TRY(arena(&pk->scan_tmp2, zk_scan_totals_elems(n, std::max<size_t>(L, 1)) + 2 * std::max<size_t>(L, 1) + 8));
   const size_t max_rsets = K.max_sets;
-  ZK_TRY(dalloc(ctx, pk, &pk->sets_L, max_rsets * n));
-  ZK_TRY(dalloc(ctx, pk, &pk->sets_N, max_rsets * n));
-  ZK_TRY(dalloc(ctx, pk, &pk->hx, n));
+  ZK_TRY(arena(&pk->sets_L, max_rsets * n));
+  ZK_TRY(arena(&pk->sets_N, max_rsets * n));
+  ZK_TRY(arena(&pk->hx, n));
   pk->small_cap = std::max<size_t>((size_t)K.NP * (K.bf + 2) + 4096, 8192);
-  for (int l = 0; l < 3; l++) ZK_TRY(dalloc(ctx, pk, &pk->small_l[l], pk->small_cap));
+  for (int l = 0; l < 3; l++) ZK_TRY(arena(&pk->small_l[l], pk->small_cap));
   pk->small = pk->small_l[0];
   pk->pin_cap = std::max<size_t>((size_t)8 << 20, 2 * n * 32);
   if (hipHostMalloc((void**)&pk->pin, pk->pin_cap + 64, hipHostMallocDefault) != hipSuccess) {
@@ -106,6 +119,28 @@ static int alloc_proof_workspace(amdzk_ctx* ctx, amdzk_pk* pk) {
   }
   pk->ptrs = pk->ptrs_l[0];
 
+  return AMDZK_OK;
+}
+
+// AMDZK_WS_POISON: every arena of the handle's per-proof workspace filled with the pattern, at the start of a call that
+// uses it (create_proof*, the lock-step batch, amdzk_check_witness). Not the pointer-table slices ptrs_l, which kernels
+// dereference, nor what a handle keeps from call to call (constant table, column tables, programs, the check's counters) —
+// among it the first lk_const columns of ct: the compressed constant lookup tables, written once by build_constant_tables or
+// copied by a clone, which the per-proof compression program skips.
+// A proof's lanes write the arenas from their own streams: the last call's lanes are waited for in front of the fill and
+// the fill is waited for behind it, so that the pattern is in place before any lane starts and over nothing still in use.
+int zk_pk_poison(amdzk_ctx* ctx, amdzk_pk* pk) {
+  if (!ctx->ws_poison) return AMDZK_OK;
+  ZK_TRY(zk_sync_all(ctx));
+  if (pk->pin) {  // every stream is idle: the staging ring starts over (pk.hpp), and is filled where it does
+    pk->pin_off = 0;
+    pin_poison(ctx, pk);
+  }
+  for (auto& a : pk->arenas) {
+    const size_t keep = a.first == (void*)pk->ct ? (size_t)pk->key->lk_const * pk->key->n * sizeof(Fr) : 0;
+    if (a.second > keep) ZK_TRY(zk_ws_poison_fill(ctx, (char*)a.first + keep, a.second - keep));
+  }
+  ZK_HIP(ctx, zk_host_wait(ctx, ctx->stream));
   return AMDZK_OK;
 }
 

@@ -254,6 +254,9 @@ struct amdzk_pk {
   char* pin = nullptr;
   size_t pin_cap = 0, pin_off = 0;
   std::vector<void*> allocs;  // what this handle allocated on the device
+  // ... of which the per-proof arenas (address, bytes): what zk_pk_poison fills (alloc_proof_workspace lists them; ptrs_l,
+  // which holds device addresses, is not among them)
+  std::vector<std::pair<void*, size_t>> arenas;
 
   Fr* adv() const { return P; }
   Fr* inst() const { return P + (size_t)key->A * key->n; }
@@ -286,6 +289,8 @@ int h2d(amdzk_ctx* ctx, void* d, const void* h, size_t bytes);
 int h2d_staged(amdzk_ctx* ctx, amdzk_pk* pk, void* d, const void* h, size_t bytes);
 int d2h(amdzk_ctx* ctx, void* h, const void* d, size_t bytes);
 int d2d(amdzk_ctx* ctx, void* dst, const void* src, size_t bytes);
+// AMDZK_WS_POISON (workspace.hpp): the handle's arenas filled with the pattern; a branch on ctx->ws_poison otherwise (keygen.hip)
+int zk_pk_poison(amdzk_ctx* ctx, amdzk_pk* pk);
 // MSM of ncols resident columns of the key's n rows -> affine points on the host (prover.hip)
 int commit_cols(amdzk_ctx* ctx, const KeyMaterial& K, int basis, const Fr* d_cols, size_t ncols, std::vector<G1Affine>& out);
 

@@ -197,6 +197,7 @@ int pos_hash_launch(amdzk_ctx* ctx, amdzk_poseidon* p, const Fr* d_in, size_t in
   std::vector<uint32_t> l32;
   if (lens) {
     ZK_TRY(pos_grow(ctx, (void**)&p->d_lens, &p->lens_cap, n * sizeof(uint32_t)));
+    if (ctx->ws_poison) ZK_TRY(zk_ws_poison_fill(ctx, p->d_lens, n * sizeof(uint32_t)));  // AMDZK_WS_POISON (workspace.hpp)
     l32.assign(lens, lens + n);
     ZK_HIP(ctx, hipMemcpyAsync(p->d_lens, l32.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     d_lens = p->d_lens;
@@ -300,6 +301,10 @@ extern "C" int amdzk_poseidon_hash(amdzk_ctx* ctx, amdzk_poseidon* p, const uint
   if (stride > SIZE_MAX / sizeof(Fr) / n) ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "poseidon: %zu sponges of up to %zu inputs do not fit size_t", n, longest);
   ZK_TRY(pos_grow(ctx, (void**)&p->d_in, &p->in_cap, n * stride * sizeof(Fr)));
   ZK_TRY(pos_grow(ctx, (void**)&p->d_out, &p->out_cap, n * sizeof(Fr)));
+  if (ctx->ws_poison) {  // AMDZK_WS_POISON (workspace.hpp): the staged inputs keep the last call's values between the sponges' ends and the stride
+    ZK_TRY(zk_ws_poison_fill(ctx, p->d_in, n * stride * sizeof(Fr)));
+    ZK_TRY(zk_ws_poison_fill(ctx, p->d_out, n * sizeof(Fr)));
+  }
   int rc = [&]() -> int {
     for (size_t b = 0; b < n; b++)
       if (lens[b]) ZK_HIP(ctx, hipMemcpyAsync(p->d_in + b * stride, inputs[b], lens[b] * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));

@@ -343,7 +343,11 @@ int build_multiopen(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, amdzk_pk::M
     ZK_FAIL(ctx, AMDZK_E_UNSUPPORTED, "create_proof: more than %u rotation sets", K.max_sets);
   }
   if (std::max<size_t>(pairs, 1) > pk->sets_Q_pairs) {
+    const void* outgrown = pk->sets_Q;  // (stays allocated until the handle goes; no longer an arena)
     ZK_TRY(dalloc(ctx, pk, &pk->sets_Q, std::max<size_t>(pairs, 1) * n));
+    pk->arenas.erase(std::remove_if(pk->arenas.begin(), pk->arenas.end(), [&](const std::pair<void*, size_t>& a) { return outgrown && a.first == outgrown; }),
+                     pk->arenas.end());
+    pk->arenas.push_back({(void*)pk->sets_Q, std::max<size_t>(pairs, 1) * n * sizeof(Fr)});
     pk->sets_Q_pairs = std::max<size_t>(pairs, 1);
   }
   mo.built = true;
@@ -1111,6 +1115,7 @@ int create_proof_body(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t NC, const uin
   if (ex.transcript && (!ex.transcript->common_point || !ex.transcript->common_scalar || !ex.transcript->write_point ||
                         !ex.transcript->write_scalar || !ex.transcript->squeeze_challenge))
     ZK_FAIL(ctx, AMDZK_E_INVALID, "create_proof: amdzk_transcript has a null member");
+  for (size_t c = 0; c < NC; c++) ZK_TRY(zk_pk_poison(ctx, pks[c]));
   amdzk_ctx *B = ctx, *C = ctx;  // the lanes (Prover)
   if (K.use_lanes && NC == 1) {  // several instances: one stream (each lane holds one commitment batch's result at a time)
     ZK_TRY(zk_lane(ctx, 0, &B));
@@ -1218,7 +1223,8 @@ struct Gang {
     if (r != AMDZK_OK) fail(m, r);
   }
   // device scratch of the gang's own (pointer tables, evaluation points and results). Valid until the next call (the slot may grow).
-  int scratch(size_t bytes, char** out) { return zk_ws_reserve(ctx, ZK_WS_STAGING, bytes, (void**)out); }
+  // The kernels dereference the tables: never poisoned (workspace.hpp).
+  int scratch(size_t bytes, char** out) { return zk_ws_reserve(ctx, ZK_WS_STAGING, bytes, (void**)out, true); }
 
   // The commitment batches the live members left in their sinks, as ONE submission per basis (a step has one basis; the products' step
   // two: the lookup products over g_lagrange, the permutation products' differences over its prefix sums), then
@@ -1445,6 +1451,8 @@ static int prove_gang(amdzk_ctx* ctx, amdzk_pk* const* pks, size_t n_proofs, con
                       const amdzk_batch_proof_opts& o, uint8_t* proofs_out, size_t proof_stride, size_t* proof_lens, int* statuses) {
   const bool use_gwc = (o.transcript_kind & AMDZK_MULTIOPEN_GWC) != 0;
   const int kind = o.transcript_kind & ~AMDZK_MULTIOPEN_GWC;
+  // (every member owns its arenas from here to the end of the batch: poisoned once, in front of the first step)
+  for (size_t b = 0; b < n_proofs; b++) ZK_TRY(zk_pk_poison(ctx, pks[b]));
   Gang g(ctx);
   g.phase_fn = o.phase_fn;
   g.phase_user = o.phase_user;

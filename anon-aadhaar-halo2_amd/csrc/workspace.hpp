@@ -19,10 +19,44 @@
 //    is dead after ANY call that may reserve it again. Its users are zk_msm_finish (msm.hip), verify_core
 //    (verify.hip), which has read everything it brought down before its first zk_msm_finish, and zk_pairing_products (pairing.hip),
 //    which calls nothing between its reservation and its last read.
-// The enum says for every shared slot which case holds and where. Nothing checks this at run time: a new driver picks its
-// slot by reading this file.
+//  * A reservation promises the MEMORY, never its contents: a user that reserves a slot twice within one operation keeps
+//    its first pointer (while nothing can have grown the slot) or writes everything again. What an earlier reservation
+//    left is not there to be read, by the same user or another.
+// The enum says for every shared slot which case holds and where.
+//
+// WHAT CHECKS THE RULES. AMDZK_WS_POISON=1, read once by amdzk_init (lanes follow their parent), fills scratch with the
+// 32-bit word ZK_WS_POISON_WORD at the moment it is handed out:
+//  * zk_ws_reserve fills the `bytes` it was asked for, on the context's stream: behind everything already enqueued, in
+//    front of everything the new user enqueues. Correct code under (S) or (N) never sees it; an outer user that reads
+//    its region after an inner reservation, a region read before it is written, or a call that counts on what the last
+//    call left, reads the pattern and computes a wrong answer that a test against the reference sees;
+//  * zk_pinned_reserve, and a proving key's staging ring when its bump pointer goes back to 0, fill the host memory at
+//    once: a host pointer still read after a new reservation is caught too;
+//  * zk_pk_poison (keygen.hip) fills the per-proof arenas of a key handle at the start of create_proof*, of the lock-step
+//    batch and of amdzk_check_witness, and starts the handle's staging ring over; witness.hip and poseidon.hip fill their
+//    handles' private buffers at the start of every run and every hash call.
+//    THE LIMIT OF THE BATCH PATH: the lock-step batch fills every member's arenas once, in front of its first step, not
+//    step by step. A step that reads what an EARLIER STEP OF THE SAME BATCH left in an arena is therefore not caught there;
+//    the steps are the solo prover's (prove_steps), and it is caught through amdzk_create_proof* only as far as the solo
+//    call shows the same dependence. What the batch path does catch: anything left by the call before.
+// The word is 5 in every 32-bit word because a wrong read must give a wrong ANSWER, not a fault: as eight limbs it is a
+// canonical non-zero Fr and Fq (top limb 5 < 0x30644e72), as an index, offset, count or loop bound it is small, as a
+// flag it is set, as a point it is not on the curve. (0xFF bytes would be 4 billion as an index.)
+// NOT POISONED, because no value is harmless as an address — regions whose content a kernel dereferences:
+//    ZK_WS_TABLES (the whole slot); the reservations of ZK_WS_STAGING made with holds_addresses = true (the lock-step
+//    batch's tables, Gang::scratch, and amdzk_msm_g1_cols_dev's column table); amdzk_pk::ptrs_l; amdzk_witness::d_ptrs.
+//    A new reservation whose content is dereferenced passes holds_addresses = true to zk_ws_reserve.
+// Nor is what a handle keeps from call to call scratch: of a key handle's arenas the first lk_const columns of ct hold the
+// compressed constant lookup tables, written once at keygen (zk_pk_poison, keygen.hip, leaves them).
+// With profiling on (amdzk_prof_enable) every fill counts as a launch of "ws_poison" in the profile map.
+// A NEW DRIVER picks its slot by reading this file and is then run under the switch: tests/test_gpu_scratch_poison.py on
+// a poisoned context of its own, or the whole suite with AMDZK_WS_POISON=1 in the environment (profiles/ws_poison_suite.txt).
+// Every result must still equal the reference exactly. Off, the switch costs one host branch per reservation.
 #pragma once
 #include <stddef.h>
+#include <stdint.h>
+
+constexpr uint32_t ZK_WS_POISON_WORD = 5;
 
 enum ZkWs : int {
   // ntt.hip, zk_ntt_ex: the ping-pong buffer of a multi-pass transform. One user.
